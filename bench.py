@@ -26,6 +26,10 @@ pair kernel + candidate stage (k_pm_build / k_pm_cand read the k-mer-word stream
 `--workload related` is the shape a kmer-db prefilter leaves (BASELINE configs[4]): genomes in families of `--fam`, every row
 holds the same-family queries only (filtered CSR rows, all pairs related at <= `--dmax` divergence); a step = `--slab` rows.  `cpu_baseline` times the reference's own CParser (oracle/_ref, kind "reference"; the C
 restatement as kind "port" if that is absent) on a strided sample of the same workload, rank 0, N = 1 only.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed -- the int32[3] records (nt_match,
+nt_mismatch, num_alns) of its pairs, as the caller of lzani_run_rows_device receives them -- to DIR/*.npy (see
+dump_outputs).  The workload is seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +49,7 @@ import shard as SH  # noqa: E402
 import synth_genomes as SG  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s measured copy)
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: all files together; beyond it a fixed, seeded sample of the pairs
 
 
 def pair_bytes(lens, params):
@@ -124,6 +129,37 @@ def cpu_baseline(seqs, params, sample_ids):
                        f"self-scheduling over reference rows as in do_matching); code = {what}"), res
 
 
+def dump_outputs(out_dir, res, ref_ids, query_ids=None):
+    """--dump-outputs: the records of the last timed step (reordered genome ids throughout).
+
+    Dense rows (query_ids None): results.npy [rows, n-1, 3], row i = reference ref_ids[i] against query j (j < ref) or
+    j + 1 (j >= ref), the ABI's dense row layout; ref_ids.npy [rows].  Filtered rows: results.npy [pairs, 3] with
+    ref_ids.npy / query_ids.npy [pairs].  float32 while every value is exact in it, else float64.  If that comes to more
+    than DUMP_LIMIT_BYTES, a fixed sample of the pairs (seed 0, in pair order) is written instead: results.npy [k, 3],
+    ref_ids.npy / query_ids.npy [k] and their flat pair indexes sample_index.npy [k]."""
+    os.makedirs(out_dir, exist_ok=True)
+    res = np.asarray(res)
+    rdt = np.float32 if int(res.max(initial=0)) < (1 << 24) else np.float64
+    rsz = np.dtype(rdt).itemsize
+    out = {"results": res, "ref_ids": np.asarray(ref_ids)}
+    if query_ids is not None:
+        out["query_ids"] = np.asarray(query_ids)
+    if res.size * rsz + sum(a.size for k, a in out.items() if k != "results") * 8 > DUMP_LIMIT_BYTES:
+        flat = res.reshape(-1, 3)
+        k = min(len(flat), (DUMP_LIMIT_BYTES - 4096) // (3 * rsz + 3 * 8))
+        idx = np.sort(np.random.default_rng(0).choice(len(flat), size=k, replace=False))
+        if query_ids is None:
+            cols = res.shape[1]
+            r = np.asarray(ref_ids, dtype=np.int64)[idx // cols]
+            j = idx % cols
+            out = {"results": flat[idx], "ref_ids": r, "query_ids": j + (j >= r)}
+        else:
+            out = {"results": flat[idx], "ref_ids": out["ref_ids"][idx], "query_ids": out["query_ids"][idx]}
+        out["sample_index"] = idx
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=rdt if name == "results" else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -151,7 +187,11 @@ def main():
                          "where RCCL refuses to run")
     ap.add_argument("--device", type=int, default=-1, help="force the HIP device ordinal")
     ap.add_argument("--no-check", action="store_true", help="skip the oracle check of the last slab (diagnostic builds that skip work on purpose)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the result records of the last timed step to DIR/*.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -293,6 +333,19 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.collective == "torch" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        if related:
+            rr, ro, rq = csr
+            dump_outputs(args.dump_outputs, shard.cpu().numpy()[:int(ro[-1]) * 3].reshape(-1, 3),
+                         np.repeat(rr, np.diff(ro.astype(np.int64))), rq)
+        elif world == 1:
+            dump_outputs(args.dump_outputs, shard.cpu().numpy()[:len(mine) * (n - 1) * 3].reshape(len(mine), n - 1, 3), mine)
+        else:
+            g = gathered.cpu().numpy().reshape(world, rows_max, n - 1, 3)
+            ids = [SH.rank_rows(rows, k, world) for k in range(world)]
+            order = np.argsort(np.concatenate(ids), kind="stable")
+            dump_outputs(args.dump_outputs, np.concatenate([g[k, :len(ids[k])] for k in range(world)])[order],
+                         np.concatenate(ids)[order])
     # per-rank split of the timed region (so that a scaling curve can be read the moment a node exists): host wall of the
     # blocking compute call, device time of the pair kernel and of the stages that do not shrink with the rank's share
     # of rows, host wall of the gather

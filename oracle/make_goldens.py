@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/ref_vectors.json with the reference's own CParser (oracle/_ref).
+"""Generate tests/golden/ref_vectors.json and tests/golden/ref_live_vectors.json with the reference build (oracle/_ref).
 
 TEST INFRASTRUCTURE ONLY.  Run in the build container (needs /root/reference to build
-oracle/_ref):   make -C oracle ref && python oracle/make_goldens.py
+oracle/_ref):   make -C oracle ref && python oracle/make_goldens.py [--live-only]
 Every vector is (inputs named by fixture/seed, expected int triples); no reference code is stored.
 """
 import json
@@ -23,8 +23,40 @@ EXTRA = {"mrd0": dict(mrd=0), "ar1": dict(ar=1), "aw64_am20": dict(aw=64, am=20)
          "mqd64_mrd64": dict(mqd=64, mrd=64), "mqd0": dict(mqd=0), "reg1": dict(reg=1), "am0": dict(am=0)}
 
 
+def live_vectors():
+    """The reference build's answers to the CPU tests that otherwise need it live: the oracle comparison on U.live_set,
+    the --out-format expansions, and (as a digest) the number formatting of U.format_real_cases."""
+    import hashlib
+    seqs = U.live_set()
+    out = {"generator": "oracle/make_goldens.py", "source": "the reference build of oracle/_ref (CParser, CParams, refresh::real_to_pchar)",
+           "all2all": {name: dict(params=prm or {}, res=O.ref_all2all(seqs, prm, threads=8).tolist()) for name, prm in U.LIVE_PARAMS.items()},
+           "out_format": {fmt: O.ref_expand_output_format(fmt) for fmt in U.OUT_FORMATS + ("tani,bogus",)}}
+    cases = U.format_real_cases()
+    digest = hashlib.sha256()
+    for v, prec in cases:
+        digest.update(O.ref_format_real(v, prec).encode() + b"\n")
+    out["format_real"] = {"count": len(cases), "sha256": digest.hexdigest(),
+                          "digest_of": "sha256 of the formatted strings of U.format_real_cases(), each followed by a newline"}
+    # the INTEGRATION.md stub that `make -C oracle ref` compiled against the reference's own headers
+    import integration_stub as IS
+    stub = IS.stub_source(os.path.join(ROOT, "INTEGRATION.md"))
+    with open(os.path.join(HERE, "_ref", "integration_stub.cpp")) as f:
+        assert f.read() == stub, "oracle/_ref/integration_stub.o is stale: make -C oracle ref"
+    assert os.path.exists(os.path.join(HERE, "_ref", "integration_stub.o"))
+    out["integration_stub"] = {"sha256": hashlib.sha256(stub.encode()).hexdigest(),
+                               "digest_of": "INTEGRATION.md section 1 as oracle/integration_stub.py writes it, compiled against the "
+                                            "reference's headers into oracle/_ref/integration_stub.o"}
+    path = os.path.join(ROOT, "tests", "golden", "ref_live_vectors.json")
+    with open(path, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 def main():
     assert O.lib_ref() is not None, "build oracle/_ref first (make -C oracle ref)"
+    live_vectors()
+    if "--live-only" in sys.argv[1:]:
+        return
     out = {"generator": "oracle/make_goldens.py", "source": "CParser of /root/reference (LZ-ANI 1.2.3) via oracle/ref_driver.cpp",
            "layout": "res[r][q] = [sym_in_matches, sym_in_literals, no_components] of parse(query=q, ref=r); diagonal zero",
            "sets": {}}

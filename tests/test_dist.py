@@ -200,6 +200,41 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     assert all(len(d["per_rank_ms_per_step"][k]["by_rank"]) == 2 for k in ("compute_ms", "kernel_ms", "fixed_ms", "gather_ms"))
 
 
+@pytest.mark.gpu
+def test_bench_dump_outputs_one_rank_and_two_ranks(tmp_path):
+    """bench.py --dump-outputs: --steps timed steps, ms_per_step in the line, and the records of the last timed step --
+    the same 100 rows whether one rank runs them or two ranks share them (gloo rehearsal on GPU 0) -- equal to the
+    oracle on a sample of pairs."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--steps", "2", "--warmup", "1", "--genomes", "300", "--seed", "9", "--lmin", "3000", "--lmax", "5000", "--cpu-sample", "0"]
+    one, two = str(tmp_path / "one"), str(tmp_path / "two")
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--slab", "100", "--dump-outputs", one] + common,
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([ln for ln in p.stdout.split("\n") if ln.startswith("{")][0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["config"]["pairs_timed"] == 2 * 100 * 299
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--slab", "50", "--collective", "gloo",
+           "--device", "0", "--dump-outputs", two] + common
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    res, ids = np.load(os.path.join(one, "results.npy")), np.load(os.path.join(one, "ref_ids.npy"))
+    assert res.dtype == np.float32 and res.shape == (100, 299, 3) and ids.tolist() == list(range(200, 300))   # timed steps 1, 2 of 3 slabs a pass
+    assert np.array_equal(res, np.load(os.path.join(two, "results.npy")))
+    assert np.array_equal(ids, np.load(os.path.join(two, "ref_ids.npy")))
+    names, seqs = SG.make_set(300, 9, lmin=3000, lmax=5000)
+    order = sorted(range(300), key=lambda i: (-len(seqs[i]), names[i]))
+    seqs = [seqs[i] for i in order]
+    for k in range(40):
+        i, j = (k * 37) % 100, (k * 7919) % 299
+        r = int(ids[i])
+        q = j if j < r else j + 1
+        assert tuple(int(x) for x in res[i, j]) == O.oracle_pair(seqs[r], seqs[q]), (r, q)
+
+
 def test_group_gather_plan_against_python_statement():
     """The shard bookkeeping of lzani_group_run_rows (lzani_plan_gather, a pure host function of the C-ABI) against
     a Python statement of the same rule, for ragged rows with empty rows, empty shards and more shards than rows:

@@ -157,10 +157,10 @@ def test_ingest_quirks(tmp_path):
 
 def test_number_formatting_against_reference_and_restatement():
     """The emitter's real_to_chars (lz-ani_amd/host/emit.h) against the Python restatement used by the golden
-    rebuilds and, where oracle/_ref exists, against the reference's own refresh::real_to_pchar."""
+    rebuilds and against the reference's own refresh::real_to_pchar: a digest of its answers stored in
+    tests/golden/ref_live_vectors.json, and case by case where oracle/_ref exists."""
     import ctypes as C
-    import random
-    import struct
+    import hashlib
     d = os.path.join(U.ROOT, "tests", "model")
     so = os.path.join(d, "libemit_shim.so")
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", os.path.join(d, "emit_shim.cpp"), "-o", so, "-lz"])
@@ -168,42 +168,36 @@ def test_number_formatting_against_reference_and_restatement():
     lib.host_format_real.argtypes = [C.c_double, C.c_int, C.c_char_p]
     buf = C.create_string_buffer(64)
     have_ref = O.lib_ref() is not None and hasattr(O.lib_ref(), "ref_format_real")
-    rnd = random.Random(3)
-    vals = [0.0, 1.0, 0.5, 1e-7, 4e-7, 0.000364, 0.98725, 0.999999, 0.9999995, 0.99999949, 9.9999995, 123456.5,
-            1234567.0, 1e21, 1e22, 5e-324, 1.7976931348623157e308]
-    for _ in range(20000):
-        k = rnd.random()
-        if k < 0.5:
-            v = rnd.randint(0, 10 ** rnd.randint(1, 7)) / rnd.randint(1, 10 ** rnd.randint(1, 7))
-        elif k < 0.7:
-            v = 100.0 * rnd.randint(0, 50000) / rnd.randint(1, 50000)
-        elif k < 0.9:
-            v = rnd.random() * 10 ** rnd.randint(-12, 12)
-        else:
-            v = struct.unpack("d", struct.pack("Q", rnd.getrandbits(62)))[0]
-        if v == v and v != float("inf"):
-            vals.append(v)
-    for i, v in enumerate(vals):
-        prec = (4, 6, 6, 6, 1, 2, 9, 15)[i % 8]
+    gold = U.load_ref_live()["format_real"]
+    cases = U.format_real_cases()
+    assert len(cases) == gold["count"]
+    digest = hashlib.sha256()
+    for v, prec in cases:
         n = lib.host_format_real(v, prec, buf)
         mine = buf.raw[:n].decode()
         assert mine == U.real_to_str(v, prec), (v, prec)
         if have_ref:
             assert mine == O.ref_format_real(v, prec), (v, prec)
+        digest.update(mine.encode() + b"\n")
+    # the reference's refresh::real_to_pchar on the same cases, stored (tests/golden/ref_live_vectors.json)
+    assert digest.hexdigest() == gold["sha256"]
 
 
-@pytest.mark.skipif(O.lib_ref() is None or not hasattr(O.lib_ref(), "ref_expand_output_format"), reason="oracle/_ref not built")
 def test_out_format_expansion_matches_reference(tmp_path):
-    """--out-format meta names and column lists: the header the binary writes is what CParams derives."""
+    """--out-format meta names and column lists: the header the binary writes is what CParams derives (stored in
+    tests/golden/ref_live_vectors.json; also live where oracle/_ref is built)."""
     names, seqs, res = _oracle_reordered(U.load_example)
     raw = str(tmp_path / "raw.txt")
     _raw_file(raw, res)
     fa = os.path.join(U.GOLD, "example", "multifasta.fna")
-    for fmt in ("standard", "lite", "complete", "lite,rlen,qlen", "nt_match,standard", "query,reference,tani", "rcov"):
+    want = U.load_ref_live()["out_format"]
+    if O.lib_ref() is not None and hasattr(O.lib_ref(), "ref_expand_output_format"):
+        assert want == {fmt: O.ref_expand_output_format(fmt) for fmt in want}
+    for fmt in U.OUT_FORMATS:
         out = str(tmp_path / "f.tsv")
         assert run(["all2all", "--in-fasta", fa, "-o", out, "--results-in", raw, "--out-format", fmt]).returncode == 0
-        assert open(out).readline().rstrip("\n").split("\t") == O.ref_expand_output_format(fmt).split(",")
-    assert O.ref_expand_output_format("tani,bogus") == "!bogus"
+        assert open(out).readline().rstrip("\n").split("\t") == want[fmt].split(",")
+    assert want["tani,bogus"] == "!bogus"
     p = run(["all2all", "--in-fasta", fa, "-o", str(tmp_path / "g.tsv"), "--results-in", raw, "--out-format", "tani,bogus"])
     assert p.returncode == 0 and "Unknown output-format component: bogus" in p.stderr      # parse failure: return 0, as the reference
 

@@ -4,7 +4,8 @@
    byte for byte from the oracle's integers through the restated emit rule;
 2. against vectors produced by the reference's CParser itself (tests/golden/ref_vectors.json,
    generator oracle/make_goldens.py);
-3. live against oracle/_ref where it has been built (this container; it also travels to the GPU box).
+3. against stored answers of the reference build (tests/golden/ref_live_vectors.json) and live against
+   oracle/_ref where it has been built.
 """
 import json
 import os
@@ -104,11 +105,15 @@ def test_edge_values_known():
     assert O.oracle_pair(e[9], e[0]) == (0, 0, 0)             # empty reference
 
 
-@pytest.mark.skipif(O.lib_ref() is None, reason="oracle/_ref not built (needs /root/reference)")
 def test_live_against_reference_build():
-    _, seqs = SG.make_set(30, 21, lmin=4000, lmax=12000, fam=5)
-    seqs[3] = np.concatenate([seqs[3][:2000], np.full(30, 5, np.uint8), seqs[3][2000:]])
-    for prm in (None, dict(mal=15, msl=9, reg=60), dict(mrd=25, mqd=55, aw=20, am=9, ar=2)):
+    """The oracle against the reference build on U.live_set: its stored answers (tests/golden/ref_live_vectors.json)
+    everywhere, and the build itself where oracle/_ref is built."""
+    seqs = U.live_set()
+    gold = U.load_ref_live()["all2all"]
+    for name, prm in U.LIVE_PARAMS.items():
         a = O.oracle_all2all(seqs, prm, threads=8)
-        b = O.ref_all2all(seqs, prm, threads=8)
-        assert np.array_equal(a, b), prm
+        assert gold[name]["params"] == (prm or {})
+        assert np.array_equal(a, np.array(gold[name]["res"], dtype=np.int32)), prm
+        if O.lib_ref() is not None:
+            b = O.ref_all2all(seqs, prm, threads=8)
+            assert np.array_equal(a, b), prm

@@ -138,6 +138,47 @@ def emit_tsv(names, lens, res, columns, in_percent=False):
 
 
 STANDARD = "qidx,ridx,query,reference,tani,gani,ani,qcov,num_alns,len_ratio".split(",")
+OUT_FORMATS = ("standard", "lite", "complete", "lite,rlen,qlen", "nt_match,standard", "query,reference,tani", "rcov")
+
+
+def format_real_cases():
+    """Seeded (value, precision) cases of the TSV number formatting: edge values, ratios, percentages, random magnitudes
+    and random bit patterns."""
+    import random
+    import struct
+    rnd = random.Random(3)
+    vals = [0.0, 1.0, 0.5, 1e-7, 4e-7, 0.000364, 0.98725, 0.999999, 0.9999995, 0.99999949, 9.9999995, 123456.5,
+            1234567.0, 1e21, 1e22, 5e-324, 1.7976931348623157e308]
+    for _ in range(20000):
+        k = rnd.random()
+        if k < 0.5:
+            v = rnd.randint(0, 10 ** rnd.randint(1, 7)) / rnd.randint(1, 10 ** rnd.randint(1, 7))
+        elif k < 0.7:
+            v = 100.0 * rnd.randint(0, 50000) / rnd.randint(1, 50000)
+        elif k < 0.9:
+            v = rnd.random() * 10 ** rnd.randint(-12, 12)
+        else:
+            v = struct.unpack("d", struct.pack("Q", rnd.getrandbits(62)))[0]
+        if v == v and v != float("inf"):
+            vals.append(v)
+    return [(v, (4, 6, 6, 6, 1, 2, 9, 15)[i % 8]) for i, v in enumerate(vals)]
+
+
+def live_set():
+    """The synthetic set of the live oracle-vs-reference comparison: 30 genomes in families of 5, an N run in one."""
+    _, seqs = SG.make_set(30, 21, lmin=4000, lmax=12000, fam=5)
+    seqs[3] = np.concatenate([seqs[3][:2000], np.full(30, 5, np.uint8), seqs[3][2000:]])
+    return seqs
+
+
+LIVE_PARAMS = {"default": None, "long": dict(mal=15, msl=9, reg=60), "mrd25_mqd55_aw20_am9_ar2": dict(mrd=25, mqd=55, aw=20, am=9, ar=2)}
+
+
+def load_ref_live():
+    """What the reference build answered on live_set, OUT_FORMATS and format_real_cases (oracle/make_goldens.py)."""
+    import json
+    with open(os.path.join(GOLD, "ref_live_vectors.json")) as f:
+        return json.load(f)
 
 
 # ---- the lane-emulating host model of the kernels (tests/model) --------------------------
