@@ -217,12 +217,16 @@ LZ_HD int equal_len(const TextView& R, int rp, const TextView& Q, int qp, int st
     return n < bound ? n : (bound > start ? bound : start);
 }
 
-// k-mer (k <= 32) starting at p; returns false if it overlaps an N or the end of the text
+// k-mer (k <= 32) starting at p; returns false if it overlaps an N or the end of the text.
+// Quirk Q14 (parser.cpp:53-103, 166, 179, 514, 585): the reference holds a k-mer in an int64_t with its first symbol in
+// the top two bits and takes a negative value for "no k-mer", so at k = 32 every k-mer whose first symbol is G or T
+// (code >= 2) is absent -- as anchor (mal) and as seed (msl) alike.  win2 puts the first symbol in the low two bits.
 LZ_HD bool kmer_at(const TextView& t, int p, int k, u64& key)
 {
     if (p < 0 || p + k > t.len) return false;
     if (winN(t.nm, p) & lowmask(k)) return false;
     key = win2(t.t2, p) & lowmask(2 * k);
+    if (k >= 32 && (key & 2)) return false;
     return true;
 }
 
@@ -769,7 +773,9 @@ struct PairMachine {
             pos += len;
         }
     }
-    LZ_HD void region_close() { if (ALN) { if (!c.fresh && c.length() >= P.reg) w.emit_region(c); c.clear(); } }
+    // (a fresh region is the reference's empty region_t -- coordinates -1, length 0 -- and calc_regions keeps it too when
+    // reg <= 0: at the first match_distant of a pair, or at the end of a pair without one; parser.cpp:797, 826)
+    LZ_HD void region_close() { if (ALN) { if (c.length() >= P.reg) w.emit_region(c); c.clear(); } }
 
     // compare_ranges folded (parser.cpp:210-248): any length, forward order
     LZ_HD void seg_range(int q0, int r0, int len)

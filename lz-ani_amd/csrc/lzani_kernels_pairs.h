@@ -46,14 +46,16 @@ LZ_HD constexpr Params folded_params(int defp)
     return defp == 2 ? Params{15, 9, 40, 40, 60, 15, 7, 3} : defp == 9 ? LZ_RTC_PARAMS : Params{11, 7, 40, 40, 35, 15, 7, 3};
 }
 // What the hand-written null chain (DevWave::null_chain) takes for granted about the parameters: one lane per tracking
-// step (mqd + 1 <= 64), a seed window of 64 .. 128 positions (two loads of window k-mers, the spare lanes of the second
+// step (mqd + 1 <= 63), a seed window of 64 .. 127 positions (two loads of window k-mers, the spare lanes of the second
 // wrapping around to position 0), extensions that fit the null-extension record (aw <= 15, lzani_core.h), the window of
 // an extension step out of a 96-bit funnel (aw >= 2, ar <= aw), msl-mers that index the 16 Kbit seed bitmap directly
 // (msl <= 7) or through the hash bits k_kmers packs above them (msl 8, 9).
+// (Its lane masks come from s_bfm_b64, which takes the width modulo 64: 64 tracking steps (mqd = 63) or 64 positions of
+// the second window load (mqd + mrd = 128) would be an empty mask, and seed candidates were lost there.)
 LZ_HD constexpr bool chain_params_ok(const Params& p)
 {
-    return p.mal >= 1 && p.mal <= 15 && p.msl >= 1 && p.msl <= 9 && p.mqd >= 0 && p.mqd <= 63 && p.mrd >= 1 &&
-           p.mqd + p.mrd >= 64 && p.mqd + p.mrd <= 128 && p.aw >= 2 && p.aw <= 15 && p.ar <= p.aw && p.am >= 0 && p.reg >= 0 && p.reg < (1 << 20);
+    return p.mal >= 1 && p.mal <= 15 && p.msl >= 1 && p.msl <= 9 && p.mqd >= 0 && p.mqd <= 62 && p.mrd >= 1 &&
+           p.mqd + p.mrd >= 64 && p.mqd + p.mrd <= 127 && p.aw >= 2 && p.aw <= 15 && p.ar <= p.aw && p.am >= 0 && p.reg >= 0 && p.reg < (1 << 20);
 }
 // CHAIN (template parameter of DevWave): 0 = no hand-written loop; 1 = the defaults, 3 = the defaults in a kernel for
 // genomes without N; 2 = the long-genome set; 9 / 10 = the run-time set (10: genomes without N)

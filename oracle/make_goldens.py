@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/ref_vectors.json and tests/golden/ref_live_vectors.json with the reference build (oracle/_ref).
+"""Generate tests/golden/ref_vectors.json, tests/golden/ref_live_vectors.json and tests/golden/ref_envelope_vectors.json
+with the reference build (oracle/_ref).
 
 TEST INFRASTRUCTURE ONLY.  Run in the build container (needs /root/reference to build
-oracle/_ref):   make -C oracle ref && python oracle/make_goldens.py [--live-only]
+oracle/_ref):   make -C oracle ref && python oracle/make_goldens.py [--live-only | --envelope-only]
 Every vector is (inputs named by fixture/seed, expected int triples); no reference code is stored.
 """
 import json
@@ -52,9 +53,33 @@ def live_vectors():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def envelope_vectors():
+    """The reference build's all2all for every edge tuple of U.EDGE_TUPLES it can run (msl <= U.REF_MAX_MSL: its short-seed
+    table has 4^msl entries) on U.edge_set() and U.envelope_family_set() (tests/test_envelope.py, tests/test_gpu_envelope.py)."""
+    sets = {"edge": U.edge_set(), "family": U.envelope_family_set()}
+    out = {"generator": "oracle/make_goldens.py", "source": "the reference build of oracle/_ref (CParser)",
+           "layout": "res[set][tuple] = int32[n][n][3], res[r][q] = [sym_in_matches, sym_in_literals, no_components] of "
+                     "parse(query=q, ref=r); diagonal zero",
+           "params": {}, "res": {k: {} for k in sets}}
+    for name, prm in U.EDGE_TUPLES.items():
+        if prm["msl"] > U.REF_MAX_MSL:
+            continue
+        out["params"][name] = prm
+        for k, seqs in sets.items():
+            out["res"][k][name] = O.ref_all2all(seqs, prm, threads=8).tolist()
+    path = os.path.join(ROOT, "tests", "golden", "ref_envelope_vectors.json")
+    with open(path, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path), "bytes;", len(out["params"]), "tuples")
+
+
 def main():
     assert O.lib_ref() is not None, "build oracle/_ref first (make -C oracle ref)"
+    if "--envelope-only" in sys.argv[1:]:
+        envelope_vectors()
+        return
     live_vectors()
+    envelope_vectors()
     if "--live-only" in sys.argv[1:]:
         return
     out = {"generator": "oracle/make_goldens.py", "source": "CParser of /root/reference (LZ-ANI 1.2.3) via oracle/ref_driver.cpp",

@@ -274,11 +274,11 @@ def fuzz_case_medium(st):
 
 def fuzz_params_chain(st):
     """A random parameter tuple INSIDE what the hand-written null chain is written for (chain_params_ok in
-    lzani_kernels_pairs.h: mqd <= 63, 64 <= mqd + mrd <= 128, 2 <= aw <= 15, ar <= aw, msl <= 9) and inside the reference's
+    lzani_kernels_pairs.h: mqd <= 62, 64 <= mqd + mrd <= 127, 2 <= aw <= 15, ar <= aw, msl <= 9) and inside the reference's
     own well-defined range (mqd <= mrd); never one of the two tuples compiled ahead of time."""
     while True:
         mrd = st.randint(32, 64)
-        mqd = st.randint(64 - mrd, min(mrd, 63))
+        mqd = st.randint(64 - mrd, min(mrd, 62, 127 - mrd))
         msl = st.randint(4, 9)
         aw = st.randint(2, 15)
         prm = dict(mal=st.randint(max(msl, 9), 13), msl=msl, mrd=mrd, mqd=mqd, reg=st.randint(10, 80), aw=aw,
@@ -350,3 +350,122 @@ def fuzz_case(st):
             g = np.tile(g[:st.randint(1, 6)], 60)[:400]
         seqs.append(np.ascontiguousarray(g))
     return prm, seqs
+
+
+# ---- the LZ parameter envelope at its edges ---------------------------------------------------
+# Plain-Python restatements of the C predicates that decide which form of the pair path a tuple takes, written from the C
+# source (not generated from it), so that the tests can predict the form and check that it ran.
+FAST_MAX_K = 15                                       # per-genome k-mer words exist for mal, msl <= 15 (lzani_hip.hip)
+AOT_SETS = {"defaults": dict(DEFAULTS), "long": dict(DEFAULTS, mal=15, msl=9, reg=60)}     # folded in ahead of time (DEFP 1, 2)
+
+
+def full_params(prm=None):
+    return dict(DEFAULTS, **(prm or {}))
+
+
+def params_supported(prm):
+    """lzani_layout.h: params_supported -- the envelope of the wave formulation (LZANI_ERR_PARAMS outside)."""
+    p = full_params(prm)
+    return (1 <= p["msl"] <= 32 and 1 <= p["mal"] <= 32 and 0 <= p["mrd"] <= 1 << 20 and 0 <= p["mqd"] <= 64 and
+            1 <= p["aw"] <= 64 and p["ar"] <= 64 and p["am"] >= 0)
+
+
+def chain_params_ok(prm):
+    """lzani_kernels_pairs.h: chain_params_ok -- the tuples the hand-written null chain is written for."""
+    p = full_params(prm)
+    return (1 <= p["mal"] <= 15 and 1 <= p["msl"] <= 9 and 0 <= p["mqd"] <= 62 and p["mrd"] >= 1 and
+            64 <= p["mqd"] + p["mrd"] <= 127 and 2 <= p["aw"] <= 15 and p["ar"] <= p["aw"] and p["am"] >= 0 and
+            0 <= p["reg"] < 1 << 20)
+
+
+def is_fast(prm):
+    p = full_params(prm)
+    return p["mal"] <= FAST_MAX_K and p["msl"] <= FAST_MAX_K
+
+
+def is_aot(prm):
+    return full_params(prm) in AOT_SETS.values()
+
+
+def index_form(seqs, prm):
+    """The anchor index of this genome set without environment overrides (lzani_layout.h: index_geometry; lzani_hip.hip:
+    choose_index_form): exact tags (the stored tag identifies the k-mer), a bucket table, tag words."""
+    p = full_params(prm)
+    T = 2 * max([len(s) for s in seqs] + [0]) + 3 * p["mrd"]
+    clog2 = lambda x: (int(x) - 1).bit_length()           # smallest b with 2^b >= x (x >= 1)
+    kb, posbits = 2 * p["mal"], max(1, clog2(T + 1))
+    dirbits = min(max(8, min(clog2(max(T, 1)), 26)), kb)
+    tagbits = min(kb - dirbits, 32 - posbits)
+    exact = tagbits == kb - dirbits
+    bk = is_fast(p) and exact and dirbits <= 26 and tagbits + posbits <= 30
+    return dict(exact=exact, bucket_table=bk, tag_words=bk and tagbits <= 7)
+
+
+# One table of edge tuples, a name per row; every row keeps mqd <= mrd (see fuzz_case).  Each row changes one group of
+# knobs from the defaults: the seed window and the tracking steps (mqd/mrd), the approximate extension (aw/am/ar), the
+# k-mer lengths (mal/msl) and the region length (reg).
+EDGE_GROUPS = {
+    "mqd_mrd": {"mqd0_mrd0": dict(mqd=0, mrd=0), "mqd0_mrd64": dict(mqd=0, mrd=64),
+                "mqd24_mrd40": dict(mqd=24, mrd=40),            # window of 64: the chain's lower bound
+                "mqd62_mrd65": dict(mqd=62, mrd=65),            # 63 tracking steps, window of 127: the chain's upper bounds
+                "mqd63_mrd64": dict(mqd=63, mrd=64),            # 64 tracking steps: outside the chain
+                "mqd40_mrd88": dict(mqd=40, mrd=88), "mqd63_mrd65": dict(mqd=63, mrd=65),    # window of 128: outside the chain
+                "mqd64_mrd64": dict(mqd=64, mrd=64),            # 65 tracking steps
+                "mqd64_mrd1000": dict(mqd=64, mrd=1000)},       # window beyond 128: no candidate bitmaps, no split
+    "aw_am_ar": {"aw1_am0_ar0": dict(aw=1, am=0, ar=0), "aw2_am0_ar2": dict(aw=2, am=0, ar=2),
+                 "aw2_am1_ar0": dict(aw=2, am=1, ar=0),         # AR = max(ar, 1) in ChainP
+                 "aw15_am15_ar15": dict(aw=15, am=15, ar=15),
+                 "aw15_am20_ar0": dict(aw=15, am=20, ar=0),     # AM = min(am, 16) in ChainP
+                 "aw16_am7_ar3": dict(aw=16, am=7, ar=3),       # outside the chain
+                 "aw64_am64_ar64": dict(aw=64, am=64, ar=64), "aw64_am64_ar-3": dict(aw=64, am=64, ar=-3)},
+    "mal_msl": {"mal1_msl1": dict(mal=1, msl=1), "mal15_msl1": dict(mal=15, msl=1), "mal9_msl9": dict(mal=9, msl=9),
+                "mal7_msl9": dict(mal=7, msl=9),                # mal < msl
+                "mal15_msl8": dict(mal=15, msl=8),              # msl 8, 9: the hashed seed-bitmap mapping
+                "mal15_msl15": dict(mal=15, msl=15), "mal16_msl16": dict(mal=16, msl=16),   # the FAST limit
+                "mal31_msl11": dict(mal=31, msl=11),
+                "mal32_msl7": dict(mal=32, msl=7), "mal32_msl11": dict(mal=32, msl=11),     # 32-symbol k-mers (quirk Q14)
+                "mal32_msl32": dict(mal=32, msl=32)},
+    "reg": {"reg-1": dict(reg=-1), "reg0": dict(reg=0), "reg1": dict(reg=1),
+            "reg100000": dict(reg=100000)},                     # longer than every genome
+}
+EDGE_TUPLES = {name: full_params(d) for g in EDGE_GROUPS.values() for name, d in g.items()}
+REF_MAX_MSL = 11                  # beyond, the reference's 4^msl short-seed table is the limit (see the fuzz tests)
+
+
+def edge_params(st):
+    """A random tuple drawn from the edges: every group of knobs from one of its edge rows or left at the defaults."""
+    p = dict(DEFAULTS)
+    for rows in EDGE_GROUPS.values():
+        names = sorted(rows)
+        k = st.randint(0, len(names))
+        if k < len(names):
+            p.update(rows[names[k]])
+    return p
+
+
+# every bound of params_supported: (knob, value one step inside, value one step outside)
+ENVELOPE_BOUNDS = [("msl", 1, 0), ("msl", 32, 33), ("mal", 1, 0), ("mal", 32, 33), ("mrd", 0, -1), ("mrd", 1 << 20, (1 << 20) + 1),
+                   ("mqd", 0, -1), ("mqd", 64, 65), ("aw", 1, 0), ("aw", 64, 65), ("ar", 64, 65), ("am", 0, -1)]
+
+
+def bound_pair(knob, ok, bad):
+    """(tuple one step inside the bound, the same tuple one step outside), the rest at the defaults with mqd <= mrd."""
+    inside = dict(DEFAULTS, **{knob: ok})
+    if knob == "mrd":
+        inside["mqd"] = min(inside["mqd"], ok)
+    else:
+        inside["mrd"] = max(inside["mrd"], inside["mqd"])
+    return inside, dict(inside, **{knob: bad})
+
+
+def envelope_family_set(with_n=True):
+    """The family set of the envelope tests: 8 genomes of 6-9 kbp in families of 3; with_n puts N runs into three of
+    them (a run at the start, one in the middle, one at the end)."""
+    _, seqs = SG.make_set(8, 91, lmin=6000, lmax=9000, fam=3)
+    seqs = [s.copy() for s in seqs]
+    if with_n:
+        seqs[1][:7] = 5
+        seqs[4][3000:3000 + 40] = 5
+        seqs[6][3500:3520] = 5
+        seqs[6][-3:] = 5
+    return seqs
