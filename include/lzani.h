@@ -170,6 +170,14 @@ int lzani_get_rtc_info(const lzani_ctx *ctx, lzani_rtc_info *info);
  * without N; cand: 0 probe, 1 join, 2 candidate bitmaps) for the gfx target `arch` and returns the size of the code
  * object, or a negative error code with the compiler's messages in `log`. */
 int64_t lzani_debug_rtc_compile(const lzani_params *p, int nfree, int cand, const char *arch, char *log, uint64_t log_cap);
+/* Test hooks: the launch record.  Every pair-kernel instantiation the engine can launch (the ones compiled ahead of
+ * time and the run-time compiled kernel per (nfree, cand)) has a fixed id and name; lzani_debug_kernel_launches copies
+ * the launches per id of the context's last run (up to cap entries) and returns the size of the table;
+ * lzani_debug_kernel_name returns the name of an id, NULL past the end (needs no context and no GPU).  Names:
+ * "pairs fast=F nfree=N defp=D aln=A bk=B cand=C", "pairs_blk nfree=N defp=D", "split nfree=N defp=D mode=M",
+ * "rtc nfree=N cand=C". */
+int lzani_debug_kernel_launches(const lzani_ctx *ctx, uint64_t *counts, uint32_t cap);
+const char *lzani_debug_kernel_name(uint32_t id);
 
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker

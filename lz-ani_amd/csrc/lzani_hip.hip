@@ -52,6 +52,91 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 // ============================================================================================
 using namespace lzani;
 
+// Launch record: one entry per pair-kernel instantiation the dispatch of run_rows_impl can launch, counted per context
+// for the last run (lzani_debug_kernel_launches).  The names follow one grammar a test can build from the dispatch rules:
+//   pairs fast=F nfree=N defp=D aln=A bk=B cand=C   k_pairs<F, N, D, A, B, C>
+//   pairs_blk nfree=N defp=D                        k_pairs_blk<N, D>
+//   split nfree=N defp=D mode=M                     k_split<N, D, M>
+//   rtc nfree=N cand=C                              the run-time compiled kernel (lzani_rtc.h), DEFP 9
+// An instantiation added to the dispatch needs a row here (pk_id refuses to compile without one) and a cell in
+// tests/test_gpu_instantiations.py.
+enum PairKernelKind { PK_PAIRS, PK_BLK, PK_SPLIT, PK_RTC };
+struct PairKernelDesc { const char* name; int kind, fast, nfree, defp, aln, bk, cand, mode; };
+enum PairKernelId : u32 {
+    PK_REGIONS_SLOW, PK_REGIONS_TW, PK_REGIONS_NOTW, PK_SLOW,
+    PK_PM_N0_D0, PK_PM_N0_D1, PK_PM_N0_D2, PK_PM_N1_D0, PK_PM_N1_D1, PK_PM_N1_D2,
+    PK_JOIN_N0_D0, PK_JOIN_N0_D1, PK_JOIN_N0_D2, PK_JOIN_N1_D0, PK_JOIN_N1_D1, PK_JOIN_N1_D2,
+    PK_TW_N0_D0, PK_TW_N0_D1, PK_TW_N1_D0, PK_TW_N1_D1,
+    PK_NOTW_N0_D0, PK_NOTW_N0_D1, PK_NOTW_N1_D0, PK_NOTW_N1_D1,
+    PK_BLK_N0_D0, PK_BLK_N0_D1, PK_BLK_N1_D0, PK_BLK_N1_D1,
+    PK_SPLIT_N0_D0_M0, PK_SPLIT_N0_D0_M1, PK_SPLIT_N0_D1_M0, PK_SPLIT_N0_D1_M1, PK_SPLIT_N0_D2_M0, PK_SPLIT_N0_D2_M1,
+    PK_SPLIT_N1_D0_M0, PK_SPLIT_N1_D0_M1, PK_SPLIT_N1_D1_M0, PK_SPLIT_N1_D1_M1, PK_SPLIT_N1_D2_M0, PK_SPLIT_N1_D2_M1,
+    PK_RTC_N0_C0, PK_RTC_N0_C1, PK_RTC_N0_C2, PK_RTC_N1_C0, PK_RTC_N1_C1, PK_RTC_N1_C2,
+    PK_COUNT
+};
+constexpr PairKernelDesc PAIR_KERNELS[PK_COUNT] = {
+    {"pairs fast=0 nfree=0 defp=0 aln=1 bk=0 cand=0", PK_PAIRS, 0, 0, 0, 1, 0, 0, 0},
+    {"pairs fast=1 nfree=0 defp=0 aln=1 bk=1 cand=0", PK_PAIRS, 1, 0, 0, 1, 1, 0, 0},
+    {"pairs fast=1 nfree=0 defp=0 aln=1 bk=0 cand=0", PK_PAIRS, 1, 0, 0, 1, 0, 0, 0},
+    {"pairs fast=0 nfree=0 defp=0 aln=0 bk=0 cand=0", PK_PAIRS, 0, 0, 0, 0, 0, 0, 0},
+    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=1 cand=2", PK_PAIRS, 1, 0, 0, 0, 1, 2, 0},
+    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=1 cand=2", PK_PAIRS, 1, 0, 1, 0, 1, 2, 0},
+    {"pairs fast=1 nfree=0 defp=2 aln=0 bk=1 cand=2", PK_PAIRS, 1, 0, 2, 0, 1, 2, 0},
+    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=1 cand=2", PK_PAIRS, 1, 1, 0, 0, 1, 2, 0},
+    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=1 cand=2", PK_PAIRS, 1, 1, 1, 0, 1, 2, 0},
+    {"pairs fast=1 nfree=1 defp=2 aln=0 bk=1 cand=2", PK_PAIRS, 1, 1, 2, 0, 1, 2, 0},
+    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=1 cand=1", PK_PAIRS, 1, 0, 0, 0, 1, 1, 0},
+    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=1 cand=1", PK_PAIRS, 1, 0, 1, 0, 1, 1, 0},
+    {"pairs fast=1 nfree=0 defp=2 aln=0 bk=1 cand=1", PK_PAIRS, 1, 0, 2, 0, 1, 1, 0},
+    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=1 cand=1", PK_PAIRS, 1, 1, 0, 0, 1, 1, 0},
+    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=1 cand=1", PK_PAIRS, 1, 1, 1, 0, 1, 1, 0},
+    {"pairs fast=1 nfree=1 defp=2 aln=0 bk=1 cand=1", PK_PAIRS, 1, 1, 2, 0, 1, 1, 0},
+    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=1 cand=0", PK_PAIRS, 1, 0, 0, 0, 1, 0, 0},
+    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=1 cand=0", PK_PAIRS, 1, 0, 1, 0, 1, 0, 0},
+    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=1 cand=0", PK_PAIRS, 1, 1, 0, 0, 1, 0, 0},
+    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=1 cand=0", PK_PAIRS, 1, 1, 1, 0, 1, 0, 0},
+    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=0 cand=0", PK_PAIRS, 1, 0, 0, 0, 0, 0, 0},
+    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=0 cand=0", PK_PAIRS, 1, 0, 1, 0, 0, 0, 0},
+    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=0 cand=0", PK_PAIRS, 1, 1, 0, 0, 0, 0, 0},
+    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=0 cand=0", PK_PAIRS, 1, 1, 1, 0, 0, 0, 0},
+    {"pairs_blk nfree=0 defp=0", PK_BLK, 1, 0, 0, 0, 1, 0, 0},
+    {"pairs_blk nfree=0 defp=1", PK_BLK, 1, 0, 1, 0, 1, 0, 0},
+    {"pairs_blk nfree=1 defp=0", PK_BLK, 1, 1, 0, 0, 1, 0, 0},
+    {"pairs_blk nfree=1 defp=1", PK_BLK, 1, 1, 1, 0, 1, 0, 0},
+    {"split nfree=0 defp=0 mode=0", PK_SPLIT, 1, 0, 0, 0, 1, 2, 0},
+    {"split nfree=0 defp=0 mode=1", PK_SPLIT, 1, 0, 0, 0, 1, 2, 1},
+    {"split nfree=0 defp=1 mode=0", PK_SPLIT, 1, 0, 1, 0, 1, 2, 0},
+    {"split nfree=0 defp=1 mode=1", PK_SPLIT, 1, 0, 1, 0, 1, 2, 1},
+    {"split nfree=0 defp=2 mode=0", PK_SPLIT, 1, 0, 2, 0, 1, 2, 0},
+    {"split nfree=0 defp=2 mode=1", PK_SPLIT, 1, 0, 2, 0, 1, 2, 1},
+    {"split nfree=1 defp=0 mode=0", PK_SPLIT, 1, 1, 0, 0, 1, 2, 0},
+    {"split nfree=1 defp=0 mode=1", PK_SPLIT, 1, 1, 0, 0, 1, 2, 1},
+    {"split nfree=1 defp=1 mode=0", PK_SPLIT, 1, 1, 1, 0, 1, 2, 0},
+    {"split nfree=1 defp=1 mode=1", PK_SPLIT, 1, 1, 1, 0, 1, 2, 1},
+    {"split nfree=1 defp=2 mode=0", PK_SPLIT, 1, 1, 2, 0, 1, 2, 0},
+    {"split nfree=1 defp=2 mode=1", PK_SPLIT, 1, 1, 2, 0, 1, 2, 1},
+    {"rtc nfree=0 cand=0", PK_RTC, 1, 0, 9, 0, 1, 0, 0},
+    {"rtc nfree=0 cand=1", PK_RTC, 1, 0, 9, 0, 1, 1, 0},
+    {"rtc nfree=0 cand=2", PK_RTC, 1, 0, 9, 0, 1, 2, 0},
+    {"rtc nfree=1 cand=0", PK_RTC, 1, 1, 9, 0, 1, 0, 0},
+    {"rtc nfree=1 cand=1", PK_RTC, 1, 1, 9, 0, 1, 1, 0},
+    {"rtc nfree=1 cand=2", PK_RTC, 1, 1, 9, 0, 1, 2, 0},
+};
+// the row of an instantiation; -1 = none (a launch site that names a kernel without a row fails to compile, see PK_COUNT_LAUNCH)
+constexpr int pk_id(int kind, int fast, int nfree, int defp, int aln, int bk, int cand, int mode)
+{
+    for (int i = 0; i < PK_COUNT; ++i) {
+        const PairKernelDesc& d = PAIR_KERNELS[i];
+        if (d.kind == kind && d.fast == fast && d.nfree == nfree && d.defp == defp && d.aln == aln && d.bk == bk && d.cand == cand && d.mode == mode)
+            return i;
+    }
+    return -1;
+}
+static_assert(pk_id(PK_PAIRS, 1, 1, 2, 0, 1, 1, 0) == PK_JOIN_N1_D2 && pk_id(PK_SPLIT, 1, 1, 2, 0, 1, 2, 1) == PK_SPLIT_N1_D2_M1 &&
+              pk_id(PK_RTC, 1, 1, 9, 0, 1, 2, 0) == PK_RTC_N1_C2 && pk_id(PK_BLK, 1, 0, 1, 0, 1, 0, 0) == PK_BLK_N0_D1,
+              "PAIR_KERNELS is out of the order of PairKernelId");
+#define PK_COUNT_LAUNCH(...) do { constexpr int id_ = pk_id(__VA_ARGS__); static_assert(id_ >= 0, "a pair kernel without a row in PAIR_KERNELS"); c->klaunch[id_] += 1; } while (0)
+
 struct lzani_ctx {
     Params P;
     int dev = 0;
@@ -137,6 +222,7 @@ struct lzani_ctx {
     lzani_rtc::State rtc;
     std::string arch;             // the device's gfx target, as hipRTC wants it
     int rtc_launches = 0;         // pair-kernel launches of the last run by a run-time compiled kernel
+    u64 klaunch[PK_COUNT] = {};   // launch record of the last run: launches per pair-kernel instantiation (PAIR_KERNELS)
     u64 pairs_seen = 0;           // directed pairs this context has been asked for so far (a run-time compile must pay)
 
     void* comm = nullptr;         // ncclComm_t of lzani_comm_init (one process per GPU), lzani_multi.h
@@ -515,6 +601,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     c->split_launches = 0;
     c->split_items = 0;
     c->rtc_launches = 0;
+    std::fill(c->klaunch, c->klaunch + PK_COUNT, (u64)0);
     if (n_rows == 0) return LZANI_OK;
     const u64 n_pairs = row_off[n_rows];
     for (u32 k = 0; k < n_rows; ++k) {
@@ -763,12 +850,14 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     // the disk cache yet is built once the context has been asked for LZANI_RTC_MIN_PAIRS pairs in all (default 2 M: the
     // first such run loses a second or two, every later run and every later process wins).
     lzani_rtc::Kernel* rtc_k = nullptr;
+    int rtc_id = PK_RTC_N0_C0;                               // (its row of the launch record)
     c->pairs_seen += n_pairs;
     if (!defp && !lgp && !rs && c->d_kmL && c->d_bk && lzani_rtc::enabled()) {
         const int cand = pm ? 2 : (use_join && c->d_tw) ? 1 : c->d_tw ? 0 : -1;
         const char* mp = getenv("LZANI_RTC_MIN_PAIRS");
         const u64 min_pairs = mp ? strtoull(mp, nullptr, 10) : 2000000ull;
         if (cand >= 0) {
+            rtc_id = PK_RTC_N0_C0 + 3 * (int)c->all_nfree + cand;
             rtc_k = lzani_rtc::get(c->rtc, c->P, c->all_nfree, cand, c->arch.c_str(), c->pairs_seen >= min_pairs);
             if (!rtc_k && c->rtc.failed) TRACE("run-time compile unavailable (%s): the generic kernel runs", c->rtc.log.c_str());
         }
@@ -957,15 +1046,16 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
             const u64 waves = e1 - e0;
             const dim3 gd((u32)std::min<u64>((waves + 3) / 4, max_blocks)), bd(256);
             HIPCHK(c, hipEventRecord(ev[2], c->stream));
-#define LZ_PAIRS(F, N, D, A, B) hipLaunchKernelGGL((k_pairs<F, N, D, A, B>), gd, bd, 0, c->stream, pa)
-#define LZ_PAIRS_JOIN(N, D) hipLaunchKernelGGL((k_pairs<true, N, D, false, true, 1>), gd, bd, 0, c->stream, pa)
-#define LZ_PAIRS_PM(N, D) hipLaunchKernelGGL((k_pairs<true, N, D, false, true, 2>), gd, bd, 0, c->stream, pa)
+#define LZ_PAIRS(F, N, D, A, B) do { hipLaunchKernelGGL((k_pairs<F, N, D, A, B>), gd, bd, 0, c->stream, pa); PK_COUNT_LAUNCH(PK_PAIRS, F, N, D, A, B, 0, 0); } while (0)
+#define LZ_PAIRS_JOIN(N, D) do { hipLaunchKernelGGL((k_pairs<true, N, D, false, true, 1>), gd, bd, 0, c->stream, pa); PK_COUNT_LAUNCH(PK_PAIRS, true, N, D, false, true, 1, 0); } while (0)
+#define LZ_PAIRS_PM(N, D) do { hipLaunchKernelGGL((k_pairs<true, N, D, false, true, 2>), gd, bd, 0, c->stream, pa); PK_COUNT_LAUNCH(PK_PAIRS, true, N, D, false, true, 2, 0); } while (0)
             const bool fast = c->d_kmL != nullptr, tw = pa.tw != nullptr, nf = c->all_nfree;
             auto rtc_launch = [&]() -> bool {
                 if (!rtc_k) return false;
                 void* kargs[] = {&pa};
                 if (hipModuleLaunchKernel(rtc_k->fn, gd.x, 1, 1, bd.x, 1, 1, 0, c->stream, kargs, nullptr) != hipSuccess) { (void)hipGetLastError(); return false; }
                 c->rtc_launches += 1;
+                c->klaunch[rtc_id] += 1;
                 return true;
             };
             // Probe form, dense rows of hundreds of pairs: blocks of 16 waves with the reference's presence filter in LDS
@@ -1016,7 +1106,8 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
                 auto launch = [&](int mode, u32 items) {
                     const dim3 gs((u32)std::min<u64>(((u64)items + 3) / 4, max_blocks)), bs4(256);
                     sa.n_work = items;
-#define LZ_SPLIT(N, D) do { if (mode == 0) hipLaunchKernelGGL((k_split<N, D, 0>), gs, bs4, 0, c->stream, sa); else hipLaunchKernelGGL((k_split<N, D, 1>), gs, bs4, 0, c->stream, sa); } while (0)
+#define LZ_SPLIT(N, D) do { if (mode == 0) { hipLaunchKernelGGL((k_split<N, D, 0>), gs, bs4, 0, c->stream, sa); PK_COUNT_LAUNCH(PK_SPLIT, true, N, D, false, true, 2, 0); } \
+                                else { hipLaunchKernelGGL((k_split<N, D, 1>), gs, bs4, 0, c->stream, sa); PK_COUNT_LAUNCH(PK_SPLIT, true, N, D, false, true, 2, 1); } } while (0)
                     if (nf) { if (dsel == 1) LZ_SPLIT(true, 1); else if (dsel == 2) LZ_SPLIT(true, 2); else LZ_SPLIT(true, 0); }
                     else { if (dsel == 1) LZ_SPLIT(false, 1); else if (dsel == 2) LZ_SPLIT(false, 2); else LZ_SPLIT(false, 0); }
 #undef LZ_SPLIT
@@ -1099,10 +1190,12 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
                 pa.fmask = c->fmask >> c->blk_fold;
                 c->blk_launches += 1;
                 const dim3 gb((u32)std::min<u64>((waves + BLK_CHUNK_MIN - 1) / BLK_CHUNK_MIN, (u64)c->n_cus * 2)), bb(64 * BLK_WAVES);
-                if (nf && defp) hipLaunchKernelGGL((k_pairs_blk<true, true>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr);
-                else if (nf) hipLaunchKernelGGL((k_pairs_blk<true, false>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr);
-                else if (defp) hipLaunchKernelGGL((k_pairs_blk<false, true>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr);
-                else hipLaunchKernelGGL((k_pairs_blk<false, false>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr);
+#define LZ_PAIRS_BLK(N, D) do { hipLaunchKernelGGL((k_pairs_blk<N, D>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr); PK_COUNT_LAUNCH(PK_BLK, true, N, D, false, true, 0, 0); } while (0)
+                if (nf && defp) LZ_PAIRS_BLK(true, true);
+                else if (nf) LZ_PAIRS_BLK(true, false);
+                else if (defp) LZ_PAIRS_BLK(false, true);
+                else LZ_PAIRS_BLK(false, false);
+#undef LZ_PAIRS_BLK
             } else if (tw) {
                 if (rtc_launch()) {}
                 else if (nf && defp) LZ_PAIRS(true, true, true, false, true);
@@ -1467,6 +1560,18 @@ int lzani_get_rtc_info(const lzani_ctx* c, lzani_rtc_info* o)
     o->reserved_ = 0;
     o->build_ms = c->rtc.compile_ms;
     return LZANI_OK;
+}
+
+int lzani_debug_kernel_launches(const lzani_ctx* c, uint64_t* counts, uint32_t cap)
+{
+    if (!c || (!counts && cap)) return LZANI_ERR_ARG;
+    for (u32 i = 0; i < cap && i < (u32)PK_COUNT; ++i) counts[i] = c->klaunch[i];
+    return (int)PK_COUNT;
+}
+
+const char* lzani_debug_kernel_name(uint32_t id)
+{
+    return id < (u32)PK_COUNT ? PAIR_KERNELS[id].name : nullptr;
 }
 
 int64_t lzani_debug_rtc_compile(const lzani_params* p, int nfree, int cand, const char* arch, char* log, uint64_t log_cap)

@@ -31,7 +31,7 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_row_costs", "lzani_partition_rows", "lzani_comm_unique_id", "lzani_comm_init", "lzani_comm_allgather",
            "lzani_comm_gatherv", "lzani_group_create", "lzani_group_destroy", "lzani_group_last_error",
            "lzani_group_set_genomes", "lzani_group_run_rows", "lzani_group_get_timing", "lzani_plan_gather", "lzani_get_rtc_info", "lzani_debug_rtc_compile",
-           "lzani_debug_sort_segments")
+           "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name")
 
 
 class LzaniError(RuntimeError):
@@ -95,6 +95,9 @@ def load_library():
         lib.lzani_get_rtc_info.argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_debug_rtc_compile.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64]
         lib.lzani_debug_rtc_compile.restype = C.c_int64
+        lib.lzani_debug_kernel_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.lzani_debug_kernel_name.argtypes = [C.c_uint32]
+        lib.lzani_debug_kernel_name.restype = C.c_char_p
         lib.lzani_run_rows_regions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_uint64, C.c_void_p]
         lib.lzani_debug_get_index.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
@@ -184,6 +187,17 @@ def rtc_compile(params=None, nfree=True, cand=2, arch="gfx950"):
     log = C.create_string_buffer(1 << 16)
     n = lib.lzani_debug_rtc_compile(arr, int(bool(nfree)), int(cand), arch.encode(), log, len(log))
     return int(n), log.value.decode(errors="replace")
+
+
+def kernel_names():
+    """Names of the launch record's entries, by id (lzani_debug_kernel_name; no GPU needed)."""
+    lib = load_library()
+    names = []
+    while True:
+        n = lib.lzani_debug_kernel_name(len(names))
+        if n is None:
+            return names
+        names.append(n.decode())
 
 
 def comm_unique_id():
@@ -359,6 +373,16 @@ class Engine:
         o = RtcInfo()
         self._check(self.lib.lzani_get_rtc_info(self.h, C.byref(o)), "lzani_get_rtc_info")
         return {k: getattr(o, k) for k, _ in RtcInfo._fields_ if k != "reserved_"}
+
+    def kernel_launches(self):
+        """Launches of the last run per pair-kernel instantiation: {name: count}, nonzero entries only."""
+        names = kernel_names()
+        counts = np.zeros(len(names), dtype=np.uint64)
+        n = self.lib.lzani_debug_kernel_launches(self.h, _ptr(counts), len(counts))
+        if n < 0:
+            self._check(n, "lzani_debug_kernel_launches")
+        assert n == len(names), (n, len(names))
+        return {names[i]: int(counts[i]) for i in range(len(names)) if counts[i]}
 
     def debug_sort_segments(self, keys, seg_len, n_seg, begin_bit, end_bit):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)

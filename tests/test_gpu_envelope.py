@@ -64,11 +64,14 @@ def _forms(eng, monkeypatch, seqs, prm, want, what):
     assert np.array_equal(got, want), (what, "default", _diff(got, want))
     assert lay["kmer_words"] == fast and lay["bucket_table"] == form["bucket_table"] and lay["tag_words"] == form["tag_words"], (what, lay)
     assert lay["n_free"] == all((s < 4).all() for s in seqs) and lay["rtc_launches"] == 0, (what, lay)
+    assert set(eng.kernel_launches()) == U.predict_kernels(seqs, prm, {"LZANI_RTC": "0"}), (what, "default", eng.kernel_launches())
     # 2. dense rows by candidate bitmaps (k-mer words, a bucket table and a seed window of up to 128 positions)
     monkeypatch.setenv("LZANI_PM_MIN_ROWS", "1")
     got = eng.all2all()
     lay = eng.layout()
+    rec = eng.kernel_launches()
     monkeypatch.delenv("LZANI_PM_MIN_ROWS")
+    assert set(rec) == U.predict_kernels(seqs, prm, {"LZANI_RTC": "0", "LZANI_PM_MIN_ROWS": "1"}), (what, "bitmaps", rec)
     assert np.array_equal(got, want), (what, "bitmaps", _diff(got, want))
     assert (lay["bitmap_launches"] >= 1) == bitmaps_ok, (what, "bitmaps", lay)
     # 3. filtered rows: a few queries per reference
@@ -84,7 +87,9 @@ def _forms(eng, monkeypatch, seqs, prm, want, what):
     monkeypatch.setenv("LZANI_BLOCK_KERNEL", "1")
     out = eng.run_rows(np.arange(n, dtype=np.uint32), off, np.array([q for x in lists for q in x], np.uint32))
     lay = eng.layout()
+    rec = eng.kernel_launches()
     monkeypatch.delenv("LZANI_BLOCK_KERNEL")
+    assert set(rec) == U.predict_kernels(seqs, prm, {"LZANI_RTC": "0", "LZANI_BLOCK_KERNEL": "1"}, "dup_lists", len(lists[0])), (what, "block kernel", rec)
     exp = np.concatenate([want[r, lists[r]] for r in range(n)])
     assert np.array_equal(out, exp), (what, "block kernel", _diff(out, exp))
     assert (lay["block_launches"] >= 1) == form["tag_words"], (what, "block kernel", lay)
@@ -94,6 +99,7 @@ def _forms(eng, monkeypatch, seqs, prm, want, what):
             monkeypatch.setenv(k, v)
         got = eng.all2all()
         lay = eng.layout()
+        assert set(eng.kernel_launches()) == U.predict_kernels(seqs, prm, {"LZANI_RTC": "0", "LZANI_PM_MIN_ROWS": "1", "LZANI_SPLIT": "1", "LZANI_SPLIT_SEGLEN": str(SPLIT_SEGLEN)}), (what, "split")
         for k in ("LZANI_PM_MIN_ROWS", "LZANI_SPLIT", "LZANI_SPLIT_SEGLEN", "LZANI_SPLIT_ALL"):
             monkeypatch.delenv(k)
         assert np.array_equal(got, want), (what, "split", _diff(got, want))
@@ -101,6 +107,7 @@ def _forms(eng, monkeypatch, seqs, prm, want, what):
     # 6. the alignment instantiation: every region of every pair
     ref_ids, row_off = L.dense_rows(n)
     out, regs = eng.run_rows_regions(ref_ids, row_off, None)
+    assert set(eng.kernel_launches()) == U.predict_kernels(seqs, prm, form="regions"), (what, "regions", eng.kernel_launches())
     assert np.array_equal(out.reshape(-1, 3), want[~np.eye(n, dtype=bool)]), (what, "regions: results")
     cols = ("ref_start", "ref_end", "seq_start", "seq_end", "num_matches", "num_mismatches")
     e = total = 0
@@ -127,7 +134,7 @@ def _rtc(monkeypatch, rtc_cache, seqs, prm, want, what):
     try:
         eng.set_genomes(seqs)
         got = eng.all2all()
-        lay, info = eng.layout(), eng.rtc_info()
+        lay, info, rec = eng.layout(), eng.rtc_info(), eng.kernel_launches()
     finally:
         eng.close()
         for k in ("LZANI_RTC_MIN_PAIRS", "LZANI_PM_MIN_ROWS"):
@@ -135,6 +142,7 @@ def _rtc(monkeypatch, rtc_cache, seqs, prm, want, what):
     assert np.array_equal(got, want), (what, "run-time compiled", _diff(got, want))
     assert lay["rtc_launches"] >= 1 and info["kernels_failed"] == 0 and info["kernels_built"] >= 1, (what, lay, info)
     assert info["folded_ahead_of_time"] == 0 and info["null_chain"] == U.chain_params_ok(prm), (what, info)
+    assert set(rec) == U.predict_kernels(seqs, prm, {"LZANI_PM_MIN_ROWS": "1"}, rtc_ready=True), (what, "run-time compiled", rec)
 
 
 @pytest.mark.parametrize("name", list(ROWS))

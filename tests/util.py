@@ -398,7 +398,7 @@ def index_form(seqs, prm):
     tagbits = min(kb - dirbits, 32 - posbits)
     exact = tagbits == kb - dirbits
     bk = is_fast(p) and exact and dirbits <= 26 and tagbits + posbits <= 30
-    return dict(exact=exact, bucket_table=bk, tag_words=bk and tagbits <= 7)
+    return dict(exact=exact, bucket_table=bk, tag_words=bk and tagbits <= 7, T=T, key_bits=kb, dir_bits=dirbits, pos_bits=posbits)
 
 
 # One table of edge tuples, a name per row; every row keeps mqd <= mrd (see fuzz_case).  Each row changes one group of
@@ -469,3 +469,206 @@ def envelope_family_set(with_n=True):
         seqs[6][3500:3520] = 5
         seqs[6][-3:] = 5
     return seqs
+
+
+# ---- the pair-kernel instantiations and the launch record ---------------------------------------
+# lzani_hip.hip names every pair-kernel instantiation its dispatch can launch (lzani_debug_kernel_name) and counts the launches
+# of a context's last run per name (Engine.kernel_launches).  The matrix below is written from the dispatch of run_rows_impl,
+# not copied from the library's table; tests/test_instantiations.py checks the two against each other and against the
+# kernel symbols of the gfx950 code object.
+PAIRS_NAME = "pairs fast={} nfree={} defp={} aln={} bk={} cand={}"
+
+
+def expected_kernel_names():
+    """Every pair-kernel instantiation the dispatch can launch.  defp: 0 generic, 1 the defaults, 2 --mal 15 --msl 9
+    --reg 60 (folded where candidates come from bitmaps or the join, and in the split); bk = the tag-word anchor queue;
+    cand: 0 probe, 1 join, 2 candidate bitmaps."""
+    names = [PAIRS_NAME.format(0, 0, 0, 1, 0, 0), PAIRS_NAME.format(1, 0, 0, 1, 1, 0), PAIRS_NAME.format(1, 0, 0, 1, 0, 0),  # regions
+             PAIRS_NAME.format(0, 0, 0, 0, 0, 0)]                                                                            # no k-mer words
+    names += [PAIRS_NAME.format(1, nf, d, 0, 1, cand) for cand in (2, 1) for nf in (0, 1) for d in (0, 1, 2)]
+    names += [PAIRS_NAME.format(1, nf, d, 0, bk, 0) for bk in (1, 0) for nf in (0, 1) for d in (0, 1)]
+    names += ["pairs_blk nfree={} defp={}".format(nf, d) for nf in (0, 1) for d in (0, 1)]
+    names += ["split nfree={} defp={} mode={}".format(nf, d, m) for nf in (0, 1) for d in (0, 1, 2) for m in (0, 1)]
+    names += ["rtc nfree={} cand={}".format(nf, cand) for nf in (0, 1) for cand in (0, 1, 2)]
+    return names
+
+
+KERNEL_NAME_RE = (r"^(pairs fast=[01] nfree=[01] defp=[012] aln=[01] bk=[01] cand=[012]|pairs_blk nfree=[01] defp=[01]|"
+                  r"split nfree=[01] defp=[012] mode=[01]|rtc nfree=[01] cand=[012])$")
+
+
+def _clog2(x):
+    return (int(x) - 1).bit_length() if x > 1 else 0
+
+
+def predict_kernels(seqs, prm, env=None, form="all2all", pairs_per_row=None, n_rows=None, rtc_ready=False):
+    """The names a run launches (lzani_hip.hip: run_rows_impl), from the genome set, the tuple, the environment (the
+    LZANI_* switches that are set) and the call: form "all2all" (dense rows), "dup_lists" (query lists that name a
+    query twice in a row: never candidate bitmaps), "regions" (lzani_run_rows_regions).  rtc_ready: the run-time
+    compiled kernel of the tuple is available (compiled or in the disk cache).  One batch, memory to spare, a block
+    kernel whose LDS filter fits."""
+    env = env or {}
+    on = lambda k: env.get(k, "")[:1] == "1"
+    off = lambda k: env.get(k, "")[:1] == "0"
+    p = full_params(prm)
+    n = len(seqs)
+    g = index_form(seqs, p)
+    fast = is_fast(p)
+    bk = g["bucket_table"] and not on("LZANI_NO_BUCKETS")
+    tw = bk and g["tag_words"] and not on("LZANI_NO_TAGWORDS")
+    window = p["mqd"] + p["mrd"] <= 128
+    join_mode = (tw and 4 * (1 << g["dir_bits"]) >= int(env.get("LZANI_JOIN_MIN_BYTES", 8 << 20)) and window and
+                 _clog2(n + 1) + g["key_bits"] + g["pos_bits"] <= 64 and not on("LZANI_NO_JOIN"))
+    nf = int(all((s < 4).all() for s in seqs))
+    d_fold = 1 if p == AOT_SETS["defaults"] else 2 if p == AOT_SETS["long"] else 0     # bitmaps, join, split
+    d_probe = int(d_fold == 1)                                                          # probe forms, block kernel
+    if form == "regions":
+        return {PAIRS_NAME.format(int(fast), 0, 0, 1, int(fast and tw), 0)}
+    if not fast:
+        return {PAIRS_NAME.format(0, 0, 0, 0, 0, 0)}
+    n_rows = n if n_rows is None else n_rows
+    pairs_per_row = n - 1 if pairs_per_row is None else pairs_per_row
+    n_pairs = n_rows * pairs_per_row
+    min_rows = max(1, int(env["LZANI_PM_MIN_ROWS"])) if "LZANI_PM_MIN_ROWS" in env else 2 if join_mode else 32 if tw else 8
+    assert form in ("all2all", "dup_lists") or (form == "lists" and (off("LZANI_PM") or not bk)), form
+    pm = form == "all2all" and bk and window and g["key_bits"] <= 30 and n >= 2 and n_rows >= min_rows and not off("LZANI_PM")
+    use_join = join_mode and not pm
+    Lmax = max(len(s) for s in seqs)
+    split = False
+    if pm:
+        cb_words = (Lmax + p["mrd"] + 320 + 1023) // 1024 * 32
+        slots = 256 * 8 * 4                                     # wave slots of the MI355X: 256 CUs, 8 blocks of 4 waves
+        on_ = on("LZANI_SPLIT") if "LZANI_SPLIT" in env else (cb_words >= 8192 and (n_pairs * 16 <= slots or (cb_words >= 65536 and n_pairs * 8 <= slots)))
+        if on_:
+            D = Lmax + p["mrd"]
+            if int(env.get("LZANI_SPLIT_SEGLEN", 0)) > 0:
+                seglen = int(env["LZANI_SPLIT_SEGLEN"])
+            else:
+                S = min(int(env.get("LZANI_SPLIT_S", 64)), max(2, slots // n_pairs))
+                seglen = -(-D // S)
+            seglen = max(seglen, 512)
+            split = -(-D // seglen) >= 2
+    fl = tw and not join_mode and _clog2(max(g["T"], 1024)) <= int(env.get("LZANI_FILTER_MAX_BITS", 18)) and not on("LZANI_NO_FILTER")
+    blk = (not pm and tw and not join_mode and fl and pairs_per_row >= 128 and
+           (on("LZANI_BLOCK_KERNEL") if "LZANI_BLOCK_KERNEL" in env else form == "all2all"))
+    cand = 2 if pm else 1 if use_join else 0 if tw else None
+    rtc = rtc_ready and not off("LZANI_RTC") and d_fold == 0 and cand is not None
+    if pm and split:
+        return {"split nfree={} defp={} mode={}".format(nf, d_fold, m) for m in (0, 1)}
+    if rtc and not blk:
+        return {"rtc nfree={} cand={}".format(nf, cand)}
+    if pm or use_join:
+        return {PAIRS_NAME.format(1, nf, d_fold, 0, 1, cand)}
+    if blk:
+        return {"pairs_blk nfree={} defp={}".format(nf, d_probe)}
+    return {PAIRS_NAME.format(1, nf, d_probe, 0, int(tw), 0)}
+
+
+# The cells of tests/test_gpu_instantiations.py: one per name of the table (two per run-time compiled kernel: a tuple
+# inside the null chain's envelope with mal 13, one outside).  A cell = a genome set, a tuple, the LZANI_* switches that
+# force the form, and a call: "all2all", "lists" (a few queries per reference), "dup_lists" (rows of >= 128 pairs, every
+# query many times), "regions".
+INST_PARAMS = {"defaults": dict(DEFAULTS), "long": dict(DEFAULTS, mal=15, msl=9, reg=60),
+               "generic": full_params(dict(mrd=50, mqd=30, reg=40, aw=12, am=5, ar=2)),
+               "slow": full_params(dict(mal=20, msl=9, reg=40)),                    # no k-mer words
+               "rtc_chain": full_params(dict(mal=13, msl=9, reg=40)),               # null chain, stretch chain of the join form
+               "rtc_plain": full_params(dict(msl=10, mqd=20, mrd=70, aw=20, am=9, ar=2, reg=40))}
+_INST_FORM_ENV = {"bitmaps": {"LZANI_PM_MIN_ROWS": "1", "LZANI_SPLIT": "0"}, "join": {"LZANI_JOIN_MIN_BYTES": "1", "LZANI_PM": "0"},
+                  "probe": {"LZANI_PM": "0"}, "block": {"LZANI_PM": "0", "LZANI_BLOCK_KERNEL": "1"},
+                  "split": {"LZANI_PM_MIN_ROWS": "1", "LZANI_SPLIT": "1", "LZANI_SPLIT_SEGLEN": "1500", "LZANI_SPLIT_ALL": "1"}}
+
+
+def _inst_cells():
+    cells = []
+
+    def add(name, setname, prm, env, form, tag=""):
+        rtc = name.startswith("rtc ")
+        env = dict(env, **({"LZANI_RTC_MIN_PAIRS": "0"} if rtc else {"LZANI_RTC": "0"}))
+        cells.append(dict(id=name.replace(" ", "_").replace("=", "") + tag, name=name, set=setname, prm=prm, env=env, form=form))
+
+    nsuf = {0: " N", 1: ""}
+    add(PAIRS_NAME.format(0, 0, 0, 1, 0, 0), "small N", "slow", {}, "regions")
+    add(PAIRS_NAME.format(1, 0, 0, 1, 1, 0), "small N", "defaults", {}, "regions")
+    add(PAIRS_NAME.format(1, 0, 0, 1, 0, 0), "small N", "generic", {"LZANI_NO_TAGWORDS": "1"}, "regions")
+    add(PAIRS_NAME.format(0, 0, 0, 0, 0, 0), "small N", "slow", {}, "lists")
+    for nf in (0, 1):
+        for d, prm in ((0, "generic"), (1, "defaults"), (2, "long")):
+            add(PAIRS_NAME.format(1, nf, d, 0, 1, 2), ("split" if d == 2 else "small") + nsuf[nf], prm, _INST_FORM_ENV["bitmaps"], "all2all")
+            add(PAIRS_NAME.format(1, nf, d, 0, 1, 1), ("long" if d == 2 else "small") + nsuf[nf], prm, _INST_FORM_ENV["join"],
+                "lists" if d == 0 else "all2all")
+            add("split nfree={} defp={} mode=0".format(nf, d), "split" + nsuf[nf], prm, _INST_FORM_ENV["split"], "all2all")
+        for d, prm in ((0, "generic"), (1, "defaults")):
+            add(PAIRS_NAME.format(1, nf, d, 0, 1, 0), "small" + nsuf[nf], prm, _INST_FORM_ENV["probe"], "lists" if nf == d else "all2all")
+            add(PAIRS_NAME.format(1, nf, d, 0, 0, 0), "small" + nsuf[nf], prm,
+                dict(_INST_FORM_ENV["probe"], **({"LZANI_NO_TAGWORDS": "1"} if nf == 0 else {"LZANI_NO_BUCKETS": "1"})), "all2all")
+            add("pairs_blk nfree={} defp={}".format(nf, d), "small" + nsuf[nf], prm, _INST_FORM_ENV["block"], "dup_lists")
+        for cand, form in ((0, "probe"), (1, "join"), (2, "bitmaps")):
+            for prm in ("rtc_chain", "rtc_plain"):
+                setname = ("mid" if prm == "rtc_chain" and cand < 2 else "small") + nsuf[nf]
+                add("rtc nfree={} cand={}".format(nf, cand), setname, prm, _INST_FORM_ENV[form], "all2all", "_" + prm)
+    return cells
+
+
+INST_CELLS = _inst_cells()
+
+
+def kernel_names_of_cell(cell):
+    """What the cell must launch: its name; a split cell both modes of its k_split."""
+    if cell["name"].startswith("split "):
+        return {cell["name"][:-1] + "0", cell["name"][:-1] + "1"}
+    return {cell["name"]}
+
+
+def _put_n_runs(seqs):
+    """N runs at the start (genome 1), in the middle (4) and at the end (6, with one in the middle); 7 shares a family with 6:
+    a related pair with N on both sides.  The rest stay N-free: pairs of N-free genomes in a run of an NFREE=false kernel."""
+    seqs = [s.copy() for s in seqs]
+    seqs[1][:9] = 5
+    seqs[4][len(seqs[4]) // 2:len(seqs[4]) // 2 + 40] = 5
+    seqs[6][-5:] = 5
+    seqs[6][1200:1217] = 5
+    seqs[7][2000:2001] = 5
+    return seqs
+
+
+_INST_SETS = {}
+
+
+def instantiation_set(name):
+    """Genome sets of the cells: related pairs (families at 0.5-15 % divergence), unrelated pairs, one genome of 300 bp;
+    ' N' = with N runs (_put_n_runs).  small: 9 genomes of 8.5-10 kbp (tag words at mal 11 from ~8.2 kbp on); split: 8 of
+    17-25 kbp; mid: + one of 140 kbp and a relative (tag words at mal 13); long: + one of 2.2 Mbp and a relative (tag
+    words at mal 15)."""
+    if name not in _INST_SETS:
+        base, with_n = name.split(" ")[0], name.endswith(" N")
+        st = SG.Stream(4242)
+        short = (st.u64(300) % np.uint64(4)).astype(np.uint8)
+        if base == "split":
+            seqs = SG.make_set(8, 4301, lmin=17000, lmax=25000, fam=4, dmin=0.005, dmax=0.15)[1]
+        else:
+            seqs = SG.make_set(9, 4302, lmin=8500, lmax=10000, fam=3, dmin=0.005, dmax=0.15)[1]
+        if with_n:
+            seqs = _put_n_runs(seqs)
+        if base in ("mid", "long"):
+            L = 140_000 if base == "mid" else 2_200_000
+            big = (st.u64(L) % np.uint64(4)).astype(np.uint8)
+            seqs = [big, SG.mutate(big, 0.02, st)] + seqs[:8]
+            if with_n:
+                seqs[0] = seqs[0].copy()
+                seqs[0][L // 3:L // 3 + 100] = 5
+        _INST_SETS[name] = [np.ascontiguousarray(s) for s in seqs] + [short]
+    return _INST_SETS[name]
+
+
+def instantiation_rows(cell, n):
+    """(ref_ids, row_off, query_ids or None) of the cell's call (query_ids None: dense rows)."""
+    ref_ids = np.arange(n, dtype=np.uint32)
+    if cell["form"] in ("all2all", "regions"):
+        return ref_ids, np.arange(n + 1, dtype=np.uint64) * np.uint64(n - 1), None
+    if cell["form"] == "lists":
+        lists = [[(r + d) % n for d in (1, 2, 4)] for r in range(n)]
+    else:
+        lists = [[q for q in range(n) if q != r] * (128 // (n - 1) + 1) for r in range(n)]
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in lists])
+    return ref_ids, off, np.array([q for x in lists for q in x], np.uint32)
