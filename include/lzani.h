@@ -95,6 +95,36 @@ const char *lzani_last_error(const lzani_ctx *ctx);
  * Ids used below are indices into this table (the reference's reordered sequence ids). */
 int lzani_set_genomes(lzani_ctx *ctx, uint32_t n, const uint8_t *const *codes, const uint32_t *len);
 
+/* Genome sets larger than the device (out-of-core).  The genome-memory limit of a context (bytes of genome tables:
+ * packed texts, N masks, k-mer words, join lists) applies at its next lzani_set_genomes; 0 (the default) is automatic.
+ * A set that does not fit stays on the host (1 B per base) and is cut, in id order, into contiguous blocks of at most
+ * limit / 2 bytes of tables each (lzani_plan_blocks); two blocks are resident at a time, and every lzani_run_rows* call
+ * runs tile by tile over (reference block, query block) with results bit-identical to the in-core run.  Automatic
+ * mode keeps a set in-core unless its tables, its 1 B/base staging copy or one index slab do not fit the free device
+ * memory; it then applies half of the free memory as the limit.  An explicit limit below twice the footprint of the
+ * largest genome makes lzani_set_genomes fail with LZANI_ERR_ARG.  For an out-of-core set lzani_get_layout's
+ * bytes_genomes is the resident region and n_free describes the whole set; lzani_debug_get_index returns
+ * LZANI_ERR_STATE. */
+int lzani_set_genome_memory(lzani_ctx *ctx, uint64_t bytes);
+
+/* The block plan as a pure host function (no GPU): block_of[g] (may be NULL) for the n genomes of lengths len under
+ * the given limit; returns the number of blocks (limit 0: one), or LZANI_ERR_ARG / LZANI_ERR_PARAMS. */
+int lzani_plan_blocks(uint32_t n, const uint32_t *len, const lzani_params *p, uint64_t limit, uint32_t *block_of);
+
+/* Residency of the current genome set and the last run.  A run takes its reference blocks in ascending order (block
+ * i to half A: nothing to do if A holds it, the halves trade places if B holds it, else one upload), and for each its
+ * query blocks: i itself, then the block B holds, then the others ascending (one upload each unless B holds it). */
+typedef struct lzani_residency_info {
+    uint64_t limit;                 /* the genome-memory limit applied to the set (0: automatic, in-core)            */
+    uint32_t blocks;                /* 1: the whole set is resident                                                   */
+    uint32_t tiles;                 /* tiles of the last run (an in-core run: 1)                                      */
+    uint64_t block_uploads;         /* block uploads of the last run                                                  */
+    uint64_t peak_resident_bytes;   /* largest genome-table footprint resident at once (in-core: the whole set's)     */
+    uint64_t host_bytes;            /* the host copy of the set's codes; 0 when in-core                               */
+    double   upload_ms;             /* device time of the last run's block uploads (packing + k-mer words)            */
+} lzani_residency_info;
+int lzani_get_residency(const lzani_ctx *ctx, lzani_residency_info *info);
+
 /* Replaces the body of the do_matching worker (lz_matcher.cpp:196-255) for n_rows reference
  * rows given in CSR form: row k has reference ref_ids[k] and queries
  * query_ids[row_off[k] .. row_off[k+1]).  query_ids == NULL means the dense row "every id !=
@@ -224,6 +254,9 @@ int lzani_group_set_genomes(lzani_group *grp, uint32_t n, const uint8_t *const *
 int lzani_group_run_rows(lzani_group *grp, uint32_t n_rows, const uint32_t *ref_ids, const uint64_t *row_off,
                          const uint32_t *query_ids, lzani_result *out);
 int lzani_group_get_timing(const lzani_group *grp, uint32_t device_index, lzani_timing *t, double *gather_ms);
+/* lzani_set_genome_memory / lzani_get_residency for every device context of the group. */
+int lzani_group_set_genome_memory(lzani_group *grp, uint64_t bytes);
+int lzani_group_get_residency(const lzani_group *grp, uint32_t device_index, lzani_residency_info *info);
 
 /* The shard bookkeeping of lzani_group_run_rows as a pure host function (no GPU): rows keep their order inside
  * their shard, the shards follow each other in the gathered buffer (shard d from result shard_base[d] on,

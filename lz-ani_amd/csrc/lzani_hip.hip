@@ -227,6 +227,28 @@ struct lzani_ctx {
 
     void* comm = nullptr;         // ncclComm_t of lzani_comm_init (one process per GPU), lzani_multi.h
     u32 n_ranks = 1, rank = 0;
+
+    // Out-of-core genome sets (lzani_ooc.h): the set stays on the host and the runs go tile by tile over
+    // (reference block, query block).  Outside a run n / L describe the whole set; the device tables above then
+    // describe the resident region (two halves, A and B, of half_words packed words each).
+    u64 mem_req = 0;              // lzani_set_genome_memory: applies at the next lzani_set_genomes; 0 = automatic
+    u64 mem_limit = 0;            // the limit applied to the current set (0: automatic mode kept it in-core)
+    bool ooc = false;
+    std::vector<uint8_t> h_codes;                 // host copy of the set's codes, genome after genome
+    std::vector<u64> h_codeoff;
+    std::vector<int> h_hasN;                      // per genome: a code >= 4
+    std::vector<u32> blk_first;                   // block b = genomes [blk_first[b], blk_first[b + 1])
+    std::vector<u64> blk_bytes;                   // genome-table footprint of every block (ooc_genome_bytes)
+    u64 half_words = 0;                           // packed words of one half (the largest block's)
+    u32 half_genomes = 0;                         // genomes of the largest block
+    int half_block[2] = {-1, -1};                 // the block each half holds (-1: none)
+    int half_a = 0;                               // which half is A (the reference block's)
+    uint8_t* d_stage = nullptr;                   // 1 B per base of the largest block
+    u64* d_up_tab = nullptr;                      // an upload's code offsets and word offsets (2 x half_genomes)
+    int* d_up_L = nullptr;                        // ... lengths, and N flags written by k_pack (2 x half_genomes)
+    u32 res_tiles = 0;                            // residency counters of the last run (lzani_get_residency)
+    u64 res_uploads = 0, res_peak = 0;
+    double res_upload_ms = 0;
 };
 
 namespace {
@@ -274,6 +296,20 @@ void free_genomes(lzani_ctx* c)
     c->d_hasN = nullptr;
     c->d_t2 = c->d_nm = c->d_nmoff = nullptr; c->d_L = nullptr; c->d_kmL = c->d_kmS = nullptr; c->kmers_ready = false;
     c->n = 0;
+    hipFree(c->d_stage); hipFree(c->d_up_tab); hipFree(c->d_up_L);
+    c->d_stage = nullptr; c->d_up_tab = nullptr; c->d_up_L = nullptr;
+    c->ooc = false; c->mem_limit = 0;
+    std::vector<uint8_t>().swap(c->h_codes); std::vector<u64>().swap(c->h_codeoff); std::vector<int>().swap(c->h_hasN);
+    c->blk_first.clear(); c->blk_bytes.clear();
+    c->half_words = 0; c->half_genomes = 0; c->half_block[0] = c->half_block[1] = -1; c->half_a = 0;
+    c->res_tiles = 0; c->res_uploads = c->res_peak = 0; c->res_upload_ms = 0;
+}
+// (the join lists of an out-of-core run belong to one tile's local genome table: released between tiles)
+void free_join_lists(lzani_ctx* c)
+{
+    hipFree(c->d_jkeys); hipFree(c->d_jkoff); hipFree(c->d_jsoff); hipFree(c->d_jcnt);
+    c->d_jkeys = nullptr; c->d_jkoff = c->d_jsoff = nullptr; c->d_jcnt = nullptr;
+    c->join_ready = false;
 }
 void free_pm(lzani_ctx* c)
 {
@@ -290,38 +326,55 @@ void free_slabs(lzani_ctx* c)
     c->d_dirz = c->d_ent = c->d_bk = c->d_tw = c->d_status = nullptr; c->slots = 0;
 }
 
-// The form of the anchor index (bucket table, tag words) is a property of the genome set and the parameters:
-// decided once per lzani_set_genomes, so the strides of the slabs never change under an allocation.
-void choose_index_form(lzani_ctx* c)
+// Per-genome k-mer words exist for mal, msl <= 15 (the fast path).
+bool kmer_words_of(const Params& P) { return P.mal <= 15 && P.msl <= 15; }
+
+struct IndexForm { u64 bk_stride, tw_stride; bool join_mode; };
+
+// Bucket table, tag words and the join form of a genome set of n genomes with this geometry (environment overrides
+// included): what choose_index_form lays out, and what the block plan of an out-of-core set (lzani_ooc.h) counts.
+IndexForm index_form_of(const Params& P, const IndexGeom& geo, u32 n)
 {
+    IndexForm f;
     int tagbits = 0;
-    while (tagbits < 32 && ((c->geo.tagmask >> tagbits) & 1u)) ++tagbits;
-    const bool exact = c->geo.tagmask == (u32)lowmask(c->geo.kb - c->geo.dirbits);
+    while (tagbits < 32 && ((geo.tagmask >> tagbits) & 1u)) ++tagbits;
+    const bool exact = geo.tagmask == (u32)lowmask(geo.kb - geo.dirbits);
     const char* e = getenv("LZANI_NO_BUCKETS");                           // experiments / test_index_forms
     const char* mx = getenv("LZANI_BK_MAX_DIRBITS");
     const int max_dirbits = mx ? atoi(mx) : 26;
     // bucket table (+ tag words): wherever the sentinels cannot be real entries; 20 B per bucket more per slot
-    c->bk_stride = (c->d_kmL && exact && c->geo.dirbits <= max_dirbits && tagbits + c->geo.posbits <= 30 && !(e && *e == '1'))
-                       ? ((u64)4 << c->geo.dirbits) : 0;
+    f.bk_stride = (kmer_words_of(P) && exact && geo.dirbits <= max_dirbits && tagbits + geo.posbits <= 30 && !(e && *e == '1'))
+                      ? ((u64)4 << geo.dirbits) : 0;
     const char* t = getenv("LZANI_NO_TAGWORDS");
-    c->tw_stride = (c->bk_stride && tagbits <= 7 && !(t && *t == '1')) ? ((u64)1 << c->geo.dirbits) : 0;
+    f.tw_stride = (f.bk_stride && tagbits <= 7 && !(t && *t == '1')) ? ((u64)1 << geo.dirbits) : 0;
     // Join form of candidate detection: where the tag words of one reference exceed what an L2 holds by far, a random
     // probe per query position costs one HBM line each; the query's k-mer list sorted by bucket turns the probes into
     // two streams (DevWave::join).  Needs the anchor queue (tag words, seed window <= 128) and keys of 64 bits.
+    const char* nj = getenv("LZANI_NO_JOIN");
+    const char* jm = getenv("LZANI_JOIN_MIN_BYTES");
+    const u64 min_bytes = jm ? strtoull(jm, nullptr, 10) : (8ull << 20);
+    const int gbits = ceil_log2((u64)n + 1);                          // the all-ones genome number is the invalid key's
+    f.join_mode = f.tw_stride && f.tw_stride * 4 >= min_bytes && P.mqd + P.mrd <= 128 &&
+                  gbits + geo.kb + geo.posbits <= 64 && !(nj && *nj == '1');
+    return f;
+}
+
+// The form of the anchor index (bucket table, tag words) is a property of the genome set and the parameters:
+// decided once per lzani_set_genomes, so the strides of the slabs never change under an allocation.
+void choose_index_form(lzani_ctx* c)
+{
     {
-        const char* nj = getenv("LZANI_NO_JOIN");
-        const char* jm = getenv("LZANI_JOIN_MIN_BYTES");
-        const u64 min_bytes = jm ? strtoull(jm, nullptr, 10) : (8ull << 20);
-        const int gbits = ceil_log2((u64)c->n_pending + 1);          // the all-ones genome number is the invalid key's
-        c->join_mode = c->tw_stride && c->tw_stride * 4 >= min_bytes && c->P.mqd + c->P.mrd <= 128 &&
-                       gbits + c->geo.kb + c->geo.posbits <= 64 && !(nj && *nj == '1');
+        const IndexForm f = index_form_of(c->P, c->geo, c->n_pending);
+        c->bk_stride = f.bk_stride;
+        c->tw_stride = f.tw_stride;
+        c->join_mode = f.join_mode;
     }
     // Sort-based index build where the directory is beyond the LDS-staged build (2^19 buckets): keys of 64 bits with up
     // to 16 bits of slot number
     {
         const char* sm = getenv("LZANI_SORT_INDEX_MIN_DIRBITS");      // tests: 0 forces it at every size
         const char* ns = getenv("LZANI_NO_SORT_INDEX");
-        c->sort_build = c->d_kmL && c->geo.dirbits >= (sm ? atoi(sm) : 20) && c->geo.kb + c->geo.posbits <= 60 && !(ns && *ns == '1');
+        c->sort_build = kmer_words_of(c->P) && c->geo.dirbits >= (sm ? atoi(sm) : 20) && c->geo.kb + c->geo.posbits <= 60 && !(ns && *ns == '1');
     }
     // Presence filter in front of the tag-word probes (probe form only; k_pairs_blk keeps the reference's in LDS): ~3 bits
     // per text position, at most 2^18 bits (genomes up to ~128 kbp); beyond, one all-ones word passes everything
@@ -1315,6 +1368,8 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
 
 }  // namespace
 
+#include "lzani_ooc.h"
+
 extern "C" {
 
 static void comm_release(lzani_ctx* c);      // lzani_multi.h
@@ -1396,6 +1451,36 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     c->geo = index_geometry(c->Tmax, c->P.mal);
     c->dir_stride = ((u64)1 << c->geo.dirbits) + 1;
     c->ent_stride = (u64)c->Tmax;
+    c->total_nm = total_nm;
+    c->n_pending = n;
+    choose_index_form(c);
+    // Residency: the whole set in HBM (step (b) below, on every genome), or blocks of it kept on the host and uploaded by
+    // the runs (lzani_ooc.h).  Automatic mode (limit 0) keeps every set in-core that can be had in-core: its tables, the
+    // staging copy and one index slab within the free memory.
+    {
+        const bool kmers = kmer_words_of(c->P);
+        u64 limit = c->mem_req;
+        if (!limit) {
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+            if (const char* fb = getenv("LZANI_FREE_BYTES")) free_b = std::min<size_t>(free_b, (size_t)strtoull(fb, nullptr, 10));   // tests: the automatic trigger
+            const u64 tables = total_nm * (16 + 8) + (kmers ? total_nm * 64 * 8 : 0);
+            const u64 per_slot = 4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride) + (c->sort_build ? (u64)16 * c->Tmax + 16 : 0);
+            if (tables + total_codes > free_b || tables + per_slot > free_b) limit = free_b / 2;     // (half for the genomes, half for slabs and bitmaps)
+        }
+        std::vector<u64> bytes;
+        std::string msg;
+        const int nb = plan_blocks_impl(n, len, c->P, limit, c->blk_first, bytes, msg);
+        if (nb < 0) return fail(c, c->mem_req ? nb : LZANI_ERR_NOMEM, "lzani_set_genomes: " + msg);
+        if (nb > 1) {
+            c->blk_bytes = bytes;
+            c->mem_limit = limit;
+            return ooc_set_genomes(c, n, codes, len);
+        }
+        c->mem_limit = c->mem_req;
+        c->res_peak = bytes[0];
+        c->blk_first.clear();
+    }
 
     DevBuf<uint8_t> d_codes;
     DevBuf<u64> d_codeoff;
@@ -1407,13 +1492,10 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     HIPCHK(c, hipMalloc(&c->d_L, (size_t)n * 4));
     HIPCHK(c, hipMalloc(&c->d_hasN, (size_t)n * 4));
     HIPCHK(c, hipMemset(c->d_hasN, 0, (size_t)n * 4));
-    c->total_nm = total_nm;
     if (c->P.mal <= 15 && c->P.msl <= 15) {
         HIPCHK(c, hipMalloc(&c->d_kmL, total_nm * 64 * 4));
         HIPCHK(c, hipMalloc(&c->d_kmS, total_nm * 64 * 4));
     }
-    c->n_pending = n;
-    choose_index_form(c);
     // The caller's sequences are separate host buffers: they go up through two pinned 64 MB staging buffers, the
     // copy of one overlapping the fill of the other (the 4 GB of config 5 take as long as the PCIe link needs).
     {
@@ -1472,7 +1554,10 @@ int lzani_run_rows_device(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids
     if (!c) return LZANI_ERR_ARG;
     if (!ref_ids || !row_off || (!d_out && n_rows && row_off[n_rows]))
         return fail(c, LZANI_ERR_ARG, "lzani_run_rows_device: null argument");
-    return run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out);
+    if (c->ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out, nullptr, nullptr);
+    const int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out);
+    c->res_tiles = rc == LZANI_OK && n_rows && row_off[n_rows] ? 1 : 0;
+    return rc;
 }
 
 int lzani_run_rows(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids, const uint64_t* row_off,
@@ -1483,9 +1568,11 @@ int lzani_run_rows(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids, const
     const u64 n_pairs = n_rows ? row_off[n_rows] : 0;
     if (n_pairs && !out) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: null output");
     HIPCHK(c, hipSetDevice(c->dev));
+    if (c->ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, nullptr);     // (host scatter)
     DevBuf<lzani_result> d_out;
     if (n_pairs) HIPCHK(c, d_out.alloc(n_pairs));
     int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.p);
+    c->res_tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
     if (rc == LZANI_OK && n_pairs) {
         hipError_t e = hipMemcpy(out, d_out.p, n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy results: ") + hipGetErrorString(e));
@@ -1507,16 +1594,21 @@ int lzani_run_rows_regions(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_id
     DevBuf<lzani_result> d_out;
     DevBuf<lzani_region> d_regions;
     DevBuf<unsigned long long> d_count;
-    if (n_pairs) HIPCHK(c, d_out.alloc(n_pairs));
+    if (n_pairs && !c->ooc) HIPCHK(c, d_out.alloc(n_pairs));      // (out-of-core: tile by tile)
     HIPCHK(c, d_regions.alloc(capacity));
     HIPCHK(c, d_count.alloc(1));
     HIPCHK(c, hipMemset(d_count.p, 0, sizeof(unsigned long long)));
     RegionSink rs{d_regions.p, d_count.p, capacity};
-    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.p, &rs);
+    int rc;
+    if (c->ooc) rc = run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, &rs);
+    else {
+        rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.p, &rs);
+        c->res_tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
+    }
     if (rc == LZANI_OK) {
         unsigned long long cnt = 0;
         hipError_t e = hipMemcpy(&cnt, rs.d_count, sizeof cnt, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && n_pairs) e = hipMemcpy(out, d_out.p, n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && n_pairs && !c->ooc) e = hipMemcpy(out, d_out.p, n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e == hipSuccess && cnt && capacity)
             e = hipMemcpy(regions, rs.d_regions, std::min<uint64_t>(cnt, capacity) * sizeof(lzani_region), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy regions: ") + hipGetErrorString(e));
@@ -1569,6 +1661,41 @@ int lzani_debug_kernel_launches(const lzani_ctx* c, uint64_t* counts, uint32_t c
     return (int)PK_COUNT;
 }
 
+int lzani_set_genome_memory(lzani_ctx* c, uint64_t bytes)
+{
+    if (!c) return LZANI_ERR_ARG;
+    c->mem_req = bytes;
+    return LZANI_OK;
+}
+
+int lzani_plan_blocks(uint32_t n, const uint32_t* len, const lzani_params* p, uint64_t limit, uint32_t* block_of)
+{
+    if (!p || !len || !n) return LZANI_ERR_ARG;
+    Params P{p->min_anchor_len, p->min_seed_len, p->max_dist_in_ref, p->max_dist_in_query,
+             p->min_region_len, p->approx_window, p->approx_mismatches, p->approx_run_len};
+    if (!params_supported(P)) return LZANI_ERR_PARAMS;
+    std::vector<u32> first;
+    std::vector<u64> bytes;
+    std::string msg;
+    const int nb = plan_blocks_impl(n, len, P, limit, first, bytes, msg);
+    if (nb > 0 && block_of)
+        for (int b = 0; b < nb; ++b) std::fill(block_of + first[b], block_of + first[b + 1], (uint32_t)b);
+    return nb;
+}
+
+int lzani_get_residency(const lzani_ctx* c, lzani_residency_info* o)
+{
+    if (!c || !o) return LZANI_ERR_ARG;
+    o->limit = c->mem_limit;
+    o->blocks = c->ooc ? (uint32_t)c->blk_first.size() - 1 : (c->n ? 1u : 0u);
+    o->tiles = c->res_tiles;
+    o->block_uploads = c->res_uploads;
+    o->peak_resident_bytes = c->res_peak;
+    o->host_bytes = c->h_codes.size();
+    o->upload_ms = c->res_upload_ms;
+    return LZANI_OK;
+}
+
 const char* lzani_debug_kernel_name(uint32_t id)
 {
     return id < (u32)PK_COUNT ? PAIR_KERNELS[id].name : nullptr;
@@ -1591,6 +1718,7 @@ int lzani_debug_get_index(lzani_ctx* c, uint32_t id, uint64_t* t2, uint64_t* nm,
 {
     if (!c) return LZANI_ERR_ARG;
     if (!c->n || id >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_debug_get_index: bad id");
+    if (c->ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_get_index: the genome is not resident (out-of-core set)");
     HIPCHK(c, hipSetDevice(c->dev));
     int rc = ensure_slabs(c, 1);
     if (rc) return rc;

@@ -459,6 +459,19 @@ int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_id
     return ret;
 }
 
+int lzani_group_set_genome_memory(lzani_group* g, uint64_t bytes)
+{
+    if (!g) return LZANI_ERR_ARG;
+    for (auto c : g->ctx) lzani_set_genome_memory(c, bytes);
+    return LZANI_OK;
+}
+
+int lzani_group_get_residency(const lzani_group* g, uint32_t device_index, lzani_residency_info* info)
+{
+    if (!g || device_index >= g->ctx.size() || !info) return LZANI_ERR_ARG;
+    return lzani_get_residency(g->ctx[device_index], info);
+}
+
 int lzani_group_get_timing(const lzani_group* g, uint32_t device_index, lzani_timing* t, double* gather_ms)
 {
     if (!g || device_index >= g->ctx.size() || !t) return LZANI_ERR_ARG;

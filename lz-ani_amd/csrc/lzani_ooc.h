@@ -1,0 +1,353 @@
+// lzani_ooc.h -- genome sets larger than the device: the block plan, block uploads and the tiled run.  Included by
+// lzani_hip.hip only, after run_rows_impl, which every tile calls unchanged.
+//
+// A set whose genome tables (packed texts, N masks, k-mer words, join lists) do not fit a genome-memory limit stays on
+// the host (1 B per base).  Its genomes are cut, in id order, into contiguous blocks of at most limit / 2 bytes of
+// tables each; the device holds two of them at a time, half A (the reference block) and half B (a query block).
+// A run goes tile by tile over (reference block i, query block j): each tile is a run_rows_impl call on a local genome
+// table of A's genomes (local ids 0 .. nA-1) and B's (nA ..), and its results are scattered to their CSR positions.
+//
+// Order of a run (what lzani_get_residency counts, and what a caller can predict):
+//   reference blocks ascending, those with rows only; block i goes to A -- no upload if A holds it, the two halves
+//   trade places if B holds it, else one upload;
+//   then its query blocks: i itself first (its queries are in A), then the block B holds if it has pairs of these rows,
+//   then the others ascending; every block that B does not hold yet is one upload.
+// The halves keep their blocks from run to run; lzani_set_genomes empties them.
+#pragma once
+
+namespace {
+
+// Results of a tile (local CSR order) -> their places in the caller's CSR order: pos[e] for the tile's pair e.
+__global__ void k_scatter_pairs(const int* __restrict__ src, int* __restrict__ dst, const u64* __restrict__ pos, u64 n)
+{
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const u64 d = 3 * pos[e];
+    dst[d] = src[3 * e];
+    dst[d + 1] = src[3 * e + 1];
+    dst[d + 2] = src[3 * e + 2];
+}
+
+// Region records of a tile: `pair` is the tile's CSR position; it becomes the caller's.
+__global__ void k_remap_regions(lzani_region* __restrict__ r, u64 n, const u64* __restrict__ pos)
+{
+    const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) r[k].pair = pos[r[k].pair];
+}
+
+// Genome-table footprint of one genome: the bytes_genomes formula of lzani_get_layout (packed text 16 B + N mask 8 B
+// per word, k-mer words 2 x 4 B per text position) plus its join lists where they apply (8 B per forward position for
+// the sorted keys, 20 B of offsets and counts).
+u64 ooc_genome_bytes(int L, const Params& P, bool kmers, bool join)
+{
+    const u64 w = text_wordsN(ref_text_len(L, P.mrd));
+    return w * (16 + 8) + (kmers ? w * 64 * 8 : 0) + (join ? (u64)L * 8 + 20 : 0);
+}
+
+// The block plan (lzani_plan_blocks): genomes in id order into contiguous blocks of at most limit / 2 bytes each.
+// first[b] .. first[b + 1] are block b's genomes, bytes[b] its footprint.  limit 0: one block.  Returns the number of
+// blocks, or LZANI_ERR_ARG with the reason in msg.
+int plan_blocks_impl(u32 n, const u32* len, const Params& P, u64 limit, std::vector<u32>& first, std::vector<u64>& bytes,
+                     std::string& msg)
+{
+    if (!n || !len) { msg = "lzani_plan_blocks: empty input"; return LZANI_ERR_ARG; }
+    int Lmax = 0;
+    for (u32 g = 0; g < n; ++g) {
+        if (len[g] > 0x3FFFFFFFu - 3u * (u32)P.mrd) { msg = "sequence too long for 32-bit text positions"; return LZANI_ERR_ARG; }
+        Lmax = std::max(Lmax, (int)len[g]);
+    }
+    const int Tmax = ref_text_len(Lmax, P.mrd);
+    const IndexForm f = index_form_of(P, index_geometry(Tmax, P.mal), n);
+    const bool kmers = kmer_words_of(P);
+    u64 fmax = 0, total = 0;
+    for (u32 g = 0; g < n; ++g) {
+        const u64 b = ooc_genome_bytes((int)len[g], P, kmers, f.join_mode);
+        fmax = std::max(fmax, b);
+        total += b;
+    }
+    first.assign(1, 0);
+    bytes.clear();
+    if (limit == 0) { first.push_back(n); bytes.push_back(total); return 1; }
+    if (fmax > limit / 2) {
+        msg = "genome-memory limit of " + std::to_string(limit) + " bytes is below the minimum of " + std::to_string(2 * fmax) +
+              " bytes (each of the two resident halves must hold the largest genome's tables, " + std::to_string(fmax) + " bytes)";
+        return LZANI_ERR_ARG;
+    }
+    u64 cur = 0;
+    for (u32 g = 0; g < n; ++g) {
+        const u64 b = ooc_genome_bytes((int)len[g], P, kmers, f.join_mode);
+        if (g > first.back() && cur + b > limit / 2) { first.push_back(g); bytes.push_back(cur); cur = 0; }
+        cur += b;
+    }
+    first.push_back(n);
+    bytes.push_back(cur);
+    return (int)bytes.size();
+}
+
+// Step (b) of lzani_set_genomes for an out-of-core set: block b from the host copy into half h -- staging, k_pack and
+// k_kmers on the block's genomes only.  Timed into res_upload_ms.
+int ooc_upload(lzani_ctx* c, u32 b, int h)
+{
+    c->half_block[h] = -1;                                     // (until the upload is complete)
+    const u32 g0 = c->blk_first[b], g1 = c->blk_first[b + 1], cnt = g1 - g0, hg = c->half_genomes;
+    const u64 bases = c->h_codeoff[g1] - c->h_codeoff[g0];
+    std::vector<u64> tab((size_t)2 * hg, 0);
+    std::vector<int> Ls((size_t)2 * hg, 0);                    // lengths, then the N flags k_pack sets
+    int Lmax = 0;
+    for (u32 g = g0; g < g1; ++g) {
+        tab[g - g0] = c->h_codeoff[g] - c->h_codeoff[g0];
+        tab[hg + g - g0] = (u64)h * c->half_words + (c->nmoff[g] - c->nmoff[g0]);
+        Ls[g - g0] = c->L[g];
+        Lmax = std::max(Lmax, c->L[g]);
+    }
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIPCHK(c, hipEventCreate(&ev[0]));
+    hipError_t e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    if (e == hipSuccess && bases) e = hipMemcpyAsync(c->d_stage, c->h_codes.data() + c->h_codeoff[g0], bases, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_up_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_up_L, Ls.data(), Ls.size() * 4, hipMemcpyHostToDevice, c->stream);
+    const int Tb = ref_text_len(Lmax, c->P.mrd);
+    const size_t maxblk = text_wordsN(Tb);
+    for (u32 k0 = 0; e == hipSuccess && k0 < cnt; k0 += 32768) {   // gridDim.y is limited to 65535
+        const u32 k = std::min<u32>(32768, cnt - k0);
+        hipLaunchKernelGGL(k_pack, dim3((u32)((maxblk + 127) / 128), k), dim3(128), 0, c->stream,
+                           c->d_stage, c->d_up_tab + k0, c->d_t2, c->d_nm, c->d_up_tab + hg + k0, c->d_up_L + k0, c->d_up_L + hg + k0, c->P.mrd, k);
+        if (c->d_kmL) {
+            GenomeTab G{c->d_t2, c->d_nm, c->d_up_tab + hg + k0, c->d_up_L + k0, c->d_kmL, c->d_kmS, c->d_up_L + hg + k0};
+            hipLaunchKernelGGL(k_kmers, dim3((Tb + 255) / 256, k), dim3(256), 0, c->stream, G, c->d_kmL, c->d_kmS, c->P.mal, c->P.msl, c->P.mrd, Tb);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);          // (also: tab and Ls leave scope)
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    hipEventDestroy(ev[0]);
+    if (ev[1]) hipEventDestroy(ev[1]);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE, std::string("block upload: ") + hipGetErrorString(e));
+    c->res_upload_ms += ms;
+    c->res_uploads += 1;
+    c->half_block[h] = (int)b;
+    return LZANI_OK;
+}
+
+// A device buffer of a run that grows as its tiles need.
+struct GrowBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf&) = delete;
+    GrowBuf& operator=(const GrowBuf&) = delete;
+    ~GrowBuf() { if (p) (void)hipFree(p); }
+    hipError_t need(size_t b)
+    {
+        if (b <= bytes) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+        const hipError_t e = hipMalloc(&p, b);
+        if (e == hipSuccess) bytes = b;
+        return e;
+    }
+};
+
+// The context's genome count and lengths are the tile's local table for the duration of one tile.
+struct LocalTable {
+    lzani_ctx* c;
+    u32 n_all;
+    std::vector<int> L_all;
+    LocalTable(lzani_ctx* c_, std::vector<int>& L_loc) : c(c_), n_all(c_->n) { L_all.swap(c->L); c->L.swap(L_loc); c->n = (u32)c->L.size(); }
+    ~LocalTable() { c->L.swap(L_all); c->n = n_all; }
+};
+
+// The tiled run: the contract of run_rows_impl, with the results written to d_out (device, caller's CSR order) and / or
+// h_out (host), regions to rs with `pair` in the caller's CSR order.
+int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
+                   int* d_out, lzani_result* h_out, const RegionSink* rs)
+{
+    const u32 n = c->n;
+    c->tm = lzani_timing{};
+    c->batches_last_run = 0;
+    c->blk_launches = c->pm_launches = c->lpt_launches = c->pmfi_launches = c->split_launches = c->rtc_launches = 0;
+    c->split_items = 0;
+    std::fill(c->klaunch, c->klaunch + PK_COUNT, (u64)0);
+    c->res_tiles = 0; c->res_uploads = 0; c->res_peak = 0; c->res_upload_ms = 0;
+    if (n_rows == 0) return LZANI_OK;
+    for (u32 k = 0; k < n_rows; ++k) {
+        if (ref_ids[k] >= n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: reference id out of range");
+        if (row_off[k + 1] < row_off[k]) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off not monotone");
+        if (!query_ids && row_off[k + 1] - row_off[k] != (u64)n - 1) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: dense row must have n-1 queries");
+    }
+    if (row_off[0] != 0) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off[0] must be 0");
+    const u64 n_pairs = row_off[n_rows];
+    if (query_ids)
+        for (u64 e = 0; e < n_pairs; ++e) if (query_ids[e] >= n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: query id out of range");
+    if (n_pairs == 0) return LZANI_OK;
+    HIPCHK(c, hipSetDevice(c->dev));
+
+    const u32 nb = (u32)c->blk_first.size() - 1;
+    std::vector<u32> bof(n);
+    for (u32 b = 0; b < nb; ++b) std::fill(bof.begin() + c->blk_first[b], bof.begin() + c->blk_first[b + 1], b);
+    std::vector<std::vector<u32>> rows_of(nb);
+    for (u32 k = 0; k < n_rows; ++k) if (row_off[k + 1] > row_off[k]) rows_of[bof[ref_ids[k]]].push_back(k);
+
+    lzani_timing tot{};
+    u64 kl[PK_COUNT] = {};
+    u32 batches = 0;
+    int blk = 0, pmc = 0, lpt = 0, pmfi = 0, split = 0, rtc = 0;
+    u64 split_items = 0, reg_done = 0;
+    GrowBuf d_res, d_pos;
+    std::vector<lzani_result> h_res;
+    struct Tile { std::vector<u32> rows; std::vector<u64> off; std::vector<u32> q; std::vector<u64> pos; };
+    std::vector<Tile> tiles(nb);
+    for (u32 i = 0; i < nb; ++i) {
+        if (rows_of[i].empty()) continue;
+        for (auto& t : tiles) { t.rows.clear(); t.off.clear(); t.q.clear(); t.pos.clear(); }
+        for (u32 k : rows_of[i]) {
+            const u32 r = ref_ids[k];
+            for (u64 e = row_off[k]; e < row_off[k + 1]; ++e) {
+                const u64 x = e - row_off[k];
+                const u32 q = query_ids ? query_ids[e] : (u32)(x < r ? x : x + 1);
+                Tile& t = tiles[bof[q]];
+                if (t.rows.empty() || t.rows.back() != k) { t.rows.push_back(k); t.off.push_back(t.q.size()); }
+                t.q.push_back(q);
+                t.pos.push_back(e);
+            }
+        }
+        // block i into A
+        if (c->half_block[c->half_a] != (int)i) {
+            if (c->half_block[c->half_a ^ 1] == (int)i) c->half_a ^= 1;
+            else { int rc = ooc_upload(c, i, c->half_a); if (rc) return rc; }
+        }
+        std::vector<u32> order;
+        if (!tiles[i].q.empty()) order.push_back(i);
+        const int held = c->half_block[c->half_a ^ 1];
+        if (held >= 0 && held != (int)i && !tiles[held].q.empty()) order.push_back((u32)held);
+        for (u32 j = 0; j < nb; ++j) if (j != i && (int)j != held && !tiles[j].q.empty()) order.push_back(j);
+        for (u32 j : order) {
+            const int hA = c->half_a, hB = c->half_a ^ 1;
+            if (j != i && c->half_block[hB] != (int)j) { int rc = ooc_upload(c, j, hB); if (rc) return rc; }
+            c->res_peak = std::max<u64>(c->res_peak, c->blk_bytes[i] + (c->half_block[hB] >= 0 ? c->blk_bytes[c->half_block[hB]] : 0));
+            Tile& t = tiles[j];
+            // the local genome table: A's genomes, then B's (unless the queries are A's own)
+            const u32 a0 = c->blk_first[i], nA = c->blk_first[i + 1] - a0;
+            const u32 b0 = c->blk_first[j], nB = j == i ? 0 : c->blk_first[j + 1] - b0;
+            std::vector<int> Lloc((size_t)nA + nB), hasN((size_t)nA + nB);
+            std::vector<u64> nmoff((size_t)nA + nB);
+            for (u32 g = 0; g < nA; ++g) {
+                Lloc[g] = c->L[a0 + g]; hasN[g] = c->h_hasN[a0 + g];
+                nmoff[g] = (u64)hA * c->half_words + (c->nmoff[a0 + g] - c->nmoff[a0]);
+            }
+            for (u32 g = 0; g < nB; ++g) {
+                Lloc[nA + g] = c->L[b0 + g]; hasN[nA + g] = c->h_hasN[b0 + g];
+                nmoff[nA + g] = (u64)hB * c->half_words + (c->nmoff[b0 + g] - c->nmoff[b0]);
+            }
+            const u32 lrows = (u32)t.rows.size();
+            const u64 tp = t.q.size();
+            std::vector<u32> lref(lrows), lq(tp);
+            t.off.push_back(tp);
+            for (u32 k = 0; k < lrows; ++k) lref[k] = ref_ids[t.rows[k]] - a0;
+            for (u64 e = 0; e < tp; ++e) lq[e] = j == i ? t.q[e] - a0 : nA + (t.q[e] - b0);
+            HIPCHK(c, hipMemcpyAsync(c->d_L, Lloc.data(), Lloc.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_hasN, hasN.data(), hasN.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_nmoff, nmoff.data(), nmoff.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, d_res.need(tp * sizeof(lzani_result)));
+            if (d_out || rs) {
+                HIPCHK(c, d_pos.need(tp * 8));
+                HIPCHK(c, hipMemcpyAsync(d_pos.p, t.pos.data(), tp * 8, hipMemcpyHostToDevice, c->stream));
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));            // (Lloc moves into the context below)
+            if (c->join_mode) free_join_lists(c);                   // (made again for this tile's table, if its form needs them)
+            int rc;
+            {
+                LocalTable lt(c, Lloc);
+                rc = run_rows_impl(c, lrows, lref.data(), t.off.data(), lq.data(), (int*)d_res.p, rs);
+                if (c->join_mode) free_join_lists(c);
+            }
+            if (rc) return rc;
+            c->res_tiles += 1;
+            tot.index_ms += c->tm.index_ms; tot.pairs_ms += c->tm.pairs_ms; tot.cand_ms += c->tm.cand_ms; tot.kmers_ms += c->tm.kmers_ms;
+            tot.pair_launches += c->tm.pair_launches; tot.index_launches += c->tm.index_launches; tot.cand_launches += c->tm.cand_launches;
+            tot.pairs += c->tm.pairs;
+            for (int x = 0; x < PK_COUNT; ++x) kl[x] += c->klaunch[x];
+            batches += c->batches_last_run; blk += c->blk_launches; pmc += c->pm_launches; lpt += c->lpt_launches;
+            pmfi += c->pmfi_launches; split += c->split_launches; rtc += c->rtc_launches; split_items += c->split_items;
+            if (d_out) {
+                hipLaunchKernelGGL(k_scatter_pairs, dim3((u32)((tp + 255) / 256)), dim3(256), 0, c->stream, (const int*)d_res.p, d_out, (const u64*)d_pos.p, tp);
+                HIPCHK(c, hipGetLastError());
+            }
+            if (h_out) {
+                h_res.resize(tp);
+                HIPCHK(c, hipMemcpyAsync(h_res.data(), d_res.p, tp * sizeof(lzani_result), hipMemcpyDeviceToHost, c->stream));
+            }
+            if (rs) {
+                unsigned long long cnt = 0;
+                HIPCHK(c, hipMemcpyAsync(&cnt, rs->d_count, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                const u64 lo = std::min<u64>(reg_done, rs->capacity), hi = std::min<u64>(cnt, rs->capacity);
+                if (hi > lo) {
+                    hipLaunchKernelGGL(k_remap_regions, dim3((u32)((hi - lo + 255) / 256)), dim3(256), 0, c->stream, rs->d_regions + lo, hi - lo, (const u64*)d_pos.p);
+                    HIPCHK(c, hipGetLastError());
+                }
+                reg_done = cnt;
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));            // (the host tables of the tile leave scope)
+            if (h_out) for (u64 e = 0; e < tp; ++e) h_out[t.pos[e]] = h_res[e];
+        }
+    }
+    c->tm = tot;
+    std::copy(kl, kl + PK_COUNT, c->klaunch);
+    c->batches_last_run = batches;
+    c->blk_launches = blk; c->pm_launches = pmc; c->lpt_launches = lpt; c->pmfi_launches = pmfi;
+    c->split_launches = split; c->rtc_launches = rtc; c->split_items = split_items;
+    TRACE("out-of-core run: %u tiles, %llu block uploads (%.1f ms)", c->res_tiles, (unsigned long long)c->res_uploads, c->res_upload_ms);
+    return LZANI_OK;
+}
+
+// lzani_set_genomes, step (b) deferred: an out-of-core set keeps a host copy of its codes and the device region of the
+// two halves; the blocks are uploaded by the runs.
+int ooc_set_genomes(lzani_ctx* c, u32 n, const uint8_t* const* codes, const uint32_t* len)
+{
+    const u32 nb = (u32)c->blk_first.size() - 1;
+    try {
+        c->h_codeoff.assign((size_t)n + 1, 0);
+        for (u32 g = 0; g < n; ++g) c->h_codeoff[g + 1] = c->h_codeoff[g] + len[g];
+        c->h_codes.resize(c->h_codeoff[n]);
+        c->h_hasN.assign(n, 0);
+    } catch (const std::bad_alloc&) {
+        return fail(c, LZANI_ERR_NOMEM, "lzani_set_genomes: host copy of an out-of-core genome set");
+    }
+    for (u32 g = 0; g < n; ++g) {
+        if (len[g]) memcpy(c->h_codes.data() + c->h_codeoff[g], codes[g], len[g]);
+        c->h_hasN[g] = std::any_of(codes[g], codes[g] + len[g], [](uint8_t v) { return v >= 4; });
+    }
+    c->all_nfree = std::none_of(c->h_hasN.begin(), c->h_hasN.end(), [](int v) { return v != 0; });
+    u64 max_bases = 0;
+    for (u32 b = 0; b < nb; ++b) {
+        const u32 g0 = c->blk_first[b], g1 = c->blk_first[b + 1];
+        c->half_words = std::max<u64>(c->half_words, (g1 < n ? c->nmoff[g1] : c->total_nm) - c->nmoff[g0]);
+        c->half_genomes = std::max<u32>(c->half_genomes, g1 - g0);
+        max_bases = std::max<u64>(max_bases, c->h_codeoff[g1] - c->h_codeoff[g0]);
+    }
+    const u64 hw = c->half_words, hg = c->half_genomes;
+    HIPCHK(c, hipMalloc(&c->d_t2, 2 * hw * 16));
+    HIPCHK(c, hipMalloc(&c->d_nm, 2 * hw * 8));
+    if (kmer_words_of(c->P)) {
+        HIPCHK(c, hipMalloc(&c->d_kmL, 2 * hw * 64 * 4));
+        HIPCHK(c, hipMalloc(&c->d_kmS, 2 * hw * 64 * 4));
+    }
+    HIPCHK(c, hipMalloc(&c->d_nmoff, 2 * hg * 8));
+    HIPCHK(c, hipMalloc(&c->d_L, 2 * hg * 4));
+    HIPCHK(c, hipMalloc(&c->d_hasN, 2 * hg * 4));
+    HIPCHK(c, hipMalloc(&c->d_stage, std::max<u64>(max_bases, 1)));
+    HIPCHK(c, hipMalloc(&c->d_up_tab, 2 * hg * 8));
+    HIPCHK(c, hipMalloc(&c->d_up_L, 2 * hg * 4));
+    c->total_nm = 2 * hw;                                          // (lzani_get_layout: the resident region's bytes)
+    c->kmers_ready = true;                                         // (made by every block upload)
+    c->ooc = true;
+    c->n = n;
+    TRACE("set_genomes: out-of-core, n=%u blocks=%u limit=%llu half=%llu words", n, nb, (unsigned long long)c->mem_limit, (unsigned long long)hw);
+    return LZANI_OK;
+}
+
+}  // namespace

@@ -5,7 +5,8 @@
 //   load sequences -> load filter -> check names -> reorder -> LZ matching -> store results.
 // The matching stage is one call per GPU into the C-ABI of include/lzani.h (liblzani_hip.so, loaded
 // with dlopen so that this binary builds and its ingest/emit code is testable without ROCm present).
-// Extras over the reference: --gpus <n> (rows dealt cyclically over n GPUs), --device <id>,
+// Extras over the reference: --gpus <n> (rows dealt cyclically over n GPUs), --device <id>, --gpu-mem <size>
+// (genome-memory limit per GPU: larger sets run out-of-core, in tiles of genome blocks),
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
 #include <dlfcn.h>
 
@@ -39,6 +40,7 @@ struct Params {
     uint64_t flt_mask = 0;
     double flt_vals[16] = {0};
     int gpus = 1, device = 0;
+    uint64_t gpu_mem = 0;                                   // --gpu-mem: genome-memory limit per GPU (0: automatic)
     string results_out, results_in;
 };
 
@@ -59,6 +61,28 @@ static string parse_output_format(const string& of)          // params.h:169-198
         P.comps.push_back(p->second);
     }
     return "";
+}
+
+// --gpu-mem: bytes, with an optional K, M or G suffix (powers of 1024); false for anything else
+static bool parse_size(const string& v, uint64_t& out)
+{
+    size_t k = 0;
+    uint64_t x = 0;
+    while (k < v.size() && isdigit((unsigned char)v[k])) {
+        const uint64_t d = (uint64_t)(v[k++] - '0');
+        if (x > (UINT64_MAX - d) / 10) return false;
+        x = x * 10 + d;
+    }
+    if (k == 0) return false;
+    int shift = 0;
+    if (k + 1 == v.size()) {
+        const char u = (char)toupper((unsigned char)v[k]);
+        shift = u == 'K' ? 10 : u == 'M' ? 20 : u == 'G' ? 30 : -1;
+        if (shift < 0) return false;
+    } else if (k != v.size()) return false;
+    if (shift && x > (UINT64_MAX >> shift)) return false;
+    out = x << shift;
+    return true;
 }
 
 static void usage()
@@ -99,6 +123,8 @@ static void usage()
          << "  -t, --threads <int>            - no of host threads; 0 means auto-detect (default: 0)\n"
          << "  -V, --verbose <int>            - verbosity level (default: 1)\n"
          << "      --gpus <int>               - number of GPUs to shard the reference rows over (default: 1)\n"
+         << "      --gpu-mem <size>           - genome-memory limit per GPU in bytes, suffix K/M/G allowed; larger genome sets\n"
+         << "                                   stay in host memory and run in tiles of genome blocks (default: 0 = automatic)\n"
          << "      --device <int>             - first HIP device ordinal (default: 0)\n";
 }
 
@@ -167,6 +193,13 @@ static bool parse_params(int argc, char** argv)
             if (!parse_bool(argv[i + 1], P.in_percent)) { cerr << "Unknown value for --out-in-percent: " << argv[1] << endl; return false; }
             i += 2;
         } else if (par == "--gpus" && has(1)) { P.gpus = max(1, atoi(argv[i + 1])); i += 2; }
+        else if (par == "--gpu-mem" && has(1)) {
+            if (!parse_size(argv[i + 1], P.gpu_mem)) {
+                cerr << "Invalid value for --gpu-mem: " << argv[i + 1] << " (bytes, with an optional K, M or G suffix)" << endl;
+                exit(1);
+            }
+            i += 2;
+        }
         else if (par == "--device" && has(1)) { P.device = atoi(argv[i + 1]); i += 2; }
         else if (par == "--results-out" && has(1)) { P.results_out = argv[i + 1]; i += 2; }
         else if (par == "--results-in" && has(1)) { P.results_in = argv[i + 1]; i += 2; }
@@ -235,6 +268,10 @@ struct Engine {
     int (*group_set_genomes)(lzani_group*, uint32_t, const uint8_t* const*, const uint32_t*) = nullptr;
     int (*group_run_rows)(lzani_group*, uint32_t, const uint32_t*, const uint64_t*, const uint32_t*, lzani_result*) = nullptr;
     int (*group_get_timing)(const lzani_group*, uint32_t, lzani_timing*, double*) = nullptr;
+    int (*set_genome_memory)(lzani_ctx*, uint64_t) = nullptr;
+    int (*get_residency)(const lzani_ctx*, lzani_residency_info*) = nullptr;
+    int (*group_set_genome_memory)(lzani_group*, uint64_t) = nullptr;
+    int (*group_get_residency)(const lzani_group*, uint32_t, lzani_residency_info*) = nullptr;
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -250,12 +287,23 @@ struct Engine {
         BIND(create) BIND(destroy) BIND(last_error) BIND(set_genomes) BIND(get_timing) BIND(run_rows_regions)
         BIND(row_costs) BIND(partition_rows)
         BIND(group_create) BIND(group_destroy) BIND(group_last_error) BIND(group_set_genomes) BIND(group_run_rows) BIND(group_get_timing)
+        BIND(set_genome_memory) BIND(get_residency) BIND(group_set_genome_memory) BIND(group_get_residency)
 #undef BIND
         return true;
     }
 };
 
 struct AlnRegion { uint32_t ref, qry; lzani_region r; };
+
+// -V 2 with --gpu-mem or an out-of-core set: how the genome set of a device was held (lzani_get_residency); a tiled
+// all2all passes its sums over its calls
+static void print_residency(int dev, const lzani_residency_info& r, uint64_t tiles, uint64_t uploads, double upload_ms)
+{
+    if (!P.gpu_mem && r.blocks <= 1) return;
+    cerr << "genome set on device " << dev << ": " << (r.blocks > 1 ? "out-of-core" : "in-core") << ", " << r.blocks << " block(s), " << tiles
+         << " tile(s), " << uploads << " block upload(s), upload " << upload_ms << " ms, limit " << r.limit << " bytes, peak resident "
+         << r.peak_resident_bytes << " bytes\n";
+}
 
 // store_alignment (lz_matcher.cpp:102-169): one BLAST-tab-like row per region; rows of one pair in
 // calc_regions order (length desc, seq_start asc), pairs in (reference, query) order.
@@ -335,6 +383,7 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
             return false;
         }
         const auto t_b = chrono::steady_clock::now();
+        E.group_set_genome_memory(grp, P.gpu_mem);
         rc = E.group_set_genomes(grp, n, ptr.data(), len.data());
         const auto t_c = chrono::steady_clock::now();
         if (rc == LZANI_OK) rc = E.group_run_rows(grp, n, ref_ids.data(), T.row_off.data(), qids, T.res.data());
@@ -349,6 +398,8 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
                     cerr << "GPU " << devs[d] << ": " << t.pairs << " pairs, index " << t.index_ms << " ms, k-mer words " << t.kmers_ms
                          << " ms, candidate stage " << t.cand_ms << " ms, pair kernel " << t.pairs_ms << " ms"
                          << (d == 0 && devs.size() > 1 ? ", gather " + to_string(gather) + " ms" : string()) << "\n";
+                lzani_residency_info ri;
+                if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) print_residency(devs[d], ri, ri.tiles, ri.block_uploads, ri.upload_ms);
             }
         E.group_destroy(grp);
         return true;
@@ -368,6 +419,7 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
         lzani_ctx* ctx = nullptr;
         int rc = E.create(&P.lz, P.device + d, &ctx);
         if (rc != LZANI_OK) { errs[d] = "lzani_create failed with code " + to_string(rc) + (rc == LZANI_ERR_PARAMS ? " (LZ parameters outside the supported envelope)" : ""); return; }
+        E.set_genome_memory(ctx, P.gpu_mem);
         rc = E.set_genomes(ctx, n, ptr.data(), len.data());
         vector<uint32_t> rows, query_ids;
         vector<uint64_t> row_off(1, 0);
@@ -402,6 +454,8 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
                 if (E.get_timing(ctx, &t) == LZANI_OK)
                     cerr << "GPU " << P.device + d << ": " << t.pairs << " pairs, index " << t.index_ms << " ms, k-mer words " << t.kmers_ms
                          << " ms, candidate stage " << t.cand_ms << " ms, pair kernel " << t.pairs_ms << " ms\n";
+                lzani_residency_info ri;
+                if (E.get_residency(ctx, &ri) == LZANI_OK) print_residency(P.device + d, ri, ri.tiles, ri.block_uploads, ri.upload_ms);
             }
         }
         E.destroy(ctx);
@@ -442,6 +496,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         cerr << "LZ matching failed: lzani_group_create failed with code " << rc << ": " << E.group_last_error(nullptr) << endl;
         return false;
     }
+    E.group_set_genome_memory(grp, P.gpu_mem);
     rc = E.group_set_genomes(grp, n, ptr.data(), len.data());
     if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; E.group_destroy(grp); return false; }
 
@@ -465,7 +520,8 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         }
     });
     vector<double> t_index(devs.size(), 0), t_pairs(devs.size(), 0), t_cand(devs.size(), 0);
-    vector<uint64_t> n_pairs(devs.size(), 0);
+    vector<uint64_t> n_pairs(devs.size(), 0), r_tiles(devs.size(), 0), r_uploads(devs.size(), 0);
+    vector<double> r_upload_ms(devs.size(), 0);
     double t_gather = 0;
     // Three sets of buffers: while the GPUs run block k, one host thread lays out the row lists of block k + 1 and another
     // moves the results of block k - 1 into the table and hands its rows to the emitter.
@@ -511,6 +567,8 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
                     t_index[d] += t.index_ms; t_pairs[d] += t.pairs_ms; t_cand[d] += t.cand_ms + t.kmers_ms; n_pairs[d] += t.pairs;
                     if (d == 0) t_gather += gather;
                 }
+                lzani_residency_info ri;
+                if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) { r_tiles[d] += ri.tiles; r_uploads[d] += ri.block_uploads; r_upload_ms[d] += ri.upload_ms; }
             }
         }
         if (f_build.valid()) f_build.get();
@@ -525,6 +583,10 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         for (size_t d = 0; d < devs.size(); ++d)
             cerr << "GPU " << devs[d] << ": " << n_pairs[d] << " pairs, index " << t_index[d] << " ms, k-mer words + candidate stage " << t_cand[d]
                  << " ms, pair kernel " << t_pairs[d] << " ms" << (d == 0 && devs.size() > 1 ? ", gather " + to_string(t_gather) + " ms" : string()) << "\n";
+        for (size_t d = 0; d < devs.size(); ++d) {
+            lzani_residency_info ri;
+            if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) print_residency(devs[d], ri, r_tiles[d], r_uploads[d], r_upload_ms[d]);
+        }
     }
     emitter.join();
     E.group_destroy(grp);

@@ -31,7 +31,9 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_row_costs", "lzani_partition_rows", "lzani_comm_unique_id", "lzani_comm_init", "lzani_comm_allgather",
            "lzani_comm_gatherv", "lzani_group_create", "lzani_group_destroy", "lzani_group_last_error",
            "lzani_group_set_genomes", "lzani_group_run_rows", "lzani_group_get_timing", "lzani_plan_gather", "lzani_get_rtc_info", "lzani_debug_rtc_compile",
-           "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name")
+           "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name",
+           "lzani_set_genome_memory", "lzani_plan_blocks", "lzani_get_residency", "lzani_group_set_genome_memory",
+           "lzani_group_get_residency")
 
 
 class LzaniError(RuntimeError):
@@ -59,10 +61,15 @@ class RtcInfo(C.Structure):
                 ("kernels_from_cache", C.c_int32), ("kernels_failed", C.c_int32), ("reserved_", C.c_int32), ("build_ms", C.c_double)]
 
 
+class ResidencyInfo(C.Structure):
+    _fields_ = [("limit", C.c_uint64), ("blocks", C.c_uint32), ("tiles", C.c_uint32), ("block_uploads", C.c_uint64),
+                ("peak_resident_bytes", C.c_uint64), ("host_bytes", C.c_uint64), ("upload_ms", C.c_double)]
+
+
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
     deps = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("lzani_core.h", "lzani_layout.h", "lzani_kernels_index.h",
-                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_multi.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h")] + [os.path.join(ROOT, "include", "lzani.h")]
+                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_multi.h", "lzani_ooc.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h")] + [os.path.join(ROOT, "include", "lzani.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -117,6 +124,11 @@ def load_library():
         lib.lzani_group_run_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lzani_group_get_timing.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.lzani_plan_gather.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+        lib.lzani_set_genome_memory.argtypes = [C.c_void_p, C.c_uint64]
+        lib.lzani_group_set_genome_memory.argtypes = [C.c_void_p, C.c_uint64]
+        lib.lzani_plan_blocks.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.lzani_get_residency.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_group_get_residency.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -178,6 +190,22 @@ def partition_rows(n_rows, n_parts, row_cost=None):
     if rc != 0:
         raise LzaniError(f"lzani_partition_rows: {ERRORS.get(rc, rc)}")
     return part
+
+
+def plan_blocks(lens, params=None, limit=0):
+    """Block plan of an out-of-core genome set (lzani_plan_blocks; no GPU needed): (number of blocks, block_of[n])."""
+    lib = load_library()
+    arr, _ = params_array(params)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    block_of = np.zeros(len(lens), dtype=np.uint32)
+    nb = lib.lzani_plan_blocks(len(lens), _ptr(lens), arr, C.c_uint64(int(limit)), _ptr(block_of))
+    if nb < 0:
+        raise LzaniError(f"lzani_plan_blocks: {ERRORS.get(nb, nb)}")
+    return nb, block_of
+
+
+def _residency(o):
+    return {k: getattr(o, k) for k, _ in ResidencyInfo._fields_}
 
 
 def rtc_compile(params=None, nfree=True, cand=2, arch="gfx950"):
@@ -250,6 +278,15 @@ class Group:
                     "lzani_group_run_rows")
         return out
 
+    def set_genome_memory(self, nbytes):
+        """Genome-memory limit of every device context, applied at the next set_genomes (0: automatic)."""
+        self._check(self.lib.lzani_group_set_genome_memory(self.h, C.c_uint64(int(nbytes))), "lzani_group_set_genome_memory")
+
+    def residency(self, device_index=0):
+        o = ResidencyInfo()
+        self._check(self.lib.lzani_group_get_residency(self.h, device_index, C.byref(o)), "lzani_group_get_residency")
+        return _residency(o)
+
     def timing(self, device_index=0):
         t = Timing()
         g = C.c_double(0)
@@ -293,6 +330,17 @@ class Engine:
         self._check(self.lib.lzani_set_genomes(self.h, len(seqs), ptrs, _ptr(lens)), "lzani_set_genomes")
         self.n = len(seqs)
         self.lens = lens
+
+    def set_genome_memory(self, nbytes):
+        """Genome-memory limit (bytes of genome tables), applied at the next set_genomes; 0 = automatic.  A set beyond
+        it stays on the host and runs in tiles of (reference block, query block)."""
+        self._check(self.lib.lzani_set_genome_memory(self.h, C.c_uint64(int(nbytes))), "lzani_set_genome_memory")
+
+    def residency(self):
+        """lzani_get_residency: limit, blocks, tiles and block_uploads of the last run, peak_resident_bytes, host_bytes, upload_ms."""
+        o = ResidencyInfo()
+        self._check(self.lib.lzani_get_residency(self.h, C.byref(o)), "lzani_get_residency")
+        return _residency(o)
 
     def run_rows(self, ref_ids, row_off, query_ids=None):
         ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
