@@ -14,7 +14,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lzani.h"
@@ -58,23 +60,11 @@ using namespace lzani;
 //   pairs_blk nfree=N defp=D                        k_pairs_blk<N, D>
 //   split nfree=N defp=D mode=M                     k_split<N, D, M>
 //   rtc nfree=N cand=C                              the run-time compiled kernel (lzani_rtc.h), DEFP 9
-// An instantiation added to the dispatch needs a row here (pk_id refuses to compile without one) and a cell in
+// An instantiation added to the dispatch needs a row here (count_launch refuses to compile without one) and a cell in
 // tests/test_gpu_instantiations.py.
 enum PairKernelKind { PK_PAIRS, PK_BLK, PK_SPLIT, PK_RTC };
 struct PairKernelDesc { const char* name; int kind, fast, nfree, defp, aln, bk, cand, mode; };
-enum PairKernelId : u32 {
-    PK_REGIONS_SLOW, PK_REGIONS_TW, PK_REGIONS_NOTW, PK_SLOW,
-    PK_PM_N0_D0, PK_PM_N0_D1, PK_PM_N0_D2, PK_PM_N1_D0, PK_PM_N1_D1, PK_PM_N1_D2,
-    PK_JOIN_N0_D0, PK_JOIN_N0_D1, PK_JOIN_N0_D2, PK_JOIN_N1_D0, PK_JOIN_N1_D1, PK_JOIN_N1_D2,
-    PK_TW_N0_D0, PK_TW_N0_D1, PK_TW_N1_D0, PK_TW_N1_D1,
-    PK_NOTW_N0_D0, PK_NOTW_N0_D1, PK_NOTW_N1_D0, PK_NOTW_N1_D1,
-    PK_BLK_N0_D0, PK_BLK_N0_D1, PK_BLK_N1_D0, PK_BLK_N1_D1,
-    PK_SPLIT_N0_D0_M0, PK_SPLIT_N0_D0_M1, PK_SPLIT_N0_D1_M0, PK_SPLIT_N0_D1_M1, PK_SPLIT_N0_D2_M0, PK_SPLIT_N0_D2_M1,
-    PK_SPLIT_N1_D0_M0, PK_SPLIT_N1_D0_M1, PK_SPLIT_N1_D1_M0, PK_SPLIT_N1_D1_M1, PK_SPLIT_N1_D2_M0, PK_SPLIT_N1_D2_M1,
-    PK_RTC_N0_C0, PK_RTC_N0_C1, PK_RTC_N0_C2, PK_RTC_N1_C0, PK_RTC_N1_C1, PK_RTC_N1_C2,
-    PK_COUNT
-};
-constexpr PairKernelDesc PAIR_KERNELS[PK_COUNT] = {
+constexpr PairKernelDesc PAIR_KERNELS[] = {
     {"pairs fast=0 nfree=0 defp=0 aln=1 bk=0 cand=0", PK_PAIRS, 0, 0, 0, 1, 0, 0, 0},
     {"pairs fast=1 nfree=0 defp=0 aln=1 bk=1 cand=0", PK_PAIRS, 1, 0, 0, 1, 1, 0, 0},
     {"pairs fast=1 nfree=0 defp=0 aln=1 bk=0 cand=0", PK_PAIRS, 1, 0, 0, 1, 0, 0, 0},
@@ -122,7 +112,8 @@ constexpr PairKernelDesc PAIR_KERNELS[PK_COUNT] = {
     {"rtc nfree=1 cand=1", PK_RTC, 1, 1, 9, 0, 1, 1, 0},
     {"rtc nfree=1 cand=2", PK_RTC, 1, 1, 9, 0, 1, 2, 0},
 };
-// the row of an instantiation; -1 = none (a launch site that names a kernel without a row fails to compile, see PK_COUNT_LAUNCH)
+constexpr int PK_COUNT = (int)(sizeof PAIR_KERNELS / sizeof PAIR_KERNELS[0]);
+// the row of an instantiation; -1 = none
 constexpr int pk_id(int kind, int fast, int nfree, int defp, int aln, int bk, int cand, int mode)
 {
     for (int i = 0; i < PK_COUNT; ++i) {
@@ -132,10 +123,34 @@ constexpr int pk_id(int kind, int fast, int nfree, int defp, int aln, int bk, in
     }
     return -1;
 }
-static_assert(pk_id(PK_PAIRS, 1, 1, 2, 0, 1, 1, 0) == PK_JOIN_N1_D2 && pk_id(PK_SPLIT, 1, 1, 2, 0, 1, 2, 1) == PK_SPLIT_N1_D2_M1 &&
-              pk_id(PK_RTC, 1, 1, 9, 0, 1, 2, 0) == PK_RTC_N1_C2 && pk_id(PK_BLK, 1, 0, 1, 0, 1, 0, 0) == PK_BLK_N0_D1,
-              "PAIR_KERNELS is out of the order of PairKernelId");
-#define PK_COUNT_LAUNCH(...) do { constexpr int id_ = pk_id(__VA_ARGS__); static_assert(id_ >= 0, "a pair kernel without a row in PAIR_KERNELS"); c->klaunch[id_] += 1; } while (0)
+// the rows of the run-time compiled kernel: PK_RTC_N0_C0 + 3 * nfree + cand
+constexpr int PK_RTC_N0_C0 = pk_id(PK_RTC, 1, 0, 9, 0, 1, 0, 0);
+static_assert(PK_RTC_N0_C0 >= 0 && pk_id(PK_RTC, 1, 0, 9, 0, 1, 2, 0) == PK_RTC_N0_C0 + 2 && pk_id(PK_RTC, 1, 1, 9, 0, 1, 0, 0) == PK_RTC_N0_C0 + 3 &&
+              pk_id(PK_RTC, 1, 1, 9, 0, 1, 2, 0) == PK_RTC_N0_C0 + 5, "the rtc rows of PAIR_KERNELS are out of order");
+
+// What the last run did (lzani_get_timing, lzani_get_layout, lzani_debug_kernel_launches): reset at its start; an
+// out-of-core run sums its tiles' records.
+struct RunRecord {
+    lzani_timing tm{};
+    u32 batches = 0;
+    // launches of k_pairs_blk; pair-kernel launches fed by candidate bitmaps, with tickets longest pair first, by a run-time
+    // compiled kernel; presence matrices made by k_pm_from_index; batches whose pairs several waves each scanned, their segments
+    int blk_launches = 0, pm_launches = 0, lpt_launches = 0, rtc_launches = 0, pmfi_launches = 0, split_launches = 0;
+    u64 split_items = 0;
+    u64 klaunch[PK_COUNT] = {};   // the launch record: launches per pair-kernel instantiation (PAIR_KERNELS)
+
+    RunRecord& operator+=(const RunRecord& o)
+    {
+        tm.index_ms += o.tm.index_ms; tm.pairs_ms += o.tm.pairs_ms; tm.cand_ms += o.tm.cand_ms; tm.kmers_ms += o.tm.kmers_ms;
+        tm.pair_launches += o.tm.pair_launches; tm.index_launches += o.tm.index_launches; tm.cand_launches += o.tm.cand_launches;
+        tm.pairs += o.tm.pairs;
+        batches += o.batches;
+        blk_launches += o.blk_launches; pm_launches += o.pm_launches; lpt_launches += o.lpt_launches; pmfi_launches += o.pmfi_launches;
+        split_launches += o.split_launches; split_items += o.split_items; rtc_launches += o.rtc_launches;
+        for (int x = 0; x < PK_COUNT; ++x) klaunch[x] += o.klaunch[x];
+        return *this;
+    }
+};
 
 struct lzani_ctx {
     Params P;
@@ -176,7 +191,6 @@ struct lzani_ctx {
     u64 fl_stride = 0;            // words per slot; 0 = no filter (d_fl = the all-ones word)
     u32 fmask = 31;
     u32 slots = 0;
-    u32 batches_last_run = 0;
     // join form of candidate detection (long genomes): per-genome k-mer lists sorted by bucket
     bool join_mode = false, join_ready = false;
     unsigned long long* d_jkeys_in = nullptr;     // unsorted keys, koff[g] + p
@@ -197,7 +211,6 @@ struct lzani_ctx {
     u64 dir_stride = 0, ent_stride = 0;
     unsigned long long* d_cursor = nullptr;
     u32* d_blkctr = nullptr;      // k_pairs_blk: one pair counter per block
-    int blk_launches = 0;         // launches of k_pairs_blk in the last run
     int blk_fold = -1;            // k_pairs_blk: LDS filter = global filter folded 2^blk_fold times (-1: not decided yet, -2: does not fit)
     // dense rows: candidates from the presence matrix of a group of references (lzani_kernels_cand.h)
     u32* d_pm = nullptr;          // the matrix of one group: 2^pm_bits rows of PM_GROUP bits
@@ -206,23 +219,16 @@ struct lzani_ctx {
     size_t pm_cbits_bytes = 0;
     u32* d_pm_pidx = nullptr;     // rows with query lists: pair of (query, slot of the group), query flags + list + count behind it
     size_t pm_pidx_bytes = 0;
-    int pm_launches = 0;          // pair-kernel launches of the last run fed by candidate bitmaps
     u32* d_lpt_cnt = nullptr;     // batches of few, long pairs: candidates per pair, then the ticket keys unsorted / sorted
     unsigned long long* d_lpt_keys = nullptr;
     size_t lpt_pairs = 0;
-    int lpt_launches = 0;         // pair-kernel launches of the last run that took their tickets longest pair first
-    int pmfi_launches = 0;        // presence matrices of the last run made by k_pm_from_index
-    int split_launches = 0;       // batches of the last run whose pairs were scanned by several waves each
-    u64 split_items = 0;          // ... segments run in all (with the ones run again)
     bool pm_attr_set = false;
     u32 pmfi_attr_set = 0;                // k_pm_from_index<RW>: bit RW = its LDS limit is raised
 
-    lzani_timing tm{};
+    RunRecord run;
     // pair kernels compiled at run time for this context's parameters (lzani_rtc.h); none for the two ahead-of-time tuples
     lzani_rtc::State rtc;
     std::string arch;             // the device's gfx target, as hipRTC wants it
-    int rtc_launches = 0;         // pair-kernel launches of the last run by a run-time compiled kernel
-    u64 klaunch[PK_COUNT] = {};   // launch record of the last run: launches per pair-kernel instantiation (PAIR_KERNELS)
     u64 pairs_seen = 0;           // directed pairs this context has been asked for so far (a run-time compile must pay)
 
     void* comm = nullptr;         // ncclComm_t of lzani_comm_init (one process per GPU), lzani_multi.h
@@ -287,12 +293,19 @@ int fail(lzani_ctx* c, int code, const std::string& msg)
                         std::string(#call) + ": " + hipGetErrorString(e_));                           \
     } while (0)
 
+// (the join lists of an out-of-core run belong to one tile's local genome table: released between tiles)
+void free_join_lists(lzani_ctx* c)
+{
+    hipFree(c->d_jkeys); hipFree(c->d_jkoff); hipFree(c->d_jsoff); hipFree(c->d_jcnt);
+    c->d_jkeys = nullptr; c->d_jkoff = c->d_jsoff = nullptr; c->d_jcnt = nullptr;
+    c->join_ready = false;
+}
 void free_genomes(lzani_ctx* c)
 {
     hipFree(c->d_t2); hipFree(c->d_nm); hipFree(c->d_nmoff); hipFree(c->d_L); hipFree(c->d_kmL); hipFree(c->d_kmS); hipFree(c->d_hasN);
-    hipFree(c->d_jkeys); hipFree(c->d_jkoff); hipFree(c->d_jsoff); hipFree(c->d_jcnt); hipFree(c->d_jtmp);
-    c->d_jkeys_in = c->d_jkeys = nullptr; c->d_jkoff = c->d_jsoff = nullptr; c->d_jcnt = nullptr; c->d_jtmp = nullptr; c->jtmp_bytes = 0;
-    c->join_mode = c->join_ready = false;
+    free_join_lists(c);
+    hipFree(c->d_jtmp);
+    c->d_jkeys_in = nullptr; c->d_jtmp = nullptr; c->jtmp_bytes = 0; c->join_mode = false;
     c->d_hasN = nullptr;
     c->d_t2 = c->d_nm = c->d_nmoff = nullptr; c->d_L = nullptr; c->d_kmL = c->d_kmS = nullptr; c->kmers_ready = false;
     c->n = 0;
@@ -304,13 +317,6 @@ void free_genomes(lzani_ctx* c)
     c->half_words = 0; c->half_genomes = 0; c->half_block[0] = c->half_block[1] = -1; c->half_a = 0;
     c->res_tiles = 0; c->res_uploads = c->res_peak = 0; c->res_upload_ms = 0;
 }
-// (the join lists of an out-of-core run belong to one tile's local genome table: released between tiles)
-void free_join_lists(lzani_ctx* c)
-{
-    hipFree(c->d_jkeys); hipFree(c->d_jkoff); hipFree(c->d_jsoff); hipFree(c->d_jcnt);
-    c->d_jkeys = nullptr; c->d_jkoff = c->d_jsoff = nullptr; c->d_jcnt = nullptr;
-    c->join_ready = false;
-}
 void free_pm(lzani_ctx* c)
 {
     hipFree(c->d_pm); hipFree(c->d_pm_cbits); hipFree(c->d_pm_pidx); hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
@@ -320,14 +326,19 @@ void free_pm(lzani_ctx* c)
 void free_slabs(lzani_ctx* c)
 {
     hipFree(c->d_dirz); hipFree(c->d_ent); hipFree(c->d_bk); hipFree(c->d_tw); hipFree(c->d_fl); hipFree(c->d_status);
-    c->d_fl = nullptr;
     hipFree(c->d_ikeys_in); hipFree(c->d_ikeys); hipFree(c->d_icnt); hipFree(c->d_ibase);
     c->d_ikeys_in = c->d_ikeys = nullptr; c->d_icnt = nullptr; c->d_ibase = nullptr;
-    c->d_dirz = c->d_ent = c->d_bk = c->d_tw = c->d_status = nullptr; c->slots = 0;
+    c->d_dirz = c->d_ent = c->d_bk = c->d_tw = c->d_fl = c->d_status = nullptr; c->slots = 0;
 }
 
 // Per-genome k-mer words exist for mal, msl <= 15 (the fast path).
 bool kmer_words_of(const Params& P) { return P.mal <= 15 && P.msl <= 15; }
+
+// An LZANI_* switch: whether it is set and begins with ch; its number (atoi / strtoull); empty where it is not set.
+bool env_is(const char* name, char ch) { const char* v = getenv(name); return v && *v == ch; }
+std::optional<bool> env_flag(const char* name) { const char* v = getenv(name); return v ? std::optional<bool>(*v == '1') : std::nullopt; }
+std::optional<int> env_int(const char* name) { const char* v = getenv(name); return v ? std::optional<int>(atoi(v)) : std::nullopt; }
+std::optional<u64> env_u64(const char* name) { const char* v = getenv(name); return v ? std::optional<u64>(strtoull(v, nullptr, 10)) : std::nullopt; }
 
 struct IndexForm { u64 bk_stride, tw_stride; bool join_mode; };
 
@@ -339,23 +350,19 @@ IndexForm index_form_of(const Params& P, const IndexGeom& geo, u32 n)
     int tagbits = 0;
     while (tagbits < 32 && ((geo.tagmask >> tagbits) & 1u)) ++tagbits;
     const bool exact = geo.tagmask == (u32)lowmask(geo.kb - geo.dirbits);
-    const char* e = getenv("LZANI_NO_BUCKETS");                           // experiments / test_index_forms
-    const char* mx = getenv("LZANI_BK_MAX_DIRBITS");
-    const int max_dirbits = mx ? atoi(mx) : 26;
+    const int max_dirbits = env_int("LZANI_BK_MAX_DIRBITS").value_or(26);
     // bucket table (+ tag words): wherever the sentinels cannot be real entries; 20 B per bucket more per slot
-    f.bk_stride = (kmer_words_of(P) && exact && geo.dirbits <= max_dirbits && tagbits + geo.posbits <= 30 && !(e && *e == '1'))
+    // (LZANI_NO_BUCKETS, LZANI_NO_TAGWORDS: experiments / test_index_forms)
+    f.bk_stride = (kmer_words_of(P) && exact && geo.dirbits <= max_dirbits && tagbits + geo.posbits <= 30 && !env_is("LZANI_NO_BUCKETS", '1'))
                       ? ((u64)4 << geo.dirbits) : 0;
-    const char* t = getenv("LZANI_NO_TAGWORDS");
-    f.tw_stride = (f.bk_stride && tagbits <= 7 && !(t && *t == '1')) ? ((u64)1 << geo.dirbits) : 0;
+    f.tw_stride = (f.bk_stride && tagbits <= 7 && !env_is("LZANI_NO_TAGWORDS", '1')) ? ((u64)1 << geo.dirbits) : 0;
     // Join form of candidate detection: where the tag words of one reference exceed what an L2 holds by far, a random
     // probe per query position costs one HBM line each; the query's k-mer list sorted by bucket turns the probes into
     // two streams (DevWave::join).  Needs the anchor queue (tag words, seed window <= 128) and keys of 64 bits.
-    const char* nj = getenv("LZANI_NO_JOIN");
-    const char* jm = getenv("LZANI_JOIN_MIN_BYTES");
-    const u64 min_bytes = jm ? strtoull(jm, nullptr, 10) : (8ull << 20);
+    const u64 min_bytes = env_u64("LZANI_JOIN_MIN_BYTES").value_or(8ull << 20);
     const int gbits = ceil_log2((u64)n + 1);                          // the all-ones genome number is the invalid key's
     f.join_mode = f.tw_stride && f.tw_stride * 4 >= min_bytes && P.mqd + P.mrd <= 128 &&
-                  gbits + geo.kb + geo.posbits <= 64 && !(nj && *nj == '1');
+                  gbits + geo.kb + geo.posbits <= 64 && !env_is("LZANI_NO_JOIN", '1');
     return f;
 }
 
@@ -370,26 +377,21 @@ void choose_index_form(lzani_ctx* c)
         c->join_mode = f.join_mode;
     }
     // Sort-based index build where the directory is beyond the LDS-staged build (2^19 buckets): keys of 64 bits with up
-    // to 16 bits of slot number
-    {
-        const char* sm = getenv("LZANI_SORT_INDEX_MIN_DIRBITS");      // tests: 0 forces it at every size
-        const char* ns = getenv("LZANI_NO_SORT_INDEX");
-        c->sort_build = kmer_words_of(c->P) && c->geo.dirbits >= (sm ? atoi(sm) : 20) && c->geo.kb + c->geo.posbits <= 60 && !(ns && *ns == '1');
-    }
+    // to 16 bits of slot number (LZANI_SORT_INDEX_MIN_DIRBITS=0, tests: at every size)
+    c->sort_build = kmer_words_of(c->P) && c->geo.dirbits >= env_int("LZANI_SORT_INDEX_MIN_DIRBITS").value_or(20) &&
+                    c->geo.kb + c->geo.posbits <= 60 && !env_is("LZANI_NO_SORT_INDEX", '1');
     // Presence filter in front of the tag-word probes (probe form only; k_pairs_blk keeps the reference's in LDS): ~3 bits
     // per text position, at most 2^18 bits (genomes up to ~128 kbp); beyond, one all-ones word passes everything
     {
-        const char* nf = getenv("LZANI_NO_FILTER");
-        const char* fx = getenv("LZANI_FILTER_MAX_BITS");
-        const int fmax = fx ? atoi(fx) : 18;                          // 2^18 bits = 32 KB of LDS per block of 16 waves
+        const int fmax = env_int("LZANI_FILTER_MAX_BITS").value_or(18);      // 2^18 bits = 32 KB of LDS per block of 16 waves
         const int fbits = std::min(ceil_log2((u64)std::max(c->Tmax, 1024)) + 1, fmax);
-        const bool on = c->tw_stride && !c->join_mode && ceil_log2((u64)std::max(c->Tmax, 1024)) <= fmax && !(nf && *nf == '1');
+        const bool on = c->tw_stride && !c->join_mode && ceil_log2((u64)std::max(c->Tmax, 1024)) <= fmax && !env_is("LZANI_NO_FILTER", '1');
         c->fl_stride = on ? ((u64)1 << fbits) / 32 : 0;
         c->blk_fold = -1;
         c->fmask = on ? (u32)((1u << fbits) - 1u) : 31u;
     }
-    const char* ms = getenv("LZANI_MAX_SLOTS");
-    c->max_slots = ms && atoi(ms) > 0 ? (u32)std::min(65535, atoi(ms)) : 65535u;
+    const int ms = env_int("LZANI_MAX_SLOTS").value_or(0);
+    c->max_slots = ms > 0 ? (u32)std::min(65535, ms) : 65535u;
     if (c->sort_build)                                  // the slot number shares the 64-bit key with hash and position
         c->max_slots = (u32)std::min<u64>(c->max_slots, (1ull << std::min(16, 64 - c->geo.kb - c->geo.posbits)) - 1);
 }
@@ -423,6 +425,17 @@ int ensure_slabs(lzani_ctx* c, u32 want_rows)
     return LZANI_OK;
 }
 
+// The radix sort's scratch grown to `need` bytes; sync: after the stream's queued work, which may still be using it.
+int grow_jtmp(lzani_ctx* c, size_t need, bool sync)
+{
+    if (need <= c->jtmp_bytes) return LZANI_OK;
+    if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(c->d_jtmp); c->d_jtmp = nullptr; c->jtmp_bytes = 0;
+    HIPCHK(c, hipMalloc(&c->d_jtmp, need));
+    c->jtmp_bytes = need;
+    return LZANI_OK;
+}
+
 GenomeTab gtab(const lzani_ctx* c) { return GenomeTab{c->d_t2, c->d_nm, c->d_nmoff, c->d_L, c->d_kmL, c->d_kmS, c->d_hasN}; }
 
 // Join form: the k-mer list of every genome as a query, sorted by (genome, bucket) -- k_join_keys + the radix sort of lzani_sort.hip,
@@ -441,8 +454,7 @@ int alloc_join_lists(lzani_ctx* c)
     if (e == hipSuccess) e = hipMalloc(&c->d_jkeys, std::max<u64>(c->jkoff[n], 1) * 8);
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_jkoff, c->jkoff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) {
-        hipFree(c->d_jkoff); hipFree(c->d_jsoff); hipFree(c->d_jcnt); hipFree(c->d_jkeys);
-        c->d_jkoff = c->d_jsoff = nullptr; c->d_jcnt = nullptr; c->d_jkeys = nullptr;
+        free_join_lists(c);
         return fail(c, e == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE, std::string("join lists: ") + hipGetErrorString(e));
     }
     return LZANI_OK;
@@ -490,11 +502,7 @@ int build_join_lists(lzani_ctx* c)
             size_t need = 0;
             int e = lzani_sort_keys(c->d_jkeys_in + c->jkoff[g0], c->d_jkeys + c->jkoff[g0], keys, c->geo.posbits, shift_g + gbits, nullptr, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "join lists: radix sort (size query) failed");
-            if (need > c->jtmp_bytes) {
-                hipFree(c->d_jtmp); c->d_jtmp = nullptr; c->jtmp_bytes = 0;
-                HIPCHK(c, hipMalloc(&c->d_jtmp, need));
-                c->jtmp_bytes = need;
-            }
+            { int rc = grow_jtmp(c, need, false); if (rc) return rc; }
             need = c->jtmp_bytes;
             e = lzani_sort_keys(c->d_jkeys_in + c->jkoff[g0], c->d_jkeys + c->jkoff[g0], keys, c->geo.posbits, shift_g + gbits, c->d_jtmp, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "join lists: radix sort failed");
@@ -506,7 +514,7 @@ int build_join_lists(lzani_ctx* c)
     HIPCHK(c, hipMemcpyAsync(c->d_jsoff, soff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));        // (also: keys_in is released below)
     c->d_jkeys_in = nullptr;
-    c->tm.index_launches += 2;
+    c->run.tm.index_launches += 2;
     return LZANI_OK;
 }
 
@@ -526,7 +534,7 @@ int ensure_kmers(lzani_ctx* c)
                            G, c->d_kmL, c->d_kmS, c->P.mal, c->P.msl, c->P.mrd, c->Tmax);
     }
     HIPCHK(c, hipGetLastError());
-    c->tm.index_launches += 1;
+    c->run.tm.index_launches += 1;
     HIPCHK(c, hipEventRecord(c->ev_km[1], c->stream));
     c->kmers_ready = true;
     c->km_timed = true;
@@ -555,10 +563,31 @@ int ensure_join(lzani_ctx* c)
     return rc;
 }
 
+// The run path's switches (experiments and tests), read where a Knobs is made: at the start of every run (tests change them
+// between the runs of one context).  Empty: not set, the run's own rule decides.
+struct Knobs {
+    bool pm = !env_is("LZANI_PM", '0');                                     // 0: no candidate bitmaps
+    std::optional<int> pm_min_rows = env_int("LZANI_PM_MIN_ROWS");
+    std::optional<u64> pm_max_bytes = env_u64("LZANI_PM_MAX_BYTES");         // the candidate bitmaps of a batch
+    std::optional<u64> pm_min_share = env_u64("LZANI_PM_MIN_SHARE");         // pairs per query and group of rows (query lists)
+    bool pm_fail_cbits = env_is("LZANI_PM_FAIL_CBITS", '1');                // tests: the bitmaps cannot be had
+    std::optional<bool> pm_from_index = env_flag("LZANI_PM_FROM_INDEX");
+    u32 blocks_per_cu = (u32)std::max(1, std::min(8, env_int("LZANI_BLOCKS_PER_CU").value_or(8)));   // occupancy experiments
+    std::optional<bool> block_kernel = env_flag("LZANI_BLOCK_KERNEL");
+    u64 rtc_min_pairs = env_u64("LZANI_RTC_MIN_PAIRS").value_or(2000000ull);
+    std::optional<bool> lpt = env_flag("LZANI_LPT"), split = env_flag("LZANI_SPLIT");
+    u64 split_s = (u64)std::max(2, env_int("LZANI_SPLIT_S").value_or(64));   // segments per pair
+    int split_seglen = env_int("LZANI_SPLIT_SEGLEN").value_or(0);           // > 0: the segment length instead
+    bool split_all = !env_is("LZANI_SPLIT_ALL", '0');                       // 0: cut only the pairs with many candidates
+    u32 split_thr = (u32)env_u64("LZANI_SPLIT_THR").value_or(0);             // ... or with this many
+    bool lds_index = !env_is("LZANI_NO_LDS_INDEX", '1');
+    int lds_index_max_dirbits = env_int("LZANI_LDS_INDEX_MAX_DIRBITS").value_or(19);
+};
+
 // Index build of `rows` references (device list d_ref_ids) into slots 0..rows-1.
 // with_tw = false: the sort-based build leaves the tag words out (a batch whose pairs read candidate bitmaps never probes them:
 // 8.6 GB less to write per 128 x 5 Mbp references)
-int build_indexes(lzani_ctx* c, const u32* d_ref_ids, u32 rows, bool with_filter = true, bool with_tw = true)
+int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, bool with_filter = true, bool with_tw = true)
 {
     IdxArgs ia;
     ia.G = gtab(c);
@@ -572,7 +601,7 @@ int build_indexes(lzani_ctx* c, const u32* d_ref_ids, u32 rows, bool with_filter
         HIPCHK(c, hipMemsetAsync(c->d_fl, 0, (size_t)rows * c->fl_stride * 4, c->stream));
         hipLaunchKernelGGL(k_idx_filter, dim3((u32)std::min<u64>(((u64)c->Tmax + 255) / 256, 64), rows), dim3(256), 0, c->stream,
                            ia, c->d_fl, c->fl_stride, c->fmask, c->Tmax);
-        c->tm.index_launches += 1;
+        c->run.tm.index_launches += 1;
     }
     if (c->sort_build) {
         // keys -> radix sort, every slot a segment of its own (lzani_sort.hip) -> the tables in one streaming pass.  A key is
@@ -586,12 +615,7 @@ int build_indexes(lzani_ctx* c, const u32* d_ref_ids, u32 rows, bool with_filter
             size_t need = 0;
             int e = lzani_sort_segments(c->d_ikeys_in, c->d_ikeys, Tm, rows, c->geo.posbits, shift_slot + 1, nullptr, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "index build: radix sort (size query) failed");
-            if (need > c->jtmp_bytes) {
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                hipFree(c->d_jtmp); c->d_jtmp = nullptr; c->jtmp_bytes = 0;
-                HIPCHK(c, hipMalloc(&c->d_jtmp, need));
-                c->jtmp_bytes = need;
-            }
+            { int rc = grow_jtmp(c, need, true); if (rc) return rc; }
             need = c->jtmp_bytes;
             e = lzani_sort_segments(c->d_ikeys_in, c->d_ikeys, Tm, rows, c->geo.posbits, shift_slot + 1, c->d_jtmp, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "index build: radix sort failed");
@@ -600,12 +624,10 @@ int build_indexes(lzani_ctx* c, const u32* d_ref_ids, u32 rows, bool with_filter
         hipLaunchKernelGGL(k_idx_from_sorted, dim3((u32)std::min<u64>((Tm + 255) / 256, 8192), rows), dim3(256), 0, c->stream,
                            ia, c->d_ikeys, c->d_icnt, c->d_ibase, c->d_bk, with_tw ? c->d_tw : nullptr, c->bk_stride, c->tw_stride);
         HIPCHK(c, hipGetLastError());
-        c->tm.index_launches += 4;
+        c->run.tm.index_launches += 4;
         return LZANI_OK;
     }
-    const char* nolds = getenv("LZANI_NO_LDS_INDEX");
-    const char* ldsmax = getenv("LZANI_LDS_INDEX_MAX_DIRBITS");
-    const bool lds_build = c->d_kmL && c->geo.dirbits <= (ldsmax ? atoi(ldsmax) : 19) && !(nolds && *nolds == '1');
+    const bool lds_build = c->d_kmL && c->geo.dirbits <= k.lds_index_max_dirbits && k.lds_index;
     // blocks per slot of the global-atomics kernels: the whole range when they build every slot, a handful when
     // they only pick up what k_idx_build left (usually nothing)
     const u32 gx_pos = lds_build ? 16u : (u32)((c->Tmax + 255) / 256), gx_bkt = lds_build ? 16u : (nb + 255) / 256;
@@ -633,30 +655,57 @@ int build_indexes(lzani_ctx* c, const u32* d_ref_ids, u32 rows, bool with_filter
                            c->d_dirz, c->d_ent, c->d_bk, c->d_tw, c->dir_stride, c->ent_stride, c->bk_stride, c->tw_stride,
                            nb, c->geo.posbits, ia.todo);
     HIPCHK(c, hipGetLastError());
-    c->tm.index_launches += 4;
+    c->run.tm.index_launches += 4;
     return LZANI_OK;
 }
 
 struct RegionSink { lzani_region* d_regions; unsigned long long* d_count; unsigned long long capacity; };
 
-int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
-                  int* d_out, const RegionSink* rs = nullptr)
+// The tuples the pair kernels fold into their code ahead of time: 1 = the defaults, 2 = the long-genome parameters
+// (--mal 15 --msl 9 --reg 60, BASELINE configs[3]; the hand-written null chain included, bitmap, join and split forms),
+// 0 = any other (the generic kernel, or one compiled at run time).
+int defp_select(const Params& q)
 {
-    if (!c->n) return fail(c, LZANI_ERR_STATE, "lzani_run_rows: no genomes set");
-    c->tm = lzani_timing{};
-    // (the k-mer words and the join lists are made by the first run after lzani_set_genomes -- inside its timed index
-    // stage, reported as kmers_ms -- and kept: they depend on the genome set and the parameters only)
-    c->batches_last_run = 0;
-    c->blk_launches = 0;
-    c->pm_launches = 0;
-    c->lpt_launches = 0;
-    c->pmfi_launches = 0;
-    c->split_launches = 0;
-    c->split_items = 0;
-    c->rtc_launches = 0;
-    std::fill(c->klaunch, c->klaunch + PK_COUNT, (u64)0);
-    if (n_rows == 0) return LZANI_OK;
-    const u64 n_pairs = row_off[n_rows];
+    if (q.mrd != 40 || q.mqd != 40 || q.aw != 15 || q.am != 7 || q.ar != 3) return 0;
+    return (q.mal == 11 && q.msl == 7 && q.reg == 35) ? 1 : (q.mal == 15 && q.msl == 9 && q.reg == 60) ? 2 : 0;
+}
+
+// The pair kernels of one form for the run-time (nfree, dsel): f(NFREE, DEFP) with both as std::integral_constant.  The forms
+// with ND = 3 have an instantiation per dsel; those with ND = 2 none for the long-genome tuple, which runs their DEFP 0.
+template <int ND, class F>
+void with_nfree_defp(bool nf, int dsel, F&& f)
+{
+    auto by_defp = [&](auto N) {
+        if (dsel == 1) f(N, std::integral_constant<int, 1>{});
+        else if (dsel == 2) f(N, std::integral_constant<int, ND == 3 ? 2 : 0>{});
+        else f(N, std::integral_constant<int, 0>{});
+    };
+    if (nf) by_defp(std::true_type{}); else by_defp(std::false_type{});
+}
+
+// One launch in the launch record; a launch of an instantiation without a row in PAIR_KERNELS does not compile.
+template <int KIND, int F, int N, int D, int A, int B, int C, int M = 0>
+void count_launch(RunRecord& r)
+{
+    constexpr int id = pk_id(KIND, F, N, D, A, B, C, M);
+    static_assert(id >= 0, "a pair kernel without a row in PAIR_KERNELS");
+    r.klaunch[id] += 1;
+}
+
+template <bool F, bool N, int D, bool A, bool B, int C>
+void launch_k_pairs(lzani_ctx* c, dim3 gd, dim3 bd, const PairArgs& pa)
+{
+    hipLaunchKernelGGL((k_pairs<F, N, D, A, B, C>), gd, bd, 0, c->stream, pa);
+    count_launch<PK_PAIRS, F, N, D, A, B, C>(c->run);
+}
+
+// What a run's rows hold beyond their checks: the pairs and, for query lists, whether a row names a query twice and how
+// many queries the groups of PM_GROUP consecutive rows involve (what the candidate form goes by).
+struct RowFacts { u64 n_pairs = 0; bool lists_dup = false; u64 lists_involved = 0; };
+
+// The checks of a run's rows (n_rows > 0) against the genome set; the query ids in one pass.
+int check_rows(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids, RowFacts& f)
+{
     for (u32 k = 0; k < n_rows; ++k) {
         if (ref_ids[k] >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: reference id out of range");
         if (row_off[k + 1] < row_off[k]) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off not monotone");
@@ -664,615 +713,561 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
             return fail(c, LZANI_ERR_ARG, "lzani_run_rows: dense row must have n-1 queries");
     }
     if (row_off[0] != 0) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off[0] must be 0");
-    // (query lists: the same pass tells whether a row names a query twice and how many queries a group of PM_GROUP
-    // consecutive rows involves -- what the candidate stage below goes by)
-    bool lists_dup = false;
-    u64 lists_involved = 0;
+    f.n_pairs = row_off[n_rows];
     if (query_ids) {
         std::vector<u32> in_row(c->n, 0xFFFFFFFFu), in_group(c->n, 0xFFFFFFFFu);
         for (u32 k = 0; k < n_rows; ++k)
             for (u64 e = row_off[k]; e < row_off[k + 1]; ++e) {
                 const u32 q = query_ids[e];
                 if (q >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: query id out of range");
-                lists_dup |= in_row[q] == k;
+                f.lists_dup |= in_row[q] == k;
                 in_row[q] = k;
-                if (in_group[q] != k / PM_GROUP) { in_group[q] = k / PM_GROUP; ++lists_involved; }
+                if (in_group[q] != k / PM_GROUP) { in_group[q] = k / PM_GROUP; ++f.lists_involved; }
             }
     }
-    if (n_pairs == 0) return LZANI_OK;
+    return LZANI_OK;
+}
 
-    HIPCHK(c, hipSetDevice(c->dev));
-    c->km_timed = false;
-    int rc = ensure_kmers(c);
+// The candidate form of a run, the geometry of its candidate bitmaps and its batches: decided once, before the first launch.
+struct RunPlan {
+    // candidates from the presence matrix of a group of references (dense rows), from the join of sorted k-mer lists (long
+    // genomes), or neither: a probe per query position
+    bool pm = false, use_join = false;
+    int Lmax = 0;                 // the longest genome
+    int pm_bits = 0;              // the presence matrix: 2^pm_bits rows of pm_group bits
+    u32 pm_group = PM_GROUP, pm_tiles = 0;
+    u64 cb_words = 0;             // 32-bit words of one pair's candidate bitmap
+    std::vector<u32> bstart;      // batch b: rows [bstart[b], bstart[b + 1])
+};
+
+// A buffer of the context grown to `bytes` (never shrunk); false, the buffer released, where it cannot be had.
+template <class T>
+bool grow(T*& p, size_t& have, size_t bytes)
+{
+    if (have >= bytes) return true;
+    hipFree(p); p = nullptr; have = 0;
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+    have = bytes;
+    return true;
+}
+
+// Batches of consecutive rows: at most rows_cap rows and cap_pairs pairs each.  Returns the most pairs of a batch.
+u64 cut_batches(u32 n_rows, const u64* row_off, u32 rows_cap, u64 cap_pairs, std::vector<u32>& bstart)
+{
+    bstart.assign(1, 0);
+    u32 rows = 0;
+    u64 pairs = 0, most = 0;
+    for (u32 k = 0; k < n_rows; ++k) {
+        const u64 len = row_off[k + 1] - row_off[k];
+        if (rows && (rows == rows_cap || pairs + len > cap_pairs)) { bstart.push_back(k); most = std::max(most, pairs); rows = 0; pairs = 0; }
+        ++rows; pairs += len;
+    }
+    bstart.push_back(n_rows);
+    return std::max(most, pairs);
+}
+
+// Dense rows: the candidates of every pair of a batch come from the presence matrix of its references
+// (lzani_kernels_cand.h) instead of a probe per query position (viral sizes) or a join of sorted k-mer lists per pair
+// (long genomes), where the rows qualify; a batch is then also bounded by what the candidate bitmaps of its pairs take,
+// and the index slabs are sized for such a batch.  p.pm stays clear where the rows do not qualify or do not fit (a genome
+// set this large: the probe / join form, batch by batch), and where a buffer (matrix, pair table, bitmaps) cannot be had
+// after all -- the sizing is an estimate, and hipMalloc may fail on a fragmented heap: the bitmap buffers are then
+// released (the probe / join form needs none of them).
+int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
+{
+    // (from 32 rows on where the probe form with tag words is the alternative; from 8 rows where it is the rounds of the
+    // first kernel: genomes whose tags do not fit a tag byte -- 260 kbp to 2 Mbp at mal 15, viral sizes at mal 13+.
+    // Below, the matrix -- 16 GB to clear at 30 key bits -- costs more than it saves.)
+    // Long genomes (the join is the alternative: 210 ms for the 56 pairs of 8 x 5 Mbp against 149 by bitmaps, 92 with the
+    // pairs cut into segments): from two rows on.
+    const u32 min_rows = k.pm_min_rows ? (u32)std::max(1, *k.pm_min_rows) : c->join_mode ? 2u : c->tw_stride ? 32u : 8u;
+    // Query lists qualify when they are dense where they are: a query that occurs in a group of rows should meet a
+    // good part of it (one matrix row read serves all its pairs of the group) -- the row x column blocks of a tiled
+    // all2all do, the few relatives a kmer-db filter leaves per row do not.  No query twice in a row (one bitmap each).
+    // (Measured in round 4 on the related workload, families of 50 in length order -- 16 pairs per query and group:
+    // the pair kernel gains 18 % from the bitmaps, the candidate stage costs more than that; against the ROUNDS of the
+    // first kernel -- no tag words: long k-mers on mid-size genomes -- the bitmaps win from two pairs per query on.)
+    const u64 min_share = k.pm_min_share.value_or(c->tw_stride ? 48 : 2);
+    const bool lists_ok = !lists || (!f.lists_dup && f.n_pairs >= min_share * f.lists_involved);
+    if (!(!regions && lists_ok && c->d_kmL && c->bk_stride && c->P.mqd + c->P.mrd <= 128 && c->geo.kb <= 30 &&
+          c->n >= 2 && n_rows >= min_rows && k.pm))
+        return LZANI_OK;
+    u64 max_row = 0;
+    for (u32 r = 0; r < n_rows; ++r) max_row = std::max<u64>(max_row, row_off[r + 1] - row_off[r]);
+    p.pm_tiles = (u32)(((u64)p.Lmax + c->P.mrd + 320 + PM_TILE - 1) / PM_TILE);
+    p.cb_words = (u64)p.pm_tiles * PM_TILE_WORDS;
+    p.pm_group = p.pm_bits <= 27 ? (u32)PM_GROUP : 128u;                    // 64-byte rows up to 2^27 of them (8 GB), 16-byte rows beyond (16 GB at 2^30)
+    const size_t m_bytes = ((size_t)1 << p.pm_bits) * (p.pm_group / 8);
+    const size_t x_bytes = lists ? ((size_t)c->n * p.pm_group + 2 * (size_t)c->n + 64) * 4 : 0;   // pair table, query flags, list, count
+    const size_t per_pair = (size_t)p.cb_words * 4;
+    const double avg_row = (double)f.n_pairs / n_rows;
+    const size_t per_slot = (size_t)4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride) + (c->sort_build ? (size_t)16 * c->Tmax + 16 : 0);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    // what this run may lay out anew: the free memory and what the context holds from earlier runs -- ITS slabs
+    // included, which is why slabs larger than this run wants are released below (ensure_slabs never shrinks them:
+    // an earlier run with sparse rows may have grown them to 60 % of the memory)
+    const size_t pool = free_b + (size_t)c->slots * per_slot + c->pm_cbits_bytes + c->pm_bytes + c->pm_pidx_bytes;
+    const size_t cap = k.pm_max_bytes.value_or(std::min((size_t)64 << 30, total_b / 4));
+    const double room = pool * 0.85 - (double)m_bytes - (double)x_bytes;
+    u64 fit = room > 0 ? (u64)(room / ((double)per_slot + avg_row * (double)per_pair)) : 0;     // rows: a slab + its pairs' bitmaps each
+    fit = std::min<u64>(fit, std::min<u32>(n_rows, c->max_slots));
+    u64 cap_pairs = std::min<u64>((u64)(cap / per_pair), 0xFFFFFFF0ull);                           // pair indexes of a batch are 32 bits
+    cap_pairs = std::min<u64>(cap_pairs, (u64)((double)fit * avg_row) + max_row);
+    if (fit < std::min<u32>(8, n_rows) || cap_pairs < max_row) return LZANI_OK;
+    if (c->slots > fit) free_slabs(c);                                     // (counted as available above)
+    if (!grow(c->d_pm, c->pm_bytes, m_bytes) || !grow(c->d_pm_pidx, c->pm_pidx_bytes, x_bytes)) {
+        TRACE("candidate bitmaps: no memory for the matrix / pair table, falling back");
+        free_pm(c);
+        return LZANI_OK;
+    }
+    const int rc = ensure_slabs(c, (u32)fit);
+    if (rc == LZANI_ERR_NOMEM) { free_pm(c); return LZANI_OK; }
     if (rc) return rc;
-    // Dense rows: the candidates of every pair of a batch come from the presence matrix of its references
-    // (lzani_kernels_cand.h) instead of a probe per query position (viral sizes) or a join of sorted k-mer lists per pair
-    // (long genomes); a batch is then also bounded by what the candidate bitmaps of its pairs take, and the index slabs
-    // are sized for such a batch.
-    bool pm = false;
-    u64 cb_words = 0;                                        // 32-bit words of one pair's candidate bitmap
-    u32 pm_tiles = 0, pm_group = PM_GROUP;
+    u32 rows_cap = c->slots;
+    if (!lists) {                                            // dense rows: whole groups of references, if there are several batches
+        u64 r = std::min<u64>(rows_cap, cap_pairs / (u64)(c->n - 1));
+        if (r < n_rows && r > p.pm_group) r -= r % p.pm_group;
+        rows_cap = (u32)std::max<u64>(r, 1);
+    }
+    size_t need = (size_t)cut_batches(n_rows, row_off, rows_cap, cap_pairs, p.bstart) * p.cb_words * 4;
+    if (k.pm_fail_cbits) need = (size_t)1 << 60;                          // tests: the fallback
+    if (!grow(c->d_pm_cbits, c->pm_cbits_bytes, need)) {
+        TRACE("candidate bitmaps: no memory for %zu bytes of bitmaps, falling back", need);
+        free_pm(c);
+        return LZANI_OK;
+    }
+    p.pm = true;
+    return LZANI_OK;
+}
+
+// The plan of a run: candidate bitmaps where the rows qualify and their buffers can be had, else the probe / join form;
+// batches of as many consecutive rows as there are index slabs (and, with bitmaps, as their pairs' bitmaps may take).
+int plan_run(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
+{
+    for (u32 g = 0; g < c->n; ++g) p.Lmax = std::max(p.Lmax, c->L[g]);
     // rows of the presence matrix: one per k-mer (exact: the mixer is a bijection on the key bits) where the genomes fill a fair
     // part of the key space, else the hash's top bits -- 2^9 rows per text position keep the false candidates below 0.2 % of the
     // query positions, and a group's matrix is cleared and built in proportion to the genomes, not to 4^mal
-    const int pm_bits = std::min(std::min(c->geo.kb, 30), ceil_log2((u64)std::max(c->Tmax, 1)) + 9);
-    bool use_join = false;
-    std::vector<u32> bstart;
-    // Two attempts: the candidate-bitmap form first where it applies; if its buffers (matrix, pair table, bitmaps) cannot be
-    // had after all -- the sizing below is an estimate, and hipMalloc may fail on a fragmented heap -- they are released
-    // and the run falls back to the probe / join form, which needs none of them.
-    for (int attempt = 0; attempt < 2; ++attempt) {
-    pm = false;
-    u32 want_rows = n_rows;
-    u64 pm_cap_pairs = 0;                                    // pairs whose bitmaps a batch may hold
-    bool pm_nomem = false;
-    if (attempt == 0) {
-        const char* e = getenv("LZANI_PM");
-        const char* mn = getenv("LZANI_PM_MIN_ROWS");
-        const char* mb = getenv("LZANI_PM_MAX_BYTES");
-        // (from 32 rows on where the probe form with tag words is the alternative; from 8 rows where it is the rounds of the
-        // first kernel: genomes whose tags do not fit a tag byte -- 260 kbp to 2 Mbp at mal 15, viral sizes at mal 13+.
-        // Below, the matrix -- 16 GB to clear at 30 key bits -- costs more than it saves.)
-        // Long genomes (the join is the alternative: 210 ms for the 56 pairs of 8 x 5 Mbp against 149 by bitmaps, 92 with the
-        // pairs cut into segments): from two rows on.
-        const u32 min_rows = mn ? (u32)std::max(1, atoi(mn)) : c->join_mode ? 2u : c->tw_stride ? 32u : 8u;
-        // Query lists qualify when they are dense where they are: a query that occurs in a group of rows should meet a
-        // good part of it (one matrix row read serves all its pairs of the group) -- the row x column blocks of a tiled
-        // all2all do, the few relatives a kmer-db filter leaves per row do not.  No query twice in a row (one bitmap each).
-        // (Measured in round 4 on the related workload, families of 50 in length order -- 16 pairs per query and group:
-        // the pair kernel gains 18 % from the bitmaps, the candidate stage costs more than that; against the ROUNDS of the
-        // first kernel -- no tag words: long k-mers on mid-size genomes -- the bitmaps win from two pairs per query on.)
-        const char* sh = getenv("LZANI_PM_MIN_SHARE");
-        const u64 min_share = sh ? strtoull(sh, nullptr, 10) : c->tw_stride ? 48 : 2;
-        const bool lists_ok = !query_ids || (!lists_dup && n_pairs >= min_share * lists_involved);
-        pm = !rs && lists_ok && c->d_kmL && c->bk_stride && c->P.mqd + c->P.mrd <= 128 && c->geo.kb <= 30 &&
-             c->n >= 2 && n_rows >= min_rows && !(e && *e == '0');
-        if (pm) {
-            int Lmax = 0;
-            u64 max_row = 0;
-            for (u32 g = 0; g < c->n; ++g) Lmax = std::max(Lmax, c->L[g]);
-            for (u32 k = 0; k < n_rows; ++k) max_row = std::max<u64>(max_row, row_off[k + 1] - row_off[k]);
-            pm_tiles = (u32)(((u64)Lmax + c->P.mrd + 320 + PM_TILE - 1) / PM_TILE);
-            cb_words = (u64)pm_tiles * PM_TILE_WORDS;
-            pm_group = pm_bits <= 27 ? (u32)PM_GROUP : 128u;                      // 64-byte rows up to 2^27 of them (8 GB), 16-byte rows beyond (16 GB at 2^30)
-            const size_t m_bytes = ((size_t)1 << pm_bits) * (pm_group / 8);
-            const size_t x_bytes = query_ids ? ((size_t)c->n * pm_group + 2 * (size_t)c->n + 64) * 4 : 0;   // pair table, query flags, list, count
-            const size_t per_pair = (size_t)cb_words * 4;
-            const double avg_row = (double)n_pairs / n_rows;
-            const size_t per_slot = (size_t)4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride) + (c->sort_build ? (size_t)16 * c->Tmax + 16 : 0);
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-            // what this run may lay out anew: the free memory and what the context holds from earlier runs -- ITS slabs
-            // included, which is why slabs larger than this run wants are released below (ensure_slabs never shrinks them:
-            // an earlier run with sparse rows may have grown them to 60 % of the memory)
-            const size_t pool = free_b + (size_t)c->slots * per_slot + c->pm_cbits_bytes + c->pm_bytes + c->pm_pidx_bytes;
-            const size_t cap = mb ? (size_t)strtoull(mb, nullptr, 10) : std::min((size_t)64 << 30, total_b / 4);
-            const double room = pool * 0.85 - (double)m_bytes - (double)x_bytes;
-            u64 fit = room > 0 ? (u64)(room / ((double)per_slot + avg_row * (double)per_pair)) : 0;     // rows: a slab + its pairs' bitmaps each
-            fit = std::min<u64>(fit, std::min<u32>(n_rows, c->max_slots));
-            pm_cap_pairs = std::min<u64>((u64)(cap / per_pair), 0xFFFFFFF0ull);                          // pair indexes of a batch are 32 bits
-            pm_cap_pairs = std::min<u64>(pm_cap_pairs, (u64)((double)fit * avg_row) + max_row);
-            if (fit < std::min<u32>(8, n_rows) || pm_cap_pairs < max_row) pm = false;    // (a genome set this large: the probe / join form, batch by batch)
-            else {
-                want_rows = (u32)fit;
-                if (c->slots > want_rows) free_slabs(c);                         // (counted as available above)
-                if (c->pm_bytes < m_bytes) {
-                    hipFree(c->d_pm); c->d_pm = nullptr; c->pm_bytes = 0;
-                    if (hipMalloc(&c->d_pm, m_bytes) != hipSuccess) { (void)hipGetLastError(); c->d_pm = nullptr; pm_nomem = true; }
-                    else c->pm_bytes = m_bytes;
-                }
-                if (!pm_nomem && c->pm_pidx_bytes < x_bytes) {
-                    hipFree(c->d_pm_pidx); c->d_pm_pidx = nullptr; c->pm_pidx_bytes = 0;
-                    if (hipMalloc(&c->d_pm_pidx, x_bytes) != hipSuccess) { (void)hipGetLastError(); c->d_pm_pidx = nullptr; pm_nomem = true; }
-                    else c->pm_pidx_bytes = x_bytes;
-                }
-            }
-        }
-    }
-    if (pm_nomem) { TRACE("candidate bitmaps: no memory for the matrix / pair table, falling back"); free_pm(c); continue; }
-    use_join = c->join_mode && !pm;
-    if (use_join) { rc = ensure_join(c); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
-    rc = ensure_slabs(c, want_rows);
-    if (rc) {
-        if (pm && rc == LZANI_ERR_NOMEM) { free_pm(c); continue; }
-        return rc;
-    }
-    // Batches: as many consecutive rows as there are index slabs -- and, with candidate bitmaps, as their pairs' bitmaps
-    // may take.
-    bstart.assign(1, 0);
-    {
-        u32 rows = 0, rows_cap = c->slots;
-        u64 pairs = 0, most = 0;
-        if (pm && !query_ids) {                              // dense rows: whole groups of references, if there are several batches
-            u64 r = std::min<u64>(rows_cap, pm_cap_pairs / (u64)(c->n - 1));
-            if (r < n_rows && r > pm_group) r -= r % pm_group;
-            rows_cap = (u32)std::max<u64>(r, 1);
-        }
-        for (u32 k = 0; k < n_rows; ++k) {
-            const u64 len = row_off[k + 1] - row_off[k];
-            if (rows && (rows == rows_cap || (pm && pairs + len > pm_cap_pairs))) { bstart.push_back(k); most = std::max(most, pairs); rows = 0; pairs = 0; }
-            ++rows; pairs += len;
-        }
-        bstart.push_back(n_rows);
-        most = std::max(most, pairs);
-        if (pm) {
-            size_t need = (size_t)most * cb_words * 4;
-            if (const char* fe = getenv("LZANI_PM_FAIL_CBITS")) if (*fe == '1') need = (size_t)1 << 60;     // tests: the fallback below
-            if (c->pm_cbits_bytes < need) {
-                hipFree(c->d_pm_cbits); c->d_pm_cbits = nullptr; c->pm_cbits_bytes = 0;
-                if (hipMalloc(&c->d_pm_cbits, need) != hipSuccess) {
-                    (void)hipGetLastError();
-                    c->d_pm_cbits = nullptr;
-                    TRACE("candidate bitmaps: no memory for %zu bytes of bitmaps, falling back", need);
-                    free_pm(c);
-                    continue;
-                }
-                c->pm_cbits_bytes = need;
-            }
-        }
-    }
-    break;
-    }
-    const u32 bs = c->slots;
+    p.pm_bits = std::min(std::min(c->geo.kb, 30), ceil_log2((u64)std::max(c->Tmax, 1)) + 9);
+    int rc = plan_bitmaps(c, k, f, n_rows, row_off, lists, regions, p);
+    if (rc || p.pm) return rc;
+    p.use_join = c->join_mode;
+    if (p.use_join) { rc = ensure_join(c); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
+    rc = ensure_slabs(c, n_rows);
+    if (rc) return rc;
+    cut_batches(n_rows, row_off, c->slots, ~0ull, p.bstart);
+    return LZANI_OK;
+}
 
-    // Batches of `bs` rows (one index slab per row).  Everything the batches need from the host -- row tables
-    // and the per-XCD work queues of every batch -- is prepared and uploaded before the first launch, so the
-    // batches follow each other on the stream without a host round trip in between.
+// The per-XCD work queues of every batch (host only): a batch's rows, longest first onto the least loaded queue (equal
+// rows: round robin).  qorder: the batch's rows queue after queue, qcum: their running pair count (one entry more per
+// batch), qb: where each queue begins in qorder.
+struct QueuePlan { std::vector<u32> qorder; std::vector<u64> qcum; std::vector<u32> qb; };
+
+QueuePlan plan_queues(u32 n_rows, const u64* row_off, const std::vector<u32>& bstart)
+{
     const u32 n_batches = (u32)bstart.size() - 1;
-    c->batches_last_run = n_batches;
-    std::vector<u32> qorder(n_rows);
-    std::vector<u64> qcum((size_t)n_rows + n_batches);
-    std::vector<u32> qb((size_t)n_batches * (NQUEUES + 1));
-    {
-        std::vector<u32> by_size;
-        std::vector<u32> queue[NQUEUES];
-        for (u32 b = 0; b < n_batches; ++b) {
-            const u32 k0 = bstart[b], rows = bstart[b + 1] - k0;
-            auto rlen = [&](u32 k) { return row_off[k0 + k + 1] - row_off[k0 + k]; };
-            // rows -> queues: longest row first onto the least loaded queue (equal rows: round robin)
-            by_size.resize(rows);
-            for (u32 k = 0; k < rows; ++k) by_size[k] = k;
-            std::stable_sort(by_size.begin(), by_size.end(), [&](u32 x, u32 y) { return rlen(x) > rlen(y); });
-            u64 load[NQUEUES] = {0};
-            for (auto& q : queue) q.clear();
-            for (u32 k : by_size) {
-                u32 best = 0;
-                for (u32 x = 1; x < NQUEUES; ++x) if (load[x] < load[best]) best = x;
-                queue[best].push_back(k);
-                load[best] += rlen(k);
-            }
-            u32 at = 0;
-            u64 cum = 0;
-            u32* qo = qorder.data() + k0;
-            u64* qc = qcum.data() + k0 + b;
-            qc[0] = 0;
-            for (u32 x = 0; x < NQUEUES; ++x) {
-                qb[(size_t)b * (NQUEUES + 1) + x] = at;
-                for (u32 k : queue[x]) { qo[at] = k; cum += rlen(k); qc[++at] = cum; }
-            }
-            qb[(size_t)b * (NQUEUES + 1) + NQUEUES] = at;
-        }
-    }
-
-    DevBuf<u32> d_ref, d_q, d_qorder;
-    DevBuf<u64> d_off, d_qcum;
-    HIPCHK(c, d_qorder.alloc(n_rows));
-    HIPCHK(c, d_qcum.alloc(qcum.size()));
-    HIPCHK(c, d_ref.alloc(n_rows));
-    HIPCHK(c, d_off.alloc((size_t)n_rows + 1));
-    HIPCHK(c, hipMemcpyAsync(d_ref, ref_ids, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_off, row_off, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_qorder, qorder.data(), qorder.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_qcum, qcum.data(), qcum.size() * 8, hipMemcpyHostToDevice, c->stream));
-    if (query_ids) {
-        HIPCHK(c, d_q.alloc(n_pairs));
-        HIPCHK(c, hipMemcpyAsync(d_q, query_ids, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    enum { EV = 5 };
-    while (c->events.size() < (size_t)EV * n_batches) {       // five stamps per batch, read back after the one sync
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreate(&e));
-        c->events.push_back(e);
-    }
-
-    u32 blocks_per_cu = 8;                                   // 8 blocks x 4 waves = 8 waves per SIMD
-    if (const char* e = getenv("LZANI_BLOCKS_PER_CU")) blocks_per_cu = (u32)std::max(1, std::min(8, atoi(e)));   // occupancy experiments
-    const u32 max_blocks = (u32)c->n_cus * blocks_per_cu;
-    const Params& q = c->P;
-    const bool defp = q.mal == 11 && q.msl == 7 && q.mrd == 40 && q.mqd == 40 && q.reg == 35 && q.aw == 15 && q.am == 7 && q.ar == 3;
-    // the long-genome parameters (--mal 15 --msl 9 --reg 60, BASELINE configs[3]): the second set the pair kernel folds into
-    // its code, the hand-written null chain included (bitmap and join forms)
-    const bool lgp = q.mal == 15 && q.msl == 9 && q.mrd == 40 && q.mqd == 40 && q.reg == 60 && q.aw == 15 && q.am == 7 && q.ar == 3;
-    std::vector<char> launched(n_batches, 0);
-    std::vector<u32> grp_seen;                               // (query lists + candidate bitmaps) the group a query was last seen in
-    u32 grp_stamp = 0;
-    const char* const bkenv = getenv("LZANI_BLOCK_KERNEL");
-    DevBuf<unsigned long long> d_cbits;                      // join form: one candidate bitmap per resident wave
-    u64 cbits_stride = 0;
-    if (use_join && !rs) {
-        int Lmax = 0;
-        for (u32 g = 0; g < c->n; ++g) Lmax = std::max(Lmax, c->L[g]);
-        cbits_stride = (u64)((Lmax + c->P.mrd) >> 6) + 8;
-        HIPCHK(c, d_cbits.alloc((size_t)max_blocks * 4 * cbits_stride));
-    }
-
-    // Any other parameter tuple: the same kernel compiled for it the first time this context needs it (lzani_rtc.h) -- the
-    // eight ints folded into the code, the hand-written null chain included where the tuple is inside what the chain is
-    // written for (chain_params_ok).  Built (or loaded from the disk cache) here, ahead of the stream's first stamp.
-    // A compile takes 2-3 s and the folded kernel saves ~0.13 s per million pairs of 40 kbp: a code object that is not in
-    // the disk cache yet is built once the context has been asked for LZANI_RTC_MIN_PAIRS pairs in all (default 2 M: the
-    // first such run loses a second or two, every later run and every later process wins).
-    lzani_rtc::Kernel* rtc_k = nullptr;
-    int rtc_id = PK_RTC_N0_C0;                               // (its row of the launch record)
-    c->pairs_seen += n_pairs;
-    if (!defp && !lgp && !rs && c->d_kmL && c->d_bk && lzani_rtc::enabled()) {
-        const int cand = pm ? 2 : (use_join && c->d_tw) ? 1 : c->d_tw ? 0 : -1;
-        const char* mp = getenv("LZANI_RTC_MIN_PAIRS");
-        const u64 min_pairs = mp ? strtoull(mp, nullptr, 10) : 2000000ull;
-        if (cand >= 0) {
-            rtc_id = PK_RTC_N0_C0 + 3 * (int)c->all_nfree + cand;
-            rtc_k = lzani_rtc::get(c->rtc, c->P, c->all_nfree, cand, c->arch.c_str(), c->pairs_seen >= min_pairs);
-            if (!rtc_k && c->rtc.failed) TRACE("run-time compile unavailable (%s): the generic kernel runs", c->rtc.log.c_str());
-        }
-    }
-
+    QueuePlan qp{std::vector<u32>(n_rows), std::vector<u64>((size_t)n_rows + n_batches), std::vector<u32>((size_t)n_batches * (NQUEUES + 1))};
+    std::vector<u32> by_size, queue[NQUEUES];
     for (u32 b = 0; b < n_batches; ++b) {
         const u32 k0 = bstart[b], rows = bstart[b + 1] - k0;
-        const u64 e0 = row_off[k0], e1 = row_off[k0 + rows];
-        hipEvent_t* ev = c->events.data() + (size_t)EV * b;
-        TRACE("batch %u rows [%u,%u) pairs [%llu,%llu) slots=%u pm=%d", b, k0, k0 + rows, (unsigned long long)e0, (unsigned long long)e1, bs, (int)pm);
-        HIPCHK(c, hipEventRecord(ev[0], c->stream));
-        // rows for k_pairs_blk (see below): dense, hundreds of pairs each, probe form with tag words and a filter
-        const bool blk_rows = !pm && !rs && c->d_kmL && c->tw_stride && !c->join_mode && c->fl_stride && e1 > e0 && (e1 - e0) / rows >= 128 &&
-                              (bkenv ? *bkenv == '1' : query_ids == nullptr);
-        rc = build_indexes(c, d_ref + k0, rows, blk_rows, !pm);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(ev[1], c->stream));
-        // Few, long pairs (the batch leaves a wave slot only a few of them): the launch is over when its slowest pair is, so
-        // the pairs with the most candidates -- the related ones -- go first (k_pm_cand counts, k_lpt_keys + a sort order)
-        // ... and fewer pairs than half the wave slots: every pair by several waves, segment by segment (lzani_kernels_split.h)
-        u32 split_S = 0;
-        int split_seglen = 0;
-        if (pm && !rs && e1 > e0 && c->P.mqd + c->P.mrd <= 128) {
-            const char* se = getenv("LZANI_SPLIT");
-            const char* sl = getenv("LZANI_SPLIT_SEGLEN");
-            const u64 bp = e1 - e0, slots = (u64)max_blocks * 4;
-            int Lmax = 0;
-            for (u32 g = 0; g < c->n; ++g) Lmax = std::max(Lmax, c->L[g]);
-            const int Dmax = Lmax + c->P.mrd;
-            // (measured at the end of round 4, 5 Mbp: 56 pairs 6 ms a launch instead of 148, 240 pairs 8 instead of 147, 992 pairs 47
-            // instead of 148: from 8 wave slots per pair on)
-            // (... measured at 5 Mbp; for shorter queries -- from 256 kbp on -- from 16 wave slots per pair, as the suite has run it)
-            const bool on = se ? *se == '1' : (cb_words >= 8192 && (bp * 16 <= slots || (cb_words >= 65536 && bp * 8 <= slots)));
-            if (on && bp * 2 <= 0xFFFFFFFFull / 64) {
-                const char* sse = getenv("LZANI_SPLIT_S");
-                u32 S = (u32)std::min<u64>(sse ? (u64)std::max(2, atoi(sse)) : 64, std::max<u64>(2, slots / bp));      // (8 x 5 Mbp: 67 / 58 / 42 ms a launch with 16 / 32 / 64 a pair)
-                int seglen = (Dmax + (int)S - 1) / (int)S;
-                if (sl && atoi(sl) > 0) { seglen = atoi(sl); S = (u32)std::min<int>(64, std::max(2, (Dmax + seglen - 1) / seglen)); }
-                seglen = std::max(seglen, 512);
-                if ((Dmax + seglen - 1) / seglen >= 2) { split_S = std::min<u32>(S, (u32)((Dmax + seglen - 1) / seglen)); split_seglen = seglen; }
-            }
+        auto rlen = [&](u32 k) { return row_off[k0 + k + 1] - row_off[k0 + k]; };
+        by_size.resize(rows);
+        for (u32 k = 0; k < rows; ++k) by_size[k] = k;
+        std::stable_sort(by_size.begin(), by_size.end(), [&](u32 x, u32 y) { return rlen(x) > rlen(y); });
+        u64 load[NQUEUES] = {0};
+        for (auto& q : queue) q.clear();
+        for (u32 k : by_size) {
+            u32 best = 0;
+            for (u32 x = 1; x < NQUEUES; ++x) if (load[x] < load[best]) best = x;
+            queue[best].push_back(k);
+            load[best] += rlen(k);
         }
-        bool lpt = false;
-        if (pm && e1 > e0) {
-            const char* le = getenv("LZANI_LPT");
-            const u64 bp = e1 - e0;
-            lpt = !rs && bp >= 2 && bp <= (u64)max_blocks * 4 * 32 && (le ? *le == '1' : cb_words >= 8192);     // (queries from ~256 kbp on)
-            if (le && *le == '0') lpt = false;
-            if (split_S >= 2) lpt = true;                        // (the split wants the candidate counts: which pairs to cut, which first)
-            if (lpt && c->lpt_pairs < bp) {
-                hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
-                c->d_lpt_cnt = nullptr; c->d_lpt_keys = nullptr; c->lpt_pairs = 0;
-                if (hipMalloc(&c->d_lpt_cnt, (size_t)bp * 4) != hipSuccess || hipMalloc(&c->d_lpt_keys, (size_t)bp * 16) != hipSuccess) {
-                    (void)hipGetLastError();
-                    hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
-                    c->d_lpt_cnt = nullptr; c->d_lpt_keys = nullptr;
-                    lpt = false;                                 // (placement only: the run goes on without it)
-                } else c->lpt_pairs = (size_t)bp;
-            }
-            if (lpt) HIPCHK(c, hipMemsetAsync(c->d_lpt_cnt, 0, (size_t)bp * 4, c->stream));
+        u32 at = 0;
+        u64 cum = 0;
+        u32* qo = qp.qorder.data() + k0;
+        u64* qc = qp.qcum.data() + k0 + b;
+        qc[0] = 0;
+        for (u32 x = 0; x < NQUEUES; ++x) {
+            qp.qb[(size_t)b * (NQUEUES + 1) + x] = at;
+            for (u32 k : queue[x]) { qo[at] = k; cum += rlen(k); qc[++at] = cum; }
         }
-        if (pm && e1 > e0) {
-            // candidate bitmaps of the batch's pairs, group by group of PM_GROUP references
-            for (u32 g0 = 0; g0 < rows; g0 += pm_group) {
-                PmArgs pg;
-                pg.G = gtab(c);
-                pg.ref_ids = d_ref + k0; pg.row_off = d_off + k0;
-                pg.slot0 = g0; pg.rows = std::min<u32>(pm_group, rows - g0);
-                pg.M = c->d_pm; pg.rw = ((pg.rows + 127) / 128) * 4; pg.mmask = (u32)lowmask(pm_bits); pg.rshift = c->geo.kb - pm_bits;
-                pg.mal = c->P.mal; pg.mrd = c->P.mrd;
-                pg.cbits = c->d_pm_cbits; pg.cb_words = cb_words; pg.e0 = e0; pg.n = c->n; pg.q0 = 0;
-                pg.query_ids = d_q.p; pg.pidx = nullptr; pg.qflag = pg.qlist = pg.qcount = nullptr;
-                pg.pcount = lpt ? c->d_lpt_cnt : nullptr;
-                if (query_ids) {                            // the lists of the group's rows -> pair table + the queries involved
-                    const size_t tab = (size_t)c->n * 32 * pg.rw;
-                    pg.pidx = c->d_pm_pidx; pg.qflag = c->d_pm_pidx + (size_t)c->n * pm_group; pg.qlist = pg.qflag + c->n; pg.qcount = pg.qlist + c->n;
-                    HIPCHK(c, hipMemsetAsync(pg.pidx, 0xFF, tab * 4, c->stream));
-                    HIPCHK(c, hipMemsetAsync(pg.qflag, 0, ((size_t)2 * c->n + 1) * 4, c->stream));
-                    hipLaunchKernelGGL(k_pm_pairs, dim3(pg.rows), dim3(256), 0, c->stream, pg);
-                }
-                // the matrix: from the group's indexes, chunk by chunk through LDS (long genomes: no global atomics, no clearing),
-                // or by one atomicOr per text position into the cleared matrix
-                const int tbits = c->geo.kb - c->geo.dirbits;
-                // (chunks of 64 KB: two blocks = 32 waves a CU; with 128 KB chunks, one block a CU, the matrix of 128 x 5 Mbp took 3 ms more)
-                const int rcl = std::min(pm_bits, pg.rw <= 4 ? 12 : pg.rw <= 8 ? 11 : 10);
-                const char* fie = getenv("LZANI_PM_FROM_INDEX");
-                const bool from_index = c->geo.tagmask == (u32)lowmask(tbits) && pm_bits == c->geo.kb && rcl >= tbits &&
-                                        (fie ? *fie == '1' : pm_bits > 24);
-                if (from_index) {
-                    c->pmfi_launches += 1;
-                    const size_t fl = ((size_t)pg.rw << rcl) * 4;
-                    const dim3 gi(1u << (pm_bits - rcl)), bi(1024);
-#define LZ_PM_FI(RW) do { \
-                        if (!(c->pmfi_attr_set & (1u << RW))) { \
-                            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_from_index<RW>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
-                            c->pmfi_attr_set |= 1u << RW; \
-                        } \
-                        hipLaunchKernelGGL(k_pm_from_index<RW>, gi, bi, fl, c->stream, pg, c->d_dirz, c->d_ent, c->dir_stride, c->ent_stride, tbits, c->geo.posbits, rcl); \
-                    } while (0)
-                    switch (pg.rw) {
-                    case 4: LZ_PM_FI(4); break;
-                    case 8: LZ_PM_FI(8); break;
-                    case 12: LZ_PM_FI(12); break;
-                    default: LZ_PM_FI(16); break;
-                    }
-#undef LZ_PM_FI
-                } else {
-                    HIPCHK(c, hipMemsetAsync(c->d_pm, 0, ((size_t)1 << pm_bits) * pg.rw * 4, c->stream));
-                    hipLaunchKernelGGL(k_pm_build, dim3((u32)std::min<u64>(((u64)c->Tmax + 255) / 256, 64), pg.rows), dim3(256), 0, c->stream, pg, c->Tmax);
-                }
-                const u32 rp = 32 * pg.rw;
-                const size_t lds = (size_t)(PM_TILE_WORDS * (rp + 1) + rp) * 4;
-                if (!c->pm_attr_set) {
-                    const size_t lmax = (size_t)(PM_TILE_WORDS * (PM_GROUP + 1) + PM_GROUP) * 4;
-                    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-                    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-                    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-                    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-                    c->pm_attr_set = true;
-                }
-                // (query lists: one row of blocks per query that occurs in the group -- counted here, the device list is
-                // k_pm_pairs' -- not per genome: 20,000 genomes x 44 tiles of blocks that find nothing to do were most of
-                // the candidate stage of a filtered run)
-                u32 nq = c->n;
-                if (query_ids) {
-                    if (grp_seen.size() != c->n) grp_seen.assign(c->n, 0xFFFFFFFFu);
-                    const u32 stamp = ++grp_stamp;
-                    nq = 0;
-                    for (u64 e = row_off[k0 + g0]; e < row_off[k0 + g0 + pg.rows]; ++e)
-                        if (grp_seen[query_ids[e]] != stamp) { grp_seen[query_ids[e]] = stamp; ++nq; }
-                }
-                for (u32 q0 = 0; q0 < nq; q0 += 32768) {       // gridDim.y is limited to 65535
-                    pg.q0 = q0;
-                    const dim3 gc(pm_tiles, std::min<u32>(32768, nq - q0)), bc(PM_CAND_THREADS);
-                    switch (pg.rw / 4) {
-                    case 1: hipLaunchKernelGGL(k_pm_cand<1>, gc, bc, lds, c->stream, pg); break;
-                    case 2: hipLaunchKernelGGL(k_pm_cand<2>, gc, bc, lds, c->stream, pg); break;
-                    case 3: hipLaunchKernelGGL(k_pm_cand<3>, gc, bc, lds, c->stream, pg); break;
-                    default: hipLaunchKernelGGL(k_pm_cand<4>, gc, bc, lds, c->stream, pg); break;
-                    }
-                }
-                c->tm.cand_launches += 2;
-            }
-            if (!lpt || c->d_lpt_cnt == nullptr) split_S = 0;    // (no candidate counts after all -- their buffer could not be had: no split)
-            if (lpt && split_S < 2) {                        // the ticket order of the batch's queues
-                const u64 bp = e1 - e0;
-                QueueBounds qbv;
-                for (int x = 0; x <= NQUEUES; ++x) qbv.v[x] = qb[(size_t)b * (NQUEUES + 1) + x];
-                hipLaunchKernelGGL(k_lpt_keys, dim3((u32)std::min<u64>((bp + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                                   d_qorder + k0, d_qcum + k0 + b, qbv, d_off + k0, e0, c->d_lpt_cnt, c->d_lpt_keys, rows, bp);
-                size_t need = 0;
-                int e = lzani_sort_keys(c->d_lpt_keys, c->d_lpt_keys + bp, bp, 32, 56, nullptr, &need, c->stream);
-                if (e == 0 && need > c->jtmp_bytes) {
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    hipFree(c->d_jtmp); c->d_jtmp = nullptr; c->jtmp_bytes = 0;
-                    HIPCHK(c, hipMalloc(&c->d_jtmp, need));
-                    c->jtmp_bytes = need;
-                }
-                need = c->jtmp_bytes;
-                if (e == 0) e = lzani_sort_keys(c->d_lpt_keys, c->d_lpt_keys + bp, bp, 32, 56, c->d_jtmp, &need, c->stream);
-                if (e != 0) return fail(c, LZANI_ERR_DEVICE, "ticket order: radix sort failed");
-            }
-            HIPCHK(c, hipGetLastError());
-        }
-        HIPCHK(c, hipEventRecord(ev[4], c->stream));
-        if (e1 > e0) {
-            PairArgs pa;
-            pa.G = gtab(c);
-            pa.P = c->P; pa.geo = c->geo;
-            pa.dirz = c->d_dirz; pa.ent = c->d_ent;
-            pa.dir_stride = c->dir_stride; pa.ent_stride = c->ent_stride;
-            pa.bk = c->d_bk; pa.bk_stride = c->bk_stride;
-            pa.tw = c->d_tw; pa.tw_stride = c->tw_stride;
-            pa.fl = c->d_fl; pa.fl_stride = c->fl_stride; pa.fmask = c->fmask;
-            pa.ref_ids = d_ref + k0; pa.row_off = d_off + k0; pa.query_ids = d_q;
-            pa.out = d_out; pa.cursor = c->d_cursor;
-            pa.qorder = d_qorder + k0; pa.qcum = d_qcum + k0 + b;
-            for (int x = 0; x <= NQUEUES; ++x) pa.qb[x] = qb[(size_t)b * (NQUEUES + 1) + x];
-            pa.skeys = cbits_stride ? c->d_jkeys : nullptr; pa.soff = c->d_jsoff; pa.scnt = c->d_jcnt;
-            pa.cbits = d_cbits.p; pa.cbits_stride = cbits_stride; pa.cb_e0 = 0;
-            if (pm) { pa.cbits = reinterpret_cast<unsigned long long*>(c->d_pm_cbits); pa.cbits_stride = cb_words / 2; pa.cb_e0 = e0; }
-            pa.reg_out = rs ? rs->d_regions : nullptr; pa.reg_count = rs ? rs->d_count : nullptr; pa.reg_cap = rs ? rs->capacity : 0;
-            pa.torder = (lpt && split_S < 2) ? c->d_lpt_keys + (e1 - e0) : nullptr;
-            c->lpt_launches += (lpt && split_S < 2) ? 1 : 0;
-            HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, NQUEUES * sizeof(unsigned long long), c->stream));
-            const u64 waves = e1 - e0;
-            const dim3 gd((u32)std::min<u64>((waves + 3) / 4, max_blocks)), bd(256);
-            HIPCHK(c, hipEventRecord(ev[2], c->stream));
-#define LZ_PAIRS(F, N, D, A, B) do { hipLaunchKernelGGL((k_pairs<F, N, D, A, B>), gd, bd, 0, c->stream, pa); PK_COUNT_LAUNCH(PK_PAIRS, F, N, D, A, B, 0, 0); } while (0)
-#define LZ_PAIRS_JOIN(N, D) do { hipLaunchKernelGGL((k_pairs<true, N, D, false, true, 1>), gd, bd, 0, c->stream, pa); PK_COUNT_LAUNCH(PK_PAIRS, true, N, D, false, true, 1, 0); } while (0)
-#define LZ_PAIRS_PM(N, D) do { hipLaunchKernelGGL((k_pairs<true, N, D, false, true, 2>), gd, bd, 0, c->stream, pa); PK_COUNT_LAUNCH(PK_PAIRS, true, N, D, false, true, 2, 0); } while (0)
-            const bool fast = c->d_kmL != nullptr, tw = pa.tw != nullptr, nf = c->all_nfree;
-            auto rtc_launch = [&]() -> bool {
-                if (!rtc_k) return false;
-                void* kargs[] = {&pa};
-                if (hipModuleLaunchKernel(rtc_k->fn, gd.x, 1, 1, bd.x, 1, 1, 0, c->stream, kargs, nullptr) != hipSuccess) { (void)hipGetLastError(); return false; }
-                c->rtc_launches += 1;
-                c->klaunch[rtc_id] += 1;
-                return true;
-            };
-            // Probe form, dense rows of hundreds of pairs: blocks of 16 waves with the reference's presence filter in LDS
-            // (k_pairs_blk).  The rows a kmer-db filter leaves hold related pairs, where most positions pass the filter:
-            // BASELINE configs[4] at full size is 6 % slower this way; LZANI_BLOCK_KERNEL=1/0 overrides.
-            bool use_blk = blk_rows && fast && tw && !pa.skeys;
-            const void* kf = nf ? (defp ? (const void*)k_pairs_blk<true, true> : (const void*)k_pairs_blk<true, false>)
-                                : (defp ? (const void*)k_pairs_blk<false, true> : (const void*)k_pairs_blk<false, false>);
-            if (use_blk && c->blk_fold == -1) {     // the largest LDS copy of the filter that leaves two blocks per CU
-                for (int fold = 0; fold <= 4 && c->blk_fold < 0; ++fold) {
-                    const size_t l = (size_t)(BLK_WAVES * SEED_LDS_WORDS + std::max<u64>(c->fl_stride >> fold, 1)) * 4;
-                    if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l) != hipSuccess) { (void)hipGetLastError(); continue; }
-                    int nb = 0;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * BLK_WAVES, l) == hipSuccess && nb >= 2) c->blk_fold = fold;
-                }
-                (void)hipGetLastError();
-                if (c->blk_fold < 0) c->blk_fold = -2;                  // none does: the wave kernel takes these rows too
-            }
-            if (c->blk_fold < 0) use_blk = false;
-            if (use_blk && !c->d_blkctr) HIPCHK(c, hipMalloc(&c->d_blkctr, (size_t)c->n_cus * 2 * 4));
-            if (rs) {                                   // alignment output: one generic instantiation per index form
-                if (!fast) LZ_PAIRS(false, false, false, true, false);
-                else if (tw) LZ_PAIRS(true, false, false, true, true);
-                else LZ_PAIRS(true, false, false, true, false);
-            } else if (!fast) LZ_PAIRS(false, false, false, false, false);
-            else if (pm && split_S >= 2) {               // few, long pairs: several waves a pair (lzani_kernels_split.h)
-                c->pm_launches += 1;
-                c->split_launches += 1;
-                const u32 npb = (u32)(e1 - e0), S = split_S;
-                DevBuf<SplitStart> d_cuts;
-                DevBuf<SplitOut> d_souts;
-                DevBuf<u32> d_work, d_next, d_cnt;
-                DevBuf<unsigned char> d_done, d_heavy;
-                HIPCHK(c, d_cuts.alloc((size_t)npb * S));
-                HIPCHK(c, d_souts.alloc((size_t)npb * S));
-                HIPCHK(c, d_work.alloc((size_t)npb * S));
-                HIPCHK(c, d_next.alloc((size_t)npb * S));
-                HIPCHK(c, d_cnt.alloc(12));
-                HIPCHK(c, d_done.alloc(npb));
-                HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 48, c->stream));
-                HIPCHK(c, hipMemsetAsync(d_done.p, 0, npb, c->stream));
-                HIPCHK(c, hipMemsetAsync(d_cuts.p, 0xFF, (size_t)npb * S * sizeof(SplitStart), c->stream));      // (cut 0 of every pair: no checkpoint)
-                SplitArgs sa;
-                sa.pa = pa; sa.rows = rows; sa.n_pairs = npb; sa.S = S; sa.seglen = split_seglen;
-                sa.cuts = d_cuts.p; sa.outs = d_souts.p; sa.work = d_work.p; sa.work_next = d_next.p; sa.counters = d_cnt.p; sa.done = d_done.p;
-                sa.reg = c->P.reg; sa.last_round = 0;
-                const int dsel = defp ? 1 : lgp ? 2 : 0;
-                auto launch = [&](int mode, u32 items) {
-                    const dim3 gs((u32)std::min<u64>(((u64)items + 3) / 4, max_blocks)), bs4(256);
-                    sa.n_work = items;
-#define LZ_SPLIT(N, D) do { if (mode == 0) { hipLaunchKernelGGL((k_split<N, D, 0>), gs, bs4, 0, c->stream, sa); PK_COUNT_LAUNCH(PK_SPLIT, true, N, D, false, true, 2, 0); } \
-                                else { hipLaunchKernelGGL((k_split<N, D, 1>), gs, bs4, 0, c->stream, sa); PK_COUNT_LAUNCH(PK_SPLIT, true, N, D, false, true, 2, 1); } } while (0)
-                    if (nf) { if (dsel == 1) LZ_SPLIT(true, 1); else if (dsel == 2) LZ_SPLIT(true, 2); else LZ_SPLIT(true, 0); }
-                    else { if (dsel == 1) LZ_SPLIT(false, 1); else if (dsel == 2) LZ_SPLIT(false, 2); else LZ_SPLIT(false, 0); }
-#undef LZ_SPLIT
-                };
-                // which pairs to cut: the ones with many anchor candidates (related: a candidate at every other position; a chance
-                // pair has one in a hundred and is scanned whole, by its segment 0 with the null chain at work) -- heaviest first
-                u32 items = 0;
-                {
-                    std::vector<u32> cnt(npb);
-                    HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_lpt_cnt, (size_t)npb * 4, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    const char* he = getenv("LZANI_SPLIT_ALL");
-                    const char* te = getenv("LZANI_SPLIT_THR");
-                    // (every pair by default: at a wave or two per SIMD a chance pair of 5 Mbp takes nearly as long as a related one;
-                    // LZANI_SPLIT_ALL=0 cuts the pairs with a candidate at one position in 32 and more only)
-                    const u32 thr = (he && *he == '0') ? (u32)(cb_words * 32 / 32) : te ? (u32)strtoul(te, nullptr, 10) : 0u;
-                    std::vector<u32> order(npb);
-                    for (u32 k = 0; k < npb; ++k) order[k] = k;
-                    std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return cnt[x] > cnt[y]; });
-                    std::vector<unsigned char> heavy(npb, 0);
-                    std::vector<u32> all;
-                    all.reserve((size_t)npb * 2);
-                    u32 n_heavy = 0;
-                    for (u32 k : order) if (cnt[k] >= thr) { heavy[k] = 1; ++n_heavy; for (u32 sg = 0; sg < S; ++sg) all.push_back(k * S + sg); }
-                    for (u32 k : order) if (cnt[k] < thr) all.push_back(k * S);
-                    items = (u32)all.size();
-                    HIPCHK(c, d_heavy.alloc(npb));
-                    HIPCHK(c, hipMemcpyAsync(d_heavy.p, heavy.data(), npb, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(d_work.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));            // (the vectors leave scope)
-                    TRACE("split: %u pairs, %u of them cut into %u segments (candidates >= %u)", npb, n_heavy, S, thr);
-                }
-                sa.heavy = d_heavy.p;
-                launch(0, npb * (S - 1));                                  // the checkpoints
-                u32* cur = d_work.p; u32* nxt = d_next.p;
-                auto t_round = std::chrono::steady_clock::now();
-                const int give_up = 6 + (int)S / 4;                      // (a chain of void segments costs a round each: more segments, more rounds allowed)
-                for (int round = 0; round < give_up + 4 && items; ++round) {
-                    HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 8, c->stream));     // tickets, next round's items (the finished pairs' count stays)
-                    sa.work = cur; sa.work_next = nxt;
-                    launch(1, items);
-                    sa.last_round = round >= give_up;
-                    hipLaunchKernelGGL(k_split_stitch, dim3((npb + 255) / 256), dim3(256), 0, c->stream, sa);
-                    u32 cnt[12] = {0};
-                    HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.p, 48, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    c->split_items += items;
-                    {
-                        const auto t_now = std::chrono::steady_clock::now();
-                        TRACE("split: round %d ran %u segments in %.1f ms, %u pairs finished, %u segments to run again (void so far, by cause: look-back cut short %u, kept/dropped %u, dropped/kept %u, floor %u, guess %u, chain %u)",
-                              round, items, std::chrono::duration<double, std::milli>(t_now - t_round).count(), cnt[2], cnt[1], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]);
-                        t_round = t_now;
-                    }
-                    items = cnt[1];
-                    std::swap(cur, nxt);
-                    if (items == 0 && cnt[2] != npb) return fail(c, LZANI_ERR_DEVICE, "split pairs: the stitch left pairs behind");
-                }
-                if (items) return fail(c, LZANI_ERR_DEVICE, "split pairs: no end of rounds");
-            } else if (pm) {                            // dense rows: candidate bitmaps made ahead (k_pm_cand)
-                c->pm_launches += 1;
-                if (rtc_launch()) {}
-                else if (nf && defp) LZ_PAIRS_PM(true, 1);
-                else if (nf && lgp) LZ_PAIRS_PM(true, 2);
-                else if (nf) LZ_PAIRS_PM(true, 0);
-                else if (defp) LZ_PAIRS_PM(false, 1);
-                else if (lgp) LZ_PAIRS_PM(false, 2);
-                else LZ_PAIRS_PM(false, 0);
-            } else if (tw && pa.skeys) {                // long genomes: candidates by the join
-                if (rtc_launch()) {}
-                else if (nf && defp) LZ_PAIRS_JOIN(true, 1);
-                else if (nf && lgp) LZ_PAIRS_JOIN(true, 2);
-                else if (nf) LZ_PAIRS_JOIN(true, 0);
-                else if (defp) LZ_PAIRS_JOIN(false, 1);
-                else if (lgp) LZ_PAIRS_JOIN(false, 2);
-                else LZ_PAIRS_JOIN(false, 0);
-            } else if (use_blk) {
-                const u32 fw = (u32)std::max<u64>(c->fl_stride >> c->blk_fold, 1);
-                const size_t lds = (size_t)(BLK_WAVES * SEED_LDS_WORDS + fw) * 4;
-                HIPCHK(c, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                pa.fmask = c->fmask >> c->blk_fold;
-                c->blk_launches += 1;
-                const dim3 gb((u32)std::min<u64>((waves + BLK_CHUNK_MIN - 1) / BLK_CHUNK_MIN, (u64)c->n_cus * 2)), bb(64 * BLK_WAVES);
-#define LZ_PAIRS_BLK(N, D) do { hipLaunchKernelGGL((k_pairs_blk<N, D>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr); PK_COUNT_LAUNCH(PK_BLK, true, N, D, false, true, 0, 0); } while (0)
-                if (nf && defp) LZ_PAIRS_BLK(true, true);
-                else if (nf) LZ_PAIRS_BLK(true, false);
-                else if (defp) LZ_PAIRS_BLK(false, true);
-                else LZ_PAIRS_BLK(false, false);
-#undef LZ_PAIRS_BLK
-            } else if (tw) {
-                if (rtc_launch()) {}
-                else if (nf && defp) LZ_PAIRS(true, true, true, false, true);
-                else if (nf) LZ_PAIRS(true, true, false, false, true);
-                else if (defp) LZ_PAIRS(true, false, true, false, true);
-                else LZ_PAIRS(true, false, false, false, true);
-            } else {
-                if (nf && defp) LZ_PAIRS(true, true, true, false, false);
-                else if (nf) LZ_PAIRS(true, true, false, false, false);
-                else if (defp) LZ_PAIRS(true, false, true, false, false);
-                else LZ_PAIRS(true, false, false, false, false);
-            }
-#undef LZ_PAIRS_PM
-#undef LZ_PAIRS_JOIN
-#undef LZ_PAIRS
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(ev[3], c->stream));
-            launched[b] = 1;
-            c->tm.pair_launches += 1;
-        }
-        c->tm.pairs += e1 - e0;
+        qp.qb[(size_t)b * (NQUEUES + 1) + NQUEUES] = at;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));       // the one host wait of the call
-    TRACE("pairs done");
+    return qp;
+}
+
+// What the batches of one run share: its rows and queues on the device, the launch geometry, the kernels of its tuple.
+struct RunCtx {
+    lzani_ctx* c;
+    const Knobs& k;
+    const RunPlan& p;
+    const RegionSink* rs; const u64* row_off; const u32* query_ids; int* d_out;     // the call's arguments
+    const u32 *d_ref, *d_q, *d_qorder;                       // their device copies, the queues
+    const u64 *d_off, *d_qcum;
+    u32 max_blocks; int dsel;                                // the launch geometry, defp_select of the tuple
+    unsigned long long* d_cbits;                             // join form: one candidate bitmap per resident wave
+    u64 cbits_stride;
+    lzani_rtc::Kernel* rtc_k; int rtc_id;                    // the tuple's run-time compiled kernel, if any, and its row of the launch record
+    std::vector<u32> grp_seen = {}; u32 grp_stamp = 0;       // (query lists + candidate bitmaps) the group a query was last seen in
+};
+
+// Batch b: rows [k0, k0 + rows), pairs [e0, e1), its queues' bounds (QueuePlan::qb); the split / LPT choice of its pair launch.
+struct Batch { u32 b, k0, rows; u64 e0, e1; const u32* qb; u32 split_S = 0; int split_seglen = 0; bool lpt = false; };
+
+// Few, long pairs (the batch leaves a wave slot only a few of them): the launch is over when its slowest pair is, so the
+// pairs with the most candidates -- the related ones -- go first (k_pm_cand counts, k_lpt_keys + a sort order)
+// ... and fewer pairs than half the wave slots: every pair by several waves, segment by segment (lzani_kernels_split.h).
+// (Candidate bitmaps only: no regions, mqd + mrd <= 128.)
+int choose_split_lpt(RunCtx& r, Batch& bt)
+{
+    lzani_ctx* c = r.c;
+    const u64 bp = bt.e1 - bt.e0, slots = (u64)r.max_blocks * 4, cb_words = r.p.cb_words;
+    const int Dmax = r.p.Lmax + c->P.mrd;
+    // (measured at the end of round 4, 5 Mbp: 56 pairs 6 ms a launch instead of 148, 240 pairs 8 instead of 147, 992 pairs 47
+    // instead of 148: from 8 wave slots per pair on)
+    // (... measured at 5 Mbp; for shorter queries -- from 256 kbp on -- from 16 wave slots per pair, as the suite has run it)
+    const bool split = r.k.split.value_or(cb_words >= 8192 && (bp * 16 <= slots || (cb_words >= 65536 && bp * 8 <= slots)));
+    if (split && bp * 2 <= 0xFFFFFFFFull / 64) {
+        u32 S = (u32)std::min<u64>(r.k.split_s, std::max<u64>(2, slots / bp));      // (8 x 5 Mbp: 67 / 58 / 42 ms a launch with 16 / 32 / 64 a pair)
+        int seglen = (Dmax + (int)S - 1) / (int)S;
+        if (r.k.split_seglen > 0) { seglen = r.k.split_seglen; S = (u32)std::min<int>(64, std::max(2, (Dmax + seglen - 1) / seglen)); }
+        seglen = std::max(seglen, 512);
+        if ((Dmax + seglen - 1) / seglen >= 2) { bt.split_S = std::min<u32>(S, (u32)((Dmax + seglen - 1) / seglen)); bt.split_seglen = seglen; }
+    }
+    // (queries from ~256 kbp on; the split wants the candidate counts: which pairs to cut, which first)
+    bt.lpt = (bp >= 2 && bp <= slots * 32 && r.k.lpt.value_or(cb_words >= 8192)) || bt.split_S >= 2;
+    if (bt.lpt && c->lpt_pairs < bp) {
+        hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
+        c->d_lpt_cnt = nullptr; c->d_lpt_keys = nullptr; c->lpt_pairs = 0;
+        if (hipMalloc(&c->d_lpt_cnt, (size_t)bp * 4) != hipSuccess || hipMalloc(&c->d_lpt_keys, (size_t)bp * 16) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
+            c->d_lpt_cnt = nullptr; c->d_lpt_keys = nullptr;
+            bt.lpt = false;                                   // (placement only: the run goes on without it)
+        } else c->lpt_pairs = (size_t)bp;
+    }
+    if (bt.lpt) HIPCHK(c, hipMemsetAsync(c->d_lpt_cnt, 0, (size_t)bp * 4, c->stream));
+    return LZANI_OK;
+}
+
+// The candidate bitmaps of the batch's pairs, group by group of pm_group references; then the ticket order of its queues.
+int candidate_stage(RunCtx& r, Batch& bt)
+{
+    lzani_ctx* c = r.c;
+    const RunPlan& p = r.p;
+    const int pm_bits = p.pm_bits;
+    for (u32 g0 = 0; g0 < bt.rows; g0 += p.pm_group) {
+        PmArgs pg;
+        pg.G = gtab(c);
+        pg.ref_ids = r.d_ref + bt.k0; pg.row_off = r.d_off + bt.k0;
+        pg.slot0 = g0; pg.rows = std::min<u32>(p.pm_group, bt.rows - g0);
+        pg.M = c->d_pm; pg.rw = ((pg.rows + 127) / 128) * 4; pg.mmask = (u32)lowmask(pm_bits); pg.rshift = c->geo.kb - pm_bits;
+        pg.mal = c->P.mal; pg.mrd = c->P.mrd;
+        pg.cbits = c->d_pm_cbits; pg.cb_words = p.cb_words; pg.e0 = bt.e0; pg.n = c->n; pg.q0 = 0;
+        pg.query_ids = r.d_q; pg.pidx = nullptr; pg.qflag = pg.qlist = pg.qcount = nullptr;
+        pg.pcount = bt.lpt ? c->d_lpt_cnt : nullptr;
+        if (r.query_ids) {                                   // the lists of the group's rows -> pair table + the queries involved
+            const size_t tab = (size_t)c->n * 32 * pg.rw;
+            pg.pidx = c->d_pm_pidx; pg.qflag = c->d_pm_pidx + (size_t)c->n * p.pm_group; pg.qlist = pg.qflag + c->n; pg.qcount = pg.qlist + c->n;
+            HIPCHK(c, hipMemsetAsync(pg.pidx, 0xFF, tab * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(pg.qflag, 0, ((size_t)2 * c->n + 1) * 4, c->stream));
+            hipLaunchKernelGGL(k_pm_pairs, dim3(pg.rows), dim3(256), 0, c->stream, pg);
+        }
+        // the matrix: from the group's indexes, chunk by chunk through LDS (long genomes: no global atomics, no clearing),
+        // or by one atomicOr per text position into the cleared matrix
+        const int tbits = c->geo.kb - c->geo.dirbits;
+        // (chunks of 64 KB: two blocks = 32 waves a CU; with 128 KB chunks, one block a CU, the matrix of 128 x 5 Mbp took 3 ms more)
+        const int rcl = std::min(pm_bits, pg.rw <= 4 ? 12 : pg.rw <= 8 ? 11 : 10);
+        const bool from_index = c->geo.tagmask == (u32)lowmask(tbits) && pm_bits == c->geo.kb && rcl >= tbits &&
+                                r.k.pm_from_index.value_or(pm_bits > 24);
+        if (from_index) {
+            c->run.pmfi_launches += 1;
+            const size_t fl = ((size_t)pg.rw << rcl) * 4;
+            const dim3 gi(1u << (pm_bits - rcl)), bi(1024);
+#define LZ_PM_FI(RW) do { \
+                if (!(c->pmfi_attr_set & (1u << RW))) { \
+                    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_from_index<RW>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
+                    c->pmfi_attr_set |= 1u << RW; \
+                } \
+                hipLaunchKernelGGL(k_pm_from_index<RW>, gi, bi, fl, c->stream, pg, c->d_dirz, c->d_ent, c->dir_stride, c->ent_stride, tbits, c->geo.posbits, rcl); \
+            } while (0)
+            switch (pg.rw) {
+            case 4: LZ_PM_FI(4); break;
+            case 8: LZ_PM_FI(8); break;
+            case 12: LZ_PM_FI(12); break;
+            default: LZ_PM_FI(16); break;
+            }
+#undef LZ_PM_FI
+        } else {
+            HIPCHK(c, hipMemsetAsync(c->d_pm, 0, ((size_t)1 << pm_bits) * pg.rw * 4, c->stream));
+            hipLaunchKernelGGL(k_pm_build, dim3((u32)std::min<u64>(((u64)c->Tmax + 255) / 256, 64), pg.rows), dim3(256), 0, c->stream, pg, c->Tmax);
+        }
+        const u32 rp = 32 * pg.rw;
+        const size_t lds = (size_t)(PM_TILE_WORDS * (rp + 1) + rp) * 4;
+        if (!c->pm_attr_set) {
+            const size_t lmax = (size_t)(PM_TILE_WORDS * (PM_GROUP + 1) + PM_GROUP) * 4;
+            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
+            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
+            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
+            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
+            c->pm_attr_set = true;
+        }
+        // (query lists: one row of blocks per query that occurs in the group -- counted here, the device list is
+        // k_pm_pairs' -- not per genome: 20,000 genomes x 44 tiles of blocks that find nothing to do were most of
+        // the candidate stage of a filtered run)
+        u32 nq = c->n;
+        if (r.query_ids) {
+            if (r.grp_seen.size() != c->n) r.grp_seen.assign(c->n, 0xFFFFFFFFu);
+            const u32 stamp = ++r.grp_stamp;
+            nq = 0;
+            for (u64 e = r.row_off[bt.k0 + g0]; e < r.row_off[bt.k0 + g0 + pg.rows]; ++e)
+                if (r.grp_seen[r.query_ids[e]] != stamp) { r.grp_seen[r.query_ids[e]] = stamp; ++nq; }
+        }
+        for (u32 q0 = 0; q0 < nq; q0 += 32768) {           // gridDim.y is limited to 65535
+            pg.q0 = q0;
+            const dim3 gc(p.pm_tiles, std::min<u32>(32768, nq - q0)), bc(PM_CAND_THREADS);
+            switch (pg.rw / 4) {
+            case 1: hipLaunchKernelGGL(k_pm_cand<1>, gc, bc, lds, c->stream, pg); break;
+            case 2: hipLaunchKernelGGL(k_pm_cand<2>, gc, bc, lds, c->stream, pg); break;
+            case 3: hipLaunchKernelGGL(k_pm_cand<3>, gc, bc, lds, c->stream, pg); break;
+            default: hipLaunchKernelGGL(k_pm_cand<4>, gc, bc, lds, c->stream, pg); break;
+            }
+        }
+        c->run.tm.cand_launches += 2;
+    }
+    if (!bt.lpt || c->d_lpt_cnt == nullptr) bt.split_S = 0;   // (no candidate counts after all -- their buffer could not be had: no split)
+    if (bt.lpt && bt.split_S < 2) {                            // the ticket order of the batch's queues
+        const u64 bp = bt.e1 - bt.e0;
+        QueueBounds qbv;
+        for (int x = 0; x <= NQUEUES; ++x) qbv.v[x] = bt.qb[x];
+        hipLaunchKernelGGL(k_lpt_keys, dim3((u32)std::min<u64>((bp + 255) / 256, 4096)), dim3(256), 0, c->stream,
+                           r.d_qorder + bt.k0, r.d_qcum + bt.k0 + bt.b, qbv, r.d_off + bt.k0, bt.e0, c->d_lpt_cnt, c->d_lpt_keys, bt.rows, bp);
+        size_t need = 0;
+        int e = lzani_sort_keys(c->d_lpt_keys, c->d_lpt_keys + bp, bp, 32, 56, nullptr, &need, c->stream);
+        if (e == 0) { int rc = grow_jtmp(c, need, true); if (rc) return rc; }
+        need = c->jtmp_bytes;
+        if (e == 0) e = lzani_sort_keys(c->d_lpt_keys, c->d_lpt_keys + bp, bp, 32, 56, c->d_jtmp, &need, c->stream);
+        if (e != 0) return fail(c, LZANI_ERR_DEVICE, "ticket order: radix sort failed");
+    }
+    HIPCHK(c, hipGetLastError());
+    return LZANI_OK;
+}
+
+// Few, long pairs: several waves a pair (lzani_kernels_split.h) -- the checkpoints, then rounds of segments until the stitch
+// has every pair.  launch(sa, mode, items): k_split of the mode (launch_pairs picks the instantiation).
+template <class Launch>
+int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
+{
+    lzani_ctx* c = r.c;
+    c->run.pm_launches += 1;
+    c->run.split_launches += 1;
+    const u32 npb = (u32)(bt.e1 - bt.e0), S = bt.split_S;
+    DevBuf<SplitStart> d_cuts;
+    DevBuf<SplitOut> d_souts;
+    DevBuf<u32> d_work, d_next, d_cnt;
+    DevBuf<unsigned char> d_done, d_heavy;
+    HIPCHK(c, d_cuts.alloc((size_t)npb * S));
+    HIPCHK(c, d_souts.alloc((size_t)npb * S));
+    HIPCHK(c, d_work.alloc((size_t)npb * S));
+    HIPCHK(c, d_next.alloc((size_t)npb * S));
+    HIPCHK(c, d_cnt.alloc(12));
+    HIPCHK(c, d_done.alloc(npb));
+    HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 48, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_done.p, 0, npb, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_cuts.p, 0xFF, (size_t)npb * S * sizeof(SplitStart), c->stream));      // (cut 0 of every pair: no checkpoint)
+    SplitArgs sa;
+    sa.pa = pa; sa.rows = bt.rows; sa.n_pairs = npb; sa.S = S; sa.seglen = bt.split_seglen;
+    sa.cuts = d_cuts.p; sa.outs = d_souts.p; sa.work = d_work.p; sa.work_next = d_next.p; sa.counters = d_cnt.p; sa.done = d_done.p;
+    sa.reg = c->P.reg; sa.last_round = 0;
+    // which pairs to cut: the ones with many anchor candidates (related: a candidate at every other position; a chance
+    // pair has one in a hundred and is scanned whole, by its segment 0 with the null chain at work) -- heaviest first
+    u32 items = 0;
+    {
+        std::vector<u32> cnt(npb);
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_lpt_cnt, (size_t)npb * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        // (every pair by default: at a wave or two per SIMD a chance pair of 5 Mbp takes nearly as long as a related one;
+        // LZANI_SPLIT_ALL=0 cuts the pairs with a candidate at one position in 32 and more only)
+        const u32 thr = !r.k.split_all ? (u32)r.p.cb_words : r.k.split_thr;
+        std::vector<u32> order(npb);
+        for (u32 k = 0; k < npb; ++k) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return cnt[x] > cnt[y]; });
+        std::vector<unsigned char> heavy(npb, 0);
+        std::vector<u32> all;
+        all.reserve((size_t)npb * 2);
+        u32 n_heavy = 0;
+        for (u32 k : order) if (cnt[k] >= thr) { heavy[k] = 1; ++n_heavy; for (u32 sg = 0; sg < S; ++sg) all.push_back(k * S + sg); }
+        for (u32 k : order) if (cnt[k] < thr) all.push_back(k * S);
+        items = (u32)all.size();
+        HIPCHK(c, d_heavy.alloc(npb));
+        HIPCHK(c, hipMemcpyAsync(d_heavy.p, heavy.data(), npb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_work.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));            // (the vectors leave scope)
+        TRACE("split: %u pairs, %u of them cut into %u segments (candidates >= %u)", npb, n_heavy, S, thr);
+    }
+    sa.heavy = d_heavy.p;
+    launch(sa, 0, npb * (S - 1));                           // the checkpoints
+    u32* cur = d_work.p; u32* nxt = d_next.p;
+    auto t_round = std::chrono::steady_clock::now();
+    const int give_up = 6 + (int)S / 4;                      // (a chain of void segments costs a round each: more segments, more rounds allowed)
+    for (int round = 0; round < give_up + 4 && items; ++round) {
+        HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 8, c->stream));     // tickets, next round's items (the finished pairs' count stays)
+        sa.work = cur; sa.work_next = nxt;
+        launch(sa, 1, items);
+        sa.last_round = round >= give_up;
+        hipLaunchKernelGGL(k_split_stitch, dim3((npb + 255) / 256), dim3(256), 0, c->stream, sa);
+        u32 cnt[12] = {0};
+        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.p, 48, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->run.split_items += items;
+        const auto t_now = std::chrono::steady_clock::now();
+        TRACE("split: round %d ran %u segments in %.1f ms, %u pairs finished, %u segments to run again (void so far, by cause: look-back cut short %u, kept/dropped %u, dropped/kept %u, floor %u, guess %u, chain %u)",
+              round, items, std::chrono::duration<double, std::milli>(t_now - t_round).count(), cnt[2], cnt[1], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]);
+        t_round = t_now;
+        items = cnt[1];
+        std::swap(cur, nxt);
+        if (items == 0 && cnt[2] != npb) return fail(c, LZANI_ERR_DEVICE, "split pairs: the stitch left pairs behind");
+    }
+    if (items) return fail(c, LZANI_ERR_DEVICE, "split pairs: no end of rounds");
+    return LZANI_OK;
+}
+
+// The largest LDS copy of the presence filter that leaves k_pairs_blk (kf) two blocks per CU, decided once per genome set
+// (blk_fold -2: none does, the wave kernel takes these rows too).
+bool blk_fits(lzani_ctx* c, const void* kf)
+{
+    if (c->blk_fold == -1) {
+        for (int fold = 0; fold <= 4 && c->blk_fold < 0; ++fold) {
+            const size_t l = (size_t)(BLK_WAVES * SEED_LDS_WORDS + std::max<u64>(c->fl_stride >> fold, 1)) * 4;
+            if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l) != hipSuccess) { (void)hipGetLastError(); continue; }
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * BLK_WAVES, l) == hipSuccess && nb >= 2) c->blk_fold = fold;
+        }
+        (void)hipGetLastError();
+        if (c->blk_fold < 0) c->blk_fold = -2;
+    }
+    return c->blk_fold >= 0;
+}
+
+// The batch's pair launch: the run's form picks the kernel, (nfree, dsel) its template arguments; a tuple compiled at run
+// time goes first where it has a kernel of the form.
+int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
+{
+    lzani_ctx* c = r.c;
+    const bool tickets = bt.lpt && bt.split_S < 2;
+    PairArgs pa;
+    pa.G = gtab(c);
+    pa.P = c->P; pa.geo = c->geo;
+    pa.dirz = c->d_dirz; pa.ent = c->d_ent;
+    pa.dir_stride = c->dir_stride; pa.ent_stride = c->ent_stride;
+    pa.bk = c->d_bk; pa.bk_stride = c->bk_stride;
+    pa.tw = c->d_tw; pa.tw_stride = c->tw_stride;
+    pa.fl = c->d_fl; pa.fl_stride = c->fl_stride; pa.fmask = c->fmask;
+    pa.ref_ids = r.d_ref + bt.k0; pa.row_off = r.d_off + bt.k0; pa.query_ids = r.d_q;
+    pa.out = r.d_out; pa.cursor = c->d_cursor;
+    pa.qorder = r.d_qorder + bt.k0; pa.qcum = r.d_qcum + bt.k0 + bt.b;
+    for (int x = 0; x <= NQUEUES; ++x) pa.qb[x] = bt.qb[x];
+    pa.skeys = r.cbits_stride ? c->d_jkeys : nullptr; pa.soff = c->d_jsoff; pa.scnt = c->d_jcnt;
+    pa.cbits = r.d_cbits; pa.cbits_stride = r.cbits_stride; pa.cb_e0 = 0;
+    if (r.p.pm) { pa.cbits = reinterpret_cast<unsigned long long*>(c->d_pm_cbits); pa.cbits_stride = r.p.cb_words / 2; pa.cb_e0 = bt.e0; }
+    pa.reg_out = r.rs ? r.rs->d_regions : nullptr; pa.reg_count = r.rs ? r.rs->d_count : nullptr; pa.reg_cap = r.rs ? r.rs->capacity : 0;
+    pa.torder = tickets ? c->d_lpt_keys + (bt.e1 - bt.e0) : nullptr;
+    c->run.lpt_launches += tickets ? 1 : 0;
+    HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, NQUEUES * sizeof(unsigned long long), c->stream));
+    const u64 waves = bt.e1 - bt.e0;
+    const dim3 gd((u32)std::min<u64>((waves + 3) / 4, r.max_blocks)), bd(256);
+    HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    const bool fast = c->d_kmL != nullptr, tw = pa.tw != nullptr, nf = c->all_nfree;
+    auto rtc_launch = [&]() -> bool {
+        if (!r.rtc_k) return false;
+        void* kargs[] = {&pa};
+        if (hipModuleLaunchKernel(r.rtc_k->fn, gd.x, 1, 1, bd.x, 1, 1, 0, c->stream, kargs, nullptr) != hipSuccess) { (void)hipGetLastError(); return false; }
+        c->run.rtc_launches += 1;
+        c->run.klaunch[r.rtc_id] += 1;
+        return true;
+    };
+    // Probe form, dense rows of hundreds of pairs: blocks of 16 waves with the reference's presence filter in LDS
+    // (k_pairs_blk).  The rows a kmer-db filter leaves hold related pairs, where most positions pass the filter:
+    // BASELINE configs[4] at full size is 6 % slower this way; LZANI_BLOCK_KERNEL=1/0 overrides.
+    const void* kf = nullptr;
+    with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) { kf = reinterpret_cast<const void*>(k_pairs_blk<N, D>); });
+    const bool use_blk = blk_rows && fast && tw && !pa.skeys && blk_fits(c, kf);
+    if (use_blk && !c->d_blkctr) HIPCHK(c, hipMalloc(&c->d_blkctr, (size_t)c->n_cus * 2 * 4));
+    int rc = LZANI_OK;
+    if (r.rs) {                                   // alignment output: one generic instantiation per index form
+        if (!fast) launch_k_pairs<false, false, 0, true, false, 0>(c, gd, bd, pa);
+        else if (tw) launch_k_pairs<true, false, 0, true, true, 0>(c, gd, bd, pa);
+        else launch_k_pairs<true, false, 0, true, false, 0>(c, gd, bd, pa);
+    } else if (!fast) launch_k_pairs<false, false, 0, false, false, 0>(c, gd, bd, pa);
+    else if (r.p.pm && bt.split_S >= 2) {            // few, long pairs: several waves a pair
+        rc = run_split(r, bt, pa, [&](SplitArgs& sa, int mode, u32 items) {
+            const dim3 gs((u32)std::min<u64>(((u64)items + 3) / 4, r.max_blocks)), bs4(256);
+            sa.n_work = items;
+            with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) {
+                if (mode == 0) { hipLaunchKernelGGL((k_split<N, D, 0>), gs, bs4, 0, c->stream, sa); count_launch<PK_SPLIT, true, N, D, false, true, 2, 0>(c->run); }
+                else { hipLaunchKernelGGL((k_split<N, D, 1>), gs, bs4, 0, c->stream, sa); count_launch<PK_SPLIT, true, N, D, false, true, 2, 1>(c->run); }
+            });
+        });
+    } else if (r.p.pm) {                          // dense rows: candidate bitmaps made ahead (k_pm_cand)
+        c->run.pm_launches += 1;
+        if (!rtc_launch()) with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 2>(c, gd, bd, pa); });
+    } else if (tw && pa.skeys) {                  // long genomes: candidates by the join
+        if (!rtc_launch()) with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 1>(c, gd, bd, pa); });
+    } else if (use_blk) {
+        const u32 fw = (u32)std::max<u64>(c->fl_stride >> c->blk_fold, 1);
+        const size_t lds = (size_t)(BLK_WAVES * SEED_LDS_WORDS + fw) * 4;
+        HIPCHK(c, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        pa.fmask = c->fmask >> c->blk_fold;
+        c->run.blk_launches += 1;
+        const dim3 gb((u32)std::min<u64>((waves + BLK_CHUNK_MIN - 1) / BLK_CHUNK_MIN, (u64)c->n_cus * 2)), bb(64 * BLK_WAVES);
+        with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) {
+            hipLaunchKernelGGL((k_pairs_blk<N, D>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr);
+            count_launch<PK_BLK, true, N, D, false, true, 0>(c->run);
+        });
+    } else if (tw) {
+        if (!rtc_launch()) with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 0>(c, gd, bd, pa); });
+    } else with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, false, 0>(c, gd, bd, pa); });
+    if (rc) return rc;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[3], c->stream));
+    return LZANI_OK;
+}
+
+constexpr int EV = 5;                             // stamps per batch: index begin / end, pairs begin / end, candidates end
+
+// One batch: index build, split / LPT choice, candidate stage, pair launch -- stream work only, stamped into ev.
+int run_batch(RunCtx& r, Batch bt, hipEvent_t* ev)
+{
+    lzani_ctx* c = r.c;
+    const RunPlan& p = r.p;
+    TRACE("batch %u rows [%u,%u) pairs [%llu,%llu) slots=%u pm=%d", bt.b, bt.k0, bt.k0 + bt.rows, (unsigned long long)bt.e0, (unsigned long long)bt.e1, c->slots, (int)p.pm);
+    HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    // rows for k_pairs_blk (launch_pairs): dense, hundreds of pairs each, probe form with tag words and a filter
+    const bool blk_rows = !p.pm && !r.rs && c->d_kmL && c->tw_stride && !c->join_mode && c->fl_stride && bt.e1 > bt.e0 &&
+                          (bt.e1 - bt.e0) / bt.rows >= 128 && r.k.block_kernel.value_or(r.query_ids == nullptr);
+    int rc = build_indexes(c, r.k, r.d_ref + bt.k0, bt.rows, blk_rows, !p.pm);
+    if (rc) return rc;
+    HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    if (p.pm && bt.e1 > bt.e0) {
+        rc = choose_split_lpt(r, bt);
+        if (!rc) rc = candidate_stage(r, bt);
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipEventRecord(ev[4], c->stream));
+    if (bt.e1 > bt.e0) {
+        rc = launch_pairs(r, bt, blk_rows, ev);
+        if (rc) return rc;
+        c->run.tm.pair_launches += 1;
+    }
+    c->run.tm.pairs += bt.e1 - bt.e0;
+    return LZANI_OK;
+}
+
+// The counters of diagnostic builds (-DLZANI_STAMPS and the like), printed and cleared after every run.
+int report_diagnostics(lzani_ctx* c, u64 n_pairs)
+{
 #ifdef LZANI_STAMPS
     {
         unsigned long long acc[8];
@@ -1332,9 +1327,19 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
         HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(g_chain_stats), z, sizeof z));
     }
 #endif
+    return LZANI_OK;
+}
+
+// The end of a run: the one host wait, the loop guards, the event timings.
+int finish_run(lzani_ctx* c, u64 n_pairs, const lzani_rtc::Kernel* rtc_k, const std::vector<u32>& bstart, const u64* row_off)
+{
+    HIPCHK(c, hipStreamSynchronize(c->stream));       // the one host wait of the call
+    TRACE("pairs done");
+    const int rc = report_diagnostics(c, n_pairs);
+    if (rc) return rc;
     int trip = 0;
     HIPCHK(c, hipMemcpyFromSymbol(&trip, HIP_SYMBOL(g_guard_trip), sizeof(int)));
-    if (rtc_k && c->rtc_launches) {              // (a code object of its own has a loop guard of its own)
+    if (rtc_k && c->run.rtc_launches) {          // (a code object of its own has a loop guard of its own)
         int t2 = 0, zero = 0;
         HIPCHK(c, hipMemcpyDtoH(&t2, rtc_k->guard, sizeof(int)));
         if (t2) { HIPCHK(c, hipMemcpyHtoD(rtc_k->guard, &zero, sizeof(int))); if (!trip) trip = t2; }
@@ -1344,26 +1349,106 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
         HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(g_guard_trip), &zero, sizeof(int)));
         return fail(c, LZANI_ERR_DEVICE, "pair kernel: loop guard " + std::to_string(trip) + " tripped (corrupt index or text)");
     }
+    lzani_timing& tm = c->run.tm;
     if (c->km_timed) {
         float ms = 0;
         HIPCHK(c, hipEventElapsedTime(&ms, c->ev_km[0], c->ev_km[1]));
-        c->tm.kmers_ms = ms;
+        tm.kmers_ms = ms;
     }
-    c->tm.kmers_ms += c->join_ms_pending;
+    tm.kmers_ms += c->join_ms_pending;
     c->join_ms_pending = 0;
-    for (u32 b = 0; b < n_batches; ++b) {
+    for (size_t b = 0; b + 1 < bstart.size(); ++b) {
         hipEvent_t* ev = c->events.data() + (size_t)EV * b;
         float ms = 0;
         HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-        c->tm.index_ms += ms;
+        tm.index_ms += ms;
         HIPCHK(c, hipEventElapsedTime(&ms, ev[1], ev[4]));
-        c->tm.cand_ms += ms;
-        if (launched[b]) {
+        tm.cand_ms += ms;
+        if (row_off[bstart[b + 1]] > row_off[bstart[b]]) {         // (a batch with pairs: its pair launch)
             HIPCHK(c, hipEventElapsedTime(&ms, ev[2], ev[3]));
-            c->tm.pairs_ms += ms;
+            tm.pairs_ms += ms;
         }
     }
     return LZANI_OK;
+}
+
+// A run of rows on the resident genome set: check, plan, queues and uploads, then the batches back to back on the stream,
+// then one wait.
+int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
+                  int* d_out, const RegionSink* rs = nullptr)
+{
+    if (!c->n) return fail(c, LZANI_ERR_STATE, "lzani_run_rows: no genomes set");
+    c->run = RunRecord{};
+    const Knobs k{};
+    if (n_rows == 0) return LZANI_OK;
+    RowFacts rf;
+    int rc = check_rows(c, n_rows, ref_ids, row_off, query_ids, rf);
+    const u64 n_pairs = rf.n_pairs;
+    if (rc || n_pairs == 0) return rc;
+
+    HIPCHK(c, hipSetDevice(c->dev));
+    // (the k-mer words and the join lists are made by the first run after lzani_set_genomes -- inside its timed index
+    // stage, reported as kmers_ms -- and kept: they depend on the genome set and the parameters only)
+    c->km_timed = false;
+    rc = ensure_kmers(c);
+    if (rc) return rc;
+    RunPlan p;
+    rc = plan_run(c, k, rf, n_rows, row_off, query_ids != nullptr, rs != nullptr, p);
+    if (rc) return rc;
+
+    // Everything the batches need from the host -- row tables and the per-XCD work queues of every batch -- is prepared and
+    // uploaded before the first launch, so the batches follow each other on the stream without a host round trip in between.
+    const u32 n_batches = (u32)p.bstart.size() - 1;
+    c->run.batches = n_batches;
+    const auto [qorder, qcum, qb] = plan_queues(n_rows, row_off, p.bstart);
+    DevBuf<u32> d_ref, d_q, d_qorder;
+    DevBuf<u64> d_off, d_qcum;
+    HIPCHK(c, d_qorder.alloc(n_rows));
+    HIPCHK(c, d_qcum.alloc(qcum.size()));
+    HIPCHK(c, d_ref.alloc(n_rows));
+    HIPCHK(c, d_off.alloc((size_t)n_rows + 1));
+    HIPCHK(c, hipMemcpyAsync(d_ref, ref_ids, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off, row_off, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_qorder, qorder.data(), qorder.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_qcum, qcum.data(), qcum.size() * 8, hipMemcpyHostToDevice, c->stream));
+    if (query_ids) {
+        HIPCHK(c, d_q.alloc(n_pairs));
+        HIPCHK(c, hipMemcpyAsync(d_q, query_ids, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    while (c->events.size() < (size_t)EV * n_batches) {       // read back after the one sync
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreate(&e));
+        c->events.push_back(e);
+    }
+    const u32 max_blocks = (u32)c->n_cus * k.blocks_per_cu;
+    DevBuf<unsigned long long> d_cbits;                      // join form: one candidate bitmap per resident wave
+    u64 cbits_stride = 0;
+    if (p.use_join && !rs) {
+        cbits_stride = (u64)((p.Lmax + c->P.mrd) >> 6) + 8;
+        HIPCHK(c, d_cbits.alloc((size_t)max_blocks * 4 * cbits_stride));
+    }
+    // Any other parameter tuple: the same kernel compiled for it the first time this context needs it (lzani_rtc.h) -- the
+    // eight ints folded into the code, the hand-written null chain included where the tuple is inside what the chain is
+    // written for (chain_params_ok).  Built (or loaded from the disk cache) here, ahead of the stream's first stamp.
+    // A compile takes 2-3 s and the folded kernel saves ~0.13 s per million pairs of 40 kbp: a code object that is not in
+    // the disk cache yet is built once the context has been asked for LZANI_RTC_MIN_PAIRS pairs in all (default 2 M: the
+    // first such run loses a second or two, every later run and every later process wins).
+    const int dsel = defp_select(c->P), cand = p.pm ? 2 : (p.use_join && c->d_tw) ? 1 : c->d_tw ? 0 : -1;
+    const int rtc_id = PK_RTC_N0_C0 + 3 * (int)c->all_nfree + cand;      // (its row of the launch record)
+    lzani_rtc::Kernel* rtc_k = nullptr;
+    c->pairs_seen += n_pairs;
+    if (!dsel && !rs && c->d_kmL && c->d_bk && lzani_rtc::enabled() && cand >= 0) {
+        rtc_k = lzani_rtc::get(c->rtc, c->P, c->all_nfree, cand, c->arch.c_str(), c->pairs_seen >= k.rtc_min_pairs);
+        if (!rtc_k && c->rtc.failed) TRACE("run-time compile unavailable (%s): the generic kernel runs", c->rtc.log.c_str());
+    }
+
+    RunCtx r{c, k, p, rs, row_off, query_ids, d_out, d_ref, d_q, d_qorder, d_off, d_qcum, max_blocks, dsel, d_cbits, cbits_stride, rtc_k, rtc_id};
+    for (u32 b = 0; b < n_batches; ++b) {
+        const u32 k0 = p.bstart[b], k1 = p.bstart[b + 1];
+        rc = run_batch(r, Batch{b, k0, k1 - k0, row_off[k0], row_off[k1], qb.data() + (size_t)b * (NQUEUES + 1)}, c->events.data() + (size_t)EV * b);
+        if (rc) return rc;
+    }
+    return finish_run(c, n_pairs, rtc_k, p.bstart, row_off);
 }
 
 }  // namespace
@@ -1620,7 +1705,7 @@ int lzani_run_rows_regions(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_id
 int lzani_get_timing(const lzani_ctx* c, lzani_timing* t)
 {
     if (!c || !t) return LZANI_ERR_ARG;
-    *t = c->tm;
+    *t = c->run.tm;
     return LZANI_OK;
 }
 
@@ -1631,23 +1716,20 @@ int lzani_get_layout(const lzani_ctx* c, lzani_layout_info* o)
     o->kmer_words = c->d_kmL != nullptr;
     o->bucket_table = c->bk_stride != 0; o->tag_words = c->tw_stride != 0;
     o->n_free = c->all_nfree;
-    o->slots = c->slots; o->batches_last_run = c->batches_last_run;
+    o->slots = c->slots; o->batches_last_run = c->run.batches;
     o->bytes_per_slot = 4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride);
     o->bytes_genomes = c->total_nm * (16 + 8) + (c->d_kmL ? c->total_nm * 64 * 8 : 0);
-    o->join_lists = c->join_mode; o->block_launches = c->blk_launches; o->bitmap_launches = c->pm_launches; o->rtc_launches = c->rtc_launches;
-    o->lpt_launches = c->lpt_launches; o->matrix_from_index = c->pmfi_launches;
-    o->split_launches = c->split_launches; o->split_segments = c->split_items;
+    o->join_lists = c->join_mode; o->block_launches = c->run.blk_launches; o->bitmap_launches = c->run.pm_launches; o->rtc_launches = c->run.rtc_launches;
+    o->lpt_launches = c->run.lpt_launches; o->matrix_from_index = c->run.pmfi_launches;
+    o->split_launches = c->run.split_launches; o->split_segments = c->run.split_items;
     return LZANI_OK;
 }
 
 int lzani_get_rtc_info(const lzani_ctx* c, lzani_rtc_info* o)
 {
     if (!c || !o) return LZANI_ERR_ARG;
-    const Params& q = c->P;
-    const bool aot = (q.mal == 11 && q.msl == 7 && q.mrd == 40 && q.mqd == 40 && q.reg == 35 && q.aw == 15 && q.am == 7 && q.ar == 3) ||
-                     (q.mal == 15 && q.msl == 9 && q.mrd == 40 && q.mqd == 40 && q.reg == 60 && q.aw == 15 && q.am == 7 && q.ar == 3);
-    o->folded_ahead_of_time = aot;
-    o->null_chain = chain_params_ok(q);
+    o->folded_ahead_of_time = defp_select(c->P) != 0;
+    o->null_chain = chain_params_ok(c->P);
     o->kernels_built = c->rtc.built; o->kernels_from_cache = c->rtc.from_cache; o->kernels_failed = c->rtc.failed;
     o->reserved_ = 0;
     o->build_ms = c->rtc.compile_ms;
@@ -1657,7 +1739,7 @@ int lzani_get_rtc_info(const lzani_ctx* c, lzani_rtc_info* o)
 int lzani_debug_kernel_launches(const lzani_ctx* c, uint64_t* counts, uint32_t cap)
 {
     if (!c || (!counts && cap)) return LZANI_ERR_ARG;
-    for (u32 i = 0; i < cap && i < (u32)PK_COUNT; ++i) counts[i] = c->klaunch[i];
+    for (u32 i = 0; i < cap && i < (u32)PK_COUNT; ++i) counts[i] = c->run.klaunch[i];
     return (int)PK_COUNT;
 }
 
@@ -1725,7 +1807,7 @@ int lzani_debug_get_index(lzani_ctx* c, uint32_t id, uint64_t* t2, uint64_t* nm,
     DevBuf<u32> d_ref;
     HIPCHK(c, d_ref.alloc(1));
     HIPCHK(c, hipMemcpy(d_ref.p, &id, 4, hipMemcpyHostToDevice));
-    rc = build_indexes(c, d_ref, 1);
+    rc = build_indexes(c, Knobs{}, d_ref, 1);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int T = ref_text_len(c->L[id], c->P.mrd);

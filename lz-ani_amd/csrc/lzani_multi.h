@@ -357,7 +357,7 @@ int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_id
     std::vector<int> rc(nd, LZANI_OK);
     auto one = [&](u32 d) {
         lzani_ctx* c = g->ctx[d];
-        if (sh[d].ref.empty()) { c->tm = lzani_timing{}; return; }       // no row for this device
+        if (sh[d].ref.empty()) { c->run.tm = lzani_timing{}; return; }   // no row for this device
         if (d && g->shard_cap[d] < std::max<u64>(sh[d].off.back(), 1)) {
             if (hipSetDevice(c->dev) != hipSuccess) { rc[d] = LZANI_ERR_DEVICE; return; }
             hipFree(d_shard[d]); d_shard[d] = nullptr; g->shard_cap[d] = 0;
@@ -475,7 +475,7 @@ int lzani_group_get_residency(const lzani_group* g, uint32_t device_index, lzani
 int lzani_group_get_timing(const lzani_group* g, uint32_t device_index, lzani_timing* t, double* gather_ms)
 {
     if (!g || device_index >= g->ctx.size() || !t) return LZANI_ERR_ARG;
-    *t = g->ctx[device_index]->tm;
+    *t = g->ctx[device_index]->run.tm;
     if (gather_ms) *gather_ms = g->gather_ms;
     return LZANI_OK;
 }

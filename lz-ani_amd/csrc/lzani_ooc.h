@@ -166,23 +166,12 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
                    int* d_out, lzani_result* h_out, const RegionSink* rs)
 {
     const u32 n = c->n;
-    c->tm = lzani_timing{};
-    c->batches_last_run = 0;
-    c->blk_launches = c->pm_launches = c->lpt_launches = c->pmfi_launches = c->split_launches = c->rtc_launches = 0;
-    c->split_items = 0;
-    std::fill(c->klaunch, c->klaunch + PK_COUNT, (u64)0);
+    c->run = RunRecord{};
     c->res_tiles = 0; c->res_uploads = 0; c->res_peak = 0; c->res_upload_ms = 0;
     if (n_rows == 0) return LZANI_OK;
-    for (u32 k = 0; k < n_rows; ++k) {
-        if (ref_ids[k] >= n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: reference id out of range");
-        if (row_off[k + 1] < row_off[k]) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off not monotone");
-        if (!query_ids && row_off[k + 1] - row_off[k] != (u64)n - 1) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: dense row must have n-1 queries");
-    }
-    if (row_off[0] != 0) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off[0] must be 0");
-    const u64 n_pairs = row_off[n_rows];
-    if (query_ids)
-        for (u64 e = 0; e < n_pairs; ++e) if (query_ids[e] >= n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: query id out of range");
-    if (n_pairs == 0) return LZANI_OK;
+    RowFacts rf;
+    const int rc0 = check_rows(c, n_rows, ref_ids, row_off, query_ids, rf);
+    if (rc0 || rf.n_pairs == 0) return rc0;
     HIPCHK(c, hipSetDevice(c->dev));
 
     const u32 nb = (u32)c->blk_first.size() - 1;
@@ -191,11 +180,8 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
     std::vector<std::vector<u32>> rows_of(nb);
     for (u32 k = 0; k < n_rows; ++k) if (row_off[k + 1] > row_off[k]) rows_of[bof[ref_ids[k]]].push_back(k);
 
-    lzani_timing tot{};
-    u64 kl[PK_COUNT] = {};
-    u32 batches = 0;
-    int blk = 0, pmc = 0, lpt = 0, pmfi = 0, split = 0, rtc = 0;
-    u64 split_items = 0, reg_done = 0;
+    RunRecord tot;
+    u64 reg_done = 0;
     GrowBuf d_res, d_pos;
     std::vector<lzani_result> h_res;
     struct Tile { std::vector<u32> rows; std::vector<u64> off; std::vector<u32> q; std::vector<u64> pos; };
@@ -266,12 +252,7 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
             }
             if (rc) return rc;
             c->res_tiles += 1;
-            tot.index_ms += c->tm.index_ms; tot.pairs_ms += c->tm.pairs_ms; tot.cand_ms += c->tm.cand_ms; tot.kmers_ms += c->tm.kmers_ms;
-            tot.pair_launches += c->tm.pair_launches; tot.index_launches += c->tm.index_launches; tot.cand_launches += c->tm.cand_launches;
-            tot.pairs += c->tm.pairs;
-            for (int x = 0; x < PK_COUNT; ++x) kl[x] += c->klaunch[x];
-            batches += c->batches_last_run; blk += c->blk_launches; pmc += c->pm_launches; lpt += c->lpt_launches;
-            pmfi += c->pmfi_launches; split += c->split_launches; rtc += c->rtc_launches; split_items += c->split_items;
+            tot += c->run;
             if (d_out) {
                 hipLaunchKernelGGL(k_scatter_pairs, dim3((u32)((tp + 255) / 256)), dim3(256), 0, c->stream, (const int*)d_res.p, d_out, (const u64*)d_pos.p, tp);
                 HIPCHK(c, hipGetLastError());
@@ -295,11 +276,7 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
             if (h_out) for (u64 e = 0; e < tp; ++e) h_out[t.pos[e]] = h_res[e];
         }
     }
-    c->tm = tot;
-    std::copy(kl, kl + PK_COUNT, c->klaunch);
-    c->batches_last_run = batches;
-    c->blk_launches = blk; c->pm_launches = pmc; c->lpt_launches = lpt; c->pmfi_launches = pmfi;
-    c->split_launches = split; c->rtc_launches = rtc; c->split_items = split_items;
+    c->run = tot;
     TRACE("out-of-core run: %u tiles, %llu block uploads (%.1f ms)", c->res_tiles, (unsigned long long)c->res_uploads, c->res_upload_ms);
     return LZANI_OK;
 }
