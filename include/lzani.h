@@ -280,6 +280,42 @@ int lzani_debug_get_index(lzani_ctx *ctx, uint32_t id, uint64_t *t2, uint64_t *n
 int lzani_debug_sort_segments(lzani_ctx *ctx, const uint64_t *keys, uint64_t *out, uint64_t seg_len, uint32_t n_seg,
                               int begin_bit, int end_bit);
 
+/* Test hook: the anchor indexes of one batch -- rows reference ids, repeats allowed -- built by the run's own index build
+ * into slots 0 .. rows-1 (the run's environment switches apply), with or without the presence filter and, where the build
+ * is the sort form, the tag words (what a batch of a run decides: with_filter, with_tw).  info receives the geometry,
+ * the strides in 32-bit words per slot (0: not built) and which build ran; every non-NULL buffer receives rows x its
+ * stride words: dirz, ent (dirz[slot][2^dirbits] entries valid), bk (4 words a bucket), tw, fl (the presence filter:
+ * bit v & filter_mask for every k-mer word v of the slot's text) and, for the LDS build, status (nonzero: the slot did not
+ * fit the block's LDS and was built by the global-atomics kernels).  More rows than the context's slab budget: LZANI_ERR_ARG. */
+#define LZANI_INDEX_BUILD_LDS      0      /* k_idx_build, one block per slot through LDS (overflowing slots: global atomics) */
+#define LZANI_INDEX_BUILD_ATOMICS  1      /* count / scan / fill / sort / buckets with global atomics                          */
+#define LZANI_INDEX_BUILD_SORT     2      /* keys, radix sort by slot segment, one streaming pass                             */
+typedef struct lzani_slab_info {
+    int32_t  key_bits, dir_bits, pos_bits;
+    uint32_t tag_mask, filter_mask;
+    int32_t  build;                       /* LZANI_INDEX_BUILD_*                                                               */
+    uint64_t dir_stride, ent_stride, bk_stride, tw_stride, fl_stride;
+} lzani_slab_info;
+int lzani_debug_index_slab(lzani_ctx *ctx, uint32_t rows, const uint32_t *ref_ids, int with_filter, int with_tw,
+                           lzani_slab_info *info, uint32_t *dirz, uint32_t *ent, uint32_t *bk, uint32_t *tw, uint32_t *fl,
+                           uint32_t *status);
+
+/* Test hook: lzani_run_rows, and after every batch's candidate stage (dense rows and qualifying query lists: candidate
+ * bitmaps from a presence matrix) the first `words` 32-bit words of every pair's candidate bitmap into cbits[pair * words]
+ * and, where the batch counted them, the pair's candidate count into pcount[pair] (0xFFFFFFFF elsewhere); either may be
+ * NULL.  Bit p of a bitmap: query position p has an anchor candidate in the pair's reference.  plan receives the
+ * candidate form of the run. */
+typedef struct lzani_cand_plan {
+    int32_t  pm;                          /* 1: candidate bitmaps from presence matrices                                     */
+    int32_t  pm_bits, rshift;             /* matrix of 2^pm_bits rows; row of a mixed hash h = (h >> rshift) & (2^pm_bits-1)  */
+    uint32_t pm_group;                    /* reference slots per matrix                                                       */
+    uint64_t cb_words;                    /* 32-bit words of one pair's bitmap                                                */
+    uint32_t batches, from_index_launches, cand_launches, counted_batches;   /* k_pm_from_index / k_pm_cand launches       */
+} lzani_cand_plan;
+int lzani_debug_run_candidates(lzani_ctx *ctx, uint32_t n_rows, const uint32_t *ref_ids, const uint64_t *row_off,
+                               const uint32_t *query_ids, lzani_result *out, uint64_t words, uint32_t *cbits,
+                               uint32_t *pcount, lzani_cand_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

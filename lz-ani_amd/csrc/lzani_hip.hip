@@ -136,6 +136,7 @@ struct RunRecord {
     // launches of k_pairs_blk; pair-kernel launches fed by candidate bitmaps, with tickets longest pair first, by a run-time
     // compiled kernel; presence matrices made by k_pm_from_index; batches whose pairs several waves each scanned, their segments
     int blk_launches = 0, pm_launches = 0, lpt_launches = 0, rtc_launches = 0, pmfi_launches = 0, split_launches = 0;
+    int pmc_launches = 0;         // k_pm_cand launches (a group of more than 32,768 queries takes several)
     u64 split_items = 0;
     u64 klaunch[PK_COUNT] = {};   // the launch record: launches per pair-kernel instantiation (PAIR_KERNELS)
 
@@ -146,7 +147,7 @@ struct RunRecord {
         tm.pairs += o.tm.pairs;
         batches += o.batches;
         blk_launches += o.blk_launches; pm_launches += o.pm_launches; lpt_launches += o.lpt_launches; pmfi_launches += o.pmfi_launches;
-        split_launches += o.split_launches; split_items += o.split_items; rtc_launches += o.rtc_launches;
+        split_launches += o.split_launches; split_items += o.split_items; rtc_launches += o.rtc_launches; pmc_launches += o.pmc_launches;
         for (int x = 0; x < PK_COUNT; ++x) klaunch[x] += o.klaunch[x];
         return *this;
     }
@@ -191,6 +192,7 @@ struct lzani_ctx {
     u64 fl_stride = 0;            // words per slot; 0 = no filter (d_fl = the all-ones word)
     u32 fmask = 31;
     u32 slots = 0;
+    int index_build = -1;         // the form the last build_indexes took: LZANI_INDEX_BUILD_LDS / _ATOMICS / _SORT (test hooks)
     // join form of candidate detection (long genomes): per-genome k-mer lists sorted by bucket
     bool join_mode = false, join_ready = false;
     unsigned long long* d_jkeys_in = nullptr;     // unsorted keys, koff[g] + p
@@ -604,6 +606,7 @@ int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, 
         c->run.tm.index_launches += 1;
     }
     if (c->sort_build) {
+        c->index_build = LZANI_INDEX_BUILD_SORT;
         // keys -> radix sort, every slot a segment of its own (lzani_sort.hip) -> the tables in one streaming pass.  A key is
         // hash || position; a position without a k-mer is all ones and sorts behind the slot's keys by the one bit above the hash.
         const int shift_slot = c->geo.kb + c->geo.posbits;
@@ -628,6 +631,7 @@ int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, 
         return LZANI_OK;
     }
     const bool lds_build = c->d_kmL && c->geo.dirbits <= k.lds_index_max_dirbits && k.lds_index;
+    c->index_build = lds_build ? LZANI_INDEX_BUILD_LDS : LZANI_INDEX_BUILD_ATOMICS;
     // blocks per slot of the global-atomics kernels: the whole range when they build every slot, a handful when
     // they only pick up what k_idx_build left (usually nothing)
     const u32 gx_pos = lds_build ? 16u : (u32)((c->Tmax + 255) / 256), gx_bkt = lds_build ? 16u : (nb + 255) / 256;
@@ -898,6 +902,10 @@ QueuePlan plan_queues(u32 n_rows, const u64* row_off, const std::vector<u32>& bs
     return qp;
 }
 
+// Test hook (lzani_debug_run_candidates): host copies of every batch's candidate bitmaps -- the first `words` words of each
+// pair -- and, where the batch counted them, its pairs' candidate counts; indexed by the run's pair offset.
+struct CandSink { u32* cbits; u64 words; u32* pcount; u32 counted_batches; };
+
 // What the batches of one run share: its rows and queues on the device, the launch geometry, the kernels of its tuple.
 struct RunCtx {
     lzani_ctx* c;
@@ -911,6 +919,7 @@ struct RunCtx {
     u64 cbits_stride;
     lzani_rtc::Kernel* rtc_k; int rtc_id;                    // the tuple's run-time compiled kernel, if any, and its row of the launch record
     std::vector<u32> grp_seen = {}; u32 grp_stamp = 0;       // (query lists + candidate bitmaps) the group a query was last seen in
+    CandSink* sink = nullptr;                                // test hook only (lzani_debug_run_candidates)
 };
 
 // Batch b: rows [k0, k0 + rows), pairs [e0, e1), its queues' bounds (QueuePlan::qb); the split / LPT choice of its pair launch.
@@ -1028,6 +1037,7 @@ int candidate_stage(RunCtx& r, Batch& bt)
         for (u32 q0 = 0; q0 < nq; q0 += 32768) {           // gridDim.y is limited to 65535
             pg.q0 = q0;
             const dim3 gc(p.pm_tiles, std::min<u32>(32768, nq - q0)), bc(PM_CAND_THREADS);
+            c->run.pmc_launches += 1;
             switch (pg.rw / 4) {
             case 1: hipLaunchKernelGGL(k_pm_cand<1>, gc, bc, lds, c->stream, pg); break;
             case 2: hipLaunchKernelGGL(k_pm_cand<2>, gc, bc, lds, c->stream, pg); break;
@@ -1235,6 +1245,23 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     return LZANI_OK;
 }
 
+// Test hook: the batch's candidate bitmaps (and counts) into the run's CandSink, after its candidate stage.
+int sink_candidates(RunCtx& r, const Batch& bt)
+{
+    lzani_ctx* c = r.c;
+    CandSink& s = *r.sink;
+    const u64 bp = bt.e1 - bt.e0, w = std::min<u64>(s.words, r.p.cb_words);
+    if (s.cbits && w)
+        HIPCHK(c, hipMemcpy2DAsync(s.cbits + bt.e0 * s.words, s.words * 4, c->d_pm_cbits, r.p.cb_words * 4, w * 4, bp,
+                                   hipMemcpyDeviceToHost, c->stream));
+    if (s.pcount && bt.lpt && c->d_lpt_cnt) {
+        HIPCHK(c, hipMemcpyAsync(s.pcount + bt.e0, c->d_lpt_cnt, bp * 4, hipMemcpyDeviceToHost, c->stream));
+        s.counted_batches += 1;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LZANI_OK;
+}
+
 constexpr int EV = 5;                             // stamps per batch: index begin / end, pairs begin / end, candidates end
 
 // One batch: index build, split / LPT choice, candidate stage, pair launch -- stream work only, stamped into ev.
@@ -1255,6 +1282,7 @@ int run_batch(RunCtx& r, Batch bt, hipEvent_t* ev)
         if (!rc) rc = candidate_stage(r, bt);
         if (rc) return rc;
     }
+    if (r.sink && p.pm && bt.e1 > bt.e0) { rc = sink_candidates(r, bt); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(ev[4], c->stream));
     if (bt.e1 > bt.e0) {
         rc = launch_pairs(r, bt, blk_rows, ev);
@@ -1375,7 +1403,7 @@ int finish_run(lzani_ctx* c, u64 n_pairs, const lzani_rtc::Kernel* rtc_k, const 
 // A run of rows on the resident genome set: check, plan, queues and uploads, then the batches back to back on the stream,
 // then one wait.
 int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
-                  int* d_out, const RegionSink* rs = nullptr)
+                  int* d_out, const RegionSink* rs = nullptr, CandSink* sink = nullptr, RunPlan* plan_out = nullptr)
 {
     if (!c->n) return fail(c, LZANI_ERR_STATE, "lzani_run_rows: no genomes set");
     c->run = RunRecord{};
@@ -1395,6 +1423,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     RunPlan p;
     rc = plan_run(c, k, rf, n_rows, row_off, query_ids != nullptr, rs != nullptr, p);
     if (rc) return rc;
+    if (plan_out) *plan_out = p;
 
     // Everything the batches need from the host -- row tables and the per-XCD work queues of every batch -- is prepared and
     // uploaded before the first launch, so the batches follow each other on the stream without a host round trip in between.
@@ -1443,6 +1472,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     }
 
     RunCtx r{c, k, p, rs, row_off, query_ids, d_out, d_ref, d_q, d_qorder, d_off, d_qcum, max_blocks, dsel, d_cbits, cbits_stride, rtc_k, rtc_id};
+    r.sink = sink;
     for (u32 b = 0; b < n_batches; ++b) {
         const u32 k0 = p.bstart[b], k1 = p.bstart[b + 1];
         rc = run_batch(r, Batch{b, k0, k1 - k0, row_off[k0], row_off[k1], qb.data() + (size_t)b * (NQUEUES + 1)}, c->events.data() + (size_t)EV * b);
@@ -1845,6 +1875,78 @@ int lzani_debug_sort_segments(lzani_ctx* c, const uint64_t* keys, uint64_t* out,
         return fail(c, LZANI_ERR_DEVICE, "lzani_debug_sort_segments: sort failed");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out.p, n * 8, hipMemcpyDeviceToHost));
+    return LZANI_OK;
+}
+
+// Test hook: the index slabs of one batch of `rows` reference ids, built by the run's own build_indexes into slots 0 .. rows-1.
+int lzani_debug_index_slab(lzani_ctx* c, uint32_t rows, const uint32_t* ref_ids, int with_filter, int with_tw,
+                           lzani_slab_info* info, uint32_t* dirz, uint32_t* ent, uint32_t* bk, uint32_t* tw, uint32_t* fl,
+                           uint32_t* status)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (!c->n || !rows || !ref_ids || !info) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: bad arguments");
+    if (c->ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_index_slab: the genomes are not resident (out-of-core set)");
+    for (u32 k = 0; k < rows; ++k)
+        if (ref_ids[k] >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: reference id out of range");
+    HIPCHK(c, hipSetDevice(c->dev));
+    int rc = ensure_slabs(c, rows);
+    if (rc) return rc;
+    if (c->slots < rows) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: more rows than index slabs");
+    DevBuf<u32> d_ref;
+    HIPCHK(c, d_ref.alloc(rows));
+    HIPCHK(c, hipMemcpy(d_ref.p, ref_ids, (size_t)rows * 4, hipMemcpyHostToDevice));
+    rc = build_indexes(c, Knobs{}, d_ref, rows, with_filter != 0, with_tw != 0);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    info->key_bits = c->geo.kb; info->dir_bits = c->geo.dirbits; info->pos_bits = c->geo.posbits; info->tag_mask = c->geo.tagmask;
+    info->filter_mask = c->fmask;
+    info->build = c->index_build;
+    info->dir_stride = c->dir_stride; info->ent_stride = c->ent_stride; info->bk_stride = c->bk_stride;
+    // (what this build wrote: the sort build leaves the tag words out without with_tw, every build the filter without with_filter)
+    info->tw_stride = (c->index_build != LZANI_INDEX_BUILD_SORT || with_tw) ? c->tw_stride : 0;
+    info->fl_stride = with_filter ? c->fl_stride : 0;
+    const size_t r = rows;
+    if (dirz) HIPCHK(c, hipMemcpy(dirz, c->d_dirz, r * c->dir_stride * 4, hipMemcpyDeviceToHost));
+    if (ent) HIPCHK(c, hipMemcpy(ent, c->d_ent, r * c->ent_stride * 4, hipMemcpyDeviceToHost));
+    if (bk && info->bk_stride) HIPCHK(c, hipMemcpy(bk, c->d_bk, r * info->bk_stride * 4, hipMemcpyDeviceToHost));
+    if (tw && info->tw_stride) HIPCHK(c, hipMemcpy(tw, c->d_tw, r * info->tw_stride * 4, hipMemcpyDeviceToHost));
+    if (fl && info->fl_stride) HIPCHK(c, hipMemcpy(fl, c->d_fl, r * info->fl_stride * 4, hipMemcpyDeviceToHost));
+    if (status) {
+        if (c->index_build == LZANI_INDEX_BUILD_LDS) HIPCHK(c, hipMemcpy(status, c->d_status, r * 4, hipMemcpyDeviceToHost));
+        else memset(status, 0, r * 4);
+    }
+    return LZANI_OK;
+}
+
+// Test hook: lzani_run_rows with the candidate bitmaps of every batch copied out on the way (CandSink).
+int lzani_debug_run_candidates(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids, const uint64_t* row_off,
+                               const uint32_t* query_ids, lzani_result* out, uint64_t words, uint32_t* cbits,
+                               uint32_t* pcount, lzani_cand_plan* plan)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (!ref_ids || !row_off || !plan) return fail(c, LZANI_ERR_ARG, "lzani_debug_run_candidates: null argument");
+    if (c->ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_run_candidates: the genomes are not resident (out-of-core set)");
+    const u64 n_pairs = n_rows ? row_off[n_rows] : 0;
+    if (n_pairs && !out) return fail(c, LZANI_ERR_ARG, "lzani_debug_run_candidates: null output");
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (pcount) std::fill(pcount, pcount + n_pairs, 0xFFFFFFFFu);
+    DevBuf<lzani_result> d_out;
+    if (n_pairs) HIPCHK(c, d_out.alloc(n_pairs));
+    CandSink sink{cbits, words, pcount, 0};
+    RunPlan p;
+    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.p, nullptr, &sink, &p);
+    if (rc == LZANI_OK && n_pairs) {
+        hipError_t e = hipMemcpy(out, d_out.p, n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy results: ") + hipGetErrorString(e));
+    }
+    if (rc) return rc;
+    plan->pm = p.pm; plan->pm_bits = p.pm ? p.pm_bits : 0; plan->rshift = p.pm ? c->geo.kb - p.pm_bits : 0;
+    plan->pm_group = p.pm ? p.pm_group : 0;
+    plan->cb_words = p.pm ? p.cb_words : 0;
+    plan->batches = c->run.batches;
+    plan->from_index_launches = (uint32_t)c->run.pmfi_launches;
+    plan->cand_launches = (uint32_t)c->run.pmc_launches;
+    plan->counted_batches = sink.counted_batches;
     return LZANI_OK;
 }
 

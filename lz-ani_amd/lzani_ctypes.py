@@ -33,7 +33,7 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_group_set_genomes", "lzani_group_run_rows", "lzani_group_get_timing", "lzani_plan_gather", "lzani_get_rtc_info", "lzani_debug_rtc_compile",
            "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name",
            "lzani_set_genome_memory", "lzani_plan_blocks", "lzani_get_residency", "lzani_group_set_genome_memory",
-           "lzani_group_get_residency")
+           "lzani_group_get_residency", "lzani_debug_index_slab", "lzani_debug_run_candidates")
 
 
 class LzaniError(RuntimeError):
@@ -59,6 +59,21 @@ class LayoutInfo(C.Structure):
 class RtcInfo(C.Structure):
     _fields_ = [("folded_ahead_of_time", C.c_int32), ("null_chain", C.c_int32), ("kernels_built", C.c_int32),
                 ("kernels_from_cache", C.c_int32), ("kernels_failed", C.c_int32), ("reserved_", C.c_int32), ("build_ms", C.c_double)]
+
+
+class SlabInfo(C.Structure):
+    _fields_ = [("key_bits", C.c_int32), ("dir_bits", C.c_int32), ("pos_bits", C.c_int32), ("tag_mask", C.c_uint32),
+                ("filter_mask", C.c_uint32), ("build", C.c_int32), ("dir_stride", C.c_uint64), ("ent_stride", C.c_uint64),
+                ("bk_stride", C.c_uint64), ("tw_stride", C.c_uint64), ("fl_stride", C.c_uint64)]
+
+
+INDEX_BUILDS = ("lds", "atomics", "sort")          # LZANI_INDEX_BUILD_*
+
+
+class CandPlan(C.Structure):
+    _fields_ = [("pm", C.c_int32), ("pm_bits", C.c_int32), ("rshift", C.c_int32), ("pm_group", C.c_uint32),
+                ("cb_words", C.c_uint64), ("batches", C.c_uint32), ("from_index_launches", C.c_uint32),
+                ("cand_launches", C.c_uint32), ("counted_batches", C.c_uint32)]
 
 
 class ResidencyInfo(C.Structure):
@@ -108,6 +123,9 @@ def load_library():
         lib.lzani_run_rows_regions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_uint64, C.c_void_p]
         lib.lzani_debug_get_index.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+        lib.lzani_debug_index_slab.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+        lib.lzani_debug_run_candidates.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lzani_debug_sort_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int]
         lib.lzani_row_costs.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.lzani_partition_rows.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -454,3 +472,43 @@ class Engine:
         self._check(self.lib.lzani_debug_get_index(self.h, gid, _ptr(t2), _ptr(nm), _ptr(dirz), _ptr(ent),
                                                    C.byref(n_ent), _ptr(geom)), "debug")
         return dict(t2=t2, nm=nm, dirz=dirz, ent=ent[:n_ent.value].copy(), geom=geom)
+
+    def debug_index_slab(self, ref_ids, with_filter=True, with_tw=True):
+        """The index slabs of one batch of reference ids (lzani_debug_index_slab): a dict of the geometry, the build that ran
+        ("lds", "atomics", "sort") and per-slot arrays [rows, stride] of dirz, ent, bk, tw, fl (None where not built) and
+        status (LDS build: nonzero = the slot fell back to the global-atomics kernels)."""
+        ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+        rows = len(ref_ids)
+        info = SlabInfo()
+        self._check(self.lib.lzani_debug_index_slab(self.h, rows, _ptr(ref_ids), int(with_filter), int(with_tw), C.byref(info),
+                                                    None, None, None, None, None, None), "lzani_debug_index_slab")
+        bufs = {k: np.zeros((rows, getattr(info, k + "_stride")), dtype=np.uint32) for k in ("dir", "ent", "bk", "tw", "fl")}
+        status = np.zeros(rows, dtype=np.uint32)
+        self._check(self.lib.lzani_debug_index_slab(self.h, rows, _ptr(ref_ids), int(with_filter), int(with_tw), C.byref(info),
+                                                    *[_ptr(bufs[k]) for k in ("dir", "ent", "bk", "tw", "fl")], _ptr(status)),
+                    "lzani_debug_index_slab")
+        out = {k: getattr(info, k) for k, _ in SlabInfo._fields_}
+        out["build"] = INDEX_BUILDS[info.build]
+        out.update(dirz=bufs["dir"], ent=bufs["ent"], status=status)
+        for k in ("bk", "tw", "fl"):
+            out[k] = bufs[k] if getattr(info, k + "_stride") else None
+        return out
+
+    def debug_run_candidates(self, ref_ids, row_off, query_ids=None, words=None):
+        """lzani_run_rows plus every pair's candidate bitmap (first `words` 32-bit words; default: enough for the longest
+        genome) and candidate count (0xFFFFFFFF where its batch did not count): (results int32[n_pairs, 3],
+        cbits uint32[n_pairs, words], pcount uint32[n_pairs], plan dict)."""
+        ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        q = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint32)
+        n_pairs = int(row_off[-1]) if len(row_off) else 0
+        if words is None:
+            words = (int(self.lens.max()) + self.params["mrd"] + 320 + 1023) // 1024 * 32
+        out = np.zeros((n_pairs, 3), dtype=np.int32)
+        cbits = np.zeros((n_pairs, words), dtype=np.uint32)
+        pcount = np.zeros(n_pairs, dtype=np.uint32)
+        plan = CandPlan()
+        self._check(self.lib.lzani_debug_run_candidates(self.h, len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q), _ptr(out),
+                                                        C.c_uint64(words), _ptr(cbits), _ptr(pcount), C.byref(plan)),
+                    "lzani_debug_run_candidates")
+        return out, cbits, pcount, {k: getattr(plan, k) for k, _ in CandPlan._fields_}

@@ -362,4 +362,21 @@ int model_ext_records_agree(const uint8_t* rcodes, uint32_t rlen, const uint8_t*
     return bad;
 }
 
+// The k-mer words of one genome's reference text as k_kmers makes its mal-mer words: per position p < T (T = 2 len + 3 mrd)
+// valid[p] = kmer_at(R, p, k) and hash[p] = mix_key(key, 2 k) there (0 elsewhere).  For the numpy port in tests/index_model.py.
+int model_kmers(const uint8_t* codes, uint32_t len, const int32_t* p8, int32_t k, uint8_t* valid, uint64_t* hash)
+{
+    Params P{p8[0], p8[1], p8[2], p8[3], p8[4], p8[5], p8[6], p8[7]};
+    if (!params_supported(P) || k < 1 || k > 32) return -1;
+    Genome g;
+    pack_genome(g, codes, (int)len, P);
+    const TextView R = g.rview();
+    for (int p = 0; p < g.T; ++p) {
+        u64 key = 0;
+        valid[p] = kmer_at(R, p, k, key) ? 1 : 0;
+        hash[p] = valid[p] ? mix_key(key, 2 * k) : 0;
+    }
+    return 0;
+}
+
 }  // extern "C"
