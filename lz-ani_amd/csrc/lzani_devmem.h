@@ -1,0 +1,67 @@
+// lzani_devmem.h -- the one owner of device memory (and of pinned host memory) on the host side of the engine.
+// Host only: no kernel sees it, and it is not among the sources a run-time compile embeds (lzani_rtc.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+
+namespace lzani {
+
+// `capacity()` elements of T on the device (PINNED: in page-locked host memory), released by the destructor.  Move-only,
+// empty by default.  Sizes are counts of T; a count of 0 allocates one element, so that a live buffer is never null.
+template <class T, bool PINNED = false>
+class DevMem {
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+
+public:
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    DevMem& operator=(DevMem&& o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; }
+        return *this;
+    }
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { reset(); }
+
+    void reset()
+    {
+        if (p_) { if constexpr (PINNED) (void)hipHostFree(p_); else (void)hipFree(p_); }
+        p_ = nullptr; cap_ = 0;
+    }
+    // A fresh buffer of exactly `count` elements; what it held is released first.  Empty where it cannot be had.
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        count = std::max<size_t>(count, 1);
+        hipError_t e;
+        if constexpr (PINNED) e = hipHostMalloc((void**)&p_, count * sizeof(T), hipHostMallocDefault);
+        else e = hipMalloc((void**)&p_, count * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr; else cap_ = count;
+        return e;
+    }
+    // At least `count` elements: kept if it is large enough already, else released and allocated anew (the contents are
+    // not carried over).
+    hipError_t reserve(size_t count) { return count <= cap_ ? hipSuccess : alloc(count); }
+
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t capacity() const { return cap_; }
+    size_t bytes() const { return cap_ * sizeof(T); }
+};
+template <class T>
+using PinMem = DevMem<T, true>;
+
+// For the callers that fall back instead of failing: whether the allocation succeeded; the runtime's sticky error is
+// cleared where it did not.
+inline bool got(hipError_t e)
+{
+    if (e == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+}  // namespace lzani

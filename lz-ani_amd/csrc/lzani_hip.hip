@@ -48,6 +48,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_kernels_pairs.h"
 #include "lzani_kernels_split.h"
 #include "lzani_rtc.h"
+#include "lzani_devmem.h"
 
 // ============================================================================================
 // Host side of the C-ABI
@@ -153,94 +154,55 @@ struct RunRecord {
     }
 };
 
-struct lzani_ctx {
-    Params P;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> events;    // four per batch of a run (index begin/end, pairs begin/end)
-    int n_cus = 256;
-    std::string err;
+// ---- the context, grouped by lifetime; every group owns its device memory (lzani_devmem.h), so that dropping a group
+// ---- is assigning a fresh one
 
+// The device tables of a genome set (kernels see them as a GenomeTab); out-of-core: of the resident region.
+struct GenomeTables {
+    DevMem<u64> t2, nm, nmoff;
+    DevMem<int> L, hasN;
+    DevMem<u32> kmL, kmS;         // k-mer arrays (fast path: mal, msl <= 15), 64 entries per nm word
+};
+
+// Join form of candidate detection (long genomes): per-genome k-mer lists sorted by bucket.  A group of its own inside the
+// genome set: the lists of an out-of-core run belong to one tile's local genome table and are released between tiles.
+struct JoinLists {
+    bool ready = false;
+    DevMem<unsigned long long> keys;      // sorted
+    DevMem<u64> koff;                     // per genome: offset of its forward positions (n + 1)
+    DevMem<u64> soff;                     // per genome: offset of its sorted valid keys (n + 1)
+    DevMem<u32> cnt;
+    std::vector<u64> h_koff;
+};
+
+// lzani_set_genomes -> the next one.
+struct GenomeSet {
     u32 n = 0, n_pending = 0;     // n_pending: genome count while lzani_set_genomes is still at work
     std::vector<int> L;
     std::vector<u64> nmoff;
     int Tmax = 0;
     IndexGeom geo{};
-    u64* d_t2 = nullptr;
-    u64* d_nm = nullptr;
-    u64* d_nmoff = nullptr;
-    int* d_L = nullptr;
-    int* d_hasN = nullptr;
-    u32* d_kmL = nullptr;     // k-mer arrays (fast path: mal, msl <= 15), 64 entries per nm word
-    u32* d_kmS = nullptr;
+    GenomeTables tab;
     u64 total_nm = 0;
     bool kmers_ready = false;
-    bool km_timed = false;        // the last run made the k-mer words (ev_km holds their stamps)
-    double join_ms_pending = 0;   // ... and / or the join lists: their time, added to that run's kmers_ms
-    hipEvent_t ev_km[2] = {nullptr, nullptr};
     bool all_nfree = false;       // no genome holds an N: the NFREE kernel instantiation applies
-
-    u32* d_dirz = nullptr;
-    u32* d_ent = nullptr;
-    u32* d_bk = nullptr;          // bucket tables
-    u64 bk_stride = 0;
-    u32* d_status = nullptr;      // per slot: the LDS index build left this slot to the global-atomics kernels
-    bool build_attr_set = false;
-    u32* d_tw = nullptr;          // tag words of the bucket tables (tag bits <= 7)
-    u64 tw_stride = 0;
-    u32* d_fl = nullptr;          // presence filters (probe form with tag words), or one all-ones word
-    u64 fl_stride = 0;            // words per slot; 0 = no filter (d_fl = the all-ones word)
-    u32 fmask = 31;
-    u32 slots = 0;
-    int index_build = -1;         // the form the last build_indexes took: LZANI_INDEX_BUILD_LDS / _ATOMICS / _SORT (test hooks)
-    // join form of candidate detection (long genomes): per-genome k-mer lists sorted by bucket
-    bool join_mode = false, join_ready = false;
-    unsigned long long* d_jkeys_in = nullptr;     // unsorted keys, koff[g] + p
-    unsigned long long* d_jkeys = nullptr;        // sorted
-    u64* d_jkoff = nullptr;                       // per genome: offset of its forward positions (n + 1)
-    u64* d_jsoff = nullptr;                       // per genome: offset of its sorted valid keys (n + 1)
-    u32* d_jcnt = nullptr;
-    void* d_jtmp = nullptr;       // radix-sort scratch (join lists and the sort-based index build)
-    size_t jtmp_bytes = 0;
-    // sort-based index build (large directories): keys of the batch's references, unsorted / sorted, per-slot counts and starts
-    bool sort_build = false;
-    unsigned long long* d_ikeys_in = nullptr;
-    unsigned long long* d_ikeys = nullptr;
-    u32* d_icnt = nullptr;
-    u64* d_ibase = nullptr;
-    std::vector<u64> jkoff;
-    u32 max_slots = 65535;        // gridDim.y limit; LZANI_MAX_SLOTS lowers it (tests force the multi-batch path)
+    // the form of the anchor index, chosen per set (choose_index_form)
     u64 dir_stride = 0, ent_stride = 0;
-    unsigned long long* d_cursor = nullptr;
-    u32* d_blkctr = nullptr;      // k_pairs_blk: one pair counter per block
+    u64 bk_stride = 0;            // bucket tables
+    u64 tw_stride = 0;            // tag words of the bucket tables (tag bits <= 7)
+    u64 fl_stride = 0;            // presence filters: words per slot; 0 = no filter (one all-ones word)
+    u32 fmask = 31;
+    bool join_mode = false;
+    bool sort_build = false;      // sort-based index build (large directories)
+    u32 max_slots = 65535;        // gridDim.y limit; LZANI_MAX_SLOTS lowers it (tests force the multi-batch path)
     int blk_fold = -1;            // k_pairs_blk: LDS filter = global filter folded 2^blk_fold times (-1: not decided yet, -2: does not fit)
-    // dense rows: candidates from the presence matrix of a group of references (lzani_kernels_cand.h)
-    u32* d_pm = nullptr;          // the matrix of one group: 2^pm_bits rows of PM_GROUP bits
-    size_t pm_bytes = 0;
-    u32* d_pm_cbits = nullptr;    // candidate bitmaps of a batch's pairs
-    size_t pm_cbits_bytes = 0;
-    u32* d_pm_pidx = nullptr;     // rows with query lists: pair of (query, slot of the group), query flags + list + count behind it
-    size_t pm_pidx_bytes = 0;
-    u32* d_lpt_cnt = nullptr;     // batches of few, long pairs: candidates per pair, then the ticket keys unsorted / sorted
-    unsigned long long* d_lpt_keys = nullptr;
-    size_t lpt_pairs = 0;
-    bool pm_attr_set = false;
-    u32 pmfi_attr_set = 0;                // k_pm_from_index<RW>: bit RW = its LDS limit is raised
-
-    RunRecord run;
-    // pair kernels compiled at run time for this context's parameters (lzani_rtc.h); none for the two ahead-of-time tuples
-    lzani_rtc::State rtc;
-    std::string arch;             // the device's gfx target, as hipRTC wants it
-    u64 pairs_seen = 0;           // directed pairs this context has been asked for so far (a run-time compile must pay)
-
-    void* comm = nullptr;         // ncclComm_t of lzani_comm_init (one process per GPU), lzani_multi.h
-    u32 n_ranks = 1, rank = 0;
+    JoinLists jl;
+    DevMem<unsigned char> d_jtmp; // radix-sort scratch (join lists, the sort-based index build, ticket order)
 
     // Out-of-core genome sets (lzani_ooc.h): the set stays on the host and the runs go tile by tile over
     // (reference block, query block).  Outside a run n / L describe the whole set; the device tables above then
     // describe the resident region (two halves, A and B, of half_words packed words each).
-    u64 mem_req = 0;              // lzani_set_genome_memory: applies at the next lzani_set_genomes; 0 = automatic
-    u64 mem_limit = 0;            // the limit applied to the current set (0: automatic mode kept it in-core)
+    u64 mem_limit = 0;            // the limit applied to this set (0: automatic mode kept it in-core)
     bool ooc = false;
     std::vector<uint8_t> h_codes;                 // host copy of the set's codes, genome after genome
     std::vector<u64> h_codeoff;
@@ -251,12 +213,67 @@ struct lzani_ctx {
     u32 half_genomes = 0;                         // genomes of the largest block
     int half_block[2] = {-1, -1};                 // the block each half holds (-1: none)
     int half_a = 0;                               // which half is A (the reference block's)
-    uint8_t* d_stage = nullptr;                   // 1 B per base of the largest block
-    u64* d_up_tab = nullptr;                      // an upload's code offsets and word offsets (2 x half_genomes)
-    int* d_up_L = nullptr;                        // ... lengths, and N flags written by k_pack (2 x half_genomes)
-    u32 res_tiles = 0;                            // residency counters of the last run (lzani_get_residency)
-    u64 res_uploads = 0, res_peak = 0;
-    double res_upload_ms = 0;
+    DevMem<uint8_t> d_stage;                      // 1 B per base of the largest block
+    DevMem<u64> d_up_tab;                         // an upload's code offsets and word offsets (2 x half_genomes)
+    DevMem<int> d_up_L;                           // ... lengths, and N flags written by k_pack (2 x half_genomes)
+};
+
+// The index slabs: grown by ensure_slabs, dropped with the genome set.
+struct IndexSlabs {
+    u32 slots = 0;
+    int index_build = -1;         // the form the last build_indexes took: LZANI_INDEX_BUILD_LDS / _ATOMICS / _SORT (test hooks)
+    DevMem<u32> d_dirz, d_ent;
+    DevMem<u32> d_bk, d_tw;       // bucket tables and their tag words
+    DevMem<u32> d_fl;             // presence filters (probe form with tag words), or one all-ones word
+    DevMem<u32> d_status;         // per slot: the LDS index build left this slot to the global-atomics kernels
+    // sort-based index build: keys of the batch's references, unsorted / sorted, per-slot counts and starts
+    DevMem<unsigned long long> d_ikeys_in, d_ikeys;
+    DevMem<u32> d_icnt;
+    DevMem<u64> d_ibase;
+};
+
+// Candidate scratch of dense rows (lzani_kernels_cand.h): grown by plan_bitmaps / choose_split_lpt, dropped with the
+// genome set or when one of them cannot be had.
+struct CandScratch {
+    DevMem<u32> d_pm;             // the presence matrix of one group: 2^pm_bits rows of PM_GROUP bits
+    DevMem<u32> d_pm_cbits;       // candidate bitmaps of a batch's pairs
+    DevMem<u32> d_pm_pidx;        // rows with query lists: pair of (query, slot of the group), query flags + list + count behind it
+    DevMem<u32> d_lpt_cnt;        // batches of few, long pairs: candidates per pair ...
+    DevMem<unsigned long long> d_lpt_keys;        // ... then the ticket keys unsorted / sorted (two per pair)
+};
+
+// Residency counters of the last run (lzani_get_residency).
+struct Residency { u32 tiles = 0; u64 uploads = 0, peak = 0; double upload_ms = 0; };
+
+struct lzani_ctx {
+    // create -> destroy
+    Params P;
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    std::vector<hipEvent_t> events;    // four per batch of a run (index begin/end, pairs begin/end)
+    int n_cus = 256;
+    std::string err;
+    hipEvent_t ev_km[2] = {nullptr, nullptr};
+    bool km_timed = false;        // the last run made the k-mer words (ev_km holds their stamps)
+    double join_ms_pending = 0;   // ... and / or the join lists: their time, added to that run's kmers_ms
+    DevMem<unsigned long long> d_cursor;
+    DevMem<u32> d_blkctr;         // k_pairs_blk: one pair counter per block
+    bool build_attr_set = false, pm_attr_set = false;
+    u32 pmfi_attr_set = 0;        // k_pm_from_index<RW>: bit RW = its LDS limit is raised
+    // pair kernels compiled at run time for this context's parameters (lzani_rtc.h); none for the two ahead-of-time tuples
+    lzani_rtc::State rtc;
+    std::string arch;             // the device's gfx target, as hipRTC wants it
+    u64 pairs_seen = 0;           // directed pairs this context has been asked for so far (a run-time compile must pay)
+    void* comm = nullptr;         // ncclComm_t of lzani_comm_init (one process per GPU), lzani_multi.h
+    u32 n_ranks = 1, rank = 0;
+    u64 mem_req = 0;              // lzani_set_genome_memory: applies at the next lzani_set_genomes; 0 = automatic
+
+    GenomeSet gs;
+    IndexSlabs sl;
+    CandScratch cs;
+    // the last run
+    RunRecord run;
+    Residency res;
 };
 
 namespace {
@@ -268,18 +285,6 @@ bool trace_on()
     return on == 1;
 }
 #define TRACE(...) do { if (trace_on()) { fprintf(stderr, "[lzani] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
-
-// Temporary device buffer, released on every exit path of the call that owns it.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)); }
-    operator T*() const { return p; }
-};
 
 int fail(lzani_ctx* c, int code, const std::string& msg)
 {
@@ -294,44 +299,6 @@ int fail(lzani_ctx* c, int code, const std::string& msg)
             return fail(c, e_ == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE,            \
                         std::string(#call) + ": " + hipGetErrorString(e_));                           \
     } while (0)
-
-// (the join lists of an out-of-core run belong to one tile's local genome table: released between tiles)
-void free_join_lists(lzani_ctx* c)
-{
-    hipFree(c->d_jkeys); hipFree(c->d_jkoff); hipFree(c->d_jsoff); hipFree(c->d_jcnt);
-    c->d_jkeys = nullptr; c->d_jkoff = c->d_jsoff = nullptr; c->d_jcnt = nullptr;
-    c->join_ready = false;
-}
-void free_genomes(lzani_ctx* c)
-{
-    hipFree(c->d_t2); hipFree(c->d_nm); hipFree(c->d_nmoff); hipFree(c->d_L); hipFree(c->d_kmL); hipFree(c->d_kmS); hipFree(c->d_hasN);
-    free_join_lists(c);
-    hipFree(c->d_jtmp);
-    c->d_jkeys_in = nullptr; c->d_jtmp = nullptr; c->jtmp_bytes = 0; c->join_mode = false;
-    c->d_hasN = nullptr;
-    c->d_t2 = c->d_nm = c->d_nmoff = nullptr; c->d_L = nullptr; c->d_kmL = c->d_kmS = nullptr; c->kmers_ready = false;
-    c->n = 0;
-    hipFree(c->d_stage); hipFree(c->d_up_tab); hipFree(c->d_up_L);
-    c->d_stage = nullptr; c->d_up_tab = nullptr; c->d_up_L = nullptr;
-    c->ooc = false; c->mem_limit = 0;
-    std::vector<uint8_t>().swap(c->h_codes); std::vector<u64>().swap(c->h_codeoff); std::vector<int>().swap(c->h_hasN);
-    c->blk_first.clear(); c->blk_bytes.clear();
-    c->half_words = 0; c->half_genomes = 0; c->half_block[0] = c->half_block[1] = -1; c->half_a = 0;
-    c->res_tiles = 0; c->res_uploads = c->res_peak = 0; c->res_upload_ms = 0;
-}
-void free_pm(lzani_ctx* c)
-{
-    hipFree(c->d_pm); hipFree(c->d_pm_cbits); hipFree(c->d_pm_pidx); hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
-    c->d_pm = c->d_pm_cbits = c->d_pm_pidx = nullptr; c->pm_bytes = c->pm_cbits_bytes = c->pm_pidx_bytes = 0;
-    c->d_lpt_cnt = nullptr; c->d_lpt_keys = nullptr; c->lpt_pairs = 0;
-}
-void free_slabs(lzani_ctx* c)
-{
-    hipFree(c->d_dirz); hipFree(c->d_ent); hipFree(c->d_bk); hipFree(c->d_tw); hipFree(c->d_fl); hipFree(c->d_status);
-    hipFree(c->d_ikeys_in); hipFree(c->d_ikeys); hipFree(c->d_icnt); hipFree(c->d_ibase);
-    c->d_ikeys_in = c->d_ikeys = nullptr; c->d_icnt = nullptr; c->d_ibase = nullptr;
-    c->d_dirz = c->d_ent = c->d_bk = c->d_tw = c->d_fl = c->d_status = nullptr; c->slots = 0;
-}
 
 // Per-genome k-mer words exist for mal, msl <= 15 (the fast path).
 bool kmer_words_of(const Params& P) { return P.mal <= 15 && P.msl <= 15; }
@@ -373,72 +340,76 @@ IndexForm index_form_of(const Params& P, const IndexGeom& geo, u32 n)
 void choose_index_form(lzani_ctx* c)
 {
     {
-        const IndexForm f = index_form_of(c->P, c->geo, c->n_pending);
-        c->bk_stride = f.bk_stride;
-        c->tw_stride = f.tw_stride;
-        c->join_mode = f.join_mode;
+        const IndexForm f = index_form_of(c->P, c->gs.geo, c->gs.n_pending);
+        c->gs.bk_stride = f.bk_stride;
+        c->gs.tw_stride = f.tw_stride;
+        c->gs.join_mode = f.join_mode;
     }
     // Sort-based index build where the directory is beyond the LDS-staged build (2^19 buckets): keys of 64 bits with up
     // to 16 bits of slot number (LZANI_SORT_INDEX_MIN_DIRBITS=0, tests: at every size)
-    c->sort_build = kmer_words_of(c->P) && c->geo.dirbits >= env_int("LZANI_SORT_INDEX_MIN_DIRBITS").value_or(20) &&
-                    c->geo.kb + c->geo.posbits <= 60 && !env_is("LZANI_NO_SORT_INDEX", '1');
+    c->gs.sort_build = kmer_words_of(c->P) && c->gs.geo.dirbits >= env_int("LZANI_SORT_INDEX_MIN_DIRBITS").value_or(20) &&
+                    c->gs.geo.kb + c->gs.geo.posbits <= 60 && !env_is("LZANI_NO_SORT_INDEX", '1');
     // Presence filter in front of the tag-word probes (probe form only; k_pairs_blk keeps the reference's in LDS): ~3 bits
     // per text position, at most 2^18 bits (genomes up to ~128 kbp); beyond, one all-ones word passes everything
     {
         const int fmax = env_int("LZANI_FILTER_MAX_BITS").value_or(18);      // 2^18 bits = 32 KB of LDS per block of 16 waves
-        const int fbits = std::min(ceil_log2((u64)std::max(c->Tmax, 1024)) + 1, fmax);
-        const bool on = c->tw_stride && !c->join_mode && ceil_log2((u64)std::max(c->Tmax, 1024)) <= fmax && !env_is("LZANI_NO_FILTER", '1');
-        c->fl_stride = on ? ((u64)1 << fbits) / 32 : 0;
-        c->blk_fold = -1;
-        c->fmask = on ? (u32)((1u << fbits) - 1u) : 31u;
+        const int fbits = std::min(ceil_log2((u64)std::max(c->gs.Tmax, 1024)) + 1, fmax);
+        const bool on = c->gs.tw_stride && !c->gs.join_mode && ceil_log2((u64)std::max(c->gs.Tmax, 1024)) <= fmax && !env_is("LZANI_NO_FILTER", '1');
+        c->gs.fl_stride = on ? ((u64)1 << fbits) / 32 : 0;
+        c->gs.blk_fold = -1;
+        c->gs.fmask = on ? (u32)((1u << fbits) - 1u) : 31u;
     }
     const int ms = env_int("LZANI_MAX_SLOTS").value_or(0);
-    c->max_slots = ms > 0 ? (u32)std::min(65535, ms) : 65535u;
-    if (c->sort_build)                                  // the slot number shares the 64-bit key with hash and position
-        c->max_slots = (u32)std::min<u64>(c->max_slots, (1ull << std::min(16, 64 - c->geo.kb - c->geo.posbits)) - 1);
+    c->gs.max_slots = ms > 0 ? (u32)std::min(65535, ms) : 65535u;
+    if (c->gs.sort_build)                                  // the slot number shares the 64-bit key with hash and position
+        c->gs.max_slots = (u32)std::min<u64>(c->gs.max_slots, (1ull << std::min(16, 64 - c->gs.geo.kb - c->gs.geo.posbits)) - 1);
 }
 
 int ensure_slabs(lzani_ctx* c, u32 want_rows)
 {
-    size_t per_slot = (size_t)4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride) + (c->sort_build ? (size_t)16 * c->Tmax + 16 : 0);
+    size_t per_slot = (size_t)4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride) + (c->gs.sort_build ? (size_t)16 * c->gs.Tmax + 16 : 0);
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    size_t have = c->slots * per_slot;
+    size_t have = c->sl.slots * per_slot;
     size_t budget = (size_t)((free_b + have) * 0.6);
-    u32 slots = (u32)std::min<size_t>(std::min<u32>(want_rows, c->max_slots), std::max<size_t>(1, budget / per_slot));
-    if (slots <= c->slots) return LZANI_OK;
-    free_slabs(c);
-    HIPCHK(c, hipMalloc(&c->d_dirz, (size_t)slots * c->dir_stride * 4));
-    HIPCHK(c, hipMalloc(&c->d_ent, (size_t)slots * c->ent_stride * 4));
-    if (c->bk_stride) HIPCHK(c, hipMalloc(&c->d_bk, (size_t)slots * c->bk_stride * 4));
-    if (c->tw_stride) HIPCHK(c, hipMalloc(&c->d_tw, (size_t)slots * c->tw_stride * 4));
-    if (c->tw_stride) {
-        HIPCHK(c, hipMalloc(&c->d_fl, std::max<size_t>((size_t)slots * c->fl_stride * 4, 4)));
-        if (!c->fl_stride) HIPCHK(c, hipMemset(c->d_fl, 0xFF, 4));
+    u32 slots = (u32)std::min<size_t>(std::min<u32>(want_rows, c->gs.max_slots), std::max<size_t>(1, budget / per_slot));
+    if (slots <= c->sl.slots) return LZANI_OK;
+    c->sl = IndexSlabs{};                              // released first: two generations need not fit
+    IndexSlabs s;
+    HIPCHK(c, s.d_dirz.alloc((size_t)slots * c->gs.dir_stride));
+    HIPCHK(c, s.d_ent.alloc((size_t)slots * c->gs.ent_stride));
+    if (c->gs.bk_stride) HIPCHK(c, s.d_bk.alloc((size_t)slots * c->gs.bk_stride));
+    if (c->gs.tw_stride) HIPCHK(c, s.d_tw.alloc((size_t)slots * c->gs.tw_stride));
+    if (c->gs.tw_stride) {
+        HIPCHK(c, s.d_fl.alloc((size_t)slots * c->gs.fl_stride));
+        if (!c->gs.fl_stride) HIPCHK(c, hipMemset(s.d_fl, 0xFF, 4));
     }
-    HIPCHK(c, hipMalloc(&c->d_status, (size_t)slots * 4));
-    if (c->sort_build) {
-        HIPCHK(c, hipMalloc(&c->d_ikeys_in, (size_t)slots * c->Tmax * 8));
-        HIPCHK(c, hipMalloc(&c->d_ikeys, (size_t)slots * c->Tmax * 8));
-        HIPCHK(c, hipMalloc(&c->d_icnt, (size_t)slots * 4));
-        HIPCHK(c, hipMalloc(&c->d_ibase, (size_t)slots * 8));
+    HIPCHK(c, s.d_status.alloc(slots));
+    if (c->gs.sort_build) {
+        HIPCHK(c, s.d_ikeys_in.alloc((size_t)slots * c->gs.Tmax));
+        HIPCHK(c, s.d_ikeys.alloc((size_t)slots * c->gs.Tmax));
+        HIPCHK(c, s.d_icnt.alloc(slots));
+        HIPCHK(c, s.d_ibase.alloc(slots));
     }
-    c->slots = slots;
+    s.slots = slots;
+    c->sl = std::move(s);
     return LZANI_OK;
 }
 
 // The radix sort's scratch grown to `need` bytes; sync: after the stream's queued work, which may still be using it.
 int grow_jtmp(lzani_ctx* c, size_t need, bool sync)
 {
-    if (need <= c->jtmp_bytes) return LZANI_OK;
+    if (need <= c->gs.d_jtmp.capacity()) return LZANI_OK;
     if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(c->d_jtmp); c->d_jtmp = nullptr; c->jtmp_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->d_jtmp, need));
-    c->jtmp_bytes = need;
+    HIPCHK(c, c->gs.d_jtmp.alloc(need));
     return LZANI_OK;
 }
 
-GenomeTab gtab(const lzani_ctx* c) { return GenomeTab{c->d_t2, c->d_nm, c->d_nmoff, c->d_L, c->d_kmL, c->d_kmS, c->d_hasN}; }
+GenomeTab gtab(const lzani_ctx* c)
+{
+    const GenomeTables& t = c->gs.tab;
+    return GenomeTab{t.t2, t.nm, t.nmoff, t.L, t.kmL, t.kmS, t.hasN};
+}
 
 // Join form: the k-mer list of every genome as a query, sorted by (genome, bucket) -- k_join_keys + the radix sort of lzani_sort.hip,
 // once per run, behind k_kmers (it is part of the path's work like the k-mer words it is made from).
@@ -446,76 +417,72 @@ GenomeTab gtab(const lzani_ctx* c) { return GenomeTab{c->d_t2, c->d_nm, c->d_nmo
 // sized so that those see what is really left
 int alloc_join_lists(lzani_ctx* c)
 {
-    const u32 n = c->n;
-    if (c->d_jkeys) return LZANI_OK;                 // (set last: a partial allocation is released below and redone)
-    c->jkoff.assign((size_t)n + 1, 0);
-    for (u32 g = 0; g < n; ++g) c->jkoff[g + 1] = c->jkoff[g] + (u64)c->L[g];
-    hipError_t e = hipMalloc(&c->d_jkoff, ((size_t)n + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&c->d_jsoff, ((size_t)n + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&c->d_jcnt, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc(&c->d_jkeys, std::max<u64>(c->jkoff[n], 1) * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_jkoff, c->jkoff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-        free_join_lists(c);
-        return fail(c, e == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE, std::string("join lists: ") + hipGetErrorString(e));
-    }
+    const u32 n = c->gs.n;
+    if (c->gs.jl.keys) return LZANI_OK;
+    JoinLists jl;                                        // (moved into the set whole, or not at all)
+    jl.h_koff.assign((size_t)n + 1, 0);
+    for (u32 g = 0; g < n; ++g) jl.h_koff[g + 1] = jl.h_koff[g] + (u64)c->gs.L[g];
+    HIPCHK(c, jl.koff.alloc((size_t)n + 1));
+    HIPCHK(c, jl.soff.alloc((size_t)n + 1));
+    HIPCHK(c, jl.cnt.alloc(n));
+    HIPCHK(c, jl.keys.alloc(jl.h_koff[n]));
+    HIPCHK(c, hipMemcpyAsync(jl.koff, jl.h_koff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    c->gs.jl = std::move(jl);
     return LZANI_OK;
 }
 
 int build_join_lists(lzani_ctx* c)
 {
-    const u32 n = c->n;
+    const u32 n = c->gs.n;
     int rc0 = alloc_join_lists(c);
     if (rc0) return rc0;
     // the unsorted keys live for the duration of the sort only (as much again as the lists themselves)
-    DevBuf<unsigned long long> keys_in;
-    HIPCHK(c, keys_in.alloc(std::max<u64>(c->jkoff[n], 1)));
-    c->d_jkeys_in = keys_in.p;
+    DevMem<unsigned long long> keys_in;
+    HIPCHK(c, keys_in.alloc(c->gs.jl.h_koff[n]));
     int Lmax = 0;
-    for (u32 g = 0; g < n; ++g) Lmax = std::max(Lmax, c->L[g]);
+    for (u32 g = 0; g < n; ++g) Lmax = std::max(Lmax, c->gs.L[g]);
     // An invalid key is all ones; the sort looks at the bits [posbits, shift_g + gbits) only, so no real genome number may
     // be all ones in gbits bits, or its keys with the all-ones hash would be indistinguishable from the invalid keys of
     // the genomes before it (found by the fuzz at n = 4: genome 3 lost the k-mers of its last bucket)
-    const int shift_g = c->geo.kb + c->geo.posbits, gbits = ceil_log2((u64)n + 1);
-    HIPCHK(c, hipMemsetAsync(c->d_jcnt, 0, (size_t)n * 4, c->stream));
+    const int shift_g = c->gs.geo.kb + c->gs.geo.posbits, gbits = ceil_log2((u64)n + 1);
+    HIPCHK(c, hipMemsetAsync(c->gs.jl.cnt, 0, (size_t)n * 4, c->stream));
     for (u32 g0 = 0; g0 < n && Lmax > 0; g0 += 32768) {
         const u32 cnt = std::min<u32>(32768, n - g0);
         GenomeTab G = gtab(c);
         G.nmoff += g0; G.L += g0;
         // (the genome number of the key is global: the kernel adds g0 through the offset tables it is given)
-        hipLaunchKernelGGL(k_join_keys, dim3((Lmax + 4095) / 4096, cnt), dim3(256), 0, c->stream, G, c->d_jkoff + g0, c->d_jkeys_in,
-                           c->d_jcnt + g0, shift_g, c->geo.posbits, Lmax, g0);
+        hipLaunchKernelGGL(k_join_keys, dim3((Lmax + 4095) / 4096, cnt), dim3(256), 0, c->stream, G, c->gs.jl.koff + g0, keys_in,
+                           c->gs.jl.cnt + g0, shift_g, c->gs.geo.posbits, Lmax, g0);
     }
     HIPCHK(c, hipGetLastError());
     std::vector<u32> valid(n);
-    HIPCHK(c, hipMemcpyAsync(valid.data(), c->d_jcnt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(valid.data(), c->gs.jl.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // sort in groups of whole genomes below 2^30 keys; invalid keys (all ones) end up behind the group's valid ones
     std::vector<u64> soff((size_t)n + 1, 0);
     for (u32 g0 = 0; g0 < n;) {
         u32 g1 = g0;
         u64 keys = 0;
-        while (g1 < n && (g1 == g0 || keys + (u64)c->L[g1] <= (1ull << 30))) keys += (u64)c->L[g1++];
+        while (g1 < n && (g1 == g0 || keys + (u64)c->gs.L[g1] <= (1ull << 30))) keys += (u64)c->gs.L[g1++];
         if (keys > 0x7FFFFFF0ull) return fail(c, LZANI_ERR_ARG, "join lists: a genome of more than 2^31 positions");
-        u64 at = c->jkoff[g0];
+        u64 at = c->gs.jl.h_koff[g0];
         for (u32 g = g0; g < g1; ++g) { soff[g] = at; at += valid[g]; }
         if (g1 == n) soff[n] = at;
         if (keys) {
             size_t need = 0;
-            int e = lzani_sort_keys(c->d_jkeys_in + c->jkoff[g0], c->d_jkeys + c->jkoff[g0], keys, c->geo.posbits, shift_g + gbits, nullptr, &need, c->stream);
+            int e = lzani_sort_keys(keys_in + c->gs.jl.h_koff[g0], c->gs.jl.keys + c->gs.jl.h_koff[g0], keys, c->gs.geo.posbits, shift_g + gbits, nullptr, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "join lists: radix sort (size query) failed");
             { int rc = grow_jtmp(c, need, false); if (rc) return rc; }
-            need = c->jtmp_bytes;
-            e = lzani_sort_keys(c->d_jkeys_in + c->jkoff[g0], c->d_jkeys + c->jkoff[g0], keys, c->geo.posbits, shift_g + gbits, c->d_jtmp, &need, c->stream);
+            need = c->gs.d_jtmp.capacity();
+            e = lzani_sort_keys(keys_in + c->gs.jl.h_koff[g0], c->gs.jl.keys + c->gs.jl.h_koff[g0], keys, c->gs.geo.posbits, shift_g + gbits, c->gs.d_jtmp, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "join lists: radix sort failed");
         }
         g0 = g1;
     }
     // (a genome's list ends after its valid keys -- d_jcnt -- not where the next list begins: between two groups sit the
     // invalid keys of the first)
-    HIPCHK(c, hipMemcpyAsync(c->d_jsoff, soff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));        // (also: keys_in is released below)
-    c->d_jkeys_in = nullptr;
+    HIPCHK(c, hipMemcpyAsync(c->gs.jl.soff, soff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));        // (before keys_in is released)
     c->run.tm.index_launches += 2;
     return LZANI_OK;
 }
@@ -526,19 +493,19 @@ int build_join_lists(lzani_ctx* c)
 // only).  Timed on their own (lzani_timing.kmers_ms).
 int ensure_kmers(lzani_ctx* c)
 {
-    if (!c->d_kmL || c->kmers_ready) return LZANI_OK;
+    if (!c->gs.tab.kmL || c->gs.kmers_ready) return LZANI_OK;
     HIPCHK(c, hipEventRecord(c->ev_km[0], c->stream));
-    for (u32 g0 = 0; g0 < c->n; g0 += 32768) {
-        u32 cnt = std::min<u32>(32768, c->n - g0);
+    for (u32 g0 = 0; g0 < c->gs.n; g0 += 32768) {
+        u32 cnt = std::min<u32>(32768, c->gs.n - g0);
         GenomeTab G = gtab(c);
         G.nmoff += g0; G.L += g0;
-        hipLaunchKernelGGL(k_kmers, dim3((c->Tmax + 255) / 256, cnt), dim3(256), 0, c->stream,
-                           G, c->d_kmL, c->d_kmS, c->P.mal, c->P.msl, c->P.mrd, c->Tmax);
+        hipLaunchKernelGGL(k_kmers, dim3((c->gs.Tmax + 255) / 256, cnt), dim3(256), 0, c->stream,
+                           G, c->gs.tab.kmL, c->gs.tab.kmS, c->P.mal, c->P.msl, c->P.mrd, c->gs.Tmax);
     }
     HIPCHK(c, hipGetLastError());
     c->run.tm.index_launches += 1;
     HIPCHK(c, hipEventRecord(c->ev_km[1], c->stream));
-    c->kmers_ready = true;
+    c->gs.kmers_ready = true;
     c->km_timed = true;
     return LZANI_OK;
 }
@@ -548,7 +515,7 @@ int ensure_kmers(lzani_ctx* c)
 // from; their time is part of that run's kmers_ms.
 int ensure_join(lzani_ctx* c)
 {
-    if (!c->join_mode || c->join_ready) return LZANI_OK;
+    if (!c->gs.join_mode || c->gs.jl.ready) return LZANI_OK;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(c, hipEventCreate(&e0));
     hipError_t e = hipEventCreate(&e1);
@@ -558,7 +525,7 @@ int ensure_join(lzani_ctx* c)
         float ms = 0;
         if (hipEventRecord(e1, c->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
             c->join_ms_pending = ms;
-        c->join_ready = true;
+        c->gs.jl.ready = true;
     }
     hipEventDestroy(e0);
     if (e1) hipEventDestroy(e1);
@@ -594,47 +561,47 @@ int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, 
     IdxArgs ia;
     ia.G = gtab(c);
     ia.ref_ids = d_ref_ids;
-    ia.dirz = c->d_dirz; ia.ent = c->d_ent;
-    ia.dir_stride = c->dir_stride; ia.ent_stride = c->ent_stride;
-    ia.mal = c->P.mal; ia.mrd = c->P.mrd; ia.geo = c->geo; ia.todo = nullptr;
-    const u32 nb = 1u << c->geo.dirbits;
+    ia.dirz = c->sl.d_dirz; ia.ent = c->sl.d_ent;
+    ia.dir_stride = c->gs.dir_stride; ia.ent_stride = c->gs.ent_stride;
+    ia.mal = c->P.mal; ia.mrd = c->P.mrd; ia.geo = c->gs.geo; ia.todo = nullptr;
+    const u32 nb = 1u << c->gs.geo.dirbits;
     { int rc = ensure_kmers(c); if (rc) return rc; }
-    if (c->fl_stride && with_filter) {              // (only the block kernel reads it)
-        HIPCHK(c, hipMemsetAsync(c->d_fl, 0, (size_t)rows * c->fl_stride * 4, c->stream));
-        hipLaunchKernelGGL(k_idx_filter, dim3((u32)std::min<u64>(((u64)c->Tmax + 255) / 256, 64), rows), dim3(256), 0, c->stream,
-                           ia, c->d_fl, c->fl_stride, c->fmask, c->Tmax);
+    if (c->gs.fl_stride && with_filter) {              // (only the block kernel reads it)
+        HIPCHK(c, hipMemsetAsync(c->sl.d_fl, 0, (size_t)rows * c->gs.fl_stride * 4, c->stream));
+        hipLaunchKernelGGL(k_idx_filter, dim3((u32)std::min<u64>(((u64)c->gs.Tmax + 255) / 256, 64), rows), dim3(256), 0, c->stream,
+                           ia, c->sl.d_fl, c->gs.fl_stride, c->gs.fmask, c->gs.Tmax);
         c->run.tm.index_launches += 1;
     }
-    if (c->sort_build) {
-        c->index_build = LZANI_INDEX_BUILD_SORT;
+    if (c->gs.sort_build) {
+        c->sl.index_build = LZANI_INDEX_BUILD_SORT;
         // keys -> radix sort, every slot a segment of its own (lzani_sort.hip) -> the tables in one streaming pass.  A key is
         // hash || position; a position without a k-mer is all ones and sorts behind the slot's keys by the one bit above the hash.
-        const int shift_slot = c->geo.kb + c->geo.posbits;
-        const u64 Tm = (u64)c->Tmax;
+        const int shift_slot = c->gs.geo.kb + c->gs.geo.posbits;
+        const u64 Tm = (u64)c->gs.Tmax;
         const u32 group = 1;
-        HIPCHK(c, hipMemsetAsync(c->d_icnt, 0, (size_t)rows * 4, c->stream));
-        hipLaunchKernelGGL(k_idx_keys, dim3((u32)((Tm + 4095) / 4096), rows), dim3(256), 0, c->stream, ia, c->d_ikeys_in, c->d_icnt, c->Tmax, shift_slot);
+        HIPCHK(c, hipMemsetAsync(c->sl.d_icnt, 0, (size_t)rows * 4, c->stream));
+        hipLaunchKernelGGL(k_idx_keys, dim3((u32)((Tm + 4095) / 4096), rows), dim3(256), 0, c->stream, ia, c->sl.d_ikeys_in, c->sl.d_icnt, c->gs.Tmax, shift_slot);
         {
             size_t need = 0;
-            int e = lzani_sort_segments(c->d_ikeys_in, c->d_ikeys, Tm, rows, c->geo.posbits, shift_slot + 1, nullptr, &need, c->stream);
+            int e = lzani_sort_segments(c->sl.d_ikeys_in, c->sl.d_ikeys, Tm, rows, c->gs.geo.posbits, shift_slot + 1, nullptr, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "index build: radix sort (size query) failed");
             { int rc = grow_jtmp(c, need, true); if (rc) return rc; }
-            need = c->jtmp_bytes;
-            e = lzani_sort_segments(c->d_ikeys_in, c->d_ikeys, Tm, rows, c->geo.posbits, shift_slot + 1, c->d_jtmp, &need, c->stream);
+            need = c->gs.d_jtmp.capacity();
+            e = lzani_sort_segments(c->sl.d_ikeys_in, c->sl.d_ikeys, Tm, rows, c->gs.geo.posbits, shift_slot + 1, c->gs.d_jtmp, &need, c->stream);
             if (e != 0) return fail(c, LZANI_ERR_DEVICE, "index build: radix sort failed");
         }
-        hipLaunchKernelGGL(k_idx_base, dim3((rows + 255) / 256), dim3(256), 0, c->stream, c->d_icnt, c->d_ibase, rows, group, Tm);
+        hipLaunchKernelGGL(k_idx_base, dim3((rows + 255) / 256), dim3(256), 0, c->stream, c->sl.d_icnt, c->sl.d_ibase, rows, group, Tm);
         hipLaunchKernelGGL(k_idx_from_sorted, dim3((u32)std::min<u64>((Tm + 255) / 256, 8192), rows), dim3(256), 0, c->stream,
-                           ia, c->d_ikeys, c->d_icnt, c->d_ibase, c->d_bk, with_tw ? c->d_tw : nullptr, c->bk_stride, c->tw_stride);
+                           ia, c->sl.d_ikeys, c->sl.d_icnt, c->sl.d_ibase, c->sl.d_bk, with_tw ? c->sl.d_tw : nullptr, c->gs.bk_stride, c->gs.tw_stride);
         HIPCHK(c, hipGetLastError());
         c->run.tm.index_launches += 4;
         return LZANI_OK;
     }
-    const bool lds_build = c->d_kmL && c->geo.dirbits <= k.lds_index_max_dirbits && k.lds_index;
-    c->index_build = lds_build ? LZANI_INDEX_BUILD_LDS : LZANI_INDEX_BUILD_ATOMICS;
+    const bool lds_build = c->gs.tab.kmL && c->gs.geo.dirbits <= k.lds_index_max_dirbits && k.lds_index;
+    c->sl.index_build = lds_build ? LZANI_INDEX_BUILD_LDS : LZANI_INDEX_BUILD_ATOMICS;
     // blocks per slot of the global-atomics kernels: the whole range when they build every slot, a handful when
     // they only pick up what k_idx_build left (usually nothing)
-    const u32 gx_pos = lds_build ? 16u : (u32)((c->Tmax + 255) / 256), gx_bkt = lds_build ? 16u : (nb + 255) / 256;
+    const u32 gx_pos = lds_build ? 16u : (u32)((c->gs.Tmax + 255) / 256), gx_bkt = lds_build ? 16u : (nb + 255) / 256;
     dim3 gp(gx_pos, rows);
     if (lds_build) {
         // one block per reference, everything through LDS; a slot that does not fit (status != 0) falls through
@@ -644,20 +611,20 @@ int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, 
             HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_idx_build), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             c->build_attr_set = true;
         }
-        HIPCHK(c, hipMemsetAsync(c->d_status, 0, (size_t)rows * 4, c->stream));
-        hipLaunchKernelGGL(k_idx_build, dim3(rows), dim3(1024), lds, c->stream, ia, c->d_bk, c->d_tw, c->bk_stride, c->tw_stride, c->d_status);
-        ia.todo = c->d_status;
-        hipLaunchKernelGGL(k_idx_zero, dim3(gx_bkt, rows), dim3(256), 0, c->stream, c->d_dirz, c->dir_stride, nb, ia.todo);
-    } else HIPCHK(c, hipMemsetAsync(c->d_dirz, 0, (size_t)rows * c->dir_stride * 4, c->stream));
-    hipLaunchKernelGGL(k_idx_count, gp, dim3(256), 0, c->stream, ia, c->Tmax);
-    hipLaunchKernelGGL(k_idx_scan, dim3(rows), dim3(1024), 0, c->stream, c->d_dirz, c->dir_stride, nb, ia.todo);
-    hipLaunchKernelGGL(k_idx_fill, gp, dim3(256), 0, c->stream, ia, c->Tmax);
+        HIPCHK(c, hipMemsetAsync(c->sl.d_status, 0, (size_t)rows * 4, c->stream));
+        hipLaunchKernelGGL(k_idx_build, dim3(rows), dim3(1024), lds, c->stream, ia, c->sl.d_bk, c->sl.d_tw, c->gs.bk_stride, c->gs.tw_stride, c->sl.d_status);
+        ia.todo = c->sl.d_status;
+        hipLaunchKernelGGL(k_idx_zero, dim3(gx_bkt, rows), dim3(256), 0, c->stream, c->sl.d_dirz, c->gs.dir_stride, nb, ia.todo);
+    } else HIPCHK(c, hipMemsetAsync(c->sl.d_dirz, 0, (size_t)rows * c->gs.dir_stride * 4, c->stream));
+    hipLaunchKernelGGL(k_idx_count, gp, dim3(256), 0, c->stream, ia, c->gs.Tmax);
+    hipLaunchKernelGGL(k_idx_scan, dim3(rows), dim3(1024), 0, c->stream, c->sl.d_dirz, c->gs.dir_stride, nb, ia.todo);
+    hipLaunchKernelGGL(k_idx_fill, gp, dim3(256), 0, c->stream, ia, c->gs.Tmax);
     hipLaunchKernelGGL(k_idx_sort, dim3(gx_bkt, rows), dim3(256), 0, c->stream,
-                       c->d_dirz, c->d_ent, c->dir_stride, c->ent_stride, nb, ia.todo, 0);
-    if (c->d_bk)
+                       c->sl.d_dirz, c->sl.d_ent, c->gs.dir_stride, c->gs.ent_stride, nb, ia.todo, 0);
+    if (c->sl.d_bk)
         hipLaunchKernelGGL(k_idx_buckets, dim3(gx_bkt, rows), dim3(256), 0, c->stream,
-                           c->d_dirz, c->d_ent, c->d_bk, c->d_tw, c->dir_stride, c->ent_stride, c->bk_stride, c->tw_stride,
-                           nb, c->geo.posbits, ia.todo);
+                           c->sl.d_dirz, c->sl.d_ent, c->sl.d_bk, c->sl.d_tw, c->gs.dir_stride, c->gs.ent_stride, c->gs.bk_stride, c->gs.tw_stride,
+                           nb, c->gs.geo.posbits, ia.todo);
     HIPCHK(c, hipGetLastError());
     c->run.tm.index_launches += 4;
     return LZANI_OK;
@@ -711,19 +678,19 @@ struct RowFacts { u64 n_pairs = 0; bool lists_dup = false; u64 lists_involved = 
 int check_rows(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids, RowFacts& f)
 {
     for (u32 k = 0; k < n_rows; ++k) {
-        if (ref_ids[k] >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: reference id out of range");
+        if (ref_ids[k] >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: reference id out of range");
         if (row_off[k + 1] < row_off[k]) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off not monotone");
-        if (!query_ids && row_off[k + 1] - row_off[k] != (u64)c->n - 1)
+        if (!query_ids && row_off[k + 1] - row_off[k] != (u64)c->gs.n - 1)
             return fail(c, LZANI_ERR_ARG, "lzani_run_rows: dense row must have n-1 queries");
     }
     if (row_off[0] != 0) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off[0] must be 0");
     f.n_pairs = row_off[n_rows];
     if (query_ids) {
-        std::vector<u32> in_row(c->n, 0xFFFFFFFFu), in_group(c->n, 0xFFFFFFFFu);
+        std::vector<u32> in_row(c->gs.n, 0xFFFFFFFFu), in_group(c->gs.n, 0xFFFFFFFFu);
         for (u32 k = 0; k < n_rows; ++k)
             for (u64 e = row_off[k]; e < row_off[k + 1]; ++e) {
                 const u32 q = query_ids[e];
-                if (q >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: query id out of range");
+                if (q >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: query id out of range");
                 f.lists_dup |= in_row[q] == k;
                 in_row[q] = k;
                 if (in_group[q] != k / PM_GROUP) { in_group[q] = k / PM_GROUP; ++f.lists_involved; }
@@ -743,17 +710,6 @@ struct RunPlan {
     u64 cb_words = 0;             // 32-bit words of one pair's candidate bitmap
     std::vector<u32> bstart;      // batch b: rows [bstart[b], bstart[b + 1])
 };
-
-// A buffer of the context grown to `bytes` (never shrunk); false, the buffer released, where it cannot be had.
-template <class T>
-bool grow(T*& p, size_t& have, size_t bytes)
-{
-    if (have >= bytes) return true;
-    hipFree(p); p = nullptr; have = 0;
-    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    have = bytes;
-    return true;
-}
 
 // Batches of consecutive rows: at most rows_cap rows and cap_pairs pairs each.  Returns the most pairs of a batch.
 u64 cut_batches(u32 n_rows, const u64* row_off, u32 rows_cap, u64 cap_pairs, std::vector<u32>& bstart)
@@ -775,7 +731,7 @@ u64 cut_batches(u32 n_rows, const u64* row_off, u32 rows_cap, u64 cap_pairs, std
 // (long genomes), where the rows qualify; a batch is then also bounded by what the candidate bitmaps of its pairs take,
 // and the index slabs are sized for such a batch.  p.pm stays clear where the rows do not qualify or do not fit (a genome
 // set this large: the probe / join form, batch by batch), and where a buffer (matrix, pair table, bitmaps) cannot be had
-// after all -- the sizing is an estimate, and hipMalloc may fail on a fragmented heap: the bitmap buffers are then
+// after all -- the sizing is an estimate, and an allocation may fail on a fragmented heap: the bitmap buffers are then
 // released (the probe / join form needs none of them).
 int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
 {
@@ -784,17 +740,17 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
     // Below, the matrix -- 16 GB to clear at 30 key bits -- costs more than it saves.)
     // Long genomes (the join is the alternative: 210 ms for the 56 pairs of 8 x 5 Mbp against 149 by bitmaps, 92 with the
     // pairs cut into segments): from two rows on.
-    const u32 min_rows = k.pm_min_rows ? (u32)std::max(1, *k.pm_min_rows) : c->join_mode ? 2u : c->tw_stride ? 32u : 8u;
+    const u32 min_rows = k.pm_min_rows ? (u32)std::max(1, *k.pm_min_rows) : c->gs.join_mode ? 2u : c->gs.tw_stride ? 32u : 8u;
     // Query lists qualify when they are dense where they are: a query that occurs in a group of rows should meet a
     // good part of it (one matrix row read serves all its pairs of the group) -- the row x column blocks of a tiled
     // all2all do, the few relatives a kmer-db filter leaves per row do not.  No query twice in a row (one bitmap each).
     // (Measured in round 4 on the related workload, families of 50 in length order -- 16 pairs per query and group:
     // the pair kernel gains 18 % from the bitmaps, the candidate stage costs more than that; against the ROUNDS of the
     // first kernel -- no tag words: long k-mers on mid-size genomes -- the bitmaps win from two pairs per query on.)
-    const u64 min_share = k.pm_min_share.value_or(c->tw_stride ? 48 : 2);
+    const u64 min_share = k.pm_min_share.value_or(c->gs.tw_stride ? 48 : 2);
     const bool lists_ok = !lists || (!f.lists_dup && f.n_pairs >= min_share * f.lists_involved);
-    if (!(!regions && lists_ok && c->d_kmL && c->bk_stride && c->P.mqd + c->P.mrd <= 128 && c->geo.kb <= 30 &&
-          c->n >= 2 && n_rows >= min_rows && k.pm))
+    if (!(!regions && lists_ok && c->gs.tab.kmL && c->gs.bk_stride && c->P.mqd + c->P.mrd <= 128 && c->gs.geo.kb <= 30 &&
+          c->gs.n >= 2 && n_rows >= min_rows && k.pm))
         return LZANI_OK;
     u64 max_row = 0;
     for (u32 r = 0; r < n_rows; ++r) max_row = std::max<u64>(max_row, row_off[r + 1] - row_off[r]);
@@ -802,43 +758,43 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
     p.cb_words = (u64)p.pm_tiles * PM_TILE_WORDS;
     p.pm_group = p.pm_bits <= 27 ? (u32)PM_GROUP : 128u;                    // 64-byte rows up to 2^27 of them (8 GB), 16-byte rows beyond (16 GB at 2^30)
     const size_t m_bytes = ((size_t)1 << p.pm_bits) * (p.pm_group / 8);
-    const size_t x_bytes = lists ? ((size_t)c->n * p.pm_group + 2 * (size_t)c->n + 64) * 4 : 0;   // pair table, query flags, list, count
+    const size_t x_bytes = lists ? ((size_t)c->gs.n * p.pm_group + 2 * (size_t)c->gs.n + 64) * 4 : 0;   // pair table, query flags, list, count
     const size_t per_pair = (size_t)p.cb_words * 4;
     const double avg_row = (double)f.n_pairs / n_rows;
-    const size_t per_slot = (size_t)4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride) + (c->sort_build ? (size_t)16 * c->Tmax + 16 : 0);
+    const size_t per_slot = (size_t)4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride) + (c->gs.sort_build ? (size_t)16 * c->gs.Tmax + 16 : 0);
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
     // what this run may lay out anew: the free memory and what the context holds from earlier runs -- ITS slabs
     // included, which is why slabs larger than this run wants are released below (ensure_slabs never shrinks them:
     // an earlier run with sparse rows may have grown them to 60 % of the memory)
-    const size_t pool = free_b + (size_t)c->slots * per_slot + c->pm_cbits_bytes + c->pm_bytes + c->pm_pidx_bytes;
+    const size_t pool = free_b + (size_t)c->sl.slots * per_slot + c->cs.d_pm_cbits.bytes() + c->cs.d_pm.bytes() + c->cs.d_pm_pidx.bytes();
     const size_t cap = k.pm_max_bytes.value_or(std::min((size_t)64 << 30, total_b / 4));
     const double room = pool * 0.85 - (double)m_bytes - (double)x_bytes;
     u64 fit = room > 0 ? (u64)(room / ((double)per_slot + avg_row * (double)per_pair)) : 0;     // rows: a slab + its pairs' bitmaps each
-    fit = std::min<u64>(fit, std::min<u32>(n_rows, c->max_slots));
+    fit = std::min<u64>(fit, std::min<u32>(n_rows, c->gs.max_slots));
     u64 cap_pairs = std::min<u64>((u64)(cap / per_pair), 0xFFFFFFF0ull);                           // pair indexes of a batch are 32 bits
     cap_pairs = std::min<u64>(cap_pairs, (u64)((double)fit * avg_row) + max_row);
     if (fit < std::min<u32>(8, n_rows) || cap_pairs < max_row) return LZANI_OK;
-    if (c->slots > fit) free_slabs(c);                                     // (counted as available above)
-    if (!grow(c->d_pm, c->pm_bytes, m_bytes) || !grow(c->d_pm_pidx, c->pm_pidx_bytes, x_bytes)) {
+    if (c->sl.slots > fit) c->sl = IndexSlabs{};                                     // (counted as available above)
+    if (!got(c->cs.d_pm.reserve(m_bytes / 4)) || !got(c->cs.d_pm_pidx.reserve(x_bytes / 4))) {
         TRACE("candidate bitmaps: no memory for the matrix / pair table, falling back");
-        free_pm(c);
+        c->cs = CandScratch{};
         return LZANI_OK;
     }
     const int rc = ensure_slabs(c, (u32)fit);
-    if (rc == LZANI_ERR_NOMEM) { free_pm(c); return LZANI_OK; }
+    if (rc == LZANI_ERR_NOMEM) { c->cs = CandScratch{}; return LZANI_OK; }
     if (rc) return rc;
-    u32 rows_cap = c->slots;
+    u32 rows_cap = c->sl.slots;
     if (!lists) {                                            // dense rows: whole groups of references, if there are several batches
-        u64 r = std::min<u64>(rows_cap, cap_pairs / (u64)(c->n - 1));
+        u64 r = std::min<u64>(rows_cap, cap_pairs / (u64)(c->gs.n - 1));
         if (r < n_rows && r > p.pm_group) r -= r % p.pm_group;
         rows_cap = (u32)std::max<u64>(r, 1);
     }
     size_t need = (size_t)cut_batches(n_rows, row_off, rows_cap, cap_pairs, p.bstart) * p.cb_words * 4;
     if (k.pm_fail_cbits) need = (size_t)1 << 60;                          // tests: the fallback
-    if (!grow(c->d_pm_cbits, c->pm_cbits_bytes, need)) {
+    if (!got(c->cs.d_pm_cbits.reserve(need / 4))) {
         TRACE("candidate bitmaps: no memory for %zu bytes of bitmaps, falling back", need);
-        free_pm(c);
+        c->cs = CandScratch{};
         return LZANI_OK;
     }
     p.pm = true;
@@ -849,18 +805,18 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
 // batches of as many consecutive rows as there are index slabs (and, with bitmaps, as their pairs' bitmaps may take).
 int plan_run(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
 {
-    for (u32 g = 0; g < c->n; ++g) p.Lmax = std::max(p.Lmax, c->L[g]);
+    for (u32 g = 0; g < c->gs.n; ++g) p.Lmax = std::max(p.Lmax, c->gs.L[g]);
     // rows of the presence matrix: one per k-mer (exact: the mixer is a bijection on the key bits) where the genomes fill a fair
     // part of the key space, else the hash's top bits -- 2^9 rows per text position keep the false candidates below 0.2 % of the
     // query positions, and a group's matrix is cleared and built in proportion to the genomes, not to 4^mal
-    p.pm_bits = std::min(std::min(c->geo.kb, 30), ceil_log2((u64)std::max(c->Tmax, 1)) + 9);
+    p.pm_bits = std::min(std::min(c->gs.geo.kb, 30), ceil_log2((u64)std::max(c->gs.Tmax, 1)) + 9);
     int rc = plan_bitmaps(c, k, f, n_rows, row_off, lists, regions, p);
     if (rc || p.pm) return rc;
-    p.use_join = c->join_mode;
+    p.use_join = c->gs.join_mode;
     if (p.use_join) { rc = ensure_join(c); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
     rc = ensure_slabs(c, n_rows);
     if (rc) return rc;
-    cut_batches(n_rows, row_off, c->slots, ~0ull, p.bstart);
+    cut_batches(n_rows, row_off, c->sl.slots, ~0ull, p.bstart);
     return LZANI_OK;
 }
 
@@ -947,17 +903,14 @@ int choose_split_lpt(RunCtx& r, Batch& bt)
     }
     // (queries from ~256 kbp on; the split wants the candidate counts: which pairs to cut, which first)
     bt.lpt = (bp >= 2 && bp <= slots * 32 && r.k.lpt.value_or(cb_words >= 8192)) || bt.split_S >= 2;
-    if (bt.lpt && c->lpt_pairs < bp) {
-        hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
-        c->d_lpt_cnt = nullptr; c->d_lpt_keys = nullptr; c->lpt_pairs = 0;
-        if (hipMalloc(&c->d_lpt_cnt, (size_t)bp * 4) != hipSuccess || hipMalloc(&c->d_lpt_keys, (size_t)bp * 16) != hipSuccess) {
-            (void)hipGetLastError();
-            hipFree(c->d_lpt_cnt); hipFree(c->d_lpt_keys);
-            c->d_lpt_cnt = nullptr; c->d_lpt_keys = nullptr;
+    if (bt.lpt && c->cs.d_lpt_cnt.capacity() < bp) {
+        c->cs.d_lpt_cnt.reset(); c->cs.d_lpt_keys.reset();    // (both released before either is made anew)
+        if (!got(c->cs.d_lpt_cnt.alloc(bp)) || !got(c->cs.d_lpt_keys.alloc(2 * bp))) {
+            c->cs.d_lpt_cnt.reset(); c->cs.d_lpt_keys.reset();
             bt.lpt = false;                                   // (placement only: the run goes on without it)
-        } else c->lpt_pairs = (size_t)bp;
+        }
     }
-    if (bt.lpt) HIPCHK(c, hipMemsetAsync(c->d_lpt_cnt, 0, (size_t)bp * 4, c->stream));
+    if (bt.lpt) HIPCHK(c, hipMemsetAsync(c->cs.d_lpt_cnt, 0, (size_t)bp * 4, c->stream));
     return LZANI_OK;
 }
 
@@ -972,24 +925,24 @@ int candidate_stage(RunCtx& r, Batch& bt)
         pg.G = gtab(c);
         pg.ref_ids = r.d_ref + bt.k0; pg.row_off = r.d_off + bt.k0;
         pg.slot0 = g0; pg.rows = std::min<u32>(p.pm_group, bt.rows - g0);
-        pg.M = c->d_pm; pg.rw = ((pg.rows + 127) / 128) * 4; pg.mmask = (u32)lowmask(pm_bits); pg.rshift = c->geo.kb - pm_bits;
+        pg.M = c->cs.d_pm; pg.rw = ((pg.rows + 127) / 128) * 4; pg.mmask = (u32)lowmask(pm_bits); pg.rshift = c->gs.geo.kb - pm_bits;
         pg.mal = c->P.mal; pg.mrd = c->P.mrd;
-        pg.cbits = c->d_pm_cbits; pg.cb_words = p.cb_words; pg.e0 = bt.e0; pg.n = c->n; pg.q0 = 0;
+        pg.cbits = c->cs.d_pm_cbits; pg.cb_words = p.cb_words; pg.e0 = bt.e0; pg.n = c->gs.n; pg.q0 = 0;
         pg.query_ids = r.d_q; pg.pidx = nullptr; pg.qflag = pg.qlist = pg.qcount = nullptr;
-        pg.pcount = bt.lpt ? c->d_lpt_cnt : nullptr;
+        pg.pcount = bt.lpt ? c->cs.d_lpt_cnt : nullptr;
         if (r.query_ids) {                                   // the lists of the group's rows -> pair table + the queries involved
-            const size_t tab = (size_t)c->n * 32 * pg.rw;
-            pg.pidx = c->d_pm_pidx; pg.qflag = c->d_pm_pidx + (size_t)c->n * p.pm_group; pg.qlist = pg.qflag + c->n; pg.qcount = pg.qlist + c->n;
+            const size_t tab = (size_t)c->gs.n * 32 * pg.rw;
+            pg.pidx = c->cs.d_pm_pidx; pg.qflag = c->cs.d_pm_pidx + (size_t)c->gs.n * p.pm_group; pg.qlist = pg.qflag + c->gs.n; pg.qcount = pg.qlist + c->gs.n;
             HIPCHK(c, hipMemsetAsync(pg.pidx, 0xFF, tab * 4, c->stream));
-            HIPCHK(c, hipMemsetAsync(pg.qflag, 0, ((size_t)2 * c->n + 1) * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(pg.qflag, 0, ((size_t)2 * c->gs.n + 1) * 4, c->stream));
             hipLaunchKernelGGL(k_pm_pairs, dim3(pg.rows), dim3(256), 0, c->stream, pg);
         }
         // the matrix: from the group's indexes, chunk by chunk through LDS (long genomes: no global atomics, no clearing),
         // or by one atomicOr per text position into the cleared matrix
-        const int tbits = c->geo.kb - c->geo.dirbits;
+        const int tbits = c->gs.geo.kb - c->gs.geo.dirbits;
         // (chunks of 64 KB: two blocks = 32 waves a CU; with 128 KB chunks, one block a CU, the matrix of 128 x 5 Mbp took 3 ms more)
         const int rcl = std::min(pm_bits, pg.rw <= 4 ? 12 : pg.rw <= 8 ? 11 : 10);
-        const bool from_index = c->geo.tagmask == (u32)lowmask(tbits) && pm_bits == c->geo.kb && rcl >= tbits &&
+        const bool from_index = c->gs.geo.tagmask == (u32)lowmask(tbits) && pm_bits == c->gs.geo.kb && rcl >= tbits &&
                                 r.k.pm_from_index.value_or(pm_bits > 24);
         if (from_index) {
             c->run.pmfi_launches += 1;
@@ -1000,7 +953,7 @@ int candidate_stage(RunCtx& r, Batch& bt)
                     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_from_index<RW>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
                     c->pmfi_attr_set |= 1u << RW; \
                 } \
-                hipLaunchKernelGGL(k_pm_from_index<RW>, gi, bi, fl, c->stream, pg, c->d_dirz, c->d_ent, c->dir_stride, c->ent_stride, tbits, c->geo.posbits, rcl); \
+                hipLaunchKernelGGL(k_pm_from_index<RW>, gi, bi, fl, c->stream, pg, c->sl.d_dirz, c->sl.d_ent, c->gs.dir_stride, c->gs.ent_stride, tbits, c->gs.geo.posbits, rcl); \
             } while (0)
             switch (pg.rw) {
             case 4: LZ_PM_FI(4); break;
@@ -1010,8 +963,8 @@ int candidate_stage(RunCtx& r, Batch& bt)
             }
 #undef LZ_PM_FI
         } else {
-            HIPCHK(c, hipMemsetAsync(c->d_pm, 0, ((size_t)1 << pm_bits) * pg.rw * 4, c->stream));
-            hipLaunchKernelGGL(k_pm_build, dim3((u32)std::min<u64>(((u64)c->Tmax + 255) / 256, 64), pg.rows), dim3(256), 0, c->stream, pg, c->Tmax);
+            HIPCHK(c, hipMemsetAsync(c->cs.d_pm, 0, ((size_t)1 << pm_bits) * pg.rw * 4, c->stream));
+            hipLaunchKernelGGL(k_pm_build, dim3((u32)std::min<u64>(((u64)c->gs.Tmax + 255) / 256, 64), pg.rows), dim3(256), 0, c->stream, pg, c->gs.Tmax);
         }
         const u32 rp = 32 * pg.rw;
         const size_t lds = (size_t)(PM_TILE_WORDS * (rp + 1) + rp) * 4;
@@ -1026,9 +979,9 @@ int candidate_stage(RunCtx& r, Batch& bt)
         // (query lists: one row of blocks per query that occurs in the group -- counted here, the device list is
         // k_pm_pairs' -- not per genome: 20,000 genomes x 44 tiles of blocks that find nothing to do were most of
         // the candidate stage of a filtered run)
-        u32 nq = c->n;
+        u32 nq = c->gs.n;
         if (r.query_ids) {
-            if (r.grp_seen.size() != c->n) r.grp_seen.assign(c->n, 0xFFFFFFFFu);
+            if (r.grp_seen.size() != c->gs.n) r.grp_seen.assign(c->gs.n, 0xFFFFFFFFu);
             const u32 stamp = ++r.grp_stamp;
             nq = 0;
             for (u64 e = r.row_off[bt.k0 + g0]; e < r.row_off[bt.k0 + g0 + pg.rows]; ++e)
@@ -1047,18 +1000,18 @@ int candidate_stage(RunCtx& r, Batch& bt)
         }
         c->run.tm.cand_launches += 2;
     }
-    if (!bt.lpt || c->d_lpt_cnt == nullptr) bt.split_S = 0;   // (no candidate counts after all -- their buffer could not be had: no split)
+    if (!bt.lpt || c->cs.d_lpt_cnt == nullptr) bt.split_S = 0;   // (no candidate counts after all -- their buffer could not be had: no split)
     if (bt.lpt && bt.split_S < 2) {                            // the ticket order of the batch's queues
         const u64 bp = bt.e1 - bt.e0;
         QueueBounds qbv;
         for (int x = 0; x <= NQUEUES; ++x) qbv.v[x] = bt.qb[x];
         hipLaunchKernelGGL(k_lpt_keys, dim3((u32)std::min<u64>((bp + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                           r.d_qorder + bt.k0, r.d_qcum + bt.k0 + bt.b, qbv, r.d_off + bt.k0, bt.e0, c->d_lpt_cnt, c->d_lpt_keys, bt.rows, bp);
+                           r.d_qorder + bt.k0, r.d_qcum + bt.k0 + bt.b, qbv, r.d_off + bt.k0, bt.e0, c->cs.d_lpt_cnt, c->cs.d_lpt_keys, bt.rows, bp);
         size_t need = 0;
-        int e = lzani_sort_keys(c->d_lpt_keys, c->d_lpt_keys + bp, bp, 32, 56, nullptr, &need, c->stream);
+        int e = lzani_sort_keys(c->cs.d_lpt_keys, c->cs.d_lpt_keys + bp, bp, 32, 56, nullptr, &need, c->stream);
         if (e == 0) { int rc = grow_jtmp(c, need, true); if (rc) return rc; }
-        need = c->jtmp_bytes;
-        if (e == 0) e = lzani_sort_keys(c->d_lpt_keys, c->d_lpt_keys + bp, bp, 32, 56, c->d_jtmp, &need, c->stream);
+        need = c->gs.d_jtmp.capacity();
+        if (e == 0) e = lzani_sort_keys(c->cs.d_lpt_keys, c->cs.d_lpt_keys + bp, bp, 32, 56, c->gs.d_jtmp, &need, c->stream);
         if (e != 0) return fail(c, LZANI_ERR_DEVICE, "ticket order: radix sort failed");
     }
     HIPCHK(c, hipGetLastError());
@@ -1074,29 +1027,29 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
     c->run.pm_launches += 1;
     c->run.split_launches += 1;
     const u32 npb = (u32)(bt.e1 - bt.e0), S = bt.split_S;
-    DevBuf<SplitStart> d_cuts;
-    DevBuf<SplitOut> d_souts;
-    DevBuf<u32> d_work, d_next, d_cnt;
-    DevBuf<unsigned char> d_done, d_heavy;
+    DevMem<SplitStart> d_cuts;
+    DevMem<SplitOut> d_souts;
+    DevMem<u32> d_work, d_next, d_cnt;
+    DevMem<unsigned char> d_done, d_heavy;
     HIPCHK(c, d_cuts.alloc((size_t)npb * S));
     HIPCHK(c, d_souts.alloc((size_t)npb * S));
     HIPCHK(c, d_work.alloc((size_t)npb * S));
     HIPCHK(c, d_next.alloc((size_t)npb * S));
     HIPCHK(c, d_cnt.alloc(12));
     HIPCHK(c, d_done.alloc(npb));
-    HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 48, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_done.p, 0, npb, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_cuts.p, 0xFF, (size_t)npb * S * sizeof(SplitStart), c->stream));      // (cut 0 of every pair: no checkpoint)
+    HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 48, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_done.get(), 0, npb, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_cuts.get(), 0xFF, (size_t)npb * S * sizeof(SplitStart), c->stream));      // (cut 0 of every pair: no checkpoint)
     SplitArgs sa;
     sa.pa = pa; sa.rows = bt.rows; sa.n_pairs = npb; sa.S = S; sa.seglen = bt.split_seglen;
-    sa.cuts = d_cuts.p; sa.outs = d_souts.p; sa.work = d_work.p; sa.work_next = d_next.p; sa.counters = d_cnt.p; sa.done = d_done.p;
+    sa.cuts = d_cuts.get(); sa.outs = d_souts.get(); sa.work = d_work.get(); sa.work_next = d_next.get(); sa.counters = d_cnt.get(); sa.done = d_done.get();
     sa.reg = c->P.reg; sa.last_round = 0;
     // which pairs to cut: the ones with many anchor candidates (related: a candidate at every other position; a chance
     // pair has one in a hundred and is scanned whole, by its segment 0 with the null chain at work) -- heaviest first
     u32 items = 0;
     {
         std::vector<u32> cnt(npb);
-        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_lpt_cnt, (size_t)npb * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->cs.d_lpt_cnt, (size_t)npb * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         // (every pair by default: at a wave or two per SIMD a chance pair of 5 Mbp takes nearly as long as a related one;
         // LZANI_SPLIT_ALL=0 cuts the pairs with a candidate at one position in 32 and more only)
@@ -1112,24 +1065,24 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
         for (u32 k : order) if (cnt[k] < thr) all.push_back(k * S);
         items = (u32)all.size();
         HIPCHK(c, d_heavy.alloc(npb));
-        HIPCHK(c, hipMemcpyAsync(d_heavy.p, heavy.data(), npb, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_work.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_heavy.get(), heavy.data(), npb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_work.get(), all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));            // (the vectors leave scope)
         TRACE("split: %u pairs, %u of them cut into %u segments (candidates >= %u)", npb, n_heavy, S, thr);
     }
-    sa.heavy = d_heavy.p;
+    sa.heavy = d_heavy.get();
     launch(sa, 0, npb * (S - 1));                           // the checkpoints
-    u32* cur = d_work.p; u32* nxt = d_next.p;
+    u32* cur = d_work.get(); u32* nxt = d_next.get();
     auto t_round = std::chrono::steady_clock::now();
     const int give_up = 6 + (int)S / 4;                      // (a chain of void segments costs a round each: more segments, more rounds allowed)
     for (int round = 0; round < give_up + 4 && items; ++round) {
-        HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 8, c->stream));     // tickets, next round's items (the finished pairs' count stays)
+        HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 8, c->stream));     // tickets, next round's items (the finished pairs' count stays)
         sa.work = cur; sa.work_next = nxt;
         launch(sa, 1, items);
         sa.last_round = round >= give_up;
         hipLaunchKernelGGL(k_split_stitch, dim3((npb + 255) / 256), dim3(256), 0, c->stream, sa);
         u32 cnt[12] = {0};
-        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.p, 48, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), 48, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->run.split_items += items;
         const auto t_now = std::chrono::steady_clock::now();
@@ -1148,17 +1101,17 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
 // (blk_fold -2: none does, the wave kernel takes these rows too).
 bool blk_fits(lzani_ctx* c, const void* kf)
 {
-    if (c->blk_fold == -1) {
-        for (int fold = 0; fold <= 4 && c->blk_fold < 0; ++fold) {
-            const size_t l = (size_t)(BLK_WAVES * SEED_LDS_WORDS + std::max<u64>(c->fl_stride >> fold, 1)) * 4;
+    if (c->gs.blk_fold == -1) {
+        for (int fold = 0; fold <= 4 && c->gs.blk_fold < 0; ++fold) {
+            const size_t l = (size_t)(BLK_WAVES * SEED_LDS_WORDS + std::max<u64>(c->gs.fl_stride >> fold, 1)) * 4;
             if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l) != hipSuccess) { (void)hipGetLastError(); continue; }
             int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * BLK_WAVES, l) == hipSuccess && nb >= 2) c->blk_fold = fold;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * BLK_WAVES, l) == hipSuccess && nb >= 2) c->gs.blk_fold = fold;
         }
         (void)hipGetLastError();
-        if (c->blk_fold < 0) c->blk_fold = -2;
+        if (c->gs.blk_fold < 0) c->gs.blk_fold = -2;
     }
-    return c->blk_fold >= 0;
+    return c->gs.blk_fold >= 0;
 }
 
 // The batch's pair launch: the run's form picks the kernel, (nfree, dsel) its template arguments; a tuple compiled at run
@@ -1169,27 +1122,27 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     const bool tickets = bt.lpt && bt.split_S < 2;
     PairArgs pa;
     pa.G = gtab(c);
-    pa.P = c->P; pa.geo = c->geo;
-    pa.dirz = c->d_dirz; pa.ent = c->d_ent;
-    pa.dir_stride = c->dir_stride; pa.ent_stride = c->ent_stride;
-    pa.bk = c->d_bk; pa.bk_stride = c->bk_stride;
-    pa.tw = c->d_tw; pa.tw_stride = c->tw_stride;
-    pa.fl = c->d_fl; pa.fl_stride = c->fl_stride; pa.fmask = c->fmask;
+    pa.P = c->P; pa.geo = c->gs.geo;
+    pa.dirz = c->sl.d_dirz; pa.ent = c->sl.d_ent;
+    pa.dir_stride = c->gs.dir_stride; pa.ent_stride = c->gs.ent_stride;
+    pa.bk = c->sl.d_bk; pa.bk_stride = c->gs.bk_stride;
+    pa.tw = c->sl.d_tw; pa.tw_stride = c->gs.tw_stride;
+    pa.fl = c->sl.d_fl; pa.fl_stride = c->gs.fl_stride; pa.fmask = c->gs.fmask;
     pa.ref_ids = r.d_ref + bt.k0; pa.row_off = r.d_off + bt.k0; pa.query_ids = r.d_q;
     pa.out = r.d_out; pa.cursor = c->d_cursor;
     pa.qorder = r.d_qorder + bt.k0; pa.qcum = r.d_qcum + bt.k0 + bt.b;
     for (int x = 0; x <= NQUEUES; ++x) pa.qb[x] = bt.qb[x];
-    pa.skeys = r.cbits_stride ? c->d_jkeys : nullptr; pa.soff = c->d_jsoff; pa.scnt = c->d_jcnt;
+    pa.skeys = r.cbits_stride ? c->gs.jl.keys : nullptr; pa.soff = c->gs.jl.soff; pa.scnt = c->gs.jl.cnt;
     pa.cbits = r.d_cbits; pa.cbits_stride = r.cbits_stride; pa.cb_e0 = 0;
-    if (r.p.pm) { pa.cbits = reinterpret_cast<unsigned long long*>(c->d_pm_cbits); pa.cbits_stride = r.p.cb_words / 2; pa.cb_e0 = bt.e0; }
+    if (r.p.pm) { pa.cbits = reinterpret_cast<unsigned long long*>(c->cs.d_pm_cbits.get()); pa.cbits_stride = r.p.cb_words / 2; pa.cb_e0 = bt.e0; }
     pa.reg_out = r.rs ? r.rs->d_regions : nullptr; pa.reg_count = r.rs ? r.rs->d_count : nullptr; pa.reg_cap = r.rs ? r.rs->capacity : 0;
-    pa.torder = tickets ? c->d_lpt_keys + (bt.e1 - bt.e0) : nullptr;
+    pa.torder = tickets ? c->cs.d_lpt_keys + (bt.e1 - bt.e0) : nullptr;
     c->run.lpt_launches += tickets ? 1 : 0;
     HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, NQUEUES * sizeof(unsigned long long), c->stream));
     const u64 waves = bt.e1 - bt.e0;
     const dim3 gd((u32)std::min<u64>((waves + 3) / 4, r.max_blocks)), bd(256);
     HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    const bool fast = c->d_kmL != nullptr, tw = pa.tw != nullptr, nf = c->all_nfree;
+    const bool fast = c->gs.tab.kmL != nullptr, tw = pa.tw != nullptr, nf = c->gs.all_nfree;
     auto rtc_launch = [&]() -> bool {
         if (!r.rtc_k) return false;
         void* kargs[] = {&pa};
@@ -1204,7 +1157,7 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     const void* kf = nullptr;
     with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) { kf = reinterpret_cast<const void*>(k_pairs_blk<N, D>); });
     const bool use_blk = blk_rows && fast && tw && !pa.skeys && blk_fits(c, kf);
-    if (use_blk && !c->d_blkctr) HIPCHK(c, hipMalloc(&c->d_blkctr, (size_t)c->n_cus * 2 * 4));
+    if (use_blk && !c->d_blkctr) HIPCHK(c, c->d_blkctr.alloc((size_t)c->n_cus * 2));
     int rc = LZANI_OK;
     if (r.rs) {                                   // alignment output: one generic instantiation per index form
         if (!fast) launch_k_pairs<false, false, 0, true, false, 0>(c, gd, bd, pa);
@@ -1226,14 +1179,14 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     } else if (tw && pa.skeys) {                  // long genomes: candidates by the join
         if (!rtc_launch()) with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 1>(c, gd, bd, pa); });
     } else if (use_blk) {
-        const u32 fw = (u32)std::max<u64>(c->fl_stride >> c->blk_fold, 1);
+        const u32 fw = (u32)std::max<u64>(c->gs.fl_stride >> c->gs.blk_fold, 1);
         const size_t lds = (size_t)(BLK_WAVES * SEED_LDS_WORDS + fw) * 4;
         HIPCHK(c, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        pa.fmask = c->fmask >> c->blk_fold;
+        pa.fmask = c->gs.fmask >> c->gs.blk_fold;
         c->run.blk_launches += 1;
         const dim3 gb((u32)std::min<u64>((waves + BLK_CHUNK_MIN - 1) / BLK_CHUNK_MIN, (u64)c->n_cus * 2)), bb(64 * BLK_WAVES);
         with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) {
-            hipLaunchKernelGGL((k_pairs_blk<N, D>), gb, bb, lds, c->stream, pa, fw, (u32)c->blk_fold, c->d_blkctr);
+            hipLaunchKernelGGL((k_pairs_blk<N, D>), gb, bb, lds, c->stream, pa, fw, (u32)c->gs.blk_fold, c->d_blkctr);
             count_launch<PK_BLK, true, N, D, false, true, 0>(c->run);
         });
     } else if (tw) {
@@ -1252,10 +1205,10 @@ int sink_candidates(RunCtx& r, const Batch& bt)
     CandSink& s = *r.sink;
     const u64 bp = bt.e1 - bt.e0, w = std::min<u64>(s.words, r.p.cb_words);
     if (s.cbits && w)
-        HIPCHK(c, hipMemcpy2DAsync(s.cbits + bt.e0 * s.words, s.words * 4, c->d_pm_cbits, r.p.cb_words * 4, w * 4, bp,
+        HIPCHK(c, hipMemcpy2DAsync(s.cbits + bt.e0 * s.words, s.words * 4, c->cs.d_pm_cbits, r.p.cb_words * 4, w * 4, bp,
                                    hipMemcpyDeviceToHost, c->stream));
-    if (s.pcount && bt.lpt && c->d_lpt_cnt) {
-        HIPCHK(c, hipMemcpyAsync(s.pcount + bt.e0, c->d_lpt_cnt, bp * 4, hipMemcpyDeviceToHost, c->stream));
+    if (s.pcount && bt.lpt && c->cs.d_lpt_cnt) {
+        HIPCHK(c, hipMemcpyAsync(s.pcount + bt.e0, c->cs.d_lpt_cnt, bp * 4, hipMemcpyDeviceToHost, c->stream));
         s.counted_batches += 1;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1269,10 +1222,10 @@ int run_batch(RunCtx& r, Batch bt, hipEvent_t* ev)
 {
     lzani_ctx* c = r.c;
     const RunPlan& p = r.p;
-    TRACE("batch %u rows [%u,%u) pairs [%llu,%llu) slots=%u pm=%d", bt.b, bt.k0, bt.k0 + bt.rows, (unsigned long long)bt.e0, (unsigned long long)bt.e1, c->slots, (int)p.pm);
+    TRACE("batch %u rows [%u,%u) pairs [%llu,%llu) slots=%u pm=%d", bt.b, bt.k0, bt.k0 + bt.rows, (unsigned long long)bt.e0, (unsigned long long)bt.e1, c->sl.slots, (int)p.pm);
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     // rows for k_pairs_blk (launch_pairs): dense, hundreds of pairs each, probe form with tag words and a filter
-    const bool blk_rows = !p.pm && !r.rs && c->d_kmL && c->tw_stride && !c->join_mode && c->fl_stride && bt.e1 > bt.e0 &&
+    const bool blk_rows = !p.pm && !r.rs && c->gs.tab.kmL && c->gs.tw_stride && !c->gs.join_mode && c->gs.fl_stride && bt.e1 > bt.e0 &&
                           (bt.e1 - bt.e0) / bt.rows >= 128 && r.k.block_kernel.value_or(r.query_ids == nullptr);
     int rc = build_indexes(c, r.k, r.d_ref + bt.k0, bt.rows, blk_rows, !p.pm);
     if (rc) return rc;
@@ -1405,7 +1358,7 @@ int finish_run(lzani_ctx* c, u64 n_pairs, const lzani_rtc::Kernel* rtc_k, const 
 int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
                   int* d_out, const RegionSink* rs = nullptr, CandSink* sink = nullptr, RunPlan* plan_out = nullptr)
 {
-    if (!c->n) return fail(c, LZANI_ERR_STATE, "lzani_run_rows: no genomes set");
+    if (!c->gs.n) return fail(c, LZANI_ERR_STATE, "lzani_run_rows: no genomes set");
     c->run = RunRecord{};
     const Knobs k{};
     if (n_rows == 0) return LZANI_OK;
@@ -1430,8 +1383,8 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     const u32 n_batches = (u32)p.bstart.size() - 1;
     c->run.batches = n_batches;
     const auto [qorder, qcum, qb] = plan_queues(n_rows, row_off, p.bstart);
-    DevBuf<u32> d_ref, d_q, d_qorder;
-    DevBuf<u64> d_off, d_qcum;
+    DevMem<u32> d_ref, d_q, d_qorder;
+    DevMem<u64> d_off, d_qcum;
     HIPCHK(c, d_qorder.alloc(n_rows));
     HIPCHK(c, d_qcum.alloc(qcum.size()));
     HIPCHK(c, d_ref.alloc(n_rows));
@@ -1450,7 +1403,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
         c->events.push_back(e);
     }
     const u32 max_blocks = (u32)c->n_cus * k.blocks_per_cu;
-    DevBuf<unsigned long long> d_cbits;                      // join form: one candidate bitmap per resident wave
+    DevMem<unsigned long long> d_cbits;                      // join form: one candidate bitmap per resident wave
     u64 cbits_stride = 0;
     if (p.use_join && !rs) {
         cbits_stride = (u64)((p.Lmax + c->P.mrd) >> 6) + 8;
@@ -1462,12 +1415,12 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     // A compile takes 2-3 s and the folded kernel saves ~0.13 s per million pairs of 40 kbp: a code object that is not in
     // the disk cache yet is built once the context has been asked for LZANI_RTC_MIN_PAIRS pairs in all (default 2 M: the
     // first such run loses a second or two, every later run and every later process wins).
-    const int dsel = defp_select(c->P), cand = p.pm ? 2 : (p.use_join && c->d_tw) ? 1 : c->d_tw ? 0 : -1;
-    const int rtc_id = PK_RTC_N0_C0 + 3 * (int)c->all_nfree + cand;      // (its row of the launch record)
+    const int dsel = defp_select(c->P), cand = p.pm ? 2 : (p.use_join && c->sl.d_tw) ? 1 : c->sl.d_tw ? 0 : -1;
+    const int rtc_id = PK_RTC_N0_C0 + 3 * (int)c->gs.all_nfree + cand;      // (its row of the launch record)
     lzani_rtc::Kernel* rtc_k = nullptr;
     c->pairs_seen += n_pairs;
-    if (!dsel && !rs && c->d_kmL && c->d_bk && lzani_rtc::enabled() && cand >= 0) {
-        rtc_k = lzani_rtc::get(c->rtc, c->P, c->all_nfree, cand, c->arch.c_str(), c->pairs_seen >= k.rtc_min_pairs);
+    if (!dsel && !rs && c->gs.tab.kmL && c->sl.d_bk && lzani_rtc::enabled() && cand >= 0) {
+        rtc_k = lzani_rtc::get(c->rtc, c->P, c->gs.all_nfree, cand, c->arch.c_str(), c->pairs_seen >= k.rtc_min_pairs);
         if (!rtc_k && c->rtc.failed) TRACE("run-time compile unavailable (%s): the generic kernel runs", c->rtc.log.c_str());
     }
 
@@ -1509,7 +1462,7 @@ int lzani_create(const lzani_params* p, int device_id, lzani_ctx** out)
     c->P = P;
     c->dev = device_id;
     bool ok = hipSetDevice(device_id) == hipSuccess && hipStreamCreate(&c->stream) == hipSuccess &&
-              hipMalloc(&c->d_cursor, NQUEUES * sizeof(unsigned long long)) == hipSuccess;
+              c->d_cursor.alloc(NQUEUES) == hipSuccess;
     if (ok) ok = hipEventCreate(&c->ev_km[0]) == hipSuccess && hipEventCreate(&c->ev_km[1]) == hipSuccess;
     if (ok) {
         hipDeviceProp_t prop;
@@ -1526,12 +1479,7 @@ void lzani_destroy(lzani_ctx* c)
     if (!c) return;
     hipSetDevice(c->dev);
     comm_release(c);
-    free_genomes(c);
-    free_slabs(c);
-    free_pm(c);
     lzani_rtc::release(c->rtc);
-    hipFree(c->d_cursor);
-    hipFree(c->d_blkctr);
     for (auto& e : c->events) if (e) hipEventDestroy(e);
     for (auto& e : c->ev_km) if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -1545,11 +1493,12 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     if (!c) return LZANI_ERR_ARG;
     if (!n || !codes || !len) return fail(c, LZANI_ERR_ARG, "lzani_set_genomes: empty input");
     HIPCHK(c, hipSetDevice(c->dev));
-    free_genomes(c);
-    free_slabs(c);
-    free_pm(c);
-    c->L.resize(n);
-    c->nmoff.resize(n);
+    c->gs = GenomeSet{};
+    c->sl = IndexSlabs{};
+    c->cs = CandScratch{};
+    c->res = Residency{};
+    c->gs.L.resize(n);
+    c->gs.nmoff.resize(n);
     std::vector<u64> codeoff(n);
     u64 total_codes = 0, total_nm = 0;
     int Lmax = 0;
@@ -1557,17 +1506,17 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
         if (len[g] > 0x3FFFFFFFu - 3u * (u32)c->P.mrd)
             return fail(c, LZANI_ERR_ARG, "lzani_set_genomes: sequence too long for 32-bit text positions");
         if (len[g] && !codes[g]) return fail(c, LZANI_ERR_ARG, "lzani_set_genomes: null sequence");
-        c->L[g] = (int)len[g];
-        Lmax = std::max(Lmax, c->L[g]);
+        c->gs.L[g] = (int)len[g];
+        Lmax = std::max(Lmax, c->gs.L[g]);
         codeoff[g] = total_codes; total_codes += len[g];
-        c->nmoff[g] = total_nm; total_nm += text_wordsN(ref_text_len(c->L[g], c->P.mrd));
+        c->gs.nmoff[g] = total_nm; total_nm += text_wordsN(ref_text_len(c->gs.L[g], c->P.mrd));
     }
-    c->Tmax = ref_text_len(Lmax, c->P.mrd);
-    c->geo = index_geometry(c->Tmax, c->P.mal);
-    c->dir_stride = ((u64)1 << c->geo.dirbits) + 1;
-    c->ent_stride = (u64)c->Tmax;
-    c->total_nm = total_nm;
-    c->n_pending = n;
+    c->gs.Tmax = ref_text_len(Lmax, c->P.mrd);
+    c->gs.geo = index_geometry(c->gs.Tmax, c->P.mal);
+    c->gs.dir_stride = ((u64)1 << c->gs.geo.dirbits) + 1;
+    c->gs.ent_stride = (u64)c->gs.Tmax;
+    c->gs.total_nm = total_nm;
+    c->gs.n_pending = n;
     choose_index_form(c);
     // Residency: the whole set in HBM (step (b) below, on every genome), or blocks of it kept on the host and uploaded by
     // the runs (lzani_ooc.h).  Automatic mode (limit 0) keeps every set in-core that can be had in-core: its tables, the
@@ -1580,46 +1529,50 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
             HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
             if (const char* fb = getenv("LZANI_FREE_BYTES")) free_b = std::min<size_t>(free_b, (size_t)strtoull(fb, nullptr, 10));   // tests: the automatic trigger
             const u64 tables = total_nm * (16 + 8) + (kmers ? total_nm * 64 * 8 : 0);
-            const u64 per_slot = 4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride) + (c->sort_build ? (u64)16 * c->Tmax + 16 : 0);
+            const u64 per_slot = 4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride) + (c->gs.sort_build ? (u64)16 * c->gs.Tmax + 16 : 0);
             if (tables + total_codes > free_b || tables + per_slot > free_b) limit = free_b / 2;     // (half for the genomes, half for slabs and bitmaps)
         }
         std::vector<u64> bytes;
         std::string msg;
-        const int nb = plan_blocks_impl(n, len, c->P, limit, c->blk_first, bytes, msg);
+        const int nb = plan_blocks_impl(n, len, c->P, limit, c->gs.blk_first, bytes, msg);
         if (nb < 0) return fail(c, c->mem_req ? nb : LZANI_ERR_NOMEM, "lzani_set_genomes: " + msg);
         if (nb > 1) {
-            c->blk_bytes = bytes;
-            c->mem_limit = limit;
+            c->gs.blk_bytes = bytes;
+            c->gs.mem_limit = limit;
             return ooc_set_genomes(c, n, codes, len);
         }
-        c->mem_limit = c->mem_req;
-        c->res_peak = bytes[0];
-        c->blk_first.clear();
+        c->gs.mem_limit = c->mem_req;
+        c->res.peak = bytes[0];
+        c->gs.blk_first.clear();
     }
 
-    DevBuf<uint8_t> d_codes;
-    DevBuf<u64> d_codeoff;
+    DevMem<uint8_t> d_codes;
+    DevMem<u64> d_codeoff;
     HIPCHK(c, d_codes.alloc(total_codes));
     HIPCHK(c, d_codeoff.alloc(n));
-    HIPCHK(c, hipMalloc(&c->d_t2, total_nm * 16));
-    HIPCHK(c, hipMalloc(&c->d_nm, total_nm * 8));
-    HIPCHK(c, hipMalloc(&c->d_nmoff, (size_t)n * 8));
-    HIPCHK(c, hipMalloc(&c->d_L, (size_t)n * 4));
-    HIPCHK(c, hipMalloc(&c->d_hasN, (size_t)n * 4));
-    HIPCHK(c, hipMemset(c->d_hasN, 0, (size_t)n * 4));
-    if (c->P.mal <= 15 && c->P.msl <= 15) {
-        HIPCHK(c, hipMalloc(&c->d_kmL, total_nm * 64 * 4));
-        HIPCHK(c, hipMalloc(&c->d_kmS, total_nm * 64 * 4));
+    {
+        GenomeTables t;                                       // (moved into the set whole, or not at all)
+        HIPCHK(c, t.t2.alloc(total_nm * 2));
+        HIPCHK(c, t.nm.alloc(total_nm));
+        HIPCHK(c, t.nmoff.alloc(n));
+        HIPCHK(c, t.L.alloc(n));
+        HIPCHK(c, t.hasN.alloc(n));
+        HIPCHK(c, hipMemset(t.hasN, 0, (size_t)n * 4));
+        if (c->P.mal <= 15 && c->P.msl <= 15) {
+            HIPCHK(c, t.kmL.alloc(total_nm * 64));
+            HIPCHK(c, t.kmS.alloc(total_nm * 64));
+        }
+        c->gs.tab = std::move(t);
     }
     // The caller's sequences are separate host buffers: they go up through two pinned 64 MB staging buffers, the
     // copy of one overlapping the fill of the other (the 4 GB of config 5 take as long as the PCIe link needs).
     {
         const u64 chunk = 64ull << 20;
-        uint8_t* pin[2] = {nullptr, nullptr};
+        PinMem<uint8_t> pin[2];
         hipEvent_t done[2] = {nullptr, nullptr};
         hipError_t e = hipSuccess;
         for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-            e = hipHostMalloc((void**)&pin[k], chunk, hipHostMallocDefault);
+            e = pin[k].alloc(chunk);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&done[k], hipEventDisableTiming);
         }
         u64 at = 0;                                               // codes staged so far
@@ -1633,33 +1586,33 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
                 fill += take; goff += take;
                 if (goff == len[g]) { ++g; goff = 0; }
             }
-            if (e == hipSuccess) e = hipMemcpyAsync(d_codes.p + at, pin[k], fill, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_codes.get() + at, pin[k], fill, hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = hipEventRecord(done[k], c->stream);
             at += fill;
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        for (int k = 0; k < 2; ++k) { if (done[k]) hipEventDestroy(done[k]); if (pin[k]) hipHostFree(pin[k]); }
+        for (int k = 0; k < 2; ++k) if (done[k]) hipEventDestroy(done[k]);
         if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE, std::string("staging the sequences: ") + hipGetErrorString(e));
     }
     HIPCHK(c, hipMemcpy(d_codeoff, codeoff.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_nmoff, c->nmoff.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_L, c->L.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    c->n = n;
-    size_t maxblk = text_wordsN(c->Tmax);
+    HIPCHK(c, hipMemcpy(c->gs.tab.nmoff, c->gs.nmoff.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->gs.tab.L, c->gs.L.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    c->gs.n = n;
+    size_t maxblk = text_wordsN(c->gs.Tmax);
     // gridDim.y is limited to 65535: pack in slices of genomes
     for (u32 g0 = 0; g0 < n; g0 += 32768) {
         u32 cnt = std::min<u32>(32768, n - g0);
         hipLaunchKernelGGL(k_pack, dim3((u32)((maxblk + 127) / 128), cnt), dim3(128), 0, c->stream,
-                           d_codes.p, d_codeoff.p + g0, c->d_t2, c->d_nm, c->d_nmoff + g0, c->d_L + g0, c->d_hasN + g0, c->P.mrd, cnt);
+                           d_codes.get(), d_codeoff.get() + g0, c->gs.tab.t2, c->gs.tab.nm, c->gs.tab.nmoff + g0, c->gs.tab.L + g0, c->gs.tab.hasN + g0, c->P.mrd, cnt);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     {
         std::vector<int> hn(n);
-        HIPCHK(c, hipMemcpy(hn.data(), c->d_hasN, (size_t)n * 4, hipMemcpyDeviceToHost));
-        c->all_nfree = std::all_of(hn.begin(), hn.end(), [](int v) { return v == 0; });
+        HIPCHK(c, hipMemcpy(hn.data(), c->gs.tab.hasN, (size_t)n * 4, hipMemcpyDeviceToHost));
+        c->gs.all_nfree = std::all_of(hn.begin(), hn.end(), [](int v) { return v == 0; });
     }
-    TRACE("set_genomes: n=%u Tmax=%d dirbits=%d posbits=%d tagmask=%x", n, c->Tmax, c->geo.dirbits, c->geo.posbits, c->geo.tagmask);
+    TRACE("set_genomes: n=%u Tmax=%d dirbits=%d posbits=%d tagmask=%x", n, c->gs.Tmax, c->gs.geo.dirbits, c->gs.geo.posbits, c->gs.geo.tagmask);
     return LZANI_OK;
 }
 
@@ -1669,9 +1622,9 @@ int lzani_run_rows_device(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids
     if (!c) return LZANI_ERR_ARG;
     if (!ref_ids || !row_off || (!d_out && n_rows && row_off[n_rows]))
         return fail(c, LZANI_ERR_ARG, "lzani_run_rows_device: null argument");
-    if (c->ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out, nullptr, nullptr);
+    if (c->gs.ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out, nullptr, nullptr);
     const int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out);
-    c->res_tiles = rc == LZANI_OK && n_rows && row_off[n_rows] ? 1 : 0;
+    c->res.tiles = rc == LZANI_OK && n_rows && row_off[n_rows] ? 1 : 0;
     return rc;
 }
 
@@ -1683,13 +1636,13 @@ int lzani_run_rows(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids, const
     const u64 n_pairs = n_rows ? row_off[n_rows] : 0;
     if (n_pairs && !out) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: null output");
     HIPCHK(c, hipSetDevice(c->dev));
-    if (c->ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, nullptr);     // (host scatter)
-    DevBuf<lzani_result> d_out;
+    if (c->gs.ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, nullptr);     // (host scatter)
+    DevMem<lzani_result> d_out;
     if (n_pairs) HIPCHK(c, d_out.alloc(n_pairs));
-    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.p);
-    c->res_tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
+    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.get());
+    c->res.tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
     if (rc == LZANI_OK && n_pairs) {
-        hipError_t e = hipMemcpy(out, d_out.p, n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(out, d_out.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy results: ") + hipGetErrorString(e));
     }
     return rc;
@@ -1706,24 +1659,24 @@ int lzani_run_rows_regions(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_id
     if (n_pairs && !out) return fail(c, LZANI_ERR_ARG, "lzani_run_rows_regions: null output");
     *n_regions = 0;
     HIPCHK(c, hipSetDevice(c->dev));
-    DevBuf<lzani_result> d_out;
-    DevBuf<lzani_region> d_regions;
-    DevBuf<unsigned long long> d_count;
-    if (n_pairs && !c->ooc) HIPCHK(c, d_out.alloc(n_pairs));      // (out-of-core: tile by tile)
+    DevMem<lzani_result> d_out;
+    DevMem<lzani_region> d_regions;
+    DevMem<unsigned long long> d_count;
+    if (n_pairs && !c->gs.ooc) HIPCHK(c, d_out.alloc(n_pairs));      // (out-of-core: tile by tile)
     HIPCHK(c, d_regions.alloc(capacity));
     HIPCHK(c, d_count.alloc(1));
-    HIPCHK(c, hipMemset(d_count.p, 0, sizeof(unsigned long long)));
-    RegionSink rs{d_regions.p, d_count.p, capacity};
+    HIPCHK(c, hipMemset(d_count.get(), 0, sizeof(unsigned long long)));
+    RegionSink rs{d_regions.get(), d_count.get(), capacity};
     int rc;
-    if (c->ooc) rc = run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, &rs);
+    if (c->gs.ooc) rc = run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, &rs);
     else {
-        rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.p, &rs);
-        c->res_tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
+        rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.get(), &rs);
+        c->res.tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
     }
     if (rc == LZANI_OK) {
         unsigned long long cnt = 0;
         hipError_t e = hipMemcpy(&cnt, rs.d_count, sizeof cnt, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && n_pairs && !c->ooc) e = hipMemcpy(out, d_out.p, n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && n_pairs && !c->gs.ooc) e = hipMemcpy(out, d_out.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e == hipSuccess && cnt && capacity)
             e = hipMemcpy(regions, rs.d_regions, std::min<uint64_t>(cnt, capacity) * sizeof(lzani_region), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy regions: ") + hipGetErrorString(e));
@@ -1742,14 +1695,14 @@ int lzani_get_timing(const lzani_ctx* c, lzani_timing* t)
 int lzani_get_layout(const lzani_ctx* c, lzani_layout_info* o)
 {
     if (!c || !o) return LZANI_ERR_ARG;
-    o->key_bits = c->geo.kb; o->dir_bits = c->geo.dirbits; o->pos_bits = c->geo.posbits; o->tag_mask = c->geo.tagmask;
-    o->kmer_words = c->d_kmL != nullptr;
-    o->bucket_table = c->bk_stride != 0; o->tag_words = c->tw_stride != 0;
-    o->n_free = c->all_nfree;
-    o->slots = c->slots; o->batches_last_run = c->run.batches;
-    o->bytes_per_slot = 4 * (c->dir_stride + c->ent_stride + c->bk_stride + c->tw_stride + c->fl_stride);
-    o->bytes_genomes = c->total_nm * (16 + 8) + (c->d_kmL ? c->total_nm * 64 * 8 : 0);
-    o->join_lists = c->join_mode; o->block_launches = c->run.blk_launches; o->bitmap_launches = c->run.pm_launches; o->rtc_launches = c->run.rtc_launches;
+    o->key_bits = c->gs.geo.kb; o->dir_bits = c->gs.geo.dirbits; o->pos_bits = c->gs.geo.posbits; o->tag_mask = c->gs.geo.tagmask;
+    o->kmer_words = c->gs.tab.kmL != nullptr;
+    o->bucket_table = c->gs.bk_stride != 0; o->tag_words = c->gs.tw_stride != 0;
+    o->n_free = c->gs.all_nfree;
+    o->slots = c->sl.slots; o->batches_last_run = c->run.batches;
+    o->bytes_per_slot = 4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride);
+    o->bytes_genomes = c->gs.total_nm * (16 + 8) + (c->gs.tab.kmL ? c->gs.total_nm * 64 * 8 : 0);
+    o->join_lists = c->gs.join_mode; o->block_launches = c->run.blk_launches; o->bitmap_launches = c->run.pm_launches; o->rtc_launches = c->run.rtc_launches;
     o->lpt_launches = c->run.lpt_launches; o->matrix_from_index = c->run.pmfi_launches;
     o->split_launches = c->run.split_launches; o->split_segments = c->run.split_items;
     return LZANI_OK;
@@ -1798,13 +1751,13 @@ int lzani_plan_blocks(uint32_t n, const uint32_t* len, const lzani_params* p, ui
 int lzani_get_residency(const lzani_ctx* c, lzani_residency_info* o)
 {
     if (!c || !o) return LZANI_ERR_ARG;
-    o->limit = c->mem_limit;
-    o->blocks = c->ooc ? (uint32_t)c->blk_first.size() - 1 : (c->n ? 1u : 0u);
-    o->tiles = c->res_tiles;
-    o->block_uploads = c->res_uploads;
-    o->peak_resident_bytes = c->res_peak;
-    o->host_bytes = c->h_codes.size();
-    o->upload_ms = c->res_upload_ms;
+    o->limit = c->gs.mem_limit;
+    o->blocks = c->gs.ooc ? (uint32_t)c->gs.blk_first.size() - 1 : (c->gs.n ? 1u : 0u);
+    o->tiles = c->res.tiles;
+    o->block_uploads = c->res.uploads;
+    o->peak_resident_bytes = c->res.peak;
+    o->host_bytes = c->gs.h_codes.size();
+    o->upload_ms = c->res.upload_ms;
     return LZANI_OK;
 }
 
@@ -1829,28 +1782,28 @@ int lzani_debug_get_index(lzani_ctx* c, uint32_t id, uint64_t* t2, uint64_t* nm,
                           uint32_t* ent, uint32_t* n_ent, uint32_t* geom)
 {
     if (!c) return LZANI_ERR_ARG;
-    if (!c->n || id >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_debug_get_index: bad id");
-    if (c->ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_get_index: the genome is not resident (out-of-core set)");
+    if (!c->gs.n || id >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_debug_get_index: bad id");
+    if (c->gs.ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_get_index: the genome is not resident (out-of-core set)");
     HIPCHK(c, hipSetDevice(c->dev));
     int rc = ensure_slabs(c, 1);
     if (rc) return rc;
-    DevBuf<u32> d_ref;
+    DevMem<u32> d_ref;
     HIPCHK(c, d_ref.alloc(1));
-    HIPCHK(c, hipMemcpy(d_ref.p, &id, 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_ref.get(), &id, 4, hipMemcpyHostToDevice));
     rc = build_indexes(c, Knobs{}, d_ref, 1);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    int T = ref_text_len(c->L[id], c->P.mrd);
+    int T = ref_text_len(c->gs.L[id], c->P.mrd);
     size_t wn = text_wordsN(T);
-    if (nm) HIPCHK(c, hipMemcpy(nm, c->d_nm + c->nmoff[id], wn * 8, hipMemcpyDeviceToHost));
-    if (t2) HIPCHK(c, hipMemcpy(t2, c->d_t2 + 2 * c->nmoff[id], wn * 16, hipMemcpyDeviceToHost));
-    std::vector<u32> d(c->dir_stride);
-    HIPCHK(c, hipMemcpy(d.data(), c->d_dirz, c->dir_stride * 4, hipMemcpyDeviceToHost));
-    u32 ne = d[c->dir_stride - 1];
-    if (dirz) memcpy(dirz, d.data(), c->dir_stride * 4);
-    if (ent && ne) HIPCHK(c, hipMemcpy(ent, c->d_ent, (size_t)ne * 4, hipMemcpyDeviceToHost));
+    if (nm) HIPCHK(c, hipMemcpy(nm, c->gs.tab.nm + c->gs.nmoff[id], wn * 8, hipMemcpyDeviceToHost));
+    if (t2) HIPCHK(c, hipMemcpy(t2, c->gs.tab.t2 + 2 * c->gs.nmoff[id], wn * 16, hipMemcpyDeviceToHost));
+    std::vector<u32> d(c->gs.dir_stride);
+    HIPCHK(c, hipMemcpy(d.data(), c->sl.d_dirz, c->gs.dir_stride * 4, hipMemcpyDeviceToHost));
+    u32 ne = d[c->gs.dir_stride - 1];
+    if (dirz) memcpy(dirz, d.data(), c->gs.dir_stride * 4);
+    if (ent && ne) HIPCHK(c, hipMemcpy(ent, c->sl.d_ent, (size_t)ne * 4, hipMemcpyDeviceToHost));
     if (n_ent) *n_ent = ne;
-    if (geom) { geom[0] = c->geo.kb; geom[1] = c->geo.dirbits; geom[2] = c->geo.posbits; geom[3] = c->geo.tagmask; }
+    if (geom) { geom[0] = c->gs.geo.kb; geom[1] = c->gs.geo.dirbits; geom[2] = c->gs.geo.posbits; geom[3] = c->gs.geo.tagmask; }
     return LZANI_OK;
 }
 
@@ -1862,19 +1815,19 @@ int lzani_debug_sort_segments(lzani_ctx* c, const uint64_t* keys, uint64_t* out,
     HIPCHK(c, hipSetDevice(c->dev));
     const size_t n = (size_t)seg_len * n_seg;
     if (n == 0) return LZANI_OK;
-    DevBuf<unsigned long long> d_in, d_out;
-    DevBuf<unsigned char> d_tmp;
+    DevMem<unsigned long long> d_in, d_out;
+    DevMem<unsigned char> d_tmp;
     HIPCHK(c, d_in.alloc(n));
     HIPCHK(c, d_out.alloc(n));
-    HIPCHK(c, hipMemcpy(d_in.p, keys, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_in.get(), keys, n * 8, hipMemcpyHostToDevice));
     size_t need = 0;
-    if (lzani_sort_segments(d_in.p, d_out.p, seg_len, n_seg, begin_bit, end_bit, nullptr, &need, c->stream) != 0)
+    if (lzani_sort_segments(d_in.get(), d_out.get(), seg_len, n_seg, begin_bit, end_bit, nullptr, &need, c->stream) != 0)
         return fail(c, LZANI_ERR_ARG, "lzani_debug_sort_segments: bad arguments");
     HIPCHK(c, d_tmp.alloc(need));
-    if (lzani_sort_segments(d_in.p, d_out.p, seg_len, n_seg, begin_bit, end_bit, d_tmp.p, &need, c->stream) != 0)
+    if (lzani_sort_segments(d_in.get(), d_out.get(), seg_len, n_seg, begin_bit, end_bit, d_tmp.get(), &need, c->stream) != 0)
         return fail(c, LZANI_ERR_DEVICE, "lzani_debug_sort_segments: sort failed");
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, d_out.p, n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, d_out.get(), n * 8, hipMemcpyDeviceToHost));
     return LZANI_OK;
 }
 
@@ -1884,35 +1837,35 @@ int lzani_debug_index_slab(lzani_ctx* c, uint32_t rows, const uint32_t* ref_ids,
                            uint32_t* status)
 {
     if (!c) return LZANI_ERR_ARG;
-    if (!c->n || !rows || !ref_ids || !info) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: bad arguments");
-    if (c->ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_index_slab: the genomes are not resident (out-of-core set)");
+    if (!c->gs.n || !rows || !ref_ids || !info) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: bad arguments");
+    if (c->gs.ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_index_slab: the genomes are not resident (out-of-core set)");
     for (u32 k = 0; k < rows; ++k)
-        if (ref_ids[k] >= c->n) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: reference id out of range");
+        if (ref_ids[k] >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: reference id out of range");
     HIPCHK(c, hipSetDevice(c->dev));
     int rc = ensure_slabs(c, rows);
     if (rc) return rc;
-    if (c->slots < rows) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: more rows than index slabs");
-    DevBuf<u32> d_ref;
+    if (c->sl.slots < rows) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: more rows than index slabs");
+    DevMem<u32> d_ref;
     HIPCHK(c, d_ref.alloc(rows));
-    HIPCHK(c, hipMemcpy(d_ref.p, ref_ids, (size_t)rows * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_ref.get(), ref_ids, (size_t)rows * 4, hipMemcpyHostToDevice));
     rc = build_indexes(c, Knobs{}, d_ref, rows, with_filter != 0, with_tw != 0);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    info->key_bits = c->geo.kb; info->dir_bits = c->geo.dirbits; info->pos_bits = c->geo.posbits; info->tag_mask = c->geo.tagmask;
-    info->filter_mask = c->fmask;
-    info->build = c->index_build;
-    info->dir_stride = c->dir_stride; info->ent_stride = c->ent_stride; info->bk_stride = c->bk_stride;
+    info->key_bits = c->gs.geo.kb; info->dir_bits = c->gs.geo.dirbits; info->pos_bits = c->gs.geo.posbits; info->tag_mask = c->gs.geo.tagmask;
+    info->filter_mask = c->gs.fmask;
+    info->build = c->sl.index_build;
+    info->dir_stride = c->gs.dir_stride; info->ent_stride = c->gs.ent_stride; info->bk_stride = c->gs.bk_stride;
     // (what this build wrote: the sort build leaves the tag words out without with_tw, every build the filter without with_filter)
-    info->tw_stride = (c->index_build != LZANI_INDEX_BUILD_SORT || with_tw) ? c->tw_stride : 0;
-    info->fl_stride = with_filter ? c->fl_stride : 0;
+    info->tw_stride = (c->sl.index_build != LZANI_INDEX_BUILD_SORT || with_tw) ? c->gs.tw_stride : 0;
+    info->fl_stride = with_filter ? c->gs.fl_stride : 0;
     const size_t r = rows;
-    if (dirz) HIPCHK(c, hipMemcpy(dirz, c->d_dirz, r * c->dir_stride * 4, hipMemcpyDeviceToHost));
-    if (ent) HIPCHK(c, hipMemcpy(ent, c->d_ent, r * c->ent_stride * 4, hipMemcpyDeviceToHost));
-    if (bk && info->bk_stride) HIPCHK(c, hipMemcpy(bk, c->d_bk, r * info->bk_stride * 4, hipMemcpyDeviceToHost));
-    if (tw && info->tw_stride) HIPCHK(c, hipMemcpy(tw, c->d_tw, r * info->tw_stride * 4, hipMemcpyDeviceToHost));
-    if (fl && info->fl_stride) HIPCHK(c, hipMemcpy(fl, c->d_fl, r * info->fl_stride * 4, hipMemcpyDeviceToHost));
+    if (dirz) HIPCHK(c, hipMemcpy(dirz, c->sl.d_dirz, r * c->gs.dir_stride * 4, hipMemcpyDeviceToHost));
+    if (ent) HIPCHK(c, hipMemcpy(ent, c->sl.d_ent, r * c->gs.ent_stride * 4, hipMemcpyDeviceToHost));
+    if (bk && info->bk_stride) HIPCHK(c, hipMemcpy(bk, c->sl.d_bk, r * info->bk_stride * 4, hipMemcpyDeviceToHost));
+    if (tw && info->tw_stride) HIPCHK(c, hipMemcpy(tw, c->sl.d_tw, r * info->tw_stride * 4, hipMemcpyDeviceToHost));
+    if (fl && info->fl_stride) HIPCHK(c, hipMemcpy(fl, c->sl.d_fl, r * info->fl_stride * 4, hipMemcpyDeviceToHost));
     if (status) {
-        if (c->index_build == LZANI_INDEX_BUILD_LDS) HIPCHK(c, hipMemcpy(status, c->d_status, r * 4, hipMemcpyDeviceToHost));
+        if (c->sl.index_build == LZANI_INDEX_BUILD_LDS) HIPCHK(c, hipMemcpy(status, c->sl.d_status, r * 4, hipMemcpyDeviceToHost));
         else memset(status, 0, r * 4);
     }
     return LZANI_OK;
@@ -1925,22 +1878,22 @@ int lzani_debug_run_candidates(lzani_ctx* c, uint32_t n_rows, const uint32_t* re
 {
     if (!c) return LZANI_ERR_ARG;
     if (!ref_ids || !row_off || !plan) return fail(c, LZANI_ERR_ARG, "lzani_debug_run_candidates: null argument");
-    if (c->ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_run_candidates: the genomes are not resident (out-of-core set)");
+    if (c->gs.ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_run_candidates: the genomes are not resident (out-of-core set)");
     const u64 n_pairs = n_rows ? row_off[n_rows] : 0;
     if (n_pairs && !out) return fail(c, LZANI_ERR_ARG, "lzani_debug_run_candidates: null output");
     HIPCHK(c, hipSetDevice(c->dev));
     if (pcount) std::fill(pcount, pcount + n_pairs, 0xFFFFFFFFu);
-    DevBuf<lzani_result> d_out;
+    DevMem<lzani_result> d_out;
     if (n_pairs) HIPCHK(c, d_out.alloc(n_pairs));
     CandSink sink{cbits, words, pcount, 0};
     RunPlan p;
-    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.p, nullptr, &sink, &p);
+    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.get(), nullptr, &sink, &p);
     if (rc == LZANI_OK && n_pairs) {
-        hipError_t e = hipMemcpy(out, d_out.p, n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(out, d_out.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy results: ") + hipGetErrorString(e));
     }
     if (rc) return rc;
-    plan->pm = p.pm; plan->pm_bits = p.pm ? p.pm_bits : 0; plan->rshift = p.pm ? c->geo.kb - p.pm_bits : 0;
+    plan->pm = p.pm; plan->pm_bits = p.pm ? p.pm_bits : 0; plan->rshift = p.pm ? c->gs.geo.kb - p.pm_bits : 0;
     plan->pm_group = p.pm ? p.pm_group : 0;
     plan->cb_words = p.pm ? p.cb_words : 0;
     plan->batches = c->run.batches;

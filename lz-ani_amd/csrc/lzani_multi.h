@@ -50,31 +50,13 @@ struct lzani_group {
     // buffers of lzani_group_run_rows, kept from call to call and grown when a call needs more (a tiled all2all makes ten
     // calls of the same size: no allocation after the first): the gathered / CSR-ordered results on the first device, a
     // shard buffer per peer, the scatter table, and two pinned staging buffers for the copy out
-    int* d_all = nullptr;
-    int* d_final = nullptr;
-    size_t res_cap = 0;                 // results (12 B each) d_all / d_final hold
-    std::vector<int*> d_shard;          // [0] unused (the first device writes into d_all)
-    std::vector<size_t> shard_cap;
-    unsigned long long* d_tab = nullptr;
-    size_t tab_cap = 0;
-    char* h_stage[2] = {nullptr, nullptr};
+    DevMem<lzani_result> d_all, d_final;
+    std::vector<DevMem<lzani_result>> d_shard;    // [0] stays empty (the first device writes into d_all); [d] lives on device d
+    DevMem<unsigned long long> d_tab;
+    PinMem<char> h_stage[2];
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
 };
 enum : size_t { GROUP_STAGE_BYTES = (size_t)32 << 20 };
-static void group_free_buffers(lzani_group* g)
-{
-    if (!g->ctx.empty()) hipSetDevice(g->ctx[0]->dev);
-    hipFree(g->d_all); hipFree(g->d_final); hipFree(g->d_tab);
-    g->d_all = g->d_final = nullptr; g->d_tab = nullptr; g->res_cap = g->tab_cap = 0;
-    for (int k = 0; k < 2; ++k) {
-        if (g->h_stage[k]) hipHostFree(g->h_stage[k]);
-        if (g->ev_stage[k]) hipEventDestroy(g->ev_stage[k]);
-        g->h_stage[k] = nullptr; g->ev_stage[k] = nullptr;
-    }
-    for (size_t d = 1; d < g->d_shard.size(); ++d)
-        if (g->d_shard[d]) { hipSetDevice(g->ctx[d]->dev); hipFree(g->d_shard[d]); g->d_shard[d] = nullptr; }
-    g->shard_cap.assign(g->shard_cap.size(), 0);
-}
 
 static void comm_release(lzani_ctx* c)
 {
@@ -230,7 +212,11 @@ int lzani_plan_gather(uint32_t n_rows, const uint64_t* row_off, const uint32_t* 
 void lzani_group_destroy(lzani_group* g)
 {
     if (!g) return;
-    group_free_buffers(g);
+    for (size_t d = 1; d < g->d_shard.size(); ++d)                  // a shard buffer is released with its device current
+        if (g->d_shard[d]) { hipSetDevice(g->ctx[d]->dev); g->d_shard[d].reset(); }
+    if (!g->ctx.empty()) hipSetDevice(g->ctx[0]->dev);
+    g->d_all.reset(); g->d_final.reset(); g->d_tab.reset();         // (on the first device; the pinned buffers go with the group)
+    for (auto e : g->ev_stage) if (e) hipEventDestroy(e);
     for (auto cm : g->comms) if (cm) ncclCommDestroy(cm);
     for (auto c : g->ctx) lzani_destroy(c);
     delete g;
@@ -302,20 +288,20 @@ int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_id
     if (n_pairs && !out) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null output");
     g->gather_ms = 0;
     lzani_ctx* c0 = g->ctx[0];
-    if (!c0->n) return gfail(g, LZANI_ERR_STATE, "lzani_group_run_rows: no genomes set");
+    if (!c0->gs.n) return gfail(g, LZANI_ERR_STATE, "lzani_group_run_rows: no genomes set");
     for (u32 k = 0; k < n_rows; ++k)
-        if (ref_ids[k] >= c0->n || row_off[k + 1] < row_off[k]) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: bad row table");
+        if (ref_ids[k] >= c0->gs.n || row_off[k + 1] < row_off[k]) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: bad row table");
     if (query_ids)
-        for (u64 e = 0; e < n_pairs; ++e) if (query_ids[e] >= c0->n) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: query id out of range");
+        for (u64 e = 0; e < n_pairs; ++e) if (query_ids[e] >= c0->gs.n) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: query id out of range");
 
     // rows -> devices
     std::vector<u32> part(n_rows);
     {
         std::vector<u64> cost;
         if (query_ids) {
-            std::vector<u32> len(c0->L.begin(), c0->L.end());
+            std::vector<u32> len(c0->gs.L.begin(), c0->gs.L.end());
             cost.resize(n_rows);
-            int rc = lzani_row_costs(n_rows, ref_ids, row_off, query_ids, c0->n, len.data(), cost.data());
+            int rc = lzani_row_costs(n_rows, ref_ids, row_off, query_ids, c0->gs.n, len.data(), cost.data());
             if (rc != LZANI_OK) return gfail(g, rc, "lzani_group_run_rows: row costs");
         }
         lzani_partition_rows(n_rows, query_ids ? cost.data() : nullptr, nd, part.data());
@@ -338,31 +324,28 @@ int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_id
         if (e != hipSuccess) return gfail(g, LZANI_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
     }
     // (grown, never shrunk; a failed growth leaves the group without buffers and the call with LZANI_ERR_NOMEM)
-    if (g->res_cap < std::max<u64>(n_pairs, 1)) {
-        hipFree(g->d_all); hipFree(g->d_final);
-        g->d_all = g->d_final = nullptr; g->res_cap = 0;
-        if (hipMalloc(&g->d_all, std::max<u64>(n_pairs, 1) * 12) != hipSuccess || hipMalloc(&g->d_final, std::max<u64>(n_pairs, 1) * 12) != hipSuccess) {
-            (void)hipGetLastError();
-            hipFree(g->d_all); g->d_all = nullptr;
+    if (g->d_final.capacity() < std::max<u64>(n_pairs, 1)) {
+        g->d_all.reset(); g->d_final.reset();                    // (both released before either is made anew)
+        if (!got(g->d_all.alloc(n_pairs)) || !got(g->d_final.alloc(n_pairs))) {
+            g->d_all.reset();
             return gfail(g, LZANI_ERR_NOMEM, "lzani_group_run_rows: result buffers on device 0");
         }
-        g->res_cap = std::max<u64>(n_pairs, 1);
     }
-    int* const d_all = g->d_all;
-    int* const d_final = g->d_final;
-    g->d_shard.resize(nd, nullptr);
-    g->shard_cap.resize(nd, 0);
-    std::vector<int*>& d_shard = g->d_shard;
+    int* const d_all = (int*)g->d_all.get();
+    int* const d_final = (int*)g->d_final.get();
+    g->d_shard.resize(nd);
+    std::vector<int*> d_shard(nd, nullptr);                      // where every device writes its shard
     d_shard[0] = d_all;
     std::vector<int> rc(nd, LZANI_OK);
     auto one = [&](u32 d) {
         lzani_ctx* c = g->ctx[d];
         if (sh[d].ref.empty()) { c->run.tm = lzani_timing{}; return; }   // no row for this device
-        if (d && g->shard_cap[d] < std::max<u64>(sh[d].off.back(), 1)) {
-            if (hipSetDevice(c->dev) != hipSuccess) { rc[d] = LZANI_ERR_DEVICE; return; }
-            hipFree(d_shard[d]); d_shard[d] = nullptr; g->shard_cap[d] = 0;
-            if (hipMalloc(&d_shard[d], std::max<u64>(sh[d].off.back(), 1) * 12) != hipSuccess) { (void)hipGetLastError(); d_shard[d] = nullptr; rc[d] = LZANI_ERR_NOMEM; return; }
-            g->shard_cap[d] = std::max<u64>(sh[d].off.back(), 1);
+        if (d) {
+            if (g->d_shard[d].capacity() < std::max<u64>(sh[d].off.back(), 1)) {
+                if (hipSetDevice(c->dev) != hipSuccess) { rc[d] = LZANI_ERR_DEVICE; return; }
+                if (!got(g->d_shard[d].alloc(sh[d].off.back()))) { rc[d] = LZANI_ERR_NOMEM; return; }
+            }
+            d_shard[d] = (int*)g->d_shard[d].get();
         }
         rc[d] = lzani_run_rows_device(c, (u32)sh[d].ref.size(), sh[d].ref.data(), sh[d].off.data(),
                                       query_ids ? sh[d].q.data() : nullptr, d_shard[d]);
@@ -410,11 +393,7 @@ int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_id
         for (u32 d = 0; d < nd && ret == LZANI_OK; ++d)
             if (sbase[d] != sh[d].base) ret = gfail(g, LZANI_ERR_STATE, "lzani_group_run_rows: gather plan and shards disagree");
         hipError_t e = ret == LZANI_OK ? hipSuccess : hipErrorInvalidValue;
-        if (e == hipSuccess && g->tab_cap < tab.size()) {
-            hipFree(g->d_tab); g->d_tab = nullptr; g->tab_cap = 0;
-            e = hipMalloc(&g->d_tab, tab.size() * 8);
-            if (e == hipSuccess) g->tab_cap = tab.size();
-        }
+        if (e == hipSuccess) e = g->d_tab.reserve(tab.size());
         unsigned long long* const d_tab = g->d_tab;
         if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c0->stream);
         if (e == hipSuccess) {
@@ -425,7 +404,7 @@ int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_id
         // the copy out: through two pinned staging buffers that take turns -- the device-to-host copy of one piece flies
         // while the host moves the piece before it into the caller's (pageable) buffer
         for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-            if (!g->h_stage[k]) e = hipHostMalloc((void**)&g->h_stage[k], GROUP_STAGE_BYTES, hipHostMallocDefault);
+            if (!g->h_stage[k]) e = g->h_stage[k].alloc(GROUP_STAGE_BYTES);
             if (e == hipSuccess && !g->ev_stage[k]) e = hipEventCreateWithFlags(&g->ev_stage[k], hipEventDisableTiming);
         }
         {

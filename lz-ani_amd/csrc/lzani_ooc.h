@@ -12,7 +12,8 @@
 //   trade places if B holds it, else one upload;
 //   then its query blocks: i itself first (its queries are in A), then the block B holds if it has pairs of these rows,
 //   then the others ascending; every block that B does not hold yet is one upload.
-// The halves keep their blocks from run to run; lzani_set_genomes empties them.
+// The halves keep their blocks from run to run; lzani_set_genomes starts a fresh GenomeSet (the context's `gs`, which owns
+// the host copy, the resident region and the upload staging) and so empties them.
 #pragma once
 
 namespace {
@@ -88,34 +89,34 @@ int plan_blocks_impl(u32 n, const u32* len, const Params& P, u64 limit, std::vec
 // k_kmers on the block's genomes only.  Timed into res_upload_ms.
 int ooc_upload(lzani_ctx* c, u32 b, int h)
 {
-    c->half_block[h] = -1;                                     // (until the upload is complete)
-    const u32 g0 = c->blk_first[b], g1 = c->blk_first[b + 1], cnt = g1 - g0, hg = c->half_genomes;
-    const u64 bases = c->h_codeoff[g1] - c->h_codeoff[g0];
+    c->gs.half_block[h] = -1;                                     // (until the upload is complete)
+    const u32 g0 = c->gs.blk_first[b], g1 = c->gs.blk_first[b + 1], cnt = g1 - g0, hg = c->gs.half_genomes;
+    const u64 bases = c->gs.h_codeoff[g1] - c->gs.h_codeoff[g0];
     std::vector<u64> tab((size_t)2 * hg, 0);
     std::vector<int> Ls((size_t)2 * hg, 0);                    // lengths, then the N flags k_pack sets
     int Lmax = 0;
     for (u32 g = g0; g < g1; ++g) {
-        tab[g - g0] = c->h_codeoff[g] - c->h_codeoff[g0];
-        tab[hg + g - g0] = (u64)h * c->half_words + (c->nmoff[g] - c->nmoff[g0]);
-        Ls[g - g0] = c->L[g];
-        Lmax = std::max(Lmax, c->L[g]);
+        tab[g - g0] = c->gs.h_codeoff[g] - c->gs.h_codeoff[g0];
+        tab[hg + g - g0] = (u64)h * c->gs.half_words + (c->gs.nmoff[g] - c->gs.nmoff[g0]);
+        Ls[g - g0] = c->gs.L[g];
+        Lmax = std::max(Lmax, c->gs.L[g]);
     }
     hipEvent_t ev[2] = {nullptr, nullptr};
     HIPCHK(c, hipEventCreate(&ev[0]));
     hipError_t e = hipEventCreate(&ev[1]);
     if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    if (e == hipSuccess && bases) e = hipMemcpyAsync(c->d_stage, c->h_codes.data() + c->h_codeoff[g0], bases, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_up_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_up_L, Ls.data(), Ls.size() * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && bases) e = hipMemcpyAsync(c->gs.d_stage, c->gs.h_codes.data() + c->gs.h_codeoff[g0], bases, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->gs.d_up_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->gs.d_up_L, Ls.data(), Ls.size() * 4, hipMemcpyHostToDevice, c->stream);
     const int Tb = ref_text_len(Lmax, c->P.mrd);
     const size_t maxblk = text_wordsN(Tb);
     for (u32 k0 = 0; e == hipSuccess && k0 < cnt; k0 += 32768) {   // gridDim.y is limited to 65535
         const u32 k = std::min<u32>(32768, cnt - k0);
         hipLaunchKernelGGL(k_pack, dim3((u32)((maxblk + 127) / 128), k), dim3(128), 0, c->stream,
-                           c->d_stage, c->d_up_tab + k0, c->d_t2, c->d_nm, c->d_up_tab + hg + k0, c->d_up_L + k0, c->d_up_L + hg + k0, c->P.mrd, k);
-        if (c->d_kmL) {
-            GenomeTab G{c->d_t2, c->d_nm, c->d_up_tab + hg + k0, c->d_up_L + k0, c->d_kmL, c->d_kmS, c->d_up_L + hg + k0};
-            hipLaunchKernelGGL(k_kmers, dim3((Tb + 255) / 256, k), dim3(256), 0, c->stream, G, c->d_kmL, c->d_kmS, c->P.mal, c->P.msl, c->P.mrd, Tb);
+                           c->gs.d_stage, c->gs.d_up_tab + k0, c->gs.tab.t2, c->gs.tab.nm, c->gs.d_up_tab + hg + k0, c->gs.d_up_L + k0, c->gs.d_up_L + hg + k0, c->P.mrd, k);
+        if (c->gs.tab.kmL) {
+            GenomeTab G{c->gs.tab.t2, c->gs.tab.nm, c->gs.d_up_tab + hg + k0, c->gs.d_up_L + k0, c->gs.tab.kmL, c->gs.tab.kmS, c->gs.d_up_L + hg + k0};
+            hipLaunchKernelGGL(k_kmers, dim3((Tb + 255) / 256, k), dim3(256), 0, c->stream, G, c->gs.tab.kmL, c->gs.tab.kmS, c->P.mal, c->P.msl, c->P.mrd, Tb);
         }
         e = hipGetLastError();
     }
@@ -126,38 +127,19 @@ int ooc_upload(lzani_ctx* c, u32 b, int h)
     hipEventDestroy(ev[0]);
     if (ev[1]) hipEventDestroy(ev[1]);
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE, std::string("block upload: ") + hipGetErrorString(e));
-    c->res_upload_ms += ms;
-    c->res_uploads += 1;
-    c->half_block[h] = (int)b;
+    c->res.upload_ms += ms;
+    c->res.uploads += 1;
+    c->gs.half_block[h] = (int)b;
     return LZANI_OK;
 }
 
-// A device buffer of a run that grows as its tiles need.
-struct GrowBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    GrowBuf() = default;
-    GrowBuf(const GrowBuf&) = delete;
-    GrowBuf& operator=(const GrowBuf&) = delete;
-    ~GrowBuf() { if (p) (void)hipFree(p); }
-    hipError_t need(size_t b)
-    {
-        if (b <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        const hipError_t e = hipMalloc(&p, b);
-        if (e == hipSuccess) bytes = b;
-        return e;
-    }
-};
-
-// The context's genome count and lengths are the tile's local table for the duration of one tile.
+// The genome set's count and lengths (gs.n / gs.L) are the tile's local table for the duration of one tile.
 struct LocalTable {
     lzani_ctx* c;
     u32 n_all;
     std::vector<int> L_all;
-    LocalTable(lzani_ctx* c_, std::vector<int>& L_loc) : c(c_), n_all(c_->n) { L_all.swap(c->L); c->L.swap(L_loc); c->n = (u32)c->L.size(); }
-    ~LocalTable() { c->L.swap(L_all); c->n = n_all; }
+    LocalTable(lzani_ctx* c_, std::vector<int>& L_loc) : c(c_), n_all(c_->gs.n) { L_all.swap(c->gs.L); c->gs.L.swap(L_loc); c->gs.n = (u32)c->gs.L.size(); }
+    ~LocalTable() { c->gs.L.swap(L_all); c->gs.n = n_all; }
 };
 
 // The tiled run: the contract of run_rows_impl, with the results written to d_out (device, caller's CSR order) and / or
@@ -165,24 +147,25 @@ struct LocalTable {
 int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
                    int* d_out, lzani_result* h_out, const RegionSink* rs)
 {
-    const u32 n = c->n;
+    const u32 n = c->gs.n;
     c->run = RunRecord{};
-    c->res_tiles = 0; c->res_uploads = 0; c->res_peak = 0; c->res_upload_ms = 0;
+    c->res = Residency{};
     if (n_rows == 0) return LZANI_OK;
     RowFacts rf;
     const int rc0 = check_rows(c, n_rows, ref_ids, row_off, query_ids, rf);
     if (rc0 || rf.n_pairs == 0) return rc0;
     HIPCHK(c, hipSetDevice(c->dev));
 
-    const u32 nb = (u32)c->blk_first.size() - 1;
+    const u32 nb = (u32)c->gs.blk_first.size() - 1;
     std::vector<u32> bof(n);
-    for (u32 b = 0; b < nb; ++b) std::fill(bof.begin() + c->blk_first[b], bof.begin() + c->blk_first[b + 1], b);
+    for (u32 b = 0; b < nb; ++b) std::fill(bof.begin() + c->gs.blk_first[b], bof.begin() + c->gs.blk_first[b + 1], b);
     std::vector<std::vector<u32>> rows_of(nb);
     for (u32 k = 0; k < n_rows; ++k) if (row_off[k + 1] > row_off[k]) rows_of[bof[ref_ids[k]]].push_back(k);
 
     RunRecord tot;
     u64 reg_done = 0;
-    GrowBuf d_res, d_pos;
+    DevMem<lzani_result> d_res;                            // grow as the tiles need
+    DevMem<u64> d_pos;
     std::vector<lzani_result> h_res;
     struct Tile { std::vector<u32> rows; std::vector<u64> off; std::vector<u32> q; std::vector<u64> pos; };
     std::vector<Tile> tiles(nb);
@@ -201,32 +184,32 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
             }
         }
         // block i into A
-        if (c->half_block[c->half_a] != (int)i) {
-            if (c->half_block[c->half_a ^ 1] == (int)i) c->half_a ^= 1;
-            else { int rc = ooc_upload(c, i, c->half_a); if (rc) return rc; }
+        if (c->gs.half_block[c->gs.half_a] != (int)i) {
+            if (c->gs.half_block[c->gs.half_a ^ 1] == (int)i) c->gs.half_a ^= 1;
+            else { int rc = ooc_upload(c, i, c->gs.half_a); if (rc) return rc; }
         }
         std::vector<u32> order;
         if (!tiles[i].q.empty()) order.push_back(i);
-        const int held = c->half_block[c->half_a ^ 1];
+        const int held = c->gs.half_block[c->gs.half_a ^ 1];
         if (held >= 0 && held != (int)i && !tiles[held].q.empty()) order.push_back((u32)held);
         for (u32 j = 0; j < nb; ++j) if (j != i && (int)j != held && !tiles[j].q.empty()) order.push_back(j);
         for (u32 j : order) {
-            const int hA = c->half_a, hB = c->half_a ^ 1;
-            if (j != i && c->half_block[hB] != (int)j) { int rc = ooc_upload(c, j, hB); if (rc) return rc; }
-            c->res_peak = std::max<u64>(c->res_peak, c->blk_bytes[i] + (c->half_block[hB] >= 0 ? c->blk_bytes[c->half_block[hB]] : 0));
+            const int hA = c->gs.half_a, hB = c->gs.half_a ^ 1;
+            if (j != i && c->gs.half_block[hB] != (int)j) { int rc = ooc_upload(c, j, hB); if (rc) return rc; }
+            c->res.peak = std::max<u64>(c->res.peak, c->gs.blk_bytes[i] + (c->gs.half_block[hB] >= 0 ? c->gs.blk_bytes[c->gs.half_block[hB]] : 0));
             Tile& t = tiles[j];
             // the local genome table: A's genomes, then B's (unless the queries are A's own)
-            const u32 a0 = c->blk_first[i], nA = c->blk_first[i + 1] - a0;
-            const u32 b0 = c->blk_first[j], nB = j == i ? 0 : c->blk_first[j + 1] - b0;
+            const u32 a0 = c->gs.blk_first[i], nA = c->gs.blk_first[i + 1] - a0;
+            const u32 b0 = c->gs.blk_first[j], nB = j == i ? 0 : c->gs.blk_first[j + 1] - b0;
             std::vector<int> Lloc((size_t)nA + nB), hasN((size_t)nA + nB);
             std::vector<u64> nmoff((size_t)nA + nB);
             for (u32 g = 0; g < nA; ++g) {
-                Lloc[g] = c->L[a0 + g]; hasN[g] = c->h_hasN[a0 + g];
-                nmoff[g] = (u64)hA * c->half_words + (c->nmoff[a0 + g] - c->nmoff[a0]);
+                Lloc[g] = c->gs.L[a0 + g]; hasN[g] = c->gs.h_hasN[a0 + g];
+                nmoff[g] = (u64)hA * c->gs.half_words + (c->gs.nmoff[a0 + g] - c->gs.nmoff[a0]);
             }
             for (u32 g = 0; g < nB; ++g) {
-                Lloc[nA + g] = c->L[b0 + g]; hasN[nA + g] = c->h_hasN[b0 + g];
-                nmoff[nA + g] = (u64)hB * c->half_words + (c->nmoff[b0 + g] - c->nmoff[b0]);
+                Lloc[nA + g] = c->gs.L[b0 + g]; hasN[nA + g] = c->gs.h_hasN[b0 + g];
+                nmoff[nA + g] = (u64)hB * c->gs.half_words + (c->gs.nmoff[b0 + g] - c->gs.nmoff[b0]);
             }
             const u32 lrows = (u32)t.rows.size();
             const u64 tp = t.q.size();
@@ -234,32 +217,32 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
             t.off.push_back(tp);
             for (u32 k = 0; k < lrows; ++k) lref[k] = ref_ids[t.rows[k]] - a0;
             for (u64 e = 0; e < tp; ++e) lq[e] = j == i ? t.q[e] - a0 : nA + (t.q[e] - b0);
-            HIPCHK(c, hipMemcpyAsync(c->d_L, Lloc.data(), Lloc.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_hasN, hasN.data(), hasN.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_nmoff, nmoff.data(), nmoff.size() * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, d_res.need(tp * sizeof(lzani_result)));
+            HIPCHK(c, hipMemcpyAsync(c->gs.tab.L, Lloc.data(), Lloc.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->gs.tab.hasN, hasN.data(), hasN.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->gs.tab.nmoff, nmoff.data(), nmoff.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, d_res.reserve(tp));
             if (d_out || rs) {
-                HIPCHK(c, d_pos.need(tp * 8));
-                HIPCHK(c, hipMemcpyAsync(d_pos.p, t.pos.data(), tp * 8, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, d_pos.reserve(tp));
+                HIPCHK(c, hipMemcpyAsync(d_pos.get(), t.pos.data(), tp * 8, hipMemcpyHostToDevice, c->stream));
             }
             HIPCHK(c, hipStreamSynchronize(c->stream));            // (Lloc moves into the context below)
-            if (c->join_mode) free_join_lists(c);                   // (made again for this tile's table, if its form needs them)
+            if (c->gs.join_mode) c->gs.jl = JoinLists{};                   // (made again for this tile's table, if its form needs them)
             int rc;
             {
                 LocalTable lt(c, Lloc);
-                rc = run_rows_impl(c, lrows, lref.data(), t.off.data(), lq.data(), (int*)d_res.p, rs);
-                if (c->join_mode) free_join_lists(c);
+                rc = run_rows_impl(c, lrows, lref.data(), t.off.data(), lq.data(), (int*)d_res.get(), rs);
+                if (c->gs.join_mode) c->gs.jl = JoinLists{};
             }
             if (rc) return rc;
-            c->res_tiles += 1;
+            c->res.tiles += 1;
             tot += c->run;
             if (d_out) {
-                hipLaunchKernelGGL(k_scatter_pairs, dim3((u32)((tp + 255) / 256)), dim3(256), 0, c->stream, (const int*)d_res.p, d_out, (const u64*)d_pos.p, tp);
+                hipLaunchKernelGGL(k_scatter_pairs, dim3((u32)((tp + 255) / 256)), dim3(256), 0, c->stream, (const int*)d_res.get(), d_out, d_pos.get(), tp);
                 HIPCHK(c, hipGetLastError());
             }
             if (h_out) {
                 h_res.resize(tp);
-                HIPCHK(c, hipMemcpyAsync(h_res.data(), d_res.p, tp * sizeof(lzani_result), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipMemcpyAsync(h_res.data(), d_res.get(), tp * sizeof(lzani_result), hipMemcpyDeviceToHost, c->stream));
             }
             if (rs) {
                 unsigned long long cnt = 0;
@@ -267,7 +250,7 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 const u64 lo = std::min<u64>(reg_done, rs->capacity), hi = std::min<u64>(cnt, rs->capacity);
                 if (hi > lo) {
-                    hipLaunchKernelGGL(k_remap_regions, dim3((u32)((hi - lo + 255) / 256)), dim3(256), 0, c->stream, rs->d_regions + lo, hi - lo, (const u64*)d_pos.p);
+                    hipLaunchKernelGGL(k_remap_regions, dim3((u32)((hi - lo + 255) / 256)), dim3(256), 0, c->stream, rs->d_regions + lo, hi - lo, d_pos.get());
                     HIPCHK(c, hipGetLastError());
                 }
                 reg_done = cnt;
@@ -277,7 +260,7 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
         }
     }
     c->run = tot;
-    TRACE("out-of-core run: %u tiles, %llu block uploads (%.1f ms)", c->res_tiles, (unsigned long long)c->res_uploads, c->res_upload_ms);
+    TRACE("out-of-core run: %u tiles, %llu block uploads (%.1f ms)", c->res.tiles, (unsigned long long)c->res.uploads, c->res.upload_ms);
     return LZANI_OK;
 }
 
@@ -285,45 +268,51 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
 // two halves; the blocks are uploaded by the runs.
 int ooc_set_genomes(lzani_ctx* c, u32 n, const uint8_t* const* codes, const uint32_t* len)
 {
-    const u32 nb = (u32)c->blk_first.size() - 1;
+    const u32 nb = (u32)c->gs.blk_first.size() - 1;
     try {
-        c->h_codeoff.assign((size_t)n + 1, 0);
-        for (u32 g = 0; g < n; ++g) c->h_codeoff[g + 1] = c->h_codeoff[g] + len[g];
-        c->h_codes.resize(c->h_codeoff[n]);
-        c->h_hasN.assign(n, 0);
+        c->gs.h_codeoff.assign((size_t)n + 1, 0);
+        for (u32 g = 0; g < n; ++g) c->gs.h_codeoff[g + 1] = c->gs.h_codeoff[g] + len[g];
+        c->gs.h_codes.resize(c->gs.h_codeoff[n]);
+        c->gs.h_hasN.assign(n, 0);
     } catch (const std::bad_alloc&) {
         return fail(c, LZANI_ERR_NOMEM, "lzani_set_genomes: host copy of an out-of-core genome set");
     }
     for (u32 g = 0; g < n; ++g) {
-        if (len[g]) memcpy(c->h_codes.data() + c->h_codeoff[g], codes[g], len[g]);
-        c->h_hasN[g] = std::any_of(codes[g], codes[g] + len[g], [](uint8_t v) { return v >= 4; });
+        if (len[g]) memcpy(c->gs.h_codes.data() + c->gs.h_codeoff[g], codes[g], len[g]);
+        c->gs.h_hasN[g] = std::any_of(codes[g], codes[g] + len[g], [](uint8_t v) { return v >= 4; });
     }
-    c->all_nfree = std::none_of(c->h_hasN.begin(), c->h_hasN.end(), [](int v) { return v != 0; });
+    c->gs.all_nfree = std::none_of(c->gs.h_hasN.begin(), c->gs.h_hasN.end(), [](int v) { return v != 0; });
     u64 max_bases = 0;
     for (u32 b = 0; b < nb; ++b) {
-        const u32 g0 = c->blk_first[b], g1 = c->blk_first[b + 1];
-        c->half_words = std::max<u64>(c->half_words, (g1 < n ? c->nmoff[g1] : c->total_nm) - c->nmoff[g0]);
-        c->half_genomes = std::max<u32>(c->half_genomes, g1 - g0);
-        max_bases = std::max<u64>(max_bases, c->h_codeoff[g1] - c->h_codeoff[g0]);
+        const u32 g0 = c->gs.blk_first[b], g1 = c->gs.blk_first[b + 1];
+        c->gs.half_words = std::max<u64>(c->gs.half_words, (g1 < n ? c->gs.nmoff[g1] : c->gs.total_nm) - c->gs.nmoff[g0]);
+        c->gs.half_genomes = std::max<u32>(c->gs.half_genomes, g1 - g0);
+        max_bases = std::max<u64>(max_bases, c->gs.h_codeoff[g1] - c->gs.h_codeoff[g0]);
     }
-    const u64 hw = c->half_words, hg = c->half_genomes;
-    HIPCHK(c, hipMalloc(&c->d_t2, 2 * hw * 16));
-    HIPCHK(c, hipMalloc(&c->d_nm, 2 * hw * 8));
+    const u64 hw = c->gs.half_words, hg = c->gs.half_genomes;
+    GenomeTables t;                                               // (moved into the set whole, or not at all)
+    DevMem<uint8_t> stage;
+    DevMem<u64> up_tab;
+    DevMem<int> up_L;
+    HIPCHK(c, t.t2.alloc(2 * hw * 2));
+    HIPCHK(c, t.nm.alloc(2 * hw));
     if (kmer_words_of(c->P)) {
-        HIPCHK(c, hipMalloc(&c->d_kmL, 2 * hw * 64 * 4));
-        HIPCHK(c, hipMalloc(&c->d_kmS, 2 * hw * 64 * 4));
+        HIPCHK(c, t.kmL.alloc(2 * hw * 64));
+        HIPCHK(c, t.kmS.alloc(2 * hw * 64));
     }
-    HIPCHK(c, hipMalloc(&c->d_nmoff, 2 * hg * 8));
-    HIPCHK(c, hipMalloc(&c->d_L, 2 * hg * 4));
-    HIPCHK(c, hipMalloc(&c->d_hasN, 2 * hg * 4));
-    HIPCHK(c, hipMalloc(&c->d_stage, std::max<u64>(max_bases, 1)));
-    HIPCHK(c, hipMalloc(&c->d_up_tab, 2 * hg * 8));
-    HIPCHK(c, hipMalloc(&c->d_up_L, 2 * hg * 4));
-    c->total_nm = 2 * hw;                                          // (lzani_get_layout: the resident region's bytes)
-    c->kmers_ready = true;                                         // (made by every block upload)
-    c->ooc = true;
-    c->n = n;
-    TRACE("set_genomes: out-of-core, n=%u blocks=%u limit=%llu half=%llu words", n, nb, (unsigned long long)c->mem_limit, (unsigned long long)hw);
+    HIPCHK(c, t.nmoff.alloc(2 * hg));
+    HIPCHK(c, t.L.alloc(2 * hg));
+    HIPCHK(c, t.hasN.alloc(2 * hg));
+    HIPCHK(c, stage.alloc(max_bases));
+    HIPCHK(c, up_tab.alloc(2 * hg));
+    HIPCHK(c, up_L.alloc(2 * hg));
+    c->gs.tab = std::move(t);
+    c->gs.d_stage = std::move(stage); c->gs.d_up_tab = std::move(up_tab); c->gs.d_up_L = std::move(up_L);
+    c->gs.total_nm = 2 * hw;                                          // (lzani_get_layout: the resident region's bytes)
+    c->gs.kmers_ready = true;                                         // (made by every block upload)
+    c->gs.ooc = true;
+    c->gs.n = n;
+    TRACE("set_genomes: out-of-core, n=%u blocks=%u limit=%llu half=%llu words", n, nb, (unsigned long long)c->gs.mem_limit, (unsigned long long)hw);
     return LZANI_OK;
 }
 
