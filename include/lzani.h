@@ -209,6 +209,37 @@ int64_t lzani_debug_rtc_compile(const lzani_params *p, int nfree, int cand, cons
 int lzani_debug_kernel_launches(const lzani_ctx *ctx, uint64_t *counts, uint32_t cap);
 const char *lzani_debug_kernel_name(uint32_t id);
 
+/* ---- K-mer prefilter: the filter rows without a kmer-db file --------------------------------------------
+ * The reference takes its filtered rows from a text file written by kmer-db (CFilter::load_filter).  This stage makes
+ * them from the resident genome set: the number of shared canonical k-mers of every unordered genome pair, and the
+ * pairs that pass a threshold.  Exact integer arithmetic, 8 <= k <= 31:
+ *   window value   v(p) = sum over j < k of code[p + j] * 4^j (first symbol least significant), defined where no
+ *                  symbol of the window is N; rc(p) is the same sum over the window's reverse complement
+ *   canonical      canon(p) = min(v(p), rc(p))
+ *   sampling       a canonical k-mer x is kept iff splitmix64(x) <= sample_max (UINT64_MAX keeps all), with
+ *                  x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB;
+ *                  x ^= x >> 31  (mod 2^64)
+ *   K(g)           the set of kept canonical k-mers of genome g; shared(a, b) = |K(a) & K(b)|
+ *   kept pairs     a < b with shared >= max(min_shared, 1) and (double)shared / (double)min(|K(a)|, |K(b)|) >= min_ratio
+ * The kept windows of the whole set must number fewer than 2^32 (else LZANI_ERR_ARG: lower sample_max).  The count
+ * matrix is worked in tiles of rows sized by a workspace budget (half of the free device memory;
+ * LZANI_PREFILTER_TILE_ROWS=<rows> forces the tile height).  The genome tables, k-mer words, index slabs and compiled
+ * kernels of the context are left as they are.  Out-of-core genome sets (lzani_set_genome_memory) are out of scope:
+ * LZANI_ERR_STATE.  LZANI_ERR_NOMEM where the workspace does not fit; the context then holds no prefilter result and
+ * is otherwise unchanged. */
+typedef struct lzani_prefilter_info {
+    int32_t  k; uint32_t tiles;                                /* tiles: row tiles of the count matrix                */
+    uint64_t positions, distinct_kmers, postings, entries;     /* valid sampled windows, distinct k-mers, (k-mer, genome) pairs, kept pairs */
+    double   keys_ms, sort_ms, count_ms, compact_ms;           /* HIP events on the context's stream: k-mer extraction; the two
+                                                                * sorts with dictionary and postings; the count matrix; the kept
+                                                                * entries of its rows                                  */
+} lzani_prefilter_info;
+/* Runs the stage on the resident genome set; results stay in the context until the next prefilter / set_genomes. */
+int lzani_prefilter(lzani_ctx *ctx, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint64_t *n_entries);
+/* kmers_of[n] = |K(g)|; row_off[n+1], ids[], shared[]: CSR of the kept pairs a < b (row a, ids ascending).  Any may be NULL. */
+int lzani_prefilter_fetch(lzani_ctx *ctx, uint32_t *kmers_of, uint64_t *row_off, uint32_t *ids, uint32_t *shared);
+int lzani_get_prefilter_info(const lzani_ctx *ctx, lzani_prefilter_info *info);
+
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
  * takes a reference, builds its index once and parses every query of the row).  Rows are independent; the

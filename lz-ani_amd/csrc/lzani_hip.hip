@@ -4,6 +4,7 @@
 //   lzani_kernels_index.h   k_pack, k_kmers, k_idx_*   genomes -> packed texts, k-mer words, anchor indexes
 //   lzani_kernels_cand.h    k_pm_build, k_pm_cand   dense rows: presence matrix of a group of references -> per-pair candidate bitmaps
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
+//   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.
 #include <hip/hip_runtime.h>
@@ -47,6 +48,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_kernels_cand.h"
 #include "lzani_kernels_pairs.h"
 #include "lzani_kernels_split.h"
+#include "lzani_kernels_prefilter.h"
 #include "lzani_rtc.h"
 #include "lzani_devmem.h"
 
@@ -242,6 +244,34 @@ struct CandScratch {
     DevMem<unsigned long long> d_lpt_keys;        // ... then the ticket keys unsorted / sorted (two per pair)
 };
 
+// The k-mer prefilter (lzani_prefilter, lzani_kernels_prefilter.h): lzani_set_genomes -> the next one.  The results stay
+// until the next prefilter; the workspace is released when the stage ends.
+struct PrefilterTile {
+    u32 r0 = 0, r1 = 0;           // rows of the count matrix the tile held
+    DevMem<u32> ids, shared;      // the kept entries of those rows, row after row
+};
+struct PrefilterWork {
+    DevMem<u64> cbase;            // per genome: number of its first chunk of PF_CHUNK forward positions (n + 1)
+    DevMem<u32> blkcnt;           // per chunk: windows kept
+    DevMem<u64> blkoff;           // ... their exclusive prefix: where a chunk's keys go, in both key passes
+    DevMem<u32> ucnt;             // per PF_CHUNK elements of a sorted array: elements that differ from their predecessor
+    DevMem<u64> uoff;
+    DevMem<unsigned long long> ka, kb;            // keys, sorted keys / dictionary, rank keys / postings, in turn
+    DevMem<unsigned char> tmp;    // radix-sort scratch
+    DevMem<u32> runoff;           // per rank: its first posting (distinct k-mers + 1)
+    DevMem<u32> mat;              // one row tile of the count matrix, rows x n
+    DevMem<u32> rowcnt;
+    DevMem<u64> rowoff;
+};
+struct Prefilter {
+    bool done = false;
+    lzani_prefilter_info info{};
+    DevMem<u32> kmers_of;                 // |K(g)|
+    std::vector<u64> row_off;             // CSR of the kept pairs (n + 1)
+    std::vector<PrefilterTile> tiles;     // in row order
+    PrefilterWork work;
+};
+
 // Residency counters of the last run (lzani_get_residency).
 struct Residency { u32 tiles = 0; u64 uploads = 0, peak = 0; double upload_ms = 0; };
 
@@ -271,6 +301,7 @@ struct lzani_ctx {
     GenomeSet gs;
     IndexSlabs sl;
     CandScratch cs;
+    Prefilter pf;
     // the last run
     RunRecord run;
     Residency res;
@@ -1438,6 +1469,206 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
 
 #include "lzani_ooc.h"
 
+namespace {
+
+// Device time of the prefilter's four stages: pairs of events on the context's stream, summed per stage at the end.
+struct PfClock {
+    hipStream_t stream;
+    std::vector<hipEvent_t> ev;           // begin, end, begin, end, ...
+    std::vector<int> stage;
+    explicit PfClock(hipStream_t s) : stream(s) {}
+    PfClock(const PfClock&) = delete;
+    PfClock& operator=(const PfClock&) = delete;
+    ~PfClock() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t mark()
+    {
+        hipEvent_t e = nullptr;
+        hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+        ev.push_back(e);
+        return hipEventRecord(e, stream);
+    }
+    hipError_t begin(int st) { stage.push_back(st); return mark(); }
+    hipError_t end() { return mark(); }
+    hipError_t collect(double ms[4])
+    {
+        for (size_t k = 0; k + 1 < ev.size(); k += 2) {
+            float t = 0;
+            hipError_t rc = hipEventSynchronize(ev[k + 1]);
+            if (rc == hipSuccess) rc = hipEventElapsedTime(&t, ev[k], ev[k + 1]);
+            if (rc != hipSuccess) return rc;
+            ms[stage[k / 2]] += t;
+        }
+        return hipSuccess;
+    }
+};
+enum { PF_ST_KEYS = 0, PF_ST_SORT = 1, PF_ST_COUNT = 2, PF_ST_COMPACT = 3 };
+
+int pf_sort(lzani_ctx* c, PrefilterWork& w, const unsigned long long* in, unsigned long long* out, size_t n, int b0, int b1)
+{
+    size_t need = w.tmp.capacity();
+    const int e = lzani_sort_keys(in, out, n, b0, b1, w.tmp, &need, c->stream);
+    if (e != 0) return fail(c, LZANI_ERR_DEVICE, std::string("lzani_prefilter: sort: ") + hipGetErrorString((hipError_t)e));
+    return LZANI_OK;
+}
+
+// The stage itself: fills pf (a fresh Prefilter) from the resident genome set.
+int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_shared, double min_ratio)
+{
+    const u32 n = c->gs.n;
+    PrefilterWork& w = pf.work;
+    lzani_prefilter_info& info = pf.info;
+    info.k = k;
+    min_shared = std::max<u32>(min_shared, 1);
+    PfClock clk(c->stream);
+    const GenomeTab G = gtab(c);
+
+    // chunks of PF_CHUNK forward positions, genome after genome
+    std::vector<u64> cbase((size_t)n + 1, 0);
+    int Lmax = 0;
+    for (u32 g = 0; g < n; ++g) {
+        cbase[g + 1] = cbase[g] + ((u64)c->gs.L[g] + PF_CHUNK - 1) / PF_CHUNK;
+        Lmax = std::max(Lmax, c->gs.L[g]);
+    }
+    const u64 n_chunks = cbase[n];
+    const u32 gx = (u32)(((u64)Lmax + PF_CHUNK - 1) / PF_CHUNK);
+    HIPCHK(c, w.cbase.alloc((size_t)n + 1));
+    HIPCHK(c, w.blkcnt.alloc(n_chunks));
+    HIPCHK(c, w.blkoff.alloc(n_chunks + 1));
+    HIPCHK(c, pf.kmers_of.alloc(n));
+    HIPCHK(c, hipMemcpyAsync(w.cbase, cbase.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(pf.kmers_of, 0, (size_t)n * 4, c->stream));
+    pf.row_off.assign((size_t)n + 1, 0);
+
+    // gridDim.y is limited to 65535: slices of genomes
+    auto keys = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) {
+        for (u32 g0 = 0; gx && g0 < n; g0 += 32768) {
+            const dim3 gd(gx, std::min<u32>(32768, n - g0));
+            if (mode == PF_COUNT) hipLaunchKernelGGL(k_pf_keys<PF_COUNT>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+            else if (mode == PF_CANON) hipLaunchKernelGGL(k_pf_keys<PF_CANON>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+            else hipLaunchKernelGGL(k_pf_keys<PF_RANK>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+        }
+    };
+    // the total of a scan, read back
+    auto scan_total = [&](const u32* cnt, u64 cnt_n, u64* off, u64& total) -> int {
+        hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, cnt, cnt_n, off);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&total, off + cnt_n, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return LZANI_OK;
+    };
+    // in[0 .. cnt) ascending -> out without adjacent duplicates; their number
+    auto uniq = [&](const unsigned long long* in, u64 cnt, unsigned long long* out, u32* per_genome, u64& n_out) -> int {
+        const u32 blocks = (u32)((cnt + PF_CHUNK - 1) / PF_CHUNK);
+        hipLaunchKernelGGL(k_pf_uniq<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, in, cnt, w.ucnt.get(), w.uoff.get(), out, per_genome, n);
+        if (int rc = scan_total(w.ucnt, blocks, w.uoff, n_out)) return rc;
+        hipLaunchKernelGGL(k_pf_uniq<true>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, in, cnt, w.ucnt.get(), w.uoff.get(), out, per_genome, n);
+        HIPCHK(c, hipGetLastError());
+        return LZANI_OK;
+    };
+
+    // ---- keys: the kept windows counted, then their canonical k-mers in position order
+    u64 Pv = 0;
+    HIPCHK(c, clk.begin(PF_ST_KEYS));
+    keys(PF_COUNT, nullptr, 0, nullptr);
+    if (int rc = scan_total(w.blkcnt, n_chunks, w.blkoff, Pv)) return rc;
+    HIPCHK(c, clk.end());
+    if (Pv >= 0xFFFFFFF0ull)
+        return fail(c, LZANI_ERR_ARG, "lzani_prefilter: " + std::to_string(Pv) + " sampled k-mer windows; the stage holds fewer than 2^32: lower sample_max");
+    info.positions = Pv;
+    u64 D = 0, M = 0;
+    if (Pv) {
+        HIPCHK(c, w.ka.alloc(Pv));
+        HIPCHK(c, w.kb.alloc(Pv));
+        HIPCHK(c, w.ucnt.alloc((Pv + PF_CHUNK - 1) / PF_CHUNK));
+        HIPCHK(c, w.uoff.alloc((Pv + PF_CHUNK - 1) / PF_CHUNK + 1));
+        {
+            size_t need1 = 0, need2 = 0;
+            if (lzani_sort_keys(w.ka, w.kb, Pv, 0, 2 * k, nullptr, &need1, c->stream) != 0 || lzani_sort_keys(w.kb, w.ka, Pv, 32, 64, nullptr, &need2, c->stream) != 0)
+                return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
+            HIPCHK(c, w.tmp.alloc(std::max(need1, need2)));
+        }
+        HIPCHK(c, clk.begin(PF_ST_KEYS));
+        keys(PF_CANON, nullptr, 0, w.ka.get());
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.end());
+        // ---- dictionary: the keys sorted, every distinct k-mer once; its place is its rank
+        HIPCHK(c, clk.begin(PF_ST_SORT));
+        if (int rc = pf_sort(c, w, w.ka, w.kb, Pv, 0, 2 * k)) return rc;
+        if (int rc = uniq(w.kb, Pv, w.ka, nullptr, D)) return rc;
+        HIPCHK(c, clk.end());
+        // ---- postings: rank << 32 | genome of every kept window, in genome order; a stable sort by rank leaves the genomes of
+        // a rank ascending; adjacent duplicates dropped, a run of equal rank lists the genomes that hold the k-mer
+        HIPCHK(c, clk.begin(PF_ST_KEYS));
+        keys(PF_RANK, w.ka.get(), D, w.kb.get());
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.end());
+        HIPCHK(c, clk.begin(PF_ST_SORT));
+        if (int rc = pf_sort(c, w, w.kb, w.ka, Pv, 32, 32 + ceil_log2(D))) return rc;
+        if (int rc = uniq(w.ka, Pv, w.kb, pf.kmers_of.get(), M)) return rc;
+        HIPCHK(c, w.runoff.alloc(D + 1));
+        hipLaunchKernelGGL(k_pf_runs, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.end());
+        w.ka.reset();                                          // (the count matrix may use the room)
+        w.tmp.reset();
+    }
+    info.distinct_kmers = D;
+    info.postings = M;
+
+    // ---- count matrix, a tile of rows at a time over the same postings, and the kept entries of its rows
+    u64 entries = 0;
+    if (M && n > 1) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        u64 rows = std::min<u64>(n, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n)));
+        if (const auto forced = env_u64("LZANI_PREFILTER_TILE_ROWS")) rows = std::min<u64>(n, std::max<u64>(1, *forced));
+        HIPCHK(c, w.mat.alloc(rows * n));
+        HIPCHK(c, w.rowcnt.alloc(rows));
+        HIPCHK(c, w.rowoff.alloc(rows + 1));
+        std::vector<u64> h_off(rows + 1);
+        const u32 count_blocks = (u32)((M + PF_THREADS - 1) / PF_THREADS);
+        for (u64 t0 = 0; t0 < n; t0 += rows) {
+            const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n, t0 + rows), nr = r1 - r0;
+            const u32 row_blocks = (nr + PF_THREADS / 64 - 1) / (PF_THREADS / 64);
+            HIPCHK(c, clk.begin(PF_ST_COUNT));
+            HIPCHK(c, hipMemsetAsync(w.mat, 0, (size_t)nr * n * 4, c->stream));
+            hipLaunchKernelGGL(k_pf_count, dim3(count_blocks), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D, n, r0, r1, w.mat.get());
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, clk.end());
+            HIPCHK(c, clk.begin(PF_ST_COMPACT));
+            hipLaunchKernelGGL(k_pf_rows<false>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
+                               w.rowcnt.get(), w.rowoff.get(), (u32*)nullptr, (u32*)nullptr);
+            hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, w.rowcnt.get(), (u64)nr, w.rowoff.get());
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            PrefilterTile tile;
+            tile.r0 = r0; tile.r1 = r1;
+            HIPCHK(c, tile.ids.alloc(h_off[nr]));
+            HIPCHK(c, tile.shared.alloc(h_off[nr]));
+            hipLaunchKernelGGL(k_pf_rows<true>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
+                               w.rowcnt.get(), w.rowoff.get(), tile.ids.get(), tile.shared.get());
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, clk.end());
+            for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = entries + h_off[r + 1];
+            entries += h_off[nr];
+            pf.tiles.push_back(std::move(tile));
+            ++info.tiles;
+        }
+    }
+    info.entries = entries;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double ms[4] = {0, 0, 0, 0};
+    HIPCHK(c, clk.collect(ms));
+    info.keys_ms = ms[PF_ST_KEYS]; info.sort_ms = ms[PF_ST_SORT]; info.count_ms = ms[PF_ST_COUNT]; info.compact_ms = ms[PF_ST_COMPACT];
+    TRACE("prefilter: k=%d positions=%llu distinct=%llu postings=%llu entries=%llu tiles=%u", k, (unsigned long long)Pv, (unsigned long long)D,
+          (unsigned long long)M, (unsigned long long)entries, info.tiles);
+    return LZANI_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 static void comm_release(lzani_ctx* c);      // lzani_multi.h
@@ -1496,6 +1727,7 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     c->gs = GenomeSet{};
     c->sl = IndexSlabs{};
     c->cs = CandScratch{};
+    c->pf = Prefilter{};
     c->res = Residency{};
     c->gs.L.resize(n);
     c->gs.nmoff.resize(n);
@@ -1900,6 +2132,56 @@ int lzani_debug_run_candidates(lzani_ctx* c, uint32_t n_rows, const uint32_t* re
     plan->from_index_launches = (uint32_t)c->run.pmfi_launches;
     plan->cand_launches = (uint32_t)c->run.pmc_launches;
     plan->counted_batches = sink.counted_batches;
+    return LZANI_OK;
+}
+
+
+int lzani_prefilter(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint64_t* n_entries)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (!c->gs.n) return fail(c, LZANI_ERR_STATE, "lzani_prefilter: no genomes (call lzani_set_genomes first)");
+    if (c->gs.ooc) return fail(c, LZANI_ERR_STATE, "lzani_prefilter: the genome set is out-of-core; the prefilter needs it resident");
+    if (k < 8 || k > 31) return fail(c, LZANI_ERR_ARG, "lzani_prefilter: k must be 8 .. 31");
+    if (!(min_ratio >= 0)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter: min_ratio must be a number >= 0");
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->pf = Prefilter{};                                       // the last result goes first: two need not fit
+    Prefilter pf;
+    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio);
+    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }     // (pf releases what it held)
+    pf.work = PrefilterWork{};
+    pf.done = true;
+    c->pf = std::move(pf);
+    if (n_entries) *n_entries = c->pf.info.entries;
+    return LZANI_OK;
+}
+
+int lzani_prefilter_fetch(lzani_ctx* c, uint32_t* kmers_of, uint64_t* row_off, uint32_t* ids, uint32_t* shared)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (!c->pf.done) return fail(c, LZANI_ERR_STATE, "lzani_prefilter_fetch: no prefilter result (call lzani_prefilter first)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    const Prefilter& pf = c->pf;
+    const u32 n = c->gs.n;
+    // everything into buffers of our own first: the caller's are written only on success
+    std::vector<u32> h_k(kmers_of ? n : 0), h_ids(ids ? pf.info.entries : 0), h_sh(shared ? pf.info.entries : 0);
+    if (kmers_of) HIPCHK(c, hipMemcpy(h_k.data(), pf.kmers_of, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (const PrefilterTile& t : pf.tiles) {
+        const u64 at = pf.row_off[t.r0], cnt = pf.row_off[t.r1] - at;
+        if (!cnt) continue;
+        if (ids) HIPCHK(c, hipMemcpy(h_ids.data() + at, t.ids, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+        if (shared) HIPCHK(c, hipMemcpy(h_sh.data() + at, t.shared, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    }
+    if (kmers_of) memcpy(kmers_of, h_k.data(), h_k.size() * 4);
+    if (row_off) memcpy(row_off, pf.row_off.data(), pf.row_off.size() * 8);
+    if (ids && !h_ids.empty()) memcpy(ids, h_ids.data(), h_ids.size() * 4);
+    if (shared && !h_sh.empty()) memcpy(shared, h_sh.data(), h_sh.size() * 4);
+    return LZANI_OK;
+}
+
+int lzani_get_prefilter_info(const lzani_ctx* c, lzani_prefilter_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    *info = c->pf.info;
     return LZANI_OK;
 }
 

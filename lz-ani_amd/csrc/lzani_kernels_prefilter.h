@@ -1,0 +1,254 @@
+// lzani_kernels_prefilter.h -- device kernels of the k-mer prefilter (lzani_prefilter): the shared canonical k-mer count
+// of every genome pair of the resident set, i.e. what the reference's CFilter::load_filter reads from a kmer-db file.
+// Included by lzani_hip.hip only (after lzani_tables.h).  Exact integer work:
+//   k_pf_keys     one thread per forward position: canonical, sampled k-mer (pf_canon / pf_keep over kmer_at of both
+//                 strands) -- counted per block, then written compacted in position order; a third pass writes
+//                 rank << 32 | genome  with the k-mer's rank found in the sorted dictionary
+//   k_pf_uniq     a sorted array without its adjacent duplicates (counted per block, then written): the dictionary of
+//                 distinct k-mers from the sorted keys, the postings from the sorted (rank, genome) keys
+//   k_pf_scan     exclusive prefix of per-block / per-row counts (one block; the arrays are 1/4096 of the data)
+//   k_pf_runs     where the postings of every rank begin
+//   k_pf_count    a wave per 64 postings: for every posting (rank, a) of the row tile, one atomic add to count[a][b] per
+//                 later posting (rank, b) of the same run, the lanes side by side over b
+//   k_pf_rows     a wave per matrix row: the kept entries counted, then written in ascending b
+// No kernel waits for another block.  The sorts between them are lzani_sort_keys (lzani_sort.hip).
+#pragma once
+#include "lzani_prefilter_defs.h"
+
+namespace lzani {
+
+enum { PF_THREADS = 256, PF_PER_THREAD = 16, PF_CHUNK = PF_THREADS * PF_PER_THREAD };
+enum { PF_COUNT = 0, PF_CANON = 1, PF_RANK = 2 };
+
+// Among the block's PF_THREADS threads: how many threads before this one raise `flag`; total: how many in all.
+__device__ __forceinline__ u32 pf_block_rank(bool flag, u32* s_w, u32& total)
+{
+    const u64 m = __builtin_amdgcn_ballot_w64(flag);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) s_w[wv] = (u32)__popcll(m);
+    __syncthreads();
+    u32 off = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < PF_THREADS / 64; ++k) { const u32 c = s_w[k]; off += k < wv ? c : 0u; tot += c; }
+    __syncthreads();
+    total = tot;
+    return off + (u32)__popcll(m & ((1ULL << lane) - 1ULL));
+}
+
+// The canonical k-mer of the window at forward position p of genome g, if the window exists, holds no N and is sampled.
+__device__ __forceinline__ bool pf_key_at(const GenomeTab& G, u32 g, int L, int p, int k, int mrd, u64 sample_max, u64& key)
+{
+    if (p > L - k) return false;
+    const u64 o = G.nmoff[g];
+    const TextView R = ref_view(G.t2 + 2 * o, G.nm + o, L, mrd, false);
+    u64 f, r;
+    if (!kmer_at(R, p, k, f) || !kmer_at(R, R.rc0 + L - p - k, k, r)) return false;
+    key = pf_canon(f, r);
+    return pf_keep(key, sample_max);
+}
+
+// index of key in the ascending dictionary (it is there)
+__device__ __forceinline__ u32 pf_find(const unsigned long long* __restrict__ dict, u64 D, u64 key)
+{
+    u64 lo = 0, hi = D;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (dict[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return (u32)lo;
+}
+
+// Block (x, y) = chunk x of PF_CHUNK forward positions of genome g0 + y; its number in the count / offset arrays is
+// cbase[g] + x.  COUNT: blkcnt[block] = kept windows.  CANON / RANK: they are written from blkoff[block] on, in position
+// order -- the canonical k-mer, or  rank in dict << 32 | genome.
+template <int MODE>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_keys(GenomeTab G, const u64* __restrict__ cbase, u32 g0, int k, int mrd, u64 sample_max,
+                                                        u32* __restrict__ blkcnt, const u64* __restrict__ blkoff,
+                                                        const unsigned long long* __restrict__ dict, u64 D, unsigned long long* __restrict__ out)
+{
+    __shared__ u32 s_w[PF_THREADS / 64];
+    __shared__ u32 s_cnt;
+    const u32 g = g0 + blockIdx.y;
+    const int L = G.L[g];
+    const u64 chunk0 = (u64)blockIdx.x * PF_CHUNK;
+    if (chunk0 >= (u64)L) return;
+    const u64 blk = cbase[g] + blockIdx.x;
+    u64 base = MODE == PF_COUNT ? 0 : blkoff[blk];
+    u32 mine = 0;
+    if (MODE == PF_COUNT) { if (threadIdx.x == 0) s_cnt = 0; __syncthreads(); }
+    for (int it = 0; it < PF_PER_THREAD; ++it) {
+        if (chunk0 + (u64)it * PF_THREADS >= (u64)L) break;              // (the same for the whole block)
+        const u64 p = chunk0 + (u64)it * PF_THREADS + threadIdx.x;
+        u64 key = 0;
+        const bool ok = p < (u64)L && pf_key_at(G, g, L, (int)p, k, mrd, sample_max, key);
+        if (MODE == PF_COUNT) mine += ok;
+        else {
+            u32 tot;
+            const u32 r = pf_block_rank(ok, s_w, tot);
+            if (ok) out[base + r] = MODE == PF_CANON ? key : ((u64)pf_find(dict, D, key) << 32) | (u64)g;
+            base += tot;
+        }
+    }
+    if (MODE == PF_COUNT) {
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        if (threadIdx.x == 0) blkcnt[blk] = s_cnt;
+    }
+}
+
+// in[0 .. n) ascending: block b takes its PF_CHUNK elements from b * PF_CHUNK on and counts (blkcnt[b]) or writes (from
+// blkoff[b] on) those that differ from their predecessor.  per_genome (WRITE, may be null): += 1 at the low 32 bits of
+// every element written.
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_uniq(const unsigned long long* __restrict__ in, u64 n, u32* __restrict__ blkcnt,
+                                                        const u64* __restrict__ blkoff, unsigned long long* __restrict__ out,
+                                                        u32* __restrict__ per_genome, u32 n_genomes)
+{
+    __shared__ u32 s_w[PF_THREADS / 64];
+    __shared__ u32 s_cnt;
+    const u64 i0 = (u64)blockIdx.x * PF_CHUNK;
+    u64 base = WRITE ? blkoff[blockIdx.x] : 0;
+    u32 mine = 0;
+    if (!WRITE) { if (threadIdx.x == 0) s_cnt = 0; __syncthreads(); }
+    for (int it = 0; it < PF_PER_THREAD; ++it) {
+        if (i0 + (u64)it * PF_THREADS >= n) break;
+        const u64 i = i0 + (u64)it * PF_THREADS + threadIdx.x;
+        u64 v = 0;
+        bool ok = false;
+        if (i < n) { v = in[i]; ok = i == 0 || in[i - 1] != v; }
+        if (!WRITE) mine += ok;
+        else {
+            u32 tot;
+            const u32 r = pf_block_rank(ok, s_w, tot);
+            if (ok) {
+                out[base + r] = v;
+                if (per_genome && (u32)v < n_genomes) atomicAdd(&per_genome[(u32)v], 1u);
+            }
+            base += tot;
+        }
+    }
+    if (!WRITE) {
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        if (threadIdx.x == 0) blkcnt[blockIdx.x] = s_cnt;
+    }
+}
+
+__device__ __forceinline__ u64 pf_shfl_up64(u64 x, int d)
+{
+    const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
+    return ((u64)hi << 32) | lo;
+}
+
+// off[0 .. n] = exclusive prefix of cnt[0 .. n), the total at off[n].  One block.
+__global__ void __launch_bounds__(1024) k_pf_scan(const u32* __restrict__ cnt, u64 n, u64* __restrict__ off)
+{
+    __shared__ u64 s_wsum[16];
+    __shared__ u64 s_carry;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (u64 base = 0; base < n; base += 1024) {
+        const u64 idx = base + threadIdx.x;
+        const u64 v = idx < n ? cnt[idx] : 0;
+        u64 x = v;
+        for (int d = 1; d < 64; d <<= 1) { const u64 y = pf_shfl_up64(x, d); if (lane >= d) x += y; }
+        if (lane == 63) s_wsum[wv] = x;
+        __syncthreads();
+        u64 woff = 0;
+        for (int k = 0; k < wv; ++k) woff += s_wsum[k];
+        const u64 carry = s_carry;
+        if (idx < n) off[idx] = carry + woff + x - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) s_carry = carry + woff + x;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[n] = s_carry;
+}
+
+// post[0 .. M) = rank << 32 | genome, ascending, every rank below D present: runoff[r] = first posting of rank r, runoff[D] = M.
+__global__ void __launch_bounds__(PF_THREADS) k_pf_runs(const unsigned long long* __restrict__ post, u64 M, u32* __restrict__ runoff, u64 D)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i == 0) runoff[D] = (u32)M;
+    if (i >= M) return;
+    const u64 r = post[i] >> 32;
+    if (r < D && (i == 0 || (post[i - 1] >> 32) != r)) runoff[r] = (u32)i;
+}
+
+// The matrix tile mat[(a - r0) * n + b], rows r0 <= a < r1: += 1 for every pair of postings (rank, a), (rank, b) with a < b.
+// A wave takes 64 consecutive postings as its a's, one after the other, the lanes over the rest of a's run: a k-mer that
+// every genome holds is spread over n / 64 waves, and a wave's adds of one step go to one matrix row.
+__global__ void __launch_bounds__(PF_THREADS) k_pf_count(const unsigned long long* __restrict__ post, u64 M, const u32* __restrict__ runoff, u64 D,
+                                                         u32 n, u32 r0, u32 r1, u32* __restrict__ mat)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 w0 = (((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6) << 6;      // the wave's first posting
+    const u64 i = w0 + lane;
+    u32 a = 0, end = 0;
+    bool act = false;
+    if (i < M) {
+        const u64 key = post[i];
+        const u64 rank = key >> 32;
+        a = (u32)key;
+        if (rank < D && a >= r0 && a < r1) {
+            const u64 e = runoff[rank + 1];
+            end = (u32)(e < M ? e : M);
+            act = (u64)end > i + 1;
+        }
+    }
+    u64 todo = __builtin_amdgcn_ballot_w64(act);
+    while (todo) {
+        const int l = ctz64(todo);
+        todo &= todo - 1;
+        const u32 al = __shfl(a, l), el = __shfl(end, l);
+        u32* __restrict__ row = mat + (u64)(al - r0) * n;
+        for (u64 j = w0 + l + 1 + lane; j < (u64)el; j += 64) {
+            const u32 b = (u32)post[j];
+            if (b < n) atomicAdd(&row[b], 1u);
+        }
+    }
+}
+
+// kept: shared >= min_shared (>= 1) and shared / min(|a|, |b|) >= min_ratio, in IEEE double division
+__device__ __forceinline__ bool pf_kept(u32 s, u32 ka, u32 kb, u32 min_shared, double min_ratio)
+{
+    if (s < min_shared) return false;
+    return (double)s / (double)(ka < kb ? ka : kb) >= min_ratio;
+}
+
+// A wave per row a of the tile: the kept entries b > a counted (rowcnt[a - r0]) or written from rowoff[a - r0] on
+// (tile-relative), in ascending b.
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_rows(const u32* __restrict__ mat, u32 n, u32 r0, u32 r1, const u32* __restrict__ kmers_of,
+                                                        u32 min_shared, double min_ratio, u32* __restrict__ rowcnt, const u64* __restrict__ rowoff,
+                                                        u32* __restrict__ ids, u32* __restrict__ shared)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6;
+    if (wave >= (u64)(r1 - r0)) return;
+    const u32 a = r0 + (u32)wave;
+    const u32* __restrict__ m = mat + wave * n;
+    const u32 ka = kmers_of[a];
+    u64 base = WRITE ? rowoff[wave] : 0;
+    u32 cnt = 0;
+    for (u64 b0 = (u64)a + 1; b0 < n; b0 += 64) {
+        const u64 b = b0 + lane;
+        u32 s = 0;
+        bool ok = false;
+        if (b < n) { s = m[b]; ok = pf_kept(s, ka, kmers_of[b], min_shared, min_ratio); }
+        const u64 mask = __builtin_amdgcn_ballot_w64(ok);
+        if (WRITE && ok) {
+            const u64 at = base + (u64)__popcll(mask & ((1ULL << lane) - 1ULL));
+            ids[at] = (u32)b;
+            shared[at] = s;
+        }
+        base += (u64)__popcll(mask);
+        cnt += (u32)__popcll(mask);
+    }
+    if (!WRITE && lane == 0) rowcnt[wave] = cnt;
+}
+
+}  // namespace lzani

@@ -1,4 +1,4 @@
-// ingest.h -- FASTA ingest, length-descending reorder and kmer-db filter of the `lz-ani` host binary.
+// ingest.h -- FASTA ingest, length-descending reorder and kmer-db / device k-mer filter rows of the `lz-ani` host binary.
 //
 // Behaviour follows the reference's host data services (studied, not copied):
 //   CSeqReservoir::load_multifasta / load_fasta / append / reorder_items
@@ -11,7 +11,9 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <filesystem>
 #include <iostream>
@@ -268,6 +270,30 @@ inline bool load_filter(const std::string& fn, double thr, Filter& f)
         for (uint32_t k = 0; k < first[i]; ++k) f.rows[f.rows[i][k]].push_back((uint32_t)i);
     return true;
 }
+
+// The same rows from the kept pairs a < b of the device k-mer prefilter (lzani_prefilter_fetch: row a lists its b's,
+// ascending), symmetrised the way load_filter does it.
+inline void filter_from_pairs(uint32_t n, const std::vector<uint64_t>& row_off, const std::vector<uint32_t>& ids, Filter& f)
+{
+    f.rows.assign(n, {});
+    for (uint32_t a = 0; a < n; ++a) f.rows[a].assign(ids.begin() + (ptrdiff_t)row_off[a], ids.begin() + (ptrdiff_t)row_off[a + 1]);
+    std::vector<uint32_t> first(n);
+    for (uint32_t i = 0; i < n; ++i) first[i] = (uint32_t)f.rows[i].size();
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t k = 0; k < first[i]; ++k) f.rows[f.rows[i][k]].push_back(i);
+}
+
+// --flt-kmers-fraction: a number in (0, 1], the whole string; false for anything else
+inline bool parse_fraction(const char* v, double& out)
+{
+    char* end = nullptr;
+    const double x = strtod(v, &end);
+    if (end == v || *end != 0 || !(x > 0) || !(x <= 1)) return false;
+    out = x;
+    return true;
+}
+// sample_max of lzani_prefilter for a sampling fraction in (0, 1]: floor(f * 2^64), saturated
+inline uint64_t sample_max_of(double f) { return f >= 1 ? UINT64_MAX : (uint64_t)std::ldexp(f, 64); }
 
 inline void reorder_filter(Filter& f, const std::vector<uint32_t>& map)
 {

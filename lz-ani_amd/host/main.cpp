@@ -5,7 +5,8 @@
 //   load sequences -> load filter -> check names -> reorder -> LZ matching -> store results.
 // The matching stage is one call per GPU into the C-ABI of include/lzani.h (liblzani_hip.so, loaded
 // with dlopen so that this binary builds and its ingest/emit code is testable without ROCm present).
-// Extras over the reference: --gpus <n> (rows dealt cyclically over n GPUs), --device <id>, --gpu-mem <size>
+// Extras over the reference: --flt-kmers <k> <thr> (the filter rows made on the GPU from the genomes themselves, in place
+// of a kmer-db file), --gpus <n> (rows dealt cyclically over n GPUs), --device <id>, --gpu-mem <size>
 // (genome-memory limit per GPU: larger sets run out-of-core, in tiles of genome blocks),
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
 #include <dlfcn.h>
@@ -42,6 +43,10 @@ struct Params {
     int gpus = 1, device = 0;
     uint64_t gpu_mem = 0;                                   // --gpu-mem: genome-memory limit per GPU (0: automatic)
     string results_out, results_in;
+    bool flt_kmers = false;                                 // --flt-kmers: the filter rows come from the device k-mer prefilter
+    int flt_k = 0;
+    string flt_fraction_arg;                                // --flt-kmers-fraction as given; checked after the flags are read
+    double flt_fraction = 1;
 };
 
 static Params P;
@@ -96,6 +101,9 @@ static void usage()
          << "      --in-dir <path>            - directory with FASTA files\n"
          << "      --multisample-fasta <bool> - multi sample FASTA input (default: true)\n"
          << "      --flt-kmerdb <fn> <float>  - filtering file (kmer-db output) and threshold\n"
+         << "      --flt-kmers <k> <float>    - filter built on the GPU instead of read from a file: pairs whose shared canonical k-mers (8 <= k <= 31)\n"
+         << "                                   are at least <float> of the smaller genome's k-mer set (not with --flt-kmerdb)\n"
+         << "      --flt-kmers-fraction <float> - fraction of the k-mers sampled for --flt-kmers, in (0, 1] (default: 1)\n"
          << "Options - output specification:\n"
          << "  -o, --out <file_name>          - output file name\n"
          << "      --out-ids <file_name>      - output file name for ids file (optional)\n"
@@ -167,6 +175,8 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--am" && has(1)) { z.approx_mismatches = atoi(argv[i + 1]); i += 2; }
         else if (par == "--ar" && has(1)) { z.approx_run_len = atoi(argv[i + 1]); i += 2; }
         else if (par == "--flt-kmerdb" && has(2)) { P.filter_fn = argv[i + 1]; P.filter_thr = atof(argv[i + 2]); i += 3; }
+        else if (par == "--flt-kmers" && has(2)) { P.flt_kmers = true; P.flt_k = atoi(argv[i + 1]); P.filter_thr = atof(argv[i + 2]); i += 3; }
+        else if (par == "--flt-kmers-fraction" && has(1)) { P.flt_fraction_arg = argv[i + 1]; i += 2; }
         else if ((par == "-V" || par == "--verbose") && has(1)) { P.verbosity = (uint32_t)atoi(argv[i + 1]); i += 2; }
         else if (par == "--out-type" && has(1)) {
             string t = argv[i + 1];
@@ -204,6 +214,16 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--results-out" && has(1)) { P.results_out = argv[i + 1]; i += 2; }
         else if (par == "--results-in" && has(1)) { P.results_in = argv[i + 1]; i += 2; }
         else { cerr << "Unknown parameter: " << argv[i] << endl; usage(); exit(1); }
+    }
+    // The device k-mer prefilter: refused here, before any input is read
+    if (P.flt_kmers && !P.filter_fn.empty()) { cerr << "--flt-kmers and --flt-kmerdb cannot be used together" << endl; exit(1); }
+    if (P.flt_kmers && (P.flt_k < 8 || P.flt_k > 31)) {
+        cerr << "Unsupported value: --flt-kmers " << P.flt_k << " (k-mer lengths 8 .. 31 are supported)" << endl;
+        exit(1);
+    }
+    if (!P.flt_fraction_arg.empty() && !parse_fraction(P.flt_fraction_arg.c_str(), P.flt_fraction)) {
+        cerr << "Invalid value for --flt-kmers-fraction: " << P.flt_fraction_arg << " (a number in (0, 1])" << endl;
+        exit(1);
     }
     if (P.inputs.empty()) { cerr << "Input file names not provided\n"; return false; }
     // The engine's parameter envelope (lz-ani_amd/csrc/lzani_layout.h: params_supported).  The reference accepts any
@@ -272,6 +292,9 @@ struct Engine {
     int (*get_residency)(const lzani_ctx*, lzani_residency_info*) = nullptr;
     int (*group_set_genome_memory)(lzani_group*, uint64_t) = nullptr;
     int (*group_get_residency)(const lzani_group*, uint32_t, lzani_residency_info*) = nullptr;
+    int (*prefilter)(lzani_ctx*, int, uint64_t, uint32_t, double, uint64_t*) = nullptr;
+    int (*prefilter_fetch)(lzani_ctx*, uint32_t*, uint64_t*, uint32_t*, uint32_t*) = nullptr;
+    int (*get_prefilter_info)(const lzani_ctx*, lzani_prefilter_info*) = nullptr;
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -288,12 +311,43 @@ struct Engine {
         BIND(row_costs) BIND(partition_rows)
         BIND(group_create) BIND(group_destroy) BIND(group_last_error) BIND(group_set_genomes) BIND(group_run_rows) BIND(group_get_timing)
         BIND(set_genome_memory) BIND(get_residency) BIND(group_set_genome_memory) BIND(group_get_residency)
+        BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info)
 #undef BIND
         return true;
     }
 };
 
 struct AlnRegion { uint32_t ref, qry; lzani_region r; };
+
+// --flt-kmers: the filter rows from the device k-mer prefilter (lzani_prefilter) on the first device, for the genomes in
+// their reordered ids: a context of its own, the genomes, the stage with min_shared 1 and the threshold as min_ratio, the
+// kept pairs; symmetrised into flt.rows like a kmer-db file's.
+static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
+{
+    const uint32_t n = (uint32_t)g.size();
+    vector<const uint8_t*> ptr(n);
+    vector<uint32_t> len(n);
+    for (uint32_t i = 0; i < n; ++i) { ptr[i] = g[i].codes.data(); len[i] = (uint32_t)g[i].codes.size(); }
+    lzani_ctx* ctx = nullptr;
+    int rc = E.create(&P.lz, P.device, &ctx);
+    if (rc != LZANI_OK) { cerr << "K-mer filter failed: lzani_create failed with code " << rc << endl; return false; }
+    uint64_t kept = 0;
+    vector<uint64_t> row_off((size_t)n + 1, 0);
+    vector<uint32_t> ids;
+    rc = E.set_genomes(ctx, n, ptr.data(), len.data());
+    if (rc == LZANI_OK) rc = E.prefilter(ctx, P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, &kept);
+    if (rc == LZANI_OK) { ids.resize(kept); rc = E.prefilter_fetch(ctx, nullptr, row_off.data(), ids.data(), nullptr); }
+    if (rc != LZANI_OK) { cerr << "K-mer filter failed: " << E.last_error(ctx) << endl; E.destroy(ctx); return false; }
+    lzani_prefilter_info pi;
+    if (P.verbosity >= 2 && E.get_prefilter_info(ctx, &pi) == LZANI_OK)
+        cerr << "k-mer filter on device " << P.device << ": k " << pi.k << ", " << pi.positions << " sampled windows, " << pi.distinct_kmers
+             << " distinct k-mers, " << pi.postings << " postings, " << pi.entries << " kept pairs, " << pi.tiles << " tile(s); keys " << pi.keys_ms
+             << " ms, sorts " << pi.sort_ms << " ms, counting " << pi.count_ms << " ms, compaction " << pi.compact_ms << " ms\n";
+    E.destroy(ctx);
+    flt.names.clear();
+    filter_from_pairs(n, row_off, ids, flt);
+    return true;
+}
 
 // -V 2 with --gpu-mem or an out-of-core set: how the genome set of a device was held (lzani_get_residency); a tiled
 // all2all passes its sums over its calls
@@ -660,6 +714,17 @@ static bool run_all2all(const char* argv0)
     if (!flt.empty()) { if (P.verbosity >= 1) cerr << "Reordering filter" << endl; reorder_filter(flt, map); }
     stamp("Reordering sequences");
 
+    Engine E;
+    bool engine_loaded = false;
+    if (P.flt_kmers) {
+        if (P.verbosity >= 1) cerr << "Building k-mer filter" << endl;
+        if (!E.load(argv0)) return false;
+        engine_loaded = true;
+        if (!kmer_filter(E, g, flt)) return false;
+        if (P.verbosity >= 1) cerr << "Filter size: " << flt.size() << endl;
+        stamp("K-mer filter");
+    }
+
     EmitParams ep;
     ep.out_name = P.out; ep.ids_name = P.out_ids; ep.single_txt = P.single_txt; ep.in_percent = P.in_percent;
     ep.comps = P.comps; ep.filter_mask = P.flt_mask; memcpy(ep.filter_vals, P.flt_vals, sizeof ep.filter_vals);
@@ -676,8 +741,7 @@ static bool run_all2all(const char* argv0)
     PairTable results;
     if (!P.results_in.empty()) { if (!read_raw(P.results_in, g.size(), results)) return false; }
     else {
-        Engine E;
-        if (!E.load(argv0)) return false;
+        if (!engine_loaded && !E.load(argv0)) return false;
         if (tiled) {
             if (P.verbosity >= 1) cerr << "Storing results (row blocks, while the matching goes on)" << endl;
             if (!do_matching_tiled(E, g, results, ep, tile)) return false;

@@ -33,7 +33,8 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_group_set_genomes", "lzani_group_run_rows", "lzani_group_get_timing", "lzani_plan_gather", "lzani_get_rtc_info", "lzani_debug_rtc_compile",
            "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name",
            "lzani_set_genome_memory", "lzani_plan_blocks", "lzani_get_residency", "lzani_group_set_genome_memory",
-           "lzani_group_get_residency", "lzani_debug_index_slab", "lzani_debug_run_candidates")
+           "lzani_group_get_residency", "lzani_debug_index_slab", "lzani_debug_run_candidates",
+           "lzani_prefilter", "lzani_prefilter_fetch", "lzani_get_prefilter_info")
 
 
 class LzaniError(RuntimeError):
@@ -81,10 +82,25 @@ class ResidencyInfo(C.Structure):
                 ("peak_resident_bytes", C.c_uint64), ("host_bytes", C.c_uint64), ("upload_ms", C.c_double)]
 
 
+class PrefilterInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("tiles", C.c_uint32), ("positions", C.c_uint64), ("distinct_kmers", C.c_uint64),
+                ("postings", C.c_uint64), ("entries", C.c_uint64), ("keys_ms", C.c_double), ("sort_ms", C.c_double),
+                ("count_ms", C.c_double), ("compact_ms", C.c_double)]
+
+
+SAMPLE_ALL = 0xFFFFFFFFFFFFFFFF                     # lzani_prefilter's sample_max that keeps every k-mer
+
+
+def sample_max_of(fraction):
+    """sample_max of a sampling fraction in (0, 1]: floor(fraction * 2^64), saturated."""
+    from fractions import Fraction
+    return min(SAMPLE_ALL, int(Fraction(float(fraction)) * (1 << 64)))
+
+
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
     deps = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("lzani_core.h", "lzani_layout.h", "lzani_kernels_index.h",
-                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_multi.h", "lzani_ooc.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h", "lzani_devmem.h")] + [os.path.join(ROOT, "include", "lzani.h")]
+                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_kernels_prefilter.h", "lzani_prefilter_defs.h", "lzani_multi.h", "lzani_ooc.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h", "lzani_devmem.h")] + [os.path.join(ROOT, "include", "lzani.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -147,6 +163,9 @@ def load_library():
         lib.lzani_plan_blocks.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.lzani_get_residency.argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_group_get_residency.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.lzani_prefilter.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p]
+        lib.lzani_prefilter_fetch.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        lib.lzani_get_prefilter_info.argtypes = [C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -359,6 +378,31 @@ class Engine:
         o = ResidencyInfo()
         self._check(self.lib.lzani_get_residency(self.h, C.byref(o)), "lzani_get_residency")
         return _residency(o)
+
+    def prefilter(self, k, sample_max=SAMPLE_ALL, min_shared=1, min_ratio=0.0):
+        """lzani_prefilter on the resident set: the shared canonical k-mer counts of all genome pairs, and the pairs a < b
+        with shared >= max(min_shared, 1) and shared / min(|K(a)|, |K(b)|) >= min_ratio.  Returns the number of kept pairs;
+        prefilter_fetch() brings them."""
+        cnt = C.c_uint64(0)
+        self._check(self.lib.lzani_prefilter(self.h, int(k), C.c_uint64(int(sample_max)), C.c_uint32(int(min_shared)),
+                                             C.c_double(float(min_ratio)), C.byref(cnt)), "lzani_prefilter")
+        return int(cnt.value)
+
+    def prefilter_info(self):
+        o = PrefilterInfo()
+        self._check(self.lib.lzani_get_prefilter_info(self.h, C.byref(o)), "lzani_get_prefilter_info")
+        return {k: getattr(o, k) for k, _ in PrefilterInfo._fields_}
+
+    def prefilter_fetch(self):
+        """(kmers_of uint32[n], row_off uint64[n + 1], ids uint32[e], shared uint32[e]): CSR of the kept pairs a < b."""
+        kmers_of = np.zeros(self.n, dtype=np.uint32)
+        row_off = np.zeros(self.n + 1, dtype=np.uint64)
+        self._check(self.lib.lzani_prefilter_fetch(self.h, _ptr(kmers_of), _ptr(row_off), None, None), "lzani_prefilter_fetch")
+        e = int(row_off[-1])
+        ids = np.zeros(e, dtype=np.uint32)
+        shared = np.zeros(e, dtype=np.uint32)
+        self._check(self.lib.lzani_prefilter_fetch(self.h, None, None, _ptr(ids), _ptr(shared)), "lzani_prefilter_fetch")
+        return kmers_of, row_off, ids, shared
 
     def run_rows(self, ref_ids, row_off, query_ids=None):
         ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)

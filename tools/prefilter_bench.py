@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""GPU box: the device k-mer prefilter (lzani_prefilter) on two workloads, one JSON line.
+  bench     the 10,000 x ~40 kbp set of bench.py (families of 10), k = 21, every k-mer
+  family    the 20,000-genome set of tools/related_bench.py (families of 50), k = 21, every k-mer and every fifth; and the
+            bar of the stage: prefilter (every fifth k-mer) + the filtered run_rows it yields against the dense run_rows of
+            the same set, wall time, same process
+Per run: the four stage times of lzani_get_prefilter_info (HIP events), postings per second over their sum, and the
+bytes the stage's passes move per posting (counted below from the run's own sizes) against the 8 TB/s HBM roofline.
+Every figure is the median of --repeats runs after one warm-up run.
+Usage: tools/prefilter_bench.py [--out profiles/prefilter_bench.json] [--repeats 3] [--small] [--no-dense]"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("lz-ani_amd", "tools"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+import numpy as np
+import lzani_ctypes as L
+import synth_genomes as SG
+
+HBM_BYTES_PER_S = 8e12
+K = 21
+
+
+def stage_bytes(info, n, updates):
+    """HBM bytes of the stage's passes, from its own counts: P kept windows, D distinct k-mers, M postings, `updates`
+    atomic adds.  Keys: three passes over the packed texts (both strands, 2 bit a base: left out) writing 8 B twice and
+    looking each window up in the dictionary (log2 D probes of 8 B, most of them cached: counted in full).  A radix
+    pass reads a key twice and writes it once (24 B); the dictionary and the postings each read the sorted keys twice
+    and write the survivors.  Counting reads a posting's run once per posting ahead of it (4 B of the atomic add each,
+    8 B read) and the matrix is cleared and read once above the diagonal."""
+    P, D, M = info["positions"], info["distinct_kmers"], info["postings"]
+    lgD = max(1, math.ceil(math.log2(max(D, 2))))
+    passes = math.ceil(2 * info["k"] / 8) + math.ceil(lgD / 8)
+    keys = P * (8 + 8 + 8 * lgD)
+    sort = P * 24 * passes + P * 16 * 2 + 8 * (D + M) + 4 * D
+    count = 8 * M * info["tiles"] + 12 * updates + 4 * n * n
+    compact = 4 * n * n // 2 + 8 * info["entries"]
+    return dict(keys=keys, sort=sort, count=count, compact=compact)
+
+
+def measure(eng, n, smax, min_shared, min_ratio, repeats):
+    eng.prefilter(K, smax, 1, 0.0)                                  # warm-up; with these thresholds: sum of shared = atomic adds
+    updates = int(eng.prefilter_fetch()[3].astype(np.int64).sum())
+    runs, walls = [], []
+    for _ in range(repeats):
+        t = time.perf_counter()
+        eng.prefilter(K, smax, min_shared, min_ratio)
+        walls.append(time.perf_counter() - t)
+        runs.append(eng.prefilter_info())
+    info = dict(runs[0])
+    for key in ("keys_ms", "sort_ms", "count_ms", "compact_ms"):
+        info[key] = float(np.median([r[key] for r in runs]))
+    dev_ms = info["keys_ms"] + info["sort_ms"] + info["count_ms"] + info["compact_ms"]
+    b = stage_bytes(info, n, updates)
+    total_b = sum(b.values())
+    info.update(device_ms=dev_ms, wall_ms=float(np.median(walls)) * 1e3, atomic_adds=updates,
+                postings_per_s=info["postings"] / (dev_ms * 1e-3) if dev_ms else None,
+                bytes_per_posting=total_b / max(info["postings"], 1), bytes_by_stage=b,
+                achieved_bytes_per_s=total_b / (dev_ms * 1e-3) if dev_ms else None,
+                share_of_hbm_roofline=total_b / (dev_ms * 1e-3) / HBM_BYTES_PER_S if dev_ms else None)
+    return info
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "prefilter_bench.json"))
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--small", action="store_true", help="a tenth of both sets (rehearsal)")
+    ap.add_argument("--no-dense", action="store_true", help="skip the dense run of the family set")
+    a = ap.parse_args()
+    n_bench, n_fam, fam = (1000, 2000, 50) if a.small else (10000, 20000, 50)
+    res = dict(tool="prefilter_bench", k=K, repeats=a.repeats, hbm_roofline_bytes_per_s=HBM_BYTES_PER_S)
+
+    _, seqs = SG.make_set_cached(n_bench, 2)
+    eng = L.Engine()
+    eng.set_genomes(seqs)
+    res["bench_set"] = dict(genomes=n_bench, fraction_1=measure(eng, n_bench, L.SAMPLE_ALL, 1, 0.0, a.repeats))
+    eng.close()
+    print("bench set:", json.dumps(res["bench_set"]), flush=True)
+
+    _, seqs = SG.make_set(n_fam, 1, fam=fam)
+    eng = L.Engine()
+    eng.set_genomes(seqs)
+    # thresholds of the family runs: 5 shared sampled 21-mers and 0.3 % of the smaller set -- far above what unrelated
+    # random genomes share by chance, far below what members of one family share
+    fs = dict(genomes=n_fam, family=fam, min_shared=5, min_ratio=0.003)
+    fs["fraction_1"] = measure(eng, n_fam, L.SAMPLE_ALL, 5, 0.003, a.repeats)
+    fs["fraction_0.2"] = measure(eng, n_fam, L.sample_max_of(0.2), 5, 0.003, a.repeats)
+    print("family set:", json.dumps(fs), flush=True)
+
+    # the bar: prefilter + filtered rows against dense rows, wall time
+    ref_ids = np.arange(n_fam, dtype=np.uint32)
+    t = time.perf_counter()
+    eng.prefilter(K, L.sample_max_of(0.2), 5, 0.003)
+    _, row_off, ids, _ = eng.prefilter_fetch()
+    a_of = np.repeat(ref_ids, np.diff(row_off).astype(np.int64))
+    r = np.concatenate((a_of, ids)).astype(np.int64)                      # both directions of every kept pair
+    q = np.concatenate((ids, a_of)).astype(np.int64)
+    order = np.lexsort((q, r))
+    q_ids = q[order].astype(np.uint32)
+    f_off = np.zeros(n_fam + 1, dtype=np.uint64)
+    f_off[1:] = np.cumsum(np.bincount(r, minlength=n_fam))
+    t_pre = time.perf_counter() - t
+    eng.run_rows(ref_ids[:fam], f_off[:fam + 1], q_ids[:int(f_off[fam])])     # warm-up of the filtered path (one family)
+    t = time.perf_counter()
+    eng.run_rows(ref_ids, f_off, q_ids)
+    t_flt = time.perf_counter() - t
+    same = int(((r // fam) == (q // fam)).sum())
+    bar = dict(prefilter_and_rows_wall_s=t_pre, filtered_run_rows_wall_s=t_flt, filtered_pairs=int(len(q_ids)),
+               same_family_pairs_kept=same, same_family_pairs=n_fam * (fam - 1), cross_family_pairs_kept=int(len(q_ids)) - same)
+    if not a.no_dense:
+        d_ids, d_off = L.dense_rows(n_fam)
+        eng.run_rows(d_ids[:8], d_off[:9], None)                          # warm-up of the dense path
+        t = time.perf_counter()
+        eng.run_rows(d_ids, d_off, None)
+        bar["dense_run_rows_wall_s"] = time.perf_counter() - t
+        bar["dense_pairs"] = int(d_off[-1])
+        bar["speedup"] = bar["dense_run_rows_wall_s"] / (t_pre + t_flt)
+    eng.close()
+    fs["filtered_against_dense"] = bar
+    res["family_set"] = fs
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    if "speedup" in bar and bar["speedup"] <= 1:
+        sys.exit("prefilter + filtered run_rows was not faster than the dense run_rows")
+
+
+if __name__ == "__main__":
+    main()
