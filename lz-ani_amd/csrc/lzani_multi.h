@@ -11,34 +11,18 @@
 //   lzani_comm_*                             one process per GPU (torchrun, MPI...): ncclCommInitRank from a
 //                                            unique id the caller distributes, ncclAllGather of padded shards
 //                                            or grouped ncclSend/ncclRecv of ragged shards to a root
-//   lzani_group_*                            one process, n GPUs (the `lz-ani --gpus n` host binary): a context
-//                                            per device on its own host thread, ncclCommInitAll, grouped
-//                                            ncclSend/ncclRecv to device 0, a scatter kernel into the caller's
-//                                            CSR order and ONE device-to-host copy
+//   lzani_group_*                            one process, n GPUs (`lz-ani --gpus n`): a context per device, ncclCommInitAll;
+//                                            lzani_group_run_rows in stages: check the rows -> deal them and make the ONE
+//                                            shard plan (lzani_shard_plan.h: free of HIP, tested on the CPU through
+//                                            lzani_plan_gather) -> ensure the buffers -> run the shards, a host thread per device
+//                                            -> grouped ncclSend/ncclRecv to device 0 -> scatter kernel into CSR order, ONE copy out
 #pragma once
 #include <rccl/rccl.h>
 
 #include <numeric>
 #include <thread>
 
-namespace {
-
-#define RCCLCHK(c, call)                                                                              \
-    do {                                                                                              \
-        ncclResult_t r_ = (call);                                                                     \
-        if (r_ != ncclSuccess)                                                                        \
-            return fail(c, LZANI_ERR_DEVICE, std::string(#call) + ": " + ncclGetErrorString(r_));     \
-    } while (0)
-
-// Rows of a gathered buffer (shard order) -> the caller's CSR order.  One block per row.
-__global__ void k_scatter_rows(const int* __restrict__ src, int* __restrict__ dst, const u64* __restrict__ src_off,
-                               const u64* __restrict__ dst_off, const u64* __restrict__ count)
-{
-    const u64 s = 3 * src_off[blockIdx.x], d = 3 * dst_off[blockIdx.x], n = 3 * count[blockIdx.x];
-    for (u64 k = threadIdx.x; k < n; k += blockDim.x) dst[d + k] = src[s + k];
-}
-
-}  // namespace
+#include "lzani_shard_plan.h"
 
 struct lzani_group {
     std::vector<lzani_ctx*> ctx;
@@ -54,9 +38,196 @@ struct lzani_group {
     std::vector<DevMem<lzani_result>> d_shard;    // [0] stays empty (the first device writes into d_all); [d] lives on device d
     DevMem<unsigned long long> d_tab;
     PinMem<char> h_stage[2];
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    hipEvent_t ev_stage[2] = {nullptr, nullptr}, ev_gather[2] = {nullptr, nullptr};   // (ev_gather: made with the group; gather_ms is from before the gather to after the scatter kernel)
 };
 enum : size_t { GROUP_STAGE_BYTES = (size_t)32 << 20 };
+
+namespace {
+
+#define RCCLCHK(c, call)                                                                              \
+    do {                                                                                              \
+        ncclResult_t r_ = (call);                                                                     \
+        if (r_ != ncclSuccess) return fail(c, LZANI_ERR_DEVICE, std::string(#call) + ": " + ncclGetErrorString(r_)); \
+    } while (0)
+#define GHIPCHK(g, call)                                                                              \
+    do {                                                                                              \
+        hipError_t e_ = (call);                                                                       \
+        if (e_ != hipSuccess) return gfail(g, LZANI_ERR_DEVICE, std::string("gather / copy out: ") + hipGetErrorString(e_)); \
+    } while (0)
+
+// Rows of a gathered buffer (shard order) -> the caller's CSR order.  One block per row.
+__global__ void k_scatter_rows(const int* __restrict__ src, int* __restrict__ dst, const u64* __restrict__ src_off,
+                               const u64* __restrict__ dst_off, const u64* __restrict__ count)
+{
+    const u64 s = 3 * src_off[blockIdx.x], d = 3 * dst_off[blockIdx.x], n = 3 * count[blockIdx.x];
+    for (u64 k = threadIdx.x; k < n; k += blockDim.x) dst[d + k] = src[s + k];
+}
+
+// ---- the stages of lzani_group_run_rows; each reports through gfail (GHIPCHK: HIPCHK for the group's gather and copy out)
+int gfail(lzani_group* g, int code, const std::string& msg) { if (g) g->err = msg; return code; }
+thread_local std::string t_group_create_err;      // why the last lzani_group_create of this thread failed (there is no group to hold it)
+
+// f(d) -> an LZANI_* code, for every device at once (threads for devices 1 .. n - 1, device 0 on the caller's); the first error wins
+template <class F> int on_every_device(lzani_group* g, F f)
+{
+    std::vector<int> rc(g->ctx.size(), LZANI_OK);
+    std::vector<std::thread> th;
+    auto one = [&](size_t d) { rc[d] = f(d); };
+    for (size_t d = 1; d < g->ctx.size(); ++d) th.emplace_back(one, d);
+    one(0);
+    for (auto& t : th) t.join();
+    for (size_t d = 0; d < g->ctx.size(); ++d)
+        if (rc[d] != LZANI_OK) return gfail(g, rc[d], "device " + std::to_string(g->devs[d]) + ": " + lzani_last_error(g->ctx[d]));
+    return LZANI_OK;
+}
+
+struct GroupRun {                       // one lzani_group_run_rows call on its way through the stages
+    u32 n_rows; const u32* ref_ids; const u64* row_off; const u32* query_ids; lzani_result* out; u64 n_pairs = 0;   // (the caller's)
+    ShardPlan plan;                     // what every device gets, and the scatter table
+    std::vector<int*> d_shard;          // where every device writes its shard ([0]: in place in d_all)
+};
+
+int group_check_rows(lzani_group* g, GroupRun& r)
+{
+    if (!r.ref_ids || !r.row_off) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null argument");
+    r.n_pairs = r.n_rows ? r.row_off[r.n_rows] : 0;
+    if (r.n_pairs && !r.out) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null output");
+    g->gather_ms = 0;
+    const u32 n = g->ctx[0]->gs.n;
+    if (!n) return gfail(g, LZANI_ERR_STATE, "lzani_group_run_rows: no genomes set");
+    for (u32 k = 0; k < r.n_rows; ++k)
+        if (r.ref_ids[k] >= n || r.row_off[k + 1] < r.row_off[k]) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: bad row table");
+    if (r.query_ids)
+        for (u64 e = 0; e < r.n_pairs; ++e) if (r.query_ids[e] >= n) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: query id out of range");
+    return LZANI_OK;
+}
+
+// rows -> devices: cyclic for dense rows, LPT on the row costs for query lists; then the one shard plan
+int group_partition_rows(lzani_group* g, GroupRun& r)
+{
+    const GenomeSet& gs = g->ctx[0]->gs;
+    const u32 nd = (u32)g->ctx.size();
+    std::vector<u32> part(r.n_rows);
+    std::vector<u64> cost(r.query_ids ? r.n_rows : 0);
+    if (r.query_ids) {
+        std::vector<u32> len(gs.L.begin(), gs.L.end());
+        int rc = lzani_row_costs(r.n_rows, r.ref_ids, r.row_off, r.query_ids, gs.n, len.data(), cost.data());
+        if (rc != LZANI_OK) return gfail(g, rc, "lzani_group_run_rows: row costs");
+    }
+    lzani_partition_rows(r.n_rows, r.query_ids ? cost.data() : nullptr, nd, part.data());
+    if (!plan_shards(r.n_rows, r.ref_ids, r.row_off, r.query_ids, part.data(), nd, r.plan)) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: gather plan");
+    return LZANI_OK;
+}
+
+// device 0 holds the gathered buffer (its own shard is written in place) and the CSR-ordered copy: grown, never shrunk
+int group_ensure_buffers(lzani_group* g, GroupRun& r)
+{
+    const hipError_t e = hipSetDevice(g->ctx[0]->dev);
+    if (e != hipSuccess) return gfail(g, LZANI_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (g->d_final.capacity() < std::max<u64>(r.n_pairs, 1)) {
+        g->d_all.reset(); g->d_final.reset();                    // (both released before either is made anew; a failure leaves none)
+        if (!got(g->d_all.alloc(r.n_pairs)) || !got(g->d_final.alloc(r.n_pairs))) {
+            g->d_all.reset();
+            return gfail(g, LZANI_ERR_NOMEM, "lzani_group_run_rows: result buffers on device 0");
+        }
+    }
+    g->d_shard.resize(g->ctx.size());                            // (a peer's shard buffer is made on its own thread, below)
+    r.d_shard.assign(g->ctx.size(), nullptr); r.d_shard[0] = (int*)g->d_all.get();
+    return LZANI_OK;
+}
+
+int group_run_shards(lzani_group* g, GroupRun& r)
+{
+    return on_every_device(g, [&](size_t d) -> int {
+        lzani_ctx* c = g->ctx[d];
+        const Shard& s = r.plan.shard[d];
+        if (s.rows.empty()) { c->run.tm = lzani_timing{}; return LZANI_OK; }   // no row for this device
+        if (d && g->d_shard[d].capacity() < std::max<u64>(s.pairs(), 1)) {
+            if (hipSetDevice(c->dev) != hipSuccess) return LZANI_ERR_DEVICE;
+            if (!got(g->d_shard[d].alloc(s.pairs()))) return LZANI_ERR_NOMEM;
+        }
+        if (d) r.d_shard[d] = (int*)g->d_shard[d].get();
+        static const u32 none = 0;                             // (lists that are all empty are still lists, not dense rows: never null)
+        const u32* q = !r.query_ids ? nullptr : s.q.empty() ? &none : s.q.data();
+        return lzani_run_rows_device(c, (u32)s.ref.size(), s.ref.data(), s.off.data(), q, r.d_shard[d]);
+    });
+}
+
+// the gather: every peer's shard to device 0 (grouped ncclSend / ncclRecv over xGMI)
+int group_gather(lzani_group* g, const GroupRun& r)
+{
+    lzani_ctx* c0 = g->ctx[0];
+    const u32 nd = (u32)g->ctx.size();
+    const std::vector<Shard>& sh = r.plan.shard;
+    GHIPCHK(g, hipSetDevice(c0->dev));
+    GHIPCHK(g, hipEventRecord(g->ev_gather[0], c0->stream));
+    if (!g->comms.empty()) {
+        ncclResult_t rn = ncclGroupStart();
+        for (u32 d = 1; d < nd && rn == ncclSuccess; ++d) {
+            const size_t cnt = (size_t)sh[d].pairs() * 3;
+            if (!cnt) continue;
+            hipSetDevice(g->ctx[d]->dev);
+            rn = ncclSend(r.d_shard[d], cnt, ncclInt32, 0, g->comms[d], g->ctx[d]->stream);
+            hipSetDevice(c0->dev);
+            if (rn == ncclSuccess) rn = ncclRecv(r.d_shard[0] + 3 * sh[d].base, cnt, ncclInt32, (int)d, g->comms[0], c0->stream);
+        }
+        ncclResult_t r2 = ncclGroupEnd();
+        if (rn == ncclSuccess) rn = r2;
+        if (rn != ncclSuccess) return gfail(g, LZANI_ERR_DEVICE, std::string("RCCL gather: ") + ncclGetErrorString(rn));
+    } else {
+        for (u32 d = 1; d < nd; ++d)                         // rehearsal on one device: plain device copies
+            if (sh[d].pairs() && hipMemcpyAsync(r.d_shard[0] + 3 * sh[d].base, r.d_shard[d], sh[d].pairs() * 12, hipMemcpyDeviceToDevice, c0->stream) != hipSuccess)
+                return gfail(g, LZANI_ERR_DEVICE, "device copy of a shard failed");
+    }
+    return LZANI_OK;
+}
+
+// shard order -> the caller's CSR order on device 0, then the one device-to-host copy
+int group_scatter_out(lzani_group* g, const GroupRun& r)
+{
+    if (!r.n_rows) return LZANI_OK;
+    lzani_ctx* c0 = g->ctx[0];
+    const std::vector<u64>& tab = r.plan.tab;
+    int* const d_final = (int*)g->d_final.get();
+    GHIPCHK(g, g->d_tab.reserve(tab.size()));
+    unsigned long long* const d_tab = g->d_tab;
+    GHIPCHK(g, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c0->stream));
+    hipLaunchKernelGGL(k_scatter_rows, dim3(r.n_rows), dim3(256), 0, c0->stream, r.d_shard[0], d_final, (const u64*)d_tab, (const u64*)d_tab + r.n_rows, (const u64*)d_tab + 2 * (size_t)r.n_rows);
+    GHIPCHK(g, hipGetLastError());
+    GHIPCHK(g, hipEventRecord(g->ev_gather[1], c0->stream));
+    // the copy out: through two pinned staging buffers that take turns -- the device-to-host copy of one piece flies
+    // while the host moves the piece before it into the caller's (pageable) buffer
+    for (int k = 0; k < 2; ++k) {
+        if (!g->h_stage[k]) GHIPCHK(g, g->h_stage[k].alloc(GROUP_STAGE_BYTES));
+        if (!g->ev_stage[k]) GHIPCHK(g, hipEventCreateWithFlags(&g->ev_stage[k], hipEventDisableTiming));
+    }
+    const size_t total = (size_t)r.n_pairs * 12;
+    size_t issued = 0, moved = 0, len[2] = {0, 0};
+    for (int k = 0; issued < total || moved < total; k ^= 1) {
+        if (len[k]) {                                  // the piece this buffer holds: wait for it, hand it over
+            GHIPCHK(g, hipEventSynchronize(g->ev_stage[k]));
+            memcpy((char*)r.out + moved, g->h_stage[k], len[k]);
+            moved += len[k];
+            len[k] = 0;
+        }
+        if (issued < total) {
+            len[k] = std::min<size_t>(GROUP_STAGE_BYTES, total - issued);
+            GHIPCHK(g, hipMemcpyAsync(g->h_stage[k], (const char*)d_final + issued, len[k], hipMemcpyDeviceToHost, c0->stream));
+            GHIPCHK(g, hipEventRecord(g->ev_stage[k], c0->stream));
+            issued += len[k];
+        }
+    }
+    GHIPCHK(g, hipStreamSynchronize(c0->stream));
+    hipError_t e = hipSuccess;
+    for (size_t d = 1; d < g->ctx.size() && e == hipSuccess; ++d) { hipSetDevice(g->ctx[d]->dev); e = hipStreamSynchronize(g->ctx[d]->stream); }
+    hipSetDevice(c0->dev);                             // (the calling thread leaves with device 0 current, as it came)
+    GHIPCHK(g, e);
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, g->ev_gather[0], g->ev_gather[1]) == hipSuccess) g->gather_ms = ms;
+    return LZANI_OK;
+}
+
+}  // namespace
 
 static void comm_release(lzani_ctx* c)
 {
@@ -177,35 +348,18 @@ int lzani_comm_gatherv(lzani_ctx* c, const void* d_send, void* d_recv, const uin
 }
 
 // ---- one process, n GPUs ------------------------------------------------------------------------------
-static int gfail(lzani_group* g, int code, const std::string& msg) { if (g) g->err = msg; return code; }
-static thread_local std::string t_group_create_err;      // why the last lzani_group_create of this thread failed (there is no group to hold it)
-
-// The shard bookkeeping of lzani_group_run_rows as a pure host function (exported so that it can be tested without a
-// GPU): rows keep their order inside a shard, shards follow each other in the gathered buffer; entry j of the scatter
-// table (j counts the rows shard by shard) says where the row's results sit in that buffer, where they belong in the
-// caller's CSR order, and how many there are.
+// The shard plan of lzani_group_run_rows (lzani_shard_plan.h states the rule) in flat arrays: testable without a GPU.
 int lzani_plan_gather(uint32_t n_rows, const uint64_t* row_off, const uint32_t* part_of_row, uint32_t n_parts,
                       uint64_t* shard_base, uint64_t* src, uint64_t* dst, uint64_t* cnt, uint32_t* row_of_entry)
 {
     if (!n_parts || (n_rows && (!row_off || !part_of_row)) || !shard_base || (n_rows && (!src || !dst || !cnt))) return LZANI_ERR_ARG;
-    std::vector<u64> pairs(n_parts, 0);
-    for (u32 k = 0; k < n_rows; ++k) {
-        if (part_of_row[k] >= n_parts || row_off[k + 1] < row_off[k]) return LZANI_ERR_ARG;
-        pairs[part_of_row[k]] += row_off[k + 1] - row_off[k];
-    }
+    ShardPlan p;
+    if (!plan_shards(n_rows, nullptr, row_off, nullptr, part_of_row, n_parts, p)) return LZANI_ERR_ARG;
     shard_base[0] = 0;
-    for (u32 d = 0; d < n_parts; ++d) shard_base[d + 1] = shard_base[d] + pairs[d];
-    std::vector<u64> at(shard_base, shard_base + n_parts);          // next free result of every shard
-    std::vector<u32> first(n_parts + 1, 0);                         // table entries of shard d: first[d] .. first[d + 1]
-    for (u32 k = 0; k < n_rows; ++k) ++first[part_of_row[k] + 1];
-    for (u32 d = 0; d < n_parts; ++d) first[d + 1] += first[d];
-    std::vector<u32> fill(first.begin(), first.end() - 1);
-    for (u32 k = 0; k < n_rows; ++k) {
-        const u32 d = part_of_row[k], j = fill[d]++;
-        src[j] = at[d]; dst[j] = row_off[k]; cnt[j] = row_off[k + 1] - row_off[k];
-        if (row_of_entry) row_of_entry[j] = k;
-        at[d] += cnt[j];
-    }
+    for (u32 d = 0; d < n_parts; ++d) shard_base[d + 1] = p.shard[d].base + p.shard[d].pairs();
+    if (row_of_entry) for (const Shard& sh : p.shard) row_of_entry = std::copy(sh.rows.begin(), sh.rows.end(), row_of_entry);
+    const u64* t = p.tab.data();
+    std::copy(t, t + n_rows, src); std::copy(t + n_rows, t + 2 * (size_t)n_rows, dst); std::copy(t + 2 * (size_t)n_rows, t + 3 * (size_t)n_rows, cnt);
     return LZANI_OK;
 }
 
@@ -217,6 +371,7 @@ void lzani_group_destroy(lzani_group* g)
     if (!g->ctx.empty()) hipSetDevice(g->ctx[0]->dev);
     g->d_all.reset(); g->d_final.reset(); g->d_tab.reset();         // (on the first device; the pinned buffers go with the group)
     for (auto e : g->ev_stage) if (e) hipEventDestroy(e);
+    for (auto e : g->ev_gather) if (e) hipEventDestroy(e);
     for (auto cm : g->comms) if (cm) ncclCommDestroy(cm);
     for (auto c : g->ctx) lzani_destroy(c);
     delete g;
@@ -247,6 +402,8 @@ int lzani_group_create(const lzani_params* p, uint32_t n_devices, const int* dev
         }
         g->ctx.push_back(c);
     }
+    hipSetDevice(g->ctx[0]->dev);                               // (gather_ms is timed between two events of the first device)
+    for (auto& e : g->ev_gather) if (hipEventCreate(&e) != hipSuccess) { t_group_create_err = "hipEventCreate failed"; lzani_group_destroy(g); return LZANI_ERR_DEVICE; }
     std::vector<int> sorted(g->devs);
     std::sort(sorted.begin(), sorted.end());
     g->rehearsal = std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end();
@@ -267,175 +424,21 @@ int lzani_group_create(const lzani_params* p, uint32_t n_devices, const int* dev
 int lzani_group_set_genomes(lzani_group* g, uint32_t n, const uint8_t* const* codes, const uint32_t* len)
 {
     if (!g) return LZANI_ERR_ARG;
-    std::vector<int> rc(g->ctx.size(), LZANI_OK);
-    std::vector<std::thread> th;
-    auto one = [&](size_t d) { rc[d] = lzani_set_genomes(g->ctx[d], n, codes, len); };
-    for (size_t d = 1; d < g->ctx.size(); ++d) th.emplace_back(one, d);
-    one(0);
-    for (auto& t : th) t.join();
-    for (size_t d = 0; d < g->ctx.size(); ++d)
-        if (rc[d] != LZANI_OK) return gfail(g, rc[d], "device " + std::to_string(g->devs[d]) + ": " + lzani_last_error(g->ctx[d]));
-    return LZANI_OK;
+    return on_every_device(g, [&](size_t d) { return lzani_set_genomes(g->ctx[d], n, codes, len); });
 }
 
 int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_ids, const uint64_t* row_off,
                          const uint32_t* query_ids, lzani_result* out)
 {
     if (!g) return LZANI_ERR_ARG;
-    if (!ref_ids || !row_off) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null argument");
-    const u32 nd = (u32)g->ctx.size();
-    const u64 n_pairs = n_rows ? row_off[n_rows] : 0;
-    if (n_pairs && !out) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null output");
-    g->gather_ms = 0;
-    lzani_ctx* c0 = g->ctx[0];
-    if (!c0->gs.n) return gfail(g, LZANI_ERR_STATE, "lzani_group_run_rows: no genomes set");
-    for (u32 k = 0; k < n_rows; ++k)
-        if (ref_ids[k] >= c0->gs.n || row_off[k + 1] < row_off[k]) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: bad row table");
-    if (query_ids)
-        for (u64 e = 0; e < n_pairs; ++e) if (query_ids[e] >= c0->gs.n) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: query id out of range");
-
-    // rows -> devices
-    std::vector<u32> part(n_rows);
-    {
-        std::vector<u64> cost;
-        if (query_ids) {
-            std::vector<u32> len(c0->gs.L.begin(), c0->gs.L.end());
-            cost.resize(n_rows);
-            int rc = lzani_row_costs(n_rows, ref_ids, row_off, query_ids, c0->gs.n, len.data(), cost.data());
-            if (rc != LZANI_OK) return gfail(g, rc, "lzani_group_run_rows: row costs");
-        }
-        lzani_partition_rows(n_rows, query_ids ? cost.data() : nullptr, nd, part.data());
-    }
-    struct Shard { std::vector<u32> rows, ref, q; std::vector<u64> off; u64 base = 0; };
-    std::vector<Shard> sh(nd);
-    for (auto& s : sh) s.off.push_back(0);
-    for (u32 k = 0; k < n_rows; ++k) {
-        Shard& s = sh[part[k]];
-        s.rows.push_back(k);
-        s.ref.push_back(ref_ids[k]);
-        if (query_ids) s.q.insert(s.q.end(), query_ids + row_off[k], query_ids + row_off[k + 1]);
-        s.off.push_back(s.off.back() + (row_off[k + 1] - row_off[k]));
-    }
-    for (u32 d = 1; d < nd; ++d) sh[d].base = sh[d - 1].base + sh[d - 1].off.back();
-
-    // device 0 holds the gathered buffer (its own shard is written in place) and the CSR-ordered copy
-    {
-        const hipError_t e = hipSetDevice(c0->dev);
-        if (e != hipSuccess) return gfail(g, LZANI_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    }
-    // (grown, never shrunk; a failed growth leaves the group without buffers and the call with LZANI_ERR_NOMEM)
-    if (g->d_final.capacity() < std::max<u64>(n_pairs, 1)) {
-        g->d_all.reset(); g->d_final.reset();                    // (both released before either is made anew)
-        if (!got(g->d_all.alloc(n_pairs)) || !got(g->d_final.alloc(n_pairs))) {
-            g->d_all.reset();
-            return gfail(g, LZANI_ERR_NOMEM, "lzani_group_run_rows: result buffers on device 0");
-        }
-    }
-    int* const d_all = (int*)g->d_all.get();
-    int* const d_final = (int*)g->d_final.get();
-    g->d_shard.resize(nd);
-    std::vector<int*> d_shard(nd, nullptr);                      // where every device writes its shard
-    d_shard[0] = d_all;
-    std::vector<int> rc(nd, LZANI_OK);
-    auto one = [&](u32 d) {
-        lzani_ctx* c = g->ctx[d];
-        if (sh[d].ref.empty()) { c->run.tm = lzani_timing{}; return; }   // no row for this device
-        if (d) {
-            if (g->d_shard[d].capacity() < std::max<u64>(sh[d].off.back(), 1)) {
-                if (hipSetDevice(c->dev) != hipSuccess) { rc[d] = LZANI_ERR_DEVICE; return; }
-                if (!got(g->d_shard[d].alloc(sh[d].off.back()))) { rc[d] = LZANI_ERR_NOMEM; return; }
-            }
-            d_shard[d] = (int*)g->d_shard[d].get();
-        }
-        rc[d] = lzani_run_rows_device(c, (u32)sh[d].ref.size(), sh[d].ref.data(), sh[d].off.data(),
-                                      query_ids ? sh[d].q.data() : nullptr, d_shard[d]);
-    };
-    {
-        std::vector<std::thread> th;
-        for (u32 d = 1; d < nd; ++d) th.emplace_back(one, d);
-        one(0);
-        for (auto& t : th) t.join();
-    }
-    int ret = LZANI_OK;
-    for (u32 d = 0; d < nd && ret == LZANI_OK; ++d)
-        if (rc[d] != LZANI_OK) ret = gfail(g, rc[d], "device " + std::to_string(g->devs[d]) + ": " + lzani_last_error(g->ctx[d]));
-
-    // the gather: every peer's shard to device 0 (grouped ncclSend / ncclRecv over xGMI)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ret == LZANI_OK) {
-        hipSetDevice(c0->dev);
-        hipEventCreate(&e0); hipEventCreate(&e1);
-        hipEventRecord(e0, c0->stream);
-        if (!g->comms.empty()) {
-            ncclResult_t r = ncclGroupStart();
-            for (u32 d = 1; d < nd && r == ncclSuccess; ++d) {
-                const size_t cnt = (size_t)sh[d].off.back() * 3;
-                if (!cnt) continue;
-                hipSetDevice(g->ctx[d]->dev);
-                r = ncclSend(d_shard[d], cnt, ncclInt32, 0, g->comms[d], g->ctx[d]->stream);
-                hipSetDevice(c0->dev);
-                if (r == ncclSuccess) r = ncclRecv(d_all + 3 * sh[d].base, cnt, ncclInt32, (int)d, g->comms[0], c0->stream);
-            }
-            ncclResult_t r2 = ncclGroupEnd();
-            if (r == ncclSuccess) r = r2;
-            if (r != ncclSuccess) ret = gfail(g, LZANI_ERR_DEVICE, std::string("RCCL gather: ") + ncclGetErrorString(r));
-        } else {
-            for (u32 d = 1; d < nd; ++d)                         // rehearsal on one device: plain device copies
-                if (sh[d].off.back() && hipMemcpyAsync(d_all + 3 * sh[d].base, d_shard[d], sh[d].off.back() * 12, hipMemcpyDeviceToDevice, c0->stream) != hipSuccess)
-                    ret = gfail(g, LZANI_ERR_DEVICE, "device copy of a shard failed");
-        }
-    }
-    if (ret == LZANI_OK && n_rows) {
-        // shard order -> the caller's CSR order on device 0, then the one device-to-host copy
-        std::vector<u64> tab(3 * (size_t)n_rows), sbase((size_t)nd + 1);
-        if (lzani_plan_gather(n_rows, row_off, part.data(), nd, sbase.data(), tab.data(), tab.data() + n_rows, tab.data() + 2 * (size_t)n_rows, nullptr) != LZANI_OK)
-            ret = gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: gather plan");
-        for (u32 d = 0; d < nd && ret == LZANI_OK; ++d)
-            if (sbase[d] != sh[d].base) ret = gfail(g, LZANI_ERR_STATE, "lzani_group_run_rows: gather plan and shards disagree");
-        hipError_t e = ret == LZANI_OK ? hipSuccess : hipErrorInvalidValue;
-        if (e == hipSuccess) e = g->d_tab.reserve(tab.size());
-        unsigned long long* const d_tab = g->d_tab;
-        if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c0->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_scatter_rows, dim3(n_rows), dim3(256), 0, c0->stream, d_all, d_final, (const u64*)d_tab, (const u64*)d_tab + n_rows, (const u64*)d_tab + 2 * (size_t)n_rows);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(e1, c0->stream);
-        // the copy out: through two pinned staging buffers that take turns -- the device-to-host copy of one piece flies
-        // while the host moves the piece before it into the caller's (pageable) buffer
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-            if (!g->h_stage[k]) e = g->h_stage[k].alloc(GROUP_STAGE_BYTES);
-            if (e == hipSuccess && !g->ev_stage[k]) e = hipEventCreateWithFlags(&g->ev_stage[k], hipEventDisableTiming);
-        }
-        {
-            const size_t total = (size_t)n_pairs * 12;
-            size_t issued = 0, moved = 0;
-            size_t len[2] = {0, 0};
-            for (int k = 0; e == hipSuccess && (issued < total || moved < total); k ^= 1) {
-                if (len[k]) {                                  // the piece this buffer holds: wait for it, hand it over
-                    e = hipEventSynchronize(g->ev_stage[k]);
-                    if (e == hipSuccess) memcpy((char*)out + moved, g->h_stage[k], len[k]);
-                    moved += len[k];
-                    len[k] = 0;
-                }
-                if (e == hipSuccess && issued < total) {
-                    len[k] = std::min<size_t>(GROUP_STAGE_BYTES, total - issued);
-                    e = hipMemcpyAsync(g->h_stage[k], (const char*)d_final + issued, len[k], hipMemcpyDeviceToHost, c0->stream);
-                    if (e == hipSuccess) e = hipEventRecord(g->ev_stage[k], c0->stream);
-                    issued += len[k];
-                }
-            }
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c0->stream);
-        for (u32 d = 1; d < nd && e == hipSuccess; ++d) { hipSetDevice(g->ctx[d]->dev); e = hipStreamSynchronize(g->ctx[d]->stream); }
-        if (ret != LZANI_OK) {}                                   // (the gather plan failed: its message stands)
-        else if (e != hipSuccess) ret = gfail(g, LZANI_ERR_DEVICE, std::string("gather / copy out: ") + hipGetErrorString(e));
-        else { float ms = 0; hipEventElapsedTime(&ms, e0, e1); g->gather_ms = ms; }
-    }
-    hipSetDevice(c0->dev);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return ret;
+    GroupRun r{n_rows, ref_ids, row_off, query_ids, out};
+    int rc = group_check_rows(g, r);
+    if (rc == LZANI_OK) rc = group_partition_rows(g, r);
+    if (rc == LZANI_OK) rc = group_ensure_buffers(g, r);
+    if (rc == LZANI_OK) rc = group_run_shards(g, r);
+    if (rc == LZANI_OK) rc = group_gather(g, r);
+    if (rc == LZANI_OK) rc = group_scatter_out(g, r);
+    return rc;
 }
 
 int lzani_group_set_genome_memory(lzani_group* g, uint64_t bytes)

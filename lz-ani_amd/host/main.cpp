@@ -319,15 +319,55 @@ struct Engine {
 
 struct AlnRegion { uint32_t ref, qry; lzani_region r; };
 
+static void genome_views(const vector<Genome>& g, vector<const uint8_t*>& ptr, vector<uint32_t>& len)   // the genomes as the C-ABI takes them
+{
+    ptr.resize(g.size()); len.resize(g.size());
+    for (size_t i = 0; i < g.size(); ++i) { ptr[i] = g[i].codes.data(); len[i] = (uint32_t)g[i].codes.size(); }
+}
+
+// The devices of a run on ng GPUs, for the group and the --out-alignment shards alike: P.device + d, or what LZANI_DEVICE_LIST names (rehearsals: "0,0,0")
+static vector<int> device_list(int ng)
+{
+    vector<int> devs;
+    if (const char* e = getenv("LZANI_DEVICE_LIST")) for (const auto& x : split(e, ',')) devs.push_back(atoi(x.c_str()));
+    else for (int d = 0; d < ng; ++d) devs.push_back(P.device + d);
+    if (devs.empty()) devs.push_back(P.device);
+    return devs;
+}
+
+// A group on devs with the genomes on every device; secs (optional): the seconds of the create and of the genomes.
+static bool open_group(const Engine& E, const vector<Genome>& g, lzani_group*& grp, const vector<int>& devs, double* secs = nullptr)
+{
+    vector<const uint8_t*> ptr; vector<uint32_t> len;
+    genome_views(g, ptr, len);
+    const auto t_a = chrono::steady_clock::now();
+    int rc = E.group_create(&P.lz, (uint32_t)devs.size(), devs.data(), &grp);
+    if (rc != LZANI_OK) { cerr << "LZ matching failed: lzani_group_create failed with code " << rc << ": " << E.group_last_error(nullptr) << endl; return false; }
+    const auto t_b = chrono::steady_clock::now();
+    E.group_set_genome_memory(grp, P.gpu_mem);
+    rc = E.group_set_genomes(grp, (uint32_t)g.size(), ptr.data(), len.data());
+    if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; E.group_destroy(grp); return false; }
+    if (secs) { secs[0] = chrono::duration<double>(t_b - t_a).count(); secs[1] = chrono::duration<double>(chrono::steady_clock::now() - t_b).count(); }
+    return true;
+}
+
+// -V 2: what one GPU did (summed: a tiled all2all's sums over its calls, the k-mer words inside the candidate figure)
+static void print_gpu_timing(int dev, const lzani_timing& t, bool summed, const double* gather)
+{
+    cerr << "GPU " << dev << ": " << t.pairs << " pairs, index " << t.index_ms << " ms, ";
+    if (summed) cerr << "k-mer words + candidate stage ";
+    else cerr << "k-mer words " << t.kmers_ms << " ms, candidate stage ";
+    cerr << t.cand_ms << " ms, pair kernel " << t.pairs_ms << " ms" << (gather ? ", gather " + to_string(*gather) + " ms" : string()) << "\n";
+}
+
 // --flt-kmers: the filter rows from the device k-mer prefilter (lzani_prefilter) on the first device, for the genomes in
 // their reordered ids: a context of its own, the genomes, the stage with min_shared 1 and the threshold as min_ratio, the
 // kept pairs; symmetrised into flt.rows like a kmer-db file's.
 static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
 {
     const uint32_t n = (uint32_t)g.size();
-    vector<const uint8_t*> ptr(n);
-    vector<uint32_t> len(n);
-    for (uint32_t i = 0; i < n; ++i) { ptr[i] = g[i].codes.data(); len[i] = (uint32_t)g[i].codes.size(); }
+    vector<const uint8_t*> ptr; vector<uint32_t> len;
+    genome_views(g, ptr, len);
     lzani_ctx* ctx = nullptr;
     int rc = E.create(&P.lz, P.device, &ctx);
     if (rc != LZANI_OK) { cerr << "K-mer filter failed: lzani_create failed with code " << rc << endl; return false; }
@@ -415,63 +455,42 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
     if (P.verbosity >= 1) cerr << "All2all sparse" << endl;
     if (flt.empty()) T.init_dense(n);
     else { T.init_sparse(flt.rows); vector<vector<uint32_t>>().swap(flt.rows); }   // the reference clears filter rows as it goes (266-267)
-    vector<const uint8_t*> ptr(n);
-    vector<uint32_t> len(n), ref_ids(n);
-    for (uint32_t i = 0; i < n; ++i) { ptr[i] = g[i].codes.data(); len[i] = (uint32_t)g[i].codes.size(); ref_ids[i] = i; }
+    vector<uint32_t> ref_ids(n);
+    for (uint32_t i = 0; i < n; ++i) ref_ids[i] = i;
     const uint32_t* qids = T.dense ? nullptr : T.query_ids.data();
-    const int ng = max(1, min<int>(P.gpus, (int)max<uint32_t>(n, 1)));
+    const vector<int> devs = device_list(max(1, min<int>(P.gpus, (int)max<uint32_t>(n, 1))));
 
     if (!aln) {
-        vector<int> devs(ng);
-        for (int d = 0; d < ng; ++d) devs[d] = P.device + d;
-        if (const char* e = getenv("LZANI_DEVICE_LIST")) {       // rehearsals: e.g. "0,0,0" runs three shards on one GPU
-            devs.clear();
-            for (const auto& x : split(e, ',')) devs.push_back(atoi(x.c_str()));
-            if (devs.empty()) devs.push_back(P.device);
-        }
-        lzani_group* grp = nullptr;
-        const auto t_a = chrono::steady_clock::now();
-        int rc = E.group_create(&P.lz, (uint32_t)devs.size(), devs.data(), &grp);
-        if (rc != LZANI_OK) {
-            cerr << "LZ matching failed: lzani_group_create failed with code " << rc << ": " << E.group_last_error(nullptr) << endl;
-            return false;
-        }
-        const auto t_b = chrono::steady_clock::now();
-        E.group_set_genome_memory(grp, P.gpu_mem);
-        rc = E.group_set_genomes(grp, n, ptr.data(), len.data());
+        lzani_group* grp = nullptr; double secs[2];
+        if (!open_group(E, g, grp, devs, secs)) return false;
         const auto t_c = chrono::steady_clock::now();
-        if (rc == LZANI_OK) rc = E.group_run_rows(grp, n, ref_ids.data(), T.row_off.data(), qids, T.res.data());
+        const int rc = E.group_run_rows(grp, n, ref_ids.data(), T.row_off.data(), qids, T.res.data());
         if (P.verbosity >= 2)
-            cerr << "engine: create " << chrono::duration<double>(t_b - t_a).count() << " s, genomes to the device " << chrono::duration<double>(t_c - t_b).count()
-                 << " s, matching " << chrono::duration<double>(chrono::steady_clock::now() - t_c).count() << " s\n";
+            cerr << "engine: create " << secs[0] << " s, genomes to the device " << secs[1] << " s, matching " << chrono::duration<double>(chrono::steady_clock::now() - t_c).count() << " s\n";
         if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; E.group_destroy(grp); return false; }
         if (P.verbosity >= 2)
             for (int d = 0; d < (int)devs.size(); ++d) {
-                lzani_timing t; double gather = 0;
-                if (E.group_get_timing(grp, (uint32_t)d, &t, &gather) == LZANI_OK)
-                    cerr << "GPU " << devs[d] << ": " << t.pairs << " pairs, index " << t.index_ms << " ms, k-mer words " << t.kmers_ms
-                         << " ms, candidate stage " << t.cand_ms << " ms, pair kernel " << t.pairs_ms << " ms"
-                         << (d == 0 && devs.size() > 1 ? ", gather " + to_string(gather) + " ms" : string()) << "\n";
-                lzani_residency_info ri;
+                lzani_timing t; lzani_residency_info ri; double gather = 0;
+                if (E.group_get_timing(grp, (uint32_t)d, &t, &gather) == LZANI_OK) print_gpu_timing(devs[d], t, false, d == 0 && devs.size() > 1 ? &gather : nullptr);
                 if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) print_residency(devs[d], ri, ri.tiles, ri.block_uploads, ri.upload_ms);
             }
         E.group_destroy(grp);
         return true;
     }
 
-    // --out-alignment: the per-pair region lists are variable-length, so every GPU's shard comes back through host
-    // memory (lzani_run_rows_regions per context); the rows are dealt by the same partition as above.
+    // --out-alignment: the per-pair region lists are variable-length, so every shard comes back through host memory
+    // (lzani_run_rows_regions, a context per entry of the device list); the rows are dealt by the group's partition.
+    vector<const uint8_t*> ptr; vector<uint32_t> len;
+    genome_views(g, ptr, len);
     vector<uint32_t> part(n);
-    {
-        vector<uint64_t> cost;
-        if (!T.dense) { cost.resize(n); E.row_costs(n, ref_ids.data(), T.row_off.data(), qids, n, len.data(), cost.data()); }
-        E.partition_rows(n, T.dense ? nullptr : cost.data(), (uint32_t)ng, part.data());
-    }
-    vector<string> errs(ng);
+    vector<uint64_t> cost(T.dense ? 0 : n);
+    if (!T.dense) E.row_costs(n, ref_ids.data(), T.row_off.data(), qids, n, len.data(), cost.data());
+    E.partition_rows(n, T.dense ? nullptr : cost.data(), (uint32_t)devs.size(), part.data());
+    vector<string> errs(devs.size());
     mutex mtx;
     auto shard = [&](int d) {
         lzani_ctx* ctx = nullptr;
-        int rc = E.create(&P.lz, P.device + d, &ctx);
+        int rc = E.create(&P.lz, devs[d], &ctx);
         if (rc != LZANI_OK) { errs[d] = "lzani_create failed with code " + to_string(rc) + (rc == LZANI_ERR_PARAMS ? " (LZ parameters outside the supported envelope)" : ""); return; }
         E.set_genome_memory(ctx, P.gpu_mem);
         rc = E.set_genomes(ctx, n, ptr.data(), len.data());
@@ -504,18 +523,15 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
                 aln->push_back(AlnRegion{rows[k], T.id_at(rows[k], x.pair - row_off[k]), x});
             }
             if (P.verbosity >= 2) {
-                lzani_timing t;
-                if (E.get_timing(ctx, &t) == LZANI_OK)
-                    cerr << "GPU " << P.device + d << ": " << t.pairs << " pairs, index " << t.index_ms << " ms, k-mer words " << t.kmers_ms
-                         << " ms, candidate stage " << t.cand_ms << " ms, pair kernel " << t.pairs_ms << " ms\n";
-                lzani_residency_info ri;
-                if (E.get_residency(ctx, &ri) == LZANI_OK) print_residency(P.device + d, ri, ri.tiles, ri.block_uploads, ri.upload_ms);
+                lzani_timing t; lzani_residency_info ri;
+                if (E.get_timing(ctx, &t) == LZANI_OK) print_gpu_timing(devs[d], t, false, nullptr);
+                if (E.get_residency(ctx, &ri) == LZANI_OK) print_residency(devs[d], ri, ri.tiles, ri.block_uploads, ri.upload_ms);
             }
         }
         E.destroy(ctx);
     };
     vector<thread> th;
-    for (int d = 1; d < ng; ++d) th.emplace_back(shard, d);
+    for (int d = 1; d < (int)devs.size(); ++d) th.emplace_back(shard, d);
     shard(0);
     for (auto& t : th) t.join();
     for (auto& e : errs) if (!e.empty()) { cerr << "LZ matching failed: " << e << endl; return false; }
@@ -533,26 +549,9 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
     const uint32_t n = (uint32_t)g.size();
     if (P.verbosity >= 1) cerr << "All2all sparse" << endl;
     T.init_dense(n);
-    vector<const uint8_t*> ptr(n);
-    vector<uint32_t> len(n);
-    for (uint32_t i = 0; i < n; ++i) { ptr[i] = g[i].codes.data(); len[i] = (uint32_t)g[i].codes.size(); }
-    const int ng = max(1, min<int>(P.gpus, (int)max<uint32_t>(n, 1)));
-    vector<int> devs(ng);
-    for (int d = 0; d < ng; ++d) devs[d] = P.device + d;
-    if (const char* e = getenv("LZANI_DEVICE_LIST")) {           // rehearsals: e.g. "0,0,0" runs three shards on one GPU
-        devs.clear();
-        for (const auto& x : split(e, ',')) devs.push_back(atoi(x.c_str()));
-        if (devs.empty()) devs.push_back(P.device);
-    }
+    const vector<int> devs = device_list(max(1, min<int>(P.gpus, (int)max<uint32_t>(n, 1))));
     lzani_group* grp = nullptr;
-    int rc = E.group_create(&P.lz, (uint32_t)devs.size(), devs.data(), &grp);
-    if (rc != LZANI_OK) {
-        cerr << "LZ matching failed: lzani_group_create failed with code " << rc << ": " << E.group_last_error(nullptr) << endl;
-        return false;
-    }
-    E.group_set_genome_memory(grp, P.gpu_mem);
-    rc = E.group_set_genomes(grp, n, ptr.data(), len.data());
-    if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; E.group_destroy(grp); return false; }
+    if (!open_group(E, g, grp, devs)) return false;
 
     ResultWriter W;
     if (!W.open(g, ep)) { E.group_destroy(grp); return false; }
@@ -573,8 +572,8 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
             W.emit_rows(g, T, blk.first, blk.second);
         }
     });
-    vector<double> t_index(devs.size(), 0), t_pairs(devs.size(), 0), t_cand(devs.size(), 0);
-    vector<uint64_t> n_pairs(devs.size(), 0), r_tiles(devs.size(), 0), r_uploads(devs.size(), 0);
+    vector<lzani_timing> t_sum(devs.size(), lzani_timing{});   // (cand_ms: the k-mer words and the candidate stage)
+    vector<uint64_t> r_tiles(devs.size(), 0), r_uploads(devs.size(), 0);
     vector<double> r_upload_ms(devs.size(), 0);
     double t_gather = 0;
     // Three sets of buffers: while the GPUs run block k, one host thread lays out the row lists of block k + 1 and another
@@ -613,12 +612,12 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         Block& B = blk[k % 3];
         if (k + 1 < n_blocks) f_build = async(launch::async, build, k + 1);
         if (!B.rows.empty()) {
-            rc = E.group_run_rows(grp, (uint32_t)B.rows.size(), B.rows.data(), B.off.data(), B.q.data(), B.out.data());
+            const int rc = E.group_run_rows(grp, (uint32_t)B.rows.size(), B.rows.data(), B.off.data(), B.q.data(), B.out.data());
             if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; ok = false; }
             for (size_t d = 0; d < devs.size() && ok; ++d) {
                 lzani_timing t; double gather = 0;
                 if (E.group_get_timing(grp, (uint32_t)d, &t, &gather) == LZANI_OK) {
-                    t_index[d] += t.index_ms; t_pairs[d] += t.pairs_ms; t_cand[d] += t.cand_ms + t.kmers_ms; n_pairs[d] += t.pairs;
+                    t_sum[d].index_ms += t.index_ms; t_sum[d].pairs_ms += t.pairs_ms; t_sum[d].cand_ms += t.cand_ms + t.kmers_ms; t_sum[d].pairs += t.pairs;
                     if (d == 0) t_gather += gather;
                 }
                 lzani_residency_info ri;
@@ -634,9 +633,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
     cv.notify_one();
     if (P.verbosity >= 2 && ok) {
         cerr << "LZ matching done (" << (n + tile - 1) / tile << " blocks of " << tile << " rows); the last rows are being written" << endl;
-        for (size_t d = 0; d < devs.size(); ++d)
-            cerr << "GPU " << devs[d] << ": " << n_pairs[d] << " pairs, index " << t_index[d] << " ms, k-mer words + candidate stage " << t_cand[d]
-                 << " ms, pair kernel " << t_pairs[d] << " ms" << (d == 0 && devs.size() > 1 ? ", gather " + to_string(t_gather) + " ms" : string()) << "\n";
+        for (size_t d = 0; d < devs.size(); ++d) print_gpu_timing(devs[d], t_sum[d], true, d == 0 && devs.size() > 1 ? &t_gather : nullptr);
         for (size_t d = 0; d < devs.size(); ++d) {
             lzani_residency_info ri;
             if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) print_residency(devs[d], ri, r_tiles[d], r_uploads[d], r_upload_ms[d]);
