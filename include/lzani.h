@@ -224,8 +224,8 @@ const char *lzani_debug_kernel_name(uint32_t id);
  * The kept windows of the whole set must number fewer than 2^32 (else LZANI_ERR_ARG: lower sample_max).  The count
  * matrix is worked in tiles of rows sized by a workspace budget (half of the free device memory;
  * LZANI_PREFILTER_TILE_ROWS=<rows> forces the tile height).  The genome tables, k-mer words, index slabs and compiled
- * kernels of the context are left as they are.  Out-of-core genome sets (lzani_set_genome_memory) are out of scope:
- * LZANI_ERR_STATE.  LZANI_ERR_NOMEM where the workspace does not fit; the context then holds no prefilter result and
+ * kernels of the context are left as they are.  Out-of-core genome sets (lzani_set_genome_memory) are out of scope
+ * here (LZANI_ERR_STATE): lzani_prefilter_codes below serves them.  LZANI_ERR_NOMEM where the workspace does not fit; the context then holds no prefilter result and
  * is otherwise unchanged. */
 typedef struct lzani_prefilter_info {
     int32_t  k; uint32_t tiles;                                /* tiles: row tiles of the count matrix                */
@@ -239,6 +239,38 @@ int lzani_prefilter(lzani_ctx *ctx, int k, uint64_t sample_max, uint32_t min_sha
 /* kmers_of[n] = |K(g)|; row_off[n+1], ids[], shared[]: CSR of the kept pairs a < b (row a, ids ascending).  Any may be NULL. */
 int lzani_prefilter_fetch(lzani_ctx *ctx, uint32_t *kmers_of, uint64_t *row_off, uint32_t *ids, uint32_t *shared);
 int lzani_get_prefilter_info(const lzani_ctx *ctx, lzani_prefilter_info *info);
+
+/* The prefilter for genome sets larger than the device: the same definitions and the same results as lzani_prefilter, but
+ * the n genomes are given here, as host symbol codes in the convention of lzani_set_genomes, and need not be (and are
+ * not made) the context's genome set.  The stage reads genomes only where it extracts keys, so they stay in host memory
+ * at 1 B per base and pass through one staging buffer on the device, slice by slice; no genome tables are built.  A
+ * genome set the context holds, in-core or out-of-core -- its tables, resident halves and the blocks they hold, k-mer
+ * words, index slabs, compiled kernels -- is left as it is.  The result replaces any earlier prefilter result, is read
+ * with lzani_prefilter_fetch / lzani_get_prefilter_info (sized by this call's n) and lasts until the next prefilter or
+ * lzani_set_genomes.  Caller buffers are read only during the call.
+ *   slices   genomes in id order, contiguous runs: a new slice starts where the next genome would take the slice's sum of
+ *            len above slice_bytes (genomes of length 0 join the current slice).  slice_bytes 0 is automatic:
+ *            min(sum len, max(longest genome, free device memory / 8)); LZANI_PREFILTER_SLICE_BYTES=<bytes> overrides the
+ *            argument.  A genome longer than the slice size: LZANI_ERR_ARG (the message names the minimum).
+ *   sweeps   each of the three key sweeps (count, canonical k-mers, rank keys) goes over all slices: up, down, up; the
+ *            slice the staging buffer holds is not copied again.  S slices: 3 S - 2 copies (S where no window is kept:
+ *            only the count sweep runs).
+ * LZANI_ERR_ARG for n == 0, NULL pointers, k outside 8 .. 31, a negative or NaN ratio, a sequence too long for 32-bit
+ * positions; LZANI_ERR_NOMEM where the staging buffer or the workspace does not fit: the context then holds no prefilter
+ * result and is otherwise unchanged. */
+int lzani_prefilter_codes(lzani_ctx *ctx, uint32_t n, const uint8_t *const *codes, const uint32_t *len,
+                          int k, uint64_t sample_max, uint32_t min_shared, double min_ratio,
+                          uint64_t slice_bytes, uint64_t *n_entries);
+/* The slice plan as a pure host function (no GPU): slice_of[g] (may be NULL) under the given slice size; returns the
+ * number of slices (slice_bytes 0: one), or LZANI_ERR_ARG (no genomes, a genome longer than slice_bytes). */
+int lzani_plan_slices(uint32_t n, const uint32_t *len, uint64_t slice_bytes, uint32_t *slice_of);
+typedef struct lzani_prefilter_stream_info {
+    uint32_t slices, slice_uploads;      /* slices of the plan; host-to-device slice copies made            */
+    uint64_t staged_bytes, stage_bytes;  /* bytes copied in all; capacity of the staging buffer             */
+    double   upload_ms;                  /* HIP events around the slice copies, on the context's stream     */
+} lzani_prefilter_stream_info;
+/* LZANI_ERR_STATE unless the context's current prefilter result came from lzani_prefilter_codes. */
+int lzani_get_prefilter_stream_info(const lzani_ctx *ctx, lzani_prefilter_stream_info *info);
 
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker

@@ -265,7 +265,10 @@ struct PrefilterWork {
 };
 struct Prefilter {
     bool done = false;
+    u32 n = 0;                            // genomes of the prefilter that made the result (lzani_prefilter_codes: not gs.n)
+    bool streamed = false;                // made by lzani_prefilter_codes: sinfo holds
     lzani_prefilter_info info{};
+    lzani_prefilter_stream_info sinfo{};
     DevMem<u32> kmers_of;                 // |K(g)|
     std::vector<u64> row_off;             // CSR of the kept pairs (n + 1)
     std::vector<PrefilterTile> tiles;     // in row order
@@ -1471,7 +1474,9 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
 
 namespace {
 
-// Device time of the prefilter's four stages: pairs of events on the context's stream, summed per stage at the end.
+// Device time of the prefilter's stages (and of the streamed form's slice copies): pairs of events on the context's stream,
+// summed per stage at the end.
+enum { PF_ST_KEYS = 0, PF_ST_SORT = 1, PF_ST_COUNT = 2, PF_ST_COMPACT = 3, PF_ST_UPLOAD = 4, PF_STAGES = 5 };
 struct PfClock {
     hipStream_t stream;
     std::vector<hipEvent_t> ev;           // begin, end, begin, end, ...
@@ -1490,7 +1495,7 @@ struct PfClock {
     }
     hipError_t begin(int st) { stage.push_back(st); return mark(); }
     hipError_t end() { return mark(); }
-    hipError_t collect(double ms[4])
+    hipError_t collect(double ms[PF_STAGES])
     {
         for (size_t k = 0; k + 1 < ev.size(); k += 2) {
             float t = 0;
@@ -1502,8 +1507,6 @@ struct PfClock {
         return hipSuccess;
     }
 };
-enum { PF_ST_KEYS = 0, PF_ST_SORT = 1, PF_ST_COUNT = 2, PF_ST_COMPACT = 3 };
-
 int pf_sort(lzani_ctx* c, PrefilterWork& w, const unsigned long long* in, unsigned long long* out, size_t n, int b0, int b1)
 {
     size_t need = w.tmp.capacity();
@@ -1512,26 +1515,102 @@ int pf_sort(lzani_ctx* c, PrefilterWork& w, const unsigned long long* in, unsign
     return LZANI_OK;
 }
 
-// The stage itself: fills pf (a fresh Prefilter) from the resident genome set.
-int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_shared, double min_ratio)
+// The slice plan of the streamed prefilter (lzani_plan_slices): genomes in id order into contiguous slices; a new slice
+// starts where the next genome would take the slice's sum of lengths above slice_bytes (so genomes of length 0 join the
+// current one).  first[s] .. first[s + 1] are slice s's genomes.  slice_bytes 0: one slice.  Returns the number of
+// slices, or LZANI_ERR_ARG with the reason in msg.
+int plan_slices_impl(u32 n, const u32* len, u64 slice_bytes, std::vector<u32>& first, std::string& msg)
 {
-    const u32 n = c->gs.n;
+    if (!n || !len) { msg = "empty input"; return LZANI_ERR_ARG; }
+    first.assign(1, 0);
+    if (slice_bytes == 0) { first.push_back(n); return 1; }
+    u32 Lmax = 0;
+    for (u32 g = 0; g < n; ++g) Lmax = std::max(Lmax, len[g]);
+    if ((u64)Lmax > slice_bytes) {
+        msg = "slice size of " + std::to_string(slice_bytes) + " bytes is below the minimum of " + std::to_string(Lmax) +
+              " bytes (a slice must hold the longest genome)";
+        return LZANI_ERR_ARG;
+    }
+    if ((u64)n > 0x7FFFFFFFull) { msg = "too many genomes"; return LZANI_ERR_ARG; }
+    u64 cur = 0;
+    for (u32 g = 0; g < n; ++g) {
+        if (cur + len[g] > slice_bytes) { first.push_back(g); cur = 0; }
+        cur += len[g];
+    }
+    first.push_back(n);
+    return (int)first.size() - 1;
+}
+
+// The streamed key source of the prefilter (lzani_prefilter_codes): the genomes stay in the caller's host memory, 1 B a
+// base, and pass slice by slice through one staging buffer on the device.  A key sweep goes over all slices, up or
+// down; the slice the buffer holds already is not copied again.
+struct PfStream {
+    const uint8_t* const* codes = nullptr;
+    const u32* len = nullptr;
+    std::vector<u32> first;               // the slice plan
+    std::vector<u64> bytes;               // per slice: the sum of its genomes' lengths
+    DevMem<unsigned char> stage;          // the largest slice
+    DevMem<u64> d_off;                    // per genome: its byte offset in the staging buffer when its slice is there
+    DevMem<u32> d_len;
+    std::vector<unsigned char> bounce;    // host side of a copy: the genomes' codes put together, a piece at a time
+    int staged = -1;                      // the slice in the buffer
+    lzani_prefilter_stream_info info{};
+};
+enum : u64 { PF_BOUNCE_BYTES = 64ull << 20 };
+
+// Slice s into the staging buffer: the codes of its genomes one after the other, through the bounce buffer.
+int pf_upload_slice(lzani_ctx* c, PfStream& st, PfClock& clk, u32 s)
+{
+    u64 at = 0;
+    size_t fill = 0;
+    auto flush = [&]() -> int {
+        if (!fill) return LZANI_OK;
+        HIPCHK(c, clk.begin(PF_ST_UPLOAD));
+        HIPCHK(c, hipMemcpyAsync(st.stage.get() + at, st.bounce.data(), fill, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, clk.end());
+        HIPCHK(c, hipStreamSynchronize(c->stream));            // (the bounce buffer is filled again)
+        at += fill;
+        fill = 0;
+        return LZANI_OK;
+    };
+    for (u32 g = st.first[s]; g < st.first[s + 1]; ++g) {
+        const uint8_t* src = st.codes[g];
+        for (u64 left = st.len[g]; left;) {
+            const size_t take = (size_t)std::min<u64>(left, st.bounce.size() - fill);
+            memcpy(st.bounce.data() + fill, src, take);
+            fill += take; src += take; left -= take;
+            if (fill == st.bounce.size()) if (int rc = flush()) return rc;
+        }
+    }
+    if (int rc = flush()) return rc;
+    st.staged = (int)s;
+    ++st.info.slice_uploads;
+    st.info.staged_bytes += st.bytes[s];
+    return LZANI_OK;
+}
+
+// The stage itself: fills pf (a fresh Prefilter) from the resident genome set, or (st given) from the n genomes of the
+// streamed source.  The two differ in where the three key sweeps take their genomes from; all behind them is shared.
+int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_shared, double min_ratio, u32 n, PfStream* st = nullptr)
+{
     PrefilterWork& w = pf.work;
     lzani_prefilter_info& info = pf.info;
     info.k = k;
+    pf.n = n;
     min_shared = std::max<u32>(min_shared, 1);
     PfClock clk(c->stream);
-    const GenomeTab G = gtab(c);
+    const GenomeTab G = st ? GenomeTab{} : gtab(c);
+    auto len_of = [&](u32 g) -> u64 { return st ? (u64)st->len[g] : (u64)c->gs.L[g]; };
 
     // chunks of PF_CHUNK forward positions, genome after genome
     std::vector<u64> cbase((size_t)n + 1, 0);
-    int Lmax = 0;
+    u64 Lmax = 0;
     for (u32 g = 0; g < n; ++g) {
-        cbase[g + 1] = cbase[g] + ((u64)c->gs.L[g] + PF_CHUNK - 1) / PF_CHUNK;
-        Lmax = std::max(Lmax, c->gs.L[g]);
+        cbase[g + 1] = cbase[g] + (len_of(g) + PF_CHUNK - 1) / PF_CHUNK;
+        Lmax = std::max(Lmax, len_of(g));
     }
     const u64 n_chunks = cbase[n];
-    const u32 gx = (u32)(((u64)Lmax + PF_CHUNK - 1) / PF_CHUNK);
+    const u32 gx = (u32)((Lmax + PF_CHUNK - 1) / PF_CHUNK);
     HIPCHK(c, w.cbase.alloc((size_t)n + 1));
     HIPCHK(c, w.blkcnt.alloc(n_chunks));
     HIPCHK(c, w.blkoff.alloc(n_chunks + 1));
@@ -1540,14 +1619,47 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
     HIPCHK(c, hipMemsetAsync(pf.kmers_of, 0, (size_t)n * 4, c->stream));
     pf.row_off.assign((size_t)n + 1, 0);
 
-    // gridDim.y is limited to 65535: slices of genomes
-    auto keys = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) {
+    // ---- the key source.  Resident: one sweep is a launch over all genomes (gridDim.y is limited to 65535: groups of genomes)
+    auto keys_resident = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
+        HIPCHK(c, clk.begin(PF_ST_KEYS));
         for (u32 g0 = 0; gx && g0 < n; g0 += 32768) {
             const dim3 gd(gx, std::min<u32>(32768, n - g0));
             if (mode == PF_COUNT) hipLaunchKernelGGL(k_pf_keys<PF_COUNT>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
             else if (mode == PF_CANON) hipLaunchKernelGGL(k_pf_keys<PF_CANON>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
             else hipLaunchKernelGGL(k_pf_keys<PF_RANK>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
         }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.end());
+        return LZANI_OK;
+    };
+    // Streamed: the slices in the sweep's direction -- copied unless the buffer holds it, then the launch over its genomes
+    auto keys_streamed = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
+        const u32 S = (u32)st->first.size() - 1;
+        const bool up = mode != PF_CANON;
+        for (u32 i = 0; i < S; ++i) {
+            const u32 s = up ? i : S - 1 - i;
+            if (st->staged != (int)s) if (int rc = pf_upload_slice(c, *st, clk, s)) return rc;
+            const u32 f = st->first[s], ns = st->first[s + 1] - f;
+            u64 lmax = 0;
+            for (u32 g = f; g < f + ns; ++g) lmax = std::max<u64>(lmax, st->len[g]);
+            const u32 sgx = (u32)((lmax + PF_CHUNK - 1) / PF_CHUNK);
+            HIPCHK(c, clk.begin(PF_ST_KEYS));
+            for (u32 y0 = 0; sgx && y0 < ns; y0 += 32768) {
+                const dim3 gd(sgx, std::min<u32>(32768, ns - y0));
+                const unsigned char* sg = st->stage.get();
+                const u64* so = st->d_off.get() + f;
+                const u32* sl = st->d_len.get() + f;
+                if (mode == PF_COUNT) hipLaunchKernelGGL(k_pf_keys_codes<PF_COUNT>, gd, dim3(PF_THREADS), 0, c->stream, sg, st->bytes[s], so, sl, w.cbase.get(), f, y0, k, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+                else if (mode == PF_CANON) hipLaunchKernelGGL(k_pf_keys_codes<PF_CANON>, gd, dim3(PF_THREADS), 0, c->stream, sg, st->bytes[s], so, sl, w.cbase.get(), f, y0, k, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+                else hipLaunchKernelGGL(k_pf_keys_codes<PF_RANK>, gd, dim3(PF_THREADS), 0, c->stream, sg, st->bytes[s], so, sl, w.cbase.get(), f, y0, k, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+            }
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, clk.end());
+        }
+        return LZANI_OK;
+    };
+    auto keys = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
+        return st ? keys_streamed(mode, dict, D, out) : keys_resident(mode, dict, D, out);
     };
     // the total of a scan, read back
     auto scan_total = [&](const u32* cnt, u64 cnt_n, u64* off, u64& total) -> int {
@@ -1569,8 +1681,8 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
 
     // ---- keys: the kept windows counted, then their canonical k-mers in position order
     u64 Pv = 0;
+    if (int rc = keys(PF_COUNT, nullptr, 0, nullptr)) return rc;
     HIPCHK(c, clk.begin(PF_ST_KEYS));
-    keys(PF_COUNT, nullptr, 0, nullptr);
     if (int rc = scan_total(w.blkcnt, n_chunks, w.blkoff, Pv)) return rc;
     HIPCHK(c, clk.end());
     if (Pv >= 0xFFFFFFF0ull)
@@ -1588,10 +1700,7 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
                 return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
             HIPCHK(c, w.tmp.alloc(std::max(need1, need2)));
         }
-        HIPCHK(c, clk.begin(PF_ST_KEYS));
-        keys(PF_CANON, nullptr, 0, w.ka.get());
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.end());
+        if (int rc = keys(PF_CANON, nullptr, 0, w.ka.get())) return rc;
         // ---- dictionary: the keys sorted, every distinct k-mer once; its place is its rank
         HIPCHK(c, clk.begin(PF_ST_SORT));
         if (int rc = pf_sort(c, w, w.ka, w.kb, Pv, 0, 2 * k)) return rc;
@@ -1599,10 +1708,8 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
         HIPCHK(c, clk.end());
         // ---- postings: rank << 32 | genome of every kept window, in genome order; a stable sort by rank leaves the genomes of
         // a rank ascending; adjacent duplicates dropped, a run of equal rank lists the genomes that hold the k-mer
-        HIPCHK(c, clk.begin(PF_ST_KEYS));
-        keys(PF_RANK, w.ka.get(), D, w.kb.get());
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.end());
+        if (int rc = keys(PF_RANK, w.ka.get(), D, w.kb.get())) return rc;
+        if (st) { HIPCHK(c, hipStreamSynchronize(c->stream)); st->stage.reset(); }        // (the last sweep is done: room for the count matrix)
         HIPCHK(c, clk.begin(PF_ST_SORT));
         if (int rc = pf_sort(c, w, w.kb, w.ka, Pv, 32, 32 + ceil_log2(D))) return rc;
         if (int rc = uniq(w.ka, Pv, w.kb, pf.kmers_of.get(), M)) return rc;
@@ -1659,9 +1766,10 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
     }
     info.entries = entries;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    double ms[4] = {0, 0, 0, 0};
+    double ms[PF_STAGES] = {0, 0, 0, 0, 0};
     HIPCHK(c, clk.collect(ms));
     info.keys_ms = ms[PF_ST_KEYS]; info.sort_ms = ms[PF_ST_SORT]; info.count_ms = ms[PF_ST_COUNT]; info.compact_ms = ms[PF_ST_COMPACT];
+    if (st) st->info.upload_ms = ms[PF_ST_UPLOAD];
     TRACE("prefilter: k=%d positions=%llu distinct=%llu postings=%llu entries=%llu tiles=%u", k, (unsigned long long)Pv, (unsigned long long)D,
           (unsigned long long)M, (unsigned long long)entries, info.tiles);
     return LZANI_OK;
@@ -2146,12 +2254,84 @@ int lzani_prefilter(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_share
     HIPCHK(c, hipSetDevice(c->dev));
     c->pf = Prefilter{};                                       // the last result goes first: two need not fit
     Prefilter pf;
-    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio);
+    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, c->gs.n);
     if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }     // (pf releases what it held)
     pf.work = PrefilterWork{};
     pf.done = true;
     c->pf = std::move(pf);
     if (n_entries) *n_entries = c->pf.info.entries;
+    return LZANI_OK;
+}
+
+int lzani_plan_slices(uint32_t n, const uint32_t* len, uint64_t slice_bytes, uint32_t* slice_of)
+{
+    std::vector<u32> first;
+    std::string msg;
+    const int ns = plan_slices_impl(n, len, slice_bytes, first, msg);
+    if (ns > 0 && slice_of)
+        for (int s = 0; s < ns; ++s) std::fill(slice_of + first[s], slice_of + first[s + 1], (uint32_t)s);
+    return ns;
+}
+
+int lzani_prefilter_codes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
+                          uint32_t min_shared, double min_ratio, uint64_t slice_bytes, uint64_t* n_entries)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (!n || !codes || !len) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: empty input");
+    if (k < 8 || k > 31) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: k must be 8 .. 31");
+    if (!(min_ratio >= 0)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: min_ratio must be a number >= 0");
+    u64 total = 0, Lmax = 0;
+    for (u32 g = 0; g < n; ++g) {
+        if (len[g] > 0x3FFFFFFFu - 3u * (u32)c->P.mrd)
+            return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: sequence too long for 32-bit text positions");
+        if (len[g] && !codes[g]) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: null sequence");
+        total += len[g];
+        Lmax = std::max<u64>(Lmax, len[g]);
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->pf = Prefilter{};                                       // the last result goes first: two need not fit
+    if (const auto forced = env_u64("LZANI_PREFILTER_SLICE_BYTES")) slice_bytes = *forced;
+    if (slice_bytes == 0) {                                    // automatic: an eighth of the free device memory (a choice, not a measurement)
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        slice_bytes = std::max<u64>(1, std::min<u64>(total, std::max<u64>(Lmax, (u64)free_b / 8)));
+    }
+    PfStream st;
+    st.codes = codes; st.len = len;
+    std::string msg;
+    const int S = plan_slices_impl(n, len, slice_bytes, st.first, msg);
+    if (S < 0) return fail(c, S, "lzani_prefilter_codes: " + msg);
+    std::vector<u64> off(n);
+    st.bytes.assign((size_t)S, 0);
+    for (int s = 0; s < S; ++s)
+        for (u32 g = st.first[s]; g < st.first[s + 1]; ++g) { off[g] = st.bytes[s]; st.bytes[s] += len[g]; }
+    const u64 cap = *std::max_element(st.bytes.begin(), st.bytes.end());
+    st.info.slices = (uint32_t)S;
+    st.info.stage_bytes = cap;
+    HIPCHK(c, st.stage.alloc(cap));
+    HIPCHK(c, st.d_off.alloc(n));
+    HIPCHK(c, st.d_len.alloc(n));
+    HIPCHK(c, hipMemcpyAsync(st.d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    st.bounce.resize((size_t)std::max<u64>(1, std::min<u64>(cap, PF_BOUNCE_BYTES)));
+    Prefilter pf;
+    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, n, &st);
+    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }     // (pf and st release what they held)
+    pf.work = PrefilterWork{};
+    pf.done = true;
+    pf.streamed = true;
+    pf.sinfo = st.info;
+    c->pf = std::move(pf);
+    if (n_entries) *n_entries = c->pf.info.entries;
+    return LZANI_OK;
+}
+
+int lzani_get_prefilter_stream_info(const lzani_ctx* c, lzani_prefilter_stream_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->pf.done || !c->pf.streamed) return LZANI_ERR_STATE;
+    *info = c->pf.sinfo;
     return LZANI_OK;
 }
 
@@ -2161,7 +2341,7 @@ int lzani_prefilter_fetch(lzani_ctx* c, uint32_t* kmers_of, uint64_t* row_off, u
     if (!c->pf.done) return fail(c, LZANI_ERR_STATE, "lzani_prefilter_fetch: no prefilter result (call lzani_prefilter first)");
     HIPCHK(c, hipSetDevice(c->dev));
     const Prefilter& pf = c->pf;
-    const u32 n = c->gs.n;
+    const u32 n = pf.n;
     // everything into buffers of our own first: the caller's are written only on success
     std::vector<u32> h_k(kmers_of ? n : 0), h_ids(ids ? pf.info.entries : 0), h_sh(shared ? pf.info.entries : 0);
     if (kmers_of) HIPCHK(c, hipMemcpy(h_k.data(), pf.kmers_of, (size_t)n * 4, hipMemcpyDeviceToHost));

@@ -4,6 +4,8 @@
 //   k_pf_keys     one thread per forward position: canonical, sampled k-mer (pf_canon / pf_keep over kmer_at of both
 //                 strands) -- counted per block, then written compacted in position order; a third pass writes
 //                 rank << 32 | genome  with the k-mer's rank found in the sorted dictionary
+//   k_pf_keys_codes  the same keys from raw symbol codes in a staging buffer (lzani_prefilter_codes: genomes that are not
+//                 resident), staged and packed in LDS; the other strand arithmetically from the forward value
 //   k_pf_uniq     a sorted array without its adjacent duplicates (counted per block, then written): the dictionary of
 //                 distinct k-mers from the sorted keys, the postings from the sorted (rank, genome) keys
 //   k_pf_scan     exclusive prefix of per-block / per-row counts (one block; the arrays are 1/4096 of the data)
@@ -81,6 +83,83 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys(GenomeTab G, const u64* 
         const u64 p = chunk0 + (u64)it * PF_THREADS + threadIdx.x;
         u64 key = 0;
         const bool ok = p < (u64)L && pf_key_at(G, g, L, (int)p, k, mrd, sample_max, key);
+        if (MODE == PF_COUNT) mine += ok;
+        else {
+            u32 tot;
+            const u32 r = pf_block_rank(ok, s_w, tot);
+            if (ok) out[base + r] = MODE == PF_CANON ? key : ((u64)pf_find(dict, D, key) << 32) | (u64)g;
+            base += tot;
+        }
+    }
+    if (MODE == PF_COUNT) {
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        if (threadIdx.x == 0) blkcnt[blk] = s_cnt;
+    }
+}
+
+// k_pf_keys for genomes that are not resident (lzani_prefilter_codes): their raw symbol codes, 1 B each, lie one after the
+// other in a staging buffer, at any byte offset.  Block (x, y) = chunk x of genome y0 + y OF THE SLICE (soff / slen: its
+// byte offset in the buffer and its length); its global id, for cbase and the PF_RANK keys, is gfirst + y0 + y.  The
+// block brings the codes of its chunk and of the k - 1 symbols behind it -- cut at the genome's end, so that no window
+// sees the next genome's codes -- into LDS with aligned 16-byte loads, packs them there (pf_pack16), and every thread
+// forms its windows from LDS (pf_window; the other strand by pf_rc_of).  Same counts, same keys in the same order as
+// k_pf_keys.  slice_bytes: the bytes of the buffer that hold the slice; none beyond is read.
+enum { PF_GROUPS = PF_CHUNK / 16 + 4 };           // groups of 16 symbols: PF_CHUNK + 30 symbols, and the two groups pf_window reads on
+template <int MODE>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_keys_codes(const unsigned char* __restrict__ stage, u64 slice_bytes, const u64* __restrict__ soff,
+                                                              const u32* __restrict__ slen, const u64* __restrict__ cbase, u32 gfirst, u32 y0, int k,
+                                                              u64 sample_max, u32* __restrict__ blkcnt, const u64* __restrict__ blkoff,
+                                                              const unsigned long long* __restrict__ dict, u64 D, unsigned long long* __restrict__ out)
+{
+    __shared__ uint4 s_raw[PF_GROUPS];            // the codes as they lie in the buffer, from the 16-byte boundary before the chunk
+    __shared__ u32 s_t2[PF_GROUPS];
+    __shared__ unsigned short s_nm[PF_GROUPS];
+    __shared__ u32 s_w[PF_THREADS / 64];
+    __shared__ u32 s_cnt;
+    const u32 y = y0 + blockIdx.y;
+    const u32 g = gfirst + y;
+    const int L = (int)slen[y];
+    const u64 chunk0 = (u64)blockIdx.x * PF_CHUNK;
+    if (chunk0 >= (u64)L) return;
+    const int cnt = (int)(((u64)L - chunk0) < (u64)(PF_CHUNK + k - 1) ? ((u64)L - chunk0) : (u64)(PF_CHUNK + k - 1));      // symbols staged
+    const u64 b0 = soff[y] + chunk0;
+    const u64 a0 = b0 & ~15ULL;
+    const int shift = (int)(b0 & 15ULL);
+    const int n16 = (shift + cnt + 15) >> 4;      // <= (15 + PF_CHUNK + 30 + 15) / 16 < PF_GROUPS
+    for (int i = threadIdx.x; i < n16; i += PF_THREADS) {
+        const u64 a = a0 + 16ULL * (u64)i;
+        uint4 v;
+        if (a + 16 <= slice_bytes) v = *reinterpret_cast<const uint4*>(stage + a);
+        else {                                    // the slice's last bytes
+            u32 wd[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) if (a + j < slice_bytes) wd[j >> 2] |= (u32)stage[a + j] << (8 * (j & 3));
+            v = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+        }
+        s_raw[i] = v;
+    }
+    __syncthreads();
+    const unsigned char* raw = reinterpret_cast<const unsigned char*>(s_raw) + shift;
+    for (int j = threadIdx.x; j < PF_GROUPS; j += PF_THREADS) {
+        const int left = cnt - 16 * j;
+        u32 sym, nb;
+        pf_pack16(raw + 16 * j, left < 0 ? 0 : (left > 16 ? 16 : left), sym, nb);
+        s_t2[j] = sym;
+        s_nm[j] = (unsigned short)nb;
+    }
+    if (MODE == PF_COUNT && threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u64 blk = cbase[g] + blockIdx.x;
+    u64 base = MODE == PF_COUNT ? 0 : blkoff[blk];
+    u32 mine = 0;
+    for (int it = 0; it < PF_PER_THREAD; ++it) {
+        if (chunk0 + (u64)it * PF_THREADS >= (u64)L) break;              // (the same for the whole block)
+        const int q = it * PF_THREADS + (int)threadIdx.x;
+        u64 f = 0, key = 0;
+        bool ok = chunk0 + (u64)q + (u64)k <= (u64)L && pf_window(s_t2, s_nm, q, k, f);
+        if (ok) { key = pf_canon(f, pf_rc_of(f, k)); ok = pf_keep(key, sample_max); }
         if (MODE == PF_COUNT) mine += ok;
         else {
             u32 tot;

@@ -7,7 +7,8 @@
 // with dlopen so that this binary builds and its ingest/emit code is testable without ROCm present).
 // Extras over the reference: --flt-kmers <k> <thr> (the filter rows made on the GPU from the genomes themselves, in place
 // of a kmer-db file), --gpus <n> (rows dealt cyclically over n GPUs), --device <id>, --gpu-mem <size>
-// (genome-memory limit per GPU: larger sets run out-of-core, in tiles of genome blocks),
+// (genome-memory limit per GPU: larger sets run out-of-core, in tiles of genome blocks; with --flt-kmers the filter then
+// streams the genomes from host memory in slices of at most that size),
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
 #include <dlfcn.h>
 
@@ -132,7 +133,9 @@ static void usage()
          << "  -V, --verbose <int>            - verbosity level (default: 1)\n"
          << "      --gpus <int>               - number of GPUs to shard the reference rows over (default: 1)\n"
          << "      --gpu-mem <size>           - genome-memory limit per GPU in bytes, suffix K/M/G allowed; larger genome sets\n"
-         << "                                   stay in host memory and run in tiles of genome blocks (default: 0 = automatic)\n"
+         << "                                   stay in host memory and run in tiles of genome blocks (default: 0 = automatic);\n"
+         << "                                   with --flt-kmers also the size of the filter's staging buffer: the genomes are\n"
+         << "                                   then streamed from host memory in slices of at most <size> bytes\n"
          << "      --device <int>             - first HIP device ordinal (default: 0)\n";
 }
 
@@ -295,6 +298,8 @@ struct Engine {
     int (*prefilter)(lzani_ctx*, int, uint64_t, uint32_t, double, uint64_t*) = nullptr;
     int (*prefilter_fetch)(lzani_ctx*, uint32_t*, uint64_t*, uint32_t*, uint32_t*) = nullptr;
     int (*get_prefilter_info)(const lzani_ctx*, lzani_prefilter_info*) = nullptr;
+    int (*prefilter_codes)(lzani_ctx*, uint32_t, const uint8_t* const*, const uint32_t*, int, uint64_t, uint32_t, double, uint64_t, uint64_t*) = nullptr;
+    int (*get_prefilter_stream_info)(const lzani_ctx*, lzani_prefilter_stream_info*) = nullptr;
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -311,7 +316,7 @@ struct Engine {
         BIND(row_costs) BIND(partition_rows)
         BIND(group_create) BIND(group_destroy) BIND(group_last_error) BIND(group_set_genomes) BIND(group_run_rows) BIND(group_get_timing)
         BIND(set_genome_memory) BIND(get_residency) BIND(group_set_genome_memory) BIND(group_get_residency)
-        BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info)
+        BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info) BIND(prefilter_codes) BIND(get_prefilter_stream_info)
 #undef BIND
         return true;
     }
@@ -360,9 +365,11 @@ static void print_gpu_timing(int dev, const lzani_timing& t, bool summed, const 
     cerr << t.cand_ms << " ms, pair kernel " << t.pairs_ms << " ms" << (gather ? ", gather " + to_string(*gather) + " ms" : string()) << "\n";
 }
 
-// --flt-kmers: the filter rows from the device k-mer prefilter (lzani_prefilter) on the first device, for the genomes in
-// their reordered ids: a context of its own, the genomes, the stage with min_shared 1 and the threshold as min_ratio, the
-// kept pairs; symmetrised into flt.rows like a kmer-db file's.
+// --flt-kmers: the filter rows from the device k-mer prefilter on the first device, for the genomes in their reordered
+// ids: a context of its own, the stage with min_shared 1 and the threshold as min_ratio, the kept pairs; symmetrised into
+// flt.rows like a kmer-db file's.  Without --gpu-mem the genomes become the context's set and lzani_prefilter runs on
+// them; with it -- or where that set went out-of-core or did not fit -- the genomes stay in host memory and
+// lzani_prefilter_codes streams them through a staging buffer of at most --gpu-mem bytes (automatic without).
 static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
 {
     const uint32_t n = (uint32_t)g.size();
@@ -374,15 +381,34 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
     uint64_t kept = 0;
     vector<uint64_t> row_off((size_t)n + 1, 0);
     vector<uint32_t> ids;
-    rc = E.set_genomes(ctx, n, ptr.data(), len.data());
-    if (rc == LZANI_OK) rc = E.prefilter(ctx, P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, &kept);
+    bool streamed = P.gpu_mem != 0;
+    if (streamed) rc = E.prefilter_codes(ctx, n, ptr.data(), len.data(), P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, P.gpu_mem, &kept);
+    else {
+        rc = E.set_genomes(ctx, n, ptr.data(), len.data());
+        if (rc == LZANI_OK) rc = E.prefilter(ctx, P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, &kept);
+        if (rc == LZANI_ERR_STATE || rc == LZANI_ERR_NOMEM) {             // the set went out-of-core, or does not fit: a fresh context, streamed
+            E.destroy(ctx);
+            ctx = nullptr;
+            rc = E.create(&P.lz, P.device, &ctx);
+            if (rc != LZANI_OK) { cerr << "K-mer filter failed: lzani_create failed with code " << rc << endl; return false; }
+            streamed = true;
+            rc = E.prefilter_codes(ctx, n, ptr.data(), len.data(), P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, 0, &kept);
+        }
+    }
     if (rc == LZANI_OK) { ids.resize(kept); rc = E.prefilter_fetch(ctx, nullptr, row_off.data(), ids.data(), nullptr); }
     if (rc != LZANI_OK) { cerr << "K-mer filter failed: " << E.last_error(ctx) << endl; E.destroy(ctx); return false; }
     lzani_prefilter_info pi;
+    lzani_prefilter_stream_info si;
+    string stream_note;
+    if (streamed && E.get_prefilter_stream_info(ctx, &si) == LZANI_OK) {
+        ostringstream ss;
+        ss << "; streamed: " << si.slices << " slice(s), " << si.slice_uploads << " upload(s), upload " << si.upload_ms << " ms, staging " << si.stage_bytes << " bytes";
+        stream_note = ss.str();
+    }
     if (P.verbosity >= 2 && E.get_prefilter_info(ctx, &pi) == LZANI_OK)
         cerr << "k-mer filter on device " << P.device << ": k " << pi.k << ", " << pi.positions << " sampled windows, " << pi.distinct_kmers
              << " distinct k-mers, " << pi.postings << " postings, " << pi.entries << " kept pairs, " << pi.tiles << " tile(s); keys " << pi.keys_ms
-             << " ms, sorts " << pi.sort_ms << " ms, counting " << pi.count_ms << " ms, compaction " << pi.compact_ms << " ms\n";
+             << " ms, sorts " << pi.sort_ms << " ms, counting " << pi.count_ms << " ms, compaction " << pi.compact_ms << " ms" << stream_note << "\n";
     E.destroy(ctx);
     flt.names.clear();
     filter_from_pairs(n, row_off, ids, flt);

@@ -34,7 +34,8 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name",
            "lzani_set_genome_memory", "lzani_plan_blocks", "lzani_get_residency", "lzani_group_set_genome_memory",
            "lzani_group_get_residency", "lzani_debug_index_slab", "lzani_debug_run_candidates",
-           "lzani_prefilter", "lzani_prefilter_fetch", "lzani_get_prefilter_info")
+           "lzani_prefilter", "lzani_prefilter_fetch", "lzani_get_prefilter_info",
+           "lzani_prefilter_codes", "lzani_plan_slices", "lzani_get_prefilter_stream_info")
 
 
 class LzaniError(RuntimeError):
@@ -86,6 +87,11 @@ class PrefilterInfo(C.Structure):
     _fields_ = [("k", C.c_int32), ("tiles", C.c_uint32), ("positions", C.c_uint64), ("distinct_kmers", C.c_uint64),
                 ("postings", C.c_uint64), ("entries", C.c_uint64), ("keys_ms", C.c_double), ("sort_ms", C.c_double),
                 ("count_ms", C.c_double), ("compact_ms", C.c_double)]
+
+
+class PrefilterStreamInfo(C.Structure):
+    _fields_ = [("slices", C.c_uint32), ("slice_uploads", C.c_uint32), ("staged_bytes", C.c_uint64), ("stage_bytes", C.c_uint64),
+                ("upload_ms", C.c_double)]
 
 
 SAMPLE_ALL = 0xFFFFFFFFFFFFFFFF                     # lzani_prefilter's sample_max that keeps every k-mer
@@ -166,6 +172,10 @@ def load_library():
         lib.lzani_prefilter.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p]
         lib.lzani_prefilter_fetch.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         lib.lzani_get_prefilter_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_prefilter_codes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_double,
+                                              C.c_uint64, C.c_void_p]
+        lib.lzani_plan_slices.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.lzani_get_prefilter_stream_info.argtypes = [C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -239,6 +249,17 @@ def plan_blocks(lens, params=None, limit=0):
     if nb < 0:
         raise LzaniError(f"lzani_plan_blocks: {ERRORS.get(nb, nb)}")
     return nb, block_of
+
+
+def plan_slices(lens, slice_bytes):
+    """Slice plan of the streamed prefilter (lzani_plan_slices; no GPU needed): (number of slices, slice_of[n])."""
+    lib = load_library()
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    slice_of = np.zeros(len(lens), dtype=np.uint32)
+    ns = lib.lzani_plan_slices(len(lens), _ptr(lens), C.c_uint64(int(slice_bytes)), _ptr(slice_of))
+    if ns < 0:
+        raise LzaniError(f"lzani_plan_slices: {ERRORS.get(ns, ns)}")
+    return ns, slice_of
 
 
 def _residency(o):
@@ -342,6 +363,7 @@ class Engine:
             raise LzaniError(f"lzani_create failed: {ERRORS.get(rc, rc)}")
         self.h = h
         self.n = 0
+        self.pf_n = 0
         self.lens = None
 
     def close(self):
@@ -386,7 +408,27 @@ class Engine:
         cnt = C.c_uint64(0)
         self._check(self.lib.lzani_prefilter(self.h, int(k), C.c_uint64(int(sample_max)), C.c_uint32(int(min_shared)),
                                              C.c_double(float(min_ratio)), C.byref(cnt)), "lzani_prefilter")
+        self.pf_n = self.n
         return int(cnt.value)
+
+    def prefilter_codes(self, seqs, k, sample_max=SAMPLE_ALL, min_shared=1, min_ratio=0.0, slice_bytes=0):
+        """lzani_prefilter_codes: the prefilter of `seqs` streamed from host memory through a staging buffer of slice_bytes
+        (0: automatic); the context's own genome set, if any, is neither needed nor touched.  Returns the number of kept
+        pairs; prefilter_fetch() brings them, prefilter_stream_info() the slice counters."""
+        seqs = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
+        ptrs = (C.c_void_p * max(len(seqs), 1))(*[s.ctypes.data for s in seqs])
+        lens = np.array([len(s) for s in seqs], dtype=np.uint32)
+        cnt = C.c_uint64(0)
+        self._check(self.lib.lzani_prefilter_codes(self.h, len(seqs), ptrs, _ptr(lens), int(k), C.c_uint64(int(sample_max)),
+                                                   C.c_uint32(int(min_shared)), C.c_double(float(min_ratio)),
+                                                   C.c_uint64(int(slice_bytes)), C.byref(cnt)), "lzani_prefilter_codes")
+        self.pf_n = len(seqs)
+        return int(cnt.value)
+
+    def prefilter_stream_info(self):
+        o = PrefilterStreamInfo()
+        self._check(self.lib.lzani_get_prefilter_stream_info(self.h, C.byref(o)), "lzani_get_prefilter_stream_info")
+        return {k: getattr(o, k) for k, _ in PrefilterStreamInfo._fields_}
 
     def prefilter_info(self):
         o = PrefilterInfo()
@@ -395,8 +437,9 @@ class Engine:
 
     def prefilter_fetch(self):
         """(kmers_of uint32[n], row_off uint64[n + 1], ids uint32[e], shared uint32[e]): CSR of the kept pairs a < b."""
-        kmers_of = np.zeros(self.n, dtype=np.uint32)
-        row_off = np.zeros(self.n + 1, dtype=np.uint64)
+        n = self.pf_n                                   # the n of the prefilter that made the result
+        kmers_of = np.zeros(n, dtype=np.uint32)
+        row_off = np.zeros(n + 1, dtype=np.uint64)
         self._check(self.lib.lzani_prefilter_fetch(self.h, _ptr(kmers_of), _ptr(row_off), None, None), "lzani_prefilter_fetch")
         e = int(row_off[-1])
         ids = np.zeros(e, dtype=np.uint32)

@@ -7,7 +7,12 @@
 Per run: the four stage times of lzani_get_prefilter_info (HIP events), postings per second over their sum, and the
 bytes the stage's passes move per posting (counted below from the run's own sizes) against the 8 TB/s HBM roofline.
 Every figure is the median of --repeats runs after one warm-up run.
-Usage: tools/prefilter_bench.py [--out profiles/prefilter_bench.json] [--repeats 3] [--small] [--no-dense]"""
+  --streamed  instead of the two workloads: the 2,000 x 36-44 kbp set (families of 50), k = 21, every fifth k-mer, through
+              both entry points -- lzani_prefilter on the set held in-core, and lzani_prefilter_codes streaming it from host
+              memory (--slice-bytes N, or --slices K for the smallest size that gives at most K slices; default: one
+              slice) -- with both info structs and the device memory each path holds for genomes
+Usage: tools/prefilter_bench.py [--out profiles/prefilter_bench.json] [--repeats 3] [--small] [--no-dense]
+       tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--out profiles/prefilter_stream_bench.json]"""
 import argparse
 import json
 import math
@@ -66,13 +71,78 @@ def measure(eng, n, smax, min_shared, min_ratio, repeats):
     return info
 
 
+STAGES = ("keys_ms", "sort_ms", "count_ms", "compact_ms")
+
+
+def streamed(a):
+    """The same set through lzani_prefilter (in-core) and lzani_prefilter_codes (streamed): medians of the stage times."""
+    n, fam, min_shared, min_ratio = (200, 50, 5, 0.003) if a.small else (2000, 50, 5, 0.003)
+    _, seqs = SG.make_set(n, 5, fam=fam, dmax=0.10)
+    lens = [len(s) for s in seqs]
+    total = sum(lens)
+    smax = L.sample_max_of(0.2)
+    sb = a.slice_bytes or total
+    if a.slices:
+        sb = next(x for x in range(-(-total // a.slices) // 4096 * 4096, total + 4096, 4096) if x >= max(lens) and L.plan_slices(lens, x)[0] <= a.slices)
+    res = dict(tool="prefilter_bench --streamed", k=K, fraction=0.2, genomes=n, bases=total, repeats=a.repeats, slice_bytes=sb)
+
+    def median_of(runs, keys):
+        out = dict(runs[0])
+        for key in keys:
+            out[key] = float(np.median([r[key] for r in runs]))
+        return out
+
+    eng = L.Engine()
+    eng.set_genomes(seqs)
+    eng.prefilter(K, smax, min_shared, min_ratio)
+    want = eng.prefilter_fetch()
+    runs, walls = [], []
+    for _ in range(a.repeats):
+        t = time.perf_counter()
+        eng.prefilter(K, smax, min_shared, min_ratio)
+        walls.append(time.perf_counter() - t)
+        runs.append(eng.prefilter_info())
+    res["resident"] = dict(median_of(runs, STAGES), wall_ms=float(np.median(walls)) * 1e3, bytes_genomes=eng.layout()["bytes_genomes"])
+    eng.close()
+    print("resident:", json.dumps(res["resident"]), flush=True)
+
+    eng = L.Engine()
+    eng.prefilter_codes(seqs, K, smax, min_shared, min_ratio, slice_bytes=sb)
+    got = eng.prefilter_fetch()
+    same = all(np.array_equal(x, y) for x, y in zip(got, want))
+    runs, sruns, walls = [], [], []
+    for _ in range(a.repeats):
+        t = time.perf_counter()
+        eng.prefilter_codes(seqs, K, smax, min_shared, min_ratio, slice_bytes=sb)
+        walls.append(time.perf_counter() - t)
+        runs.append(eng.prefilter_info())
+        sruns.append(eng.prefilter_stream_info())
+    eng.close()
+    res["streamed"] = dict(median_of(runs, STAGES), wall_ms=float(np.median(walls)) * 1e3, stream=median_of(sruns, ("upload_ms",)),
+                           equal_to_resident=bool(same))
+    print("streamed:", json.dumps(res["streamed"]), flush=True)
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    if not same:
+        sys.exit("the streamed prefilter's result differs from the resident one's")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "prefilter_bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--small", action="store_true", help="a tenth of both sets (rehearsal)")
     ap.add_argument("--no-dense", action="store_true", help="skip the dense run of the family set")
+    ap.add_argument("--streamed", action="store_true", help="lzani_prefilter against lzani_prefilter_codes on one set")
+    ap.add_argument("--slice-bytes", type=int, default=0, help="--streamed: slice size (default: the whole set in one slice)")
+    ap.add_argument("--slices", type=int, default=0, help="--streamed: the smallest slice size (in 4 KiB steps) that gives at most this many slices")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "prefilter_stream_bench.json" if a.streamed else "prefilter_bench.json")
+    if a.streamed:
+        return streamed(a)
     n_bench, n_fam, fam = (1000, 2000, 50) if a.small else (10000, 20000, 50)
     res = dict(tool="prefilter_bench", k=K, repeats=a.repeats, hbm_roofline_bytes_per_s=HBM_BYTES_PER_S)
 
