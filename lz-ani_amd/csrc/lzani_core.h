@@ -252,6 +252,25 @@ LZ_HD u64 mix_key(u64 key, int kb)
     x = (x * 0xC2B2AE3D27D4EB4FULL) & m;
     return x;
 }
+// The mal-mer word of a text position (tables.h: kmL) from the packed text itself, mal <= 16: `syms` = the 16 symbols
+// from the position on, first symbol in the low two bits -- the low half of win2, or a funnel shift over two 32-bit
+// text words.  k_kmers stores this value; the pair kernel's refill recomputes it from the text words it reads anyway.
+LZ_HD u32 kml_from_syms(u32 syms, int mal)
+{
+    return (u32)mix_key((u64)(syms & (u32)lowmask(2 * mal)), 2 * mal);
+}
+// kmer_at's answer without the key (k < 32), from the N flags of the position (`nwin` = winN(t.nm, p), read by the caller)
+LZ_HD bool kmer_valid_n(const TextView& t, int p, int k, u64 nwin)
+{
+    return p >= 0 && p + k <= t.len && !(nwin & lowmask(k));
+}
+// the same for a genome without N (the only N of its reference text are the pads), at a position p of the text's head
+// [0, L + mrd) -- the part a query view covers: the k-mer must end inside the run of real symbols that starts at 0, which
+// is the forward strand, or both strands where no pad separates them (mrd = 0)
+LZ_HD bool kmer_valid_nfree_head(int L, int mrd, int p, int k)
+{
+    return p + k <= (mrd == 0 ? 2 * L : L);
+}
 LZ_HD void key_slot(const IndexView& I, u64 key, u32& bucket, u32& tag)
 {
     u64 h = mix_key(key, I.kb);

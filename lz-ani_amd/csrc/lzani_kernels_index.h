@@ -25,7 +25,7 @@ __global__ void k_kmers(GenomeTab G, u32* __restrict__ kmL, u32* __restrict__ km
     TextView R = ref_view(G.t2 + 2 * o, G.nm + o, G.L[g], mrd, false);
     u64 key;
     u32 a = KM_INVALID, b = KM_INVALID;
-    if (kmer_at(R, p, mal, key)) a = (u32)mix_key(key, 2 * mal);
+    if (kmer_at(R, p, mal, key)) a = kml_from_syms((u32)key, mal);       // (mal <= 15 here; DevWave::refill makes the same word from the text)
     if (kmer_at(R, p, msl, key)) {
         b = (u32)key;
         // msl 8, 9: 14 hash bits above the msl-mer -- word and bit of the pair kernel's seed bitmap (DevWave::bm_hash,

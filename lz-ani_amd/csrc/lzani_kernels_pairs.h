@@ -634,12 +634,25 @@ struct DevWave {
         lds_order();
         bool simple, dead = false;
         int pos;
+        const u32* const pq = reinterpret_cast<const u32*>(Q.t2) + ((u32)qp >> 4);
+        const u32 sq = ((u32)qp & 15u) * 2u;
+        const u32 q0 = pq[0], q1 = pq[1];
+        const u32 qlo = __builtin_amdgcn_alignbit(q1, q0, sq);
+        u64 qn = 0;                                    // N flags of the query from qp on (pairs with N)
+        bool qvalid = true;                            // bitmap form: the text the query is a prefix of has a mal-mer at qp (kmer_at)
+        if (JOIN) {
+            const TextView QR = ref_view(Q.t2, Q.nm, Q.L, P.mrd, Q.nfree);
+            if (R.nfree && Q.nfree) qvalid = kmer_valid_nfree_head(Q.L, P.mrd, qp, P.mal);
+            else { qn = winN(Q.nm, qp); qvalid = kmer_valid_n(QR, qp, P.mal, qn); }
+        }
         if (JOIN) {
             // bitmap form: the bitmap says where, not which bucket slot -- the candidate's bucket (its first four entries,
             // 16 bytes) is read whole and the entry carrying the tag picked from it: one dependent load instead of tag word
             // + entry, and no tag-word table needed (tags of any width: mid-size genomes with long k-mers)
-            const u32 hq = qkL[(u32)qp];
-            const bool ok = live & (hq != KM_INVALID);
+            // (the candidate's mal-mer word is made from the query text, which the compare below reads anyway -- what
+            // k_kmers stored at qkL[qp], without that random read in front of the bucket's)
+            const u32 hq = kml_from_syms(qlo, P.mal);
+            const bool ok = live & qvalid;
             const uint4 bkv = reinterpret_cast<const uint4*>(I.bk)[ok ? hq >> tb : 0u];
             const u32 tag = hq & I.tagmask;                  // (BK_EMPTY / BK_OVERFLOW never carry a real tag: tag + position bits <= 30)
             const bool m0 = (bkv.x >> I.posbits) == tag, m1 = (bkv.y >> I.posbits) == tag, m2 = (bkv.z >> I.posbits) == tag,
@@ -659,18 +672,23 @@ struct DevWave {
         // 32 symbols of both texts from pos / qp on, as two 32-bit words each (funnel of three dwords by v_alignbit, no branch,
         // no 64-bit shift)
         const u32* const pr = reinterpret_cast<const u32*>(R.t2) + ((u32)pos >> 4);
-        const u32* const pq = reinterpret_cast<const u32*>(Q.t2) + ((u32)qp >> 4);
-        const u32 sr = ((u32)pos & 15u) * 2u, sq = ((u32)qp & 15u) * 2u;
-        const u32 r0 = pr[0], r1 = pr[1], r2 = pr[2], q0 = pq[0], q1 = pq[1], q2 = pq[2];
-        const u32 dlo = __builtin_amdgcn_alignbit(r1, r0, sr) ^ __builtin_amdgcn_alignbit(q1, q0, sq);
-        const u32 dhi = __builtin_amdgcn_alignbit(r2, r1, sr) ^ __builtin_amdgcn_alignbit(q2, q1, sq);
+        const u32 sr = ((u32)pos & 15u) * 2u;
+        const u32 r0 = pr[0], r1 = pr[1], r2 = pr[2];
+        // (the query's upper words are read here, a second time for q1 -- an L1 hit: held across the bucket's round trip
+        // they cost a register the kernel does not have, i.e. scratch; the empty asm keeps the two reads apart)
+        const u32* pq2 = pq;
+        asm volatile("" : "+v"(pq2));
+        const u32 qhi = __builtin_amdgcn_alignbit(pq2[2], pq2[1], sq);
+        const u32 dlo = __builtin_amdgcn_alignbit(r1, r0, sr) ^ qlo;
+        const u32 dhi = __builtin_amdgcn_alignbit(r2, r1, sr) ^ qhi;
         const u32 mlo = (dlo | (dlo >> 1)) & 0x55555555u, mhi = (dhi | (dhi >> 1)) & 0x55555555u;
         int same = mlo ? ((int)__builtin_ctz(mlo) >> 1) : mhi ? 16 + ((int)__builtin_ctz(mhi) >> 1) : (int)AQ_LANE_CAP;
         int bound;
         if (R.nfree && Q.nfree) bound = imin(run_end(R, pos) - pos, run_end(Q, qp) - qp);
         else {
             bound = imin(R.len - pos, Q.len - qp);
-            const u32 nn = (u32)(winN(R.nm, pos) | winN(Q.nm, qp));
+            if (!JOIN) qn = winN(Q.nm, qp);
+            const u32 nn = (u32)(winN(R.nm, pos) | qn);
             same = imin(same, nn ? (int)__builtin_ctz(nn) : AQ_LANE_CAP);
         }
         const bool lng = (same == AQ_LANE_CAP) & (bound > AQ_LANE_CAP);
