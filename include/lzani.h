@@ -221,12 +221,34 @@ const char *lzani_debug_kernel_name(uint32_t id);
  *                  x ^= x >> 31  (mod 2^64)
  *   K(g)           the set of kept canonical k-mers of genome g; shared(a, b) = |K(a) & K(b)|
  *   kept pairs     a < b with shared >= max(min_shared, 1) and (double)shared / (double)min(|K(a)|, |K(b)|) >= min_ratio
- * The kept windows of the whole set must number fewer than 2^32 (else LZANI_ERR_ARG: lower sample_max).  The count
- * matrix is worked in tiles of rows sized by a workspace budget (half of the free device memory;
- * LZANI_PREFILTER_TILE_ROWS=<rows> forces the tile height).  The genome tables, k-mer words, index slabs and compiled
+ * K-mer passes: the workspace is 24 B per kept window (keys, sorted keys, radix scratch) and a pass of the pipeline holds
+ * fewer than 2^32 windows, so the stage runs in as many passes over disjoint classes of k-mers as that takes.  shared and
+ * |K(g)| are sums over k-mers: every pass adds into the same counts, and the results are those of one pass, bit for bit.
+ *   hash           h(x) = splitmix64(x), the hash of the sampling rule
+ *   bin            bin(x) = (h(x) >> 20) & 4095: 4,096 bins, from the hash's low half (sampling by h <= sample_max does not
+ *                  skew them)
+ *   pass plan      P >= 1 contiguous bin ranges [lo_p, hi_p) that cover 0 .. 4096 in order; pass p works on exactly the
+ *                  kept canonical k-mers with lo_p <= bin(x) < hi_p
+ *   forced plan    LZANI_PREFILTER_PASSES=<P>, 1 <= P <= 4096 (else LZANI_ERR_ARG): lo_p = floor(4096 * p / P)
+ *   automatic      from the histogram of the kept windows per bin over the whole set, greedy from bin 0: a pass takes bins
+ *                  while its sum of windows stays <= cap.  cap = min(2^32 - 17, B / 24) -- 2^32 - 17 keys is what one sort
+ *                  call takes -- with B a quarter of the free device memory at the time of the call;
+ *                  LZANI_PREFILTER_MAX_WINDOWS=<w> replaces cap (a test and bench hook).  A single bin above cap:
+ *                  LZANI_ERR_ARG, the message names the bin's windows -- the one case where the answer is a lower
+ *                  sample_max.  (A forced plan is not held to cap, only to 2^32 - 17 windows per pass.)
+ *   one pass       where the whole set's kept windows are <= cap and no plan is forced (or P = 1 is): no histogram is
+ *                  taken, and the count matrix's tiles are worked over the one set of postings
+ *   several        tile outer, pass inner: every (tile, pass) rebuilds the pass's postings and adds them into the tile,
+ *                  T * P' key pipelines for T tiles and P' passes that hold a window; |K(g)| is complete after the first
+ *                  tile's passes.  The workspace is that of the fullest pass, allocated once; the tile is sized behind it
+ *   key sweeps     W = 1 where no window is kept (the count of the whole set); 3 with one pass (count, canonical k-mers,
+ *                  rank keys); 2 + 3 * T * P' with several (the count of the whole set, the histogram, three per pipeline)
+ * The count matrix is worked in tiles of rows sized by a workspace budget (half of the device memory free when the tile is
+ * allocated: behind the postings, or behind the passes' workspace; LZANI_PREFILTER_TILE_ROWS=<rows> forces the tile height).  The genome tables, k-mer words, index slabs and compiled
  * kernels of the context are left as they are.  Out-of-core genome sets (lzani_set_genome_memory) are out of scope
- * here (LZANI_ERR_STATE): lzani_prefilter_codes below serves them.  LZANI_ERR_NOMEM where the workspace does not fit; the context then holds no prefilter result and
- * is otherwise unchanged. */
+ * here (LZANI_ERR_STATE): lzani_prefilter_codes below serves them.  LZANI_ERR_NOMEM where the workspace of the fullest
+ * pass or a one-row matrix tile does not fit; after an error the context holds no prefilter result and is otherwise
+ * unchanged. */
 typedef struct lzani_prefilter_info {
     int32_t  k; uint32_t tiles;                                /* tiles: row tiles of the count matrix                */
     uint64_t positions, distinct_kmers, postings, entries;     /* valid sampled windows, distinct k-mers, (k-mer, genome) pairs, kept pairs */
@@ -239,6 +261,22 @@ int lzani_prefilter(lzani_ctx *ctx, int k, uint64_t sample_max, uint32_t min_sha
 /* kmers_of[n] = |K(g)|; row_off[n+1], ids[], shared[]: CSR of the kept pairs a < b (row a, ids ascending).  Any may be NULL. */
 int lzani_prefilter_fetch(lzani_ctx *ctx, uint32_t *kmers_of, uint64_t *row_off, uint32_t *ids, uint32_t *shared);
 int lzani_get_prefilter_info(const lzani_ctx *ctx, lzani_prefilter_info *info);
+/* The k-mer passes of the last prefilter (either entry point).  positions, distinct_kmers and postings of
+ * lzani_prefilter_info are the sums over the passes of one tile -- the classes are disjoint, so the one-pass values --
+ * and its *_ms fields sum everything that ran, the histogram sweep apart (hist_ms). */
+typedef struct lzani_prefilter_pass_info {
+    uint32_t passes, key_sweeps;          /* passes of the plan; key sweeps run in all (histogram included) */
+    uint64_t cap, largest_pass;           /* windows a pass may hold; windows of the fullest pass            */
+    uint64_t workspace_bytes;             /* ka + kb + radix scratch as allocated                            */
+    double   hist_ms;                     /* the histogram sweep (0 when P == 1 without one)                 */
+} lzani_prefilter_pass_info;
+/* LZANI_ERR_STATE without a prefilter result. */
+int lzani_get_prefilter_pass_info(const lzani_ctx *ctx, lzani_prefilter_pass_info *info);
+/* bin_lo[passes + 1] of the last prefilter (may be NULL); returns passes or a negative error */
+int lzani_prefilter_pass_plan(const lzani_ctx *ctx, uint32_t *bin_lo);
+/* the plan rule as a pure host function (no GPU): hist[4096], cap, forced (0: automatic) -> bin_lo (may be NULL; up to
+ * 4097 entries), returns P or LZANI_ERR_ARG (a bin above cap; forced above 4096).  A forced plan reads neither hist nor cap. */
+int lzani_plan_passes(const uint64_t *hist, uint64_t cap, uint32_t forced, uint32_t *bin_lo);
 
 /* The prefilter for genome sets larger than the device: the same definitions and the same results as lzani_prefilter, but
  * the n genomes are given here, as host symbol codes in the convention of lzani_set_genomes, and need not be (and are
@@ -252,9 +290,10 @@ int lzani_get_prefilter_info(const lzani_ctx *ctx, lzani_prefilter_info *info);
  *            len above slice_bytes (genomes of length 0 join the current slice).  slice_bytes 0 is automatic:
  *            min(sum len, max(longest genome, free device memory / 8)); LZANI_PREFILTER_SLICE_BYTES=<bytes> overrides the
  *            argument.  A genome longer than the slice size: LZANI_ERR_ARG (the message names the minimum).
- *   sweeps   each of the three key sweeps (count, canonical k-mers, rank keys) goes over all slices: up, down, up; the
- *            slice the staging buffer holds is not copied again.  S slices: 3 S - 2 copies (S where no window is kept:
- *            only the count sweep runs).
+ *   sweeps   every key sweep of every k-mer pass (W of them, see "key sweeps" above) goes over all slices, and the sweeps
+ *            alternate: up, down, up, ...; the slice the staging buffer holds is not copied again.  S slices:
+ *            W * (S - 1) + 1 copies -- 3 S - 2 with one pass, S where no window is kept.  The staging buffer stays
+ *            until the last sweep of the last tile, so with several passes the matrix tile is sized beside it.
  * LZANI_ERR_ARG for n == 0, NULL pointers, k outside 8 .. 31, a negative or NaN ratio, a sequence too long for 32-bit
  * positions; LZANI_ERR_NOMEM where the staging buffer or the workspace does not fit: the context then holds no prefilter
  * result and is otherwise unchanged. */

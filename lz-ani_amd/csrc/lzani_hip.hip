@@ -269,6 +269,8 @@ struct Prefilter {
     bool streamed = false;                // made by lzani_prefilter_codes: sinfo holds
     lzani_prefilter_info info{};
     lzani_prefilter_stream_info sinfo{};
+    lzani_prefilter_pass_info pinfo{};
+    std::vector<u32> bin_lo;              // the pass plan: pass p holds the bins bin_lo[p] .. bin_lo[p + 1]
     DevMem<u32> kmers_of;                 // |K(g)|
     std::vector<u64> row_off;             // CSR of the kept pairs (n + 1)
     std::vector<PrefilterTile> tiles;     // in row order
@@ -1476,7 +1478,8 @@ namespace {
 
 // Device time of the prefilter's stages (and of the streamed form's slice copies): pairs of events on the context's stream,
 // summed per stage at the end.
-enum { PF_ST_KEYS = 0, PF_ST_SORT = 1, PF_ST_COUNT = 2, PF_ST_COMPACT = 3, PF_ST_UPLOAD = 4, PF_STAGES = 5 };
+enum { PF_ST_KEYS = 0, PF_ST_SORT = 1, PF_ST_COUNT = 2, PF_ST_COMPACT = 3, PF_ST_UPLOAD = 4, PF_ST_HIST = 5, PF_STAGES = 6 };
+constexpr u64 PF_MAX_PASS_WINDOWS = 0xFFFFFFEFull;       // what one pass may hold: the u32 run offsets of its postings, and lzani_sort_keys' limit
 struct PfClock {
     hipStream_t stream;
     std::vector<hipEvent_t> ev;           // begin, end, begin, end, ...
@@ -1589,15 +1592,44 @@ int pf_upload_slice(lzani_ctx* c, PfStream& st, PfClock& clk, u32 s)
     return LZANI_OK;
 }
 
+// The pass plan of the prefilter (lzani_plan_passes): bin_lo[0 .. P] with bin_lo[0] = 0 and bin_lo[P] = PF_BINS.  Forced:
+// P equal ranges.  Automatic: greedy from bin 0, a pass takes bins while its sum of windows stays <= cap.  Returns P, or
+// LZANI_ERR_ARG (forced above PF_BINS; a single bin above cap: *bad_bin names it).
+int plan_passes_impl(const u64* hist, u64 cap, u32 forced, std::vector<u32>& bin_lo, u32* bad_bin = nullptr)
+{
+    bin_lo.assign(1, 0);
+    if (forced) {
+        if (forced > PF_BINS) return LZANI_ERR_ARG;
+        for (u32 p = 1; p <= forced; ++p) bin_lo.push_back((u32)((u64)PF_BINS * p / forced));
+        return (int)forced;
+    }
+    if (!hist) return LZANI_ERR_ARG;
+    u64 sum = 0;
+    for (u32 b = 0; b < PF_BINS; ++b) {
+        if (hist[b] > cap) { if (bad_bin) *bad_bin = b; return LZANI_ERR_ARG; }
+        if (hist[b] > cap - sum) { bin_lo.push_back(b); sum = 0; }        // (sum <= cap always; a pass holds a bin at least)
+        sum += hist[b];
+    }
+    bin_lo.push_back(PF_BINS);
+    return (int)bin_lo.size() - 1;
+}
+
 // The stage itself: fills pf (a fresh Prefilter) from the resident genome set, or (st given) from the n genomes of the
-// streamed source.  The two differ in where the three key sweeps take their genomes from; all behind them is shared.
+// streamed source.  The two differ in where the key sweeps take their genomes from; all behind them is shared.  One
+// k-mer pass (the whole set fits the window cap and none is forced): count sweep, keys, dictionary, postings, then the
+// matrix tiles over the same postings.  Several: histogram sweep, pass plan, then tile after tile every pass's pipeline
+// on its own windows, adding into the tile.
 int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_shared, double min_ratio, u32 n, PfStream* st = nullptr)
 {
     PrefilterWork& w = pf.work;
     lzani_prefilter_info& info = pf.info;
+    lzani_prefilter_pass_info& pinfo = pf.pinfo;
     info.k = k;
     pf.n = n;
     min_shared = std::max<u32>(min_shared, 1);
+    const std::optional<u64> forced_passes = env_u64("LZANI_PREFILTER_PASSES");
+    if (forced_passes && (*forced_passes < 1 || *forced_passes > PF_BINS))
+        return fail(c, LZANI_ERR_ARG, "lzani_prefilter: LZANI_PREFILTER_PASSES must be 1 .. " + std::to_string((int)PF_BINS));
     PfClock clk(c->stream);
     const GenomeTab G = st ? GenomeTab{} : gtab(c);
     auto len_of = [&](u32 g) -> u64 { return st ? (u64)st->len[g] : (u64)c->gs.L[g]; };
@@ -1619,23 +1651,33 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
     HIPCHK(c, hipMemsetAsync(pf.kmers_of, 0, (size_t)n * 4, c->stream));
     pf.row_off.assign((size_t)n + 1, 0);
 
-    // ---- the key source.  Resident: one sweep is a launch over all genomes (gridDim.y is limited to 65535: groups of genomes)
-    auto keys_resident = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
-        HIPCHK(c, clk.begin(PF_ST_KEYS));
+    // ---- the key source: one sweep over all genomes in `mode`, of the windows whose bin lies in [lo, hi) (ranged; else of
+    // all).  PF_HIST: out is the histogram.  Resident: a sweep is a launch over all genomes (gridDim.y is limited to 65535:
+    // groups of genomes)
+    auto keys_resident = [&](int mode, bool ranged, u32 lo, u32 hi, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
+        using Fn = decltype(&k_pf_keys<PF_COUNT, false>);
+        static const Fn kernel[4][2] = {{k_pf_keys<PF_COUNT, false>, k_pf_keys<PF_COUNT, true>}, {k_pf_keys<PF_CANON, false>, k_pf_keys<PF_CANON, true>},
+                                        {k_pf_keys<PF_RANK, false>, k_pf_keys<PF_RANK, true>}, {k_pf_keys<PF_HIST, false>, k_pf_keys<PF_HIST, false>}};
+        HIPCHK(c, clk.begin(mode == PF_HIST ? PF_ST_HIST : PF_ST_KEYS));
         for (u32 g0 = 0; gx && g0 < n; g0 += 32768) {
             const dim3 gd(gx, std::min<u32>(32768, n - g0));
-            if (mode == PF_COUNT) hipLaunchKernelGGL(k_pf_keys<PF_COUNT>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
-            else if (mode == PF_CANON) hipLaunchKernelGGL(k_pf_keys<PF_CANON>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
-            else hipLaunchKernelGGL(k_pf_keys<PF_RANK>, gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+            hipLaunchKernelGGL(kernel[mode][ranged], gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, lo, hi,
+                               w.blkcnt.get(), w.blkoff.get(), dict, D, out);
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
         return LZANI_OK;
     };
-    // Streamed: the slices in the sweep's direction -- copied unless the buffer holds it, then the launch over its genomes
-    auto keys_streamed = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
+    // Streamed: the slices in the sweep's direction -- copied unless the buffer holds it, then the launch over its genomes.
+    // The sweeps alternate: up, down, up, ...
+    auto keys_streamed = [&](int mode, bool ranged, u32 lo, u32 hi, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
+        using Fn = decltype(&k_pf_keys_codes<PF_COUNT, false>);
+        static const Fn kernel[4][2] = {{k_pf_keys_codes<PF_COUNT, false>, k_pf_keys_codes<PF_COUNT, true>},
+                                        {k_pf_keys_codes<PF_CANON, false>, k_pf_keys_codes<PF_CANON, true>},
+                                        {k_pf_keys_codes<PF_RANK, false>, k_pf_keys_codes<PF_RANK, true>},
+                                        {k_pf_keys_codes<PF_HIST, false>, k_pf_keys_codes<PF_HIST, false>}};
         const u32 S = (u32)st->first.size() - 1;
-        const bool up = mode != PF_CANON;
+        const bool up = pinfo.key_sweeps % 2 == 0;
         for (u32 i = 0; i < S; ++i) {
             const u32 s = up ? i : S - 1 - i;
             if (st->staged != (int)s) if (int rc = pf_upload_slice(c, *st, clk, s)) return rc;
@@ -1643,23 +1685,22 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
             u64 lmax = 0;
             for (u32 g = f; g < f + ns; ++g) lmax = std::max<u64>(lmax, st->len[g]);
             const u32 sgx = (u32)((lmax + PF_CHUNK - 1) / PF_CHUNK);
-            HIPCHK(c, clk.begin(PF_ST_KEYS));
+            HIPCHK(c, clk.begin(mode == PF_HIST ? PF_ST_HIST : PF_ST_KEYS));
             for (u32 y0 = 0; sgx && y0 < ns; y0 += 32768) {
                 const dim3 gd(sgx, std::min<u32>(32768, ns - y0));
-                const unsigned char* sg = st->stage.get();
-                const u64* so = st->d_off.get() + f;
-                const u32* sl = st->d_len.get() + f;
-                if (mode == PF_COUNT) hipLaunchKernelGGL(k_pf_keys_codes<PF_COUNT>, gd, dim3(PF_THREADS), 0, c->stream, sg, st->bytes[s], so, sl, w.cbase.get(), f, y0, k, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
-                else if (mode == PF_CANON) hipLaunchKernelGGL(k_pf_keys_codes<PF_CANON>, gd, dim3(PF_THREADS), 0, c->stream, sg, st->bytes[s], so, sl, w.cbase.get(), f, y0, k, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
-                else hipLaunchKernelGGL(k_pf_keys_codes<PF_RANK>, gd, dim3(PF_THREADS), 0, c->stream, sg, st->bytes[s], so, sl, w.cbase.get(), f, y0, k, sample_max, w.blkcnt.get(), w.blkoff.get(), dict, D, out);
+                hipLaunchKernelGGL(kernel[mode][ranged], gd, dim3(PF_THREADS), 0, c->stream, (const unsigned char*)st->stage.get(), st->bytes[s],
+                                   (const u64*)(st->d_off.get() + f), (const u32*)(st->d_len.get() + f), w.cbase.get(), f, y0, k, sample_max, lo, hi,
+                                   w.blkcnt.get(), w.blkoff.get(), dict, D, out);
             }
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, clk.end());
         }
         return LZANI_OK;
     };
-    auto keys = [&](int mode, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
-        return st ? keys_streamed(mode, dict, D, out) : keys_resident(mode, dict, D, out);
+    auto keys = [&](int mode, bool ranged, u32 lo, u32 hi, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
+        const int rc = st ? keys_streamed(mode, ranged, lo, hi, dict, D, out) : keys_resident(mode, ranged, lo, hi, dict, D, out);
+        ++pinfo.key_sweeps;
+        return rc;
     };
     // the total of a scan, read back
     auto scan_total = [&](const u32* cnt, u64 cnt_n, u64* off, u64& total) -> int {
@@ -1678,100 +1719,193 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
         HIPCHK(c, hipGetLastError());
         return LZANI_OK;
     };
-
-    // ---- keys: the kept windows counted, then their canonical k-mers in position order
-    u64 Pv = 0;
-    if (int rc = keys(PF_COUNT, nullptr, 0, nullptr)) return rc;
-    HIPCHK(c, clk.begin(PF_ST_KEYS));
-    if (int rc = scan_total(w.blkcnt, n_chunks, w.blkoff, Pv)) return rc;
-    HIPCHK(c, clk.end());
-    if (Pv >= 0xFFFFFFF0ull)
-        return fail(c, LZANI_ERR_ARG, "lzani_prefilter: " + std::to_string(Pv) + " sampled k-mer windows; the stage holds fewer than 2^32: lower sample_max");
-    info.positions = Pv;
-    u64 D = 0, M = 0;
-    if (Pv) {
-        HIPCHK(c, w.ka.alloc(Pv));
-        HIPCHK(c, w.kb.alloc(Pv));
-        HIPCHK(c, w.ucnt.alloc((Pv + PF_CHUNK - 1) / PF_CHUNK));
-        HIPCHK(c, w.uoff.alloc((Pv + PF_CHUNK - 1) / PF_CHUNK + 1));
-        {
-            size_t need1 = 0, need2 = 0;
-            if (lzani_sort_keys(w.ka, w.kb, Pv, 0, 2 * k, nullptr, &need1, c->stream) != 0 || lzani_sort_keys(w.kb, w.ka, Pv, 32, 64, nullptr, &need2, c->stream) != 0)
-                return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
-            HIPCHK(c, w.tmp.alloc(std::max(need1, need2)));
-        }
-        if (int rc = keys(PF_CANON, nullptr, 0, w.ka.get())) return rc;
+    // the kept windows of a pass counted per chunk (blkcnt) and scanned (blkoff): where the two key sweeps behind it write
+    auto count_windows = [&](bool ranged, u32 lo, u32 hi, u64& Pw) -> int {
+        if (int rc = keys(PF_COUNT, ranged, lo, hi, nullptr, 0, nullptr)) return rc;
+        HIPCHK(c, clk.begin(PF_ST_KEYS));
+        if (int rc = scan_total(w.blkcnt, n_chunks, w.blkoff, Pw)) return rc;
+        HIPCHK(c, clk.end());
+        return LZANI_OK;
+    };
+    // ka, kb, the uniq counters and the radix scratch for passes of at most `windows` kept windows
+    auto alloc_keys = [&](u64 windows) -> int {
+        HIPCHK(c, w.ka.alloc(windows));
+        HIPCHK(c, w.kb.alloc(windows));
+        HIPCHK(c, w.ucnt.alloc((windows + PF_CHUNK - 1) / PF_CHUNK));
+        HIPCHK(c, w.uoff.alloc((windows + PF_CHUNK - 1) / PF_CHUNK + 1));
+        size_t need1 = 0, need2 = 0;
+        if (lzani_sort_keys(w.ka, w.kb, windows, 0, 2 * k, nullptr, &need1, c->stream) != 0 || lzani_sort_keys(w.kb, w.ka, windows, 32, 64, nullptr, &need2, c->stream) != 0)
+            return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
+        HIPCHK(c, w.tmp.alloc(std::max(need1, need2)));
+        pinfo.workspace_bytes = w.ka.bytes() + w.kb.bytes() + w.tmp.bytes();
+        return LZANI_OK;
+    };
+    // The pipeline of one pass behind its count_windows (Pw > 0 windows): dictionary in ka, then the postings in kb and
+    // where every rank's begin (runoff, allocated here unless it is large enough).  per_genome: |K(g)| += the genome's
+    // distinct k-mers of the pass.
+    auto postings_of = [&](bool ranged, u32 lo, u32 hi, u64 Pw, u32* per_genome, bool last_sweep, u64& D, u64& M) -> int {
+        if (int rc = keys(PF_CANON, ranged, lo, hi, nullptr, 0, w.ka.get())) return rc;
         // ---- dictionary: the keys sorted, every distinct k-mer once; its place is its rank
         HIPCHK(c, clk.begin(PF_ST_SORT));
-        if (int rc = pf_sort(c, w, w.ka, w.kb, Pv, 0, 2 * k)) return rc;
-        if (int rc = uniq(w.kb, Pv, w.ka, nullptr, D)) return rc;
+        if (int rc = pf_sort(c, w, w.ka, w.kb, Pw, 0, 2 * k)) return rc;
+        if (int rc = uniq(w.kb, Pw, w.ka, nullptr, D)) return rc;
         HIPCHK(c, clk.end());
         // ---- postings: rank << 32 | genome of every kept window, in genome order; a stable sort by rank leaves the genomes of
         // a rank ascending; adjacent duplicates dropped, a run of equal rank lists the genomes that hold the k-mer
-        if (int rc = keys(PF_RANK, w.ka.get(), D, w.kb.get())) return rc;
-        if (st) { HIPCHK(c, hipStreamSynchronize(c->stream)); st->stage.reset(); }        // (the last sweep is done: room for the count matrix)
+        if (int rc = keys(PF_RANK, ranged, lo, hi, w.ka.get(), D, w.kb.get())) return rc;
+        if (st && last_sweep) { HIPCHK(c, hipStreamSynchronize(c->stream)); st->stage.reset(); }      // (the last sweep is done: room for the count matrix)
         HIPCHK(c, clk.begin(PF_ST_SORT));
-        if (int rc = pf_sort(c, w, w.kb, w.ka, Pv, 32, 32 + ceil_log2(D))) return rc;
-        if (int rc = uniq(w.ka, Pv, w.kb, pf.kmers_of.get(), M)) return rc;
-        HIPCHK(c, w.runoff.alloc(D + 1));
+        if (int rc = pf_sort(c, w, w.kb, w.ka, Pw, 32, 32 + ceil_log2(D))) return rc;
+        if (int rc = uniq(w.ka, Pw, w.kb, per_genome, M)) return rc;
+        HIPCHK(c, w.runoff.reserve(D + 1));
         hipLaunchKernelGGL(k_pf_runs, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
-        w.ka.reset();                                          // (the count matrix may use the room)
-        w.tmp.reset();
-    }
-    info.distinct_kmers = D;
-    info.postings = M;
-
-    // ---- count matrix, a tile of rows at a time over the same postings, and the kept entries of its rows
-    u64 entries = 0;
-    if (M && n > 1) {
+        return LZANI_OK;
+    };
+    // the height of the matrix tile from what is free now, and the tile's buffers
+    u64 rows = 0;
+    std::vector<u64> h_off;
+    auto alloc_tile = [&]() -> int {
         size_t free_b = 0, total_b = 0;
         HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        u64 rows = std::min<u64>(n, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n)));
+        rows = std::min<u64>(n, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n)));
         if (const auto forced = env_u64("LZANI_PREFILTER_TILE_ROWS")) rows = std::min<u64>(n, std::max<u64>(1, *forced));
         HIPCHK(c, w.mat.alloc(rows * n));
         HIPCHK(c, w.rowcnt.alloc(rows));
         HIPCHK(c, w.rowoff.alloc(rows + 1));
-        std::vector<u64> h_off(rows + 1);
-        const u32 count_blocks = (u32)((M + PF_THREADS - 1) / PF_THREADS);
-        for (u64 t0 = 0; t0 < n; t0 += rows) {
-            const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n, t0 + rows), nr = r1 - r0;
-            const u32 row_blocks = (nr + PF_THREADS / 64 - 1) / (PF_THREADS / 64);
-            HIPCHK(c, clk.begin(PF_ST_COUNT));
-            HIPCHK(c, hipMemsetAsync(w.mat, 0, (size_t)nr * n * 4, c->stream));
-            hipLaunchKernelGGL(k_pf_count, dim3(count_blocks), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D, n, r0, r1, w.mat.get());
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, clk.end());
-            HIPCHK(c, clk.begin(PF_ST_COMPACT));
-            hipLaunchKernelGGL(k_pf_rows<false>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
-                               w.rowcnt.get(), w.rowoff.get(), (u32*)nullptr, (u32*)nullptr);
-            hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, w.rowcnt.get(), (u64)nr, w.rowoff.get());
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            PrefilterTile tile;
-            tile.r0 = r0; tile.r1 = r1;
-            HIPCHK(c, tile.ids.alloc(h_off[nr]));
-            HIPCHK(c, tile.shared.alloc(h_off[nr]));
-            hipLaunchKernelGGL(k_pf_rows<true>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
-                               w.rowcnt.get(), w.rowoff.get(), tile.ids.get(), tile.shared.get());
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, clk.end());
-            for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = entries + h_off[r + 1];
-            entries += h_off[nr];
-            pf.tiles.push_back(std::move(tile));
-            ++info.tiles;
-        }
+        h_off.resize(rows + 1);
+        return LZANI_OK;
+    };
+    u64 entries = 0;
+    // the postings in kb added into the tile of rows r0 .. r1; clear: the tile's first pass
+    auto count_tile = [&](u32 r0, u32 r1, u64 D, u64 M, bool clear) -> int {
+        HIPCHK(c, clk.begin(PF_ST_COUNT));
+        if (clear) HIPCHK(c, hipMemsetAsync(w.mat, 0, (size_t)(r1 - r0) * n * 4, c->stream));
+        hipLaunchKernelGGL(k_pf_count, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D, n, r0, r1, w.mat.get());
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.end());
+        return LZANI_OK;
+    };
+    // the kept entries of the tile's rows into a PrefilterTile of their own
+    auto compact_tile = [&](u32 r0, u32 r1) -> int {
+        const u32 nr = r1 - r0, row_blocks = (nr + PF_THREADS / 64 - 1) / (PF_THREADS / 64);
+        HIPCHK(c, clk.begin(PF_ST_COMPACT));
+        hipLaunchKernelGGL(k_pf_rows<false>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
+                           w.rowcnt.get(), w.rowoff.get(), (u32*)nullptr, (u32*)nullptr);
+        hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, w.rowcnt.get(), (u64)nr, w.rowoff.get());
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        PrefilterTile tile;
+        tile.r0 = r0; tile.r1 = r1;
+        HIPCHK(c, tile.ids.alloc(h_off[nr]));
+        HIPCHK(c, tile.shared.alloc(h_off[nr]));
+        hipLaunchKernelGGL(k_pf_rows<true>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
+                           w.rowcnt.get(), w.rowoff.get(), tile.ids.get(), tile.shared.get());
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.end());
+        for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = entries + h_off[r + 1];
+        entries += h_off[nr];
+        pf.tiles.push_back(std::move(tile));
+        ++info.tiles;
+        return LZANI_OK;
+    };
+
+    // ---- the kept windows of the whole set counted; whether they go in one pass
+    u64 Pv = 0;
+    if (int rc = count_windows(false, 0, PF_BINS, Pv)) return rc;
+    u64 cap = PF_MAX_PASS_WINDOWS;
+    if (const auto forced = env_u64("LZANI_PREFILTER_MAX_WINDOWS")) cap = *forced;
+    else {                                                     // a quarter of the free device memory for the 24 B per window (a choice, not a measurement)
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        cap = std::min<u64>(cap, (u64)free_b / 4 / 24);
     }
+    pinfo.cap = cap;
+    info.positions = Pv;
+    const bool one_pass = forced_passes ? *forced_passes == 1 : Pv <= cap;
+    pf.bin_lo = {0, PF_BINS};
+    u64 D = 0, M = 0;
+    if (Pv && one_pass) {
+        if (Pv > PF_MAX_PASS_WINDOWS)
+            return fail(c, LZANI_ERR_ARG, "lzani_prefilter: " + std::to_string(Pv) + " sampled k-mer windows in the one forced pass; a pass holds fewer than 2^32");
+        pinfo.largest_pass = Pv;
+        if (int rc = alloc_keys(Pv)) return rc;
+        if (int rc = postings_of(false, 0, PF_BINS, Pv, pf.kmers_of.get(), true, D, M)) return rc;
+        w.ka.reset();                                          // (the count matrix may use the room)
+        w.tmp.reset();
+        // ---- count matrix, a tile of rows at a time over the same postings, and the kept entries of its rows
+        if (M && n > 1) {
+            if (int rc = alloc_tile()) return rc;
+            for (u64 t0 = 0; t0 < n; t0 += rows) {
+                const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n, t0 + rows);
+                if (int rc = count_tile(r0, r1, D, M, true)) return rc;
+                if (int rc = compact_tile(r0, r1)) return rc;
+            }
+        }
+    } else if (Pv) {
+        // ---- several passes: the histogram of the kept windows over the bins, the plan, the workspace of the fullest pass
+        DevMem<unsigned long long> d_hist;
+        std::vector<u64> hist(PF_BINS);
+        HIPCHK(c, d_hist.alloc(PF_BINS));
+        HIPCHK(c, hipMemsetAsync(d_hist, 0, (size_t)PF_BINS * 8, c->stream));
+        if (int rc = keys(PF_HIST, false, 0, PF_BINS, nullptr, 0, d_hist.get())) return rc;
+        HIPCHK(c, hipMemcpyAsync(hist.data(), d_hist, (size_t)PF_BINS * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        d_hist.reset();
+        u32 bad_bin = 0;
+        const int np = plan_passes_impl(hist.data(), cap, forced_passes ? (u32)*forced_passes : 0u, pf.bin_lo, &bad_bin);
+        if (np < 0)
+            return fail(c, LZANI_ERR_ARG, "lzani_prefilter: bin " + std::to_string(bad_bin) + " of the k-mer passes alone holds " + std::to_string(hist[bad_bin]) +
+                                          " sampled k-mer windows, a pass at most " + std::to_string(cap) + ": lower sample_max");
+        std::vector<u64> pass_windows((size_t)np, 0);
+        for (int p = 0; p < np; ++p)
+            for (u32 b = pf.bin_lo[p]; b < pf.bin_lo[p + 1]; ++b) pass_windows[p] += hist[b];
+        const u64 largest = *std::max_element(pass_windows.begin(), pass_windows.end());
+        if (largest > PF_MAX_PASS_WINDOWS)
+            return fail(c, LZANI_ERR_ARG, "lzani_prefilter: " + std::to_string(largest) + " sampled k-mer windows in one of the forced passes; a pass holds fewer than 2^32");
+        pinfo.largest_pass = largest;
+        if (int rc = alloc_keys(largest)) return rc;
+        HIPCHK(c, w.runoff.alloc(largest + 1));                // (a pass's distinct k-mers are no more than its windows)
+        // the matrix tile from what the workspace (and the staging buffer, which stays to the last sweep) leaves
+        const bool with_matrix = n > 1;
+        if (with_matrix) { if (int rc = alloc_tile()) return rc; } else rows = n;
+        // ---- tile outer, pass inner: every (tile, pass) rebuilds the pass's postings and adds them into the tile
+        u64 Psum = 0;
+        int last_p = 0;
+        for (int p = 0; p < np; ++p) if (pass_windows[p]) last_p = p;
+        for (u64 t0 = 0; t0 < n; t0 += rows) {
+            const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n, t0 + rows);
+            bool clear = true;
+            for (int p = 0; p < np; ++p) {
+                if (!pass_windows[p]) continue;                // (nothing to add)
+                const u32 lo = pf.bin_lo[p], hi = pf.bin_lo[p + 1];
+                u64 Pw = 0, Dp = 0, Mp = 0;
+                if (int rc = count_windows(true, lo, hi, Pw)) return rc;
+                if (Pw != pass_windows[p]) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: a pass's windows differ from the histogram's");
+                if (int rc = postings_of(true, lo, hi, Pw, t0 == 0 ? pf.kmers_of.get() : nullptr, t0 + rows >= n && p == last_p, Dp, Mp)) return rc;
+                if (t0 == 0) { Psum += Pw; D += Dp; M += Mp; }
+                if (with_matrix) if (int rc = count_tile(r0, r1, Dp, Mp, clear)) return rc;
+                clear = false;
+            }
+            if (with_matrix) if (int rc = compact_tile(r0, r1)) return rc;
+        }
+        if (Psum != Pv) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: the passes' windows do not sum to the set's");
+    } else if (forced_passes)
+        plan_passes_impl(nullptr, cap, (u32)*forced_passes, pf.bin_lo);
+    pinfo.passes = (u32)pf.bin_lo.size() - 1;
+    info.distinct_kmers = D;
+    info.postings = M;
     info.entries = entries;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    double ms[PF_STAGES] = {0, 0, 0, 0, 0};
+    double ms[PF_STAGES] = {0, 0, 0, 0, 0, 0};
     HIPCHK(c, clk.collect(ms));
     info.keys_ms = ms[PF_ST_KEYS]; info.sort_ms = ms[PF_ST_SORT]; info.count_ms = ms[PF_ST_COUNT]; info.compact_ms = ms[PF_ST_COMPACT];
+    pinfo.hist_ms = ms[PF_ST_HIST];
     if (st) st->info.upload_ms = ms[PF_ST_UPLOAD];
-    TRACE("prefilter: k=%d positions=%llu distinct=%llu postings=%llu entries=%llu tiles=%u", k, (unsigned long long)Pv, (unsigned long long)D,
-          (unsigned long long)M, (unsigned long long)entries, info.tiles);
+    TRACE("prefilter: k=%d positions=%llu distinct=%llu postings=%llu entries=%llu tiles=%u passes=%u", k, (unsigned long long)Pv, (unsigned long long)D,
+          (unsigned long long)M, (unsigned long long)entries, info.tiles, pinfo.passes);
     return LZANI_OK;
 }
 
@@ -2333,6 +2467,30 @@ int lzani_get_prefilter_stream_info(const lzani_ctx* c, lzani_prefilter_stream_i
     if (!c->pf.done || !c->pf.streamed) return LZANI_ERR_STATE;
     *info = c->pf.sinfo;
     return LZANI_OK;
+}
+
+int lzani_get_prefilter_pass_info(const lzani_ctx* c, lzani_prefilter_pass_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->pf.done) return LZANI_ERR_STATE;
+    *info = c->pf.pinfo;
+    return LZANI_OK;
+}
+
+int lzani_prefilter_pass_plan(const lzani_ctx* c, uint32_t* bin_lo)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (!c->pf.done) return LZANI_ERR_STATE;
+    if (bin_lo) std::copy(c->pf.bin_lo.begin(), c->pf.bin_lo.end(), bin_lo);
+    return (int)c->pf.bin_lo.size() - 1;
+}
+
+int lzani_plan_passes(const uint64_t* hist, uint64_t cap, uint32_t forced, uint32_t* bin_lo)
+{
+    std::vector<u32> lo;
+    const int np = plan_passes_impl(hist, cap, forced, lo);
+    if (np > 0 && bin_lo) std::copy(lo.begin(), lo.end(), bin_lo);
+    return np;
 }
 
 int lzani_prefilter_fetch(lzani_ctx* c, uint32_t* kmers_of, uint64_t* row_off, uint32_t* ids, uint32_t* shared)

@@ -3,7 +3,9 @@
 // Included by lzani_hip.hip only (after lzani_tables.h).  Exact integer work:
 //   k_pf_keys     one thread per forward position: canonical, sampled k-mer (pf_canon / pf_keep over kmer_at of both
 //                 strands) -- counted per block, then written compacted in position order; a third pass writes
-//                 rank << 32 | genome  with the k-mer's rank found in the sorted dictionary
+//                 rank << 32 | genome  with the k-mer's rank found in the sorted dictionary.  RANGED: only the windows of
+//                 one k-mer pass, pf_bin(k-mer) in [bin_lo, bin_hi).  A fourth mode adds every kept window into the
+//                 histogram of the PF_BINS bins (per block in LDS, then one atomic add per non-empty bin)
 //   k_pf_keys_codes  the same keys from raw symbol codes in a staging buffer (lzani_prefilter_codes: genomes that are not
 //                 resident), staged and packed in LDS; the other strand arithmetically from the forward value
 //   k_pf_uniq     a sorted array without its adjacent duplicates (counted per block, then written): the dictionary of
@@ -20,7 +22,7 @@
 namespace lzani {
 
 enum { PF_THREADS = 256, PF_PER_THREAD = 16, PF_CHUNK = PF_THREADS * PF_PER_THREAD };
-enum { PF_COUNT = 0, PF_CANON = 1, PF_RANK = 2 };
+enum { PF_COUNT = 0, PF_CANON = 1, PF_RANK = 2, PF_HIST = 3 };
 
 // Among the block's PF_THREADS threads: how many threads before this one raise `flag`; total: how many in all.
 __device__ __forceinline__ u32 pf_block_rank(bool flag, u32* s_w, u32& total)
@@ -60,30 +62,58 @@ __device__ __forceinline__ u32 pf_find(const unsigned long long* __restrict__ di
     return (u32)lo;
 }
 
+// Whether a kept k-mer belongs to the pass of bins [lo, hi).  Not RANGED: every one does, and nothing is computed.
+template <bool RANGED>
+__device__ __forceinline__ bool pf_in_pass(u64 key, u32 lo, u32 hi)
+{
+    if (!RANGED) return true;
+    const u32 b = pf_bin(key);
+    return b >= lo && b < hi;
+}
+
+// PF_HIST: the block's histogram in LDS cleared / added into hist[PF_BINS], the empty bins left out.
+__device__ __forceinline__ void pf_hist_clear(u32* s_hist)
+{
+    for (int i = threadIdx.x; i < PF_BINS; i += PF_THREADS) s_hist[i] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ void pf_hist_flush(const u32* s_hist, unsigned long long* __restrict__ hist)
+{
+    __syncthreads();
+    for (int i = threadIdx.x; i < PF_BINS; i += PF_THREADS) {
+        const u32 c = s_hist[i];
+        if (c) atomicAdd(&hist[i], (unsigned long long)c);
+    }
+}
+
 // Block (x, y) = chunk x of PF_CHUNK forward positions of genome g0 + y; its number in the count / offset arrays is
 // cbase[g] + x.  COUNT: blkcnt[block] = kept windows.  CANON / RANK: they are written from blkoff[block] on, in position
-// order -- the canonical k-mer, or  rank in dict << 32 | genome.
-template <int MODE>
+// order -- the canonical k-mer, or  rank in dict << 32 | genome.  RANGED: of the kept windows only those of the pass
+// [bin_lo, bin_hi).  HIST (never RANGED): out is the histogram u64[PF_BINS]; blkcnt / blkoff are not touched.
+template <int MODE, bool RANGED>
 __global__ void __launch_bounds__(PF_THREADS) k_pf_keys(GenomeTab G, const u64* __restrict__ cbase, u32 g0, int k, int mrd, u64 sample_max,
-                                                        u32* __restrict__ blkcnt, const u64* __restrict__ blkoff,
+                                                        u32 bin_lo, u32 bin_hi, u32* __restrict__ blkcnt, const u64* __restrict__ blkoff,
                                                         const unsigned long long* __restrict__ dict, u64 D, unsigned long long* __restrict__ out)
 {
     __shared__ u32 s_w[PF_THREADS / 64];
     __shared__ u32 s_cnt;
+    __shared__ u32 s_hist[MODE == PF_HIST ? PF_BINS : 1];
     const u32 g = g0 + blockIdx.y;
     const int L = G.L[g];
     const u64 chunk0 = (u64)blockIdx.x * PF_CHUNK;
     if (chunk0 >= (u64)L) return;
     const u64 blk = cbase[g] + blockIdx.x;
-    u64 base = MODE == PF_COUNT ? 0 : blkoff[blk];
+    u64 base = MODE == PF_COUNT || MODE == PF_HIST ? 0 : blkoff[blk];
     u32 mine = 0;
     if (MODE == PF_COUNT) { if (threadIdx.x == 0) s_cnt = 0; __syncthreads(); }
+    if (MODE == PF_HIST) pf_hist_clear(s_hist);
     for (int it = 0; it < PF_PER_THREAD; ++it) {
         if (chunk0 + (u64)it * PF_THREADS >= (u64)L) break;              // (the same for the whole block)
         const u64 p = chunk0 + (u64)it * PF_THREADS + threadIdx.x;
         u64 key = 0;
-        const bool ok = p < (u64)L && pf_key_at(G, g, L, (int)p, k, mrd, sample_max, key);
+        const bool ok = p < (u64)L && pf_key_at(G, g, L, (int)p, k, mrd, sample_max, key) && pf_in_pass<RANGED>(key, bin_lo, bin_hi);
         if (MODE == PF_COUNT) mine += ok;
+        else if (MODE == PF_HIST) { if (ok) atomicAdd(&s_hist[pf_bin(key)], 1u); }
         else {
             u32 tot;
             const u32 r = pf_block_rank(ok, s_w, tot);
@@ -97,6 +127,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys(GenomeTab G, const u64* 
         __syncthreads();
         if (threadIdx.x == 0) blkcnt[blk] = s_cnt;
     }
+    if (MODE == PF_HIST) pf_hist_flush(s_hist, out);
 }
 
 // k_pf_keys for genomes that are not resident (lzani_prefilter_codes): their raw symbol codes, 1 B each, lie one after the
@@ -107,10 +138,10 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys(GenomeTab G, const u64* 
 // forms its windows from LDS (pf_window; the other strand by pf_rc_of).  Same counts, same keys in the same order as
 // k_pf_keys.  slice_bytes: the bytes of the buffer that hold the slice; none beyond is read.
 enum { PF_GROUPS = PF_CHUNK / 16 + 4 };           // groups of 16 symbols: PF_CHUNK + 30 symbols, and the two groups pf_window reads on
-template <int MODE>
+template <int MODE, bool RANGED>
 __global__ void __launch_bounds__(PF_THREADS) k_pf_keys_codes(const unsigned char* __restrict__ stage, u64 slice_bytes, const u64* __restrict__ soff,
                                                               const u32* __restrict__ slen, const u64* __restrict__ cbase, u32 gfirst, u32 y0, int k,
-                                                              u64 sample_max, u32* __restrict__ blkcnt, const u64* __restrict__ blkoff,
+                                                              u64 sample_max, u32 bin_lo, u32 bin_hi, u32* __restrict__ blkcnt, const u64* __restrict__ blkoff,
                                                               const unsigned long long* __restrict__ dict, u64 D, unsigned long long* __restrict__ out)
 {
     __shared__ uint4 s_raw[PF_GROUPS];            // the codes as they lie in the buffer, from the 16-byte boundary before the chunk
@@ -118,6 +149,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys_codes(const unsigned cha
     __shared__ unsigned short s_nm[PF_GROUPS];
     __shared__ u32 s_w[PF_THREADS / 64];
     __shared__ u32 s_cnt;
+    __shared__ u32 s_hist[MODE == PF_HIST ? PF_BINS : 1];
     const u32 y = y0 + blockIdx.y;
     const u32 g = gfirst + y;
     const int L = (int)slen[y];
@@ -151,16 +183,18 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys_codes(const unsigned cha
     }
     if (MODE == PF_COUNT && threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
+    if (MODE == PF_HIST) pf_hist_clear(s_hist);
     const u64 blk = cbase[g] + blockIdx.x;
-    u64 base = MODE == PF_COUNT ? 0 : blkoff[blk];
+    u64 base = MODE == PF_COUNT || MODE == PF_HIST ? 0 : blkoff[blk];
     u32 mine = 0;
     for (int it = 0; it < PF_PER_THREAD; ++it) {
         if (chunk0 + (u64)it * PF_THREADS >= (u64)L) break;              // (the same for the whole block)
         const int q = it * PF_THREADS + (int)threadIdx.x;
         u64 f = 0, key = 0;
         bool ok = chunk0 + (u64)q + (u64)k <= (u64)L && pf_window(s_t2, s_nm, q, k, f);
-        if (ok) { key = pf_canon(f, pf_rc_of(f, k)); ok = pf_keep(key, sample_max); }
+        if (ok) { key = pf_canon(f, pf_rc_of(f, k)); ok = pf_keep(key, sample_max) && pf_in_pass<RANGED>(key, bin_lo, bin_hi); }
         if (MODE == PF_COUNT) mine += ok;
+        else if (MODE == PF_HIST) { if (ok) atomicAdd(&s_hist[pf_bin(key)], 1u); }
         else {
             u32 tot;
             const u32 r = pf_block_rank(ok, s_w, tot);
@@ -174,6 +208,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys_codes(const unsigned cha
         __syncthreads();
         if (threadIdx.x == 0) blkcnt[blk] = s_cnt;
     }
+    if (MODE == PF_HIST) pf_hist_flush(s_hist, out);
 }
 
 // in[0 .. n) ascending: block b takes its PF_CHUNK elements from b * PF_CHUNK on and counts (blkcnt[b]) or writes (from

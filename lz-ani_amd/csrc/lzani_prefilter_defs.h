@@ -1,7 +1,7 @@
 // lzani_prefilter_defs.h -- the definitions of the k-mer prefilter that host and device share: the canonical k-mer and
-// the sampling rule (include/lzani.h: lzani_prefilter), and how the streamed form makes a window's two values from raw
-// symbol codes.  Plain integer arithmetic mod 2^64; the kernels of lzani_kernels_prefilter.h and the host test shims
-// compile the same text.
+// the sampling rule (include/lzani.h: lzani_prefilter), the bin that assigns a k-mer to a pass, and how the streamed form
+// makes a window's two values from raw symbol codes.  Plain integer arithmetic mod 2^64; the kernels of
+// lzani_kernels_prefilter.h and the host test shims compile the same text.
 #pragma once
 #include "lzani_core.h"
 
@@ -22,6 +22,11 @@ LZ_HD u64 pf_canon(u64 fwd, u64 rc) { return fwd < rc ? fwd : rc; }
 
 // sampling: a canonical k-mer is kept iff its hash does not exceed sample_max (all ones keeps everything)
 LZ_HD bool pf_keep(u64 canon, u64 sample_max) { return pf_splitmix64(canon) <= sample_max; }
+
+// k-mer passes: the bin of a canonical k-mer, one of PF_BINS; a pass works on the k-mers of a contiguous range of bins.
+// Bits of the hash's low half: sampling by the hash's value (its high bits decide) does not skew them.
+enum { PF_BINS = 4096 };
+LZ_HD u32 pf_bin(u64 canon) { return (u32)(pf_splitmix64(canon) >> 20) & (u32)(PF_BINS - 1); }
 
 // ---- windows from raw symbol codes (the streamed prefilter, lzani_prefilter_codes): no packed text, no second strand
 

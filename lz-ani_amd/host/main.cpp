@@ -300,6 +300,7 @@ struct Engine {
     int (*get_prefilter_info)(const lzani_ctx*, lzani_prefilter_info*) = nullptr;
     int (*prefilter_codes)(lzani_ctx*, uint32_t, const uint8_t* const*, const uint32_t*, int, uint64_t, uint32_t, double, uint64_t, uint64_t*) = nullptr;
     int (*get_prefilter_stream_info)(const lzani_ctx*, lzani_prefilter_stream_info*) = nullptr;
+    int (*get_prefilter_pass_info)(const lzani_ctx*, lzani_prefilter_pass_info*) = nullptr;
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -316,7 +317,7 @@ struct Engine {
         BIND(row_costs) BIND(partition_rows)
         BIND(group_create) BIND(group_destroy) BIND(group_last_error) BIND(group_set_genomes) BIND(group_run_rows) BIND(group_get_timing)
         BIND(set_genome_memory) BIND(get_residency) BIND(group_set_genome_memory) BIND(group_get_residency)
-        BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info) BIND(prefilter_codes) BIND(get_prefilter_stream_info)
+        BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info) BIND(prefilter_codes) BIND(get_prefilter_stream_info) BIND(get_prefilter_pass_info)
 #undef BIND
         return true;
     }
@@ -399,12 +400,14 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
     if (rc != LZANI_OK) { cerr << "K-mer filter failed: " << E.last_error(ctx) << endl; E.destroy(ctx); return false; }
     lzani_prefilter_info pi;
     lzani_prefilter_stream_info si;
+    lzani_prefilter_pass_info ps;
     string stream_note;
     if (streamed && E.get_prefilter_stream_info(ctx, &si) == LZANI_OK) {
         ostringstream ss;
         ss << "; streamed: " << si.slices << " slice(s), " << si.slice_uploads << " upload(s), upload " << si.upload_ms << " ms, staging " << si.stage_bytes << " bytes";
         stream_note = ss.str();
     }
+    if (E.get_prefilter_pass_info(ctx, &ps) == LZANI_OK && ps.passes > 1) stream_note += "; " + to_string(ps.passes) + " passes";
     if (P.verbosity >= 2 && E.get_prefilter_info(ctx, &pi) == LZANI_OK)
         cerr << "k-mer filter on device " << P.device << ": k " << pi.k << ", " << pi.positions << " sampled windows, " << pi.distinct_kmers
              << " distinct k-mers, " << pi.postings << " postings, " << pi.entries << " kept pairs, " << pi.tiles << " tile(s); keys " << pi.keys_ms

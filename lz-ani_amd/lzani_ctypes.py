@@ -35,7 +35,8 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_set_genome_memory", "lzani_plan_blocks", "lzani_get_residency", "lzani_group_set_genome_memory",
            "lzani_group_get_residency", "lzani_debug_index_slab", "lzani_debug_run_candidates",
            "lzani_prefilter", "lzani_prefilter_fetch", "lzani_get_prefilter_info",
-           "lzani_prefilter_codes", "lzani_plan_slices", "lzani_get_prefilter_stream_info")
+           "lzani_prefilter_codes", "lzani_plan_slices", "lzani_get_prefilter_stream_info",
+           "lzani_get_prefilter_pass_info", "lzani_prefilter_pass_plan", "lzani_plan_passes")
 
 
 class LzaniError(RuntimeError):
@@ -94,6 +95,12 @@ class PrefilterStreamInfo(C.Structure):
                 ("upload_ms", C.c_double)]
 
 
+class PrefilterPassInfo(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("key_sweeps", C.c_uint32), ("cap", C.c_uint64), ("largest_pass", C.c_uint64),
+                ("workspace_bytes", C.c_uint64), ("hist_ms", C.c_double)]
+
+
+PREFILTER_BINS = 4096                               # bins of the prefilter's k-mer passes
 SAMPLE_ALL = 0xFFFFFFFFFFFFFFFF                     # lzani_prefilter's sample_max that keeps every k-mer
 
 
@@ -176,6 +183,9 @@ def load_library():
                                               C.c_uint64, C.c_void_p]
         lib.lzani_plan_slices.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.lzani_get_prefilter_stream_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_get_prefilter_pass_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_prefilter_pass_plan.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_plan_passes.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -249,6 +259,20 @@ def plan_blocks(lens, params=None, limit=0):
     if nb < 0:
         raise LzaniError(f"lzani_plan_blocks: {ERRORS.get(nb, nb)}")
     return nb, block_of
+
+
+def plan_passes(hist, cap, forced=0):
+    """Pass plan of the prefilter (lzani_plan_passes; no GPU needed): bin_lo[P + 1] from the windows per bin, the windows a
+    pass may hold and a forced number of passes (0: automatic)."""
+    lib = load_library()
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    if len(hist) != PREFILTER_BINS:
+        raise LzaniError(f"lzani_plan_passes: the histogram has {PREFILTER_BINS} bins")
+    bin_lo = np.zeros(PREFILTER_BINS + 1, dtype=np.uint32)
+    np_ = lib.lzani_plan_passes(_ptr(hist), C.c_uint64(int(cap)), C.c_uint32(int(forced)), _ptr(bin_lo))
+    if np_ < 0:
+        raise LzaniError(f"lzani_plan_passes: {ERRORS.get(np_, np_)}")
+    return bin_lo[:np_ + 1].copy()
 
 
 def plan_slices(lens, slice_bytes):
@@ -429,6 +453,18 @@ class Engine:
         o = PrefilterStreamInfo()
         self._check(self.lib.lzani_get_prefilter_stream_info(self.h, C.byref(o)), "lzani_get_prefilter_stream_info")
         return {k: getattr(o, k) for k, _ in PrefilterStreamInfo._fields_}
+
+    def prefilter_pass_info(self):
+        o = PrefilterPassInfo()
+        self._check(self.lib.lzani_get_prefilter_pass_info(self.h, C.byref(o)), "lzani_get_prefilter_pass_info")
+        return {k: getattr(o, k) for k, _ in PrefilterPassInfo._fields_}
+
+    def prefilter_pass_plan(self):
+        """bin_lo[passes + 1] of the last prefilter: pass p held the bins bin_lo[p] .. bin_lo[p + 1]."""
+        bin_lo = np.zeros(PREFILTER_BINS + 1, dtype=np.uint32)
+        np_ = self.lib.lzani_prefilter_pass_plan(self.h, _ptr(bin_lo))
+        self._check(min(np_, 0), "lzani_prefilter_pass_plan")
+        return bin_lo[:np_ + 1].copy()
 
     def prefilter_info(self):
         o = PrefilterInfo()

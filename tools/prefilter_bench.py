@@ -10,9 +10,11 @@ Every figure is the median of --repeats runs after one warm-up run.
   --streamed  instead of the two workloads: the 2,000 x 36-44 kbp set (families of 50), k = 21, every fifth k-mer, through
               both entry points -- lzani_prefilter on the set held in-core, and lzani_prefilter_codes streaming it from host
               memory (--slice-bytes N, or --slices K for the smallest size that gives at most K slices; default: one
-              slice) -- with both info structs and the device memory each path holds for genomes
+              slice) -- with both info structs and the device memory each path holds for genomes; --passes P forces the
+              k-mer passes of both (LZANI_PREFILTER_PASSES) and the line carries passes, key_sweeps, hist_ms and
+              workspace_bytes of lzani_get_prefilter_pass_info
 Usage: tools/prefilter_bench.py [--out profiles/prefilter_bench.json] [--repeats 3] [--small] [--no-dense]
-       tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--out profiles/prefilter_stream_bench.json]"""
+       tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--passes P] [--out profiles/prefilter_stream_bench.json]"""
 import argparse
 import json
 import math
@@ -84,7 +86,10 @@ def streamed(a):
     sb = a.slice_bytes or total
     if a.slices:
         sb = next(x for x in range(-(-total // a.slices) // 4096 * 4096, total + 4096, 4096) if x >= max(lens) and L.plan_slices(lens, x)[0] <= a.slices)
-    res = dict(tool="prefilter_bench --streamed", k=K, fraction=0.2, genomes=n, bases=total, repeats=a.repeats, slice_bytes=sb)
+    if a.passes:
+        os.environ["LZANI_PREFILTER_PASSES"] = str(a.passes)
+    res = dict(tool="prefilter_bench --streamed", k=K, fraction=0.2, genomes=n, bases=total, repeats=a.repeats, slice_bytes=sb,
+               forced_passes=a.passes)
 
     def median_of(runs, keys):
         out = dict(runs[0])
@@ -101,8 +106,9 @@ def streamed(a):
         t = time.perf_counter()
         eng.prefilter(K, smax, min_shared, min_ratio)
         walls.append(time.perf_counter() - t)
-        runs.append(eng.prefilter_info())
-    res["resident"] = dict(median_of(runs, STAGES), wall_ms=float(np.median(walls)) * 1e3, bytes_genomes=eng.layout()["bytes_genomes"])
+        runs.append(dict(eng.prefilter_info(), **eng.prefilter_pass_info()))
+    res["resident"] = dict(median_of(runs, STAGES + ("hist_ms",)), wall_ms=float(np.median(walls)) * 1e3, walls_ms=[w * 1e3 for w in walls],
+                           keys_ms_runs=[r["keys_ms"] for r in runs], bytes_genomes=eng.layout()["bytes_genomes"])
     eng.close()
     print("resident:", json.dumps(res["resident"]), flush=True)
 
@@ -115,10 +121,10 @@ def streamed(a):
         t = time.perf_counter()
         eng.prefilter_codes(seqs, K, smax, min_shared, min_ratio, slice_bytes=sb)
         walls.append(time.perf_counter() - t)
-        runs.append(eng.prefilter_info())
+        runs.append(dict(eng.prefilter_info(), **eng.prefilter_pass_info()))
         sruns.append(eng.prefilter_stream_info())
     eng.close()
-    res["streamed"] = dict(median_of(runs, STAGES), wall_ms=float(np.median(walls)) * 1e3, stream=median_of(sruns, ("upload_ms",)),
+    res["streamed"] = dict(median_of(runs, STAGES + ("hist_ms",)), wall_ms=float(np.median(walls)) * 1e3, stream=median_of(sruns, ("upload_ms",)),
                            equal_to_resident=bool(same))
     print("streamed:", json.dumps(res["streamed"]), flush=True)
     line = json.dumps(res)
@@ -138,6 +144,7 @@ def main():
     ap.add_argument("--no-dense", action="store_true", help="skip the dense run of the family set")
     ap.add_argument("--streamed", action="store_true", help="lzani_prefilter against lzani_prefilter_codes on one set")
     ap.add_argument("--slice-bytes", type=int, default=0, help="--streamed: slice size (default: the whole set in one slice)")
+    ap.add_argument("--passes", type=int, default=0, help="--streamed: force this many k-mer passes (LZANI_PREFILTER_PASSES)")
     ap.add_argument("--slices", type=int, default=0, help="--streamed: the smallest slice size (in 4 KiB steps) that gives at most this many slices")
     a = ap.parse_args()
     a.out = a.out or os.path.join(ROOT, "profiles", "prefilter_stream_bench.json" if a.streamed else "prefilter_bench.json")
