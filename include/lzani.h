@@ -311,6 +311,33 @@ typedef struct lzani_prefilter_stream_info {
 /* LZANI_ERR_STATE unless the context's current prefilter result came from lzani_prefilter_codes. */
 int lzani_get_prefilter_stream_info(const lzani_ctx *ctx, lzani_prefilter_stream_info *info);
 
+/* The cross form: a query set against a reference set.  The n genomes are one id space cut at n_ref: ids 0 .. n_ref - 1
+ * are the references, ids n_ref .. n - 1 the queries (n_query = n - n_ref).  Everything defined above stays as it is --
+ * window value, canonical k-mer, sampling, K(g), shared(a, b), the kept rule, bins, pass plan, key sweeps -- and the cross
+ * form keeps exactly the pairs a < n_ref <= b that pass the kept rule: its result is the all-pairs result of the same set
+ * restricted to those pairs, bit for bit.  kmers_of is that of all n genomes, shared that of every kept pair, ids ascend
+ * inside a row, and the rows a >= n_ref are empty.  lzani_prefilter_fetch and the info calls above read a cross result
+ * like any other: positions, distinct_kmers and postings are those of the all-pairs run (the key pipeline is the same),
+ * entries is the number of kept cross pairs.
+ *   matrix   n_ref rows of n_query counts, mat[(a - r0) * n_query + (b - n_ref)], worked in tiles of rows that cover
+ *            0 .. n_ref only: min(n_ref, max(1, free / 2 / (4 * n_query))) rows, or LZANI_PREFILTER_TILE_ROWS clipped to
+ *            n_ref.  A run of postings lists its references before its queries; only reference postings of the tile add,
+ *            and only over the queries of their run, so no add is spent on a pair that is not a cross pair.
+ * n_ref == 0 or n_ref >= n: LZANI_ERR_ARG.  Every other error, and what a failed call leaves behind, is that of the
+ * all-pairs counterpart; lzani_prefilter_cross refuses an out-of-core set with LZANI_ERR_STATE, like lzani_prefilter. */
+int lzani_prefilter_cross(lzani_ctx *ctx, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio,
+                          uint32_t n_ref, uint64_t *n_entries);                 /* resident set              */
+int lzani_prefilter_codes_cross(lzani_ctx *ctx, uint32_t n, const uint8_t *const *codes, const uint32_t *len,
+                                int k, uint64_t sample_max, uint32_t min_shared, double min_ratio,
+                                uint64_t slice_bytes, uint32_t n_ref, uint64_t *n_entries);   /* streamed    */
+typedef struct lzani_prefilter_cross_info {
+    uint32_t n_ref, n_query;       /* n_query = n - n_ref                                        */
+    uint32_t tile_rows, reserved_; /* height of the matrix tile as allocated; 0                  */
+    uint64_t matrix_bytes;         /* tile_rows * n_query * 4, as allocated                      */
+} lzani_prefilter_cross_info;
+/* LZANI_ERR_STATE unless the context's current prefilter result came from a cross call. */
+int lzani_get_prefilter_cross_info(const lzani_ctx *ctx, lzani_prefilter_cross_info *info);
+
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
  * takes a reference, builds its index once and parses every query of the row).  Rows are independent; the

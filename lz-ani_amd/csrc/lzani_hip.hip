@@ -259,7 +259,8 @@ struct PrefilterWork {
     DevMem<unsigned long long> ka, kb;            // keys, sorted keys / dictionary, rank keys / postings, in turn
     DevMem<unsigned char> tmp;    // radix-sort scratch
     DevMem<u32> runoff;           // per rank: its first posting (distinct k-mers + 1)
-    DevMem<u32> mat;              // one row tile of the count matrix, rows x n
+    DevMem<u32> runsplit;         // cross form, per rank: its first posting of a query (distinct k-mers + 1)
+    DevMem<u32> mat;              // one row tile of the count matrix, rows x n (cross form: rows x n_query)
     DevMem<u32> rowcnt;
     DevMem<u64> rowoff;
 };
@@ -267,6 +268,8 @@ struct Prefilter {
     bool done = false;
     u32 n = 0;                            // genomes of the prefilter that made the result (lzani_prefilter_codes: not gs.n)
     bool streamed = false;                // made by lzani_prefilter_codes: sinfo holds
+    bool cross = false;                   // made by a cross call: cinfo holds
+    lzani_prefilter_cross_info cinfo{};
     lzani_prefilter_info info{};
     lzani_prefilter_stream_info sinfo{};
     lzani_prefilter_pass_info pinfo{};
@@ -1618,14 +1621,19 @@ int plan_passes_impl(const u64* hist, u64 cap, u32 forced, std::vector<u32>& bin
 // streamed source.  The two differ in where the key sweeps take their genomes from; all behind them is shared.  One
 // k-mer pass (the whole set fits the window cap and none is forced): count sweep, keys, dictionary, postings, then the
 // matrix tiles over the same postings.  Several: histogram sweep, pass plan, then tile after tile every pass's pipeline
-// on its own windows, adding into the tile.
-int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_shared, double min_ratio, u32 n, PfStream* st = nullptr)
+// on its own windows, adding into the tile.  n_ref > 0: the cross form -- the matrix is the n_ref reference rows by the
+// n - n_ref query columns, its tiles cover the references only, and every set of postings gets its runsplit.
+int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_shared, double min_ratio, u32 n, PfStream* st = nullptr, u32 n_ref = 0)
 {
     PrefilterWork& w = pf.work;
     lzani_prefilter_info& info = pf.info;
     lzani_prefilter_pass_info& pinfo = pf.pinfo;
     info.k = k;
     pf.n = n;
+    const bool cross = n_ref != 0;
+    const u32 n_rows = cross ? n_ref : n, n_cols = cross ? n - n_ref : n;      // the count matrix
+    pf.cross = cross;
+    pf.cinfo.n_ref = n_ref; pf.cinfo.n_query = cross ? n_cols : 0;
     min_shared = std::max<u32>(min_shared, 1);
     const std::optional<u64> forced_passes = env_u64("LZANI_PREFILTER_PASSES");
     if (forced_passes && (*forced_passes < 1 || *forced_passes > PF_BINS))
@@ -1759,6 +1767,10 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
         if (int rc = uniq(w.ka, Pw, w.kb, per_genome, M)) return rc;
         HIPCHK(c, w.runoff.reserve(D + 1));
         hipLaunchKernelGGL(k_pf_runs, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D);
+        if (cross) {
+            HIPCHK(c, w.runsplit.reserve(D + 1));
+            hipLaunchKernelGGL(k_pf_split, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, D, n_ref, w.runsplit.get());
+        }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
         return LZANI_OK;
@@ -1769,20 +1781,22 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
     auto alloc_tile = [&]() -> int {
         size_t free_b = 0, total_b = 0;
         HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        rows = std::min<u64>(n, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n)));
-        if (const auto forced = env_u64("LZANI_PREFILTER_TILE_ROWS")) rows = std::min<u64>(n, std::max<u64>(1, *forced));
-        HIPCHK(c, w.mat.alloc(rows * n));
+        rows = std::min<u64>(n_rows, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n_cols)));
+        if (const auto forced = env_u64("LZANI_PREFILTER_TILE_ROWS")) rows = std::min<u64>(n_rows, std::max<u64>(1, *forced));
+        HIPCHK(c, w.mat.alloc(rows * n_cols));
         HIPCHK(c, w.rowcnt.alloc(rows));
         HIPCHK(c, w.rowoff.alloc(rows + 1));
         h_off.resize(rows + 1);
+        if (cross) { pf.cinfo.tile_rows = (u32)rows; pf.cinfo.matrix_bytes = w.mat.bytes(); }
         return LZANI_OK;
     };
     u64 entries = 0;
     // the postings in kb added into the tile of rows r0 .. r1; clear: the tile's first pass
     auto count_tile = [&](u32 r0, u32 r1, u64 D, u64 M, bool clear) -> int {
         HIPCHK(c, clk.begin(PF_ST_COUNT));
-        if (clear) HIPCHK(c, hipMemsetAsync(w.mat, 0, (size_t)(r1 - r0) * n * 4, c->stream));
-        hipLaunchKernelGGL(k_pf_count, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D, n, r0, r1, w.mat.get());
+        if (clear) HIPCHK(c, hipMemsetAsync(w.mat, 0, (size_t)(r1 - r0) * n_cols * 4, c->stream));
+        hipLaunchKernelGGL((cross ? k_pf_count<true> : k_pf_count<false>), dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M,
+                           w.runoff.get(), D, n, r0, r1, w.mat.get(), (const u32*)w.runsplit.get(), n_ref);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
         return LZANI_OK;
@@ -1791,8 +1805,8 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
     auto compact_tile = [&](u32 r0, u32 r1) -> int {
         const u32 nr = r1 - r0, row_blocks = (nr + PF_THREADS / 64 - 1) / (PF_THREADS / 64);
         HIPCHK(c, clk.begin(PF_ST_COMPACT));
-        hipLaunchKernelGGL(k_pf_rows<false>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
-                           w.rowcnt.get(), w.rowoff.get(), (u32*)nullptr, (u32*)nullptr);
+        hipLaunchKernelGGL((cross ? k_pf_rows<false, true> : k_pf_rows<false, false>), dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1,
+                           pf.kmers_of.get(), min_shared, min_ratio, w.rowcnt.get(), w.rowoff.get(), (u32*)nullptr, (u32*)nullptr, n_ref);
         hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, w.rowcnt.get(), (u64)nr, w.rowoff.get());
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1801,8 +1815,8 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
         tile.r0 = r0; tile.r1 = r1;
         HIPCHK(c, tile.ids.alloc(h_off[nr]));
         HIPCHK(c, tile.shared.alloc(h_off[nr]));
-        hipLaunchKernelGGL(k_pf_rows<true>, dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1, pf.kmers_of.get(), min_shared, min_ratio,
-                           w.rowcnt.get(), w.rowoff.get(), tile.ids.get(), tile.shared.get());
+        hipLaunchKernelGGL((cross ? k_pf_rows<true, true> : k_pf_rows<true, false>), dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1,
+                           pf.kmers_of.get(), min_shared, min_ratio, w.rowcnt.get(), w.rowoff.get(), tile.ids.get(), tile.shared.get(), n_ref);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
         for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = entries + h_off[r + 1];
@@ -1838,8 +1852,8 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
         // ---- count matrix, a tile of rows at a time over the same postings, and the kept entries of its rows
         if (M && n > 1) {
             if (int rc = alloc_tile()) return rc;
-            for (u64 t0 = 0; t0 < n; t0 += rows) {
-                const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n, t0 + rows);
+            for (u64 t0 = 0; t0 < n_rows; t0 += rows) {
+                const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n_rows, t0 + rows);
                 if (int rc = count_tile(r0, r1, D, M, true)) return rc;
                 if (int rc = compact_tile(r0, r1)) return rc;
             }
@@ -1868,15 +1882,16 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
         pinfo.largest_pass = largest;
         if (int rc = alloc_keys(largest)) return rc;
         HIPCHK(c, w.runoff.alloc(largest + 1));                // (a pass's distinct k-mers are no more than its windows)
+        if (cross) HIPCHK(c, w.runsplit.alloc(largest + 1));
         // the matrix tile from what the workspace (and the staging buffer, which stays to the last sweep) leaves
         const bool with_matrix = n > 1;
-        if (with_matrix) { if (int rc = alloc_tile()) return rc; } else rows = n;
+        if (with_matrix) { if (int rc = alloc_tile()) return rc; } else rows = n_rows;
         // ---- tile outer, pass inner: every (tile, pass) rebuilds the pass's postings and adds them into the tile
         u64 Psum = 0;
         int last_p = 0;
         for (int p = 0; p < np; ++p) if (pass_windows[p]) last_p = p;
-        for (u64 t0 = 0; t0 < n; t0 += rows) {
-            const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n, t0 + rows);
+        for (u64 t0 = 0; t0 < n_rows; t0 += rows) {
+            const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n_rows, t0 + rows);
             bool clear = true;
             for (int p = 0; p < np; ++p) {
                 if (!pass_windows[p]) continue;                // (nothing to add)
@@ -1884,7 +1899,7 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
                 u64 Pw = 0, Dp = 0, Mp = 0;
                 if (int rc = count_windows(true, lo, hi, Pw)) return rc;
                 if (Pw != pass_windows[p]) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: a pass's windows differ from the histogram's");
-                if (int rc = postings_of(true, lo, hi, Pw, t0 == 0 ? pf.kmers_of.get() : nullptr, t0 + rows >= n && p == last_p, Dp, Mp)) return rc;
+                if (int rc = postings_of(true, lo, hi, Pw, t0 == 0 ? pf.kmers_of.get() : nullptr, t0 + rows >= n_rows && p == last_p, Dp, Mp)) return rc;
                 if (t0 == 0) { Psum += Pw; D += Dp; M += Mp; }
                 if (with_matrix) if (int rc = count_tile(r0, r1, Dp, Mp, clear)) return rc;
                 clear = false;
@@ -1898,6 +1913,7 @@ int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_s
     info.distinct_kmers = D;
     info.postings = M;
     info.entries = entries;
+    for (size_t g = n_rows; g < n; ++g) pf.row_off[g + 1] = entries;      // (cross form: the query rows are empty)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double ms[PF_STAGES] = {0, 0, 0, 0, 0, 0};
     HIPCHK(c, clk.collect(ms));
@@ -2378,7 +2394,8 @@ int lzani_debug_run_candidates(lzani_ctx* c, uint32_t n_rows, const uint32_t* re
 }
 
 
-int lzani_prefilter(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint64_t* n_entries)
+// lzani_prefilter (n_ref null) and lzani_prefilter_cross
+static int prefilter_resident(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, const uint32_t* n_ref, uint64_t* n_entries)
 {
     if (!c) return LZANI_ERR_ARG;
     if (!c->gs.n) return fail(c, LZANI_ERR_STATE, "lzani_prefilter: no genomes (call lzani_set_genomes first)");
@@ -2387,14 +2404,25 @@ int lzani_prefilter(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_share
     if (!(min_ratio >= 0)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter: min_ratio must be a number >= 0");
     HIPCHK(c, hipSetDevice(c->dev));
     c->pf = Prefilter{};                                       // the last result goes first: two need not fit
+    if (n_ref && (*n_ref == 0 || *n_ref >= c->gs.n)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_cross: n_ref must be 1 .. n - 1");
     Prefilter pf;
-    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, c->gs.n);
+    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, c->gs.n, nullptr, n_ref ? *n_ref : 0);
     if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }     // (pf releases what it held)
     pf.work = PrefilterWork{};
     pf.done = true;
     c->pf = std::move(pf);
     if (n_entries) *n_entries = c->pf.info.entries;
     return LZANI_OK;
+}
+
+int lzani_prefilter(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint64_t* n_entries)
+{
+    return prefilter_resident(c, k, sample_max, min_shared, min_ratio, nullptr, n_entries);
+}
+
+int lzani_prefilter_cross(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint32_t n_ref, uint64_t* n_entries)
+{
+    return prefilter_resident(c, k, sample_max, min_shared, min_ratio, &n_ref, n_entries);
 }
 
 int lzani_plan_slices(uint32_t n, const uint32_t* len, uint64_t slice_bytes, uint32_t* slice_of)
@@ -2407,8 +2435,9 @@ int lzani_plan_slices(uint32_t n, const uint32_t* len, uint64_t slice_bytes, uin
     return ns;
 }
 
-int lzani_prefilter_codes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
-                          uint32_t min_shared, double min_ratio, uint64_t slice_bytes, uint64_t* n_entries)
+// lzani_prefilter_codes (n_ref null) and lzani_prefilter_codes_cross
+static int prefilter_streamed(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
+                              uint32_t min_shared, double min_ratio, uint64_t slice_bytes, const uint32_t* n_ref, uint64_t* n_entries)
 {
     if (!c) return LZANI_ERR_ARG;
     if (!n || !codes || !len) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: empty input");
@@ -2424,6 +2453,7 @@ int lzani_prefilter_codes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes,
     }
     HIPCHK(c, hipSetDevice(c->dev));
     c->pf = Prefilter{};                                       // the last result goes first: two need not fit
+    if (n_ref && (*n_ref == 0 || *n_ref >= n)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes_cross: n_ref must be 1 .. n - 1");
     if (const auto forced = env_u64("LZANI_PREFILTER_SLICE_BYTES")) slice_bytes = *forced;
     if (slice_bytes == 0) {                                    // automatic: an eighth of the free device memory (a choice, not a measurement)
         size_t free_b = 0, total_b = 0;
@@ -2450,7 +2480,7 @@ int lzani_prefilter_codes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes,
     HIPCHK(c, hipStreamSynchronize(c->stream));
     st.bounce.resize((size_t)std::max<u64>(1, std::min<u64>(cap, PF_BOUNCE_BYTES)));
     Prefilter pf;
-    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, n, &st);
+    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, n, &st, n_ref ? *n_ref : 0);
     if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }     // (pf and st release what they held)
     pf.work = PrefilterWork{};
     pf.done = true;
@@ -2458,6 +2488,26 @@ int lzani_prefilter_codes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes,
     pf.sinfo = st.info;
     c->pf = std::move(pf);
     if (n_entries) *n_entries = c->pf.info.entries;
+    return LZANI_OK;
+}
+
+int lzani_prefilter_codes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
+                          uint32_t min_shared, double min_ratio, uint64_t slice_bytes, uint64_t* n_entries)
+{
+    return prefilter_streamed(c, n, codes, len, k, sample_max, min_shared, min_ratio, slice_bytes, nullptr, n_entries);
+}
+
+int lzani_prefilter_codes_cross(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
+                                uint32_t min_shared, double min_ratio, uint64_t slice_bytes, uint32_t n_ref, uint64_t* n_entries)
+{
+    return prefilter_streamed(c, n, codes, len, k, sample_max, min_shared, min_ratio, slice_bytes, &n_ref, n_entries);
+}
+
+int lzani_get_prefilter_cross_info(const lzani_ctx* c, lzani_prefilter_cross_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->pf.done || !c->pf.cross) return LZANI_ERR_STATE;
+    *info = c->pf.cinfo;
     return LZANI_OK;
 }
 

@@ -12,8 +12,10 @@
 //                 distinct k-mers from the sorted keys, the postings from the sorted (rank, genome) keys
 //   k_pf_scan     exclusive prefix of per-block / per-row counts (one block; the arrays are 1/4096 of the data)
 //   k_pf_runs     where the postings of every rank begin
+//   k_pf_split    cross form: where the postings of every rank pass from the references (genome < n_ref) to the queries
 //   k_pf_count    a wave per 64 postings: for every posting (rank, a) of the row tile, one atomic add to count[a][b] per
-//                 later posting (rank, b) of the same run, the lanes side by side over b
+//                 later posting (rank, b) of the same run, the lanes side by side over b.  CROSS: a is a reference, the
+//                 b's are the run's queries only, and the tile is n_ref rows of n - n_ref columns
 //   k_pf_rows     a wave per matrix row: the kept entries counted, then written in ascending b
 // No kernel waits for another block.  The sorts between them are lzani_sort_keys (lzani_sort.hip).
 #pragma once
@@ -292,16 +294,36 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_runs(const unsigned long long
     if (r < D && (i == 0 || (post[i - 1] >> 32) != r)) runoff[r] = (u32)i;
 }
 
+// Cross form (lzani_prefilter_cross): a run lists its genomes ascending, the references (genome < n_ref) before the
+// queries.  runsplit[r] = the first posting of run r whose genome is >= n_ref, runoff[r + 1] where it has none;
+// runsplit[D] = M.  One thread per posting, and exactly one posting of a run writes the run's entry: its first one if
+// that is a query, a query behind a reference, or its last one (index + 1) if that is a reference.
+__global__ void __launch_bounds__(PF_THREADS) k_pf_split(const unsigned long long* __restrict__ post, u64 M, u64 D, u32 n_ref, u32* __restrict__ runsplit)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i == 0) runsplit[D] = (u32)M;
+    if (i >= M) return;
+    const u64 key = post[i];
+    const u64 r = key >> 32;
+    if (r >= D) return;
+    if ((u32)key >= n_ref) {
+        if (i == 0 || (post[i - 1] >> 32) != r || (u32)post[i - 1] < n_ref) runsplit[r] = (u32)i;
+    } else if (i + 1 == M || (post[i + 1] >> 32) != r) runsplit[r] = (u32)(i + 1);
+}
+
 // The matrix tile mat[(a - r0) * n + b], rows r0 <= a < r1: += 1 for every pair of postings (rank, a), (rank, b) with a < b.
 // A wave takes 64 consecutive postings as its a's, one after the other, the lanes over the rest of a's run: a k-mer that
 // every genome holds is spread over n / 64 waves, and a wave's adds of one step go to one matrix row.
+// CROSS: the tile is mat[(a - r0) * (n - n_ref) + (b - n_ref)], rows r0 <= a < r1 <= n_ref; a posting is active iff it is
+// a reference of the tile and its run holds a query, and the lanes go over the run's queries, [runsplit[rank], end).
+template <bool CROSS>
 __global__ void __launch_bounds__(PF_THREADS) k_pf_count(const unsigned long long* __restrict__ post, u64 M, const u32* __restrict__ runoff, u64 D,
-                                                         u32 n, u32 r0, u32 r1, u32* __restrict__ mat)
+                                                         u32 n, u32 r0, u32 r1, u32* __restrict__ mat, const u32* __restrict__ runsplit, u32 n_ref)
 {
     const int lane = threadIdx.x & 63;
     const u64 w0 = (((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6) << 6;      // the wave's first posting
     const u64 i = w0 + lane;
-    u32 a = 0, end = 0;
+    u32 a = 0, end = 0, from = 0;
     bool act = false;
     if (i < M) {
         const u64 key = post[i];
@@ -310,7 +332,11 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_count(const unsigned long lon
         if (rank < D && a >= r0 && a < r1) {
             const u64 e = runoff[rank + 1];
             end = (u32)(e < M ? e : M);
-            act = (u64)end > i + 1;
+            if (CROSS) {
+                from = runsplit[rank];                         // (a < r1 <= n_ref: the split lies behind i)
+                act = from < end;
+            } else
+                act = (u64)end > i + 1;
         }
     }
     u64 todo = __builtin_amdgcn_ballot_w64(act);
@@ -318,10 +344,19 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_count(const unsigned long lon
         const int l = ctz64(todo);
         todo &= todo - 1;
         const u32 al = __shfl(a, l), el = __shfl(end, l);
-        u32* __restrict__ row = mat + (u64)(al - r0) * n;
-        for (u64 j = w0 + l + 1 + lane; j < (u64)el; j += 64) {
-            const u32 b = (u32)post[j];
-            if (b < n) atomicAdd(&row[b], 1u);
+        if (CROSS) {
+            const u32 nq = n - n_ref, fl = __shfl(from, l);
+            u32* __restrict__ row = mat + (u64)(al - r0) * nq;
+            for (u64 j = (u64)fl + lane; j < (u64)el; j += 64) {
+                const u32 c = (u32)post[j] - n_ref;            // (below n_ref: wraps beyond nq)
+                if (c < nq) atomicAdd(&row[c], 1u);
+            }
+        } else {
+            u32* __restrict__ row = mat + (u64)(al - r0) * n;
+            for (u64 j = w0 + l + 1 + lane; j < (u64)el; j += 64) {
+                const u32 b = (u32)post[j];
+                if (b < n) atomicAdd(&row[b], 1u);
+            }
         }
     }
 }
@@ -334,25 +369,26 @@ __device__ __forceinline__ bool pf_kept(u32 s, u32 ka, u32 kb, u32 min_shared, d
 }
 
 // A wave per row a of the tile: the kept entries b > a counted (rowcnt[a - r0]) or written from rowoff[a - r0] on
-// (tile-relative), in ascending b.
-template <bool WRITE>
+// (tile-relative), in ascending b.  CROSS: the row holds the n - n_ref queries, column c is b = n_ref + c.
+template <bool WRITE, bool CROSS>
 __global__ void __launch_bounds__(PF_THREADS) k_pf_rows(const u32* __restrict__ mat, u32 n, u32 r0, u32 r1, const u32* __restrict__ kmers_of,
                                                         u32 min_shared, double min_ratio, u32* __restrict__ rowcnt, const u64* __restrict__ rowoff,
-                                                        u32* __restrict__ ids, u32* __restrict__ shared)
+                                                        u32* __restrict__ ids, u32* __restrict__ shared, u32 n_ref)
 {
     const int lane = threadIdx.x & 63;
     const u64 wave = ((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6;
     if (wave >= (u64)(r1 - r0)) return;
     const u32 a = r0 + (u32)wave;
-    const u32* __restrict__ m = mat + wave * n;
+    const u32 c0 = CROSS ? n_ref : 0u;                          // the row's first column is genome c0
+    const u32* __restrict__ m = mat + wave * (n - c0);
     const u32 ka = kmers_of[a];
     u64 base = WRITE ? rowoff[wave] : 0;
     u32 cnt = 0;
-    for (u64 b0 = (u64)a + 1; b0 < n; b0 += 64) {
+    for (u64 b0 = CROSS ? (u64)n_ref : (u64)a + 1; b0 < n; b0 += 64) {
         const u64 b = b0 + lane;
         u32 s = 0;
         bool ok = false;
-        if (b < n) { s = m[b]; ok = pf_kept(s, ka, kmers_of[b], min_shared, min_ratio); }
+        if (b < n) { s = m[b - c0]; ok = pf_kept(s, ka, kmers_of[b], min_shared, min_ratio); }
         const u64 mask = __builtin_amdgcn_ballot_w64(ok);
         if (WRITE && ok) {
             const u64 at = base + (u64)__popcll(mask & ((1ULL << lane) - 1ULL));

@@ -6,7 +6,8 @@
 // The matching stage is one call per GPU into the C-ABI of include/lzani.h (liblzani_hip.so, loaded
 // with dlopen so that this binary builds and its ingest/emit code is testable without ROCm present).
 // Extras over the reference: --flt-kmers <k> <thr> (the filter rows made on the GPU from the genomes themselves, in place
-// of a kmer-db file), --gpus <n> (rows dealt cyclically over n GPUs), --device <id>, --gpu-mem <size>
+// of a kmer-db file), the mode query2ref (--query-fasta / --query-txt / --query-dir: a query set against the reference set
+// of --in-*, the cross pairs only), --gpus <n> (rows dealt cyclically over n GPUs), --device <id>, --gpu-mem <size>
 // (genome-memory limit per GPU: larger sets run out-of-core, in tiles of genome blocks; with --flt-kmers the filter then
 // streams the genomes from host memory in slices of at most that size),
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
@@ -37,6 +38,9 @@ struct Params {
     bool multisample = true, in_percent = false, single_txt = false;
     double filter_thr = 0;
     vector<string> inputs;
+    bool query2ref = false;                                 // mode query2ref: the genomes of query_inputs against those of inputs
+    vector<string> query_inputs;
+    bool query_given = false;                               // a --query-* flag was read
     string out, out_ids, out_aln, filter_fn, out_format = "standard";
     vector<Comp> comps;
     uint64_t flt_mask = 0;
@@ -96,10 +100,14 @@ static void usage()
     cerr << INFO << "\n"
          << "Tool for rapid determination of similarities among sets of DNA sequences\n"
          << "Usage:\nlz-ani <mode> [options]\nModes:\n  all2all                        - all to all\n"
+         << "  query2ref                      - every query (--query-*) against every reference (--in-*): the cross pairs only\n"
          << "Options - input specification:\n"
          << "      --in-fasta <file_name>     - FASTA file (for multisample-fasta mode)\n"
          << "      --in-txt <file_name>       - text file with FASTA file names\n"
          << "      --in-dir <path>            - directory with FASTA files\n"
+         << "      --query-fasta <file_name>  - query2ref: FASTA file with the queries\n"
+         << "      --query-txt <file_name>    - query2ref: text file with the queries' FASTA file names\n"
+         << "      --query-dir <path>         - query2ref: directory with the queries' FASTA files\n"
          << "      --multisample-fasta <bool> - multi sample FASTA input (default: true)\n"
          << "      --flt-kmerdb <fn> <float>  - filtering file (kmer-db output) and threshold\n"
          << "      --flt-kmers <k> <float>    - filter built on the GPU instead of read from a file: pairs whose shared canonical k-mers (8 <= k <= 31)\n"
@@ -146,25 +154,30 @@ static bool parse_params(int argc, char** argv)
 {
     if (argc == 2 && argv[1] == "--version"s) { cerr << VER << endl; return true; }
     if (argc < 3) { usage(); return false; }
-    if (argv[1] != "all2all"s) { cerr << "Unknown mode: " << argv[1] << endl; usage(); return false; }
+    if (argv[1] == "query2ref"s) P.query2ref = true;
+    else if (argv[1] != "all2all"s) { cerr << "Unknown mode: " << argv[1] << endl; usage(); return false; }
     lzani_params& z = P.lz;
     for (int i = 2; i < argc;) {
         string par = argv[i];
         auto has = [&](int k) { return i + k < argc; };
-        if (par == "--in-txt" && has(1)) {
+        const bool qry = par.rfind("--query-", 0) == 0;       // the same three sources for either side
+        vector<string>& inputs = qry ? P.query_inputs : P.inputs;
+        const string src = qry ? "--in-" + par.substr(8) : par;
+        if (qry && has(1)) P.query_given = true;
+        if (src == "--in-txt" && has(1)) {
             ifstream ifs(argv[i + 1]);
             if (!ifs.is_open()) { cerr << "Cannot open file: " << argv[i + 1] << endl; return false; }
-            P.inputs.assign(istream_iterator<string>(ifs), istream_iterator<string>());
-            if (P.inputs.empty()) return false;
+            inputs.assign(istream_iterator<string>(ifs), istream_iterator<string>());
+            if (inputs.empty()) return false;
             i += 2;
-        } else if (par == "--in-dir" && has(1)) {
+        } else if (src == "--in-dir" && has(1)) {
             try {
-                P.inputs.clear();
-                for (const auto& fs : filesystem::directory_iterator(filesystem::path(argv[i + 1]))) P.inputs.push_back(fs.path().string());
+                inputs.clear();
+                for (const auto& fs : filesystem::directory_iterator(filesystem::path(argv[i + 1]))) inputs.push_back(fs.path().string());
             } catch (...) { cerr << "Non-existing directory: " << argv[i + 1] << endl; return false; }
-            if (P.inputs.empty()) return false;
+            if (inputs.empty()) return false;
             i += 2;
-        } else if (par == "--in-fasta" && has(1)) { P.inputs.assign(1, argv[i + 1]); i += 2; }
+        } else if (src == "--in-fasta" && has(1)) { inputs.assign(1, argv[i + 1]); i += 2; }
         else if ((par == "-o" || par == "--out") && has(1)) { P.out = argv[i + 1]; i += 2; }
         else if (par == "--out-ids" && has(1)) { P.out_ids = argv[i + 1]; i += 2; }
         else if (par == "--out-alignment" && has(1)) { P.out_aln = argv[i + 1]; i += 2; }
@@ -218,6 +231,10 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--results-in" && has(1)) { P.results_in = argv[i + 1]; i += 2; }
         else { cerr << "Unknown parameter: " << argv[i] << endl; usage(); exit(1); }
     }
+    // query2ref: what it does not take, and what only it takes
+    if (P.query2ref && !P.filter_fn.empty()) { cerr << "--flt-kmerdb cannot be used with query2ref (use --flt-kmers)" << endl; exit(1); }
+    if (!P.query2ref && P.query_given) { cerr << "--query-fasta, --query-txt and --query-dir belong to the mode query2ref" << endl; exit(1); }
+    if (P.query2ref && P.query_inputs.empty()) { cerr << "Query file names not provided (--query-fasta, --query-txt or --query-dir)" << endl; exit(1); }
     // The device k-mer prefilter: refused here, before any input is read
     if (P.flt_kmers && !P.filter_fn.empty()) { cerr << "--flt-kmers and --flt-kmerdb cannot be used together" << endl; exit(1); }
     if (P.flt_kmers && (P.flt_k < 8 || P.flt_k > 31)) {
@@ -301,6 +318,8 @@ struct Engine {
     int (*prefilter_codes)(lzani_ctx*, uint32_t, const uint8_t* const*, const uint32_t*, int, uint64_t, uint32_t, double, uint64_t, uint64_t*) = nullptr;
     int (*get_prefilter_stream_info)(const lzani_ctx*, lzani_prefilter_stream_info*) = nullptr;
     int (*get_prefilter_pass_info)(const lzani_ctx*, lzani_prefilter_pass_info*) = nullptr;
+    int (*prefilter_cross)(lzani_ctx*, int, uint64_t, uint32_t, double, uint32_t, uint64_t*) = nullptr;
+    int (*prefilter_codes_cross)(lzani_ctx*, uint32_t, const uint8_t* const*, const uint32_t*, int, uint64_t, uint32_t, double, uint64_t, uint32_t, uint64_t*) = nullptr;
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -318,6 +337,7 @@ struct Engine {
         BIND(group_create) BIND(group_destroy) BIND(group_last_error) BIND(group_set_genomes) BIND(group_run_rows) BIND(group_get_timing)
         BIND(set_genome_memory) BIND(get_residency) BIND(group_set_genome_memory) BIND(group_get_residency)
         BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info) BIND(prefilter_codes) BIND(get_prefilter_stream_info) BIND(get_prefilter_pass_info)
+        BIND(prefilter_cross) BIND(prefilter_codes_cross)
 #undef BIND
         return true;
     }
@@ -370,10 +390,19 @@ static void print_gpu_timing(int dev, const lzani_timing& t, bool summed, const 
 // ids: a context of its own, the stage with min_shared 1 and the threshold as min_ratio, the kept pairs; symmetrised into
 // flt.rows like a kmer-db file's.  Without --gpu-mem the genomes become the context's set and lzani_prefilter runs on
 // them; with it -- or where that set went out-of-core or did not fit -- the genomes stay in host memory and
-// lzani_prefilter_codes streams them through a staging buffer of at most --gpu-mem bytes (automatic without).
-static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
+// lzani_prefilter_codes streams them through a staging buffer of at most --gpu-mem bytes (automatic without).  n_ref > 0
+// (query2ref): the cross form of either, the kept pairs of the references 0 .. n_ref - 1 with the queries behind them.
+static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, uint32_t n_ref = 0)
 {
     const uint32_t n = (uint32_t)g.size();
+    auto resident = [&](lzani_ctx* ctx, uint64_t* kept) {
+        return n_ref ? E.prefilter_cross(ctx, P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, n_ref, kept)
+                     : E.prefilter(ctx, P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, kept);
+    };
+    auto codes = [&](lzani_ctx* ctx, const vector<const uint8_t*>& ptr, const vector<uint32_t>& len, uint64_t slice, uint64_t* kept) {
+        return n_ref ? E.prefilter_codes_cross(ctx, n, ptr.data(), len.data(), P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, slice, n_ref, kept)
+                     : E.prefilter_codes(ctx, n, ptr.data(), len.data(), P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, slice, kept);
+    };
     vector<const uint8_t*> ptr; vector<uint32_t> len;
     genome_views(g, ptr, len);
     lzani_ctx* ctx = nullptr;
@@ -383,17 +412,17 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
     vector<uint64_t> row_off((size_t)n + 1, 0);
     vector<uint32_t> ids;
     bool streamed = P.gpu_mem != 0;
-    if (streamed) rc = E.prefilter_codes(ctx, n, ptr.data(), len.data(), P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, P.gpu_mem, &kept);
+    if (streamed) rc = codes(ctx, ptr, len, P.gpu_mem, &kept);
     else {
         rc = E.set_genomes(ctx, n, ptr.data(), len.data());
-        if (rc == LZANI_OK) rc = E.prefilter(ctx, P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, &kept);
+        if (rc == LZANI_OK) rc = resident(ctx, &kept);
         if (rc == LZANI_ERR_STATE || rc == LZANI_ERR_NOMEM) {             // the set went out-of-core, or does not fit: a fresh context, streamed
             E.destroy(ctx);
             ctx = nullptr;
             rc = E.create(&P.lz, P.device, &ctx);
             if (rc != LZANI_OK) { cerr << "K-mer filter failed: lzani_create failed with code " << rc << endl; return false; }
             streamed = true;
-            rc = E.prefilter_codes(ctx, n, ptr.data(), len.data(), P.flt_k, sample_max_of(P.flt_fraction), 1, P.filter_thr, 0, &kept);
+            rc = codes(ctx, ptr, len, 0, &kept);
         }
     }
     if (rc == LZANI_OK) { ids.resize(kept); rc = E.prefilter_fetch(ctx, nullptr, row_off.data(), ids.data(), nullptr); }
@@ -408,6 +437,7 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt)
         stream_note = ss.str();
     }
     if (E.get_prefilter_pass_info(ctx, &ps) == LZANI_OK && ps.passes > 1) stream_note += "; " + to_string(ps.passes) + " passes";
+    if (n_ref) stream_note += "; " + to_string(n_ref) + " x " + to_string(n - n_ref);
     if (P.verbosity >= 2 && E.get_prefilter_info(ctx, &pi) == LZANI_OK)
         cerr << "k-mer filter on device " << P.device << ": k " << pi.k << ", " << pi.positions << " sampled windows, " << pi.distinct_kmers
              << " distinct k-mers, " << pi.postings << " postings, " << pi.entries << " kept pairs, " << pi.tiles << " tile(s); keys " << pi.keys_ms
@@ -713,6 +743,12 @@ static bool run_all2all(const char* argv0)
     vector<Genome> g;
     if (P.multisample ? !load_multifasta(P.inputs, g) : !load_fasta(P.inputs, (uint32_t)P.lz.max_dist_in_ref, g)) return false;
     if (P.verbosity >= 2) cerr << g.size() << endl;
+    vector<Genome> qry;                                     // query2ref: the queries, through the same loader
+    if (P.query2ref) {
+        if (P.multisample ? !load_multifasta(P.query_inputs, qry) : !load_fasta(P.query_inputs, (uint32_t)P.lz.max_dist_in_ref, qry)) return false;
+        if (P.verbosity >= 2) cerr << qry.size() << endl;
+        if (g.empty() || qry.empty()) { cerr << "query2ref needs at least one reference and one query sequence" << endl; return false; }
+    }
     stamp("Loading sequences");
 
     Filter flt;
@@ -738,6 +774,13 @@ static bool run_all2all(const char* argv0)
     if (P.verbosity >= 1) cerr << "Reordering sequences" << endl;
     auto map = reorder(g);
     if (!flt.empty()) { if (P.verbosity >= 1) cerr << "Reordering filter" << endl; reorder_filter(flt, map); }
+    // query2ref: each side in its own order; the ids are the references, then the queries
+    const uint32_t n_ref = P.query2ref ? (uint32_t)g.size() : 0;
+    if (P.query2ref) {
+        reorder(qry);
+        g.insert(g.end(), make_move_iterator(qry.begin()), make_move_iterator(qry.end()));
+        qry.clear();
+    }
     stamp("Reordering sequences");
 
     Engine E;
@@ -746,9 +789,16 @@ static bool run_all2all(const char* argv0)
         if (P.verbosity >= 1) cerr << "Building k-mer filter" << endl;
         if (!E.load(argv0)) return false;
         engine_loaded = true;
-        if (!kmer_filter(E, g, flt)) return false;
+        if (!kmer_filter(E, g, flt, n_ref)) return false;
         if (P.verbosity >= 1) cerr << "Filter size: " << flt.size() << endl;
         stamp("K-mer filter");
+    } else if (P.query2ref) {                               // every cross pair, as the kept pairs of a prefilter that drops none
+        const uint32_t n = (uint32_t)g.size();
+        vector<uint64_t> row_off((size_t)n + 1);
+        vector<uint32_t> ids((size_t)n_ref * (n - n_ref));
+        for (uint32_t a = 0; a <= n; ++a) row_off[a] = (uint64_t)min(a, n_ref) * (n - n_ref);
+        for (size_t e = 0; e < ids.size(); ++e) ids[e] = n_ref + (uint32_t)(e % (n - n_ref));
+        filter_from_pairs(n, row_off, ids, flt);
     }
 
     EmitParams ep;

@@ -36,7 +36,8 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_group_get_residency", "lzani_debug_index_slab", "lzani_debug_run_candidates",
            "lzani_prefilter", "lzani_prefilter_fetch", "lzani_get_prefilter_info",
            "lzani_prefilter_codes", "lzani_plan_slices", "lzani_get_prefilter_stream_info",
-           "lzani_get_prefilter_pass_info", "lzani_prefilter_pass_plan", "lzani_plan_passes")
+           "lzani_get_prefilter_pass_info", "lzani_prefilter_pass_plan", "lzani_plan_passes",
+           "lzani_prefilter_cross", "lzani_prefilter_codes_cross", "lzani_get_prefilter_cross_info")
 
 
 class LzaniError(RuntimeError):
@@ -98,6 +99,11 @@ class PrefilterStreamInfo(C.Structure):
 class PrefilterPassInfo(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("key_sweeps", C.c_uint32), ("cap", C.c_uint64), ("largest_pass", C.c_uint64),
                 ("workspace_bytes", C.c_uint64), ("hist_ms", C.c_double)]
+
+
+class PrefilterCrossInfo(C.Structure):
+    _fields_ = [("n_ref", C.c_uint32), ("n_query", C.c_uint32), ("tile_rows", C.c_uint32), ("reserved_", C.c_uint32),
+                ("matrix_bytes", C.c_uint64)]
 
 
 PREFILTER_BINS = 4096                               # bins of the prefilter's k-mer passes
@@ -186,6 +192,10 @@ def load_library():
         lib.lzani_get_prefilter_pass_info.argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_prefilter_pass_plan.argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_plan_passes.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+        lib.lzani_prefilter_cross.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32, C.c_void_p]
+        lib.lzani_prefilter_codes_cross.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_double,
+                                                    C.c_uint64, C.c_uint32, C.c_void_p]
+        lib.lzani_get_prefilter_cross_info.argtypes = [C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -206,6 +216,28 @@ def dense_rows(n, rows=None):
     ref_ids = np.arange(n, dtype=np.uint32) if rows is None else np.asarray(rows, dtype=np.uint32)
     row_off = np.arange(len(ref_ids) + 1, dtype=np.uint64) * np.uint64(max(n - 1, 0))
     return ref_ids, row_off
+
+
+def cross_rows(n, n_ref, pair_off=None, pair_ids=None):
+    """The directed rows run_rows takes for the cross pairs of the references 0 .. n_ref - 1 and the queries n_ref .. n - 1,
+    in both directions: (ref_ids, row_off, query_ids).  Without a CSR: every reference with all queries ascending, then
+    every query with all references ascending.  With the CSR of kept pairs a < n_ref <= b (pair_off[n + 1], pair_ids, as
+    prefilter_fetch gives it): one row per genome that has a partner, in id order, its partners ascending."""
+    n, n_ref = int(n), int(n_ref)
+    if pair_off is None:
+        a = np.repeat(np.arange(n_ref, dtype=np.int64), n - n_ref)
+        b = np.tile(np.arange(n_ref, n, dtype=np.int64), n_ref)
+    else:
+        a = np.repeat(np.arange(n, dtype=np.int64), np.diff(np.asarray(pair_off).astype(np.int64)))
+        b = np.asarray(pair_ids, dtype=np.int64)
+    rows = np.concatenate((a, b))                           # row a lists b, row b lists a
+    cols = np.concatenate((b, a))
+    order = np.lexsort((cols, rows))
+    rows, cols = rows[order], cols[order]
+    cnt = np.bincount(rows, minlength=n)
+    ref_ids = np.flatnonzero(cnt).astype(np.uint32)
+    row_off = np.concatenate(([0], np.cumsum(cnt[cnt > 0]))).astype(np.uint64)
+    return ref_ids, row_off, cols.astype(np.uint32)
 
 
 def row_costs(ref_ids, row_off, query_ids, lens):
@@ -448,6 +480,34 @@ class Engine:
                                                    C.c_uint64(int(slice_bytes)), C.byref(cnt)), "lzani_prefilter_codes")
         self.pf_n = len(seqs)
         return int(cnt.value)
+
+    def prefilter_cross(self, k, n_ref, sample_max=SAMPLE_ALL, min_shared=1, min_ratio=0.0):
+        """lzani_prefilter_cross on the resident set: the prefilter restricted to the pairs a < n_ref <= b (references
+        0 .. n_ref - 1 against queries n_ref .. n - 1).  Returns the number of kept pairs; prefilter_fetch() brings them,
+        prefilter_cross_info() the shape of the count matrix."""
+        cnt = C.c_uint64(0)
+        self.pf_n = self.n
+        self._check(self.lib.lzani_prefilter_cross(self.h, int(k), C.c_uint64(int(sample_max)), C.c_uint32(int(min_shared)),
+                                                   C.c_double(float(min_ratio)), C.c_uint32(int(n_ref)), C.byref(cnt)), "lzani_prefilter_cross")
+        return int(cnt.value)
+
+    def prefilter_codes_cross(self, seqs, k, n_ref, sample_max=SAMPLE_ALL, min_shared=1, min_ratio=0.0, slice_bytes=0):
+        """lzani_prefilter_codes_cross: prefilter_cross of `seqs` streamed from host memory, as prefilter_codes streams them."""
+        seqs = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
+        ptrs = (C.c_void_p * max(len(seqs), 1))(*[s.ctypes.data for s in seqs])
+        lens = np.array([len(s) for s in seqs], dtype=np.uint32)
+        cnt = C.c_uint64(0)
+        self.pf_n = len(seqs)
+        self._check(self.lib.lzani_prefilter_codes_cross(self.h, len(seqs), ptrs, _ptr(lens), int(k), C.c_uint64(int(sample_max)),
+                                                         C.c_uint32(int(min_shared)), C.c_double(float(min_ratio)),
+                                                         C.c_uint64(int(slice_bytes)), C.c_uint32(int(n_ref)), C.byref(cnt)),
+                    "lzani_prefilter_codes_cross")
+        return int(cnt.value)
+
+    def prefilter_cross_info(self):
+        o = PrefilterCrossInfo()
+        self._check(self.lib.lzani_get_prefilter_cross_info(self.h, C.byref(o)), "lzani_get_prefilter_cross_info")
+        return {k: getattr(o, k) for k, _ in PrefilterCrossInfo._fields_ if k != "reserved_"}
 
     def prefilter_stream_info(self):
         o = PrefilterStreamInfo()

@@ -13,8 +13,14 @@ Every figure is the median of --repeats runs after one warm-up run.
               slice) -- with both info structs and the device memory each path holds for genomes; --passes P forces the
               k-mer passes of both (LZANI_PREFILTER_PASSES) and the line carries passes, key_sweeps, hist_ms and
               workspace_bytes of lzani_get_prefilter_pass_info
+  --cross N_REF [N_REF ...]  instead of the two workloads: the same 2,000-genome set, k = 21, every fifth k-mer, through the
+              all-pairs form (lzani_prefilter) and, for every n_ref given, the cross form (lzani_prefilter_cross: the first
+              n_ref genomes as references against the rest) in one process: count_ms, compact_ms (every run and the
+              median), matrix_bytes, tiles, entries and the atomic adds of both forms; the cross result is checked against
+              the all-pairs result restricted to the cross pairs
 Usage: tools/prefilter_bench.py [--out profiles/prefilter_bench.json] [--repeats 3] [--small] [--no-dense]
-       tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--passes P] [--out profiles/prefilter_stream_bench.json]"""
+       tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--passes P] [--out profiles/prefilter_stream_bench.json]
+       tools/prefilter_bench.py --cross N_REF [N_REF ...] [--out profiles/prefilter_cross_bench.json]"""
 import argparse
 import json
 import math
@@ -136,6 +142,57 @@ def streamed(a):
         sys.exit("the streamed prefilter's result differs from the resident one's")
 
 
+def cross(a):
+    """The all-pairs form and the cross form at every n_ref of --cross on one set, in one process."""
+    n, fam, min_shared, min_ratio = (200, 50, 5, 0.003) if a.small else (2000, 50, 5, 0.003)
+    _, seqs = SG.make_set(n, 5, fam=fam, dmax=0.10)
+    smax = L.sample_max_of(0.2)
+    res = dict(tool="prefilter_bench --cross", k=K, fraction=0.2, genomes=n, bases=sum(len(s) for s in seqs), repeats=a.repeats,
+               min_shared=min_shared, min_ratio=min_ratio)
+    eng = L.Engine()
+    eng.set_genomes(seqs)
+
+    def runs_of(call, adds_call):
+        adds_call()                                                 # warm-up; thresholds (1, 0): the sum of shared = the atomic adds
+        adds = int(eng.prefilter_fetch()[3].astype(np.int64).sum())
+        runs = []
+        for _ in range(a.repeats):
+            call()
+            runs.append(eng.prefilter_info())
+        out = {key: runs[0][key] for key in ("tiles", "entries", "postings")}
+        for key in ("count_ms", "compact_ms"):
+            out[key] = float(np.median([r[key] for r in runs]))
+            out[key + "_runs"] = [r[key] for r in runs]
+        out["count_plus_compact_ms_runs"] = [r["count_ms"] + r["compact_ms"] for r in runs]
+        out["atomic_adds"] = adds
+        return out
+
+    res["all_pairs"] = runs_of(lambda: eng.prefilter(K, smax, min_shared, min_ratio), lambda: eng.prefilter(K, smax, 1, 0.0))
+    res["all_pairs"]["matrix_bytes"] = 4 * n * -(-n // res["all_pairs"]["tiles"]) if res["all_pairs"]["tiles"] else 0
+    want = eng.prefilter_fetch()
+    a_of = np.repeat(np.arange(n), np.diff(want[1]).astype(np.int64))
+    print("all pairs:", json.dumps(res["all_pairs"]), flush=True)
+    res["cross"], same = [], True
+    for n_ref in a.cross:
+        c = runs_of(lambda: eng.prefilter_cross(K, n_ref, smax, min_shared, min_ratio), lambda: eng.prefilter_cross(K, n_ref, smax, 1, 0.0))
+        c.update(eng.prefilter_cross_info())
+        got = eng.prefilter_fetch()
+        ok = (a_of < n_ref) & (want[2] >= n_ref)
+        c["equal_to_restricted_all_pairs"] = bool(np.array_equal(got[0], want[0]) and np.array_equal(got[2], want[2][ok]) and np.array_equal(got[3], want[3][ok]) and
+                                                  np.array_equal(np.diff(got[1]).astype(np.int64), np.bincount(a_of[ok], minlength=n)))
+        same = same and c["equal_to_restricted_all_pairs"]
+        res["cross"].append(c)
+        print("cross:", json.dumps(c), flush=True)
+    eng.close()
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    if not same:
+        sys.exit("the cross prefilter's result differs from the restricted all-pairs result")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -146,8 +203,12 @@ def main():
     ap.add_argument("--slice-bytes", type=int, default=0, help="--streamed: slice size (default: the whole set in one slice)")
     ap.add_argument("--passes", type=int, default=0, help="--streamed: force this many k-mer passes (LZANI_PREFILTER_PASSES)")
     ap.add_argument("--slices", type=int, default=0, help="--streamed: the smallest slice size (in 4 KiB steps) that gives at most this many slices")
+    ap.add_argument("--cross", type=int, nargs="+", default=None, metavar="N_REF",
+                    help="the cross form (the first N_REF genomes against the rest) beside the all-pairs form on one set")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "prefilter_stream_bench.json" if a.streamed else "prefilter_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "prefilter_cross_bench.json" if a.cross else "prefilter_stream_bench.json" if a.streamed else "prefilter_bench.json")
+    if a.cross:
+        return cross(a)
     if a.streamed:
         return streamed(a)
     n_bench, n_fam, fam = (1000, 2000, 50) if a.small else (10000, 20000, 50)
