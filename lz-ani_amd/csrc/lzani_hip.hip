@@ -6,7 +6,11 @@
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
-// lzani_core.h; sizes and the parameter envelope are lzani_layout.h.
+// lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  Three layers of the host side are files of their
+// own, included at fixed places below:
+//   lzani_ooc.h         genome sets larger than the device: block plan, block uploads, the tiled run
+//   lzani_prefilter.h   the k-mer prefilter's host stage: slice and pass plans, the pass / tile driver, its entry points
+//   lzani_multi.h       the multi-GPU layer
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1476,456 +1480,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
 }  // namespace
 
 #include "lzani_ooc.h"
-
-namespace {
-
-// Device time of the prefilter's stages (and of the streamed form's slice copies): pairs of events on the context's stream,
-// summed per stage at the end.
-enum { PF_ST_KEYS = 0, PF_ST_SORT = 1, PF_ST_COUNT = 2, PF_ST_COMPACT = 3, PF_ST_UPLOAD = 4, PF_ST_HIST = 5, PF_STAGES = 6 };
-constexpr u64 PF_MAX_PASS_WINDOWS = 0xFFFFFFEFull;       // what one pass may hold: the u32 run offsets of its postings, and lzani_sort_keys' limit
-struct PfClock {
-    hipStream_t stream;
-    std::vector<hipEvent_t> ev;           // begin, end, begin, end, ...
-    std::vector<int> stage;
-    explicit PfClock(hipStream_t s) : stream(s) {}
-    PfClock(const PfClock&) = delete;
-    PfClock& operator=(const PfClock&) = delete;
-    ~PfClock() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t mark()
-    {
-        hipEvent_t e = nullptr;
-        hipError_t rc = hipEventCreate(&e);
-        if (rc != hipSuccess) return rc;
-        ev.push_back(e);
-        return hipEventRecord(e, stream);
-    }
-    hipError_t begin(int st) { stage.push_back(st); return mark(); }
-    hipError_t end() { return mark(); }
-    hipError_t collect(double ms[PF_STAGES])
-    {
-        for (size_t k = 0; k + 1 < ev.size(); k += 2) {
-            float t = 0;
-            hipError_t rc = hipEventSynchronize(ev[k + 1]);
-            if (rc == hipSuccess) rc = hipEventElapsedTime(&t, ev[k], ev[k + 1]);
-            if (rc != hipSuccess) return rc;
-            ms[stage[k / 2]] += t;
-        }
-        return hipSuccess;
-    }
-};
-int pf_sort(lzani_ctx* c, PrefilterWork& w, const unsigned long long* in, unsigned long long* out, size_t n, int b0, int b1)
-{
-    size_t need = w.tmp.capacity();
-    const int e = lzani_sort_keys(in, out, n, b0, b1, w.tmp, &need, c->stream);
-    if (e != 0) return fail(c, LZANI_ERR_DEVICE, std::string("lzani_prefilter: sort: ") + hipGetErrorString((hipError_t)e));
-    return LZANI_OK;
-}
-
-// The slice plan of the streamed prefilter (lzani_plan_slices): genomes in id order into contiguous slices; a new slice
-// starts where the next genome would take the slice's sum of lengths above slice_bytes (so genomes of length 0 join the
-// current one).  first[s] .. first[s + 1] are slice s's genomes.  slice_bytes 0: one slice.  Returns the number of
-// slices, or LZANI_ERR_ARG with the reason in msg.
-int plan_slices_impl(u32 n, const u32* len, u64 slice_bytes, std::vector<u32>& first, std::string& msg)
-{
-    if (!n || !len) { msg = "empty input"; return LZANI_ERR_ARG; }
-    first.assign(1, 0);
-    if (slice_bytes == 0) { first.push_back(n); return 1; }
-    u32 Lmax = 0;
-    for (u32 g = 0; g < n; ++g) Lmax = std::max(Lmax, len[g]);
-    if ((u64)Lmax > slice_bytes) {
-        msg = "slice size of " + std::to_string(slice_bytes) + " bytes is below the minimum of " + std::to_string(Lmax) +
-              " bytes (a slice must hold the longest genome)";
-        return LZANI_ERR_ARG;
-    }
-    if ((u64)n > 0x7FFFFFFFull) { msg = "too many genomes"; return LZANI_ERR_ARG; }
-    u64 cur = 0;
-    for (u32 g = 0; g < n; ++g) {
-        if (cur + len[g] > slice_bytes) { first.push_back(g); cur = 0; }
-        cur += len[g];
-    }
-    first.push_back(n);
-    return (int)first.size() - 1;
-}
-
-// The streamed key source of the prefilter (lzani_prefilter_codes): the genomes stay in the caller's host memory, 1 B a
-// base, and pass slice by slice through one staging buffer on the device.  A key sweep goes over all slices, up or
-// down; the slice the buffer holds already is not copied again.
-struct PfStream {
-    const uint8_t* const* codes = nullptr;
-    const u32* len = nullptr;
-    std::vector<u32> first;               // the slice plan
-    std::vector<u64> bytes;               // per slice: the sum of its genomes' lengths
-    DevMem<unsigned char> stage;          // the largest slice
-    DevMem<u64> d_off;                    // per genome: its byte offset in the staging buffer when its slice is there
-    DevMem<u32> d_len;
-    std::vector<unsigned char> bounce;    // host side of a copy: the genomes' codes put together, a piece at a time
-    int staged = -1;                      // the slice in the buffer
-    lzani_prefilter_stream_info info{};
-};
-enum : u64 { PF_BOUNCE_BYTES = 64ull << 20 };
-
-// Slice s into the staging buffer: the codes of its genomes one after the other, through the bounce buffer.
-int pf_upload_slice(lzani_ctx* c, PfStream& st, PfClock& clk, u32 s)
-{
-    u64 at = 0;
-    size_t fill = 0;
-    auto flush = [&]() -> int {
-        if (!fill) return LZANI_OK;
-        HIPCHK(c, clk.begin(PF_ST_UPLOAD));
-        HIPCHK(c, hipMemcpyAsync(st.stage.get() + at, st.bounce.data(), fill, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, clk.end());
-        HIPCHK(c, hipStreamSynchronize(c->stream));            // (the bounce buffer is filled again)
-        at += fill;
-        fill = 0;
-        return LZANI_OK;
-    };
-    for (u32 g = st.first[s]; g < st.first[s + 1]; ++g) {
-        const uint8_t* src = st.codes[g];
-        for (u64 left = st.len[g]; left;) {
-            const size_t take = (size_t)std::min<u64>(left, st.bounce.size() - fill);
-            memcpy(st.bounce.data() + fill, src, take);
-            fill += take; src += take; left -= take;
-            if (fill == st.bounce.size()) if (int rc = flush()) return rc;
-        }
-    }
-    if (int rc = flush()) return rc;
-    st.staged = (int)s;
-    ++st.info.slice_uploads;
-    st.info.staged_bytes += st.bytes[s];
-    return LZANI_OK;
-}
-
-// The pass plan of the prefilter (lzani_plan_passes): bin_lo[0 .. P] with bin_lo[0] = 0 and bin_lo[P] = PF_BINS.  Forced:
-// P equal ranges.  Automatic: greedy from bin 0, a pass takes bins while its sum of windows stays <= cap.  Returns P, or
-// LZANI_ERR_ARG (forced above PF_BINS; a single bin above cap: *bad_bin names it).
-int plan_passes_impl(const u64* hist, u64 cap, u32 forced, std::vector<u32>& bin_lo, u32* bad_bin = nullptr)
-{
-    bin_lo.assign(1, 0);
-    if (forced) {
-        if (forced > PF_BINS) return LZANI_ERR_ARG;
-        for (u32 p = 1; p <= forced; ++p) bin_lo.push_back((u32)((u64)PF_BINS * p / forced));
-        return (int)forced;
-    }
-    if (!hist) return LZANI_ERR_ARG;
-    u64 sum = 0;
-    for (u32 b = 0; b < PF_BINS; ++b) {
-        if (hist[b] > cap) { if (bad_bin) *bad_bin = b; return LZANI_ERR_ARG; }
-        if (hist[b] > cap - sum) { bin_lo.push_back(b); sum = 0; }        // (sum <= cap always; a pass holds a bin at least)
-        sum += hist[b];
-    }
-    bin_lo.push_back(PF_BINS);
-    return (int)bin_lo.size() - 1;
-}
-
-// The stage itself: fills pf (a fresh Prefilter) from the resident genome set, or (st given) from the n genomes of the
-// streamed source.  The two differ in where the key sweeps take their genomes from; all behind them is shared.  One
-// k-mer pass (the whole set fits the window cap and none is forced): count sweep, keys, dictionary, postings, then the
-// matrix tiles over the same postings.  Several: histogram sweep, pass plan, then tile after tile every pass's pipeline
-// on its own windows, adding into the tile.  n_ref > 0: the cross form -- the matrix is the n_ref reference rows by the
-// n - n_ref query columns, its tiles cover the references only, and every set of postings gets its runsplit.
-int prefilter_impl(lzani_ctx* c, Prefilter& pf, int k, u64 sample_max, u32 min_shared, double min_ratio, u32 n, PfStream* st = nullptr, u32 n_ref = 0)
-{
-    PrefilterWork& w = pf.work;
-    lzani_prefilter_info& info = pf.info;
-    lzani_prefilter_pass_info& pinfo = pf.pinfo;
-    info.k = k;
-    pf.n = n;
-    const bool cross = n_ref != 0;
-    const u32 n_rows = cross ? n_ref : n, n_cols = cross ? n - n_ref : n;      // the count matrix
-    pf.cross = cross;
-    pf.cinfo.n_ref = n_ref; pf.cinfo.n_query = cross ? n_cols : 0;
-    min_shared = std::max<u32>(min_shared, 1);
-    const std::optional<u64> forced_passes = env_u64("LZANI_PREFILTER_PASSES");
-    if (forced_passes && (*forced_passes < 1 || *forced_passes > PF_BINS))
-        return fail(c, LZANI_ERR_ARG, "lzani_prefilter: LZANI_PREFILTER_PASSES must be 1 .. " + std::to_string((int)PF_BINS));
-    PfClock clk(c->stream);
-    const GenomeTab G = st ? GenomeTab{} : gtab(c);
-    auto len_of = [&](u32 g) -> u64 { return st ? (u64)st->len[g] : (u64)c->gs.L[g]; };
-
-    // chunks of PF_CHUNK forward positions, genome after genome
-    std::vector<u64> cbase((size_t)n + 1, 0);
-    u64 Lmax = 0;
-    for (u32 g = 0; g < n; ++g) {
-        cbase[g + 1] = cbase[g] + (len_of(g) + PF_CHUNK - 1) / PF_CHUNK;
-        Lmax = std::max(Lmax, len_of(g));
-    }
-    const u64 n_chunks = cbase[n];
-    const u32 gx = (u32)((Lmax + PF_CHUNK - 1) / PF_CHUNK);
-    HIPCHK(c, w.cbase.alloc((size_t)n + 1));
-    HIPCHK(c, w.blkcnt.alloc(n_chunks));
-    HIPCHK(c, w.blkoff.alloc(n_chunks + 1));
-    HIPCHK(c, pf.kmers_of.alloc(n));
-    HIPCHK(c, hipMemcpyAsync(w.cbase, cbase.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(pf.kmers_of, 0, (size_t)n * 4, c->stream));
-    pf.row_off.assign((size_t)n + 1, 0);
-
-    // ---- the key source: one sweep over all genomes in `mode`, of the windows whose bin lies in [lo, hi) (ranged; else of
-    // all).  PF_HIST: out is the histogram.  Resident: a sweep is a launch over all genomes (gridDim.y is limited to 65535:
-    // groups of genomes)
-    auto keys_resident = [&](int mode, bool ranged, u32 lo, u32 hi, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
-        using Fn = decltype(&k_pf_keys<PF_COUNT, false>);
-        static const Fn kernel[4][2] = {{k_pf_keys<PF_COUNT, false>, k_pf_keys<PF_COUNT, true>}, {k_pf_keys<PF_CANON, false>, k_pf_keys<PF_CANON, true>},
-                                        {k_pf_keys<PF_RANK, false>, k_pf_keys<PF_RANK, true>}, {k_pf_keys<PF_HIST, false>, k_pf_keys<PF_HIST, false>}};
-        HIPCHK(c, clk.begin(mode == PF_HIST ? PF_ST_HIST : PF_ST_KEYS));
-        for (u32 g0 = 0; gx && g0 < n; g0 += 32768) {
-            const dim3 gd(gx, std::min<u32>(32768, n - g0));
-            hipLaunchKernelGGL(kernel[mode][ranged], gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), g0, k, c->P.mrd, sample_max, lo, hi,
-                               w.blkcnt.get(), w.blkoff.get(), dict, D, out);
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.end());
-        return LZANI_OK;
-    };
-    // Streamed: the slices in the sweep's direction -- copied unless the buffer holds it, then the launch over its genomes.
-    // The sweeps alternate: up, down, up, ...
-    auto keys_streamed = [&](int mode, bool ranged, u32 lo, u32 hi, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
-        using Fn = decltype(&k_pf_keys_codes<PF_COUNT, false>);
-        static const Fn kernel[4][2] = {{k_pf_keys_codes<PF_COUNT, false>, k_pf_keys_codes<PF_COUNT, true>},
-                                        {k_pf_keys_codes<PF_CANON, false>, k_pf_keys_codes<PF_CANON, true>},
-                                        {k_pf_keys_codes<PF_RANK, false>, k_pf_keys_codes<PF_RANK, true>},
-                                        {k_pf_keys_codes<PF_HIST, false>, k_pf_keys_codes<PF_HIST, false>}};
-        const u32 S = (u32)st->first.size() - 1;
-        const bool up = pinfo.key_sweeps % 2 == 0;
-        for (u32 i = 0; i < S; ++i) {
-            const u32 s = up ? i : S - 1 - i;
-            if (st->staged != (int)s) if (int rc = pf_upload_slice(c, *st, clk, s)) return rc;
-            const u32 f = st->first[s], ns = st->first[s + 1] - f;
-            u64 lmax = 0;
-            for (u32 g = f; g < f + ns; ++g) lmax = std::max<u64>(lmax, st->len[g]);
-            const u32 sgx = (u32)((lmax + PF_CHUNK - 1) / PF_CHUNK);
-            HIPCHK(c, clk.begin(mode == PF_HIST ? PF_ST_HIST : PF_ST_KEYS));
-            for (u32 y0 = 0; sgx && y0 < ns; y0 += 32768) {
-                const dim3 gd(sgx, std::min<u32>(32768, ns - y0));
-                hipLaunchKernelGGL(kernel[mode][ranged], gd, dim3(PF_THREADS), 0, c->stream, (const unsigned char*)st->stage.get(), st->bytes[s],
-                                   (const u64*)(st->d_off.get() + f), (const u32*)(st->d_len.get() + f), w.cbase.get(), f, y0, k, sample_max, lo, hi,
-                                   w.blkcnt.get(), w.blkoff.get(), dict, D, out);
-            }
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, clk.end());
-        }
-        return LZANI_OK;
-    };
-    auto keys = [&](int mode, bool ranged, u32 lo, u32 hi, const unsigned long long* dict, u64 D, unsigned long long* out) -> int {
-        const int rc = st ? keys_streamed(mode, ranged, lo, hi, dict, D, out) : keys_resident(mode, ranged, lo, hi, dict, D, out);
-        ++pinfo.key_sweeps;
-        return rc;
-    };
-    // the total of a scan, read back
-    auto scan_total = [&](const u32* cnt, u64 cnt_n, u64* off, u64& total) -> int {
-        hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, cnt, cnt_n, off);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(&total, off + cnt_n, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return LZANI_OK;
-    };
-    // in[0 .. cnt) ascending -> out without adjacent duplicates; their number
-    auto uniq = [&](const unsigned long long* in, u64 cnt, unsigned long long* out, u32* per_genome, u64& n_out) -> int {
-        const u32 blocks = (u32)((cnt + PF_CHUNK - 1) / PF_CHUNK);
-        hipLaunchKernelGGL(k_pf_uniq<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, in, cnt, w.ucnt.get(), w.uoff.get(), out, per_genome, n);
-        if (int rc = scan_total(w.ucnt, blocks, w.uoff, n_out)) return rc;
-        hipLaunchKernelGGL(k_pf_uniq<true>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, in, cnt, w.ucnt.get(), w.uoff.get(), out, per_genome, n);
-        HIPCHK(c, hipGetLastError());
-        return LZANI_OK;
-    };
-    // the kept windows of a pass counted per chunk (blkcnt) and scanned (blkoff): where the two key sweeps behind it write
-    auto count_windows = [&](bool ranged, u32 lo, u32 hi, u64& Pw) -> int {
-        if (int rc = keys(PF_COUNT, ranged, lo, hi, nullptr, 0, nullptr)) return rc;
-        HIPCHK(c, clk.begin(PF_ST_KEYS));
-        if (int rc = scan_total(w.blkcnt, n_chunks, w.blkoff, Pw)) return rc;
-        HIPCHK(c, clk.end());
-        return LZANI_OK;
-    };
-    // ka, kb, the uniq counters and the radix scratch for passes of at most `windows` kept windows
-    auto alloc_keys = [&](u64 windows) -> int {
-        HIPCHK(c, w.ka.alloc(windows));
-        HIPCHK(c, w.kb.alloc(windows));
-        HIPCHK(c, w.ucnt.alloc((windows + PF_CHUNK - 1) / PF_CHUNK));
-        HIPCHK(c, w.uoff.alloc((windows + PF_CHUNK - 1) / PF_CHUNK + 1));
-        size_t need1 = 0, need2 = 0;
-        if (lzani_sort_keys(w.ka, w.kb, windows, 0, 2 * k, nullptr, &need1, c->stream) != 0 || lzani_sort_keys(w.kb, w.ka, windows, 32, 64, nullptr, &need2, c->stream) != 0)
-            return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
-        HIPCHK(c, w.tmp.alloc(std::max(need1, need2)));
-        pinfo.workspace_bytes = w.ka.bytes() + w.kb.bytes() + w.tmp.bytes();
-        return LZANI_OK;
-    };
-    // The pipeline of one pass behind its count_windows (Pw > 0 windows): dictionary in ka, then the postings in kb and
-    // where every rank's begin (runoff, allocated here unless it is large enough).  per_genome: |K(g)| += the genome's
-    // distinct k-mers of the pass.
-    auto postings_of = [&](bool ranged, u32 lo, u32 hi, u64 Pw, u32* per_genome, bool last_sweep, u64& D, u64& M) -> int {
-        if (int rc = keys(PF_CANON, ranged, lo, hi, nullptr, 0, w.ka.get())) return rc;
-        // ---- dictionary: the keys sorted, every distinct k-mer once; its place is its rank
-        HIPCHK(c, clk.begin(PF_ST_SORT));
-        if (int rc = pf_sort(c, w, w.ka, w.kb, Pw, 0, 2 * k)) return rc;
-        if (int rc = uniq(w.kb, Pw, w.ka, nullptr, D)) return rc;
-        HIPCHK(c, clk.end());
-        // ---- postings: rank << 32 | genome of every kept window, in genome order; a stable sort by rank leaves the genomes of
-        // a rank ascending; adjacent duplicates dropped, a run of equal rank lists the genomes that hold the k-mer
-        if (int rc = keys(PF_RANK, ranged, lo, hi, w.ka.get(), D, w.kb.get())) return rc;
-        if (st && last_sweep) { HIPCHK(c, hipStreamSynchronize(c->stream)); st->stage.reset(); }      // (the last sweep is done: room for the count matrix)
-        HIPCHK(c, clk.begin(PF_ST_SORT));
-        if (int rc = pf_sort(c, w, w.kb, w.ka, Pw, 32, 32 + ceil_log2(D))) return rc;
-        if (int rc = uniq(w.ka, Pw, w.kb, per_genome, M)) return rc;
-        HIPCHK(c, w.runoff.reserve(D + 1));
-        hipLaunchKernelGGL(k_pf_runs, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, w.runoff.get(), D);
-        if (cross) {
-            HIPCHK(c, w.runsplit.reserve(D + 1));
-            hipLaunchKernelGGL(k_pf_split, dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M, D, n_ref, w.runsplit.get());
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.end());
-        return LZANI_OK;
-    };
-    // the height of the matrix tile from what is free now, and the tile's buffers
-    u64 rows = 0;
-    std::vector<u64> h_off;
-    auto alloc_tile = [&]() -> int {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        rows = std::min<u64>(n_rows, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n_cols)));
-        if (const auto forced = env_u64("LZANI_PREFILTER_TILE_ROWS")) rows = std::min<u64>(n_rows, std::max<u64>(1, *forced));
-        HIPCHK(c, w.mat.alloc(rows * n_cols));
-        HIPCHK(c, w.rowcnt.alloc(rows));
-        HIPCHK(c, w.rowoff.alloc(rows + 1));
-        h_off.resize(rows + 1);
-        if (cross) { pf.cinfo.tile_rows = (u32)rows; pf.cinfo.matrix_bytes = w.mat.bytes(); }
-        return LZANI_OK;
-    };
-    u64 entries = 0;
-    // the postings in kb added into the tile of rows r0 .. r1; clear: the tile's first pass
-    auto count_tile = [&](u32 r0, u32 r1, u64 D, u64 M, bool clear) -> int {
-        HIPCHK(c, clk.begin(PF_ST_COUNT));
-        if (clear) HIPCHK(c, hipMemsetAsync(w.mat, 0, (size_t)(r1 - r0) * n_cols * 4, c->stream));
-        hipLaunchKernelGGL((cross ? k_pf_count<true> : k_pf_count<false>), dim3((u32)((M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), M,
-                           w.runoff.get(), D, n, r0, r1, w.mat.get(), (const u32*)w.runsplit.get(), n_ref);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.end());
-        return LZANI_OK;
-    };
-    // the kept entries of the tile's rows into a PrefilterTile of their own
-    auto compact_tile = [&](u32 r0, u32 r1) -> int {
-        const u32 nr = r1 - r0, row_blocks = (nr + PF_THREADS / 64 - 1) / (PF_THREADS / 64);
-        HIPCHK(c, clk.begin(PF_ST_COMPACT));
-        hipLaunchKernelGGL((cross ? k_pf_rows<false, true> : k_pf_rows<false, false>), dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1,
-                           pf.kmers_of.get(), min_shared, min_ratio, w.rowcnt.get(), w.rowoff.get(), (u32*)nullptr, (u32*)nullptr, n_ref);
-        hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, w.rowcnt.get(), (u64)nr, w.rowoff.get());
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        PrefilterTile tile;
-        tile.r0 = r0; tile.r1 = r1;
-        HIPCHK(c, tile.ids.alloc(h_off[nr]));
-        HIPCHK(c, tile.shared.alloc(h_off[nr]));
-        hipLaunchKernelGGL((cross ? k_pf_rows<true, true> : k_pf_rows<true, false>), dim3(row_blocks), dim3(PF_THREADS), 0, c->stream, w.mat.get(), n, r0, r1,
-                           pf.kmers_of.get(), min_shared, min_ratio, w.rowcnt.get(), w.rowoff.get(), tile.ids.get(), tile.shared.get(), n_ref);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.end());
-        for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = entries + h_off[r + 1];
-        entries += h_off[nr];
-        pf.tiles.push_back(std::move(tile));
-        ++info.tiles;
-        return LZANI_OK;
-    };
-
-    // ---- the kept windows of the whole set counted; whether they go in one pass
-    u64 Pv = 0;
-    if (int rc = count_windows(false, 0, PF_BINS, Pv)) return rc;
-    u64 cap = PF_MAX_PASS_WINDOWS;
-    if (const auto forced = env_u64("LZANI_PREFILTER_MAX_WINDOWS")) cap = *forced;
-    else {                                                     // a quarter of the free device memory for the 24 B per window (a choice, not a measurement)
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        cap = std::min<u64>(cap, (u64)free_b / 4 / 24);
-    }
-    pinfo.cap = cap;
-    info.positions = Pv;
-    const bool one_pass = forced_passes ? *forced_passes == 1 : Pv <= cap;
-    pf.bin_lo = {0, PF_BINS};
-    u64 D = 0, M = 0;
-    if (Pv && one_pass) {
-        if (Pv > PF_MAX_PASS_WINDOWS)
-            return fail(c, LZANI_ERR_ARG, "lzani_prefilter: " + std::to_string(Pv) + " sampled k-mer windows in the one forced pass; a pass holds fewer than 2^32");
-        pinfo.largest_pass = Pv;
-        if (int rc = alloc_keys(Pv)) return rc;
-        if (int rc = postings_of(false, 0, PF_BINS, Pv, pf.kmers_of.get(), true, D, M)) return rc;
-        w.ka.reset();                                          // (the count matrix may use the room)
-        w.tmp.reset();
-        // ---- count matrix, a tile of rows at a time over the same postings, and the kept entries of its rows
-        if (M && n > 1) {
-            if (int rc = alloc_tile()) return rc;
-            for (u64 t0 = 0; t0 < n_rows; t0 += rows) {
-                const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n_rows, t0 + rows);
-                if (int rc = count_tile(r0, r1, D, M, true)) return rc;
-                if (int rc = compact_tile(r0, r1)) return rc;
-            }
-        }
-    } else if (Pv) {
-        // ---- several passes: the histogram of the kept windows over the bins, the plan, the workspace of the fullest pass
-        DevMem<unsigned long long> d_hist;
-        std::vector<u64> hist(PF_BINS);
-        HIPCHK(c, d_hist.alloc(PF_BINS));
-        HIPCHK(c, hipMemsetAsync(d_hist, 0, (size_t)PF_BINS * 8, c->stream));
-        if (int rc = keys(PF_HIST, false, 0, PF_BINS, nullptr, 0, d_hist.get())) return rc;
-        HIPCHK(c, hipMemcpyAsync(hist.data(), d_hist, (size_t)PF_BINS * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        d_hist.reset();
-        u32 bad_bin = 0;
-        const int np = plan_passes_impl(hist.data(), cap, forced_passes ? (u32)*forced_passes : 0u, pf.bin_lo, &bad_bin);
-        if (np < 0)
-            return fail(c, LZANI_ERR_ARG, "lzani_prefilter: bin " + std::to_string(bad_bin) + " of the k-mer passes alone holds " + std::to_string(hist[bad_bin]) +
-                                          " sampled k-mer windows, a pass at most " + std::to_string(cap) + ": lower sample_max");
-        std::vector<u64> pass_windows((size_t)np, 0);
-        for (int p = 0; p < np; ++p)
-            for (u32 b = pf.bin_lo[p]; b < pf.bin_lo[p + 1]; ++b) pass_windows[p] += hist[b];
-        const u64 largest = *std::max_element(pass_windows.begin(), pass_windows.end());
-        if (largest > PF_MAX_PASS_WINDOWS)
-            return fail(c, LZANI_ERR_ARG, "lzani_prefilter: " + std::to_string(largest) + " sampled k-mer windows in one of the forced passes; a pass holds fewer than 2^32");
-        pinfo.largest_pass = largest;
-        if (int rc = alloc_keys(largest)) return rc;
-        HIPCHK(c, w.runoff.alloc(largest + 1));                // (a pass's distinct k-mers are no more than its windows)
-        if (cross) HIPCHK(c, w.runsplit.alloc(largest + 1));
-        // the matrix tile from what the workspace (and the staging buffer, which stays to the last sweep) leaves
-        const bool with_matrix = n > 1;
-        if (with_matrix) { if (int rc = alloc_tile()) return rc; } else rows = n_rows;
-        // ---- tile outer, pass inner: every (tile, pass) rebuilds the pass's postings and adds them into the tile
-        u64 Psum = 0;
-        int last_p = 0;
-        for (int p = 0; p < np; ++p) if (pass_windows[p]) last_p = p;
-        for (u64 t0 = 0; t0 < n_rows; t0 += rows) {
-            const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n_rows, t0 + rows);
-            bool clear = true;
-            for (int p = 0; p < np; ++p) {
-                if (!pass_windows[p]) continue;                // (nothing to add)
-                const u32 lo = pf.bin_lo[p], hi = pf.bin_lo[p + 1];
-                u64 Pw = 0, Dp = 0, Mp = 0;
-                if (int rc = count_windows(true, lo, hi, Pw)) return rc;
-                if (Pw != pass_windows[p]) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: a pass's windows differ from the histogram's");
-                if (int rc = postings_of(true, lo, hi, Pw, t0 == 0 ? pf.kmers_of.get() : nullptr, t0 + rows >= n_rows && p == last_p, Dp, Mp)) return rc;
-                if (t0 == 0) { Psum += Pw; D += Dp; M += Mp; }
-                if (with_matrix) if (int rc = count_tile(r0, r1, Dp, Mp, clear)) return rc;
-                clear = false;
-            }
-            if (with_matrix) if (int rc = compact_tile(r0, r1)) return rc;
-        }
-        if (Psum != Pv) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: the passes' windows do not sum to the set's");
-    } else if (forced_passes)
-        plan_passes_impl(nullptr, cap, (u32)*forced_passes, pf.bin_lo);
-    pinfo.passes = (u32)pf.bin_lo.size() - 1;
-    info.distinct_kmers = D;
-    info.postings = M;
-    info.entries = entries;
-    for (size_t g = n_rows; g < n; ++g) pf.row_off[g + 1] = entries;      // (cross form: the query rows are empty)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    double ms[PF_STAGES] = {0, 0, 0, 0, 0, 0};
-    HIPCHK(c, clk.collect(ms));
-    info.keys_ms = ms[PF_ST_KEYS]; info.sort_ms = ms[PF_ST_SORT]; info.count_ms = ms[PF_ST_COUNT]; info.compact_ms = ms[PF_ST_COMPACT];
-    pinfo.hist_ms = ms[PF_ST_HIST];
-    if (st) st->info.upload_ms = ms[PF_ST_UPLOAD];
-    TRACE("prefilter: k=%d positions=%llu distinct=%llu postings=%llu entries=%llu tiles=%u passes=%u", k, (unsigned long long)Pv, (unsigned long long)D,
-          (unsigned long long)M, (unsigned long long)entries, info.tiles, pinfo.passes);
-    return LZANI_OK;
-}
-
-}  // namespace
+#include "lzani_prefilter.h"
 
 extern "C" {
 
@@ -2390,186 +1945,6 @@ int lzani_debug_run_candidates(lzani_ctx* c, uint32_t n_rows, const uint32_t* re
     plan->from_index_launches = (uint32_t)c->run.pmfi_launches;
     plan->cand_launches = (uint32_t)c->run.pmc_launches;
     plan->counted_batches = sink.counted_batches;
-    return LZANI_OK;
-}
-
-
-// lzani_prefilter (n_ref null) and lzani_prefilter_cross
-static int prefilter_resident(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, const uint32_t* n_ref, uint64_t* n_entries)
-{
-    if (!c) return LZANI_ERR_ARG;
-    if (!c->gs.n) return fail(c, LZANI_ERR_STATE, "lzani_prefilter: no genomes (call lzani_set_genomes first)");
-    if (c->gs.ooc) return fail(c, LZANI_ERR_STATE, "lzani_prefilter: the genome set is out-of-core; the prefilter needs it resident");
-    if (k < 8 || k > 31) return fail(c, LZANI_ERR_ARG, "lzani_prefilter: k must be 8 .. 31");
-    if (!(min_ratio >= 0)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter: min_ratio must be a number >= 0");
-    HIPCHK(c, hipSetDevice(c->dev));
-    c->pf = Prefilter{};                                       // the last result goes first: two need not fit
-    if (n_ref && (*n_ref == 0 || *n_ref >= c->gs.n)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_cross: n_ref must be 1 .. n - 1");
-    Prefilter pf;
-    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, c->gs.n, nullptr, n_ref ? *n_ref : 0);
-    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }     // (pf releases what it held)
-    pf.work = PrefilterWork{};
-    pf.done = true;
-    c->pf = std::move(pf);
-    if (n_entries) *n_entries = c->pf.info.entries;
-    return LZANI_OK;
-}
-
-int lzani_prefilter(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint64_t* n_entries)
-{
-    return prefilter_resident(c, k, sample_max, min_shared, min_ratio, nullptr, n_entries);
-}
-
-int lzani_prefilter_cross(lzani_ctx* c, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint32_t n_ref, uint64_t* n_entries)
-{
-    return prefilter_resident(c, k, sample_max, min_shared, min_ratio, &n_ref, n_entries);
-}
-
-int lzani_plan_slices(uint32_t n, const uint32_t* len, uint64_t slice_bytes, uint32_t* slice_of)
-{
-    std::vector<u32> first;
-    std::string msg;
-    const int ns = plan_slices_impl(n, len, slice_bytes, first, msg);
-    if (ns > 0 && slice_of)
-        for (int s = 0; s < ns; ++s) std::fill(slice_of + first[s], slice_of + first[s + 1], (uint32_t)s);
-    return ns;
-}
-
-// lzani_prefilter_codes (n_ref null) and lzani_prefilter_codes_cross
-static int prefilter_streamed(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
-                              uint32_t min_shared, double min_ratio, uint64_t slice_bytes, const uint32_t* n_ref, uint64_t* n_entries)
-{
-    if (!c) return LZANI_ERR_ARG;
-    if (!n || !codes || !len) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: empty input");
-    if (k < 8 || k > 31) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: k must be 8 .. 31");
-    if (!(min_ratio >= 0)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: min_ratio must be a number >= 0");
-    u64 total = 0, Lmax = 0;
-    for (u32 g = 0; g < n; ++g) {
-        if (len[g] > 0x3FFFFFFFu - 3u * (u32)c->P.mrd)
-            return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: sequence too long for 32-bit text positions");
-        if (len[g] && !codes[g]) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes: null sequence");
-        total += len[g];
-        Lmax = std::max<u64>(Lmax, len[g]);
-    }
-    HIPCHK(c, hipSetDevice(c->dev));
-    c->pf = Prefilter{};                                       // the last result goes first: two need not fit
-    if (n_ref && (*n_ref == 0 || *n_ref >= n)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter_codes_cross: n_ref must be 1 .. n - 1");
-    if (const auto forced = env_u64("LZANI_PREFILTER_SLICE_BYTES")) slice_bytes = *forced;
-    if (slice_bytes == 0) {                                    // automatic: an eighth of the free device memory (a choice, not a measurement)
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        slice_bytes = std::max<u64>(1, std::min<u64>(total, std::max<u64>(Lmax, (u64)free_b / 8)));
-    }
-    PfStream st;
-    st.codes = codes; st.len = len;
-    std::string msg;
-    const int S = plan_slices_impl(n, len, slice_bytes, st.first, msg);
-    if (S < 0) return fail(c, S, "lzani_prefilter_codes: " + msg);
-    std::vector<u64> off(n);
-    st.bytes.assign((size_t)S, 0);
-    for (int s = 0; s < S; ++s)
-        for (u32 g = st.first[s]; g < st.first[s + 1]; ++g) { off[g] = st.bytes[s]; st.bytes[s] += len[g]; }
-    const u64 cap = *std::max_element(st.bytes.begin(), st.bytes.end());
-    st.info.slices = (uint32_t)S;
-    st.info.stage_bytes = cap;
-    HIPCHK(c, st.stage.alloc(cap));
-    HIPCHK(c, st.d_off.alloc(n));
-    HIPCHK(c, st.d_len.alloc(n));
-    HIPCHK(c, hipMemcpyAsync(st.d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(st.d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    st.bounce.resize((size_t)std::max<u64>(1, std::min<u64>(cap, PF_BOUNCE_BYTES)));
-    Prefilter pf;
-    const int rc = prefilter_impl(c, pf, k, sample_max, min_shared, min_ratio, n, &st, n_ref ? *n_ref : 0);
-    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }     // (pf and st release what they held)
-    pf.work = PrefilterWork{};
-    pf.done = true;
-    pf.streamed = true;
-    pf.sinfo = st.info;
-    c->pf = std::move(pf);
-    if (n_entries) *n_entries = c->pf.info.entries;
-    return LZANI_OK;
-}
-
-int lzani_prefilter_codes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
-                          uint32_t min_shared, double min_ratio, uint64_t slice_bytes, uint64_t* n_entries)
-{
-    return prefilter_streamed(c, n, codes, len, k, sample_max, min_shared, min_ratio, slice_bytes, nullptr, n_entries);
-}
-
-int lzani_prefilter_codes_cross(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, const uint32_t* len, int k, uint64_t sample_max,
-                                uint32_t min_shared, double min_ratio, uint64_t slice_bytes, uint32_t n_ref, uint64_t* n_entries)
-{
-    return prefilter_streamed(c, n, codes, len, k, sample_max, min_shared, min_ratio, slice_bytes, &n_ref, n_entries);
-}
-
-int lzani_get_prefilter_cross_info(const lzani_ctx* c, lzani_prefilter_cross_info* info)
-{
-    if (!c || !info) return LZANI_ERR_ARG;
-    if (!c->pf.done || !c->pf.cross) return LZANI_ERR_STATE;
-    *info = c->pf.cinfo;
-    return LZANI_OK;
-}
-
-int lzani_get_prefilter_stream_info(const lzani_ctx* c, lzani_prefilter_stream_info* info)
-{
-    if (!c || !info) return LZANI_ERR_ARG;
-    if (!c->pf.done || !c->pf.streamed) return LZANI_ERR_STATE;
-    *info = c->pf.sinfo;
-    return LZANI_OK;
-}
-
-int lzani_get_prefilter_pass_info(const lzani_ctx* c, lzani_prefilter_pass_info* info)
-{
-    if (!c || !info) return LZANI_ERR_ARG;
-    if (!c->pf.done) return LZANI_ERR_STATE;
-    *info = c->pf.pinfo;
-    return LZANI_OK;
-}
-
-int lzani_prefilter_pass_plan(const lzani_ctx* c, uint32_t* bin_lo)
-{
-    if (!c) return LZANI_ERR_ARG;
-    if (!c->pf.done) return LZANI_ERR_STATE;
-    if (bin_lo) std::copy(c->pf.bin_lo.begin(), c->pf.bin_lo.end(), bin_lo);
-    return (int)c->pf.bin_lo.size() - 1;
-}
-
-int lzani_plan_passes(const uint64_t* hist, uint64_t cap, uint32_t forced, uint32_t* bin_lo)
-{
-    std::vector<u32> lo;
-    const int np = plan_passes_impl(hist, cap, forced, lo);
-    if (np > 0 && bin_lo) std::copy(lo.begin(), lo.end(), bin_lo);
-    return np;
-}
-
-int lzani_prefilter_fetch(lzani_ctx* c, uint32_t* kmers_of, uint64_t* row_off, uint32_t* ids, uint32_t* shared)
-{
-    if (!c) return LZANI_ERR_ARG;
-    if (!c->pf.done) return fail(c, LZANI_ERR_STATE, "lzani_prefilter_fetch: no prefilter result (call lzani_prefilter first)");
-    HIPCHK(c, hipSetDevice(c->dev));
-    const Prefilter& pf = c->pf;
-    const u32 n = pf.n;
-    // everything into buffers of our own first: the caller's are written only on success
-    std::vector<u32> h_k(kmers_of ? n : 0), h_ids(ids ? pf.info.entries : 0), h_sh(shared ? pf.info.entries : 0);
-    if (kmers_of) HIPCHK(c, hipMemcpy(h_k.data(), pf.kmers_of, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (const PrefilterTile& t : pf.tiles) {
-        const u64 at = pf.row_off[t.r0], cnt = pf.row_off[t.r1] - at;
-        if (!cnt) continue;
-        if (ids) HIPCHK(c, hipMemcpy(h_ids.data() + at, t.ids, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-        if (shared) HIPCHK(c, hipMemcpy(h_sh.data() + at, t.shared, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    }
-    if (kmers_of) memcpy(kmers_of, h_k.data(), h_k.size() * 4);
-    if (row_off) memcpy(row_off, pf.row_off.data(), pf.row_off.size() * 8);
-    if (ids && !h_ids.empty()) memcpy(ids, h_ids.data(), h_ids.size() * 4);
-    if (shared && !h_sh.empty()) memcpy(shared, h_sh.data(), h_sh.size() * 4);
-    return LZANI_OK;
-}
-
-int lzani_get_prefilter_info(const lzani_ctx* c, lzani_prefilter_info* info)
-{
-    if (!c || !info) return LZANI_ERR_ARG;
-    *info = c->pf.info;
     return LZANI_OK;
 }
 

@@ -88,6 +88,37 @@ __device__ __forceinline__ void pf_hist_flush(const u32* s_hist, unsigned long l
     }
 }
 
+// The tail the two key kernels share.  pf_emit: one window of every thread of the block (ok: it is kept and of the pass,
+// key: its canonical k-mer) -- COUNT: counted in `mine`; HIST: added to the block's histogram; CANON / RANK: written at
+// out[base + its rank among the block's kept windows of this step], and base moves past them.  Every thread of the block
+// calls it (pf_block_rank holds barriers).
+template <int MODE>
+__device__ __forceinline__ void pf_emit(bool ok, u64 key, u32 g, const unsigned long long* __restrict__ dict, u64 D, unsigned long long* __restrict__ out,
+                                        u64& base, u32& mine, u32* s_w, u32* s_hist)
+{
+    if (MODE == PF_COUNT) mine += ok;
+    else if (MODE == PF_HIST) { if (ok) atomicAdd(&s_hist[pf_bin(key)], 1u); }
+    else {
+        u32 tot;
+        const u32 r = pf_block_rank(ok, s_w, tot);
+        if (ok) out[base + r] = MODE == PF_CANON ? key : ((u64)pf_find(dict, D, key) << 32) | (u64)g;
+        base += tot;
+    }
+}
+// pf_keys_end: the block's epilogue -- COUNT: the threads' counts reduced into blkcnt[blk] (*s_cnt was cleared before a
+// barrier); HIST: the block's histogram flushed into out.
+template <int MODE>
+__device__ __forceinline__ void pf_keys_end(u32 mine, u32* __restrict__ blkcnt, u64 blk, u32* s_cnt, const u32* s_hist, unsigned long long* __restrict__ out)
+{
+    if (MODE == PF_COUNT) {
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(s_cnt, mine);
+        __syncthreads();
+        if (threadIdx.x == 0) blkcnt[blk] = *s_cnt;
+    }
+    if (MODE == PF_HIST) pf_hist_flush(s_hist, out);
+}
+
 // Block (x, y) = chunk x of PF_CHUNK forward positions of genome g0 + y; its number in the count / offset arrays is
 // cbase[g] + x.  COUNT: blkcnt[block] = kept windows.  CANON / RANK: they are written from blkoff[block] on, in position
 // order -- the canonical k-mer, or  rank in dict << 32 | genome.  RANGED: of the kept windows only those of the pass
@@ -114,22 +145,9 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys(GenomeTab G, const u64* 
         const u64 p = chunk0 + (u64)it * PF_THREADS + threadIdx.x;
         u64 key = 0;
         const bool ok = p < (u64)L && pf_key_at(G, g, L, (int)p, k, mrd, sample_max, key) && pf_in_pass<RANGED>(key, bin_lo, bin_hi);
-        if (MODE == PF_COUNT) mine += ok;
-        else if (MODE == PF_HIST) { if (ok) atomicAdd(&s_hist[pf_bin(key)], 1u); }
-        else {
-            u32 tot;
-            const u32 r = pf_block_rank(ok, s_w, tot);
-            if (ok) out[base + r] = MODE == PF_CANON ? key : ((u64)pf_find(dict, D, key) << 32) | (u64)g;
-            base += tot;
-        }
+        pf_emit<MODE>(ok, key, g, dict, D, out, base, mine, s_w, s_hist);
     }
-    if (MODE == PF_COUNT) {
-        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
-        __syncthreads();
-        if (threadIdx.x == 0) blkcnt[blk] = s_cnt;
-    }
-    if (MODE == PF_HIST) pf_hist_flush(s_hist, out);
+    pf_keys_end<MODE>(mine, blkcnt, blk, &s_cnt, s_hist, out);
 }
 
 // k_pf_keys for genomes that are not resident (lzani_prefilter_codes): their raw symbol codes, 1 B each, lie one after the
@@ -195,22 +213,9 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys_codes(const unsigned cha
         u64 f = 0, key = 0;
         bool ok = chunk0 + (u64)q + (u64)k <= (u64)L && pf_window(s_t2, s_nm, q, k, f);
         if (ok) { key = pf_canon(f, pf_rc_of(f, k)); ok = pf_keep(key, sample_max) && pf_in_pass<RANGED>(key, bin_lo, bin_hi); }
-        if (MODE == PF_COUNT) mine += ok;
-        else if (MODE == PF_HIST) { if (ok) atomicAdd(&s_hist[pf_bin(key)], 1u); }
-        else {
-            u32 tot;
-            const u32 r = pf_block_rank(ok, s_w, tot);
-            if (ok) out[base + r] = MODE == PF_CANON ? key : ((u64)pf_find(dict, D, key) << 32) | (u64)g;
-            base += tot;
-        }
+        pf_emit<MODE>(ok, key, g, dict, D, out, base, mine, s_w, s_hist);
     }
-    if (MODE == PF_COUNT) {
-        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
-        __syncthreads();
-        if (threadIdx.x == 0) blkcnt[blk] = s_cnt;
-    }
-    if (MODE == PF_HIST) pf_hist_flush(s_hist, out);
+    pf_keys_end<MODE>(mine, blkcnt, blk, &s_cnt, s_hist, out);
 }
 
 // in[0 .. n) ascending: block b takes its PF_CHUNK elements from b * PF_CHUNK on and counts (blkcnt[b]) or writes (from

@@ -119,7 +119,7 @@ def sample_max_of(fraction):
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
     deps = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("lzani_core.h", "lzani_layout.h", "lzani_kernels_index.h",
-                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_kernels_prefilter.h", "lzani_prefilter_defs.h", "lzani_multi.h", "lzani_shard_plan.h", "lzani_ooc.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h", "lzani_devmem.h")] + [os.path.join(ROOT, "include", "lzani.h")]
+                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_kernels_prefilter.h", "lzani_prefilter_defs.h", "lzani_multi.h", "lzani_shard_plan.h", "lzani_ooc.h", "lzani_prefilter.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h", "lzani_devmem.h")] + [os.path.join(ROOT, "include", "lzani.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",

@@ -104,10 +104,14 @@ def test_forced_tiling_gives_the_same_result(small, monkeypatch):
         eng.prefilter(k, smax, min_shared, min_ratio)
         whole = eng.prefilter_fetch()
         assert eng.prefilter_info()["tiles"] == 1
+        pi = eng.prefilter_pass_info()
+        assert (pi["passes"], pi["key_sweeps"], pi["hist_ms"]) == (1, 3, 0)
         monkeypatch.setenv("LZANI_PREFILTER_TILE_ROWS", "7")
         eng.prefilter(k, smax, min_shared, min_ratio)
         tiled = eng.prefilter_fetch()
         assert eng.prefilter_info()["tiles"] == (len(seqs) + 6) // 7 > 1
+        pi = eng.prefilter_pass_info()                                   # one pass: the tiles count from the same postings
+        assert (pi["passes"], pi["key_sweeps"], pi["hist_ms"]) == (1, 3, 0)
         _same(tiled, whole, "tiled against whole")
         _same(tiled, want, "tiled against the model")
 

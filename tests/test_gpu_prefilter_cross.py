@@ -12,6 +12,7 @@ import lzani_ctypes as L
 import oracle as O
 import prefilter_cross_model as XM
 import prefilter_model as PM
+import prefilter_pass_model as PP
 import synth_genomes as SG
 import util as U
 
@@ -162,6 +163,7 @@ def test_forced_tiles(engines, monkeypatch, rows, n_ref):
         eng.prefilter_cross(k, n_ref, smax, min_shared, min_ratio)
         _same(eng.prefilter_fetch(), _cross_want("A", seqs, k, smax, n_ref, min_shared, min_ratio), (rows, n_ref, k))
         assert eng.prefilter_info()["tiles"] == (n_ref + rows - 1) // rows
+        assert eng.prefilter_pass_info()["key_sweeps"] == 3               # one pass: every tile counts from the same postings
         assert _check_cross_info(eng, len(seqs), n_ref)["tile_rows"] == min(rows, n_ref)
     monkeypatch.setenv("LZANI_PREFILTER_TILE_ROWS", "1000")                  # above n_ref: clipped to it
     eng.prefilter_cross(16, n_ref)
@@ -174,9 +176,11 @@ def test_forced_passes_and_tiles(engines, monkeypatch, n_ref):
     monkeypatch.setenv("LZANI_PREFILTER_PASSES", "3")
     monkeypatch.setenv("LZANI_PREFILTER_TILE_ROWS", "7")
     for k, (min_shared, min_ratio) in ((16, THRESHOLDS[0]), (31, THRESHOLDS[1])):
+        windows = PP.pass_windows(PP.histogram(seqs, k, PM.SAMPLE_ALL), PP.forced_plan(3))
         eng.prefilter_cross(k, n_ref, PM.SAMPLE_ALL, min_shared, min_ratio)
         _same(eng.prefilter_fetch(), _cross_want("A", seqs, k, PM.SAMPLE_ALL, n_ref, min_shared, min_ratio), (n_ref, k))
         assert eng.prefilter_pass_info()["passes"] == 3 and eng.prefilter_info()["tiles"] == (n_ref + 6) // 7
+        assert eng.prefilter_pass_info()["key_sweeps"] == PP.key_sweeps((n_ref + 6) // 7, windows)
         assert eng.prefilter_info()["postings"] == int(_model("A", seqs, k, PM.SAMPLE_ALL)[0].sum())
         _check_cross_info(eng, len(seqs), n_ref)
 

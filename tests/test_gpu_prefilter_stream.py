@@ -180,10 +180,14 @@ def test_forced_tiling_with_several_slices_gives_the_same_result(streamer, monke
     streamer.prefilter_codes(seqs, k, smax, slice_bytes=slice_sizes(k)["three"])
     assert streamer.prefilter_info()["tiles"] == (len(seqs) + 6) // 7 and streamer.prefilter_stream_info()["slices"] == 3
     _same(streamer.prefilter_fetch(), want, "tiled, three slices")
+    # one pass: the tiles count from the same postings, so the sweeps and the uploads are those of the untiled run
+    assert streamer.prefilter_pass_info()["key_sweeps"] == 3 and streamer.prefilter_stream_info()["slice_uploads"] == 3 * 3 - 2
     # the environment's slice size overrides the argument
     monkeypatch.setenv("LZANI_PREFILTER_SLICE_BYTES", "8197")
     streamer.prefilter_codes(seqs, k, smax, slice_bytes=sum(lens))
-    assert streamer.prefilter_stream_info()["slices"] == L.plan_slices(lens, 8197)[0]
+    si = streamer.prefilter_stream_info()
+    assert si["slices"] == L.plan_slices(lens, 8197)[0]
+    assert streamer.prefilter_pass_info()["key_sweeps"] == 3 and si["slice_uploads"] == 3 * si["slices"] - 2
     _same(streamer.prefilter_fetch(), want, "tiled, many slices")
 
 
