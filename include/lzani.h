@@ -338,6 +338,55 @@ typedef struct lzani_prefilter_cross_info {
 /* LZANI_ERR_STATE unless the context's current prefilter result came from a cross call. */
 int lzani_get_prefilter_cross_info(const lzani_ctx *ctx, lzani_prefilter_cross_info *info);
 
+/* Sparse counting: a second accumulator for the count stage of all four entry points.  The matrix holds n_rows * n_cols
+ * counts whether or not a pair shares anything; the pair table holds the pairs that do, and its size follows them.  Results
+ * are those of the dense form bit for bit: kmers_of, row_off, ids, shared, and positions, distinct_kmers, postings, entries.
+ *   table     S slots, S a power of two, of a u64 key and a u32 count (12 B a slot).  key(a, b) = a << 32 | b with global
+ *             genome ids (a < b; cross form a < n_ref <= b), all ones marks a free slot, the home slot is
+ *             splitmix64(key) & (S - 1), collisions go to the next slot and wrap at S
+ *   size      the largest power of two with 12 * S <= half of the device memory free where the matrix tile would be sized,
+ *             at most the smallest power of two >= 2 * n_rows * n_cols, and at most 2^32 (the kept keys of a tile are
+ *             sorted in one call).  LZANI_PREFILTER_TABLE_SLOTS=<S> forces it (a test and bench hook; a power of two >= 2,
+ *             else LZANI_ERR_ARG)
+ *   tiles     row ranges [r0, r1) as in the dense form, and one tile holds at most S / 2 distinct pairs over all its
+ *             passes.  The first attempt takes all rows, h = n_rows.  An attempt that meets pair S / 2 + 1 is abandoned:
+ *             the table is cleared, h = max(1, h / 2), and the same r0 starts again from its first pass.  A finished tile
+ *             leaves h as it is (clipped to the rows left); h does not grow back.  One row above S / 2 pairs:
+ *             LZANI_ERR_NOMEM, the message names the row and S; the dense form is the way out.  Whether a tile is
+ *             finished depends on its number of distinct pairs only, not on the order the adds arrive in
+ *   sweeps    one pass: the postings are built once and a new attempt only repeats the count, W = 3.  Several:
+ *             W = 2 + 3 * pass_runs, pass_runs the (attempt, non-empty pass) pairs whose postings were built -- P' where
+ *             nothing overflowed, against the dense form's T * P'.  |K(g)| of a pass is added once, whatever is repeated
+ *   output    after a tile's last pass the keys of the slots that pass the kept rule are sorted, which puts them row after
+ *             row with ascending ids; the table's own order is never visible
+ *   mode      LZANI_PF_COUNTING_AUTO (the default) stays dense wherever the dense rule gives one tile or
+ *             LZANI_PREFILTER_TILE_ROWS is set (a forced tile height is a statement about the matrix), and takes the table
+ *             where the matrix would need more than one tile.  A choice, not a measurement: a set whose pairs nearly all
+ *             share a k-mer is better off dense, and that is not detected.  _SPARSE ignores LZANI_PREFILTER_TILE_ROWS.
+ * lzani_prefilter_info of a sparse result: tiles = finished tiles; count_ms = clearing the table and the inserts;
+ * compact_ms = the scan of the slots, the sort and the look-up of the counts. */
+#define LZANI_PF_COUNTING_AUTO   0
+#define LZANI_PF_COUNTING_DENSE  1
+#define LZANI_PF_COUNTING_SPARSE 2
+/* Holds for the context's later prefilter calls; any other mode: LZANI_ERR_ARG.  An earlier result stays. */
+int lzani_set_prefilter_counting(lzani_ctx *ctx, int mode);
+typedef struct lzani_prefilter_sparse_info {
+    uint32_t sparse;                /* 1: the current result was counted into the pair table      */
+    uint32_t attempts, pass_runs;   /* tile attempts (abandoned ones included); (attempt, pass) pairs run */
+    uint32_t reserved_;
+    uint64_t slots, table_bytes;    /* as allocated                                                */
+    uint64_t pairs_seen;            /* pairs with shared >= 1, summed over the finished tiles      */
+    uint64_t max_fill;              /* most slots in use at the end of a finished tile             */
+} lzani_prefilter_sparse_info;
+/* LZANI_ERR_STATE without a prefilter result; all zero for a dense one, and for one that had nothing to count (a single
+ * genome, no postings). */
+int lzani_get_prefilter_sparse_info(const lzani_ctx *ctx, lzani_prefilter_sparse_info *info);
+/* The tile rule as a pure host function (no GPU): row_pairs[r] = the distinct pairs of row r (shared >= 1, over all
+ * passes), slots = S -> tile_r0[0 .. T] (may be NULL; up to n_rows + 1 entries, tile t holds the rows tile_r0[t] ..
+ * tile_r0[t + 1]) and *attempts (may be NULL).  Returns T, LZANI_ERR_ARG (no rows, no row_pairs, slots not a power of
+ * two >= 2), or LZANI_ERR_NOMEM for a row above slots / 2. */
+int lzani_plan_sparse_tiles(uint32_t n_rows, const uint64_t *row_pairs, uint64_t slots, uint32_t *tile_r0, uint32_t *attempts);
+
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
  * takes a reference, builds its index once and parses every query of the row).  Rows are independent; the

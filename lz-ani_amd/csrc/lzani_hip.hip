@@ -267,6 +267,14 @@ struct PrefilterWork {
     DevMem<u32> mat;              // one row tile of the count matrix, rows x n (cross form: rows x n_query)
     DevMem<u32> rowcnt;
     DevMem<u64> rowoff;
+    // sparse counting: the pair table in place of mat
+    DevMem<unsigned long long> sp_keys;           // per slot: a << 32 | b, all ones where it is free
+    DevMem<u32> sp_cnt;           // ... and the pair's count
+    DevMem<u32> sp_ctl;           // slots in use, the overflow word
+    DevMem<u32> sp_bcnt;          // per PF_CHUNK slots: the kept ones
+    DevMem<u64> sp_boff;
+    DevMem<unsigned long long> sp_kin, sp_kout;   // a tile's kept keys in table order / sorted
+    DevMem<unsigned char> sp_tmp; // radix-sort scratch of the kept keys
 };
 struct Prefilter {
     bool done = false;
@@ -277,6 +285,7 @@ struct Prefilter {
     lzani_prefilter_info info{};
     lzani_prefilter_stream_info sinfo{};
     lzani_prefilter_pass_info pinfo{};
+    lzani_prefilter_sparse_info spinfo{}; // all zero unless the pair table counted
     std::vector<u32> bin_lo;              // the pass plan: pass p holds the bins bin_lo[p] .. bin_lo[p + 1]
     DevMem<u32> kmers_of;                 // |K(g)|
     std::vector<u64> row_off;             // CSR of the kept pairs (n + 1)
@@ -309,6 +318,7 @@ struct lzani_ctx {
     void* comm = nullptr;         // ncclComm_t of lzani_comm_init (one process per GPU), lzani_multi.h
     u32 n_ranks = 1, rank = 0;
     u64 mem_req = 0;              // lzani_set_genome_memory: applies at the next lzani_set_genomes; 0 = automatic
+    int pf_counting = LZANI_PF_COUNTING_AUTO;     // lzani_set_prefilter_counting: the accumulator of the later prefilter calls
 
     GenomeSet gs;
     IndexSlabs sl;

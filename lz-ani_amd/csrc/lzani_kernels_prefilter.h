@@ -17,6 +17,10 @@
 //                 later posting (rank, b) of the same run, the lanes side by side over b.  CROSS: a is a reference, the
 //                 b's are the run's queries only, and the tile is n_ref rows of n - n_ref columns
 //   k_pf_rows     a wave per matrix row: the kept entries counted, then written in ascending b
+//   k_pf_count_sparse  k_pf_count with a pair table in place of the matrix tile (sparse counting): every add inserts the
+//                 pair's key by linear probing and adds to its slot; bounded, with an overflow word for a table too small
+//   k_pf_sparse_kept / _fetch / _rowoff  the table's kept keys (counted per block, then written), and behind their sort
+//                 the ids and counts of the sorted keys and where every row of the tile begins
 // No kernel waits for another block.  The sorts between them are lzani_sort_keys (lzani_sort.hip).
 #pragma once
 #include "lzani_prefilter_defs.h"
@@ -404,6 +408,162 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_rows(const u32* __restrict__ 
         cnt += (u32)__popcll(mask);
     }
     if (!WRITE && lane == 0) rowcnt[wave] = cnt;
+}
+
+// ---- Sparse counting: the pair table in place of the matrix tile.  S slots (a power of two) of keys[S] (u64) and cnt[S]
+// (u32); the key of a pair is  a << 32 | b  with global genome ids (a < b; CROSS: a < n_ref <= b), PF_SP_EMPTY (all ones,
+// no pair's key) marks a free slot; a key's home is pf_splitmix64(key) & (S - 1), collisions go on to the next slot and
+// wrap at S.  A slot's key changes once, from empty to its final value.  ctl[PF_SP_USED] = slots claimed,
+// ctl[PF_SP_OVERFLOW] != 0: the tile's pairs are more than S / 2 and the attempt is void.
+
+constexpr u64 PF_SP_EMPTY = ~0ULL;
+enum { PF_SP_USED = 0, PF_SP_OVERFLOW = 1 };
+
+__device__ __forceinline__ void pf_sp_give_up(u32* __restrict__ ctl) { __hip_atomic_store(&ctl[PF_SP_OVERFLOW], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// += 1 at the slot of `key`, which is claimed where the key is new.  At most S probe steps; none waits for another lane.
+// The pre-read goes past the L1 (a relaxed agent-scope load): what it may still return is an empty that has been taken
+// since, never a wrong key, and then the compare-and-swap's old value decides.  The claim that finds S / 2 slots in use
+// already, and a probe sequence that runs out, raise the overflow word: false, and the lane adds no more.
+__device__ __forceinline__ bool pf_sp_add(unsigned long long* __restrict__ keys, u32* __restrict__ cnt, u64 S, u32* __restrict__ ctl, u64 key)
+{
+    const u64 mask = S - 1;
+    u64 slot = pf_splitmix64(key) & mask;
+    for (u64 step = 0; step < S; ++step, slot = (slot + 1) & mask) {
+        u64 cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == PF_SP_EMPTY) {
+            cur = atomicCAS(&keys[slot], (unsigned long long)PF_SP_EMPTY, (unsigned long long)key);
+            if (cur == PF_SP_EMPTY) {                          // the slot is this lane's
+                if ((u64)atomicAdd(&ctl[PF_SP_USED], 1u) >= S / 2) { pf_sp_give_up(ctl); return false; }
+                cur = key;
+            }
+        }
+        if (cur == key) { atomicAdd(&cnt[slot], 1u); return true; }
+    }
+    pf_sp_give_up(ctl);
+    return false;
+}
+
+// k_pf_count with the table behind it: the same waves over the same postings, the same activity test against [r0, r1),
+// and where k_pf_count adds into row[b] the pair's key is inserted and its slot's count goes up by one.  A wave reads the
+// overflow word before every a and leaves where it is raised; a lane whose add fails ends its run.
+template <bool CROSS>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_count_sparse(const unsigned long long* __restrict__ post, u64 M, const u32* __restrict__ runoff, u64 D,
+                                                                u32 n, u32 r0, u32 r1, unsigned long long* __restrict__ keys, u32* __restrict__ cnt, u64 S,
+                                                                u32* __restrict__ ctl, const u32* __restrict__ runsplit, u32 n_ref)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 w0 = (((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6) << 6;      // the wave's first posting
+    const u64 i = w0 + lane;
+    u32 a = 0, end = 0, from = 0;
+    bool act = false;
+    if (i < M) {
+        const u64 key = post[i];
+        const u64 rank = key >> 32;
+        a = (u32)key;
+        if (rank < D && a >= r0 && a < r1) {
+            const u64 e = runoff[rank + 1];
+            end = (u32)(e < M ? e : M);
+            if (CROSS) {
+                from = runsplit[rank];
+                act = from < end;
+            } else
+                act = (u64)end > i + 1;
+        }
+    }
+    u64 todo = __builtin_amdgcn_ballot_w64(act);
+    while (todo) {
+        const u32 ovf = __hip_atomic_load(&ctl[PF_SP_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__builtin_amdgcn_ballot_w64(ovf != 0)) return;     // (the whole wave, whatever lane saw it)
+        const int l = ctz64(todo);
+        todo &= todo - 1;
+        const u32 al = __shfl(a, l), el = __shfl(end, l);
+        const u64 hi = (u64)al << 32;
+        if (CROSS) {
+            const u32 nq = n - n_ref, fl = __shfl(from, l);
+            for (u64 j = (u64)fl + lane; j < (u64)el; j += 64) {
+                const u32 b = (u32)post[j];
+                if (b - n_ref < nq && !pf_sp_add(keys, cnt, S, ctl, hi | b)) break;
+            }
+        } else {
+            for (u64 j = w0 + l + 1 + lane; j < (u64)el; j += 64) {
+                const u32 b = (u32)post[j];
+                if (b < n && !pf_sp_add(keys, cnt, S, ctl, hi | b)) break;
+            }
+        }
+    }
+}
+
+// The kept slots of the table: block b takes the PF_CHUNK slots from b * PF_CHUNK on and counts (blkcnt[b]) or writes
+// (from blkoff[b] on) the keys of the occupied slots whose count passes pf_kept.  The order is the table's, the sort
+// behind it makes it the result's.
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_sparse_kept(const unsigned long long* __restrict__ keys, const u32* __restrict__ cnt, u64 S,
+                                                               const u32* __restrict__ kmers_of, u32 min_shared, double min_ratio,
+                                                               u32* __restrict__ blkcnt, const u64* __restrict__ blkoff, unsigned long long* __restrict__ out)
+{
+    __shared__ u32 s_w[PF_THREADS / 64];
+    __shared__ u32 s_cnt;
+    const u64 i0 = (u64)blockIdx.x * PF_CHUNK;
+    u64 base = WRITE ? blkoff[blockIdx.x] : 0;
+    u32 mine = 0;
+    if (!WRITE) { if (threadIdx.x == 0) s_cnt = 0; __syncthreads(); }
+    for (int it = 0; it < PF_PER_THREAD; ++it) {
+        if (i0 + (u64)it * PF_THREADS >= S) break;
+        const u64 i = i0 + (u64)it * PF_THREADS + threadIdx.x;
+        u64 key = PF_SP_EMPTY;
+        bool ok = false;
+        if (i < S) {
+            key = keys[i];
+            ok = key != PF_SP_EMPTY && pf_kept(cnt[i], kmers_of[(u32)(key >> 32)], kmers_of[(u32)key], min_shared, min_ratio);
+        }
+        if (!WRITE) mine += ok;
+        else {
+            u32 tot;
+            const u32 r = pf_block_rank(ok, s_w, tot);
+            if (ok) out[base + r] = key;
+            base += tot;
+        }
+    }
+    if (!WRITE) {
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        if (threadIdx.x == 0) blkcnt[blockIdx.x] = s_cnt;
+    }
+}
+
+// sorted[0 .. K): the kept keys ascending, i.e. row after row with ascending b.  ids[i] = b, shared[i] = the count of the
+// key's slot, found by the probe sequence of the insert (the key is in the table; S steps at most).
+__global__ void __launch_bounds__(PF_THREADS) k_pf_sparse_fetch(const unsigned long long* __restrict__ sorted, u64 K, const unsigned long long* __restrict__ keys,
+                                                                const u32* __restrict__ cnt, u64 S, u32* __restrict__ ids, u32* __restrict__ shared)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= K) return;
+    const u64 key = sorted[i], mask = S - 1;
+    u64 slot = pf_splitmix64(key) & mask;
+    u32 s = 0;
+    for (u64 step = 0; step < S; ++step, slot = (slot + 1) & mask) {
+        const u64 cur = keys[slot];
+        if (cur == key) { s = cnt[slot]; break; }
+        if (cur == PF_SP_EMPTY) break;
+    }
+    ids[i] = (u32)key;
+    shared[i] = s;
+}
+
+// A thread per row of the tile and one more: rowoff[r] = how many sorted keys lie below (r0 + r) << 32, r = 0 .. nr.
+__global__ void __launch_bounds__(PF_THREADS) k_pf_sparse_rowoff(const unsigned long long* __restrict__ sorted, u64 K, u32 r0, u32 nr, u64* __restrict__ rowoff)
+{
+    const u64 r = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (r > (u64)nr) return;
+    const u64 key = ((u64)r0 + r) << 32;
+    u64 lo = 0, hi = K;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (sorted[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    rowoff[r] = lo;
 }
 
 }  // namespace lzani

@@ -16,6 +16,8 @@
 //     (count of its windows, canonical keys -> sorted dictionary, rank keys -> sorted postings), added into the tile
 //     (count_tile), and after the tile's last pass its kept entries are compacted into a PrefilterTile.  With one pass the
 //     postings are built once, before the tiles, and every tile counts from them
+//     Sparse counting (include/lzani.h): the pair table stands where the matrix tile stands -- alloc_table / count_sparse /
+//     compact_sparse beside alloc_tile / count_tile / compact_tile -- and the tiles come from PfTiles' halving rule
 //   totals, stage times.
 //
 // What the counters count:
@@ -27,7 +29,10 @@
 //   sinfo.slice_uploads / staged_bytes  slices copied into the staging buffer: a sweep walks the slices up or down in
 //       turn and does not copy the one the buffer holds, so W sweeps over S slices upload W (S - 1) + 1
 //   cinfo.tile_rows / matrix_bytes  the tile of the cross matrix.
+//   spinfo (sparse counting)  attempts, pass_runs, slots, table_bytes, pairs_seen, max_fill; info.tiles then counts the
+//       finished tiles, and with several passes W = 2 + 3 pass_runs.
 #pragma once
+#include "lzani_sparse_plan.h"
 
 namespace {
 
@@ -186,16 +191,18 @@ struct PfPass { bool ranged = false; u32 lo = 0, hi = PF_BINS; u64 windows = 0, 
 // n_ref > 0: the cross form -- the matrix is the n_ref reference rows by the n - n_ref query columns, its tiles cover the
 // references only, and every set of postings gets its runsplit.
 struct PfRun {
-    lzani_ctx* c; Prefilter& pf; PrefilterWork& w; lzani_prefilter_info& info; lzani_prefilter_pass_info& pinfo; PfStream* st;
+    lzani_ctx* c; Prefilter& pf; PrefilterWork& w; lzani_prefilter_info& info; lzani_prefilter_pass_info& pinfo; lzani_prefilter_sparse_info& sp; PfStream* st;
     PfClock clk;
     const GenomeTab G;                    // resident source
     const int k; const u64 sample_max; const u32 min_shared; const double min_ratio;
     const u32 n, n_ref, n_rows, n_cols;   // genomes; cross form: references; the count matrix
     u64 n_chunks = 0, rows = 0;           // chunks of all genomes; the tile's height
     std::vector<u64> h_off;               // a tile's row offsets, read back
+    bool sparse = false;                  // the pair table counts, not the matrix tile
+    u64 slots = 0, sp_used = 0;           // its slots; those in use after the last count into it
 
     PfRun(lzani_ctx* c_, Prefilter& pf_, int k_, u64 sample_max_, u32 min_shared_, double min_ratio_, u32 n_, PfStream* st_, u32 n_ref_)
-        : c(c_), pf(pf_), w(pf_.work), info(pf_.info), pinfo(pf_.pinfo), st(st_), clk(c_->stream), G(st_ ? GenomeTab{} : gtab(c_)), k(k_), sample_max(sample_max_),
+        : c(c_), pf(pf_), w(pf_.work), info(pf_.info), pinfo(pf_.pinfo), sp(pf_.spinfo), st(st_), clk(c_->stream), G(st_ ? GenomeTab{} : gtab(c_)), k(k_), sample_max(sample_max_),
           min_shared(std::max<u32>(min_shared_, 1)), min_ratio(min_ratio_), n(n_), n_ref(n_ref_), n_rows(n_ref_ ? n_ref_ : n_), n_cols(n_ref_ ? n_ - n_ref_ : n_) {}
 
     u64 len_of(u32 g) const { return st ? (u64)st->len[g] : (u64)c->gs.L[g]; }
@@ -304,12 +311,14 @@ struct PfRun {
         HIPCHK(c, clk.end());
         return LZANI_OK;
     }
+    // the dense rule: the rows of a matrix tile in half of the free device memory
+    u64 dense_rows(size_t free_b) const { return std::min<u64>(n_rows, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n_cols))); }
     // the height of the matrix tile from what is free now, and the tile's buffers
     int alloc_tile()
     {
         size_t free_b = 0, total_b = 0;
         HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        rows = std::min<u64>(n_rows, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n_cols)));
+        rows = dense_rows(free_b);
         if (const auto forced = env_u64("LZANI_PREFILTER_TILE_ROWS")) rows = std::min<u64>(n_rows, std::max<u64>(1, *forced));
         HIPCHK(c, w.mat.alloc(rows * n_cols));
         HIPCHK(c, w.rowcnt.alloc(rows));
@@ -355,6 +364,102 @@ struct PfRun {
         return LZANI_OK;
     }
 
+    // Which accumulator counts (called where the tile is sized).  Automatic: the matrix wherever the dense rule gives one
+    // tile or a tile height is forced, the table where the matrix would need several tiles (a choice, not a measurement).
+    int choose_counting()
+    {
+        sparse = c->pf_counting == LZANI_PF_COUNTING_SPARSE;
+        if (c->pf_counting != LZANI_PF_COUNTING_AUTO || env_u64("LZANI_PREFILTER_TILE_ROWS")) return LZANI_OK;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        sparse = dense_rows(free_b) < n_rows;
+        return LZANI_OK;
+    }
+    // the slots of the pair table from what is free now, and the table's buffers
+    int alloc_table()
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        const u64 cells = (u64)n_rows * n_cols;                    // (< 2^64)
+        u64 top = 2;                                               // the smallest power of two >= 2 * cells, 2^32 at most
+        while (top < ((u64)1 << 32) && top / 2 < cells) top *= 2;
+        slots = 0;
+        for (u64 s = 2; s <= top && 12 * s <= (u64)free_b / 2; s *= 2) slots = s;
+        if (const auto forced = env_u64("LZANI_PREFILTER_TABLE_SLOTS")) slots = *forced;      // (checked in run())
+        if (!slots) return fail(c, LZANI_ERR_NOMEM, "lzani_prefilter: no room for a pair table of two slots");
+        HIPCHK(c, w.sp_keys.alloc(slots));
+        HIPCHK(c, w.sp_cnt.alloc(slots));
+        HIPCHK(c, w.sp_ctl.alloc(2));
+        HIPCHK(c, w.sp_bcnt.alloc((slots + PF_CHUNK - 1) / PF_CHUNK));
+        HIPCHK(c, w.sp_boff.alloc((slots + PF_CHUNK - 1) / PF_CHUNK + 1));
+        sp.sparse = 1; sp.slots = slots; sp.table_bytes = w.sp_keys.bytes() + w.sp_cnt.bytes();
+        return LZANI_OK;
+    }
+    // count_tile into the pair table.  clear: the attempt's first pass.  overflow: the rows r0 .. r1 hold more than
+    // slots / 2 pairs (with the passes so far), the attempt is void; else sp_used = the slots in use.
+    int count_sparse(u32 r0, u32 r1, const PfPass& p, bool clear, bool& overflow)
+    {
+        HIPCHK(c, clk.begin(PF_ST_COUNT));
+        if (clear) {
+            HIPCHK(c, hipMemsetAsync(w.sp_keys, 0xFF, (size_t)slots * 8, c->stream));
+            HIPCHK(c, hipMemsetAsync(w.sp_cnt, 0, (size_t)slots * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(w.sp_ctl, 0, 8, c->stream));
+        }
+        hipLaunchKernelGGL((n_ref ? k_pf_count_sparse<true> : k_pf_count_sparse<false>), dim3((u32)((p.M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream,
+                           w.kb.get(), p.M, w.runoff.get(), p.D, n, r0, r1, w.sp_keys.get(), w.sp_cnt.get(), slots, w.sp_ctl.get(), (const u32*)w.runsplit.get(), n_ref);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.end());
+        u32 ctl[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(ctl, w.sp_ctl, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        overflow = ctl[PF_SP_OVERFLOW] != 0;
+        sp_used = ctl[PF_SP_USED];
+        return LZANI_OK;
+    }
+    // compact_tile from the pair table: the kept keys, sorted (row after row, ascending b), their ids and counts, the rows' offsets
+    int compact_sparse(u32 r0, u32 r1)
+    {
+        const u32 nr = r1 - r0, blocks = (u32)((slots + PF_CHUNK - 1) / PF_CHUNK);
+        u64 K = 0;
+        HIPCHK(c, clk.begin(PF_ST_COMPACT));
+        hipLaunchKernelGGL(k_pf_sparse_kept<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, w.sp_keys.get(), w.sp_cnt.get(), slots, pf.kmers_of.get(), min_shared,
+                           min_ratio, w.sp_bcnt.get(), w.sp_boff.get(), (unsigned long long*)nullptr);
+        if (int rc = scan_total(w.sp_bcnt, blocks, w.sp_boff, K)) return rc;
+        size_t need = 0;
+        const int bits = 32 + ceil_log2(n);
+        if (lzani_sort_keys(nullptr, nullptr, K, 0, bits, nullptr, &need, c->stream) != 0) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
+        HIPCHK(c, w.sp_kin.reserve(K));
+        HIPCHK(c, w.sp_kout.reserve(K));
+        HIPCHK(c, w.sp_tmp.reserve(need));
+        PrefilterTile tile;
+        tile.r0 = r0; tile.r1 = r1;
+        HIPCHK(c, tile.ids.alloc(K));
+        HIPCHK(c, tile.shared.alloc(K));
+        HIPCHK(c, w.rowoff.reserve((size_t)nr + 1));
+        hipLaunchKernelGGL(k_pf_sparse_kept<true>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, w.sp_keys.get(), w.sp_cnt.get(), slots, pf.kmers_of.get(), min_shared,
+                           min_ratio, w.sp_bcnt.get(), w.sp_boff.get(), w.sp_kin.get());
+        HIPCHK(c, hipGetLastError());
+        size_t have = w.sp_tmp.capacity();
+        const int e = lzani_sort_keys(w.sp_kin, w.sp_kout, K, 0, bits, w.sp_tmp, &have, c->stream);
+        if (e != 0) return fail(c, LZANI_ERR_DEVICE, std::string("lzani_prefilter: sort: ") + hipGetErrorString((hipError_t)e));
+        if (K) hipLaunchKernelGGL(k_pf_sparse_fetch, dim3((u32)((K + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.sp_kout.get(), K, w.sp_keys.get(),
+                                  w.sp_cnt.get(), slots, tile.ids.get(), tile.shared.get());
+        hipLaunchKernelGGL(k_pf_sparse_rowoff, dim3(nr / PF_THREADS + 1), dim3(PF_THREADS), 0, c->stream, w.sp_kout.get(), K, r0, nr, w.rowoff.get());
+        HIPCHK(c, hipGetLastError());
+        h_off.resize((size_t)nr + 1);
+        HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, clk.end());
+        if (h_off[nr] != K) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: the pair table's kept keys lie outside the tile's rows");
+        for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = info.entries + h_off[r + 1];
+        info.entries += K;
+        pf.tiles.push_back(std::move(tile));
+        ++info.tiles;
+        sp.pairs_seen += sp_used;
+        sp.max_fill = std::max<u64>(sp.max_fill, sp_used);
+        return LZANI_OK;
+    }
+
     // Several passes: the histogram of the kept windows over the bins, the plan (pf.bin_lo), and `passes`: those of the plan
     // that hold a window (an empty one has nothing to add), with their windows.
     int plan_from_histogram(u32 forced, std::vector<PfPass>& passes)
@@ -396,7 +501,11 @@ struct PfRun {
     //   workspace of the fullest pass stays, and runoff / runsplit are allocated at largest + 1 (a pass's distinct k-mers
     //   are no more than its windows).  Streamed: the staging buffer goes after the last key sweep and not before -- with
     //   one pass that is before the tile is sized, with several the tile is sized beside it.
-    // |K(g)| is accumulated on the first tile only, once per pass.
+    //   Sparse counting: the same loop over PfTiles, with attempts that may be abandoned.  Then a tile's passes can run more
+    //   than once, so |K(g)| of a pass goes in where the pass's postings are built for the first time (kmers_in), and the
+    //   last key sweep is not known in advance: with several passes the staging buffer is released behind the loop.  With
+    //   one pass an abandoned attempt repeats the count only.  W = 2 + 3 pass_runs with several passes.
+    // |K(g)| is accumulated once per pass: dense, on the first tile.
     int tiles_and_passes(std::vector<PfPass>& passes)
     {
         const bool rebuild = passes[0].ranged;
@@ -410,22 +519,41 @@ struct PfRun {
             w.tmp.reset();
         }
         const bool with_matrix = n > 1 && (rebuild || passes[0].M);
-        if (with_matrix) { if (int rc = alloc_tile()) return rc; } else rows = n_rows;
-        for (u64 t0 = 0; t0 < n_rows; t0 += rows) {
-            const u32 r0 = (u32)t0, r1 = (u32)std::min<u64>(n_rows, t0 + rows);
-            bool clear = true;
-            for (PfPass& p : passes) {
+        if (with_matrix) {
+            if (int rc = choose_counting()) return rc;
+            if (int rc = sparse ? alloc_table() : alloc_tile()) return rc;
+        } else rows = n_rows;
+        if (sparse && !rebuild) sp.pass_runs = 1;
+        std::vector<char> kmers_in(passes.size(), 0);             // per pass: its |K(g)| is in
+        PfTiles tl(n_rows, sparse ? n_rows : rows);
+        while (tl.more()) {
+            const u32 r0 = tl.r0, r1 = tl.r1();
+            tl.attempt();
+            bool clear = true, overflow = false;
+            for (size_t i = 0; i < passes.size() && !overflow; ++i) {
+                PfPass& p = passes[i];
                 if (rebuild) {
                     u64 Pw = 0;
                     if (int rc = count_windows(p, Pw)) return rc;
                     if (Pw != p.windows) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: a pass's windows differ from the histogram's");
-                    if (int rc = build_postings(p, t0 == 0 ? pf.kmers_of.get() : nullptr, t0 + rows >= n_rows && &p == &passes.back())) return rc;
+                    if (int rc = build_postings(p, kmers_in[i] ? nullptr : pf.kmers_of.get(), !sparse && r1 == n_rows && i + 1 == passes.size())) return rc;
+                    kmers_in[i] = 1;
+                    if (sparse) ++sp.pass_runs;
                 }
-                if (with_matrix) if (int rc = count_tile(r0, r1, p, clear)) return rc;
+                if (with_matrix) if (int rc = sparse ? count_sparse(r0, r1, p, clear, overflow) : count_tile(r0, r1, p, clear)) return rc;
                 clear = false;
             }
-            if (with_matrix) if (int rc = compact_tile(r0, r1)) return rc;
+            if (overflow) {
+                if (!tl.halve())
+                    return fail(c, LZANI_ERR_NOMEM, "lzani_prefilter: row " + std::to_string(r0) + " alone shares k-mers with more than " + std::to_string(slots / 2) +
+                                                    " genomes, half of the pair table's " + std::to_string(slots) + " slots: count into the matrix (dense counting)");
+                continue;
+            }
+            if (with_matrix) if (int rc = sparse ? compact_sparse(r0, r1) : compact_tile(r0, r1)) return rc;
+            tl.finished();
         }
+        if (sparse) sp.attempts = tl.attempts;
+        if (st && sparse && rebuild) { HIPCHK(c, hipStreamSynchronize(c->stream)); st->stage.reset(); }
         return LZANI_OK;
     }
 
@@ -437,6 +565,8 @@ struct PfRun {
         if (forced_passes && (*forced_passes < 1 || *forced_passes > PF_BINS))
             return fail(c, LZANI_ERR_ARG, "lzani_prefilter: LZANI_PREFILTER_PASSES must be 1 .. " + std::to_string((int)PF_BINS));
         const u32 forced = forced_passes ? (u32)*forced_passes : 0u;
+        if (const auto forced_slots = env_u64("LZANI_PREFILTER_TABLE_SLOTS"))
+            if (!pf_slots_ok(*forced_slots)) return fail(c, LZANI_ERR_ARG, "lzani_prefilter: LZANI_PREFILTER_TABLE_SLOTS must be a power of two >= 2");
 
         // chunks of PF_CHUNK forward positions, genome after genome
         std::vector<u64> cbase((size_t)n + 1, 0);
@@ -485,8 +615,9 @@ struct PfRun {
         info.keys_ms = ms[PF_ST_KEYS]; info.sort_ms = ms[PF_ST_SORT]; info.count_ms = ms[PF_ST_COUNT]; info.compact_ms = ms[PF_ST_COMPACT];
         pinfo.hist_ms = ms[PF_ST_HIST];
         if (st) st->info.upload_ms = ms[PF_ST_UPLOAD];
-        TRACE("prefilter: k=%d positions=%llu distinct=%llu postings=%llu entries=%llu tiles=%u passes=%u", k, (unsigned long long)Pv,
-              (unsigned long long)info.distinct_kmers, (unsigned long long)info.postings, (unsigned long long)info.entries, info.tiles, pinfo.passes);
+        TRACE("prefilter: k=%d positions=%llu distinct=%llu postings=%llu entries=%llu tiles=%u passes=%u sparse=%u attempts=%u slots=%llu", k, (unsigned long long)Pv,
+              (unsigned long long)info.distinct_kmers, (unsigned long long)info.postings, (unsigned long long)info.entries, info.tiles, pinfo.passes, sp.sparse,
+              sp.attempts, (unsigned long long)sp.slots);
         return LZANI_OK;
     }
 };
@@ -641,6 +772,33 @@ int lzani_prefilter_pass_plan(const lzani_ctx* c, uint32_t* bin_lo)
     if (!c->pf.done) return LZANI_ERR_STATE;
     if (bin_lo) std::copy(c->pf.bin_lo.begin(), c->pf.bin_lo.end(), bin_lo);
     return (int)c->pf.bin_lo.size() - 1;
+}
+
+int lzani_set_prefilter_counting(lzani_ctx* c, int mode)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (mode != LZANI_PF_COUNTING_AUTO && mode != LZANI_PF_COUNTING_DENSE && mode != LZANI_PF_COUNTING_SPARSE)
+        return fail(c, LZANI_ERR_ARG, "lzani_set_prefilter_counting: the mode is LZANI_PF_COUNTING_AUTO, _DENSE or _SPARSE");
+    c->pf_counting = mode;
+    return LZANI_OK;
+}
+
+int lzani_get_prefilter_sparse_info(const lzani_ctx* c, lzani_prefilter_sparse_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->pf.done) return LZANI_ERR_STATE;
+    *info = c->pf.spinfo;
+    return LZANI_OK;
+}
+
+int lzani_plan_sparse_tiles(uint32_t n_rows, const uint64_t* row_pairs, uint64_t slots, uint32_t* tile_r0, uint32_t* attempts)
+{
+    std::vector<u32> first;
+    u32 att = 0;
+    const int nt = plan_sparse_tiles_impl(n_rows, row_pairs, slots, first, att);
+    if (nt > 0 && tile_r0) std::copy(first.begin(), first.end(), tile_r0);
+    if (nt > 0 && attempts) *attempts = att;
+    return nt;
 }
 
 int lzani_plan_passes(const uint64_t* hist, uint64_t cap, uint32_t forced, uint32_t* bin_lo)

@@ -52,6 +52,8 @@ struct Params {
     int flt_k = 0;
     string flt_fraction_arg;                                // --flt-kmers-fraction as given; checked after the flags are read
     double flt_fraction = 1;
+    string flt_counting_arg;                                // --flt-kmers-counting as given; checked after the flags are read
+    int flt_counting = LZANI_PF_COUNTING_AUTO;
 };
 
 static Params P;
@@ -113,6 +115,8 @@ static void usage()
          << "      --flt-kmers <k> <float>    - filter built on the GPU instead of read from a file: pairs whose shared canonical k-mers (8 <= k <= 31)\n"
          << "                                   are at least <float> of the smaller genome's k-mer set (not with --flt-kmerdb)\n"
          << "      --flt-kmers-fraction <float> - fraction of the k-mers sampled for --flt-kmers, in (0, 1] (default: 1)\n"
+         << "      --flt-kmers-counting <auto|dense|sparse> - where --flt-kmers counts shared k-mers: a matrix of all pairs, or a table of\n"
+         << "                                   the pairs that share one (default: auto, the table where the matrix needs several tiles)\n"
          << "Options - output specification:\n"
          << "  -o, --out <file_name>          - output file name\n"
          << "      --out-ids <file_name>      - output file name for ids file (optional)\n"
@@ -193,6 +197,7 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--flt-kmerdb" && has(2)) { P.filter_fn = argv[i + 1]; P.filter_thr = atof(argv[i + 2]); i += 3; }
         else if (par == "--flt-kmers" && has(2)) { P.flt_kmers = true; P.flt_k = atoi(argv[i + 1]); P.filter_thr = atof(argv[i + 2]); i += 3; }
         else if (par == "--flt-kmers-fraction" && has(1)) { P.flt_fraction_arg = argv[i + 1]; i += 2; }
+        else if (par == "--flt-kmers-counting" && has(1)) { P.flt_counting_arg = argv[i + 1]; i += 2; }
         else if ((par == "-V" || par == "--verbose") && has(1)) { P.verbosity = (uint32_t)atoi(argv[i + 1]); i += 2; }
         else if (par == "--out-type" && has(1)) {
             string t = argv[i + 1];
@@ -244,6 +249,15 @@ static bool parse_params(int argc, char** argv)
     if (!P.flt_fraction_arg.empty() && !parse_fraction(P.flt_fraction_arg.c_str(), P.flt_fraction)) {
         cerr << "Invalid value for --flt-kmers-fraction: " << P.flt_fraction_arg << " (a number in (0, 1])" << endl;
         exit(1);
+    }
+    if (!P.flt_counting_arg.empty()) {
+        if (P.flt_counting_arg == "auto") P.flt_counting = LZANI_PF_COUNTING_AUTO;
+        else if (P.flt_counting_arg == "dense") P.flt_counting = LZANI_PF_COUNTING_DENSE;
+        else if (P.flt_counting_arg == "sparse") P.flt_counting = LZANI_PF_COUNTING_SPARSE;
+        else {
+            cerr << "Invalid value for --flt-kmers-counting: " << P.flt_counting_arg << " (auto, dense or sparse)" << endl;
+            exit(1);
+        }
     }
     if (P.inputs.empty()) { cerr << "Input file names not provided\n"; return false; }
     // The engine's parameter envelope (lz-ani_amd/csrc/lzani_layout.h: params_supported).  The reference accepts any
@@ -320,6 +334,8 @@ struct Engine {
     int (*get_prefilter_pass_info)(const lzani_ctx*, lzani_prefilter_pass_info*) = nullptr;
     int (*prefilter_cross)(lzani_ctx*, int, uint64_t, uint32_t, double, uint32_t, uint64_t*) = nullptr;
     int (*prefilter_codes_cross)(lzani_ctx*, uint32_t, const uint8_t* const*, const uint32_t*, int, uint64_t, uint32_t, double, uint64_t, uint32_t, uint64_t*) = nullptr;
+    int (*set_prefilter_counting)(lzani_ctx*, int) = nullptr;
+    int (*get_prefilter_sparse_info)(const lzani_ctx*, lzani_prefilter_sparse_info*) = nullptr;
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -337,7 +353,7 @@ struct Engine {
         BIND(group_create) BIND(group_destroy) BIND(group_last_error) BIND(group_set_genomes) BIND(group_run_rows) BIND(group_get_timing)
         BIND(set_genome_memory) BIND(get_residency) BIND(group_set_genome_memory) BIND(group_get_residency)
         BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info) BIND(prefilter_codes) BIND(get_prefilter_stream_info) BIND(get_prefilter_pass_info)
-        BIND(prefilter_cross) BIND(prefilter_codes_cross)
+        BIND(prefilter_cross) BIND(prefilter_codes_cross) BIND(set_prefilter_counting) BIND(get_prefilter_sparse_info)
 #undef BIND
         return true;
     }
@@ -392,6 +408,7 @@ static void print_gpu_timing(int dev, const lzani_timing& t, bool summed, const 
 // them; with it -- or where that set went out-of-core or did not fit -- the genomes stay in host memory and
 // lzani_prefilter_codes streams them through a staging buffer of at most --gpu-mem bytes (automatic without).  n_ref > 0
 // (query2ref): the cross form of either, the kept pairs of the references 0 .. n_ref - 1 with the queries behind them.
+// --flt-kmers-counting goes to the context before the stage runs.
 static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, uint32_t n_ref = 0)
 {
     const uint32_t n = (uint32_t)g.size();
@@ -412,6 +429,7 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, u
     vector<uint64_t> row_off((size_t)n + 1, 0);
     vector<uint32_t> ids;
     bool streamed = P.gpu_mem != 0;
+    E.set_prefilter_counting(ctx, P.flt_counting);
     if (streamed) rc = codes(ctx, ptr, len, P.gpu_mem, &kept);
     else {
         rc = E.set_genomes(ctx, n, ptr.data(), len.data());
@@ -422,6 +440,7 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, u
             rc = E.create(&P.lz, P.device, &ctx);
             if (rc != LZANI_OK) { cerr << "K-mer filter failed: lzani_create failed with code " << rc << endl; return false; }
             streamed = true;
+            E.set_prefilter_counting(ctx, P.flt_counting);
             rc = codes(ctx, ptr, len, 0, &kept);
         }
     }
@@ -430,7 +449,10 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, u
     lzani_prefilter_info pi;
     lzani_prefilter_stream_info si;
     lzani_prefilter_pass_info ps;
-    string stream_note;
+    lzani_prefilter_sparse_info sp;
+    string stream_note, sparse_note;
+    if (E.get_prefilter_sparse_info(ctx, &sp) == LZANI_OK && sp.sparse)                   // (the tiles are in the line already)
+        sparse_note = "; sparse counting: " + to_string(sp.attempts) + " attempt(s), " + to_string(sp.slots) + " slots";
     if (streamed && E.get_prefilter_stream_info(ctx, &si) == LZANI_OK) {
         ostringstream ss;
         ss << "; streamed: " << si.slices << " slice(s), " << si.slice_uploads << " upload(s), upload " << si.upload_ms << " ms, staging " << si.stage_bytes << " bytes";
@@ -441,7 +463,7 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, u
     if (P.verbosity >= 2 && E.get_prefilter_info(ctx, &pi) == LZANI_OK)
         cerr << "k-mer filter on device " << P.device << ": k " << pi.k << ", " << pi.positions << " sampled windows, " << pi.distinct_kmers
              << " distinct k-mers, " << pi.postings << " postings, " << pi.entries << " kept pairs, " << pi.tiles << " tile(s); keys " << pi.keys_ms
-             << " ms, sorts " << pi.sort_ms << " ms, counting " << pi.count_ms << " ms, compaction " << pi.compact_ms << " ms" << stream_note << "\n";
+             << " ms, sorts " << pi.sort_ms << " ms, counting " << pi.count_ms << " ms, compaction " << pi.compact_ms << " ms" << sparse_note << stream_note << "\n";
     E.destroy(ctx);
     flt.names.clear();
     filter_from_pairs(n, row_off, ids, flt);

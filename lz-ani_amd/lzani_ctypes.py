@@ -37,7 +37,8 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_prefilter", "lzani_prefilter_fetch", "lzani_get_prefilter_info",
            "lzani_prefilter_codes", "lzani_plan_slices", "lzani_get_prefilter_stream_info",
            "lzani_get_prefilter_pass_info", "lzani_prefilter_pass_plan", "lzani_plan_passes",
-           "lzani_prefilter_cross", "lzani_prefilter_codes_cross", "lzani_get_prefilter_cross_info")
+           "lzani_prefilter_cross", "lzani_prefilter_codes_cross", "lzani_get_prefilter_cross_info",
+           "lzani_set_prefilter_counting", "lzani_get_prefilter_sparse_info", "lzani_plan_sparse_tiles")
 
 
 class LzaniError(RuntimeError):
@@ -106,6 +107,12 @@ class PrefilterCrossInfo(C.Structure):
                 ("matrix_bytes", C.c_uint64)]
 
 
+class PrefilterSparseInfo(C.Structure):
+    _fields_ = [("sparse", C.c_uint32), ("attempts", C.c_uint32), ("pass_runs", C.c_uint32), ("reserved_", C.c_uint32),
+                ("slots", C.c_uint64), ("table_bytes", C.c_uint64), ("pairs_seen", C.c_uint64), ("max_fill", C.c_uint64)]
+
+
+PF_COUNTING = {"auto": 0, "dense": 1, "sparse": 2}   # LZANI_PF_COUNTING_*
 PREFILTER_BINS = 4096                               # bins of the prefilter's k-mer passes
 SAMPLE_ALL = 0xFFFFFFFFFFFFFFFF                     # lzani_prefilter's sample_max that keeps every k-mer
 
@@ -119,7 +126,7 @@ def sample_max_of(fraction):
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
     deps = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("lzani_core.h", "lzani_layout.h", "lzani_kernels_index.h",
-                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_kernels_prefilter.h", "lzani_prefilter_defs.h", "lzani_multi.h", "lzani_shard_plan.h", "lzani_ooc.h", "lzani_prefilter.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h", "lzani_devmem.h")] + [os.path.join(ROOT, "include", "lzani.h")]
+                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_kernels_prefilter.h", "lzani_prefilter_defs.h", "lzani_multi.h", "lzani_shard_plan.h", "lzani_sparse_plan.h", "lzani_ooc.h", "lzani_prefilter.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h", "lzani_devmem.h")] + [os.path.join(ROOT, "include", "lzani.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -196,6 +203,9 @@ def load_library():
         lib.lzani_prefilter_codes_cross.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_double,
                                                     C.c_uint64, C.c_uint32, C.c_void_p]
         lib.lzani_get_prefilter_cross_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_set_prefilter_counting.argtypes = [C.c_void_p, C.c_int]
+        lib.lzani_get_prefilter_sparse_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_plan_sparse_tiles.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -305,6 +315,19 @@ def plan_passes(hist, cap, forced=0):
     if np_ < 0:
         raise LzaniError(f"lzani_plan_passes: {ERRORS.get(np_, np_)}")
     return bin_lo[:np_ + 1].copy()
+
+
+def plan_sparse_tiles(row_pairs, slots):
+    """Tiles of sparse counting (lzani_plan_sparse_tiles; no GPU needed): (tile_r0[T + 1], attempts) from the distinct pairs
+    of every row and the slots of the pair table."""
+    lib = load_library()
+    row_pairs = np.ascontiguousarray(row_pairs, dtype=np.uint64)
+    tile_r0 = np.zeros(len(row_pairs) + 1, dtype=np.uint32)
+    attempts = C.c_uint32(0)
+    nt = lib.lzani_plan_sparse_tiles(len(row_pairs), _ptr(row_pairs) if len(row_pairs) else None, C.c_uint64(int(slots)), _ptr(tile_r0), C.byref(attempts))
+    if nt < 0:
+        raise LzaniError(f"lzani_plan_sparse_tiles: {ERRORS.get(nt, nt)}")
+    return tile_r0[:nt + 1].copy(), attempts.value
 
 
 def plan_slices(lens, slice_bytes):
@@ -503,6 +526,15 @@ class Engine:
                                                          C.c_uint64(int(slice_bytes)), C.c_uint32(int(n_ref)), C.byref(cnt)),
                     "lzani_prefilter_codes_cross")
         return int(cnt.value)
+
+    def set_prefilter_counting(self, mode):
+        """lzani_set_prefilter_counting: "auto", "dense" or "sparse" (or the LZANI_PF_COUNTING_* number) for the later prefilter calls."""
+        self._check(self.lib.lzani_set_prefilter_counting(self.h, int(PF_COUNTING.get(mode, mode))), "lzani_set_prefilter_counting")
+
+    def prefilter_sparse_info(self):
+        o = PrefilterSparseInfo()
+        self._check(self.lib.lzani_get_prefilter_sparse_info(self.h, C.byref(o)), "lzani_get_prefilter_sparse_info")
+        return {k: getattr(o, k) for k, _ in PrefilterSparseInfo._fields_ if k != "reserved_"}
 
     def prefilter_cross_info(self):
         o = PrefilterCrossInfo()

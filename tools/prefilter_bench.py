@@ -12,14 +12,17 @@ Every figure is the median of --repeats runs after one warm-up run.
               memory (--slice-bytes N, or --slices K for the smallest size that gives at most K slices; default: one
               slice) -- with both info structs and the device memory each path holds for genomes; --passes P forces the
               k-mer passes of both (LZANI_PREFILTER_PASSES) and the line carries passes, key_sweeps, hist_ms and
-              workspace_bytes of lzani_get_prefilter_pass_info
+              workspace_bytes of lzani_get_prefilter_pass_info; --counting auto|dense|sparse chooses the accumulator of both
+              (lzani_set_prefilter_counting; the line then carries lzani_get_prefilter_sparse_info and count_ms + compact_ms
+              of every run) and --tile-rows R forces the height of the dense matrix tile (LZANI_PREFILTER_TILE_ROWS)
   --cross N_REF [N_REF ...]  instead of the two workloads: the same 2,000-genome set, k = 21, every fifth k-mer, through the
               all-pairs form (lzani_prefilter) and, for every n_ref given, the cross form (lzani_prefilter_cross: the first
               n_ref genomes as references against the rest) in one process: count_ms, compact_ms (every run and the
               median), matrix_bytes, tiles, entries and the atomic adds of both forms; the cross result is checked against
               the all-pairs result restricted to the cross pairs
 Usage: tools/prefilter_bench.py [--out profiles/prefilter_bench.json] [--repeats 3] [--small] [--no-dense]
-       tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--passes P] [--out profiles/prefilter_stream_bench.json]
+       tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--passes P] [--counting sparse] [--tile-rows R]
+                                [--out profiles/prefilter_stream_bench.json]
        tools/prefilter_bench.py --cross N_REF [N_REF ...] [--out profiles/prefilter_cross_bench.json]"""
 import argparse
 import json
@@ -94,8 +97,17 @@ def streamed(a):
         sb = next(x for x in range(-(-total // a.slices) // 4096 * 4096, total + 4096, 4096) if x >= max(lens) and L.plan_slices(lens, x)[0] <= a.slices)
     if a.passes:
         os.environ["LZANI_PREFILTER_PASSES"] = str(a.passes)
+    if a.tile_rows:
+        os.environ["LZANI_PREFILTER_TILE_ROWS"] = str(a.tile_rows)
     res = dict(tool="prefilter_bench --streamed", k=K, fraction=0.2, genomes=n, bases=total, repeats=a.repeats, slice_bytes=sb,
-               forced_passes=a.passes)
+               forced_passes=a.passes, counting=a.counting, tile_rows=a.tile_rows, matrix_bytes=4 * n * min(n, a.tile_rows or n))
+
+    def run_info(eng):
+        return dict(eng.prefilter_info(), **eng.prefilter_pass_info(), sparse=eng.prefilter_sparse_info())
+
+    def per_run(runs):
+        return dict(count_plus_compact_ms_runs=[r["count_ms"] + r["compact_ms"] for r in runs], count_ms_runs=[r["count_ms"] for r in runs],
+                    compact_ms_runs=[r["compact_ms"] for r in runs])
 
     def median_of(runs, keys):
         out = dict(runs[0])
@@ -105,33 +117,38 @@ def streamed(a):
 
     eng = L.Engine()
     eng.set_genomes(seqs)
-    eng.prefilter(K, smax, min_shared, min_ratio)
+    eng.prefilter(K, smax, min_shared, min_ratio)                   # the dense result is what every form must give
     want = eng.prefilter_fetch()
+    eng.set_prefilter_counting(a.counting)
+    eng.prefilter(K, smax, min_shared, min_ratio)                   # warm-up in the form measured
+    same_resident = all(np.array_equal(x, y) for x, y in zip(eng.prefilter_fetch(), want))
     runs, walls = [], []
     for _ in range(a.repeats):
         t = time.perf_counter()
         eng.prefilter(K, smax, min_shared, min_ratio)
         walls.append(time.perf_counter() - t)
-        runs.append(dict(eng.prefilter_info(), **eng.prefilter_pass_info()))
+        runs.append(run_info(eng))
     res["resident"] = dict(median_of(runs, STAGES + ("hist_ms",)), wall_ms=float(np.median(walls)) * 1e3, walls_ms=[w * 1e3 for w in walls],
-                           keys_ms_runs=[r["keys_ms"] for r in runs], bytes_genomes=eng.layout()["bytes_genomes"])
+                           keys_ms_runs=[r["keys_ms"] for r in runs], bytes_genomes=eng.layout()["bytes_genomes"], equal_to_dense=bool(same_resident),
+                           **per_run(runs))
     eng.close()
     print("resident:", json.dumps(res["resident"]), flush=True)
 
     eng = L.Engine()
+    eng.set_prefilter_counting(a.counting)
     eng.prefilter_codes(seqs, K, smax, min_shared, min_ratio, slice_bytes=sb)
     got = eng.prefilter_fetch()
-    same = all(np.array_equal(x, y) for x, y in zip(got, want))
+    same = same_resident and all(np.array_equal(x, y) for x, y in zip(got, want))
     runs, sruns, walls = [], [], []
     for _ in range(a.repeats):
         t = time.perf_counter()
         eng.prefilter_codes(seqs, K, smax, min_shared, min_ratio, slice_bytes=sb)
         walls.append(time.perf_counter() - t)
-        runs.append(dict(eng.prefilter_info(), **eng.prefilter_pass_info()))
+        runs.append(run_info(eng))
         sruns.append(eng.prefilter_stream_info())
     eng.close()
-    res["streamed"] = dict(median_of(runs, STAGES + ("hist_ms",)), wall_ms=float(np.median(walls)) * 1e3, stream=median_of(sruns, ("upload_ms",)),
-                           equal_to_resident=bool(same))
+    res["streamed"] = dict(median_of(runs, STAGES + ("hist_ms",)), wall_ms=float(np.median(walls)) * 1e3, walls_ms=[w * 1e3 for w in walls],
+                           keys_ms_runs=[r["keys_ms"] for r in runs], stream=median_of(sruns, ("upload_ms",)), equal_to_resident=bool(same), **per_run(runs))
     print("streamed:", json.dumps(res["streamed"]), flush=True)
     line = json.dumps(res)
     print(line)
@@ -139,7 +156,7 @@ def streamed(a):
     with open(a.out, "w") as f:
         f.write(line + "\n")
     if not same:
-        sys.exit("the streamed prefilter's result differs from the resident one's")
+        sys.exit("the prefilter's results differ: streamed from resident, or the form measured from the dense one")
 
 
 def cross(a):
@@ -202,6 +219,8 @@ def main():
     ap.add_argument("--streamed", action="store_true", help="lzani_prefilter against lzani_prefilter_codes on one set")
     ap.add_argument("--slice-bytes", type=int, default=0, help="--streamed: slice size (default: the whole set in one slice)")
     ap.add_argument("--passes", type=int, default=0, help="--streamed: force this many k-mer passes (LZANI_PREFILTER_PASSES)")
+    ap.add_argument("--counting", choices=("auto", "dense", "sparse"), default="auto", help="--streamed: the accumulator of the count stage (lzani_set_prefilter_counting)")
+    ap.add_argument("--tile-rows", type=int, default=0, help="--streamed: force the height of the dense matrix tile (LZANI_PREFILTER_TILE_ROWS)")
     ap.add_argument("--slices", type=int, default=0, help="--streamed: the smallest slice size (in 4 KiB steps) that gives at most this many slices")
     ap.add_argument("--cross", type=int, nargs="+", default=None, metavar="N_REF",
                     help="the cross form (the first N_REF genomes against the rest) beside the all-pairs form on one set")
