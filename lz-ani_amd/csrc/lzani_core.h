@@ -530,11 +530,16 @@ LZ_HD u32 compress_even16(u32 x)      // bits 0,2,4,.. of x -> bits 0..15
     x = (x | (x >> 8)) & 0x0000FFFFu;
     return x;
 }
-LZ_HD u32 bits_below16(int n) { return n <= 0 ? 0u : n >= 16 ? 0xFFFFu : (1u << n) - 1u; }
+LZ_HD int clamp16(int n) { return imax(0, imin(n, 16)); }
+LZ_HD u32 bits_range16(int a, int b)   // bits a <= j < b of a 16-bit window (two clamps, two shifts, no compare-and-select chain)
+{
+    const int l = clamp16(a), h = imax(clamp16(b), l);
+    return (1u << h) - (1u << l);
+}
 LZ_HD u32 valid_bits16(const TextView& t, int p0)
 {
-    u32 v = bits_below16(t.L - p0) & ~bits_below16(-p0);
-    if (t.rc0 != NO_RC) v |= bits_below16(t.rc0 + t.L - p0) & ~bits_below16(t.rc0 - p0);
+    u32 v = bits_range16(-p0, t.L - p0);
+    if (t.rc0 != NO_RC) v |= bits_range16(t.rc0 - p0, t.rc0 + t.L - p0);
     return v;
 }
 // bit j (j < 16) = 1 iff Q[q0+j] does not match R[r0+j]; bits 16..31 set.  Equal to lane_mism32's low 16 bits.
@@ -587,41 +592,116 @@ LZ_HD u32 ext_qual32(u32 B, int ar)            // qual bits of a chunk's first 3
     for (int k = 1; k < a && k < 32; ++k) acc &= (Z << k) | (u32)lowmask(k);      // symbols before the start count as matches
     return acc;
 }
+// The two halves of the record, each from the mismatch mask of its side (aw <= 30; bit j = the j-th symbol away from the
+// match, a symbol that may not be looked at counts as a mismatch): what null_ext_record states, for both of its readers.
+LZ_HD u32 ext_record_bwd(const Params& P, u32 Bb)
+{
+    const u32 wm = (u32)lowmask(P.aw);
+    const u32 qb = ext_qual32(Bb, P.ar) & wm;
+    if (popc32(Bb & wm) <= P.am) return qb;
+    if (P.aw > 15) return qb | EXT_REC_BRKB;
+    u32 x = Bb & wm;                                                    // the scan breaks at the (am+1)-th mismatch
+    for (int k = 0; k < P.am; ++k) x &= x - 1u;
+    const u32 q = qb & (u32)lowmask((int)__builtin_ctz(x) + 1);
+    const int b = q ? 32 - (int)__builtin_clz(q) : 0;                    // ends at the last qualifying symbol
+    return (u32)b | ((u32)(b - popc32(Bb & (u32)lowmask(b))) << 4) | EXT_REC_BRKB;
+}
+LZ_HD u32 ext_record_fwd(const Params& P, u32 Bf)                       // the bits to OR into the record
+{
+    const u32 wm = (u32)lowmask(P.aw);
+    if (popc32(Bf & wm) <= P.am) return 0u;
+    u32 x = Bf & wm;                                                    // the scan breaks at the (am+1)-th mismatch
+    for (int k = 0; k < P.am; ++k) x &= x - 1u;
+    const u32 qf = ext_qual32(Bf, P.ar) & (u32)lowmask((int)__builtin_ctz(x) + 1);
+    if (qf == 0) return EXT_REC_NULLF | (P.aw <= 15 ? (u32)EXT_REC_FWDK : 0u);
+    if (P.aw > 15) return 0u;
+    const int e = 32 - (int)__builtin_clz(qf);                           // ends at the last qualifying symbol
+    return EXT_REC_FWDK | ((u32)e << 24) | ((u32)popc32(Bf & (u32)lowmask(e)) << 20);
+}
 LZ_HD u32 null_ext_record(const Params& P, const TextView& R, const TextView& Q, int qp, int pos, int al, bool narrow = true)
 {
     if (P.aw > 30) return EXT_REC_NONE;
-    const u32 wm = (u32)lowmask(P.aw);
     u32 rec = ext_rec_none(P.aw);
-    if (qp >= 32 && pos >= 32) {                                       // all 32 symbols before the match exist
+    if (qp >= 32 && pos >= 32)                                         // all 32 symbols before the match exist
         // bit j = symbol qp-1-j / pos-1-j; only the first aw of them are looked at
-        const u32 Bb = (narrow && P.aw <= 15) ? (brev32(lane_mism16(R, Q, qp - 16, pos - 16)) >> 16) | 0xFFFF0000u
-                                                : brev32(lane_mism32(R, Q, qp - 32, pos - 32));
-        const u32 qb = ext_qual32(Bb, P.ar) & wm;
-        if (popc32(Bb & wm) <= P.am) rec = qb;
-        else if (P.aw > 15) rec = qb | EXT_REC_BRKB;
-        else {                                                          // the scan breaks at the (am+1)-th mismatch
-            u32 x = Bb & wm;
-            for (int k = 0; k < P.am; ++k) x &= x - 1u;
-            const u32 q = qb & (u32)lowmask((int)__builtin_ctz(x) + 1);
-            const int b = q ? 32 - (int)__builtin_clz(q) : 0;            // ends at the last qualifying symbol
-            rec = (u32)b | ((u32)(b - popc32(Bb & (u32)lowmask(b))) << 4) | EXT_REC_BRKB;
-        }
-    }
+        rec = ext_record_bwd(P, (narrow && P.aw <= 15) ? (brev32(lane_mism16(R, Q, qp - 16, pos - 16)) >> 16) | 0xFFFF0000u
+                                                       : brev32(lane_mism32(R, Q, qp - 32, pos - 32)));
     const int fq = qp + al, fr = pos + al;
-    if (imin(Q.len - fq, R.len - fr) >= P.aw) {
-        const u32 Bf = (narrow && P.aw <= 15) ? lane_mism16(R, Q, fq, fr) : lane_mism32(R, Q, fq, fr);
-        if (popc32(Bf & wm) > P.am) {                                   // the scan breaks at the (am+1)-th mismatch
-            u32 x = Bf & wm;
-            for (int k = 0; k < P.am; ++k) x &= x - 1u;
-            const u32 qf = ext_qual32(Bf, P.ar) & (u32)lowmask((int)__builtin_ctz(x) + 1);
-            if (qf == 0) rec |= EXT_REC_NULLF | (P.aw <= 15 ? (u32)EXT_REC_FWDK : 0u);
-            else if (P.aw <= 15) {
-                const int e = 32 - (int)__builtin_clz(qf);               // ends at the last qualifying symbol
-                rec |= EXT_REC_FWDK | ((u32)e << 24) | ((u32)popc32(Bf & (u32)lowmask(e)) << 20);
-            }
-        }
-    }
+    if (imin(Q.len - fq, R.len - fr) >= P.aw)
+        rec |= ext_record_fwd(P, (narrow && P.aw <= 15) ? lane_mism16(R, Q, fq, fr) : lane_mism32(R, Q, fq, fr));
     return rec;
+}
+
+// ---- a queued candidate resolved from ONE fetch of each text ----------------------------------------------------
+// A candidate at query position qp / reference position pos is compared over 32 symbols, and its record (aw <= 15)
+// looks at the 16 symbols in front of the match and at the 16 behind its al <= 32 symbols: all of it lies in the
+// dwords (p >> 4) - 1 .. (p >> 4) + 3 of either text, p = qp / pos.  The refill requests the ten of them together
+// (lzani_kernels_pairs.h) and takes the compare and both windows of the record from them.
+struct TextWords5 { u32 m, a, b, c, d; };
+LZ_HD u32 funnel32(u32 hi, u32 lo, u32 s)      // the low 32 bits of (hi:lo) >> s, s < 32 (v_alignbit_b32)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, s);
+#else
+    return (u32)((((u64)hi << 32) | lo) >> s);
+#endif
+}
+// p >= 0 and p < t.len.  Dword -1 of a text is not read: where p < 16, m holds dword 0 (no record looks in front of
+// p < 32).  Dword (p >> 4) + 3 exists behind every position of a text (lzani_layout.h: two spare blocks of 64 symbols).
+LZ_HD TextWords5 text_words5(const u64* t2, int p)
+{
+    const u32* t32 = reinterpret_cast<const u32*>(t2);               // symbol j at bits 2*(j&15) of dword j>>4
+    const u32 w = (u32)p >> 4;
+    return TextWords5{t32[(u32)imax(p - 16, 0) >> 4], t32[w], t32[w + 1], t32[w + 2], t32[w + 3]};
+}
+// What the resolve keeps of the ten words: the XOR of the two texts' 2-bit codes, aligned to the candidate -- back = the
+// 16 symbols in front of qp / pos (symbol p - 16 + j at bits 2j), d0 d1 d2 = the 48 symbols from qp / pos on.  Four
+// registers instead of ten, and every window the record looks at is a funnel out of them.
+struct ResolveDiff { u32 back, d0, d1, d2; };
+LZ_HD ResolveDiff resolve_diff(const TextWords5& r, int pos, const TextWords5& q, int qp)
+{
+    const u32 sr = ((u32)pos & 15u) * 2u, sq = ((u32)qp & 15u) * 2u;
+    return ResolveDiff{funnel32(r.a, r.m, sr) ^ funnel32(q.a, q.m, sq), funnel32(r.b, r.a, sr) ^ funnel32(q.b, q.a, sq),
+                       funnel32(r.c, r.b, sr) ^ funnel32(q.c, q.b, sq), funnel32(r.d, r.c, sr) ^ funnel32(q.d, q.c, sq)};
+}
+// number of equal symbols of R[pos ..] and Q[qp ..] among the first 32, by the 2-bit codes alone (what win2f's compare gives)
+LZ_HD int diff_same32(const ResolveDiff& D)
+{
+    const u32 mlo = (D.d0 | (D.d0 >> 1)) & 0x55555555u, mhi = (D.d1 | (D.d1 >> 1)) & 0x55555555u;
+    const int nlo = (int)__builtin_ctz(mlo | 0x80000000u) >> 1, nhi = 16 + ((int)__builtin_ctz(mhi | 0x80000000u) >> 1);
+    return mlo ? nlo : mhi ? nhi : 32;
+}
+// N-free text: [p - 32, p + n) lies inside one strand (pos_valid's fold: two unsigned compares), n >= 0
+LZ_HD bool span_in_strand(const TextView& t, int p, int n)
+{
+    const u32 a = (u32)(p - 32), b = a - (u32)t.rc0, m = a < b ? a : b;
+    return m < (u32)t.L && m + 32u + (u32)n <= (u32)t.L;
+}
+// null_ext_record(P, R, Q, qp, pos, al) of two N-free texts for aw <= 15 and 0 <= al <= 32, from the words.  Where the
+// 32 symbols in front of the match and the 16 behind it lie inside one strand of either text -- all but a few dozen
+// positions of a genome -- every symbol the record looks at is valid and no validity mask is built.
+LZ_HD u32 null_ext_record_xor(const Params& P, const TextView& R, const TextView& Q, u32 xb, u32 xf, int qp, int pos, int al)
+{
+    const int fq = qp + al, fr = pos + al;
+    u32 vb = 0xFFFFu, vf = 0xFFFFu;
+    bool back = true, fwd = true;
+    if (__builtin_expect(!(span_in_strand(R, pos, al + 16) & span_in_strand(Q, qp, al + 16)), 0)) {
+        back = qp >= 32 && pos >= 32;
+        fwd = imin(Q.len - fq, R.len - fr) >= P.aw;
+        vb = valid_bits16(R, pos - 16) & valid_bits16(Q, qp - 16);
+        vf = valid_bits16(R, fr) & valid_bits16(Q, fq);
+    }
+    const u32 Bb = (brev32(compress_even16(xb | (xb >> 1)) | ~vb) >> 16) | 0xFFFF0000u;
+    const u32 Bf = compress_even16(xf | (xf >> 1)) | ~vf;
+    u32 rec = back ? ext_record_bwd(P, Bb) : ext_rec_none(P.aw);
+    if (fwd) rec |= ext_record_fwd(P, Bf);
+    return rec;
+}
+LZ_HD u32 null_ext_record_diff(const Params& P, const TextView& R, const TextView& Q, const ResolveDiff& D, int qp, int pos, int al)
+{
+    // the 16 symbols behind the match: symbols al .. al + 15 of d0 d1 d2 (al = 32: d2 itself, whatever the upper word)
+    const u32 xf = funnel32((u32)al < 16u ? D.d1 : D.d2, (u32)al < 16u ? D.d0 : (u32)al < 32u ? D.d1 : D.d2, ((u32)al & 15u) * 2u);
+    return null_ext_record_xor(P, R, Q, D.back, xf, qp, pos, al);
 }
 // the backward extension is empty, by the record; reach = how far back the machine may look, uncapped
 // (min(avail, i, bpos); the scan itself looks at min(64, reach) symbols, and aw <= 30 < 64)

@@ -669,20 +669,15 @@ struct DevWave {
             // far beyond the text)
             pos = simple ? (int)(I.bk[simple ? slot : 0u] & (u32)lowmask(I.posbits)) : 0;
         }
-        // 32 symbols of both texts from pos / qp on, as two 32-bit words each (funnel of three dwords by v_alignbit, no branch,
-        // no 64-bit shift)
-        const u32* const pr = reinterpret_cast<const u32*>(R.t2) + ((u32)pos >> 4);
-        const u32 sr = ((u32)pos & 15u) * 2u;
-        const u32 r0 = pr[0], r1 = pr[1], r2 = pr[2];
-        // (the query's upper words are read here, a second time for q1 -- an L1 hit: held across the bucket's round trip
-        // they cost a register the kernel does not have, i.e. scratch; the empty asm keeps the two reads apart)
-        const u32* pq2 = pq;
-        asm volatile("" : "+v"(pq2));
-        const u32 qhi = __builtin_amdgcn_alignbit(pq2[2], pq2[1], sq);
-        const u32 dlo = __builtin_amdgcn_alignbit(r1, r0, sr) ^ qlo;
-        const u32 dhi = __builtin_amdgcn_alignbit(r2, r1, sr) ^ qhi;
-        const u32 mlo = (dlo | (dlo >> 1)) & 0x55555555u, mhi = (dhi | (dhi >> 1)) & 0x55555555u;
-        int same = mlo ? ((int)__builtin_ctz(mlo) >> 1) : mhi ? 16 + ((int)__builtin_ctz(mhi) >> 1) : (int)AQ_LANE_CAP;
+        // ONE fetch of each text behind the bucket: the five dwords around pos and around qp, requested together and waited
+        // for once -- the 32-symbol compare and both windows of the record come out of them (lzani_core.h: resolve_diff).
+        // (The query's words are read a second time for q0, q1 -- L1 hits: held across the bucket's round trip they cost
+        // registers the kernel does not have; the empty asm keeps the two reads apart.)
+        int qp2 = qp;
+        asm volatile("" : "+v"(qp2));
+        ResolveDiff df = resolve_diff(text_words5(R.t2, pos), pos, text_words5(Q.t2, qp2), qp);
+        asm volatile("" : "+v"(df.back), "+v"(df.d0), "+v"(df.d1), "+v"(df.d2));     // (made here: four live registers, not ten)
+        int same = diff_same32(df);
         int bound;
         if (R.nfree && Q.nfree) bound = imin(run_end(R, pos) - pos, run_end(Q, qp) - qp);
         else {
@@ -702,7 +697,12 @@ struct DevWave {
         a_len = plain ? al0 : -1 - al0;
         // what a distant event at this candidate needs to see that neither extension moves, worked out now, by the
         // lane, for the whole batch at once
-        a_ext = (simple & !lng) ? null_ext_record(P, R, Q, qp, pos, al0) : ext_rec_none(P.aw);
+        // (two statements on purpose: from the words the record is a select under the lanes' exec mask, no load in it; the
+        // windowed form of pairs with N, or of aw > 15, is a branch with loads of its own.  One statement choosing between
+        // them compiles to the same code in the kernels with folded parameters and to more scratch in the generic ones.)
+        a_ext = ext_rec_none(P.aw);
+        if (R.nfree && Q.nfree && P.aw <= 15) a_ext = (simple & !lng) ? null_ext_record_diff(P, R, Q, df, qp, pos, al0) : a_ext;
+        else if (simple & !lng) a_ext = null_ext_record(P, R, Q, qp, pos, al0);
         // A candidate the lane has resolved to a match shorter than mal is no anchor and never an event -- the tag of
         // another k-mer in the bucket, about as many per pair as there are true anchors: it leaves the queue here, all
         // of a batch in one stable compaction (lane permute, no LDS memory), instead of costing the sequential scan a
