@@ -6,8 +6,10 @@
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
-// lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  Three layers of the host side are files of their
+// lzani_core.h; sizes and the parameter envelope are lzani_layout.h; the pure decisions of a run (batches, queues, the
+// split rule, the bytes of a slab slot) are lzani_run_plan.h, free of HIP.  Four layers of the host side are files of their
 // own, included at fixed places below:
+//   lzani_dense.h       the dense-row stage of a run: candidate bitmaps from the presence matrix, the split of few, long pairs
 //   lzani_ooc.h         genome sets larger than the device: block plan, block uploads, the tiled run
 //   lzani_prefilter.h   the k-mer prefilter's host stage: slice and pass plans, the pass / tile driver, its entry points
 //   lzani_multi.h       the multi-GPU layer
@@ -55,6 +57,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_kernels_prefilter.h"
 #include "lzani_rtc.h"
 #include "lzani_devmem.h"
+#include "lzani_run_plan.h"
 
 // ============================================================================================
 // Host side of the C-ABI
@@ -238,14 +241,20 @@ struct IndexSlabs {
     DevMem<u64> d_ibase;
 };
 
-// Candidate scratch of dense rows (lzani_kernels_cand.h): grown by plan_bitmaps / choose_split_lpt, dropped with the
-// genome set or when one of them cannot be had.
+// Candidate scratch of dense rows (lzani_dense.h): grown by plan_bitmaps / choose_split_lpt / run_split, dropped with the
+// genome set or when the matrix, the pair table or the bitmaps cannot be had.
 struct CandScratch {
     DevMem<u32> d_pm;             // the presence matrix of one group: 2^pm_bits rows of PM_GROUP bits
     DevMem<u32> d_pm_cbits;       // candidate bitmaps of a batch's pairs
     DevMem<u32> d_pm_pidx;        // rows with query lists: pair of (query, slot of the group), query flags + list + count behind it
     DevMem<u32> d_lpt_cnt;        // batches of few, long pairs: candidates per pair ...
     DevMem<unsigned long long> d_lpt_keys;        // ... then the ticket keys unsorted / sorted (two per pair)
+    // few, long pairs by several waves each (run_split): per segment its checkpoint and its result, the work lists of this
+    // round and the next; the counters; per pair: finished, cut into segments
+    DevMem<SplitStart> d_sp_cuts;
+    DevMem<SplitOut> d_sp_outs;
+    DevMem<u32> d_sp_work, d_sp_next, d_sp_cnt;
+    DevMem<unsigned char> d_sp_done, d_sp_heavy;
 };
 
 // The k-mer prefilter (lzani_prefilter, lzani_kernels_prefilter.h): lzani_set_genomes -> the next one.  The results stay
@@ -309,8 +318,7 @@ struct lzani_ctx {
     double join_ms_pending = 0;   // ... and / or the join lists: their time, added to that run's kmers_ms
     DevMem<unsigned long long> d_cursor;
     DevMem<u32> d_blkctr;         // k_pairs_blk: one pair counter per block
-    bool build_attr_set = false, pm_attr_set = false;
-    u32 pmfi_attr_set = 0;        // k_pm_from_index<RW>: bit RW = its LDS limit is raised
+    std::vector<std::pair<const void*, size_t>> lds_limits;     // the dynamic-LDS limit this context gave a kernel (raise_lds)
     // pair kernels compiled at run time for this context's parameters (lzani_rtc.h); none for the two ahead-of-time tuples
     lzani_rtc::State rtc;
     std::string arch;             // the device's gfx target, as hipRTC wants it
@@ -361,6 +369,49 @@ bool env_is(const char* name, char ch) { const char* v = getenv(name); return v 
 std::optional<bool> env_flag(const char* name) { const char* v = getenv(name); return v ? std::optional<bool>(*v == '1') : std::nullopt; }
 std::optional<int> env_int(const char* name) { const char* v = getenv(name); return v ? std::optional<int>(atoi(v)) : std::nullopt; }
 std::optional<u64> env_u64(const char* name) { const char* v = getenv(name); return v ? std::optional<u64>(strtoull(v, nullptr, 10)) : std::nullopt; }
+
+// The one place that raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize): lds_limit is what
+// this context last gave the kernel (0: the default), raise_lds calls the runtime only where that is below `bytes`.
+size_t& lds_limit(lzani_ctx* c, const void* fn)
+{
+    for (auto& e : c->lds_limits) if (e.first == fn) return e.second;
+    c->lds_limits.emplace_back(fn, 0);
+    return c->lds_limits.back().second;
+}
+template <class K>
+int raise_lds(lzani_ctx* c, K* kernel, size_t bytes)
+{
+    const void* fn = reinterpret_cast<const void*>(kernel);
+    size_t& have = lds_limit(c, fn);
+    if (bytes <= have) return LZANI_OK;
+    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    have = bytes;
+    return LZANI_OK;
+}
+
+// The engine's radix sort (lzani_sort.hip) of n_seg segments of seg_len keys by the bits [begin_bit, end_bit), on the
+// context's stream.  sort_scratch_bytes: its size query.  sort_keys: the query, `scratch` grown to what it asks for -- sync:
+// behind the stream's queued work, which may still be using it -- and the sort.  `what` names the caller's sort in the message.
+int sort_scratch_bytes(lzani_ctx* c, size_t seg_len, size_t n_seg, int begin_bit, int end_bit, const char* what, size_t& need)
+{
+    if (lzani_sort_segments(nullptr, nullptr, seg_len, n_seg, begin_bit, end_bit, nullptr, &need, c->stream) != 0)
+        return fail(c, LZANI_ERR_DEVICE, std::string(what) + " (size query) failed");
+    return LZANI_OK;
+}
+int sort_keys(lzani_ctx* c, DevMem<unsigned char>& scratch, const unsigned long long* in, unsigned long long* out, size_t seg_len, size_t n_seg,
+              int begin_bit, int end_bit, const char* what, bool sync)
+{
+    size_t need = 0;
+    if (int rc = sort_scratch_bytes(c, seg_len, n_seg, begin_bit, end_bit, what, need)) return rc;
+    if (need > scratch.capacity()) {
+        if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, scratch.alloc(need));
+    }
+    size_t have = scratch.capacity();
+    const int e = lzani_sort_segments(in, out, seg_len, n_seg, begin_bit, end_bit, scratch, &have, c->stream);
+    if (e != 0) return fail(c, LZANI_ERR_DEVICE, std::string(what) + " failed: " + hipGetErrorString((hipError_t)e));
+    return LZANI_OK;
+}
 
 struct IndexForm { u64 bk_stride, tw_stride; bool join_mode; };
 
@@ -418,9 +469,15 @@ void choose_index_form(lzani_ctx* c)
         c->gs.max_slots = (u32)std::min<u64>(c->gs.max_slots, (1ull << std::min(16, 64 - c->gs.geo.kb - c->gs.geo.posbits)) - 1);
 }
 
+// The bytes of one index slab slot of the set (lzani_run_plan.h): the tables, and the keys of the sort-based build.
+SlabBytes slot_bytes(const GenomeSet& gs)
+{
+    return slab_bytes_per_slot(gs.dir_stride, gs.ent_stride, gs.bk_stride, gs.tw_stride, gs.fl_stride, gs.sort_build, (u64)gs.Tmax);
+}
+
 int ensure_slabs(lzani_ctx* c, u32 want_rows)
 {
-    size_t per_slot = (size_t)4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride) + (c->gs.sort_build ? (size_t)16 * c->gs.Tmax + 16 : 0);
+    const size_t per_slot = (size_t)slot_bytes(c->gs).total();
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
     size_t have = c->sl.slots * per_slot;
@@ -446,15 +503,6 @@ int ensure_slabs(lzani_ctx* c, u32 want_rows)
     }
     s.slots = slots;
     c->sl = std::move(s);
-    return LZANI_OK;
-}
-
-// The radix sort's scratch grown to `need` bytes; sync: after the stream's queued work, which may still be using it.
-int grow_jtmp(lzani_ctx* c, size_t need, bool sync)
-{
-    if (need <= c->gs.d_jtmp.capacity()) return LZANI_OK;
-    if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, c->gs.d_jtmp.alloc(need));
     return LZANI_OK;
 }
 
@@ -521,15 +569,10 @@ int build_join_lists(lzani_ctx* c)
         u64 at = c->gs.jl.h_koff[g0];
         for (u32 g = g0; g < g1; ++g) { soff[g] = at; at += valid[g]; }
         if (g1 == n) soff[n] = at;
-        if (keys) {
-            size_t need = 0;
-            int e = lzani_sort_keys(keys_in + c->gs.jl.h_koff[g0], c->gs.jl.keys + c->gs.jl.h_koff[g0], keys, c->gs.geo.posbits, shift_g + gbits, nullptr, &need, c->stream);
-            if (e != 0) return fail(c, LZANI_ERR_DEVICE, "join lists: radix sort (size query) failed");
-            { int rc = grow_jtmp(c, need, false); if (rc) return rc; }
-            need = c->gs.d_jtmp.capacity();
-            e = lzani_sort_keys(keys_in + c->gs.jl.h_koff[g0], c->gs.jl.keys + c->gs.jl.h_koff[g0], keys, c->gs.geo.posbits, shift_g + gbits, c->gs.d_jtmp, &need, c->stream);
-            if (e != 0) return fail(c, LZANI_ERR_DEVICE, "join lists: radix sort failed");
-        }
+        if (keys)
+            if (int rc = sort_keys(c, c->gs.d_jtmp, keys_in + c->gs.jl.h_koff[g0], c->gs.jl.keys + c->gs.jl.h_koff[g0], keys, 1, c->gs.geo.posbits, shift_g + gbits,
+                                   "join lists: radix sort", false))
+                return rc;
         g0 = g1;
     }
     // (a genome's list ends after its valid keys -- d_jcnt -- not where the next list begins: between two groups sit the
@@ -634,15 +677,7 @@ int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, 
         const u32 group = 1;
         HIPCHK(c, hipMemsetAsync(c->sl.d_icnt, 0, (size_t)rows * 4, c->stream));
         hipLaunchKernelGGL(k_idx_keys, dim3((u32)((Tm + 4095) / 4096), rows), dim3(256), 0, c->stream, ia, c->sl.d_ikeys_in, c->sl.d_icnt, c->gs.Tmax, shift_slot);
-        {
-            size_t need = 0;
-            int e = lzani_sort_segments(c->sl.d_ikeys_in, c->sl.d_ikeys, Tm, rows, c->gs.geo.posbits, shift_slot + 1, nullptr, &need, c->stream);
-            if (e != 0) return fail(c, LZANI_ERR_DEVICE, "index build: radix sort (size query) failed");
-            { int rc = grow_jtmp(c, need, true); if (rc) return rc; }
-            need = c->gs.d_jtmp.capacity();
-            e = lzani_sort_segments(c->sl.d_ikeys_in, c->sl.d_ikeys, Tm, rows, c->gs.geo.posbits, shift_slot + 1, c->gs.d_jtmp, &need, c->stream);
-            if (e != 0) return fail(c, LZANI_ERR_DEVICE, "index build: radix sort failed");
-        }
+        if (int rc = sort_keys(c, c->gs.d_jtmp, c->sl.d_ikeys_in, c->sl.d_ikeys, Tm, rows, c->gs.geo.posbits, shift_slot + 1, "index build: radix sort", true)) return rc;
         hipLaunchKernelGGL(k_idx_base, dim3((rows + 255) / 256), dim3(256), 0, c->stream, c->sl.d_icnt, c->sl.d_ibase, rows, group, Tm);
         hipLaunchKernelGGL(k_idx_from_sorted, dim3((u32)std::min<u64>((Tm + 255) / 256, 8192), rows), dim3(256), 0, c->stream,
                            ia, c->sl.d_ikeys, c->sl.d_icnt, c->sl.d_ibase, c->sl.d_bk, with_tw ? c->sl.d_tw : nullptr, c->gs.bk_stride, c->gs.tw_stride);
@@ -660,10 +695,7 @@ int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, 
         // one block per reference, everything through LDS; a slot that does not fit (status != 0) falls through
         // to the global-atomics kernels below, which skip every other slot
         const size_t lds = (size_t)(IDX_RANGE / 2 + IDX_STAGE) * 4;
-        if (!c->build_attr_set) {
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_idx_build), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            c->build_attr_set = true;
-        }
+        { int rc = raise_lds(c, k_idx_build, lds); if (rc) return rc; }
         HIPCHK(c, hipMemsetAsync(c->sl.d_status, 0, (size_t)rows * 4, c->stream));
         hipLaunchKernelGGL(k_idx_build, dim3(rows), dim3(1024), lds, c->stream, ia, c->sl.d_bk, c->sl.d_tw, c->gs.bk_stride, c->gs.tw_stride, c->sl.d_status);
         ia.todo = c->sl.d_status;
@@ -764,156 +796,7 @@ struct RunPlan {
     std::vector<u32> bstart;      // batch b: rows [bstart[b], bstart[b + 1])
 };
 
-// Batches of consecutive rows: at most rows_cap rows and cap_pairs pairs each.  Returns the most pairs of a batch.
-u64 cut_batches(u32 n_rows, const u64* row_off, u32 rows_cap, u64 cap_pairs, std::vector<u32>& bstart)
-{
-    bstart.assign(1, 0);
-    u32 rows = 0;
-    u64 pairs = 0, most = 0;
-    for (u32 k = 0; k < n_rows; ++k) {
-        const u64 len = row_off[k + 1] - row_off[k];
-        if (rows && (rows == rows_cap || pairs + len > cap_pairs)) { bstart.push_back(k); most = std::max(most, pairs); rows = 0; pairs = 0; }
-        ++rows; pairs += len;
-    }
-    bstart.push_back(n_rows);
-    return std::max(most, pairs);
-}
-
-// Dense rows: the candidates of every pair of a batch come from the presence matrix of its references
-// (lzani_kernels_cand.h) instead of a probe per query position (viral sizes) or a join of sorted k-mer lists per pair
-// (long genomes), where the rows qualify; a batch is then also bounded by what the candidate bitmaps of its pairs take,
-// and the index slabs are sized for such a batch.  p.pm stays clear where the rows do not qualify or do not fit (a genome
-// set this large: the probe / join form, batch by batch), and where a buffer (matrix, pair table, bitmaps) cannot be had
-// after all -- the sizing is an estimate, and an allocation may fail on a fragmented heap: the bitmap buffers are then
-// released (the probe / join form needs none of them).
-int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
-{
-    // (from 32 rows on where the probe form with tag words is the alternative; from 8 rows where it is the rounds of the
-    // first kernel: genomes whose tags do not fit a tag byte -- 260 kbp to 2 Mbp at mal 15, viral sizes at mal 13+.
-    // Below, the matrix -- 16 GB to clear at 30 key bits -- costs more than it saves.)
-    // Long genomes (the join is the alternative: 210 ms for the 56 pairs of 8 x 5 Mbp against 149 by bitmaps, 92 with the
-    // pairs cut into segments): from two rows on.
-    const u32 min_rows = k.pm_min_rows ? (u32)std::max(1, *k.pm_min_rows) : c->gs.join_mode ? 2u : c->gs.tw_stride ? 32u : 8u;
-    // Query lists qualify when they are dense where they are: a query that occurs in a group of rows should meet a
-    // good part of it (one matrix row read serves all its pairs of the group) -- the row x column blocks of a tiled
-    // all2all do, the few relatives a kmer-db filter leaves per row do not.  No query twice in a row (one bitmap each).
-    // (Measured in round 4 on the related workload, families of 50 in length order -- 16 pairs per query and group:
-    // the pair kernel gains 18 % from the bitmaps, the candidate stage costs more than that; against the ROUNDS of the
-    // first kernel -- no tag words: long k-mers on mid-size genomes -- the bitmaps win from two pairs per query on.)
-    const u64 min_share = k.pm_min_share.value_or(c->gs.tw_stride ? 48 : 2);
-    const bool lists_ok = !lists || (!f.lists_dup && f.n_pairs >= min_share * f.lists_involved);
-    if (!(!regions && lists_ok && c->gs.tab.kmL && c->gs.bk_stride && c->P.mqd + c->P.mrd <= 128 && c->gs.geo.kb <= 30 &&
-          c->gs.n >= 2 && n_rows >= min_rows && k.pm))
-        return LZANI_OK;
-    u64 max_row = 0;
-    for (u32 r = 0; r < n_rows; ++r) max_row = std::max<u64>(max_row, row_off[r + 1] - row_off[r]);
-    p.pm_tiles = (u32)(((u64)p.Lmax + c->P.mrd + 320 + PM_TILE - 1) / PM_TILE);
-    p.cb_words = (u64)p.pm_tiles * PM_TILE_WORDS;
-    p.pm_group = p.pm_bits <= 27 ? (u32)PM_GROUP : 128u;                    // 64-byte rows up to 2^27 of them (8 GB), 16-byte rows beyond (16 GB at 2^30)
-    const size_t m_bytes = ((size_t)1 << p.pm_bits) * (p.pm_group / 8);
-    const size_t x_bytes = lists ? ((size_t)c->gs.n * p.pm_group + 2 * (size_t)c->gs.n + 64) * 4 : 0;   // pair table, query flags, list, count
-    const size_t per_pair = (size_t)p.cb_words * 4;
-    const double avg_row = (double)f.n_pairs / n_rows;
-    const size_t per_slot = (size_t)4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride) + (c->gs.sort_build ? (size_t)16 * c->gs.Tmax + 16 : 0);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    // what this run may lay out anew: the free memory and what the context holds from earlier runs -- ITS slabs
-    // included, which is why slabs larger than this run wants are released below (ensure_slabs never shrinks them:
-    // an earlier run with sparse rows may have grown them to 60 % of the memory)
-    const size_t pool = free_b + (size_t)c->sl.slots * per_slot + c->cs.d_pm_cbits.bytes() + c->cs.d_pm.bytes() + c->cs.d_pm_pidx.bytes();
-    const size_t cap = k.pm_max_bytes.value_or(std::min((size_t)64 << 30, total_b / 4));
-    const double room = pool * 0.85 - (double)m_bytes - (double)x_bytes;
-    u64 fit = room > 0 ? (u64)(room / ((double)per_slot + avg_row * (double)per_pair)) : 0;     // rows: a slab + its pairs' bitmaps each
-    fit = std::min<u64>(fit, std::min<u32>(n_rows, c->gs.max_slots));
-    u64 cap_pairs = std::min<u64>((u64)(cap / per_pair), 0xFFFFFFF0ull);                           // pair indexes of a batch are 32 bits
-    cap_pairs = std::min<u64>(cap_pairs, (u64)((double)fit * avg_row) + max_row);
-    if (fit < std::min<u32>(8, n_rows) || cap_pairs < max_row) return LZANI_OK;
-    if (c->sl.slots > fit) c->sl = IndexSlabs{};                                     // (counted as available above)
-    if (!got(c->cs.d_pm.reserve(m_bytes / 4)) || !got(c->cs.d_pm_pidx.reserve(x_bytes / 4))) {
-        TRACE("candidate bitmaps: no memory for the matrix / pair table, falling back");
-        c->cs = CandScratch{};
-        return LZANI_OK;
-    }
-    const int rc = ensure_slabs(c, (u32)fit);
-    if (rc == LZANI_ERR_NOMEM) { c->cs = CandScratch{}; return LZANI_OK; }
-    if (rc) return rc;
-    u32 rows_cap = c->sl.slots;
-    if (!lists) {                                            // dense rows: whole groups of references, if there are several batches
-        u64 r = std::min<u64>(rows_cap, cap_pairs / (u64)(c->gs.n - 1));
-        if (r < n_rows && r > p.pm_group) r -= r % p.pm_group;
-        rows_cap = (u32)std::max<u64>(r, 1);
-    }
-    size_t need = (size_t)cut_batches(n_rows, row_off, rows_cap, cap_pairs, p.bstart) * p.cb_words * 4;
-    if (k.pm_fail_cbits) need = (size_t)1 << 60;                          // tests: the fallback
-    if (!got(c->cs.d_pm_cbits.reserve(need / 4))) {
-        TRACE("candidate bitmaps: no memory for %zu bytes of bitmaps, falling back", need);
-        c->cs = CandScratch{};
-        return LZANI_OK;
-    }
-    p.pm = true;
-    return LZANI_OK;
-}
-
-// The plan of a run: candidate bitmaps where the rows qualify and their buffers can be had, else the probe / join form;
-// batches of as many consecutive rows as there are index slabs (and, with bitmaps, as their pairs' bitmaps may take).
-int plan_run(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
-{
-    for (u32 g = 0; g < c->gs.n; ++g) p.Lmax = std::max(p.Lmax, c->gs.L[g]);
-    // rows of the presence matrix: one per k-mer (exact: the mixer is a bijection on the key bits) where the genomes fill a fair
-    // part of the key space, else the hash's top bits -- 2^9 rows per text position keep the false candidates below 0.2 % of the
-    // query positions, and a group's matrix is cleared and built in proportion to the genomes, not to 4^mal
-    p.pm_bits = std::min(std::min(c->gs.geo.kb, 30), ceil_log2((u64)std::max(c->gs.Tmax, 1)) + 9);
-    int rc = plan_bitmaps(c, k, f, n_rows, row_off, lists, regions, p);
-    if (rc || p.pm) return rc;
-    p.use_join = c->gs.join_mode;
-    if (p.use_join) { rc = ensure_join(c); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
-    rc = ensure_slabs(c, n_rows);
-    if (rc) return rc;
-    cut_batches(n_rows, row_off, c->sl.slots, ~0ull, p.bstart);
-    return LZANI_OK;
-}
-
-// The per-XCD work queues of every batch (host only): a batch's rows, longest first onto the least loaded queue (equal
-// rows: round robin).  qorder: the batch's rows queue after queue, qcum: their running pair count (one entry more per
-// batch), qb: where each queue begins in qorder.
-struct QueuePlan { std::vector<u32> qorder; std::vector<u64> qcum; std::vector<u32> qb; };
-
-QueuePlan plan_queues(u32 n_rows, const u64* row_off, const std::vector<u32>& bstart)
-{
-    const u32 n_batches = (u32)bstart.size() - 1;
-    QueuePlan qp{std::vector<u32>(n_rows), std::vector<u64>((size_t)n_rows + n_batches), std::vector<u32>((size_t)n_batches * (NQUEUES + 1))};
-    std::vector<u32> by_size, queue[NQUEUES];
-    for (u32 b = 0; b < n_batches; ++b) {
-        const u32 k0 = bstart[b], rows = bstart[b + 1] - k0;
-        auto rlen = [&](u32 k) { return row_off[k0 + k + 1] - row_off[k0 + k]; };
-        by_size.resize(rows);
-        for (u32 k = 0; k < rows; ++k) by_size[k] = k;
-        std::stable_sort(by_size.begin(), by_size.end(), [&](u32 x, u32 y) { return rlen(x) > rlen(y); });
-        u64 load[NQUEUES] = {0};
-        for (auto& q : queue) q.clear();
-        for (u32 k : by_size) {
-            u32 best = 0;
-            for (u32 x = 1; x < NQUEUES; ++x) if (load[x] < load[best]) best = x;
-            queue[best].push_back(k);
-            load[best] += rlen(k);
-        }
-        u32 at = 0;
-        u64 cum = 0;
-        u32* qo = qp.qorder.data() + k0;
-        u64* qc = qp.qcum.data() + k0 + b;
-        qc[0] = 0;
-        for (u32 x = 0; x < NQUEUES; ++x) {
-            qp.qb[(size_t)b * (NQUEUES + 1) + x] = at;
-            for (u32 k : queue[x]) { qo[at] = k; cum += rlen(k); qc[++at] = cum; }
-        }
-        qp.qb[(size_t)b * (NQUEUES + 1) + NQUEUES] = at;
-    }
-    return qp;
-}
-
-// Test hook (lzani_debug_run_candidates): host copies of every batch's candidate bitmaps -- the first `words` words of each
-// pair -- and, where the batch counted them, its pairs' candidate counts; indexed by the run's pair offset.
-struct CandSink { u32* cbits; u64 words; u32* pcount; u32 counted_batches; };
+struct CandSink;                                  // lzani_dense.h
 
 // What the batches of one run share: its rows and queues on the device, the launch geometry, the kernels of its tuple.
 struct RunCtx {
@@ -934,219 +817,28 @@ struct RunCtx {
 // Batch b: rows [k0, k0 + rows), pairs [e0, e1), its queues' bounds (QueuePlan::qb); the split / LPT choice of its pair launch.
 struct Batch { u32 b, k0, rows; u64 e0, e1; const u32* qb; u32 split_S = 0; int split_seglen = 0; bool lpt = false; };
 
-// Few, long pairs (the batch leaves a wave slot only a few of them): the launch is over when its slowest pair is, so the
-// pairs with the most candidates -- the related ones -- go first (k_pm_cand counts, k_lpt_keys + a sort order)
-// ... and fewer pairs than half the wave slots: every pair by several waves, segment by segment (lzani_kernels_split.h).
-// (Candidate bitmaps only: no regions, mqd + mrd <= 128.)
-int choose_split_lpt(RunCtx& r, Batch& bt)
-{
-    lzani_ctx* c = r.c;
-    const u64 bp = bt.e1 - bt.e0, slots = (u64)r.max_blocks * 4, cb_words = r.p.cb_words;
-    const int Dmax = r.p.Lmax + c->P.mrd;
-    // (measured at the end of round 4, 5 Mbp: 56 pairs 6 ms a launch instead of 148, 240 pairs 8 instead of 147, 992 pairs 47
-    // instead of 148: from 8 wave slots per pair on)
-    // (... measured at 5 Mbp; for shorter queries -- from 256 kbp on -- from 16 wave slots per pair, as the suite has run it)
-    const bool split = r.k.split.value_or(cb_words >= 8192 && (bp * 16 <= slots || (cb_words >= 65536 && bp * 8 <= slots)));
-    if (split && bp * 2 <= 0xFFFFFFFFull / 64) {
-        u32 S = (u32)std::min<u64>(r.k.split_s, std::max<u64>(2, slots / bp));      // (8 x 5 Mbp: 67 / 58 / 42 ms a launch with 16 / 32 / 64 a pair)
-        int seglen = (Dmax + (int)S - 1) / (int)S;
-        if (r.k.split_seglen > 0) { seglen = r.k.split_seglen; S = (u32)std::min<int>(64, std::max(2, (Dmax + seglen - 1) / seglen)); }
-        seglen = std::max(seglen, 512);
-        if ((Dmax + seglen - 1) / seglen >= 2) { bt.split_S = std::min<u32>(S, (u32)((Dmax + seglen - 1) / seglen)); bt.split_seglen = seglen; }
-    }
-    // (queries from ~256 kbp on; the split wants the candidate counts: which pairs to cut, which first)
-    bt.lpt = (bp >= 2 && bp <= slots * 32 && r.k.lpt.value_or(cb_words >= 8192)) || bt.split_S >= 2;
-    if (bt.lpt && c->cs.d_lpt_cnt.capacity() < bp) {
-        c->cs.d_lpt_cnt.reset(); c->cs.d_lpt_keys.reset();    // (both released before either is made anew)
-        if (!got(c->cs.d_lpt_cnt.alloc(bp)) || !got(c->cs.d_lpt_keys.alloc(2 * bp))) {
-            c->cs.d_lpt_cnt.reset(); c->cs.d_lpt_keys.reset();
-            bt.lpt = false;                                   // (placement only: the run goes on without it)
-        }
-    }
-    if (bt.lpt) HIPCHK(c, hipMemsetAsync(c->cs.d_lpt_cnt, 0, (size_t)bp * 4, c->stream));
-    return LZANI_OK;
-}
+}  // namespace
 
-// The candidate bitmaps of the batch's pairs, group by group of pm_group references; then the ticket order of its queues.
-int candidate_stage(RunCtx& r, Batch& bt)
-{
-    lzani_ctx* c = r.c;
-    const RunPlan& p = r.p;
-    const int pm_bits = p.pm_bits;
-    for (u32 g0 = 0; g0 < bt.rows; g0 += p.pm_group) {
-        PmArgs pg;
-        pg.G = gtab(c);
-        pg.ref_ids = r.d_ref + bt.k0; pg.row_off = r.d_off + bt.k0;
-        pg.slot0 = g0; pg.rows = std::min<u32>(p.pm_group, bt.rows - g0);
-        pg.M = c->cs.d_pm; pg.rw = ((pg.rows + 127) / 128) * 4; pg.mmask = (u32)lowmask(pm_bits); pg.rshift = c->gs.geo.kb - pm_bits;
-        pg.mal = c->P.mal; pg.mrd = c->P.mrd;
-        pg.cbits = c->cs.d_pm_cbits; pg.cb_words = p.cb_words; pg.e0 = bt.e0; pg.n = c->gs.n; pg.q0 = 0;
-        pg.query_ids = r.d_q; pg.pidx = nullptr; pg.qflag = pg.qlist = pg.qcount = nullptr;
-        pg.pcount = bt.lpt ? c->cs.d_lpt_cnt : nullptr;
-        if (r.query_ids) {                                   // the lists of the group's rows -> pair table + the queries involved
-            const size_t tab = (size_t)c->gs.n * 32 * pg.rw;
-            pg.pidx = c->cs.d_pm_pidx; pg.qflag = c->cs.d_pm_pidx + (size_t)c->gs.n * p.pm_group; pg.qlist = pg.qflag + c->gs.n; pg.qcount = pg.qlist + c->gs.n;
-            HIPCHK(c, hipMemsetAsync(pg.pidx, 0xFF, tab * 4, c->stream));
-            HIPCHK(c, hipMemsetAsync(pg.qflag, 0, ((size_t)2 * c->gs.n + 1) * 4, c->stream));
-            hipLaunchKernelGGL(k_pm_pairs, dim3(pg.rows), dim3(256), 0, c->stream, pg);
-        }
-        // the matrix: from the group's indexes, chunk by chunk through LDS (long genomes: no global atomics, no clearing),
-        // or by one atomicOr per text position into the cleared matrix
-        const int tbits = c->gs.geo.kb - c->gs.geo.dirbits;
-        // (chunks of 64 KB: two blocks = 32 waves a CU; with 128 KB chunks, one block a CU, the matrix of 128 x 5 Mbp took 3 ms more)
-        const int rcl = std::min(pm_bits, pg.rw <= 4 ? 12 : pg.rw <= 8 ? 11 : 10);
-        const bool from_index = c->gs.geo.tagmask == (u32)lowmask(tbits) && pm_bits == c->gs.geo.kb && rcl >= tbits &&
-                                r.k.pm_from_index.value_or(pm_bits > 24);
-        if (from_index) {
-            c->run.pmfi_launches += 1;
-            const size_t fl = ((size_t)pg.rw << rcl) * 4;
-            const dim3 gi(1u << (pm_bits - rcl)), bi(1024);
-#define LZ_PM_FI(RW) do { \
-                if (!(c->pmfi_attr_set & (1u << RW))) { \
-                    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_from_index<RW>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
-                    c->pmfi_attr_set |= 1u << RW; \
-                } \
-                hipLaunchKernelGGL(k_pm_from_index<RW>, gi, bi, fl, c->stream, pg, c->sl.d_dirz, c->sl.d_ent, c->gs.dir_stride, c->gs.ent_stride, tbits, c->gs.geo.posbits, rcl); \
-            } while (0)
-            switch (pg.rw) {
-            case 4: LZ_PM_FI(4); break;
-            case 8: LZ_PM_FI(8); break;
-            case 12: LZ_PM_FI(12); break;
-            default: LZ_PM_FI(16); break;
-            }
-#undef LZ_PM_FI
-        } else {
-            HIPCHK(c, hipMemsetAsync(c->cs.d_pm, 0, ((size_t)1 << pm_bits) * pg.rw * 4, c->stream));
-            hipLaunchKernelGGL(k_pm_build, dim3((u32)std::min<u64>(((u64)c->gs.Tmax + 255) / 256, 64), pg.rows), dim3(256), 0, c->stream, pg, c->gs.Tmax);
-        }
-        const u32 rp = 32 * pg.rw;
-        const size_t lds = (size_t)(PM_TILE_WORDS * (rp + 1) + rp) * 4;
-        if (!c->pm_attr_set) {
-            const size_t lmax = (size_t)(PM_TILE_WORDS * (PM_GROUP + 1) + PM_GROUP) * 4;
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_pm_cand<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
-            c->pm_attr_set = true;
-        }
-        // (query lists: one row of blocks per query that occurs in the group -- counted here, the device list is
-        // k_pm_pairs' -- not per genome: 20,000 genomes x 44 tiles of blocks that find nothing to do were most of
-        // the candidate stage of a filtered run)
-        u32 nq = c->gs.n;
-        if (r.query_ids) {
-            if (r.grp_seen.size() != c->gs.n) r.grp_seen.assign(c->gs.n, 0xFFFFFFFFu);
-            const u32 stamp = ++r.grp_stamp;
-            nq = 0;
-            for (u64 e = r.row_off[bt.k0 + g0]; e < r.row_off[bt.k0 + g0 + pg.rows]; ++e)
-                if (r.grp_seen[r.query_ids[e]] != stamp) { r.grp_seen[r.query_ids[e]] = stamp; ++nq; }
-        }
-        for (u32 q0 = 0; q0 < nq; q0 += 32768) {           // gridDim.y is limited to 65535
-            pg.q0 = q0;
-            const dim3 gc(p.pm_tiles, std::min<u32>(32768, nq - q0)), bc(PM_CAND_THREADS);
-            c->run.pmc_launches += 1;
-            switch (pg.rw / 4) {
-            case 1: hipLaunchKernelGGL(k_pm_cand<1>, gc, bc, lds, c->stream, pg); break;
-            case 2: hipLaunchKernelGGL(k_pm_cand<2>, gc, bc, lds, c->stream, pg); break;
-            case 3: hipLaunchKernelGGL(k_pm_cand<3>, gc, bc, lds, c->stream, pg); break;
-            default: hipLaunchKernelGGL(k_pm_cand<4>, gc, bc, lds, c->stream, pg); break;
-            }
-        }
-        c->run.tm.cand_launches += 2;
-    }
-    if (!bt.lpt || c->cs.d_lpt_cnt == nullptr) bt.split_S = 0;   // (no candidate counts after all -- their buffer could not be had: no split)
-    if (bt.lpt && bt.split_S < 2) {                            // the ticket order of the batch's queues
-        const u64 bp = bt.e1 - bt.e0;
-        QueueBounds qbv;
-        for (int x = 0; x <= NQUEUES; ++x) qbv.v[x] = bt.qb[x];
-        hipLaunchKernelGGL(k_lpt_keys, dim3((u32)std::min<u64>((bp + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                           r.d_qorder + bt.k0, r.d_qcum + bt.k0 + bt.b, qbv, r.d_off + bt.k0, bt.e0, c->cs.d_lpt_cnt, c->cs.d_lpt_keys, bt.rows, bp);
-        size_t need = 0;
-        int e = lzani_sort_keys(c->cs.d_lpt_keys, c->cs.d_lpt_keys + bp, bp, 32, 56, nullptr, &need, c->stream);
-        if (e == 0) { int rc = grow_jtmp(c, need, true); if (rc) return rc; }
-        need = c->gs.d_jtmp.capacity();
-        if (e == 0) e = lzani_sort_keys(c->cs.d_lpt_keys, c->cs.d_lpt_keys + bp, bp, 32, 56, c->gs.d_jtmp, &need, c->stream);
-        if (e != 0) return fail(c, LZANI_ERR_DEVICE, "ticket order: radix sort failed");
-    }
-    HIPCHK(c, hipGetLastError());
-    return LZANI_OK;
-}
+#include "lzani_dense.h"
 
-// Few, long pairs: several waves a pair (lzani_kernels_split.h) -- the checkpoints, then rounds of segments until the stitch
-// has every pair.  launch(sa, mode, items): k_split of the mode (launch_pairs picks the instantiation).
-template <class Launch>
-int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
+namespace {
+
+// The plan of a run: candidate bitmaps where the rows qualify and their buffers can be had, else the probe / join form;
+// batches of as many consecutive rows as there are index slabs (and, with bitmaps, as their pairs' bitmaps may take).
+int plan_run(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
 {
-    lzani_ctx* c = r.c;
-    c->run.pm_launches += 1;
-    c->run.split_launches += 1;
-    const u32 npb = (u32)(bt.e1 - bt.e0), S = bt.split_S;
-    DevMem<SplitStart> d_cuts;
-    DevMem<SplitOut> d_souts;
-    DevMem<u32> d_work, d_next, d_cnt;
-    DevMem<unsigned char> d_done, d_heavy;
-    HIPCHK(c, d_cuts.alloc((size_t)npb * S));
-    HIPCHK(c, d_souts.alloc((size_t)npb * S));
-    HIPCHK(c, d_work.alloc((size_t)npb * S));
-    HIPCHK(c, d_next.alloc((size_t)npb * S));
-    HIPCHK(c, d_cnt.alloc(12));
-    HIPCHK(c, d_done.alloc(npb));
-    HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 48, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_done.get(), 0, npb, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_cuts.get(), 0xFF, (size_t)npb * S * sizeof(SplitStart), c->stream));      // (cut 0 of every pair: no checkpoint)
-    SplitArgs sa;
-    sa.pa = pa; sa.rows = bt.rows; sa.n_pairs = npb; sa.S = S; sa.seglen = bt.split_seglen;
-    sa.cuts = d_cuts.get(); sa.outs = d_souts.get(); sa.work = d_work.get(); sa.work_next = d_next.get(); sa.counters = d_cnt.get(); sa.done = d_done.get();
-    sa.reg = c->P.reg; sa.last_round = 0;
-    // which pairs to cut: the ones with many anchor candidates (related: a candidate at every other position; a chance
-    // pair has one in a hundred and is scanned whole, by its segment 0 with the null chain at work) -- heaviest first
-    u32 items = 0;
-    {
-        std::vector<u32> cnt(npb);
-        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->cs.d_lpt_cnt, (size_t)npb * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        // (every pair by default: at a wave or two per SIMD a chance pair of 5 Mbp takes nearly as long as a related one;
-        // LZANI_SPLIT_ALL=0 cuts the pairs with a candidate at one position in 32 and more only)
-        const u32 thr = !r.k.split_all ? (u32)r.p.cb_words : r.k.split_thr;
-        std::vector<u32> order(npb);
-        for (u32 k = 0; k < npb; ++k) order[k] = k;
-        std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return cnt[x] > cnt[y]; });
-        std::vector<unsigned char> heavy(npb, 0);
-        std::vector<u32> all;
-        all.reserve((size_t)npb * 2);
-        u32 n_heavy = 0;
-        for (u32 k : order) if (cnt[k] >= thr) { heavy[k] = 1; ++n_heavy; for (u32 sg = 0; sg < S; ++sg) all.push_back(k * S + sg); }
-        for (u32 k : order) if (cnt[k] < thr) all.push_back(k * S);
-        items = (u32)all.size();
-        HIPCHK(c, d_heavy.alloc(npb));
-        HIPCHK(c, hipMemcpyAsync(d_heavy.get(), heavy.data(), npb, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_work.get(), all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));            // (the vectors leave scope)
-        TRACE("split: %u pairs, %u of them cut into %u segments (candidates >= %u)", npb, n_heavy, S, thr);
-    }
-    sa.heavy = d_heavy.get();
-    launch(sa, 0, npb * (S - 1));                           // the checkpoints
-    u32* cur = d_work.get(); u32* nxt = d_next.get();
-    auto t_round = std::chrono::steady_clock::now();
-    const int give_up = 6 + (int)S / 4;                      // (a chain of void segments costs a round each: more segments, more rounds allowed)
-    for (int round = 0; round < give_up + 4 && items; ++round) {
-        HIPCHK(c, hipMemsetAsync(d_cnt.get(), 0, 8, c->stream));     // tickets, next round's items (the finished pairs' count stays)
-        sa.work = cur; sa.work_next = nxt;
-        launch(sa, 1, items);
-        sa.last_round = round >= give_up;
-        hipLaunchKernelGGL(k_split_stitch, dim3((npb + 255) / 256), dim3(256), 0, c->stream, sa);
-        u32 cnt[12] = {0};
-        HIPCHK(c, hipMemcpyAsync(cnt, d_cnt.get(), 48, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->run.split_items += items;
-        const auto t_now = std::chrono::steady_clock::now();
-        TRACE("split: round %d ran %u segments in %.1f ms, %u pairs finished, %u segments to run again (void so far, by cause: look-back cut short %u, kept/dropped %u, dropped/kept %u, floor %u, guess %u, chain %u)",
-              round, items, std::chrono::duration<double, std::milli>(t_now - t_round).count(), cnt[2], cnt[1], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]);
-        t_round = t_now;
-        items = cnt[1];
-        std::swap(cur, nxt);
-        if (items == 0 && cnt[2] != npb) return fail(c, LZANI_ERR_DEVICE, "split pairs: the stitch left pairs behind");
-    }
-    if (items) return fail(c, LZANI_ERR_DEVICE, "split pairs: no end of rounds");
+    for (u32 g = 0; g < c->gs.n; ++g) p.Lmax = std::max(p.Lmax, c->gs.L[g]);
+    // rows of the presence matrix: one per k-mer (exact: the mixer is a bijection on the key bits) where the genomes fill a fair
+    // part of the key space, else the hash's top bits -- 2^9 rows per text position keep the false candidates below 0.2 % of the
+    // query positions, and a group's matrix is cleared and built in proportion to the genomes, not to 4^mal
+    p.pm_bits = std::min(std::min(c->gs.geo.kb, 30), ceil_log2((u64)std::max(c->gs.Tmax, 1)) + 9);
+    int rc = plan_bitmaps(c, k, f, n_rows, row_off, lists, regions, p);
+    if (rc || p.pm) return rc;
+    p.use_join = c->gs.join_mode;
+    if (p.use_join) { rc = ensure_join(c); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
+    rc = ensure_slabs(c, n_rows);
+    if (rc) return rc;
+    cut_batches(n_rows, row_off, c->sl.slots, ~0ull, p.bstart);
     return LZANI_OK;
 }
 
@@ -1158,6 +850,7 @@ bool blk_fits(lzani_ctx* c, const void* kf)
         for (int fold = 0; fold <= 4 && c->gs.blk_fold < 0; ++fold) {
             const size_t l = (size_t)(BLK_WAVES * SEED_LDS_WORDS + std::max<u64>(c->gs.fl_stride >> fold, 1)) * 4;
             if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l) != hipSuccess) { (void)hipGetLastError(); continue; }
+            lds_limit(c, kf) = l;                      // (what the kernel has now: the launch's raise_lds finds the fold settled on)
             int nb = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * BLK_WAVES, l) == hipSuccess && nb >= 2) c->gs.blk_fold = fold;
         }
@@ -1234,7 +927,8 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     } else if (use_blk) {
         const u32 fw = (u32)std::max<u64>(c->gs.fl_stride >> c->gs.blk_fold, 1);
         const size_t lds = (size_t)(BLK_WAVES * SEED_LDS_WORDS + fw) * 4;
-        HIPCHK(c, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        rc = raise_lds(c, kf, lds);              // (a no-op after blk_fits, which recorded the fold it settled on)
+        if (rc) return rc;
         pa.fmask = c->gs.fmask >> c->gs.blk_fold;
         c->run.blk_launches += 1;
         const dim3 gb((u32)std::min<u64>((waves + BLK_CHUNK_MIN - 1) / BLK_CHUNK_MIN, (u64)c->n_cus * 2)), bb(64 * BLK_WAVES);
@@ -1248,23 +942,6 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev[3], c->stream));
-    return LZANI_OK;
-}
-
-// Test hook: the batch's candidate bitmaps (and counts) into the run's CandSink, after its candidate stage.
-int sink_candidates(RunCtx& r, const Batch& bt)
-{
-    lzani_ctx* c = r.c;
-    CandSink& s = *r.sink;
-    const u64 bp = bt.e1 - bt.e0, w = std::min<u64>(s.words, r.p.cb_words);
-    if (s.cbits && w)
-        HIPCHK(c, hipMemcpy2DAsync(s.cbits + bt.e0 * s.words, s.words * 4, c->cs.d_pm_cbits, r.p.cb_words * 4, w * 4, bp,
-                                   hipMemcpyDeviceToHost, c->stream));
-    if (s.pcount && bt.lpt && c->cs.d_lpt_cnt) {
-        HIPCHK(c, hipMemcpyAsync(s.pcount + bt.e0, c->cs.d_lpt_cnt, bp * 4, hipMemcpyDeviceToHost, c->stream));
-        s.counted_batches += 1;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     return LZANI_OK;
 }
 
@@ -1435,7 +1112,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     // uploaded before the first launch, so the batches follow each other on the stream without a host round trip in between.
     const u32 n_batches = (u32)p.bstart.size() - 1;
     c->run.batches = n_batches;
-    const auto [qorder, qcum, qb] = plan_queues(n_rows, row_off, p.bstart);
+    const auto [qorder, qcum, qb] = plan_queues(n_rows, row_off, p.bstart, NQUEUES);
     DevMem<u32> d_ref, d_q, d_qorder;
     DevMem<u64> d_off, d_qcum;
     HIPCHK(c, d_qorder.alloc(n_rows));
@@ -1584,7 +1261,7 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
             HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
             if (const char* fb = getenv("LZANI_FREE_BYTES")) free_b = std::min<size_t>(free_b, (size_t)strtoull(fb, nullptr, 10));   // tests: the automatic trigger
             const u64 tables = total_nm * (16 + 8) + (kmers ? total_nm * 64 * 8 : 0);
-            const u64 per_slot = 4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride) + (c->gs.sort_build ? (u64)16 * c->gs.Tmax + 16 : 0);
+            const u64 per_slot = slot_bytes(c->gs).total();
             if (tables + total_codes > free_b || tables + per_slot > free_b) limit = free_b / 2;     // (half for the genomes, half for slabs and bitmaps)
         }
         std::vector<u64> bytes;
@@ -1755,7 +1432,7 @@ int lzani_get_layout(const lzani_ctx* c, lzani_layout_info* o)
     o->bucket_table = c->gs.bk_stride != 0; o->tag_words = c->gs.tw_stride != 0;
     o->n_free = c->gs.all_nfree;
     o->slots = c->sl.slots; o->batches_last_run = c->run.batches;
-    o->bytes_per_slot = 4 * (c->gs.dir_stride + c->gs.ent_stride + c->gs.bk_stride + c->gs.tw_stride + c->gs.fl_stride);
+    o->bytes_per_slot = slot_bytes(c->gs).tables;           // (without the keys of the sort-based build)
     o->bytes_genomes = c->gs.total_nm * (16 + 8) + (c->gs.tab.kmL ? c->gs.total_nm * 64 * 8 : 0);
     o->join_lists = c->gs.join_mode; o->block_launches = c->run.blk_launches; o->bitmap_launches = c->run.pm_launches; o->rtc_launches = c->run.rtc_launches;
     o->lpt_launches = c->run.lpt_launches; o->matrix_from_index = c->run.pmfi_launches;
@@ -1870,17 +1547,13 @@ int lzani_debug_sort_segments(lzani_ctx* c, const uint64_t* keys, uint64_t* out,
     HIPCHK(c, hipSetDevice(c->dev));
     const size_t n = (size_t)seg_len * n_seg;
     if (n == 0) return LZANI_OK;
+    if (begin_bit < 0 || end_bit > 64 || end_bit < begin_bit) return fail(c, LZANI_ERR_ARG, "lzani_debug_sort_segments: bad arguments");
     DevMem<unsigned long long> d_in, d_out;
     DevMem<unsigned char> d_tmp;
     HIPCHK(c, d_in.alloc(n));
     HIPCHK(c, d_out.alloc(n));
     HIPCHK(c, hipMemcpy(d_in.get(), keys, n * 8, hipMemcpyHostToDevice));
-    size_t need = 0;
-    if (lzani_sort_segments(d_in.get(), d_out.get(), seg_len, n_seg, begin_bit, end_bit, nullptr, &need, c->stream) != 0)
-        return fail(c, LZANI_ERR_ARG, "lzani_debug_sort_segments: bad arguments");
-    HIPCHK(c, d_tmp.alloc(need));
-    if (lzani_sort_segments(d_in.get(), d_out.get(), seg_len, n_seg, begin_bit, end_bit, d_tmp.get(), &need, c->stream) != 0)
-        return fail(c, LZANI_ERR_DEVICE, "lzani_debug_sort_segments: sort failed");
+    if (int rc = sort_keys(c, d_tmp, d_in.get(), d_out.get(), seg_len, n_seg, begin_bit, end_bit, "lzani_debug_sort_segments: sort", false)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out.get(), n * 8, hipMemcpyDeviceToHost));
     return LZANI_OK;

@@ -1,7 +1,7 @@
 // lzani_prefilter.h -- host side of the k-mer prefilter: the slice plan, the pass plan, the pass / tile driver and the
 // entry points (lzani_prefilter, _cross, _codes, _codes_cross, the fetch and the info calls).  Included by lzani_hip.hip
-// only, after lzani_ooc.h; of that file it uses lzani_ctx (which holds the Prefilter), fail, HIPCHK, gtab and env_u64.
-// The kernels are lzani_kernels_prefilter.h, the sort is lzani_sort_keys.
+// only, after lzani_ooc.h; of that file it uses lzani_ctx (which holds the Prefilter), fail, HIPCHK, gtab, env_u64 and
+// sort_keys.  The kernels are lzani_kernels_prefilter.h, the sort is lzani_sort.hip's.
 //
 // The stage computes, for every pair of genomes, how many sampled canonical k-mers they share, and keeps the pairs
 // above the thresholds as CSR rows.  The cross form (n_ref > 0) does so for the n_ref reference rows against the
@@ -72,10 +72,7 @@ struct PfClock {
 };
 int pf_sort(lzani_ctx* c, PrefilterWork& w, const unsigned long long* in, unsigned long long* out, size_t n, int b0, int b1)
 {
-    size_t need = w.tmp.capacity();
-    const int e = lzani_sort_keys(in, out, n, b0, b1, w.tmp, &need, c->stream);
-    if (e != 0) return fail(c, LZANI_ERR_DEVICE, std::string("lzani_prefilter: sort: ") + hipGetErrorString((hipError_t)e));
-    return LZANI_OK;
+    return sort_keys(c, w.tmp, in, out, n, 1, b0, b1, "lzani_prefilter: sort", false);      // (alloc_keys sized the scratch: it does not grow)
 }
 
 // The slice plan of the streamed prefilter (lzani_plan_slices): genomes in id order into contiguous slices; a new slice
@@ -276,8 +273,8 @@ struct PfRun {
         HIPCHK(c, w.ucnt.alloc((windows + PF_CHUNK - 1) / PF_CHUNK));
         HIPCHK(c, w.uoff.alloc((windows + PF_CHUNK - 1) / PF_CHUNK + 1));
         size_t need1 = 0, need2 = 0;
-        if (lzani_sort_keys(w.ka, w.kb, windows, 0, 2 * k, nullptr, &need1, c->stream) != 0 || lzani_sort_keys(w.kb, w.ka, windows, 32, 64, nullptr, &need2, c->stream) != 0)
-            return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
+        if (int rc = sort_scratch_bytes(c, windows, 1, 0, 2 * k, "lzani_prefilter: sort", need1)) return rc;
+        if (int rc = sort_scratch_bytes(c, windows, 1, 32, 64, "lzani_prefilter: sort", need2)) return rc;
         HIPCHK(c, w.tmp.alloc(std::max(need1, need2)));
         pinfo.workspace_bytes = w.ka.bytes() + w.kb.bytes() + w.tmp.bytes();
         return LZANI_OK;
@@ -425,12 +422,9 @@ struct PfRun {
         hipLaunchKernelGGL(k_pf_sparse_kept<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, w.sp_keys.get(), w.sp_cnt.get(), slots, pf.kmers_of.get(), min_shared,
                            min_ratio, w.sp_bcnt.get(), w.sp_boff.get(), (unsigned long long*)nullptr);
         if (int rc = scan_total(w.sp_bcnt, blocks, w.sp_boff, K)) return rc;
-        size_t need = 0;
         const int bits = 32 + ceil_log2(n);
-        if (lzani_sort_keys(nullptr, nullptr, K, 0, bits, nullptr, &need, c->stream) != 0) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: sort scratch size");
         HIPCHK(c, w.sp_kin.reserve(K));
         HIPCHK(c, w.sp_kout.reserve(K));
-        HIPCHK(c, w.sp_tmp.reserve(need));
         PrefilterTile tile;
         tile.r0 = r0; tile.r1 = r1;
         HIPCHK(c, tile.ids.alloc(K));
@@ -439,9 +433,7 @@ struct PfRun {
         hipLaunchKernelGGL(k_pf_sparse_kept<true>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, w.sp_keys.get(), w.sp_cnt.get(), slots, pf.kmers_of.get(), min_shared,
                            min_ratio, w.sp_bcnt.get(), w.sp_boff.get(), w.sp_kin.get());
         HIPCHK(c, hipGetLastError());
-        size_t have = w.sp_tmp.capacity();
-        const int e = lzani_sort_keys(w.sp_kin, w.sp_kout, K, 0, bits, w.sp_tmp, &have, c->stream);
-        if (e != 0) return fail(c, LZANI_ERR_DEVICE, std::string("lzani_prefilter: sort: ") + hipGetErrorString((hipError_t)e));
+        if (int rc = sort_keys(c, w.sp_tmp, w.sp_kin, w.sp_kout, K, 1, 0, bits, "lzani_prefilter: sort", false)) return rc;
         if (K) hipLaunchKernelGGL(k_pf_sparse_fetch, dim3((u32)((K + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.sp_kout.get(), K, w.sp_keys.get(),
                                   w.sp_cnt.get(), slots, tile.ids.get(), tile.shared.get());
         hipLaunchKernelGGL(k_pf_sparse_rowoff, dim3(nr / PF_THREADS + 1), dim3(PF_THREADS), 0, c->stream, w.sp_kout.get(), K, r0, nr, w.rowoff.get());

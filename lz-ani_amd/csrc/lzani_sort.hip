@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 namespace {
 
 typedef unsigned long long u64;
@@ -184,11 +186,18 @@ int lzani_sort_segments(const unsigned long long* in, unsigned long long* out, s
     if (*tmp_bytes < need) return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
     if (passes == 0) return (int)hipMemcpyAsync(out, in, n * 8, hipMemcpyDeviceToDevice, stream);
-    static bool attr_set = false;                     // (per process; the attribute belongs to the function, on every device)
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, RS_TILE * 8);
+    // The raised LDS limit of k_rs_scatter, once per device: bit d = device d has it.  The sort has no context, and the
+    // contexts of a group reach it from one thread per device: two threads that both find the bit clear both set the
+    // attribute (the same value, harmless) and both set the bit.  A device beyond the mask sets it on every call.
+    static std::atomic<unsigned long long> raised{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    const unsigned long long bit = dev < 64 ? 1ull << dev : 0;
+    if (!(raised.load(std::memory_order_acquire) & bit)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, RS_TILE * 8);
         if (e != hipSuccess) return (int)e;
-        attr_set = true;
+        raised.fetch_or(bit, std::memory_order_release);
     }
     char* t = static_cast<char*>(tmp);
     u64* alt = passes > 1 ? reinterpret_cast<u64*>(t) : nullptr;

@@ -125,8 +125,8 @@ def sample_max_of(fraction):
 
 def build_library(force=False):
     """hipcc cross-compiles for gfx950 without a GPU present."""
-    deps = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("lzani_core.h", "lzani_layout.h", "lzani_kernels_index.h",
-                                                             "lzani_kernels_cand.h", "lzani_kernels_pairs.h", "lzani_kernels_split.h", "lzani_kernels_prefilter.h", "lzani_prefilter_defs.h", "lzani_multi.h", "lzani_shard_plan.h", "lzani_sparse_plan.h", "lzani_ooc.h", "lzani_prefilter.h", "lzani_sort.hip", "lzani_tables.h", "lzani_rtc.h", "lzani_devmem.h")] + [os.path.join(ROOT, "include", "lzani.h")]
+    csrc = os.path.join(HERE, "csrc")                       # every header and source there: a new one cannot be forgotten
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".hip"))] + [os.path.join(ROOT, "include", "lzani.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",

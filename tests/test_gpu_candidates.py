@@ -3,7 +3,8 @@ reference slot (directory, entries, bucket table, tag words), its presence filte
 of the candidate stage -- against host statements made from the raw sequences (tests/index_model.py).  Every case also
 checks the run's triples against the oracle, so the structures checked are those of a correct run; and every case asserts
 from the engine's own report that the planned form really ran (build path, matrix from the index, hashed rows, group size,
-batches).  Out of scope: the join form's per-wave bitmaps and the split path's segments."""
+batches).  Out of scope: the join form's per-wave bitmaps and the split path's segments (the split's buffers, which the
+candidate scratch keeps between batches and runs, have one test at the end)."""
 import numpy as np
 import pytest
 
@@ -291,3 +292,50 @@ def test_more_than_32768_queries_in_one_group(monkeypatch):
     assert np.array_equal(got, oracle)
     exp = IM.expected_bitmaps(seqs, prm["mrd"], prm["mal"], plan["rshift"], plan["pm_bits"], pair_ref, pair_qry, cb.shape[1])
     assert np.array_equal(cb, exp)                              # every query's bitmap is one tile: all words written
+
+
+# ---- the split's buffers in the candidate scratch --------------------------------------------------------------------
+
+def test_split_buffers_survive_batches_and_runs(monkeypatch):
+    """The split path's buffers live in the context's candidate scratch: two batches of one run share them, a batch of
+    more segments and a larger batch grow them, a smaller batch reuses them -- every run equal to the same rows without
+    the split and to the oracle.  16 related genomes of 4-6 kbp, N runs in four; 8 index slots (the fewest the bitmap plan
+    takes for 16 rows) make two batches of 8 rows = 120 pairs, every pair cut into 3-5 segments of 1,500 positions.
+    LZANI_MAX_SLOTS is read when the genomes are set, so run (b) sets them again on the same engine: the scratch goes with
+    the set and is made anew, larger; the growth in place is the run with segments of 700 positions before it."""
+    seqs = [np.ascontiguousarray(s) for s in U._put_n_runs(SG.make_set(16, 616, lmin=4000, lmax=6000, fam=4)[1])]
+    n = len(seqs)
+    env = {"LZANI_PM_MIN_ROWS": "1", "LZANI_MAX_SLOTS": "8", "LZANI_SPLIT": "1", "LZANI_SPLIT_SEGLEN": "1500", "LZANI_SPLIT_ALL": "1",
+           "LZANI_RTC": "0"}
+    # the shape, before the GPU is asked: candidate bitmaps and the split for a batch of 8 rows, two such batches
+    names = {"split nfree=0 defp=1 mode=0", "split nfree=0 defp=1 mode=1"}
+    assert U.predict_kernels(seqs, None, env, n_rows=8) == names and U.predict_kernels(seqs, None, env, n_rows=4) == names
+    assert n == 16 and -(-n // int(env["LZANI_MAX_SLOTS"])) == 2
+    assert all(3 <= -(-(len(s) + 40) // 1500) <= 5 for s in seqs)
+    want = O.oracle_all2all(seqs, None, threads=16)
+    eng = _engine(monkeypatch, env, None, seqs)
+
+    def check(got, batches, min_segments):
+        lay = eng.layout()
+        assert lay["batches_last_run"] == batches and lay["split_launches"] == batches and lay["bitmap_launches"] == batches, lay
+        assert lay["split_segments"] >= min_segments, lay
+        assert set(eng.kernel_launches()) == names
+        assert np.array_equal(got, base) and np.array_equal(got, want)
+
+    monkeypatch.setenv("LZANI_SPLIT", "0")
+    base = eng.all2all()
+    lay = eng.layout()
+    assert lay["batches_last_run"] == 2 and lay["split_launches"] == 0 and lay["bitmap_launches"] == 2, lay
+    monkeypatch.setenv("LZANI_SPLIT", "1")
+    check(eng.all2all(), 2, 2 * 240)                        # (a) two batches: the second finds the first one's buffers
+    monkeypatch.setenv("LZANI_SPLIT_SEGLEN", "700")
+    check(eng.all2all(), 2, 2 * 120 * 6)                    # more segments a pair: the segment buffers grow in place
+    monkeypatch.setenv("LZANI_SPLIT_SEGLEN", "1500")
+    monkeypatch.delenv("LZANI_MAX_SLOTS")
+    eng.set_genomes(seqs)
+    check(eng.all2all(), 1, 240 * 3)                        # (b) one batch of 240 pairs
+    ref_ids, row_off = _dense(np.arange(4), n)
+    pair_ref, pair_qry = _pairs(n, ref_ids, row_off, None)
+    base, want = base[pair_ref, pair_qry], want[pair_ref, pair_qry]
+    check(eng.run_rows(ref_ids, row_off), 1, 60 * 3)        # (c) rows 0 .. 3: a smaller batch in the same buffers
+    eng.close()

@@ -501,6 +501,29 @@ def _clog2(x):
     return (int(x) - 1).bit_length() if x > 1 else 0
 
 
+WAVE_SLOTS = 256 * 8 * 4                # wave slots of the MI355X: 256 CUs, 8 blocks of 4 waves
+
+
+def split_rule(n_pairs, cb_words, dmax, env=None, slots=WAVE_SLOTS):
+    """Whether a dense batch of n_pairs pairs with candidate bitmaps of cb_words words is split -- its pairs scanned by
+    several waves each -- restated from lzani_run_plan.h (choose_split), not a call into the library.  dmax: the longest
+    genome + mrd; env: the LZANI_SPLIT* switches that are set."""
+    env = env or {}
+    if "LZANI_SPLIT" in env:
+        on = env["LZANI_SPLIT"][:1] == "1"
+    else:
+        on = cb_words >= 8192 and (n_pairs * 16 <= slots or (cb_words >= 65536 and n_pairs * 8 <= slots))
+    if not on or n_pairs * 2 > 0xFFFFFFFF // 64:            # (segment numbers are 32 bits)
+        return False
+    if int(env.get("LZANI_SPLIT_SEGLEN", 0)) > 0:
+        seglen = int(env["LZANI_SPLIT_SEGLEN"])
+    else:
+        S = min(max(2, int(env.get("LZANI_SPLIT_S", 64))), max(2, slots // n_pairs))
+        seglen = -(-dmax // S)
+    seglen = max(seglen, 512)
+    return -(-dmax // seglen) >= 2
+
+
 def predict_kernels(seqs, prm, env=None, form="all2all", pairs_per_row=None, n_rows=None, rtc_ready=False):
     """The names a run launches (lzani_hip.hip: run_rows_impl), from the genome set, the tuple, the environment (the
     LZANI_* switches that are set) and the call: form "all2all" (dense rows), "dup_lists" (query lists that name a
@@ -537,17 +560,7 @@ def predict_kernels(seqs, prm, env=None, form="all2all", pairs_per_row=None, n_r
     split = False
     if pm:
         cb_words = (Lmax + p["mrd"] + 320 + 1023) // 1024 * 32
-        slots = 256 * 8 * 4                                     # wave slots of the MI355X: 256 CUs, 8 blocks of 4 waves
-        on_ = on("LZANI_SPLIT") if "LZANI_SPLIT" in env else (cb_words >= 8192 and (n_pairs * 16 <= slots or (cb_words >= 65536 and n_pairs * 8 <= slots)))
-        if on_:
-            D = Lmax + p["mrd"]
-            if int(env.get("LZANI_SPLIT_SEGLEN", 0)) > 0:
-                seglen = int(env["LZANI_SPLIT_SEGLEN"])
-            else:
-                S = min(int(env.get("LZANI_SPLIT_S", 64)), max(2, slots // n_pairs))
-                seglen = -(-D // S)
-            seglen = max(seglen, 512)
-            split = -(-D // seglen) >= 2
+        split = split_rule(n_pairs, cb_words, Lmax + p["mrd"], env)
     fl = tw and not join_mode and _clog2(max(g["T"], 1024)) <= int(env.get("LZANI_FILTER_MAX_BITS", 18)) and not on("LZANI_NO_FILTER")
     blk = (not pm and tw and not join_mode and fl and pairs_per_row >= 128 and
            (on("LZANI_BLOCK_KERNEL") if "LZANI_BLOCK_KERNEL" in env else form == "all2all"))
