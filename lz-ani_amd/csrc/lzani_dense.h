@@ -2,8 +2,9 @@
 // matrix of the batch's references (lzani_kernels_cand.h) instead of a probe per query position or a join per pair, and,
 // where a batch holds few, long pairs, those pairs by several waves each (lzani_kernels_split.h).  Included by
 // lzani_hip.hip only, between the run's types and its pair launch; of that file it uses lzani_ctx (which holds the
-// CandScratch), RunCtx / Batch / RunPlan / Knobs / RowFacts, fail, HIPCHK, TRACE, gtab, ensure_slabs, raise_lds and
-// sort_keys.  The pure decisions -- the batches, the split / LPT rule, the bytes of a slab slot -- are lzani_run_plan.h.
+// CandScratch), RunCtx / Batch / RunPlan / Knobs / RowFacts, fail, HIPCHK, TRACE, raise_lds and sort_keys, of
+// lzani_index.h gtab, slot_bytes, ensure_slabs and for_slices.  The pure decisions -- the batches, the split / LPT rule,
+// the bytes of a slab slot -- are lzani_run_plan.h.
 // Host only: not among the sources a run-time compile embeds (lzani_rtc.h).
 //
 // Order of work:
@@ -43,16 +44,16 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
     // Below, the matrix -- 16 GB to clear at 30 key bits -- costs more than it saves.)
     // Long genomes (the join is the alternative: 210 ms for the 56 pairs of 8 x 5 Mbp against 149 by bitmaps, 92 with the
     // pairs cut into segments): from two rows on.
-    const u32 min_rows = k.pm_min_rows ? (u32)std::max(1, *k.pm_min_rows) : c->gs.join_mode ? 2u : c->gs.tw_stride ? 32u : 8u;
+    const u32 min_rows = k.pm_min_rows ? (u32)std::max(1, *k.pm_min_rows) : c->gs.lay.join_mode ? 2u : c->gs.lay.tw_stride ? 32u : 8u;
     // Query lists qualify when they are dense where they are: a query that occurs in a group of rows should meet a
     // good part of it (one matrix row read serves all its pairs of the group) -- the row x column blocks of a tiled
     // all2all do, the few relatives a kmer-db filter leaves per row do not.  No query twice in a row (one bitmap each).
     // (Measured in round 4 on the related workload, families of 50 in length order -- 16 pairs per query and group:
     // the pair kernel gains 18 % from the bitmaps, the candidate stage costs more than that; against the ROUNDS of the
     // first kernel -- no tag words: long k-mers on mid-size genomes -- the bitmaps win from two pairs per query on.)
-    const u64 min_share = k.pm_min_share.value_or(c->gs.tw_stride ? 48 : 2);
+    const u64 min_share = k.pm_min_share.value_or(c->gs.lay.tw_stride ? 48 : 2);
     const bool lists_ok = !lists || (!f.lists_dup && f.n_pairs >= min_share * f.lists_involved);
-    if (!(!regions && lists_ok && c->gs.tab.kmL && c->gs.bk_stride && c->P.mqd + c->P.mrd <= 128 && c->gs.geo.kb <= 30 &&
+    if (!(!regions && lists_ok && c->gs.tab.kmL && c->gs.lay.bk_stride && c->P.mqd + c->P.mrd <= 128 && c->gs.geo.kb <= 30 &&
           c->gs.n >= 2 && n_rows >= min_rows && k.pm))
         return LZANI_OK;
     u64 max_row = 0;
@@ -74,7 +75,7 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
     const size_t cap = k.pm_max_bytes.value_or(std::min((size_t)64 << 30, total_b / 4));
     const double room = pool * 0.85 - (double)m_bytes - (double)x_bytes;
     u64 fit = room > 0 ? (u64)(room / ((double)per_slot + avg_row * (double)per_pair)) : 0;     // rows: a slab + its pairs' bitmaps each
-    fit = std::min<u64>(fit, std::min<u32>(n_rows, c->gs.max_slots));
+    fit = std::min<u64>(fit, std::min<u32>(n_rows, c->gs.lay.max_slots));
     u64 cap_pairs = std::min<u64>((u64)(cap / per_pair), 0xFFFFFFF0ull);                           // pair indexes of a batch are 32 bits
     cap_pairs = std::min<u64>(cap_pairs, (u64)((double)fit * avg_row) + max_row);
     if (fit < std::min<u32>(8, n_rows) || cap_pairs < max_row) return LZANI_OK;
@@ -202,11 +203,11 @@ int candidate_stage(RunCtx& r, Batch& bt)
             for (u64 e = r.row_off[bt.k0 + g0]; e < r.row_off[bt.k0 + g0 + pg.rows]; ++e)
                 if (r.grp_seen[r.query_ids[e]] != stamp) { r.grp_seen[r.query_ids[e]] = stamp; ++nq; }
         }
-        for (u32 q0 = 0; q0 < nq; q0 += 32768) {           // gridDim.y is limited to 65535
+        for_slices(nq, [&](u32 q0, u32 cnt) {
             pg.q0 = q0;
             c->run.pmc_launches += 1;
-            hipLaunchKernelGGL(kc, dim3(p.pm_tiles, std::min<u32>(32768, nq - q0)), dim3(PM_CAND_THREADS), lds, c->stream, pg);
-        }
+            hipLaunchKernelGGL(kc, dim3(p.pm_tiles, cnt), dim3(PM_CAND_THREADS), lds, c->stream, pg);
+        });
         c->run.tm.cand_launches += 2;
     }
     if (!bt.lpt || c->cs.d_lpt_cnt == nullptr) bt.split_S = 0;   // (no candidate counts after all -- their buffer could not be had: no split)

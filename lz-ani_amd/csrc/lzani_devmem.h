@@ -1,4 +1,4 @@
-// lzani_devmem.h -- the one owner of device memory (and of pinned host memory) on the host side of the engine.
+// lzani_devmem.h -- the one owner of device memory (and of pinned host memory) and of events on the host side of the engine.
 // Host only: no kernel sees it, and it is not among the sources a run-time compile embeds (lzani_rtc.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,6 +54,51 @@ public:
 };
 template <class T>
 using PinMem = DevMem<T, true>;
+
+// A HIP event, destroyed by the destructor.  Move-only, empty by default.
+class DevEvent {
+    hipEvent_t e_ = nullptr;
+
+public:
+    DevEvent() = default;
+    DevEvent(DevEvent&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    DevEvent& operator=(DevEvent&& o) noexcept { std::swap(e_, o.e_); return *this; }
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    ~DevEvent() { reset(); }
+
+    void reset()
+    {
+        if (e_) (void)hipEventDestroy(e_);
+        e_ = nullptr;
+    }
+    hipError_t create(unsigned flags = hipEventDefault)
+    {
+        reset();
+        const hipError_t e = hipEventCreateWithFlags(&e_, flags);
+        if (e != hipSuccess) e_ = nullptr;
+        return e;
+    }
+    operator hipEvent_t() const { return e_; }
+};
+
+// The device time of a stretch of a stream's work: begin and end are recorded on the stream (the events are made by the
+// first begin and used again by the later ones), elapsed waits for the end and reads the time between them.
+struct StreamSpan {
+    DevEvent ev[2];
+    hipError_t begin(hipStream_t s)
+    {
+        for (DevEvent& e : ev)
+            if (!e) { const hipError_t rc = e.create(); if (rc != hipSuccess) return rc; }
+        return hipEventRecord(ev[0], s);
+    }
+    hipError_t end(hipStream_t s) { return hipEventRecord(ev[1], s); }
+    hipError_t elapsed(float& ms)
+    {
+        const hipError_t rc = hipEventSynchronize(ev[1]);
+        return rc != hipSuccess ? rc : hipEventElapsedTime(&ms, ev[0], ev[1]);
+    }
+};
 
 // For the callers that fall back instead of failing: whether the allocation succeeded; the runtime's sticky error is
 // cleared where it did not.

@@ -1,14 +1,18 @@
-// lzani_hip.hip -- the C-ABI of include/lzani.h: context, device memory, launches.  gfx950 (MI355X) only.
+// lzani_hip.hip -- the C-ABI of include/lzani.h: the context, the run driver (check_rows ... run_rows_impl) and the entry
+// points.  gfx950 (MI355X) only.
 //
-// The kernels (all integer / bit work; no MFMA by design) live in two headers included below:
+// The kernels (all integer / bit work; no MFMA by design) live in the headers included below:
 //   lzani_kernels_index.h   k_pack, k_kmers, k_idx_*   genomes -> packed texts, k-mer words, anchor indexes
 //   lzani_kernels_cand.h    k_pm_build, k_pm_cand   dense rows: presence matrix of a group of references -> per-pair candidate bitmaps
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
-// lzani_core.h; sizes and the parameter envelope are lzani_layout.h; the pure decisions of a run (batches, queues, the
-// split rule, the bytes of a slab slot) are lzani_run_plan.h, free of HIP.  Four layers of the host side are files of their
-// own, included at fixed places below:
+// lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
+// (batches, queues, the split rule, the bytes of a slab slot) in lzani_run_plan.h, those of a genome set (the set-level
+// switches, the form of the index, footprints, the block plan, residency, the slot count of the slabs) in lzani_set_plan.h.
+// Device memory and events have one owner each, lzani_devmem.h.  Five layers of the host side are files of their own,
+// included at fixed places below:
+//   lzani_index.h       the index stage: genome upload, slabs, k-mer words, join lists, the index build, its test hooks
 //   lzani_dense.h       the dense-row stage of a run: candidate bitmaps from the presence matrix, the split of few, long pairs
 //   lzani_ooc.h         genome sets larger than the device: block plan, block uploads, the tiled run
 //   lzani_prefilter.h   the k-mer prefilter's host stage: slice and pass plans, the pass / tile driver, its entry points
@@ -58,6 +62,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_rtc.h"
 #include "lzani_devmem.h"
 #include "lzani_run_plan.h"
+#include "lzani_set_plan.h"
 
 // ============================================================================================
 // Host side of the C-ABI
@@ -186,7 +191,7 @@ struct JoinLists {
 
 // lzani_set_genomes -> the next one.
 struct GenomeSet {
-    u32 n = 0, n_pending = 0;     // n_pending: genome count while lzani_set_genomes is still at work
+    u32 n = 0;
     std::vector<int> L;
     std::vector<u64> nmoff;
     int Tmax = 0;
@@ -195,15 +200,8 @@ struct GenomeSet {
     u64 total_nm = 0;
     bool kmers_ready = false;
     bool all_nfree = false;       // no genome holds an N: the NFREE kernel instantiation applies
-    // the form of the anchor index, chosen per set (choose_index_form)
     u64 dir_stride = 0, ent_stride = 0;
-    u64 bk_stride = 0;            // bucket tables
-    u64 tw_stride = 0;            // tag words of the bucket tables (tag bits <= 7)
-    u64 fl_stride = 0;            // presence filters: words per slot; 0 = no filter (one all-ones word)
-    u32 fmask = 31;
-    bool join_mode = false;
-    bool sort_build = false;      // sort-based index build (large directories)
-    u32 max_slots = 65535;        // gridDim.y limit; LZANI_MAX_SLOTS lowers it (tests force the multi-batch path)
+    SetLayout lay;                // the form of the anchor index, chosen per set (set_layout_of)
     int blk_fold = -1;            // k_pairs_blk: LDS filter = global filter folded 2^blk_fold times (-1: not decided yet, -2: does not fit)
     JoinLists jl;
     DevMem<unsigned char> d_jtmp; // radix-sort scratch (join lists, the sort-based index build, ticket order)
@@ -310,11 +308,11 @@ struct lzani_ctx {
     Params P;
     int dev = 0;
     hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> events;    // four per batch of a run (index begin/end, pairs begin/end)
+    std::vector<DevEvent> events;      // EV per batch of a run, made as the runs need them and used again
     int n_cus = 256;
     std::string err;
-    hipEvent_t ev_km[2] = {nullptr, nullptr};
-    bool km_timed = false;        // the last run made the k-mer words (ev_km holds their stamps)
+    StreamSpan km_span;
+    bool km_timed = false;        // the last run made the k-mer words (km_span holds their stamps)
     double join_ms_pending = 0;   // ... and / or the join lists: their time, added to that run's kmers_ms
     DevMem<unsigned long long> d_cursor;
     DevMem<u32> d_blkctr;         // k_pairs_blk: one pair counter per block
@@ -361,15 +359,6 @@ int fail(lzani_ctx* c, int code, const std::string& msg)
                         std::string(#call) + ": " + hipGetErrorString(e_));                           \
     } while (0)
 
-// Per-genome k-mer words exist for mal, msl <= 15 (the fast path).
-bool kmer_words_of(const Params& P) { return P.mal <= 15 && P.msl <= 15; }
-
-// An LZANI_* switch: whether it is set and begins with ch; its number (atoi / strtoull); empty where it is not set.
-bool env_is(const char* name, char ch) { const char* v = getenv(name); return v && *v == ch; }
-std::optional<bool> env_flag(const char* name) { const char* v = getenv(name); return v ? std::optional<bool>(*v == '1') : std::nullopt; }
-std::optional<int> env_int(const char* name) { const char* v = getenv(name); return v ? std::optional<int>(atoi(v)) : std::nullopt; }
-std::optional<u64> env_u64(const char* name) { const char* v = getenv(name); return v ? std::optional<u64>(strtoull(v, nullptr, 10)) : std::nullopt; }
-
 // The one place that raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize): lds_limit is what
 // this context last gave the kernel (0: the default), raise_lds calls the runtime only where that is below `bytes`.
 size_t& lds_limit(lzani_ctx* c, const void* fn)
@@ -413,221 +402,6 @@ int sort_keys(lzani_ctx* c, DevMem<unsigned char>& scratch, const unsigned long 
     return LZANI_OK;
 }
 
-struct IndexForm { u64 bk_stride, tw_stride; bool join_mode; };
-
-// Bucket table, tag words and the join form of a genome set of n genomes with this geometry (environment overrides
-// included): what choose_index_form lays out, and what the block plan of an out-of-core set (lzani_ooc.h) counts.
-IndexForm index_form_of(const Params& P, const IndexGeom& geo, u32 n)
-{
-    IndexForm f;
-    int tagbits = 0;
-    while (tagbits < 32 && ((geo.tagmask >> tagbits) & 1u)) ++tagbits;
-    const bool exact = geo.tagmask == (u32)lowmask(geo.kb - geo.dirbits);
-    const int max_dirbits = env_int("LZANI_BK_MAX_DIRBITS").value_or(26);
-    // bucket table (+ tag words): wherever the sentinels cannot be real entries; 20 B per bucket more per slot
-    // (LZANI_NO_BUCKETS, LZANI_NO_TAGWORDS: experiments / test_index_forms)
-    f.bk_stride = (kmer_words_of(P) && exact && geo.dirbits <= max_dirbits && tagbits + geo.posbits <= 30 && !env_is("LZANI_NO_BUCKETS", '1'))
-                      ? ((u64)4 << geo.dirbits) : 0;
-    f.tw_stride = (f.bk_stride && tagbits <= 7 && !env_is("LZANI_NO_TAGWORDS", '1')) ? ((u64)1 << geo.dirbits) : 0;
-    // Join form of candidate detection: where the tag words of one reference exceed what an L2 holds by far, a random
-    // probe per query position costs one HBM line each; the query's k-mer list sorted by bucket turns the probes into
-    // two streams (DevWave::join).  Needs the anchor queue (tag words, seed window <= 128) and keys of 64 bits.
-    const u64 min_bytes = env_u64("LZANI_JOIN_MIN_BYTES").value_or(8ull << 20);
-    const int gbits = ceil_log2((u64)n + 1);                          // the all-ones genome number is the invalid key's
-    f.join_mode = f.tw_stride && f.tw_stride * 4 >= min_bytes && P.mqd + P.mrd <= 128 &&
-                  gbits + geo.kb + geo.posbits <= 64 && !env_is("LZANI_NO_JOIN", '1');
-    return f;
-}
-
-// The form of the anchor index (bucket table, tag words) is a property of the genome set and the parameters:
-// decided once per lzani_set_genomes, so the strides of the slabs never change under an allocation.
-void choose_index_form(lzani_ctx* c)
-{
-    {
-        const IndexForm f = index_form_of(c->P, c->gs.geo, c->gs.n_pending);
-        c->gs.bk_stride = f.bk_stride;
-        c->gs.tw_stride = f.tw_stride;
-        c->gs.join_mode = f.join_mode;
-    }
-    // Sort-based index build where the directory is beyond the LDS-staged build (2^19 buckets): keys of 64 bits with up
-    // to 16 bits of slot number (LZANI_SORT_INDEX_MIN_DIRBITS=0, tests: at every size)
-    c->gs.sort_build = kmer_words_of(c->P) && c->gs.geo.dirbits >= env_int("LZANI_SORT_INDEX_MIN_DIRBITS").value_or(20) &&
-                    c->gs.geo.kb + c->gs.geo.posbits <= 60 && !env_is("LZANI_NO_SORT_INDEX", '1');
-    // Presence filter in front of the tag-word probes (probe form only; k_pairs_blk keeps the reference's in LDS): ~3 bits
-    // per text position, at most 2^18 bits (genomes up to ~128 kbp); beyond, one all-ones word passes everything
-    {
-        const int fmax = env_int("LZANI_FILTER_MAX_BITS").value_or(18);      // 2^18 bits = 32 KB of LDS per block of 16 waves
-        const int fbits = std::min(ceil_log2((u64)std::max(c->gs.Tmax, 1024)) + 1, fmax);
-        const bool on = c->gs.tw_stride && !c->gs.join_mode && ceil_log2((u64)std::max(c->gs.Tmax, 1024)) <= fmax && !env_is("LZANI_NO_FILTER", '1');
-        c->gs.fl_stride = on ? ((u64)1 << fbits) / 32 : 0;
-        c->gs.blk_fold = -1;
-        c->gs.fmask = on ? (u32)((1u << fbits) - 1u) : 31u;
-    }
-    const int ms = env_int("LZANI_MAX_SLOTS").value_or(0);
-    c->gs.max_slots = ms > 0 ? (u32)std::min(65535, ms) : 65535u;
-    if (c->gs.sort_build)                                  // the slot number shares the 64-bit key with hash and position
-        c->gs.max_slots = (u32)std::min<u64>(c->gs.max_slots, (1ull << std::min(16, 64 - c->gs.geo.kb - c->gs.geo.posbits)) - 1);
-}
-
-// The bytes of one index slab slot of the set (lzani_run_plan.h): the tables, and the keys of the sort-based build.
-SlabBytes slot_bytes(const GenomeSet& gs)
-{
-    return slab_bytes_per_slot(gs.dir_stride, gs.ent_stride, gs.bk_stride, gs.tw_stride, gs.fl_stride, gs.sort_build, (u64)gs.Tmax);
-}
-
-int ensure_slabs(lzani_ctx* c, u32 want_rows)
-{
-    const size_t per_slot = (size_t)slot_bytes(c->gs).total();
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    size_t have = c->sl.slots * per_slot;
-    size_t budget = (size_t)((free_b + have) * 0.6);
-    u32 slots = (u32)std::min<size_t>(std::min<u32>(want_rows, c->gs.max_slots), std::max<size_t>(1, budget / per_slot));
-    if (slots <= c->sl.slots) return LZANI_OK;
-    c->sl = IndexSlabs{};                              // released first: two generations need not fit
-    IndexSlabs s;
-    HIPCHK(c, s.d_dirz.alloc((size_t)slots * c->gs.dir_stride));
-    HIPCHK(c, s.d_ent.alloc((size_t)slots * c->gs.ent_stride));
-    if (c->gs.bk_stride) HIPCHK(c, s.d_bk.alloc((size_t)slots * c->gs.bk_stride));
-    if (c->gs.tw_stride) HIPCHK(c, s.d_tw.alloc((size_t)slots * c->gs.tw_stride));
-    if (c->gs.tw_stride) {
-        HIPCHK(c, s.d_fl.alloc((size_t)slots * c->gs.fl_stride));
-        if (!c->gs.fl_stride) HIPCHK(c, hipMemset(s.d_fl, 0xFF, 4));
-    }
-    HIPCHK(c, s.d_status.alloc(slots));
-    if (c->gs.sort_build) {
-        HIPCHK(c, s.d_ikeys_in.alloc((size_t)slots * c->gs.Tmax));
-        HIPCHK(c, s.d_ikeys.alloc((size_t)slots * c->gs.Tmax));
-        HIPCHK(c, s.d_icnt.alloc(slots));
-        HIPCHK(c, s.d_ibase.alloc(slots));
-    }
-    s.slots = slots;
-    c->sl = std::move(s);
-    return LZANI_OK;
-}
-
-GenomeTab gtab(const lzani_ctx* c)
-{
-    const GenomeTables& t = c->gs.tab;
-    return GenomeTab{t.t2, t.nm, t.nmoff, t.L, t.kmL, t.kmS, t.hasN};
-}
-
-// Join form: the k-mer list of every genome as a query, sorted by (genome, bucket) -- k_join_keys + the radix sort of lzani_sort.hip,
-// once per run, behind k_kmers (it is part of the path's work like the k-mer words it is made from).
-// the resident part of the join lists (the sorted keys: 8 B per forward position), allocated before the index slabs are
-// sized so that those see what is really left
-int alloc_join_lists(lzani_ctx* c)
-{
-    const u32 n = c->gs.n;
-    if (c->gs.jl.keys) return LZANI_OK;
-    JoinLists jl;                                        // (moved into the set whole, or not at all)
-    jl.h_koff.assign((size_t)n + 1, 0);
-    for (u32 g = 0; g < n; ++g) jl.h_koff[g + 1] = jl.h_koff[g] + (u64)c->gs.L[g];
-    HIPCHK(c, jl.koff.alloc((size_t)n + 1));
-    HIPCHK(c, jl.soff.alloc((size_t)n + 1));
-    HIPCHK(c, jl.cnt.alloc(n));
-    HIPCHK(c, jl.keys.alloc(jl.h_koff[n]));
-    HIPCHK(c, hipMemcpyAsync(jl.koff, jl.h_koff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    c->gs.jl = std::move(jl);
-    return LZANI_OK;
-}
-
-int build_join_lists(lzani_ctx* c)
-{
-    const u32 n = c->gs.n;
-    int rc0 = alloc_join_lists(c);
-    if (rc0) return rc0;
-    // the unsorted keys live for the duration of the sort only (as much again as the lists themselves)
-    DevMem<unsigned long long> keys_in;
-    HIPCHK(c, keys_in.alloc(c->gs.jl.h_koff[n]));
-    int Lmax = 0;
-    for (u32 g = 0; g < n; ++g) Lmax = std::max(Lmax, c->gs.L[g]);
-    // An invalid key is all ones; the sort looks at the bits [posbits, shift_g + gbits) only, so no real genome number may
-    // be all ones in gbits bits, or its keys with the all-ones hash would be indistinguishable from the invalid keys of
-    // the genomes before it (found by the fuzz at n = 4: genome 3 lost the k-mers of its last bucket)
-    const int shift_g = c->gs.geo.kb + c->gs.geo.posbits, gbits = ceil_log2((u64)n + 1);
-    HIPCHK(c, hipMemsetAsync(c->gs.jl.cnt, 0, (size_t)n * 4, c->stream));
-    for (u32 g0 = 0; g0 < n && Lmax > 0; g0 += 32768) {
-        const u32 cnt = std::min<u32>(32768, n - g0);
-        GenomeTab G = gtab(c);
-        G.nmoff += g0; G.L += g0;
-        // (the genome number of the key is global: the kernel adds g0 through the offset tables it is given)
-        hipLaunchKernelGGL(k_join_keys, dim3((Lmax + 4095) / 4096, cnt), dim3(256), 0, c->stream, G, c->gs.jl.koff + g0, keys_in,
-                           c->gs.jl.cnt + g0, shift_g, c->gs.geo.posbits, Lmax, g0);
-    }
-    HIPCHK(c, hipGetLastError());
-    std::vector<u32> valid(n);
-    HIPCHK(c, hipMemcpyAsync(valid.data(), c->gs.jl.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // sort in groups of whole genomes below 2^30 keys; invalid keys (all ones) end up behind the group's valid ones
-    std::vector<u64> soff((size_t)n + 1, 0);
-    for (u32 g0 = 0; g0 < n;) {
-        u32 g1 = g0;
-        u64 keys = 0;
-        while (g1 < n && (g1 == g0 || keys + (u64)c->gs.L[g1] <= (1ull << 30))) keys += (u64)c->gs.L[g1++];
-        if (keys > 0x7FFFFFF0ull) return fail(c, LZANI_ERR_ARG, "join lists: a genome of more than 2^31 positions");
-        u64 at = c->gs.jl.h_koff[g0];
-        for (u32 g = g0; g < g1; ++g) { soff[g] = at; at += valid[g]; }
-        if (g1 == n) soff[n] = at;
-        if (keys)
-            if (int rc = sort_keys(c, c->gs.d_jtmp, keys_in + c->gs.jl.h_koff[g0], c->gs.jl.keys + c->gs.jl.h_koff[g0], keys, 1, c->gs.geo.posbits, shift_g + gbits,
-                                   "join lists: radix sort", false))
-                return rc;
-        g0 = g1;
-    }
-    // (a genome's list ends after its valid keys -- d_jcnt -- not where the next list begins: between two groups sit the
-    // invalid keys of the first)
-    HIPCHK(c, hipMemcpyAsync(c->gs.jl.soff, soff.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));        // (before keys_in is released)
-    c->run.tm.index_launches += 2;
-    return LZANI_OK;
-}
-
-// Per-genome k-mer words (and, for long genomes, the sorted join lists made from them): once per genome set, by the
-// first run after lzani_set_genomes -- before its index slabs are sized, so that the slabs see what the lists and the
-// sort's temporaries have left -- and kept for the runs that follow (they depend on the genomes and the parameters
-// only).  Timed on their own (lzani_timing.kmers_ms).
-int ensure_kmers(lzani_ctx* c)
-{
-    if (!c->gs.tab.kmL || c->gs.kmers_ready) return LZANI_OK;
-    HIPCHK(c, hipEventRecord(c->ev_km[0], c->stream));
-    for (u32 g0 = 0; g0 < c->gs.n; g0 += 32768) {
-        u32 cnt = std::min<u32>(32768, c->gs.n - g0);
-        GenomeTab G = gtab(c);
-        G.nmoff += g0; G.L += g0;
-        hipLaunchKernelGGL(k_kmers, dim3((c->gs.Tmax + 255) / 256, cnt), dim3(256), 0, c->stream,
-                           G, c->gs.tab.kmL, c->gs.tab.kmS, c->P.mal, c->P.msl, c->P.mrd, c->gs.Tmax);
-    }
-    HIPCHK(c, hipGetLastError());
-    c->run.tm.index_launches += 1;
-    HIPCHK(c, hipEventRecord(c->ev_km[1], c->stream));
-    c->gs.kmers_ready = true;
-    c->km_timed = true;
-    return LZANI_OK;
-}
-
-// The sorted join lists of a long-genome set (join form of candidate detection): made by the first run that needs them
-// -- dense rows take their candidates from the presence matrix instead -- and kept like the k-mer words they are made
-// from; their time is part of that run's kmers_ms.
-int ensure_join(lzani_ctx* c)
-{
-    if (!c->gs.join_mode || c->gs.jl.ready) return LZANI_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
-    int rc = e == hipSuccess ? build_join_lists(c) : fail(c, LZANI_ERR_DEVICE, std::string("join lists: ") + hipGetErrorString(e));
-    if (rc == LZANI_OK) {
-        float ms = 0;
-        if (hipEventRecord(e1, c->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
-            c->join_ms_pending = ms;
-        c->gs.jl.ready = true;
-    }
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return rc;
-}
-
 // The run path's switches (experiments and tests), read where a Knobs is made: at the start of every run (tests change them
 // between the runs of one context).  Empty: not set, the run's own rule decides.
 struct Knobs {
@@ -649,71 +423,11 @@ struct Knobs {
     int lds_index_max_dirbits = env_int("LZANI_LDS_INDEX_MAX_DIRBITS").value_or(19);
 };
 
-// Index build of `rows` references (device list d_ref_ids) into slots 0..rows-1.
-// with_tw = false: the sort-based build leaves the tag words out (a batch whose pairs read candidate bitmaps never probes them:
-// 8.6 GB less to write per 128 x 5 Mbp references)
-int build_indexes(lzani_ctx* c, const Knobs& k, const u32* d_ref_ids, u32 rows, bool with_filter = true, bool with_tw = true)
-{
-    IdxArgs ia;
-    ia.G = gtab(c);
-    ia.ref_ids = d_ref_ids;
-    ia.dirz = c->sl.d_dirz; ia.ent = c->sl.d_ent;
-    ia.dir_stride = c->gs.dir_stride; ia.ent_stride = c->gs.ent_stride;
-    ia.mal = c->P.mal; ia.mrd = c->P.mrd; ia.geo = c->gs.geo; ia.todo = nullptr;
-    const u32 nb = 1u << c->gs.geo.dirbits;
-    { int rc = ensure_kmers(c); if (rc) return rc; }
-    if (c->gs.fl_stride && with_filter) {              // (only the block kernel reads it)
-        HIPCHK(c, hipMemsetAsync(c->sl.d_fl, 0, (size_t)rows * c->gs.fl_stride * 4, c->stream));
-        hipLaunchKernelGGL(k_idx_filter, dim3((u32)std::min<u64>(((u64)c->gs.Tmax + 255) / 256, 64), rows), dim3(256), 0, c->stream,
-                           ia, c->sl.d_fl, c->gs.fl_stride, c->gs.fmask, c->gs.Tmax);
-        c->run.tm.index_launches += 1;
-    }
-    if (c->gs.sort_build) {
-        c->sl.index_build = LZANI_INDEX_BUILD_SORT;
-        // keys -> radix sort, every slot a segment of its own (lzani_sort.hip) -> the tables in one streaming pass.  A key is
-        // hash || position; a position without a k-mer is all ones and sorts behind the slot's keys by the one bit above the hash.
-        const int shift_slot = c->gs.geo.kb + c->gs.geo.posbits;
-        const u64 Tm = (u64)c->gs.Tmax;
-        const u32 group = 1;
-        HIPCHK(c, hipMemsetAsync(c->sl.d_icnt, 0, (size_t)rows * 4, c->stream));
-        hipLaunchKernelGGL(k_idx_keys, dim3((u32)((Tm + 4095) / 4096), rows), dim3(256), 0, c->stream, ia, c->sl.d_ikeys_in, c->sl.d_icnt, c->gs.Tmax, shift_slot);
-        if (int rc = sort_keys(c, c->gs.d_jtmp, c->sl.d_ikeys_in, c->sl.d_ikeys, Tm, rows, c->gs.geo.posbits, shift_slot + 1, "index build: radix sort", true)) return rc;
-        hipLaunchKernelGGL(k_idx_base, dim3((rows + 255) / 256), dim3(256), 0, c->stream, c->sl.d_icnt, c->sl.d_ibase, rows, group, Tm);
-        hipLaunchKernelGGL(k_idx_from_sorted, dim3((u32)std::min<u64>((Tm + 255) / 256, 8192), rows), dim3(256), 0, c->stream,
-                           ia, c->sl.d_ikeys, c->sl.d_icnt, c->sl.d_ibase, c->sl.d_bk, with_tw ? c->sl.d_tw : nullptr, c->gs.bk_stride, c->gs.tw_stride);
-        HIPCHK(c, hipGetLastError());
-        c->run.tm.index_launches += 4;
-        return LZANI_OK;
-    }
-    const bool lds_build = c->gs.tab.kmL && c->gs.geo.dirbits <= k.lds_index_max_dirbits && k.lds_index;
-    c->sl.index_build = lds_build ? LZANI_INDEX_BUILD_LDS : LZANI_INDEX_BUILD_ATOMICS;
-    // blocks per slot of the global-atomics kernels: the whole range when they build every slot, a handful when
-    // they only pick up what k_idx_build left (usually nothing)
-    const u32 gx_pos = lds_build ? 16u : (u32)((c->gs.Tmax + 255) / 256), gx_bkt = lds_build ? 16u : (nb + 255) / 256;
-    dim3 gp(gx_pos, rows);
-    if (lds_build) {
-        // one block per reference, everything through LDS; a slot that does not fit (status != 0) falls through
-        // to the global-atomics kernels below, which skip every other slot
-        const size_t lds = (size_t)(IDX_RANGE / 2 + IDX_STAGE) * 4;
-        { int rc = raise_lds(c, k_idx_build, lds); if (rc) return rc; }
-        HIPCHK(c, hipMemsetAsync(c->sl.d_status, 0, (size_t)rows * 4, c->stream));
-        hipLaunchKernelGGL(k_idx_build, dim3(rows), dim3(1024), lds, c->stream, ia, c->sl.d_bk, c->sl.d_tw, c->gs.bk_stride, c->gs.tw_stride, c->sl.d_status);
-        ia.todo = c->sl.d_status;
-        hipLaunchKernelGGL(k_idx_zero, dim3(gx_bkt, rows), dim3(256), 0, c->stream, c->sl.d_dirz, c->gs.dir_stride, nb, ia.todo);
-    } else HIPCHK(c, hipMemsetAsync(c->sl.d_dirz, 0, (size_t)rows * c->gs.dir_stride * 4, c->stream));
-    hipLaunchKernelGGL(k_idx_count, gp, dim3(256), 0, c->stream, ia, c->gs.Tmax);
-    hipLaunchKernelGGL(k_idx_scan, dim3(rows), dim3(1024), 0, c->stream, c->sl.d_dirz, c->gs.dir_stride, nb, ia.todo);
-    hipLaunchKernelGGL(k_idx_fill, gp, dim3(256), 0, c->stream, ia, c->gs.Tmax);
-    hipLaunchKernelGGL(k_idx_sort, dim3(gx_bkt, rows), dim3(256), 0, c->stream,
-                       c->sl.d_dirz, c->sl.d_ent, c->gs.dir_stride, c->gs.ent_stride, nb, ia.todo, 0);
-    if (c->sl.d_bk)
-        hipLaunchKernelGGL(k_idx_buckets, dim3(gx_bkt, rows), dim3(256), 0, c->stream,
-                           c->sl.d_dirz, c->sl.d_ent, c->sl.d_bk, c->sl.d_tw, c->gs.dir_stride, c->gs.ent_stride, c->gs.bk_stride, c->gs.tw_stride,
-                           nb, c->gs.geo.posbits, ia.todo);
-    HIPCHK(c, hipGetLastError());
-    c->run.tm.index_launches += 4;
-    return LZANI_OK;
-}
+}  // namespace
+
+#include "lzani_index.h"
+
+namespace {
 
 struct RegionSink { lzani_region* d_regions; unsigned long long* d_count; unsigned long long capacity; };
 
@@ -834,7 +548,7 @@ int plan_run(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const 
     p.pm_bits = std::min(std::min(c->gs.geo.kb, 30), ceil_log2((u64)std::max(c->gs.Tmax, 1)) + 9);
     int rc = plan_bitmaps(c, k, f, n_rows, row_off, lists, regions, p);
     if (rc || p.pm) return rc;
-    p.use_join = c->gs.join_mode;
+    p.use_join = c->gs.lay.join_mode;
     if (p.use_join) { rc = ensure_join(c); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
     rc = ensure_slabs(c, n_rows);
     if (rc) return rc;
@@ -848,7 +562,7 @@ bool blk_fits(lzani_ctx* c, const void* kf)
 {
     if (c->gs.blk_fold == -1) {
         for (int fold = 0; fold <= 4 && c->gs.blk_fold < 0; ++fold) {
-            const size_t l = (size_t)(BLK_WAVES * SEED_LDS_WORDS + std::max<u64>(c->gs.fl_stride >> fold, 1)) * 4;
+            const size_t l = (size_t)(BLK_WAVES * SEED_LDS_WORDS + std::max<u64>(c->gs.lay.fl_stride >> fold, 1)) * 4;
             if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l) != hipSuccess) { (void)hipGetLastError(); continue; }
             lds_limit(c, kf) = l;                      // (what the kernel has now: the launch's raise_lds finds the fold settled on)
             int nb = 0;
@@ -862,7 +576,7 @@ bool blk_fits(lzani_ctx* c, const void* kf)
 
 // The batch's pair launch: the run's form picks the kernel, (nfree, dsel) its template arguments; a tuple compiled at run
 // time goes first where it has a kernel of the form.
-int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
+int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, const DevEvent* ev)
 {
     lzani_ctx* c = r.c;
     const bool tickets = bt.lpt && bt.split_S < 2;
@@ -871,9 +585,9 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     pa.P = c->P; pa.geo = c->gs.geo;
     pa.dirz = c->sl.d_dirz; pa.ent = c->sl.d_ent;
     pa.dir_stride = c->gs.dir_stride; pa.ent_stride = c->gs.ent_stride;
-    pa.bk = c->sl.d_bk; pa.bk_stride = c->gs.bk_stride;
-    pa.tw = c->sl.d_tw; pa.tw_stride = c->gs.tw_stride;
-    pa.fl = c->sl.d_fl; pa.fl_stride = c->gs.fl_stride; pa.fmask = c->gs.fmask;
+    pa.bk = c->sl.d_bk; pa.bk_stride = c->gs.lay.bk_stride;
+    pa.tw = c->sl.d_tw; pa.tw_stride = c->gs.lay.tw_stride;
+    pa.fl = c->sl.d_fl; pa.fl_stride = c->gs.lay.fl_stride; pa.fmask = c->gs.lay.fmask;
     pa.ref_ids = r.d_ref + bt.k0; pa.row_off = r.d_off + bt.k0; pa.query_ids = r.d_q;
     pa.out = r.d_out; pa.cursor = c->d_cursor;
     pa.qorder = r.d_qorder + bt.k0; pa.qcum = r.d_qcum + bt.k0 + bt.b;
@@ -925,11 +639,11 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
     } else if (tw && pa.skeys) {                  // long genomes: candidates by the join
         if (!rtc_launch()) with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 1>(c, gd, bd, pa); });
     } else if (use_blk) {
-        const u32 fw = (u32)std::max<u64>(c->gs.fl_stride >> c->gs.blk_fold, 1);
+        const u32 fw = (u32)std::max<u64>(c->gs.lay.fl_stride >> c->gs.blk_fold, 1);
         const size_t lds = (size_t)(BLK_WAVES * SEED_LDS_WORDS + fw) * 4;
         rc = raise_lds(c, kf, lds);              // (a no-op after blk_fits, which recorded the fold it settled on)
         if (rc) return rc;
-        pa.fmask = c->gs.fmask >> c->gs.blk_fold;
+        pa.fmask = c->gs.lay.fmask >> c->gs.blk_fold;
         c->run.blk_launches += 1;
         const dim3 gb((u32)std::min<u64>((waves + BLK_CHUNK_MIN - 1) / BLK_CHUNK_MIN, (u64)c->n_cus * 2)), bb(64 * BLK_WAVES);
         with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) {
@@ -948,14 +662,14 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, hipEvent_t* ev)
 constexpr int EV = 5;                             // stamps per batch: index begin / end, pairs begin / end, candidates end
 
 // One batch: index build, split / LPT choice, candidate stage, pair launch -- stream work only, stamped into ev.
-int run_batch(RunCtx& r, Batch bt, hipEvent_t* ev)
+int run_batch(RunCtx& r, Batch bt, const DevEvent* ev)
 {
     lzani_ctx* c = r.c;
     const RunPlan& p = r.p;
     TRACE("batch %u rows [%u,%u) pairs [%llu,%llu) slots=%u pm=%d", bt.b, bt.k0, bt.k0 + bt.rows, (unsigned long long)bt.e0, (unsigned long long)bt.e1, c->sl.slots, (int)p.pm);
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     // rows for k_pairs_blk (launch_pairs): dense, hundreds of pairs each, probe form with tag words and a filter
-    const bool blk_rows = !p.pm && !r.rs && c->gs.tab.kmL && c->gs.tw_stride && !c->gs.join_mode && c->gs.fl_stride && bt.e1 > bt.e0 &&
+    const bool blk_rows = !p.pm && !r.rs && c->gs.tab.kmL && c->gs.lay.tw_stride && !c->gs.lay.join_mode && c->gs.lay.fl_stride && bt.e1 > bt.e0 &&
                           (bt.e1 - bt.e0) / bt.rows >= 128 && r.k.block_kernel.value_or(r.query_ids == nullptr);
     int rc = build_indexes(c, r.k, r.d_ref + bt.k0, bt.rows, blk_rows, !p.pm);
     if (rc) return rc;
@@ -1063,13 +777,13 @@ int finish_run(lzani_ctx* c, u64 n_pairs, const lzani_rtc::Kernel* rtc_k, const 
     lzani_timing& tm = c->run.tm;
     if (c->km_timed) {
         float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_km[0], c->ev_km[1]));
+        HIPCHK(c, c->km_span.elapsed(ms));
         tm.kmers_ms = ms;
     }
     tm.kmers_ms += c->join_ms_pending;
     c->join_ms_pending = 0;
     for (size_t b = 0; b + 1 < bstart.size(); ++b) {
-        hipEvent_t* ev = c->events.data() + (size_t)EV * b;
+        const DevEvent* ev = c->events.data() + (size_t)EV * b;
         float ms = 0;
         HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
         tm.index_ms += ms;
@@ -1128,9 +842,9 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
         HIPCHK(c, hipMemcpyAsync(d_q, query_ids, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
     }
     while (c->events.size() < (size_t)EV * n_batches) {       // read back after the one sync
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreate(&e));
-        c->events.push_back(e);
+        DevEvent e;
+        HIPCHK(c, e.create());
+        c->events.push_back(std::move(e));
     }
     const u32 max_blocks = (u32)c->n_cus * k.blocks_per_cu;
     DevMem<unsigned long long> d_cbits;                      // join form: one candidate bitmap per resident wave
@@ -1183,8 +897,7 @@ int lzani_create(const lzani_params* p, int device_id, lzani_ctx** out)
 {
     if (!p || !out) return LZANI_ERR_ARG;
     *out = nullptr;
-    Params P{p->min_anchor_len, p->min_seed_len, p->max_dist_in_ref, p->max_dist_in_query,
-             p->min_region_len, p->approx_window, p->approx_mismatches, p->approx_run_len};
+    const Params P = params_of(*p);
     if (!params_supported(P)) return LZANI_ERR_PARAMS;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return LZANI_ERR_DEVICE;
@@ -1194,7 +907,6 @@ int lzani_create(const lzani_params* p, int device_id, lzani_ctx** out)
     c->dev = device_id;
     bool ok = hipSetDevice(device_id) == hipSuccess && hipStreamCreate(&c->stream) == hipSuccess &&
               c->d_cursor.alloc(NQUEUES) == hipSuccess;
-    if (ok) ok = hipEventCreate(&c->ev_km[0]) == hipSuccess && hipEventCreate(&c->ev_km[1]) == hipSuccess;
     if (ok) {
         hipDeviceProp_t prop;
         ok = hipGetDeviceProperties(&prop, device_id) == hipSuccess;
@@ -1211,8 +923,6 @@ void lzani_destroy(lzani_ctx* c)
     hipSetDevice(c->dev);
     comm_release(c);
     lzani_rtc::release(c->rtc);
-    for (auto& e : c->events) if (e) hipEventDestroy(e);
-    for (auto& e : c->ev_km) if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1248,104 +958,31 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     c->gs.dir_stride = ((u64)1 << c->gs.geo.dirbits) + 1;
     c->gs.ent_stride = (u64)c->gs.Tmax;
     c->gs.total_nm = total_nm;
-    c->gs.n_pending = n;
-    choose_index_form(c);
-    // Residency: the whole set in HBM (step (b) below, on every genome), or blocks of it kept on the host and uploaded by
+    const SetKnobs k{};
+    c->gs.lay = set_layout_of(c->P, c->gs.geo, c->gs.Tmax, n, k);
+    // Residency: the whole set in HBM (upload_genomes, on every genome), or blocks of it kept on the host and uploaded by
     // the runs (lzani_ooc.h).  Automatic mode (limit 0) keeps every set in-core that can be had in-core: its tables, the
     // staging copy and one index slab within the free memory.
-    {
-        const bool kmers = kmer_words_of(c->P);
-        u64 limit = c->mem_req;
-        if (!limit) {
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-            if (const char* fb = getenv("LZANI_FREE_BYTES")) free_b = std::min<size_t>(free_b, (size_t)strtoull(fb, nullptr, 10));   // tests: the automatic trigger
-            const u64 tables = total_nm * (16 + 8) + (kmers ? total_nm * 64 * 8 : 0);
-            const u64 per_slot = slot_bytes(c->gs).total();
-            if (tables + total_codes > free_b || tables + per_slot > free_b) limit = free_b / 2;     // (half for the genomes, half for slabs and bitmaps)
-        }
-        std::vector<u64> bytes;
-        std::string msg;
-        const int nb = plan_blocks_impl(n, len, c->P, limit, c->gs.blk_first, bytes, msg);
-        if (nb < 0) return fail(c, c->mem_req ? nb : LZANI_ERR_NOMEM, "lzani_set_genomes: " + msg);
-        if (nb > 1) {
-            c->gs.blk_bytes = bytes;
-            c->gs.mem_limit = limit;
-            return ooc_set_genomes(c, n, codes, len);
-        }
-        c->gs.mem_limit = c->mem_req;
-        c->res.peak = bytes[0];
-        c->gs.blk_first.clear();
+    u64 limit = c->mem_req;
+    if (!limit) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        if (k.free_bytes) free_b = std::min<size_t>(free_b, (size_t)*k.free_bytes);
+        limit = auto_genome_limit(genome_table_bytes(total_nm, kmer_words_of(c->P)), total_codes, slot_bytes(c->gs).total(), free_b);
     }
-
-    DevMem<uint8_t> d_codes;
-    DevMem<u64> d_codeoff;
-    HIPCHK(c, d_codes.alloc(total_codes));
-    HIPCHK(c, d_codeoff.alloc(n));
-    {
-        GenomeTables t;                                       // (moved into the set whole, or not at all)
-        HIPCHK(c, t.t2.alloc(total_nm * 2));
-        HIPCHK(c, t.nm.alloc(total_nm));
-        HIPCHK(c, t.nmoff.alloc(n));
-        HIPCHK(c, t.L.alloc(n));
-        HIPCHK(c, t.hasN.alloc(n));
-        HIPCHK(c, hipMemset(t.hasN, 0, (size_t)n * 4));
-        if (c->P.mal <= 15 && c->P.msl <= 15) {
-            HIPCHK(c, t.kmL.alloc(total_nm * 64));
-            HIPCHK(c, t.kmS.alloc(total_nm * 64));
-        }
-        c->gs.tab = std::move(t);
+    std::vector<u64> bytes;
+    std::string msg;
+    const int nb = plan_blocks_impl(n, len, c->P, limit, k, c->gs.blk_first, bytes, msg);
+    if (nb < 0) return fail(c, c->mem_req ? nb : LZANI_ERR_NOMEM, "lzani_set_genomes: " + msg);
+    if (nb > 1) {
+        c->gs.blk_bytes = bytes;
+        c->gs.mem_limit = limit;
+        return ooc_set_genomes(c, n, codes, len);
     }
-    // The caller's sequences are separate host buffers: they go up through two pinned 64 MB staging buffers, the
-    // copy of one overlapping the fill of the other (the 4 GB of config 5 take as long as the PCIe link needs).
-    {
-        const u64 chunk = 64ull << 20;
-        PinMem<uint8_t> pin[2];
-        hipEvent_t done[2] = {nullptr, nullptr};
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-            e = pin[k].alloc(chunk);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&done[k], hipEventDisableTiming);
-        }
-        u64 at = 0;                                               // codes staged so far
-        u32 g = 0; u64 goff = 0;                                  // next genome / offset inside it
-        for (int k = 0; e == hipSuccess && at < total_codes; k ^= 1) {
-            e = hipEventSynchronize(done[k]);                     // the previous copy out of this buffer (no-op the first time)
-            u64 fill = 0;
-            while (g < n && fill < chunk) {
-                const u64 take = std::min<u64>(chunk - fill, (u64)len[g] - goff);
-                if (take) memcpy(pin[k] + fill, codes[g] + goff, take);
-                fill += take; goff += take;
-                if (goff == len[g]) { ++g; goff = 0; }
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(d_codes.get() + at, pin[k], fill, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipEventRecord(done[k], c->stream);
-            at += fill;
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        for (int k = 0; k < 2; ++k) if (done[k]) hipEventDestroy(done[k]);
-        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE, std::string("staging the sequences: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemcpy(d_codeoff, codeoff.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->gs.tab.nmoff, c->gs.nmoff.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->gs.tab.L, c->gs.L.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    c->gs.n = n;
-    size_t maxblk = text_wordsN(c->gs.Tmax);
-    // gridDim.y is limited to 65535: pack in slices of genomes
-    for (u32 g0 = 0; g0 < n; g0 += 32768) {
-        u32 cnt = std::min<u32>(32768, n - g0);
-        hipLaunchKernelGGL(k_pack, dim3((u32)((maxblk + 127) / 128), cnt), dim3(128), 0, c->stream,
-                           d_codes.get(), d_codeoff.get() + g0, c->gs.tab.t2, c->gs.tab.nm, c->gs.tab.nmoff + g0, c->gs.tab.L + g0, c->gs.tab.hasN + g0, c->P.mrd, cnt);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    {
-        std::vector<int> hn(n);
-        HIPCHK(c, hipMemcpy(hn.data(), c->gs.tab.hasN, (size_t)n * 4, hipMemcpyDeviceToHost));
-        c->gs.all_nfree = std::all_of(hn.begin(), hn.end(), [](int v) { return v == 0; });
-    }
-    TRACE("set_genomes: n=%u Tmax=%d dirbits=%d posbits=%d tagmask=%x", n, c->gs.Tmax, c->gs.geo.dirbits, c->gs.geo.posbits, c->gs.geo.tagmask);
-    return LZANI_OK;
+    c->gs.mem_limit = c->mem_req;
+    c->res.peak = bytes[0];
+    c->gs.blk_first.clear();
+    return upload_genomes(c, n, codes, len, codeoff, total_codes);
 }
 
 int lzani_run_rows_device(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids, const uint64_t* row_off,
@@ -1429,12 +1066,12 @@ int lzani_get_layout(const lzani_ctx* c, lzani_layout_info* o)
     if (!c || !o) return LZANI_ERR_ARG;
     o->key_bits = c->gs.geo.kb; o->dir_bits = c->gs.geo.dirbits; o->pos_bits = c->gs.geo.posbits; o->tag_mask = c->gs.geo.tagmask;
     o->kmer_words = c->gs.tab.kmL != nullptr;
-    o->bucket_table = c->gs.bk_stride != 0; o->tag_words = c->gs.tw_stride != 0;
+    o->bucket_table = c->gs.lay.bk_stride != 0; o->tag_words = c->gs.lay.tw_stride != 0;
     o->n_free = c->gs.all_nfree;
     o->slots = c->sl.slots; o->batches_last_run = c->run.batches;
     o->bytes_per_slot = slot_bytes(c->gs).tables;           // (without the keys of the sort-based build)
-    o->bytes_genomes = c->gs.total_nm * (16 + 8) + (c->gs.tab.kmL ? c->gs.total_nm * 64 * 8 : 0);
-    o->join_lists = c->gs.join_mode; o->block_launches = c->run.blk_launches; o->bitmap_launches = c->run.pm_launches; o->rtc_launches = c->run.rtc_launches;
+    o->bytes_genomes = genome_table_bytes(c->gs.total_nm, c->gs.tab.kmL != nullptr);
+    o->join_lists = c->gs.lay.join_mode; o->block_launches = c->run.blk_launches; o->bitmap_launches = c->run.pm_launches; o->rtc_launches = c->run.rtc_launches;
     o->lpt_launches = c->run.lpt_launches; o->matrix_from_index = c->run.pmfi_launches;
     o->split_launches = c->run.split_launches; o->split_segments = c->run.split_items;
     return LZANI_OK;
@@ -1468,13 +1105,12 @@ int lzani_set_genome_memory(lzani_ctx* c, uint64_t bytes)
 int lzani_plan_blocks(uint32_t n, const uint32_t* len, const lzani_params* p, uint64_t limit, uint32_t* block_of)
 {
     if (!p || !len || !n) return LZANI_ERR_ARG;
-    Params P{p->min_anchor_len, p->min_seed_len, p->max_dist_in_ref, p->max_dist_in_query,
-             p->min_region_len, p->approx_window, p->approx_mismatches, p->approx_run_len};
+    const Params P = params_of(*p);
     if (!params_supported(P)) return LZANI_ERR_PARAMS;
     std::vector<u32> first;
     std::vector<u64> bytes;
     std::string msg;
-    const int nb = plan_blocks_impl(n, len, P, limit, first, bytes, msg);
+    const int nb = plan_blocks_impl(n, len, P, limit, SetKnobs{}, first, bytes, msg);
     if (nb > 0 && block_of)
         for (int b = 0; b < nb; ++b) std::fill(block_of + first[b], block_of + first[b + 1], (uint32_t)b);
     return nb;
@@ -1501,42 +1137,12 @@ const char* lzani_debug_kernel_name(uint32_t id)
 int64_t lzani_debug_rtc_compile(const lzani_params* p, int nfree, int cand, const char* arch, char* log, uint64_t log_cap)
 {
     if (!p || !arch || cand < 0 || cand > 2) return LZANI_ERR_ARG;
-    Params P{p->min_anchor_len, p->min_seed_len, p->max_dist_in_ref, p->max_dist_in_query,
-             p->min_region_len, p->approx_window, p->approx_mismatches, p->approx_run_len};
+    const Params P = params_of(*p);
     if (!params_supported(P) || P.mal > 15 || P.msl > 15) return LZANI_ERR_PARAMS;
     std::string lg;
     const size_t n = lzani_rtc::compile_only(P, nfree != 0, cand, arch, lg);
     if (log && log_cap) { snprintf(log, (size_t)log_cap, "%s", lg.c_str()); }
     return n ? (int64_t)n : (int64_t)LZANI_ERR_DEVICE;
-}
-
-int lzani_debug_get_index(lzani_ctx* c, uint32_t id, uint64_t* t2, uint64_t* nm, uint32_t* dirz,
-                          uint32_t* ent, uint32_t* n_ent, uint32_t* geom)
-{
-    if (!c) return LZANI_ERR_ARG;
-    if (!c->gs.n || id >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_debug_get_index: bad id");
-    if (c->gs.ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_get_index: the genome is not resident (out-of-core set)");
-    HIPCHK(c, hipSetDevice(c->dev));
-    int rc = ensure_slabs(c, 1);
-    if (rc) return rc;
-    DevMem<u32> d_ref;
-    HIPCHK(c, d_ref.alloc(1));
-    HIPCHK(c, hipMemcpy(d_ref.get(), &id, 4, hipMemcpyHostToDevice));
-    rc = build_indexes(c, Knobs{}, d_ref, 1);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int T = ref_text_len(c->gs.L[id], c->P.mrd);
-    size_t wn = text_wordsN(T);
-    if (nm) HIPCHK(c, hipMemcpy(nm, c->gs.tab.nm + c->gs.nmoff[id], wn * 8, hipMemcpyDeviceToHost));
-    if (t2) HIPCHK(c, hipMemcpy(t2, c->gs.tab.t2 + 2 * c->gs.nmoff[id], wn * 16, hipMemcpyDeviceToHost));
-    std::vector<u32> d(c->gs.dir_stride);
-    HIPCHK(c, hipMemcpy(d.data(), c->sl.d_dirz, c->gs.dir_stride * 4, hipMemcpyDeviceToHost));
-    u32 ne = d[c->gs.dir_stride - 1];
-    if (dirz) memcpy(dirz, d.data(), c->gs.dir_stride * 4);
-    if (ent && ne) HIPCHK(c, hipMemcpy(ent, c->sl.d_ent, (size_t)ne * 4, hipMemcpyDeviceToHost));
-    if (n_ent) *n_ent = ne;
-    if (geom) { geom[0] = c->gs.geo.kb; geom[1] = c->gs.geo.dirbits; geom[2] = c->gs.geo.posbits; geom[3] = c->gs.geo.tagmask; }
-    return LZANI_OK;
 }
 
 // Test hook: the engine's radix sort (lzani_sort.hip) on host keys -- n_seg segments of seg_len keys, each sorted on its own by
@@ -1556,46 +1162,6 @@ int lzani_debug_sort_segments(lzani_ctx* c, const uint64_t* keys, uint64_t* out,
     if (int rc = sort_keys(c, d_tmp, d_in.get(), d_out.get(), seg_len, n_seg, begin_bit, end_bit, "lzani_debug_sort_segments: sort", false)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out.get(), n * 8, hipMemcpyDeviceToHost));
-    return LZANI_OK;
-}
-
-// Test hook: the index slabs of one batch of `rows` reference ids, built by the run's own build_indexes into slots 0 .. rows-1.
-int lzani_debug_index_slab(lzani_ctx* c, uint32_t rows, const uint32_t* ref_ids, int with_filter, int with_tw,
-                           lzani_slab_info* info, uint32_t* dirz, uint32_t* ent, uint32_t* bk, uint32_t* tw, uint32_t* fl,
-                           uint32_t* status)
-{
-    if (!c) return LZANI_ERR_ARG;
-    if (!c->gs.n || !rows || !ref_ids || !info) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: bad arguments");
-    if (c->gs.ooc) return fail(c, LZANI_ERR_STATE, "lzani_debug_index_slab: the genomes are not resident (out-of-core set)");
-    for (u32 k = 0; k < rows; ++k)
-        if (ref_ids[k] >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: reference id out of range");
-    HIPCHK(c, hipSetDevice(c->dev));
-    int rc = ensure_slabs(c, rows);
-    if (rc) return rc;
-    if (c->sl.slots < rows) return fail(c, LZANI_ERR_ARG, "lzani_debug_index_slab: more rows than index slabs");
-    DevMem<u32> d_ref;
-    HIPCHK(c, d_ref.alloc(rows));
-    HIPCHK(c, hipMemcpy(d_ref.get(), ref_ids, (size_t)rows * 4, hipMemcpyHostToDevice));
-    rc = build_indexes(c, Knobs{}, d_ref, rows, with_filter != 0, with_tw != 0);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    info->key_bits = c->gs.geo.kb; info->dir_bits = c->gs.geo.dirbits; info->pos_bits = c->gs.geo.posbits; info->tag_mask = c->gs.geo.tagmask;
-    info->filter_mask = c->gs.fmask;
-    info->build = c->sl.index_build;
-    info->dir_stride = c->gs.dir_stride; info->ent_stride = c->gs.ent_stride; info->bk_stride = c->gs.bk_stride;
-    // (what this build wrote: the sort build leaves the tag words out without with_tw, every build the filter without with_filter)
-    info->tw_stride = (c->sl.index_build != LZANI_INDEX_BUILD_SORT || with_tw) ? c->gs.tw_stride : 0;
-    info->fl_stride = with_filter ? c->gs.fl_stride : 0;
-    const size_t r = rows;
-    if (dirz) HIPCHK(c, hipMemcpy(dirz, c->sl.d_dirz, r * c->gs.dir_stride * 4, hipMemcpyDeviceToHost));
-    if (ent) HIPCHK(c, hipMemcpy(ent, c->sl.d_ent, r * c->gs.ent_stride * 4, hipMemcpyDeviceToHost));
-    if (bk && info->bk_stride) HIPCHK(c, hipMemcpy(bk, c->sl.d_bk, r * info->bk_stride * 4, hipMemcpyDeviceToHost));
-    if (tw && info->tw_stride) HIPCHK(c, hipMemcpy(tw, c->sl.d_tw, r * info->tw_stride * 4, hipMemcpyDeviceToHost));
-    if (fl && info->fl_stride) HIPCHK(c, hipMemcpy(fl, c->sl.d_fl, r * info->fl_stride * 4, hipMemcpyDeviceToHost));
-    if (status) {
-        if (c->sl.index_build == LZANI_INDEX_BUILD_LDS) HIPCHK(c, hipMemcpy(status, c->sl.d_status, r * 4, hipMemcpyDeviceToHost));
-        else memset(status, 0, r * 4);
-    }
     return LZANI_OK;
 }
 

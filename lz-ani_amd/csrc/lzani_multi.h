@@ -38,7 +38,7 @@ struct lzani_group {
     std::vector<DevMem<lzani_result>> d_shard;    // [0] stays empty (the first device writes into d_all); [d] lives on device d
     DevMem<unsigned long long> d_tab;
     PinMem<char> h_stage[2];
-    hipEvent_t ev_stage[2] = {nullptr, nullptr}, ev_gather[2] = {nullptr, nullptr};   // (ev_gather: made with the group; gather_ms is from before the gather to after the scatter kernel)
+    DevEvent ev_stage[2], ev_gather[2];   // (ev_gather: made with the group; gather_ms is from before the gather to after the scatter kernel)
 };
 enum : size_t { GROUP_STAGE_BYTES = (size_t)32 << 20 };
 
@@ -199,7 +199,7 @@ int group_scatter_out(lzani_group* g, const GroupRun& r)
     // while the host moves the piece before it into the caller's (pageable) buffer
     for (int k = 0; k < 2; ++k) {
         if (!g->h_stage[k]) GHIPCHK(g, g->h_stage[k].alloc(GROUP_STAGE_BYTES));
-        if (!g->ev_stage[k]) GHIPCHK(g, hipEventCreateWithFlags(&g->ev_stage[k], hipEventDisableTiming));
+        if (!g->ev_stage[k]) GHIPCHK(g, g->ev_stage[k].create(hipEventDisableTiming));
     }
     const size_t total = (size_t)r.n_pairs * 12;
     size_t issued = 0, moved = 0, len[2] = {0, 0};
@@ -370,8 +370,8 @@ void lzani_group_destroy(lzani_group* g)
         if (g->d_shard[d]) { hipSetDevice(g->ctx[d]->dev); g->d_shard[d].reset(); }
     if (!g->ctx.empty()) hipSetDevice(g->ctx[0]->dev);
     g->d_all.reset(); g->d_final.reset(); g->d_tab.reset();         // (on the first device; the pinned buffers go with the group)
-    for (auto e : g->ev_stage) if (e) hipEventDestroy(e);
-    for (auto e : g->ev_gather) if (e) hipEventDestroy(e);
+    for (auto& e : g->ev_stage) e.reset();
+    for (auto& e : g->ev_gather) e.reset();
     for (auto cm : g->comms) if (cm) ncclCommDestroy(cm);
     for (auto c : g->ctx) lzani_destroy(c);
     delete g;
@@ -403,7 +403,7 @@ int lzani_group_create(const lzani_params* p, uint32_t n_devices, const int* dev
         g->ctx.push_back(c);
     }
     hipSetDevice(g->ctx[0]->dev);                               // (gather_ms is timed between two events of the first device)
-    for (auto& e : g->ev_gather) if (hipEventCreate(&e) != hipSuccess) { t_group_create_err = "hipEventCreate failed"; lzani_group_destroy(g); return LZANI_ERR_DEVICE; }
+    for (auto& e : g->ev_gather) if (e.create() != hipSuccess) { t_group_create_err = "hipEventCreate failed"; lzani_group_destroy(g); return LZANI_ERR_DEVICE; }
     std::vector<int> sorted(g->devs);
     std::sort(sorted.begin(), sorted.end());
     g->rehearsal = std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end();

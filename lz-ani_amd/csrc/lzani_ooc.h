@@ -1,5 +1,7 @@
-// lzani_ooc.h -- genome sets larger than the device: the block plan, block uploads and the tiled run.  Included by
-// lzani_hip.hip only, after run_rows_impl, which every tile calls unchanged.
+// lzani_ooc.h -- genome sets larger than the device: block uploads and the tiled run.  Included by lzani_hip.hip only,
+// after run_rows_impl, which every tile calls unchanged; of that file it uses lzani_ctx, check_rows, RunRecord, RegionSink,
+// fail, HIPCHK and TRACE, of lzani_index.h for_slices, pack_genomes and launch_kmers.  The block plan and the footprint
+// of a genome (plan_blocks_impl, ooc_genome_bytes) are lzani_set_plan.h.
 //
 // A set whose genome tables (packed texts, N masks, k-mer words, join lists) do not fit a genome-memory limit stays on
 // the host (1 B per base).  Its genomes are cut, in id order, into contiguous blocks of at most limit / 2 bytes of
@@ -36,57 +38,8 @@ __global__ void k_remap_regions(lzani_region* __restrict__ r, u64 n, const u64* 
     if (k < n) r[k].pair = pos[r[k].pair];
 }
 
-// Genome-table footprint of one genome: the bytes_genomes formula of lzani_get_layout (packed text 16 B + N mask 8 B
-// per word, k-mer words 2 x 4 B per text position) plus its join lists where they apply (8 B per forward position for
-// the sorted keys, 20 B of offsets and counts).
-u64 ooc_genome_bytes(int L, const Params& P, bool kmers, bool join)
-{
-    const u64 w = text_wordsN(ref_text_len(L, P.mrd));
-    return w * (16 + 8) + (kmers ? w * 64 * 8 : 0) + (join ? (u64)L * 8 + 20 : 0);
-}
-
-// The block plan (lzani_plan_blocks): genomes in id order into contiguous blocks of at most limit / 2 bytes each.
-// first[b] .. first[b + 1] are block b's genomes, bytes[b] its footprint.  limit 0: one block.  Returns the number of
-// blocks, or LZANI_ERR_ARG with the reason in msg.
-int plan_blocks_impl(u32 n, const u32* len, const Params& P, u64 limit, std::vector<u32>& first, std::vector<u64>& bytes,
-                     std::string& msg)
-{
-    if (!n || !len) { msg = "lzani_plan_blocks: empty input"; return LZANI_ERR_ARG; }
-    int Lmax = 0;
-    for (u32 g = 0; g < n; ++g) {
-        if (len[g] > 0x3FFFFFFFu - 3u * (u32)P.mrd) { msg = "sequence too long for 32-bit text positions"; return LZANI_ERR_ARG; }
-        Lmax = std::max(Lmax, (int)len[g]);
-    }
-    const int Tmax = ref_text_len(Lmax, P.mrd);
-    const IndexForm f = index_form_of(P, index_geometry(Tmax, P.mal), n);
-    const bool kmers = kmer_words_of(P);
-    u64 fmax = 0, total = 0;
-    for (u32 g = 0; g < n; ++g) {
-        const u64 b = ooc_genome_bytes((int)len[g], P, kmers, f.join_mode);
-        fmax = std::max(fmax, b);
-        total += b;
-    }
-    first.assign(1, 0);
-    bytes.clear();
-    if (limit == 0) { first.push_back(n); bytes.push_back(total); return 1; }
-    if (fmax > limit / 2) {
-        msg = "genome-memory limit of " + std::to_string(limit) + " bytes is below the minimum of " + std::to_string(2 * fmax) +
-              " bytes (each of the two resident halves must hold the largest genome's tables, " + std::to_string(fmax) + " bytes)";
-        return LZANI_ERR_ARG;
-    }
-    u64 cur = 0;
-    for (u32 g = 0; g < n; ++g) {
-        const u64 b = ooc_genome_bytes((int)len[g], P, kmers, f.join_mode);
-        if (g > first.back() && cur + b > limit / 2) { first.push_back(g); bytes.push_back(cur); cur = 0; }
-        cur += b;
-    }
-    first.push_back(n);
-    bytes.push_back(cur);
-    return (int)bytes.size();
-}
-
-// Step (b) of lzani_set_genomes for an out-of-core set: block b from the host copy into half h -- staging, k_pack and
-// k_kmers on the block's genomes only.  Timed into res_upload_ms.
+// The upload of an out-of-core set: block b from the host copy into half h -- staging, k_pack and k_kmers on the
+// block's genomes only (pack_genomes / launch_kmers of lzani_index.h, slice by slice).  Timed into res.upload_ms.
 int ooc_upload(lzani_ctx* c, u32 b, int h)
 {
     c->gs.half_block[h] = -1;                                     // (until the upload is complete)
@@ -101,32 +54,21 @@ int ooc_upload(lzani_ctx* c, u32 b, int h)
         Ls[g - g0] = c->gs.L[g];
         Lmax = std::max(Lmax, c->gs.L[g]);
     }
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIPCHK(c, hipEventCreate(&ev[0]));
-    hipError_t e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    if (e == hipSuccess && bases) e = hipMemcpyAsync(c->gs.d_stage, c->gs.h_codes.data() + c->gs.h_codeoff[g0], bases, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->gs.d_up_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->gs.d_up_L, Ls.data(), Ls.size() * 4, hipMemcpyHostToDevice, c->stream);
-    const int Tb = ref_text_len(Lmax, c->P.mrd);
-    const size_t maxblk = text_wordsN(Tb);
-    for (u32 k0 = 0; e == hipSuccess && k0 < cnt; k0 += 32768) {   // gridDim.y is limited to 65535
-        const u32 k = std::min<u32>(32768, cnt - k0);
-        hipLaunchKernelGGL(k_pack, dim3((u32)((maxblk + 127) / 128), k), dim3(128), 0, c->stream,
-                           c->gs.d_stage, c->gs.d_up_tab + k0, c->gs.tab.t2, c->gs.tab.nm, c->gs.d_up_tab + hg + k0, c->gs.d_up_L + k0, c->gs.d_up_L + hg + k0, c->P.mrd, k);
-        if (c->gs.tab.kmL) {
-            GenomeTab G{c->gs.tab.t2, c->gs.tab.nm, c->gs.d_up_tab + hg + k0, c->gs.d_up_L + k0, c->gs.tab.kmL, c->gs.tab.kmS, c->gs.d_up_L + hg + k0};
-            hipLaunchKernelGGL(k_kmers, dim3((Tb + 255) / 256, k), dim3(256), 0, c->stream, G, c->gs.tab.kmL, c->gs.tab.kmS, c->P.mal, c->P.msl, c->P.mrd, Tb);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);          // (also: tab and Ls leave scope)
+    StreamSpan span;
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    hipEventDestroy(ev[0]);
-    if (ev[1]) hipEventDestroy(ev[1]);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE, std::string("block upload: ") + hipGetErrorString(e));
+    HIPCHK(c, span.begin(c->stream));
+    if (bases) HIPCHK(c, hipMemcpyAsync(c->gs.d_stage, c->gs.h_codes.data() + c->gs.h_codeoff[g0], bases, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->gs.d_up_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->gs.d_up_L, Ls.data(), Ls.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const int Tb = ref_text_len(Lmax, c->P.mrd);
+    const GenomeTables& t = c->gs.tab;
+    for_slices(cnt, [&](u32 k0, u32 k) {
+        pack_genomes(c, c->gs.d_stage, c->gs.d_up_tab, t.t2, t.nm, c->gs.d_up_tab + hg, c->gs.d_up_L, c->gs.d_up_L + hg, Tb, k0, k);
+        if (t.kmL) launch_kmers(c, GenomeTab{t.t2, t.nm, c->gs.d_up_tab + hg, c->gs.d_up_L, t.kmL, t.kmS, c->gs.d_up_L + hg + k0}, Tb, k0, k);
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, span.end(c->stream));
+    HIPCHK(c, span.elapsed(ms));                                  // (also: tab and Ls leave scope)
     c->res.upload_ms += ms;
     c->res.uploads += 1;
     c->gs.half_block[h] = (int)b;
@@ -226,12 +168,12 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
                 HIPCHK(c, hipMemcpyAsync(d_pos.get(), t.pos.data(), tp * 8, hipMemcpyHostToDevice, c->stream));
             }
             HIPCHK(c, hipStreamSynchronize(c->stream));            // (Lloc moves into the context below)
-            if (c->gs.join_mode) c->gs.jl = JoinLists{};                   // (made again for this tile's table, if its form needs them)
+            if (c->gs.lay.join_mode) c->gs.jl = JoinLists{};                   // (made again for this tile's table, if its form needs them)
             int rc;
             {
                 LocalTable lt(c, Lloc);
                 rc = run_rows_impl(c, lrows, lref.data(), t.off.data(), lq.data(), (int*)d_res.get(), rs);
-                if (c->gs.join_mode) c->gs.jl = JoinLists{};
+                if (c->gs.lay.join_mode) c->gs.jl = JoinLists{};
             }
             if (rc) return rc;
             c->res.tiles += 1;
@@ -264,8 +206,8 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
     return LZANI_OK;
 }
 
-// lzani_set_genomes, step (b) deferred: an out-of-core set keeps a host copy of its codes and the device region of the
-// two halves; the blocks are uploaded by the runs.
+// lzani_set_genomes for a set that does not stay in-core: it keeps a host copy of its codes and the device region of
+// the two halves; the blocks are uploaded by the runs.
 int ooc_set_genomes(lzani_ctx* c, u32 n, const uint8_t* const* codes, const uint32_t* len)
 {
     const u32 nb = (u32)c->gs.blk_first.size() - 1;

@@ -1,7 +1,8 @@
 // lzani_prefilter.h -- host side of the k-mer prefilter: the slice plan, the pass plan, the pass / tile driver and the
 // entry points (lzani_prefilter, _cross, _codes, _codes_cross, the fetch and the info calls).  Included by lzani_hip.hip
-// only, after lzani_ooc.h; of that file it uses lzani_ctx (which holds the Prefilter), fail, HIPCHK, gtab, env_u64 and
-// sort_keys.  The kernels are lzani_kernels_prefilter.h, the sort is lzani_sort.hip's.
+// only, after lzani_ooc.h; of that file it uses lzani_ctx (which holds the Prefilter), fail, HIPCHK and sort_keys, of
+// lzani_index.h gtab and for_slices, of lzani_set_plan.h env_u64, of lzani_devmem.h DevEvent.  The kernels are
+// lzani_kernels_prefilter.h, the sort is lzani_sort.hip's.
 //
 // The stage computes, for every pair of genomes, how many sampled canonical k-mers they share, and keeps the pairs
 // above the thresholds as CSR rows.  The cross form (n_ref > 0) does so for the n_ref reference rows against the
@@ -42,19 +43,16 @@ enum { PF_ST_KEYS = 0, PF_ST_SORT = 1, PF_ST_COUNT = 2, PF_ST_COMPACT = 3, PF_ST
 constexpr u64 PF_MAX_PASS_WINDOWS = 0xFFFFFFEFull;       // what one pass may hold: the u32 run offsets of its postings, and lzani_sort_keys' limit
 struct PfClock {
     hipStream_t stream;
-    std::vector<hipEvent_t> ev;           // begin, end, begin, end, ...
+    std::vector<DevEvent> ev;             // begin, end, begin, end, ...
     std::vector<int> stage;
     explicit PfClock(hipStream_t s) : stream(s) {}
-    PfClock(const PfClock&) = delete;
-    PfClock& operator=(const PfClock&) = delete;
-    ~PfClock() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
     hipError_t mark()
     {
-        hipEvent_t e = nullptr;
-        hipError_t rc = hipEventCreate(&e);
+        DevEvent e;
+        const hipError_t rc = e.create();
         if (rc != hipSuccess) return rc;
-        ev.push_back(e);
-        return hipEventRecord(e, stream);
+        ev.push_back(std::move(e));
+        return hipEventRecord(ev.back(), stream);
     }
     hipError_t begin(int st) { stage.push_back(st); return mark(); }
     hipError_t end() { return mark(); }
@@ -207,7 +205,7 @@ struct PfRun {
     // One key sweep: pass p's windows of all genomes in `mode` (PF_HIST: out is the histogram; PF_RANK: the dictionary is
     // in ka).  A sweep goes over runs of genomes.  Resident: one run, all genomes.  Streamed: a run per slice, the slices in
     // the sweep's direction (the sweeps alternate: up, down, up, ...), each copied unless the buffer holds it.  A run is
-    // launched in groups of genomes (gridDim.y is limited to 65535); the two sources differ in the kernel and its arguments.
+    // launched in slices of genomes (for_slices); the two sources differ in the kernel and its arguments.
     int keys(int mode, const PfPass& p, unsigned long long* out)
     {
         const unsigned long long* dict = mode == PF_RANK ? w.ka.get() : nullptr;
@@ -222,8 +220,8 @@ struct PfRun {
             for (u32 g = f; g < f + ns; ++g) lmax = std::max(lmax, len_of(g));
             const u32 gx = (u32)((lmax + PF_CHUNK - 1) / PF_CHUNK);
             HIPCHK(c, clk.begin(mode == PF_HIST ? PF_ST_HIST : PF_ST_KEYS));
-            for (u32 y0 = 0; gx && y0 < ns; y0 += 32768) {
-                const dim3 gd(gx, std::min<u32>(32768, ns - y0));
+            if (gx) for_slices(ns, [&](u32 y0, u32 cnt) {
+                const dim3 gd(gx, cnt);
                 if (st)
                     hipLaunchKernelGGL(pf_keys_codes_kernel[mode][p.ranged], gd, dim3(PF_THREADS), 0, c->stream, (const unsigned char*)st->stage.get(), st->bytes[s],
                                        (const u64*)(st->d_off.get() + f), (const u32*)(st->d_len.get() + f), w.cbase.get(), f, y0, k, sample_max, p.lo, p.hi,
@@ -231,7 +229,7 @@ struct PfRun {
                 else
                     hipLaunchKernelGGL(pf_keys_kernel[mode][p.ranged], gd, dim3(PF_THREADS), 0, c->stream, G, w.cbase.get(), y0, k, c->P.mrd, sample_max, p.lo, p.hi,
                                        w.blkcnt.get(), w.blkoff.get(), dict, D, out);
-            }
+            });
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, clk.end());
         }

@@ -1,4 +1,4 @@
-"""Plain-Python statements of the out-of-core rules (lz-ani_amd/csrc/lzani_ooc.h): the genome-table footprint of a genome,
+"""Plain-Python statements of the out-of-core rules (lz-ani_amd/csrc/lzani_set_plan.h, lzani_ooc.h): the genome-table footprint of a genome,
 the block plan (lzani_plan_blocks) and the tile schedule of a run (what lzani_get_residency counts)."""
 import numpy as np
 
@@ -10,7 +10,7 @@ def _clog2(x):
 
 
 def join_lists(lens, prm):
-    """lzani_hip.hip index_form_of, without environment overrides: the join form of candidate detection."""
+    """lzani_set_plan.h set_layout_of, without environment overrides: the join form of candidate detection."""
     p = U.full_params(prm)
     f = U.index_form([range(int(L)) for L in lens], p)
     tw = f["tag_words"]

@@ -41,6 +41,8 @@ def _set(name):
         seqs = U._put_n_runs(SG.make_set(9, 613, lmin=2300, lmax=3000, fam=3)[1]) + [_rand(st, 3)]
     elif name == "hashed":       # mal 15 on 20-70 kbp: a matrix of fewer rows than k-mers
         seqs = SG.make_set(10, 614, lmin=20000, lmax=70000, fam=5)[1]
+    elif name == "three":        # the index hooks, the timing and the event tests: random, no N
+        seqs = [_rand(st, 300), _rand(st, 2000), _rand(st, 9000)]
     elif name == "tiny530":      # 530 genomes of 250-600 bp (mal 9: exact matrix made from the index, groups of 512)
         base = SG.make_set(530, 615, lmin=250, lmax=600, fam=10)[1]
         seqs = [s.copy() for s in base]
@@ -129,6 +131,69 @@ def test_index_slabs_match_statement(monkeypatch, case):
     got = eng.all2all()
     eng.close()
     assert np.array_equal(got, _oracle(name, None if tup is None else U.EDGE_TUPLES[tup]))
+
+
+def _buckets_equal(dirz, ent_a, ent_b, what):
+    """Two entry arrays of one directory, bucket by bucket: exactly where a bucket has at most 32 entries (the builds sort
+    those), as sorted arrays beyond (fill order).  Returns the share of buckets beyond 32."""
+    cnt = np.diff(dirz.astype(np.int64))
+    bucket = np.repeat(np.arange(len(cnt)), cnt)
+    small = cnt[bucket] <= 32
+    assert np.array_equal(ent_a[small], ent_b[small]), f"{what}: entries of sorted buckets differ"
+    assert np.array_equal(ent_a[np.lexsort((ent_a, bucket))], ent_b[np.lexsort((ent_b, bucket))]), f"{what}: large buckets differ"
+    return float((cnt > 32).mean())
+
+
+@pytest.mark.parametrize("build, env", [("lds", {}), ("atomics", {"LZANI_NO_LDS_INDEX": "1"}), ("sort", {"LZANI_SORT_INDEX_MIN_DIRBITS": "0"})])
+def test_the_two_index_hooks_agree(monkeypatch, build, env):
+    """lzani_debug_get_index is the one-row case of lzani_debug_index_slab: for every genome, geometry, directory, entry
+    count and entries equal slot 0 of the slab of that one reference, on each of the three index builds."""
+    seqs = _set("three")
+    eng = _engine(monkeypatch, env, None, seqs)          # (the sort switch is read by set_genomes)
+    for g in range(len(seqs)):
+        a = eng.debug_index(g)
+        s = eng.debug_index_slab([g])
+        assert s["build"] == build, s["build"]
+        assert a["geom"].tolist() == [s["key_bits"], s["dir_bits"], s["pos_bits"], s["tag_mask"]]
+        assert np.array_equal(a["dirz"], s["dirz"][0])
+        n_ent = int(a["dirz"][-1])
+        assert n_ent == len(a["ent"]) == int(s["dirz"][0][-1]) and n_ent > 0
+        large = _buckets_equal(a["dirz"], a["ent"], s["ent"][0][:n_ent], f"genome {g}, {build}")
+        assert large < 0.01, large                       # (the exact comparison is what runs)
+    eng.close()
+
+
+def test_kmer_words_are_timed_once_per_genome_set(monkeypatch):
+    """kmers_ms: the first run after set_genomes makes the k-mer words and reports their time, the second finds them; a
+    new set_genomes starts over.  (tests/test_gpu_parity.py prints kmers_ms and asserts nothing about it.)"""
+    seqs = _set("three")
+    eng = _engine(monkeypatch, {}, None, seqs)
+    first = eng.all2all()
+    assert eng.timing()["kmers_ms"] > 0
+    second = eng.all2all()
+    assert eng.timing()["kmers_ms"] == 0
+    assert np.array_equal(first, second) and np.array_equal(first, _oracle("three", None))
+    eng.set_genomes(seqs)
+    third = eng.all2all()
+    assert eng.timing()["kmers_ms"] > 0
+    assert np.array_equal(third, first)
+    eng.close()
+
+
+def test_batch_events_grow_and_are_used_again(monkeypatch):
+    """The context's per-batch events: a run of three batches (LZANI_MAX_SLOTS=1: a slab slot, so a row a batch) makes them,
+    a run of one batch on the same context uses the first of them again, close() releases them."""
+    seqs = _set("three")
+    eng = _engine(monkeypatch, {"LZANI_MAX_SLOTS": "1"}, None, seqs)
+    got = eng.all2all()
+    assert eng.layout()["batches_last_run"] == len(seqs) and eng.layout()["slots"] == 1
+    assert np.array_equal(got, _oracle("three", None))
+    monkeypatch.delenv("LZANI_MAX_SLOTS")
+    eng.set_genomes(seqs)
+    got = eng.all2all()
+    assert eng.layout()["batches_last_run"] == 1 and eng.layout()["slots"] == len(seqs)
+    assert np.array_equal(got, _oracle("three", None))
+    eng.close()
 
 
 # ---- candidate bitmaps -----------------------------------------------------------------------------------------------

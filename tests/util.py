@@ -355,7 +355,7 @@ def fuzz_case(st):
 # ---- the LZ parameter envelope at its edges ---------------------------------------------------
 # Plain-Python restatements of the C predicates that decide which form of the pair path a tuple takes, written from the C
 # source (not generated from it), so that the tests can predict the form and check that it ran.
-FAST_MAX_K = 15                                       # per-genome k-mer words exist for mal, msl <= 15 (lzani_hip.hip)
+FAST_MAX_K = 15                                       # per-genome k-mer words exist for mal, msl <= 15 (lzani_set_plan.h)
 AOT_SETS = {"defaults": dict(DEFAULTS), "long": dict(DEFAULTS, mal=15, msl=9, reg=60)}     # folded in ahead of time (DEFP 1, 2)
 
 
@@ -387,9 +387,11 @@ def is_aot(prm):
     return full_params(prm) in AOT_SETS.values()
 
 
-def index_form(seqs, prm):
-    """The anchor index of this genome set without environment overrides (lzani_layout.h: index_geometry; lzani_hip.hip:
-    choose_index_form): exact tags (the stored tag identifies the k-mer), a bucket table, tag words."""
+def index_form(seqs, prm, join=False):
+    """The anchor index of this genome set without environment overrides (lzani_layout.h: index_geometry; lzani_set_plan.h:
+    set_layout_of): exact tags (the stored tag identifies the k-mer), a bucket table, tag words; whether the index is built
+    by sorting, the presence filter and the most slabs a batch may take.  join: the set takes the join form of candidate
+    detection (ooc_model.join_lists), which has no filter."""
     p = full_params(prm)
     T = 2 * max([len(s) for s in seqs] + [0]) + 3 * p["mrd"]
     clog2 = lambda x: (int(x) - 1).bit_length()           # smallest b with 2^b >= x (x >= 1)
@@ -398,7 +400,17 @@ def index_form(seqs, prm):
     tagbits = min(kb - dirbits, 32 - posbits)
     exact = tagbits == kb - dirbits
     bk = is_fast(p) and exact and dirbits <= 26 and tagbits + posbits <= 30
-    return dict(exact=exact, bucket_table=bk, tag_words=bk and tagbits <= 7, T=T, key_bits=kb, dir_bits=dirbits, pos_bits=posbits)
+    tw = bk and tagbits <= 7
+    # directories of 2^20 buckets and more are built by a radix sort of 64-bit keys: slot number, hash, position -- the slot
+    # number gets what hash and position leave, 16 bits at the most, and all ones is no slot
+    sort_build = is_fast(p) and dirbits >= 20 and kb + posbits <= 60
+    max_slots = min(65535, (1 << min(16, 64 - kb - posbits)) - 1) if sort_build else 65535     # 65535: gridDim.y
+    # presence filter (probe form with tag words): f = ceil(log2 T) + 1 bits of the hash, texts below 1,024 symbols counted as
+    # 1,024, 18 bits at the most (32 KB of LDS); no filter for texts beyond 2^18 symbols: one all-ones word, mask 31
+    tbits = clog2(max(T, 1024))
+    fbits = min(tbits + 1, 18) if tw and not join and tbits <= 18 else 0
+    return dict(exact=exact, bucket_table=bk, tag_words=tw, T=T, key_bits=kb, dir_bits=dirbits, pos_bits=posbits,
+                sort_build=sort_build, max_slots=max_slots, filter_bits=fbits, filter_mask=(1 << fbits) - 1 if fbits else 31)
 
 
 # One table of edge tuples, a name per row; every row keeps mqd <= mrd (see fuzz_case).  Each row changes one group of
