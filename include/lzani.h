@@ -208,6 +208,21 @@ int64_t lzani_debug_rtc_compile(const lzani_params *p, int nfree, int cand, cons
  * "rtc nfree=N cand=C". */
 int lzani_debug_kernel_launches(const lzani_ctx *ctx, uint64_t *counts, uint32_t cap);
 const char *lzani_debug_kernel_name(uint32_t id);
+/* Test hook: the repair loop of the split path (a pair scanned by several waves) in the context's last run, summed over
+ * its split batches.  A stitch that does not get through finds one void segment; before the give-up round
+ * (6 + S / 4 rounds, or LZANI_SPLIT_GIVE_UP) the void segment's cut is disabled and the segment that handed over to it is
+ * resumed; in the give-up round, or where nothing can be retried, every cut of the pair is disabled and its segment 0
+ * scans it whole. */
+typedef struct {
+    uint64_t pairs_cut;             /* pairs that were cut into segments (the others: scanned whole by their segment 0)    */
+    uint64_t rounds;                /* rounds of segments + stitch: the most of any batch                                  */
+    uint64_t resumed;               /* segments listed to resume                                                           */
+    uint64_t given_up;              /* pairs whose cuts were all disabled                                                  */
+    uint64_t voids[6];              /* void stitches by cause: 0 a look-back cut short, 1 kept by the segment / dropped by
+                                       the true scan, 2 the other way round, 3 the true floor above what the segment's
+                                       look-backs hold for, 4 kept on a guess and cut short, 5 a broken chain              */
+} lzani_split_stats;
+int lzani_debug_split_stats(const lzani_ctx *ctx, lzani_split_stats *stats);
 
 /* ---- K-mer prefilter: the filter rows without a kmer-db file --------------------------------------------
  * The reference takes its filtered rows from a text file written by kmer-db (CFilter::load_filter).  This stage makes

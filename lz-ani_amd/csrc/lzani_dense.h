@@ -257,7 +257,7 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
     sa.reg = c->P.reg; sa.last_round = 0;
     // which pairs to cut: the ones with many anchor candidates (related: a candidate at every other position; a chance
     // pair has one in a hundred and is scanned whole, by its segment 0 with the null chain at work) -- heaviest first
-    u32 items = 0;
+    u32 items = 0, n_heavy = 0;
     {
         std::vector<u32> cnt(npb);
         HIPCHK(c, hipMemcpyAsync(cnt.data(), cs.d_lpt_cnt, (size_t)npb * 4, hipMemcpyDeviceToHost, c->stream));
@@ -271,7 +271,6 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
         std::vector<unsigned char> heavy(npb, 0);
         std::vector<u32> all;
         all.reserve((size_t)npb * 2);
-        u32 n_heavy = 0;
         for (u32 k : order) if (cnt[k] >= thr) { heavy[k] = 1; ++n_heavy; for (u32 sg = 0; sg < S; ++sg) all.push_back(k * S + sg); }
         for (u32 k : order) if (cnt[k] < thr) all.push_back(k * S);
         items = (u32)all.size();
@@ -283,7 +282,10 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
     launch(sa, 0, npb * (S - 1));                           // the checkpoints
     u32* cur = cs.d_sp_work.get(); u32* nxt = cs.d_sp_next.get();
     auto t_round = std::chrono::steady_clock::now();
-    const int give_up = 6 + (int)S / 4;                      // (a chain of void segments costs a round each: more segments, more rounds allowed)
+    // (a chain of void segments costs a round each: more segments, more rounds allowed; LZANI_SPLIT_GIVE_UP: a diagnostic switch)
+    const int give_up = std::max(0, r.k.split_give_up.value_or(6 + (int)S / 4));
+    c->run.split_cut += n_heavy;
+    u32 last[12] = {0};
     for (int round = 0; round < give_up + 4 && items; ++round) {
         HIPCHK(c, hipMemsetAsync(cs.d_sp_cnt.get(), 0, 8, c->stream));     // tickets, next round's items (the finished pairs' count stays)
         sa.work = cur; sa.work_next = nxt;
@@ -294,6 +296,8 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
         HIPCHK(c, hipMemcpyAsync(cnt, cs.d_sp_cnt.get(), 48, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->run.split_items += items;
+        c->run.split_rounds = std::max(c->run.split_rounds, (u32)round + 1);
+        std::copy(cnt, cnt + 12, last);
         const auto t_now = std::chrono::steady_clock::now();
         TRACE("split: round %d ran %u segments in %.1f ms, %u pairs finished, %u segments to run again (void so far, by cause: look-back cut short %u, kept/dropped %u, dropped/kept %u, floor %u, guess %u, chain %u)",
               round, items, std::chrono::duration<double, std::milli>(t_now - t_round).count(), cnt[2], cnt[1], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]);
@@ -303,6 +307,9 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
         if (items == 0 && cnt[2] != npb) return fail(c, LZANI_ERR_DEVICE, "split pairs: the stitch left pairs behind");
     }
     if (items) return fail(c, LZANI_ERR_DEVICE, "split pairs: no end of rounds");
+    // (the stitch's counters run through the batch's rounds: the last round's copy is the batch's sum)
+    for (int k = 0; k < 6; ++k) c->run.split_void[k] += last[4 + k];
+    c->run.split_resumed += last[10]; c->run.split_given_up += last[11];
     return LZANI_OK;
 }
 

@@ -153,6 +153,10 @@ struct RunRecord {
     int blk_launches = 0, pm_launches = 0, lpt_launches = 0, rtc_launches = 0, pmfi_launches = 0, split_launches = 0;
     int pmc_launches = 0;         // k_pm_cand launches (a group of more than 32,768 queries takes several)
     u64 split_items = 0;
+    // the split's repair loop (lzani_debug_split_stats): pairs cut, the most rounds of a batch, items listed to resume, pairs
+    // given up (all cuts disabled, scanned whole by segment 0), void stitches by cause (lzani_core.h: split_stitch)
+    u64 split_cut = 0, split_resumed = 0, split_given_up = 0, split_void[6] = {};
+    u32 split_rounds = 0;
     u64 klaunch[PK_COUNT] = {};   // the launch record: launches per pair-kernel instantiation (PAIR_KERNELS)
 
     RunRecord& operator+=(const RunRecord& o)
@@ -163,6 +167,9 @@ struct RunRecord {
         batches += o.batches;
         blk_launches += o.blk_launches; pm_launches += o.pm_launches; lpt_launches += o.lpt_launches; pmfi_launches += o.pmfi_launches;
         split_launches += o.split_launches; split_items += o.split_items; rtc_launches += o.rtc_launches; pmc_launches += o.pmc_launches;
+        split_cut += o.split_cut; split_resumed += o.split_resumed; split_given_up += o.split_given_up;
+        split_rounds = std::max(split_rounds, o.split_rounds);
+        for (int x = 0; x < 6; ++x) split_void[x] += o.split_void[x];
         for (int x = 0; x < PK_COUNT; ++x) klaunch[x] += o.klaunch[x];
         return *this;
     }
@@ -419,6 +426,7 @@ struct Knobs {
     int split_seglen = env_int("LZANI_SPLIT_SEGLEN").value_or(0);           // > 0: the segment length instead
     bool split_all = !env_is("LZANI_SPLIT_ALL", '0');                       // 0: cut only the pairs with many candidates
     u32 split_thr = (u32)env_u64("LZANI_SPLIT_THR").value_or(0);             // ... or with this many
+    std::optional<int> split_give_up = env_int("LZANI_SPLIT_GIVE_UP");       // rounds before a pair's cuts are given up (empty: 6 + S / 4)
     bool lds_index = !env_is("LZANI_NO_LDS_INDEX", '1');
     int lds_index_max_dirbits = env_int("LZANI_LDS_INDEX_MAX_DIRBITS").value_or(19);
 };
@@ -1093,6 +1101,14 @@ int lzani_debug_kernel_launches(const lzani_ctx* c, uint64_t* counts, uint32_t c
     if (!c || (!counts && cap)) return LZANI_ERR_ARG;
     for (u32 i = 0; i < cap && i < (u32)PK_COUNT; ++i) counts[i] = c->run.klaunch[i];
     return (int)PK_COUNT;
+}
+
+int lzani_debug_split_stats(const lzani_ctx* c, lzani_split_stats* o)
+{
+    if (!c || !o) return LZANI_ERR_ARG;
+    o->pairs_cut = c->run.split_cut; o->rounds = c->run.split_rounds; o->resumed = c->run.split_resumed; o->given_up = c->run.split_given_up;
+    for (int k = 0; k < 6; ++k) o->voids[k] = c->run.split_void[k];
+    return LZANI_OK;
 }
 
 int lzani_set_genome_memory(lzani_ctx* c, uint64_t bytes)

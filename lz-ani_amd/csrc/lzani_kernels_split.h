@@ -31,7 +31,7 @@ struct SplitArgs {
     const u32* work;             // this launch's items: p * S + segment (checkpoints: every (p, cut >= 1), no list)
     u32 n_work;
     u32* work_next;              // the stitch's: segments to run again
-    u32* counters;               // [0] tickets of the running launch, [1] items in work_next, [2] pairs finished, [4..11] void segments by cause
+    u32* counters;               // [0] tickets of the running launch, [1] items in work_next, [2] pairs finished, [4..9] void segments by cause, [10] items listed to resume, [11] pairs given up
     unsigned char* done;         // per pair: stitched and stored
     int reg;
     int last_round;              // the stitch: a pair that still does not get through has all its cuts disabled and segment 0 listed
@@ -140,7 +140,8 @@ __global__ void __launch_bounds__(256) k_split_stitch(SplitArgs a)
         if (at < 0 || from < 0 || a.last_round) {          // nothing to retry (or out of rounds): segment 0 scans the pair whole
             for (u32 k = 1; k < a.S; ++k) cuts[k].i = -1;
             item = p * a.S;
-        } else { cuts[at].i = -1; item = (p * a.S + (u32)from) | 0x80000000u; }     // (bit 31: resume, see split_body)
+            atomicAdd(&a.counters[11], 1u);
+        } else { cuts[at].i = -1; item = (p * a.S + (u32)from) | 0x80000000u; atomicAdd(&a.counters[10], 1u); }     // (bit 31: resume, see split_body)
         a.work_next[atomicAdd(&a.counters[1], 1u)] = item;
     }
 }

@@ -31,7 +31,7 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_row_costs", "lzani_partition_rows", "lzani_comm_unique_id", "lzani_comm_init", "lzani_comm_allgather",
            "lzani_comm_gatherv", "lzani_group_create", "lzani_group_destroy", "lzani_group_last_error",
            "lzani_group_set_genomes", "lzani_group_run_rows", "lzani_group_get_timing", "lzani_plan_gather", "lzani_get_rtc_info", "lzani_debug_rtc_compile",
-           "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name",
+           "lzani_debug_sort_segments", "lzani_debug_kernel_launches", "lzani_debug_kernel_name", "lzani_debug_split_stats",
            "lzani_set_genome_memory", "lzani_plan_blocks", "lzani_get_residency", "lzani_group_set_genome_memory",
            "lzani_group_get_residency", "lzani_debug_index_slab", "lzani_debug_run_candidates",
            "lzani_prefilter", "lzani_prefilter_fetch", "lzani_get_prefilter_info",
@@ -64,6 +64,11 @@ class LayoutInfo(C.Structure):
 class RtcInfo(C.Structure):
     _fields_ = [("folded_ahead_of_time", C.c_int32), ("null_chain", C.c_int32), ("kernels_built", C.c_int32),
                 ("kernels_from_cache", C.c_int32), ("kernels_failed", C.c_int32), ("reserved_", C.c_int32), ("build_ms", C.c_double)]
+
+
+class SplitStats(C.Structure):
+    _fields_ = [("pairs_cut", C.c_uint64), ("rounds", C.c_uint64), ("resumed", C.c_uint64), ("given_up", C.c_uint64),
+                ("voids", C.c_uint64 * 6)]
 
 
 class SlabInfo(C.Structure):
@@ -162,6 +167,7 @@ def load_library():
         lib.lzani_debug_kernel_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         lib.lzani_debug_kernel_name.argtypes = [C.c_uint32]
         lib.lzani_debug_kernel_name.restype = C.c_char_p
+        lib.lzani_debug_split_stats.argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_run_rows_regions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_uint64, C.c_void_p]
         lib.lzani_debug_get_index.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
@@ -664,6 +670,14 @@ class Engine:
             self._check(n, "lzani_debug_kernel_launches")
         assert n == len(names), (n, len(names))
         return {names[i]: int(counts[i]) for i in range(len(names)) if counts[i]}
+
+    def split_stats(self):
+        """lzani_debug_split_stats: the split path's repair loop in the last run -- pairs_cut, rounds (the most of a batch),
+        resumed, given_up and voids (a list by cause 0..5)."""
+        o = SplitStats()
+        self._check(self.lib.lzani_debug_split_stats(self.h, C.byref(o)), "lzani_debug_split_stats")
+        return dict(pairs_cut=int(o.pairs_cut), rounds=int(o.rounds), resumed=int(o.resumed), given_up=int(o.given_up),
+                    voids=[int(v) for v in o.voids])
 
     def debug_sort_segments(self, keys, seg_len, n_seg, begin_bit, end_bit):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)

@@ -240,6 +240,78 @@ int model_split_all2all(uint32_t n, const uint8_t* const* codes, const uint32_t*
     return 0;
 }
 
+// The device's round structure of the split (lzani_dense.h: run_split; lzani_kernels_split.h: split_body, k_split_stitch),
+// pair by pair: every pair has S cuts, a cut every `seglen` query positions (a cut at or behind the end of the scan has no
+// checkpoint); round 0 runs every segment of a cut pair (heavy[r * n + q] != 0; heavy == nullptr: every pair) and segment 0
+// alone of the others, every later round the one item the stitch listed.  The stitch of round k (last round: k >= give_up)
+// either gets through, or -- a void with at >= 0 and from >= 0 before the last round -- disables cuts[at] and lists
+// segment `from` to resume, or disables every cut and lists segment 0 to scan the pair whole (given up).  give_up < 0:
+// the device's own rule, 6 + S / 4.  A pair still unfinished after give_up + 4 rounds is the device's error "no end of
+// rounds": -2.  out as model_all2all; stats as lzani_split_stats: [0] pairs cut, [1] rounds (the most of a pair, which is
+// the most of a batch whatever the batches), [2] segments resumed, [3] pairs given up, [4..9] void stitches by cause (the
+// stitch's own `why`), and beyond the device's: [10] the most resumes of one pair, [11] pairs with a void stitch.
+int model_split_rounds(uint32_t n, const uint8_t* const* codes, const uint32_t* len, const int32_t* p8, int32_t seglen, int32_t S, int32_t give_up,
+                       const uint8_t* heavy, int32_t* out, int64_t* stats)
+{
+    Params P{p8[0], p8[1], p8[2], p8[3], p8[4], p8[5], p8[6], p8[7]};
+    if (!params_supported(P) || seglen < 1 || S < 2) return -1;
+    uint32_t maxL = 0;
+    for (uint32_t i = 0; i < n; ++i) maxL = std::max(maxL, len[i]);
+    IndexGeom geo = index_geometry(ref_text_len((int)maxL, P.mrd), P.mal);
+    std::vector<Genome> G(n);
+    for (uint32_t i = 0; i < n; ++i) { pack_genome(G[i], codes[i], (int)len[i], P); build_index(G[i], P, geo); }
+    for (int k = 0; k < 12; ++k) stats[k] = 0;
+    if (give_up < 0) give_up = 6 + S / 4;
+    for (uint32_t r = 0; r < n; ++r)
+        for (uint32_t q = 0; q < n; ++q) {
+            int32_t* o = out + ((size_t)r * n + q) * 3;
+            if (r == q) { o[0] = o[1] = o[2] = 0; continue; }
+            const int D = G[q].D, iend = D - P.msl;
+            const bool cut = !heavy || heavy[(size_t)r * n + q];
+            stats[0] += cut;
+            std::vector<SplitStart> cuts(S, SplitStart{-1, -1, -1, -1, -1, -1});      // (the device's memset of 0xFF)
+            std::vector<SplitOut> segs(S);
+            auto machine = [&](auto&& f) {
+                HostWave w{P, G[r].rview(), G[q].qview(), G[r].iv};
+                PairMachine<HostWave> m(w, P, G[r].T, D);
+                f(m);
+            };
+            for (int j = 1; j < S; ++j) {
+                cuts[j] = SplitStart{-1, 0, 0, 0, 0, 0};
+                if (j * seglen < iend && cut) machine([&](auto& m) { m.run_checkpoint(j * seglen, &cuts[j]); });
+            }
+            auto fresh = [&](int j) {
+                if (j > 0 && cuts[j].i < 0) { segs[j] = SplitOut{}; segs[j].first = 2; segs[j].stop = -1; segs[j].open_rs = -1; return; }
+                machine([&](auto& m) { m.run_segment(j, j ? &cuts[j] : nullptr, cuts.data(), S, &segs[j]); });
+            };
+            for (int j = 0; j < (cut ? S : 1); ++j) fresh(j);
+            int res[3] = {0, 0, 0};
+            int64_t resumes = 0;
+            bool done = false, any_void = false;
+            for (int round = 0; round < give_up + 4 && !done; ++round) {
+                stats[1] = std::max<int64_t>(stats[1], round + 1);
+                int at = -1, from = -1, why = 5;
+                if (split_stitch(cuts.data(), segs.data(), S, P.reg, res, &at, &from, &why)) { done = true; break; }
+                stats[4 + (why & 7)] += 1;
+                any_void = true;
+                if (at < 0 || from < 0 || round >= give_up) {
+                    for (int k = 1; k < S; ++k) cuts[k].i = -1;
+                    stats[3] += 1;
+                    fresh(0);
+                } else {
+                    cuts[at].i = -1;
+                    stats[2] += 1; ++resumes;
+                    machine([&](auto& m) { m.resume_segment(from, cuts.data(), S, &segs[from]); });
+                }
+            }
+            if (!done) return -2;
+            stats[10] = std::max(stats[10], resumes);
+            stats[11] += any_void;
+            o[0] = res[0]; o[1] = res[1]; o[2] = res[2];
+        }
+    return 0;
+}
+
 // The anchor-queue formulation of the device's find_event (queue_wave.h) on the host: out as model_all2all.
 int model_queue_all2all(uint32_t n, const uint8_t* const* codes, const uint32_t* len, const int32_t* p8, int32_t* out)
 {

@@ -26,7 +26,7 @@ NFREE_ROWS = ("mqd0_mrd0", "mqd63_mrd65", "aw2_am1_ar0", "aw15_am20_ar0", "mal7_
 ROWS = dict(U.EDGE_TUPLES, **{"aot_" + k: v for k, v in U.AOT_SETS.items()})
 SPLIT_SEGLEN = 1500
 FORM_ENV = ("LZANI_RTC", "LZANI_RTC_MIN_PAIRS", "LZANI_PM_MIN_ROWS", "LZANI_BLOCK_KERNEL", "LZANI_SPLIT", "LZANI_SPLIT_SEGLEN",
-            "LZANI_SPLIT_ALL", "LZANI_PM")
+            "LZANI_SPLIT_ALL", "LZANI_SPLIT_GIVE_UP", "LZANI_PM")
 
 
 @pytest.fixture(scope="module")

@@ -619,11 +619,13 @@ def test_matrix_from_index_and_longest_pair_first_forced(monkeypatch):
 
 
 def test_pairs_split_over_several_waves_forced(monkeypatch):
-    """Few, long pairs by several waves each (lzani_kernels_split.h: checkpoints, segments, stitch, void segments run again)
-    at sizes the oracle covers whole, forced by the environment with cuts every 1,500-6,000 query positions: related and
-    unrelated pairs, default and long-k-mer parameters (the hand-written loops inside the segments), genomes with N (the
-    generic instantiation's bounds), a run-time parameter tuple on the generic kernel.  Equal to the unsplit run and to
-    the oracle; the layout info says the pairs were split."""
+    """Few, long pairs by several waves each (lzani_kernels_split.h: checkpoints, segments, stitch) at sizes the oracle
+    covers whole, forced by the environment with cuts every 1,500-6,000 query positions: related and unrelated pairs,
+    default and long-k-mer parameters (the hand-written loops inside the segments), genomes with N (the generic
+    instantiation's bounds), a run-time parameter tuple on the generic kernel.  Equal to the unsplit run and to the
+    oracle; the layout info says the pairs were split and how many segments ran.  What it observes is the end result and
+    the segment count: on the host model these inputs have no void segment (the first three) or four of one cause (the
+    last), so the repair loop -- void segments, resumes, the give-up round -- is tests/test_gpu_split_repair.py's."""
     withn = [s.copy() for s in SG.make_set(20, 24, lmin=17000, lmax=21000, fam=5)[1]]
     for k in range(0, 20, 3):
         withn[k][400:400 + 9 + 2 * k] = 5

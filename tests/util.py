@@ -223,6 +223,39 @@ def model_split_all2all(seqs, params=None, seglen=1000):
     return out, stats
 
 
+SPLIT_STAT_FIELDS = ("pairs_cut", "rounds", "resumed", "given_up")      # then voids[6]: lzani_split_stats, Engine.split_stats()
+
+
+def model_split_rounds(seqs, params=None, seglen=512, S=None, give_up=-1, heavy=None):
+    """Every pair the way the device's split runs it (run_split + k_split_stitch: rounds of segments and stitches, a void
+    segment's cut disabled and the segment before it resumed, after give_up rounds every cut disabled and segment 0 run
+    fresh) through the host model: (results, stats), stats as Engine.split_stats() plus "max_resumes_of_a_pair" and
+    "pairs_with_void".
+    S: the cuts of every pair (default: split_plan's for this set); give_up < 0: the device's rule, 6 + S / 4;
+    heavy: bool[n, n], the pairs that are cut (default: all)."""
+    lib = model_lib()
+    p = full_params(params)
+    if S is None:
+        dmax = max(len(s) for s in seqs) + p["mrd"]
+        S, seglen = split_plan(len(seqs) * (len(seqs) - 1), (dmax + 320 + 1023) // 1024 * 32, dmax, {"LZANI_SPLIT": "1", "LZANI_SPLIT_SEGLEN": str(seglen)})
+    seqs, ptrs, lens = O._seq_table(seqs)
+    n = len(seqs)
+    out = np.zeros((n, n, 3), dtype=np.int32)
+    stats = np.zeros(12, dtype=np.int64)
+    hv = None if heavy is None else np.ascontiguousarray(heavy, dtype=np.uint8)
+    rc = lib.model_split_rounds(n, ptrs, O._ptr(lens), O.params_array(params), int(seglen), int(S), int(give_up),
+                                None if hv is None else O._ptr(hv), O._ptr(out), O._ptr(stats))
+    if rc == -2:
+        raise RuntimeError("model: no end of rounds")
+    if rc != 0:
+        raise ValueError("model: unsupported parameters")
+    st = {k: int(stats[i]) for i, k in enumerate(SPLIT_STAT_FIELDS)}
+    st["voids"] = [int(v) for v in stats[4:10]]
+    st["max_resumes_of_a_pair"] = int(stats[10])
+    st["pairs_with_void"] = int(stats[11])
+    return out, st
+
+
 def model_pair_regions(ref, qry, params=None):
     """(result triple, regions sorted like calc_regions) through the ALN instantiation of the model."""
     lib = model_lib()
@@ -536,6 +569,22 @@ def split_rule(n_pairs, cb_words, dmax, env=None, slots=WAVE_SLOTS):
     return -(-dmax // seglen) >= 2
 
 
+def split_plan(n_pairs, cb_words, dmax, env=None, slots=WAVE_SLOTS):
+    """(S, seglen) of a split batch -- the cuts of every pair and the query positions between two cuts -- restated from
+    lzani_run_plan.h (choose_split) as split_rule is; (0, 0) where the batch is not split."""
+    env = env or {}
+    if not split_rule(n_pairs, cb_words, dmax, env, slots):
+        return 0, 0
+    ceil_div = lambda a, b: -(-a // b)
+    S = min(max(2, int(env.get("LZANI_SPLIT_S", 64))), max(2, slots // n_pairs))
+    seglen = ceil_div(dmax, S)
+    if int(env.get("LZANI_SPLIT_SEGLEN", 0)) > 0:
+        seglen = int(env["LZANI_SPLIT_SEGLEN"])
+        S = min(64, max(2, ceil_div(dmax, seglen)))
+    seglen = max(seglen, 512)
+    return min(S, ceil_div(dmax, seglen)), seglen
+
+
 def predict_kernels(seqs, prm, env=None, form="all2all", pairs_per_row=None, n_rows=None, rtc_ready=False):
     """The names a run launches (lzani_hip.hip: run_rows_impl), from the genome set, the tuple, the environment (the
     LZANI_* switches that are set) and the call: form "all2all" (dense rows), "dup_lists" (query lists that name a
@@ -697,3 +746,131 @@ def instantiation_rows(cell, n):
     off = np.zeros(n + 1, np.uint64)
     off[1:] = np.cumsum([len(x) for x in lists])
     return ref_ids, off, np.array([q for x in lists for q in x], np.uint32)
+
+
+# ---- the split's repair loop: void segments, resumes, the give-up round -----------------------------------------
+# tools/split_void_search.py looks through seeded small sets for ones whose split run (cuts every 512 positions) has void
+# segments on the host model; tests/test_split_repair.py and tests/test_gpu_split_repair.py run its finds, listed in
+# SPLIT_REPAIR_TABLE as (class, seed) with the model's counts at the device's give-up rule.
+SPLIT_REPAIR_ENV = {"LZANI_RTC": "0", "LZANI_PM_MIN_ROWS": "1", "LZANI_SPLIT": "1", "LZANI_SPLIT_SEGLEN": "512", "LZANI_SPLIT_ALL": "1"}
+SPLIT_REPAIR_CLASSES = ("generic", "defaults", "long", "wide")
+SPLIT_REPAIR_DEFP = {"generic": 0, "wide": 0, "defaults": 1, "long": 2}        # the split kernels' defp
+
+
+def split_repair_case(cls, seed):
+    """(tuple, genomes) of one seeded case of the search: 2-4 genomes of 4-9 kbp, one family (an ancestor and mutated copies
+    at 8-28 % divergence; the generic and wide classes from 1 % on), in two cases out of five with an N run in one genome.
+    generic: a random tuple with mal, msl <= 15 and mqd <= mrd <= 64 that is neither of the two folded ahead of time; wide:
+    the same from fuzz_case's wider ranges (msl from 1, aw up to 64, am up to 20, ar up to 12, mrd and mqd from 0)."""
+    st = SG.Stream(0x5EED00000000 + 1000003 * SPLIT_REPAIR_CLASSES.index(cls) + seed)
+    n = st.randint(2, 4)
+    with_n = st.one() < 0.4
+    if cls == "wide":
+        while True:
+            msl = st.randint(1, 12)
+            mrd = st.randint(0, 64)
+            prm = dict(mal=st.randint(msl, min(15, msl + 8)), msl=msl, mrd=mrd, mqd=st.randint(0, min(mrd, 64)), reg=st.randint(1, 80),
+                       aw=st.randint(1, 64), am=st.randint(0, 20), ar=st.randint(0, 12))
+            if prm not in AOT_SETS.values():
+                break
+        dmin = 0.01
+    elif cls == "generic":
+        while True:
+            msl = st.randint(3, 12)
+            mrd = st.randint(8, 64)
+            prm = dict(mal=st.randint(max(msl, 6), 15), msl=msl, mrd=mrd, mqd=st.randint(4, min(mrd, 64)), reg=st.randint(10, 80),
+                       aw=st.randint(4, 40), am=st.randint(1, 12), ar=st.randint(1, 6))
+            if prm not in AOT_SETS.values():
+                break
+        dmin = 0.01
+    else:
+        prm = dict(AOT_SETS[cls])
+        dmin = 0.08
+    seqs = SG.make_set(n, 7919 * seed + 13, lmin=4000, lmax=9000, fam=n, dmin=dmin, dmax=0.28)[1]
+    if with_n:
+        g = st.randint(0, n - 1)
+        a = st.randint(0, len(seqs[g]) - 100)
+        seqs[g] = seqs[g].copy()
+        seqs[g][a:a + st.randint(1, 60)] = 5
+    return prm, [np.ascontiguousarray(s) for s in seqs]
+
+
+# What the search found (tools/split_void_search.py; the classes' seeds 0 .. 19,999, defaults 0 .. 9,999, long 0 .. 59,999):
+# per entry the model's counts at the device's give-up rule.  wide 85 and 675 run out of rounds by that rule: one pair each
+# is given up.
+SPLIT_REPAIR_TABLE = [
+    dict(cls='wide', seed=85, nfree=1, pairs_cut=12, rounds=11, resumed=21, given_up=1, voids=[12, 3, 0, 0, 7, 0], max_resumes_of_a_pair=9),
+    dict(cls='wide', seed=145, nfree=0, pairs_cut=6, rounds=2, resumed=2, given_up=0, voids=[1, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='wide', seed=675, nfree=0, pairs_cut=6, rounds=12, resumed=13, given_up=1, voids=[12, 1, 0, 0, 1, 0], max_resumes_of_a_pair=10),
+    dict(cls='wide', seed=974, nfree=0, pairs_cut=2, rounds=2, resumed=1, given_up=0, voids=[0, 0, 1, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='wide', seed=1698, nfree=0, pairs_cut=2, rounds=3, resumed=3, given_up=0, voids=[3, 0, 0, 0, 0, 0], max_resumes_of_a_pair=2),
+    dict(cls='wide', seed=2423, nfree=0, pairs_cut=12, rounds=2, resumed=5, given_up=0, voids=[0, 0, 0, 4, 1, 0], max_resumes_of_a_pair=1),
+    dict(cls='wide', seed=2937, nfree=1, pairs_cut=12, rounds=2, resumed=3, given_up=0, voids=[0, 1, 2, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='generic', seed=46, nfree=1, pairs_cut=12, rounds=5, resumed=18, given_up=0, voids=[0, 0, 0, 0, 18, 0], max_resumes_of_a_pair=4),
+    dict(cls='generic', seed=274, nfree=1, pairs_cut=12, rounds=4, resumed=8, given_up=0, voids=[0, 8, 0, 0, 0, 0], max_resumes_of_a_pair=3),
+    dict(cls='generic', seed=770, nfree=0, pairs_cut=12, rounds=5, resumed=13, given_up=0, voids=[0, 13, 0, 0, 0, 0], max_resumes_of_a_pair=4),
+    dict(cls='generic', seed=976, nfree=0, pairs_cut=12, rounds=7, resumed=18, given_up=0, voids=[0, 0, 0, 0, 18, 0], max_resumes_of_a_pair=6),
+    dict(cls='generic', seed=16419, nfree=1, pairs_cut=12, rounds=3, resumed=8, given_up=0, voids=[2, 5, 0, 1, 0, 0], max_resumes_of_a_pair=2),
+    dict(cls='generic', seed=18986, nfree=0, pairs_cut=2, rounds=2, resumed=1, given_up=0, voids=[0, 0, 1, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='defaults', seed=2134, nfree=0, pairs_cut=6, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='defaults', seed=2144, nfree=1, pairs_cut=12, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='defaults', seed=2272, nfree=1, pairs_cut=12, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='defaults', seed=2398, nfree=0, pairs_cut=6, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='defaults', seed=2562, nfree=1, pairs_cut=2, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='defaults', seed=3005, nfree=0, pairs_cut=6, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='long', seed=1343, nfree=1, pairs_cut=2, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='long', seed=1675, nfree=0, pairs_cut=12, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='long', seed=2439, nfree=0, pairs_cut=6, rounds=2, resumed=1, given_up=0, voids=[0, 1, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+    dict(cls='long', seed=3108, nfree=1, pairs_cut=6, rounds=2, resumed=2, given_up=0, voids=[0, 2, 0, 0, 0, 0], max_resumes_of_a_pair=1),
+]
+SPLIT_REPAIR_IDS = ["{}_{}".format(e["cls"], e["seed"]) for e in SPLIT_REPAIR_TABLE]
+# entries of four genomes whose voids all lie in the rows of one half of the references (two batches of two rows)
+SPLIT_REPAIR_ONE_BATCH = [("wide", 85), ("wide", 2937), ("defaults", 2144), ("long", 1675)]
+_split_repair_cache = {}
+
+
+def split_repair_base(cls, seed):
+    """(tuple, genomes, the oracle's results) of a case of the search, made once."""
+    key = (cls, seed)
+    if key not in _split_repair_cache:
+        prm, seqs = split_repair_case(cls, seed)
+        _split_repair_cache[key] = (prm, seqs, O.oracle_all2all(seqs, prm, threads=4))
+    return _split_repair_cache[key]
+
+
+def split_repair_model(cls, seed, give_up=-1):
+    """(results, stats) of the model's split run of a case at cuts every 512 positions, made once per give-up rule."""
+    key = (cls, seed, give_up)
+    if key not in _split_repair_cache:
+        prm, seqs, _ = split_repair_base(cls, seed)
+        _split_repair_cache[key] = model_split_rounds(seqs, prm, seglen=512, give_up=give_up)
+    return _split_repair_cache[key]
+
+
+def split_partial_case(form):
+    """A defaults case of the search with a stranger appended (shorter than the longest genome: the cuts and the index
+    geometry stay), for a run that cuts some pairs only: (tuple, genomes, candidate counts int[n, n], threshold, switches).
+    A pair is cut where its candidates -- the set bits of its bitmap, by the exact statement (index_model.plain_bitmap: the
+    matrix of the defaults' 11-mers is exact) -- reach the threshold.  form "thr": LZANI_SPLIT_THR, between the stranger's
+    pairs and the family's; form "all0": LZANI_SPLIT_ALL=0, whose threshold is the words of a pair's bitmap (a candidate at
+    one position in 32) whatever LZANI_SPLIT_THR says, which parts the family's pairs."""
+    import index_model as IM
+    key = ("partial", form)
+    if key not in _split_repair_cache:
+        prm, seqs, _ = split_repair_base("defaults", 2144)
+        st = SG.Stream(977)
+        seqs = list(seqs) + [(st.u64(min(len(s) for s in seqs) - 100) % np.uint64(4)).astype(np.uint8)]
+        n = len(seqs)
+        words = IM.cand_words(max(len(s) for s in seqs), prm["mrd"])
+        cnt = np.array([[int(IM.popcounts(IM.plain_bitmap(seqs[r], seqs[q], prm["mrd"], prm["mal"], words))) if r != q else 0
+                         for q in range(n)] for r in range(n)])
+        env = dict(SPLIT_REPAIR_ENV)
+        del env["LZANI_SPLIT_ALL"]
+        if form == "thr":
+            thr = 20
+            env["LZANI_SPLIT_THR"] = str(thr)
+        else:
+            thr = words
+            env.update(LZANI_SPLIT_ALL="0", LZANI_SPLIT_THR="20")
+        _split_repair_cache[key] = (prm, seqs, cnt, thr, env)
+    return _split_repair_cache[key]
