@@ -2,7 +2,7 @@
 // matrix of the batch's references (lzani_kernels_cand.h) instead of a probe per query position or a join per pair, and,
 // where a batch holds few, long pairs, those pairs by several waves each (lzani_kernels_split.h).  Included by
 // lzani_hip.hip only, between the run's types and its pair launch; of that file it uses lzani_ctx (which holds the
-// CandScratch), RunCtx / Batch / RunPlan / Knobs / RowFacts, fail, HIPCHK, TRACE, raise_lds and sort_keys, of
+// CandScratch), RunCtx / Batch / RunPlan / Knobs / RowFacts, fail, HIPCHK, TRACE, raise_lds, sort_keys and launch_row, of
 // lzani_index.h gtab, slot_bytes, ensure_slabs and for_slices.  The pure decisions -- the batches, the split / LPT rule,
 // the bytes of a slab slot -- are lzani_run_plan.h.
 // Host only: not among the sources a run-time compile embeds (lzani_rtc.h).
@@ -224,15 +224,14 @@ int candidate_stage(RunCtx& r, Batch& bt)
 }
 
 // Few, long pairs: several waves a pair (lzani_kernels_split.h) -- the checkpoints, then rounds of segments until the stitch
-// has every pair.  launch(sa, mode, items): k_split of the mode (launch_pairs picks the instantiation).
+// has every pair.  row: the mode-0 row of the batch's k_split in PAIR_KERNELS (choose_pair_kernel), mode 1 the row behind it.
 // The buffers are CandScratch's, grown here and kept: a batch of the same or a smaller size allocates nothing.  Where
 // their last use is ordered: everything that touches them -- the memsets below, the two uploads, k_split (cuts, heavy, its
 // work list, outs, the ticket counter), k_split_stitch (cuts, outs, done, the counters, the next round's list) -- is work of the context's one stream, and the last of it, the final round's stitch, lies before the
 // hipStreamSynchronize that ends that round (the host reads the counters there).  So the next batch's memsets are ordered
 // behind every earlier use by the stream alone, a buffer that has to grow is released by hipFree, which waits for the
 // device, and nothing outside this function reads them: the device-wide wait of the per-batch hipFree was not relied on.
-template <class Launch>
-int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
+int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, int row)
 {
     lzani_ctx* c = r.c;
     CandScratch& cs = c->cs;
@@ -255,6 +254,11 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
     sa.cuts = cs.d_sp_cuts.get(); sa.outs = cs.d_sp_outs.get(); sa.work = cs.d_sp_work.get(); sa.work_next = cs.d_sp_next.get();
     sa.counters = cs.d_sp_cnt.get(); sa.done = cs.d_sp_done.get(); sa.heavy = cs.d_sp_heavy.get();
     sa.reg = c->P.reg; sa.last_round = 0;
+    auto launch = [&](int mode, u32 items) {
+        sa.n_work = items;
+        void* kargs[] = {&sa};
+        return launch_row(c, row + mode, dim3((u32)std::min<u64>(((u64)items + 3) / 4, r.max_blocks)), dim3(256), kargs);
+    };
     // which pairs to cut: the ones with many anchor candidates (related: a candidate at every other position; a chance
     // pair has one in a hundred and is scanned whole, by its segment 0 with the null chain at work) -- heaviest first
     u32 items = 0, n_heavy = 0;
@@ -279,7 +283,7 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
         HIPCHK(c, hipStreamSynchronize(c->stream));            // (the vectors leave scope)
         TRACE("split: %u pairs, %u of them cut into %u segments (candidates >= %u)", npb, n_heavy, S, thr);
     }
-    launch(sa, 0, npb * (S - 1));                           // the checkpoints
+    HIPCHK(c, launch(0, npb * (S - 1)));                    // the checkpoints
     u32* cur = cs.d_sp_work.get(); u32* nxt = cs.d_sp_next.get();
     auto t_round = std::chrono::steady_clock::now();
     // (a chain of void segments costs a round each: more segments, more rounds allowed; LZANI_SPLIT_GIVE_UP: a diagnostic switch)
@@ -289,7 +293,7 @@ int run_split(RunCtx& r, const Batch& bt, const PairArgs& pa, Launch&& launch)
     for (int round = 0; round < give_up + 4 && items; ++round) {
         HIPCHK(c, hipMemsetAsync(cs.d_sp_cnt.get(), 0, 8, c->stream));     // tickets, next round's items (the finished pairs' count stays)
         sa.work = cur; sa.work_next = nxt;
-        launch(sa, 1, items);
+        HIPCHK(c, launch(1, items));
         sa.last_round = round >= give_up;
         hipLaunchKernelGGL(k_split_stitch, dim3((npb + 255) / 256), dim3(256), 0, c->stream, sa);
         u32 cnt[12] = {0};

@@ -8,7 +8,8 @@
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
-// (batches, queues, the split rule, the bytes of a slab slot) in lzani_run_plan.h, those of a genome set (the set-level
+// (batches, queues, the split rule, the bytes of a slab slot) in lzani_run_plan.h, which pair kernel a launch takes (the
+// table of the instantiations, choose_pair_kernel) in lzani_pair_dispatch.h, those of a genome set (the set-level
 // switches, the form of the index, footprints, the block plan, residency, the slot count of the slabs) in lzani_set_plan.h.
 // Device memory and events have one owner each, lzani_devmem.h.  Five layers of the host side are files of their own,
 // included at fixed places below:
@@ -27,7 +28,6 @@
 #include <new>
 #include <optional>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/lzani.h"
@@ -62,86 +62,13 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_rtc.h"
 #include "lzani_devmem.h"
 #include "lzani_run_plan.h"
+#include "lzani_pair_dispatch.h"
 #include "lzani_set_plan.h"
 
 // ============================================================================================
 // Host side of the C-ABI
 // ============================================================================================
 using namespace lzani;
-
-// Launch record: one entry per pair-kernel instantiation the dispatch of run_rows_impl can launch, counted per context
-// for the last run (lzani_debug_kernel_launches).  The names follow one grammar a test can build from the dispatch rules:
-//   pairs fast=F nfree=N defp=D aln=A bk=B cand=C   k_pairs<F, N, D, A, B, C>
-//   pairs_blk nfree=N defp=D                        k_pairs_blk<N, D>
-//   split nfree=N defp=D mode=M                     k_split<N, D, M>
-//   rtc nfree=N cand=C                              the run-time compiled kernel (lzani_rtc.h), DEFP 9
-// An instantiation added to the dispatch needs a row here (count_launch refuses to compile without one) and a cell in
-// tests/test_gpu_instantiations.py.
-enum PairKernelKind { PK_PAIRS, PK_BLK, PK_SPLIT, PK_RTC };
-struct PairKernelDesc { const char* name; int kind, fast, nfree, defp, aln, bk, cand, mode; };
-constexpr PairKernelDesc PAIR_KERNELS[] = {
-    {"pairs fast=0 nfree=0 defp=0 aln=1 bk=0 cand=0", PK_PAIRS, 0, 0, 0, 1, 0, 0, 0},
-    {"pairs fast=1 nfree=0 defp=0 aln=1 bk=1 cand=0", PK_PAIRS, 1, 0, 0, 1, 1, 0, 0},
-    {"pairs fast=1 nfree=0 defp=0 aln=1 bk=0 cand=0", PK_PAIRS, 1, 0, 0, 1, 0, 0, 0},
-    {"pairs fast=0 nfree=0 defp=0 aln=0 bk=0 cand=0", PK_PAIRS, 0, 0, 0, 0, 0, 0, 0},
-    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=1 cand=2", PK_PAIRS, 1, 0, 0, 0, 1, 2, 0},
-    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=1 cand=2", PK_PAIRS, 1, 0, 1, 0, 1, 2, 0},
-    {"pairs fast=1 nfree=0 defp=2 aln=0 bk=1 cand=2", PK_PAIRS, 1, 0, 2, 0, 1, 2, 0},
-    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=1 cand=2", PK_PAIRS, 1, 1, 0, 0, 1, 2, 0},
-    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=1 cand=2", PK_PAIRS, 1, 1, 1, 0, 1, 2, 0},
-    {"pairs fast=1 nfree=1 defp=2 aln=0 bk=1 cand=2", PK_PAIRS, 1, 1, 2, 0, 1, 2, 0},
-    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=1 cand=1", PK_PAIRS, 1, 0, 0, 0, 1, 1, 0},
-    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=1 cand=1", PK_PAIRS, 1, 0, 1, 0, 1, 1, 0},
-    {"pairs fast=1 nfree=0 defp=2 aln=0 bk=1 cand=1", PK_PAIRS, 1, 0, 2, 0, 1, 1, 0},
-    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=1 cand=1", PK_PAIRS, 1, 1, 0, 0, 1, 1, 0},
-    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=1 cand=1", PK_PAIRS, 1, 1, 1, 0, 1, 1, 0},
-    {"pairs fast=1 nfree=1 defp=2 aln=0 bk=1 cand=1", PK_PAIRS, 1, 1, 2, 0, 1, 1, 0},
-    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=1 cand=0", PK_PAIRS, 1, 0, 0, 0, 1, 0, 0},
-    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=1 cand=0", PK_PAIRS, 1, 0, 1, 0, 1, 0, 0},
-    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=1 cand=0", PK_PAIRS, 1, 1, 0, 0, 1, 0, 0},
-    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=1 cand=0", PK_PAIRS, 1, 1, 1, 0, 1, 0, 0},
-    {"pairs fast=1 nfree=0 defp=0 aln=0 bk=0 cand=0", PK_PAIRS, 1, 0, 0, 0, 0, 0, 0},
-    {"pairs fast=1 nfree=0 defp=1 aln=0 bk=0 cand=0", PK_PAIRS, 1, 0, 1, 0, 0, 0, 0},
-    {"pairs fast=1 nfree=1 defp=0 aln=0 bk=0 cand=0", PK_PAIRS, 1, 1, 0, 0, 0, 0, 0},
-    {"pairs fast=1 nfree=1 defp=1 aln=0 bk=0 cand=0", PK_PAIRS, 1, 1, 1, 0, 0, 0, 0},
-    {"pairs_blk nfree=0 defp=0", PK_BLK, 1, 0, 0, 0, 1, 0, 0},
-    {"pairs_blk nfree=0 defp=1", PK_BLK, 1, 0, 1, 0, 1, 0, 0},
-    {"pairs_blk nfree=1 defp=0", PK_BLK, 1, 1, 0, 0, 1, 0, 0},
-    {"pairs_blk nfree=1 defp=1", PK_BLK, 1, 1, 1, 0, 1, 0, 0},
-    {"split nfree=0 defp=0 mode=0", PK_SPLIT, 1, 0, 0, 0, 1, 2, 0},
-    {"split nfree=0 defp=0 mode=1", PK_SPLIT, 1, 0, 0, 0, 1, 2, 1},
-    {"split nfree=0 defp=1 mode=0", PK_SPLIT, 1, 0, 1, 0, 1, 2, 0},
-    {"split nfree=0 defp=1 mode=1", PK_SPLIT, 1, 0, 1, 0, 1, 2, 1},
-    {"split nfree=0 defp=2 mode=0", PK_SPLIT, 1, 0, 2, 0, 1, 2, 0},
-    {"split nfree=0 defp=2 mode=1", PK_SPLIT, 1, 0, 2, 0, 1, 2, 1},
-    {"split nfree=1 defp=0 mode=0", PK_SPLIT, 1, 1, 0, 0, 1, 2, 0},
-    {"split nfree=1 defp=0 mode=1", PK_SPLIT, 1, 1, 0, 0, 1, 2, 1},
-    {"split nfree=1 defp=1 mode=0", PK_SPLIT, 1, 1, 1, 0, 1, 2, 0},
-    {"split nfree=1 defp=1 mode=1", PK_SPLIT, 1, 1, 1, 0, 1, 2, 1},
-    {"split nfree=1 defp=2 mode=0", PK_SPLIT, 1, 1, 2, 0, 1, 2, 0},
-    {"split nfree=1 defp=2 mode=1", PK_SPLIT, 1, 1, 2, 0, 1, 2, 1},
-    {"rtc nfree=0 cand=0", PK_RTC, 1, 0, 9, 0, 1, 0, 0},
-    {"rtc nfree=0 cand=1", PK_RTC, 1, 0, 9, 0, 1, 1, 0},
-    {"rtc nfree=0 cand=2", PK_RTC, 1, 0, 9, 0, 1, 2, 0},
-    {"rtc nfree=1 cand=0", PK_RTC, 1, 1, 9, 0, 1, 0, 0},
-    {"rtc nfree=1 cand=1", PK_RTC, 1, 1, 9, 0, 1, 1, 0},
-    {"rtc nfree=1 cand=2", PK_RTC, 1, 1, 9, 0, 1, 2, 0},
-};
-constexpr int PK_COUNT = (int)(sizeof PAIR_KERNELS / sizeof PAIR_KERNELS[0]);
-// the row of an instantiation; -1 = none
-constexpr int pk_id(int kind, int fast, int nfree, int defp, int aln, int bk, int cand, int mode)
-{
-    for (int i = 0; i < PK_COUNT; ++i) {
-        const PairKernelDesc& d = PAIR_KERNELS[i];
-        if (d.kind == kind && d.fast == fast && d.nfree == nfree && d.defp == defp && d.aln == aln && d.bk == bk && d.cand == cand && d.mode == mode)
-            return i;
-    }
-    return -1;
-}
-// the rows of the run-time compiled kernel: PK_RTC_N0_C0 + 3 * nfree + cand
-constexpr int PK_RTC_N0_C0 = pk_id(PK_RTC, 1, 0, 9, 0, 1, 0, 0);
-static_assert(PK_RTC_N0_C0 >= 0 && pk_id(PK_RTC, 1, 0, 9, 0, 1, 2, 0) == PK_RTC_N0_C0 + 2 && pk_id(PK_RTC, 1, 1, 9, 0, 1, 0, 0) == PK_RTC_N0_C0 + 3 &&
-              pk_id(PK_RTC, 1, 1, 9, 0, 1, 2, 0) == PK_RTC_N0_C0 + 5, "the rtc rows of PAIR_KERNELS are out of order");
 
 // What the last run did (lzani_get_timing, lzani_get_layout, lzani_debug_kernel_launches): reset at its start; an
 // out-of-core run sums its tiles' records.
@@ -448,33 +375,26 @@ int defp_select(const Params& q)
     return (q.mal == 11 && q.msl == 7 && q.reg == 35) ? 1 : (q.mal == 15 && q.msl == 9 && q.reg == 60) ? 2 : 0;
 }
 
-// The pair kernels of one form for the run-time (nfree, dsel): f(NFREE, DEFP) with both as std::integral_constant.  The forms
-// with ND = 3 have an instantiation per dsel; those with ND = 2 none for the long-genome tuple, which runs their DEFP 0.
-template <int ND, class F>
-void with_nfree_defp(bool nf, int dsel, F&& f)
-{
-    auto by_defp = [&](auto N) {
-        if (dsel == 1) f(N, std::integral_constant<int, 1>{});
-        else if (dsel == 2) f(N, std::integral_constant<int, ND == 3 ? 2 : 0>{});
-        else f(N, std::integral_constant<int, 0>{});
-    };
-    if (nf) by_defp(std::true_type{}); else by_defp(std::false_type{});
-}
+// Launch record: launches per row of PAIR_KERNELS (lzani_pair_dispatch.h), counted per context for the last run
+// (lzani_debug_kernel_launches).  The kernels' host addresses in row order, from the lists the table is made of (the rows
+// of the run-time compiled kernel have none: its function belongs to a module, lzani_rtc.h).
+#define LZANI_PK_PAIRS_FN(F, N, D, A, B, C) reinterpret_cast<const void*>(k_pairs<F, N, D, A, B, C>),
+#define LZANI_PK_BLK_FN(N, D) reinterpret_cast<const void*>(k_pairs_blk<N, D>),
+#define LZANI_PK_SPLIT_FN(N, D, M) reinterpret_cast<const void*>(k_split<N, D, M>),
+#define LZANI_PK_RTC_FN(N, C) nullptr,
+const void* const PAIR_KERNEL_FN[PK_COUNT] = {
+    LZANI_PK_PAIRS_ROWS(LZANI_PK_PAIRS_FN) LZANI_PK_BLK_ROWS(LZANI_PK_BLK_FN) LZANI_PK_SPLIT_ROWS(LZANI_PK_SPLIT_FN)
+    LZANI_PK_RTC_ROWS(LZANI_PK_RTC_FN)
+};
 
-// One launch in the launch record; a launch of an instantiation without a row in PAIR_KERNELS does not compile.
-template <int KIND, int F, int N, int D, int A, int B, int C, int M = 0>
-void count_launch(RunRecord& r)
+// The one launch of a pair kernel, on the context's stream: the kernel of the row -- `rtc`: the module function of a
+// run-time compiled row -- and, where the launch was taken, its count in the launch record.
+hipError_t launch_row(lzani_ctx* c, int row, dim3 gd, dim3 bd, void** args, size_t lds = 0, hipFunction_t rtc = nullptr)
 {
-    constexpr int id = pk_id(KIND, F, N, D, A, B, C, M);
-    static_assert(id >= 0, "a pair kernel without a row in PAIR_KERNELS");
-    r.klaunch[id] += 1;
-}
-
-template <bool F, bool N, int D, bool A, bool B, int C>
-void launch_k_pairs(lzani_ctx* c, dim3 gd, dim3 bd, const PairArgs& pa)
-{
-    hipLaunchKernelGGL((k_pairs<F, N, D, A, B, C>), gd, bd, 0, c->stream, pa);
-    count_launch<PK_PAIRS, F, N, D, A, B, C>(c->run);
+    const hipError_t e = PAIR_KERNELS[row].kind == PK_RTC ? hipModuleLaunchKernel(rtc, gd.x, 1, 1, bd.x, 1, 1, 0, c->stream, args, nullptr)
+                                                          : hipLaunchKernel(PAIR_KERNEL_FN[row], gd, bd, args, lds, c->stream);
+    if (e == hipSuccess) c->run.klaunch[row] += 1;
+    return e;
 }
 
 // What a run's rows hold beyond their checks: the pairs and, for query lists, whether a row names a query twice and how
@@ -531,7 +451,7 @@ struct RunCtx {
     u32 max_blocks; int dsel;                                // the launch geometry, defp_select of the tuple
     unsigned long long* d_cbits;                             // join form: one candidate bitmap per resident wave
     u64 cbits_stride;
-    lzani_rtc::Kernel* rtc_k; int rtc_id;                    // the tuple's run-time compiled kernel, if any, and its row of the launch record
+    lzani_rtc::Kernel* rtc_k;                                // the tuple's run-time compiled kernel, if any
     std::vector<u32> grp_seen = {}; u32 grp_stamp = 0;       // (query lists + candidate bitmaps) the group a query was last seen in
     CandSink* sink = nullptr;                                // test hook only (lzani_debug_run_candidates)
 };
@@ -582,8 +502,8 @@ bool blk_fits(lzani_ctx* c, const void* kf)
     return c->gs.blk_fold >= 0;
 }
 
-// The batch's pair launch: the run's form picks the kernel, (nfree, dsel) its template arguments; a tuple compiled at run
-// time goes first where it has a kernel of the form.
+// The batch's pair launch: the arguments, the facts of the launch, its kernel (choose_pair_kernel); a tuple compiled at
+// run time goes first where the choice offers its kernel.
 int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, const DevEvent* ev)
 {
     lzani_ctx* c = r.c;
@@ -610,57 +530,41 @@ int launch_pairs(RunCtx& r, const Batch& bt, bool blk_rows, const DevEvent* ev)
     const u64 waves = bt.e1 - bt.e0;
     const dim3 gd((u32)std::min<u64>((waves + 3) / 4, r.max_blocks)), bd(256);
     HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    const bool fast = c->gs.tab.kmL != nullptr, tw = pa.tw != nullptr, nf = c->gs.all_nfree;
-    auto rtc_launch = [&]() -> bool {
-        if (!r.rtc_k) return false;
-        void* kargs[] = {&pa};
-        if (hipModuleLaunchKernel(r.rtc_k->fn, gd.x, 1, 1, bd.x, 1, 1, 0, c->stream, kargs, nullptr) != hipSuccess) { (void)hipGetLastError(); return false; }
-        c->run.rtc_launches += 1;
-        c->run.klaunch[r.rtc_id] += 1;
-        return true;
-    };
+    PairFacts f;
+    f.regions = r.rs != nullptr; f.fast = c->gs.tab.kmL != nullptr; f.tw = pa.tw != nullptr;
+    f.pm = r.p.pm; f.split = bt.split_S >= 2; f.join = pa.skeys != nullptr;
+    f.nfree = c->gs.all_nfree; f.dsel = r.dsel; f.rtc = r.rtc_k != nullptr;
     // Probe form, dense rows of hundreds of pairs: blocks of 16 waves with the reference's presence filter in LDS
     // (k_pairs_blk).  The rows a kmer-db filter leaves hold related pairs, where most positions pass the filter:
     // BASELINE configs[4] at full size is 6 % slower this way; LZANI_BLOCK_KERNEL=1/0 overrides.
-    const void* kf = nullptr;
-    with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) { kf = reinterpret_cast<const void*>(k_pairs_blk<N, D>); });
-    const bool use_blk = blk_rows && fast && tw && !pa.skeys && blk_fits(c, kf);
-    if (use_blk && !c->d_blkctr) HIPCHK(c, c->d_blkctr.alloc((size_t)c->n_cus * 2));
+    const void* kf = PAIR_KERNEL_FN[pair_blk_row(f.nfree, f.dsel)];
+    f.blk = blk_rows && f.fast && f.tw && !f.join && blk_fits(c, kf);
+    if (f.blk && !c->d_blkctr) HIPCHK(c, c->d_blkctr.alloc((size_t)c->n_cus * 2));
+    const PairChoice ch = choose_pair_kernel(f);
+    const PairKernelDesc& d = PAIR_KERNELS[ch.row];
     int rc = LZANI_OK;
-    if (r.rs) {                                   // alignment output: one generic instantiation per index form
-        if (!fast) launch_k_pairs<false, false, 0, true, false, 0>(c, gd, bd, pa);
-        else if (tw) launch_k_pairs<true, false, 0, true, true, 0>(c, gd, bd, pa);
-        else launch_k_pairs<true, false, 0, true, false, 0>(c, gd, bd, pa);
-    } else if (!fast) launch_k_pairs<false, false, 0, false, false, 0>(c, gd, bd, pa);
-    else if (r.p.pm && bt.split_S >= 2) {            // few, long pairs: several waves a pair
-        rc = run_split(r, bt, pa, [&](SplitArgs& sa, int mode, u32 items) {
-            const dim3 gs((u32)std::min<u64>(((u64)items + 3) / 4, r.max_blocks)), bs4(256);
-            sa.n_work = items;
-            with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) {
-                if (mode == 0) { hipLaunchKernelGGL((k_split<N, D, 0>), gs, bs4, 0, c->stream, sa); count_launch<PK_SPLIT, true, N, D, false, true, 2, 0>(c->run); }
-                else { hipLaunchKernelGGL((k_split<N, D, 1>), gs, bs4, 0, c->stream, sa); count_launch<PK_SPLIT, true, N, D, false, true, 2, 1>(c->run); }
-            });
-        });
-    } else if (r.p.pm) {                          // dense rows: candidate bitmaps made ahead (k_pm_cand)
-        c->run.pm_launches += 1;
-        if (!rtc_launch()) with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 2>(c, gd, bd, pa); });
-    } else if (tw && pa.skeys) {                  // long genomes: candidates by the join
-        if (!rtc_launch()) with_nfree_defp<3>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 1>(c, gd, bd, pa); });
-    } else if (use_blk) {
-        const u32 fw = (u32)std::max<u64>(c->gs.lay.fl_stride >> c->gs.blk_fold, 1);
+    if (d.kind == PK_SPLIT) rc = run_split(r, bt, pa, ch.row);           // few, long pairs: several waves a pair
+    else if (d.kind == PK_BLK) {
+        u32 fw = (u32)std::max<u64>(c->gs.lay.fl_stride >> c->gs.blk_fold, 1), fold = (u32)c->gs.blk_fold;
         const size_t lds = (size_t)(BLK_WAVES * SEED_LDS_WORDS + fw) * 4;
         rc = raise_lds(c, kf, lds);              // (a no-op after blk_fits, which recorded the fold it settled on)
         if (rc) return rc;
         pa.fmask = c->gs.lay.fmask >> c->gs.blk_fold;
         c->run.blk_launches += 1;
         const dim3 gb((u32)std::min<u64>((waves + BLK_CHUNK_MIN - 1) / BLK_CHUNK_MIN, (u64)c->n_cus * 2)), bb(64 * BLK_WAVES);
-        with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) {
-            hipLaunchKernelGGL((k_pairs_blk<N, D>), gb, bb, lds, c->stream, pa, fw, (u32)c->gs.blk_fold, c->d_blkctr);
-            count_launch<PK_BLK, true, N, D, false, true, 0>(c->run);
-        });
-    } else if (tw) {
-        if (!rtc_launch()) with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, true, 0>(c, gd, bd, pa); });
-    } else with_nfree_defp<2>(nf, r.dsel, [&](auto N, auto D) { launch_k_pairs<true, N, D, false, false, 0>(c, gd, bd, pa); });
+        u32* blkctr = c->d_blkctr.get();
+        void* kargs[] = {&pa, &fw, &fold, &blkctr};
+        HIPCHK(c, launch_row(c, ch.row, gb, bb, kargs, lds));
+    } else {
+        c->run.pm_launches += d.cand == 2 ? 1 : 0;          // dense rows: candidate bitmaps made ahead (k_pm_cand)
+        void* kargs[] = {&pa};
+        bool by_rtc = false;
+        if (ch.rtc_row >= 0) {
+            by_rtc = launch_row(c, ch.rtc_row, gd, bd, kargs, 0, r.rtc_k->fn) == hipSuccess;
+            if (by_rtc) c->run.rtc_launches += 1; else (void)hipGetLastError();
+        }
+        if (!by_rtc) HIPCHK(c, launch_row(c, ch.row, gd, bd, kargs));
+    }
     if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev[3], c->stream));
@@ -867,8 +771,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     // A compile takes 2-3 s and the folded kernel saves ~0.13 s per million pairs of 40 kbp: a code object that is not in
     // the disk cache yet is built once the context has been asked for LZANI_RTC_MIN_PAIRS pairs in all (default 2 M: the
     // first such run loses a second or two, every later run and every later process wins).
-    const int dsel = defp_select(c->P), cand = p.pm ? 2 : (p.use_join && c->sl.d_tw) ? 1 : c->sl.d_tw ? 0 : -1;
-    const int rtc_id = PK_RTC_N0_C0 + 3 * (int)c->gs.all_nfree + cand;      // (its row of the launch record)
+    const int dsel = defp_select(c->P), cand = pair_cand(p.pm, p.use_join, c->sl.d_tw != nullptr);
     lzani_rtc::Kernel* rtc_k = nullptr;
     c->pairs_seen += n_pairs;
     if (!dsel && !rs && c->gs.tab.kmL && c->sl.d_bk && lzani_rtc::enabled() && cand >= 0) {
@@ -876,7 +779,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
         if (!rtc_k && c->rtc.failed) TRACE("run-time compile unavailable (%s): the generic kernel runs", c->rtc.log.c_str());
     }
 
-    RunCtx r{c, k, p, rs, row_off, query_ids, d_out, d_ref, d_q, d_qorder, d_off, d_qcum, max_blocks, dsel, d_cbits, cbits_stride, rtc_k, rtc_id};
+    RunCtx r{c, k, p, rs, row_off, query_ids, d_out, d_ref, d_q, d_qorder, d_off, d_qcum, max_blocks, dsel, d_cbits, cbits_stride, rtc_k};
     r.sink = sink;
     for (u32 b = 0; b < n_batches; ++b) {
         const u32 k0 = p.bstart[b], k1 = p.bstart[b + 1];

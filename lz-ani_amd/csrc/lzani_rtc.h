@@ -128,6 +128,35 @@ inline void write_file_atomic(const std::string& dir, const std::string& path, c
     if (rename(tmp.c_str(), path.c_str()) != 0) (void)unlink(tmp.c_str());
 }
 
+// The options of the compile, the gfx target first: part of the disk cache's key.
+inline std::vector<std::string> options_of(const char* arch)
+{
+    return {std::string("--offload-arch=") + arch, "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value"};
+}
+
+// The one compile step (no device needed): `src` with `opts` into `code`.  false: no code object, and `err` says why;
+// `clog` is the compiler's own log in either case.
+inline bool compile(const std::string& src, const std::vector<std::string>& opts, std::vector<char>& code, std::string& err, std::string& clog)
+{
+    std::vector<const char*> o;
+    for (const std::string& s : opts) o.push_back(s.c_str());
+    hiprtcProgram prog = nullptr;
+    hiprtcResult r = hiprtcCreateProgram(&prog, src.c_str(), "lzani_rtc_pairs.hip", 0, nullptr, nullptr);
+    if (r == HIPRTC_SUCCESS) r = hiprtcCompileProgram(prog, (int)o.size(), o.data());
+    size_t ls = 0, cs = 0;
+    err = r == HIPRTC_SUCCESS ? "" : std::string("hipRTC: ") + hiprtcGetErrorString(r);
+    clog.clear();
+    if (prog && hiprtcGetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
+        clog.assign(ls, '\0');
+        if (hiprtcGetProgramLog(prog, &clog[0]) != HIPRTC_SUCCESS) clog.clear();
+    }
+    code.clear();
+    if (r == HIPRTC_SUCCESS && hiprtcGetCodeSize(prog, &cs) == HIPRTC_SUCCESS && cs) { code.resize(cs); if (hiprtcGetCode(prog, code.data()) != HIPRTC_SUCCESS) code.clear(); }
+    if (prog) (void)hiprtcDestroyProgram(&prog);
+    if (r == HIPRTC_SUCCESS && code.empty()) err = "hipRTC: no code object";
+    return !code.empty();
+}
+
 // The kernel of (nfree, cand) for the parameters P on the current device, built or loaded on first use; nullptr if it
 // cannot be had (the caller then launches the generic ahead-of-time kernel).
 // may_compile = false: only a code object already on disk is taken (a compile costs 2-3 s: it pays from some millions of
@@ -138,12 +167,11 @@ inline Kernel* get(State& st, const lzani::Params& P, bool nfree, int cand, cons
     if (k.tried) return k.fn ? &k : nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     const std::string src = source_of(P, nfree, cand);
-    const std::string archopt = std::string("--offload-arch=") + arch;
-    std::vector<const char*> opts = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value"};
+    const std::vector<std::string> opts = options_of(arch);
     int ver_major = 0, ver_minor = 0;
     (void)hiprtcVersion(&ver_major, &ver_minor);
     std::string keytext = src;
-    for (const char* o : opts) { keytext += o; keytext += ' '; }
+    for (const std::string& o : opts) { keytext += o; keytext += ' '; }
     keytext += std::to_string(ver_major) + "." + std::to_string(ver_minor);
     char name[64];
     snprintf(name, sizeof name, "pairs_%016llx.co", fnv1a(keytext));
@@ -153,24 +181,8 @@ inline Kernel* get(State& st, const lzani::Params& P, bool nfree, int cand, cons
     if (!cached && !may_compile) return nullptr;
     k.tried = true;
     if (!cached) {
-        hiprtcProgram prog = nullptr;
-        hiprtcResult r = hiprtcCreateProgram(&prog, src.c_str(), "lzani_rtc_pairs.hip", 0, nullptr, nullptr);
-        if (r == HIPRTC_SUCCESS) r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
-        if (r != HIPRTC_SUCCESS) {
-            size_t ls = 0;
-            st.log = std::string("hipRTC: ") + hiprtcGetErrorString(r);
-            if (prog && hiprtcGetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-                std::string lg(ls, '\0');
-                if (hiprtcGetProgramLog(prog, &lg[0]) == HIPRTC_SUCCESS) st.log += ": " + lg.substr(0, 2000);
-            }
-            if (prog) (void)hiprtcDestroyProgram(&prog);
-            ++st.failed;
-            return nullptr;
-        }
-        size_t cs = 0;
-        if (hiprtcGetCodeSize(prog, &cs) == HIPRTC_SUCCESS && cs) { code.resize(cs); if (hiprtcGetCode(prog, code.data()) != HIPRTC_SUCCESS) code.clear(); }
-        (void)hiprtcDestroyProgram(&prog);
-        if (code.empty()) { st.log = "hipRTC: no code object"; ++st.failed; return nullptr; }
+        std::string err, clog;
+        if (!compile(src, opts, code, err, clog)) { st.log = err + (clog.empty() ? "" : ": " + clog.substr(0, 2000)); ++st.failed; return nullptr; }
         if (!path.empty()) write_file_atomic(dir, path, code);
     }
     size_t gbytes = 0;
@@ -190,24 +202,15 @@ inline Kernel* get(State& st, const lzani::Params& P, bool nfree, int cand, cons
     return &k;
 }
 
-// compile only (no device needed): the size of the code object, or 0 with the compiler's log in `log`
+// compile only (no device needed), with the source and the options of `get`: the size of the code object, or 0; the
+// compiler's whole log in `log`
 inline size_t compile_only(const lzani::Params& P, bool nfree, int cand, const char* arch, std::string& log)
 {
-    const std::string src = source_of(P, nfree, cand);
-    const std::string archopt = std::string("--offload-arch=") + arch;
-    const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value"};
-    hiprtcProgram prog = nullptr;
-    hiprtcResult r = hiprtcCreateProgram(&prog, src.c_str(), "lzani_rtc_pairs.hip", 0, nullptr, nullptr);
-    if (r == HIPRTC_SUCCESS) r = hiprtcCompileProgram(prog, 5, opts);
-    size_t ls = 0, cs = 0;
-    log = r == HIPRTC_SUCCESS ? "" : std::string("hipRTC: ") + hiprtcGetErrorString(r);
-    if (prog && hiprtcGetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-        std::string lg(ls, '\0');
-        if (hiprtcGetProgramLog(prog, &lg[0]) == HIPRTC_SUCCESS) log += lg;
-    }
-    if (r == HIPRTC_SUCCESS) (void)hiprtcGetCodeSize(prog, &cs);
-    if (prog) (void)hiprtcDestroyProgram(&prog);
-    return r == HIPRTC_SUCCESS ? cs : 0;
+    std::vector<char> code;
+    std::string err, clog;
+    const bool ok = compile(source_of(P, nfree, cand), options_of(arch), code, err, clog);
+    log = err + clog;
+    return ok ? code.size() : 0;
 }
 
 inline void release(State& st)

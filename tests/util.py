@@ -517,10 +517,12 @@ def envelope_family_set(with_n=True):
 
 
 # ---- the pair-kernel instantiations and the launch record ---------------------------------------
-# lzani_hip.hip names every pair-kernel instantiation its dispatch can launch (lzani_debug_kernel_name) and counts the launches
-# of a context's last run per name (Engine.kernel_launches).  The matrix below is written from the dispatch of run_rows_impl,
-# not copied from the library's table; tests/test_instantiations.py checks the two against each other and against the
-# kernel symbols of the gfx950 code object.
+# The library names every pair-kernel instantiation its dispatch can launch (lzani_debug_kernel_name) and counts the launches
+# of a context's last run per name (Engine.kernel_launches).  The table and the choice of a launch's kernel live in
+# lzani_pair_dispatch.h (choose_pair_kernel), the facts it goes by are gathered in lzani_hip.hip (run_rows_impl, run_batch,
+# launch_pairs).  The matrix below is written from those rules, not copied from the library's table;
+# tests/test_instantiations.py checks the two against each other and against the kernel symbols of the gfx950 code object,
+# tests/test_pair_dispatch.py pair_kernel_choice against choose_pair_kernel over every combination of the facts.
 PAIRS_NAME = "pairs fast={} nfree={} defp={} aln={} bk={} cand={}"
 
 
@@ -585,6 +587,26 @@ def split_plan(n_pairs, cb_words, dmax, env=None, slots=WAVE_SLOTS):
     return min(S, ceil_div(dmax, seglen)), seglen
 
 
+def pair_kernel_choice(regions, fast, tw, pm, split, join, blk, nfree, dsel, rtc):
+    """(the ahead-of-time name, the run-time compiled name tried first or None) of one pair launch, from the facts
+    lzani_pair_dispatch.h (PairFacts) goes by -- restated, not a call into the library.  A split: its mode-0 name.
+    dsel: 0 generic, 1 the defaults, 2 the long-genome tuple, which the probe forms and the block kernel run generic."""
+    nf, d_probe = int(nfree), int(dsel == 1)
+    if regions:
+        return PAIRS_NAME.format(int(fast), 0, 0, 1, int(fast and tw), 0), None
+    if not fast:
+        return PAIRS_NAME.format(0, 0, 0, 0, 0, 0), None
+    if pm and split:
+        return "split nfree={} defp={} mode=0".format(nf, dsel), None
+    cand = 2 if pm else 1 if join and tw else 0 if tw else None
+    rtc_name = "rtc nfree={} cand={}".format(nf, cand) if rtc and cand is not None else None
+    if cand in (2, 1):
+        return PAIRS_NAME.format(1, nf, dsel, 0, 1, cand), rtc_name
+    if blk:
+        return "pairs_blk nfree={} defp={}".format(nf, d_probe), None
+    return PAIRS_NAME.format(1, nf, d_probe, 0, int(tw), 0), rtc_name
+
+
 def predict_kernels(seqs, prm, env=None, form="all2all", pairs_per_row=None, n_rows=None, rtc_ready=False):
     """The names a run launches (lzani_hip.hip: run_rows_impl), from the genome set, the tuple, the environment (the
     LZANI_* switches that are set) and the call: form "all2all" (dense rows), "dup_lists" (query lists that name a
@@ -605,11 +627,8 @@ def predict_kernels(seqs, prm, env=None, form="all2all", pairs_per_row=None, n_r
                  _clog2(n + 1) + g["key_bits"] + g["pos_bits"] <= 64 and not on("LZANI_NO_JOIN"))
     nf = int(all((s < 4).all() for s in seqs))
     d_fold = 1 if p == AOT_SETS["defaults"] else 2 if p == AOT_SETS["long"] else 0     # bitmaps, join, split
-    d_probe = int(d_fold == 1)                                                          # probe forms, block kernel
-    if form == "regions":
-        return {PAIRS_NAME.format(int(fast), 0, 0, 1, int(fast and tw), 0)}
-    if not fast:
-        return {PAIRS_NAME.format(0, 0, 0, 0, 0, 0)}
+    if form == "regions" or not fast:
+        return {pair_kernel_choice(form == "regions", fast, tw, False, False, False, False, nf, d_fold, False)[0]}
     n_rows = n if n_rows is None else n_rows
     pairs_per_row = n - 1 if pairs_per_row is None else pairs_per_row
     n_pairs = n_rows * pairs_per_row
@@ -625,17 +644,11 @@ def predict_kernels(seqs, prm, env=None, form="all2all", pairs_per_row=None, n_r
     fl = tw and not join_mode and _clog2(max(g["T"], 1024)) <= int(env.get("LZANI_FILTER_MAX_BITS", 18)) and not on("LZANI_NO_FILTER")
     blk = (not pm and tw and not join_mode and fl and pairs_per_row >= 128 and
            (on("LZANI_BLOCK_KERNEL") if "LZANI_BLOCK_KERNEL" in env else form == "all2all"))
-    cand = 2 if pm else 1 if use_join else 0 if tw else None
-    rtc = rtc_ready and not off("LZANI_RTC") and d_fold == 0 and cand is not None
-    if pm and split:
-        return {"split nfree={} defp={} mode={}".format(nf, d_fold, m) for m in (0, 1)}
-    if rtc and not blk:
-        return {"rtc nfree={} cand={}".format(nf, cand)}
-    if pm or use_join:
-        return {PAIRS_NAME.format(1, nf, d_fold, 0, 1, cand)}
-    if blk:
-        return {"pairs_blk nfree={} defp={}".format(nf, d_probe)}
-    return {PAIRS_NAME.format(1, nf, d_probe, 0, int(tw), 0)}
+    rtc = rtc_ready and not off("LZANI_RTC") and d_fold == 0
+    aot, rtc_name = pair_kernel_choice(False, fast, tw, pm, split, use_join, blk, nf, d_fold, rtc)
+    if aot.startswith("split "):
+        return {aot, aot.replace("mode=0", "mode=1")}              # (a split batch runs both modes)
+    return {rtc_name or aot}
 
 
 # The cells of tests/test_gpu_instantiations.py: one per name of the table (two per run-time compiled kernel: a tuple
