@@ -6,6 +6,7 @@
 //   lzani_kernels_cand.h    k_pm_build, k_pm_cand   dense rows: presence matrix of a group of references -> per-pair candidate bitmaps
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
+//   lzani_block.h           block_sum, block_rank, block_scan_step   what a block's threads work out together (index, prefilter)
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
 // (batches, queues, the split rule, the bytes of a slab slot) in lzani_run_plan.h, which pair kernel a launch takes (the

@@ -9,6 +9,7 @@
 //                 prepare_ht_long, parser.cpp:53-103, 146-189): bucket directory + (tag|pos)
 //                 entries, ascending inside a bucket; bucket table and tag words for viral sizes
 #pragma once
+#include "lzani_block.h"
 
 namespace lzani {
 
@@ -67,6 +68,7 @@ __global__ void __launch_bounds__(256) k_join_keys(GenomeTab G, const u64* __res
         out[p] = ok ? ((unsigned long long)(g_base + g) << shift_g) | ((unsigned long long)h << posbits) | (unsigned long long)p : ~0ULL;
         mine += ok;
     }
+    // (block_sum's statements, kept here: with the helper this kernel's code comes out 14 instructions longer)
     for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
     __syncthreads();
@@ -175,9 +177,7 @@ __global__ void __launch_bounds__(256) k_idx_keys(IdxArgs a, unsigned long long*
         mine += ok;
     }
     (void)shift_slot;
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
-    __syncthreads();
+    block_sum(mine, &s_cnt);
     if (threadIdx.x == 0 && s_cnt) atomicAdd(&cnt[slot], s_cnt);
 }
 
@@ -289,26 +289,12 @@ __global__ void __launch_bounds__(1024) k_idx_scan(u32* dirz, u64 dir_stride, u3
     __shared__ u32 carry_s;
     if (todo && !todo[blockIdx.x]) return;
     u32* cnt = dirz + (u64)blockIdx.x * dir_stride + 1;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (threadIdx.x == 0) carry_s = 0;
     __syncthreads();
     for (u32 base = 0; base < nb; base += 1024) {
-        u32 idx = base + threadIdx.x;
-        u32 v = idx < nb ? cnt[idx] : 0;
-        u32 x = v;                                   // inclusive scan inside the wave
-        for (int d = 1; d < 64; d <<= 1) {
-            u32 y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[wv] = x;
-        __syncthreads();
-        u32 woff = 0;
-        for (int k = 0; k < wv; ++k) woff += wsum[k];
-        u32 carry = carry_s;
-        if (idx < nb) cnt[idx] = carry + woff + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + woff + x;
-        __syncthreads();
+        const u32 idx = base + threadIdx.x;
+        const u32 before = block_scan_step<u32>(idx < nb ? cnt[idx] : 0, wsum, &carry_s);
+        if (idx < nb) cnt[idx] = before;
     }
 }
 

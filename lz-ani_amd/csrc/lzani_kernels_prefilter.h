@@ -8,42 +8,31 @@
 //                 histogram of the PF_BINS bins (per block in LDS, then one atomic add per non-empty bin)
 //   k_pf_keys_codes  the same keys from raw symbol codes in a staging buffer (lzani_prefilter_codes: genomes that are not
 //                 resident), staged and packed in LDS; the other strand arithmetically from the forward value
-//   k_pf_uniq     a sorted array without its adjacent duplicates (counted per block, then written): the dictionary of
-//                 distinct k-mers from the sorted keys, the postings from the sorted (rank, genome) keys
+//   pf_compact    count, then write, of a block's PF_CHUNK elements (the block sum and the block rank of lzani_block.h):
+//                 the one skeleton of k_pf_uniq and k_pf_sparse_kept, which say what is kept and where it is put
+//   k_pf_uniq     a sorted array without its adjacent duplicates: the dictionary of distinct k-mers from the sorted keys,
+//                 the postings from the sorted (rank, genome) keys
 //   k_pf_scan     exclusive prefix of per-block / per-row counts (one block; the arrays are 1/4096 of the data)
 //   k_pf_runs     where the postings of every rank begin
 //   k_pf_split    cross form: where the postings of every rank pass from the references (genome < n_ref) to the queries
-//   k_pf_count    a wave per 64 postings: for every posting (rank, a) of the row tile, one atomic add to count[a][b] per
-//                 later posting (rank, b) of the same run, the lanes side by side over b.  CROSS: a is a reference, the
-//                 b's are the run's queries only, and the tile is n_ref rows of n - n_ref columns
+//   pf_walk       the posting walker, a wave per 64 postings: for every posting (rank, a) of the row tile, one add per later
+//                 posting (rank, b) of the same run, the lanes side by side over b.  CROSS: a is a reference, the b's are
+//                 the run's queries only, and the tile is n_ref rows of n - n_ref columns.  Its two accumulators:
+//   k_pf_count        PfMatrixAcc: an add is one atomic add to count[a][b] of the matrix tile
+//   k_pf_count_sparse PfTableAcc (sparse counting): an add inserts the pair's key into the pair table by linear probing
+//                 and adds to its slot; bounded, with an overflow word for a table too small, polled before every a
 //   k_pf_rows     a wave per matrix row: the kept entries counted, then written in ascending b
-//   k_pf_count_sparse  k_pf_count with a pair table in place of the matrix tile (sparse counting): every add inserts the
-//                 pair's key by linear probing and adds to its slot; bounded, with an overflow word for a table too small
-//   k_pf_sparse_kept / _fetch / _rowoff  the table's kept keys (counted per block, then written), and behind their sort
-//                 the ids and counts of the sorted keys and where every row of the tile begins
+//   k_pf_sparse_kept / _fetch / _rowoff  the table's kept keys, and behind their sort the ids and counts of the sorted keys
+//                 and where every row of the tile begins
 // No kernel waits for another block.  The sorts between them are lzani_sort_keys (lzani_sort.hip).
 #pragma once
+#include "lzani_block.h"
 #include "lzani_prefilter_defs.h"
 
 namespace lzani {
 
 enum { PF_THREADS = 256, PF_PER_THREAD = 16, PF_CHUNK = PF_THREADS * PF_PER_THREAD };
 enum { PF_COUNT = 0, PF_CANON = 1, PF_RANK = 2, PF_HIST = 3 };
-
-// Among the block's PF_THREADS threads: how many threads before this one raise `flag`; total: how many in all.
-__device__ __forceinline__ u32 pf_block_rank(bool flag, u32* s_w, u32& total)
-{
-    const u64 m = __builtin_amdgcn_ballot_w64(flag);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) s_w[wv] = (u32)__popcll(m);
-    __syncthreads();
-    u32 off = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < PF_THREADS / 64; ++k) { const u32 c = s_w[k]; off += k < wv ? c : 0u; tot += c; }
-    __syncthreads();
-    total = tot;
-    return off + (u32)__popcll(m & ((1ULL << lane) - 1ULL));
-}
 
 // The canonical k-mer of the window at forward position p of genome g, if the window exists, holds no N and is sampled.
 __device__ __forceinline__ bool pf_key_at(const GenomeTab& G, u32 g, int L, int p, int k, int mrd, u64 sample_max, u64& key)
@@ -95,7 +84,7 @@ __device__ __forceinline__ void pf_hist_flush(const u32* s_hist, unsigned long l
 // The tail the two key kernels share.  pf_emit: one window of every thread of the block (ok: it is kept and of the pass,
 // key: its canonical k-mer) -- COUNT: counted in `mine`; HIST: added to the block's histogram; CANON / RANK: written at
 // out[base + its rank among the block's kept windows of this step], and base moves past them.  Every thread of the block
-// calls it (pf_block_rank holds barriers).
+// calls it (block_rank holds barriers).
 template <int MODE>
 __device__ __forceinline__ void pf_emit(bool ok, u64 key, u32 g, const unsigned long long* __restrict__ dict, u64 D, unsigned long long* __restrict__ out,
                                         u64& base, u32& mine, u32* s_w, u32* s_hist)
@@ -104,7 +93,7 @@ __device__ __forceinline__ void pf_emit(bool ok, u64 key, u32 g, const unsigned 
     else if (MODE == PF_HIST) { if (ok) atomicAdd(&s_hist[pf_bin(key)], 1u); }
     else {
         u32 tot;
-        const u32 r = pf_block_rank(ok, s_w, tot);
+        const u32 r = block_rank<PF_THREADS>(ok, s_w, tot);
         if (ok) out[base + r] = MODE == PF_CANON ? key : ((u64)pf_find(dict, D, key) << 32) | (u64)g;
         base += tot;
     }
@@ -115,9 +104,7 @@ template <int MODE>
 __device__ __forceinline__ void pf_keys_end(u32 mine, u32* __restrict__ blkcnt, u64 blk, u32* s_cnt, const u32* s_hist, unsigned long long* __restrict__ out)
 {
     if (MODE == PF_COUNT) {
-        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(s_cnt, mine);
-        __syncthreads();
+        block_sum(mine, s_cnt);
         if (threadIdx.x == 0) blkcnt[blk] = *s_cnt;
     }
     if (MODE == PF_HIST) pf_hist_flush(s_hist, out);
@@ -222,13 +209,11 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_keys_codes(const unsigned cha
     pf_keys_end<MODE>(mine, blkcnt, blk, &s_cnt, s_hist, out);
 }
 
-// in[0 .. n) ascending: block b takes its PF_CHUNK elements from b * PF_CHUNK on and counts (blkcnt[b]) or writes (from
-// blkoff[b] on) those that differ from their predecessor.  per_genome (WRITE, may be null): += 1 at the low 32 bits of
-// every element written.
-template <bool WRITE>
-__global__ void __launch_bounds__(PF_THREADS) k_pf_uniq(const unsigned long long* __restrict__ in, u64 n, u32* __restrict__ blkcnt,
-                                                        const u64* __restrict__ blkoff, unsigned long long* __restrict__ out,
-                                                        u32* __restrict__ per_genome, u32 n_genomes)
+// Count, then write: block b takes the PF_CHUNK elements from b * PF_CHUNK on of n, and of those that item.kept(i, v)
+// keeps (v: what it read of element i) it counts them (blkcnt[b]), or (WRITE) hands each to item.put(at, v), at = blkoff[b]
+// + its rank among the block's kept elements, in the order of i.  The whole block calls it, once.
+template <bool WRITE, class Item>
+__device__ __forceinline__ void pf_compact(u64 n, u32* __restrict__ blkcnt, const u64* __restrict__ blkoff, Item item)
 {
     __shared__ u32 s_w[PF_THREADS / 64];
     __shared__ u32 s_cnt;
@@ -237,34 +222,44 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_uniq(const unsigned long long
     u32 mine = 0;
     if (!WRITE) { if (threadIdx.x == 0) s_cnt = 0; __syncthreads(); }
     for (int it = 0; it < PF_PER_THREAD; ++it) {
-        if (i0 + (u64)it * PF_THREADS >= n) break;
+        if (i0 + (u64)it * PF_THREADS >= n) break;                       // (the same for the whole block)
         const u64 i = i0 + (u64)it * PF_THREADS + threadIdx.x;
         u64 v = 0;
-        bool ok = false;
-        if (i < n) { v = in[i]; ok = i == 0 || in[i - 1] != v; }
+        const bool ok = i < n && item.kept(i, v);
         if (!WRITE) mine += ok;
         else {
             u32 tot;
-            const u32 r = pf_block_rank(ok, s_w, tot);
-            if (ok) {
-                out[base + r] = v;
-                if (per_genome && (u32)v < n_genomes) atomicAdd(&per_genome[(u32)v], 1u);
-            }
+            const u32 r = block_rank<PF_THREADS>(ok, s_w, tot);
+            if (ok) item.put(base + r, v);
             base += tot;
         }
     }
     if (!WRITE) {
-        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
-        __syncthreads();
+        block_sum(mine, &s_cnt);
         if (threadIdx.x == 0) blkcnt[blockIdx.x] = s_cnt;
     }
 }
 
-__device__ __forceinline__ u64 pf_shfl_up64(u64 x, int d)
+// in[0 .. n) ascending: the elements that differ from their predecessor, counted or written by pf_compact.  per_genome
+// (WRITE, may be null): += 1 at the low 32 bits of every element written.
+struct PfUniqItem {
+    const unsigned long long* __restrict__ in;
+    unsigned long long* __restrict__ out;
+    u32* __restrict__ per_genome;
+    u32 n_genomes;
+    __device__ __forceinline__ bool kept(u64 i, u64& v) const { v = in[i]; return i == 0 || in[i - 1] != v; }
+    __device__ __forceinline__ void put(u64 at, u64 v) const
+    {
+        out[at] = v;
+        if (per_genome && (u32)v < n_genomes) atomicAdd(&per_genome[(u32)v], 1u);
+    }
+};
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_uniq(const unsigned long long* __restrict__ in, u64 n, u32* __restrict__ blkcnt,
+                                                        const u64* __restrict__ blkoff, unsigned long long* __restrict__ out,
+                                                        u32* __restrict__ per_genome, u32 n_genomes)
 {
-    const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
-    return ((u64)hi << 32) | lo;
+    pf_compact<WRITE>(n, blkcnt, blkoff, PfUniqItem{in, out, per_genome, n_genomes});
 }
 
 // off[0 .. n] = exclusive prefix of cnt[0 .. n), the total at off[n].  One block.
@@ -272,23 +267,12 @@ __global__ void __launch_bounds__(1024) k_pf_scan(const u32* __restrict__ cnt, u
 {
     __shared__ u64 s_wsum[16];
     __shared__ u64 s_carry;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (threadIdx.x == 0) s_carry = 0;
     __syncthreads();
     for (u64 base = 0; base < n; base += 1024) {
         const u64 idx = base + threadIdx.x;
-        const u64 v = idx < n ? cnt[idx] : 0;
-        u64 x = v;
-        for (int d = 1; d < 64; d <<= 1) { const u64 y = pf_shfl_up64(x, d); if (lane >= d) x += y; }
-        if (lane == 63) s_wsum[wv] = x;
-        __syncthreads();
-        u64 woff = 0;
-        for (int k = 0; k < wv; ++k) woff += s_wsum[k];
-        const u64 carry = s_carry;
-        if (idx < n) off[idx] = carry + woff + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + woff + x;
-        __syncthreads();
+        const u64 before = block_scan_step<u64>(idx < n ? cnt[idx] : 0, s_wsum, &s_carry);
+        if (idx < n) off[idx] = before;
     }
     if (threadIdx.x == 0) off[n] = s_carry;
 }
@@ -320,14 +304,18 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_split(const unsigned long lon
     } else if (i + 1 == M || (post[i + 1] >> 32) != r) runsplit[r] = (u32)(i + 1);
 }
 
-// The matrix tile mat[(a - r0) * n + b], rows r0 <= a < r1: += 1 for every pair of postings (rank, a), (rank, b) with a < b.
+// The posting walker: for every pair of postings (rank, a), (rank, b) with r0 <= a < r1 and a < b, one acc.add(b).
 // A wave takes 64 consecutive postings as its a's, one after the other, the lanes over the rest of a's run: a k-mer that
-// every genome holds is spread over n / 64 waves, and a wave's adds of one step go to one matrix row.
-// CROSS: the tile is mat[(a - r0) * (n - n_ref) + (b - n_ref)], rows r0 <= a < r1 <= n_ref; a posting is active iff it is
-// a reference of the tile and its run holds a query, and the lanes go over the run's queries, [runsplit[rank], end).
-template <bool CROSS>
-__global__ void __launch_bounds__(PF_THREADS) k_pf_count(const unsigned long long* __restrict__ post, u64 M, const u32* __restrict__ runoff, u64 D,
-                                                         u32 n, u32 r0, u32 r1, u32* __restrict__ mat, const u32* __restrict__ runsplit, u32 n_ref)
+// every genome holds is spread over n / 64 waves, and a wave's adds of one step belong to one row a.
+// CROSS: the rows are references, r1 <= n_ref, the columns the n - n_ref queries: a posting is active iff it is a
+// reference of the tile and its run holds a query, the lanes go over the run's queries, [runsplit[rank], end), and the
+// column handed to add is b - n_ref.
+// The accumulator says what an add does.  Before each a, acc.go(): false ends the walk for the whole wave (every lane
+// gets the same answer).  acc.row(a): the adds that follow belong to row a.  acc.add(c): column c of that row += 1;
+// false ends this lane's part of the run and nothing else.
+template <bool CROSS, class Acc>
+__device__ __forceinline__ void pf_walk(const unsigned long long* __restrict__ post, u64 M, const u32* __restrict__ runoff, u64 D, u32 n, u32 r0, u32 r1,
+                                        const u32* __restrict__ runsplit, u32 n_ref, Acc acc)
 {
     const int lane = threadIdx.x & 63;
     const u64 w0 = (((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6) << 6;      // the wave's first posting
@@ -348,26 +336,35 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_count(const unsigned long lon
                 act = (u64)end > i + 1;
         }
     }
+    const u32 c0 = CROSS ? n_ref : 0u, nc = n - c0;            // the first column's genome; columns
     u64 todo = __builtin_amdgcn_ballot_w64(act);
     while (todo) {
+        if (!acc.go()) return;
         const int l = ctz64(todo);
         todo &= todo - 1;
-        const u32 al = __shfl(a, l), el = __shfl(end, l);
-        if (CROSS) {
-            const u32 nq = n - n_ref, fl = __shfl(from, l);
-            u32* __restrict__ row = mat + (u64)(al - r0) * nq;
-            for (u64 j = (u64)fl + lane; j < (u64)el; j += 64) {
-                const u32 c = (u32)post[j] - n_ref;            // (below n_ref: wraps beyond nq)
-                if (c < nq) atomicAdd(&row[c], 1u);
-            }
-        } else {
-            u32* __restrict__ row = mat + (u64)(al - r0) * n;
-            for (u64 j = w0 + l + 1 + lane; j < (u64)el; j += 64) {
-                const u32 b = (u32)post[j];
-                if (b < n) atomicAdd(&row[b], 1u);
-            }
+        const u32 el = __shfl(end, l);
+        acc.row(__shfl(a, l));
+        for (u64 j = (CROSS ? (u64)__shfl(from, l) : w0 + l + 1) + lane; j < (u64)el; j += 64) {
+            const u32 c = (u32)post[j] - c0;                   // (CROSS, a genome below n_ref: wraps beyond nc)
+            if (c < nc && !acc.add(c)) break;
         }
     }
+}
+
+// The matrix tile as the walker's accumulator: mat[(a - r0) * cols + c] += 1, cols = n (CROSS: n - n_ref) columns a row.
+struct PfMatrixAcc {
+    u32* __restrict__ mat;
+    u32 r0, cols;
+    u32* row_;
+    __device__ __forceinline__ bool go() const { return true; }
+    __device__ __forceinline__ void row(u32 a) { row_ = mat + (u64)(a - r0) * cols; }
+    __device__ __forceinline__ bool add(u32 c) const { atomicAdd(&row_[c], 1u); return true; }
+};
+template <bool CROSS>
+__global__ void __launch_bounds__(PF_THREADS) k_pf_count(const unsigned long long* __restrict__ post, u64 M, const u32* __restrict__ runoff, u64 D,
+                                                         u32 n, u32 r0, u32 r1, u32* __restrict__ mat, const u32* __restrict__ runsplit, u32 n_ref)
+{
+    pf_walk<CROSS>(post, M, runoff, D, n, r0, r1, runsplit, n_ref, PfMatrixAcc{mat, r0, CROSS ? n - n_ref : n, nullptr});
 }
 
 // kept: shared >= min_shared (>= 1) and shared / min(|a|, |b|) >= min_ratio, in IEEE double division
@@ -444,93 +441,54 @@ __device__ __forceinline__ bool pf_sp_add(unsigned long long* __restrict__ keys,
     return false;
 }
 
-// k_pf_count with the table behind it: the same waves over the same postings, the same activity test against [r0, r1),
-// and where k_pf_count adds into row[b] the pair's key is inserted and its slot's count goes up by one.  A wave reads the
-// overflow word before every a and leaves where it is raised; a lane whose add fails ends its run.
+// The pair table as the walker's accumulator: an add inserts the pair's key  a << 32 | c0 + c  (c0: the genome of column
+// 0) and its slot's count goes up by one.  A wave reads the overflow word before every a and leaves where it is raised,
+// whatever lane saw it; a lane whose add fails ends its run.
+struct PfTableAcc {
+    unsigned long long* __restrict__ keys;
+    u32* __restrict__ cnt;
+    u64 S;
+    u32* __restrict__ ctl;
+    u32 c0;
+    u64 hi_;
+    __device__ __forceinline__ bool go() const
+    {
+        const u32 ovf = __hip_atomic_load(&ctl[PF_SP_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return !__builtin_amdgcn_ballot_w64(ovf != 0);
+    }
+    __device__ __forceinline__ void row(u32 a) { hi_ = (u64)a << 32; }
+    __device__ __forceinline__ bool add(u32 c) const { return pf_sp_add(keys, cnt, S, ctl, hi_ | (u32)(c0 + c)); }
+};
 template <bool CROSS>
 __global__ void __launch_bounds__(PF_THREADS) k_pf_count_sparse(const unsigned long long* __restrict__ post, u64 M, const u32* __restrict__ runoff, u64 D,
                                                                 u32 n, u32 r0, u32 r1, unsigned long long* __restrict__ keys, u32* __restrict__ cnt, u64 S,
                                                                 u32* __restrict__ ctl, const u32* __restrict__ runsplit, u32 n_ref)
 {
-    const int lane = threadIdx.x & 63;
-    const u64 w0 = (((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6) << 6;      // the wave's first posting
-    const u64 i = w0 + lane;
-    u32 a = 0, end = 0, from = 0;
-    bool act = false;
-    if (i < M) {
-        const u64 key = post[i];
-        const u64 rank = key >> 32;
-        a = (u32)key;
-        if (rank < D && a >= r0 && a < r1) {
-            const u64 e = runoff[rank + 1];
-            end = (u32)(e < M ? e : M);
-            if (CROSS) {
-                from = runsplit[rank];
-                act = from < end;
-            } else
-                act = (u64)end > i + 1;
-        }
-    }
-    u64 todo = __builtin_amdgcn_ballot_w64(act);
-    while (todo) {
-        const u32 ovf = __hip_atomic_load(&ctl[PF_SP_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__builtin_amdgcn_ballot_w64(ovf != 0)) return;     // (the whole wave, whatever lane saw it)
-        const int l = ctz64(todo);
-        todo &= todo - 1;
-        const u32 al = __shfl(a, l), el = __shfl(end, l);
-        const u64 hi = (u64)al << 32;
-        if (CROSS) {
-            const u32 nq = n - n_ref, fl = __shfl(from, l);
-            for (u64 j = (u64)fl + lane; j < (u64)el; j += 64) {
-                const u32 b = (u32)post[j];
-                if (b - n_ref < nq && !pf_sp_add(keys, cnt, S, ctl, hi | b)) break;
-            }
-        } else {
-            for (u64 j = w0 + l + 1 + lane; j < (u64)el; j += 64) {
-                const u32 b = (u32)post[j];
-                if (b < n && !pf_sp_add(keys, cnt, S, ctl, hi | b)) break;
-            }
-        }
-    }
+    pf_walk<CROSS>(post, M, runoff, D, n, r0, r1, runsplit, n_ref, PfTableAcc{keys, cnt, S, ctl, CROSS ? n_ref : 0u, 0});
 }
 
-// The kept slots of the table: block b takes the PF_CHUNK slots from b * PF_CHUNK on and counts (blkcnt[b]) or writes
-// (from blkoff[b] on) the keys of the occupied slots whose count passes pf_kept.  The order is the table's, the sort
-// behind it makes it the result's.
+// The kept slots of the table, counted or written by pf_compact: the keys of the occupied slots whose count passes
+// pf_kept.  The order is the table's, the sort behind it makes it the result's.
+struct PfTableItem {
+    const unsigned long long* __restrict__ keys;
+    const u32* __restrict__ cnt;
+    const u32* __restrict__ kmers_of;
+    u32 min_shared;
+    double min_ratio;
+    unsigned long long* __restrict__ out;
+    __device__ __forceinline__ bool kept(u64 i, u64& key) const
+    {
+        key = keys[i];
+        return key != PF_SP_EMPTY && pf_kept(cnt[i], kmers_of[(u32)(key >> 32)], kmers_of[(u32)key], min_shared, min_ratio);
+    }
+    __device__ __forceinline__ void put(u64 at, u64 key) const { out[at] = key; }
+};
 template <bool WRITE>
 __global__ void __launch_bounds__(PF_THREADS) k_pf_sparse_kept(const unsigned long long* __restrict__ keys, const u32* __restrict__ cnt, u64 S,
                                                                const u32* __restrict__ kmers_of, u32 min_shared, double min_ratio,
                                                                u32* __restrict__ blkcnt, const u64* __restrict__ blkoff, unsigned long long* __restrict__ out)
 {
-    __shared__ u32 s_w[PF_THREADS / 64];
-    __shared__ u32 s_cnt;
-    const u64 i0 = (u64)blockIdx.x * PF_CHUNK;
-    u64 base = WRITE ? blkoff[blockIdx.x] : 0;
-    u32 mine = 0;
-    if (!WRITE) { if (threadIdx.x == 0) s_cnt = 0; __syncthreads(); }
-    for (int it = 0; it < PF_PER_THREAD; ++it) {
-        if (i0 + (u64)it * PF_THREADS >= S) break;
-        const u64 i = i0 + (u64)it * PF_THREADS + threadIdx.x;
-        u64 key = PF_SP_EMPTY;
-        bool ok = false;
-        if (i < S) {
-            key = keys[i];
-            ok = key != PF_SP_EMPTY && pf_kept(cnt[i], kmers_of[(u32)(key >> 32)], kmers_of[(u32)key], min_shared, min_ratio);
-        }
-        if (!WRITE) mine += ok;
-        else {
-            u32 tot;
-            const u32 r = pf_block_rank(ok, s_w, tot);
-            if (ok) out[base + r] = key;
-            base += tot;
-        }
-    }
-    if (!WRITE) {
-        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_cnt, mine);
-        __syncthreads();
-        if (threadIdx.x == 0) blkcnt[blockIdx.x] = s_cnt;
-    }
+    pf_compact<WRITE>(S, blkcnt, blkoff, PfTableItem{keys, cnt, kmers_of, min_shared, min_ratio, out});
 }
 
 // sorted[0 .. K): the kept keys ascending, i.e. row after row with ascending b.  ids[i] = b, shared[i] = the count of the

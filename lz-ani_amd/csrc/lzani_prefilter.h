@@ -68,6 +68,17 @@ struct PfClock {
         return hipSuccess;
     }
 };
+// blocks of PF_CHUNK elements (the key and compaction kernels) / of PF_THREADS threads, one per element, that cover x
+u64 pf_chunks(u64 x) { return (x + PF_CHUNK - 1) / PF_CHUNK; }
+u32 pf_blocks(u64 x) { return (u32)((x + PF_THREADS - 1) / PF_THREADS); }
+// the free device memory now
+int pf_free_bytes(lzani_ctx* c, u64& bytes)
+{
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));      // (the text of a failure names the call as written here)
+    bytes = free_b;
+    return LZANI_OK;
+}
 int pf_sort(lzani_ctx* c, PrefilterWork& w, const unsigned long long* in, unsigned long long* out, size_t n, int b0, int b1)
 {
     return sort_keys(c, w.tmp, in, out, n, 1, b0, b1, "lzani_prefilter: sort", false);      // (alloc_keys sized the scratch: it does not grow)
@@ -218,7 +229,7 @@ struct PfRun {
             const u32 f = st ? st->first[s] : 0, ns = st ? st->first[s + 1] - f : n;
             u64 lmax = 0;
             for (u32 g = f; g < f + ns; ++g) lmax = std::max(lmax, len_of(g));
-            const u32 gx = (u32)((lmax + PF_CHUNK - 1) / PF_CHUNK);
+            const u32 gx = (u32)pf_chunks(lmax);
             HIPCHK(c, clk.begin(mode == PF_HIST ? PF_ST_HIST : PF_ST_KEYS));
             if (gx) for_slices(ns, [&](u32 y0, u32 cnt) {
                 const dim3 gd(gx, cnt);
@@ -247,7 +258,7 @@ struct PfRun {
     // in[0 .. cnt) ascending -> out without adjacent duplicates; their number
     int uniq(const unsigned long long* in, u64 cnt, unsigned long long* out, u32* per_genome, u64& n_out)
     {
-        const u32 blocks = (u32)((cnt + PF_CHUNK - 1) / PF_CHUNK);
+        const u32 blocks = (u32)pf_chunks(cnt);
         hipLaunchKernelGGL(k_pf_uniq<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, in, cnt, w.ucnt.get(), w.uoff.get(), out, per_genome, n);
         if (int rc = scan_total(w.ucnt, blocks, w.uoff, n_out)) return rc;
         hipLaunchKernelGGL(k_pf_uniq<true>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, in, cnt, w.ucnt.get(), w.uoff.get(), out, per_genome, n);
@@ -268,8 +279,8 @@ struct PfRun {
     {
         HIPCHK(c, w.ka.alloc(windows));
         HIPCHK(c, w.kb.alloc(windows));
-        HIPCHK(c, w.ucnt.alloc((windows + PF_CHUNK - 1) / PF_CHUNK));
-        HIPCHK(c, w.uoff.alloc((windows + PF_CHUNK - 1) / PF_CHUNK + 1));
+        HIPCHK(c, w.ucnt.alloc(pf_chunks(windows)));
+        HIPCHK(c, w.uoff.alloc(pf_chunks(windows) + 1));
         size_t need1 = 0, need2 = 0;
         if (int rc = sort_scratch_bytes(c, windows, 1, 0, 2 * k, "lzani_prefilter: sort", need1)) return rc;
         if (int rc = sort_scratch_bytes(c, windows, 1, 32, 64, "lzani_prefilter: sort", need2)) return rc;
@@ -295,7 +306,7 @@ struct PfRun {
         HIPCHK(c, clk.begin(PF_ST_SORT));
         if (int rc = pf_sort(c, w, w.kb, w.ka, p.windows, 32, 32 + ceil_log2(p.D))) return rc;
         if (int rc = uniq(w.ka, p.windows, w.kb, per_genome, p.M)) return rc;
-        const dim3 grid((u32)((p.M + PF_THREADS - 1) / PF_THREADS));
+        const dim3 grid(pf_blocks(p.M));
         HIPCHK(c, w.runoff.reserve(p.D + 1));
         hipLaunchKernelGGL(k_pf_runs, grid, dim3(PF_THREADS), 0, c->stream, w.kb.get(), p.M, w.runoff.get(), p.D);
         if (n_ref) {
@@ -307,18 +318,17 @@ struct PfRun {
         return LZANI_OK;
     }
     // the dense rule: the rows of a matrix tile in half of the free device memory
-    u64 dense_rows(size_t free_b) const { return std::min<u64>(n_rows, std::max<u64>(1, (u64)free_b / 2 / ((u64)4 * n_cols))); }
+    u64 dense_rows(u64 free_b) const { return std::min<u64>(n_rows, std::max<u64>(1, free_b / 2 / ((u64)4 * n_cols))); }
     // the height of the matrix tile from what is free now, and the tile's buffers
     int alloc_tile()
     {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        u64 free_b = 0;
+        if (int rc = pf_free_bytes(c, free_b)) return rc;
         rows = dense_rows(free_b);
         if (const auto forced = env_u64("LZANI_PREFILTER_TILE_ROWS")) rows = std::min<u64>(n_rows, std::max<u64>(1, *forced));
         HIPCHK(c, w.mat.alloc(rows * n_cols));
         HIPCHK(c, w.rowcnt.alloc(rows));
         HIPCHK(c, w.rowoff.alloc(rows + 1));
-        h_off.resize(rows + 1);
         if (n_ref) { pf.cinfo.tile_rows = (u32)rows; pf.cinfo.matrix_bytes = w.mat.bytes(); }
         return LZANI_OK;
     }
@@ -327,11 +337,29 @@ struct PfRun {
     {
         HIPCHK(c, clk.begin(PF_ST_COUNT));
         if (clear) HIPCHK(c, hipMemsetAsync(w.mat, 0, (size_t)(r1 - r0) * n_cols * 4, c->stream));
-        hipLaunchKernelGGL((n_ref ? k_pf_count<true> : k_pf_count<false>), dim3((u32)((p.M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), p.M,
+        hipLaunchKernelGGL((n_ref ? k_pf_count<true> : k_pf_count<false>), dim3(pf_blocks(p.M)), dim3(PF_THREADS), 0, c->stream, w.kb.get(), p.M,
                            w.runoff.get(), p.D, n, r0, r1, w.mat.get(), (const u32*)w.runsplit.get(), n_ref);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
         return LZANI_OK;
+    }
+    // What compact_tile and compact_sparse end in.  read_rowoff: the offsets of the tile's nr rows, tile-relative, from
+    // rowoff into h_off[0 .. nr].  publish_tile: the tile joins the result behind the tiles so far -- its rows' offsets
+    // into pf.row_off, its entries (h_off[nr]) into info.entries.
+    int read_rowoff(u32 nr)
+    {
+        h_off.resize((size_t)nr + 1);
+        HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return LZANI_OK;
+    }
+    void publish_tile(PrefilterTile&& tile)
+    {
+        const u32 nr = tile.r1 - tile.r0;
+        for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)tile.r0 + r + 1] = info.entries + h_off[r + 1];
+        info.entries += h_off[nr];                                 // (the kept pairs of the tiles so far)
+        pf.tiles.push_back(std::move(tile));
+        ++info.tiles;
     }
     // the kept entries of the tile's rows into a PrefilterTile of their own
     int compact_tile(u32 r0, u32 r1)
@@ -342,8 +370,7 @@ struct PfRun {
                            pf.kmers_of.get(), min_shared, min_ratio, w.rowcnt.get(), w.rowoff.get(), (u32*)nullptr, (u32*)nullptr, n_ref);
         hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, w.rowcnt.get(), (u64)nr, w.rowoff.get());
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (int rc = read_rowoff(nr)) return rc;
         PrefilterTile tile;
         tile.r0 = r0; tile.r1 = r1;
         HIPCHK(c, tile.ids.alloc(h_off[nr]));
@@ -352,10 +379,7 @@ struct PfRun {
                            pf.kmers_of.get(), min_shared, min_ratio, w.rowcnt.get(), w.rowoff.get(), tile.ids.get(), tile.shared.get(), n_ref);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
-        for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = info.entries + h_off[r + 1];
-        info.entries += h_off[nr];                                 // (the kept pairs of the tiles so far)
-        pf.tiles.push_back(std::move(tile));
-        ++info.tiles;
+        publish_tile(std::move(tile));
         return LZANI_OK;
     }
 
@@ -365,28 +389,28 @@ struct PfRun {
     {
         sparse = c->pf_counting == LZANI_PF_COUNTING_SPARSE;
         if (c->pf_counting != LZANI_PF_COUNTING_AUTO || env_u64("LZANI_PREFILTER_TILE_ROWS")) return LZANI_OK;
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        u64 free_b = 0;
+        if (int rc = pf_free_bytes(c, free_b)) return rc;
         sparse = dense_rows(free_b) < n_rows;
         return LZANI_OK;
     }
     // the slots of the pair table from what is free now, and the table's buffers
     int alloc_table()
     {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        u64 free_b = 0;
+        if (int rc = pf_free_bytes(c, free_b)) return rc;
         const u64 cells = (u64)n_rows * n_cols;                    // (< 2^64)
         u64 top = 2;                                               // the smallest power of two >= 2 * cells, 2^32 at most
         while (top < ((u64)1 << 32) && top / 2 < cells) top *= 2;
         slots = 0;
-        for (u64 s = 2; s <= top && 12 * s <= (u64)free_b / 2; s *= 2) slots = s;
+        for (u64 s = 2; s <= top && 12 * s <= free_b / 2; s *= 2) slots = s;
         if (const auto forced = env_u64("LZANI_PREFILTER_TABLE_SLOTS")) slots = *forced;      // (checked in run())
         if (!slots) return fail(c, LZANI_ERR_NOMEM, "lzani_prefilter: no room for a pair table of two slots");
         HIPCHK(c, w.sp_keys.alloc(slots));
         HIPCHK(c, w.sp_cnt.alloc(slots));
         HIPCHK(c, w.sp_ctl.alloc(2));
-        HIPCHK(c, w.sp_bcnt.alloc((slots + PF_CHUNK - 1) / PF_CHUNK));
-        HIPCHK(c, w.sp_boff.alloc((slots + PF_CHUNK - 1) / PF_CHUNK + 1));
+        HIPCHK(c, w.sp_bcnt.alloc(pf_chunks(slots)));
+        HIPCHK(c, w.sp_boff.alloc(pf_chunks(slots) + 1));
         sp.sparse = 1; sp.slots = slots; sp.table_bytes = w.sp_keys.bytes() + w.sp_cnt.bytes();
         return LZANI_OK;
     }
@@ -400,7 +424,7 @@ struct PfRun {
             HIPCHK(c, hipMemsetAsync(w.sp_cnt, 0, (size_t)slots * 4, c->stream));
             HIPCHK(c, hipMemsetAsync(w.sp_ctl, 0, 8, c->stream));
         }
-        hipLaunchKernelGGL((n_ref ? k_pf_count_sparse<true> : k_pf_count_sparse<false>), dim3((u32)((p.M + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream,
+        hipLaunchKernelGGL((n_ref ? k_pf_count_sparse<true> : k_pf_count_sparse<false>), dim3(pf_blocks(p.M)), dim3(PF_THREADS), 0, c->stream,
                            w.kb.get(), p.M, w.runoff.get(), p.D, n, r0, r1, w.sp_keys.get(), w.sp_cnt.get(), slots, w.sp_ctl.get(), (const u32*)w.runsplit.get(), n_ref);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, clk.end());
@@ -414,7 +438,7 @@ struct PfRun {
     // compact_tile from the pair table: the kept keys, sorted (row after row, ascending b), their ids and counts, the rows' offsets
     int compact_sparse(u32 r0, u32 r1)
     {
-        const u32 nr = r1 - r0, blocks = (u32)((slots + PF_CHUNK - 1) / PF_CHUNK);
+        const u32 nr = r1 - r0, blocks = (u32)pf_chunks(slots);
         u64 K = 0;
         HIPCHK(c, clk.begin(PF_ST_COMPACT));
         hipLaunchKernelGGL(k_pf_sparse_kept<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, w.sp_keys.get(), w.sp_cnt.get(), slots, pf.kmers_of.get(), min_shared,
@@ -432,19 +456,14 @@ struct PfRun {
                            min_ratio, w.sp_bcnt.get(), w.sp_boff.get(), w.sp_kin.get());
         HIPCHK(c, hipGetLastError());
         if (int rc = sort_keys(c, w.sp_tmp, w.sp_kin, w.sp_kout, K, 1, 0, bits, "lzani_prefilter: sort", false)) return rc;
-        if (K) hipLaunchKernelGGL(k_pf_sparse_fetch, dim3((u32)((K + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, c->stream, w.sp_kout.get(), K, w.sp_keys.get(),
+        if (K) hipLaunchKernelGGL(k_pf_sparse_fetch, dim3(pf_blocks(K)), dim3(PF_THREADS), 0, c->stream, w.sp_kout.get(), K, w.sp_keys.get(),
                                   w.sp_cnt.get(), slots, tile.ids.get(), tile.shared.get());
         hipLaunchKernelGGL(k_pf_sparse_rowoff, dim3(nr / PF_THREADS + 1), dim3(PF_THREADS), 0, c->stream, w.sp_kout.get(), K, r0, nr, w.rowoff.get());
         HIPCHK(c, hipGetLastError());
-        h_off.resize((size_t)nr + 1);
-        HIPCHK(c, hipMemcpyAsync(h_off.data(), w.rowoff, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (int rc = read_rowoff(nr)) return rc;
         HIPCHK(c, clk.end());
         if (h_off[nr] != K) return fail(c, LZANI_ERR_DEVICE, "lzani_prefilter: the pair table's kept keys lie outside the tile's rows");
-        for (u32 r = 0; r < nr; ++r) pf.row_off[(size_t)r0 + r + 1] = info.entries + h_off[r + 1];
-        info.entries += K;
-        pf.tiles.push_back(std::move(tile));
-        ++info.tiles;
+        publish_tile(std::move(tile));
         sp.pairs_seen += sp_used;
         sp.max_fill = std::max<u64>(sp.max_fill, sp_used);
         return LZANI_OK;
@@ -560,7 +579,7 @@ struct PfRun {
 
         // chunks of PF_CHUNK forward positions, genome after genome
         std::vector<u64> cbase((size_t)n + 1, 0);
-        for (u32 g = 0; g < n; ++g) cbase[g + 1] = cbase[g] + (len_of(g) + PF_CHUNK - 1) / PF_CHUNK;
+        for (u32 g = 0; g < n; ++g) cbase[g + 1] = cbase[g] + pf_chunks(len_of(g));
         n_chunks = cbase[n];
         HIPCHK(c, w.cbase.alloc((size_t)n + 1));
         HIPCHK(c, w.blkcnt.alloc(n_chunks));
@@ -576,9 +595,9 @@ struct PfRun {
         pinfo.cap = PF_MAX_PASS_WINDOWS;
         if (const auto forced_cap = env_u64("LZANI_PREFILTER_MAX_WINDOWS")) pinfo.cap = *forced_cap;
         else {                                                     // a quarter of the free device memory for the 24 B per window (a choice, not a measurement)
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-            pinfo.cap = std::min<u64>(pinfo.cap, (u64)free_b / 4 / 24);
+            u64 free_b = 0;
+            if (int rc = pf_free_bytes(c, free_b)) return rc;
+            pinfo.cap = std::min<u64>(pinfo.cap, free_b / 4 / 24);
         }
         info.positions = Pv;
         // ---- the plan.  One pass is {0, PF_BINS} with the unranged kernels and no histogram.  No kept window: no pass runs,
@@ -670,9 +689,9 @@ int prefilter_streamed(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, co
     if (int rc = pf_drop_last(c, "lzani_prefilter_codes", n, n_ref)) return rc;
     if (const auto forced = env_u64("LZANI_PREFILTER_SLICE_BYTES")) slice_bytes = *forced;
     if (slice_bytes == 0) {                                    // automatic: an eighth of the free device memory (a choice, not a measurement)
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        slice_bytes = std::max<u64>(1, std::min<u64>(total, std::max<u64>(Lmax, (u64)free_b / 8)));
+        u64 free_b = 0;
+        if (int rc = pf_free_bytes(c, free_b)) return rc;
+        slice_bytes = std::max<u64>(1, std::min<u64>(total, std::max<u64>(Lmax, free_b / 8)));
     }
     PfStream st;
     st.codes = codes; st.len = len;

@@ -1,7 +1,8 @@
 """GPU: sparse counting of the k-mer prefilter (lzani_set_prefilter_counting, LZANI_PREFILTER_TABLE_SLOTS) against the dense
 one-pass result of the same context, byte for byte, and against the numpy statement of the definitions
 (tests/prefilter_model.py, tests/prefilter_cross_model.py); the tiles and attempts against the statement of the tile rule
-(tests/prefilter_sparse_model.py).  All four entry points, one pass and several, a table that is nearly full, tables that
+(tests/prefilter_sparse_model.py).  All four entry points, one pass and several, a table that is nearly full, tables of several
+compaction blocks and scan steps, tables that
 overflow and halve the tile, one that cannot hold a row, and the host binary."""
 import os
 import subprocess
@@ -171,6 +172,28 @@ def test_a_full_table(resident, monkeypatch):
         info = _check(resident, k, smax, min_shared, min_ratio, base, base_info, "full table")
         si = resident.prefilter_sparse_info()
         assert info["tiles"] == 1 and si == dict(sparse=1, attempts=1, pass_runs=1, slots=512, table_bytes=12 * 512, pairs_seen=231, max_fill=231)
+
+
+@pytest.mark.parametrize("slots, n_ref", [(4096, 0), (8192, 0), (1 << 22, 0), (1 << 23, 0), (8192, 9), (1 << 23, 9)])
+def test_a_table_of_several_blocks(resident, monkeypatch, slots, n_ref):
+    """The compaction of the table over more than one block of 4,096 slots, and the scan of its block counts over more
+    than one step of 1,024.  4096: one full block, its loop never breaks; 8192: two blocks, the second writes from a
+    non-zero offset; 2^22: 1,024 block counts, exactly one scan step; 2^23: 2,048, the scan's carry is used."""
+    k, smax = 21, PM.SAMPLE_ALL
+    seen = int(pairs_of(k, smax, n_ref).sum())
+    assert seen == (8 if n_ref else 35)
+    for min_shared, min_ratio in THRESHOLDS:
+        base, base_info = baseline(resident, k, smax, min_shared, min_ratio, n_ref)
+        resident.set_prefilter_counting("sparse")
+        monkeypatch.setenv("LZANI_PREFILTER_TABLE_SLOTS", str(slots))
+        if n_ref:
+            resident.prefilter_cross(k, n_ref, smax, min_shared, min_ratio)
+        else:
+            resident.prefilter(k, smax, min_shared, min_ratio)
+        monkeypatch.delenv("LZANI_PREFILTER_TABLE_SLOTS")
+        info = _check(resident, k, smax, min_shared, min_ratio, base, base_info, ("several blocks", slots, n_ref), n_ref)
+        si = resident.prefilter_sparse_info()
+        assert info["tiles"] == 1 and si == dict(sparse=1, attempts=1, pass_runs=1, slots=slots, table_bytes=12 * slots, pairs_seen=seen, max_fill=seen)
 
 
 @pytest.mark.parametrize("slots, tiles, attempts", [(256, 2, 3), (32, 24, 28)])
