@@ -37,7 +37,7 @@ struct CandSink { u32* cbits; u64 words; u32* pcount; u32 counted_batches; };
 // set this large: the probe / join form, batch by batch), and where a buffer (matrix, pair table, bitmaps) cannot be had
 // after all -- the sizing is an estimate, and an allocation may fail on a fragmented heap: the bitmap buffers are then
 // released (the probe / join form needs none of them).
-int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
+int plan_bitmaps(lzani_ctx* c, const RunGenomes& g, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
 {
     // (from 32 rows on where the probe form with tag words is the alternative; from 8 rows where it is the rounds of the
     // first kernel: genomes whose tags do not fit a tag byte -- 260 kbp to 2 Mbp at mal 15, viral sizes at mal 13+.
@@ -54,7 +54,7 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
     const u64 min_share = k.pm_min_share.value_or(c->gs.lay.tw_stride ? 48 : 2);
     const bool lists_ok = !lists || (!f.lists_dup && f.n_pairs >= min_share * f.lists_involved);
     if (!(!regions && lists_ok && c->gs.tab.kmL && c->gs.lay.bk_stride && c->P.mqd + c->P.mrd <= 128 && c->gs.geo.kb <= 30 &&
-          c->gs.n >= 2 && n_rows >= min_rows && k.pm))
+          g.n >= 2 && n_rows >= min_rows && k.pm))
         return LZANI_OK;
     u64 max_row = 0;
     for (u32 r = 0; r < n_rows; ++r) max_row = std::max<u64>(max_row, row_off[r + 1] - row_off[r]);
@@ -62,7 +62,7 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
     p.cb_words = (u64)p.pm_tiles * PM_TILE_WORDS;
     p.pm_group = p.pm_bits <= 27 ? (u32)PM_GROUP : 128u;                    // 64-byte rows up to 2^27 of them (8 GB), 16-byte rows beyond (16 GB at 2^30)
     const size_t m_bytes = ((size_t)1 << p.pm_bits) * (p.pm_group / 8);
-    const size_t x_bytes = lists ? ((size_t)c->gs.n * p.pm_group + 2 * (size_t)c->gs.n + 64) * 4 : 0;   // pair table, query flags, list, count
+    const size_t x_bytes = lists ? ((size_t)g.n * p.pm_group + 2 * (size_t)g.n + 64) * 4 : 0;   // pair table, query flags, list, count
     const size_t per_pair = (size_t)p.cb_words * 4;
     const double avg_row = (double)f.n_pairs / n_rows;
     const size_t per_slot = (size_t)slot_bytes(c->gs).total();
@@ -90,7 +90,7 @@ int plan_bitmaps(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, co
     if (rc) return rc;
     u32 rows_cap = c->sl.slots;
     if (!lists) {                                            // dense rows: whole groups of references, if there are several batches
-        u64 r = std::min<u64>(rows_cap, cap_pairs / (u64)(c->gs.n - 1));
+        u64 r = std::min<u64>(rows_cap, cap_pairs / (u64)(g.n - 1));
         if (r < n_rows && r > p.pm_group) r -= r % p.pm_group;
         rows_cap = (u32)std::max<u64>(r, 1);
     }
@@ -153,6 +153,7 @@ int candidate_stage(RunCtx& r, Batch& bt)
     lzani_ctx* c = r.c;
     const RunPlan& p = r.p;
     const int pm_bits = p.pm_bits;
+    const u32 n = r.g.n;                                     // genomes of the run's table
     for (u32 g0 = 0; g0 < bt.rows; g0 += p.pm_group) {
         PmArgs pg;
         pg.G = gtab(c);
@@ -160,14 +161,14 @@ int candidate_stage(RunCtx& r, Batch& bt)
         pg.slot0 = g0; pg.rows = std::min<u32>(p.pm_group, bt.rows - g0);
         pg.M = c->cs.d_pm; pg.rw = ((pg.rows + 127) / 128) * 4; pg.mmask = (u32)lowmask(pm_bits); pg.rshift = c->gs.geo.kb - pm_bits;
         pg.mal = c->P.mal; pg.mrd = c->P.mrd;
-        pg.cbits = c->cs.d_pm_cbits; pg.cb_words = p.cb_words; pg.e0 = bt.e0; pg.n = c->gs.n; pg.q0 = 0;
+        pg.cbits = c->cs.d_pm_cbits; pg.cb_words = p.cb_words; pg.e0 = bt.e0; pg.n = n; pg.q0 = 0;
         pg.query_ids = r.d_q; pg.pidx = nullptr; pg.qflag = pg.qlist = pg.qcount = nullptr;
         pg.pcount = bt.lpt ? c->cs.d_lpt_cnt : nullptr;
         if (r.query_ids) {                                   // the lists of the group's rows -> pair table + the queries involved
-            const size_t tab = (size_t)c->gs.n * 32 * pg.rw;
-            pg.pidx = c->cs.d_pm_pidx; pg.qflag = c->cs.d_pm_pidx + (size_t)c->gs.n * p.pm_group; pg.qlist = pg.qflag + c->gs.n; pg.qcount = pg.qlist + c->gs.n;
+            const size_t tab = (size_t)n * 32 * pg.rw;
+            pg.pidx = c->cs.d_pm_pidx; pg.qflag = c->cs.d_pm_pidx + (size_t)n * p.pm_group; pg.qlist = pg.qflag + n; pg.qcount = pg.qlist + n;
             HIPCHK(c, hipMemsetAsync(pg.pidx, 0xFF, tab * 4, c->stream));
-            HIPCHK(c, hipMemsetAsync(pg.qflag, 0, ((size_t)2 * c->gs.n + 1) * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(pg.qflag, 0, ((size_t)2 * n + 1) * 4, c->stream));
             hipLaunchKernelGGL(k_pm_pairs, dim3(pg.rows), dim3(256), 0, c->stream, pg);
         }
         // the matrix: from the group's indexes, chunk by chunk through LDS (long genomes: no global atomics, no clearing),
@@ -195,9 +196,9 @@ int candidate_stage(RunCtx& r, Batch& bt)
         // (query lists: one row of blocks per query that occurs in the group -- counted here, the device list is
         // k_pm_pairs' -- not per genome: 20,000 genomes x 44 tiles of blocks that find nothing to do were most of
         // the candidate stage of a filtered run)
-        u32 nq = c->gs.n;
+        u32 nq = n;
         if (r.query_ids) {
-            if (r.grp_seen.size() != c->gs.n) r.grp_seen.assign(c->gs.n, 0xFFFFFFFFu);
+            if (r.grp_seen.size() != n) r.grp_seen.assign(n, 0xFFFFFFFFu);
             const u32 stamp = ++r.grp_stamp;
             nq = 0;
             for (u64 e = r.row_off[bt.k0 + g0]; e < r.row_off[bt.k0 + g0 + pg.rows]; ++e)

@@ -11,7 +11,8 @@
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
 // (batches, queues, the split rule, the bytes of a slab slot) in lzani_run_plan.h, which pair kernel a launch takes (the
 // table of the instantiations, choose_pair_kernel) in lzani_pair_dispatch.h, those of a genome set (the set-level
-// switches, the form of the index, footprints, the block plan, residency, the slot count of the slabs) in lzani_set_plan.h.
+// switches, the form of the index, footprints, the block plan, residency, the slot count of the slabs) in lzani_set_plan.h,
+// those of an out-of-core run (the order of its tiles, their local tables, the tables of an upload) in lzani_tile_plan.h.
 // Device memory and events have one owner each, lzani_devmem.h.  Five layers of the host side are files of their own,
 // included at fixed places below:
 //   lzani_index.h       the index stage: genome upload, slabs, k-mer words, join lists, the index build, its test hooks
@@ -22,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -65,6 +67,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_run_plan.h"
 #include "lzani_pair_dispatch.h"
 #include "lzani_set_plan.h"
+#include "lzani_tile_plan.h"
 
 // ============================================================================================
 // Host side of the C-ABI
@@ -142,8 +145,9 @@ struct GenomeSet {
     DevMem<unsigned char> d_jtmp; // radix-sort scratch (join lists, the sort-based index build, ticket order)
 
     // Out-of-core genome sets (lzani_ooc.h): the set stays on the host and the runs go tile by tile over
-    // (reference block, query block).  Outside a run n / L describe the whole set; the device tables above then
-    // describe the resident region (two halves, A and B, of half_words packed words each).
+    // (reference block, query block).  n / L describe the whole set at all times -- a tile's run is given its local
+    // table as a RunGenomes -- and the device tables above the resident region (two halves, A and B, of half_words
+    // packed words each).
     u64 mem_limit = 0;            // the limit applied to this set (0: automatic mode kept it in-core)
     bool ooc = false;
     std::vector<uint8_t> h_codes;                 // host copy of the set's codes, genome after genome
@@ -159,6 +163,10 @@ struct GenomeSet {
     DevMem<u64> d_up_tab;                         // an upload's code offsets and word offsets (2 x half_genomes)
     DevMem<int> d_up_L;                           // ... lengths, and N flags written by k_pack (2 x half_genomes)
 };
+
+// The genome table of one run, count and lengths: the set's own (run_genomes_of) or, out-of-core, a tile's local one
+// (lzani_tile_plan.h).  run_rows_impl and everything below it go by this, never by gs.n / gs.L.
+struct RunGenomes { u32 n; const int* L; };
 
 // The index slabs: grown by ensure_slabs, dropped with the genome set.
 struct IndexSlabs {
@@ -403,22 +411,22 @@ hipError_t launch_row(lzani_ctx* c, int row, dim3 gd, dim3 bd, void** args, size
 struct RowFacts { u64 n_pairs = 0; bool lists_dup = false; u64 lists_involved = 0; };
 
 // The checks of a run's rows (n_rows > 0) against the genome set; the query ids in one pass.
-int check_rows(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids, RowFacts& f)
+int check_rows(lzani_ctx* c, const RunGenomes& g, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids, RowFacts& f)
 {
     for (u32 k = 0; k < n_rows; ++k) {
-        if (ref_ids[k] >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: reference id out of range");
+        if (ref_ids[k] >= g.n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: reference id out of range");
         if (row_off[k + 1] < row_off[k]) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off not monotone");
-        if (!query_ids && row_off[k + 1] - row_off[k] != (u64)c->gs.n - 1)
+        if (!query_ids && row_off[k + 1] - row_off[k] != (u64)g.n - 1)
             return fail(c, LZANI_ERR_ARG, "lzani_run_rows: dense row must have n-1 queries");
     }
     if (row_off[0] != 0) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: row_off[0] must be 0");
     f.n_pairs = row_off[n_rows];
     if (query_ids) {
-        std::vector<u32> in_row(c->gs.n, 0xFFFFFFFFu), in_group(c->gs.n, 0xFFFFFFFFu);
+        std::vector<u32> in_row(g.n, 0xFFFFFFFFu), in_group(g.n, 0xFFFFFFFFu);
         for (u32 k = 0; k < n_rows; ++k)
             for (u64 e = row_off[k]; e < row_off[k + 1]; ++e) {
                 const u32 q = query_ids[e];
-                if (q >= c->gs.n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: query id out of range");
+                if (q >= g.n) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: query id out of range");
                 f.lists_dup |= in_row[q] == k;
                 in_row[q] = k;
                 if (in_group[q] != k / PM_GROUP) { in_group[q] = k / PM_GROUP; ++f.lists_involved; }
@@ -444,6 +452,7 @@ struct CandSink;                                  // lzani_dense.h
 // What the batches of one run share: its rows and queues on the device, the launch geometry, the kernels of its tuple.
 struct RunCtx {
     lzani_ctx* c;
+    RunGenomes g;                                            // the genome table of the run
     const Knobs& k;
     const RunPlan& p;
     const RegionSink* rs; const u64* row_off; const u32* query_ids; int* d_out;     // the call's arguments
@@ -468,17 +477,17 @@ namespace {
 
 // The plan of a run: candidate bitmaps where the rows qualify and their buffers can be had, else the probe / join form;
 // batches of as many consecutive rows as there are index slabs (and, with bitmaps, as their pairs' bitmaps may take).
-int plan_run(lzani_ctx* c, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
+int plan_run(lzani_ctx* c, const RunGenomes& g, const Knobs& k, const RowFacts& f, u32 n_rows, const u64* row_off, bool lists, bool regions, RunPlan& p)
 {
-    for (u32 g = 0; g < c->gs.n; ++g) p.Lmax = std::max(p.Lmax, c->gs.L[g]);
+    for (u32 x = 0; x < g.n; ++x) p.Lmax = std::max(p.Lmax, g.L[x]);
     // rows of the presence matrix: one per k-mer (exact: the mixer is a bijection on the key bits) where the genomes fill a fair
     // part of the key space, else the hash's top bits -- 2^9 rows per text position keep the false candidates below 0.2 % of the
     // query positions, and a group's matrix is cleared and built in proportion to the genomes, not to 4^mal
     p.pm_bits = std::min(std::min(c->gs.geo.kb, 30), ceil_log2((u64)std::max(c->gs.Tmax, 1)) + 9);
-    int rc = plan_bitmaps(c, k, f, n_rows, row_off, lists, regions, p);
+    int rc = plan_bitmaps(c, g, k, f, n_rows, row_off, lists, regions, p);
     if (rc || p.pm) return rc;
     p.use_join = c->gs.lay.join_mode;
-    if (p.use_join) { rc = ensure_join(c); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
+    if (p.use_join) { rc = ensure_join(c, g); if (rc) return rc; }          // (before the slabs are sized: they take 60 % of what is left)
     rc = ensure_slabs(c, n_rows);
     if (rc) return rc;
     cut_batches(n_rows, row_off, c->sl.slots, ~0ull, p.bstart);
@@ -710,17 +719,19 @@ int finish_run(lzani_ctx* c, u64 n_pairs, const lzani_rtc::Kernel* rtc_k, const 
     return LZANI_OK;
 }
 
-// A run of rows on the resident genome set: check, plan, queues and uploads, then the batches back to back on the stream,
-// then one wait.
-int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
+RunGenomes run_genomes_of(const lzani_ctx* c) { return RunGenomes{c->gs.n, c->gs.L.data()}; }     // the set's own table
+
+// A run of rows on the resident genomes, whose table is g: check, plan, queues and uploads, then the batches back to back
+// on the stream, then one wait.
+int run_rows_impl(lzani_ctx* c, const RunGenomes& g, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
                   int* d_out, const RegionSink* rs = nullptr, CandSink* sink = nullptr, RunPlan* plan_out = nullptr)
 {
-    if (!c->gs.n) return fail(c, LZANI_ERR_STATE, "lzani_run_rows: no genomes set");
+    if (!g.n) return fail(c, LZANI_ERR_STATE, "lzani_run_rows: no genomes set");
     c->run = RunRecord{};
     const Knobs k{};
     if (n_rows == 0) return LZANI_OK;
     RowFacts rf;
-    int rc = check_rows(c, n_rows, ref_ids, row_off, query_ids, rf);
+    int rc = check_rows(c, g, n_rows, ref_ids, row_off, query_ids, rf);
     const u64 n_pairs = rf.n_pairs;
     if (rc || n_pairs == 0) return rc;
 
@@ -731,7 +742,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
     rc = ensure_kmers(c);
     if (rc) return rc;
     RunPlan p;
-    rc = plan_run(c, k, rf, n_rows, row_off, query_ids != nullptr, rs != nullptr, p);
+    rc = plan_run(c, g, k, rf, n_rows, row_off, query_ids != nullptr, rs != nullptr, p);
     if (rc) return rc;
     if (plan_out) *plan_out = p;
 
@@ -780,7 +791,7 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
         if (!rtc_k && c->rtc.failed) TRACE("run-time compile unavailable (%s): the generic kernel runs", c->rtc.log.c_str());
     }
 
-    RunCtx r{c, k, p, rs, row_off, query_ids, d_out, d_ref, d_q, d_qorder, d_off, d_qcum, max_blocks, dsel, d_cbits, cbits_stride, rtc_k};
+    RunCtx r{c, g, k, p, rs, row_off, query_ids, d_out, d_ref, d_q, d_qorder, d_off, d_qcum, max_blocks, dsel, d_cbits, cbits_stride, rtc_k};
     r.sink = sink;
     for (u32 b = 0; b < n_batches; ++b) {
         const u32 k0 = p.bstart[b], k1 = p.bstart[b + 1];
@@ -793,6 +804,25 @@ int run_rows_impl(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_o
 }  // namespace
 
 #include "lzani_ooc.h"
+
+namespace {
+
+// The one fork of the run entry points: tile by tile for an out-of-core set -- results to d_out (device) and / or h_out
+// (host) -- else one run on the set's own table, whose results go to d_out or, where the caller gave a host buffer, to
+// *d_res, made here for the caller to copy out (null with a null h_out).  Sets the tile count of lzani_get_residency.
+int run_rows_any(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
+                 int* d_out, lzani_result* h_out, DevMem<lzani_result>* d_res, const RegionSink* rs)
+{
+    if (c->gs.ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, d_out, h_out, rs);
+    const u64 n_pairs = n_rows ? row_off[n_rows] : 0;
+    if (h_out && n_pairs) { HIPCHK(c, d_res->alloc(n_pairs)); d_out = (int*)d_res->get(); }
+    const int rc = run_rows_impl(c, run_genomes_of(c), n_rows, ref_ids, row_off, query_ids, d_out, rs);
+    c->res.tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
+    return rc;
+}
+
+}  // namespace
+
 #include "lzani_prefilter.h"
 
 extern "C" {
@@ -903,10 +933,7 @@ int lzani_run_rows_device(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids
     if (!c) return LZANI_ERR_ARG;
     if (!ref_ids || !row_off || (!d_out && n_rows && row_off[n_rows]))
         return fail(c, LZANI_ERR_ARG, "lzani_run_rows_device: null argument");
-    if (c->gs.ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out, nullptr, nullptr);
-    const int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out);
-    c->res.tiles = rc == LZANI_OK && n_rows && row_off[n_rows] ? 1 : 0;
-    return rc;
+    return run_rows_any(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out, nullptr, nullptr, nullptr);
 }
 
 int lzani_run_rows(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids, const uint64_t* row_off,
@@ -917,13 +944,10 @@ int lzani_run_rows(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_ids, const
     const u64 n_pairs = n_rows ? row_off[n_rows] : 0;
     if (n_pairs && !out) return fail(c, LZANI_ERR_ARG, "lzani_run_rows: null output");
     HIPCHK(c, hipSetDevice(c->dev));
-    if (c->gs.ooc) return run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, nullptr);     // (host scatter)
-    DevMem<lzani_result> d_out;
-    if (n_pairs) HIPCHK(c, d_out.alloc(n_pairs));
-    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.get());
-    c->res.tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
-    if (rc == LZANI_OK && n_pairs) {
-        hipError_t e = hipMemcpy(out, d_out.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
+    DevMem<lzani_result> d_res;
+    int rc = run_rows_any(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, &d_res, nullptr);
+    if (rc == LZANI_OK && d_res) {
+        hipError_t e = hipMemcpy(out, d_res.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy results: ") + hipGetErrorString(e));
     }
     return rc;
@@ -940,24 +964,18 @@ int lzani_run_rows_regions(lzani_ctx* c, uint32_t n_rows, const uint32_t* ref_id
     if (n_pairs && !out) return fail(c, LZANI_ERR_ARG, "lzani_run_rows_regions: null output");
     *n_regions = 0;
     HIPCHK(c, hipSetDevice(c->dev));
-    DevMem<lzani_result> d_out;
+    DevMem<lzani_result> d_res;
     DevMem<lzani_region> d_regions;
     DevMem<unsigned long long> d_count;
-    if (n_pairs && !c->gs.ooc) HIPCHK(c, d_out.alloc(n_pairs));      // (out-of-core: tile by tile)
     HIPCHK(c, d_regions.alloc(capacity));
     HIPCHK(c, d_count.alloc(1));
     HIPCHK(c, hipMemset(d_count.get(), 0, sizeof(unsigned long long)));
     RegionSink rs{d_regions.get(), d_count.get(), capacity};
-    int rc;
-    if (c->gs.ooc) rc = run_rows_tiled(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, &rs);
-    else {
-        rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.get(), &rs);
-        c->res.tiles = rc == LZANI_OK && n_pairs ? 1 : 0;
-    }
+    int rc = run_rows_any(c, n_rows, ref_ids, row_off, query_ids, nullptr, out, &d_res, &rs);
     if (rc == LZANI_OK) {
         unsigned long long cnt = 0;
         hipError_t e = hipMemcpy(&cnt, rs.d_count, sizeof cnt, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && n_pairs && !c->gs.ooc) e = hipMemcpy(out, d_out.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && d_res) e = hipMemcpy(out, d_res.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e == hipSuccess && cnt && capacity)
             e = hipMemcpy(regions, rs.d_regions, std::min<uint64_t>(cnt, capacity) * sizeof(lzani_region), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy regions: ") + hipGetErrorString(e));
@@ -1101,7 +1119,7 @@ int lzani_debug_run_candidates(lzani_ctx* c, uint32_t n_rows, const uint32_t* re
     if (n_pairs) HIPCHK(c, d_out.alloc(n_pairs));
     CandSink sink{cbits, words, pcount, 0};
     RunPlan p;
-    int rc = run_rows_impl(c, n_rows, ref_ids, row_off, query_ids, (int*)d_out.get(), nullptr, &sink, &p);
+    int rc = run_rows_impl(c, run_genomes_of(c), n_rows, ref_ids, row_off, query_ids, (int*)d_out.get(), nullptr, &sink, &p);
     if (rc == LZANI_OK && n_pairs) {
         hipError_t e = hipMemcpy(out, d_out.get(), n_pairs * sizeof(lzani_result), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, LZANI_ERR_DEVICE, std::string("copy results: ") + hipGetErrorString(e));

@@ -157,13 +157,13 @@ int ensure_slabs(lzani_ctx* c, u32 want_rows)
 // once per run, behind k_kmers (it is part of the path's work like the k-mer words it is made from).
 // the resident part of the join lists (the sorted keys: 8 B per forward position), allocated before the index slabs are
 // sized so that those see what is really left
-int alloc_join_lists(lzani_ctx* c)
+int alloc_join_lists(lzani_ctx* c, const RunGenomes& g)
 {
-    const u32 n = c->gs.n;
+    const u32 n = g.n;
     if (c->gs.jl.keys) return LZANI_OK;
     JoinLists jl;                                        // (moved into the set whole, or not at all)
     jl.h_koff.assign((size_t)n + 1, 0);
-    for (u32 g = 0; g < n; ++g) jl.h_koff[g + 1] = jl.h_koff[g] + (u64)c->gs.L[g];
+    for (u32 x = 0; x < n; ++x) jl.h_koff[x + 1] = jl.h_koff[x] + (u64)g.L[x];
     HIPCHK(c, jl.koff.alloc((size_t)n + 1));
     HIPCHK(c, jl.soff.alloc((size_t)n + 1));
     HIPCHK(c, jl.cnt.alloc(n));
@@ -173,16 +173,16 @@ int alloc_join_lists(lzani_ctx* c)
     return LZANI_OK;
 }
 
-int build_join_lists(lzani_ctx* c)
+int build_join_lists(lzani_ctx* c, const RunGenomes& g)
 {
-    const u32 n = c->gs.n;
-    int rc0 = alloc_join_lists(c);
+    const u32 n = g.n;
+    int rc0 = alloc_join_lists(c, g);
     if (rc0) return rc0;
     // the unsorted keys live for the duration of the sort only (as much again as the lists themselves)
     DevMem<unsigned long long> keys_in;
     HIPCHK(c, keys_in.alloc(c->gs.jl.h_koff[n]));
     int Lmax = 0;
-    for (u32 g = 0; g < n; ++g) Lmax = std::max(Lmax, c->gs.L[g]);
+    for (u32 x = 0; x < n; ++x) Lmax = std::max(Lmax, g.L[x]);
     // An invalid key is all ones; the sort looks at the bits [posbits, shift_g + gbits) only, so no real genome number may
     // be all ones in gbits bits, or its keys with the all-ones hash would be indistinguishable from the invalid keys of
     // the genomes before it (found by the fuzz at n = 4: genome 3 lost the k-mers of its last bucket)
@@ -205,10 +205,10 @@ int build_join_lists(lzani_ctx* c)
     for (u32 g0 = 0; g0 < n;) {
         u32 g1 = g0;
         u64 keys = 0;
-        while (g1 < n && (g1 == g0 || keys + (u64)c->gs.L[g1] <= (1ull << 30))) keys += (u64)c->gs.L[g1++];
+        while (g1 < n && (g1 == g0 || keys + (u64)g.L[g1] <= (1ull << 30))) keys += (u64)g.L[g1++];
         if (keys > 0x7FFFFFF0ull) return fail(c, LZANI_ERR_ARG, "join lists: a genome of more than 2^31 positions");
         u64 at = c->gs.jl.h_koff[g0];
-        for (u32 g = g0; g < g1; ++g) { soff[g] = at; at += valid[g]; }
+        for (u32 x = g0; x < g1; ++x) { soff[x] = at; at += valid[x]; }
         if (g1 == n) soff[n] = at;
         if (keys)
             if (int rc = sort_keys(c, c->gs.d_jtmp, keys_in + c->gs.jl.h_koff[g0], c->gs.jl.keys + c->gs.jl.h_koff[g0], keys, 1, c->gs.geo.posbits, shift_g + gbits,
@@ -227,7 +227,8 @@ int build_join_lists(lzani_ctx* c)
 // Per-genome k-mer words (and, for long genomes, the sorted join lists made from them): once per genome set, by the
 // first run after lzani_set_genomes -- before its index slabs are sized, so that the slabs see what the lists and the
 // sort's temporaries have left -- and kept for the runs that follow (they depend on the genomes and the parameters
-// only).  Timed on their own (lzani_timing.kmers_ms).
+// only).  Timed on their own (lzani_timing.kmers_ms).  They belong to the set, not to a run: made for gs.n genomes, in-core
+// only (out-of-core, every block upload makes its own and kmers_ready is set from the start).
 int ensure_kmers(lzani_ctx* c)
 {
     if (!c->gs.tab.kmL || c->gs.kmers_ready) return LZANI_OK;
@@ -244,13 +245,13 @@ int ensure_kmers(lzani_ctx* c)
 // The sorted join lists of a long-genome set (join form of candidate detection): made by the first run that needs them
 // -- dense rows take their candidates from the presence matrix instead -- and kept like the k-mer words they are made
 // from; their time is part of that run's kmers_ms.
-int ensure_join(lzani_ctx* c)
+int ensure_join(lzani_ctx* c, const RunGenomes& g)
 {
     if (!c->gs.lay.join_mode || c->gs.jl.ready) return LZANI_OK;
     StreamSpan span;
     float ms = 0;
     HIPCHK(c, span.begin(c->stream));
-    if (int rc = build_join_lists(c)) return rc;
+    if (int rc = build_join_lists(c, g)) return rc;
     HIPCHK(c, span.end(c->stream));
     HIPCHK(c, span.elapsed(ms));
     c->join_ms_pending = ms;

@@ -1,7 +1,8 @@
 // lzani_ooc.h -- genome sets larger than the device: block uploads and the tiled run.  Included by lzani_hip.hip only,
-// after run_rows_impl, which every tile calls unchanged; of that file it uses lzani_ctx, check_rows, RunRecord, RegionSink,
-// fail, HIPCHK and TRACE, of lzani_index.h for_slices, pack_genomes and launch_kmers.  The block plan and the footprint
-// of a genome (plan_blocks_impl, ooc_genome_bytes) are lzani_set_plan.h.
+// after run_rows_impl, which every tile calls on its own genome table; of that file it uses lzani_ctx, RunGenomes, check_rows,
+// RunRecord, RegionSink, fail, HIPCHK and TRACE, of lzani_index.h for_slices, pack_genomes and launch_kmers.  The block plan
+// and the footprint of a genome (plan_blocks_impl, ooc_genome_bytes) are lzani_set_plan.h; the decisions of a tiled run --
+// the steps below, every tile's local tables, the tables of an upload -- are lzani_tile_plan.h, and this file is their driver.
 //
 // A set whose genome tables (packed texts, N masks, k-mer words, join lists) do not fit a genome-memory limit stays on
 // the host (1 B per base).  Its genomes are cut, in id order, into contiguous blocks of at most limit / 2 bytes of
@@ -38,29 +39,27 @@ __global__ void k_remap_regions(lzani_region* __restrict__ r, u64 n, const u64* 
     if (k < n) r[k].pair = pos[r[k].pair];
 }
 
+// What the plan's genome tables are made from (lzani_tile_plan.h), of the context's set.
+TileSet tile_set_of(const GenomeSet& gs)
+{
+    return TileSet{gs.blk_first, gs.L, gs.nmoff, gs.h_hasN, gs.h_codeoff, gs.half_words, gs.half_genomes};
+}
+
 // The upload of an out-of-core set: block b from the host copy into half h -- staging, k_pack and k_kmers on the
-// block's genomes only (pack_genomes / launch_kmers of lzani_index.h, slice by slice).  Timed into res.upload_ms.
+// block's genomes only (pack_genomes / launch_kmers of lzani_index.h, slice by slice), by the tables of
+// plan_tile_upload.  Timed into res.upload_ms.
 int ooc_upload(lzani_ctx* c, u32 b, int h)
 {
     c->gs.half_block[h] = -1;                                     // (until the upload is complete)
-    const u32 g0 = c->gs.blk_first[b], g1 = c->gs.blk_first[b + 1], cnt = g1 - g0, hg = c->gs.half_genomes;
-    const u64 bases = c->gs.h_codeoff[g1] - c->gs.h_codeoff[g0];
-    std::vector<u64> tab((size_t)2 * hg, 0);
-    std::vector<int> Ls((size_t)2 * hg, 0);                    // lengths, then the N flags k_pack sets
-    int Lmax = 0;
-    for (u32 g = g0; g < g1; ++g) {
-        tab[g - g0] = c->gs.h_codeoff[g] - c->gs.h_codeoff[g0];
-        tab[hg + g - g0] = (u64)h * c->gs.half_words + (c->gs.nmoff[g] - c->gs.nmoff[g0]);
-        Ls[g - g0] = c->gs.L[g];
-        Lmax = std::max(Lmax, c->gs.L[g]);
-    }
+    const u32 cnt = c->gs.blk_first[b + 1] - c->gs.blk_first[b], hg = c->gs.half_genomes;
+    const TileUpload u = plan_tile_upload(tile_set_of(c->gs), b, h);
     StreamSpan span;
     float ms = 0;
     HIPCHK(c, span.begin(c->stream));
-    if (bases) HIPCHK(c, hipMemcpyAsync(c->gs.d_stage, c->gs.h_codes.data() + c->gs.h_codeoff[g0], bases, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->gs.d_up_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->gs.d_up_L, Ls.data(), Ls.size() * 4, hipMemcpyHostToDevice, c->stream));
-    const int Tb = ref_text_len(Lmax, c->P.mrd);
+    if (u.bases) HIPCHK(c, hipMemcpyAsync(c->gs.d_stage, c->gs.h_codes.data() + u.code0, u.bases, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->gs.d_up_tab, u.tab.data(), u.tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->gs.d_up_L, u.Ls.data(), u.Ls.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const int Tb = ref_text_len(u.Lmax, c->P.mrd);
     const GenomeTables& t = c->gs.tab;
     for_slices(cnt, [&](u32 k0, u32 k) {
         pack_genomes(c, c->gs.d_stage, c->gs.d_up_tab, t.t2, t.nm, c->gs.d_up_tab + hg, c->gs.d_up_L, c->gs.d_up_L + hg, Tb, k0, k);
@@ -68,113 +67,62 @@ int ooc_upload(lzani_ctx* c, u32 b, int h)
     });
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, span.end(c->stream));
-    HIPCHK(c, span.elapsed(ms));                                  // (also: tab and Ls leave scope)
+    HIPCHK(c, span.elapsed(ms));                                  // (also: the upload's host tables leave scope)
     c->res.upload_ms += ms;
     c->res.uploads += 1;
     c->gs.half_block[h] = (int)b;
     return LZANI_OK;
 }
 
-// The genome set's count and lengths (gs.n / gs.L) are the tile's local table for the duration of one tile.
-struct LocalTable {
-    lzani_ctx* c;
-    u32 n_all;
-    std::vector<int> L_all;
-    LocalTable(lzani_ctx* c_, std::vector<int>& L_loc) : c(c_), n_all(c_->gs.n) { L_all.swap(c->gs.L); c->gs.L.swap(L_loc); c->gs.n = (u32)c->gs.L.size(); }
-    ~LocalTable() { c->gs.L.swap(L_all); c->gs.n = n_all; }
-};
-
 // The tiled run: the contract of run_rows_impl, with the results written to d_out (device, caller's CSR order) and / or
-// h_out (host), regions to rs with `pair` in the caller's CSR order.
+// h_out (host), regions to rs with `pair` in the caller's CSR order.  The steps, the row tables of a reference block's
+// tiles and a tile's genome table are the plan's (lzani_tile_plan.h); here they are copied, launched, waited for, counted.
 int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
                    int* d_out, lzani_result* h_out, const RegionSink* rs)
 {
-    const u32 n = c->gs.n;
     c->run = RunRecord{};
     c->res = Residency{};
     if (n_rows == 0) return LZANI_OK;
     RowFacts rf;
-    const int rc0 = check_rows(c, n_rows, ref_ids, row_off, query_ids, rf);
+    const int rc0 = check_rows(c, run_genomes_of(c), n_rows, ref_ids, row_off, query_ids, rf);
     if (rc0 || rf.n_pairs == 0) return rc0;
     HIPCHK(c, hipSetDevice(c->dev));
 
-    const u32 nb = (u32)c->gs.blk_first.size() - 1;
-    std::vector<u32> bof(n);
-    for (u32 b = 0; b < nb; ++b) std::fill(bof.begin() + c->gs.blk_first[b], bof.begin() + c->gs.blk_first[b + 1], b);
-    std::vector<std::vector<u32>> rows_of(nb);
-    for (u32 k = 0; k < n_rows; ++k) if (row_off[k + 1] > row_off[k]) rows_of[bof[ref_ids[k]]].push_back(k);
+    const TileRows rows{n_rows, ref_ids, row_off, query_ids};
+    const std::vector<u32> bof = block_of_genomes(c->gs.blk_first);
+    Halves halves{{c->gs.half_block[0], c->gs.half_block[1]}, c->gs.half_a};      // the state now; after the plan, the state the steps lead to
+    const std::vector<TileStep> steps = plan_tile_steps(c->gs.blk_first, bof, rows, halves);
 
     RunRecord tot;
     u64 reg_done = 0;
     DevMem<lzani_result> d_res;                            // grow as the tiles need
     DevMem<u64> d_pos;
     std::vector<lzani_result> h_res;
-    struct Tile { std::vector<u32> rows; std::vector<u64> off; std::vector<u32> q; std::vector<u64> pos; };
-    std::vector<Tile> tiles(nb);
-    for (u32 i = 0; i < nb; ++i) {
-        if (rows_of[i].empty()) continue;
-        for (auto& t : tiles) { t.rows.clear(); t.off.clear(); t.q.clear(); t.pos.clear(); }
-        for (u32 k : rows_of[i]) {
-            const u32 r = ref_ids[k];
-            for (u64 e = row_off[k]; e < row_off[k + 1]; ++e) {
-                const u64 x = e - row_off[k];
-                const u32 q = query_ids ? query_ids[e] : (u32)(x < r ? x : x + 1);
-                Tile& t = tiles[bof[q]];
-                if (t.rows.empty() || t.rows.back() != k) { t.rows.push_back(k); t.off.push_back(t.q.size()); }
-                t.q.push_back(q);
-                t.pos.push_back(e);
-            }
-        }
-        // block i into A
-        if (c->gs.half_block[c->gs.half_a] != (int)i) {
-            if (c->gs.half_block[c->gs.half_a ^ 1] == (int)i) c->gs.half_a ^= 1;
-            else { int rc = ooc_upload(c, i, c->gs.half_a); if (rc) return rc; }
-        }
-        std::vector<u32> order;
-        if (!tiles[i].q.empty()) order.push_back(i);
-        const int held = c->gs.half_block[c->gs.half_a ^ 1];
-        if (held >= 0 && held != (int)i && !tiles[held].q.empty()) order.push_back((u32)held);
-        for (u32 j = 0; j < nb; ++j) if (j != i && (int)j != held && !tiles[j].q.empty()) order.push_back(j);
-        for (u32 j : order) {
-            const int hA = c->gs.half_a, hB = c->gs.half_a ^ 1;
-            if (j != i && c->gs.half_block[hB] != (int)j) { int rc = ooc_upload(c, j, hB); if (rc) return rc; }
-            c->res.peak = std::max<u64>(c->res.peak, c->gs.blk_bytes[i] + (c->gs.half_block[hB] >= 0 ? c->gs.blk_bytes[c->gs.half_block[hB]] : 0));
-            Tile& t = tiles[j];
-            // the local genome table: A's genomes, then B's (unless the queries are A's own)
-            const u32 a0 = c->gs.blk_first[i], nA = c->gs.blk_first[i + 1] - a0;
-            const u32 b0 = c->gs.blk_first[j], nB = j == i ? 0 : c->gs.blk_first[j + 1] - b0;
-            std::vector<int> Lloc((size_t)nA + nB), hasN((size_t)nA + nB);
-            std::vector<u64> nmoff((size_t)nA + nB);
-            for (u32 g = 0; g < nA; ++g) {
-                Lloc[g] = c->gs.L[a0 + g]; hasN[g] = c->gs.h_hasN[a0 + g];
-                nmoff[g] = (u64)hA * c->gs.half_words + (c->gs.nmoff[a0 + g] - c->gs.nmoff[a0]);
-            }
-            for (u32 g = 0; g < nB; ++g) {
-                Lloc[nA + g] = c->gs.L[b0 + g]; hasN[nA + g] = c->gs.h_hasN[b0 + g];
-                nmoff[nA + g] = (u64)hB * c->gs.half_words + (c->gs.nmoff[b0 + g] - c->gs.nmoff[b0]);
-            }
-            const u32 lrows = (u32)t.rows.size();
-            const u64 tp = t.q.size();
-            std::vector<u32> lref(lrows), lq(tp);
-            t.off.push_back(tp);
-            for (u32 k = 0; k < lrows; ++k) lref[k] = ref_ids[t.rows[k]] - a0;
-            for (u64 e = 0; e < tp; ++e) lq[e] = j == i ? t.q[e] - a0 : nA + (t.q[e] - b0);
-            HIPCHK(c, hipMemcpyAsync(c->gs.tab.L, Lloc.data(), Lloc.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->gs.tab.hasN, hasN.data(), hasN.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->gs.tab.nmoff, nmoff.data(), nmoff.size() * 8, hipMemcpyHostToDevice, c->stream));
+    std::vector<TileTable> tiles;
+    for (const TileStep& s : steps) {
+        plan_tile_tables(c->gs.blk_first, bof, rows, s, tiles);
+        c->gs.half_a = s.half_a;
+        if (s.a == TILE_A_UPLOADS) { int rc = ooc_upload(c, s.i, s.half_a); if (rc) return rc; }
+        for (const TileStep::Query& sq : s.q) {
+            const int hB = s.half_a ^ 1;
+            if (sq.b_upload) { int rc = ooc_upload(c, sq.j, hB); if (rc) return rc; }
+            c->res.peak = std::max<u64>(c->res.peak, c->gs.blk_bytes[s.i] + (c->gs.half_block[hB] >= 0 ? c->gs.blk_bytes[c->gs.half_block[hB]] : 0));
+            const TileTable& t = tiles[sq.j];
+            const TileGenomes g = plan_tile_genomes(tile_set_of(c->gs), s.i, sq.j, s.half_a);
+            const u64 tp = t.pairs();
+            HIPCHK(c, hipMemcpyAsync(c->gs.tab.L, g.L.data(), g.L.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->gs.tab.hasN, g.hasN.data(), g.hasN.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->gs.tab.nmoff, g.nmoff.data(), g.nmoff.size() * 8, hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, d_res.reserve(tp));
             if (d_out || rs) {
                 HIPCHK(c, d_pos.reserve(tp));
                 HIPCHK(c, hipMemcpyAsync(d_pos.get(), t.pos.data(), tp * 8, hipMemcpyHostToDevice, c->stream));
             }
-            HIPCHK(c, hipStreamSynchronize(c->stream));            // (Lloc moves into the context below)
+            HIPCHK(c, hipStreamSynchronize(c->stream));            // (the copies above read pageable host vectors: they are done before the tile's run begins)
             if (c->gs.lay.join_mode) c->gs.jl = JoinLists{};                   // (made again for this tile's table, if its form needs them)
-            int rc;
-            {
-                LocalTable lt(c, Lloc);
-                rc = run_rows_impl(c, lrows, lref.data(), t.off.data(), lq.data(), (int*)d_res.get(), rs);
-                if (c->gs.lay.join_mode) c->gs.jl = JoinLists{};
-            }
+            const int rc = run_rows_impl(c, RunGenomes{(u32)g.L.size(), g.L.data()}, (u32)t.rows.size(), t.lref.data(), t.off.data(), t.lq.data(),
+                                         (int*)d_res.get(), rs);
+            if (c->gs.lay.join_mode) c->gs.jl = JoinLists{};
             if (rc) return rc;
             c->res.tiles += 1;
             tot += c->run;
@@ -201,6 +149,7 @@ int run_rows_tiled(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_
             if (h_out) for (u64 e = 0; e < tp; ++e) h_out[t.pos[e]] = h_res[e];
         }
     }
+    assert(halves.a == c->gs.half_a && halves.block[0] == c->gs.half_block[0] && halves.block[1] == c->gs.half_block[1]);
     c->run = tot;
     TRACE("out-of-core run: %u tiles, %llu block uploads (%.1f ms)", c->res.tiles, (unsigned long long)c->res.uploads, c->res.upload_ms);
     return LZANI_OK;

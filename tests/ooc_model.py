@@ -1,5 +1,5 @@
-"""Plain-Python statements of the out-of-core rules (lz-ani_amd/csrc/lzani_set_plan.h, lzani_ooc.h): the genome-table footprint of a genome,
-the block plan (lzani_plan_blocks) and the tile schedule of a run (what lzani_get_residency counts)."""
+"""Plain-Python statements of the out-of-core rules (lz-ani_amd/csrc/lzani_set_plan.h, lzani_tile_plan.h): the genome-table footprint of a
+genome, the block plan (lzani_plan_blocks) and the tile schedule of a run (its ordered steps; what lzani_get_residency counts)."""
 import numpy as np
 
 import util as U
@@ -70,10 +70,11 @@ def limit_for_blocks(lens, prm, blocks, join=None):
     return None
 
 
-def schedule(block_of, ref_ids, row_off, query_ids, state=(None, None)):
-    """Tiles and block uploads of one run from the halves' state (block in A, block in B): reference blocks ascending;
-    block i to A (nothing if A holds it, the halves trade places if B holds it, else an upload); its query blocks i, then
-    the one B holds, then the others ascending, each an upload unless B holds it.  Returns (tiles, uploads, state)."""
+def steps(block_of, ref_ids, row_off, query_ids, state=(None, None)):
+    """The ordered steps of one run from the halves' state (block in A, block in B), as lzani_tile_plan.h's plan_tile_steps
+    makes them: reference blocks ascending, those that have rows with pairs; block i to A ("keep" if A holds it, "trade" if B
+    holds it and the halves trade places, else "upload"); its query blocks i, then the one B holds, then the others
+    ascending, each with whether B uploads it.  Returns ([(i, what A does, [(j, B uploads), ...]), ...], state)."""
     block_of = np.asarray(block_of)
     n, nb = len(block_of), int(block_of.max()) + 1
     size = np.bincount(block_of, minlength=nb)
@@ -82,7 +83,7 @@ def schedule(block_of, ref_ids, row_off, query_ids, state=(None, None)):
         if row_off[k + 1] > row_off[k]:
             rows_of[int(block_of[r])].append(k)
     a, b = state
-    tiles = uploads = 0
+    out = []
     for i in range(nb):
         if not rows_of[i]:
             continue
@@ -93,15 +94,28 @@ def schedule(block_of, ref_ids, row_off, query_ids, state=(None, None)):
                 js.update(x for x in range(nb) if size[x] > (1 if x == block_of[r] else 0))
             else:
                 js.update(int(block_of[q]) for q in query_ids[int(row_off[k]):int(row_off[k + 1])])
+        what = "keep"
         if a != i:
             if b == i:
-                a, b = b, a
+                a, b, what = b, a, "trade"
             else:
-                a, uploads = i, uploads + 1
+                a, what = i, "upload"
         order = ([i] if i in js else []) + ([b] if b is not None and b != i and b in js else [])
         order += sorted(j for j in js if j != i and j != b)
+        qs = []
         for j in order:
-            if j != i and b != j:
-                b, uploads = j, uploads + 1
-            tiles += 1
-    return tiles, uploads, (a, b)
+            up = j != i and b != j
+            if up:
+                b = j
+            qs.append((j, up))
+        out.append((i, what, qs))
+    return out, (a, b)
+
+
+def schedule(block_of, ref_ids, row_off, query_ids, state=(None, None)):
+    """Tiles and block uploads of one run from the halves' state (block in A, block in B): what steps() lists, counted.
+    Returns (tiles, uploads, state)."""
+    st, state = steps(block_of, ref_ids, row_off, query_ids, state)
+    tiles = sum(len(qs) for _, _, qs in st)
+    uploads = sum(what == "upload" for _, what, _ in st) + sum(up for _, _, qs in st for _, up in qs)
+    return tiles, int(uploads), state
