@@ -402,6 +402,64 @@ int lzani_get_prefilter_sparse_info(const lzani_ctx *ctx, lzani_prefilter_sparse
  * two >= 2), or LZANI_ERR_NOMEM for a row above slots / 2. */
 int lzani_plan_sparse_tiles(uint32_t n_rows, const uint64_t *row_pairs, uint64_t slots, uint32_t *tile_r0, uint32_t *attempts);
 
+/* ---- Output filter on the device: only the pairs that pass come back -------------------------------------------
+ * The reference's --out-filter drops a TSV line when one of its five ratios is below its minimum (lz_matcher.cpp:437-462).
+ * A line needs the pair in both directions, which a finished run holds side by side in device memory; this stage reads
+ * that buffer and keeps the unordered pairs of which at least one line survives, so that the host neither receives nor
+ * stores the others.  It is a post-stage over a result buffer: the pair kernels and their dispatch know nothing of it.
+ *   rows       a call's rows are the CSR of lzani_run_rows: ref_ids, row_off, and query_ids or NULL for dense rows
+ *   leading    a directed entry (ref a, query b) with a < b; its mate is the entry (ref b, query a) of the same call; a
+ *              leading entry without a mate is unpaired: dropped and counted.  Entries with b <= a are read as mates only
+ *   lengths    report_len[n]: the lengths the ratios divide by (NULL: the genome set's own).  A host that prints lengths
+ *              without contig separators passes those
+ *   the rule   X = result of (ref a, query b), Y = result of (ref b, query a), la = report_len[a], lb = report_len[b];
+ *              every division an IEEE double division of exact integers, the integer sums in 32-bit arithmetic:
+ *                tani = (double)(X.m + Y.m) / (la + lb)                                  m: sym_in_matches, l: sym_in_literals
+ *                line 0 (query b): gani = (double)X.m / lb;  ani = X.m + X.l != 0 ? (double)X.m / (X.m + X.l) : 0;
+ *                                  qcov = (double)(X.m + X.l) / lb;  rcov = (double)(Y.m + Y.l) / la
+ *                line 1 (query a): the same with X and Y, and la and lb, exchanged
+ *              a line passes unless one of its five values is < its minimum (a NaN or inf value is below nothing); the
+ *              pair is kept iff a line passes.  A NaN minimum: LZANI_ERR_ARG
+ *   order      the kept records come in the order of the leading entries in the CSR: the call's rows, and ascending b
+ *              inside a row.  Rows passed in ascending id order give the order of the reference's output file
+ *   kept forms ref_ids must be distinct and, where query_ids is given, every row's ids ascend strictly: LZANI_ERR_ARG
+ *              otherwise, checked on the host before anything runs (lzani_run_rows itself accepts what it accepted)
+ * The result -- 36 B a kept pair -- stays in the context until the next kept call or lzani_set_genomes; its size is known
+ * from a count pass before it is allocated, and LZANI_ERR_NOMEM leaves the context without a kept result and otherwise
+ * unchanged. */
+typedef struct lzani_out_filter { double min_tani, min_gani, min_ani, min_qcov, min_rcov; } lzani_out_filter;
+typedef struct lzani_kept_pair {
+    uint32_t a, b;            /* a < b */
+    lzani_result x;           /* parse(query b, ref a) */
+    lzani_result y;           /* parse(query a, ref b) */
+    uint32_t lines;           /* bit 0: the line "b against a" passes; bit 1: "a against b" passes; never 0 */
+} lzani_kept_pair;            /* 36 bytes, 32-bit fields only */
+typedef struct lzani_kept_info {
+    uint64_t entries, leading;        /* directed entries of the call; those with a < b                          */
+    uint64_t unpaired;                /* leading entries without a mate                                          */
+    uint64_t kept_pairs, kept_lines;  /* records; lines that pass, summed over them                              */
+    uint64_t bytes_to_host;           /* copied out by the fetches so far                                        */
+    double   filter_ms;               /* HIP events on the context's stream: count, scan, write                  */
+} lzani_kept_info;
+/* The rule as a pure host function (no GPU): the `lines` of one pair.  NULL pointers or a NaN minimum: 0xFFFFFFFF. */
+uint32_t lzani_out_filter_lines(const lzani_out_filter *f, const lzani_result *x, const lzani_result *y, uint32_t len_a, uint32_t len_b);
+/* lzani_run_rows into a device buffer, then the stage; the full result buffer never reaches the host.  Out-of-core sets too. */
+int lzani_run_rows_kept(lzani_ctx *ctx, uint32_t n_rows, const uint32_t *ref_ids, const uint64_t *row_off, const uint32_t *query_ids,
+                        const lzani_out_filter *f, const uint32_t *report_len, uint64_t *n_kept);
+/* Records first .. first + count - 1 of the kept result.  A range past the end: LZANI_ERR_ARG; no result: LZANI_ERR_STATE. */
+int lzani_kept_fetch(lzani_ctx *ctx, uint64_t first, uint64_t count, lzani_kept_pair *out);
+/* The stage alone on a caller's device buffer (this context's GPU) of row_off[n_rows] lzani_result records of n genomes.
+ * Needs no genome set; report_len must not be NULL. */
+int lzani_filter_results_device(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len, uint32_t n_rows, const uint32_t *ref_ids,
+                                const uint64_t *row_off, const uint32_t *query_ids, const void *d_results,
+                                const lzani_out_filter *f, uint64_t *n_kept);
+/* Test hook: the same with the results in host memory (uploaded here): the stage on made-up integers. */
+int lzani_debug_filter_results(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len, uint32_t n_rows, const uint32_t *ref_ids,
+                               const uint64_t *row_off, const uint32_t *query_ids, const lzani_result *results,
+                               const lzani_out_filter *f, uint64_t *n_kept);
+/* LZANI_ERR_STATE without a kept result. */
+int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
+
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
  * takes a reference, builds its index once and parses every query of the row).  Rows are independent; the
@@ -450,6 +508,13 @@ int lzani_group_get_timing(const lzani_group *grp, uint32_t device_index, lzani_
 /* lzani_set_genome_memory / lzani_get_residency for every device context of the group. */
 int lzani_group_set_genome_memory(lzani_group *grp, uint64_t bytes);
 int lzani_group_get_residency(const lzani_group *grp, uint32_t device_index, lzani_residency_info *info);
+/* lzani_run_rows_kept for the group: the shards are gathered and put into the caller's CSR order on the first device as in
+ * lzani_group_run_rows, the output filter's stage runs there on that buffer, and the copy of the full results to the host
+ * is left out.  The kept result belongs to the first device's context; the fetch and the info read it. */
+int lzani_group_run_rows_kept(lzani_group *grp, uint32_t n_rows, const uint32_t *ref_ids, const uint64_t *row_off,
+                              const uint32_t *query_ids, const lzani_out_filter *f, const uint32_t *report_len, uint64_t *n_kept);
+int lzani_group_kept_fetch(lzani_group *grp, uint64_t first, uint64_t count, lzani_kept_pair *out);
+int lzani_group_get_kept_info(const lzani_group *grp, lzani_kept_info *info);
 
 /* The shard bookkeeping of lzani_group_run_rows as a pure host function (no GPU): rows keep their order inside
  * their shard, the shards follow each other in the gathered buffer (shard d from result shard_base[d] on,

@@ -6,6 +6,7 @@
 //   lzani_kernels_cand.h    k_pm_build, k_pm_cand   dense rows: presence matrix of a group of references -> per-pair candidate bitmaps
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
+//   lzani_kernels_outfilter.h   k_of_kept   the output filter: the pairs of a finished result buffer of which a TSV line passes
 //   lzani_block.h           block_sum, block_rank, block_scan_step   what a block's threads work out together (index, prefilter)
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
@@ -19,6 +20,7 @@
 //   lzani_dense.h       the dense-row stage of a run: candidate bitmaps from the presence matrix, the split of few, long pairs
 //   lzani_ooc.h         genome sets larger than the device: block plan, block uploads, the tiled run
 //   lzani_prefilter.h   the k-mer prefilter's host stage: slice and pass plans, the pass / tile driver, its entry points
+//   lzani_kept.h        the output filter's host stage: a run whose results stay on the device, only the kept pairs come back
 //   lzani_multi.h       the multi-GPU layer
 #include <hip/hip_runtime.h>
 
@@ -62,6 +64,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_kernels_pairs.h"
 #include "lzani_kernels_split.h"
 #include "lzani_kernels_prefilter.h"
+#include "lzani_kernels_outfilter.h"
 #include "lzani_rtc.h"
 #include "lzani_devmem.h"
 #include "lzani_run_plan.h"
@@ -243,6 +246,13 @@ struct Prefilter {
     PrefilterWork work;
 };
 
+// The output filter's result (lzani_kept.h): a kept call -> the next one, or lzani_set_genomes.
+struct Kept {
+    bool done = false;
+    lzani_kept_info info{};
+    DevMem<u32> rec;                      // 9 words a kept pair (lzani_kept_pair)
+};
+
 // Residency counters of the last run (lzani_get_residency).
 struct Residency { u32 tiles = 0; u64 uploads = 0, peak = 0; double upload_ms = 0; };
 
@@ -273,6 +283,7 @@ struct lzani_ctx {
     IndexSlabs sl;
     CandScratch cs;
     Prefilter pf;
+    Kept kept;
     // the last run
     RunRecord run;
     Residency res;
@@ -824,6 +835,7 @@ int run_rows_any(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_of
 }  // namespace
 
 #include "lzani_prefilter.h"
+#include "lzani_kept.h"
 
 extern "C" {
 
@@ -880,6 +892,7 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     c->sl = IndexSlabs{};
     c->cs = CandScratch{};
     c->pf = Prefilter{};
+    c->kept = Kept{};
     c->res = Residency{};
     c->gs.L.resize(n);
     c->gs.nmoff.resize(n);

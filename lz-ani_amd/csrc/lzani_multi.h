@@ -16,6 +16,9 @@
 //                                            shard plan (lzani_shard_plan.h: free of HIP, tested on the CPU through
 //                                            lzani_plan_gather) -> ensure the buffers -> run the shards, a host thread per device
 //                                            -> grouped ncclSend/ncclRecv to device 0 -> scatter kernel into CSR order, ONE copy out
+//                                            lzani_group_run_rows_kept: the same stages up to the scatter kernel, then the output
+//                                            filter's stage (lzani_kept.h) on the CSR-ordered buffer, on the first device's context
+//                                            and stream; the copy out of the full results is left out
 #pragma once
 #include <rccl/rccl.h>
 
@@ -83,6 +86,7 @@ template <class F> int on_every_device(lzani_group* g, F f)
 
 struct GroupRun {                       // one lzani_group_run_rows call on its way through the stages
     u32 n_rows; const u32* ref_ids; const u64* row_off; const u32* query_ids; lzani_result* out; u64 n_pairs = 0;   // (the caller's)
+    bool kept = false;                  // lzani_group_run_rows_kept: no host output, the results end on the first device
     ShardPlan plan;                     // what every device gets, and the scatter table
     std::vector<int*> d_shard;          // where every device writes its shard ([0]: in place in d_all)
 };
@@ -91,7 +95,7 @@ int group_check_rows(lzani_group* g, GroupRun& r)
 {
     if (!r.ref_ids || !r.row_off) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null argument");
     r.n_pairs = r.n_rows ? r.row_off[r.n_rows] : 0;
-    if (r.n_pairs && !r.out) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null output");
+    if (r.n_pairs && !r.out && !r.kept) return gfail(g, LZANI_ERR_ARG, "lzani_group_run_rows: null output");
     g->gather_ms = 0;
     const u32 n = g->ctx[0]->gs.n;
     if (!n) return gfail(g, LZANI_ERR_STATE, "lzani_group_run_rows: no genomes set");
@@ -182,8 +186,8 @@ int group_gather(lzani_group* g, const GroupRun& r)
     return LZANI_OK;
 }
 
-// shard order -> the caller's CSR order on device 0, then the one device-to-host copy
-int group_scatter_out(lzani_group* g, const GroupRun& r)
+// shard order -> the caller's CSR order on device 0 (d_final), on the first context's stream
+int group_scatter(lzani_group* g, const GroupRun& r)
 {
     if (!r.n_rows) return LZANI_OK;
     lzani_ctx* c0 = g->ctx[0];
@@ -195,6 +199,30 @@ int group_scatter_out(lzani_group* g, const GroupRun& r)
     hipLaunchKernelGGL(k_scatter_rows, dim3(r.n_rows), dim3(256), 0, c0->stream, r.d_shard[0], d_final, (const u64*)d_tab, (const u64*)d_tab + r.n_rows, (const u64*)d_tab + 2 * (size_t)r.n_rows);
     GHIPCHK(g, hipGetLastError());
     GHIPCHK(g, hipEventRecord(g->ev_gather[1], c0->stream));
+    return LZANI_OK;
+}
+
+// the end of a group run: every device's stream drained, the gather's time read
+int group_finish(lzani_group* g, const GroupRun& r)
+{
+    if (!r.n_rows) return LZANI_OK;
+    lzani_ctx* c0 = g->ctx[0];
+    GHIPCHK(g, hipStreamSynchronize(c0->stream));
+    hipError_t e = hipSuccess;
+    for (size_t d = 1; d < g->ctx.size() && e == hipSuccess; ++d) { hipSetDevice(g->ctx[d]->dev); e = hipStreamSynchronize(g->ctx[d]->stream); }
+    hipSetDevice(c0->dev);                             // (the calling thread leaves with device 0 current, as it came)
+    GHIPCHK(g, e);
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, g->ev_gather[0], g->ev_gather[1]) == hipSuccess) g->gather_ms = ms;
+    return LZANI_OK;
+}
+
+// the one device-to-host copy of the CSR-ordered results
+int group_copy_out(lzani_group* g, const GroupRun& r)
+{
+    if (!r.n_rows) return LZANI_OK;
+    lzani_ctx* c0 = g->ctx[0];
+    const int* const d_final = (const int*)g->d_final.get();
     // the copy out: through two pinned staging buffers that take turns -- the device-to-host copy of one piece flies
     // while the host moves the piece before it into the caller's (pageable) buffer
     for (int k = 0; k < 2; ++k) {
@@ -217,13 +245,6 @@ int group_scatter_out(lzani_group* g, const GroupRun& r)
             issued += len[k];
         }
     }
-    GHIPCHK(g, hipStreamSynchronize(c0->stream));
-    hipError_t e = hipSuccess;
-    for (size_t d = 1; d < g->ctx.size() && e == hipSuccess; ++d) { hipSetDevice(g->ctx[d]->dev); e = hipStreamSynchronize(g->ctx[d]->stream); }
-    hipSetDevice(c0->dev);                             // (the calling thread leaves with device 0 current, as it came)
-    GHIPCHK(g, e);
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, g->ev_gather[0], g->ev_gather[1]) == hipSuccess) g->gather_ms = ms;
     return LZANI_OK;
 }
 
@@ -437,8 +458,51 @@ int lzani_group_run_rows(lzani_group* g, uint32_t n_rows, const uint32_t* ref_id
     if (rc == LZANI_OK) rc = group_ensure_buffers(g, r);
     if (rc == LZANI_OK) rc = group_run_shards(g, r);
     if (rc == LZANI_OK) rc = group_gather(g, r);
-    if (rc == LZANI_OK) rc = group_scatter_out(g, r);
+    if (rc == LZANI_OK) rc = group_scatter(g, r);
+    if (rc == LZANI_OK) rc = group_copy_out(g, r);
+    if (rc == LZANI_OK) rc = group_finish(g, r);
     return rc;
+}
+
+int lzani_group_run_rows_kept(lzani_group* g, uint32_t n_rows, const uint32_t* ref_ids, const uint64_t* row_off,
+                              const uint32_t* query_ids, const lzani_out_filter* f, const uint32_t* report_len, uint64_t* n_kept)
+{
+    if (!g) return LZANI_ERR_ARG;
+    lzani_ctx* c0 = g->ctx[0];
+    const std::string fn = "lzani_group_run_rows_kept";
+    auto of_c0 = [&](int rc) { return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(c0)); };
+    GroupRun r{n_rows, ref_ids, row_off, query_ids, nullptr};
+    r.kept = true;
+    int rc = group_check_rows(g, r);
+    if (rc != LZANI_OK) return rc;
+    if (int e = of_c0(kept_check_filter(c0, fn, f))) return e;
+    std::vector<u32> row_of, own;
+    KeptRows kr;
+    if (int e = of_c0(kept_check_rows(c0, fn, c0->gs.n, n_rows, ref_ids, row_off, query_ids, row_of, kr))) return e;
+    if (!report_len) { own = kept_own_lengths(c0); report_len = own.data(); }
+    GHIPCHK(g, hipSetDevice(c0->dev));
+    c0->kept = Kept{};                                          // the last result goes first: two need not fit
+    rc = group_partition_rows(g, r);
+    if (rc == LZANI_OK) rc = group_ensure_buffers(g, r);
+    if (rc == LZANI_OK) rc = group_run_shards(g, r);
+    if (rc == LZANI_OK) rc = group_gather(g, r);
+    if (rc == LZANI_OK) rc = group_scatter(g, r);
+    if (rc == LZANI_OK) rc = group_finish(g, r);
+    if (rc != LZANI_OK) return rc;
+    return of_c0(kept_stage(c0, c0->gs.n, report_len, n_rows, ref_ids, row_off, query_ids, row_of, kr, (const int*)g->d_final.get(), *f, n_kept));
+}
+
+int lzani_group_kept_fetch(lzani_group* g, uint64_t first, uint64_t count, lzani_kept_pair* out)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_kept_fetch(g->ctx[0], first, count, out);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_get_kept_info(const lzani_group* g, lzani_kept_info* info)
+{
+    if (!g) return LZANI_ERR_ARG;
+    return lzani_get_kept_info(g->ctx[0], info);
 }
 
 int lzani_group_set_genome_memory(lzani_group* g, uint64_t bytes)

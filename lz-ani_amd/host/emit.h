@@ -282,6 +282,24 @@ inline void format_row(const std::vector<Genome>& g, const std::vector<uint32_t>
     }
 }
 
+// --out-filter applied on the device (lzani_run_rows_kept): the engine hands back only the pairs of which a line passes,
+// each with both directions and the lines that pass.  The text of one record: those lines, with no cut left to apply.
+inline void format_kept(const std::vector<Genome>& g, const std::vector<uint32_t>& len, const EmitParams& ep, const lzani_kept_pair& k, std::string& out)
+{
+    static const std::vector<Cut> no_cuts;
+    const double tani = (double)(k.x.sym_in_matches + k.y.sym_in_matches) / (len[k.b] + len[k.a]);
+    if (k.lines & 1u) write_direction(make_direction(g, len, k.b, k.a, k.x, k.y, tani), ep, no_cuts, out);
+    if (k.lines & 2u) write_direction(make_direction(g, len, k.a, k.b, k.y, k.x, tani), ep, no_cuts, out);
+}
+
+// reported length: separators between the contigs of a multi-part item are not counted (lz_matcher.cpp:430-431)
+inline std::vector<uint32_t> report_lengths(const std::vector<Genome>& g, int mrd)
+{
+    std::vector<uint32_t> len(g.size());
+    for (size_t i = 0; i < g.size(); ++i) len[i] = (uint32_t)g[i].codes.size() - (g[i].no_parts - 1) * (uint32_t)mrd;
+    return len;
+}
+
 // The result files, written front to back: open() puts down the ids file and the header line, emit_rows(a0, a1)
 // the text of the reference rows [a0, a1) -- which needs every pair {a, b > a} of those rows in both directions, no
 // more -- and close() finishes.  A host that computes the all2all block by block (lz-ani's tiled matching) emits the
@@ -302,9 +320,7 @@ public:
         } else fn_ids = ep.out_name;
         ofs.open(fn_ids, std::ios::binary);
         if (!ofs.is_open()) { std::cerr << "Cannot open output file: " << fn_ids << std::endl; return false; }
-        // reported length: separators between the contigs of a multi-part item are not counted (lz_matcher.cpp:430-431)
-        len.resize(g.size());
-        for (size_t i = 0; i < g.size(); ++i) len[i] = (uint32_t)g[i].codes.size() - (g[i].no_parts - 1) * (uint32_t)ep.mrd;
+        len = report_lengths(g, ep.mrd);
         if (ep.single_txt) {
             ofs << ep.params_dump;
             ofs << "[no_input_sequences]\n" << g.size() << "\n[input_sequences]\n";
@@ -357,6 +373,22 @@ public:
             writer = std::thread([o, &buf, cnt]() { for (size_t k = 0; k < cnt; ++k) o->write(buf[k].data(), (std::streamsize)buf[k].size()); });
         }
     }
+
+    // The records of a kept result, in the order given (the engine's: the leading entries of the call), formatted by the
+    // threads in contiguous shares and written in order.
+    void emit_kept(const std::vector<Genome>& g, const lzani_kept_pair* rec, size_t cnt)
+    {
+        if (writer.joinable()) writer.join();
+        const size_t nt = std::max<size_t>(1, std::min<size_t>(ep.threads, cnt / 4096 + 1));
+        std::vector<std::string> part(nt);
+        auto worker = [&](size_t t) { for (size_t k = cnt * t / nt; k < cnt * (t + 1) / nt; ++k) format_kept(g, len, ep, rec[k], part[t]); };
+        std::vector<std::thread> th;
+        for (size_t t = 1; t < nt; ++t) th.emplace_back(worker, t);
+        worker(0);
+        for (auto& t : th) t.join();
+        for (const std::string& s : part) ofs.write(s.data(), (std::streamsize)s.size());
+    }
+    const std::vector<uint32_t>& lengths() const { return len; }
 
     bool close()
     {

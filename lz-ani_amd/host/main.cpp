@@ -11,6 +11,8 @@
 // (genome-memory limit per GPU: larger sets run out-of-core, in tiles of genome blocks; with --flt-kmers the filter then
 // streams the genomes from host memory in slices of at most that size),
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
+// --out-filter on a two-TSV output is applied on the device (lzani_group_run_rows_kept): only the pairs of which a line
+// passes come back, and the table of all pairs is never made; LZANI_OUT_FILTER=host keeps the filter on the host.
 #include <dlfcn.h>
 
 #include <chrono>
@@ -336,6 +338,11 @@ struct Engine {
     int (*prefilter_codes_cross)(lzani_ctx*, uint32_t, const uint8_t* const*, const uint32_t*, int, uint64_t, uint32_t, double, uint64_t, uint32_t, uint64_t*) = nullptr;
     int (*set_prefilter_counting)(lzani_ctx*, int) = nullptr;
     int (*get_prefilter_sparse_info)(const lzani_ctx*, lzani_prefilter_sparse_info*) = nullptr;
+    // the output filter on the device: bound where the library has it (an older one: the filter stays on the host)
+    int (*group_run_rows_kept)(lzani_group*, uint32_t, const uint32_t*, const uint64_t*, const uint32_t*, const lzani_out_filter*, const uint32_t*, uint64_t*) = nullptr;
+    int (*group_kept_fetch)(lzani_group*, uint64_t, uint64_t, lzani_kept_pair*) = nullptr;
+    int (*group_get_kept_info)(const lzani_group*, lzani_kept_info*) = nullptr;
+    bool has_kept() const { return group_run_rows_kept && group_kept_fetch && group_get_kept_info; }
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -354,6 +361,9 @@ struct Engine {
         BIND(set_genome_memory) BIND(get_residency) BIND(group_set_genome_memory) BIND(group_get_residency)
         BIND(prefilter) BIND(prefilter_fetch) BIND(get_prefilter_info) BIND(prefilter_codes) BIND(get_prefilter_stream_info) BIND(get_prefilter_pass_info)
         BIND(prefilter_cross) BIND(prefilter_codes_cross) BIND(set_prefilter_counting) BIND(get_prefilter_sparse_info)
+#undef BIND
+#define BIND(f) f = reinterpret_cast<decltype(f)>(dlsym(so, "lzani_" #f));
+        BIND(group_run_rows_kept) BIND(group_kept_fetch) BIND(group_get_kept_info)
 #undef BIND
         return true;
     }
@@ -480,6 +490,16 @@ static void print_residency(int dev, const lzani_residency_info& r, uint64_t til
          << r.peak_resident_bytes << " bytes\n";
 }
 
+// -V 2 after an untiled group run: every device's timing and residency
+static void print_group_devices(const Engine& E, lzani_group* grp, const vector<int>& devs)
+{
+    for (int d = 0; d < (int)devs.size(); ++d) {
+        lzani_timing t; lzani_residency_info ri; double gather = 0;
+        if (E.group_get_timing(grp, (uint32_t)d, &t, &gather) == LZANI_OK) print_gpu_timing(devs[d], t, false, d == 0 && devs.size() > 1 ? &gather : nullptr);
+        if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) print_residency(devs[d], ri, ri.tiles, ri.block_uploads, ri.upload_ms);
+    }
+}
+
 // store_alignment (lz_matcher.cpp:102-169): one BLAST-tab-like row per region; rows of one pair in
 // calc_regions order (length desc, seq_start asc), pairs in (reference, query) order.
 static bool store_alignment(const vector<Genome>& g, vector<AlnRegion>& regs)
@@ -526,6 +546,80 @@ static bool store_alignment(const vector<Genome>& g, vector<AlnRegion>& regs)
     return true;
 }
 
+// --out-filter as the engine takes it, and whether the device applies it: a two-TSV output, no --out-alignment (its own cut
+// stays on the host), no --results-in / --results-out (they carry every pair), numbers for minima (a NaN drops nothing on
+// the host and is refused by the engine), and LZANI_OUT_FILTER=host not set.
+static lzani_out_filter out_filter_minima()
+{
+    return lzani_out_filter{P.flt_vals[(int)Comp::tani], P.flt_vals[(int)Comp::gani], P.flt_vals[(int)Comp::ani], P.flt_vals[(int)Comp::qcov], P.flt_vals[(int)Comp::rcov]};
+}
+static bool out_filter_on_device()
+{
+    const lzani_out_filter f = out_filter_minima();
+    const bool nan = f.min_tani != f.min_tani || f.min_gani != f.min_gani || f.min_ani != f.min_ani || f.min_qcov != f.min_qcov || f.min_rcov != f.min_rcov;
+    const char* e = getenv("LZANI_OUT_FILTER");
+    return P.flt_mask != 0 && !P.single_txt && P.out_aln.empty() && P.results_in.empty() && P.results_out.empty() && !nan && !(e && e == "host"s);
+}
+
+// -V 2: the one line of the device's output filter (a tiled all2all: the sums over its blocks)
+static void print_kept(const lzani_kept_info& k)
+{
+    cerr << "out-filter on the device: " << k.kept_pairs << " pairs, " << k.kept_lines << " lines kept of " << k.leading << " pairs, " << k.unpaired
+         << " unpaired, " << k.filter_ms << " ms\n";
+}
+
+// The kept records of the group's last kept call, fetched in pieces of a million (36 MB) and written as they come.
+static bool emit_kept_result(const Engine& E, lzani_group* grp, const vector<Genome>& g, ResultWriter& W, uint64_t n_kept)
+{
+    vector<lzani_kept_pair> rec;
+    for (uint64_t first = 0; first < n_kept; first += rec.size()) {
+        rec.resize((size_t)min<uint64_t>(n_kept - first, 1u << 20));
+        if (E.group_kept_fetch(grp, first, rec.size(), rec.data()) != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; return false; }
+        W.emit_kept(g, rec.data(), rec.size());
+    }
+    return true;
+}
+
+// do_matching with the output filter on the device, untiled: the rows in ascending id order (lists ascending), one
+// lzani_group_run_rows_kept with the printed lengths, and the kept records -- in the order of the output file -- written
+// as they are fetched.  No PairTable.  flt's rows are sorted by the caller (lists_ascend).
+static bool do_matching_kept(const Engine& E, const vector<Genome>& g, Filter& flt, const EmitParams& ep)
+{
+    const uint32_t n = (uint32_t)g.size();
+    if (P.verbosity >= 1) cerr << "All2all sparse" << endl;
+    const bool dense = flt.empty();
+    vector<uint32_t> ref_ids(n), qids;
+    vector<uint64_t> row_off((size_t)n + 1, 0);
+    for (uint32_t r = 0; r < n; ++r) { ref_ids[r] = r; row_off[r + 1] = row_off[r] + (dense ? (uint64_t)n - 1 : flt.rows[r].size()); }
+    if (!dense) {
+        qids.reserve(row_off[n] + 1);
+        for (auto& row : flt.rows) qids.insert(qids.end(), row.begin(), row.end());
+        vector<vector<uint32_t>>().swap(flt.rows);
+        qids.push_back(0);                                      // (lists that are all empty are still lists: never null)
+    }
+    const vector<int> devs = device_list(max(1, min<int>(P.gpus, (int)max<uint32_t>(n, 1))));
+    lzani_group* grp = nullptr; double secs[2];
+    if (!open_group(E, g, grp, devs, secs)) return false;
+    const lzani_out_filter f = out_filter_minima();
+    const vector<uint32_t> rlen = report_lengths(g, ep.mrd);   // the lengths the TSV prints
+    uint64_t n_kept = 0;
+    const auto t_c = chrono::steady_clock::now();
+    const int rc = E.group_run_rows_kept(grp, n, ref_ids.data(), row_off.data(), dense ? nullptr : qids.data(), &f, rlen.data(), &n_kept);
+    if (P.verbosity >= 2)
+        cerr << "engine: create " << secs[0] << " s, genomes to the device " << secs[1] << " s, matching " << chrono::duration<double>(chrono::steady_clock::now() - t_c).count() << " s\n";
+    if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; E.group_destroy(grp); return false; }
+    if (P.verbosity >= 2) {
+        print_group_devices(E, grp, devs);
+        lzani_kept_info ki;
+        if (E.group_get_kept_info(grp, &ki) == LZANI_OK) print_kept(ki);
+    }
+    if (P.verbosity >= 1) cerr << "Storing results" << endl;
+    ResultWriter W;
+    const bool ok = W.open(g, ep) && emit_kept_result(E, grp, g, W, n_kept);
+    E.group_destroy(grp);
+    return ok && W.close();
+}
+
 // do_matching (lz_matcher.cpp:172-277).  The reference's workers pull reference rows off an atomic counter and
 // run one CParser each; here the whole row table goes to the engine in one call: lzani_group_run_rows deals
 // the rows over the GPUs of the group (cyclic for dense rows, LPT for filtered ones), runs them, gathers the
@@ -549,12 +643,7 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
         if (P.verbosity >= 2)
             cerr << "engine: create " << secs[0] << " s, genomes to the device " << secs[1] << " s, matching " << chrono::duration<double>(chrono::steady_clock::now() - t_c).count() << " s\n";
         if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; E.group_destroy(grp); return false; }
-        if (P.verbosity >= 2)
-            for (int d = 0; d < (int)devs.size(); ++d) {
-                lzani_timing t; lzani_residency_info ri; double gather = 0;
-                if (E.group_get_timing(grp, (uint32_t)d, &t, &gather) == LZANI_OK) print_gpu_timing(devs[d], t, false, d == 0 && devs.size() > 1 ? &gather : nullptr);
-                if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) print_residency(devs[d], ri, ri.tiles, ri.block_uploads, ri.upload_ms);
-            }
+        if (P.verbosity >= 2) print_group_devices(E, grp, devs);
         E.group_destroy(grp);
         return true;
     }
@@ -625,11 +714,14 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
 // 371-567, walks the pairs the same way, after ALL of do_matching): an emitter thread formats and writes the rows of A
 // while the GPUs work on the next block.  Every directed pair is still computed exactly once; the file is byte for
 // byte the one the untiled run writes.
-static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTable& T, const EmitParams& ep, uint32_t tile)
+// kept: the output filter on the device -- every block's call is lzani_group_run_rows_kept, whose records are exactly the
+// pairs {a in A, b > a} of which a line passes, in the file's order (the block holds both directions of each); they are
+// fetched behind the call and written by the emitter thread while the next block runs, and the table T is not made.
+static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTable& T, const EmitParams& ep, uint32_t tile, bool kept)
 {
     const uint32_t n = (uint32_t)g.size();
     if (P.verbosity >= 1) cerr << "All2all sparse" << endl;
-    T.init_dense(n);
+    if (!kept) T.init_dense(n);
     const vector<int> devs = device_list(max(1, min<int>(P.gpus, (int)max<uint32_t>(n, 1))));
     lzani_group* grp = nullptr;
     if (!open_group(E, g, grp, devs)) return false;
@@ -640,19 +732,25 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
     mutex mtx;
     condition_variable cv;
     deque<pair<uint32_t, uint32_t>> ready;
+    deque<vector<lzani_kept_pair>> ready_kept;                  // kept: the records of the finished blocks
     bool done = false;
     thread emitter([&]() {
         for (;;) {
             pair<uint32_t, uint32_t> blk;
+            vector<lzani_kept_pair> rec;
             {
                 unique_lock<mutex> lk(mtx);
-                cv.wait(lk, [&]() { return done || !ready.empty(); });
-                if (ready.empty()) return;
-                blk = ready.front(); ready.pop_front();
+                cv.wait(lk, [&]() { return done || !ready.empty() || !ready_kept.empty(); });
+                if (ready.empty() && ready_kept.empty()) return;
+                if (kept) { rec = move(ready_kept.front()); ready_kept.pop_front(); }
+                else { blk = ready.front(); ready.pop_front(); }
             }
-            W.emit_rows(g, T, blk.first, blk.second);
+            if (kept) W.emit_kept(g, rec.data(), rec.size());
+            else W.emit_rows(g, T, blk.first, blk.second);
         }
     });
+    const lzani_out_filter flt_min = out_filter_minima();
+    lzani_kept_info k_sum{};
     vector<lzani_timing> t_sum(devs.size(), lzani_timing{});   // (cand_ms: the k-mer words and the candidate stage)
     vector<uint64_t> r_tiles(devs.size(), 0), r_uploads(devs.size(), 0);
     vector<double> r_upload_ms(devs.size(), 0);
@@ -674,7 +772,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
             B.rows.push_back(r);
             B.off.push_back(B.q.size());
         }
-        B.out.resize(B.q.size());
+        if (!kept) B.out.resize(B.q.size());
     };
     auto post = [&](uint32_t k) {
         Block& B = blk[k % 3];
@@ -693,8 +791,22 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         Block& B = blk[k % 3];
         if (k + 1 < n_blocks) f_build = async(launch::async, build, k + 1);
         if (!B.rows.empty()) {
-            const int rc = E.group_run_rows(grp, (uint32_t)B.rows.size(), B.rows.data(), B.off.data(), B.q.data(), B.out.data());
+            uint64_t n_kept = 0;
+            const int rc = kept ? E.group_run_rows_kept(grp, (uint32_t)B.rows.size(), B.rows.data(), B.off.data(), B.q.data(), &flt_min, W.lengths().data(), &n_kept)
+                                : E.group_run_rows(grp, (uint32_t)B.rows.size(), B.rows.data(), B.off.data(), B.q.data(), B.out.data());
             if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; ok = false; }
+            if (kept && ok) {
+                vector<lzani_kept_pair> rec((size_t)n_kept);
+                lzani_kept_info ki;
+                if (E.group_kept_fetch(grp, 0, n_kept, rec.data()) != LZANI_OK || E.group_get_kept_info(grp, &ki) != LZANI_OK) {
+                    cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; ok = false;
+                } else {
+                    k_sum.entries += ki.entries; k_sum.leading += ki.leading; k_sum.unpaired += ki.unpaired; k_sum.kept_pairs += ki.kept_pairs;
+                    k_sum.kept_lines += ki.kept_lines; k_sum.filter_ms += ki.filter_ms;
+                    { lock_guard<mutex> lk(mtx); ready_kept.push_back(move(rec)); }
+                    cv.notify_one();
+                }
+            }
             for (size_t d = 0; d < devs.size() && ok; ++d) {
                 lzani_timing t; double gather = 0;
                 if (E.group_get_timing(grp, (uint32_t)d, &t, &gather) == LZANI_OK) {
@@ -707,7 +819,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         }
         if (f_build.valid()) f_build.get();
         if (f_post.valid()) f_post.get();                         // (block k - 1 is out of its buffers before block k + 2 is laid out in them)
-        if (ok) f_post = async(launch::async, post, k);
+        if (ok && !kept) f_post = async(launch::async, post, k);
     }
     if (f_post.valid()) f_post.get();
     { lock_guard<mutex> lk(mtx); done = true; }
@@ -719,10 +831,23 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
             lzani_residency_info ri;
             if (E.group_get_residency(grp, (uint32_t)d, &ri) == LZANI_OK) print_residency(devs[d], ri, r_tiles[d], r_uploads[d], r_upload_ms[d]);
         }
+        if (kept) print_kept(k_sum);
     }
     emitter.join();
     E.group_destroy(grp);
     return W.close() && ok;
+}
+
+// The filter's rows sorted (as PairTable::init_sparse would sort them); whether every row then ascends strictly, which the
+// engine's kept form asks for (a kmer-db file that names a pair twice: the filter stays on the host).
+static bool lists_ascend(Filter& flt)
+{
+    bool strict = true;
+    for (auto& row : flt.rows) {
+        sort(row.begin(), row.end());
+        strict = strict && adjacent_find(row.begin(), row.end()) == row.end();
+    }
+    return strict;
 }
 
 // test seams: the matching stage's integers as text, "ref query mat lit comp" per directed pair
@@ -837,22 +962,28 @@ static bool run_all2all(const char* argv0)
     const bool tiled = tile > 0 && P.results_in.empty() && P.out_aln.empty() && flt.empty() && g.size() >= tile_min && g.size() > tile;
 
     PairTable results;
+    bool stored = tiled;                                    // the result files are written already
     if (!P.results_in.empty()) { if (!read_raw(P.results_in, g.size(), results)) return false; }
     else {
         if (!engine_loaded && !E.load(argv0)) return false;
+        // --out-filter on the device where it applies to the TSV, the library has the stage and the filter's lists are sets
+        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt);
         if (tiled) {
             if (P.verbosity >= 1) cerr << "Storing results (row blocks, while the matching goes on)" << endl;
-            if (!do_matching_tiled(E, g, results, ep, tile)) return false;
+            if (!do_matching_tiled(E, g, results, ep, tile, kept)) return false;
+        } else if (kept) {
+            if (!do_matching_kept(E, g, flt, ep)) return false;
+            stored = true;
         } else {
             vector<AlnRegion> aln;
             if (!do_matching(E, g, flt, results, P.out_aln.empty() ? nullptr : &aln)) return false;
             if (!P.out_aln.empty() && !store_alignment(g, aln)) return false;
         }
     }
-    stamp(tiled ? "LZ matching + storing results" : "LZ matching");
+    stamp(stored ? "LZ matching + storing results" : "LZ matching");
     if (!P.results_out.empty() && !write_raw(P.results_out, results)) return false;
 
-    if (!tiled) {
+    if (!stored) {
         if (P.verbosity >= 1) cerr << "Storing results" << endl;
         if (!store_results(g, results, ep)) return false;
         stamp("Storing results");

@@ -38,7 +38,10 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_prefilter_codes", "lzani_plan_slices", "lzani_get_prefilter_stream_info",
            "lzani_get_prefilter_pass_info", "lzani_prefilter_pass_plan", "lzani_plan_passes",
            "lzani_prefilter_cross", "lzani_prefilter_codes_cross", "lzani_get_prefilter_cross_info",
-           "lzani_set_prefilter_counting", "lzani_get_prefilter_sparse_info", "lzani_plan_sparse_tiles")
+           "lzani_set_prefilter_counting", "lzani_get_prefilter_sparse_info", "lzani_plan_sparse_tiles",
+           "lzani_out_filter_lines", "lzani_run_rows_kept", "lzani_kept_fetch", "lzani_filter_results_device",
+           "lzani_debug_filter_results", "lzani_get_kept_info", "lzani_group_run_rows_kept", "lzani_group_kept_fetch",
+           "lzani_group_get_kept_info")
 
 
 class LzaniError(RuntimeError):
@@ -115,6 +118,50 @@ class PrefilterCrossInfo(C.Structure):
 class PrefilterSparseInfo(C.Structure):
     _fields_ = [("sparse", C.c_uint32), ("attempts", C.c_uint32), ("pass_runs", C.c_uint32), ("reserved_", C.c_uint32),
                 ("slots", C.c_uint64), ("table_bytes", C.c_uint64), ("pairs_seen", C.c_uint64), ("max_fill", C.c_uint64)]
+
+
+class OutFilter(C.Structure):
+    _fields_ = [("min_tani", C.c_double), ("min_gani", C.c_double), ("min_ani", C.c_double), ("min_qcov", C.c_double),
+                ("min_rcov", C.c_double)]
+
+
+class Result(C.Structure):
+    _fields_ = [("sym_in_matches", C.c_int32), ("sym_in_literals", C.c_int32), ("no_components", C.c_int32)]
+
+
+class KeptPair(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("x", Result), ("y", Result), ("lines", C.c_uint32)]
+
+
+class KeptInfo(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("leading", C.c_uint64), ("unpaired", C.c_uint64), ("kept_pairs", C.c_uint64),
+                ("kept_lines", C.c_uint64), ("bytes_to_host", C.c_uint64), ("filter_ms", C.c_double)]
+
+
+# lzani_kept_pair as a numpy record: x = parse(query b, ref a), y = parse(query a, ref b), three int32 each
+KEPT_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("x", np.int32, (3,)), ("y", np.int32, (3,)), ("lines", np.uint32)])
+assert KEPT_DTYPE.itemsize == C.sizeof(KeptPair) == 36
+FILTER_FIELDS = ("tani", "gani", "ani", "qcov", "rcov")
+
+
+def out_filter(flt=None, **minima):
+    """An OutFilter from a dict / keywords of minima by column name (tani, gani, ani, qcov, rcov; the others 0)."""
+    m = dict(flt or {}, **minima)
+    assert set(m) <= set(FILTER_FIELDS), m
+    return OutFilter(*[float(m.get(k, 0.0)) for k in FILTER_FIELDS])
+
+
+def out_filter_lines(flt, x, y, len_a, len_b):
+    """lzani_out_filter_lines (no GPU needed): the `lines` of the pair a < b with x = result of (ref a, query b) and
+    y = result of (ref b, query a); 0xFFFFFFFF where a minimum is NaN."""
+    lib = load_library()
+    f = flt if isinstance(flt, OutFilter) else out_filter(flt)
+    rx, ry = Result(*[int(v) for v in x]), Result(*[int(v) for v in y])
+    return int(lib.lzani_out_filter_lines(C.byref(f), C.byref(rx), C.byref(ry), C.c_uint32(int(len_a)), C.c_uint32(int(len_b))))
+
+
+def _kept_info(o):
+    return {k: getattr(o, k) for k, _ in KeptInfo._fields_}
 
 
 PF_COUNTING = {"auto": 0, "dense": 1, "sparse": 2}   # LZANI_PF_COUNTING_*
@@ -212,6 +259,16 @@ def load_library():
         lib.lzani_set_prefilter_counting.argtypes = [C.c_void_p, C.c_int]
         lib.lzani_get_prefilter_sparse_info.argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_plan_sparse_tiles.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.lzani_out_filter_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.lzani_out_filter_lines.restype = C.c_uint32
+        lib.lzani_run_rows_kept.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+        lib.lzani_kept_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.lzani_filter_results_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+        lib.lzani_debug_filter_results.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+        lib.lzani_get_kept_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_group_run_rows_kept.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+        lib.lzani_group_kept_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.lzani_group_get_kept_info.argtypes = [C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -421,6 +478,29 @@ class Group:
                     "lzani_group_run_rows")
         return out
 
+    def run_rows_kept(self, ref_ids, row_off, query_ids=None, flt=None, report_len=None):
+        """lzani_group_run_rows_kept and the fetch of all records: a KEPT_DTYPE array; kept_info() has the counters."""
+        ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        q = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint32)
+        rl = None if report_len is None else np.ascontiguousarray(report_len, dtype=np.uint32)
+        f = flt if isinstance(flt, OutFilter) else out_filter(flt)
+        cnt = C.c_uint64(0)
+        self._check(self.lib.lzani_group_run_rows_kept(self.h, len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q), C.byref(f), _ptr(rl),
+                                                       C.byref(cnt)), "lzani_group_run_rows_kept")
+        return self.kept_fetch(0, int(cnt.value))
+
+    def kept_fetch(self, first, count):
+        out = np.zeros(int(count), dtype=KEPT_DTYPE)
+        self._check(self.lib.lzani_group_kept_fetch(self.h, C.c_uint64(int(first)), C.c_uint64(int(count)), _ptr(out) if count else None),
+                    "lzani_group_kept_fetch")
+        return out
+
+    def kept_info(self):
+        o = KeptInfo()
+        self._check(self.lib.lzani_group_get_kept_info(self.h, C.byref(o)), "lzani_group_get_kept_info")
+        return _kept_info(o)
+
     def set_genome_memory(self, nbytes):
         """Genome-memory limit of every device context, applied at the next set_genomes (0: automatic)."""
         self._check(self.lib.lzani_group_set_genome_memory(self.h, C.c_uint64(int(nbytes))), "lzani_group_set_genome_memory")
@@ -590,6 +670,52 @@ class Engine:
         self._check(self.lib.lzani_run_rows(self.h, len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q), _ptr(out)),
                     "lzani_run_rows")
         return out
+
+    def run_rows_kept(self, ref_ids, row_off, query_ids=None, flt=None, report_len=None, fetch=True):
+        """lzani_run_rows_kept: the rows run, their results stay on the device, and the output filter keeps the pairs a < b of
+        which a line passes the minima `flt` (an OutFilter, or a dict by column name).  Returns the records (KEPT_DTYPE), all
+        fetched at once, or with fetch=False their number; kept_fetch() / kept_info() read the result."""
+        ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        q = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint32)
+        rl = None if report_len is None else np.ascontiguousarray(report_len, dtype=np.uint32)
+        f = flt if isinstance(flt, OutFilter) else out_filter(flt)
+        cnt = C.c_uint64(0)
+        self._check(self.lib.lzani_run_rows_kept(self.h, len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q), C.byref(f), _ptr(rl),
+                                                 C.byref(cnt)), "lzani_run_rows_kept")
+        return self.kept_fetch(0, int(cnt.value)) if fetch else int(cnt.value)
+
+    def filter_results(self, n, report_len, ref_ids, row_off, query_ids, results, flt, fetch=True):
+        """The output filter's stage alone on made-up or earlier results of n genomes: `results` is an int32[entries, 3] array
+        (lzani_debug_filter_results uploads it) or an int, the raw device pointer of such a buffer
+        (lzani_filter_results_device).  Returns like run_rows_kept."""
+        ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        q = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint32)
+        rl = np.ascontiguousarray(report_len, dtype=np.uint32)
+        f = flt if isinstance(flt, OutFilter) else out_filter(flt)
+        cnt = C.c_uint64(0)
+        if isinstance(results, (int, np.integer)):
+            self._check(self.lib.lzani_filter_results_device(self.h, int(n), _ptr(rl), len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q),
+                                                             C.c_void_p(int(results)), C.byref(f), C.byref(cnt)), "lzani_filter_results_device")
+        else:
+            res = np.ascontiguousarray(results, dtype=np.int32).reshape(-1, 3)
+            self._check(self.lib.lzani_debug_filter_results(self.h, int(n), _ptr(rl), len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q),
+                                                            _ptr(res) if len(res) else None, C.byref(f), C.byref(cnt)), "lzani_debug_filter_results")
+        return self.kept_fetch(0, int(cnt.value)) if fetch else int(cnt.value)
+
+    def kept_fetch(self, first, count):
+        """lzani_kept_fetch: records first .. first + count - 1 of the kept result (KEPT_DTYPE)."""
+        out = np.zeros(int(count), dtype=KEPT_DTYPE)
+        self._check(self.lib.lzani_kept_fetch(self.h, C.c_uint64(int(first)), C.c_uint64(int(count)), _ptr(out) if count else None),
+                    "lzani_kept_fetch")
+        return out
+
+    def kept_info(self):
+        """lzani_get_kept_info: entries, leading, unpaired, kept_pairs, kept_lines, bytes_to_host, filter_ms."""
+        o = KeptInfo()
+        self._check(self.lib.lzani_get_kept_info(self.h, C.byref(o)), "lzani_get_kept_info")
+        return _kept_info(o)
 
     def run_rows_device(self, ref_ids, row_off, query_ids, d_out_ptr):
         """Results stay on the GPU at raw device pointer d_out_ptr (3 int32 per pair)."""
