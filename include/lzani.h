@@ -460,6 +460,79 @@ int lzani_debug_filter_results(lzani_ctx *ctx, uint32_t n, const uint32_t *repor
 /* LZANI_ERR_STATE without a kept result. */
 int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
 
+/* ---- Clustering the kept pairs on the device: single linkage and greedy -----------------------------------------
+ * The kept records of the output filter are the edge list of the similarity graph; this stage clusters it where it lies.
+ * It is a post-stage over finished kept results, like the output filter over a result buffer: the pair kernels and their
+ * dispatch know nothing of it.  The three algorithms are defined by the statements below and by nothing else (no claim
+ * of equality with another program's output is made); lzani_cluster_host is their sequential form.
+ *   graph      the nodes are the n genomes, by the ids of lzani_set_genomes (the lz-ani binary reorders genomes: id 0 is
+ *              the first line of its ids file).  The edge {a, b}, a < b, exists iff the pair is a kept pair of a kept call
+ *              that was added: a pair of which at least one TSV line passes the output filter, which is therefore the
+ *              edge threshold
+ *   weight     with X, Y, la, lb and lines of the output filter above, every division an IEEE double division of exact
+ *              integers (the integer sums in 32-bit arithmetic), one value per line -- line 0 has bit 0 of lines, line 1
+ *              bit 1:
+ *                LZANI_CLUSTER_TANI   (double)(X.m + Y.m) / (la + lb)                      for both lines
+ *                LZANI_CLUSTER_GANI   line 0: (double)X.m / lb;   line 1: (double)Y.m / la
+ *                LZANI_CLUSTER_ANI    line 0: X.m + X.l != 0 ? (double)X.m / (X.m + X.l) : 0;   line 1: the same with Y
+ *              w is the largest value over the lines that `lines` names.  A NaN value reads as 0 (and so do the negative
+ *              values and -0 that only made-up integers give); +inf stays.  So w >= 0, and weights order like their bit
+ *              patterns read as 64-bit unsigned integers
+ *   edge set   edges are added over one or several calls; adding an edge twice is the same as adding it once (it carries
+ *              the same weight), and the order of additions never shows in a result
+ *   rep_of     rep_of[v] is the representative of v's cluster; a representative has rep_of[r] == r
+ *     LZANI_CLUSTER_SINGLE        the clusters are the connected components; rep_of[v] is the smallest id of v's component
+ *     LZANI_CLUSTER_GREEDY_FIRST  greedy incremental, in the manner of CD-HIT: the genomes in ascending id order, v becomes
+ *                                 a representative iff no earlier representative is its neighbour; otherwise rep_of[v] is
+ *                                 the smallest id among its neighbouring representatives (always < v: one exists below v).
+ *                                 The representatives are the lexicographically first maximal independent set
+ *     LZANI_CLUSTER_GREEDY_BEST   nearest centroid, in the manner of UCLUST: the same representatives; for another v,
+ *                                 rep_of[v] is the neighbouring representative r < v with the largest w, ties to the
+ *                                 smallest r.  Representatives above v do not count: they did not exist when v was placed
+ *   numbering  cluster_of[v] = the number of representatives with an id below rep_of[v]: clusters are numbered in
+ *              ascending order of their representative; clusters = the number of representatives
+ * The device stage: the union-find of SINGLE hooks the larger root under the smaller, so that parent[v] <= v at every
+ * moment; the greedy representatives are the fixed point of rounds of an edge pass and a node pass whose stores are
+ * idempotent and final, so the result is that of the statements whatever the schedule.  `rounds` is 1 for SINGLE and the
+ * number of greedy rounds up to the first that left no node undecided (a path with ascending ids needs n / 2 to n).
+ * Not here: complete linkage, greedy set cover, Leiden. */
+#define LZANI_CLUSTER_SINGLE        0
+#define LZANI_CLUSTER_GREEDY_FIRST  1
+#define LZANI_CLUSTER_GREEDY_BEST   2
+#define LZANI_CLUSTER_TANI          0
+#define LZANI_CLUSTER_GANI          1
+#define LZANI_CLUSTER_ANI           2
+typedef struct lzani_cluster_edge { uint32_t a, b; double w; } lzani_cluster_edge;      /* 16 bytes */
+typedef struct lzani_cluster_info {
+    uint32_t n;                       /* genomes                                                                 */
+    int32_t  algo, measure;           /* of the last run (-1 before one); of the begin                           */
+    uint32_t rounds;                  /* of the last run                                                         */
+    uint64_t edges;                   /* edge records added so far (an edge added twice counts twice)            */
+    uint64_t clusters, singletons, largest;   /* of the last run: clusters, those of one genome, the largest's size */
+    uint64_t edge_bytes;              /* device bytes of the edge buffer                                         */
+    double   add_ms, run_ms;          /* HIP events on the context's stream: the add_kept calls summed; the last run */
+} lzani_cluster_info;
+/* The weight as a pure host function (no GPU).  NULL pointers or an unknown measure: NaN. */
+double lzani_cluster_weight(int measure, const lzani_result *x, const lzani_result *y, uint32_t lines, uint32_t len_a, uint32_t len_b);
+/* The sequential statement as a pure host function (no GPU).  rep_of[n]; cluster_of[n] and n_clusters may be NULL.  An edge
+ * with a == b, an id >= n, a NaN or negative w, or an unknown algo: LZANI_ERR_ARG.  (b, a) with b > a is the edge (a, b). */
+int lzani_cluster_host(uint32_t n, const lzani_cluster_edge *edges, uint64_t count, int algo, uint32_t *rep_of, uint32_t *cluster_of,
+                       uint32_t *n_clusters);
+/* An empty edge set for n genomes, whose reported lengths (NULL: the genome set's own, n must be its size) stay on the device.
+ * Drops the cluster state there was; lzani_set_genomes drops it too.  No genome set: LZANI_ERR_STATE. */
+int lzani_cluster_begin(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len, int measure);
+/* Appends the edges of the context's current kept result, one per record, weighted on the device.  No begin or no kept
+ * result: LZANI_ERR_STATE; a kept result of another n: LZANI_ERR_ARG; LZANI_ERR_NOMEM leaves the edges that were there. */
+int lzani_cluster_add_kept(lzani_ctx *ctx, uint64_t *edges_total);
+/* Test hook: appends made-up edges from host memory, checked like those of lzani_cluster_host before anything runs. */
+int lzani_debug_cluster_add_edges(lzani_ctx *ctx, const lzani_cluster_edge *edges, uint64_t count);
+/* May be called again with another algo on the same edges.  No begin: LZANI_ERR_STATE. */
+int lzani_cluster_run(lzani_ctx *ctx, int algo, uint64_t *n_clusters);
+/* rep_of[n], cluster_of[n] of the last run; either may be NULL.  No run since the begin or the last add: LZANI_ERR_STATE. */
+int lzani_cluster_fetch(lzani_ctx *ctx, uint32_t *rep_of, uint32_t *cluster_of);
+/* LZANI_ERR_STATE before a begin. */
+int lzani_get_cluster_info(const lzani_ctx *ctx, lzani_cluster_info *info);
+
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
  * takes a reference, builds its index once and parses every query of the row).  Rows are independent; the
@@ -515,6 +588,12 @@ int lzani_group_run_rows_kept(lzani_group *grp, uint32_t n_rows, const uint32_t 
                               const uint32_t *query_ids, const lzani_out_filter *f, const uint32_t *report_len, uint64_t *n_kept);
 int lzani_group_kept_fetch(lzani_group *grp, uint64_t first, uint64_t count, lzani_kept_pair *out);
 int lzani_group_get_kept_info(const lzani_group *grp, lzani_kept_info *info);
+/* The cluster stage for the group: on the first device's context, where the group's kept results are. */
+int lzani_group_cluster_begin(lzani_group *grp, uint32_t n, const uint32_t *report_len, int measure);
+int lzani_group_cluster_add_kept(lzani_group *grp, uint64_t *edges_total);
+int lzani_group_cluster_run(lzani_group *grp, int algo, uint64_t *n_clusters);
+int lzani_group_cluster_fetch(lzani_group *grp, uint32_t *rep_of, uint32_t *cluster_of);
+int lzani_group_get_cluster_info(const lzani_group *grp, lzani_cluster_info *info);
 
 /* The shard bookkeeping of lzani_group_run_rows as a pure host function (no GPU): rows keep their order inside
  * their shard, the shards follow each other in the gathered buffer (shard d from result shard_base[d] on,

@@ -1,0 +1,243 @@
+// lzani_cluster.h -- host side of the cluster stage (include/lzani.h states the definitions): the edge buffer and its growth,
+// the run -- union-find for single linkage, rounds of the greedy representatives, assignment, numbering -- and the entry
+// points (lzani_cluster_begin, lzani_cluster_add_kept, lzani_debug_cluster_add_edges, lzani_cluster_run, lzani_cluster_fetch,
+// lzani_get_cluster_info and the pure lzani_cluster_weight and lzani_cluster_host).  Included by lzani_hip.hip only, behind
+// lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept), fail and HIPCHK, of lzani_prefilter.h
+// pf_blocks, of lzani_devmem.h DevMem and StreamSpan.  The kernels are lzani_kernels_cluster.h; the group's form is in
+// lzani_multi.h.
+//
+// What the stage reads and writes.  add_kept, per record: 36 B and two lengths read, 16 B written.  SINGLE: per edge 16 B
+// and the two paths to the roots, one CAS per hook that is won; per node one path.  A greedy round: per edge 16 B and one or
+// two state words read, at most one word stored; per node two words.  The assignment: per edge 16 B and two state words,
+// one atomic per edge of a node that is no representative (BEST: two passes).  The numbering: per node three words, one
+// atomic, and the scan of n flags.
+#pragma once
+
+namespace {
+
+enum { CL_BATCH = 8 };                                  // greedy rounds launched between two reads of the undecided counts
+
+int cluster_state(lzani_ctx* c, const std::string& fn)
+{
+    if (!c->cl.begun) return fail(c, LZANI_ERR_STATE, fn + ": no cluster state (call lzani_cluster_begin first)");
+    return LZANI_OK;
+}
+
+// Room for `need` edges: kept if there is, else a buffer of at least twice the size, the edges copied on the device.  A
+// failure leaves the buffer and its edges as they were.
+int cluster_reserve(lzani_ctx* c, u64 need)
+{
+    Cluster& k = c->cl;
+    if ((need + PF_THREADS - 1) / PF_THREADS > 0x7FFFFFFFull) return fail(c, LZANI_ERR_ARG, "cluster stage: more edges than one launch covers");
+    if (need <= k.edges.capacity()) return LZANI_OK;
+    DevMem<lzani_cluster_edge> bigger;
+    const u64 twice = std::max<u64>(need, 2 * (u64)k.edges.capacity());
+    if (!got(bigger.alloc((size_t)twice))) HIPCHK(c, bigger.alloc((size_t)need));
+    if (k.info.edges) {
+        HIPCHK(c, hipMemcpyAsync(bigger.get(), k.edges.get(), (size_t)k.info.edges * sizeof(lzani_cluster_edge), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    k.edges = std::move(bigger);
+    k.info.edge_bytes = k.edges.bytes();
+    return LZANI_OK;
+}
+
+// The run on the context's edges: fills rep_of, cluster_of and the run's part of `info`.
+int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& cluster_of, lzani_cluster_info& info)
+{
+    const Cluster& k = c->cl;
+    const u32 n = k.info.n;
+    const u64 E = k.info.edges;
+    const lzani_cluster_edge* edges = k.edges.get();
+    DevMem<u32> parent, state, blocked, flag, size, counters, undecided;
+    DevMem<unsigned long long> best;
+    DevMem<u64> below;
+    HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, flag.alloc(n)); HIPCHK(c, size.alloc(n));
+    HIPCHK(c, best.alloc(n)); HIPCHK(c, below.alloc((size_t)n + 1));
+    HIPCHK(c, counters.alloc(CL_COUNTERS)); HIPCHK(c, undecided.alloc(CL_BATCH));
+    HIPCHK(c, rep_of.alloc(n)); HIPCHK(c, cluster_of.alloc(n));
+    const dim3 nodes(pf_blocks(n)), edge_blocks(pf_blocks(E)), threads(PF_THREADS);
+    StreamSpan span;
+    HIPCHK(c, span.begin(c->stream));
+    HIPCHK(c, hipMemsetAsync(counters, 0, CL_COUNTERS * sizeof(u32), c->stream));
+    hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
+    u64 rounds = 1;
+    if (algo == LZANI_CLUSTER_SINGLE) {
+        if (E) hipLaunchKernelGGL(k_cl_hook, edge_blocks, threads, 0, c->stream, edges, E, parent.get());
+        hipLaunchKernelGGL(k_cl_roots, nodes, threads, 0, c->stream, n, (const u32*)parent.get(), rep_of.get());
+    } else {
+        rounds = 0;
+        for (bool done = false; !done;) {
+            // the lowest undecided node is decided in every round: n rounds always do, and a defect ends here instead of spinning
+            if (rounds >= (u64)n + 1) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: nodes still undecided after n + 1 rounds");
+            const u32 batch = (u32)std::min<u64>(CL_BATCH, (u64)n + 1 - rounds);
+            HIPCHK(c, hipMemsetAsync(undecided, 0, CL_BATCH * sizeof(u32), c->stream));
+            for (u32 r = 0; r < batch; ++r) {
+                if (E) hipLaunchKernelGGL(k_cl_greedy_edges, edge_blocks, threads, 0, c->stream, edges, E, state.get(), blocked.get());
+                hipLaunchKernelGGL(k_cl_greedy_nodes, nodes, threads, 0, c->stream, n, state.get(), blocked.get(), undecided.get() + r);
+            }
+            HIPCHK(c, hipGetLastError());
+            u32 left[CL_BATCH];
+            HIPCHK(c, hipMemcpyAsync(left, undecided, sizeof left, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            u32 r = 0;
+            while (r < batch && left[r]) ++r;
+            done = r < batch;
+            rounds += done ? r + 1 : batch;             // (the rounds behind the first that left no node change nothing)
+        }
+        hipLaunchKernelGGL(k_cl_assign_init, nodes, threads, 0, c->stream, n, (const u32*)state.get(), rep_of.get());
+        if (E && algo == LZANI_CLUSTER_GREEDY_BEST)
+            hipLaunchKernelGGL(k_cl_assign_best, edge_blocks, threads, 0, c->stream, edges, E, (const u32*)state.get(), best.get());
+        if (E) hipLaunchKernelGGL(k_cl_assign_min, edge_blocks, threads, 0, c->stream, edges, E, (const u32*)state.get(),
+                                  algo == LZANI_CLUSTER_GREEDY_BEST ? (const unsigned long long*)best.get() : nullptr, rep_of.get());
+    }
+    hipLaunchKernelGGL(k_cl_flags, nodes, threads, 0, c->stream, n, (const u32*)rep_of.get(), flag.get(), size.get());
+    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)flag.get(), (u64)n, below.get());
+    hipLaunchKernelGGL(k_cl_number, nodes, threads, 0, c->stream, n, (const u32*)rep_of.get(), (const u64*)below.get(), (const u32*)size.get(),
+                       cluster_of.get(), counters.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, span.end(c->stream));
+    u32 h_counters[CL_COUNTERS] = {0, 0};
+    u64 clusters = 0;
+    HIPCHK(c, hipMemcpyAsync(h_counters, counters, sizeof h_counters, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&clusters, below.get() + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIPCHK(c, span.elapsed(ms));
+    info.algo = algo; info.rounds = (u32)rounds; info.clusters = clusters; info.singletons = h_counters[CL_SINGLETONS];
+    info.largest = h_counters[CL_LARGEST]; info.run_ms = ms;
+    TRACE("cluster: algo=%d n=%u edges=%llu rounds=%llu clusters=%llu", algo, n, (unsigned long long)E, (unsigned long long)rounds, (unsigned long long)clusters);
+    return LZANI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+double lzani_cluster_weight(int measure, const lzani_result* x, const lzani_result* y, uint32_t lines, uint32_t len_a, uint32_t len_b)
+{
+    if (!x || !y || !cluster_measure_known(measure)) return __builtin_nan("");
+    return cluster_weight(measure, *x, *y, lines, len_a, len_b);
+}
+
+int lzani_cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, int algo, uint32_t* rep_of, uint32_t* cluster_of, uint32_t* n_clusters)
+{
+    try { return cluster_host(n, edges, count, algo, rep_of, cluster_of, n_clusters); }
+    catch (const std::bad_alloc&) { return LZANI_ERR_NOMEM; }
+}
+
+int lzani_cluster_begin(lzani_ctx* c, uint32_t n, const uint32_t* report_len, int measure)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_cluster_begin";
+    if (!c->gs.n) return fail(c, LZANI_ERR_STATE, fn + ": no genomes set");
+    if (!n || !cluster_measure_known(measure)) return fail(c, LZANI_ERR_ARG, fn + ": no genomes or an unknown measure");
+    if (!report_len && n != c->gs.n) return fail(c, LZANI_ERR_ARG, fn + ": the genome set's own lengths are those of its n genomes");
+    std::vector<u32> own;
+    if (!report_len) { own = kept_own_lengths(c); report_len = own.data(); }
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->cl = Cluster{};                                         // the last state goes first
+    Cluster k;
+    HIPCHK(c, k.len.alloc(n));
+    HIPCHK(c, hipMemcpyAsync(k.len.get(), report_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    k.info.n = n; k.info.measure = measure; k.info.algo = -1;
+    k.begun = true;
+    c->cl = std::move(k);
+    return LZANI_OK;
+}
+
+int lzani_cluster_add_kept(lzani_ctx* c, uint64_t* edges_total)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_cluster_add_kept";
+    if (int rc = cluster_state(c, fn)) return rc;
+    if (!c->kept.done) return fail(c, LZANI_ERR_STATE, fn + ": no kept result (call lzani_run_rows_kept first)");
+    Cluster& k = c->cl;
+    if (c->kept.n != k.info.n) return fail(c, LZANI_ERR_ARG, fn + ": the kept result is one of " + std::to_string(c->kept.n) + " genomes, the cluster state of " + std::to_string(k.info.n));
+    const u64 K = c->kept.info.kept_pairs;                     // the buffer's need, known before the kernel runs
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (int rc = cluster_reserve(c, k.info.edges + K)) return rc;
+    if (K) {
+        StreamSpan span;
+        HIPCHK(c, span.begin(c->stream));
+        hipLaunchKernelGGL(k_cl_add_kept, dim3(pf_blocks(K)), dim3(PF_THREADS), 0, c->stream, (const u32*)c->kept.rec.get(), K, (const u32*)k.len.get(),
+                           (int)k.info.measure, k.edges.get(), k.info.edges);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, span.end(c->stream));
+        float ms = 0;
+        HIPCHK(c, span.elapsed(ms));
+        k.info.add_ms += ms;
+        k.info.edges += K;
+        k.ran = false;
+    }
+    if (edges_total) *edges_total = k.info.edges;
+    return LZANI_OK;
+}
+
+int lzani_debug_cluster_add_edges(lzani_ctx* c, const lzani_cluster_edge* edges, uint64_t count)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_debug_cluster_add_edges";
+    if (int rc = cluster_state(c, fn)) return rc;
+    if (count && !edges) return fail(c, LZANI_ERR_ARG, fn + ": null edges");
+    Cluster& k = c->cl;
+    std::vector<lzani_cluster_edge> norm(edges, edges + count);
+    for (lzani_cluster_edge& e : norm) {
+        if (!cluster_edge_ok(k.info.n, e)) return fail(c, LZANI_ERR_ARG, fn + ": an edge with a == b, an id out of range, or a weight that is negative or not a number");
+        if (e.a > e.b) std::swap(e.a, e.b);
+        e.w = cluster_value(e.w);
+    }
+    if (!count) return LZANI_OK;
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (int rc = cluster_reserve(c, k.info.edges + count)) return rc;
+    HIPCHK(c, hipMemcpyAsync(k.edges.get() + k.info.edges, norm.data(), (size_t)count * sizeof(lzani_cluster_edge), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    k.info.edges += count;
+    k.ran = false;
+    return LZANI_OK;
+}
+
+int lzani_cluster_run(lzani_ctx* c, int algo, uint64_t* n_clusters)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_cluster_run";
+    if (int rc = cluster_state(c, fn)) return rc;
+    if (!cluster_algo_known(algo)) return fail(c, LZANI_ERR_ARG, fn + ": unknown algorithm");
+    HIPCHK(c, hipSetDevice(c->dev));
+    Cluster& k = c->cl;
+    k.ran = false;
+    k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes first
+    DevMem<u32> rep_of, cluster_of;
+    lzani_cluster_info info = k.info;
+    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info);
+    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    k.info = info;
+    k.rep_of = std::move(rep_of); k.cluster_of = std::move(cluster_of);
+    k.ran = true;
+    if (n_clusters) *n_clusters = info.clusters;
+    return LZANI_OK;
+}
+
+int lzani_cluster_fetch(lzani_ctx* c, uint32_t* rep_of, uint32_t* cluster_of)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_cluster_fetch";
+    if (int rc = cluster_state(c, fn)) return rc;
+    const Cluster& k = c->cl;
+    if (!k.ran) return fail(c, LZANI_ERR_STATE, fn + ": no run since the begin or the last added edges (call lzani_cluster_run first)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (rep_of) HIPCHK(c, hipMemcpy(rep_of, k.rep_of.get(), (size_t)k.info.n * 4, hipMemcpyDeviceToHost));
+    if (cluster_of) HIPCHK(c, hipMemcpy(cluster_of, k.cluster_of.get(), (size_t)k.info.n * 4, hipMemcpyDeviceToHost));
+    return LZANI_OK;
+}
+
+int lzani_get_cluster_info(const lzani_ctx* c, lzani_cluster_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->cl.begun) return LZANI_ERR_STATE;
+    *info = c->cl.info;
+    return LZANI_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,120 @@
+// lzani_cluster_plan.h -- the rule and the sequential statement of the cluster stage (include/lzani.h, "clustering the kept
+// pairs"): the weight of an edge, and the three algorithms on a host edge array -- union-find with the smaller root as
+// parent, and the greedy sweep over adjacency lists.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
+// weight; the pure host functions lzani_cluster_weight and lzani_cluster_host (lzani_cluster.h) and the host binary, which
+// includes this header directly, call both.  Free of HIP but for the guard macro; compiled without fast-math and with
+// -ffp-contract=off: every ratio is one IEEE double division of exact integers, so host and device give the same bits.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/lzani.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define LZANI_CL_HD __host__ __device__
+#else
+#define LZANI_CL_HD
+#endif
+
+namespace lzani {
+
+LZANI_CL_HD inline bool cluster_measure_known(int measure) { return measure >= LZANI_CLUSTER_TANI && measure <= LZANI_CLUSTER_ANI; }
+LZANI_CL_HD inline bool cluster_algo_known(int algo) { return algo >= LZANI_CLUSTER_SINGLE && algo <= LZANI_CLUSTER_GREEDY_BEST; }
+
+// a value that is not above 0 -- NaN, and the negative values and -0 that only made-up integers give -- reads as +0
+LZANI_CL_HD inline double cluster_value(double v) { return v > 0 ? v : 0.0; }
+
+// The weight of the pair a < b: X = result of (ref a, query b), Y = result of (ref b, query a), la / lb the reported lengths,
+// lines as the output filter gives them.  The largest value of the measure over the lines that `lines` names; 0 for none.
+LZANI_CL_HD inline double cluster_weight(int measure, const lzani_result& X, const lzani_result& Y, uint32_t lines, uint32_t la, uint32_t lb)
+{
+    double v0, v1;
+    if (measure == LZANI_CLUSTER_TANI) {
+        const int32_t mm = (int32_t)((uint32_t)X.sym_in_matches + (uint32_t)Y.sym_in_matches);
+        v0 = v1 = (double)mm / (uint32_t)(la + lb);
+    } else if (measure == LZANI_CLUSTER_GANI) {
+        v0 = (double)X.sym_in_matches / lb;
+        v1 = (double)Y.sym_in_matches / la;
+    } else {
+        const int32_t ax = (int32_t)((uint32_t)X.sym_in_matches + (uint32_t)X.sym_in_literals);
+        const int32_t ay = (int32_t)((uint32_t)Y.sym_in_matches + (uint32_t)Y.sym_in_literals);
+        v0 = ax != 0 ? (double)X.sym_in_matches / ax : 0;
+        v1 = ay != 0 ? (double)Y.sym_in_matches / ay : 0;
+    }
+    v0 = (lines & 1u) ? cluster_value(v0) : 0.0;
+    v1 = (lines & 2u) ? cluster_value(v1) : 0.0;
+    return v0 > v1 ? v0 : v1;
+}
+
+// w >= 0 (or +inf): weights order like these
+inline uint64_t cluster_weight_bits(double w)
+{
+    uint64_t b;
+    memcpy(&b, &w, 8);
+    return b;
+}
+
+// What every entry point checks of an edge passed in by hand.
+inline bool cluster_edge_ok(uint32_t n, const lzani_cluster_edge& e) { return e.a != e.b && e.a < n && e.b < n && e.w >= 0; }
+
+// rep_of -> cluster_of and the number of clusters: clusters numbered in ascending order of their representative.
+inline uint32_t cluster_number(uint32_t n, const uint32_t* rep_of, uint32_t* cluster_of)
+{
+    std::vector<uint32_t> below((size_t)n + 1, 0);
+    for (uint32_t v = 0; v < n; ++v) below[v + 1] = below[v] + (rep_of[v] == v ? 1u : 0u);
+    if (cluster_of)
+        for (uint32_t v = 0; v < n; ++v) cluster_of[v] = below[rep_of[v]];
+    return below[n];
+}
+
+// The sequential statement.  rep_of[n] is written; cluster_of and n_clusters may be null.  LZANI_ERR_ARG for an edge that
+// cluster_edge_ok refuses or an unknown algo; (b, a) with b > a is the edge (a, b).
+inline int cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, int algo, uint32_t* rep_of, uint32_t* cluster_of, uint32_t* n_clusters)
+{
+    if (!rep_of || (count && !edges) || !cluster_algo_known(algo)) return LZANI_ERR_ARG;
+    for (uint64_t i = 0; i < count; ++i)
+        if (!cluster_edge_ok(n, edges[i])) return LZANI_ERR_ARG;
+    if (algo == LZANI_CLUSTER_SINGLE) {
+        std::vector<uint32_t> parent(n);
+        for (uint32_t v = 0; v < n; ++v) parent[v] = v;
+        auto root = [&](uint32_t v) {
+            while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; }
+            return v;
+        };
+        for (uint64_t i = 0; i < count; ++i) {
+            const uint32_t ra = root(edges[i].a), rb = root(edges[i].b);
+            if (ra != rb) parent[ra > rb ? ra : rb] = ra > rb ? rb : ra;         // the smaller root is the parent
+        }
+        for (uint32_t v = 0; v < n; ++v) rep_of[v] = root(v);                     // ... so a root is its tree's smallest id
+    } else {
+        // adjacency lists of the neighbours below each node
+        std::vector<uint64_t> off((size_t)n + 1, 0);
+        for (uint64_t i = 0; i < count; ++i) off[(edges[i].a > edges[i].b ? edges[i].a : edges[i].b) + 1]++;
+        for (uint32_t v = 0; v < n; ++v) off[v + 1] += off[v];
+        std::vector<uint32_t> nb(count);
+        std::vector<double> nw(count);
+        std::vector<uint64_t> at(off.begin(), off.end() - 1);
+        for (uint64_t i = 0; i < count; ++i) {
+            const uint32_t lo = edges[i].a < edges[i].b ? edges[i].a : edges[i].b, hi = edges[i].a < edges[i].b ? edges[i].b : edges[i].a;
+            nb[at[hi]] = lo; nw[at[hi]] = edges[i].w; at[hi]++;
+        }
+        for (uint32_t v = 0; v < n; ++v) {              // the sweep: every node below v is placed
+            uint32_t best = v;
+            double best_w = 0;
+            for (uint64_t e = off[v]; e < off[v + 1]; ++e) {
+                const uint32_t r = nb[e];
+                if (rep_of[r] != r) continue;
+                const bool better = best == v || (algo == LZANI_CLUSTER_GREEDY_FIRST ? r < best : (nw[e] > best_w || (nw[e] == best_w && r < best)));
+                if (better) { best = r; best_w = nw[e]; }
+            }
+            rep_of[v] = best;
+        }
+    }
+    const uint32_t k = cluster_number(n, rep_of, cluster_of);
+    if (n_clusters) *n_clusters = k;
+    return LZANI_OK;
+}
+
+}  // namespace lzani

@@ -7,6 +7,7 @@
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 //   lzani_kernels_outfilter.h   k_of_kept   the output filter: the pairs of a finished result buffer of which a TSV line passes
+//   lzani_kernels_cluster.h     k_cl_*   the cluster stage: single linkage and greedy clustering of the kept pairs
 //   lzani_block.h           block_sum, block_rank, block_scan_step   what a block's threads work out together (index, prefilter)
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
@@ -14,13 +15,14 @@
 // table of the instantiations, choose_pair_kernel) in lzani_pair_dispatch.h, those of a genome set (the set-level
 // switches, the form of the index, footprints, the block plan, residency, the slot count of the slabs) in lzani_set_plan.h,
 // those of an out-of-core run (the order of its tiles, their local tables, the tables of an upload) in lzani_tile_plan.h.
-// Device memory and events have one owner each, lzani_devmem.h.  Five layers of the host side are files of their own,
+// Device memory and events have one owner each, lzani_devmem.h.  Six layers of the host side are files of their own,
 // included at fixed places below:
 //   lzani_index.h       the index stage: genome upload, slabs, k-mer words, join lists, the index build, its test hooks
 //   lzani_dense.h       the dense-row stage of a run: candidate bitmaps from the presence matrix, the split of few, long pairs
 //   lzani_ooc.h         genome sets larger than the device: block plan, block uploads, the tiled run
 //   lzani_prefilter.h   the k-mer prefilter's host stage: slice and pass plans, the pass / tile driver, its entry points
 //   lzani_kept.h        the output filter's host stage: a run whose results stay on the device, only the kept pairs come back
+//   lzani_cluster.h     the cluster stage's host side: the edges of the kept results, the run, its entry points
 //   lzani_multi.h       the multi-GPU layer
 #include <hip/hip_runtime.h>
 
@@ -65,6 +67,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_kernels_split.h"
 #include "lzani_kernels_prefilter.h"
 #include "lzani_kernels_outfilter.h"
+#include "lzani_kernels_cluster.h"
 #include "lzani_rtc.h"
 #include "lzani_devmem.h"
 #include "lzani_run_plan.h"
@@ -249,8 +252,18 @@ struct Prefilter {
 // The output filter's result (lzani_kept.h): a kept call -> the next one, or lzani_set_genomes.
 struct Kept {
     bool done = false;
+    u32 n = 0;                            // the genomes of the call
     lzani_kept_info info{};
     DevMem<u32> rec;                      // 9 words a kept pair (lzani_kept_pair)
+};
+
+// The cluster stage's state (lzani_cluster.h): lzani_cluster_begin -> the next one, or lzani_set_genomes.
+struct Cluster {
+    bool begun = false, ran = false;      // ran: rep_of and cluster_of are those of the edges as they are
+    lzani_cluster_info info{};
+    DevMem<u32> len;                      // the reported lengths (n)
+    DevMem<lzani_cluster_edge> edges;     // info.edges of them, a < b; grown geometrically
+    DevMem<u32> rep_of, cluster_of;       // of the last run (n each)
 };
 
 // Residency counters of the last run (lzani_get_residency).
@@ -284,6 +297,7 @@ struct lzani_ctx {
     CandScratch cs;
     Prefilter pf;
     Kept kept;
+    Cluster cl;
     // the last run
     RunRecord run;
     Residency res;
@@ -836,6 +850,7 @@ int run_rows_any(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_of
 
 #include "lzani_prefilter.h"
 #include "lzani_kept.h"
+#include "lzani_cluster.h"
 
 extern "C" {
 
@@ -893,6 +908,7 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     c->cs = CandScratch{};
     c->pf = Prefilter{};
     c->kept = Kept{};
+    c->cl = Cluster{};
     c->res = Residency{};
     c->gs.L.resize(n);
     c->gs.nmoff.resize(n);

@@ -63,6 +63,7 @@ int kept_check_filter(lzani_ctx* c, const std::string& fn, const lzani_out_filte
 int kept_stage_run(lzani_ctx* c, Kept& k, u32 n, const u32* report_len, u32 n_rows, const u32* ref_ids, const u64* row_off, const u32* query_ids,
                    const std::vector<u32>& row_of, const KeptRows& kr, const int* d_results, const lzani_out_filter& f)
 {
+    k.n = n;
     k.info.entries = kr.entries; k.info.leading = kr.leading;
     const u64 E = kr.entries;
     if (!E) { HIPCHK(c, k.rec.alloc(0)); return LZANI_OK; }

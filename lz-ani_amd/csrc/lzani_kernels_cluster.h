@@ -1,0 +1,187 @@
+// lzani_kernels_cluster.h -- device kernels of the cluster stage (lzani_cluster.h; include/lzani.h states the definitions,
+// lzani_cluster_plan.h the weight).  Included by lzani_hip.hip only, behind lzani_kernels_outfilter.h; of
+// lzani_kernels_prefilter.h it uses PF_THREADS (256-thread blocks) and the scan k_pf_scan, of lzani_block.h block_sum.
+//   k_cl_add_kept    one thread per kept record: the weight, one 16-byte edge by one 16-byte vector store
+//   k_cl_init        per node: parent = v, state = UNDECIDED, blocked = 0, best = 0, size = 0
+//   k_cl_hook        SINGLE, one thread per edge: the two roots by following parent, the larger hooked under the smaller
+//                    with atomicCAS(&parent[hi], hi, lo); on a lost CAS, look again.  parent[v] <= v at every moment: no
+//                    cycle, and every retry follows a hook that some thread made
+//   k_cl_roots       SINGLE, per node, behind the kernel boundary: rep_of[v] = root(v)
+//   k_cl_greedy_edges / k_cl_greedy_nodes   one round of the greedy representatives (below)
+//   k_cl_assign_init, k_cl_assign_best, k_cl_assign_min   rep_of of the nodes that are no representatives
+//   k_cl_flags, k_cl_number   the numbering: flags rep_of[v] == v and cluster sizes; behind the scan cluster_of and the
+//                    counts of singletons and of the largest cluster
+// Words that other blocks write inside a launch (parent, state, blocked) are read and written with relaxed agent-scope
+// atomics only: the L2 of an XCD is not coherent with the others for plain accesses inside a kernel.  No thread ever waits
+// for a value that another block has yet to write; edge indexes are 64-bit throughout.
+#pragma once
+#include "lzani_cluster_plan.h"
+
+namespace lzani {
+
+enum : u32 { CL_UNDECIDED = 0, CL_REP = 1, CL_NONREP = 2 };
+enum { CL_SINGLETONS = 0, CL_LARGEST = 1, CL_COUNTERS = 2 };
+constexpr u32 CL_NONE = 0xFFFFFFFFu;
+
+__device__ __forceinline__ u32 cl_load(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void cl_store(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// an edge as the passes read it: one 16-byte load; lo < hi
+struct ClEdge { u32 lo, hi; u64 wbits; };
+__device__ __forceinline__ ClEdge cl_edge(const lzani_cluster_edge* __restrict__ edges, u64 i)
+{
+    const uint4 v = reinterpret_cast<const uint4*>(edges)[i];
+    return ClEdge{v.x, v.y, ((u64)v.w << 32) | v.z};
+}
+
+// rec: 9 words a kept pair (lzani_kept_pair); the edges from `base` on
+__global__ void __launch_bounds__(PF_THREADS) k_cl_add_kept(const u32* __restrict__ rec, u64 count, const u32* __restrict__ len, int measure,
+                                                            lzani_cluster_edge* __restrict__ edges, u64 base)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const u32* __restrict__ r = rec + 9 * i;
+    const u32 a = r[0], b = r[1];
+    const lzani_result X{(int)r[2], (int)r[3], (int)r[4]}, Y{(int)r[5], (int)r[6], (int)r[7]};
+    const double w = cluster_weight(measure, X, Y, r[8], len[a], len[b]);
+    const u64 bits = (u64)__double_as_longlong(w);
+    reinterpret_cast<uint4*>(edges)[base + i] = make_uint4(a, b, (u32)bits, (u32)(bits >> 32));
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_init(u32 n, u32* __restrict__ parent, u32* __restrict__ state, u32* __restrict__ blocked,
+                                                        unsigned long long* __restrict__ best, u32* __restrict__ size)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    parent[v] = v; state[v] = CL_UNDECIDED; blocked[v] = 0; best[v] = 0; size[v] = 0;
+}
+
+// The root of v's tree, halving the path on the way: parent[x] is replaced by an ancestor of x only, with an atomic store
+// (a node that has a parent below it is never a root again, so the store cannot undo a hook).
+__device__ __forceinline__ u32 cl_root(u32* parent, u32 v)
+{
+    for (;;) {
+        const u32 p = cl_load(&parent[v]);
+        if (p == v) return v;
+        const u32 g = cl_load(&parent[p]);
+        if (g == p) return p;
+        cl_store(&parent[v], g);
+        v = g;
+    }
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_hook(const lzani_cluster_edge* __restrict__ edges, u64 count, u32* parent)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const ClEdge e = cl_edge(edges, i);
+    u32 a = cl_root(parent, e.lo), b = cl_root(parent, e.hi);
+    while (a != b) {
+        const u32 lo = a < b ? a : b, hi = a < b ? b : a;
+        const u32 old = atomicCAS(&parent[hi], hi, lo);          // (device scope)
+        if (old == hi) break;
+        a = cl_root(parent, old);                                // hi has a parent now: look again from there
+        b = cl_root(parent, lo);
+    }
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_roots(u32 n, const u32* __restrict__ parent, u32* __restrict__ rep_of)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    u32 x = v;
+    for (u32 p = parent[x]; p != x; p = parent[x]) x = p;
+    rep_of[v] = x;
+}
+
+// One round of the greedy representatives.  Edge pass, a < b: state[a] == REP stores state[b] = NONREP; state[a] ==
+// UNDECIDED stores blocked[b] = 1.  Node pass: an UNDECIDED node with blocked == 0 becomes REP; blocked is cleared; the
+// nodes still undecided are counted.  Both stored values are idempotent, REP and NONREP are final, and a stale UNDECIDED
+// read inside a round only delays a decision: the fixed point is the set of the definition whatever the schedule, and the
+// lowest undecided node is decided in every round.
+__global__ void __launch_bounds__(PF_THREADS) k_cl_greedy_edges(const lzani_cluster_edge* __restrict__ edges, u64 count, u32* state, u32* blocked)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const ClEdge e = cl_edge(edges, i);
+    if (cl_load(&state[e.hi]) != CL_UNDECIDED) return;           // (final: nothing left to say about it)
+    const u32 s = cl_load(&state[e.lo]);
+    if (s == CL_REP) cl_store(&state[e.hi], CL_NONREP);
+    else if (s == CL_UNDECIDED) cl_store(&blocked[e.hi], 1u);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_greedy_nodes(u32 n, u32* __restrict__ state, u32* __restrict__ blocked, u32* __restrict__ undecided)
+{
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 mine = 0;
+    if (v < n && state[v] == CL_UNDECIDED) {
+        if (blocked[v]) { blocked[v] = 0; mine = 1; }
+        else state[v] = CL_REP;
+    }
+    block_sum(mine, &s_cnt);
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(undecided, s_cnt);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_assign_init(u32 n, const u32* __restrict__ state, u32* __restrict__ rep_of)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v < n) rep_of[v] = state[v] == CL_REP ? v : CL_NONE;
+}
+// BEST, first pass: the largest weight's bits over the representative neighbours below a node
+__global__ void __launch_bounds__(PF_THREADS) k_cl_assign_best(const lzani_cluster_edge* __restrict__ edges, u64 count, const u32* __restrict__ state,
+                                                               unsigned long long* __restrict__ best)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const ClEdge e = cl_edge(edges, i);
+    if (state[e.lo] == CL_REP && state[e.hi] == CL_NONREP) atomicMax(&best[e.hi], (unsigned long long)e.wbits);
+}
+// FIRST (best null): the smallest representative neighbour; BEST, second pass: among the edges of the largest weight
+__global__ void __launch_bounds__(PF_THREADS) k_cl_assign_min(const lzani_cluster_edge* __restrict__ edges, u64 count, const u32* __restrict__ state,
+                                                              const unsigned long long* __restrict__ best, u32* __restrict__ rep_of)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const ClEdge e = cl_edge(edges, i);
+    if (state[e.lo] != CL_REP || state[e.hi] != CL_NONREP) return;
+    if (best && best[e.hi] != e.wbits) return;
+    atomicMin(&rep_of[e.hi], e.lo);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_flags(u32 n, const u32* __restrict__ rep_of, u32* __restrict__ flag, u32* __restrict__ size)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    const u32 r = rep_of[v];
+    flag[v] = r == v ? 1u : 0u;
+    if (r < n) atomicAdd(&size[r], 1u);                          // (every node has a representative; a defect must not write astray)
+}
+// below[v] = the representatives with an id below v (the scan of the flags)
+__global__ void __launch_bounds__(PF_THREADS) k_cl_number(u32 n, const u32* __restrict__ rep_of, const u64* __restrict__ below, const u32* __restrict__ size,
+                                                          u32* __restrict__ cluster_of, u32* __restrict__ counters)
+{
+    __shared__ u32 s_one, s_max;
+    if (threadIdx.x == 0) { s_one = 0; s_max = 0; }
+    __syncthreads();
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 one = 0, sz = 0;
+    if (v < n) {
+        const u32 r = rep_of[v];
+        cluster_of[v] = r < n ? (u32)below[r] : CL_NONE;
+        sz = size[v];
+        one = sz == 1 ? 1u : 0u;
+    }
+    block_sum(one, &s_one);
+    for (int d = 32; d >= 1; d >>= 1) { const u32 o = __shfl_xor(sz, d); sz = sz > o ? sz : o; }
+    if ((threadIdx.x & 63) == 0 && sz) atomicMax(&s_max, sz);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_one) atomicAdd(&counters[CL_SINGLETONS], s_one);
+        if (s_max) atomicMax(&counters[CL_LARGEST], s_max);
+    }
+}
+
+}  // namespace lzani

@@ -19,6 +19,7 @@
 //                                            lzani_group_run_rows_kept: the same stages up to the scatter kernel, then the output
 //                                            filter's stage (lzani_kept.h) on the CSR-ordered buffer, on the first device's context
 //                                            and stream; the copy out of the full results is left out
+//                                            lzani_group_cluster_*: the cluster stage (lzani_cluster.h) on that context
 #pragma once
 #include <rccl/rccl.h>
 
@@ -503,6 +504,41 @@ int lzani_group_get_kept_info(const lzani_group* g, lzani_kept_info* info)
 {
     if (!g) return LZANI_ERR_ARG;
     return lzani_get_kept_info(g->ctx[0], info);
+}
+
+// The cluster stage for the group (lzani_cluster.h): on the first device's context, where the group's kept results are.
+int lzani_group_cluster_begin(lzani_group* g, uint32_t n, const uint32_t* report_len, int measure)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_cluster_begin(g->ctx[0], n, report_len, measure);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_cluster_add_kept(lzani_group* g, uint64_t* edges_total)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_cluster_add_kept(g->ctx[0], edges_total);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_cluster_run(lzani_group* g, int algo, uint64_t* n_clusters)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_cluster_run(g->ctx[0], algo, n_clusters);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_cluster_fetch(lzani_group* g, uint32_t* rep_of, uint32_t* cluster_of)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_cluster_fetch(g->ctx[0], rep_of, cluster_of);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_get_cluster_info(const lzani_group* g, lzani_cluster_info* info)
+{
+    if (!g) return LZANI_ERR_ARG;
+    return lzani_get_cluster_info(g->ctx[0], info);
 }
 
 int lzani_group_set_genome_memory(lzani_group* g, uint64_t bytes)

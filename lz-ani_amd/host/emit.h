@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/lzani.h"
+#include "../csrc/lzani_cluster_plan.h"
 #include "ingest.h"
 
 namespace host {
@@ -179,12 +180,12 @@ struct Direction {
     double tani, gani, ani, qcov, rcov;
 };
 
-inline Direction make_direction(const std::vector<Genome>& g, const std::vector<uint32_t>& len, uint32_t q, uint32_t r,
-                                const lzani_result& own, const lzani_result& rev, double tani)
+// the numbers of a direction (the names stay null)
+inline Direction direction_values(const std::vector<uint32_t>& len, uint32_t q, uint32_t r, const lzani_result& own, const lzani_result& rev, double tani)
 {
     Direction d;
     d.qidx = q; d.ridx = r; d.qlen = len[q]; d.rlen = len[r];
-    d.qname = &g[q].name; d.rname = &g[r].name;
+    d.qname = d.rname = nullptr;
     d.nt_match = own.sym_in_matches; d.nt_mismatch = own.sym_in_literals; d.num_alns = own.no_components;
     const int32_t aligned = own.sym_in_matches + own.sym_in_literals, aligned_rev = rev.sym_in_matches + rev.sym_in_literals;
     d.tani = tani;
@@ -192,6 +193,14 @@ inline Direction make_direction(const std::vector<Genome>& g, const std::vector<
     d.ani = aligned != 0 ? (double)own.sym_in_matches / aligned : 0;
     d.qcov = (double)aligned / d.qlen;
     d.rcov = (double)aligned_rev / d.rlen;
+    return d;
+}
+
+inline Direction make_direction(const std::vector<Genome>& g, const std::vector<uint32_t>& len, uint32_t q, uint32_t r,
+                                const lzani_result& own, const lzani_result& rev, double tani)
+{
+    Direction d = direction_values(len, q, r, own, rev, tani);
+    d.qname = &g[q].name; d.rname = &g[r].name;
     return d;
 }
 
@@ -241,9 +250,15 @@ inline std::vector<Cut> make_cuts(const EmitParams& ep)
     return cuts;
 }
 
+inline bool direction_passes(const Direction& d, const std::vector<Cut>& cuts)
+{
+    for (const Cut& c : cuts) if (d.*(c.field) < c.min) return false;
+    return true;
+}
+
 inline void write_direction(const Direction& d, const EmitParams& ep, const std::vector<Cut>& cuts, std::string& out)
 {
-    for (const Cut& c : cuts) if (d.*(c.field) < c.min) return;
+    if (!direction_passes(d, cuts)) return;
     LineOut o{out, {0}};
     const ColumnFn* col = column_table();
     const double m = ep.in_percent ? 100 : 1;
@@ -279,6 +294,26 @@ inline void format_row(const std::vector<Genome>& g, const std::vector<uint32_t>
         const double tani = (double)(X.sym_in_matches + Y->sym_in_matches) / (len[b] + len[a]);
         write_direction(make_direction(g, len, b, a, X, *Y, tani), ep, cuts, out);
         write_direction(make_direction(g, len, a, b, *Y, X, tani), ep, cuts, out);
+    }
+}
+
+// The edges of the similarity graph as this emitter sees them (the host path of `lz-ani --cluster`): the pairs format_row
+// walks, of which direction_passes lets at least one line through; those lines give `lines`, lzani_cluster_plan.h the weight.
+inline void cluster_edges_of(const std::vector<uint32_t>& len, const PairTable& T, const std::vector<Cut>& cuts, int measure,
+                             std::vector<lzani_cluster_edge>& edges)
+{
+    for (uint32_t a = 0; a < T.n; ++a) {
+        const uint64_t cnt = T.row_size(a);
+        for (uint64_t j = T.first_above(a); j < cnt; ++j) {
+            const uint32_t b = T.id_at(a, j);
+            const lzani_result& X = T.at(a, j);
+            const lzani_result* Y = T.find(b, a);
+            if (!Y) continue;
+            const double tani = (double)(X.sym_in_matches + Y->sym_in_matches) / (len[b] + len[a]);
+            Direction d0 = direction_values(len, b, a, X, *Y, tani), d1 = direction_values(len, a, b, *Y, X, tani);
+            const uint32_t lines = (direction_passes(d0, cuts) ? 1u : 0u) | (direction_passes(d1, cuts) ? 2u : 0u);
+            if (lines) edges.push_back(lzani_cluster_edge{a, b, lzani::cluster_weight(measure, X, *Y, lines, len[a], len[b])});
+        }
     }
 }
 

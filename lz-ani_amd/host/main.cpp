@@ -13,6 +13,9 @@
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
 // --out-filter on a two-TSV output is applied on the device (lzani_group_run_rows_kept): only the pairs of which a line
 // passes come back, and the table of all pairs is never made; LZANI_OUT_FILTER=host keeps the filter on the host.
+// --cluster <single|greedy-first|greedy-best> clusters the pairs the output filter keeps (include/lzani.h, "clustering the
+// kept pairs") and writes one line per genome to --cluster-out: on the device where the filter is applied there
+// (lzani_group_cluster_*), else by the sequential statement of lzani_cluster_plan.h over the emitter's own lines.
 #include <dlfcn.h>
 
 #include <chrono>
@@ -56,6 +59,9 @@ struct Params {
     double flt_fraction = 1;
     string flt_counting_arg;                                // --flt-kmers-counting as given; checked after the flags are read
     int flt_counting = LZANI_PF_COUNTING_AUTO;
+    string cluster_arg, cluster_out, cluster_measure_arg;  // --cluster, --cluster-out, --cluster-measure as given
+    bool cluster = false, cluster_reps = false;             // --cluster given; --cluster-representatives
+    int cluster_algo = LZANI_CLUSTER_SINGLE, cluster_measure = LZANI_CLUSTER_TANI;
 };
 
 static Params P;
@@ -133,6 +139,11 @@ static void usage()
     for (auto& kv : comp_metas()) cerr << "                                   " << kv.first << "=" << kv.second << "\n";
     cerr << "                                   (default: standard)\n"
          << "      --out-filter <par> <float> - store only results with <par> (can be: tani, gani, ani, cov) at least <float>; can be used multiple times\n"
+         << "      --cluster <algorithm>      - all2all: cluster the pairs that --out-filter keeps; one of single (connected components),\n"
+         << "                                   greedy-first (first representative, as CD-HIT), greedy-best (most similar representative, as UCLUST)\n"
+         << "      --cluster-out <file_name>  - output file of --cluster: one line per sequence, its id and its cluster number\n"
+         << "      --cluster-measure <type>   - the similarity greedy-best compares: tani, gani or ani (default: tani)\n"
+         << "      --cluster-representatives  - write the representative's id instead of the cluster number\n"
          << "Options - LZ-parsing-related:\n"
          << "  -a, --mal <int>                - min. anchor length (default: 11)\n"
          << "  -s, --msl <int>                - min. seed length (default: 7)\n"
@@ -236,6 +247,10 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--device" && has(1)) { P.device = atoi(argv[i + 1]); i += 2; }
         else if (par == "--results-out" && has(1)) { P.results_out = argv[i + 1]; i += 2; }
         else if (par == "--results-in" && has(1)) { P.results_in = argv[i + 1]; i += 2; }
+        else if (par == "--cluster" && has(1)) { P.cluster = true; P.cluster_arg = argv[i + 1]; i += 2; }
+        else if (par == "--cluster-out" && has(1)) { P.cluster_out = argv[i + 1]; i += 2; }
+        else if (par == "--cluster-measure" && has(1)) { P.cluster_measure_arg = argv[i + 1]; i += 2; }
+        else if (par == "--cluster-representatives") { P.cluster_reps = true; i += 1; }
         else { cerr << "Unknown parameter: " << argv[i] << endl; usage(); exit(1); }
     }
     // query2ref: what it does not take, and what only it takes
@@ -260,6 +275,25 @@ static bool parse_params(int argc, char** argv)
             cerr << "Invalid value for --flt-kmers-counting: " << P.flt_counting_arg << " (auto, dense or sparse)" << endl;
             exit(1);
         }
+    }
+    // --cluster: refused here, before any input is read
+    if (!P.cluster && (!P.cluster_out.empty() || !P.cluster_measure_arg.empty() || P.cluster_reps)) {
+        cerr << "--cluster-out, --cluster-measure and --cluster-representatives belong to --cluster" << endl;
+        exit(1);
+    }
+    if (P.cluster) {
+        static const map<string, int> algos = {{"single", LZANI_CLUSTER_SINGLE}, {"greedy-first", LZANI_CLUSTER_GREEDY_FIRST}, {"greedy-best", LZANI_CLUSTER_GREEDY_BEST}};
+        static const map<string, int> measures = {{"tani", LZANI_CLUSTER_TANI}, {"gani", LZANI_CLUSTER_GANI}, {"ani", LZANI_CLUSTER_ANI}};
+        const auto a = algos.find(P.cluster_arg);
+        if (a == algos.end()) { cerr << "Unknown value for --cluster: " << P.cluster_arg << " (single, greedy-first or greedy-best)" << endl; exit(1); }
+        P.cluster_algo = a->second;
+        const auto m = measures.find(P.cluster_measure_arg.empty() ? "tani" : P.cluster_measure_arg);
+        if (m == measures.end()) { cerr << "Unknown value for --cluster-measure: " << P.cluster_measure_arg << " (tani, gani or ani)" << endl; exit(1); }
+        P.cluster_measure = m->second;
+        if (P.cluster_out.empty()) { cerr << "--cluster needs --cluster-out <file_name>" << endl; exit(1); }
+        if (P.query2ref) { cerr << "--cluster belongs to the mode all2all (query2ref compares two sets)" << endl; exit(1); }
+        if (P.single_txt) { cerr << "--cluster cannot be used with --out-type single-txt (it takes no output filter)" << endl; exit(1); }
+        if (!P.flt_mask) { cerr << "--cluster needs an --out-filter: the pairs it keeps are the edges of the graph" << endl; exit(1); }
     }
     if (P.inputs.empty()) { cerr << "Input file names not provided\n"; return false; }
     // The engine's parameter envelope (lz-ani_amd/csrc/lzani_layout.h: params_supported).  The reference accepts any
@@ -343,6 +377,13 @@ struct Engine {
     int (*group_kept_fetch)(lzani_group*, uint64_t, uint64_t, lzani_kept_pair*) = nullptr;
     int (*group_get_kept_info)(const lzani_group*, lzani_kept_info*) = nullptr;
     bool has_kept() const { return group_run_rows_kept && group_kept_fetch && group_get_kept_info; }
+    // the cluster stage: bound where the library has it (an older one: the clusters are made on the host)
+    int (*group_cluster_begin)(lzani_group*, uint32_t, const uint32_t*, int) = nullptr;
+    int (*group_cluster_add_kept)(lzani_group*, uint64_t*) = nullptr;
+    int (*group_cluster_run)(lzani_group*, int, uint64_t*) = nullptr;
+    int (*group_cluster_fetch)(lzani_group*, uint32_t*, uint32_t*) = nullptr;
+    int (*group_get_cluster_info)(const lzani_group*, lzani_cluster_info*) = nullptr;
+    bool has_cluster() const { return group_cluster_begin && group_cluster_add_kept && group_cluster_run && group_cluster_fetch && group_get_cluster_info; }
     bool load(const char* argv0)
     {
         vector<string> cand;
@@ -364,6 +405,7 @@ struct Engine {
 #undef BIND
 #define BIND(f) f = reinterpret_cast<decltype(f)>(dlsym(so, "lzani_" #f));
         BIND(group_run_rows_kept) BIND(group_kept_fetch) BIND(group_get_kept_info)
+        BIND(group_cluster_begin) BIND(group_cluster_add_kept) BIND(group_cluster_run) BIND(group_cluster_fetch) BIND(group_get_cluster_info)
 #undef BIND
         return true;
     }
@@ -568,6 +610,64 @@ static void print_kept(const lzani_kept_info& k)
          << " unpaired, " << k.filter_ms << " ms\n";
 }
 
+// --cluster-out: one line per genome in the order of the ids file, its id and its cluster number or its representative's id.
+static bool write_clusters(const vector<Genome>& g, const vector<uint32_t>& rep_of, const vector<uint32_t>& cluster_of)
+{
+    ofstream o(P.cluster_out, ios::binary);
+    if (!o.is_open()) { cerr << "Cannot open output file: " << P.cluster_out << endl; return false; }
+    o << "object\t" << (P.cluster_reps ? "representative" : "cluster") << "\n";
+    for (size_t i = 0; i < g.size(); ++i) {
+        o << g[i].name << '\t';
+        if (P.cluster_reps) o << g[rep_of[i]].name; else o << cluster_of[i];
+        o << '\n';
+    }
+    o.close();
+    return !o.fail();
+}
+
+// The device path of --cluster: an empty edge set before the kept calls, the edges of each kept call added behind it, and
+// at the end the run, the fetch and the file.
+static bool cluster_begin(const Engine& E, lzani_group* grp, const vector<uint32_t>& rlen)
+{
+    if (E.group_cluster_begin(grp, (uint32_t)rlen.size(), rlen.data(), P.cluster_measure) == LZANI_OK) return true;
+    cerr << "Clustering failed: " << E.group_last_error(grp) << endl;
+    return false;
+}
+static bool cluster_add_kept(const Engine& E, lzani_group* grp)
+{
+    if (E.group_cluster_add_kept(grp, nullptr) == LZANI_OK) return true;
+    cerr << "Clustering failed: " << E.group_last_error(grp) << endl;
+    return false;
+}
+static bool cluster_finish(const Engine& E, lzani_group* grp, const vector<Genome>& g)
+{
+    vector<uint32_t> rep_of(g.size()), cluster_of(g.size());
+    if (E.group_cluster_run(grp, P.cluster_algo, nullptr) != LZANI_OK || E.group_cluster_fetch(grp, rep_of.data(), cluster_of.data()) != LZANI_OK) {
+        cerr << "Clustering failed: " << E.group_last_error(grp) << endl;
+        return false;
+    }
+    lzani_cluster_info ci;
+    if (P.verbosity >= 2 && E.group_get_cluster_info(grp, &ci) == LZANI_OK)
+        cerr << "clusters on the device: " << ci.clusters << " of " << ci.n << " sequences (" << ci.singletons << " singletons, the largest of " << ci.largest
+             << ") from " << ci.edges << " pairs, " << ci.rounds << " round(s), add " << ci.add_ms << " ms, run " << ci.run_ms << " ms\n";
+    return write_clusters(g, rep_of, cluster_of);
+}
+
+// The host path of --cluster: the pairs of which the emitter lets a line through, by the sequential statement.
+static bool cluster_on_host(const vector<Genome>& g, const PairTable& T, const EmitParams& ep)
+{
+    vector<lzani_cluster_edge> edges;
+    cluster_edges_of(report_lengths(g, ep.mrd), T, make_cuts(ep), P.cluster_measure, edges);
+    vector<uint32_t> rep_of(g.size()), cluster_of(g.size());
+    uint32_t k = 0;
+    if (!g.empty() && lzani::cluster_host((uint32_t)g.size(), edges.data(), edges.size(), P.cluster_algo, rep_of.data(), cluster_of.data(), &k) != LZANI_OK) {
+        cerr << "Clustering failed" << endl;
+        return false;
+    }
+    if (P.verbosity >= 2) cerr << "clusters on the host: " << k << " of " << g.size() << " sequences from " << edges.size() << " pairs\n";
+    return write_clusters(g, rep_of, cluster_of);
+}
+
 // The kept records of the group's last kept call, fetched in pieces of a million (36 MB) and written as they come.
 static bool emit_kept_result(const Engine& E, lzani_group* grp, const vector<Genome>& g, ResultWriter& W, uint64_t n_kept)
 {
@@ -603,6 +703,7 @@ static bool do_matching_kept(const Engine& E, const vector<Genome>& g, Filter& f
     const lzani_out_filter f = out_filter_minima();
     const vector<uint32_t> rlen = report_lengths(g, ep.mrd);   // the lengths the TSV prints
     uint64_t n_kept = 0;
+    if (P.cluster && !cluster_begin(E, grp, rlen)) { E.group_destroy(grp); return false; }
     const auto t_c = chrono::steady_clock::now();
     const int rc = E.group_run_rows_kept(grp, n, ref_ids.data(), row_off.data(), dense ? nullptr : qids.data(), &f, rlen.data(), &n_kept);
     if (P.verbosity >= 2)
@@ -613,6 +714,7 @@ static bool do_matching_kept(const Engine& E, const vector<Genome>& g, Filter& f
         lzani_kept_info ki;
         if (E.group_get_kept_info(grp, &ki) == LZANI_OK) print_kept(ki);
     }
+    if (P.cluster && !(cluster_add_kept(E, grp) && cluster_finish(E, grp, g))) { E.group_destroy(grp); return false; }
     if (P.verbosity >= 1) cerr << "Storing results" << endl;
     ResultWriter W;
     const bool ok = W.open(g, ep) && emit_kept_result(E, grp, g, W, n_kept);
@@ -750,6 +852,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         }
     });
     const lzani_out_filter flt_min = out_filter_minima();
+    const bool cluster = kept && P.cluster;                    // every unordered pair lies in exactly one block: its edges are added there
     lzani_kept_info k_sum{};
     vector<lzani_timing> t_sum(devs.size(), lzani_timing{});   // (cand_ms: the k-mer words and the candidate stage)
     vector<uint64_t> r_tiles(devs.size(), 0), r_uploads(devs.size(), 0);
@@ -784,7 +887,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         { lock_guard<mutex> lk(mtx); ready.emplace_back(B.a0, B.a1); }
         cv.notify_one();
     };
-    bool ok = true;
+    bool ok = !cluster || cluster_begin(E, grp, W.lengths());
     future<void> f_build, f_post;
     build(0);
     for (uint32_t k = 0; k < n_blocks && ok; ++k) {
@@ -795,6 +898,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
             const int rc = kept ? E.group_run_rows_kept(grp, (uint32_t)B.rows.size(), B.rows.data(), B.off.data(), B.q.data(), &flt_min, W.lengths().data(), &n_kept)
                                 : E.group_run_rows(grp, (uint32_t)B.rows.size(), B.rows.data(), B.off.data(), B.q.data(), B.out.data());
             if (rc != LZANI_OK) { cerr << "LZ matching failed: " << E.group_last_error(grp) << endl; ok = false; }
+            if (cluster && ok) ok = cluster_add_kept(E, grp);       // before the next block's kept call replaces the records
             if (kept && ok) {
                 vector<lzani_kept_pair> rec((size_t)n_kept);
                 lzani_kept_info ki;
@@ -822,6 +926,7 @@ static bool do_matching_tiled(const Engine& E, const vector<Genome>& g, PairTabl
         if (ok && !kept) f_post = async(launch::async, post, k);
     }
     if (f_post.valid()) f_post.get();
+    if (cluster && ok) ok = cluster_finish(E, grp, g);
     { lock_guard<mutex> lk(mtx); done = true; }
     cv.notify_one();
     if (P.verbosity >= 2 && ok) {
@@ -963,11 +1068,13 @@ static bool run_all2all(const char* argv0)
 
     PairTable results;
     bool stored = tiled;                                    // the result files are written already
+    bool clustered = false;                                 // ... and so is the cluster file (the device path)
     if (!P.results_in.empty()) { if (!read_raw(P.results_in, g.size(), results)) return false; }
     else {
         if (!engine_loaded && !E.load(argv0)) return false;
         // --out-filter on the device where it applies to the TSV, the library has the stage and the filter's lists are sets
-        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt);
+        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt) && (!P.cluster || E.has_cluster());
+        clustered = kept && P.cluster;
         if (tiled) {
             if (P.verbosity >= 1) cerr << "Storing results (row blocks, while the matching goes on)" << endl;
             if (!do_matching_tiled(E, g, results, ep, tile, kept)) return false;
@@ -982,6 +1089,8 @@ static bool run_all2all(const char* argv0)
     }
     stamp(stored ? "LZ matching + storing results" : "LZ matching");
     if (!P.results_out.empty() && !write_raw(P.results_out, results)) return false;
+
+    if (P.cluster && !clustered && !cluster_on_host(g, results, ep)) return false;
 
     if (!stored) {
         if (P.verbosity >= 1) cerr << "Storing results" << endl;

@@ -41,7 +41,11 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_set_prefilter_counting", "lzani_get_prefilter_sparse_info", "lzani_plan_sparse_tiles",
            "lzani_out_filter_lines", "lzani_run_rows_kept", "lzani_kept_fetch", "lzani_filter_results_device",
            "lzani_debug_filter_results", "lzani_get_kept_info", "lzani_group_run_rows_kept", "lzani_group_kept_fetch",
-           "lzani_group_get_kept_info")
+           "lzani_group_get_kept_info",
+           "lzani_cluster_weight", "lzani_cluster_host", "lzani_cluster_begin", "lzani_cluster_add_kept",
+           "lzani_debug_cluster_add_edges", "lzani_cluster_run", "lzani_cluster_fetch", "lzani_get_cluster_info",
+           "lzani_group_cluster_begin", "lzani_group_cluster_add_kept", "lzani_group_cluster_run", "lzani_group_cluster_fetch",
+           "lzani_group_get_cluster_info")
 
 
 class LzaniError(RuntimeError):
@@ -164,6 +168,60 @@ def _kept_info(o):
     return {k: getattr(o, k) for k, _ in KeptInfo._fields_}
 
 
+class ClusterInfo(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("algo", C.c_int32), ("measure", C.c_int32), ("rounds", C.c_uint32), ("edges", C.c_uint64),
+                ("clusters", C.c_uint64), ("singletons", C.c_uint64), ("largest", C.c_uint64), ("edge_bytes", C.c_uint64),
+                ("add_ms", C.c_double), ("run_ms", C.c_double)]
+
+
+# lzani_cluster_edge as a numpy record: a < b (either order is taken), w >= 0
+EDGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("w", np.float64)])
+assert EDGE_DTYPE.itemsize == 16
+CLUSTER_ALGOS = {"single": 0, "greedy-first": 1, "greedy-best": 2}        # LZANI_CLUSTER_SINGLE ...
+CLUSTER_MEASURES = {"tani": 0, "gani": 1, "ani": 2}                       # LZANI_CLUSTER_TANI ...
+
+
+def _algo(a):
+    return CLUSTER_ALGOS[a] if isinstance(a, str) else int(a)
+
+
+def _measure(m):
+    return CLUSTER_MEASURES[m] if isinstance(m, str) else int(m)
+
+
+def _cluster_info(o):
+    return {k: getattr(o, k) for k, _ in ClusterInfo._fields_}
+
+
+def cluster_edges(a, b, w):
+    """An EDGE_DTYPE array from three sequences."""
+    e = np.zeros(len(a), dtype=EDGE_DTYPE)
+    e["a"], e["b"], e["w"] = a, b, w
+    return e
+
+
+def cluster_weight(measure, x, y, lines, len_a, len_b):
+    """lzani_cluster_weight (no GPU needed): the weight of the pair a < b with x = result of (ref a, query b), y = result of
+    (ref b, query a) and the output filter's `lines`; NaN for an unknown measure."""
+    lib = load_library()
+    rx, ry = Result(*[int(v) for v in x]), Result(*[int(v) for v in y])
+    return float(lib.lzani_cluster_weight(_measure(measure), C.byref(rx), C.byref(ry), C.c_uint32(int(lines)), C.c_uint32(int(len_a)),
+                                          C.c_uint32(int(len_b))))
+
+
+def cluster_host(n, edges, algo):
+    """lzani_cluster_host (no GPU needed): (rep_of uint32[n], cluster_of uint32[n], clusters) of EDGE_DTYPE edges."""
+    lib = load_library()
+    e = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    rep, cl = np.zeros(int(n), dtype=np.uint32), np.zeros(int(n), dtype=np.uint32)
+    k = C.c_uint32(0)
+    rc = lib.lzani_cluster_host(C.c_uint32(int(n)), _ptr(e) if len(e) else None, C.c_uint64(len(e)), _algo(algo), _ptr(rep) if n else None,
+                                _ptr(cl) if n else None, C.byref(k))
+    if rc != 0:
+        raise LzaniError(f"lzani_cluster_host: {ERRORS.get(rc, rc)}")
+    return rep, cl, int(k.value)
+
+
 PF_COUNTING = {"auto": 0, "dense": 1, "sparse": 2}   # LZANI_PF_COUNTING_*
 PREFILTER_BINS = 4096                               # bins of the prefilter's k-mer passes
 SAMPLE_ALL = 0xFFFFFFFFFFFFFFFF                     # lzani_prefilter's sample_max that keeps every k-mer
@@ -269,6 +327,16 @@ def load_library():
         lib.lzani_group_run_rows_kept.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         lib.lzani_group_kept_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         lib.lzani_group_get_kept_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_cluster_weight.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.lzani_cluster_weight.restype = C.c_double
+        lib.lzani_cluster_host.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        for pre in ("lzani_", "lzani_group_"):
+            getattr(lib, pre + "cluster_begin").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+            getattr(lib, pre + "cluster_add_kept").argtypes = [C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "cluster_run").argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            getattr(lib, pre + "cluster_fetch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "get_cluster_info").argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_debug_cluster_add_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         _lib = lib
     return _lib
 
@@ -437,8 +505,46 @@ def comm_unique_id():
     return bytes(buf)
 
 
-class Group:
+class _ClusterCalls:
+    """The cluster stage of an Engine (pre = "lzani_") or a Group (pre = "lzani_group_": the first device's context)."""
+
+    def cluster_begin(self, n=None, report_len=None, measure="tani"):
+        """An empty edge set for n genomes (default: the genome set's) with their reported lengths (default: its own)."""
+        n = int(self.n if n is None else n)
+        rl = None if report_len is None else np.ascontiguousarray(report_len, dtype=np.uint32)
+        assert rl is None or len(rl) == n
+        self._check(getattr(self.lib, self._pre + "cluster_begin")(self.h, n, _ptr(rl), _measure(measure)), self._pre + "cluster_begin")
+        self._cluster_n = n
+
+    def cluster_add_kept(self):
+        """Appends the edges of the current kept result; returns the number of edge records there are now."""
+        tot = C.c_uint64(0)
+        self._check(getattr(self.lib, self._pre + "cluster_add_kept")(self.h, C.byref(tot)), self._pre + "cluster_add_kept")
+        return int(tot.value)
+
+    def cluster_run(self, algo):
+        """Runs "single", "greedy-first" or "greedy-best" on the edges there are; returns the number of clusters."""
+        k = C.c_uint64(0)
+        self._check(getattr(self.lib, self._pre + "cluster_run")(self.h, _algo(algo), C.byref(k)), self._pre + "cluster_run")
+        return int(k.value)
+
+    def cluster_fetch(self):
+        """(rep_of uint32[n], cluster_of uint32[n]) of the last run."""
+        n = getattr(self, "_cluster_n", 0)
+        rep, cl = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(getattr(self.lib, self._pre + "cluster_fetch")(self.h, _ptr(rep), _ptr(cl)), self._pre + "cluster_fetch")
+        return rep[:n], cl[:n]
+
+    def cluster_info(self):
+        """n, algo, measure, rounds, edges, clusters, singletons, largest, edge_bytes, add_ms, run_ms."""
+        o = ClusterInfo()
+        self._check(getattr(self.lib, self._pre + "get_cluster_info")(self.h, C.byref(o)), self._pre + "get_cluster_info")
+        return _cluster_info(o)
+
+
+class Group(_ClusterCalls):
     """lzani_group_*: one process, several GPUs (what `lz-ani --gpus n` uses)."""
+    _pre = "lzani_group_"
 
     def __init__(self, params=None, devices=(0,)):
         self.lib = load_library()
@@ -518,7 +624,14 @@ class Group:
                     cand_ms=t.cand_ms, kmers_ms=t.kmers_ms)
 
 
-class Engine:
+class Engine(_ClusterCalls):
+    _pre = "lzani_"
+
+    def debug_cluster_add_edges(self, edges):
+        """Test hook: appends made-up EDGE_DTYPE edges from host memory."""
+        e = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+        self._check(self.lib.lzani_debug_cluster_add_edges(self.h, _ptr(e) if len(e) else None, C.c_uint64(len(e))), "lzani_debug_cluster_add_edges")
+
     def __init__(self, params=None, device=0):
         self.lib = load_library()
         arr, self.params = params_array(params)

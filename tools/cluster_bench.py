@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""GPU box: the cluster stage on the family set of tools/related_bench.py (n genomes in families of `fam`, the rows hold the
+same-family pairs) behind an output filter that keeps the related pairs.  One lzani_run_rows_kept, then per algorithm
+begin -> add_kept -> run; lzani_cluster_host on the same edges for the wall time of the sequential statement, and its
+answer compared.  Prints one JSON object (profiles/cluster_stage.json).  Usage: tools/cluster_bench.py [n] [fam] [dmax]"""
+import json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("lz-ani_amd", "oracle", "tools", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+import numpy as np
+import lzani_ctypes as L
+import cluster_model as CM
+import synth_genomes as SG
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
+fam = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+dmax = float(sys.argv[3]) if len(sys.argv) > 3 else 0.15
+flt = {"ani": 0.7, "qcov": 0.5}
+t = time.perf_counter()
+_, seqs = SG.make_set(n, 1, fam=fam, dmax=dmax)
+print(f"{n} genomes made in {time.perf_counter() - t:.0f} s", file=sys.stderr, flush=True)
+rows = [[q for q in range((r // fam) * fam, min(n, (r // fam + 1) * fam)) if q != r] for r in range(n)]
+ref_ids = np.arange(n, dtype=np.uint32)
+row_off = np.zeros(n + 1, dtype=np.uint64)
+row_off[1:] = np.cumsum([len(r) for r in rows])
+q = np.array([x for r in rows for x in r], dtype=np.uint32)
+eng = L.Engine()
+eng.set_genomes(seqs)
+t = time.perf_counter()
+kept = eng.run_rows_kept(ref_ids, row_off, q, flt, fetch=False)
+wall = time.perf_counter() - t
+tm, ki = eng.timing(), eng.kept_info()
+print(f"run_rows_kept: {wall:.1f} s wall, pairs_ms {tm['pairs_ms']:.1f}, kept {kept} of {ki['leading']} pairs", file=sys.stderr, flush=True)
+rec = eng.kept_fetch(0, kept)
+lens = np.array([len(s) for s in seqs], dtype=np.uint32)
+out = dict(workload=dict(genomes=n, family=fam, dmax=dmax, directed_pairs=int(len(q)), out_filter=flt, leading_pairs=int(ki["leading"]),
+                         kept_pairs=int(kept)),
+           pairs_ms=tm["pairs_ms"], index_ms=tm["index_ms"], filter_ms=ki["filter_ms"], algorithms={})
+for algo in CM.ALGOS:
+    eng.cluster_begin(measure="tani")
+    eng.cluster_add_kept()
+    eng.cluster_run(algo)
+    eng.cluster_run(algo)                                   # (the second run: no first-launch cost)
+    info = eng.cluster_info()
+    rep, cl = eng.cluster_fetch()
+    edges = L.cluster_edges(rec["a"], rec["b"], CM.weight("tani", rec["x"], rec["y"], rec["lines"], lens[rec["a"]], lens[rec["b"]]))
+    t = time.perf_counter()
+    h_rep, h_cl, h_k = L.cluster_host(n, edges, algo)
+    host_ms = (time.perf_counter() - t) * 1e3
+    same = bool(np.array_equal(rep, h_rep) and np.array_equal(cl, h_cl))
+    out["algorithms"][algo] = dict(edges=int(info["edges"]), add_ms=info["add_ms"], run_ms=info["run_ms"], rounds=int(info["rounds"]),
+                                   clusters=int(info["clusters"]), singletons=int(info["singletons"]), largest=int(info["largest"]),
+                                   edge_bytes=int(info["edge_bytes"]), cluster_host_wall_ms=host_ms, equals_cluster_host=same,
+                                   below_pairs_ms=bool(info["add_ms"] + info["run_ms"] < tm["pairs_ms"]))
+eng.close()
+print(json.dumps(out, indent=1))
+sys.exit(0 if all(a["equals_cluster_host"] for a in out["algorithms"].values()) else 1)
