@@ -1,4 +1,6 @@
-// emit.h -- result files of the `lz-ani` host binary: ids TSV, ANI TSV, single-txt.
+// emit.h -- result files of the `lz-ani` host binary: ids TSV, ANI TSV, single-txt -- the number formatting, the table of all
+// pairs, the records of the pairs that are written, their text and the writer.  Uses ingest.h (Genome, split) and
+// csrc/lzani_out_filter.h (the five values of a line and the filter's rule); nothing of the binary's other headers.
 //
 // Behaviour follows CLZMatcher::store_results (/root/reference/src/lz_matcher.cpp:280-579) and the
 // number formatting of refresh::real_to_pchar (/root/reference/libs/refresh/conversions/lib/
@@ -21,7 +23,7 @@
 #include <vector>
 
 #include "../../include/lzani.h"
-#include "../csrc/lzani_cluster_plan.h"
+#include "../csrc/lzani_out_filter.h"
 #include "ingest.h"
 
 namespace host {
@@ -120,22 +122,23 @@ struct PairTable {
     std::vector<uint32_t> query_ids;        // filtered runs only
     std::vector<lzani_result> res;          // CSR-aligned
 
-    void init_dense(uint32_t n_)
+    // results = false: the layout alone (the engine's kept form never fills the table)
+    void init_dense(uint32_t n_, bool results = true)
     {
         n = n_; dense = true; query_ids.clear();
         row_off.resize((size_t)n + 1);
         for (uint32_t r = 0; r <= n; ++r) row_off[r] = (uint64_t)r * (n ? n - 1 : 0);
-        res.assign(row_off[n], lzani_result{0, 0, 0});
+        res.assign(results ? row_off[n] : 0, lzani_result{0, 0, 0});
     }
     // rows[r] = query ids of reference r (any order; sorted here)
-    void init_sparse(std::vector<std::vector<uint32_t>>& rows)
+    void init_sparse(std::vector<std::vector<uint32_t>>& rows, bool results = true)
     {
         n = (uint32_t)rows.size(); dense = false;
         row_off.assign((size_t)n + 1, 0);
         for (uint32_t r = 0; r < n; ++r) { std::sort(rows[r].begin(), rows[r].end()); row_off[r + 1] = row_off[r] + rows[r].size(); }
         query_ids.resize(row_off[n]);
         for (uint32_t r = 0; r < n; ++r) std::copy(rows[r].begin(), rows[r].end(), query_ids.begin() + (ptrdiff_t)row_off[r]);
-        res.assign(row_off[n], lzani_result{0, 0, 0});
+        res.assign(results ? row_off[n] : 0, lzani_result{0, 0, 0});
     }
     uint64_t row_size(uint32_t r) const { return row_off[r + 1] - row_off[r]; }
     uint32_t id_at(uint32_t r, uint64_t j) const { return dense ? (uint32_t)j + (j >= r ? 1u : 0u) : query_ids[row_off[r] + j]; }
@@ -161,8 +164,8 @@ struct EmitParams {
     std::string out_name, ids_name;
     bool single_txt = false, in_percent = false;
     std::vector<Comp> comps;
-    uint64_t filter_mask = 0;
-    double filter_vals[16] = {0};
+    lzani_out_filter filter{0, 0, 0, 0, 0};                // --out-filter: the minima, 0 where none was named
+    bool filtered = false;                                 // an --out-filter was given
     uint32_t threads = 1;
     std::string params_dump;                               // CParams::str() text for single-txt
     int mrd = 40;
@@ -171,37 +174,21 @@ struct EmitParams {
 // ---- one TSV line = one DIRECTION of an unordered pair --------------------------------------------------
 // For the pair {a < b} the stage computed X = parse(query b, ref a) and Y = parse(query a, ref b).  A line
 // describes one of them ("own") with the other ("rev") supplying the reference-side coverage; the two lines
-// of a pair share tani.  All ratios are IEEE double divisions of exact integers, as in the reference
-// (lz_matcher.cpp:434-447), so equal integers give byte-equal text.
+// of a pair share tani.  The ratios are those of lzani_out_filter.h -- IEEE double divisions of exact integers, as
+// in the reference (lz_matcher.cpp:434-447) -- so equal integers give byte-equal text, and the filter decides by
+// the numbers that are printed.
 struct Direction {
     uint32_t qidx, ridx, qlen, rlen;
     const std::string *qname, *rname;
     int32_t nt_match, nt_mismatch, num_alns;
-    double tani, gani, ani, qcov, rcov;
+    lzani::out_ratios v;
 };
-
-// the numbers of a direction (the names stay null)
-inline Direction direction_values(const std::vector<uint32_t>& len, uint32_t q, uint32_t r, const lzani_result& own, const lzani_result& rev, double tani)
-{
-    Direction d;
-    d.qidx = q; d.ridx = r; d.qlen = len[q]; d.rlen = len[r];
-    d.qname = d.rname = nullptr;
-    d.nt_match = own.sym_in_matches; d.nt_mismatch = own.sym_in_literals; d.num_alns = own.no_components;
-    const int32_t aligned = own.sym_in_matches + own.sym_in_literals, aligned_rev = rev.sym_in_matches + rev.sym_in_literals;
-    d.tani = tani;
-    d.gani = (double)own.sym_in_matches / d.qlen;
-    d.ani = aligned != 0 ? (double)own.sym_in_matches / aligned : 0;
-    d.qcov = (double)aligned / d.qlen;
-    d.rcov = (double)aligned_rev / d.rlen;
-    return d;
-}
 
 inline Direction make_direction(const std::vector<Genome>& g, const std::vector<uint32_t>& len, uint32_t q, uint32_t r,
                                 const lzani_result& own, const lzani_result& rev, double tani)
 {
-    Direction d = direction_values(len, q, r, own, rev, tani);
-    d.qname = &g[q].name; d.rname = &g[r].name;
-    return d;
+    return Direction{q, r, len[q], len[r], &g[q].name, &g[r].name, own.sym_in_matches, own.sym_in_literals, own.no_components,
+                     lzani::out_line_ratios(tani, own, rev, len[q], len[r])};
 }
 
 struct LineOut {
@@ -223,11 +210,11 @@ inline const ColumnFn* column_table()
         /* ridx        */ [](LineOut& o, const Direction& d, double) { o.u(d.ridx); },
         /* qlen        */ [](LineOut& o, const Direction& d, double) { o.u(d.qlen); },
         /* rlen        */ [](LineOut& o, const Direction& d, double) { o.u(d.rlen); },
-        /* tani        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.tani, 6); },
-        /* gani        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.gani, 6); },
-        /* ani         */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.ani, 6); },
-        /* qcov        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.qcov, 6); },
-        /* rcov        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.rcov, 6); },
+        /* tani        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.v.tani, 6); },
+        /* gani        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.v.gani, 6); },
+        /* ani         */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.v.ani, 6); },
+        /* qcov        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.v.qcov, 6); },
+        /* rcov        */ [](LineOut& o, const Direction& d, double m) { o.r(m * d.v.rcov, 6); },
         /* len_ratio   */ [](LineOut& o, const Direction& d, double) {
             if (d.qlen && d.rlen) o.r(d.qlen < d.rlen ? (double)d.qlen / d.rlen : (double)d.rlen / d.qlen, 4);
             else o.s.push_back('0'); },
@@ -237,28 +224,8 @@ inline const ColumnFn* column_table()
     return t;
 }
 
-// --out-filter: minimum values per ratio column (a line is dropped when any ratio is below its minimum)
-struct Cut { double Direction::*field; double min; };
-inline std::vector<Cut> make_cuts(const EmitParams& ep)
+inline void write_direction(const Direction& d, const EmitParams& ep, std::string& out)
 {
-    std::vector<Cut> cuts;
-    if (!ep.filter_mask) return cuts;
-    static const std::pair<Comp, double Direction::*> ratio[] = {
-        {Comp::tani, &Direction::tani}, {Comp::gani, &Direction::gani}, {Comp::ani, &Direction::ani},
-        {Comp::qcov, &Direction::qcov}, {Comp::rcov, &Direction::rcov}};
-    for (auto& x : ratio) cuts.push_back(Cut{x.second, ep.filter_vals[(int)x.first]});
-    return cuts;
-}
-
-inline bool direction_passes(const Direction& d, const std::vector<Cut>& cuts)
-{
-    for (const Cut& c : cuts) if (d.*(c.field) < c.min) return false;
-    return true;
-}
-
-inline void write_direction(const Direction& d, const EmitParams& ep, const std::vector<Cut>& cuts, std::string& out)
-{
-    if (!direction_passes(d, cuts)) return;
     LineOut o{out, {0}};
     const ColumnFn* col = column_table();
     const double m = ep.in_percent ? 100 : 1;
@@ -271,60 +238,52 @@ inline void write_direction(const Direction& d, const EmitParams& ep, const std:
     out.push_back('\n');
 }
 
-// Text of the unordered pairs {a < b} led by genome a (one reference row of the output file):
-// two TSV lines per pair (b against a, then a against b), or one single-txt line.
-inline void format_row(const std::vector<Genome>& g, const std::vector<uint32_t>& len, const PairTable& T, const EmitParams& ep,
-                       const std::vector<Cut>& cuts, uint32_t a, std::string& out)
+// ---- one record = one unordered pair with the lines of it that are written ------------------------------
+// The engine's kept form hands back lzani_kept_pair records (--out-filter applied on the device: only the pairs of which a
+// line passes, lzani_group_run_rows_kept); a table of all pairs becomes the same records here, so that the text and the
+// cluster edges are made from records alone.
+
+// The table pairs {a < b} led by genome a with both directions computed, in ascending b: f(b, X, Y).  A pair without
+// its mate is skipped (the reference asserts symmetry here, lz_matcher.cpp:417-418).
+template <class F>
+inline void for_pairs_led_by(const PairTable& T, uint32_t a, F&& f)
 {
     const uint64_t cnt = T.row_size(a);
     for (uint64_t j = T.first_above(a); j < cnt; ++j) {
         const uint32_t b = T.id_at(a, j);
-        const lzani_result& X = T.at(a, j);                 // parse(query = b, ref = a)
         const lzani_result* Y = T.find(b, a);               // parse(query = a, ref = b)
-        if (!Y) continue;                                   // the reference asserts symmetry here (lz_matcher.cpp:417-418)
-        if (ep.single_txt) {
-            LineOut o{out, {0}};
-            o.u(a); out.push_back(' '); o.u(b);
-            for (const lzani_result* r : {Y, &X}) {
-                out.push_back(' '); o.i(r->sym_in_matches); out.push_back(' '); o.i(r->sym_in_literals); out.push_back(' '); o.i(r->no_components);
-            }
-            out.push_back('\n');
-            continue;
-        }
-        const double tani = (double)(X.sym_in_matches + Y->sym_in_matches) / (len[b] + len[a]);
-        write_direction(make_direction(g, len, b, a, X, *Y, tani), ep, cuts, out);
-        write_direction(make_direction(g, len, a, b, *Y, X, tani), ep, cuts, out);
+        if (Y) f(b, T.at(a, j), *Y);                        // T.at(a, j) = parse(query = b, ref = a)
     }
 }
 
-// The edges of the similarity graph as this emitter sees them (the host path of `lz-ani --cluster`): the pairs format_row
-// walks, of which direction_passes lets at least one line through; those lines give `lines`, lzani_cluster_plan.h the weight.
-inline void cluster_edges_of(const std::vector<uint32_t>& len, const PairTable& T, const std::vector<Cut>& cuts, int measure,
-                             std::vector<lzani_cluster_edge>& edges)
+// The record of a table pair: the lines the filter keeps, both where no filter was given (no filter is not five zero
+// minima: made-up integers may give negative ratios).
+inline lzani_kept_pair make_record(const std::vector<uint32_t>& len, const EmitParams& ep, uint32_t a, uint32_t b, const lzani_result& X, const lzani_result& Y)
 {
-    for (uint32_t a = 0; a < T.n; ++a) {
-        const uint64_t cnt = T.row_size(a);
-        for (uint64_t j = T.first_above(a); j < cnt; ++j) {
-            const uint32_t b = T.id_at(a, j);
-            const lzani_result& X = T.at(a, j);
-            const lzani_result* Y = T.find(b, a);
-            if (!Y) continue;
-            const double tani = (double)(X.sym_in_matches + Y->sym_in_matches) / (len[b] + len[a]);
-            Direction d0 = direction_values(len, b, a, X, *Y, tani), d1 = direction_values(len, a, b, *Y, X, tani);
-            const uint32_t lines = (direction_passes(d0, cuts) ? 1u : 0u) | (direction_passes(d1, cuts) ? 2u : 0u);
-            if (lines) edges.push_back(lzani_cluster_edge{a, b, lzani::cluster_weight(measure, X, *Y, lines, len[a], len[b])});
-        }
-    }
+    return lzani_kept_pair{a, b, X, Y, ep.filtered ? lzani::out_filter_lines(ep.filter, X, Y, len[a], len[b]) : 3u};
 }
 
-// --out-filter applied on the device (lzani_run_rows_kept): the engine hands back only the pairs of which a line passes,
-// each with both directions and the lines that pass.  The text of one record: those lines, with no cut left to apply.
+// The text of one record: the TSV lines that `lines` names (b against a, then a against b).
 inline void format_kept(const std::vector<Genome>& g, const std::vector<uint32_t>& len, const EmitParams& ep, const lzani_kept_pair& k, std::string& out)
 {
-    static const std::vector<Cut> no_cuts;
-    const double tani = (double)(k.x.sym_in_matches + k.y.sym_in_matches) / (len[k.b] + len[k.a]);
-    if (k.lines & 1u) write_direction(make_direction(g, len, k.b, k.a, k.x, k.y, tani), ep, no_cuts, out);
-    if (k.lines & 2u) write_direction(make_direction(g, len, k.a, k.b, k.y, k.x, tani), ep, no_cuts, out);
+    const double tani = lzani::out_pair_tani(k.x, k.y, len[k.a], len[k.b]);
+    if (k.lines & 1u) write_direction(make_direction(g, len, k.b, k.a, k.x, k.y, tani), ep, out);
+    if (k.lines & 2u) write_direction(make_direction(g, len, k.a, k.b, k.y, k.x, tani), ep, out);
+}
+
+// Text of the unordered pairs {a < b} led by genome a (one reference row of the output file): the lines of each pair's
+// record, or one single-txt line.
+inline void format_row(const std::vector<Genome>& g, const std::vector<uint32_t>& len, const PairTable& T, const EmitParams& ep, uint32_t a, std::string& out)
+{
+    for_pairs_led_by(T, a, [&](uint32_t b, const lzani_result& X, const lzani_result& Y) {
+        if (!ep.single_txt) { format_kept(g, len, ep, make_record(len, ep, a, b, X, Y), out); return; }
+        LineOut o{out, {0}};
+        o.u(a); out.push_back(' '); o.u(b);
+        for (const lzani_result* r : {&Y, &X}) {
+            out.push_back(' '); o.i(r->sym_in_matches); out.push_back(' '); o.i(r->sym_in_literals); out.push_back(' '); o.i(r->no_components);
+        }
+        out.push_back('\n');
+    });
 }
 
 // reported length: separators between the contigs of a multi-part item are not counted (lz_matcher.cpp:430-431)
@@ -375,7 +334,6 @@ public:
             }
             ofs << "\n";
         }
-        cuts = make_cuts(ep);
         return true;
     }
 
@@ -396,7 +354,7 @@ public:
                     size_t k = next.fetch_add(1);
                     if (k >= cnt) break;
                     buf[k].clear();
-                    format_row(g, len, T, ep, cuts, (uint32_t)(base + k), buf[k]);
+                    format_row(g, len, T, ep, (uint32_t)(base + k), buf[k]);
                 }
             };
             std::vector<std::thread> th;
@@ -437,7 +395,6 @@ private:
     EmitParams ep;
     std::ofstream ofs;
     std::vector<uint32_t> len;
-    std::vector<Cut> cuts;
     std::vector<std::string> text[2];
     int cur = 0;
     std::thread writer;

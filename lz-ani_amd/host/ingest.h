@@ -1,4 +1,5 @@
 // ingest.h -- FASTA ingest, length-descending reorder and kmer-db / device k-mer filter rows of the `lz-ani` host binary.
+// Uses nothing of the binary's other headers.
 //
 // Behaviour follows the reference's host data services (studied, not copied):
 //   CSeqReservoir::load_multifasta / load_fasta / append / reorder_items

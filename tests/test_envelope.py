@@ -175,7 +175,7 @@ def test_refusal_edge_through_the_c_abi_needs_no_device():
 
 
 def test_refusal_edge_through_the_host_binary(tmp_path):
-    """The host binary's envelope (host/main.cpp) at the same bounds: one step outside is "Unsupported value" and exit 1
+    """The host binary's envelope (host/cli.h) at the same bounds: one step outside is "Unsupported value" and exit 1
     before any input is read, one step inside goes on to the input (here: a missing file)."""
     subprocess.check_call(["make", "-s", "-C", os.path.dirname(EXE)])
     flags = {"msl": "--msl", "mal": "--mal", "mrd": "--mrd", "mqd": "--mqd", "aw": "--aw", "ar": "--ar", "am": "--am"}

@@ -1,5 +1,5 @@
-"""GPU: `lz-ani --out-filter` with the filter applied on the device (lzani_group_run_rows_kept; do_matching_kept and the
-kept form of do_matching_tiled in lz-ani_amd/host/main.cpp) writes the bytes the host filter writes (LZANI_OUT_FILTER=host):
+"""GPU: `lz-ani --out-filter` with the filter applied on the device (lzani_group_run_rows_kept; the kept forms of
+do_matching and do_matching_tiled in lz-ani_amd/host/match.h) writes the bytes the host filter writes (LZANI_OUT_FILTER=host):
 dense and with a kmer-db filter, untiled and in row blocks, all2all and query2ref, one shard and three."""
 import os
 import subprocess

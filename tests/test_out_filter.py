@@ -1,6 +1,7 @@
 """CPU: the rule of the output filter as the library states it (lzani_out_filter_lines, csrc/lzani_out_filter.h) against
-tests/out_filter_model.py -- seeded tuples and the edges -- and the host binary through its --results-in seam, where the
-filter stays on the host."""
+tests/out_filter_model.py -- seeded tuples and the edges -- the host emitter's two routes from a pair to its text (the table
+of all pairs and a kept record, tests/model/emit_shim.cpp) against the model, and the host binary through its --results-in
+seam, where the filter stays on the host."""
 import os
 import subprocess
 
@@ -132,3 +133,66 @@ def test_results_in_seam_keeps_the_host_filter(tmp_path):
                 want.append(ln)
         got = open(out).read().split("\n")
         assert got[:-1] == want and got[-1] == "" and 1 < len(want) < len(full) - 1
+
+
+COMPLETE = "qidx,ridx,query,reference,tani,gani,ani,qcov,rcov,num_alns,len_ratio,qlen,rlen,nt_match,nt_mismatch".split(",")
+
+
+@pytest.fixture(scope="module")
+def format_pair():
+    """host_format_pair of tests/model/emit_shim.cpp: (x, y, la, lb, filter or None, percent, kept lines) -> (the lines of the
+    table route's record, its text through format_row, the text of a lzani_kept_pair through format_kept)."""
+    import ctypes as C
+    d = os.path.join(U.ROOT, "tests", "model")
+    so = os.path.join(d, "libemit_pair_shim.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", os.path.join(d, "emit_shim.cpp"), "-o", so, "-lz"])
+    lib = C.CDLL(so)
+    lib.host_format_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_uint32, C.c_char_p, C.c_char_p, C.c_size_t]
+    lib.host_format_pair.restype = C.c_uint32
+    a, b = C.create_string_buffer(4096), C.create_string_buffer(4096)
+
+    def call(x, y, la, lb, flt, percent, kept_lines):
+        rx, ry = (C.c_int32 * 3)(*x), (C.c_int32 * 3)(*y)
+        minima = None if flt is None else (C.c_double * 5)(*(flt.get(k, 0.0) for k in M.FIELDS))
+        lines = lib.host_format_pair(rx, ry, la, lb, minima, int(percent), kept_lines, a, b, 4096)
+        assert lines != REFUSED
+        return lines, a.value.decode(), b.value.decode()
+    return call
+
+
+def test_printed_lines_and_filter_follow_the_model_on_seeded_tuples(format_pair):
+    """The emitter's two routes to a pair's text -- the table of all pairs (format_row) and a kept record (format_kept, its
+    `lines` from lzani_out_filter_lines as the device stage would set them) -- give the same bytes, and those are the lines
+    of util.emit_tsv that out_filter_model.lines keeps: with a filter and without, in percent (every other tuple) and not.
+    Tuples with a printed length of 0 are left out (a line then prints inf or NaN, which real_to_chars does not take): 9.75 %
+    by construction."""
+    all_tuples = tuples(20261, 4000)
+    seen, used = set(), 0
+    for i, (x, y, la, lb, flt) in enumerate(all_tuples):
+        if la == 0 or lb == 0:
+            continue
+        used += 1
+        percent = bool(i & 1)
+        res = np.zeros((2, 2, 3), dtype=np.int64)
+        res[0, 1], res[1, 0] = x, y
+        both = U.emit_tsv(["A", "B"], [la, lb], res, COMPLETE, in_percent=percent).split("\n")[1:3]
+        assert all(both) and both[0].startswith("1\t0\tB\tA\t") and both[1].startswith("0\t1\tA\tB\t")
+        lines, by_table, by_record = format_pair(x, y, la, lb, None, percent, 3)
+        assert lines == 3 and by_table == by_record == both[0] + "\n" + both[1] + "\n", (x, y, la, lb)
+        want = int(M.lines(flt, x, y, la, lb))
+        lines, by_table, by_record = format_pair(x, y, la, lb, flt, percent, L.out_filter_lines(flt, x, y, la, lb))
+        assert lines == want, (x, y, la, lb, flt)
+        assert by_table == by_record == "".join(both[k] + "\n" for k in (0, 1) if want >> k & 1), (x, y, la, lb, flt)
+        seen.add(want)
+    assert len(all_tuples) - used < 0.15 * len(all_tuples)
+    assert seen == {0, 1, 2, 3}
+
+
+def test_host_record_wraps_like_the_rule(format_pair):
+    """The 32-bit wrap case of test_edges through the emitter's own record (lines only: the model prints no wrapped text)."""
+    big = (2**31 - 5, 100, 1)
+    la, lb = 2**31, 2**31 + 7
+    for flt in ({"tani": 0.5}, {"qcov": 0.0}, {"gani": 0.25, "rcov": 0.25}):
+        want = int(M.lines(flt, big, big, la, lb))
+        assert format_pair(big, big, la, lb, flt, False, want)[0] == want == L.out_filter_lines(flt, big, big, la, lb), flt
+    assert format_pair(big, big, la, lb, None, False, 3)[0] == 3
