@@ -460,10 +460,10 @@ int lzani_debug_filter_results(lzani_ctx *ctx, uint32_t n, const uint32_t *repor
 /* LZANI_ERR_STATE without a kept result. */
 int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
 
-/* ---- Clustering the kept pairs on the device: single linkage and greedy -----------------------------------------
+/* ---- Clustering the kept pairs on the device: single linkage, greedy and set cover -------------------------------
  * The kept records of the output filter are the edge list of the similarity graph; this stage clusters it where it lies.
  * It is a post-stage over finished kept results, like the output filter over a result buffer: the pair kernels and their
- * dispatch know nothing of it.  The three algorithms are defined by the statements below and by nothing else (no claim
+ * dispatch know nothing of it.  The four algorithms are defined by the statements below and by nothing else (no claim
  * of equality with another program's output is made); lzani_cluster_host is their sequential form.
  *   graph      the nodes are the n genomes, by the ids of lzani_set_genomes (the lz-ani binary reorders genomes: id 0 is
  *              the first line of its ids file).  The edge {a, b}, a < b, exists iff the pair is a kept pair of a kept call
@@ -489,16 +489,42 @@ int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
  *     LZANI_CLUSTER_GREEDY_BEST   nearest centroid, in the manner of UCLUST: the same representatives; for another v,
  *                                 rep_of[v] is the neighbouring representative r < v with the largest w, ties to the
  *                                 smallest r.  Representatives above v do not count: they did not exist when v was placed
+ *     LZANI_CLUSTER_SET_COVER     greedy set cover, the default of MMseqs2-style clustering, on the graph with distinct
+ *                                 edges (the same pair added twice, in either orientation or over several add calls, is
+ *                                 one edge; weights and the measure play no part).  All nodes start unassigned.  While a
+ *                                 node is unassigned: c(v) = the number of unassigned neighbours of the unassigned node
+ *                                 v; the unassigned v with the largest c(v), ties to the smallest id, becomes a
+ *                                 representative (rep_of[v] = v), every unassigned neighbour u of v gets rep_of[u] = v,
+ *                                 and all of these are assigned.  An isolated or left-over node with c = 0 becomes its own
+ *                                 representative.  Unlike the greedy forms, a representative may have a larger id than
+ *                                 its members
  *   numbering  cluster_of[v] = the number of representatives with an id below rep_of[v]: clusters are numbered in
  *              ascending order of their representative; clusters = the number of representatives
  * The device stage: the union-find of SINGLE hooks the larger root under the smaller, so that parent[v] <= v at every
  * moment; the greedy representatives are the fixed point of rounds of an edge pass and a node pass whose stores are
  * idempotent and final, so the result is that of the statements whatever the schedule.  `rounds` is 1 for SINGLE and the
  * number of greedy rounds up to the first that left no node undecided (a path with ascending ids needs n / 2 to n).
- * Not here: complete linkage, greedy set cover, Leiden. */
+ * SET_COVER on the device: the edge records are made distinct once per run in a workspace of the run (keys lo << 32 | hi,
+ * sorted, unique; the edge buffer itself is only read).  key(v) = c(v) << 32 | (0xFFFFFFFF - v) for an unassigned v, 0 for
+ * an assigned one: a strict total order, "largest c, then smallest id" on top, never 0 for an unassigned node as
+ * v < n <= 2^32 - 1.  A round takes the unassigned nodes as they are at its start and selects every one whose key is the
+ * largest among the unassigned nodes within two hops (itself, its unassigned neighbours, theirs); every selected node
+ * covers its unassigned neighbours as of the round's start.  The rounds give exactly the sequential result: call a
+ * selection valid when the node has the largest key within its two hops.  The sequential step is valid (the global maximum
+ * is a local one).  Keys only fall, and the key of v changes only when a neighbour of v is assigned, which takes a
+ * selection within two hops of v: so one valid selection leaves the key and the cover set of every other valid node as
+ * they were, and that node valid.  The process ends, so every maximal schedule of valid selections ends in the same
+ * representatives and members.  Two nodes selected in one round are more than two hops apart: their cover sets are
+ * disjoint and neither covers the other.  (With a one-hop maximum the result is wrong: on the edges (0,1) (1,2) (2,3)
+ * (3,4) (3,5) the statement gives rep_of = 0 0 3 3 3 3, and one hop selects 1 in the first round.)  `rounds` is the number
+ * of the first round that left no node unassigned; the global maximum is selected in every round, so n rounds always do
+ * (a path with ascending ids takes n / 3; disjoint near-cliques one or two).  More than 2^32 - 17 edge records:
+ * LZANI_ERR_ARG; a workspace that does not fit: LZANI_ERR_NOMEM, and the cluster state is as before the run.
+ * Not here: complete linkage, Leiden. */
 #define LZANI_CLUSTER_SINGLE        0
 #define LZANI_CLUSTER_GREEDY_FIRST  1
 #define LZANI_CLUSTER_GREEDY_BEST   2
+#define LZANI_CLUSTER_SET_COVER     4   /* 4, not 3: 3 stays an unknown algorithm (tests/test_cluster.py holds 3 and -1 to LZANI_ERR_ARG) */
 #define LZANI_CLUSTER_TANI          0
 #define LZANI_CLUSTER_GANI          1
 #define LZANI_CLUSTER_ANI           2
@@ -512,6 +538,12 @@ typedef struct lzani_cluster_info {
     uint64_t edge_bytes;              /* device bytes of the edge buffer                                         */
     double   add_ms, run_ms;          /* HIP events on the context's stream: the add_kept calls summed; the last run */
 } lzani_cluster_info;
+typedef struct lzani_cluster_cover_info {      /* of a LZANI_CLUSTER_SET_COVER run */
+    uint64_t distinct_edges;          /* edges of the graph: the edge records without their repetitions             */
+    uint64_t duplicate_edges;         /* edge records beyond the first of their pair (edges - distinct_edges)       */
+    uint64_t workspace_bytes;         /* device bytes of the run's workspace: keys, sort scratch, the per-node words */
+    double   dedup_ms, rounds_ms;     /* HIP events on the context's stream: keys, sort and unique; the rounds      */
+} lzani_cluster_cover_info;
 /* The weight as a pure host function (no GPU).  NULL pointers or an unknown measure: NaN. */
 double lzani_cluster_weight(int measure, const lzani_result *x, const lzani_result *y, uint32_t lines, uint32_t len_a, uint32_t len_b);
 /* The sequential statement as a pure host function (no GPU).  rep_of[n]; cluster_of[n] and n_clusters may be NULL.  An edge
@@ -532,6 +564,8 @@ int lzani_cluster_run(lzani_ctx *ctx, int algo, uint64_t *n_clusters);
 int lzani_cluster_fetch(lzani_ctx *ctx, uint32_t *rep_of, uint32_t *cluster_of);
 /* LZANI_ERR_STATE before a begin. */
 int lzani_get_cluster_info(const lzani_ctx *ctx, lzani_cluster_info *info);
+/* LZANI_ERR_STATE unless the last run was one of LZANI_CLUSTER_SET_COVER. */
+int lzani_get_cluster_cover_info(const lzani_ctx *ctx, lzani_cluster_cover_info *info);
 
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
@@ -594,6 +628,7 @@ int lzani_group_cluster_add_kept(lzani_group *grp, uint64_t *edges_total);
 int lzani_group_cluster_run(lzani_group *grp, int algo, uint64_t *n_clusters);
 int lzani_group_cluster_fetch(lzani_group *grp, uint32_t *rep_of, uint32_t *cluster_of);
 int lzani_group_get_cluster_info(const lzani_group *grp, lzani_cluster_info *info);
+int lzani_group_get_cluster_cover_info(const lzani_group *grp, lzani_cluster_cover_info *info);
 
 /* The shard bookkeeping of lzani_group_run_rows as a pure host function (no GPU): rows keep their order inside
  * their shard, the shards follow each other in the gathered buffer (shard d from result shard_base[d] on,

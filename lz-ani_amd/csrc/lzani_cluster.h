@@ -1,16 +1,21 @@
 // lzani_cluster.h -- host side of the cluster stage (include/lzani.h states the definitions): the edge buffer and its growth,
-// the run -- union-find for single linkage, rounds of the greedy representatives, assignment, numbering -- and the entry
-// points (lzani_cluster_begin, lzani_cluster_add_kept, lzani_debug_cluster_add_edges, lzani_cluster_run, lzani_cluster_fetch,
-// lzani_get_cluster_info and the pure lzani_cluster_weight and lzani_cluster_host).  Included by lzani_hip.hip only, behind
-// lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept), fail and HIPCHK, of lzani_prefilter.h
-// pf_blocks, of lzani_devmem.h DevMem and StreamSpan.  The kernels are lzani_kernels_cluster.h; the group's form is in
+// the run -- union-find for single linkage, rounds of the greedy representatives, assignment, or the distinct edges and
+// the rounds of set cover; numbering -- and the entry points (lzani_cluster_begin, lzani_cluster_add_kept,
+// lzani_debug_cluster_add_edges, lzani_cluster_run, lzani_cluster_fetch, lzani_get_cluster_info,
+// lzani_get_cluster_cover_info and the pure lzani_cluster_weight and lzani_cluster_host).  Included by lzani_hip.hip only,
+// behind lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept), fail, HIPCHK and sort_keys, of
+// lzani_prefilter.h pf_blocks and pf_chunks, of lzani_devmem.h DevMem and StreamSpan.  The kernels are lzani_kernels_cluster.h; the group's form is in
 // lzani_multi.h.
 //
 // What the stage reads and writes.  add_kept, per record: 36 B and two lengths read, 16 B written.  SINGLE: per edge 16 B
 // and the two paths to the roots, one CAS per hook that is won; per node one path.  A greedy round: per edge 16 B and one or
 // two state words read, at most one word stored; per node two words.  The assignment: per edge 16 B and two state words,
 // one atomic per edge of a node that is no representative (BEST: two passes).  The numbering: per node three words, one
-// atomic, and the scan of n flags.
+// atomic, and the scan of n flags.  Set cover, once per run: per edge record 16 B read and 8 B written, two sorts of as
+// many bits as an id has, and the compaction (8 B read twice, 8 B written per distinct edge).  A set-cover round, per
+// distinct edge: 8 B three times; two rep_of words and two atomic adds (count); two keys and one atomic max (first hop);
+// two m1 words and at most one atomic max (second hop: none inside a clique, where every m1 is the same); per node six
+// words read and five written.  Worst case of the rounds: the path with ascending ids, n / 3.
 #pragma once
 
 namespace {
@@ -42,27 +47,127 @@ int cluster_reserve(lzani_ctx* c, u64 need)
     return LZANI_OK;
 }
 
-// The run on the context's edges: fills rep_of, cluster_of and the run's part of `info`.
-int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& cluster_of, lzani_cluster_info& info)
+// The workspace of a set-cover run, allocated whole before the run touches the cluster state: the keys of the edge records
+// and of the distinct edges (two buffers of E, the sort's in and out in turn), the sort's scratch, the compaction's block
+// counts and offsets, and per node the counter and the three 64-bit words of a round.
+constexpr u64 CL_COVER_MAX_EDGES = 0xFFFFFFEFull;       // 2^32 - 17: lzani_sort_keys' limit
+struct CoverWork {
+    DevMem<unsigned long long> ka, kb, key, m1, m2;
+    DevMem<unsigned char> scratch;
+    DevMem<u32> ucnt, cnt;
+    DevMem<u64> uoff;
+    int bits = 1;                                       // of an id below n
+    u64 bytes() const { return ka.bytes() + kb.bytes() + key.bytes() + m1.bytes() + m2.bytes() + scratch.bytes() + ucnt.bytes() + cnt.bytes() + uoff.bytes(); }
+};
+
+int cluster_cover_alloc(lzani_ctx* c, CoverWork& w)
+{
+    const u32 n = c->cl.info.n;
+    const u64 E = c->cl.info.edges;
+    if (E > CL_COVER_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: set cover sorts at most 2^32 - 17 edge records");
+    while (w.bits < 32 && ((u64)1 << w.bits) < n) ++w.bits;
+    size_t need = 0;                                    // (the same for the two sorts: as many bits, as many keys)
+    if (int rc = sort_scratch_bytes(c, (size_t)E, 1, 0, w.bits, "lzani_cluster_run: sort", need)) return rc;
+    HIPCHK(c, w.ka.alloc((size_t)E)); HIPCHK(c, w.kb.alloc((size_t)E)); HIPCHK(c, w.scratch.alloc(need));
+    HIPCHK(c, w.ucnt.alloc((size_t)pf_chunks(E))); HIPCHK(c, w.uoff.alloc((size_t)pf_chunks(E) + 1));
+    HIPCHK(c, w.cnt.alloc(n)); HIPCHK(c, w.key.alloc(n)); HIPCHK(c, w.m1.alloc(n)); HIPCHK(c, w.m2.alloc(n));
+    return LZANI_OK;
+}
+
+// The distinct edges of the context's edge records, ascending, in w.kb: D of them.  The edge buffer is only read.
+int cluster_cover_dedup(lzani_ctx* c, CoverWork& w, u64& D)
+{
+    const u64 E = c->cl.info.edges;
+    D = 0;
+    if (!E) return LZANI_OK;
+    hipLaunchKernelGGL(k_cl_cover_keys, dim3(pf_blocks(E)), dim3(PF_THREADS), 0, c->stream, (const lzani_cluster_edge*)c->cl.edges.get(), E, w.ka.get());
+    HIPCHK(c, hipGetLastError());
+    // by hi, then (the sort is stable) by lo: only the bits an id below n has
+    if (int rc = sort_keys(c, w.scratch, w.ka.get(), w.kb.get(), (size_t)E, 1, 0, w.bits, "lzani_cluster_run: sort", false)) return rc;
+    if (int rc = sort_keys(c, w.scratch, w.kb.get(), w.ka.get(), (size_t)E, 1, 32, 32 + w.bits, "lzani_cluster_run: sort", false)) return rc;
+    const u32 blocks = (u32)pf_chunks(E);
+    hipLaunchKernelGGL(k_pf_uniq<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, (const unsigned long long*)w.ka.get(), E, w.ucnt.get(),
+                       (const u64*)w.uoff.get(), w.kb.get(), (u32*)nullptr, 0u);
+    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.ucnt.get(), (u64)blocks, w.uoff.get());
+    hipLaunchKernelGGL(k_pf_uniq<true>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, (const unsigned long long*)w.ka.get(), E, w.ucnt.get(),
+                       (const u64*)w.uoff.get(), w.kb.get(), (u32*)nullptr, 0u);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&D, w.uoff.get() + blocks, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (D > E) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more distinct edges than edge records");
+    return LZANI_OK;
+}
+
+// The rounds of set cover over the D distinct edges of w.kb (lzani_kernels_cluster.h): rep_of, and the number of the first
+// round that left no node unassigned.
+int cluster_cover_rounds(lzani_ctx* c, CoverWork& w, u64 D, u32* rep_of, u32* undecided, u64& rounds)
+{
+    const u32 n = c->cl.info.n;
+    const dim3 nodes(pf_blocks(n)), edge_blocks(pf_blocks(D)), threads(PF_THREADS);
+    const unsigned long long* pairs = w.kb.get();
+    rounds = 0;
+    for (bool done = false; !done;) {
+        // the unassigned node with the largest key is selected in every round: n rounds always do, and a defect ends here instead of spinning
+        if (rounds >= (u64)n + 1) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: nodes still unassigned after n + 1 rounds");
+        const u32 batch = (u32)std::min<u64>(CL_BATCH, (u64)n + 1 - rounds);
+        HIPCHK(c, hipMemsetAsync(undecided, 0, CL_BATCH * sizeof(u32), c->stream));
+        for (u32 r = 0; r < batch; ++r) {
+            if (D) hipLaunchKernelGGL(k_cl_cover_count, edge_blocks, threads, 0, c->stream, pairs, D, n, (const u32*)rep_of, w.cnt.get());
+            hipLaunchKernelGGL(k_cl_cover_key, nodes, threads, 0, c->stream, n, (const u32*)rep_of, w.cnt.get(), w.key.get(), w.m1.get(), w.m2.get());
+            if (D) hipLaunchKernelGGL(k_cl_cover_max, edge_blocks, threads, 0, c->stream, pairs, D, n, (const unsigned long long*)w.key.get(), w.m1.get());
+            if (D) hipLaunchKernelGGL(k_cl_cover_max, edge_blocks, threads, 0, c->stream, pairs, D, n, (const unsigned long long*)w.m1.get(), w.m2.get());
+            hipLaunchKernelGGL(k_cl_cover_decide, nodes, threads, 0, c->stream, n, (const unsigned long long*)w.m1.get(), (const unsigned long long*)w.m2.get(),
+                               rep_of, undecided + r);
+        }
+        HIPCHK(c, hipGetLastError());
+        u32 left[CL_BATCH];
+        HIPCHK(c, hipMemcpyAsync(left, undecided, sizeof left, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        u32 r = 0;
+        while (r < batch && left[r]) ++r;
+        done = r < batch;
+        rounds += done ? r + 1 : batch;                 // (the rounds behind the first that left no node change nothing)
+    }
+    return LZANI_OK;
+}
+
+// The run on the context's edges: fills rep_of, cluster_of and the run's part of `info` (set cover: `cover`, from `work`).
+int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& cluster_of, lzani_cluster_info& info, CoverWork& work,
+                      lzani_cluster_cover_info& cover)
 {
     const Cluster& k = c->cl;
     const u32 n = k.info.n;
     const u64 E = k.info.edges;
     const lzani_cluster_edge* edges = k.edges.get();
+    const bool set_cover = algo == LZANI_CLUSTER_SET_COVER;
     DevMem<u32> parent, state, blocked, flag, size, counters, undecided;
     DevMem<unsigned long long> best;
     DevMem<u64> below;
-    HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, flag.alloc(n)); HIPCHK(c, size.alloc(n));
-    HIPCHK(c, best.alloc(n)); HIPCHK(c, below.alloc((size_t)n + 1));
+    if (!set_cover) { HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, best.alloc(n)); }
+    HIPCHK(c, flag.alloc(n)); HIPCHK(c, size.alloc(n)); HIPCHK(c, below.alloc((size_t)n + 1));
     HIPCHK(c, counters.alloc(CL_COUNTERS)); HIPCHK(c, undecided.alloc(CL_BATCH));
     HIPCHK(c, rep_of.alloc(n)); HIPCHK(c, cluster_of.alloc(n));
     const dim3 nodes(pf_blocks(n)), edge_blocks(pf_blocks(E)), threads(PF_THREADS);
     StreamSpan span;
     HIPCHK(c, span.begin(c->stream));
     HIPCHK(c, hipMemsetAsync(counters, 0, CL_COUNTERS * sizeof(u32), c->stream));
-    hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
+    if (!set_cover) hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
     u64 rounds = 1;
-    if (algo == LZANI_CLUSTER_SINGLE) {
+    if (set_cover) {
+        StreamSpan dedup, cover_rounds;
+        u64 D = 0;
+        HIPCHK(c, dedup.begin(c->stream));
+        if (int rc = cluster_cover_dedup(c, work, D)) return rc;
+        HIPCHK(c, dedup.end(c->stream));
+        HIPCHK(c, cover_rounds.begin(c->stream));
+        hipLaunchKernelGGL(k_cl_cover_init, nodes, threads, 0, c->stream, n, rep_of.get(), work.cnt.get(), size.get());
+        if (int rc = cluster_cover_rounds(c, work, D, rep_of.get(), undecided.get(), rounds)) return rc;
+        HIPCHK(c, cover_rounds.end(c->stream));
+        float dedup_ms = 0, rounds_ms = 0;
+        HIPCHK(c, dedup.elapsed(dedup_ms));
+        HIPCHK(c, cover_rounds.elapsed(rounds_ms));
+        cover = lzani_cluster_cover_info{D, E - D, work.bytes(), dedup_ms, rounds_ms};
+    } else if (algo == LZANI_CLUSTER_SINGLE) {
         if (E) hipLaunchKernelGGL(k_cl_hook, edge_blocks, threads, 0, c->stream, edges, E, parent.get());
         hipLaunchKernelGGL(k_cl_roots, nodes, threads, 0, c->stream, n, (const u32*)parent.get(), rep_of.get());
     } else {
@@ -206,13 +311,18 @@ int lzani_cluster_run(lzani_ctx* c, int algo, uint64_t* n_clusters)
     if (!cluster_algo_known(algo)) return fail(c, LZANI_ERR_ARG, fn + ": unknown algorithm");
     HIPCHK(c, hipSetDevice(c->dev));
     Cluster& k = c->cl;
+    CoverWork work;                                            // set cover: refused, or short of memory, with the state as it was
+    if (algo == LZANI_CLUSTER_SET_COVER)
+        if (int rc = cluster_cover_alloc(c, work)) return rc;
     k.ran = false;
     k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes first
     DevMem<u32> rep_of, cluster_of;
     lzani_cluster_info info = k.info;
-    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info);
+    lzani_cluster_cover_info cover{};
+    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info, work, cover);
     if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     k.info = info;
+    k.cover = cover;
     k.rep_of = std::move(rep_of); k.cluster_of = std::move(cluster_of);
     k.ran = true;
     if (n_clusters) *n_clusters = info.clusters;
@@ -237,6 +347,14 @@ int lzani_get_cluster_info(const lzani_ctx* c, lzani_cluster_info* info)
     if (!c || !info) return LZANI_ERR_ARG;
     if (!c->cl.begun) return LZANI_ERR_STATE;
     *info = c->cl.info;
+    return LZANI_OK;
+}
+
+int lzani_get_cluster_cover_info(const lzani_ctx* c, lzani_cluster_cover_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_SET_COVER) return LZANI_ERR_STATE;
+    *info = c->cl.cover;
     return LZANI_OK;
 }
 

@@ -1,6 +1,6 @@
 // lzani_cluster_plan.h -- the rule and the sequential statement of the cluster stage (include/lzani.h, "clustering the kept
-// pairs"): the weight of an edge, and the three algorithms on a host edge array -- union-find with the smaller root as
-// parent, and the greedy sweep over adjacency lists.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
+// pairs"): the weight of an edge, and the four algorithms on a host edge array -- union-find with the smaller root as
+// parent, the greedy sweep over adjacency lists, and greedy set cover by a lazy max-heap.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
 // weight; the pure host functions lzani_cluster_weight and lzani_cluster_host (lzani_cluster.h) and the host binary, which
 // includes this header directly, call both.  Free of HIP but for the guard macro; compiled without fast-math and with
 // -ffp-contract=off: every ratio is one IEEE double division of exact integers, so host and device give the same bits.
@@ -8,6 +8,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+#include <queue>
 #include <vector>
 
 #include "../../include/lzani.h"
@@ -21,7 +23,10 @@
 namespace lzani {
 
 LZANI_CL_HD inline bool cluster_measure_known(int measure) { return measure >= LZANI_CLUSTER_TANI && measure <= LZANI_CLUSTER_ANI; }
-LZANI_CL_HD inline bool cluster_algo_known(int algo) { return algo >= LZANI_CLUSTER_SINGLE && algo <= LZANI_CLUSTER_GREEDY_BEST; }
+LZANI_CL_HD inline bool cluster_algo_known(int algo)
+{
+    return (algo >= LZANI_CLUSTER_SINGLE && algo <= LZANI_CLUSTER_GREEDY_BEST) || algo == LZANI_CLUSTER_SET_COVER;
+}
 
 // a value that is not above 0 -- NaN, and the negative values and -0 that only made-up integers give -- reads as +0
 LZANI_CL_HD inline double cluster_value(double v) { return v > 0 ? v : 0.0; }
@@ -69,6 +74,52 @@ inline uint32_t cluster_number(uint32_t n, const uint32_t* rep_of, uint32_t* clu
     return below[n];
 }
 
+// The key of set cover: the unassigned node with the largest key is the next representative -- the largest count c of
+// unassigned neighbours, ties to the smallest id.  v < n <= 2^32 - 1, so a key is never 0 (what an assigned node has on the
+// device).
+LZANI_CL_HD inline uint64_t cluster_cover_key(uint32_t c, uint32_t v) { return ((uint64_t)c << 32) | (0xFFFFFFFFu - v); }
+LZANI_CL_HD inline uint32_t cluster_cover_node(uint64_t key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+// LZANI_CLUSTER_SET_COVER on the edges as they come: the distinct pairs (normalised, sorted, unique), adjacency lists of
+// both directions, and a max-heap of keys that is never repaired -- a popped key that is no longer its node's key is
+// dropped, a count that falls pushes the new key.  Every edge lowers a count at most twice: O(E log E).
+inline void cluster_cover_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, uint32_t* rep_of)
+{
+    std::vector<uint64_t> pairs(count);
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t lo = edges[i].a < edges[i].b ? edges[i].a : edges[i].b, hi = edges[i].a < edges[i].b ? edges[i].b : edges[i].a;
+        pairs[i] = ((uint64_t)lo << 32) | hi;
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    std::vector<uint64_t> off((size_t)n + 1, 0);
+    for (uint64_t p : pairs) { off[(p >> 32) + 1]++; off[(uint32_t)p + 1]++; }
+    for (uint32_t v = 0; v < n; ++v) off[v + 1] += off[v];
+    std::vector<uint32_t> nb(2 * pairs.size());
+    std::vector<uint64_t> at(off.begin(), off.end() - 1);
+    for (uint64_t p : pairs) { nb[at[p >> 32]++] = (uint32_t)p; nb[at[(uint32_t)p]++] = (uint32_t)(p >> 32); }
+    std::vector<uint32_t> c(n);
+    std::vector<char> assigned(n, 0);
+    std::priority_queue<uint64_t> heap;
+    for (uint32_t v = 0; v < n; ++v) { c[v] = (uint32_t)(off[v + 1] - off[v]); heap.push(cluster_cover_key(c[v], v)); }
+    std::vector<uint32_t> taken;
+    while (!heap.empty()) {
+        const uint64_t key = heap.top();
+        heap.pop();
+        const uint32_t v = cluster_cover_node(key);
+        if (assigned[v] || key != cluster_cover_key(c[v], v)) continue;          // (a key of before a count fell)
+        taken.assign(1, v);
+        for (uint64_t e = off[v]; e < off[v + 1]; ++e)
+            if (!assigned[nb[e]]) taken.push_back(nb[e]);
+        for (uint32_t u : taken) { rep_of[u] = v; assigned[u] = 1; }
+        for (uint32_t u : taken)
+            for (uint64_t e = off[u]; e < off[u + 1]; ++e) {
+                const uint32_t y = nb[e];
+                if (!assigned[y]) heap.push(cluster_cover_key(--c[y], y));
+            }
+    }
+}
+
 // The sequential statement.  rep_of[n] is written; cluster_of and n_clusters may be null.  LZANI_ERR_ARG for an edge that
 // cluster_edge_ok refuses or an unknown algo; (b, a) with b > a is the edge (a, b).
 inline int cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, int algo, uint32_t* rep_of, uint32_t* cluster_of, uint32_t* n_clusters)
@@ -88,6 +139,8 @@ inline int cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t co
             if (ra != rb) parent[ra > rb ? ra : rb] = ra > rb ? rb : ra;         // the smaller root is the parent
         }
         for (uint32_t v = 0; v < n; ++v) rep_of[v] = root(v);                     // ... so a root is its tree's smallest id
+    } else if (algo == LZANI_CLUSTER_SET_COVER) {
+        cluster_cover_host(n, edges, count, rep_of);
     } else {
         // adjacency lists of the neighbours below each node
         std::vector<uint64_t> off((size_t)n + 1, 0);

@@ -11,6 +11,7 @@
 //   k_cl_assign_init, k_cl_assign_best, k_cl_assign_min   rep_of of the nodes that are no representatives
 //   k_cl_flags, k_cl_number   the numbering: flags rep_of[v] == v and cluster sizes; behind the scan cluster_of and the
 //                    counts of singletons and of the largest cluster
+//   k_cl_cover_*     greedy set cover: the keys of the distinct edges, and the passes of a round (at the end of this file)
 // Words that other blocks write inside a launch (parent, state, blocked) are read and written with relaxed agent-scope
 // atomics only: the L2 of an XCD is not coherent with the others for plain accesses inside a kernel.  No thread ever waits
 // for a value that another block has yet to write; edge indexes are 64-bit throughout.
@@ -182,6 +183,97 @@ __global__ void __launch_bounds__(PF_THREADS) k_cl_number(u32 n, const u32* __re
         if (s_one) atomicAdd(&counters[CL_SINGLETONS], s_one);
         if (s_max) atomicMax(&counters[CL_LARGEST], s_max);
     }
+}
+
+// ---- LZANI_CLUSTER_SET_COVER ----------------------------------------------------------------------------------------
+// The passes run over the distinct edges: keys lo << 32 | hi (k_cl_cover_keys), sorted and made unique on the host side's
+// order (lzani_sort_keys, k_pf_uniq).  A node is unassigned while rep_of[v] == CL_NONE; rep_of is written by the decide
+// pass only, so between two decide passes it is the round's snapshot.  A round, with key(v) = cluster_cover_key(c(v), v)
+// for an unassigned node and 0 for an assigned one:
+//   k_cl_cover_count   per edge of two unassigned ends: cnt += 1 at both (atomicAdd)
+//   k_cl_cover_key     per node: key = m1 = its key from cnt, m2 = 0, cnt = 0 for the next round
+//   k_cl_cover_max     key -> m1, per edge of two unassigned ends: the larger key into m1 of the other end (one atomicMax;
+//                      the end with the larger key has it in its own m1 already).  Behind it m1[v] = the largest key of v
+//                      and its unassigned neighbours
+//   k_cl_cover_max     m1 -> m2, per such edge: the larger m1 into m2 of the other end, nothing where they are equal.
+//                      Behind it max(m1[w], m2[w]) = the largest key within two hops of w
+//   k_cl_cover_decide  per unassigned node v, with w = the node of the key m1[v] (v itself or a neighbour): w is selected
+//                      iff its two-hop maximum is its own key, and v is assigned in this round iff w is selected, with
+//                      rep_of[v] = w.  For: a selected v has w == v; a v with a selected neighbour u has all of its
+//                      neighbourhood within two hops of u, so m1[v] is u's key; and a selected w is v or a neighbour of
+//                      v.  So the selected node and the nodes it covers take their representative in one node pass, one
+//                      plain store each, and the nodes left unassigned are summed into the round's counter
+// Every pass reads only words that no thread writes in the same launch, or goes through the atomics named; everything else
+// crosses a kernel boundary.  A round behind the one that left no node unassigned finds every key 0 and changes nothing.
+__global__ void __launch_bounds__(PF_THREADS) k_cl_cover_keys(const lzani_cluster_edge* __restrict__ edges, u64 count, unsigned long long* __restrict__ keys)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const ClEdge e = cl_edge(edges, i);
+    keys[i] = ((u64)e.lo << 32) | e.hi;
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_cover_init(u32 n, u32* __restrict__ rep_of, u32* __restrict__ cnt, u32* __restrict__ size)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    rep_of[v] = CL_NONE; cnt[v] = 0; size[v] = 0;
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_cover_count(const unsigned long long* __restrict__ pairs, u64 count, u32 n, const u32* __restrict__ rep_of,
+                                                               u32* __restrict__ cnt)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const u64 p = pairs[i];
+    const u32 lo = (u32)(p >> 32), hi = (u32)p;
+    if (lo >= n || hi >= n) return;                              // (ids are checked where edges come in; a defect must not write astray)
+    if (rep_of[lo] != CL_NONE || rep_of[hi] != CL_NONE) return;
+    atomicAdd(&cnt[lo], 1u);
+    atomicAdd(&cnt[hi], 1u);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_cover_key(u32 n, const u32* __restrict__ rep_of, u32* __restrict__ cnt, unsigned long long* __restrict__ key,
+                                                             unsigned long long* __restrict__ m1, unsigned long long* __restrict__ m2)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    const u64 k = rep_of[v] == CL_NONE ? cluster_cover_key(cnt[v], v) : 0;
+    key[v] = k; m1[v] = k; m2[v] = 0; cnt[v] = 0;
+}
+
+// from[]: key for the first hop (into = m1), m1 for the second (into = m2); 0 marks an assigned node in both
+__global__ void __launch_bounds__(PF_THREADS) k_cl_cover_max(const unsigned long long* __restrict__ pairs, u64 count, u32 n,
+                                                             const unsigned long long* __restrict__ from, unsigned long long* __restrict__ into)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const u64 p = pairs[i];
+    const u32 lo = (u32)(p >> 32), hi = (u32)p;
+    if (lo >= n || hi >= n) return;
+    const u64 a = from[lo], b = from[hi];
+    if (!a || !b || a == b) return;
+    if (a > b) atomicMax(&into[hi], (unsigned long long)a);
+    else atomicMax(&into[lo], (unsigned long long)b);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_cover_decide(u32 n, const unsigned long long* __restrict__ m1, const unsigned long long* __restrict__ m2,
+                                                                u32* __restrict__ rep_of, u32* __restrict__ unassigned)
+{
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 mine = 0;
+    const u64 m = v < n ? m1[v] : 0;
+    if (m) {                                                     // v is unassigned
+        const u32 w = cluster_cover_node(m);
+        const u64 a = w < n ? m1[w] : 0, b = w < n ? m2[w] : 0;
+        if (w < n && (a > b ? a : b) == m) rep_of[v] = w;
+        else mine = 1;
+    }
+    block_sum(mine, &s_cnt);
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(unassigned, s_cnt);
 }
 
 }  // namespace lzani

@@ -251,6 +251,10 @@ static bool cluster_finish(const Group& G, const vector<Genome>& g)
     if (P.verbosity >= 2 && G.E.group_get_cluster_info(G, &ci) == LZANI_OK)
         cerr << "clusters on the device: " << ci.clusters << " of " << ci.n << " sequences (" << ci.singletons << " singletons, the largest of " << ci.largest
              << ") from " << ci.edges << " pairs, " << ci.rounds << " round(s), add " << ci.add_ms << " ms, run " << ci.run_ms << " ms\n";
+    lzani_cluster_cover_info cv;
+    if (P.verbosity >= 2 && G.E.group_get_cluster_cover_info && G.E.group_get_cluster_cover_info(G, &cv) == LZANI_OK)
+        cerr << "set cover: " << cv.distinct_edges << " distinct pairs (" << cv.duplicate_edges << " given again), unique " << cv.dedup_ms << " ms, rounds "
+             << cv.rounds_ms << " ms, workspace " << cv.workspace_bytes << " bytes\n";
     return write_clusters(g, rep_of, cluster_of);
 }
 

@@ -2,7 +2,7 @@
 """GPU box: the cluster stage on the family set of tools/related_bench.py (n genomes in families of `fam`, the rows hold the
 same-family pairs) behind an output filter that keeps the related pairs.  One lzani_run_rows_kept, then per algorithm
 begin -> add_kept -> run; lzani_cluster_host on the same edges for the wall time of the sequential statement, and its
-answer compared.  Prints one JSON object (profiles/cluster_stage.json).  Usage: tools/cluster_bench.py [n] [fam] [dmax]"""
+answer compared.  Prints one JSON object (profiles/cluster_stage.json; with set cover, profiles/cluster_cover.json).  Usage: tools/cluster_bench.py [n] [fam] [dmax]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("lz-ani_amd", "oracle", "tools", "tests"):
@@ -36,7 +36,7 @@ lens = np.array([len(s) for s in seqs], dtype=np.uint32)
 out = dict(workload=dict(genomes=n, family=fam, dmax=dmax, directed_pairs=int(len(q)), out_filter=flt, leading_pairs=int(ki["leading"]),
                          kept_pairs=int(kept)),
            pairs_ms=tm["pairs_ms"], index_ms=tm["index_ms"], filter_ms=ki["filter_ms"], algorithms={})
-for algo in CM.ALGOS:
+for algo in CM.ALGOS + ("set-cover",):
     eng.cluster_begin(measure="tani")
     eng.cluster_add_kept()
     eng.cluster_run(algo)
@@ -52,6 +52,11 @@ for algo in CM.ALGOS:
                                    clusters=int(info["clusters"]), singletons=int(info["singletons"]), largest=int(info["largest"]),
                                    edge_bytes=int(info["edge_bytes"]), cluster_host_wall_ms=host_ms, equals_cluster_host=same,
                                    below_pairs_ms=bool(info["add_ms"] + info["run_ms"] < tm["pairs_ms"]))
+    if algo == "set-cover":                                 # what the run says of its distinct edges, and the ratio for the record
+        cov = eng.cluster_cover_info()
+        out["algorithms"][algo].update(distinct_edges=int(cov["distinct_edges"]), duplicate_edges=int(cov["duplicate_edges"]),
+                                       workspace_bytes=int(cov["workspace_bytes"]), dedup_ms=cov["dedup_ms"], rounds_ms=cov["rounds_ms"],
+                                       run_ms_over_greedy_first=info["run_ms"] / out["algorithms"]["greedy-first"]["run_ms"])
 eng.close()
 print(json.dumps(out, indent=1))
 sys.exit(0 if all(a["equals_cluster_host"] for a in out["algorithms"].values()) else 1)
