@@ -460,10 +460,10 @@ int lzani_debug_filter_results(lzani_ctx *ctx, uint32_t n, const uint32_t *repor
 /* LZANI_ERR_STATE without a kept result. */
 int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
 
-/* ---- Clustering the kept pairs on the device: single linkage, greedy and set cover -------------------------------
+/* ---- Clustering the kept pairs on the device: single linkage, greedy, set cover and complete linkage ---------------
  * The kept records of the output filter are the edge list of the similarity graph; this stage clusters it where it lies.
  * It is a post-stage over finished kept results, like the output filter over a result buffer: the pair kernels and their
- * dispatch know nothing of it.  The four algorithms are defined by the statements below and by nothing else (no claim
+ * dispatch know nothing of it.  The five algorithms are defined by the statements below and by nothing else (no claim
  * of equality with another program's output is made); lzani_cluster_host is their sequential form.
  *   graph      the nodes are the n genomes, by the ids of lzani_set_genomes (the lz-ani binary reorders genomes: id 0 is
  *              the first line of its ids file).  The edge {a, b}, a < b, exists iff the pair is a kept pair of a kept call
@@ -498,6 +498,17 @@ int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
  *                                 and all of these are assigned.  An isolated or left-over node with c = 0 becomes its own
  *                                 representative.  Unlike the greedy forms, a representative may have a larger id than
  *                                 its members
+ *     LZANI_CLUSTER_COMPLETE      complete linkage (farthest neighbour) at the output filter's cut, on the graph with
+ *                                 distinct edges as for set cover; the weight of an edge is the smallest w over its
+ *                                 records (kept records of one pair carry one weight; only made-up edges can differ, and
+ *                                 the statement is one about the weakest link).  An edge of weight 0 is an edge.  Every
+ *                                 node starts as a cluster of its own; id(C) is the smallest member id.  Two clusters A
+ *                                 and B are linked iff every pair {a, b}, a in A, b in B, is an edge; the link's value
+ *                                 s(A, B) is the smallest weight among those |A| * |B| edges.  A missing edge means no
+ *                                 link, whatever the weights.  While a link exists: the link with the largest s, ties to
+ *                                 the smallest lower id, then to the smallest other id, is taken and its two clusters
+ *                                 merge.  rep_of[v] = id(final cluster of v).  Every final cluster is a clique of kept
+ *                                 pairs, no two final clusters are linked, and the measure matters as for GREEDY_BEST
  *   numbering  cluster_of[v] = the number of representatives with an id below rep_of[v]: clusters are numbered in
  *              ascending order of their representative; clusters = the number of representatives
  * The device stage: the union-find of SINGLE hooks the larger root under the smaller, so that parent[v] <= v at every
@@ -520,11 +531,34 @@ int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
  * of the first round that left no node unassigned; the global maximum is selected in every round, so n rounds always do
  * (a path with ascending ids takes n / 3; disjoint near-cliques one or two).  More than 2^32 - 17 edge records:
  * LZANI_ERR_ARG; a workspace that does not fit: LZANI_ERR_NOMEM, and the cluster state is as before the run.
- * Not here: complete linkage, Leiden. */
+ * COMPLETE on the device: rounds of reciprocal best links.  From a cluster's own point of view its best link is the one
+ * with the largest s, ties to the smallest neighbouring cluster id; in a round every pair of clusters that are each other's
+ * best link merges.  The rounds give exactly the sequential result: (1) call a merge valid when the two clusters are each
+ * other's best link.  (2) The sequential step is valid: a link that beats (A, B) from A's side or from B's side -- a larger
+ * s, or the same s and a smaller neighbour id -- would precede (A, B) in the global order.  (3) For this linkage
+ * s(X u Y, Z) = min(s(X, Z), s(Y, Z)), and there is no link where either is missing: a merge never raises a value and never
+ * makes a link where there was none.  (4) If C and D are each other's best and X, Y merge elsewhere, the new link
+ * (C, X u Y) can only tie with (C, D) when both (C, X) and (C, Y) tied with it; both then lost on id, so
+ * min(id X, id Y) > id D still holds, and (C, D) stays C's best; the same from D's side.  (5) A valid merge therefore
+ * leaves every other valid merge valid, merges of disjoint pairs commute, and the process ends (every merge takes a cluster
+ * away): every maximal schedule of valid merges ends in the same partition.  Two pairs merged in one round are disjoint, by
+ * reciprocity.  A round works on the entry list L of (ca, cb, count, wmin), ca < cb -- the links and link candidates of the
+ * contracted graph, at first the edge records with count 1: the entries are relabelled and inserted into a table of
+ * S >= 2 * |L| slots, S a power of two (key ca << 32 | cb, all ones a free slot, home splitmix64(key) & (S - 1), linear
+ * probing; count added, weight bits taken to their minimum), which in the first round also makes the edges distinct; a slot
+ * is a link iff count == |ca| * |cb| (in 64 bits); every cluster's best link is found in two passes (the largest weight
+ * bits, then the smallest id among those); the links are compacted into the next L (a slot that is no link is dropped for
+ * good: no superset of an incomplete pair is complete); the reciprocal pairs merge, the larger id under the smaller.
+ * `rounds` is the number of the first round that merged nothing, 1 for an edgeless graph: a property of the graph, not of
+ * the schedule (a path with ascending ids and equal weights takes n / 2 + 1).  The global best link merges in every round,
+ * so n rounds always do.  More than 2^32 - 17 edge records: LZANI_ERR_ARG; a workspace that does not fit:
+ * LZANI_ERR_NOMEM, and the cluster state is as before the run; a probe sequence that runs out: LZANI_ERR_DEVICE.
+ * Not here: Leiden. */
 #define LZANI_CLUSTER_SINGLE        0
 #define LZANI_CLUSTER_GREEDY_FIRST  1
 #define LZANI_CLUSTER_GREEDY_BEST   2
 #define LZANI_CLUSTER_SET_COVER     4   /* 4, not 3: 3 stays an unknown algorithm (tests/test_cluster.py holds 3 and -1 to LZANI_ERR_ARG) */
+#define LZANI_CLUSTER_COMPLETE      6   /* 6, not 5: 3 and 5 stay unknown algorithms (tests/test_cluster_cover.py holds 3, 5 and -1 to LZANI_ERR_ARG) */
 #define LZANI_CLUSTER_TANI          0
 #define LZANI_CLUSTER_GANI          1
 #define LZANI_CLUSTER_ANI           2
@@ -544,6 +578,14 @@ typedef struct lzani_cluster_cover_info {      /* of a LZANI_CLUSTER_SET_COVER r
     uint64_t workspace_bytes;         /* device bytes of the run's workspace: keys, sort scratch, the per-node words */
     double   dedup_ms, rounds_ms;     /* HIP events on the context's stream: keys, sort and unique; the rounds      */
 } lzani_cluster_cover_info;
+typedef struct lzani_cluster_link_info {       /* of a LZANI_CLUSTER_COMPLETE run */
+    uint64_t distinct_edges;          /* edges of the graph: the edge records without their repetitions             */
+    uint64_t duplicate_edges;         /* edge records beyond the first of their pair (edges - distinct_edges)       */
+    uint64_t merges;                  /* merges of two clusters over all rounds (n - clusters)                      */
+    uint64_t table_slots;             /* S of the first round: the smallest power of two >= 2 * edge records        */
+    uint64_t workspace_bytes;         /* device bytes of the run's workspace: table, entry list, the per-cluster words */
+    double   dedup_ms, rounds_ms;     /* HIP events on the context's stream: the first round's insert; all rounds   */
+} lzani_cluster_link_info;
 /* The weight as a pure host function (no GPU).  NULL pointers or an unknown measure: NaN. */
 double lzani_cluster_weight(int measure, const lzani_result *x, const lzani_result *y, uint32_t lines, uint32_t len_a, uint32_t len_b);
 /* The sequential statement as a pure host function (no GPU).  rep_of[n]; cluster_of[n] and n_clusters may be NULL.  An edge
@@ -566,6 +608,8 @@ int lzani_cluster_fetch(lzani_ctx *ctx, uint32_t *rep_of, uint32_t *cluster_of);
 int lzani_get_cluster_info(const lzani_ctx *ctx, lzani_cluster_info *info);
 /* LZANI_ERR_STATE unless the last run was one of LZANI_CLUSTER_SET_COVER. */
 int lzani_get_cluster_cover_info(const lzani_ctx *ctx, lzani_cluster_cover_info *info);
+/* LZANI_ERR_STATE unless the last run was one of LZANI_CLUSTER_COMPLETE. */
+int lzani_get_cluster_link_info(const lzani_ctx *ctx, lzani_cluster_link_info *info);
 
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
@@ -629,6 +673,7 @@ int lzani_group_cluster_run(lzani_group *grp, int algo, uint64_t *n_clusters);
 int lzani_group_cluster_fetch(lzani_group *grp, uint32_t *rep_of, uint32_t *cluster_of);
 int lzani_group_get_cluster_info(const lzani_group *grp, lzani_cluster_info *info);
 int lzani_group_get_cluster_cover_info(const lzani_group *grp, lzani_cluster_cover_info *info);
+int lzani_group_get_cluster_link_info(const lzani_group *grp, lzani_cluster_link_info *info);
 
 /* The shard bookkeeping of lzani_group_run_rows as a pure host function (no GPU): rows keep their order inside
  * their shard, the shards follow each other in the gathered buffer (shard d from result shard_base[d] on,

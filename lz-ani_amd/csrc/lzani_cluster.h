@@ -1,8 +1,9 @@
 // lzani_cluster.h -- host side of the cluster stage (include/lzani.h states the definitions): the edge buffer and its growth,
-// the run -- union-find for single linkage, rounds of the greedy representatives, assignment, or the distinct edges and
-// the rounds of set cover; numbering -- and the entry points (lzani_cluster_begin, lzani_cluster_add_kept,
-// lzani_debug_cluster_add_edges, lzani_cluster_run, lzani_cluster_fetch, lzani_get_cluster_info,
-// lzani_get_cluster_cover_info and the pure lzani_cluster_weight and lzani_cluster_host).  Included by lzani_hip.hip only,
+// the run -- union-find for single linkage, rounds of the greedy representatives, assignment, the distinct edges and
+// the rounds of set cover, or the contraction rounds of complete linkage; numbering -- and the entry points
+// (lzani_cluster_begin, lzani_cluster_add_kept, lzani_debug_cluster_add_edges, lzani_cluster_run, lzani_cluster_fetch,
+// lzani_get_cluster_info, lzani_get_cluster_cover_info, lzani_get_cluster_link_info and the pure lzani_cluster_weight and
+// lzani_cluster_host).  Included by lzani_hip.hip only,
 // behind lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept), fail, HIPCHK and sort_keys, of
 // lzani_prefilter.h pf_blocks and pf_chunks, of lzani_devmem.h DevMem and StreamSpan.  The kernels are lzani_kernels_cluster.h; the group's form is in
 // lzani_multi.h.
@@ -15,7 +16,14 @@
 // many bits as an id has, and the compaction (8 B read twice, 8 B written per distinct edge).  A set-cover round, per
 // distinct edge: 8 B three times; two rep_of words and two atomic adds (count); two keys and one atomic max (first hop);
 // two m1 words and at most one atomic max (second hop: none inside a clique, where every m1 is the same); per node six
-// words read and five written.  Worst case of the rounds: the path with ascending ids, n / 3.
+// words read and five written.  Worst case of the rounds: the path with ascending ids, n / 3.  Complete linkage, a round
+// over an entry list of |L| (the first: the E edge records, 16 B each; later 24 B an entry) and its table of S slots, the
+// smallest power of two >= 2 |L|: 24 B a slot set; per entry its read, two labels, and at a load of at most 1 / 2 a few
+// probes, one CAS where the slot is new, one atomic add and one atomic min; per slot 8 B four times (best weight, best id,
+// the compaction's count and write), and per link two sizes, 16 B more, two atomic max, up to two atomic min, and 24 B
+// written to the next list; per cluster 12 B cleared, one or two best ids read and, where it merges, four words; per node
+// two words.  The merges and |L| are read back once a round (two words and one: no batching as in the greedy rounds, since
+// the next round's grid is |L|'s).  Worst case of the rounds: the path with ascending ids and equal weights, n / 2 + 1.
 #pragma once
 
 namespace {
@@ -131,19 +139,110 @@ int cluster_cover_rounds(lzani_ctx* c, CoverWork& w, u64 D, u32* rep_of, u32* un
     return LZANI_OK;
 }
 
-// The run on the context's edges: fills rep_of, cluster_of and the run's part of `info` (set cover: `cover`, from `work`).
+// The workspace of a complete-linkage run, allocated whole before the run touches the cluster state: the table of S slots
+// (S for the first round, the largest), the entry list (at most one entry per distinct edge), the compaction's block counts
+// and offsets, per cluster label, size, best weight and best id, and the round's two control words.
+constexpr u64 CL_LINK_MAX_EDGES = 0xFFFFFFEFull;        // 2^32 - 17, as for set cover
+struct LinkWork {
+    DevMem<unsigned long long> tkey, tcnt, tw, lkey, lcnt, lw, bestw;
+    DevMem<u32> label, csize, bestid, ucnt, ctl;
+    DevMem<u64> uoff;
+    u64 S = 1;                                          // of the first round
+    u64 bytes() const
+    {
+        return tkey.bytes() + tcnt.bytes() + tw.bytes() + lkey.bytes() + lcnt.bytes() + lw.bytes() + bestw.bytes() + label.bytes() + csize.bytes() +
+               bestid.bytes() + ucnt.bytes() + ctl.bytes() + uoff.bytes();
+    }
+};
+
+// the smallest power of two >= 2 * entries (1 for none)
+u64 cluster_link_slots(u64 entries)
+{
+    u64 S = 1;
+    while (S < 2 * entries) S <<= 1;
+    return S;
+}
+
+int cluster_link_alloc(lzani_ctx* c, LinkWork& w)
+{
+    const u32 n = c->cl.info.n;
+    const u64 E = c->cl.info.edges;
+    if (E > CL_LINK_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: complete linkage takes at most 2^32 - 17 edge records");
+    w.S = cluster_link_slots(E);
+    HIPCHK(c, w.tkey.alloc((size_t)w.S)); HIPCHK(c, w.tcnt.alloc((size_t)w.S)); HIPCHK(c, w.tw.alloc((size_t)w.S));
+    HIPCHK(c, w.lkey.alloc((size_t)E)); HIPCHK(c, w.lcnt.alloc((size_t)E)); HIPCHK(c, w.lw.alloc((size_t)E));
+    HIPCHK(c, w.ucnt.alloc((size_t)pf_chunks(w.S))); HIPCHK(c, w.uoff.alloc((size_t)pf_chunks(w.S) + 1));
+    HIPCHK(c, w.label.alloc(n)); HIPCHK(c, w.csize.alloc(n)); HIPCHK(c, w.bestw.alloc(n)); HIPCHK(c, w.bestid.alloc(n));
+    HIPCHK(c, w.ctl.alloc(CL_LINK_CTL));
+    return LZANI_OK;
+}
+
+// The rounds of complete linkage (lzani_kernels_cluster.h): rep_of, the number of the first round that merged nothing, the
+// merges, the distinct edges (the first round's links: every distinct edge is one) and the time of the first insert.
+int cluster_link_rounds(lzani_ctx* c, LinkWork& w, u32* rep_of, u64& rounds, u64& merges, u64& D, float& dedup_ms)
+{
+    const Cluster& k = c->cl;
+    const u32 n = k.info.n;
+    const dim3 nodes(pf_blocks(n)), threads(PF_THREADS);
+    u64 L = k.info.edges;                               // entries of the round: edge records, then the last round's links
+    rounds = 1; merges = 0; D = 0; dedup_ms = 0;
+    StreamSpan first;
+    for (; L; ++rounds) {                               // (no entry: no link, and the round merges nothing)
+        // the link with the largest value merges in every round: n rounds always do, and a defect ends here instead of spinning
+        if (rounds > (u64)n + 1) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: links still merging after n + 1 rounds");
+        const ClLinkTable t{w.tkey.get(), w.tcnt.get(), w.tw.get(), cluster_link_slots(L)};
+        if (t.S > w.S) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more link entries than edge records");
+        const dim3 slots(pf_blocks(t.S));
+        const u32 chunks = (u32)pf_chunks(t.S);
+        if (rounds == 1) HIPCHK(c, first.begin(c->stream));
+        HIPCHK(c, hipMemsetAsync(t.key, 0xFF, (size_t)t.S * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(t.w, 0xFF, (size_t)t.S * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(t.cnt, 0, (size_t)t.S * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LINK_CTL * sizeof(u32), c->stream));
+        hipLaunchKernelGGL(k_cl_link_insert, dim3(pf_blocks(L)), threads, 0, c->stream, rounds == 1 ? (const lzani_cluster_edge*)k.edges.get() : nullptr,
+                           (const unsigned long long*)w.lkey.get(), (const unsigned long long*)w.lcnt.get(), (const unsigned long long*)w.lw.get(), L, n,
+                           (const u32*)w.label.get(), t, w.ctl.get());
+        if (rounds == 1) HIPCHK(c, first.end(c->stream));
+        hipLaunchKernelGGL(k_cl_link_clear, nodes, threads, 0, c->stream, n, w.bestw.get(), w.bestid.get());
+        hipLaunchKernelGGL(k_cl_link_bestw, slots, threads, 0, c->stream, t, n, (const u32*)w.csize.get(), w.bestw.get());
+        hipLaunchKernelGGL(k_cl_link_bestid, slots, threads, 0, c->stream, t, n, (const u32*)w.csize.get(), (const unsigned long long*)w.bestw.get(), w.bestid.get());
+        hipLaunchKernelGGL(k_cl_link_compact<false>, dim3(chunks), threads, 0, c->stream, t, n, (const u32*)w.csize.get(), w.ucnt.get(), (const u64*)w.uoff.get(),
+                           w.lkey.get(), w.lcnt.get(), w.lw.get());
+        hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.ucnt.get(), (u64)chunks, w.uoff.get());
+        hipLaunchKernelGGL(k_cl_link_compact<true>, dim3(chunks), threads, 0, c->stream, t, n, (const u32*)w.csize.get(), w.ucnt.get(), (const u64*)w.uoff.get(),
+                           w.lkey.get(), w.lcnt.get(), w.lw.get());
+        hipLaunchKernelGGL(k_cl_link_merge, nodes, threads, 0, c->stream, n, (const u32*)w.bestid.get(), w.label.get(), w.csize.get(), w.ctl.get());
+        hipLaunchKernelGGL(k_cl_link_relabel, nodes, threads, 0, c->stream, n, (const u32*)w.label.get(), rep_of);
+        HIPCHK(c, hipGetLastError());
+        u32 ctl[CL_LINK_CTL] = {0, 0};
+        u64 links = 0;
+        HIPCHK(c, hipMemcpyAsync(ctl, w.ctl.get(), sizeof ctl, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&links, w.uoff.get() + chunks, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (ctl[CL_LINK_ERR]) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the cluster-pair table's probe sequence ran out, or an id out of range");
+        if (links > L) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more links than entries");
+        if (rounds == 1) { D = links; HIPCHK(c, first.elapsed(dedup_ms)); }
+        if (!ctl[CL_LINK_MERGES]) break;
+        merges += ctl[CL_LINK_MERGES];
+        L = links;
+    }
+    return LZANI_OK;
+}
+
+// The run on the context's edges: fills rep_of, cluster_of and the run's part of `info` (set cover: `cover`, from `work`;
+// complete linkage: `link`, from `lwork`).
 int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& cluster_of, lzani_cluster_info& info, CoverWork& work,
-                      lzani_cluster_cover_info& cover)
+                      lzani_cluster_cover_info& cover, LinkWork& lwork, lzani_cluster_link_info& link)
 {
     const Cluster& k = c->cl;
     const u32 n = k.info.n;
     const u64 E = k.info.edges;
     const lzani_cluster_edge* edges = k.edges.get();
-    const bool set_cover = algo == LZANI_CLUSTER_SET_COVER;
+    const bool set_cover = algo == LZANI_CLUSTER_SET_COVER, complete = algo == LZANI_CLUSTER_COMPLETE;
     DevMem<u32> parent, state, blocked, flag, size, counters, undecided;
     DevMem<unsigned long long> best;
     DevMem<u64> below;
-    if (!set_cover) { HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, best.alloc(n)); }
+    if (!set_cover && !complete) { HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, best.alloc(n)); }
     HIPCHK(c, flag.alloc(n)); HIPCHK(c, size.alloc(n)); HIPCHK(c, below.alloc((size_t)n + 1));
     HIPCHK(c, counters.alloc(CL_COUNTERS)); HIPCHK(c, undecided.alloc(CL_BATCH));
     HIPCHK(c, rep_of.alloc(n)); HIPCHK(c, cluster_of.alloc(n));
@@ -151,7 +250,7 @@ int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& 
     StreamSpan span;
     HIPCHK(c, span.begin(c->stream));
     HIPCHK(c, hipMemsetAsync(counters, 0, CL_COUNTERS * sizeof(u32), c->stream));
-    if (!set_cover) hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
+    if (!set_cover && !complete) hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
     u64 rounds = 1;
     if (set_cover) {
         StreamSpan dedup, cover_rounds;
@@ -167,6 +266,16 @@ int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& 
         HIPCHK(c, dedup.elapsed(dedup_ms));
         HIPCHK(c, cover_rounds.elapsed(rounds_ms));
         cover = lzani_cluster_cover_info{D, E - D, work.bytes(), dedup_ms, rounds_ms};
+    } else if (complete) {
+        StreamSpan link_rounds;
+        u64 merges = 0, D = 0;
+        float dedup_ms = 0, rounds_ms = 0;
+        HIPCHK(c, link_rounds.begin(c->stream));
+        hipLaunchKernelGGL(k_cl_link_init, nodes, threads, 0, c->stream, n, lwork.label.get(), lwork.csize.get(), rep_of.get(), size.get());
+        if (int rc = cluster_link_rounds(c, lwork, rep_of.get(), rounds, merges, D, dedup_ms)) return rc;
+        HIPCHK(c, link_rounds.end(c->stream));
+        HIPCHK(c, link_rounds.elapsed(rounds_ms));
+        link = lzani_cluster_link_info{D, E - D, merges, lwork.S, lwork.bytes(), dedup_ms, rounds_ms};
     } else if (algo == LZANI_CLUSTER_SINGLE) {
         if (E) hipLaunchKernelGGL(k_cl_hook, edge_blocks, threads, 0, c->stream, edges, E, parent.get());
         hipLaunchKernelGGL(k_cl_roots, nodes, threads, 0, c->stream, n, (const u32*)parent.get(), rep_of.get());
@@ -314,15 +423,20 @@ int lzani_cluster_run(lzani_ctx* c, int algo, uint64_t* n_clusters)
     CoverWork work;                                            // set cover: refused, or short of memory, with the state as it was
     if (algo == LZANI_CLUSTER_SET_COVER)
         if (int rc = cluster_cover_alloc(c, work)) return rc;
+    LinkWork lwork;                                            // complete linkage: the same
+    if (algo == LZANI_CLUSTER_COMPLETE)
+        if (int rc = cluster_link_alloc(c, lwork)) return rc;
     k.ran = false;
     k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes first
     DevMem<u32> rep_of, cluster_of;
     lzani_cluster_info info = k.info;
     lzani_cluster_cover_info cover{};
-    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info, work, cover);
+    lzani_cluster_link_info link{};
+    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info, work, cover, lwork, link);
     if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     k.info = info;
     k.cover = cover;
+    k.link = link;
     k.rep_of = std::move(rep_of); k.cluster_of = std::move(cluster_of);
     k.ran = true;
     if (n_clusters) *n_clusters = info.clusters;
@@ -355,6 +469,14 @@ int lzani_get_cluster_cover_info(const lzani_ctx* c, lzani_cluster_cover_info* i
     if (!c || !info) return LZANI_ERR_ARG;
     if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_SET_COVER) return LZANI_ERR_STATE;
     *info = c->cl.cover;
+    return LZANI_OK;
+}
+
+int lzani_get_cluster_link_info(const lzani_ctx* c, lzani_cluster_link_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_COMPLETE) return LZANI_ERR_STATE;
+    *info = c->cl.link;
     return LZANI_OK;
 }
 

@@ -1,6 +1,7 @@
 // lzani_cluster_plan.h -- the rule and the sequential statement of the cluster stage (include/lzani.h, "clustering the kept
-// pairs"): the weight of an edge, and the four algorithms on a host edge array -- union-find with the smaller root as
-// parent, the greedy sweep over adjacency lists, and greedy set cover by a lazy max-heap.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
+// pairs"): the weight of an edge, and the five algorithms on a host edge array -- union-find with the smaller root as
+// parent, the greedy sweep over adjacency lists, greedy set cover by a lazy max-heap, and complete linkage by a map from
+// link to (count, smallest weight) with a lazy max-heap of the links.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
 // weight; the pure host functions lzani_cluster_weight and lzani_cluster_host (lzani_cluster.h) and the host binary, which
 // includes this header directly, call both.  Free of HIP but for the guard macro; compiled without fast-math and with
 // -ffp-contract=off: every ratio is one IEEE double division of exact integers, so host and device give the same bits.
@@ -10,6 +11,9 @@
 
 #include <algorithm>
 #include <queue>
+#include <tuple>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/lzani.h"
@@ -25,7 +29,7 @@ namespace lzani {
 LZANI_CL_HD inline bool cluster_measure_known(int measure) { return measure >= LZANI_CLUSTER_TANI && measure <= LZANI_CLUSTER_ANI; }
 LZANI_CL_HD inline bool cluster_algo_known(int algo)
 {
-    return (algo >= LZANI_CLUSTER_SINGLE && algo <= LZANI_CLUSTER_GREEDY_BEST) || algo == LZANI_CLUSTER_SET_COVER;
+    return (algo >= LZANI_CLUSTER_SINGLE && algo <= LZANI_CLUSTER_GREEDY_BEST) || algo == LZANI_CLUSTER_SET_COVER || algo == LZANI_CLUSTER_COMPLETE;
 }
 
 // a value that is not above 0 -- NaN, and the negative values and -0 that only made-up integers give -- reads as +0
@@ -120,6 +124,79 @@ inline void cluster_cover_host(uint32_t n, const lzani_cluster_edge* edges, uint
     }
 }
 
+// LZANI_CLUSTER_COMPLETE on the edges as they come.  The distinct pairs with their smallest weight (sorted by pair, then by
+// weight bits: the first record of a pair).  A cluster is known by a handle, the id it had when it was a node; id[h] is
+// its smallest member.  pair[key(h, z)] = (count, wmin) of the edges between two live clusters, kept only while the pair can
+// still be a link: when x and y merge, the neighbours of the union are those z of the shorter adjacency list that both
+// have an entry with and whose summed count is |x u y| * |z| -- every other entry is incomplete for good (no superset of
+// an incomplete pair is complete), so a count kept here is never above the true one and equals it where it matters.  The
+// heap holds (s, ~lower id, ~other id, handles) of every link there is, pushed when it comes to be; it is never repaired:
+// a popped entry counts only if both handles live, carry those ids, and their pair is a link of that value now.  A merge
+// costs the shorter of two adjacency lists and the lists only shrink: O(E log E) on sparse graphs.
+inline void cluster_link_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, uint32_t* rep_of)
+{
+    typedef std::pair<uint64_t, uint64_t> Rec;                                    // (lo << 32 | hi, weight bits); later (count, wmin)
+    std::vector<Rec> recs(count);
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t lo = edges[i].a < edges[i].b ? edges[i].a : edges[i].b, hi = edges[i].a < edges[i].b ? edges[i].b : edges[i].a;
+        recs[i] = Rec(((uint64_t)lo << 32) | hi, cluster_weight_bits(cluster_value(edges[i].w)));
+    }
+    std::sort(recs.begin(), recs.end());
+    recs.erase(std::unique(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.first == y.first; }), recs.end());
+    auto key = [](uint32_t x, uint32_t y) { return x < y ? ((uint64_t)x << 32) | y : ((uint64_t)y << 32) | x; };
+    typedef std::tuple<uint64_t, uint32_t, uint32_t, uint32_t, uint32_t> Link;    // s, ~lower id, ~other id, the two handles
+    std::priority_queue<Link> heap;
+    std::unordered_map<uint64_t, Rec> pair;
+    pair.reserve(recs.size());
+    std::vector<std::vector<uint32_t>> adj(n);
+    std::vector<uint32_t> id(n), size(n, 1), into(n);
+    std::vector<char> live(n, 1);
+    for (uint32_t v = 0; v < n; ++v) id[v] = into[v] = v;
+    for (const Rec& r : recs) {
+        const uint32_t lo = (uint32_t)(r.first >> 32), hi = (uint32_t)r.first;
+        pair[r.first] = Rec(1, r.second);
+        adj[lo].push_back(hi); adj[hi].push_back(lo);
+        heap.push(Link(r.second, ~lo, ~hi, lo, hi));
+    }
+    std::vector<uint32_t> next;
+    while (!heap.empty()) {
+        const Link top = heap.top();
+        heap.pop();
+        uint32_t x = std::get<3>(top), y = std::get<4>(top);
+        if (!live[x] || !live[y]) continue;
+        if ((id[x] < id[y] ? id[x] : id[y]) != ~std::get<1>(top) || (id[x] < id[y] ? id[y] : id[x]) != ~std::get<2>(top)) continue;
+        const auto it = pair.find(key(x, y));
+        if (it == pair.end() || it->second.first != (uint64_t)size[x] * size[y] || it->second.second != std::get<0>(top)) continue;
+        pair.erase(it);
+        if (adj[x].size() > adj[y].size()) std::swap(x, y);                       // x has the shorter list and goes into y
+        const uint32_t merged = size[x] + size[y], mid = id[x] < id[y] ? id[x] : id[y];
+        next.clear();
+        for (uint32_t z : adj[x]) {
+            if (z == y || !live[z]) continue;
+            const auto xz = pair.find(key(x, z));
+            if (xz == pair.end()) continue;                                       // (listed twice, or dropped before)
+            const Rec ex = xz->second;
+            pair.erase(xz);
+            const auto yz = pair.find(key(y, z));
+            if (yz == pair.end()) continue;
+            const Rec both(ex.first + yz->second.first, ex.second < yz->second.second ? ex.second : yz->second.second);
+            if (both.first != (uint64_t)merged * size[z]) { pair.erase(yz); continue; }
+            yz->second = both;
+            next.push_back(z);
+            heap.push(Link(both.second, ~(mid < id[z] ? mid : id[z]), ~(mid < id[z] ? id[z] : mid), y, z));
+        }
+        live[x] = 0; into[x] = y;
+        size[y] = merged; id[y] = mid;
+        adj[y].swap(next);
+        std::vector<uint32_t>().swap(adj[x]);
+    }
+    for (uint32_t v = 0; v < n; ++v) {
+        uint32_t h = v;
+        while (into[h] != h) { into[h] = into[into[h]]; h = into[h]; }
+        rep_of[v] = id[h];
+    }
+}
+
 // The sequential statement.  rep_of[n] is written; cluster_of and n_clusters may be null.  LZANI_ERR_ARG for an edge that
 // cluster_edge_ok refuses or an unknown algo; (b, a) with b > a is the edge (a, b).
 inline int cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, int algo, uint32_t* rep_of, uint32_t* cluster_of, uint32_t* n_clusters)
@@ -141,6 +218,8 @@ inline int cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t co
         for (uint32_t v = 0; v < n; ++v) rep_of[v] = root(v);                     // ... so a root is its tree's smallest id
     } else if (algo == LZANI_CLUSTER_SET_COVER) {
         cluster_cover_host(n, edges, count, rep_of);
+    } else if (algo == LZANI_CLUSTER_COMPLETE) {
+        cluster_link_host(n, edges, count, rep_of);
     } else {
         // adjacency lists of the neighbours below each node
         std::vector<uint64_t> off((size_t)n + 1, 0);

@@ -7,7 +7,7 @@
 //   lzani_kernels_pairs.h   DevWave, k_pairs   the pair kernel
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 //   lzani_kernels_outfilter.h   k_of_kept   the output filter: the pairs of a finished result buffer of which a TSV line passes
-//   lzani_kernels_cluster.h     k_cl_*   the cluster stage: single linkage, greedy clustering and greedy set cover of the kept pairs
+//   lzani_kernels_cluster.h     k_cl_*   the cluster stage: single linkage, greedy clustering, greedy set cover and complete linkage of the kept pairs
 //   lzani_block.h           block_sum, block_rank, block_scan_step   what a block's threads work out together (index, prefilter)
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
@@ -262,6 +262,7 @@ struct Cluster {
     bool begun = false, ran = false;      // ran: rep_of and cluster_of are those of the edges as they are
     lzani_cluster_info info{};
     lzani_cluster_cover_info cover{};     // of the last run, where that was set cover (info.algo says)
+    lzani_cluster_link_info link{};       // of the last run, where that was complete linkage
     DevMem<u32> len;                      // the reported lengths (n)
     DevMem<lzani_cluster_edge> edges;     // info.edges of them, a < b; grown geometrically
     DevMem<u32> rep_of, cluster_of;       // of the last run (n each)

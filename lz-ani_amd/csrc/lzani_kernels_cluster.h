@@ -1,6 +1,7 @@
 // lzani_kernels_cluster.h -- device kernels of the cluster stage (lzani_cluster.h; include/lzani.h states the definitions,
 // lzani_cluster_plan.h the weight).  Included by lzani_hip.hip only, behind lzani_kernels_outfilter.h; of
-// lzani_kernels_prefilter.h it uses PF_THREADS (256-thread blocks) and the scan k_pf_scan, of lzani_block.h block_sum.
+// lzani_kernels_prefilter.h it uses PF_THREADS (256-thread blocks), the scan k_pf_scan and the compaction pf_compact, of
+// lzani_prefilter_defs.h pf_splitmix64, of lzani_block.h block_sum.
 //   k_cl_add_kept    one thread per kept record: the weight, one 16-byte edge by one 16-byte vector store
 //   k_cl_init        per node: parent = v, state = UNDECIDED, blocked = 0, best = 0, size = 0
 //   k_cl_hook        SINGLE, one thread per edge: the two roots by following parent, the larger hooked under the smaller
@@ -11,7 +12,8 @@
 //   k_cl_assign_init, k_cl_assign_best, k_cl_assign_min   rep_of of the nodes that are no representatives
 //   k_cl_flags, k_cl_number   the numbering: flags rep_of[v] == v and cluster sizes; behind the scan cluster_of and the
 //                    counts of singletons and of the largest cluster
-//   k_cl_cover_*     greedy set cover: the keys of the distinct edges, and the passes of a round (at the end of this file)
+//   k_cl_cover_*     greedy set cover: the keys of the distinct edges, and the passes of a round (behind the numbering)
+//   k_cl_link_*      complete linkage: the cluster-pair table and the passes of a round (at the end of this file)
 // Words that other blocks write inside a launch (parent, state, blocked) are read and written with relaxed agent-scope
 // atomics only: the L2 of an XCD is not coherent with the others for plain accesses inside a kernel.  No thread ever waits
 // for a value that another block has yet to write; edge indexes are 64-bit throughout.
@@ -274,6 +276,166 @@ __global__ void __launch_bounds__(PF_THREADS) k_cl_cover_decide(u32 n, const uns
     }
     block_sum(mine, &s_cnt);
     if (threadIdx.x == 0 && s_cnt) atomicAdd(unassigned, s_cnt);
+}
+
+// ---- LZANI_CLUSTER_COMPLETE -----------------------------------------------------------------------------------------
+// Rounds of reciprocal best links (include/lzani.h has the statement and the argument).  A cluster is known by its id, its
+// smallest member; label[c] == c while c lives, else the cluster that took it in the round it went; csize[c] is a live
+// cluster's size.  The entry list L (lkey, lcnt, lw: ca << 32 | cb with ca < cb, count, smallest weight bits) holds the
+// links of the last round's table; the first round reads the edge records in its place, count 1 each.  The table: S slots,
+// a power of two >= 2 * entries, of tkey (CL_LINK_FREE, all ones, marks a free slot: no key, as ca < cb <= 2^32 - 2), tcnt
+// and tw.  A round:
+//   (memsets)          tkey = tw = all ones, tcnt = 0 over the round's S; ctl = 0
+//   k_cl_link_insert   per entry: both ends through label[], entries inside one cluster skipped; the slot of the key from
+//                      its home pf_splitmix64(key) & (S - 1), the next slot on a collision, wrapping at S: atomicCAS on
+//                      the key, atomicAdd on the count (of the edge records, which make the edges distinct here, only the
+//                      one that claims the slot adds), 64-bit atomicMin on the weight bits.  At most S probe steps: a
+//                      sequence that runs out, or an id >= n, raises ctl[CL_LINK_ERR] and the run ends in
+//                      LZANI_ERR_DEVICE.  No step waits for another thread
+//   k_cl_link_clear    per cluster: bestw = 0, bestid = CL_NONE
+//   k_cl_link_bestw    per slot that is a link -- count == (u64)csize[ca] * csize[cb] --: atomicMax of the weight bits into
+//                      bestw of both ends
+//   k_cl_link_bestid   per link whose weight is an end's bestw: atomicMin of the other id into bestid of that end.  (A
+//                      cluster without a link keeps CL_NONE; one whose best weight is 0 has links of weight 0 to show it)
+//   k_cl_link_compact  <false>, k_pf_scan, <true>: the links into L, in the table's order, by pf_compact; before the merge,
+//                      as the sizes say what a link is
+//   k_cl_link_merge    per cluster a with b = bestid[a]: bestid[b] == a and a < b: label[b] = a, csize[a] += csize[b], one
+//                      merge counted.  a's words are written by a's thread alone, b's label too, and csize[b] is read
+//                      by it alone: b's own thread merges nothing, as its partner a lies below it
+//   k_cl_link_relabel  per node: rep_of[v] = label[rep_of[v]]: one hop, as only pairs merge in a round
+// Within a launch the table's words and bestw / bestid are touched through the atomics named and through nothing else;
+// label, csize, rep_of and L are read, or written by one thread a word, and cross a kernel boundary before another thread
+// reads them.  Slot and entry indexes are 64-bit.
+constexpr u64 CL_LINK_FREE = ~0ULL;
+enum { CL_LINK_ERR = 0, CL_LINK_MERGES = 1, CL_LINK_CTL = 2 };
+
+struct ClLinkTable { unsigned long long* __restrict__ key; unsigned long long* __restrict__ cnt; unsigned long long* __restrict__ w; u64 S; };
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_init(u32 n, u32* __restrict__ label, u32* __restrict__ csize, u32* __restrict__ rep_of, u32* __restrict__ size)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    label[v] = v; csize[v] = 1; rep_of[v] = v; size[v] = 0;
+}
+
+// edges != null: the first round, entry i is edge record i; else entry i of L
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_insert(const lzani_cluster_edge* __restrict__ edges, const unsigned long long* __restrict__ lkey,
+                                                               const unsigned long long* __restrict__ lcnt, const unsigned long long* __restrict__ lw, u64 count,
+                                                               u32 n, const u32* __restrict__ label, ClLinkTable t, u32* __restrict__ ctl)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    u32 a, b;
+    u64 c, w;
+    if (edges) { const ClEdge e = cl_edge(edges, i); a = e.lo; b = e.hi; c = 1; w = e.wbits; }
+    else { const u64 k = lkey[i]; a = (u32)(k >> 32); b = (u32)k; c = lcnt[i]; w = lw[i]; }
+    if (a >= n || b >= n) { atomicOr(&ctl[CL_LINK_ERR], 1u); return; }   // (ids are checked where edges come in; a defect must not read astray)
+    a = label[a]; b = label[b];
+    if (a == b) return;
+    if (a >= n || b >= n) { atomicOr(&ctl[CL_LINK_ERR], 1u); return; }
+    const u64 key = a < b ? ((u64)a << 32) | b : ((u64)b << 32) | a, mask = t.S - 1;
+    u64 slot = pf_splitmix64(key) & mask;
+    bool mine = false;
+    for (u64 step = 0; step < t.S; ++step, slot = (slot + 1) & mask) {
+        u64 cur = __hip_atomic_load(&t.key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == CL_LINK_FREE) {
+            cur = atomicCAS(&t.key[slot], (unsigned long long)CL_LINK_FREE, (unsigned long long)key);
+            if (cur == CL_LINK_FREE) { cur = key; mine = true; }          // the slot is this thread's
+        }
+        if (cur == key) {
+            if (!edges || mine) atomicAdd(&t.cnt[slot], (unsigned long long)c);  // (an edge record given again is the same edge)
+            atomicMin(&t.w[slot], (unsigned long long)w);
+            return;
+        }
+    }
+    atomicOr(&ctl[CL_LINK_ERR], 1u);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_clear(u32 n, unsigned long long* __restrict__ bestw, u32* __restrict__ bestid)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    bestw[v] = 0; bestid[v] = CL_NONE;
+}
+
+// Whether slot i holds a link, and then its ends and weight bits.  Read behind the insert's kernel boundary.
+__device__ __forceinline__ bool cl_link_at(const ClLinkTable& t, u64 i, u32 n, const u32* __restrict__ csize, u32& a, u32& b, u64& w)
+{
+    const u64 key = t.key[i];
+    if (key == CL_LINK_FREE) return false;
+    a = (u32)(key >> 32); b = (u32)key;
+    if (a >= n || b >= n) return false;
+    w = t.w[i];
+    return t.cnt[i] == (u64)csize[a] * (u64)csize[b];
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_bestw(ClLinkTable t, u32 n, const u32* __restrict__ csize, unsigned long long* __restrict__ bestw)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 a, b;
+    u64 w;
+    if (i >= t.S || !cl_link_at(t, i, n, csize, a, b, w)) return;
+    atomicMax(&bestw[a], (unsigned long long)w);
+    atomicMax(&bestw[b], (unsigned long long)w);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_bestid(ClLinkTable t, u32 n, const u32* __restrict__ csize, const unsigned long long* __restrict__ bestw,
+                                                               u32* __restrict__ bestid)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 a, b;
+    u64 w;
+    if (i >= t.S || !cl_link_at(t, i, n, csize, a, b, w)) return;
+    if (bestw[a] == w) atomicMin(&bestid[a], b);
+    if (bestw[b] == w) atomicMin(&bestid[b], a);
+}
+
+// The links of the table, counted or written by pf_compact: slot i goes to entry `at` of L.
+struct ClLinkItem {
+    ClLinkTable t;
+    u32 n;
+    const u32* __restrict__ csize;
+    unsigned long long* __restrict__ lkey;
+    unsigned long long* __restrict__ lcnt;
+    unsigned long long* __restrict__ lw;
+    __device__ __forceinline__ bool kept(u64 i, u64& slot) const
+    {
+        u32 a, b;
+        u64 w;
+        slot = i;
+        return cl_link_at(t, i, n, csize, a, b, w);
+    }
+    __device__ __forceinline__ void put(u64 at, u64 slot) const { lkey[at] = t.key[slot]; lcnt[at] = t.cnt[slot]; lw[at] = t.w[slot]; }
+};
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_compact(ClLinkTable t, u32 n, const u32* __restrict__ csize, u32* __restrict__ blkcnt,
+                                                                const u64* __restrict__ blkoff, unsigned long long* __restrict__ lkey,
+                                                                unsigned long long* __restrict__ lcnt, unsigned long long* __restrict__ lw)
+{
+    pf_compact<WRITE>(t.S, blkcnt, blkoff, ClLinkItem{t, n, csize, lkey, lcnt, lw});
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_merge(u32 n, const u32* __restrict__ bestid, u32* label, u32* csize, u32* __restrict__ ctl)
+{
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u32 a = blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 mine = 0;
+    if (a < n) {
+        const u32 b = bestid[a];
+        if (b < n && a < b && bestid[b] == a) { label[b] = a; csize[a] += csize[b]; mine = 1; }
+    }
+    block_sum(mine, &s_cnt);
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(&ctl[CL_LINK_MERGES], s_cnt);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_cl_link_relabel(u32 n, const u32* __restrict__ label, u32* __restrict__ rep_of)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    const u32 r = rep_of[v];
+    if (r < n) rep_of[v] = label[r];
 }
 
 }  // namespace lzani

@@ -547,6 +547,12 @@ int lzani_group_get_cluster_cover_info(const lzani_group* g, lzani_cluster_cover
     return lzani_get_cluster_cover_info(g->ctx[0], info);
 }
 
+int lzani_group_get_cluster_link_info(const lzani_group* g, lzani_cluster_link_info* info)
+{
+    if (!g) return LZANI_ERR_ARG;
+    return lzani_get_cluster_link_info(g->ctx[0], info);
+}
+
 int lzani_group_set_genome_memory(lzani_group* g, uint64_t bytes)
 {
     if (!g) return LZANI_ERR_ARG;

@@ -121,9 +121,10 @@ static void usage()
          << "      --out-filter <par> <float> - store only results with <par> (can be: tani, gani, ani, cov) at least <float>; can be used multiple times\n"
          << "      --cluster <algorithm>      - all2all: cluster the pairs that --out-filter keeps; one of single (connected components),\n"
          << "                                   greedy-first (first representative, as CD-HIT), greedy-best (most similar representative, as UCLUST),\n"
-         << "                                   set-cover (the sequence with the most unassigned neighbours first, as MMseqs2's greedy set cover)\n"
+         << "                                   set-cover (the sequence with the most unassigned neighbours first, as MMseqs2's greedy set cover),\n"
+         << "                                   complete-linkage (every two members of a cluster are a kept pair; the most similar clusters merge first)\n"
          << "      --cluster-out <file_name>  - output file of --cluster: one line per sequence, its id and its cluster number\n"
-         << "      --cluster-measure <type>   - the similarity greedy-best compares: tani, gani or ani (default: tani); accepted and without\n"
+         << "      --cluster-measure <type>   - the similarity greedy-best and complete-linkage compare: tani, gani or ani (default: tani); accepted and without\n"
          << "                                   effect for single, greedy-first and set-cover\n"
          << "      --cluster-representatives  - write the representative's id instead of the cluster number\n"
          << "Options - LZ-parsing-related:\n"
@@ -265,10 +266,10 @@ static bool parse_params(int argc, char** argv)
     }
     if (P.cluster) {
         static const map<string, int> algos = {{"single", LZANI_CLUSTER_SINGLE}, {"greedy-first", LZANI_CLUSTER_GREEDY_FIRST}, {"greedy-best", LZANI_CLUSTER_GREEDY_BEST},
-                                               {"set-cover", LZANI_CLUSTER_SET_COVER}};
+                                               {"set-cover", LZANI_CLUSTER_SET_COVER}, {"complete-linkage", LZANI_CLUSTER_COMPLETE}};
         static const map<string, int> measures = {{"tani", LZANI_CLUSTER_TANI}, {"gani", LZANI_CLUSTER_GANI}, {"ani", LZANI_CLUSTER_ANI}};
         const auto a = algos.find(P.cluster_arg);
-        if (a == algos.end()) { cerr << "Unknown value for --cluster: " << P.cluster_arg << " (single, greedy-first, greedy-best or set-cover)" << endl; exit(1); }
+        if (a == algos.end()) { cerr << "Unknown value for --cluster: " << P.cluster_arg << " (single, greedy-first, greedy-best, set-cover or complete-linkage)" << endl; exit(1); }
         P.cluster_algo = a->second;
         const auto m = measures.find(P.cluster_measure_arg.empty() ? "tani" : P.cluster_measure_arg);
         if (m == measures.end()) { cerr << "Unknown value for --cluster-measure: " << P.cluster_measure_arg << " (tani, gani or ani)" << endl; exit(1); }

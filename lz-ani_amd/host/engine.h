@@ -14,7 +14,8 @@
 
 // Every symbol the binary calls, named once (without its lzani_ prefix).  Required: a library without one is refused.
 // Kept (the output filter on the device) and cluster (the cluster stage): bound where the library has them; an older one
-// keeps the filter, or the clustering, on the host.  Cover (what -V 2 says of a set-cover run): read where it is there.
+// keeps the filter, or the clustering, on the host.  Cover and link (what -V 2 says of a set-cover or a
+// complete-linkage run): read where they are there.
 #define LZANI_ENGINE_REQUIRED(X) \
     X(create) X(destroy) X(last_error) X(set_genomes) X(get_timing) X(run_rows_regions) X(row_costs) X(partition_rows) \
     X(group_create) X(group_destroy) X(group_last_error) X(group_set_genomes) X(group_run_rows) X(group_get_timing) \
@@ -23,7 +24,7 @@
     X(prefilter_cross) X(prefilter_codes_cross) X(set_prefilter_counting) X(get_prefilter_sparse_info)
 #define LZANI_ENGINE_KEPT(X) X(group_run_rows_kept) X(group_kept_fetch) X(group_get_kept_info)
 #define LZANI_ENGINE_CLUSTER(X) X(group_cluster_begin) X(group_cluster_add_kept) X(group_cluster_run) X(group_cluster_fetch) X(group_get_cluster_info)
-#define LZANI_ENGINE_COVER(X) X(group_get_cluster_cover_info)
+#define LZANI_ENGINE_COVER(X) X(group_get_cluster_cover_info) X(group_get_cluster_link_info)
 
 struct Engine {
     void* so = nullptr;

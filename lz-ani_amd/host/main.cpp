@@ -13,7 +13,7 @@
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
 // --out-filter on a two-TSV output is applied on the device (lzani_group_run_rows_kept): only the pairs of which a line
 // passes come back, and the table of all pairs is never made; LZANI_OUT_FILTER=host keeps the filter on the host.
-// --cluster <single|greedy-first|greedy-best|set-cover> clusters the pairs the output filter keeps (include/lzani.h,
+// --cluster <single|greedy-first|greedy-best|set-cover|complete-linkage> clusters the pairs the output filter keeps (include/lzani.h,
 // "clustering the kept pairs") and writes one line per genome to --cluster-out: on the device where the filter is applied there
 // (lzani_group_cluster_*), else by the sequential statement of lzani_cluster_plan.h over the emitter's own lines.
 // This file keeps the raw seams, the stage sequence and main; cli.h holds the command line, engine.h the binding of the

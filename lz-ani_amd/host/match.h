@@ -255,6 +255,10 @@ static bool cluster_finish(const Group& G, const vector<Genome>& g)
     if (P.verbosity >= 2 && G.E.group_get_cluster_cover_info && G.E.group_get_cluster_cover_info(G, &cv) == LZANI_OK)
         cerr << "set cover: " << cv.distinct_edges << " distinct pairs (" << cv.duplicate_edges << " given again), unique " << cv.dedup_ms << " ms, rounds "
              << cv.rounds_ms << " ms, workspace " << cv.workspace_bytes << " bytes\n";
+    lzani_cluster_link_info lk;
+    if (P.verbosity >= 2 && G.E.group_get_cluster_link_info && G.E.group_get_cluster_link_info(G, &lk) == LZANI_OK)
+        cerr << "complete linkage: " << lk.distinct_edges << " distinct pairs (" << lk.duplicate_edges << " given again), " << lk.merges << " merges, table of "
+             << lk.table_slots << " slots, first insert " << lk.dedup_ms << " ms, rounds " << lk.rounds_ms << " ms, workspace " << lk.workspace_bytes << " bytes\n";
     return write_clusters(g, rep_of, cluster_of);
 }
 

@@ -45,7 +45,8 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_cluster_weight", "lzani_cluster_host", "lzani_cluster_begin", "lzani_cluster_add_kept",
            "lzani_debug_cluster_add_edges", "lzani_cluster_run", "lzani_cluster_fetch", "lzani_get_cluster_info",
            "lzani_group_cluster_begin", "lzani_group_cluster_add_kept", "lzani_group_cluster_run", "lzani_group_cluster_fetch",
-           "lzani_group_get_cluster_info", "lzani_get_cluster_cover_info", "lzani_group_get_cluster_cover_info")
+           "lzani_group_get_cluster_info", "lzani_get_cluster_cover_info", "lzani_group_get_cluster_cover_info",
+           "lzani_get_cluster_link_info", "lzani_group_get_cluster_link_info")
 
 
 class LzaniError(RuntimeError):
@@ -179,10 +180,16 @@ class ClusterCoverInfo(C.Structure):
                 ("dedup_ms", C.c_double), ("rounds_ms", C.c_double)]
 
 
+class ClusterLinkInfo(C.Structure):
+    _fields_ = [("distinct_edges", C.c_uint64), ("duplicate_edges", C.c_uint64), ("merges", C.c_uint64), ("table_slots", C.c_uint64),
+                ("workspace_bytes", C.c_uint64), ("dedup_ms", C.c_double), ("rounds_ms", C.c_double)]
+
+
 # lzani_cluster_edge as a numpy record: a < b (either order is taken), w >= 0
 EDGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("w", np.float64)])
 assert EDGE_DTYPE.itemsize == 16
-CLUSTER_ALGOS = {"single": 0, "greedy-first": 1, "greedy-best": 2, "set-cover": 4}     # LZANI_CLUSTER_SINGLE ... (3 is no algorithm)
+CLUSTER_ALGOS = {"single": 0, "greedy-first": 1, "greedy-best": 2, "set-cover": 4,     # LZANI_CLUSTER_SINGLE ... (3 and 5 are no algorithms)
+                 "complete-linkage": 6}
 CLUSTER_MEASURES = {"tani": 0, "gani": 1, "ani": 2}                       # LZANI_CLUSTER_TANI ...
 
 
@@ -342,6 +349,7 @@ def load_library():
             getattr(lib, pre + "cluster_fetch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
             getattr(lib, pre + "get_cluster_info").argtypes = [C.c_void_p, C.c_void_p]
             getattr(lib, pre + "get_cluster_cover_info").argtypes = [C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "get_cluster_link_info").argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_debug_cluster_add_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         _lib = lib
     return _lib
@@ -529,7 +537,7 @@ class _ClusterCalls:
         return int(tot.value)
 
     def cluster_run(self, algo):
-        """Runs "single", "greedy-first", "greedy-best" or "set-cover" on the edges there are; returns the number of clusters."""
+        """Runs "single", "greedy-first", "greedy-best", "set-cover" or "complete-linkage" on the edges there are; returns the number of clusters."""
         k = C.c_uint64(0)
         self._check(getattr(self.lib, self._pre + "cluster_run")(self.h, _algo(algo), C.byref(k)), self._pre + "cluster_run")
         return int(k.value)
@@ -552,6 +560,13 @@ class _ClusterCalls:
         o = ClusterCoverInfo()
         self._check(getattr(self.lib, self._pre + "get_cluster_cover_info")(self.h, C.byref(o)), self._pre + "get_cluster_cover_info")
         return {k: getattr(o, k) for k, _ in ClusterCoverInfo._fields_}
+
+    def cluster_link_info(self):
+        """distinct_edges, duplicate_edges, merges, table_slots, workspace_bytes, dedup_ms, rounds_ms of the last run, a
+        "complete-linkage" one."""
+        o = ClusterLinkInfo()
+        self._check(getattr(self.lib, self._pre + "get_cluster_link_info")(self.h, C.byref(o)), self._pre + "get_cluster_link_info")
+        return {k: getattr(o, k) for k, _ in ClusterLinkInfo._fields_}
 
 
 class Group(_ClusterCalls):

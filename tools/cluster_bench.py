@@ -2,7 +2,9 @@
 """GPU box: the cluster stage on the family set of tools/related_bench.py (n genomes in families of `fam`, the rows hold the
 same-family pairs) behind an output filter that keeps the related pairs.  One lzani_run_rows_kept, then per algorithm
 begin -> add_kept -> run; lzani_cluster_host on the same edges for the wall time of the sequential statement, and its
-answer compared.  Prints one JSON object (profiles/cluster_stage.json; with set cover, profiles/cluster_cover.json).  Usage: tools/cluster_bench.py [n] [fam] [dmax]"""
+answer compared; then complete linkage on its worst shape, a path of made-up edges with ascending ids and equal weights
+(one merge a round).  Prints one JSON object (profiles/cluster_stage.json; with set cover, profiles/cluster_cover.json;
+with complete linkage, profiles/cluster_link.json).  Usage: tools/cluster_bench.py [n] [fam] [dmax] [path nodes]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("lz-ani_amd", "oracle", "tools", "tests"):
@@ -15,6 +17,7 @@ import synth_genomes as SG
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
 fam = int(sys.argv[2]) if len(sys.argv) > 2 else 50
 dmax = float(sys.argv[3]) if len(sys.argv) > 3 else 0.15
+path_n = int(sys.argv[4]) if len(sys.argv) > 4 else 4000
 flt = {"ani": 0.7, "qcov": 0.5}
 t = time.perf_counter()
 _, seqs = SG.make_set(n, 1, fam=fam, dmax=dmax)
@@ -36,7 +39,7 @@ lens = np.array([len(s) for s in seqs], dtype=np.uint32)
 out = dict(workload=dict(genomes=n, family=fam, dmax=dmax, directed_pairs=int(len(q)), out_filter=flt, leading_pairs=int(ki["leading"]),
                          kept_pairs=int(kept)),
            pairs_ms=tm["pairs_ms"], index_ms=tm["index_ms"], filter_ms=ki["filter_ms"], algorithms={})
-for algo in CM.ALGOS + ("set-cover",):
+for algo in CM.ALGOS + ("set-cover", "complete-linkage"):
     eng.cluster_begin(measure="tani")
     eng.cluster_add_kept()
     eng.cluster_run(algo)
@@ -57,6 +60,21 @@ for algo in CM.ALGOS + ("set-cover",):
         out["algorithms"][algo].update(distinct_edges=int(cov["distinct_edges"]), duplicate_edges=int(cov["duplicate_edges"]),
                                        workspace_bytes=int(cov["workspace_bytes"]), dedup_ms=cov["dedup_ms"], rounds_ms=cov["rounds_ms"],
                                        run_ms_over_greedy_first=info["run_ms"] / out["algorithms"]["greedy-first"]["run_ms"])
+    if algo == "complete-linkage":
+        lk = eng.cluster_link_info()
+        out["algorithms"][algo].update(distinct_edges=int(lk["distinct_edges"]), duplicate_edges=int(lk["duplicate_edges"]), merges=int(lk["merges"]),
+                                       table_slots=int(lk["table_slots"]), workspace_bytes=int(lk["workspace_bytes"]), dedup_ms=lk["dedup_ms"],
+                                       rounds_ms=lk["rounds_ms"], run_ms_over_single=info["run_ms"] / out["algorithms"]["single"]["run_ms"],
+                                       run_ms_over_set_cover=info["run_ms"] / out["algorithms"]["set-cover"]["run_ms"])
+# the worst shape of complete linkage: path_n nodes in a path, path_n / 2 + 1 rounds of one merge each
+eng.cluster_begin(path_n, np.ones(path_n, np.uint32))
+eng.debug_cluster_add_edges(L.cluster_edges(np.arange(path_n - 1), np.arange(1, path_n), np.full(path_n - 1, 0.5)))
+eng.cluster_run("complete-linkage")
+eng.cluster_run("complete-linkage")
+info, lk = eng.cluster_info(), eng.cluster_link_info()
+out["complete_linkage_path"] = dict(nodes=path_n, edges=int(info["edges"]), rounds=int(info["rounds"]), merges=int(lk["merges"]), clusters=int(info["clusters"]),
+                                    run_ms=info["run_ms"], rounds_ms=lk["rounds_ms"], dedup_ms=lk["dedup_ms"], ms_per_round=lk["rounds_ms"] / info["rounds"],
+                                    workspace_bytes=int(lk["workspace_bytes"]))
 eng.close()
 print(json.dumps(out, indent=1))
 sys.exit(0 if all(a["equals_cluster_host"] for a in out["algorithms"].values()) else 1)
