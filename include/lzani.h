@@ -509,6 +509,61 @@ int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
  *                                 the smallest lower id, then to the smallest other id, is taken and its two clusters
  *                                 merge.  rep_of[v] = id(final cluster of v).  Every final cluster is a clique of kept
  *                                 pairs, no two final clusters are linked, and the measure matters as for GREEDY_BEST
+ *     LZANI_CLUSTER_LEIDEN        deterministic Leiden with the constant Potts model (CPM), on the graph with distinct
+ *                                 edges as for set cover; the weight of an edge is the smallest w over its records.  No
+ *                                 claim of equality with igraph or Clusty is made, as for the others.  Arithmetic: a weight
+ *                                 is quantised once, q = min(floor(w * 2^20), 2^20) (the product with a power of two and
+ *                                 the floor are exact in a double; +inf clamps to 2^20); the resolution gamma in [0, 1]
+ *                                 (default 0.7) is read as g = llround(gamma * 2^20); everything below is signed 64-bit
+ *                                 integer arithmetic.  n > 2^21: LZANI_ERR_ARG (g * n^2 stays inside 2^62; edge sums stay
+ *                                 below 2^52 under the 2^32 - 17 record limit).
+ *                                 A level is a graph of level nodes with sizes s (original genomes: 1) and distinct
+ *                                 entries (a < b, q).  A community is a set of level nodes; its id is always its smallest
+ *                                 member, recomputed after every round, so every rule is a function of the partition and
+ *                                 not of label history.  S_C = the sum of the sizes in C; W(v, C) = the sum of q over the
+ *                                 entries between v and the members of C other than v.
+ *                                 val(v, C) = W(v, C) - g * s_v * (S_C - [v in C] * s_v).  The option "alone" has the
+ *                                 value 0, exists only for a v that is not alone already, and its community is {v}.
+ *                                 A moving round on a partition P: (1) from the snapshot at the round's start every v
+ *                                 takes its best option among its own community, the communities of its neighbours and
+ *                                 alone: the largest val, ties to staying first, then to the smallest community id, alone
+ *                                 last; D(v) = val(best) - val(own); v is a candidate iff D(v) > 0.  (2) A candidate
+ *                                 touches its own community and its target; alone touches only its own.  (3) v moves iff
+ *                                 in each community it touches it has the largest key among all candidates that touch
+ *                                 that community; the key is the largest D, ties to the smallest v.  (4) All moves are
+ *                                 applied, then ids and sizes are recomputed (where the smallest member left, the
+ *                                 remainder is renamed by the id rule).  (5) The phase ends with the first round that has
+ *                                 no candidate.
+ *                                 A refinement round inside P, from the partition R of singletons: v is eligible iff its
+ *                                 R-community holds one level node (itself, never joined) and it is well connected,
+ *                                 W(v, P(v)) >= g * s_v * (S_P(v) - s_v).  A target is an R-community C != {v} inside
+ *                                 P(v) with W(v, C) > 0, that is itself well connected -- ext(C) >= g * S_C * (S_P - S_C),
+ *                                 ext(C) the weight between C and the rest of its P-community -- and with
+ *                                 D = W(v, C) - g * s_v * S_C >= 0.  The largest D wins, ties to the smallest id; the
+ *                                 exclusivity rule of the moving round applies with the touched communities {v} and C;
+ *                                 the phase ends with the first round without a mover.  This is Leiden's refinement with
+ *                                 the random choice replaced by the greedy one (the limit theta -> 0 of the paper);
+ *                                 R-communities are connected by construction.
+ *                                 Aggregation: the new level nodes are the R-communities, numbered in ascending order of
+ *                                 their smallest member; sizes are summed; entries are contracted through R with their q
+ *                                 summed, those inside one R-community dropped (they enter no val); the new level starts
+ *                                 from P.  An iteration, at each level: the moving phase; if every P-community is one
+ *                                 level node, stop; the refinement; if this level neither moved nor merged anything,
+ *                                 stop; aggregate.  `iterations` in 1..16 (default 2): each starts again from the original
+ *                                 graph with the previous result as P; the run stops early after an iteration in which no
+ *                                 moving round moved anything.  rep_of[v] = the smallest original id of v's final
+ *                                 community.  The measure matters as for GREEDY_BEST.
+ *                                 Why a round is well defined and the phases end: two movers of one round touch disjoint
+ *                                 communities, so the communities a mover leaves and joins are those of the snapshot and
+ *                                 its D is exactly its gain when applied.  The integer quality
+ *                                 Q = sum_C (W_inside(C) - g * sum_{pairs u < v in C} s_u * s_v) rises by the sum of the
+ *                                 applied D, strictly; the candidate with the globally largest key always moves; Q is
+ *                                 bounded: the moving phase terminates, and the result of a round depends on the
+ *                                 partition alone, not on any schedule.  In the refinement a node that moved is never
+ *                                 eligible again, so at most n_level moves are made.  Safety stop: a phase that has run
+ *                                 64 * n_level + 64 rounds ends the run in LZANI_ERR_DEVICE; this is a stop without a
+ *                                 proof that valid inputs stay below it.  The host form applies the same cap, so a graph
+ *                                 that reaches it is found on the CPU
  *   numbering  cluster_of[v] = the number of representatives with an id below rep_of[v]: clusters are numbered in
  *              ascending order of their representative; clusters = the number of representatives
  * The device stage: the union-find of SINGLE hooks the larger root under the smaller, so that parent[v] <= v at every
@@ -553,12 +608,22 @@ int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
  * the schedule (a path with ascending ids and equal weights takes n / 2 + 1).  The global best link merges in every round,
  * so n rounds always do.  More than 2^32 - 17 edge records: LZANI_ERR_ARG; a workspace that does not fit:
  * LZANI_ERR_NOMEM, and the cluster state is as before the run; a probe sequence that runs out: LZANI_ERR_DEVICE.
- * Not here: Leiden. */
+ * LEIDEN on the device: the edge records are made distinct once per run in a table keyed lo << 32 | hi with a 64-bit
+ * atomicMin of q, compacted into the level-0 entry list (the edge buffer is only read).  A moving round sums W(v, C) in a
+ * table keyed node << 32 | community of the other end (S a power of two >= 2 * the insertions, atomicCAS on the key, 64-bit
+ * atomicAdd on the sum, probing bounded by S); per slot it takes val(own), then the largest D per node (atomicMax) and
+ * the smallest community id among the slots that equal it (atomicMin); the same max-then-min pair runs per community over
+ * the candidates; every node decides for itself, and the smallest members, ids and sizes are recomputed.  A refinement
+ * round has the same skeleton, with an entry pass for ext and the member counts.  All of it are the statement's rounds word
+ * for word: `levels`, the round counts, `moves`, `merges` and `quality` of lzani_cluster_leiden_info are properties of
+ * the graph.  More than 2^32 - 17 edge records or n > 2^21: LZANI_ERR_ARG; a workspace that does not fit: LZANI_ERR_NOMEM,
+ * and the cluster state is as before the run; a probe sequence that runs out or a phase at its cap: LZANI_ERR_DEVICE. */
 #define LZANI_CLUSTER_SINGLE        0
 #define LZANI_CLUSTER_GREEDY_FIRST  1
 #define LZANI_CLUSTER_GREEDY_BEST   2
 #define LZANI_CLUSTER_SET_COVER     4   /* 4, not 3: 3 stays an unknown algorithm (tests/test_cluster.py holds 3 and -1 to LZANI_ERR_ARG) */
 #define LZANI_CLUSTER_COMPLETE      6   /* 6, not 5: 3 and 5 stay unknown algorithms (tests/test_cluster_cover.py holds 3, 5 and -1 to LZANI_ERR_ARG) */
+#define LZANI_CLUSTER_LEIDEN        8   /* 8, not 7: 3, 5 and 7 stay unknown algorithms (tests/test_cluster_link.py holds them to LZANI_ERR_ARG) */
 #define LZANI_CLUSTER_TANI          0
 #define LZANI_CLUSTER_GANI          1
 #define LZANI_CLUSTER_ANI           2
@@ -586,12 +651,38 @@ typedef struct lzani_cluster_link_info {       /* of a LZANI_CLUSTER_COMPLETE ru
     uint64_t workspace_bytes;         /* device bytes of the run's workspace: table, entry list, the per-cluster words */
     double   dedup_ms, rounds_ms;     /* HIP events on the context's stream: the first round's insert; all rounds   */
 } lzani_cluster_link_info;
+typedef struct lzani_cluster_leiden_info {     /* of a LZANI_CLUSTER_LEIDEN run */
+    uint64_t iterations;              /* iterations run (the run stops after one without a move)                    */
+    uint64_t levels;                  /* moving phases, over all iterations                                         */
+    uint64_t move_rounds, refine_rounds;   /* rounds of all phases, the last of each phase (no mover) included      */
+    uint64_t moves, merges;           /* movers of the moving rounds; movers of the refinement rounds               */
+    int64_t  quality;                 /* Q of the result on the original graph, in units of 2^-20                   */
+    uint64_t resolution_q;            /* g = llround(resolution * 2^20)                                             */
+    uint64_t distinct_edges;          /* edges of the graph: the edge records without their repetitions             */
+    uint64_t duplicate_edges;         /* edge records beyond the first of their pair (edges - distinct_edges)       */
+    uint64_t table_slots;             /* S of the largest table: the smallest power of two >= 4 * edge records      */
+    uint64_t workspace_bytes;         /* device bytes of the run's workspace: table, entry lists, per-node words    */
+    double   dedup_ms, rounds_ms;     /* HIP events on the context's stream: the distinct edges; all iterations     */
+} lzani_cluster_leiden_info;
 /* The weight as a pure host function (no GPU).  NULL pointers or an unknown measure: NaN. */
 double lzani_cluster_weight(int measure, const lzani_result *x, const lzani_result *y, uint32_t lines, uint32_t len_a, uint32_t len_b);
 /* The sequential statement as a pure host function (no GPU).  rep_of[n]; cluster_of[n] and n_clusters may be NULL.  An edge
  * with a == b, an id >= n, a NaN or negative w, or an unknown algo: LZANI_ERR_ARG.  (b, a) with b > a is the edge (a, b). */
 int lzani_cluster_host(uint32_t n, const lzani_cluster_edge *edges, uint64_t count, int algo, uint32_t *rep_of, uint32_t *cluster_of,
                        uint32_t *n_clusters);
+/* LZANI_CLUSTER_LEIDEN as a pure host function with its parameters (lzani_cluster_host runs it with the defaults 0.7 and 2):
+ * a sequential form of exactly the rounds of the statement.  info (may be NULL) receives the counts, quality and
+ * resolution_q; its device fields are 0.  resolution outside [0, 1] or NaN, iterations outside 1..16, n > 2^21, a bad edge:
+ * LZANI_ERR_ARG; a phase at its cap of rounds: LZANI_ERR_DEVICE. */
+int lzani_cluster_leiden_host(uint32_t n, const lzani_cluster_edge *edges, uint64_t count, double resolution, int iterations,
+                              uint32_t *rep_of, uint32_t *cluster_of, lzani_cluster_leiden_info *info);
+/* Test hook: the same with a phase's cap of rounds set to cap_mul * n_level + cap_add in place of 64 * n_level + 64. */
+int lzani_debug_cluster_leiden_host_cap(uint32_t n, const lzani_cluster_edge *edges, uint64_t count, double resolution, int iterations,
+                                        uint64_t cap_mul, uint64_t cap_add, uint32_t *rep_of, uint32_t *cluster_of,
+                                        lzani_cluster_leiden_info *info);
+/* The parameters of LZANI_CLUSTER_LEIDEN runs of this context, until it is destroyed; the defaults are 0.7 and 2.
+ * resolution outside [0, 1] or NaN, iterations outside 1..16: LZANI_ERR_ARG, and the parameters stay. */
+int lzani_set_cluster_leiden(lzani_ctx *ctx, double resolution, int iterations);
 /* An empty edge set for n genomes, whose reported lengths (NULL: the genome set's own, n must be its size) stay on the device.
  * Drops the cluster state there was; lzani_set_genomes drops it too.  No genome set: LZANI_ERR_STATE. */
 int lzani_cluster_begin(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len, int measure);
@@ -610,6 +701,8 @@ int lzani_get_cluster_info(const lzani_ctx *ctx, lzani_cluster_info *info);
 int lzani_get_cluster_cover_info(const lzani_ctx *ctx, lzani_cluster_cover_info *info);
 /* LZANI_ERR_STATE unless the last run was one of LZANI_CLUSTER_COMPLETE. */
 int lzani_get_cluster_link_info(const lzani_ctx *ctx, lzani_cluster_link_info *info);
+/* LZANI_ERR_STATE unless the last run was one of LZANI_CLUSTER_LEIDEN. */
+int lzani_get_cluster_leiden_info(const lzani_ctx *ctx, lzani_cluster_leiden_info *info);
 
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
@@ -674,6 +767,8 @@ int lzani_group_cluster_fetch(lzani_group *grp, uint32_t *rep_of, uint32_t *clus
 int lzani_group_get_cluster_info(const lzani_group *grp, lzani_cluster_info *info);
 int lzani_group_get_cluster_cover_info(const lzani_group *grp, lzani_cluster_cover_info *info);
 int lzani_group_get_cluster_link_info(const lzani_group *grp, lzani_cluster_link_info *info);
+int lzani_group_set_cluster_leiden(lzani_group *grp, double resolution, int iterations);
+int lzani_group_get_cluster_leiden_info(const lzani_group *grp, lzani_cluster_leiden_info *info);
 
 /* The shard bookkeeping of lzani_group_run_rows as a pure host function (no GPU): rows keep their order inside
  * their shard, the shards follow each other in the gathered buffer (shard d from result shard_base[d] on,

@@ -1,9 +1,10 @@
 // lzani_cluster.h -- host side of the cluster stage (include/lzani.h states the definitions): the edge buffer and its growth,
 // the run -- union-find for single linkage, rounds of the greedy representatives, assignment, the distinct edges and
-// the rounds of set cover, or the contraction rounds of complete linkage; numbering -- and the entry points
+// the rounds of set cover, the contraction rounds of complete linkage, or the levels and rounds of Leiden; numbering --
+// and the entry points
 // (lzani_cluster_begin, lzani_cluster_add_kept, lzani_debug_cluster_add_edges, lzani_cluster_run, lzani_cluster_fetch,
-// lzani_get_cluster_info, lzani_get_cluster_cover_info, lzani_get_cluster_link_info and the pure lzani_cluster_weight and
-// lzani_cluster_host).  Included by lzani_hip.hip only,
+// lzani_get_cluster_info, lzani_get_cluster_cover_info, lzani_get_cluster_link_info, lzani_set_cluster_leiden,
+// lzani_get_cluster_leiden_info and the pure lzani_cluster_weight, lzani_cluster_host and lzani_cluster_leiden_host).  Included by lzani_hip.hip only,
 // behind lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept), fail, HIPCHK and sort_keys, of
 // lzani_prefilter.h pf_blocks and pf_chunks, of lzani_devmem.h DevMem and StreamSpan.  The kernels are lzani_kernels_cluster.h; the group's form is in
 // lzani_multi.h.
@@ -24,6 +25,13 @@
 // written to the next list; per cluster 12 B cleared, one or two best ids read and, where it merges, four words; per node
 // two words.  The merges and |L| are read back once a round (two words and one: no batching as in the greedy rounds, since
 // the next round's grid is |L|'s).  Worst case of the rounds: the path with ascending ids and equal weights, n / 2 + 1.
+// Leiden, a moving round over the level's |L| entries, m nodes and a table of S slots, the smallest power of two >= 4 |L|:
+// 16 B a slot and 8 B a node set; per entry 16 B, two community words, two probe sequences, a CAS where the slot is new and
+// two 64-bit atomic adds; per slot key and sum three times, one atomic max and at most one atomic min; per node some 60 B,
+// two atomic max and up to two atomic min on the community words, one atomic min on its label's smallest member and one
+// atomic add on its community's size.  A refinement round: the same, and two atomic adds an entry more.  The control words
+// are read back once in CL_LD_BATCH rounds, the aggregation's two counts once a level.  Worst case: one clique of n, n
+// moving rounds.
 #pragma once
 
 namespace {
@@ -229,20 +237,254 @@ int cluster_link_rounds(lzani_ctx* c, LinkWork& w, u32* rep_of, u64& rounds, u64
     return LZANI_OK;
 }
 
+// The workspace of a Leiden run, allocated whole before the run touches the cluster state: the table of S slots (S for the
+// largest round there can be: 2 * E insertions), the level-0 entry list and the working list of the higher levels (at most
+// one entry per distinct edge each), the compaction's block counts and offsets, the per-node and per-community words of
+// the rounds (two sets of sizes and partitions: a level and the one aggregated from it), and the control words.
+constexpr u64 CL_LEIDEN_MAX_EDGES = 0xFFFFFFEFull;      // 2^32 - 17, as for set cover
+struct LeidenWork {
+    DevMem<unsigned long long> tkey, tval, e0key, wkey, bestd, cd, quality;
+    DevMem<i64> e0q, wq, ownw, valown, ext;             // ownw: W(v, own) of a moving round, W(v, P(v)) of a refinement
+    DevMem<u32> s, s2, P, P2, R, SP, SR, cntr, well, bestid, cv, newlab, minm, node_of, flag, ucnt, ctl;
+    DevMem<u64> uoff, below;
+    u64 S = 1;
+    u64 bytes() const
+    {
+        return tkey.bytes() + tval.bytes() + e0key.bytes() + wkey.bytes() + bestd.bytes() + cd.bytes() + quality.bytes() + e0q.bytes() + wq.bytes() +
+               ownw.bytes() + valown.bytes() + ext.bytes() + s.bytes() + s2.bytes() + P.bytes() + P2.bytes() + R.bytes() + SP.bytes() + SR.bytes() +
+               cntr.bytes() + well.bytes() + bestid.bytes() + cv.bytes() + newlab.bytes() + minm.bytes() + node_of.bytes() + flag.bytes() +
+               ucnt.bytes() + ctl.bytes() + uoff.bytes() + below.bytes();
+    }
+};
+
+int cluster_leiden_alloc(lzani_ctx* c, LeidenWork& w)
+{
+    const u32 n = c->cl.info.n;
+    const u64 E = c->cl.info.edges;
+    if (n > CL_LEIDEN_MAX_N) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: Leiden takes at most 2^21 genomes");
+    if (E > CL_LEIDEN_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: Leiden takes at most 2^32 - 17 edge records");
+    w.S = cluster_link_slots(2 * E);
+    HIPCHK(c, w.tkey.alloc((size_t)w.S)); HIPCHK(c, w.tval.alloc((size_t)w.S));
+    HIPCHK(c, w.e0key.alloc((size_t)E)); HIPCHK(c, w.e0q.alloc((size_t)E)); HIPCHK(c, w.wkey.alloc((size_t)E)); HIPCHK(c, w.wq.alloc((size_t)E));
+    HIPCHK(c, w.ucnt.alloc((size_t)pf_chunks(w.S))); HIPCHK(c, w.uoff.alloc((size_t)pf_chunks(w.S) + 1));
+    HIPCHK(c, w.bestd.alloc(n)); HIPCHK(c, w.cd.alloc(n)); HIPCHK(c, w.ownw.alloc(n)); HIPCHK(c, w.valown.alloc(n)); HIPCHK(c, w.ext.alloc(n));
+    HIPCHK(c, w.s.alloc(n)); HIPCHK(c, w.s2.alloc(n)); HIPCHK(c, w.P.alloc(n)); HIPCHK(c, w.P2.alloc(n)); HIPCHK(c, w.R.alloc(n));
+    HIPCHK(c, w.SP.alloc(n)); HIPCHK(c, w.SR.alloc(n)); HIPCHK(c, w.cntr.alloc(n)); HIPCHK(c, w.well.alloc(n)); HIPCHK(c, w.bestid.alloc(n));
+    HIPCHK(c, w.cv.alloc(n)); HIPCHK(c, w.newlab.alloc(n)); HIPCHK(c, w.minm.alloc(2 * (size_t)n)); HIPCHK(c, w.node_of.alloc(n));
+    HIPCHK(c, w.flag.alloc(n)); HIPCHK(c, w.below.alloc((size_t)n + 1));
+    HIPCHK(c, w.quality.alloc(1)); HIPCHK(c, w.ctl.alloc(CL_LD_CTL));
+    return LZANI_OK;
+}
+
+// A phase on a level of m nodes: round(r) launches one round whose movers go to ctl[CL_LD_MOVERS + r] (and, where it counts
+// them, the communities behind it to ctl[CL_LD_COMMS + r]); batches of CL_LD_BATCH rounds between two reads of the control
+// words, as a round behind the one without a mover changes nothing.  rounds: up to the first without a mover, that one
+// included; movers: their sum; comms: the communities behind the last round.
+template <class Round>
+int cluster_leiden_phase(lzani_ctx* c, LeidenWork& w, u32 m, const char* what, Round round, u64& rounds, u64& movers, u32& comms)
+{
+    const u64 cap = CL_LEIDEN_CAP_MUL * m + CL_LEIDEN_CAP_ADD;
+    rounds = 0; movers = 0; comms = 0;
+    for (bool done = false; !done;) {
+        // a safety stop, not a bound that is proved: see include/lzani.h
+        if (rounds >= cap) return fail(c, LZANI_ERR_DEVICE, std::string("lzani_cluster_run: Leiden's ") + what + " still moves nodes after 64 * n + 64 rounds");
+        const u32 batch = (u32)std::min<u64>(CL_LD_BATCH, cap - rounds);
+        HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
+        for (u32 r = 0; r < batch; ++r) HIPCHK(c, round(r));
+        HIPCHK(c, hipGetLastError());
+        u32 ctl[CL_LD_CTL];
+        HIPCHK(c, hipMemcpyAsync(ctl, w.ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (ctl[CL_LD_ERR]) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the node-community table's probe sequence ran out, or an id out of range");
+        u32 r = 0;
+        while (r < batch && ctl[CL_LD_MOVERS + r]) movers += ctl[CL_LD_MOVERS + r++];
+        done = r < batch;
+        rounds += done ? r + 1 : batch;
+        comms = ctl[CL_LD_COMMS + (done ? r : batch - 1)];
+    }
+    return LZANI_OK;
+}
+
+// The table of a round cleared: the keys all ones, the values `fill` bytes.
+hipError_t cluster_leiden_clear(lzani_ctx* c, const ClLdTable& t, int fill)
+{
+    const hipError_t e = hipMemsetAsync(t.key, 0xFF, (size_t)t.S * 8, c->stream);
+    return e != hipSuccess ? e : hipMemsetAsync(t.val, fill, (size_t)t.S * 8, c->stream);
+}
+
+// The table's occupied slots into the entry list (key, q); their number at w.uoff[pf_chunks(t.S)].
+void cluster_leiden_compact(lzani_ctx* c, LeidenWork& w, const ClLdTable& t, unsigned long long* key, i64* q)
+{
+    const u32 chunks = (u32)pf_chunks(t.S);
+    const dim3 threads(PF_THREADS);
+    hipLaunchKernelGGL(k_ld_compact<false>, dim3(chunks), threads, 0, c->stream, t, w.ucnt.get(), (const u64*)w.uoff.get(), key, q);
+    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.ucnt.get(), (u64)chunks, w.uoff.get());
+    hipLaunchKernelGGL(k_ld_compact<true>, dim3(chunks), threads, 0, c->stream, t, w.ucnt.get(), (const u64*)w.uoff.get(), key, q);
+}
+
+// The iterations of Leiden (lzani_kernels_cluster.h): rep_of (v at the start) and what the run did.
+int cluster_leiden_rounds(lzani_ctx* c, LeidenWork& w, u32* rep_of, lzani_cluster_leiden_info& out)
+{
+    const Cluster& k = c->cl;
+    const u32 n = k.info.n;
+    const u64 E = k.info.edges;
+    const i64 g = cluster_leiden_g(c->leiden_resolution);
+    const dim3 threads(PF_THREADS), all(pf_blocks(n));
+    out = lzani_cluster_leiden_info{};
+    out.resolution_q = (u64)g; out.table_slots = w.S; out.workspace_bytes = w.bytes();
+    // the distinct edges with their smallest q: the level-0 entry list
+    StreamSpan dedup, span;
+    u64 D = 0;
+    HIPCHK(c, dedup.begin(c->stream));
+    if (E) {
+        const ClLdTable t{w.tkey.get(), w.tval.get(), cluster_link_slots(E)};
+        HIPCHK(c, cluster_leiden_clear(c, t, 0xFF));
+        HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
+        hipLaunchKernelGGL(k_ld_dedup, dim3(pf_blocks(E)), threads, 0, c->stream, (const lzani_cluster_edge*)k.edges.get(), E, n, t, w.ctl.get());
+        cluster_leiden_compact(c, w, t, w.e0key.get(), w.e0q.get());
+        HIPCHK(c, hipGetLastError());
+        u32 err = 0;
+        HIPCHK(c, hipMemcpyAsync(&err, w.ctl.get() + CL_LD_ERR, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&D, w.uoff.get() + pf_chunks(t.S), 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (err) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the edge table's probe sequence ran out, or an id out of range");
+        if (D > E) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more distinct edges than edge records");
+    }
+    HIPCHK(c, dedup.end(c->stream));
+    out.distinct_edges = D; out.duplicate_edges = E - D;
+    HIPCHK(c, span.begin(c->stream));
+    for (int it = 0; it < c->leiden_iterations; ++it) {
+        out.iterations++;
+        u32 m = n;                                      // the level: its nodes, its entries and where they are
+        u64 L = D;
+        const unsigned long long* lkey = w.e0key.get();
+        const i64* lq = w.e0q.get();
+        hipLaunchKernelGGL(k_ld_level0, all, threads, 0, c->stream, n, (const u32*)rep_of, w.s.get(), w.P.get(), w.node_of.get());
+        HIPCHK(c, hipMemsetAsync(w.SP, 0, (size_t)n * 4, c->stream));
+        hipLaunchKernelGGL(k_ld_sizes, all, threads, 0, c->stream, n, (const u32*)w.s.get(), (const u32*)w.P.get(), w.SP.get(), (u32*)nullptr, (u32*)nullptr);
+        u64 moved_in_iteration = 0;
+        for (;;) {
+            out.levels++;
+            const dim3 nodes(pf_blocks(m)), entries(pf_blocks(L));
+            const ClLdTable t{w.tkey.get(), w.tval.get(), cluster_link_slots(2 * L)};
+            if (t.S > w.S) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more entries than edge records");
+            const dim3 slots(pf_blocks(t.S));
+            u32 *s = w.s.get(), *P = w.P.get(), *R = w.R.get(), *SP = w.SP.get(), *SR = w.SR.get(), *cntr = w.cntr.get(), *ctl = w.ctl.get();
+            u64 rounds = 0, moved = 0, merged = 0;
+            u32 comms = 0;
+            auto share = [&](u32* part, u32* S, u32* cnt, u32 r, bool count_comms) {         // the passes both kinds of round end in
+                hipLaunchKernelGGL(k_ld_cand_max, nodes, threads, 0, c->stream, m, (const u32*)part, (const unsigned long long*)w.bestd.get(),
+                                   (const u32*)w.bestid.get(), w.cd.get());
+                hipLaunchKernelGGL(k_ld_cand_min, nodes, threads, 0, c->stream, m, (const u32*)part, (const unsigned long long*)w.bestd.get(),
+                                   (const u32*)w.bestid.get(), (const unsigned long long*)w.cd.get(), w.cv.get());
+                hipLaunchKernelGGL(k_ld_decide, nodes, threads, 0, c->stream, m, (const u32*)part, (const unsigned long long*)w.bestd.get(),
+                                   (const u32*)w.bestid.get(), (const u32*)w.cv.get(), w.newlab.get(), w.minm.get(), ctl + CL_LD_MOVERS + r);
+                hipLaunchKernelGGL(k_ld_minm, nodes, threads, 0, c->stream, m, (const u32*)w.newlab.get(), w.minm.get());
+                hipLaunchKernelGGL(k_ld_newid, nodes, threads, 0, c->stream, m, (const u32*)w.newlab.get(), (const u32*)w.minm.get(), part, S, cnt);
+                hipLaunchKernelGGL(k_ld_sizes, nodes, threads, 0, c->stream, m, (const u32*)s, (const u32*)part, S, cnt,
+                                   count_comms ? ctl + CL_LD_COMMS + r : (u32*)nullptr);
+            };
+            auto move_round = [&](u32 r) -> hipError_t {
+                if (hipError_t e = cluster_leiden_clear(c, t, 0)) return e;
+                if (hipError_t e = hipMemsetAsync(w.ownw, 0, (size_t)m * 8, c->stream)) return e;
+                if (L) hipLaunchKernelGGL(k_ld_move_insert, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)P, t, ctl);
+                hipLaunchKernelGGL(k_ld_move_stay, slots, threads, 0, c->stream, t, m, (const u32*)P, w.ownw.get());
+                hipLaunchKernelGGL(k_ld_move_node, nodes, threads, 0, c->stream, m, g, (const u32*)s, (const u32*)P, (const u32*)SP, (const i64*)w.ownw.get(),
+                                   w.valown.get(), w.bestd.get(), w.bestid.get(), w.cd.get(), w.cv.get());
+                hipLaunchKernelGGL(k_ld_move_bestd, slots, threads, 0, c->stream, t, m, g, (const u32*)s, (const u32*)P, (const u32*)SP,
+                                   (const i64*)w.valown.get(), w.bestd.get());
+                hipLaunchKernelGGL(k_ld_move_bestid, slots, threads, 0, c->stream, t, m, g, (const u32*)s, (const u32*)P, (const u32*)SP,
+                                   (const i64*)w.valown.get(), (const unsigned long long*)w.bestd.get(), w.bestid.get());
+                share(P, SP, nullptr, r, true);
+                return hipSuccess;
+            };
+            if (int rc = cluster_leiden_phase(c, w, m, "moving phase", move_round, rounds, moved, comms)) return rc;
+            out.move_rounds += rounds; out.moves += moved; moved_in_iteration += moved;
+            if (comms == m) break;                      // every community is one level node
+            hipLaunchKernelGGL(k_ld_refine_init, nodes, threads, 0, c->stream, m, (const u32*)s, R, SR, cntr, w.ownw.get());
+            if (L) hipLaunchKernelGGL(k_ld_wp, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)P, w.ownw.get());
+            hipLaunchKernelGGL(k_ld_well, nodes, threads, 0, c->stream, m, g, (const u32*)s, (const u32*)P, (const u32*)SP, (const i64*)w.ownw.get(), w.well.get());
+            const ClLdRefine rf{g, s, P, R, SP, SR, cntr, w.well.get(), w.ext.get()};
+            auto refine_round = [&](u32 r) -> hipError_t {
+                if (hipError_t e = cluster_leiden_clear(c, t, 0)) return e;
+                if (hipError_t e = hipMemsetAsync(w.ext, 0, (size_t)m * 8, c->stream)) return e;
+                if (L) hipLaunchKernelGGL(k_ld_refine_insert, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)P, (const u32*)R, t, w.ext.get(), ctl);
+                hipLaunchKernelGGL(k_ld_refine_node, nodes, threads, 0, c->stream, m, w.bestd.get(), w.bestid.get(), w.cd.get(), w.cv.get());
+                hipLaunchKernelGGL(k_ld_refine_bestd, slots, threads, 0, c->stream, t, m, rf, w.bestd.get());
+                hipLaunchKernelGGL(k_ld_refine_bestid, slots, threads, 0, c->stream, t, m, rf, (const unsigned long long*)w.bestd.get(), w.bestid.get());
+                share(R, SR, cntr, r, false);
+                return hipSuccess;
+            };
+            if (int rc = cluster_leiden_phase(c, w, m, "refinement", refine_round, rounds, merged, comms)) return rc;
+            out.refine_rounds += rounds; out.merges += merged;
+            if (!moved && !merged) break;               // nothing can change any more
+            // aggregation: the R-communities, numbered in ascending order of their smallest member, and the entries between them
+            hipLaunchKernelGGL(k_ld_agg_flags, nodes, threads, 0, c->stream, m, (const u32*)R, w.flag.get());
+            hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.flag.get(), (u64)m, w.below.get());
+            hipLaunchKernelGGL(k_ld_agg_nodes, nodes, threads, 0, c->stream, m, (const u32*)R, (const u32*)P, (const u32*)SR, (const u64*)w.below.get(),
+                               w.s2.get(), w.P2.get());
+            hipLaunchKernelGGL(k_ld_agg_nodeof, all, threads, 0, c->stream, n, m, (const u32*)R, (const u64*)w.below.get(), w.node_of.get());
+            const ClLdTable ta{w.tkey.get(), w.tval.get(), cluster_link_slots(L)};
+            HIPCHK(c, cluster_leiden_clear(c, ta, 0));
+            HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
+            if (L) hipLaunchKernelGGL(k_ld_agg_insert, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)R, (const u64*)w.below.get(), ta, ctl);
+            cluster_leiden_compact(c, w, ta, w.wkey.get(), w.wq.get());
+            HIPCHK(c, hipGetLastError());
+            u64 m2 = 0, L2 = 0;
+            u32 err = 0;
+            HIPCHK(c, hipMemcpyAsync(&m2, w.below.get() + m, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&L2, w.uoff.get() + pf_chunks(ta.S), 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&err, w.ctl.get() + CL_LD_ERR, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (err) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the contraction table's probe sequence ran out, or an id out of range");
+            if (!m2 || m2 > m || L2 > L) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: an aggregated level larger than the level it comes from");
+            std::swap(w.s, w.s2); std::swap(w.P, w.P2);
+            m = (u32)m2; L = L2; lkey = w.wkey.get(); lq = w.wq.get();
+            HIPCHK(c, hipMemsetAsync(w.SP, 0, (size_t)m * 4, c->stream));
+            hipLaunchKernelGGL(k_ld_sizes, dim3(pf_blocks(m)), threads, 0, c->stream, m, (const u32*)w.s.get(), (const u32*)w.P.get(), w.SP.get(), (u32*)nullptr,
+                               (u32*)nullptr);
+        }
+        // rep_of: the smallest original id of every final community
+        hipLaunchKernelGGL(k_ld_final, all, threads, 0, c->stream, n, m, (const u32*)w.node_of.get(), (const u32*)w.P.get(), w.newlab.get(), w.minm.get());
+        hipLaunchKernelGGL(k_ld_minm, all, threads, 0, c->stream, n, (const u32*)w.newlab.get(), w.minm.get());
+        hipLaunchKernelGGL(k_ld_newid, all, threads, 0, c->stream, n, (const u32*)w.newlab.get(), (const u32*)w.minm.get(), rep_of, w.SP.get(), (u32*)nullptr);
+        HIPCHK(c, hipGetLastError());
+        if (!moved_in_iteration) break;
+    }
+    // Q of the result on the original graph (k_ld_newid left SP cleared)
+    HIPCHK(c, hipMemsetAsync(w.quality, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_ld_sizes, all, threads, 0, c->stream, n, (const u32*)nullptr, (const u32*)rep_of, w.SP.get(), (u32*)nullptr, (u32*)nullptr);
+    if (D) hipLaunchKernelGGL(k_ld_quality_edges, dim3(pf_blocks(D)), threads, 0, c->stream, (const unsigned long long*)w.e0key.get(), (const i64*)w.e0q.get(), D, n,
+                              (const u32*)rep_of, w.quality.get());
+    hipLaunchKernelGGL(k_ld_quality_nodes, all, threads, 0, c->stream, n, g, (const u32*)w.SP.get(), w.quality.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, span.end(c->stream));
+    unsigned long long quality = 0;
+    HIPCHK(c, hipMemcpyAsync(&quality, w.quality.get(), 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float dedup_ms = 0, rounds_ms = 0;
+    HIPCHK(c, dedup.elapsed(dedup_ms));
+    HIPCHK(c, span.elapsed(rounds_ms));
+    out.quality = (int64_t)quality; out.dedup_ms = dedup_ms; out.rounds_ms = rounds_ms;
+    return LZANI_OK;
+}
+
 // The run on the context's edges: fills rep_of, cluster_of and the run's part of `info` (set cover: `cover`, from `work`;
 // complete linkage: `link`, from `lwork`).
 int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& cluster_of, lzani_cluster_info& info, CoverWork& work,
-                      lzani_cluster_cover_info& cover, LinkWork& lwork, lzani_cluster_link_info& link)
+                      lzani_cluster_cover_info& cover, LinkWork& lwork, lzani_cluster_link_info& link, LeidenWork& ldwork,
+                      lzani_cluster_leiden_info& leiden)
 {
     const Cluster& k = c->cl;
     const u32 n = k.info.n;
     const u64 E = k.info.edges;
     const lzani_cluster_edge* edges = k.edges.get();
-    const bool set_cover = algo == LZANI_CLUSTER_SET_COVER, complete = algo == LZANI_CLUSTER_COMPLETE;
+    const bool set_cover = algo == LZANI_CLUSTER_SET_COVER, complete = algo == LZANI_CLUSTER_COMPLETE, is_leiden = algo == LZANI_CLUSTER_LEIDEN;
+    const bool plain = !set_cover && !complete && !is_leiden;                    // SINGLE and the greedy forms: parent, state, blocked, best
     DevMem<u32> parent, state, blocked, flag, size, counters, undecided;
     DevMem<unsigned long long> best;
     DevMem<u64> below;
-    if (!set_cover && !complete) { HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, best.alloc(n)); }
+    if (plain) { HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, best.alloc(n)); }
     HIPCHK(c, flag.alloc(n)); HIPCHK(c, size.alloc(n)); HIPCHK(c, below.alloc((size_t)n + 1));
     HIPCHK(c, counters.alloc(CL_COUNTERS)); HIPCHK(c, undecided.alloc(CL_BATCH));
     HIPCHK(c, rep_of.alloc(n)); HIPCHK(c, cluster_of.alloc(n));
@@ -250,7 +492,7 @@ int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& 
     StreamSpan span;
     HIPCHK(c, span.begin(c->stream));
     HIPCHK(c, hipMemsetAsync(counters, 0, CL_COUNTERS * sizeof(u32), c->stream));
-    if (!set_cover && !complete) hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
+    if (plain) hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
     u64 rounds = 1;
     if (set_cover) {
         StreamSpan dedup, cover_rounds;
@@ -276,6 +518,10 @@ int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& 
         HIPCHK(c, link_rounds.end(c->stream));
         HIPCHK(c, link_rounds.elapsed(rounds_ms));
         link = lzani_cluster_link_info{D, E - D, merges, lwork.S, lwork.bytes(), dedup_ms, rounds_ms};
+    } else if (is_leiden) {
+        hipLaunchKernelGGL(k_ld_init, nodes, threads, 0, c->stream, n, rep_of.get(), size.get());
+        if (int rc = cluster_leiden_rounds(c, ldwork, rep_of.get(), leiden)) return rc;
+        rounds = leiden.move_rounds + leiden.refine_rounds;
     } else if (algo == LZANI_CLUSTER_SINGLE) {
         if (E) hipLaunchKernelGGL(k_cl_hook, edge_blocks, threads, 0, c->stream, edges, E, parent.get());
         hipLaunchKernelGGL(k_cl_roots, nodes, threads, 0, c->stream, n, (const u32*)parent.get(), rep_of.get());
@@ -338,6 +584,41 @@ int lzani_cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t cou
 {
     try { return cluster_host(n, edges, count, algo, rep_of, cluster_of, n_clusters); }
     catch (const std::bad_alloc&) { return LZANI_ERR_NOMEM; }
+}
+
+// the edges checked as cluster_host checks them, then Leiden with its parameters and the numbering
+static int cluster_leiden_host_call(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, double resolution, int iterations, uint64_t cap_mul,
+                                    uint64_t cap_add, uint32_t* rep_of, uint32_t* cluster_of, lzani_cluster_leiden_info* info)
+{
+    if (!rep_of || (count && !edges)) return LZANI_ERR_ARG;
+    for (uint64_t i = 0; i < count; ++i)
+        if (!cluster_edge_ok(n, edges[i])) return LZANI_ERR_ARG;
+    try {
+        if (int rc = cluster_leiden_host(n, edges, count, resolution, iterations, rep_of, info, cap_mul, cap_add)) return rc;
+        cluster_number(n, rep_of, cluster_of);
+        return LZANI_OK;
+    } catch (const std::bad_alloc&) { return LZANI_ERR_NOMEM; }
+}
+
+int lzani_cluster_leiden_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, double resolution, int iterations, uint32_t* rep_of,
+                              uint32_t* cluster_of, lzani_cluster_leiden_info* info)
+{
+    return cluster_leiden_host_call(n, edges, count, resolution, iterations, CL_LEIDEN_CAP_MUL, CL_LEIDEN_CAP_ADD, rep_of, cluster_of, info);
+}
+
+int lzani_debug_cluster_leiden_host_cap(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, double resolution, int iterations, uint64_t cap_mul,
+                                        uint64_t cap_add, uint32_t* rep_of, uint32_t* cluster_of, lzani_cluster_leiden_info* info)
+{
+    return cluster_leiden_host_call(n, edges, count, resolution, iterations, cap_mul, cap_add, rep_of, cluster_of, info);
+}
+
+int lzani_set_cluster_leiden(lzani_ctx* c, double resolution, int iterations)
+{
+    if (!c) return LZANI_ERR_ARG;
+    if (!cluster_leiden_params_ok(resolution, iterations))
+        return fail(c, LZANI_ERR_ARG, "lzani_set_cluster_leiden: the resolution lies in [0, 1], the iterations in 1..16");
+    c->leiden_resolution = resolution; c->leiden_iterations = iterations;
+    return LZANI_OK;
 }
 
 int lzani_cluster_begin(lzani_ctx* c, uint32_t n, const uint32_t* report_len, int measure)
@@ -426,17 +707,22 @@ int lzani_cluster_run(lzani_ctx* c, int algo, uint64_t* n_clusters)
     LinkWork lwork;                                            // complete linkage: the same
     if (algo == LZANI_CLUSTER_COMPLETE)
         if (int rc = cluster_link_alloc(c, lwork)) return rc;
+    LeidenWork ldwork;                                         // Leiden: the same
+    if (algo == LZANI_CLUSTER_LEIDEN)
+        if (int rc = cluster_leiden_alloc(c, ldwork)) return rc;
     k.ran = false;
     k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes first
     DevMem<u32> rep_of, cluster_of;
     lzani_cluster_info info = k.info;
     lzani_cluster_cover_info cover{};
     lzani_cluster_link_info link{};
-    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info, work, cover, lwork, link);
+    lzani_cluster_leiden_info leiden{};
+    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info, work, cover, lwork, link, ldwork, leiden);
     if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     k.info = info;
     k.cover = cover;
     k.link = link;
+    k.leiden = leiden;
     k.rep_of = std::move(rep_of); k.cluster_of = std::move(cluster_of);
     k.ran = true;
     if (n_clusters) *n_clusters = info.clusters;
@@ -477,6 +763,14 @@ int lzani_get_cluster_link_info(const lzani_ctx* c, lzani_cluster_link_info* inf
     if (!c || !info) return LZANI_ERR_ARG;
     if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_COMPLETE) return LZANI_ERR_STATE;
     *info = c->cl.link;
+    return LZANI_OK;
+}
+
+int lzani_get_cluster_leiden_info(const lzani_ctx* c, lzani_cluster_leiden_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_LEIDEN) return LZANI_ERR_STATE;
+    *info = c->cl.leiden;
     return LZANI_OK;
 }
 

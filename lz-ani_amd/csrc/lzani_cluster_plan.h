@@ -1,15 +1,19 @@
 // lzani_cluster_plan.h -- the rule and the sequential statement of the cluster stage (include/lzani.h, "clustering the kept
-// pairs"): the weight of an edge, and the five algorithms on a host edge array -- union-find with the smaller root as
-// parent, the greedy sweep over adjacency lists, greedy set cover by a lazy max-heap, and complete linkage by a map from
-// link to (count, smallest weight) with a lazy max-heap of the links.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
-// weight; the pure host functions lzani_cluster_weight and lzani_cluster_host (lzani_cluster.h) and the host binary, which
+// pairs"): the weight of an edge, and the six algorithms on a host edge array -- union-find with the smaller root as
+// parent, the greedy sweep over adjacency lists, greedy set cover by a lazy max-heap, complete linkage by a map from
+// link to (count, smallest weight) with a lazy max-heap of the links, and Leiden (CPM) by the rounds of its statement over
+// adjacency lists per level.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
+// weight (and Leiden's quantisation); the pure host functions lzani_cluster_weight, lzani_cluster_host and lzani_cluster_leiden_host (lzani_cluster.h) and the host binary, which
 // includes this header directly, call both.  Free of HIP but for the guard macro; compiled without fast-math and with
 // -ffp-contract=off: every ratio is one IEEE double division of exact integers, so host and device give the same bits.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
+#include <math.h>
+
 #include <algorithm>
+#include <map>
 #include <queue>
 #include <tuple>
 #include <unordered_map>
@@ -29,7 +33,8 @@ namespace lzani {
 LZANI_CL_HD inline bool cluster_measure_known(int measure) { return measure >= LZANI_CLUSTER_TANI && measure <= LZANI_CLUSTER_ANI; }
 LZANI_CL_HD inline bool cluster_algo_known(int algo)
 {
-    return (algo >= LZANI_CLUSTER_SINGLE && algo <= LZANI_CLUSTER_GREEDY_BEST) || algo == LZANI_CLUSTER_SET_COVER || algo == LZANI_CLUSTER_COMPLETE;
+    return (algo >= LZANI_CLUSTER_SINGLE && algo <= LZANI_CLUSTER_GREEDY_BEST) || algo == LZANI_CLUSTER_SET_COVER || algo == LZANI_CLUSTER_COMPLETE ||
+           algo == LZANI_CLUSTER_LEIDEN;
 }
 
 // a value that is not above 0 -- NaN, and the negative values and -0 that only made-up integers give -- reads as +0
@@ -197,6 +202,236 @@ inline void cluster_link_host(uint32_t n, const lzani_cluster_edge* edges, uint6
     }
 }
 
+// ---- LZANI_CLUSTER_LEIDEN ---------------------------------------------------------------------------------------------
+// The arithmetic of the statement: weights and the resolution in units of 2^-20, everything else in signed 64 bits.
+constexpr int64_t CL_LEIDEN_ONE = (int64_t)1 << 20;
+constexpr uint32_t CL_LEIDEN_MAX_N = 1u << 21;          // g * n^2 stays inside 2^62
+constexpr double CL_LEIDEN_RESOLUTION = 0.7;
+constexpr int CL_LEIDEN_ITERATIONS = 2, CL_LEIDEN_MAX_ITERATIONS = 16;
+constexpr uint64_t CL_LEIDEN_CAP_MUL = 64, CL_LEIDEN_CAP_ADD = 64;   // a phase of cap_mul * n_level + cap_add rounds is stopped
+// w >= 0 or +inf: min(floor(w * 2^20), 2^20).  The product is exact, the conversion truncates what is not negative.
+LZANI_CL_HD inline int64_t cluster_leiden_q(double w) { return w >= 1.0 ? CL_LEIDEN_ONE : (int64_t)(w * 1048576.0); }
+inline bool cluster_leiden_params_ok(double resolution, int iterations)
+{
+    return resolution >= 0 && resolution <= 1 && iterations >= 1 && iterations <= CL_LEIDEN_MAX_ITERATIONS;   // (NaN fails the first)
+}
+inline int64_t cluster_leiden_g(double resolution) { return (int64_t)llround(resolution * 1048576.0); }
+
+// A level of the sequential form: sizes, the distinct entries a < b with their q, the partition P (a community's id is its
+// smallest member) and the adjacency map of every node.
+struct LeidenLevel {
+    uint32_t m = 0;
+    std::vector<int64_t> s;
+    std::vector<uint64_t> key;
+    std::vector<int64_t> q;
+    std::vector<uint32_t> P;
+    std::vector<std::vector<std::pair<uint32_t, int64_t>>> adj;
+    void link()
+    {
+        adj.assign(m, std::vector<std::pair<uint32_t, int64_t>>());
+        for (size_t i = 0; i < key.size(); ++i) {
+            const uint32_t a = (uint32_t)(key[i] >> 32), b = (uint32_t)key[i];
+            adj[a].push_back(std::make_pair(b, q[i]));
+            adj[b].push_back(std::make_pair(a, q[i]));
+        }
+    }
+};
+
+// labels (any values below `span`) -> the smallest member of every label's set
+inline void leiden_smallest_member(std::vector<uint32_t>& part, const std::vector<uint32_t>& labels, size_t span)
+{
+    std::vector<uint32_t> low(span, 0xFFFFFFFFu);
+    for (uint32_t v = 0; v < labels.size(); ++v)
+        if (v < low[labels[v]]) low[labels[v]] = v;
+    for (uint32_t v = 0; v < labels.size(); ++v) part[v] = low[labels[v]];
+}
+
+// The largest key of a community over the candidates that touch it: the largest D, ties to the smallest node.
+struct LeidenTouch {
+    std::vector<int64_t> D;
+    std::vector<uint32_t> v;
+    explicit LeidenTouch(uint32_t m) : D(m, -1), v(m, 0xFFFFFFFFu) {}
+    void touch(uint32_t c, int64_t d, uint32_t node)
+    {
+        if (d > D[c] || (d == D[c] && node < v[c])) { D[c] = d; v[c] = node; }
+    }
+};
+
+// One moving round; returns the movers.
+inline uint64_t leiden_move_round(LeidenLevel& L, int64_t g)
+{
+    const uint32_t m = L.m, ALONE = m;
+    std::vector<int64_t> S(m, 0), D(m, 0);
+    std::vector<uint32_t> T(m, 0);
+    for (uint32_t v = 0; v < m; ++v) S[L.P[v]] += L.s[v];
+    std::map<uint32_t, int64_t> W;
+    for (uint32_t v = 0; v < m; ++v) {
+        W.clear();
+        for (const auto& e : L.adj[v]) W[L.P[e.first]] += e.second;
+        const uint32_t own = L.P[v];
+        const auto at = W.find(own);
+        const int64_t val_own = (at == W.end() ? 0 : at->second) - g * L.s[v] * (S[own] - L.s[v]);
+        int64_t best = val_own;                                                   // staying first
+        uint32_t target = own;
+        for (const auto& c : W) {                                                 // then the smallest community id
+            if (c.first == own) continue;
+            const int64_t val = c.second - g * L.s[v] * S[c.first];
+            if (val > best) { best = val; target = c.first; }
+        }
+        if (S[own] != L.s[v] && 0 > best) { best = 0; target = ALONE; }          // alone last
+        D[v] = best - val_own; T[v] = target;
+    }
+    LeidenTouch t(m);
+    for (uint32_t v = 0; v < m; ++v) {
+        if (D[v] <= 0) continue;
+        t.touch(L.P[v], D[v], v);
+        if (T[v] != ALONE) t.touch(T[v], D[v], v);
+    }
+    std::vector<uint32_t> labels(L.P);
+    uint64_t movers = 0;
+    for (uint32_t v = 0; v < m; ++v)
+        if (D[v] > 0 && t.v[L.P[v]] == v && (T[v] == ALONE || t.v[T[v]] == v)) { labels[v] = T[v] == ALONE ? m + v : T[v]; ++movers; }
+    leiden_smallest_member(L.P, labels, 2 * (size_t)m);
+    return movers;
+}
+
+// One refinement round on R inside L.P; returns the movers.
+inline uint64_t leiden_refine_round(const LeidenLevel& L, int64_t g, std::vector<uint32_t>& R, const std::vector<char>& well, const std::vector<int64_t>& SP)
+{
+    const uint32_t m = L.m, NONE = 0xFFFFFFFFu;
+    std::vector<int64_t> SR(m, 0), ext(m, 0), D(m, -1);
+    std::vector<uint32_t> members(m, 0), T(m, NONE);
+    for (uint32_t v = 0; v < m; ++v) { SR[R[v]] += L.s[v]; members[R[v]]++; }
+    for (size_t i = 0; i < L.key.size(); ++i) {
+        const uint32_t a = (uint32_t)(L.key[i] >> 32), b = (uint32_t)L.key[i];
+        if (L.P[a] == L.P[b] && R[a] != R[b]) { ext[R[a]] += L.q[i]; ext[R[b]] += L.q[i]; }
+    }
+    std::map<uint32_t, int64_t> W;
+    for (uint32_t v = 0; v < m; ++v) {
+        if (members[R[v]] != 1 || !well[v]) continue;
+        W.clear();
+        for (const auto& e : L.adj[v])
+            if (L.P[e.first] == L.P[v] && R[e.first] != R[v]) W[R[e.first]] += e.second;
+        for (const auto& c : W) {
+            if (c.second <= 0 || ext[c.first] < g * SR[c.first] * (SP[L.P[v]] - SR[c.first])) continue;
+            const int64_t d = c.second - g * L.s[v] * SR[c.first];
+            if (d >= 0 && d > D[v]) { D[v] = d; T[v] = c.first; }
+        }
+    }
+    LeidenTouch t(m);
+    for (uint32_t v = 0; v < m; ++v)
+        if (T[v] != NONE) { t.touch(R[v], D[v], v); t.touch(T[v], D[v], v); }
+    std::vector<uint32_t> labels(R);
+    uint64_t movers = 0;
+    for (uint32_t v = 0; v < m; ++v)
+        if (T[v] != NONE && t.v[R[v]] == v && t.v[T[v]] == v) { labels[v] = T[v]; ++movers; }
+    leiden_smallest_member(R, labels, m);
+    return movers;
+}
+
+// LZANI_CLUSTER_LEIDEN on the edges as they come: a sequential form of exactly the rounds of the statement.  rep_of[n] is
+// written; info's counts, quality and resolution_q too (its device fields stay 0).  LZANI_ERR_DEVICE where a phase reaches
+// its cap of rounds.
+inline int cluster_leiden_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, double resolution, int iterations, uint32_t* rep_of,
+                               lzani_cluster_leiden_info* info, uint64_t cap_mul = CL_LEIDEN_CAP_MUL, uint64_t cap_add = CL_LEIDEN_CAP_ADD)
+{
+    if (!cluster_leiden_params_ok(resolution, iterations) || n > CL_LEIDEN_MAX_N) return LZANI_ERR_ARG;
+    const int64_t g = cluster_leiden_g(resolution);
+    typedef std::pair<uint64_t, int64_t> Rec;
+    std::vector<Rec> recs(count);
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t lo = edges[i].a < edges[i].b ? edges[i].a : edges[i].b, hi = edges[i].a < edges[i].b ? edges[i].b : edges[i].a;
+        recs[i] = Rec(((uint64_t)lo << 32) | hi, cluster_leiden_q(cluster_value(edges[i].w)));
+    }
+    std::sort(recs.begin(), recs.end());                                          // by pair, then by q: the first record has the smallest
+    recs.erase(std::unique(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.first == y.first; }), recs.end());
+    lzani_cluster_leiden_info st{};
+    st.resolution_q = (uint64_t)g; st.distinct_edges = recs.size(); st.duplicate_edges = count - recs.size();
+    for (uint32_t v = 0; v < n; ++v) rep_of[v] = v;
+    for (int it = 0; it < iterations; ++it) {
+        st.iterations++;
+        LeidenLevel L;
+        L.m = n; L.s.assign(n, 1); L.P.assign(rep_of, rep_of + n);
+        L.key.resize(recs.size()); L.q.resize(recs.size());
+        for (size_t i = 0; i < recs.size(); ++i) { L.key[i] = recs[i].first; L.q[i] = recs[i].second; }
+        L.link();
+        std::vector<uint32_t> node_of(n);
+        for (uint32_t v = 0; v < n; ++v) node_of[v] = v;
+        uint64_t moved_in_iteration = 0;
+        for (;;) {
+            st.levels++;
+            const uint32_t m = L.m;
+            const uint64_t cap = cap_mul * m + cap_add;
+            uint64_t moved = 0, merged = 0;
+            for (uint64_t rounds = 0;; ) {
+                if (rounds >= cap) return LZANI_ERR_DEVICE;
+                ++rounds; st.move_rounds++;
+                const uint64_t k = leiden_move_round(L, g);
+                moved += k;
+                if (!k) break;
+            }
+            st.moves += moved; moved_in_iteration += moved;
+            bool single = true;
+            for (uint32_t v = 0; v < m && single; ++v) single = L.P[v] == v;
+            if (single) break;
+            std::vector<int64_t> SP(m, 0);
+            for (uint32_t v = 0; v < m; ++v) SP[L.P[v]] += L.s[v];
+            std::vector<char> well(m);
+            for (uint32_t v = 0; v < m; ++v) {
+                int64_t w = 0;
+                for (const auto& e : L.adj[v])
+                    if (L.P[e.first] == L.P[v]) w += e.second;
+                well[v] = w >= g * L.s[v] * (SP[L.P[v]] - L.s[v]);
+            }
+            std::vector<uint32_t> R(m);
+            for (uint32_t v = 0; v < m; ++v) R[v] = v;
+            for (uint64_t rounds = 0;; ) {
+                if (rounds >= cap) return LZANI_ERR_DEVICE;
+                ++rounds; st.refine_rounds++;
+                const uint64_t k = leiden_refine_round(L, g, R, well, SP);
+                merged += k;
+                if (!k) break;
+            }
+            st.merges += merged;
+            if (!moved && !merged) break;
+            // aggregation: the R-communities in ascending order of their smallest member
+            std::vector<uint32_t> index(m, 0);
+            uint32_t m2 = 0;
+            for (uint32_t v = 0; v < m; ++v)
+                if (R[v] == v) index[v] = m2++;
+            LeidenLevel N;
+            N.m = m2; N.s.assign(m2, 0); N.P.resize(m2);
+            for (uint32_t v = 0; v < m; ++v) N.s[index[R[v]]] += L.s[v];
+            for (uint32_t v = 0; v < m; ++v)
+                if (R[v] == v) N.P[index[v]] = index[L.P[v]];                      // (P's smallest member is the smallest of its R-community)
+            std::map<uint64_t, int64_t> sum;
+            for (size_t i = 0; i < L.key.size(); ++i) {
+                const uint32_t x = index[R[(uint32_t)(L.key[i] >> 32)]], y = index[R[(uint32_t)L.key[i]]];
+                if (x != y) sum[x < y ? ((uint64_t)x << 32) | y : ((uint64_t)y << 32) | x] += L.q[i];
+            }
+            for (const auto& e : sum) { N.key.push_back(e.first); N.q.push_back(e.second); }
+            N.link();
+            for (uint32_t v = 0; v < n; ++v) node_of[v] = index[R[node_of[v]]];
+            L = std::move(N);
+        }
+        std::vector<uint32_t> labels(n);
+        for (uint32_t v = 0; v < n; ++v) labels[v] = L.P[node_of[v]];
+        std::vector<uint32_t> part(n);
+        leiden_smallest_member(part, labels, n);
+        for (uint32_t v = 0; v < n; ++v) rep_of[v] = part[v];
+        if (!moved_in_iteration) break;
+    }
+    std::vector<int64_t> size(n, 0);
+    for (uint32_t v = 0; v < n; ++v) size[rep_of[v]]++;
+    int64_t quality = 0;
+    for (const Rec& r : recs)
+        if (rep_of[(uint32_t)(r.first >> 32)] == rep_of[(uint32_t)r.first]) quality += r.second;
+    for (uint32_t v = 0; v < n; ++v) quality -= g * (size[v] * (size[v] - 1) / 2);
+    st.quality = quality;
+    if (info) *info = st;
+    return LZANI_OK;
+}
+
 // The sequential statement.  rep_of[n] is written; cluster_of and n_clusters may be null.  LZANI_ERR_ARG for an edge that
 // cluster_edge_ok refuses or an unknown algo; (b, a) with b > a is the edge (a, b).
 inline int cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t count, int algo, uint32_t* rep_of, uint32_t* cluster_of, uint32_t* n_clusters)
@@ -220,6 +455,8 @@ inline int cluster_host(uint32_t n, const lzani_cluster_edge* edges, uint64_t co
         cluster_cover_host(n, edges, count, rep_of);
     } else if (algo == LZANI_CLUSTER_COMPLETE) {
         cluster_link_host(n, edges, count, rep_of);
+    } else if (algo == LZANI_CLUSTER_LEIDEN) {
+        if (int rc = cluster_leiden_host(n, edges, count, CL_LEIDEN_RESOLUTION, CL_LEIDEN_ITERATIONS, rep_of, nullptr)) return rc;
     } else {
         // adjacency lists of the neighbours below each node
         std::vector<uint64_t> off((size_t)n + 1, 0);

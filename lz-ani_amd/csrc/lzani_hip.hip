@@ -263,6 +263,7 @@ struct Cluster {
     lzani_cluster_info info{};
     lzani_cluster_cover_info cover{};     // of the last run, where that was set cover (info.algo says)
     lzani_cluster_link_info link{};       // of the last run, where that was complete linkage
+    lzani_cluster_leiden_info leiden{};   // of the last run, where that was Leiden
     DevMem<u32> len;                      // the reported lengths (n)
     DevMem<lzani_cluster_edge> edges;     // info.edges of them, a < b; grown geometrically
     DevMem<u32> rep_of, cluster_of;       // of the last run (n each)
@@ -292,6 +293,8 @@ struct lzani_ctx {
     void* comm = nullptr;         // ncclComm_t of lzani_comm_init (one process per GPU), lzani_multi.h
     u32 n_ranks = 1, rank = 0;
     u64 mem_req = 0;              // lzani_set_genome_memory: applies at the next lzani_set_genomes; 0 = automatic
+    double leiden_resolution = CL_LEIDEN_RESOLUTION;      // lzani_set_cluster_leiden: the parameters of the later Leiden runs
+    int leiden_iterations = CL_LEIDEN_ITERATIONS;
     int pf_counting = LZANI_PF_COUNTING_AUTO;     // lzani_set_prefilter_counting: the accumulator of the later prefilter calls
 
     GenomeSet gs;

@@ -13,7 +13,8 @@
 //   k_cl_flags, k_cl_number   the numbering: flags rep_of[v] == v and cluster sizes; behind the scan cluster_of and the
 //                    counts of singletons and of the largest cluster
 //   k_cl_cover_*     greedy set cover: the keys of the distinct edges, and the passes of a round (behind the numbering)
-//   k_cl_link_*      complete linkage: the cluster-pair table and the passes of a round (at the end of this file)
+//   k_cl_link_*      complete linkage: the cluster-pair table and the passes of a round
+//   k_ld_*           Leiden (CPM): the node-community table and the passes of the rounds (at the end of this file)
 // Words that other blocks write inside a launch (parent, state, blocked) are read and written with relaxed agent-scope
 // atomics only: the L2 of an XCD is not coherent with the others for plain accesses inside a kernel.  No thread ever waits
 // for a value that another block has yet to write; edge indexes are 64-bit throughout.
@@ -436,6 +437,451 @@ __global__ void __launch_bounds__(PF_THREADS) k_cl_link_relabel(u32 n, const u32
     if (v >= n) return;
     const u32 r = rep_of[v];
     if (r < n) rep_of[v] = label[r];
+}
+
+// ---- LZANI_CLUSTER_LEIDEN -------------------------------------------------------------------------------------------
+// Rounds of the statement in include/lzani.h, in signed 64-bit integers (q and g in units of 2^-20).  A level: m nodes with
+// sizes s, the entry list (lkey = a << 32 | b with a < b, lq), the partition P with SP[c] = the size of community c (a
+// community's id is its smallest member).  The table: S slots, a power of two >= 2 * the insertions, of tkey (CL_LD_FREE,
+// all ones, marks a free slot: no key, as every id is below 2^21) and tval; home pf_splitmix64(key) & (S - 1), the next
+// slot on a collision, wrapping at S, at most S probe steps: a sequence that runs out, or an id out of range, raises
+// ctl[CL_LD_ERR] and the run ends in LZANI_ERR_DEVICE.  No step waits for another thread.
+//   k_ld_dedup         once per run, per edge record: key lo << 32 | hi, 64-bit atomicMin of q into tval (all ones before)
+//   k_ld_compact       <false>, k_pf_scan, <true>: the occupied slots into an entry list, in the table's order (pf_compact)
+// A moving round (memsets: tkey all ones, tval 0 over the round's S; ownw 0):
+//   k_ld_move_insert   per entry, for both ends: tval += q at the key node << 32 | community of the other end (atomicCAS on
+//                      the key, 64-bit atomicAdd on the sum)
+//   k_ld_move_stay     per slot of a node's own community: ownw[v] = W(v, own), one plain store by the one such slot
+//   k_ld_move_node     per node: valown = val(v, own); bestd = the D of alone where that is an option and above 0, else 0;
+//                      bestid = none; and, v read as a community, cd = 0, cv = none
+//   k_ld_move_bestd    per slot of another community with D = val - valown > 0: atomicMax of D into bestd[v]
+//   k_ld_move_bestid   per such slot with D == bestd[v]: atomicMin of the community into bestid[v].  (bestd > 0 and bestid
+//                      none: alone won; a community that ties with alone wins, as alone comes last)
+//   k_ld_cand_max      per candidate (bestd > 0): atomicMax of D into cd of its own community and of its target
+//   k_ld_cand_min      per candidate: atomicMin of v into cv of those of the two where cd == D
+//   k_ld_decide        per node, plain stores by its own thread: v moves iff cv names it in every community it touches;
+//                      newlab[v] = the target (m + v for alone: no community has that label), else its own; the labels'
+//                      smallest members cleared; the movers summed into the round's counter
+//   k_ld_minm, k_ld_newid, k_ld_sizes   relabel: atomicMin of the smallest member per label; part[v] = that member, the
+//                      sizes cleared; the sizes (and member counts) summed, the communities counted
+// A refinement round inside P on R (SR, cntr: sizes and member counts of the R-communities; well: the phase's
+// well-connected nodes, from k_ld_wp and k_ld_well) has the same skeleton: k_ld_refine_insert (entries inside one
+// P-community between two R-communities; also ext[R] += q at both ends), k_ld_refine_node, k_ld_refine_bestd / _bestid (D + 1,
+// so that D = 0 counts), then k_ld_cand_max .. k_ld_sizes on R.  Aggregation: k_ld_agg_flags, k_pf_scan, k_ld_agg_nodes,
+// k_ld_agg_nodeof, k_ld_agg_insert (the contracted key, q summed), k_ld_compact.
+// Within a launch the table's words, bestd / bestid, cd / cv, ext, the smallest members, sizes and counts are touched through
+// the atomics named and through nothing else; every other word is read, or written by one thread, and crosses a kernel
+// boundary before another thread reads it.  Slot and entry indexes are 64-bit.
+typedef long long i64;
+constexpr u64 CL_LD_FREE = ~0ULL;
+enum { CL_LD_BATCH = 4 };                                // rounds launched between two reads of the control words
+enum { CL_LD_ERR = 0, CL_LD_MOVERS = 1, CL_LD_COMMS = 1 + CL_LD_BATCH, CL_LD_CTL = 1 + 2 * CL_LD_BATCH };
+
+struct ClLdTable { unsigned long long* key; unsigned long long* val; u64 S; };
+
+// The slot of `key`, claimed where it is new; t.S where the probe sequence runs out.
+__device__ __forceinline__ u64 cl_ld_slot(const ClLdTable& t, u64 key)
+{
+    const u64 mask = t.S - 1;
+    u64 slot = pf_splitmix64(key) & mask;
+    for (u64 step = 0; step < t.S; ++step, slot = (slot + 1) & mask) {
+        u64 cur = __hip_atomic_load(&t.key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == CL_LD_FREE) {
+            cur = atomicCAS(&t.key[slot], (unsigned long long)CL_LD_FREE, (unsigned long long)key);
+            if (cur == CL_LD_FREE) cur = key;
+        }
+        if (cur == key) return slot;
+    }
+    return t.S;
+}
+__device__ __forceinline__ void cl_ld_add(const ClLdTable& t, u64 key, i64 q, u32* __restrict__ ctl)
+{
+    const u64 slot = cl_ld_slot(t, key);
+    if (slot >= t.S) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }
+    atomicAdd(&t.val[slot], (unsigned long long)q);
+}
+// the sum of x over the wave, in every lane
+__device__ __forceinline__ i64 cl_ld_wave_sum(i64 x)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u32 lo = __shfl_xor((u32)(u64)x, d), hi = __shfl_xor((u32)((u64)x >> 32), d);
+        x += (i64)(((u64)hi << 32) | lo);
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_init(u32 n, u32* __restrict__ rep_of, u32* __restrict__ size)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    rep_of[v] = v; size[v] = 0;
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_dedup(const lzani_cluster_edge* __restrict__ edges, u64 count, u32 n, ClLdTable t, u32* __restrict__ ctl)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const ClEdge e = cl_edge(edges, i);
+    if (e.lo >= e.hi || e.hi >= n) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }   // (ids are checked where edges come in; a defect must not write astray)
+    const u64 slot = cl_ld_slot(t, ((u64)e.lo << 32) | e.hi);
+    if (slot >= t.S) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }
+    atomicMin(&t.val[slot], (unsigned long long)cluster_leiden_q(__longlong_as_double((long long)e.wbits)));
+}
+
+struct ClLdItem {
+    ClLdTable t;
+    unsigned long long* __restrict__ lkey;
+    i64* __restrict__ lq;
+    __device__ __forceinline__ bool kept(u64 i, u64& slot) const { slot = i; return t.key[i] != CL_LD_FREE; }
+    __device__ __forceinline__ void put(u64 at, u64 slot) const { lkey[at] = t.key[slot]; lq[at] = (i64)t.val[slot]; }
+};
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_ld_compact(ClLdTable t, u32* __restrict__ blkcnt, const u64* __restrict__ blkoff,
+                                                           unsigned long long* __restrict__ lkey, i64* __restrict__ lq)
+{
+    pf_compact<WRITE>(t.S, blkcnt, blkoff, ClLdItem{t, lkey, lq});
+}
+
+// The start of an iteration: the original graph with the last result as P.
+__global__ void __launch_bounds__(PF_THREADS) k_ld_level0(u32 n, const u32* __restrict__ rep_of, u32* __restrict__ s, u32* __restrict__ P, u32* __restrict__ node_of)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= n) return;
+    s[v] = 1; P[v] = rep_of[v]; node_of[v] = v;
+}
+
+// S[part[v]] += s[v] (s null: 1), cnt[part[v]] += 1 (cnt may be null); the communities (part[v] == v) into *comms (may be null)
+__global__ void __launch_bounds__(PF_THREADS) k_ld_sizes(u32 m, const u32* __restrict__ s, const u32* __restrict__ part, u32* __restrict__ S, u32* __restrict__ cnt,
+                                                         u32* __restrict__ comms)
+{
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 mine = 0;
+    if (v < m) {
+        const u32 c = part[v];
+        if (c < m) {
+            atomicAdd(&S[c], s ? s[v] : 1u);
+            if (cnt) atomicAdd(&cnt[c], 1u);
+        }
+        mine = c == v ? 1u : 0u;
+    }
+    block_sum(mine, &s_cnt);
+    if (comms && threadIdx.x == 0 && s_cnt) atomicAdd(comms, s_cnt);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_move_insert(const unsigned long long* __restrict__ lkey, const i64* __restrict__ lq, u64 count, u32 m,
+                                                               const u32* __restrict__ P, ClLdTable t, u32* __restrict__ ctl)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const u64 k = lkey[i];
+    const u32 a = (u32)(k >> 32), b = (u32)k;
+    if (a >= m || b >= m) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }
+    const i64 q = lq[i];
+    cl_ld_add(t, ((u64)a << 32) | P[b], q, ctl);
+    cl_ld_add(t, ((u64)b << 32) | P[a], q, ctl);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_move_stay(ClLdTable t, u32 m, const u32* __restrict__ P, i64* __restrict__ ownw)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= t.S) return;
+    const u64 key = t.key[i];
+    if (key == CL_LD_FREE) return;
+    const u32 v = (u32)(key >> 32);
+    if (v < m && P[v] == (u32)key) ownw[v] = (i64)t.val[i];
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_move_node(u32 m, i64 g, const u32* __restrict__ s, const u32* __restrict__ P, const u32* __restrict__ SP,
+                                                             const i64* __restrict__ ownw, i64* __restrict__ valown, unsigned long long* __restrict__ bestd,
+                                                             u32* __restrict__ bestid, unsigned long long* __restrict__ cd, u32* __restrict__ cv)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    const u32 own = P[v];
+    const i64 sv = s[v], So = own < m ? SP[own] : sv;
+    const i64 vo = ownw[v] - g * sv * (So - sv);
+    valown[v] = vo;
+    bestd[v] = (So != sv && vo < 0) ? (unsigned long long)(-vo) : 0ULL;       // alone: val 0, only for a node that is not alone
+    bestid[v] = CL_NONE;
+    cd[v] = 0; cv[v] = CL_NONE;
+}
+
+// Whether slot i is an option of its node in another community, and then the node, the community and D.
+__device__ __forceinline__ bool cl_ld_move_at(const ClLdTable& t, u64 i, u32 m, i64 g, const u32* __restrict__ s, const u32* __restrict__ P,
+                                              const u32* __restrict__ SP, const i64* __restrict__ valown, u32& v, u32& c, i64& D)
+{
+    const u64 key = t.key[i];
+    if (key == CL_LD_FREE) return false;
+    v = (u32)(key >> 32); c = (u32)key;
+    if (v >= m || c >= m || P[v] == c) return false;
+    D = (i64)t.val[i] - g * (i64)s[v] * (i64)SP[c] - valown[v];
+    return D > 0;
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_move_bestd(ClLdTable t, u32 m, i64 g, const u32* __restrict__ s, const u32* __restrict__ P,
+                                                              const u32* __restrict__ SP, const i64* __restrict__ valown, unsigned long long* __restrict__ bestd)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 v, c;
+    i64 D;
+    if (i >= t.S || !cl_ld_move_at(t, i, m, g, s, P, SP, valown, v, c, D)) return;
+    atomicMax(&bestd[v], (unsigned long long)D);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_move_bestid(ClLdTable t, u32 m, i64 g, const u32* __restrict__ s, const u32* __restrict__ P,
+                                                               const u32* __restrict__ SP, const i64* __restrict__ valown,
+                                                               const unsigned long long* __restrict__ bestd, u32* __restrict__ bestid)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 v, c;
+    i64 D;
+    if (i >= t.S || !cl_ld_move_at(t, i, m, g, s, P, SP, valown, v, c, D)) return;
+    if (bestd[v] == (unsigned long long)D) atomicMin(&bestid[v], c);
+}
+
+// part: P of a moving round, R of a refinement round.  A candidate has bestd > 0; its target is bestid (none: alone).
+__global__ void __launch_bounds__(PF_THREADS) k_ld_cand_max(u32 m, const u32* __restrict__ part, const unsigned long long* __restrict__ bestd,
+                                                            const u32* __restrict__ bestid, unsigned long long* __restrict__ cd)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    const u64 D = bestd[v];
+    if (!D) return;
+    const u32 own = part[v], to = bestid[v];
+    if (own < m) atomicMax(&cd[own], (unsigned long long)D);
+    if (to < m) atomicMax(&cd[to], (unsigned long long)D);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_cand_min(u32 m, const u32* __restrict__ part, const unsigned long long* __restrict__ bestd,
+                                                            const u32* __restrict__ bestid, const unsigned long long* __restrict__ cd, u32* __restrict__ cv)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    const u64 D = bestd[v];
+    if (!D) return;
+    const u32 own = part[v], to = bestid[v];
+    if (own < m && cd[own] == D) atomicMin(&cv[own], v);
+    if (to < m && cd[to] == D) atomicMin(&cv[to], v);
+}
+
+// minm has 2 * m words: the labels of the communities, and m + v for a node that goes alone
+__global__ void __launch_bounds__(PF_THREADS) k_ld_decide(u32 m, const u32* __restrict__ part, const unsigned long long* __restrict__ bestd,
+                                                          const u32* __restrict__ bestid, const u32* __restrict__ cv, u32* __restrict__ newlab,
+                                                          u32* __restrict__ minm, u32* __restrict__ movers)
+{
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 mine = 0;
+    if (v < m) {
+        const u32 own = part[v], to = bestid[v];
+        u32 lab = own;
+        if (bestd[v] && own < m && cv[own] == v && (to == CL_NONE || (to < m && cv[to] == v))) { lab = to == CL_NONE ? m + v : to; mine = 1; }
+        newlab[v] = lab;
+        minm[v] = CL_NONE; minm[m + v] = CL_NONE;
+    }
+    block_sum(mine, &s_cnt);
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(movers, s_cnt);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_minm(u32 m, const u32* __restrict__ newlab, u32* __restrict__ minm)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    const u32 lab = newlab[v];
+    if (lab < 2 * m) atomicMin(&minm[lab], v);
+}
+
+// part[v] = the smallest member of v's label; S[v] and cnt[v] (may be null) cleared for k_ld_sizes
+__global__ void __launch_bounds__(PF_THREADS) k_ld_newid(u32 m, const u32* __restrict__ newlab, const u32* __restrict__ minm, u32* __restrict__ part,
+                                                         u32* __restrict__ S, u32* __restrict__ cnt)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    const u32 lab = newlab[v];
+    part[v] = lab < 2 * m ? minm[lab] : CL_NONE;
+    S[v] = 0;
+    if (cnt) cnt[v] = 0;
+}
+
+// The start of a refinement: R = singletons, their sizes and counts; wp cleared for k_ld_wp.
+__global__ void __launch_bounds__(PF_THREADS) k_ld_refine_init(u32 m, const u32* __restrict__ s, u32* __restrict__ R, u32* __restrict__ SR, u32* __restrict__ cntr,
+                                                               i64* __restrict__ wp)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    R[v] = v; SR[v] = s[v]; cntr[v] = 1; wp[v] = 0;
+}
+// wp[v] = W(v, P(v))
+__global__ void __launch_bounds__(PF_THREADS) k_ld_wp(const unsigned long long* __restrict__ lkey, const i64* __restrict__ lq, u64 count, u32 m,
+                                                      const u32* __restrict__ P, i64* __restrict__ wp)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const u64 k = lkey[i];
+    const u32 a = (u32)(k >> 32), b = (u32)k;
+    if (a >= m || b >= m || P[a] != P[b]) return;
+    atomicAdd(reinterpret_cast<unsigned long long*>(&wp[a]), (unsigned long long)lq[i]);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&wp[b]), (unsigned long long)lq[i]);
+}
+__global__ void __launch_bounds__(PF_THREADS) k_ld_well(u32 m, i64 g, const u32* __restrict__ s, const u32* __restrict__ P, const u32* __restrict__ SP,
+                                                        const i64* __restrict__ wp, u32* __restrict__ well)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    const u32 own = P[v];
+    const i64 sv = s[v], So = own < m ? SP[own] : sv;
+    well[v] = wp[v] >= g * sv * (So - sv) ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_refine_insert(const unsigned long long* __restrict__ lkey, const i64* __restrict__ lq, u64 count, u32 m,
+                                                                 const u32* __restrict__ P, const u32* __restrict__ R, ClLdTable t, i64* __restrict__ ext,
+                                                                 u32* __restrict__ ctl)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const u64 k = lkey[i];
+    const u32 a = (u32)(k >> 32), b = (u32)k;
+    if (a >= m || b >= m) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }
+    if (P[a] != P[b]) return;
+    const u32 ra = R[a], rb = R[b];
+    if (ra == rb) return;
+    if (ra >= m || rb >= m) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }
+    const i64 q = lq[i];
+    cl_ld_add(t, ((u64)a << 32) | rb, q, ctl);
+    cl_ld_add(t, ((u64)b << 32) | ra, q, ctl);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&ext[ra]), (unsigned long long)q);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&ext[rb]), (unsigned long long)q);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_refine_node(u32 m, unsigned long long* __restrict__ bestd, u32* __restrict__ bestid,
+                                                               unsigned long long* __restrict__ cd, u32* __restrict__ cv)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m) return;
+    bestd[v] = 0; bestid[v] = CL_NONE; cd[v] = 0; cv[v] = CL_NONE;
+}
+
+struct ClLdRefine {
+    i64 g;
+    const u32* __restrict__ s;
+    const u32* __restrict__ P;
+    const u32* __restrict__ R;
+    const u32* __restrict__ SP;
+    const u32* __restrict__ SR;
+    const u32* __restrict__ cntr;
+    const u32* __restrict__ well;
+    const i64* __restrict__ ext;
+};
+// Whether slot i is a target of its node, and then the node, the R-community and D + 1.
+__device__ __forceinline__ bool cl_ld_refine_at(const ClLdTable& t, u64 i, u32 m, const ClLdRefine& r, u32& v, u32& c, u64& D1)
+{
+    const u64 key = t.key[i];
+    if (key == CL_LD_FREE) return false;
+    v = (u32)(key >> 32); c = (u32)key;
+    if (v >= m || c >= m) return false;
+    const u32 rv = r.R[v], pv = r.P[v];
+    if (rv >= m || pv >= m || r.cntr[rv] != 1 || !r.well[v]) return false;
+    const i64 W = (i64)t.val[i], Sc = r.SR[c];
+    if (W <= 0 || r.ext[c] < r.g * Sc * ((i64)r.SP[pv] - Sc)) return false;
+    const i64 D = W - r.g * (i64)r.s[v] * Sc;
+    D1 = (u64)(D + 1);
+    return D >= 0;
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_refine_bestd(ClLdTable t, u32 m, ClLdRefine r, unsigned long long* __restrict__ bestd)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 v, c;
+    u64 D1;
+    if (i >= t.S || !cl_ld_refine_at(t, i, m, r, v, c, D1)) return;
+    atomicMax(&bestd[v], (unsigned long long)D1);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_refine_bestid(ClLdTable t, u32 m, ClLdRefine r, const unsigned long long* __restrict__ bestd, u32* __restrict__ bestid)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    u32 v, c;
+    u64 D1;
+    if (i >= t.S || !cl_ld_refine_at(t, i, m, r, v, c, D1)) return;
+    if (bestd[v] == D1) atomicMin(&bestid[v], c);
+}
+
+__global__ void __launch_bounds__(PF_THREADS) k_ld_agg_flags(u32 m, const u32* __restrict__ R, u32* __restrict__ flag)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v < m) flag[v] = R[v] == v ? 1u : 0u;
+}
+// below[v] = the R-communities with a smallest member below v: the new node of the R-community v
+__global__ void __launch_bounds__(PF_THREADS) k_ld_agg_nodes(u32 m, const u32* __restrict__ R, const u32* __restrict__ P, const u32* __restrict__ SR,
+                                                             const u64* __restrict__ below, u32* __restrict__ s2, u32* __restrict__ P2)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (v >= m || R[v] != v) return;
+    const u32 i = (u32)below[v], p = P[v];
+    if (i >= m) return;
+    s2[i] = SR[v];
+    P2[i] = p < m ? (u32)below[p] : CL_NONE;                     // (P's smallest member is the smallest of its R-community)
+}
+__global__ void __launch_bounds__(PF_THREADS) k_ld_agg_nodeof(u32 n, u32 m, const u32* __restrict__ R, const u64* __restrict__ below, u32* __restrict__ node_of)
+{
+    const u32 x = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (x >= n) return;
+    const u32 v = node_of[x];
+    const u32 r = v < m ? R[v] : CL_NONE;
+    node_of[x] = r < m ? (u32)below[r] : CL_NONE;
+}
+__global__ void __launch_bounds__(PF_THREADS) k_ld_agg_insert(const unsigned long long* __restrict__ lkey, const i64* __restrict__ lq, u64 count, u32 m,
+                                                              const u32* __restrict__ R, const u64* __restrict__ below, ClLdTable t, u32* __restrict__ ctl)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const u64 k = lkey[i];
+    const u32 a = (u32)(k >> 32), b = (u32)k;
+    if (a >= m || b >= m) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }
+    const u32 ra = R[a], rb = R[b];
+    if (ra == rb) return;
+    if (ra >= m || rb >= m) { atomicOr(&ctl[CL_LD_ERR], 1u); return; }
+    const u32 x = (u32)below[ra], y = (u32)below[rb];
+    cl_ld_add(t, x < y ? ((u64)x << 32) | y : ((u64)y << 32) | x, lq[i], ctl);
+}
+
+// The end of an iteration: the label of an original genome is the community of its level node.
+__global__ void __launch_bounds__(PF_THREADS) k_ld_final(u32 n, u32 m, const u32* __restrict__ node_of, const u32* __restrict__ P, u32* __restrict__ newlab,
+                                                         u32* __restrict__ minm)
+{
+    const u32 x = blockIdx.x * PF_THREADS + threadIdx.x;
+    if (x >= n) return;
+    const u32 v = node_of[x];
+    newlab[x] = v < m ? P[v] : CL_NONE;
+    minm[x] = CL_NONE; minm[n + x] = CL_NONE;
+}
+
+// quality += the q of the level-0 entries inside one cluster; -= g * size * (size - 1) / 2 per cluster (cnt: k_ld_sizes)
+__global__ void __launch_bounds__(PF_THREADS) k_ld_quality_edges(const unsigned long long* __restrict__ lkey, const i64* __restrict__ lq, u64 count, u32 n,
+                                                                 const u32* __restrict__ rep_of, unsigned long long* __restrict__ quality)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    i64 mine = 0;
+    if (i < count) {
+        const u64 k = lkey[i];
+        const u32 a = (u32)(k >> 32), b = (u32)k;
+        if (a < n && b < n && rep_of[a] == rep_of[b]) mine = lq[i];
+    }
+    mine = cl_ld_wave_sum(mine);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(quality, (unsigned long long)mine);
+}
+__global__ void __launch_bounds__(PF_THREADS) k_ld_quality_nodes(u32 n, i64 g, const u32* __restrict__ cnt, unsigned long long* __restrict__ quality)
+{
+    const u32 v = blockIdx.x * PF_THREADS + threadIdx.x;
+    i64 mine = 0;
+    if (v < n) { const i64 z = cnt[v]; mine = g * (z * (z - 1) / 2); }
+    mine = cl_ld_wave_sum(mine);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(quality, (unsigned long long)(-mine));
 }
 
 }  // namespace lzani

@@ -553,6 +553,19 @@ int lzani_group_get_cluster_link_info(const lzani_group* g, lzani_cluster_link_i
     return lzani_get_cluster_link_info(g->ctx[0], info);
 }
 
+int lzani_group_set_cluster_leiden(lzani_group* g, double resolution, int iterations)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_set_cluster_leiden(g->ctx[0], resolution, iterations);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_get_cluster_leiden_info(const lzani_group* g, lzani_cluster_leiden_info* info)
+{
+    if (!g) return LZANI_ERR_ARG;
+    return lzani_get_cluster_leiden_info(g->ctx[0], info);
+}
+
 int lzani_group_set_genome_memory(lzani_group* g, uint64_t bytes)
 {
     if (!g) return LZANI_ERR_ARG;

@@ -42,6 +42,9 @@ struct Params {
     string cluster_arg, cluster_out, cluster_measure_arg;  // --cluster, --cluster-out, --cluster-measure as given
     bool cluster = false, cluster_reps = false;             // --cluster given; --cluster-representatives
     int cluster_algo = LZANI_CLUSTER_SINGLE, cluster_measure = LZANI_CLUSTER_TANI;
+    string leiden_resolution_arg, leiden_iterations_arg;    // --cluster-leiden-resolution, --cluster-leiden-iterations as given
+    double leiden_resolution = 0.7;                         // ... and read: Clusty's defaults
+    int leiden_iterations = 2;
 };
 
 static Params P;
@@ -122,11 +125,14 @@ static void usage()
          << "      --cluster <algorithm>      - all2all: cluster the pairs that --out-filter keeps; one of single (connected components),\n"
          << "                                   greedy-first (first representative, as CD-HIT), greedy-best (most similar representative, as UCLUST),\n"
          << "                                   set-cover (the sequence with the most unassigned neighbours first, as MMseqs2's greedy set cover),\n"
-         << "                                   complete-linkage (every two members of a cluster are a kept pair; the most similar clusters merge first)\n"
+         << "                                   complete-linkage (every two members of a cluster are a kept pair; the most similar clusters merge first),\n"
+         << "                                   leiden-cpm (deterministic Leiden with the constant Potts model: for genus- and family-level groupings)\n"
          << "      --cluster-out <file_name>  - output file of --cluster: one line per sequence, its id and its cluster number\n"
-         << "      --cluster-measure <type>   - the similarity greedy-best and complete-linkage compare: tani, gani or ani (default: tani); accepted and without\n"
+         << "      --cluster-measure <type>   - the similarity greedy-best and complete-linkage compare and leiden-cpm sums: tani, gani or ani (default: tani); accepted and without\n"
          << "                                   effect for single, greedy-first and set-cover\n"
          << "      --cluster-representatives  - write the representative's id instead of the cluster number\n"
+         << "      --cluster-leiden-resolution <float> - leiden-cpm: the resolution, 0 .. 1 (default: 0.7); larger values give smaller clusters\n"
+         << "      --cluster-leiden-iterations <int>   - leiden-cpm: the iterations, 1 .. 16 (default: 2)\n"
          << "Options - LZ-parsing-related:\n"
          << "  -a, --mal <int>                - min. anchor length (default: 11)\n"
          << "  -s, --msl <int>                - min. seed length (default: 7)\n"
@@ -234,6 +240,8 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--cluster-out" && has(1)) { P.cluster_out = argv[i + 1]; i += 2; }
         else if (par == "--cluster-measure" && has(1)) { P.cluster_measure_arg = argv[i + 1]; i += 2; }
         else if (par == "--cluster-representatives") { P.cluster_reps = true; i += 1; }
+        else if (par == "--cluster-leiden-resolution" && has(1)) { P.leiden_resolution_arg = argv[i + 1]; i += 2; }
+        else if (par == "--cluster-leiden-iterations" && has(1)) { P.leiden_iterations_arg = argv[i + 1]; i += 2; }
         else { cerr << "Unknown parameter: " << argv[i] << endl; usage(); exit(1); }
     }
     // query2ref: what it does not take, and what only it takes
@@ -264,12 +272,33 @@ static bool parse_params(int argc, char** argv)
         cerr << "--cluster-out, --cluster-measure and --cluster-representatives belong to --cluster" << endl;
         exit(1);
     }
+    if ((!P.leiden_resolution_arg.empty() || !P.leiden_iterations_arg.empty()) && P.cluster_arg != "leiden-cpm") {
+        cerr << "--cluster-leiden-resolution and --cluster-leiden-iterations belong to --cluster leiden-cpm" << endl;
+        exit(1);
+    }
+    if (!P.leiden_resolution_arg.empty()) {
+        char* end = nullptr;
+        P.leiden_resolution = strtod(P.leiden_resolution_arg.c_str(), &end);
+        if (end == P.leiden_resolution_arg.c_str() || *end || !(P.leiden_resolution >= 0 && P.leiden_resolution <= 1)) {
+            cerr << "Unsupported value: --cluster-leiden-resolution " << P.leiden_resolution_arg << " (resolutions 0 .. 1 are supported)" << endl;
+            exit(1);
+        }
+    }
+    if (!P.leiden_iterations_arg.empty()) {
+        char* end = nullptr;
+        const long it = strtol(P.leiden_iterations_arg.c_str(), &end, 10);
+        if (end == P.leiden_iterations_arg.c_str() || *end || it < 1 || it > 16) {
+            cerr << "Unsupported value: --cluster-leiden-iterations " << P.leiden_iterations_arg << " (1 .. 16 iterations are supported)" << endl;
+            exit(1);
+        }
+        P.leiden_iterations = (int)it;
+    }
     if (P.cluster) {
         static const map<string, int> algos = {{"single", LZANI_CLUSTER_SINGLE}, {"greedy-first", LZANI_CLUSTER_GREEDY_FIRST}, {"greedy-best", LZANI_CLUSTER_GREEDY_BEST},
-                                               {"set-cover", LZANI_CLUSTER_SET_COVER}, {"complete-linkage", LZANI_CLUSTER_COMPLETE}};
+                                               {"set-cover", LZANI_CLUSTER_SET_COVER}, {"complete-linkage", LZANI_CLUSTER_COMPLETE}, {"leiden-cpm", LZANI_CLUSTER_LEIDEN}};
         static const map<string, int> measures = {{"tani", LZANI_CLUSTER_TANI}, {"gani", LZANI_CLUSTER_GANI}, {"ani", LZANI_CLUSTER_ANI}};
         const auto a = algos.find(P.cluster_arg);
-        if (a == algos.end()) { cerr << "Unknown value for --cluster: " << P.cluster_arg << " (single, greedy-first, greedy-best, set-cover or complete-linkage)" << endl; exit(1); }
+        if (a == algos.end()) { cerr << "Unknown value for --cluster: " << P.cluster_arg << " (single, greedy-first, greedy-best, set-cover, complete-linkage or leiden-cpm)" << endl; exit(1); }
         P.cluster_algo = a->second;
         const auto m = measures.find(P.cluster_measure_arg.empty() ? "tani" : P.cluster_measure_arg);
         if (m == measures.end()) { cerr << "Unknown value for --cluster-measure: " << P.cluster_measure_arg << " (tani, gani or ani)" << endl; exit(1); }

@@ -13,7 +13,7 @@
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
 // --out-filter on a two-TSV output is applied on the device (lzani_group_run_rows_kept): only the pairs of which a line
 // passes come back, and the table of all pairs is never made; LZANI_OUT_FILTER=host keeps the filter on the host.
-// --cluster <single|greedy-first|greedy-best|set-cover|complete-linkage> clusters the pairs the output filter keeps (include/lzani.h,
+// --cluster <single|greedy-first|greedy-best|set-cover|complete-linkage|leiden-cpm> clusters the pairs the output filter keeps (include/lzani.h,
 // "clustering the kept pairs") and writes one line per genome to --cluster-out: on the device where the filter is applied there
 // (lzani_group_cluster_*), else by the sequential statement of lzani_cluster_plan.h over the emitter's own lines.
 // This file keeps the raw seams, the stage sequence and main; cli.h holds the command line, engine.h the binding of the
@@ -138,7 +138,7 @@ static bool run_all2all()
     else {
         if (!engine_loaded && !E.load()) return false;
         // --out-filter on the device where it applies to the TSV, the library has the stage and the filter's lists are sets
-        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt) && (!P.cluster || E.has_cluster());
+        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt) && (!P.cluster || (P.cluster_algo == LZANI_CLUSTER_LEIDEN ? E.has_leiden() : E.has_cluster()));
         clustered = kept && P.cluster;
         if (tiled) {
             if (P.verbosity >= 1) cerr << "Storing results (row blocks, while the matching goes on)" << endl;

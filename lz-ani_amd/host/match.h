@@ -245,6 +245,7 @@ static bool cluster_begin(const Group& G, const vector<uint32_t>& rlen)
 static bool cluster_finish(const Group& G, const vector<Genome>& g)
 {
     vector<uint32_t> rep_of(g.size()), cluster_of(g.size());
+    if (P.cluster_algo == LZANI_CLUSTER_LEIDEN && G.E.group_set_cluster_leiden(G, P.leiden_resolution, P.leiden_iterations) != LZANI_OK) return clustering_failed(G);
     if (G.E.group_cluster_run(G, P.cluster_algo, nullptr) != LZANI_OK || G.E.group_cluster_fetch(G, rep_of.data(), cluster_of.data()) != LZANI_OK)
         return clustering_failed(G);
     lzani_cluster_info ci;
@@ -259,6 +260,11 @@ static bool cluster_finish(const Group& G, const vector<Genome>& g)
     if (P.verbosity >= 2 && G.E.group_get_cluster_link_info && G.E.group_get_cluster_link_info(G, &lk) == LZANI_OK)
         cerr << "complete linkage: " << lk.distinct_edges << " distinct pairs (" << lk.duplicate_edges << " given again), " << lk.merges << " merges, table of "
              << lk.table_slots << " slots, first insert " << lk.dedup_ms << " ms, rounds " << lk.rounds_ms << " ms, workspace " << lk.workspace_bytes << " bytes\n";
+    lzani_cluster_leiden_info ld;
+    if (P.verbosity >= 2 && G.E.group_get_cluster_leiden_info && G.E.group_get_cluster_leiden_info(G, &ld) == LZANI_OK)
+        cerr << "Leiden: " << ld.distinct_edges << " distinct pairs (" << ld.duplicate_edges << " given again), " << ld.iterations << " iterations, " << ld.levels
+             << " levels, " << ld.move_rounds << " moving and " << ld.refine_rounds << " refinement rounds, " << ld.moves << " moves, " << ld.merges
+             << " merges, quality " << ld.quality << " / 2^20 (distinct " << ld.dedup_ms << " ms, rounds " << ld.rounds_ms << " ms)\n";
     return write_clusters(g, rep_of, cluster_of);
 }
 
@@ -274,7 +280,15 @@ static bool cluster_on_host(const vector<Genome>& g, const PairTable& T, const E
         });
     vector<uint32_t> rep_of(g.size()), cluster_of(g.size());
     uint32_t k = 0;
-    if (!g.empty() && lzani::cluster_host((uint32_t)g.size(), edges.data(), edges.size(), P.cluster_algo, rep_of.data(), cluster_of.data(), &k) != LZANI_OK) {
+    auto run = [&]() {
+        if (P.cluster_algo != LZANI_CLUSTER_LEIDEN)
+            return lzani::cluster_host((uint32_t)g.size(), edges.data(), edges.size(), P.cluster_algo, rep_of.data(), cluster_of.data(), &k);
+        // Leiden with the resolution and the iterations asked for (cluster_host runs the defaults)
+        if (int rc = lzani::cluster_leiden_host((uint32_t)g.size(), edges.data(), edges.size(), P.leiden_resolution, P.leiden_iterations, rep_of.data(), nullptr)) return rc;
+        k = lzani::cluster_number((uint32_t)g.size(), rep_of.data(), cluster_of.data());
+        return (int)LZANI_OK;
+    };
+    if (!g.empty() && run() != LZANI_OK) {
         cerr << "Clustering failed" << endl;
         return false;
     }

@@ -46,7 +46,9 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_debug_cluster_add_edges", "lzani_cluster_run", "lzani_cluster_fetch", "lzani_get_cluster_info",
            "lzani_group_cluster_begin", "lzani_group_cluster_add_kept", "lzani_group_cluster_run", "lzani_group_cluster_fetch",
            "lzani_group_get_cluster_info", "lzani_get_cluster_cover_info", "lzani_group_get_cluster_cover_info",
-           "lzani_get_cluster_link_info", "lzani_group_get_cluster_link_info")
+           "lzani_get_cluster_link_info", "lzani_group_get_cluster_link_info", "lzani_cluster_leiden_host",
+           "lzani_debug_cluster_leiden_host_cap", "lzani_set_cluster_leiden", "lzani_group_set_cluster_leiden",
+           "lzani_get_cluster_leiden_info", "lzani_group_get_cluster_leiden_info")
 
 
 class LzaniError(RuntimeError):
@@ -185,11 +187,18 @@ class ClusterLinkInfo(C.Structure):
                 ("workspace_bytes", C.c_uint64), ("dedup_ms", C.c_double), ("rounds_ms", C.c_double)]
 
 
+class ClusterLeidenInfo(C.Structure):
+    _fields_ = [("iterations", C.c_uint64), ("levels", C.c_uint64), ("move_rounds", C.c_uint64), ("refine_rounds", C.c_uint64),
+                ("moves", C.c_uint64), ("merges", C.c_uint64), ("quality", C.c_int64), ("resolution_q", C.c_uint64),
+                ("distinct_edges", C.c_uint64), ("duplicate_edges", C.c_uint64), ("table_slots", C.c_uint64), ("workspace_bytes", C.c_uint64),
+                ("dedup_ms", C.c_double), ("rounds_ms", C.c_double)]
+
+
 # lzani_cluster_edge as a numpy record: a < b (either order is taken), w >= 0
 EDGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("w", np.float64)])
 assert EDGE_DTYPE.itemsize == 16
 CLUSTER_ALGOS = {"single": 0, "greedy-first": 1, "greedy-best": 2, "set-cover": 4,     # LZANI_CLUSTER_SINGLE ... (3 and 5 are no algorithms)
-                 "complete-linkage": 6}
+                 "complete-linkage": 6, "leiden-cpm": 8}                  # (7 is none either; "leiden" alone is no name)
 CLUSTER_MEASURES = {"tani": 0, "gani": 1, "ani": 2}                       # LZANI_CLUSTER_TANI ...
 
 
@@ -232,6 +241,24 @@ def cluster_host(n, edges, algo):
     if rc != 0:
         raise LzaniError(f"lzani_cluster_host: {ERRORS.get(rc, rc)}")
     return rep, cl, int(k.value)
+
+
+def cluster_leiden_host(n, edges, resolution=0.7, iterations=2, cap=None):
+    """lzani_cluster_leiden_host (no GPU needed): (rep_of uint32[n], cluster_of uint32[n], info dict) of EDGE_DTYPE edges.
+    cap = (cap_mul, cap_add): the test hook with a phase's cap of rounds at cap_mul * n_level + cap_add."""
+    lib = load_library()
+    e = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
+    rep, cl = np.zeros(int(n), dtype=np.uint32), np.zeros(int(n), dtype=np.uint32)
+    o = ClusterLeidenInfo()
+    head = (C.c_uint32(int(n)), _ptr(e) if len(e) else None, C.c_uint64(len(e)), C.c_double(float(resolution)), C.c_int(int(iterations)))
+    tail = (_ptr(rep) if n else None, _ptr(cl) if n else None, C.byref(o))
+    if cap is None:
+        rc = lib.lzani_cluster_leiden_host(*head, *tail)
+    else:
+        rc = lib.lzani_debug_cluster_leiden_host_cap(*head, C.c_uint64(int(cap[0])), C.c_uint64(int(cap[1])), *tail)
+    if rc != 0:
+        raise LzaniError(f"lzani_cluster_leiden_host: {ERRORS.get(rc, rc)}")
+    return rep, cl, {k: getattr(o, k) for k, _ in ClusterLeidenInfo._fields_}
 
 
 PF_COUNTING = {"auto": 0, "dense": 1, "sparse": 2}   # LZANI_PF_COUNTING_*
@@ -350,6 +377,11 @@ def load_library():
             getattr(lib, pre + "get_cluster_info").argtypes = [C.c_void_p, C.c_void_p]
             getattr(lib, pre + "get_cluster_cover_info").argtypes = [C.c_void_p, C.c_void_p]
             getattr(lib, pre + "get_cluster_link_info").argtypes = [C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "get_cluster_leiden_info").argtypes = [C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "set_cluster_leiden").argtypes = [C.c_void_p, C.c_double, C.c_int]
+        lib.lzani_cluster_leiden_host.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lzani_debug_cluster_leiden_host_cap.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_int, C.c_uint64, C.c_uint64,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lzani_debug_cluster_add_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         _lib = lib
     return _lib
@@ -537,7 +569,8 @@ class _ClusterCalls:
         return int(tot.value)
 
     def cluster_run(self, algo):
-        """Runs "single", "greedy-first", "greedy-best", "set-cover" or "complete-linkage" on the edges there are; returns the number of clusters."""
+        """Runs "single", "greedy-first", "greedy-best", "set-cover", "complete-linkage" or "leiden-cpm" on the edges there are; returns the number
+        of clusters."""
         k = C.c_uint64(0)
         self._check(getattr(self.lib, self._pre + "cluster_run")(self.h, _algo(algo), C.byref(k)), self._pre + "cluster_run")
         return int(k.value)
@@ -567,6 +600,18 @@ class _ClusterCalls:
         o = ClusterLinkInfo()
         self._check(getattr(self.lib, self._pre + "get_cluster_link_info")(self.h, C.byref(o)), self._pre + "get_cluster_link_info")
         return {k: getattr(o, k) for k, _ in ClusterLinkInfo._fields_}
+
+    def set_cluster_leiden(self, resolution=0.7, iterations=2):
+        """The parameters of the later "leiden-cpm" runs: resolution in [0, 1], iterations in 1..16."""
+        self._check(getattr(self.lib, self._pre + "set_cluster_leiden")(self.h, C.c_double(float(resolution)), C.c_int(int(iterations))),
+                    self._pre + "set_cluster_leiden")
+
+    def cluster_leiden_info(self):
+        """iterations, levels, move_rounds, refine_rounds, moves, merges, quality, resolution_q, distinct_edges, duplicate_edges,
+        table_slots, workspace_bytes, dedup_ms, rounds_ms of the last run, which was one of "leiden-cpm"."""
+        o = ClusterLeidenInfo()
+        self._check(getattr(self.lib, self._pre + "get_cluster_leiden_info")(self.h, C.byref(o)), self._pre + "get_cluster_leiden_info")
+        return {k: getattr(o, k) for k, _ in ClusterLeidenInfo._fields_}
 
 
 class Group(_ClusterCalls):
