@@ -402,6 +402,59 @@ int lzani_get_prefilter_sparse_info(const lzani_ctx *ctx, lzani_prefilter_sparse
  * two >= 2), or LZANI_ERR_NOMEM for a row above slots / 2. */
 int lzani_plan_sparse_tiles(uint32_t n_rows, const uint64_t *row_pairs, uint64_t slots, uint32_t *tile_r0, uint32_t *attempts);
 
+/* Limit: every genome keeps its N best pairs (what Vclust's prefilter calls --max-seqs).  A post-stage over the context's
+ * current prefilter result R, whichever entry point and whichever counting form made it: R is the kept pairs a < b with
+ * shared(a, b), and kmers_of.  The stage bounds the pairs that go on to the alignment at limiting genomes * N, whatever
+ * the sizes of the families are.
+ *   score      q(a, b) = floor(shared(a, b) * (2^32 - 1) / min(|K(a)|, |K(b)|)) in unsigned 64-bit arithmetic (shared <=
+ *              min < 2^32: the product fits; 1 <= q <= 2^32 - 1).  An integer score of this project's own, like Leiden's
+ *              2^-20 units: no claim of equality with another program's ordering
+ *   limiting   all-pairs result: every genome.  Cross result: the queries only (ids >= n_ref) -- a reference may be the
+ *              best hit of any number of queries
+ *   list       of genome g: all its partners h in R, whichever of the two has the smaller id, ordered by q descending,
+ *              ties to the smaller h; rank_g(h) = h's position in it, from 0
+ *   survival   pair (a, b) survives iff rank_a(b) < N for a limiting a, or rank_b(a) < N for a limiting b.  All-pairs: the
+ *              union -- one endpoint that counts the other among its N best is enough.  Cross: the query's rank alone
+ *   result     R restricted to the survivors: the same CSR form (row a, ids ascending), shared and kmers_of unchanged,
+ *              lzani_prefilter_info.entries the new count and the other fields of that struct as they were.
+ *              lzani_prefilter_fetch then reads the limited result, which lasts as long as any prefilter result does
+ * What the definition gives:
+ *   - N >= the largest degree changes nothing
+ *   - applying the stage twice with the same N equals applying it once (a survivor's rank can only fall when entries ahead
+ *     of it go)
+ *   - every limiting genome of degree d keeps at least min(d, N) pairs (more where a partner's list keeps others)
+ *   - the limited cross result is NOT the limited all-pairs result restricted to the cross pairs: the references do not
+ *     limit, and a query ranks its references only
+ * The device form: one key ~q << 32 | e per entry e in CSR order, sorted by its high half (stably: equal scores keep CSR
+ * order, which for a fixed genome is ascending partner id); one directed key g << 32 | i per limiting endpoint g of sorted
+ * position i, sorted stably by g, which leaves every genome's list in order; the first N of every list mark their entry;
+ * the marked entries are compacted row by row.  Exact, independent of the schedule (the only atomics are integer adds),
+ * O(entries) memory, no work quadratic in a degree.
+ * LZANI_ERR_STATE without a prefilter result; LZANI_ERR_ARG for N == 0 and for a result of more than 2^31 - 9 entries
+ * (twice as many keys must fit one sort call of 2^32 - 17).  The workspace is allocated whole before the result is
+ * touched: LZANI_ERR_NOMEM or a device error leaves the unlimited result in place and readable. */
+typedef struct lzani_prefilter_limit_info {
+    uint32_t max_per_genome, limiting;   /* N; limiting genomes                               */
+    uint64_t entries_in, entries_out;
+    uint64_t genomes_cut;                /* limiting genomes whose list was longer than N     */
+    uint64_t workspace_bytes;            /* as allocated                                      */
+    double   limit_ms;                   /* HIP events on the context's stream                */
+} lzani_prefilter_limit_info;
+int lzani_prefilter_limit(lzani_ctx *ctx, uint32_t max_per_genome, uint64_t *n_entries);
+/* LZANI_ERR_STATE without a prefilter result, or where the current one was never limited. */
+int lzani_get_prefilter_limit_info(const lzani_ctx *ctx, lzani_prefilter_limit_info *info);
+/* The rule as a pure host function (no GPU): keep[e] = 1 / 0 per CSR entry; n_ref 0 = all-pairs.  LZANI_ERR_ARG for
+ * n == 0, N == 0, n_ref >= n, NULL arrays, offsets that do not start at 0 or descend, more than 2^31 - 9 entries, ids that
+ * do not ascend strictly inside a row or are <= the row, an id >= n, shared == 0, shared > min(|K|), and in the cross form
+ * an entry that is not a pair a < n_ref <= b. */
+int lzani_prefilter_limit_host(uint32_t n, uint32_t n_ref, const uint32_t *kmers_of, const uint64_t *row_off,
+                               const uint32_t *ids, const uint32_t *shared, uint32_t max_per_genome, uint8_t *keep);
+/* Test hook, in the manner of lzani_debug_filter_results and lzani_debug_cluster_add_edges: installs a made-up prefilter
+ * result (uploaded here) in place of the context's, so that the stage runs on chosen integers; n_ref 0 = all-pairs.  The
+ * arrays are checked as lzani_prefilter_limit_host checks them (LZANI_ERR_ARG); an earlier result is dropped first. */
+int lzani_debug_prefilter_set(lzani_ctx *ctx, uint32_t n, uint32_t n_ref, const uint32_t *kmers_of,
+                              const uint64_t *row_off, const uint32_t *ids, const uint32_t *shared);
+
 /* ---- Output filter on the device: only the pairs that pass come back -------------------------------------------
  * The reference's --out-filter drops a TSV line when one of its five ratios is below its minimum (lz_matcher.cpp:437-462).
  * A line needs the pair in both directions, which a finished run holds side by side in device memory; this stage reads

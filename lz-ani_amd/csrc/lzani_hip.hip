@@ -242,6 +242,8 @@ struct Prefilter {
     lzani_prefilter_stream_info sinfo{};
     lzani_prefilter_pass_info pinfo{};
     lzani_prefilter_sparse_info spinfo{}; // all zero unless the pair table counted
+    bool limited = false;                 // lzani_prefilter_limit cut the result: linfo holds, and one tile covers all rows
+    lzani_prefilter_limit_info linfo{};
     std::vector<u32> bin_lo;              // the pass plan: pass p holds the bins bin_lo[p] .. bin_lo[p + 1]
     DevMem<u32> kmers_of;                 // |K(g)|
     std::vector<u64> row_off;             // CSR of the kept pairs (n + 1)
@@ -854,6 +856,7 @@ int run_rows_any(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_of
 }  // namespace
 
 #include "lzani_prefilter.h"
+#include "lzani_prefilter_limit.h"
 #include "lzani_kept.h"
 #include "lzani_cluster.h"
 

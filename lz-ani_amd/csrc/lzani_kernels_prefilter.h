@@ -24,6 +24,8 @@
 //   k_pf_rows     a wave per matrix row: the kept entries counted, then written in ascending b
 //   k_pf_sparse_kept / _fetch / _rowoff  the table's kept keys, and behind their sort the ids and counts of the sorted keys
 //                 and where every row of the tile begins
+//   k_pfl_*       the limit stage over a finished result (lzani_prefilter_limit.h): an entry's row, the score keys, the
+//                 directed keys and degrees, the survivor marks, the genomes cut, and the surviving entries of every row
 // No kernel waits for another block.  The sorts between them are lzani_sort_keys (lzani_sort.hip).
 #pragma once
 #include "lzani_block.h"
@@ -522,6 +524,102 @@ __global__ void __launch_bounds__(PF_THREADS) k_pf_sparse_rowoff(const unsigned 
         if (sorted[mid] < key) lo = mid + 1; else hi = mid;
     }
     rowoff[r] = lo;
+}
+
+// ---- The limit stage (lzani_prefilter_limit.h): every limiting genome keeps its N best pairs.  E entries in CSR order
+// (rowoff[n + 1], ids, shared), e < 2^31; no kernel waits for another block, and the only atomics are integer adds whose
+// order cannot show.
+
+// A wave per row a: row_of[e] = a for the row's entries, so that the passes over the entries find an entry's row at its
+// own index.
+__global__ void __launch_bounds__(PF_THREADS) k_pfl_rowof(const u64* __restrict__ rowoff, u32 n, u32* __restrict__ row_of)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 a = ((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6;
+    if (a >= (u64)n) return;
+    const u64 e1 = rowoff[a + 1];
+    for (u64 e = rowoff[a] + lane; e < e1; e += 64) row_of[e] = (u32)a;
+}
+
+// A thread per entry e, in CSR order: key[e] = ~q << 32 | e with q = pf_limit_score of the entry's pair -- ascending keys
+// are descending scores.
+__global__ void __launch_bounds__(PF_THREADS) k_pfl_keys(const u32* __restrict__ row_of, const u32* __restrict__ ids, const u32* __restrict__ shared, u64 E,
+                                                         const u32* __restrict__ kmers_of, unsigned long long* __restrict__ key)
+{
+    const u64 e = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (e >= E) return;
+    const u32 q = pf_limit_score(shared[e], kmers_of[row_of[e]], kmers_of[ids[e]]);
+    key[e] = ((u64)(~q) << 32) | e;
+}
+
+// A thread per position i of the keys sorted by score: the directed keys  g << 32 | i  of the entry's limiting endpoints
+// -- both (at 2 i and 2 i + 1), or (CROSS) the query alone (at i) -- and deg[g] += 1 for each.
+template <bool CROSS>
+__global__ void __launch_bounds__(PF_THREADS) k_pfl_directed(const unsigned long long* __restrict__ sorted, u64 E, const u32* __restrict__ row_of,
+                                                             const u32* __restrict__ ids, unsigned long long* __restrict__ dkey, u32* __restrict__ deg)
+{
+    const u64 i = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (i >= E) return;
+    const u32 e = (u32)sorted[i];
+    const u32 b = ids[e];
+    if (CROSS) dkey[i] = ((u64)b << 32) | i;
+    else {
+        const u32 a = row_of[e];
+        reinterpret_cast<ulonglong2*>(dkey)[i] = make_ulonglong2(((u64)a << 32) | i, ((u64)b << 32) | i);
+        atomicAdd(&deg[a], 1u);
+    }
+    atomicAdd(&deg[b], 1u);
+}
+
+// A thread per directed key, sorted by genome (a genome's keys then ascend in i: its list in order).  start[g]: where the
+// keys of g begin.  The first N of a genome mark their entry: survive[e] = 1, a plain store of the same value by whoever
+// gets there.
+__global__ void __launch_bounds__(PF_THREADS) k_pfl_mark(const unsigned long long* __restrict__ dsorted, u64 Dk, const u64* __restrict__ start, u32 max_per_genome,
+                                                         const unsigned long long* __restrict__ sorted, unsigned char* __restrict__ survive)
+{
+    const u64 p = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    if (p >= Dk) return;
+    const u64 key = dsorted[p];
+    if (p - start[(u32)(key >> 32)] < (u64)max_per_genome) survive[(u32)sorted[(u32)key]] = 1;
+}
+
+// A thread per genome: *cut += the genomes whose list is longer than N (one atomic add per block that has one).
+__global__ void __launch_bounds__(PF_THREADS) k_pfl_cut(const u32* __restrict__ deg, u32 n, u32 max_per_genome, u32* __restrict__ cut)
+{
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const u64 g = (u64)blockIdx.x * PF_THREADS + threadIdx.x;
+    block_sum(g < (u64)n && deg[g] > max_per_genome ? 1u : 0u, &s_cnt);
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(cut, s_cnt);
+}
+
+// k_pf_rows over the entries instead of the matrix: a wave per row a, its surviving entries counted (rowcnt[a]) or written
+// from out_off[a] on, in the row's order.
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_pfl_rows(const u64* __restrict__ rowoff, u32 n, const unsigned char* __restrict__ survive,
+                                                         const u32* __restrict__ ids, const u32* __restrict__ shared, u32* __restrict__ rowcnt,
+                                                         const u64* __restrict__ out_off, u32* __restrict__ out_ids, u32* __restrict__ out_shared)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 a = ((u64)blockIdx.x * PF_THREADS + threadIdx.x) >> 6;
+    if (a >= (u64)n) return;
+    const u64 e1 = rowoff[a + 1];
+    u64 base = WRITE ? out_off[a] : 0;
+    u32 cnt = 0;
+    for (u64 e0 = rowoff[a]; e0 < e1; e0 += 64) {
+        const u64 e = e0 + lane;
+        const bool ok = e < e1 && survive[e] != 0;
+        const u64 mask = __builtin_amdgcn_ballot_w64(ok);
+        if (WRITE && ok) {
+            const u64 at = base + (u64)__popcll(mask & ((1ULL << lane) - 1ULL));
+            out_ids[at] = ids[e];
+            out_shared[at] = shared[e];
+        }
+        base += (u64)__popcll(mask);
+        cnt += (u32)__popcll(mask);
+    }
+    if (!WRITE && lane == 0) rowcnt[a] = cnt;
 }
 
 }  // namespace lzani

@@ -28,6 +28,14 @@ LZ_HD bool pf_keep(u64 canon, u64 sample_max) { return pf_splitmix64(canon) <= s
 enum { PF_BINS = 4096 };
 LZ_HD u32 pf_bin(u64 canon) { return (u32)(pf_splitmix64(canon) >> 20) & (u32)(PF_BINS - 1); }
 
+// The limit stage's score of a kept pair (include/lzani.h: lzani_prefilter_limit): floor(shared * (2^32 - 1) / min(|K(a)|,
+// |K(b)|)) in unsigned 64-bit arithmetic; 1 <= shared <= min, so the product fits and the score is 1 .. 2^32 - 1.
+LZ_HD u32 pf_limit_score(u32 shared, u32 ka, u32 kb)
+{
+    const u64 m = ka < kb ? ka : kb;
+    return m ? (u32)((u64)shared * 0xFFFFFFFFull / m) : 0u;
+}
+
 // ---- windows from raw symbol codes (the streamed prefilter, lzani_prefilter_codes): no packed text, no second strand
 
 // The packed value of a window's reverse complement from the window's own packed value (k <= 32): every 2-bit group

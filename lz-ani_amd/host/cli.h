@@ -39,6 +39,8 @@ struct Params {
     double flt_fraction = 1;
     string flt_counting_arg;                                // --flt-kmers-counting as given; checked after the flags are read
     int flt_counting = LZANI_PF_COUNTING_AUTO;
+    string flt_max_seqs_arg;                                // --flt-kmers-max-seqs as given; checked after the flags are read
+    uint32_t flt_max_seqs = 0;                              // 0: no limit
     string cluster_arg, cluster_out, cluster_measure_arg;  // --cluster, --cluster-out, --cluster-measure as given
     bool cluster = false, cluster_reps = false;             // --cluster given; --cluster-representatives
     int cluster_algo = LZANI_CLUSTER_SINGLE, cluster_measure = LZANI_CLUSTER_TANI;
@@ -108,6 +110,8 @@ static void usage()
          << "      --flt-kmers-fraction <float> - fraction of the k-mers sampled for --flt-kmers, in (0, 1] (default: 1)\n"
          << "      --flt-kmers-counting <auto|dense|sparse> - where --flt-kmers counts shared k-mers: a matrix of all pairs, or a table of\n"
          << "                                   the pairs that share one (default: auto, the table where the matrix needs several tiles)\n"
+         << "      --flt-kmers-max-seqs <int> - with --flt-kmers: every sequence (query2ref: every query) keeps only its <int> most similar\n"
+         << "                                   sequences by shared k-mers; a pair stays where either sequence keeps it (default: no limit)\n"
          << "Options - output specification:\n"
          << "  -o, --out <file_name>          - output file name\n"
          << "      --out-ids <file_name>      - output file name for ids file (optional)\n"
@@ -200,6 +204,7 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--flt-kmers" && has(2)) { P.flt_kmers = true; P.flt_k = atoi(argv[i + 1]); P.filter_thr = atof(argv[i + 2]); i += 3; }
         else if (par == "--flt-kmers-fraction" && has(1)) { P.flt_fraction_arg = argv[i + 1]; i += 2; }
         else if (par == "--flt-kmers-counting" && has(1)) { P.flt_counting_arg = argv[i + 1]; i += 2; }
+        else if (par == "--flt-kmers-max-seqs" && has(1)) { P.flt_max_seqs_arg = argv[i + 1]; i += 2; }
         else if ((par == "-V" || par == "--verbose") && has(1)) { P.verbosity = (uint32_t)atoi(argv[i + 1]); i += 2; }
         else if (par == "--out-type" && has(1)) {
             string t = argv[i + 1];
@@ -266,6 +271,16 @@ static bool parse_params(int argc, char** argv)
             cerr << "Invalid value for --flt-kmers-counting: " << P.flt_counting_arg << " (auto, dense or sparse)" << endl;
             exit(1);
         }
+    }
+    if (!P.flt_max_seqs_arg.empty()) {
+        if (!P.flt_kmers) { cerr << "--flt-kmers-max-seqs belongs to --flt-kmers" << endl; exit(1); }
+        char* end = nullptr;
+        const unsigned long long v = strtoull(P.flt_max_seqs_arg.c_str(), &end, 10);
+        if (!isdigit((unsigned char)P.flt_max_seqs_arg[0]) || *end || v < 1 || v > UINT32_MAX) {
+            cerr << "Invalid value for --flt-kmers-max-seqs: " << P.flt_max_seqs_arg << " (an integer >= 1)" << endl;
+            exit(1);
+        }
+        P.flt_max_seqs = (uint32_t)v;
     }
     // --cluster: refused here, before any input is read
     if (!P.cluster && (!P.cluster_out.empty() || !P.cluster_measure_arg.empty() || P.cluster_reps)) {

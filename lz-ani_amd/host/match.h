@@ -106,12 +106,15 @@ static void print_engine_line(const Group& G, double matching_secs)
 // them; with it -- or where that set went out-of-core or did not fit -- the genomes stay in host memory and
 // lzani_prefilter_codes streams them through a staging buffer of at most --gpu-mem bytes (automatic without).  n_ref > 0
 // (query2ref): the cross form of either, the kept pairs of the references 0 .. n_ref - 1 with the queries behind them.
-// --flt-kmers-counting goes to the context before the stage runs.
+// --flt-kmers-counting goes to the context before the stage runs.  --flt-kmers-max-seqs: lzani_prefilter_limit cuts the
+// result of whichever of the four calls made it, before it is fetched.
 static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, uint32_t n_ref = 0)
 {
     const uint32_t n = (uint32_t)g.size();
     vector<const uint8_t*> ptr; vector<uint32_t> len;
     genome_views(g, ptr, len);
+    if (P.flt_max_seqs)
+        if (const char* sym = E.missing_limit()) { cerr << "Missing symbol " << sym << " (--flt-kmers-max-seqs needs it)" << endl; return false; }
     Context ctx(E);
     auto fresh = [&]() {                                                  // a new context, configured
         ctx.reset();
@@ -144,13 +147,21 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, u
             rc = codes(0, &kept);
         }
     }
+    if (rc == LZANI_OK && P.flt_max_seqs) rc = E.prefilter_limit(ctx, P.flt_max_seqs, &kept);
     if (rc == LZANI_OK) { ids.resize(kept); rc = E.prefilter_fetch(ctx, nullptr, row_off.data(), ids.data(), nullptr); }
     if (rc != LZANI_OK) { cerr << "K-mer filter failed: " << E.last_error(ctx) << endl; return false; }
     lzani_prefilter_info pi;
     lzani_prefilter_stream_info si;
     lzani_prefilter_pass_info ps;
     lzani_prefilter_sparse_info sp;
-    string stream_note, sparse_note;
+    lzani_prefilter_limit_info li;
+    string stream_note, sparse_note, limit_note;
+    if (P.flt_max_seqs && E.get_prefilter_limit_info(ctx, &li) == LZANI_OK) {
+        ostringstream ss;
+        ss << "; max-seqs " << li.max_per_genome << ": " << li.entries_out << " of " << li.entries_in << " pairs stay, " << li.genomes_cut << " of " << li.limiting
+           << " sequences cut, limit " << li.limit_ms << " ms";
+        limit_note = ss.str();
+    }
     if (E.get_prefilter_sparse_info(ctx, &sp) == LZANI_OK && sp.sparse)                   // (the tiles are in the line already)
         sparse_note = "; sparse counting: " + to_string(sp.attempts) + " attempt(s), " + to_string(sp.slots) + " slots";
     if (streamed && E.get_prefilter_stream_info(ctx, &si) == LZANI_OK) {
@@ -163,7 +174,7 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, u
     if (P.verbosity >= 2 && E.get_prefilter_info(ctx, &pi) == LZANI_OK)
         cerr << "k-mer filter on device " << P.device << ": k " << pi.k << ", " << pi.positions << " sampled windows, " << pi.distinct_kmers
              << " distinct k-mers, " << pi.postings << " postings, " << pi.entries << " kept pairs, " << pi.tiles << " tile(s); keys " << pi.keys_ms
-             << " ms, sorts " << pi.sort_ms << " ms, counting " << pi.count_ms << " ms, compaction " << pi.compact_ms << " ms" << sparse_note << stream_note << "\n";
+             << " ms, sorts " << pi.sort_ms << " ms, counting " << pi.count_ms << " ms, compaction " << pi.compact_ms << " ms" << sparse_note << stream_note << limit_note << "\n";
     flt.names.clear();
     filter_from_pairs(n, row_off, ids, flt);
     return true;

@@ -39,6 +39,7 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_get_prefilter_pass_info", "lzani_prefilter_pass_plan", "lzani_plan_passes",
            "lzani_prefilter_cross", "lzani_prefilter_codes_cross", "lzani_get_prefilter_cross_info",
            "lzani_set_prefilter_counting", "lzani_get_prefilter_sparse_info", "lzani_plan_sparse_tiles",
+           "lzani_prefilter_limit", "lzani_get_prefilter_limit_info", "lzani_prefilter_limit_host", "lzani_debug_prefilter_set",
            "lzani_out_filter_lines", "lzani_run_rows_kept", "lzani_kept_fetch", "lzani_filter_results_device",
            "lzani_debug_filter_results", "lzani_get_kept_info", "lzani_group_run_rows_kept", "lzani_group_kept_fetch",
            "lzani_group_get_kept_info",
@@ -125,6 +126,11 @@ class PrefilterCrossInfo(C.Structure):
 class PrefilterSparseInfo(C.Structure):
     _fields_ = [("sparse", C.c_uint32), ("attempts", C.c_uint32), ("pass_runs", C.c_uint32), ("reserved_", C.c_uint32),
                 ("slots", C.c_uint64), ("table_bytes", C.c_uint64), ("pairs_seen", C.c_uint64), ("max_fill", C.c_uint64)]
+
+
+class PrefilterLimitInfo(C.Structure):
+    _fields_ = [("max_per_genome", C.c_uint32), ("limiting", C.c_uint32), ("entries_in", C.c_uint64), ("entries_out", C.c_uint64),
+                ("genomes_cut", C.c_uint64), ("workspace_bytes", C.c_uint64), ("limit_ms", C.c_double)]
 
 
 class OutFilter(C.Structure):
@@ -356,6 +362,10 @@ def load_library():
         lib.lzani_set_prefilter_counting.argtypes = [C.c_void_p, C.c_int]
         lib.lzani_get_prefilter_sparse_info.argtypes = [C.c_void_p, C.c_void_p]
         lib.lzani_plan_sparse_tiles.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.lzani_prefilter_limit.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.lzani_get_prefilter_limit_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_prefilter_limit_host.argtypes = [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p]
+        lib.lzani_debug_prefilter_set.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
         lib.lzani_out_filter_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.lzani_out_filter_lines.restype = C.c_uint32
         lib.lzani_run_rows_kept.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
@@ -505,6 +515,24 @@ def plan_sparse_tiles(row_pairs, slots):
     if nt < 0:
         raise LzaniError(f"lzani_plan_sparse_tiles: {ERRORS.get(nt, nt)}")
     return tile_r0[:nt + 1].copy(), attempts.value
+
+
+def _csr_arrays(kmers_of, row_off, ids, shared):
+    return (np.ascontiguousarray(kmers_of, dtype=np.uint32), np.ascontiguousarray(row_off, dtype=np.uint64),
+            np.ascontiguousarray(ids, dtype=np.uint32), np.ascontiguousarray(shared, dtype=np.uint32))
+
+
+def prefilter_limit_host(n, n_ref, kmers_of, row_off, ids, shared, max_per_genome):
+    """The limit rule of the prefilter (lzani_prefilter_limit_host; no GPU needed): keep uint8[e], 1 where the CSR entry
+    survives with at most max_per_genome pairs per limiting genome; n_ref 0 = all-pairs."""
+    lib = load_library()
+    kmers_of, row_off, ids, shared = _csr_arrays(kmers_of, row_off, ids, shared)
+    keep = np.zeros(len(ids), dtype=np.uint8)
+    rc = lib.lzani_prefilter_limit_host(int(n), int(n_ref), _ptr(kmers_of), _ptr(row_off), _ptr(ids), _ptr(shared),
+                                        C.c_uint32(int(max_per_genome)), _ptr(keep))
+    if rc != 0:
+        raise LzaniError(f"lzani_prefilter_limit_host: {ERRORS.get(rc, rc)}")
+    return keep
 
 
 def plan_slices(lens, slice_bytes):
@@ -801,6 +829,25 @@ class Engine(_ClusterCalls):
     def set_prefilter_counting(self, mode):
         """lzani_set_prefilter_counting: "auto", "dense" or "sparse" (or the LZANI_PF_COUNTING_* number) for the later prefilter calls."""
         self._check(self.lib.lzani_set_prefilter_counting(self.h, int(PF_COUNTING.get(mode, mode))), "lzani_set_prefilter_counting")
+
+    def prefilter_limit(self, max_per_genome):
+        """lzani_prefilter_limit: the current prefilter result cut to every limiting genome's max_per_genome best pairs.
+        Returns the number of pairs that survive; prefilter_fetch() brings them, prefilter_limit_info() the counters."""
+        cnt = C.c_uint64(0)
+        self._check(self.lib.lzani_prefilter_limit(self.h, C.c_uint32(int(max_per_genome)), C.byref(cnt)), "lzani_prefilter_limit")
+        return int(cnt.value)
+
+    def prefilter_limit_info(self):
+        o = PrefilterLimitInfo()
+        self._check(self.lib.lzani_get_prefilter_limit_info(self.h, C.byref(o)), "lzani_get_prefilter_limit_info")
+        return {k: getattr(o, k) for k, _ in PrefilterLimitInfo._fields_}
+
+    def debug_prefilter_set(self, n, n_ref, kmers_of, row_off, ids, shared):
+        """lzani_debug_prefilter_set: a made-up prefilter result in place of the context's (n_ref 0 = all-pairs)."""
+        kmers_of, row_off, ids, shared = _csr_arrays(kmers_of, row_off, ids, shared)
+        self._check(self.lib.lzani_debug_prefilter_set(self.h, int(n), int(n_ref), _ptr(kmers_of), _ptr(row_off), _ptr(ids), _ptr(shared)),
+                    "lzani_debug_prefilter_set")
+        self.pf_n = int(n)
 
     def prefilter_sparse_info(self):
         o = PrefilterSparseInfo()

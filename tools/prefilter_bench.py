@@ -20,10 +20,15 @@ Every figure is the median of --repeats runs after one warm-up run.
               n_ref genomes as references against the rest) in one process: count_ms, compact_ms (every run and the
               median), matrix_bytes, tiles, entries and the atomic adds of both forms; the cross result is checked against
               the all-pairs result restricted to the cross pairs
+  --max-seqs N  instead of the two workloads: the same 2,000-genome set, k = 21, every fifth k-mer, through lzani_prefilter and
+              behind it lzani_prefilter_limit with N: lzani_get_prefilter_limit_info of every run (limit_ms every run and the
+              median) beside the prefilter's stage times, the limited result checked against lzani_prefilter_limit_host on the
+              unlimited fetch, and the pair-kernel time (lzani_get_timing) of the filtered rows without and with the limit
 Usage: tools/prefilter_bench.py [--out profiles/prefilter_bench.json] [--repeats 3] [--small] [--no-dense]
        tools/prefilter_bench.py --streamed [--slice-bytes N | --slices K] [--passes P] [--counting sparse] [--tile-rows R]
                                 [--out profiles/prefilter_stream_bench.json]
-       tools/prefilter_bench.py --cross N_REF [N_REF ...] [--out profiles/prefilter_cross_bench.json]"""
+       tools/prefilter_bench.py --cross N_REF [N_REF ...] [--out profiles/prefilter_cross_bench.json]
+       tools/prefilter_bench.py --max-seqs N [--out profiles/prefilter_limit_bench.json]"""
 import argparse
 import json
 import math
@@ -210,6 +215,67 @@ def cross(a):
         sys.exit("the cross prefilter's result differs from the restricted all-pairs result")
 
 
+def filtered_rows(n, row_off, ids):
+    """Both directions of every kept pair as the rows run_rows takes: (ref_ids, row_off, query_ids)."""
+    ref_ids = np.arange(n, dtype=np.uint32)
+    a_of = np.repeat(ref_ids, np.diff(row_off).astype(np.int64))
+    r = np.concatenate((a_of, ids)).astype(np.int64)
+    q = np.concatenate((ids, a_of)).astype(np.int64)
+    order = np.lexsort((q, r))
+    f_off = np.zeros(n + 1, dtype=np.uint64)
+    f_off[1:] = np.cumsum(np.bincount(r, minlength=n))
+    return ref_ids, f_off, q[order].astype(np.uint32)
+
+
+def limit(a):
+    """lzani_prefilter and behind it lzani_prefilter_limit on one set, and what the limit saves the pair kernel."""
+    n, fam, min_shared, min_ratio = (200, 50, 5, 0.003) if a.small else (2000, 50, 5, 0.003)
+    _, seqs = SG.make_set(n, 5, fam=fam, dmax=0.10)
+    smax = L.sample_max_of(0.2)
+    N = a.max_seqs
+    res = dict(tool="prefilter_bench --max-seqs", k=K, fraction=0.2, genomes=n, family=fam, bases=sum(len(s) for s in seqs), repeats=a.repeats,
+               min_shared=min_shared, min_ratio=min_ratio, max_seqs=N)
+    eng = L.Engine()
+    eng.set_genomes(seqs)
+    eng.prefilter(K, smax, min_shared, min_ratio)                   # warm-up, and the unlimited result
+    unl = eng.prefilter_fetch()
+    eng.prefilter_limit(N)
+    got = eng.prefilter_fetch()
+    keep = L.prefilter_limit_host(n, 0, *unl, N).astype(bool)
+    a_of = np.repeat(np.arange(n), np.diff(unl[1]).astype(np.int64))
+    same = bool(np.array_equal(got[0], unl[0]) and np.array_equal(got[2], unl[2][keep]) and np.array_equal(got[3], unl[3][keep]) and
+                np.array_equal(np.diff(got[1]).astype(np.int64), np.bincount(a_of[keep], minlength=n)))
+    runs, lruns = [], []
+    for _ in range(a.repeats):
+        eng.prefilter(K, smax, min_shared, min_ratio)
+        runs.append(eng.prefilter_info())
+        eng.prefilter_limit(N)
+        lruns.append(eng.prefilter_limit_info())
+    res["prefilter"] = {key: float(np.median([r[key] for r in runs])) for key in STAGES}
+    res["prefilter"].update(entries=runs[0]["entries"], postings=runs[0]["postings"], compact_ms_runs=[r["compact_ms"] for r in runs])
+    res["limit"] = dict(lruns[0], limit_ms=float(np.median([r["limit_ms"] for r in lruns])), limit_ms_runs=[r["limit_ms"] for r in lruns],
+                        equal_to_host_rule=same)
+    print("limit:", json.dumps(res["limit"]), flush=True)
+    # the pair kernel over the filtered rows, without and with the limit
+    rows = {"unlimited": filtered_rows(n, unl[1], unl[2]), "limited": filtered_rows(n, got[1], got[2])}
+    eng.run_rows(rows["limited"][0][:fam], rows["limited"][1][:fam + 1], rows["limited"][2][:int(rows["limited"][1][fam])])     # warm-up (one family)
+    for tag, (ref_ids, f_off, q_ids) in rows.items():
+        pr = []
+        for _ in range(a.repeats):
+            eng.run_rows(ref_ids, f_off, q_ids)
+            pr.append(eng.timing()["pairs_ms"])
+        res["rows_" + tag] = dict(directed_pairs=int(len(q_ids)), pairs_ms=float(np.median(pr)), pairs_ms_runs=pr)
+    res["pairs_ms_saved"] = res["rows_unlimited"]["pairs_ms"] - res["rows_limited"]["pairs_ms"]
+    eng.close()
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    if not same:
+        sys.exit("the limited result differs from lzani_prefilter_limit_host on the unlimited fetch")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -224,8 +290,11 @@ def main():
     ap.add_argument("--slices", type=int, default=0, help="--streamed: the smallest slice size (in 4 KiB steps) that gives at most this many slices")
     ap.add_argument("--cross", type=int, nargs="+", default=None, metavar="N_REF",
                     help="the cross form (the first N_REF genomes against the rest) beside the all-pairs form on one set")
+    ap.add_argument("--max-seqs", type=int, default=0, metavar="N", help="lzani_prefilter_limit with N behind the prefilter, and the pair-kernel time of the rows it saves")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "prefilter_cross_bench.json" if a.cross else "prefilter_stream_bench.json" if a.streamed else "prefilter_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "prefilter_limit_bench.json" if a.max_seqs else "prefilter_cross_bench.json" if a.cross else "prefilter_stream_bench.json" if a.streamed else "prefilter_bench.json")
+    if a.max_seqs:
+        return limit(a)
     if a.cross:
         return cross(a)
     if a.streamed:
