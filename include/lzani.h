@@ -83,7 +83,8 @@ typedef struct lzani_ctx lzani_ctx;
 void lzani_default_params(lzani_params *p);
 
 /* Replaces CParser::CParser(const CParams&) (parser.h:237-241), once per GPU instead of once
- * per thread.  device_id is the HIP device ordinal. */
+ * per thread.  device_id is the HIP device ordinal.  LZANI_ERR_NOMEM where the context's one device buffer cannot be
+ * had, LZANI_ERR_DEVICE for every other failure of the device; *out is NULL then and nothing is left allocated. */
 int lzani_create(const lzani_params *p, int device_id, lzani_ctx **out);
 void lzani_destroy(lzani_ctx *ctx);
 const char *lzani_last_error(const lzani_ctx *ctx);
@@ -92,7 +93,11 @@ const char *lzani_last_error(const lzani_ctx *ctx);
  * lz_matcher.cpp:207-221): all n genomes at once, one symbol per byte in the reservoir's
  * codes (A0 C1 G2 T3, anything >= 4 is N; seq_reservoir.h:241-248).  The engine packs them to
  * 2 bit + N mask on the device and keeps them resident; caller buffers may be freed on return.
- * Ids used below are indices into this table (the reference's reordered sequence ids). */
+ * Ids used below are indices into this table (the reference's reordered sequence ids).
+ * The call drops the genome set there was and everything made from it -- index slabs, candidate scratch, prefilter, kept
+ * and cluster results -- before it allocates.  LZANI_ERR_NOMEM, in-core or out-of-core, therefore leaves the context
+ * without a genome set: every call that needs one returns LZANI_ERR_STATE until a lzani_set_genomes succeeds, and one
+ * with the same arguments may be tried again on the same context. */
 int lzani_set_genomes(lzani_ctx *ctx, uint32_t n, const uint8_t *const *codes, const uint32_t *len);
 
 /* Genome sets larger than the device (out-of-core).  The genome-memory limit of a context (bytes of genome tables:
@@ -130,7 +135,13 @@ int lzani_get_residency(const lzani_ctx *ctx, lzani_residency_info *info);
  * query_ids[row_off[k] .. row_off[k+1]).  query_ids == NULL means the dense row "every id !=
  * ref, ascending" (row_off[k+1]-row_off[k] must then be n-1), i.e. lz_matcher.cpp:214-233;
  * a non-NULL list is the filtered case (234-250).  out is CSR-aligned (out[e] belongs to
- * query_ids[e]) in host memory: out[e] = calc_stats() of parse(query = query_ids[e], ref = ref_ids[k]). */
+ * query_ids[e]) in host memory: out[e] = calc_stats() of parse(query = query_ids[e], ref = ref_ids[k]).
+ * LZANI_ERR_NOMEM (every lzani_run_rows* form): `out` is unspecified, the genome set and the results of the other stages
+ * (prefilter, kept, cluster) are as they were, and the same call may be made again.  What the run path keeps between runs
+ * -- index slabs, candidate scratch, join lists -- may have been released; the next run makes it anew.  Where only the
+ * buffers of a faster form cannot be had (presence matrix, pair table, candidate bitmaps, the slabs sized for them, the
+ * longest-pair-first order), the run takes the form that needs none of them and succeeds with the same results;
+ * lzani_get_layout's bitmap_launches, or lpt_launches and split_launches, of that run are then 0. */
 int lzani_run_rows(lzani_ctx *ctx, uint32_t n_rows, const uint32_t *ref_ids, const uint64_t *row_off,
                    const uint32_t *query_ids, lzani_result *out);
 
@@ -275,6 +286,7 @@ typedef struct lzani_prefilter_info {
 int lzani_prefilter(lzani_ctx *ctx, int k, uint64_t sample_max, uint32_t min_shared, double min_ratio, uint64_t *n_entries);
 /* kmers_of[n] = |K(g)|; row_off[n+1], ids[], shared[]: CSR of the kept pairs a < b (row a, ids ascending).  Any may be NULL. */
 int lzani_prefilter_fetch(lzani_ctx *ctx, uint32_t *kmers_of, uint64_t *row_off, uint32_t *ids, uint32_t *shared);
+/* LZANI_ERR_STATE without a prefilter result, like the fetch. */
 int lzani_get_prefilter_info(const lzani_ctx *ctx, lzani_prefilter_info *info);
 /* The k-mer passes of the last prefilter (either entry point).  positions, distinct_kmers and postings of
  * lzani_prefilter_info are the sums over the passes of one tile -- the classes are disjoint, so the one-pass values --
@@ -506,7 +518,8 @@ int lzani_kept_fetch(lzani_ctx *ctx, uint64_t first, uint64_t count, lzani_kept_
 int lzani_filter_results_device(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len, uint32_t n_rows, const uint32_t *ref_ids,
                                 const uint64_t *row_off, const uint32_t *query_ids, const void *d_results,
                                 const lzani_out_filter *f, uint64_t *n_kept);
-/* Test hook: the same with the results in host memory (uploaded here): the stage on made-up integers. */
+/* Test hook: the same with the results in host memory (uploaded here): the stage on made-up integers.  LZANI_ERR_NOMEM at
+ * the upload too leaves the context without a kept result. */
 int lzani_debug_filter_results(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len, uint32_t n_rows, const uint32_t *ref_ids,
                                const uint64_t *row_off, const uint32_t *query_ids, const lzani_result *results,
                                const lzani_out_filter *f, uint64_t *n_kept);
@@ -737,14 +750,19 @@ int lzani_debug_cluster_leiden_host_cap(uint32_t n, const lzani_cluster_edge *ed
  * resolution outside [0, 1] or NaN, iterations outside 1..16: LZANI_ERR_ARG, and the parameters stay. */
 int lzani_set_cluster_leiden(lzani_ctx *ctx, double resolution, int iterations);
 /* An empty edge set for n genomes, whose reported lengths (NULL: the genome set's own, n must be its size) stay on the device.
- * Drops the cluster state there was; lzani_set_genomes drops it too.  No genome set: LZANI_ERR_STATE. */
+ * Drops the cluster state there was; lzani_set_genomes drops it too.  No genome set: LZANI_ERR_STATE.  The drop comes
+ * first: LZANI_ERR_NOMEM leaves the context without a cluster state (the cluster calls: LZANI_ERR_STATE until a begin
+ * succeeds). */
 int lzani_cluster_begin(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len, int measure);
 /* Appends the edges of the context's current kept result, one per record, weighted on the device.  No begin or no kept
  * result: LZANI_ERR_STATE; a kept result of another n: LZANI_ERR_ARG; LZANI_ERR_NOMEM leaves the edges that were there. */
 int lzani_cluster_add_kept(lzani_ctx *ctx, uint64_t *edges_total);
-/* Test hook: appends made-up edges from host memory, checked like those of lzani_cluster_host before anything runs. */
+/* Test hook: appends made-up edges from host memory, checked like those of lzani_cluster_host before anything runs.
+ * LZANI_ERR_NOMEM leaves the edges that were there, and the last run's result with them. */
 int lzani_debug_cluster_add_edges(lzani_ctx *ctx, const lzani_cluster_edge *edges, uint64_t count);
-/* May be called again with another algo on the same edges.  No begin: LZANI_ERR_STATE. */
+/* May be called again with another algo on the same edges.  No begin: LZANI_ERR_STATE.  Every algorithm allocates all
+ * its run needs -- the result buffers included -- before it drops the last run's result: LZANI_ERR_NOMEM leaves the
+ * cluster state as before the run, lzani_cluster_fetch and the info calls answer as they did. */
 int lzani_cluster_run(lzani_ctx *ctx, int algo, uint64_t *n_clusters);
 /* rep_of[n], cluster_of[n] of the last run; either may be NULL.  No run since the begin or the last add: LZANI_ERR_STATE. */
 int lzani_cluster_fetch(lzani_ctx *ctx, uint32_t *rep_of, uint32_t *cluster_of);
@@ -793,7 +811,11 @@ int lzani_comm_gatherv(lzani_ctx *ctx, const void *d_send, void *d_recv, const u
  * own host thread; lzani_group_run_rows has the contract of lzani_run_rows -- it partitions the rows as above,
  * runs every shard on its device, gathers the shards on the first device over RCCL (ncclCommInitAll + grouped
  * ncclSend/ncclRecv), restores the caller's CSR order there and copies the results out once.
- * Listing one device twice is allowed for rehearsals on a single GPU (shards then move by device copies). */
+ * Listing one device twice is allowed for rehearsals on a single GPU (shards then move by device copies).
+ * LZANI_ERR_NOMEM of a group call: what the single-context call promises holds for every device context; the group's
+ * own buffers (gathered results, shard buffers, scatter table, pinned staging) are kept or released whole, never with a
+ * stale size, and the same call may be made again.  lzani_group_run_rows_kept then leaves the first device's context
+ * without a kept result. */
 typedef struct lzani_group lzani_group;
 int lzani_group_create(const lzani_params *p, uint32_t n_devices, const int *device_ids, lzani_group **out);
 void lzani_group_destroy(lzani_group *grp);
@@ -830,6 +852,16 @@ int lzani_group_get_cluster_leiden_info(const lzani_group *grp, lzani_cluster_le
  * where they belong in the caller's CSR order (dst[j] = row_off[row]) and how many there are (cnt[j]). */
 int lzani_plan_gather(uint32_t n_rows, const uint64_t *row_off, const uint32_t *part_of_row, uint32_t n_parts,
                       uint64_t *shard_base, uint64_t *src, uint64_t *dst, uint64_t *cnt, uint32_t *row_of_entry);
+
+/* Test hook: an allocation fault.  Every device and pinned-host allocation of the library, of any context and any thread
+ * of the process, is an attempt; the attempts are numbered from 1, starting again at every call of this function.  The
+ * call arms the fault so that the first-th attempt from now fails, and the count - 1 attempts behind it (count = 2^63:
+ * every one from there on); first == 0 disarms, first > 0 with count == 0 is LZANI_ERR_ARG.  An attempt that is hit
+ * behaves as a refused allocation does -- the buffer is left empty, the caller sees the runtime's out-of-memory code --
+ * but the runtime is not called: no memory is exhausted and no error of the runtime is left behind.  *seen (may be NULL)
+ * receives the attempts counted since the previous call, refused ones included.  Needs no context and no GPU.  Not for
+ * production use: the fault is process-wide. */
+int lzani_debug_alloc_fault(uint64_t first, uint64_t count, uint64_t *seen);
 
 /* Test hook: copies out the device-built packed reference text and anchor index of one genome
  * (any pointer may be NULL).  Sizes: nm = ((T+63)/64+2) u64, t2 = twice that, with

@@ -469,9 +469,28 @@ int cluster_leiden_rounds(lzani_ctx* c, LeidenWork& w, u32* rep_of, lzani_cluste
     return LZANI_OK;
 }
 
-// The run on the context's edges: fills rep_of, cluster_of and the run's part of `info` (set cover: `cover`, from `work`;
-// complete linkage: `link`, from `lwork`).
-int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& cluster_of, lzani_cluster_info& info, CoverWork& work,
+// What every algorithm's run works in, and what it leaves: allocated whole before the run touches the cluster state, like
+// the workspaces of set cover, complete linkage and Leiden above.
+struct StageWork {
+    DevMem<u32> parent, state, blocked, flag, size, counters, undecided;     // parent, state, blocked, best: SINGLE and the greedy forms
+    DevMem<unsigned long long> best;
+    DevMem<u64> below;
+    DevMem<u32> rep_of, cluster_of;                                          // the run's result
+};
+bool cluster_algo_plain(int algo) { return algo != LZANI_CLUSTER_SET_COVER && algo != LZANI_CLUSTER_COMPLETE && algo != LZANI_CLUSTER_LEIDEN; }
+int cluster_stage_alloc(lzani_ctx* c, int algo, StageWork& s)
+{
+    const u32 n = c->cl.info.n;
+    if (cluster_algo_plain(algo)) { HIPCHK(c, s.parent.alloc(n)); HIPCHK(c, s.state.alloc(n)); HIPCHK(c, s.blocked.alloc(n)); HIPCHK(c, s.best.alloc(n)); }
+    HIPCHK(c, s.flag.alloc(n)); HIPCHK(c, s.size.alloc(n)); HIPCHK(c, s.below.alloc((size_t)n + 1));
+    HIPCHK(c, s.counters.alloc(CL_COUNTERS)); HIPCHK(c, s.undecided.alloc(CL_BATCH));
+    HIPCHK(c, s.rep_of.alloc(n)); HIPCHK(c, s.cluster_of.alloc(n));
+    return LZANI_OK;
+}
+
+// The run on the context's edges: fills sw.rep_of, sw.cluster_of and the run's part of `info` (set cover: `cover`, from `work`;
+// complete linkage: `link`, from `lwork`).  It allocates nothing.
+int cluster_run_stage(lzani_ctx* c, int algo, StageWork& sw, lzani_cluster_info& info, CoverWork& work,
                       lzani_cluster_cover_info& cover, LinkWork& lwork, lzani_cluster_link_info& link, LeidenWork& ldwork,
                       lzani_cluster_leiden_info& leiden)
 {
@@ -480,14 +499,11 @@ int cluster_run_stage(lzani_ctx* c, int algo, DevMem<u32>& rep_of, DevMem<u32>& 
     const u64 E = k.info.edges;
     const lzani_cluster_edge* edges = k.edges.get();
     const bool set_cover = algo == LZANI_CLUSTER_SET_COVER, complete = algo == LZANI_CLUSTER_COMPLETE, is_leiden = algo == LZANI_CLUSTER_LEIDEN;
-    const bool plain = !set_cover && !complete && !is_leiden;                    // SINGLE and the greedy forms: parent, state, blocked, best
-    DevMem<u32> parent, state, blocked, flag, size, counters, undecided;
-    DevMem<unsigned long long> best;
-    DevMem<u64> below;
-    if (plain) { HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, best.alloc(n)); }
-    HIPCHK(c, flag.alloc(n)); HIPCHK(c, size.alloc(n)); HIPCHK(c, below.alloc((size_t)n + 1));
-    HIPCHK(c, counters.alloc(CL_COUNTERS)); HIPCHK(c, undecided.alloc(CL_BATCH));
-    HIPCHK(c, rep_of.alloc(n)); HIPCHK(c, cluster_of.alloc(n));
+    const bool plain = cluster_algo_plain(algo);
+    DevMem<u32>&parent = sw.parent, &state = sw.state, &blocked = sw.blocked, &flag = sw.flag, &size = sw.size, &counters = sw.counters, &undecided = sw.undecided;
+    DevMem<unsigned long long>& best = sw.best;
+    DevMem<u64>& below = sw.below;
+    DevMem<u32>&rep_of = sw.rep_of, &cluster_of = sw.cluster_of;
     const dim3 nodes(pf_blocks(n)), edge_blocks(pf_blocks(E)), threads(PF_THREADS);
     StreamSpan span;
     HIPCHK(c, span.begin(c->stream));
@@ -710,20 +726,21 @@ int lzani_cluster_run(lzani_ctx* c, int algo, uint64_t* n_clusters)
     LeidenWork ldwork;                                         // Leiden: the same
     if (algo == LZANI_CLUSTER_LEIDEN)
         if (int rc = cluster_leiden_alloc(c, ldwork)) return rc;
+    StageWork sw;                                              // every algorithm: the same
+    if (int rc = cluster_stage_alloc(c, algo, sw)) return rc;
     k.ran = false;
-    k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes first
-    DevMem<u32> rep_of, cluster_of;
+    k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes before the run, not before its memory is had
     lzani_cluster_info info = k.info;
     lzani_cluster_cover_info cover{};
     lzani_cluster_link_info link{};
     lzani_cluster_leiden_info leiden{};
-    const int rc = cluster_run_stage(c, algo, rep_of, cluster_of, info, work, cover, lwork, link, ldwork, leiden);
+    const int rc = cluster_run_stage(c, algo, sw, info, work, cover, lwork, link, ldwork, leiden);
     if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     k.info = info;
     k.cover = cover;
     k.link = link;
     k.leiden = leiden;
-    k.rep_of = std::move(rep_of); k.cluster_of = std::move(cluster_of);
+    k.rep_of = std::move(sw.rep_of); k.cluster_of = std::move(sw.cluster_of);
     k.ran = true;
     if (n_clusters) *n_clusters = info.clusters;
     return LZANI_OK;

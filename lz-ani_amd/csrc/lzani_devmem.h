@@ -4,9 +4,35 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
+#include <cstdint>
 
 namespace lzani {
+
+// The allocation fault of the tests (lzani_debug_alloc_fault): three process-wide counters, inert unless armed.  Every
+// allocation attempt, device or pinned, takes the next attempt number (a relaxed add) and reads `first` (a relaxed load);
+// armed -- first > 0 -- the attempts numbered first .. first + count - 1 are refused.  The numbers start again at 1 with
+// every alloc_fault_arm.  Threads share the counters: which of two concurrent attempts gets a number is not fixed.
+inline std::atomic<uint64_t> g_alloc_seen{0}, g_alloc_first{0}, g_alloc_count{0};
+
+// Whether this attempt is to be refused.
+inline bool alloc_refused()
+{
+    const uint64_t k = g_alloc_seen.fetch_add(1, std::memory_order_relaxed) + 1;
+    const uint64_t lo = g_alloc_first.load(std::memory_order_relaxed);
+    return lo && k >= lo && k - lo < g_alloc_count.load(std::memory_order_relaxed);
+}
+// first > 0: the first-th attempt from now is refused, and the count - 1 behind it; first == 0: none is.  Returns the
+// attempts counted since the previous call.
+inline uint64_t alloc_fault_arm(uint64_t first, uint64_t count)
+{
+    g_alloc_first.store(0, std::memory_order_relaxed);           // (nothing is refused while the range changes)
+    g_alloc_count.store(first ? count : 0, std::memory_order_relaxed);
+    const uint64_t before = g_alloc_seen.exchange(0, std::memory_order_relaxed);
+    g_alloc_first.store(first, std::memory_order_relaxed);
+    return before;
+}
 
 // `capacity()` elements of T on the device (PINNED: in page-locked host memory), released by the destructor.  Move-only,
 // empty by default.  Sizes are counts of T; a count of 0 allocates one element, so that a live buffer is never null.
@@ -37,6 +63,7 @@ public:
     {
         reset();
         count = std::max<size_t>(count, 1);
+        if (alloc_refused()) return hipErrorOutOfMemory;       // (the runtime is not asked: nothing is exhausted, no sticky error)
         hipError_t e;
         if constexpr (PINNED) e = hipHostMalloc((void**)&p_, count * sizeof(T), hipHostMallocDefault);
         else e = hipMalloc((void**)&p_, count * sizeof(T));

@@ -882,8 +882,12 @@ int lzani_create(const lzani_params* p, int device_id, lzani_ctx** out)
     if (!c) return LZANI_ERR_NOMEM;
     c->P = P;
     c->dev = device_id;
-    bool ok = hipSetDevice(device_id) == hipSuccess && hipStreamCreate(&c->stream) == hipSuccess &&
-              c->d_cursor.alloc(NQUEUES) == hipSuccess;
+    bool ok = hipSetDevice(device_id) == hipSuccess && hipStreamCreate(&c->stream) == hipSuccess;
+    if (ok) {                                                  // the queue cursors: the one buffer a context is made with
+        const hipError_t e = c->d_cursor.alloc(NQUEUES);
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); lzani_destroy(c); return LZANI_ERR_NOMEM; }
+        ok = e == hipSuccess;
+    }
     if (ok) {
         hipDeviceProp_t prop;
         ok = hipGetDeviceProperties(&prop, device_id) == hipSuccess;
@@ -1101,6 +1105,15 @@ int lzani_get_residency(const lzani_ctx* c, lzani_residency_info* o)
     o->peak_resident_bytes = c->res.peak;
     o->host_bytes = c->gs.h_codes.size();
     o->upload_ms = c->res.upload_ms;
+    return LZANI_OK;
+}
+
+// Test hook: the allocation fault of lzani_devmem.h.  Needs no context and calls no runtime.
+int lzani_debug_alloc_fault(uint64_t first, uint64_t count, uint64_t* seen)
+{
+    if (first && !count) return LZANI_ERR_ARG;
+    const uint64_t before = alloc_fault_arm(first, count);
+    if (seen) *seen = before;
     return LZANI_OK;
 }
 

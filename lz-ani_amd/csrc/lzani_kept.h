@@ -163,7 +163,10 @@ int lzani_debug_filter_results(lzani_ctx* c, uint32_t n, const uint32_t* report_
     if (E && !results) return fail(c, LZANI_ERR_ARG, "lzani_debug_filter_results: null results");
     HIPCHK(c, hipSetDevice(c->dev));
     DevMem<lzani_result> d_res;
-    HIPCHK(c, d_res.alloc(E));
+    if (const hipError_t e = d_res.alloc(E); e != hipSuccess) {
+        c->kept = Kept{};                                      // as where the stage itself runs short: no kept result, not the last call's
+        HIPCHK(c, e);
+    }
     if (E) HIPCHK(c, hipMemcpy(d_res.get(), results, (size_t)E * sizeof(lzani_result), hipMemcpyHostToDevice));
     return lzani_filter_results_device(c, n, report_len, n_rows, ref_ids, row_off, query_ids, d_res.get(), f, n_kept);
 }

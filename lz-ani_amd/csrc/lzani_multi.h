@@ -56,7 +56,9 @@ namespace {
 #define GHIPCHK(g, call)                                                                              \
     do {                                                                                              \
         hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return gfail(g, LZANI_ERR_DEVICE, std::string("gather / copy out: ") + hipGetErrorString(e_)); \
+        if (e_ != hipSuccess)                                                                         \
+            return gfail(g, e_ == hipErrorOutOfMemory ? LZANI_ERR_NOMEM : LZANI_ERR_DEVICE,           \
+                         std::string("gather / copy out: ") + hipGetErrorString(e_));                 \
     } while (0)
 
 // Rows of a gathered buffer (shard order) -> the caller's CSR order.  One block per row.
@@ -149,7 +151,7 @@ int group_run_shards(lzani_group* g, GroupRun& r)
         if (s.rows.empty()) { c->run.tm = lzani_timing{}; return LZANI_OK; }   // no row for this device
         if (d && g->d_shard[d].capacity() < std::max<u64>(s.pairs(), 1)) {
             if (hipSetDevice(c->dev) != hipSuccess) return LZANI_ERR_DEVICE;
-            if (!got(g->d_shard[d].alloc(s.pairs()))) return LZANI_ERR_NOMEM;
+            if (!got(g->d_shard[d].alloc(s.pairs()))) return fail(c, LZANI_ERR_NOMEM, "lzani_group_run_rows: the device's shard buffer");
         }
         if (d) r.d_shard[d] = (int*)g->d_shard[d].get();
         static const u32 none = 0;                             // (lists that are all empty are still lists, not dense rows: never null)
@@ -418,7 +420,8 @@ int lzani_group_create(const lzani_params* p, uint32_t n_devices, const int* dev
         int rc = lzani_create(p, device_ids[d], &c);
         if (rc != LZANI_OK) {
             t_group_create_err = "lzani_create on device " + std::to_string(device_ids[d]) + " failed with code " + std::to_string(rc) +
-                                 (rc == LZANI_ERR_PARAMS ? " (LZ parameters outside the supported envelope)" : rc == LZANI_ERR_DEVICE ? " (no such HIP device, or its stream could not be made)" : "");
+                                 (rc == LZANI_ERR_PARAMS ? " (LZ parameters outside the supported envelope)" : rc == LZANI_ERR_DEVICE ? " (no such HIP device, or its stream could not be made)" :
+                                  rc == LZANI_ERR_NOMEM ? " (out of memory)" : "");
             lzani_group_destroy(g);
             return rc;
         }

@@ -844,6 +844,7 @@ int lzani_prefilter_fetch(lzani_ctx* c, uint32_t* kmers_of, uint64_t* row_off, u
 int lzani_get_prefilter_info(const lzani_ctx* c, lzani_prefilter_info* info)
 {
     if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->pf.done) return LZANI_ERR_STATE;
     *info = c->pf.info;
     return LZANI_OK;
 }

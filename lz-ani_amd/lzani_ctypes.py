@@ -49,7 +49,7 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_group_get_cluster_info", "lzani_get_cluster_cover_info", "lzani_group_get_cluster_cover_info",
            "lzani_get_cluster_link_info", "lzani_group_get_cluster_link_info", "lzani_cluster_leiden_host",
            "lzani_debug_cluster_leiden_host_cap", "lzani_set_cluster_leiden", "lzani_group_set_cluster_leiden",
-           "lzani_get_cluster_leiden_info", "lzani_group_get_cluster_leiden_info")
+           "lzani_get_cluster_leiden_info", "lzani_group_get_cluster_leiden_info", "lzani_debug_alloc_fault")
 
 
 class LzaniError(RuntimeError):
@@ -393,8 +393,39 @@ def load_library():
         lib.lzani_debug_cluster_leiden_host_cap.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_double, C.c_int, C.c_uint64, C.c_uint64,
                                                             C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lzani_debug_cluster_add_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.lzani_debug_alloc_fault.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         _lib = lib
     return _lib
+
+
+ALLOC_FAULT_ALL = 1 << 63                           # lzani_debug_alloc_fault's count for "every attempt from `first` on"
+
+
+def alloc_fault(first=0, count=1):
+    """lzani_debug_alloc_fault (test hook, process-wide, no GPU needed): the first-th device or pinned allocation attempt
+    from now fails, and the count - 1 behind it; first = 0 disarms.  Returns the attempts counted since the previous call."""
+    lib = load_library()
+    seen = C.c_uint64(0)
+    rc = lib.lzani_debug_alloc_fault(C.c_uint64(int(first)), C.c_uint64(int(count)), C.byref(seen))
+    if rc != 0:
+        raise LzaniError(f"lzani_debug_alloc_fault: {ERRORS.get(rc, rc)}")
+    return int(seen.value)
+
+
+class AllocFault:
+    """`with AllocFault(first, count) as f:` arms the fault for the block and always disarms on the way out; f.seen is then
+    the number of attempts the block made."""
+
+    def __init__(self, first=0, count=1):
+        self.first, self.count, self.seen = int(first), int(count), None
+
+    def __enter__(self):
+        alloc_fault(self.first, self.count)
+        return self
+
+    def __exit__(self, *exc):
+        self.seen = alloc_fault(0)
+        return False
 
 
 def params_array(params=None):
