@@ -1,13 +1,19 @@
-// lzani_cluster.h -- host side of the cluster stage (include/lzani.h states the definitions): the edge buffer and its growth,
-// the run -- union-find for single linkage, rounds of the greedy representatives, assignment, the distinct edges and
-// the rounds of set cover, the contraction rounds of complete linkage, or the levels and rounds of Leiden; numbering --
-// and the entry points
-// (lzani_cluster_begin, lzani_cluster_add_kept, lzani_debug_cluster_add_edges, lzani_cluster_run, lzani_cluster_fetch,
-// lzani_get_cluster_info, lzani_get_cluster_cover_info, lzani_get_cluster_link_info, lzani_set_cluster_leiden,
-// lzani_get_cluster_leiden_info and the pure lzani_cluster_weight, lzani_cluster_host and lzani_cluster_leiden_host).  Included by lzani_hip.hip only,
-// behind lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept), fail, HIPCHK and sort_keys, of
-// lzani_prefilter.h pf_blocks and pf_chunks, of lzani_devmem.h DevMem and StreamSpan.  The kernels are lzani_kernels_cluster.h; the group's form is in
-// lzani_multi.h.
+// lzani_cluster.h -- host side of the cluster stage (include/lzani.h states the definitions): the edge buffer and its growth
+// (cluster_reserve); ClusterStage, what every run works in and leaves (flag, size, below, the counters, a batch's round
+// words, rep_of, cluster_of, rounds); the helpers the units share -- cluster_rounds (rounds launched in batches between two
+// reads of their words: the one place of that arithmetic), cluster_compact (count pass, k_pf_scan, write pass),
+// cluster_table_slots, cluster_table_clear and CL_ALLOC (a workspace buffer, counted into the unit's bytes as it is had) --;
+// one unit per family of algorithms -- PlainUnit (SINGLE and the greedy forms), CoverUnit, LinkUnit, LeidenUnit --, each with
+// its device buffers, alloc(c) with its limits and refusals, run(c, stage), which fills stage.rep_of and stage.rounds, and
+// `info`, its own info struct (PlainUnit: none); cluster_run_stage (span and counters, the unit's run, the numbering) and
+// cluster_run_as<Unit> (the unit, then the stage, allocated whole before the cluster state is touched); and the entry points
+// (lzani_cluster_begin, lzani_cluster_add_kept, lzani_debug_cluster_add_edges, lzani_cluster_run -- the one choice of a unit
+// by `algo` --, lzani_cluster_fetch, lzani_get_cluster_info, lzani_get_cluster_cover_info, lzani_get_cluster_link_info,
+// lzani_set_cluster_leiden, lzani_get_cluster_leiden_info and the pure lzani_cluster_weight, lzani_cluster_host and
+// lzani_cluster_leiden_host).  A further algorithm is one more unit and one more case in lzani_cluster_run.
+// Included by lzani_hip.hip only, behind lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept),
+// fail, HIPCHK and sort_keys, of lzani_prefilter.h pf_blocks and pf_chunks, of lzani_devmem.h DevMem and StreamSpan.  The
+// kernels are lzani_kernels_cluster.h; the group's form is in lzani_multi.h.
 //
 // What the stage reads and writes.  add_kept, per record: 36 B and two lengths read, 16 B written.  SINGLE: per edge 16 B
 // and the two paths to the roots, one CAS per hook that is won; per node one path.  A greedy round: per edge 16 B and one or
@@ -36,7 +42,8 @@
 
 namespace {
 
-enum { CL_BATCH = 8 };                                  // greedy rounds launched between two reads of the undecided counts
+enum { CL_BATCH = 8 };                                  // greedy and set-cover rounds launched between two reads of their words
+constexpr u64 CL_MAX_EDGES = 0xFFFFFFEFull;             // 2^32 - 17: lzani_sort_keys' limit, and that of the units with a workspace
 
 int cluster_state(lzani_ctx* c, const std::string& fn)
 {
@@ -63,526 +70,541 @@ int cluster_reserve(lzani_ctx* c, u64 need)
     return LZANI_OK;
 }
 
-// The workspace of a set-cover run, allocated whole before the run touches the cluster state: the keys of the edge records
-// and of the distinct edges (two buffers of E, the sort's in and out in turn), the sort's scratch, the compaction's block
-// counts and offsets, and per node the counter and the three 64-bit words of a round.
-constexpr u64 CL_COVER_MAX_EDGES = 0xFFFFFFEFull;       // 2^32 - 17: lzani_sort_keys' limit
-struct CoverWork {
+// What every algorithm's run works in, and what it leaves.  Like the units' workspaces it is allocated whole before the run
+// touches the cluster state.
+struct ClusterStage {
+    int algo = 0;
+    u64 rounds = 1;                                     // the unit's run says
+    DevMem<u32> flag, size, counters, undecided;        // undecided: a word per round of a batch (the greedy forms, set cover)
+    DevMem<u64> below;
+    DevMem<u32> rep_of, cluster_of;                     // the run's result
+    int alloc(lzani_ctx* c)
+    {
+        const u32 n = c->cl.info.n;
+        HIPCHK(c, flag.alloc(n)); HIPCHK(c, size.alloc(n)); HIPCHK(c, below.alloc((size_t)n + 1));
+        HIPCHK(c, counters.alloc(CL_COUNTERS)); HIPCHK(c, undecided.alloc(CL_BATCH));
+        HIPCHK(c, rep_of.alloc(n)); HIPCHK(c, cluster_of.alloc(n));
+        return LZANI_OK;
+    }
+};
+
+// One buffer of a unit's workspace: its own allocation and its own attempt, counted into the unit's `bytes` as it is had, so
+// that `count` is the one statement of its size.
+#define CL_ALLOC(buf, count) do { HIPCHK(c, buf.alloc(count)); bytes += buf.bytes(); } while (0)
+
+// Rounds launched `batch` at a time between two reads of their words: round r of a batch leaves words[first + r] != 0 while
+// there is more to do, and a round behind the first that left 0 changes nothing.  More than `cap` rounds: `still`.
+struct ClRounds {
+    u32 batch;
+    u64 cap;
+    const char* still;
+    u32* words;                                        // `count` of them, cleared before every batch and read back whole
+    u32 count, first;
+};
+// launch(r) launches round r of a batch; seen(words, r, last) is given every batch's words on the host, the number r of its
+// rounds that had more to do and the index of the last that counts.  rounds: up to the first that left 0, that one included.
+template <class Launch, class Seen = int (*)(const u32*, u32, u32)>
+int cluster_rounds(lzani_ctx* c, const ClRounds& p, u64& rounds, Launch launch, Seen seen = [](const u32*, u32, u32) { return (int)LZANI_OK; })
+{
+    u32 words[CL_LD_CTL];
+    static_assert(CL_LD_CTL >= CL_BATCH, "the host copy holds either family's words");
+    rounds = 0;
+    for (bool done = false; !done;) {
+        if (rounds >= p.cap) return fail(c, LZANI_ERR_DEVICE, p.still);      // a defect ends here instead of spinning
+        const u32 batch = (u32)std::min<u64>(p.batch, p.cap - rounds);
+        HIPCHK(c, hipMemsetAsync(p.words, 0, p.count * sizeof(u32), c->stream));
+        for (u32 r = 0; r < batch; ++r) HIPCHK(c, launch(r));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(words, p.words, p.count * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        u32 r = 0;
+        while (r < batch && words[p.first + r]) ++r;
+        done = r < batch;
+        rounds += done ? r + 1 : batch;
+        if (int rc = seen(words, r, done ? r : batch - 1)) return rc;
+    }
+    return LZANI_OK;
+}
+
+// The kept ones of `items` into a list: pass(std::false_type, chunks) launches the count pass over `chunks` blocks,
+// k_pf_scan makes the blocks' offsets, pass(std::true_type, chunks) writes.  Returns where the total is, on the device.
+template <class Pass>
+const u64* cluster_compact(lzani_ctx* c, u64 items, u32* ucnt, u64* uoff, Pass pass)
+{
+    const u32 chunks = (u32)pf_chunks(items);
+    pass(std::false_type{}, chunks);
+    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, ucnt, (u64)chunks, uoff);
+    pass(std::true_type{}, chunks);
+    return uoff + chunks;
+}
+
+// the slots of a table of `insertions`: the smallest power of two >= 2 * insertions (1 for none)
+u64 cluster_table_slots(u64 insertions)
+{
+    u64 S = 1;
+    while (S < 2 * insertions) S <<= 1;
+    return S;
+}
+
+struct ClFill { unsigned long long* words; int byte; };
+// A round's table cleared: S keys all ones, and S words of every other array of `byte` bytes.
+hipError_t cluster_table_clear(lzani_ctx* c, u64 S, unsigned long long* key, std::initializer_list<ClFill> others)
+{
+    hipError_t e = hipMemsetAsync(key, 0xFF, (size_t)S * 8, c->stream);
+    for (const ClFill& f : others)
+        if (e == hipSuccess) e = hipMemsetAsync(f.words, f.byte, (size_t)S * 8, c->stream);
+    return e;
+}
+
+// SINGLE (union-find) and the greedy forms (rounds of representatives, then the assignment).
+struct PlainUnit {
+    DevMem<u32> parent, state, blocked;
+    DevMem<unsigned long long> best;
+    std::monostate info;
+    int alloc(lzani_ctx* c)
+    {
+        const u32 n = c->cl.info.n;
+        HIPCHK(c, parent.alloc(n)); HIPCHK(c, state.alloc(n)); HIPCHK(c, blocked.alloc(n)); HIPCHK(c, best.alloc(n));
+        return LZANI_OK;
+    }
+    int run(lzani_ctx* c, ClusterStage& st)
+    {
+        const u32 n = c->cl.info.n;
+        const u64 E = c->cl.info.edges;
+        const lzani_cluster_edge* edges = c->cl.edges;
+        const dim3 nodes(pf_blocks(n)), edge_blocks(pf_blocks(E)), threads(PF_THREADS);
+        hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent, state, blocked, best, st.size);
+        if (st.algo == LZANI_CLUSTER_SINGLE) {
+            if (E) hipLaunchKernelGGL(k_cl_hook, edge_blocks, threads, 0, c->stream, edges, E, parent);
+            hipLaunchKernelGGL(k_cl_roots, nodes, threads, 0, c->stream, n, parent, st.rep_of);
+            return LZANI_OK;
+        }
+        // the lowest undecided node is decided in every round: n rounds always do
+        const ClRounds p{CL_BATCH, (u64)n + 1, "lzani_cluster_run: nodes still undecided after n + 1 rounds", st.undecided, CL_BATCH, 0};
+        auto round = [&](u32 r) {
+            if (E) hipLaunchKernelGGL(k_cl_greedy_edges, edge_blocks, threads, 0, c->stream, edges, E, state, blocked);
+            hipLaunchKernelGGL(k_cl_greedy_nodes, nodes, threads, 0, c->stream, n, state, blocked, st.undecided.get() + r);
+            return hipSuccess;
+        };
+        if (int rc = cluster_rounds(c, p, st.rounds, round)) return rc;
+        const bool by_weight = st.algo == LZANI_CLUSTER_GREEDY_BEST;
+        hipLaunchKernelGGL(k_cl_assign_init, nodes, threads, 0, c->stream, n, state, st.rep_of);
+        if (E && by_weight) hipLaunchKernelGGL(k_cl_assign_best, edge_blocks, threads, 0, c->stream, edges, E, state, best);
+        if (E) hipLaunchKernelGGL(k_cl_assign_min, edge_blocks, threads, 0, c->stream, edges, E, state, by_weight ? best.get() : nullptr, st.rep_of);
+        return LZANI_OK;
+    }
+};
+
+// Set cover.  The workspace: the keys of the edge records and of the distinct edges (two buffers of E, the sort's in and out
+// in turn), the sort's scratch, the compaction's block counts and offsets, and per node the counter and the three 64-bit
+// words of a round.
+struct CoverUnit {
     DevMem<unsigned long long> ka, kb, key, m1, m2;
     DevMem<unsigned char> scratch;
     DevMem<u32> ucnt, cnt;
     DevMem<u64> uoff;
     int bits = 1;                                       // of an id below n
-    u64 bytes() const { return ka.bytes() + kb.bytes() + key.bytes() + m1.bytes() + m2.bytes() + scratch.bytes() + ucnt.bytes() + cnt.bytes() + uoff.bytes(); }
+    u64 bytes = 0;
+    lzani_cluster_cover_info info{};
+    int alloc(lzani_ctx* c)
+    {
+        const u32 n = c->cl.info.n;
+        const u64 E = c->cl.info.edges;
+        if (E > CL_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: set cover sorts at most 2^32 - 17 edge records");
+        while (bits < 32 && ((u64)1 << bits) < n) ++bits;
+        size_t need = 0;                                // (the same for the two sorts: as many bits, as many keys)
+        if (int rc = sort_scratch_bytes(c, (size_t)E, 1, 0, bits, "lzani_cluster_run: sort", need)) return rc;
+        CL_ALLOC(ka, (size_t)E); CL_ALLOC(kb, (size_t)E); CL_ALLOC(scratch, need);
+        CL_ALLOC(ucnt, (size_t)pf_chunks(E)); CL_ALLOC(uoff, (size_t)pf_chunks(E) + 1);
+        CL_ALLOC(cnt, n); CL_ALLOC(key, n); CL_ALLOC(m1, n); CL_ALLOC(m2, n);
+        return LZANI_OK;
+    }
+    // The distinct edges of the context's edge records, ascending, in kb: D of them.  The edge buffer is only read.
+    int dedup(lzani_ctx* c, u64& D)
+    {
+        const u64 E = c->cl.info.edges;
+        D = 0;
+        if (!E) return LZANI_OK;
+        hipLaunchKernelGGL(k_cl_cover_keys, dim3(pf_blocks(E)), dim3(PF_THREADS), 0, c->stream, c->cl.edges, E, ka);
+        HIPCHK(c, hipGetLastError());
+        // by hi, then (the sort is stable) by lo: only the bits an id below n has
+        if (int rc = sort_keys(c, scratch, ka, kb, (size_t)E, 1, 0, bits, "lzani_cluster_run: sort", false)) return rc;
+        if (int rc = sort_keys(c, scratch, kb, ka, (size_t)E, 1, 32, 32 + bits, "lzani_cluster_run: sort", false)) return rc;
+        const u64* total = cluster_compact(c, E, ucnt, uoff, [&](auto write, u32 chunks) {
+            hipLaunchKernelGGL(k_pf_uniq<decltype(write)::value>, dim3(chunks), dim3(PF_THREADS), 0, c->stream, ka, E, ucnt, uoff, kb, (u32*)nullptr, 0u);
+        });
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&D, total, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (D > E) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more distinct edges than edge records");
+        return LZANI_OK;
+    }
+    // The dedup, then the rounds over the D distinct edges of kb (lzani_kernels_cluster.h): rounds is the number of the first
+    // that left no node unassigned.
+    int run(lzani_ctx* c, ClusterStage& st)
+    {
+        const u32 n = c->cl.info.n;
+        const dim3 nodes(pf_blocks(n)), threads(PF_THREADS);
+        StreamSpan dedup_span, rounds_span;
+        u64 D = 0;
+        HIPCHK(c, dedup_span.begin(c->stream));
+        if (int rc = dedup(c, D)) return rc;
+        HIPCHK(c, dedup_span.end(c->stream));
+        HIPCHK(c, rounds_span.begin(c->stream));
+        hipLaunchKernelGGL(k_cl_cover_init, nodes, threads, 0, c->stream, n, st.rep_of, cnt, st.size);
+        const dim3 edge_blocks(pf_blocks(D));
+        // the unassigned node with the largest key is selected in every round: n rounds always do
+        const ClRounds p{CL_BATCH, (u64)n + 1, "lzani_cluster_run: nodes still unassigned after n + 1 rounds", st.undecided, CL_BATCH, 0};
+        auto round = [&](u32 r) {
+            if (D) hipLaunchKernelGGL(k_cl_cover_count, edge_blocks, threads, 0, c->stream, kb, D, n, st.rep_of, cnt);
+            hipLaunchKernelGGL(k_cl_cover_key, nodes, threads, 0, c->stream, n, st.rep_of, cnt, key, m1, m2);
+            if (D) hipLaunchKernelGGL(k_cl_cover_max, edge_blocks, threads, 0, c->stream, kb, D, n, key, m1);
+            if (D) hipLaunchKernelGGL(k_cl_cover_max, edge_blocks, threads, 0, c->stream, kb, D, n, m1, m2);
+            hipLaunchKernelGGL(k_cl_cover_decide, nodes, threads, 0, c->stream, n, m1, m2, st.rep_of, st.undecided.get() + r);
+            return hipSuccess;
+        };
+        if (int rc = cluster_rounds(c, p, st.rounds, round)) return rc;
+        HIPCHK(c, rounds_span.end(c->stream));
+        float dedup_ms = 0, rounds_ms = 0;
+        HIPCHK(c, dedup_span.elapsed(dedup_ms));
+        HIPCHK(c, rounds_span.elapsed(rounds_ms));
+        info = lzani_cluster_cover_info{D, c->cl.info.edges - D, bytes, dedup_ms, rounds_ms};
+        return LZANI_OK;
+    }
 };
 
-int cluster_cover_alloc(lzani_ctx* c, CoverWork& w)
-{
-    const u32 n = c->cl.info.n;
-    const u64 E = c->cl.info.edges;
-    if (E > CL_COVER_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: set cover sorts at most 2^32 - 17 edge records");
-    while (w.bits < 32 && ((u64)1 << w.bits) < n) ++w.bits;
-    size_t need = 0;                                    // (the same for the two sorts: as many bits, as many keys)
-    if (int rc = sort_scratch_bytes(c, (size_t)E, 1, 0, w.bits, "lzani_cluster_run: sort", need)) return rc;
-    HIPCHK(c, w.ka.alloc((size_t)E)); HIPCHK(c, w.kb.alloc((size_t)E)); HIPCHK(c, w.scratch.alloc(need));
-    HIPCHK(c, w.ucnt.alloc((size_t)pf_chunks(E))); HIPCHK(c, w.uoff.alloc((size_t)pf_chunks(E) + 1));
-    HIPCHK(c, w.cnt.alloc(n)); HIPCHK(c, w.key.alloc(n)); HIPCHK(c, w.m1.alloc(n)); HIPCHK(c, w.m2.alloc(n));
-    return LZANI_OK;
-}
-
-// The distinct edges of the context's edge records, ascending, in w.kb: D of them.  The edge buffer is only read.
-int cluster_cover_dedup(lzani_ctx* c, CoverWork& w, u64& D)
-{
-    const u64 E = c->cl.info.edges;
-    D = 0;
-    if (!E) return LZANI_OK;
-    hipLaunchKernelGGL(k_cl_cover_keys, dim3(pf_blocks(E)), dim3(PF_THREADS), 0, c->stream, (const lzani_cluster_edge*)c->cl.edges.get(), E, w.ka.get());
-    HIPCHK(c, hipGetLastError());
-    // by hi, then (the sort is stable) by lo: only the bits an id below n has
-    if (int rc = sort_keys(c, w.scratch, w.ka.get(), w.kb.get(), (size_t)E, 1, 0, w.bits, "lzani_cluster_run: sort", false)) return rc;
-    if (int rc = sort_keys(c, w.scratch, w.kb.get(), w.ka.get(), (size_t)E, 1, 32, 32 + w.bits, "lzani_cluster_run: sort", false)) return rc;
-    const u32 blocks = (u32)pf_chunks(E);
-    hipLaunchKernelGGL(k_pf_uniq<false>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, (const unsigned long long*)w.ka.get(), E, w.ucnt.get(),
-                       (const u64*)w.uoff.get(), w.kb.get(), (u32*)nullptr, 0u);
-    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.ucnt.get(), (u64)blocks, w.uoff.get());
-    hipLaunchKernelGGL(k_pf_uniq<true>, dim3(blocks), dim3(PF_THREADS), 0, c->stream, (const unsigned long long*)w.ka.get(), E, w.ucnt.get(),
-                       (const u64*)w.uoff.get(), w.kb.get(), (u32*)nullptr, 0u);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(&D, w.uoff.get() + blocks, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (D > E) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more distinct edges than edge records");
-    return LZANI_OK;
-}
-
-// The rounds of set cover over the D distinct edges of w.kb (lzani_kernels_cluster.h): rep_of, and the number of the first
-// round that left no node unassigned.
-int cluster_cover_rounds(lzani_ctx* c, CoverWork& w, u64 D, u32* rep_of, u32* undecided, u64& rounds)
-{
-    const u32 n = c->cl.info.n;
-    const dim3 nodes(pf_blocks(n)), edge_blocks(pf_blocks(D)), threads(PF_THREADS);
-    const unsigned long long* pairs = w.kb.get();
-    rounds = 0;
-    for (bool done = false; !done;) {
-        // the unassigned node with the largest key is selected in every round: n rounds always do, and a defect ends here instead of spinning
-        if (rounds >= (u64)n + 1) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: nodes still unassigned after n + 1 rounds");
-        const u32 batch = (u32)std::min<u64>(CL_BATCH, (u64)n + 1 - rounds);
-        HIPCHK(c, hipMemsetAsync(undecided, 0, CL_BATCH * sizeof(u32), c->stream));
-        for (u32 r = 0; r < batch; ++r) {
-            if (D) hipLaunchKernelGGL(k_cl_cover_count, edge_blocks, threads, 0, c->stream, pairs, D, n, (const u32*)rep_of, w.cnt.get());
-            hipLaunchKernelGGL(k_cl_cover_key, nodes, threads, 0, c->stream, n, (const u32*)rep_of, w.cnt.get(), w.key.get(), w.m1.get(), w.m2.get());
-            if (D) hipLaunchKernelGGL(k_cl_cover_max, edge_blocks, threads, 0, c->stream, pairs, D, n, (const unsigned long long*)w.key.get(), w.m1.get());
-            if (D) hipLaunchKernelGGL(k_cl_cover_max, edge_blocks, threads, 0, c->stream, pairs, D, n, (const unsigned long long*)w.m1.get(), w.m2.get());
-            hipLaunchKernelGGL(k_cl_cover_decide, nodes, threads, 0, c->stream, n, (const unsigned long long*)w.m1.get(), (const unsigned long long*)w.m2.get(),
-                               rep_of, undecided + r);
-        }
-        HIPCHK(c, hipGetLastError());
-        u32 left[CL_BATCH];
-        HIPCHK(c, hipMemcpyAsync(left, undecided, sizeof left, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        u32 r = 0;
-        while (r < batch && left[r]) ++r;
-        done = r < batch;
-        rounds += done ? r + 1 : batch;                 // (the rounds behind the first that left no node change nothing)
-    }
-    return LZANI_OK;
-}
-
-// The workspace of a complete-linkage run, allocated whole before the run touches the cluster state: the table of S slots
-// (S for the first round, the largest), the entry list (at most one entry per distinct edge), the compaction's block counts
-// and offsets, per cluster label, size, best weight and best id, and the round's two control words.
-constexpr u64 CL_LINK_MAX_EDGES = 0xFFFFFFEFull;        // 2^32 - 17, as for set cover
-struct LinkWork {
+// Complete linkage.  The workspace: the table of S slots (S for the first round, the largest), the entry list (at most one
+// entry per distinct edge), the compaction's block counts and offsets, per cluster label, size, best weight and best id,
+// and the round's two control words.
+struct LinkUnit {
     DevMem<unsigned long long> tkey, tcnt, tw, lkey, lcnt, lw, bestw;
     DevMem<u32> label, csize, bestid, ucnt, ctl;
     DevMem<u64> uoff;
     u64 S = 1;                                          // of the first round
-    u64 bytes() const
+    u64 bytes = 0;
+    lzani_cluster_link_info info{};
+    int alloc(lzani_ctx* c)
     {
-        return tkey.bytes() + tcnt.bytes() + tw.bytes() + lkey.bytes() + lcnt.bytes() + lw.bytes() + bestw.bytes() + label.bytes() + csize.bytes() +
-               bestid.bytes() + ucnt.bytes() + ctl.bytes() + uoff.bytes();
+        const u32 n = c->cl.info.n;
+        const u64 E = c->cl.info.edges;
+        if (E > CL_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: complete linkage takes at most 2^32 - 17 edge records");
+        S = cluster_table_slots(E);
+        CL_ALLOC(tkey, (size_t)S); CL_ALLOC(tcnt, (size_t)S); CL_ALLOC(tw, (size_t)S);
+        CL_ALLOC(lkey, (size_t)E); CL_ALLOC(lcnt, (size_t)E); CL_ALLOC(lw, (size_t)E);
+        CL_ALLOC(ucnt, (size_t)pf_chunks(S)); CL_ALLOC(uoff, (size_t)pf_chunks(S) + 1);
+        CL_ALLOC(label, n); CL_ALLOC(csize, n); CL_ALLOC(bestw, n); CL_ALLOC(bestid, n);
+        CL_ALLOC(ctl, CL_LINK_CTL);
+        return LZANI_OK;
+    }
+    // The rounds (lzani_kernels_cluster.h): rounds is the number of the first that merged nothing; the info holds the merges,
+    // the distinct edges (the first round's links: every distinct edge is one) and the time of the first insert.
+    int run(lzani_ctx* c, ClusterStage& st)
+    {
+        const u32 n = c->cl.info.n;
+        const u64 E = c->cl.info.edges;
+        const dim3 nodes(pf_blocks(n)), threads(PF_THREADS);
+        u64 L = E;                                      // entries of the round: edge records, then the last round's links
+        u64 rounds = 1, merges = 0, D = 0;
+        float dedup_ms = 0, rounds_ms = 0;
+        StreamSpan span, first;
+        HIPCHK(c, span.begin(c->stream));
+        hipLaunchKernelGGL(k_cl_link_init, nodes, threads, 0, c->stream, n, label, csize, st.rep_of, st.size);
+        for (; L; ++rounds) {                           // (no entry: no link, and the round merges nothing)
+            // the link with the largest value merges in every round: n rounds always do, and a defect ends here instead of spinning
+            if (rounds > (u64)n + 1) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: links still merging after n + 1 rounds");
+            const ClLinkTable t{tkey, tcnt, tw, cluster_table_slots(L)};
+            if (t.S > S) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more link entries than edge records");
+            const dim3 slots(pf_blocks(t.S));
+            if (rounds == 1) HIPCHK(c, first.begin(c->stream));
+            HIPCHK(c, cluster_table_clear(c, t.S, t.key, {{t.w, 0xFF}, {t.cnt, 0}}));
+            HIPCHK(c, hipMemsetAsync(ctl, 0, CL_LINK_CTL * sizeof(u32), c->stream));
+            hipLaunchKernelGGL(k_cl_link_insert, dim3(pf_blocks(L)), threads, 0, c->stream, rounds == 1 ? c->cl.edges.get() : nullptr, lkey, lcnt, lw, L, n,
+                               label, t, ctl);
+            if (rounds == 1) HIPCHK(c, first.end(c->stream));
+            hipLaunchKernelGGL(k_cl_link_clear, nodes, threads, 0, c->stream, n, bestw, bestid);
+            hipLaunchKernelGGL(k_cl_link_bestw, slots, threads, 0, c->stream, t, n, csize, bestw);
+            hipLaunchKernelGGL(k_cl_link_bestid, slots, threads, 0, c->stream, t, n, csize, bestw, bestid);
+            const u64* total = cluster_compact(c, t.S, ucnt, uoff, [&](auto write, u32 chunks) {
+                hipLaunchKernelGGL(k_cl_link_compact<decltype(write)::value>, dim3(chunks), threads, 0, c->stream, t, n, csize, ucnt, uoff, lkey, lcnt, lw);
+            });
+            hipLaunchKernelGGL(k_cl_link_merge, nodes, threads, 0, c->stream, n, bestid, label, csize, ctl);
+            hipLaunchKernelGGL(k_cl_link_relabel, nodes, threads, 0, c->stream, n, label, st.rep_of);
+            HIPCHK(c, hipGetLastError());
+            u32 h_ctl[CL_LINK_CTL] = {0, 0};
+            u64 links = 0;
+            HIPCHK(c, hipMemcpyAsync(h_ctl, ctl, sizeof h_ctl, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&links, total, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (h_ctl[CL_LINK_ERR]) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the cluster-pair table's probe sequence ran out, or an id out of range");
+            if (links > L) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more links than entries");
+            if (rounds == 1) { D = links; HIPCHK(c, first.elapsed(dedup_ms)); }
+            if (!h_ctl[CL_LINK_MERGES]) break;
+            merges += h_ctl[CL_LINK_MERGES];
+            L = links;
+        }
+        HIPCHK(c, span.end(c->stream));
+        HIPCHK(c, span.elapsed(rounds_ms));
+        st.rounds = rounds;
+        info = lzani_cluster_link_info{D, E - D, merges, S, bytes, dedup_ms, rounds_ms};
+        return LZANI_OK;
     }
 };
 
-// the smallest power of two >= 2 * entries (1 for none)
-u64 cluster_link_slots(u64 entries)
-{
-    u64 S = 1;
-    while (S < 2 * entries) S <<= 1;
-    return S;
-}
-
-int cluster_link_alloc(lzani_ctx* c, LinkWork& w)
-{
-    const u32 n = c->cl.info.n;
-    const u64 E = c->cl.info.edges;
-    if (E > CL_LINK_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: complete linkage takes at most 2^32 - 17 edge records");
-    w.S = cluster_link_slots(E);
-    HIPCHK(c, w.tkey.alloc((size_t)w.S)); HIPCHK(c, w.tcnt.alloc((size_t)w.S)); HIPCHK(c, w.tw.alloc((size_t)w.S));
-    HIPCHK(c, w.lkey.alloc((size_t)E)); HIPCHK(c, w.lcnt.alloc((size_t)E)); HIPCHK(c, w.lw.alloc((size_t)E));
-    HIPCHK(c, w.ucnt.alloc((size_t)pf_chunks(w.S))); HIPCHK(c, w.uoff.alloc((size_t)pf_chunks(w.S) + 1));
-    HIPCHK(c, w.label.alloc(n)); HIPCHK(c, w.csize.alloc(n)); HIPCHK(c, w.bestw.alloc(n)); HIPCHK(c, w.bestid.alloc(n));
-    HIPCHK(c, w.ctl.alloc(CL_LINK_CTL));
-    return LZANI_OK;
-}
-
-// The rounds of complete linkage (lzani_kernels_cluster.h): rep_of, the number of the first round that merged nothing, the
-// merges, the distinct edges (the first round's links: every distinct edge is one) and the time of the first insert.
-int cluster_link_rounds(lzani_ctx* c, LinkWork& w, u32* rep_of, u64& rounds, u64& merges, u64& D, float& dedup_ms)
-{
-    const Cluster& k = c->cl;
-    const u32 n = k.info.n;
-    const dim3 nodes(pf_blocks(n)), threads(PF_THREADS);
-    u64 L = k.info.edges;                               // entries of the round: edge records, then the last round's links
-    rounds = 1; merges = 0; D = 0; dedup_ms = 0;
-    StreamSpan first;
-    for (; L; ++rounds) {                               // (no entry: no link, and the round merges nothing)
-        // the link with the largest value merges in every round: n rounds always do, and a defect ends here instead of spinning
-        if (rounds > (u64)n + 1) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: links still merging after n + 1 rounds");
-        const ClLinkTable t{w.tkey.get(), w.tcnt.get(), w.tw.get(), cluster_link_slots(L)};
-        if (t.S > w.S) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more link entries than edge records");
-        const dim3 slots(pf_blocks(t.S));
-        const u32 chunks = (u32)pf_chunks(t.S);
-        if (rounds == 1) HIPCHK(c, first.begin(c->stream));
-        HIPCHK(c, hipMemsetAsync(t.key, 0xFF, (size_t)t.S * 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(t.w, 0xFF, (size_t)t.S * 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(t.cnt, 0, (size_t)t.S * 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LINK_CTL * sizeof(u32), c->stream));
-        hipLaunchKernelGGL(k_cl_link_insert, dim3(pf_blocks(L)), threads, 0, c->stream, rounds == 1 ? (const lzani_cluster_edge*)k.edges.get() : nullptr,
-                           (const unsigned long long*)w.lkey.get(), (const unsigned long long*)w.lcnt.get(), (const unsigned long long*)w.lw.get(), L, n,
-                           (const u32*)w.label.get(), t, w.ctl.get());
-        if (rounds == 1) HIPCHK(c, first.end(c->stream));
-        hipLaunchKernelGGL(k_cl_link_clear, nodes, threads, 0, c->stream, n, w.bestw.get(), w.bestid.get());
-        hipLaunchKernelGGL(k_cl_link_bestw, slots, threads, 0, c->stream, t, n, (const u32*)w.csize.get(), w.bestw.get());
-        hipLaunchKernelGGL(k_cl_link_bestid, slots, threads, 0, c->stream, t, n, (const u32*)w.csize.get(), (const unsigned long long*)w.bestw.get(), w.bestid.get());
-        hipLaunchKernelGGL(k_cl_link_compact<false>, dim3(chunks), threads, 0, c->stream, t, n, (const u32*)w.csize.get(), w.ucnt.get(), (const u64*)w.uoff.get(),
-                           w.lkey.get(), w.lcnt.get(), w.lw.get());
-        hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.ucnt.get(), (u64)chunks, w.uoff.get());
-        hipLaunchKernelGGL(k_cl_link_compact<true>, dim3(chunks), threads, 0, c->stream, t, n, (const u32*)w.csize.get(), w.ucnt.get(), (const u64*)w.uoff.get(),
-                           w.lkey.get(), w.lcnt.get(), w.lw.get());
-        hipLaunchKernelGGL(k_cl_link_merge, nodes, threads, 0, c->stream, n, (const u32*)w.bestid.get(), w.label.get(), w.csize.get(), w.ctl.get());
-        hipLaunchKernelGGL(k_cl_link_relabel, nodes, threads, 0, c->stream, n, (const u32*)w.label.get(), rep_of);
-        HIPCHK(c, hipGetLastError());
-        u32 ctl[CL_LINK_CTL] = {0, 0};
-        u64 links = 0;
-        HIPCHK(c, hipMemcpyAsync(ctl, w.ctl.get(), sizeof ctl, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&links, w.uoff.get() + chunks, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (ctl[CL_LINK_ERR]) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the cluster-pair table's probe sequence ran out, or an id out of range");
-        if (links > L) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more links than entries");
-        if (rounds == 1) { D = links; HIPCHK(c, first.elapsed(dedup_ms)); }
-        if (!ctl[CL_LINK_MERGES]) break;
-        merges += ctl[CL_LINK_MERGES];
-        L = links;
-    }
-    return LZANI_OK;
-}
-
-// The workspace of a Leiden run, allocated whole before the run touches the cluster state: the table of S slots (S for the
-// largest round there can be: 2 * E insertions), the level-0 entry list and the working list of the higher levels (at most
-// one entry per distinct edge each), the compaction's block counts and offsets, the per-node and per-community words of
-// the rounds (two sets of sizes and partitions: a level and the one aggregated from it), and the control words.
-constexpr u64 CL_LEIDEN_MAX_EDGES = 0xFFFFFFEFull;      // 2^32 - 17, as for set cover
-struct LeidenWork {
+// Leiden.  The workspace: the table of S slots (S for the largest round there can be: 2 * E insertions), the level-0 entry
+// list and the working list of the higher levels (at most one entry per distinct edge each), the compaction's block counts
+// and offsets, the per-node and per-community words of the rounds (two sets of sizes and partitions: a level and the one
+// aggregated from it), and the control words.
+struct LeidenUnit {
     DevMem<unsigned long long> tkey, tval, e0key, wkey, bestd, cd, quality;
     DevMem<i64> e0q, wq, ownw, valown, ext;             // ownw: W(v, own) of a moving round, W(v, P(v)) of a refinement
     DevMem<u32> s, s2, P, P2, R, SP, SR, cntr, well, bestid, cv, newlab, minm, node_of, flag, ucnt, ctl;
     DevMem<u64> uoff, below;
     u64 S = 1;
-    u64 bytes() const
+    u64 bytes = 0;
+    lzani_cluster_leiden_info info{};
+    int alloc(lzani_ctx* c)
     {
-        return tkey.bytes() + tval.bytes() + e0key.bytes() + wkey.bytes() + bestd.bytes() + cd.bytes() + quality.bytes() + e0q.bytes() + wq.bytes() +
-               ownw.bytes() + valown.bytes() + ext.bytes() + s.bytes() + s2.bytes() + P.bytes() + P2.bytes() + R.bytes() + SP.bytes() + SR.bytes() +
-               cntr.bytes() + well.bytes() + bestid.bytes() + cv.bytes() + newlab.bytes() + minm.bytes() + node_of.bytes() + flag.bytes() +
-               ucnt.bytes() + ctl.bytes() + uoff.bytes() + below.bytes();
+        const u32 n = c->cl.info.n;
+        const u64 E = c->cl.info.edges;
+        if (n > CL_LEIDEN_MAX_N) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: Leiden takes at most 2^21 genomes");
+        if (E > CL_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: Leiden takes at most 2^32 - 17 edge records");
+        S = cluster_table_slots(2 * E);
+        CL_ALLOC(tkey, (size_t)S); CL_ALLOC(tval, (size_t)S);
+        CL_ALLOC(e0key, (size_t)E); CL_ALLOC(e0q, (size_t)E); CL_ALLOC(wkey, (size_t)E); CL_ALLOC(wq, (size_t)E);
+        CL_ALLOC(ucnt, (size_t)pf_chunks(S)); CL_ALLOC(uoff, (size_t)pf_chunks(S) + 1);
+        CL_ALLOC(bestd, n); CL_ALLOC(cd, n); CL_ALLOC(ownw, n); CL_ALLOC(valown, n); CL_ALLOC(ext, n);
+        CL_ALLOC(s, n); CL_ALLOC(s2, n); CL_ALLOC(P, n); CL_ALLOC(P2, n); CL_ALLOC(R, n);
+        CL_ALLOC(SP, n); CL_ALLOC(SR, n); CL_ALLOC(cntr, n); CL_ALLOC(well, n); CL_ALLOC(bestid, n);
+        CL_ALLOC(cv, n); CL_ALLOC(newlab, n); CL_ALLOC(minm, 2 * (size_t)n); CL_ALLOC(node_of, n);
+        CL_ALLOC(flag, n); CL_ALLOC(below, (size_t)n + 1);
+        CL_ALLOC(quality, 1); CL_ALLOC(ctl, CL_LD_CTL);
+        return LZANI_OK;
     }
-};
-
-int cluster_leiden_alloc(lzani_ctx* c, LeidenWork& w)
-{
-    const u32 n = c->cl.info.n;
-    const u64 E = c->cl.info.edges;
-    if (n > CL_LEIDEN_MAX_N) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: Leiden takes at most 2^21 genomes");
-    if (E > CL_LEIDEN_MAX_EDGES) return fail(c, LZANI_ERR_ARG, "lzani_cluster_run: Leiden takes at most 2^32 - 17 edge records");
-    w.S = cluster_link_slots(2 * E);
-    HIPCHK(c, w.tkey.alloc((size_t)w.S)); HIPCHK(c, w.tval.alloc((size_t)w.S));
-    HIPCHK(c, w.e0key.alloc((size_t)E)); HIPCHK(c, w.e0q.alloc((size_t)E)); HIPCHK(c, w.wkey.alloc((size_t)E)); HIPCHK(c, w.wq.alloc((size_t)E));
-    HIPCHK(c, w.ucnt.alloc((size_t)pf_chunks(w.S))); HIPCHK(c, w.uoff.alloc((size_t)pf_chunks(w.S) + 1));
-    HIPCHK(c, w.bestd.alloc(n)); HIPCHK(c, w.cd.alloc(n)); HIPCHK(c, w.ownw.alloc(n)); HIPCHK(c, w.valown.alloc(n)); HIPCHK(c, w.ext.alloc(n));
-    HIPCHK(c, w.s.alloc(n)); HIPCHK(c, w.s2.alloc(n)); HIPCHK(c, w.P.alloc(n)); HIPCHK(c, w.P2.alloc(n)); HIPCHK(c, w.R.alloc(n));
-    HIPCHK(c, w.SP.alloc(n)); HIPCHK(c, w.SR.alloc(n)); HIPCHK(c, w.cntr.alloc(n)); HIPCHK(c, w.well.alloc(n)); HIPCHK(c, w.bestid.alloc(n));
-    HIPCHK(c, w.cv.alloc(n)); HIPCHK(c, w.newlab.alloc(n)); HIPCHK(c, w.minm.alloc(2 * (size_t)n)); HIPCHK(c, w.node_of.alloc(n));
-    HIPCHK(c, w.flag.alloc(n)); HIPCHK(c, w.below.alloc((size_t)n + 1));
-    HIPCHK(c, w.quality.alloc(1)); HIPCHK(c, w.ctl.alloc(CL_LD_CTL));
-    return LZANI_OK;
-}
-
-// A phase on a level of m nodes: round(r) launches one round whose movers go to ctl[CL_LD_MOVERS + r] (and, where it counts
-// them, the communities behind it to ctl[CL_LD_COMMS + r]); batches of CL_LD_BATCH rounds between two reads of the control
-// words, as a round behind the one without a mover changes nothing.  rounds: up to the first without a mover, that one
-// included; movers: their sum; comms: the communities behind the last round.
-template <class Round>
-int cluster_leiden_phase(lzani_ctx* c, LeidenWork& w, u32 m, const char* what, Round round, u64& rounds, u64& movers, u32& comms)
-{
-    const u64 cap = CL_LEIDEN_CAP_MUL * m + CL_LEIDEN_CAP_ADD;
-    rounds = 0; movers = 0; comms = 0;
-    for (bool done = false; !done;) {
-        // a safety stop, not a bound that is proved: see include/lzani.h
-        if (rounds >= cap) return fail(c, LZANI_ERR_DEVICE, std::string("lzani_cluster_run: Leiden's ") + what + " still moves nodes after 64 * n + 64 rounds");
-        const u32 batch = (u32)std::min<u64>(CL_LD_BATCH, cap - rounds);
-        HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
-        for (u32 r = 0; r < batch; ++r) HIPCHK(c, round(r));
-        HIPCHK(c, hipGetLastError());
-        u32 ctl[CL_LD_CTL];
-        HIPCHK(c, hipMemcpyAsync(ctl, w.ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (ctl[CL_LD_ERR]) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the node-community table's probe sequence ran out, or an id out of range");
-        u32 r = 0;
-        while (r < batch && ctl[CL_LD_MOVERS + r]) movers += ctl[CL_LD_MOVERS + r++];
-        done = r < batch;
-        rounds += done ? r + 1 : batch;
-        comms = ctl[CL_LD_COMMS + (done ? r : batch - 1)];
+    // A phase on a level of m nodes: round(r) launches one round whose movers go to ctl[CL_LD_MOVERS + r] (and, where it
+    // counts them, the communities behind it to ctl[CL_LD_COMMS + r]).  rounds: up to the first without a mover, that one
+    // included; movers: their sum; comms: the communities behind the last round.
+    template <class Round>
+    int phase(lzani_ctx* c, u32 m, const char* still, Round round, u64& rounds, u64& movers, u32& comms)
+    {
+        // the cap is a safety stop, not a bound that is proved: see include/lzani.h
+        const ClRounds p{CL_LD_BATCH, CL_LEIDEN_CAP_MUL * m + CL_LEIDEN_CAP_ADD, still, ctl, CL_LD_CTL, CL_LD_MOVERS};
+        movers = 0; comms = 0;
+        return cluster_rounds(c, p, rounds, round, [&](const u32* h, u32 moving, u32 last) {
+            if (h[CL_LD_ERR]) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the node-community table's probe sequence ran out, or an id out of range");
+            for (u32 r = 0; r < moving; ++r) movers += h[CL_LD_MOVERS + r];
+            comms = h[CL_LD_COMMS + last];
+            return (int)LZANI_OK;
+        });
     }
-    return LZANI_OK;
-}
-
-// The table of a round cleared: the keys all ones, the values `fill` bytes.
-hipError_t cluster_leiden_clear(lzani_ctx* c, const ClLdTable& t, int fill)
-{
-    const hipError_t e = hipMemsetAsync(t.key, 0xFF, (size_t)t.S * 8, c->stream);
-    return e != hipSuccess ? e : hipMemsetAsync(t.val, fill, (size_t)t.S * 8, c->stream);
-}
-
-// The table's occupied slots into the entry list (key, q); their number at w.uoff[pf_chunks(t.S)].
-void cluster_leiden_compact(lzani_ctx* c, LeidenWork& w, const ClLdTable& t, unsigned long long* key, i64* q)
-{
-    const u32 chunks = (u32)pf_chunks(t.S);
-    const dim3 threads(PF_THREADS);
-    hipLaunchKernelGGL(k_ld_compact<false>, dim3(chunks), threads, 0, c->stream, t, w.ucnt.get(), (const u64*)w.uoff.get(), key, q);
-    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.ucnt.get(), (u64)chunks, w.uoff.get());
-    hipLaunchKernelGGL(k_ld_compact<true>, dim3(chunks), threads, 0, c->stream, t, w.ucnt.get(), (const u64*)w.uoff.get(), key, q);
-}
-
-// The iterations of Leiden (lzani_kernels_cluster.h): rep_of (v at the start) and what the run did.
-int cluster_leiden_rounds(lzani_ctx* c, LeidenWork& w, u32* rep_of, lzani_cluster_leiden_info& out)
-{
-    const Cluster& k = c->cl;
-    const u32 n = k.info.n;
-    const u64 E = k.info.edges;
-    const i64 g = cluster_leiden_g(c->leiden_resolution);
-    const dim3 threads(PF_THREADS), all(pf_blocks(n));
-    out = lzani_cluster_leiden_info{};
-    out.resolution_q = (u64)g; out.table_slots = w.S; out.workspace_bytes = w.bytes();
-    // the distinct edges with their smallest q: the level-0 entry list
-    StreamSpan dedup, span;
-    u64 D = 0;
-    HIPCHK(c, dedup.begin(c->stream));
-    if (E) {
-        const ClLdTable t{w.tkey.get(), w.tval.get(), cluster_link_slots(E)};
-        HIPCHK(c, cluster_leiden_clear(c, t, 0xFF));
-        HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
-        hipLaunchKernelGGL(k_ld_dedup, dim3(pf_blocks(E)), threads, 0, c->stream, (const lzani_cluster_edge*)k.edges.get(), E, n, t, w.ctl.get());
-        cluster_leiden_compact(c, w, t, w.e0key.get(), w.e0q.get());
-        HIPCHK(c, hipGetLastError());
-        u32 err = 0;
-        HIPCHK(c, hipMemcpyAsync(&err, w.ctl.get() + CL_LD_ERR, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&D, w.uoff.get() + pf_chunks(t.S), 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (err) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the edge table's probe sequence ran out, or an id out of range");
-        if (D > E) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more distinct edges than edge records");
+    // The table's occupied slots into the entry list (key, q); returns where their number is.
+    const u64* compact(lzani_ctx* c, const ClLdTable& t, unsigned long long* key, i64* q)
+    {
+        return cluster_compact(c, t.S, ucnt, uoff, [&](auto write, u32 chunks) {
+            hipLaunchKernelGGL(k_ld_compact<decltype(write)::value>, dim3(chunks), dim3(PF_THREADS), 0, c->stream, t, ucnt, uoff, key, q);
+        });
     }
-    HIPCHK(c, dedup.end(c->stream));
-    out.distinct_edges = D; out.duplicate_edges = E - D;
-    HIPCHK(c, span.begin(c->stream));
-    for (int it = 0; it < c->leiden_iterations; ++it) {
-        out.iterations++;
-        u32 m = n;                                      // the level: its nodes, its entries and where they are
-        u64 L = D;
-        const unsigned long long* lkey = w.e0key.get();
-        const i64* lq = w.e0q.get();
-        hipLaunchKernelGGL(k_ld_level0, all, threads, 0, c->stream, n, (const u32*)rep_of, w.s.get(), w.P.get(), w.node_of.get());
-        HIPCHK(c, hipMemsetAsync(w.SP, 0, (size_t)n * 4, c->stream));
-        hipLaunchKernelGGL(k_ld_sizes, all, threads, 0, c->stream, n, (const u32*)w.s.get(), (const u32*)w.P.get(), w.SP.get(), (u32*)nullptr, (u32*)nullptr);
-        u64 moved_in_iteration = 0;
-        for (;;) {
-            out.levels++;
-            const dim3 nodes(pf_blocks(m)), entries(pf_blocks(L));
-            const ClLdTable t{w.tkey.get(), w.tval.get(), cluster_link_slots(2 * L)};
-            if (t.S > w.S) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more entries than edge records");
-            const dim3 slots(pf_blocks(t.S));
-            u32 *s = w.s.get(), *P = w.P.get(), *R = w.R.get(), *SP = w.SP.get(), *SR = w.SR.get(), *cntr = w.cntr.get(), *ctl = w.ctl.get();
-            u64 rounds = 0, moved = 0, merged = 0;
-            u32 comms = 0;
-            auto share = [&](u32* part, u32* S, u32* cnt, u32 r, bool count_comms) {         // the passes both kinds of round end in
-                hipLaunchKernelGGL(k_ld_cand_max, nodes, threads, 0, c->stream, m, (const u32*)part, (const unsigned long long*)w.bestd.get(),
-                                   (const u32*)w.bestid.get(), w.cd.get());
-                hipLaunchKernelGGL(k_ld_cand_min, nodes, threads, 0, c->stream, m, (const u32*)part, (const unsigned long long*)w.bestd.get(),
-                                   (const u32*)w.bestid.get(), (const unsigned long long*)w.cd.get(), w.cv.get());
-                hipLaunchKernelGGL(k_ld_decide, nodes, threads, 0, c->stream, m, (const u32*)part, (const unsigned long long*)w.bestd.get(),
-                                   (const u32*)w.bestid.get(), (const u32*)w.cv.get(), w.newlab.get(), w.minm.get(), ctl + CL_LD_MOVERS + r);
-                hipLaunchKernelGGL(k_ld_minm, nodes, threads, 0, c->stream, m, (const u32*)w.newlab.get(), w.minm.get());
-                hipLaunchKernelGGL(k_ld_newid, nodes, threads, 0, c->stream, m, (const u32*)w.newlab.get(), (const u32*)w.minm.get(), part, S, cnt);
-                hipLaunchKernelGGL(k_ld_sizes, nodes, threads, 0, c->stream, m, (const u32*)s, (const u32*)part, S, cnt,
-                                   count_comms ? ctl + CL_LD_COMMS + r : (u32*)nullptr);
-            };
-            auto move_round = [&](u32 r) -> hipError_t {
-                if (hipError_t e = cluster_leiden_clear(c, t, 0)) return e;
-                if (hipError_t e = hipMemsetAsync(w.ownw, 0, (size_t)m * 8, c->stream)) return e;
-                if (L) hipLaunchKernelGGL(k_ld_move_insert, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)P, t, ctl);
-                hipLaunchKernelGGL(k_ld_move_stay, slots, threads, 0, c->stream, t, m, (const u32*)P, w.ownw.get());
-                hipLaunchKernelGGL(k_ld_move_node, nodes, threads, 0, c->stream, m, g, (const u32*)s, (const u32*)P, (const u32*)SP, (const i64*)w.ownw.get(),
-                                   w.valown.get(), w.bestd.get(), w.bestid.get(), w.cd.get(), w.cv.get());
-                hipLaunchKernelGGL(k_ld_move_bestd, slots, threads, 0, c->stream, t, m, g, (const u32*)s, (const u32*)P, (const u32*)SP,
-                                   (const i64*)w.valown.get(), w.bestd.get());
-                hipLaunchKernelGGL(k_ld_move_bestid, slots, threads, 0, c->stream, t, m, g, (const u32*)s, (const u32*)P, (const u32*)SP,
-                                   (const i64*)w.valown.get(), (const unsigned long long*)w.bestd.get(), w.bestid.get());
-                share(P, SP, nullptr, r, true);
-                return hipSuccess;
-            };
-            if (int rc = cluster_leiden_phase(c, w, m, "moving phase", move_round, rounds, moved, comms)) return rc;
-            out.move_rounds += rounds; out.moves += moved; moved_in_iteration += moved;
-            if (comms == m) break;                      // every community is one level node
-            hipLaunchKernelGGL(k_ld_refine_init, nodes, threads, 0, c->stream, m, (const u32*)s, R, SR, cntr, w.ownw.get());
-            if (L) hipLaunchKernelGGL(k_ld_wp, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)P, w.ownw.get());
-            hipLaunchKernelGGL(k_ld_well, nodes, threads, 0, c->stream, m, g, (const u32*)s, (const u32*)P, (const u32*)SP, (const i64*)w.ownw.get(), w.well.get());
-            const ClLdRefine rf{g, s, P, R, SP, SR, cntr, w.well.get(), w.ext.get()};
-            auto refine_round = [&](u32 r) -> hipError_t {
-                if (hipError_t e = cluster_leiden_clear(c, t, 0)) return e;
-                if (hipError_t e = hipMemsetAsync(w.ext, 0, (size_t)m * 8, c->stream)) return e;
-                if (L) hipLaunchKernelGGL(k_ld_refine_insert, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)P, (const u32*)R, t, w.ext.get(), ctl);
-                hipLaunchKernelGGL(k_ld_refine_node, nodes, threads, 0, c->stream, m, w.bestd.get(), w.bestid.get(), w.cd.get(), w.cv.get());
-                hipLaunchKernelGGL(k_ld_refine_bestd, slots, threads, 0, c->stream, t, m, rf, w.bestd.get());
-                hipLaunchKernelGGL(k_ld_refine_bestid, slots, threads, 0, c->stream, t, m, rf, (const unsigned long long*)w.bestd.get(), w.bestid.get());
-                share(R, SR, cntr, r, false);
-                return hipSuccess;
-            };
-            if (int rc = cluster_leiden_phase(c, w, m, "refinement", refine_round, rounds, merged, comms)) return rc;
-            out.refine_rounds += rounds; out.merges += merged;
-            if (!moved && !merged) break;               // nothing can change any more
-            // aggregation: the R-communities, numbered in ascending order of their smallest member, and the entries between them
-            hipLaunchKernelGGL(k_ld_agg_flags, nodes, threads, 0, c->stream, m, (const u32*)R, w.flag.get());
-            hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.flag.get(), (u64)m, w.below.get());
-            hipLaunchKernelGGL(k_ld_agg_nodes, nodes, threads, 0, c->stream, m, (const u32*)R, (const u32*)P, (const u32*)SR, (const u64*)w.below.get(),
-                               w.s2.get(), w.P2.get());
-            hipLaunchKernelGGL(k_ld_agg_nodeof, all, threads, 0, c->stream, n, m, (const u32*)R, (const u64*)w.below.get(), w.node_of.get());
-            const ClLdTable ta{w.tkey.get(), w.tval.get(), cluster_link_slots(L)};
-            HIPCHK(c, cluster_leiden_clear(c, ta, 0));
-            HIPCHK(c, hipMemsetAsync(w.ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
-            if (L) hipLaunchKernelGGL(k_ld_agg_insert, entries, threads, 0, c->stream, lkey, lq, L, m, (const u32*)R, (const u64*)w.below.get(), ta, ctl);
-            cluster_leiden_compact(c, w, ta, w.wkey.get(), w.wq.get());
-            HIPCHK(c, hipGetLastError());
-            u64 m2 = 0, L2 = 0;
-            u32 err = 0;
-            HIPCHK(c, hipMemcpyAsync(&m2, w.below.get() + m, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(&L2, w.uoff.get() + pf_chunks(ta.S), 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(&err, w.ctl.get() + CL_LD_ERR, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (err) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the contraction table's probe sequence ran out, or an id out of range");
-            if (!m2 || m2 > m || L2 > L) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: an aggregated level larger than the level it comes from");
-            std::swap(w.s, w.s2); std::swap(w.P, w.P2);
-            m = (u32)m2; L = L2; lkey = w.wkey.get(); lq = w.wq.get();
-            HIPCHK(c, hipMemsetAsync(w.SP, 0, (size_t)m * 4, c->stream));
-            hipLaunchKernelGGL(k_ld_sizes, dim3(pf_blocks(m)), threads, 0, c->stream, m, (const u32*)w.s.get(), (const u32*)w.P.get(), w.SP.get(), (u32*)nullptr,
-                               (u32*)nullptr);
-        }
-        // rep_of: the smallest original id of every final community
-        hipLaunchKernelGGL(k_ld_final, all, threads, 0, c->stream, n, m, (const u32*)w.node_of.get(), (const u32*)w.P.get(), w.newlab.get(), w.minm.get());
-        hipLaunchKernelGGL(k_ld_minm, all, threads, 0, c->stream, n, (const u32*)w.newlab.get(), w.minm.get());
-        hipLaunchKernelGGL(k_ld_newid, all, threads, 0, c->stream, n, (const u32*)w.newlab.get(), (const u32*)w.minm.get(), rep_of, w.SP.get(), (u32*)nullptr);
-        HIPCHK(c, hipGetLastError());
-        if (!moved_in_iteration) break;
-    }
-    // Q of the result on the original graph (k_ld_newid left SP cleared)
-    HIPCHK(c, hipMemsetAsync(w.quality, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_ld_sizes, all, threads, 0, c->stream, n, (const u32*)nullptr, (const u32*)rep_of, w.SP.get(), (u32*)nullptr, (u32*)nullptr);
-    if (D) hipLaunchKernelGGL(k_ld_quality_edges, dim3(pf_blocks(D)), threads, 0, c->stream, (const unsigned long long*)w.e0key.get(), (const i64*)w.e0q.get(), D, n,
-                              (const u32*)rep_of, w.quality.get());
-    hipLaunchKernelGGL(k_ld_quality_nodes, all, threads, 0, c->stream, n, g, (const u32*)w.SP.get(), w.quality.get());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, span.end(c->stream));
-    unsigned long long quality = 0;
-    HIPCHK(c, hipMemcpyAsync(&quality, w.quality.get(), 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float dedup_ms = 0, rounds_ms = 0;
-    HIPCHK(c, dedup.elapsed(dedup_ms));
-    HIPCHK(c, span.elapsed(rounds_ms));
-    out.quality = (int64_t)quality; out.dedup_ms = dedup_ms; out.rounds_ms = rounds_ms;
-    return LZANI_OK;
-}
-
-// What every algorithm's run works in, and what it leaves: allocated whole before the run touches the cluster state, like
-// the workspaces of set cover, complete linkage and Leiden above.
-struct StageWork {
-    DevMem<u32> parent, state, blocked, flag, size, counters, undecided;     // parent, state, blocked, best: SINGLE and the greedy forms
-    DevMem<unsigned long long> best;
-    DevMem<u64> below;
-    DevMem<u32> rep_of, cluster_of;                                          // the run's result
-};
-bool cluster_algo_plain(int algo) { return algo != LZANI_CLUSTER_SET_COVER && algo != LZANI_CLUSTER_COMPLETE && algo != LZANI_CLUSTER_LEIDEN; }
-int cluster_stage_alloc(lzani_ctx* c, int algo, StageWork& s)
-{
-    const u32 n = c->cl.info.n;
-    if (cluster_algo_plain(algo)) { HIPCHK(c, s.parent.alloc(n)); HIPCHK(c, s.state.alloc(n)); HIPCHK(c, s.blocked.alloc(n)); HIPCHK(c, s.best.alloc(n)); }
-    HIPCHK(c, s.flag.alloc(n)); HIPCHK(c, s.size.alloc(n)); HIPCHK(c, s.below.alloc((size_t)n + 1));
-    HIPCHK(c, s.counters.alloc(CL_COUNTERS)); HIPCHK(c, s.undecided.alloc(CL_BATCH));
-    HIPCHK(c, s.rep_of.alloc(n)); HIPCHK(c, s.cluster_of.alloc(n));
-    return LZANI_OK;
-}
-
-// The run on the context's edges: fills sw.rep_of, sw.cluster_of and the run's part of `info` (set cover: `cover`, from `work`;
-// complete linkage: `link`, from `lwork`).  It allocates nothing.
-int cluster_run_stage(lzani_ctx* c, int algo, StageWork& sw, lzani_cluster_info& info, CoverWork& work,
-                      lzani_cluster_cover_info& cover, LinkWork& lwork, lzani_cluster_link_info& link, LeidenWork& ldwork,
-                      lzani_cluster_leiden_info& leiden)
-{
-    const Cluster& k = c->cl;
-    const u32 n = k.info.n;
-    const u64 E = k.info.edges;
-    const lzani_cluster_edge* edges = k.edges.get();
-    const bool set_cover = algo == LZANI_CLUSTER_SET_COVER, complete = algo == LZANI_CLUSTER_COMPLETE, is_leiden = algo == LZANI_CLUSTER_LEIDEN;
-    const bool plain = cluster_algo_plain(algo);
-    DevMem<u32>&parent = sw.parent, &state = sw.state, &blocked = sw.blocked, &flag = sw.flag, &size = sw.size, &counters = sw.counters, &undecided = sw.undecided;
-    DevMem<unsigned long long>& best = sw.best;
-    DevMem<u64>& below = sw.below;
-    DevMem<u32>&rep_of = sw.rep_of, &cluster_of = sw.cluster_of;
-    const dim3 nodes(pf_blocks(n)), edge_blocks(pf_blocks(E)), threads(PF_THREADS);
-    StreamSpan span;
-    HIPCHK(c, span.begin(c->stream));
-    HIPCHK(c, hipMemsetAsync(counters, 0, CL_COUNTERS * sizeof(u32), c->stream));
-    if (plain) hipLaunchKernelGGL(k_cl_init, nodes, threads, 0, c->stream, n, parent.get(), state.get(), blocked.get(), best.get(), size.get());
-    u64 rounds = 1;
-    if (set_cover) {
-        StreamSpan dedup, cover_rounds;
+    // The iterations (lzani_kernels_cluster.h): rep_of (v at the start), rounds, and what the run did.
+    int run(lzani_ctx* c, ClusterStage& st)
+    {
+        const u32 n = c->cl.info.n;
+        const u64 E = c->cl.info.edges;
+        const i64 g = cluster_leiden_g(c->leiden_resolution);
+        const dim3 threads(PF_THREADS), all(pf_blocks(n));
+        u32* rep_of = st.rep_of;
+        hipLaunchKernelGGL(k_ld_init, all, threads, 0, c->stream, n, rep_of, st.size);
+        lzani_cluster_leiden_info& out = info;
+        out = lzani_cluster_leiden_info{};
+        out.resolution_q = (u64)g; out.table_slots = S; out.workspace_bytes = bytes;
+        // the distinct edges with their smallest q: the level-0 entry list
+        StreamSpan dedup, span;
         u64 D = 0;
         HIPCHK(c, dedup.begin(c->stream));
-        if (int rc = cluster_cover_dedup(c, work, D)) return rc;
+        if (E) {
+            const ClLdTable t{tkey, tval, cluster_table_slots(E)};
+            HIPCHK(c, cluster_table_clear(c, t.S, t.key, {{t.val, 0xFF}}));
+            HIPCHK(c, hipMemsetAsync(ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
+            hipLaunchKernelGGL(k_ld_dedup, dim3(pf_blocks(E)), threads, 0, c->stream, c->cl.edges, E, n, t, ctl);
+            const u64* total = compact(c, t, e0key, e0q);
+            HIPCHK(c, hipGetLastError());
+            u32 err = 0;
+            HIPCHK(c, hipMemcpyAsync(&err, ctl.get() + CL_LD_ERR, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&D, total, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (err) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the edge table's probe sequence ran out, or an id out of range");
+            if (D > E) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more distinct edges than edge records");
+        }
         HIPCHK(c, dedup.end(c->stream));
-        HIPCHK(c, cover_rounds.begin(c->stream));
-        hipLaunchKernelGGL(k_cl_cover_init, nodes, threads, 0, c->stream, n, rep_of.get(), work.cnt.get(), size.get());
-        if (int rc = cluster_cover_rounds(c, work, D, rep_of.get(), undecided.get(), rounds)) return rc;
-        HIPCHK(c, cover_rounds.end(c->stream));
+        out.distinct_edges = D; out.duplicate_edges = E - D;
+        HIPCHK(c, span.begin(c->stream));
+        for (int it = 0; it < c->leiden_iterations; ++it) {
+            out.iterations++;
+            u32 m = n;                                  // the level: its nodes, its entries and where they are
+            u64 L = D;
+            const unsigned long long* lkey = e0key;
+            const i64* lq = e0q;
+            hipLaunchKernelGGL(k_ld_level0, all, threads, 0, c->stream, n, rep_of, s, P, node_of);
+            HIPCHK(c, hipMemsetAsync(SP, 0, (size_t)n * 4, c->stream));
+            hipLaunchKernelGGL(k_ld_sizes, all, threads, 0, c->stream, n, s, P, SP, (u32*)nullptr, (u32*)nullptr);
+            u64 moved_in_iteration = 0;
+            for (;;) {
+                out.levels++;
+                const dim3 nodes(pf_blocks(m)), entries(pf_blocks(L));
+                const ClLdTable t{tkey, tval, cluster_table_slots(2 * L)};
+                if (t.S > S) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: more entries than edge records");
+                const dim3 slots(pf_blocks(t.S));
+                u64 rounds = 0, moved = 0, merged = 0;
+                u32 comms = 0;
+                auto share = [&](u32* part, u32* sizes, u32* cnt, u32 r, bool count_comms) {      // the passes both kinds of round end in
+                    hipLaunchKernelGGL(k_ld_cand_max, nodes, threads, 0, c->stream, m, part, bestd, bestid, cd);
+                    hipLaunchKernelGGL(k_ld_cand_min, nodes, threads, 0, c->stream, m, part, bestd, bestid, cd, cv);
+                    hipLaunchKernelGGL(k_ld_decide, nodes, threads, 0, c->stream, m, part, bestd, bestid, cv, newlab, minm, ctl.get() + CL_LD_MOVERS + r);
+                    hipLaunchKernelGGL(k_ld_minm, nodes, threads, 0, c->stream, m, newlab, minm);
+                    hipLaunchKernelGGL(k_ld_newid, nodes, threads, 0, c->stream, m, newlab, minm, part, sizes, cnt);
+                    hipLaunchKernelGGL(k_ld_sizes, nodes, threads, 0, c->stream, m, s, part, sizes, cnt, count_comms ? ctl.get() + CL_LD_COMMS + r : (u32*)nullptr);
+                };
+                auto move_round = [&](u32 r) -> hipError_t {
+                    if (hipError_t e = cluster_table_clear(c, t.S, t.key, {{t.val, 0}})) return e;
+                    if (hipError_t e = hipMemsetAsync(ownw, 0, (size_t)m * 8, c->stream)) return e;
+                    if (L) hipLaunchKernelGGL(k_ld_move_insert, entries, threads, 0, c->stream, lkey, lq, L, m, P, t, ctl);
+                    hipLaunchKernelGGL(k_ld_move_stay, slots, threads, 0, c->stream, t, m, P, ownw);
+                    hipLaunchKernelGGL(k_ld_move_node, nodes, threads, 0, c->stream, m, g, s, P, SP, ownw, valown, bestd, bestid, cd, cv);
+                    hipLaunchKernelGGL(k_ld_move_bestd, slots, threads, 0, c->stream, t, m, g, s, P, SP, valown, bestd);
+                    hipLaunchKernelGGL(k_ld_move_bestid, slots, threads, 0, c->stream, t, m, g, s, P, SP, valown, bestd, bestid);
+                    share(P, SP, nullptr, r, true);
+                    return hipSuccess;
+                };
+                if (int rc = phase(c, m, "lzani_cluster_run: Leiden's moving phase still moves nodes after 64 * n + 64 rounds", move_round, rounds, moved, comms)) return rc;
+                out.move_rounds += rounds; out.moves += moved; moved_in_iteration += moved;
+                if (comms == m) break;                  // every community is one level node
+                hipLaunchKernelGGL(k_ld_refine_init, nodes, threads, 0, c->stream, m, s, R, SR, cntr, ownw);
+                if (L) hipLaunchKernelGGL(k_ld_wp, entries, threads, 0, c->stream, lkey, lq, L, m, P, ownw);
+                hipLaunchKernelGGL(k_ld_well, nodes, threads, 0, c->stream, m, g, s, P, SP, ownw, well);
+                const ClLdRefine rf{g, s, P, R, SP, SR, cntr, well, ext};
+                auto refine_round = [&](u32 r) -> hipError_t {
+                    if (hipError_t e = cluster_table_clear(c, t.S, t.key, {{t.val, 0}})) return e;
+                    if (hipError_t e = hipMemsetAsync(ext, 0, (size_t)m * 8, c->stream)) return e;
+                    if (L) hipLaunchKernelGGL(k_ld_refine_insert, entries, threads, 0, c->stream, lkey, lq, L, m, P, R, t, ext, ctl);
+                    hipLaunchKernelGGL(k_ld_refine_node, nodes, threads, 0, c->stream, m, bestd, bestid, cd, cv);
+                    hipLaunchKernelGGL(k_ld_refine_bestd, slots, threads, 0, c->stream, t, m, rf, bestd);
+                    hipLaunchKernelGGL(k_ld_refine_bestid, slots, threads, 0, c->stream, t, m, rf, bestd, bestid);
+                    share(R, SR, cntr, r, false);
+                    return hipSuccess;
+                };
+                if (int rc = phase(c, m, "lzani_cluster_run: Leiden's refinement still moves nodes after 64 * n + 64 rounds", refine_round, rounds, merged, comms)) return rc;
+                out.refine_rounds += rounds; out.merges += merged;
+                if (!moved && !merged) break;           // nothing can change any more
+                // aggregation: the R-communities, numbered in ascending order of their smallest member, and the entries between them
+                hipLaunchKernelGGL(k_ld_agg_flags, nodes, threads, 0, c->stream, m, R, flag);
+                hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, flag, (u64)m, below);
+                hipLaunchKernelGGL(k_ld_agg_nodes, nodes, threads, 0, c->stream, m, R, P, SR, below, s2, P2);
+                hipLaunchKernelGGL(k_ld_agg_nodeof, all, threads, 0, c->stream, n, m, R, below, node_of);
+                const ClLdTable ta{tkey, tval, cluster_table_slots(L)};
+                HIPCHK(c, cluster_table_clear(c, ta.S, ta.key, {{ta.val, 0}}));
+                HIPCHK(c, hipMemsetAsync(ctl, 0, CL_LD_CTL * sizeof(u32), c->stream));
+                if (L) hipLaunchKernelGGL(k_ld_agg_insert, entries, threads, 0, c->stream, lkey, lq, L, m, R, below, ta, ctl);
+                const u64* total = compact(c, ta, wkey, wq);
+                HIPCHK(c, hipGetLastError());
+                u64 m2 = 0, L2 = 0;
+                u32 err = 0;
+                HIPCHK(c, hipMemcpyAsync(&m2, below.get() + m, 8, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipMemcpyAsync(&L2, total, 8, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipMemcpyAsync(&err, ctl.get() + CL_LD_ERR, 4, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                if (err) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: the contraction table's probe sequence ran out, or an id out of range");
+                if (!m2 || m2 > m || L2 > L) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: an aggregated level larger than the level it comes from");
+                std::swap(s, s2); std::swap(P, P2);
+                m = (u32)m2; L = L2; lkey = wkey; lq = wq;
+                HIPCHK(c, hipMemsetAsync(SP, 0, (size_t)m * 4, c->stream));
+                hipLaunchKernelGGL(k_ld_sizes, dim3(pf_blocks(m)), threads, 0, c->stream, m, s, P, SP, (u32*)nullptr, (u32*)nullptr);
+            }
+            // rep_of: the smallest original id of every final community
+            hipLaunchKernelGGL(k_ld_final, all, threads, 0, c->stream, n, m, node_of, P, newlab, minm);
+            hipLaunchKernelGGL(k_ld_minm, all, threads, 0, c->stream, n, newlab, minm);
+            hipLaunchKernelGGL(k_ld_newid, all, threads, 0, c->stream, n, newlab, minm, rep_of, SP, (u32*)nullptr);
+            HIPCHK(c, hipGetLastError());
+            if (!moved_in_iteration) break;
+        }
+        // Q of the result on the original graph (k_ld_newid left SP cleared)
+        HIPCHK(c, hipMemsetAsync(quality, 0, 8, c->stream));
+        hipLaunchKernelGGL(k_ld_sizes, all, threads, 0, c->stream, n, (const u32*)nullptr, rep_of, SP, (u32*)nullptr, (u32*)nullptr);
+        if (D) hipLaunchKernelGGL(k_ld_quality_edges, dim3(pf_blocks(D)), threads, 0, c->stream, e0key, e0q, D, n, rep_of, quality);
+        hipLaunchKernelGGL(k_ld_quality_nodes, all, threads, 0, c->stream, n, g, SP, quality);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, span.end(c->stream));
+        unsigned long long h_quality = 0;
+        HIPCHK(c, hipMemcpyAsync(&h_quality, quality, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         float dedup_ms = 0, rounds_ms = 0;
         HIPCHK(c, dedup.elapsed(dedup_ms));
-        HIPCHK(c, cover_rounds.elapsed(rounds_ms));
-        cover = lzani_cluster_cover_info{D, E - D, work.bytes(), dedup_ms, rounds_ms};
-    } else if (complete) {
-        StreamSpan link_rounds;
-        u64 merges = 0, D = 0;
-        float dedup_ms = 0, rounds_ms = 0;
-        HIPCHK(c, link_rounds.begin(c->stream));
-        hipLaunchKernelGGL(k_cl_link_init, nodes, threads, 0, c->stream, n, lwork.label.get(), lwork.csize.get(), rep_of.get(), size.get());
-        if (int rc = cluster_link_rounds(c, lwork, rep_of.get(), rounds, merges, D, dedup_ms)) return rc;
-        HIPCHK(c, link_rounds.end(c->stream));
-        HIPCHK(c, link_rounds.elapsed(rounds_ms));
-        link = lzani_cluster_link_info{D, E - D, merges, lwork.S, lwork.bytes(), dedup_ms, rounds_ms};
-    } else if (is_leiden) {
-        hipLaunchKernelGGL(k_ld_init, nodes, threads, 0, c->stream, n, rep_of.get(), size.get());
-        if (int rc = cluster_leiden_rounds(c, ldwork, rep_of.get(), leiden)) return rc;
-        rounds = leiden.move_rounds + leiden.refine_rounds;
-    } else if (algo == LZANI_CLUSTER_SINGLE) {
-        if (E) hipLaunchKernelGGL(k_cl_hook, edge_blocks, threads, 0, c->stream, edges, E, parent.get());
-        hipLaunchKernelGGL(k_cl_roots, nodes, threads, 0, c->stream, n, (const u32*)parent.get(), rep_of.get());
-    } else {
-        rounds = 0;
-        for (bool done = false; !done;) {
-            // the lowest undecided node is decided in every round: n rounds always do, and a defect ends here instead of spinning
-            if (rounds >= (u64)n + 1) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_run: nodes still undecided after n + 1 rounds");
-            const u32 batch = (u32)std::min<u64>(CL_BATCH, (u64)n + 1 - rounds);
-            HIPCHK(c, hipMemsetAsync(undecided, 0, CL_BATCH * sizeof(u32), c->stream));
-            for (u32 r = 0; r < batch; ++r) {
-                if (E) hipLaunchKernelGGL(k_cl_greedy_edges, edge_blocks, threads, 0, c->stream, edges, E, state.get(), blocked.get());
-                hipLaunchKernelGGL(k_cl_greedy_nodes, nodes, threads, 0, c->stream, n, state.get(), blocked.get(), undecided.get() + r);
-            }
-            HIPCHK(c, hipGetLastError());
-            u32 left[CL_BATCH];
-            HIPCHK(c, hipMemcpyAsync(left, undecided, sizeof left, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            u32 r = 0;
-            while (r < batch && left[r]) ++r;
-            done = r < batch;
-            rounds += done ? r + 1 : batch;             // (the rounds behind the first that left no node change nothing)
-        }
-        hipLaunchKernelGGL(k_cl_assign_init, nodes, threads, 0, c->stream, n, (const u32*)state.get(), rep_of.get());
-        if (E && algo == LZANI_CLUSTER_GREEDY_BEST)
-            hipLaunchKernelGGL(k_cl_assign_best, edge_blocks, threads, 0, c->stream, edges, E, (const u32*)state.get(), best.get());
-        if (E) hipLaunchKernelGGL(k_cl_assign_min, edge_blocks, threads, 0, c->stream, edges, E, (const u32*)state.get(),
-                                  algo == LZANI_CLUSTER_GREEDY_BEST ? (const unsigned long long*)best.get() : nullptr, rep_of.get());
+        HIPCHK(c, span.elapsed(rounds_ms));
+        out.quality = (int64_t)h_quality; out.dedup_ms = dedup_ms; out.rounds_ms = rounds_ms;
+        st.rounds = out.move_rounds + out.refine_rounds;
+        return LZANI_OK;
     }
-    hipLaunchKernelGGL(k_cl_flags, nodes, threads, 0, c->stream, n, (const u32*)rep_of.get(), flag.get(), size.get());
-    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)flag.get(), (u64)n, below.get());
-    hipLaunchKernelGGL(k_cl_number, nodes, threads, 0, c->stream, n, (const u32*)rep_of.get(), (const u64*)below.get(), (const u32*)size.get(),
-                       cluster_of.get(), counters.get());
+};
+
+// The run of `unit` on the context's edges: the span and the counters, the unit's run (rep_of, rounds, its own info), the
+// numbering (cluster_of and the run's part of `info`).  It allocates nothing.
+template <class Unit>
+int cluster_run_stage(lzani_ctx* c, Unit& unit, ClusterStage& st, lzani_cluster_info& info)
+{
+    const u32 n = c->cl.info.n;
+    const dim3 nodes(pf_blocks(n)), threads(PF_THREADS);
+    StreamSpan span;
+    HIPCHK(c, span.begin(c->stream));
+    HIPCHK(c, hipMemsetAsync(st.counters, 0, CL_COUNTERS * sizeof(u32), c->stream));
+    if (int rc = unit.run(c, st)) return rc;
+    hipLaunchKernelGGL(k_cl_flags, nodes, threads, 0, c->stream, n, st.rep_of, st.flag, st.size);
+    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, st.flag, (u64)n, st.below);
+    hipLaunchKernelGGL(k_cl_number, nodes, threads, 0, c->stream, n, st.rep_of, st.below, st.size, st.cluster_of, st.counters);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, span.end(c->stream));
     u32 h_counters[CL_COUNTERS] = {0, 0};
     u64 clusters = 0;
-    HIPCHK(c, hipMemcpyAsync(h_counters, counters, sizeof h_counters, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&clusters, below.get() + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_counters, st.counters, sizeof h_counters, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&clusters, st.below.get() + n, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(c, span.elapsed(ms));
-    info.algo = algo; info.rounds = (u32)rounds; info.clusters = clusters; info.singletons = h_counters[CL_SINGLETONS];
+    info.algo = st.algo; info.rounds = (u32)st.rounds; info.clusters = clusters; info.singletons = h_counters[CL_SINGLETONS];
     info.largest = h_counters[CL_LARGEST]; info.run_ms = ms;
-    TRACE("cluster: algo=%d n=%u edges=%llu rounds=%llu clusters=%llu", algo, n, (unsigned long long)E, (unsigned long long)rounds, (unsigned long long)clusters);
+    TRACE("cluster: algo=%d n=%u edges=%llu rounds=%llu clusters=%llu", st.algo, n, (unsigned long long)c->cl.info.edges, (unsigned long long)st.rounds,
+          (unsigned long long)clusters);
+    return LZANI_OK;
+}
+
+// lzani_cluster_run with the unit of its algorithm.  The unit and the stage are allocated whole first: refused, or short of
+// memory, with the cluster state as it was.
+template <class Unit>
+int cluster_run_as(lzani_ctx* c, int algo, uint64_t* n_clusters)
+{
+    Cluster& k = c->cl;
+    Unit unit;
+    if (int rc = unit.alloc(c)) return rc;
+    ClusterStage st;
+    if (int rc = st.alloc(c)) return rc;
+    st.algo = algo;
+    k.ran = false;
+    k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes before the run, not before its memory is had
+    lzani_cluster_info info = k.info;
+    const int rc = cluster_run_stage(c, unit, st, info);
+    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    k.info = info;
+    k.specific = unit.info;
+    k.rep_of = std::move(st.rep_of); k.cluster_of = std::move(st.cluster_of);
+    k.ran = true;
+    if (n_clusters) *n_clusters = info.clusters;
+    return LZANI_OK;
+}
+
+// The info of the last run where that was one of the algorithm whose info struct `Info` is.
+template <class Info>
+int cluster_specific_info(const lzani_ctx* c, Info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    const Info* last = c->cl.begun ? std::get_if<Info>(&c->cl.specific) : nullptr;
+    if (!last) return LZANI_ERR_STATE;
+    *info = *last;
     return LZANI_OK;
 }
 
@@ -672,8 +694,8 @@ int lzani_cluster_add_kept(lzani_ctx* c, uint64_t* edges_total)
     if (K) {
         StreamSpan span;
         HIPCHK(c, span.begin(c->stream));
-        hipLaunchKernelGGL(k_cl_add_kept, dim3(pf_blocks(K)), dim3(PF_THREADS), 0, c->stream, (const u32*)c->kept.rec.get(), K, (const u32*)k.len.get(),
-                           (int)k.info.measure, k.edges.get(), k.info.edges);
+        hipLaunchKernelGGL(k_cl_add_kept, dim3(pf_blocks(K)), dim3(PF_THREADS), 0, c->stream, c->kept.rec, K, k.len, (int)k.info.measure, k.edges,
+                           k.info.edges);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, span.end(c->stream));
         float ms = 0;
@@ -716,34 +738,12 @@ int lzani_cluster_run(lzani_ctx* c, int algo, uint64_t* n_clusters)
     if (int rc = cluster_state(c, fn)) return rc;
     if (!cluster_algo_known(algo)) return fail(c, LZANI_ERR_ARG, fn + ": unknown algorithm");
     HIPCHK(c, hipSetDevice(c->dev));
-    Cluster& k = c->cl;
-    CoverWork work;                                            // set cover: refused, or short of memory, with the state as it was
-    if (algo == LZANI_CLUSTER_SET_COVER)
-        if (int rc = cluster_cover_alloc(c, work)) return rc;
-    LinkWork lwork;                                            // complete linkage: the same
-    if (algo == LZANI_CLUSTER_COMPLETE)
-        if (int rc = cluster_link_alloc(c, lwork)) return rc;
-    LeidenWork ldwork;                                         // Leiden: the same
-    if (algo == LZANI_CLUSTER_LEIDEN)
-        if (int rc = cluster_leiden_alloc(c, ldwork)) return rc;
-    StageWork sw;                                              // every algorithm: the same
-    if (int rc = cluster_stage_alloc(c, algo, sw)) return rc;
-    k.ran = false;
-    k.rep_of.reset(); k.cluster_of.reset();                    // the last run's result goes before the run, not before its memory is had
-    lzani_cluster_info info = k.info;
-    lzani_cluster_cover_info cover{};
-    lzani_cluster_link_info link{};
-    lzani_cluster_leiden_info leiden{};
-    const int rc = cluster_run_stage(c, algo, sw, info, work, cover, lwork, link, ldwork, leiden);
-    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    k.info = info;
-    k.cover = cover;
-    k.link = link;
-    k.leiden = leiden;
-    k.rep_of = std::move(sw.rep_of); k.cluster_of = std::move(sw.cluster_of);
-    k.ran = true;
-    if (n_clusters) *n_clusters = info.clusters;
-    return LZANI_OK;
+    switch (algo) {                                            // the one place that knows which unit an algorithm is
+    case LZANI_CLUSTER_SET_COVER: return cluster_run_as<CoverUnit>(c, algo, n_clusters);
+    case LZANI_CLUSTER_COMPLETE: return cluster_run_as<LinkUnit>(c, algo, n_clusters);
+    case LZANI_CLUSTER_LEIDEN: return cluster_run_as<LeidenUnit>(c, algo, n_clusters);
+    default: return cluster_run_as<PlainUnit>(c, algo, n_clusters);
+    }
 }
 
 int lzani_cluster_fetch(lzani_ctx* c, uint32_t* rep_of, uint32_t* cluster_of)
@@ -767,28 +767,8 @@ int lzani_get_cluster_info(const lzani_ctx* c, lzani_cluster_info* info)
     return LZANI_OK;
 }
 
-int lzani_get_cluster_cover_info(const lzani_ctx* c, lzani_cluster_cover_info* info)
-{
-    if (!c || !info) return LZANI_ERR_ARG;
-    if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_SET_COVER) return LZANI_ERR_STATE;
-    *info = c->cl.cover;
-    return LZANI_OK;
-}
-
-int lzani_get_cluster_link_info(const lzani_ctx* c, lzani_cluster_link_info* info)
-{
-    if (!c || !info) return LZANI_ERR_ARG;
-    if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_COMPLETE) return LZANI_ERR_STATE;
-    *info = c->cl.link;
-    return LZANI_OK;
-}
-
-int lzani_get_cluster_leiden_info(const lzani_ctx* c, lzani_cluster_leiden_info* info)
-{
-    if (!c || !info) return LZANI_ERR_ARG;
-    if (!c->cl.begun || c->cl.info.algo != LZANI_CLUSTER_LEIDEN) return LZANI_ERR_STATE;
-    *info = c->cl.leiden;
-    return LZANI_OK;
-}
+int lzani_get_cluster_cover_info(const lzani_ctx* c, lzani_cluster_cover_info* info) { return cluster_specific_info(c, info); }
+int lzani_get_cluster_link_info(const lzani_ctx* c, lzani_cluster_link_info* info) { return cluster_specific_info(c, info); }
+int lzani_get_cluster_leiden_info(const lzani_ctx* c, lzani_cluster_leiden_info* info) { return cluster_specific_info(c, info); }
 
 }  // extern "C"

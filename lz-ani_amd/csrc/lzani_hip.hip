@@ -35,6 +35,8 @@
 #include <new>
 #include <optional>
 #include <string>
+#include <type_traits>
+#include <variant>
 #include <vector>
 
 #include "../../include/lzani.h"
@@ -263,10 +265,9 @@ struct Kept {
 struct Cluster {
     bool begun = false, ran = false;      // ran: rep_of and cluster_of are those of the edges as they are
     lzani_cluster_info info{};
-    lzani_cluster_cover_info cover{};     // of the last run, where that was set cover (info.algo says)
-    lzani_cluster_link_info link{};       // of the last run, where that was complete linkage
-    lzani_cluster_leiden_info leiden{};   // of the last run, where that was Leiden
-    DevMem<u32> len;                      // the reported lengths (n)
+    // the last run's own info where its algorithm (info.algo) has one: set cover, complete linkage or Leiden
+    std::variant<std::monostate, lzani_cluster_cover_info, lzani_cluster_link_info, lzani_cluster_leiden_info> specific;
+    DevMem<u32> len;                     // the reported lengths (n)
     DevMem<lzani_cluster_edge> edges;     // info.edges of them, a < b; grown geometrically
     DevMem<u32> rep_of, cluster_of;       // of the last run (n each)
 };

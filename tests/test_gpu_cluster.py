@@ -83,6 +83,17 @@ def test_made_up_graphs(eng, graphs):
     assert reps[("inf_weight", "greedy-first")].tolist() == [0, 1, 0] and reps[("inf_weight", "greedy-best")].tolist() == [0, 1, 1]
 
 
+@pytest.mark.parametrize("algo", CM.ALGOS[1:])
+@pytest.mark.parametrize("key, rounds", [("empty_1", 1), ("empty_5", 1), ("star_0", 2)])
+def test_greedy_rounds_where_the_schedule_cannot_change_them(eng, graphs, key, rounds, algo):
+    """elsewhere a stale read may delay a decision by a round; without an edge every node is a representative in round 1, and
+    in the star with the centre lowest the centre is decided in round 1 and, a kernel boundary later, its leaves in round 2"""
+    n, a, b, w = graphs[key]
+    begin(eng, n, a, b, w)
+    _, info = check_run(eng, key, n, a, b, w, algo, len(a))
+    assert info["rounds"] == rounds, (key, algo, info)
+
+
 def test_planted_families(eng):
     n, a, b, w, members = G.families()
     assert len(a) == 245000                                 # 958 blocks of edges

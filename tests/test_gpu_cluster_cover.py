@@ -121,6 +121,30 @@ def test_seams_of_the_kernels(eng):
     assert rep.tolist() == [0, 1, 2, 3, 4, 5, 6, 3, 8] and cov["distinct_edges"] == 1 and cov["duplicate_edges"] == 4999
 
 
+@pytest.mark.parametrize("n, rounds", [(21, 7), (24, 8), (27, 9), (48, 16), (51, 17)])
+def test_batch_seams_of_the_rounds(eng, n, rounds):
+    """the ascending path takes n / 3 rounds: one below, at and one above a batch of eight rounds, then the same at two batches"""
+    _, a, b, w = G.path(n, "asc")
+    want, model_rounds = CC.cover_rounds(n, CM.edge_set(a, b))
+    assert model_rounds == rounds
+    begin(eng, n, a, b, w)
+    rep, info, _ = check_run(eng, n, a, b, w, f"path of {n}")
+    assert np.array_equal(rep, want) and info["rounds"] == rounds, (n, info["rounds"], rounds)
+
+
+# lzani_cluster_cover_info.workspace_bytes of the commit before the workspaces summed their own allocations, read from its build
+# on an MI355X: graph -> bytes.  A size, not a timing: any difference is a defect.
+WORKSPACE = {"small_random": 32900, "one_edge": 2196, "empty_1": 1080}
+
+
+@pytest.mark.parametrize("key", list(WORKSPACE))
+def test_workspace_bytes_are_those_of_the_hand_written_sum(eng, key):
+    n, a, b, w = G.graphs()[key]
+    begin(eng, n, a, b, w)
+    eng.cluster_run(ALGO)
+    assert eng.cluster_cover_info()["workspace_bytes"] == WORKSPACE[key]
+
+
 def test_two_add_calls_with_an_overlap(eng):
     n, a, b, w = G.graphs()["small_random"]
     eng.cluster_begin(n, np.ones(n, np.uint32))

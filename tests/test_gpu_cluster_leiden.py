@@ -92,6 +92,35 @@ def test_random_graphs(eng):
     assert several > 20
 
 
+@pytest.mark.parametrize("n, move_rounds, refine_rounds", [(3, 6, 6), (4, 7, 8), (5, 8, 10), (8, 11, 16), (9, 12, 18)])
+def test_batch_seams_of_the_rounds(eng, n, move_rounds, refine_rounds):
+    """a clique of equal weights: one mover a round, so a phase of about n rounds -- below, at and above one batch of four
+    rounds and two"""
+    iu = np.triu_indices(n, 1)
+    a, b, w = iu[0], iu[1], np.full(len(iu[0]), 0.9)
+    want = model(n, a, b, w)
+    assert (want["move_rounds"], want["refine_rounds"], want["clusters"]) == (move_rounds, refine_rounds, 1)
+    begin(eng, n, a, b, w)
+    _, _, ld = check_run(eng, n, want, f"clique of {n}")
+    for count in ("levels", "move_rounds", "refine_rounds", "moves", "merges"):           # (check_run holds them all; by name here)
+        assert ld[count] == want[count], (n, count)
+
+
+# table_slots and workspace_bytes of lzani_cluster_leiden_info of the commit before the workspaces summed their own
+# allocations, read from its build on an MI355X: graph -> (slots, bytes).  Sizes, not timings: any difference is a defect.
+WORKSPACE = {"small_random": (4096, 144008), "one_edge": (4, 616), "empty_1": (1, 232)}
+
+
+@pytest.mark.parametrize("key", list(WORKSPACE))
+def test_workspace_bytes_are_those_of_the_hand_written_sum(eng, key):
+    n, a, b, w = G.graphs()[key]
+    begin(eng, n, a, b, w)
+    eng.set_cluster_leiden()
+    eng.cluster_run(ALGO)
+    ld = eng.cluster_leiden_info()
+    assert (ld["table_slots"], ld["workspace_bytes"]) == WORKSPACE[key]
+
+
 def near_cliques(fams=400, size=50, seed=50):
     """`fams` cliques of `size` with shuffled ids and 1 % of their edges removed; weights of three levels"""
     rng = np.random.default_rng(seed)

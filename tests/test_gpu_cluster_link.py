@@ -112,6 +112,20 @@ def test_one_merge_a_round(eng):
     assert not rep.any() and (info["rounds"], lk["merges"], info["clusters"]) == (200, 199, 1)
 
 
+# table_slots and workspace_bytes of lzani_cluster_link_info of the commit before the workspaces summed their own allocations,
+# read from its build on an MI355X: graph -> (slots, bytes).  Sizes, not timings: any difference is a defect.
+WORKSPACE = {"small_random": (2048, 75980), "one_edge": (2, 180), "empty_1": (1, 96)}
+
+
+@pytest.mark.parametrize("key", list(WORKSPACE))
+def test_workspace_bytes_are_those_of_the_hand_written_sum(eng, key):
+    n, a, b, w = G.graphs()[key]
+    begin(eng, n, a, b, w)
+    eng.cluster_run(ALGO)
+    lk = eng.cluster_link_info()
+    assert (lk["table_slots"], lk["workspace_bytes"]) == WORKSPACE[key]
+
+
 def test_small_cases_and_seams(eng):
     # one node, no edge: round 1 merges nothing
     begin(eng, 1, [], [])
