@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/ref_vectors.json, tests/golden/ref_live_vectors.json and tests/golden/ref_envelope_vectors.json
-with the reference build (oracle/_ref).
+"""Generate tests/golden/ref_vectors.json, tests/golden/ref_live_vectors.json, tests/golden/ref_envelope_vectors.json and
+tests/golden/repeat_vectors.json with the reference build (oracle/_ref).
 
 TEST INFRASTRUCTURE ONLY.  Run in the build container (needs /root/reference to build
-oracle/_ref):   make -C oracle ref && python oracle/make_goldens.py [--live-only | --envelope-only]
+oracle/_ref):   make -C oracle ref && python oracle/make_goldens.py [--live-only | --envelope-only | --repeats-only]
 Every vector is (inputs named by fixture/seed, expected int triples); no reference code is stored.
 """
 import json
@@ -73,11 +73,40 @@ def envelope_vectors():
     print("wrote", path, os.path.getsize(path), "bytes;", len(out["params"]), "tuples")
 
 
+def repeat_vectors():
+    """The reference build's answers on repeat-structured inputs (tests/repeat_genomes.py, tests/repeat_ties.py): result triples
+    and regions of every tie case, and the all2all of the 'small' repeat sets under the defaults and the 'generic' tuple
+    (tests/test_repeats.py)."""
+    import repeat_genomes as RG
+    import repeat_ties as RT
+    out = {"generator": "oracle/make_goldens.py", "source": "the reference build of oracle/_ref (CParser)",
+           "layout": "ties[case] = {res: [sym_in_matches, sym_in_literals, no_components], regions: flat rows of [ref_start, ref_end, "
+                     "seq_start, seq_end, num_matches, num_mismatches]} of parse(query=qry, ref=ref); sets[set/tuple].res = "
+                     "int32[n][n][3], res[r][q] of parse(query=q, ref=r), diagonal zero",
+           "ties": {}, "sets": {}, "checksums": {}}
+    for c in RT.tie_cases():
+        res, regs = O.ref_pair(c["ref"], c["qry"], None, want_regions=True)
+        out["ties"][c["name"]] = dict(res=list(res), regions=regs.reshape(-1).tolist())
+    for name in ("small", "small N"):
+        seqs = RG.repeat_set(name)
+        out["checksums"][name] = RG.checksum(seqs)
+        for pn in ("defaults", "generic"):
+            out["sets"][f"{name}/{pn}"] = dict(params=U.INST_PARAMS[pn], res=O.ref_all2all(seqs, U.INST_PARAMS[pn], threads=8).tolist())
+    path = os.path.join(ROOT, "tests", "golden", "repeat_vectors.json")
+    with open(path, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path), "bytes;", len(out["ties"]), "tie cases,", len(out["sets"]), "sets")
+
+
 def main():
     assert O.lib_ref() is not None, "build oracle/_ref first (make -C oracle ref)"
+    if "--repeats-only" in sys.argv[1:]:
+        repeat_vectors()
+        return
     if "--envelope-only" in sys.argv[1:]:
         envelope_vectors()
         return
+    repeat_vectors()
     live_vectors()
     envelope_vectors()
     if "--live-only" in sys.argv[1:]:

@@ -211,7 +211,11 @@ def model_all2all(seqs, params=None):
 
 def model_split_all2all(seqs, params=None, seglen=1000):
     """Every pair by several segments (lzani_core.h: checkpoints, segments, stitch) through the host model: (results, stats)
-    with stats = [pairs stitched, pairs the stitch voided, segments in all, segments skipped by the hand-overs]."""
+    with stats = [pairs stitched, segments run again after a void stitch, segments in all, segments skipped by the hand-overs].
+    The fourth is two counts in one number, on purpose (tests/model/lzani_model.cpp: "counted apart"): a stitched pair adds
+    its segments that no hand-over reached, and a pair that eight repair rounds did not stitch -- it is scanned whole -- adds
+    1,000,000.  So stats[3] // 1,000,000 pairs were not stitched (stats[0] + that = all pairs), and stats[3] % 1,000,000 < stats[2]
+    segments were skipped: 2,000,244 on a set of 20 pairs with 18 stitched is 2 pairs and 244 segments."""
     lib = model_lib()
     seqs, ptrs, lens = O._seq_table(seqs)
     n = len(seqs)
