@@ -7,13 +7,10 @@ runs its call and asserts (tests/inst_cell.py: run_cell) that
 - run-time compiled cells: no compile failed, and rtc_info() reports the null chain as chain_params_ok says."""
 import pytest
 
-import oracle as O
 import util as U
-from inst_cell import run_cell
+from inst_cell import oracle_of, run_cell
 
 pytestmark = pytest.mark.gpu
-
-_ORACLE = {}
 
 
 @pytest.fixture(scope="module")
@@ -21,13 +18,6 @@ def rtc_cache(tmp_path_factory):
     return str(tmp_path_factory.mktemp("rtc_cache"))
 
 
-def _oracle(setname, prm_name):
-    key = (setname, prm_name)
-    if key not in _ORACLE:
-        _ORACLE[key] = O.oracle_all2all(U.instantiation_set(setname), U.INST_PARAMS[prm_name], threads=16)
-    return _ORACLE[key]
-
-
 @pytest.mark.parametrize("cell", U.INST_CELLS, ids=[c["id"] for c in U.INST_CELLS])
 def test_instantiation_matches_the_oracle(monkeypatch, rtc_cache, cell):
-    run_cell(monkeypatch, rtc_cache, cell, U.instantiation_set(cell["set"]), _oracle(cell["set"], cell["prm"]))
+    run_cell(monkeypatch, rtc_cache, cell, U.instantiation_set(cell["set"]), oracle_of(cell["set"], cell["prm"]))
