@@ -676,16 +676,17 @@ int report_diagnostics(lzani_ctx* c, u64 n_pairs)
     {
         unsigned long long acc[36], z[36] = {0};
         HIPCHK(c, hipMemcpyFromSymbol(acc, HIP_SYMBOL(g_path_stats), sizeof acc));
-        const char* nm[24] = {"find_event calls", "fe: seed straight from the chain's round", "fe: common call, plain candidate", "fe: light rounds", "fe: light round hit",
-                              "fe: light round without a hit", "fe: merge loop hit", "fe: jump to a plain candidate", "stretch calls", "stretch: not applicable",
-                              "stretch: no seed step", "stretch: anchor before the seed", "stretch: seed event", "stretch: ... with the masks", "stretch: sum of seed steps",
-                              "refills", "chain: nothing", "chain: round done", "chain: event found", "chain: seed event known", "events", "close events", "extension chunks", "stretch chain: events committed"};
+#define LZ_SLOT_NAME(k, name) name,
+        const char* const slot[36] = {LZ_PATH_SLOTS(LZ_SLOT_NAME)};      // (lzani_kernels_pairs.h: the names' one home)
+#undef LZ_SLOT_NAME
+        const char* const* const nm = slot;
         fprintf(stderr, "[lzani paths] pairs=%llu, per pair:", (unsigned long long)n_pairs);
         for (int k = 0; k < 24; ++k) fprintf(stderr, " %s=%.1f;", nm[k], (double)acc[k] / (double)n_pairs);
-        const char* wn[12] = {"-", "text end", "no seed step", "several window positions", "seed bounds", "match of 64+", "anchor before the seed", "tag in two slots / overflow",
-                              "anchor elsewhere", "extension runs on", "-", "-"};
+        const char* const* const wn = slot + 24;
         fprintf(stderr, "\n[lzani paths] stretch chain exits per pair:");
         for (int k = 1; k < 10; ++k) fprintf(stderr, " %s=%.1f;", wn[k], (double)acc[24 + k] / (double)n_pairs);
+        fprintf(stderr, "\n[lzani paths raw]");                          // the totals themselves, one line per run (tests/path_cover.py)
+        for (int k = 0; k < 36; ++k) fprintf(stderr, " %llu", acc[k]);
         fprintf(stderr, "\n");
         HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(g_path_stats), z, sizeof z));
     }
@@ -694,7 +695,9 @@ int report_diagnostics(lzani_ctx* c, u64 n_pairs)
     {
         unsigned long long acc[24], z[24] = {0};
         HIPCHK(c, hipMemcpyFromSymbol(acc, HIP_SYMBOL(g_chain_stats), sizeof acc));
-        const char* nm[8] = {"chain_calls", "commits", "exit_nothing", "exit_seed", "exit_not_plain", "exit_event", "events_general", "refills"};
+#define LZ_SLOT_NAME(k, name) name,
+        const char* const nm[24] = {LZ_CHAIN_SLOTS(LZ_SLOT_NAME)};       // (lzani_kernels_pairs.h: the names' one home)
+#undef LZ_SLOT_NAME
         fprintf(stderr, "[lzani chain] pairs=%llu per pair:", (unsigned long long)n_pairs);
         for (int k = 0; k < 8; ++k) fprintf(stderr, " %s=%.1f", nm[k], (double)acc[k] / (double)n_pairs);
         fprintf(stderr, "\n[lzani chain] wave cycles per pair: after exit_nothing=%.0f after round_done=%.0f after exit_event=%.0f inside the chain=%.0f\n",
@@ -704,6 +707,9 @@ int report_diagnostics(lzani_ctx* c, u64 n_pairs)
         fprintf(stderr, "[lzani chain] exit_seed by the test that handed the round back, per pair: anchor's own step=%.1f no window position=%.1f several=%.1f text end=%.1f long seed=%.1f other=%.1f; event known, commit left=%.1f\n",
                 (double)acc[16] / (double)n_pairs, (double)acc[17] / (double)n_pairs, (double)acc[18] / (double)n_pairs, (double)acc[19] / (double)n_pairs,
                 (double)acc[20] / (double)n_pairs, (double)acc[21] / (double)n_pairs, (double)acc[22] / (double)n_pairs);
+        fprintf(stderr, "[lzani chain raw]");
+        for (int k = 0; k < 24; ++k) fprintf(stderr, " %llu", acc[k]);
+        fprintf(stderr, "\n");
         HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(g_chain_stats), z, sizeof z));
     }
 #endif

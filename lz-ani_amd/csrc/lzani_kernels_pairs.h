@@ -116,6 +116,22 @@ struct DevWave {
     unsigned sr[4] = {0, 0, 0, 0};                  // events found but not null, by reason: close, region kept (or none open), no forward record, backward
     unsigned long long stc[4] = {0, 0, 0, 0}, stc_t0 = 0;
     int stc_open = -2;
+    // The slots of g_chain_stats, by number: st[k] at k, stc[k] at 8 + k, sr[k] at 12 + k, sw[k] at 16 + k (flush_chain_stats).
+    // This list is the one home of their names: report_diagnostics prints from it, tests/path_cover.py is checked against it.
+#define LZ_CHAIN_SLOTS(X) \
+    X(0, "chain_calls") X(1, "commits") X(2, "exit_nothing") X(3, "exit_seed") X(4, "exit_not_plain") X(5, "exit_event") \
+    X(6, "events_general") X(7, "refills") \
+    X(8, "cycles after exit_nothing") X(9, "cycles after round_done") X(10, "cycles after exit_event") X(11, "cycles inside the chain") \
+    X(12, "not null: close") X(13, "not null: region kept or none open") X(14, "not null: no forward record") X(15, "not null: backward side") \
+    X(16, "exit_seed: anchor's own step") X(17, "exit_seed: no window position") X(18, "exit_seed: several") X(19, "exit_seed: text end") \
+    X(20, "exit_seed: long seed") X(21, "exit_seed: other") X(22, "event known, commit left") X(23, "-")
+    template <class Acc> __device__ __forceinline__ void flush_chain_stats(Acc* g, int ln) const
+    {
+        for (int k = 0; k < 8; ++k) atomicAdd(&g[k], ln == 0 ? (unsigned long long)st[k] : 0ULL);
+        for (int k = 0; k < 4; ++k) atomicAdd(&g[8 + k], ln == 0 ? stc[k] : 0ULL);
+        for (int k = 0; k < 4; ++k) atomicAdd(&g[12 + k], ln == 0 ? (unsigned long long)sr[k] : 0ULL);
+        for (int k = 0; k < 8; ++k) atomicAdd(&g[16 + k], ln == 0 ? (unsigned long long)sw[k] : 0ULL);
+    }
     __device__ __forceinline__ void cycles_mark(int code)
     {
         unsigned long long t;
@@ -128,6 +144,23 @@ struct DevWave {
 #ifdef LZANI_PATH_STATS                             // diagnostic build: which path found the events of a pair (LZ_PS slots, see lzani_hip.hip)
     unsigned ps[24] = {0};
     unsigned pw[12] = {0};                          // stretch chain: exits by reason
+    // The slots of g_path_stats, by number: ps[k] (LZ_PS(k), LZ_PSN(k, n)) at k, pw[k] at 24 + k (flush_path_stats).
+    // This list is the one home of their names: report_diagnostics prints from it, tests/path_cover.py is checked against it.
+#define LZ_PATH_SLOTS(X) \
+    X(0, "find_event calls") X(1, "fe: seed straight from the chain's round") X(2, "fe: common call, plain candidate") X(3, "fe: light rounds") \
+    X(4, "fe: light round hit") X(5, "fe: light round without a hit") X(6, "fe: merge loop hit") X(7, "fe: jump to a plain candidate") \
+    X(8, "stretch calls") X(9, "stretch: not applicable") X(10, "stretch: no seed step") X(11, "stretch: anchor before the seed") \
+    X(12, "stretch: seed event") X(13, "stretch: ... with the masks") X(14, "stretch: sum of seed steps") \
+    X(15, "refills") X(16, "chain: nothing") X(17, "chain: round done") X(18, "chain: event found") X(19, "chain: seed event known") \
+    X(20, "events") X(21, "close events") X(22, "extension chunks") X(23, "stretch chain: events committed") \
+    X(24, "-") X(25, "text end") X(26, "no seed step") X(27, "several window positions") X(28, "seed bounds") X(29, "match of 64+") \
+    X(30, "anchor before the seed") X(31, "tag in two slots / overflow") X(32, "anchor elsewhere") X(33, "extension runs on") \
+    X(34, "-") X(35, "-")
+    template <class Acc> __device__ __forceinline__ void flush_path_stats(Acc* g, int ln) const
+    {
+        for (int k = 0; k < 24; ++k) atomicAdd(&g[k], ln == 0 ? (unsigned long long)ps[k] : 0ULL);
+        for (int k = 0; k < 12; ++k) atomicAdd(&g[24 + k], ln == 0 ? (unsigned long long)pw[k] : 0ULL);
+    }
 #define LZ_PS(k) (ps[k] += 1)
 #define LZ_PSN(k, n) (ps[k] += (unsigned)(n))
 #else
@@ -2576,14 +2609,10 @@ __device__ __forceinline__ void pair_body(const PairArgs& a, u32 lo, u32 j, int 
     }
 #endif
 #ifdef LZANI_PATH_STATS
-    for (int k = 0; k < 24; ++k) atomicAdd(&g_path_stats[k], lane == 0 ? (unsigned long long)w.ps[k] : 0ULL);
-    for (int k = 0; k < 12; ++k) atomicAdd(&g_path_stats[24 + k], lane == 0 ? (unsigned long long)w.pw[k] : 0ULL);
+    w.flush_path_stats(g_path_stats, lane);
 #endif
 #ifdef LZANI_CHAIN_STATS
-    for (int k = 0; k < 8; ++k) atomicAdd(&g_chain_stats[k], lane == 0 ? (unsigned long long)w.st[k] : 0ULL);
-    for (int k = 0; k < 4; ++k) atomicAdd(&g_chain_stats[8 + k], lane == 0 ? w.stc[k] : 0ULL);
-    for (int k = 0; k < 4; ++k) atomicAdd(&g_chain_stats[12 + k], lane == 0 ? (unsigned long long)w.sr[k] : 0ULL);
-    for (int k = 0; k < 8; ++k) atomicAdd(&g_chain_stats[16 + k], lane == 0 ? (unsigned long long)w.sw[k] : 0ULL);
+    w.flush_chain_stats(g_chain_stats, lane);
 #endif
 #ifdef LZANI_STAMPS
     w.stamp(0);

@@ -98,6 +98,12 @@ __device__ __forceinline__ void split_body(const SplitArgs& a, u32 p, u32 seg, b
             m.run_segment((int)seg, seg > 0 ? &st : nullptr, cuts, (int)a.S, so);
         }
     }
+#ifdef LZANI_PATH_STATS                             // diagnostic builds: a checkpoint's and a segment's counters, as pair_body flushes a pair's
+    w.flush_path_stats(g_path_stats, lane);
+#endif
+#ifdef LZANI_CHAIN_STATS
+    w.flush_chain_stats(g_chain_stats, lane);
+#endif
 }
 
 template <bool NFREE, int DEFP, int MODE>

@@ -278,17 +278,33 @@ def sample_max_of(fraction):
     return min(SAMPLE_ALL, int(Fraction(float(fraction)) * (1 << 64)))
 
 
-def build_library(force=False):
-    """hipcc cross-compiles for gfx950 without a GPU present."""
+DIAG_LIB_PATH = os.path.join(ROOT, "build", "diag", "liblzani_cover.so")
+DIAG_DEFINES = ("-DLZANI_PATH_STATS", "-DLZANI_CHAIN_STATS")
+
+
+def _build(out, defines, force):
     csrc = os.path.join(HERE, "csrc")                       # every header and source there: a new one cannot be forgotten
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".hip"))] + [os.path.join(ROOT, "include", "lzani.h")]
-    if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
-        return LIB_PATH
+    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-           "-Wno-unused-value", "-I" + os.path.join(HERE, "csrc"), "-I" + os.path.join(ROOT, "include"),      # (-I: the .incbin of lzani_rtc.h)
-           "-o", LIB_PATH, SRC, os.path.join(HERE, "csrc", "lzani_sort.hip"), "-lrccl", "-lhiprtc"]
+           "-Wno-unused-value", *defines, "-I" + os.path.join(HERE, "csrc"), "-I" + os.path.join(ROOT, "include"),      # (-I: the .incbin of lzani_rtc.h)
+           "-o", out, SRC, os.path.join(HERE, "csrc", "lzani_sort.hip"), "-lrccl", "-lhiprtc"]
     subprocess.check_call(cmd)
-    return LIB_PATH
+    return out
+
+
+def build_library(force=False):
+    """hipcc cross-compiles for gfx950 without a GPU present."""
+    return _build(LIB_PATH, (), force)
+
+
+def build_diag_library(force=False):
+    """The coverage library of tests/test_gpu_path_cover.py: build_library's recipe plus the two counter defines (the pair
+    kernel's exits by reason, printed as raw totals per run: report_diagnostics), build/diag/liblzani_cover.so; run with
+    LZANI_LIB pointing at it.  The same staleness rule."""
+    return _build(DIAG_LIB_PATH, DIAG_DEFINES, force)
 
 
 _lib = None

@@ -7,6 +7,7 @@ context).  A cell clears the LZANI_* switches, sets its own (apply_env), runs it
 - run-time compiled cells: no compile failed, and rtc_info() reports the null chain as chain_params_ok says.
 run_cell is the cell on a context of its own.  A node of tests/context_walk.py is a cell with three more keys: "kernels" (the
 names of its launch record; None: not asserted), "blocks" (what residency() must count) and "limit"."""
+import hashlib
 import time
 
 import numpy as np
@@ -64,9 +65,10 @@ def apply_env(monkeypatch, rtc_cache, node):
         monkeypatch.setenv(k, v)
 
 
-def call_and_check(eng, node, seqs, want, where):
+def call_and_check(eng, node, seqs, want, where, seen=None):
     """The node's call on the engine eng, which holds the genome set seqs; want: the oracle's all2all of the set under the
-    node's tuple; where: what every assertion message begins with.  Returns the number of pairs."""
+    node's tuple; where: what every assertion message begins with.  Returns the number of pairs.  seen: a dict that gets the
+    launch record ("kernels") and the SHA-256 of the result array ("digest") before anything is asserted."""
     prm = U.INST_PARAMS[node["prm"]]
     n = len(seqs)
     ref_ids, off, q = U.instantiation_rows(node, n)
@@ -77,6 +79,8 @@ def call_and_check(eng, node, seqs, want, where):
     else:
         out = eng.run_rows(ref_ids, off, q)
     rec, info = eng.kernel_launches(), eng.rtc_info()
+    if seen is not None:
+        seen.update(kernels=dict(rec), digest=hashlib.sha256(np.ascontiguousarray(out).tobytes()).hexdigest())
     kernels = node["kernels"] if "kernels" in node else U.kernel_names_of_cell(node)
     if kernels is not None:
         assert set(rec) == kernels, (where, rec)
@@ -102,14 +106,15 @@ def call_and_check(eng, node, seqs, want, where):
     return len(exp)
 
 
-def run_cell(monkeypatch, rtc_cache, cell, seqs, want):
-    """One cell on the genome set seqs, on a context of its own; want: the oracle's all2all of the set under the cell's tuple."""
+def run_cell(monkeypatch, rtc_cache, cell, seqs, want, seen=None):
+    """One cell on the genome set seqs, on a context of its own; want: the oracle's all2all of the set under the cell's tuple;
+    seen: see call_and_check."""
     apply_env(monkeypatch, rtc_cache, cell)
     t0 = time.time()
     eng = L.Engine(U.INST_PARAMS[cell["prm"]])
     try:
         eng.set_genomes(seqs)
-        pairs = call_and_check(eng, cell, seqs, want, cell["id"])
+        pairs = call_and_check(eng, cell, seqs, want, cell["id"], seen)
     finally:
         eng.close()
     print(f"cell {cell['id']}: set '{cell['set']}', {pairs} pairs, {time.time() - t0:.2f} s")

@@ -384,6 +384,72 @@ def checksum(seqs):
     return c
 
 
+# ---- the exit sets: pairs laid out for single exits of the pair kernel's hand-written loops ------------------------------
+# (tests/path_cover.py: the slots the random and the repeat-structured sets leave at zero)
+EXIT_LEN, EXIT_STEP, EXIT_FIRST = 9000, 420, 300
+EXIT_SET_NAMES = ("exits", "exits N")
+# A motif is the bursts of a relative behind its start s, as (from, to) offsets: every symbol of a burst is substituted, there
+# are no indels (the diagonal holds), and what lies between two bursts stays exact.  Each opens with a burst of 50 -- longer
+# than mqd: the scan loses track and comes back through the anchor queue, which then covers the steps behind the next
+# event, so the null chain (not the light rounds of a stretch the scan has outrun) looks at them -- then 18 exact symbols
+# (an anchor under both tuples: the event the chain starts from) and a burst of 10.
+EXIT_MOTIFS = {
+    "long seed": ((0, 50), (68, 78)),                      # ... then >= 130 exact symbols: the seed's match runs over 64 + msl
+    "several": ((0, 50), (68, 78), (90, 100)),             # ... then 12 exact whose first 10 stand 30 further on as well (exit_pair plants them)
+    "short seeds": ((0, 50), (68, 78), (90, 100), (113, 123)),   # ... then seeds of 12 and 13: below mal 15, no anchor at their step
+}
+# the end of the text, as offsets from the end: 18 exact, a burst, a seed of 12 that starts 62 before the end (inside the
+# last 64 + msl symbols: the chain's bounds test hands it back), a burst, 40 exact to the end
+EXIT_TAIL = ((-140, -90), (-72, -62), (-50, -40))
+
+
+def exit_pair(st, L=EXIT_LEN):
+    """(g, h): a random genome and its relative by bursts, motif after motif of EXIT_MOTIFS every EXIT_STEP symbols and
+    EXIT_TAIL at the end -- the null chain's exits 'long seed' (sw[4]), 'several' (sw[2]) and 'text end' (sw[3]), and a seed
+    handed back by the bounds test with no anchor at its step (find_event's LZ_PS(1))."""
+    g = _rnd(st, L)
+    kinds = list(EXIT_MOTIFS)
+    starts = list(range(EXIT_FIRST, L - EXIT_STEP - 200, EXIT_STEP))
+    for k, s in enumerate(starts):
+        if kinds[k % len(kinds)] == "several":
+            g[s + 108:s + 118] = g[s + 78:s + 88]
+    h = g.copy()
+    shift = (st.u64(L) % np.uint64(3)).astype(np.uint8) + 1
+    spans = [(s + a, s + b) for k, s in enumerate(starts) for a, b in EXIT_MOTIFS[kinds[k % len(kinds)]]]
+    spans += [(L + a, L + b) for a, b in EXIT_TAIL]
+    for a, b in spans:
+        h[a:b] = (h[a:b] + shift[a:b]) % 4
+    return np.ascontiguousarray(g), np.ascontiguousarray(h)
+
+
+def exit_strand_end(g, st, L=8600):
+    """A stranger to g that holds, 3,000 symbols in, the reverse complement of g's first 30 symbols -- as a query its match
+    ends where the reference text ends, past the last complete seed window, and the null chain hands back nothing -- and
+    300 symbols on 30 symbols of g's middle: the next queued candidate, plain, which find_event's common call takes
+    (LZ_PS(2))."""
+    return np.ascontiguousarray(np.concatenate([_rnd(st, 3000), rc(g[:30]), _rnd(st, 300), g[5000:5030], _rnd(st, L - 3360)]))
+
+
+_EXIT_SETS = {}
+
+
+def exit_set(name):
+    """'exits': exit_pair's two genomes, exit_strand_end's stranger and a relative of the first at 5 %; ' N': the relative
+    with N runs at its start, in its middle and at its end (the others stay N-free: a pair with an N leaves the chain's
+    seed event at its bounds test)."""
+    if name not in _EXIT_SETS:
+        st = SG.Stream(4320)
+        g, h = exit_pair(st)
+        x = exit_strand_end(g, st)
+        m = SG.mutate(g, 0.05, st)
+        if name.endswith(" N"):
+            m[:9] = 5
+            m[len(m) // 2:len(m) // 2 + 40] = 5
+            m[-5:] = 5
+        _EXIT_SETS[name] = [np.ascontiguousarray(s) for s in (g, h, x, m)]
+    return _EXIT_SETS[name]
+
+
 # ---- fuzz cases ----------------------------------------------------------------------------------------------------------
 def fuzz_seqs(st, lo, hi):
     """Five genomes of lo..hi symbols: a structured genome, two relatives with a translocation (one with N runs at its

@@ -13,6 +13,7 @@ import pytest
 
 import lzani_ctypes as L
 import oracle as O
+import path_cover as PC
 import prefilter_cross_model as XM
 import prefilter_model as PM
 import repeat_genomes as RG
@@ -65,6 +66,20 @@ def _gpu_all2all(seqs, prm=None):
 @pytest.mark.parametrize("cell", U.INST_CELLS, ids=[c["id"] for c in U.INST_CELLS])
 def test_instantiation_matches_the_oracle_on_repeats(monkeypatch, rtc_cache, cell):
     run_cell(monkeypatch, rtc_cache, cell, RG.repeat_set(cell["set"]), _oracle(cell["set"], cell["prm"]))
+
+
+# ---- the exit sets: pairs laid out for single exits of the hand-written loops, on the shipped library -------------------------
+EXIT_CELLS = [c for c in PC.cells() if c["set"] in RG.EXIT_SET_NAMES]
+
+
+@pytest.mark.parametrize("cell", EXIT_CELLS, ids=[c["id"].replace(" | ", "-").replace(" ", "_") for c in EXIT_CELLS])
+def test_exit_sets_match_the_oracle(monkeypatch, rtc_cache, cell):
+    """Every chain class of tests/path_cover.py that runs an exit set (repeat_genomes.exit_set), on the shipped library: the
+    class's kernel in the launch record, every pair bit-equal to the oracle."""
+    key = ("exit", cell["set"], cell["prm"])
+    if key not in _ORACLE:
+        _ORACLE[key] = O.oracle_all2all(RG.exit_set(cell["set"]), U.INST_PARAMS[cell["prm"]], threads=16)
+    run_cell(monkeypatch, rtc_cache, cell, RG.exit_set(cell["set"]), _ORACLE[key])
 
 
 # ---- differential fuzz ---------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import lzani_ctypes as L
+import path_cover as PC
 import util as U
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
@@ -123,3 +124,61 @@ def test_sets_hold_what_the_cells_need():
     assert U.index_form(U.instantiation_set("long"), U.INST_PARAMS["long"])["tag_words"]
     assert U.index_form(U.instantiation_set("mid"), U.INST_PARAMS["rtc_chain"])["tag_words"]
     assert U.index_form(U.instantiation_set("small"), U.INST_PARAMS["defaults"])["tag_words"]
+
+
+# ---- the counters of the diagnostic builds (tests/path_cover.py, tests/test_gpu_path_cover.py) ---------------------------
+def _text(path):
+    with open(path) as f:
+        return f.read()
+
+
+def test_counter_slots_are_the_headers():
+    """The slot tables tests/test_gpu_path_cover.py goes by are the header's, number by number, and the statements that count
+    use the numbers the tables name: a renumbered slot fails here, not on the GPU."""
+    pairs = _text(PC.PAIRS_H)
+    assert PC.header_slots(pairs, "LZ_PATH_SLOTS") == list(enumerate(PC.PATH_SLOTS))
+    assert PC.header_slots(pairs, "LZ_CHAIN_SLOTS") == list(enumerate(PC.CHAIN_SLOTS))
+    assert "unsigned ps[24] = {0};" in pairs and "unsigned pw[12] = {0};" in pairs and "unsigned st[8]" in pairs and "unsigned sw[8]" in pairs
+    hip = _text(os.path.join(os.path.dirname(PC.PAIRS_H), "lzani_hip.hip"))
+    assert "g_path_stats[{}];".format(len(PC.PATH_SLOTS)) in hip and "g_chain_stats[{}];".format(len(PC.CHAIN_SLOTS)) in hip
+    for path, lines in PC.COUNTING_TEXT.items():
+        text = _text(path)
+        for line in lines:
+            assert text.count(line) == 1, (os.path.basename(path), line, text.count(line))
+    count = lambda rx: dict(collections.Counter(int(k) for k in re.findall(rx, pairs)))
+    assert count(r"\bLZ_PS\((\d+)\)") == PC.LZ_PS_SITES
+    assert count(r"\bLZ_NC_WHY\((\d+)\)") == PC.LZ_NC_WHY_SITES
+    assert count(r"\bLZ_SC_WHY\((\d+)\)") == PC.LZ_SC_WHY_SITES
+    assert re.findall(r"\bLZ_PSN\((\d+),", pairs) == ["23"]
+    # every required slot is one the tables name, and has a name
+    for s in PC.REQUIRED:
+        vec, k, label = PC.slot(*s)
+        assert (PC.PATH_SLOTS if vec == "paths" else PC.CHAIN_SLOTS)[k] != "-", label
+
+
+def test_coverage_cells_select_their_class():
+    """Every chain class has its cells, every cell's set, tuple and switches lead the dispatch (util.predict_kernels) to the
+    class's kernel, and every exit set is some class's."""
+    cells = PC.cells()
+    assert len({c["id"] for c in cells}) == len(cells)
+    for cls in PC.CLASSES:
+        t, nf, form = cls
+        mine = [c for c in cells if c["class"] == cls]
+        assert len(mine) >= 2, cls
+        d = {"defaults": 1, "long": 2}[t]
+        if form == "split":
+            want = {"split nfree={} defp={} mode={}".format(nf, d, m) for m in (0, 1)}
+        elif form == "probe":
+            want = {U.PAIRS_NAME.format(1, nf, d if d == 1 else 0, 0, 1, 0)}          # (the long tuple runs generic there)
+        else:
+            want = {U.PAIRS_NAME.format(1, nf, d, 0, 1, {"bitmaps": 2, "join": 1}[form])}
+        for c in mine:
+            assert c["kernels"] == want and c["env"]["LZANI_RTC"] == "0", (c["id"], c["kernels"])
+    import repeat_genomes as RG
+    assert {c["set"] for c in cells if c["set"].startswith("exits")} == set(RG.EXIT_SET_NAMES)
+
+
+def test_parse_raw_sums_the_runs():
+    text = ("[lzani paths] pairs=2, per pair: x=1.0;\n[lzani paths raw]" + " 1" * 36 + "\n[lzani chain raw]" + " 2" * 24 + "\n"
+            "noise\n[lzani paths raw]" + " 3" * 36 + "\n")
+    assert PC.parse_raw(text) == {"paths": [4] * 36, "chain": [2] * 24}

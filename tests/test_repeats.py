@@ -27,6 +27,7 @@ PRM_NAMES = ("defaults", "long", "rtc_chain", "generic", "slow", "chain")
 N_FUZZ = 24
 CHECKSUMS = {"small": 1148848280, "small N": 4041387137, "split": 760150264, "split N": 1040223856, "mid": 1780726521,
              "mid N": 1322096561, "long": 3166499075, "long N": 1698580550}
+EXIT_CHECKSUMS = {"exits": 2987010118, "exits N": 1291578073}
 _SPLIT_STATS = {}
 
 
@@ -43,6 +44,36 @@ def load_recorded():
 # ---- the generator ---------------------------------------------------------------------------------------------------------
 def test_named_sets_do_not_drift():
     assert {name: RG.checksum(RG.repeat_set(name)) for name in RG.SET_NAMES} == CHECKSUMS
+
+
+def test_exit_sets_do_not_drift_and_hold_their_motifs():
+    """The exit sets' bytes depend on the seed alone; the relative differs from its ancestor in the bursts alone, at every
+    symbol of a burst; a 'several' motif's seed stands twice in the ancestor, 30 apart; only the last genome of 'exits N'
+    holds N; the stranger carries the reverse complement of the ancestor's first 30 symbols; host model and oracle agree."""
+    assert {name: RG.checksum(RG.exit_set(name)) for name in RG.EXIT_SET_NAMES} == EXIT_CHECKSUMS
+    g, h, x, m = RG.exit_set("exits")
+    L = len(g)
+    assert L == len(h) == RG.EXIT_LEN
+    kinds = list(RG.EXIT_MOTIFS)
+    starts = list(range(RG.EXIT_FIRST, L - RG.EXIT_STEP - 200, RG.EXIT_STEP))
+    assert len(starts) >= 3 * len(kinds)
+    burst = np.zeros(L, bool)
+    for k, s in enumerate(starts):
+        for a, b in RG.EXIT_MOTIFS[kinds[k % len(kinds)]]:
+            burst[s + a:s + b] = True
+        if kinds[k % len(kinds)] == "several":
+            assert np.array_equal(g[s + 78:s + 88], g[s + 108:s + 118])
+    for a, b in RG.EXIT_TAIL:
+        burst[L + a:L + b] = True
+    assert np.array_equal(g != h, burst)
+    assert np.array_equal(x[3000:3030], RG.rc(g[:30])) and np.array_equal(x[3330:3360], g[5000:5030])
+    gn = RG.exit_set("exits N")
+    assert [bool((s > 3).any()) for s in gn] == [False, False, False, True] and gn[3][0] > 3 and gn[3][-1] > 3
+    assert all(np.array_equal(a, b) for a, b in zip(gn[:3], (g, h, x)))
+    for name in RG.EXIT_SET_NAMES:
+        for pn in ("defaults", "long"):
+            want = O.oracle_all2all(RG.exit_set(name), U.INST_PARAMS[pn], threads=8)
+            assert np.array_equal(U.model_all2all(RG.exit_set(name), U.INST_PARAMS[pn]), want), (name, pn)
 
 
 @pytest.mark.parametrize("name", RG.SET_NAMES)
