@@ -271,6 +271,19 @@ LZ_HD bool kmer_valid_nfree_head(int L, int mrd, int p, int k)
 {
     return p + k <= (mrd == 0 ? 2 * L : L);
 }
+// The msl-mer word of a text position (tables.h: kmS) from the packed text itself, msl <= 7: `syms` as for kml_from_syms.
+// The word is the msl-mer alone there -- the low bits of the text, first symbol lowest; at msl 8 and 9 k_kmers packs hash
+// bits above it, which the text does not hold.  k_kmers stores this value.
+LZ_HD constexpr bool kms_is_text(int msl) { return msl >= 1 && msl <= 7; }
+LZ_HD u32 kms_from_syms(u32 syms, int msl)
+{
+    return syms & (u32)lowmask(2 * msl);
+}
+// ... and whether the position holds an msl-mer, for a genome without N at a position of the text's head: kmer_at's answer
+LZ_HD bool kms_valid_nfree_head(int L, int mrd, int p, int msl)
+{
+    return kmer_valid_nfree_head(L, mrd, p, msl);
+}
 LZ_HD void key_slot(const IndexView& I, u64 key, u32& bucket, u32& tag)
 {
     u64 h = mix_key(key, I.kb);

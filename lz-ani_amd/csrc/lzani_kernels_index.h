@@ -28,7 +28,7 @@ __global__ void k_kmers(GenomeTab G, u32* __restrict__ kmL, u32* __restrict__ km
     u32 a = KM_INVALID, b = KM_INVALID;
     if (kmer_at(R, p, mal, key)) a = kml_from_syms((u32)key, mal);       // (mal <= 15 here; DevWave::refill makes the same word from the text)
     if (kmer_at(R, p, msl, key)) {
-        b = (u32)key;
+        b = kms_from_syms((u32)key, msl);            // (msl <= 15 here; at msl <= 7 the pair kernel may take it from the text)
         // msl 8, 9: 14 hash bits above the msl-mer -- word and bit of the pair kernel's seed bitmap (DevWave::bm_hash,
         // LZ_NC_WORD9) without a multiply per round; 0x3FFF stays KM_INVALID's alone.  Equality of two words is still
         // equality of the msl-mers.

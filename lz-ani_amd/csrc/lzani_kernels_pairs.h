@@ -70,6 +70,18 @@ template <int CHAIN> struct ChainP {
            NT = MQD + 1, WIN = MQD + MRD };
 };
 
+// Diagnostic build -DLZANI_EXP_QCACHED (wrong results, timing only): every read of the query's seed words -- the null and
+// stretch chains' rounds, track_round, find_event_round -- goes to one kilobyte of words that stays in the cache: the upper
+// bound of what taking those words from anywhere warmer than kmS can give (profiles/seed_from_text_ab.json, "bound").
+// (The stretch chain's load of the steps' mal-mer hashes shares the round's address register and is cached with them: the
+// bound is the headline kernel's, which has no stretch chain.)
+#ifdef LZANI_EXP_QCACHED
+#define LZ_QK_AT(i, lane) ((u32)(((i) & 0x3ff) + (lane)))
+#define LZ_QTEXT_OF(CP) false
+#else
+#define LZ_QK_AT(i, lane) ((u32)((i) + (lane)))
+#define LZ_QTEXT_OF(CP) (CP::NF && kms_is_text(CP::MSL))          /* the hand-written loops take the query's seed words from its text */
+#endif
 #ifndef LZANI_STRETCH_DENSE
 #define LZANI_STRETCH_DENSE 0
 #endif
@@ -419,6 +431,29 @@ struct DevWave {
         }
     }
 
+    // The seed word of query position p (a tracking step of a round).  At msl <= 7 and in a pair without N it is made from
+    // the packed query text -- 10 KB at 40 kbp, which the refill keeps warm -- instead of read from the query's kmS array, 16
+    // times as large and read once per pair, i.e. always cold (lzani_core.h: kms_from_syms, kms_valid_nfree_head).  The two
+    // text dwords are in bounds: a query view is the head of the genome's full text (fwd | pads | RC, lzani_layout.h), so
+    // symbol p + 31 lies inside it or in its two spare blocks for every p < L + mrd.  A pair with an N (the N flags decide
+    // what is an msl-mer) and msl 8, 9 (hash bits above the msl-mer) keep the load.  So do the kernels without the
+    // hand-written loops (parameters at run time, no anchor queue): every round of theirs is the compiler's, and there
+    // the two words, the funnel and the rule cost more than the cold line did (generic kernel, reg 36: 955 -> 997 ms).
+    static constexpr bool QTEXT_KERNEL = CHAIN != 0 && LZ_QTEXT_OF(ChainP<CHAIN>);
+    __device__ __forceinline__ bool seed_word_from_text() const { return QTEXT_KERNEL; }
+    __device__ __forceinline__ u32 query_seed_word(int i, int ln) const
+    {
+#ifndef LZANI_EXP_QCACHED
+        if (seed_word_from_text()) {
+            const int p = uniform(i) + ln;                   // (the round's position is the machine's: the same on every lane -- said so, it stays scalar)
+            const u32a* const w = reinterpret_cast<const u32a*>(Q.t2) + ((u32)p >> 4);
+            const u32 syms = funnel32(w[1], w[0], ((u32)p & 15u) * 2u);
+            return kms_valid_nfree_head(Q.L, P.mrd, p, P.msl) ? kms_from_syms(syms, P.msl) : KM_INVALID;
+        }
+#endif
+        return qkS[LZ_QK_AT(i, ln)];
+    }
+
     // Fast round (k-mer words available, seed window <= 128): the lanes only DETECT candidates --
     // a bucket entry whose tag equals the step's mal-mer, a window position whose msl-mer equals the
     // step's -- and the wave then verifies the candidates of the first candidate lane together
@@ -441,7 +476,7 @@ struct DevWave {
         hq = lane < n ? hq : KM_INVALID;
         if (W > 0) {                                                 // wave-uniform
             const int w0 = imin(lane, W - 1), w1 = imin(lane + 64, W - 1);
-            qk = qkS[(u32)(i + lane)];
+            qk = query_seed_word(i, lane);
             rk0 = rkS[(u32)(r_end + w0)];
             rk1 = rkS[(u32)(r_end + w1)];
             qk = lane < nt ? qk : KM_INVALID;
@@ -876,7 +911,7 @@ struct DevWave {
 #ifdef LZANI_PRIO
         __builtin_amdgcn_s_setprio(LZANI_PRIO);
 #endif
-        qk = qkS[(u32)(i + lane)];
+        qk = query_seed_word(i, lane);
         rk0 = rkS[(u32)(r_end + w0)];
         rk1 = rkS[(u32)(r_end + w1)];
 #ifdef LZANI_PRIO
@@ -932,7 +967,7 @@ struct DevWave {
         const int rlim = R.len - MSL + 1 - WIN;                 // the seed window of r_end <= rlim is complete
         const u32 ldsb = (u32)(size_t)bitmap;                   // LDS byte offset (low half of the flat address)
         const u32 zero = 0, one = 1;
-        const u32* const qks = uniform_ptr(qkS);
+        [[maybe_unused]] const u32* const qks = uniform_ptr(qkS);          // (form T of the query words does not read it)
         const u32* const rks = uniform_ptr(rkS);
         int code, ap, rec, t0, t1, t2, kb, kc, qh = q_head;
         u64 m, seed;
@@ -950,6 +985,21 @@ struct DevWave {
             qc_u = __builtin_amdgcn_readfirstlane(q_cnt); ilim_u = __builtin_amdgcn_readfirstlane(ilim); rlim_u = __builtin_amdgcn_readfirstlane(rlim);
         }
         u32 rk0, rk1, qk, a0, a1, aq, t, bq, w1, dumv, qkb, rk0b, rk1b;
+        // form T of the query words (LZ_NC_LOADS_X): the two register pairs its text words land in
+        constexpr bool QTEXT = LZ_QTEXT_OF(CP);
+        // (v60 .. v63 exist in every kernel of the loops: they are built for at most 8 waves a SIMD, 64 VGPRs and more -- LZANI_WAVES_PER_SIMD; a
+        // lower cap would have to move the pairs.  The literal pairs and the register variables must name the same
+        // registers: the assembler sees only the former, the allocator only the latter.)
+        [[maybe_unused]] register u32 qkT asm("v60"), qkTh asm("v61"), qkbT asm("v62"), qkbTh asm("v63");
+        // (the general turn's rule compares against qend - mrd = Lq - msl: kms_valid_nfree_head at mrd >= 1, where the query's
+        // own strand ends the run of real symbols; at mrd 0 the helper lets an msl-mer run on into the other strand)
+        static_assert(!QTEXT || MRD >= 1, "form T states kms_valid_nfree_head for mrd >= 1 only (chain_params_ok)");
+#define LZ_NC_QOUT_K [qk] "=&v"(qk)
+#define LZ_NC_QOUTB_K [qkb] "=&v"(qkb)
+#define LZ_NC_QOUT_T [qk] "=&v"(qkT), [qkh] "=&v"(qkTh)
+#define LZ_NC_QOUTB_T [qkb] "=&v"(qkbT), [qkbh] "=&v"(qkbTh)
+#define LZ_NC_QIN_K [qks] "s"(qks),
+#define LZ_NC_QIN_T
 #ifdef LZANI_CHAIN_STATS
         int ncnt = 0;
 #define LZ_NC_COUNT "s_add_i32 %[ncnt], %[ncnt], 1\n\t"
@@ -966,17 +1016,58 @@ struct DevWave {
 #else
 #define LZ_NC_NOSEED
 #endif
+#ifdef LZANI_EXP_QCACHED                            // diagnostic build (wrong results): the round's query words from one cached 4 KB (LZ_QK_AT)
+#define LZ_NC_QCACHED "v_and_b32_e32 %[a0], 0xffc, %[a0]\n\t"
+#else
+#define LZ_NC_QCACHED
+#endif
         // the three loads of a tracking round (msl-mers of the 41 steps and of the 80 window positions).  The lanes beyond
         // (steps >= NT, window positions >= WIN) are not masked: their steps are cut from the result (LZ_NC_SEEDS), their
         // window positions are positions of the first load again; what leaves the loop with the round in hand is masked then (LZ_NC_FIX)
-#define LZ_NC_LOADS_X(I, R, QK, K0, K1) \
-            "v_add_lshl_u32 %[a0], %[lane], %[" I "], 2\n\t" \
+        // The query's words come in one of two forms (QF).  K: from its kmS array, as the window's.  T (a kernel for genomes
+        // without N, msl <= 7: query_seed_word): from the packed query text -- the two dwords that hold the 16 symbols from
+        // i + lane on, ONE load into a register pair (still three loads a round: every vmcnt count stands), and behind the
+        // wait a funnel shift by 2 ((i + lane) & 15) and the mask of 2 msl bits (LZ_NC_QDEC).  The pair's upper half is only
+        // live while the load flies.  The operand syntax has no name for the half of a pair, so the two pairs are fixed
+        // registers (LZ_NC_QKP / LZ_NC_QKBP, the variables qk / qkh / qkb / qkbh below).  In bounds: query_seed_word.
+#define LZ_NC_CAT(F, X) LZ_NC_##X##_##F
+#define LZ_NC_QKP "v[60:61]"
+#define LZ_NC_QKBP "v[62:63]"
+#define LZ_NC_QADDR_K(I) "v_add_lshl_u32 %[a0], %[lane], %[" I "], 2\n\t" LZ_NC_QCACHED
+#define LZ_NC_QADDR_T(I) \
+            "v_add_u32_e32 %[a0], %[" I "], %[lane]\n\t" \
+            "v_lshrrev_b32_e32 %[a0], 2, %[a0]\n\t" \
+            "v_and_b32_e32 %[a0], -4, %[a0]\n\t"            /* the byte address of dword (i + lane) >> 4 */
+#define LZ_NC_QLOAD_K(QK, QP) "global_load_dword %[" QK "], %[a0], %[qks]\n\t"
+#define LZ_NC_QLOAD_T(QK, QP) "global_load_dwordx2 " QP ", %[a0], %[qt2]\n\t"
+#define LZ_NC_LOADS_X(QF, I, R, QK, QP, K0, K1) \
+            LZ_NC_CAT(QF, QADDR)(I) \
             "v_add_lshl_u32 %[a1], %[lane], %[" R "], 2\n\t" \
             "v_add_lshl_u32 %[aq], %[w1], %[" R "], 2\n\t" \
-            "global_load_dword %[" QK "], %[a0], %[qks]\n\t" \
+            LZ_NC_CAT(QF, QLOAD)(QK, QP) \
             "global_load_dword %[" K0 "], %[a1], %[rks]\n\t" \
             "global_load_dword %[" K1 "], %[aq], %[rks]\n\t"
-#define LZ_NC_LOADS_F LZ_NC_LOADS_X("i", "rend", "qk", "rk0", "rk1")
+#define LZ_NC_LOADS_F(QF) LZ_NC_LOADS_X(QF, "i", "rend", "qk", LZ_NC_QKP, "rk0", "rk1")
+        // the query words of a round out of the text words that have landed (form T; aq and t are free at that point of the
+        // round).  QDECF: a fast turn's -- its GO bit promises an msl-mer at all 64 positions.  QDECG: the general turn's and the
+        // stretch chain's -- a step whose msl-mer would run beyond the query's last symbol, i + lane + msl > Lq, has none
+        // (kms_valid_nfree_head; Lq - msl = qend - mrd in a pair without N, and this form's kernels have no other)
+#define LZ_NC_QPREF_K(I)
+#define LZ_NC_QDECF_K(I, QK, QH)
+#define LZ_NC_QDECG_K(I, QK, QH)
+        /* (a fast turn works the shift out while its loads fly -- aq is free from the next turn's request to the round's own use) */
+#define LZ_NC_QPREF_T(I) "v_add_lshl_u32 %[aq], %[lane], %[" I "], 1\n\t"  /* (v_alignbit takes the low five bits) */
+#define LZ_NC_QDECF_T(I, QK, QH) \
+            "v_alignbit_b32 %[" QK "], %[" QH "], %[" QK "], %[aq]\n\t" \
+            "v_and_b32_e32 %[" QK "], %[KMASK], %[" QK "]\n\t"
+#define LZ_NC_QDECG_T(I, QK, QH) \
+            "v_add_u32_e32 %[aq], %[" I "], %[lane]\n\t" \
+            "v_add_u32_e32 %[t], %[MRD], %[aq]\n\t" \
+            "v_lshlrev_b32_e32 %[aq], 1, %[aq]\n\t" \
+            "v_cmp_ge_i32_e32 vcc, %[qend], %[t]\n\t" \
+            "v_alignbit_b32 %[" QK "], %[" QH "], %[" QK "], %[aq]\n\t" \
+            "v_and_b32_e32 %[" QK "], %[KMASK], %[" QK "]\n\t" \
+            "v_cndmask_b32_e32 %[" QK "], -1, %[" QK "], vcc\n\t"
         // the round itself (track_round + seed_prefilter): window k-mers into the LDS bitmap, every step tests its own, the
         // bits are cleared again; leaves the steps with a seed candidate in seed.  A lane without a k-mer (KM_INVALID >> 5 is
         // beyond every word of the bitmap) works on its own word behind the bitmap (SEED_PAD) by a minimum: no lane select,
@@ -1002,12 +1093,13 @@ struct DevWave {
             "v_lshrrev_b32_e32 %[" T "], %[KS], %[" K "]\n\t" \
             "v_lshlrev_b32_e32 %[" T "], %[" T "], %[one]\n\t" \
             "v_lshl_add_u32 %[" A "], %[" A "], 2, %[ldsb]\n\t"
-#define LZ_NC_ROUND_X(WORD, WAIT, QK, K0, K1) \
+#define LZ_NC_ROUND_X(QDEC, WORD, WAIT, I, QK, QH, K0, K1) \
             WAIT "\n\t" \
             WORD("a0", "t", K0) \
             "ds_or_b32 %[a0], %[t]\n\t" \
             WORD("a1", "bq", K1) \
             "ds_or_b32 %[a1], %[bq]\n\t" \
+            QDEC(I, QK, QH) \
             WORD("aq", "t", QK) \
             "ds_read_b32 %[aq], %[aq]\n\t" \
             "ds_write_b32 %[a0], %[zero]\n\t" \
@@ -1015,9 +1107,9 @@ struct DevWave {
             "s_waitcnt lgkmcnt(2)\n\t" \
             "v_and_b32_e32 %[aq], %[aq], %[t]\n\t" \
             "v_cmp_ne_u32_e64 %[seed], 0, %[aq]\n\t"
-#define LZ_NC_ROUND_F(WORD) LZ_NC_ROUND_X(WORD, "s_waitcnt vmcnt(0)", "qk", "rk0", "rk1")
+#define LZ_NC_ROUND_F(QF, WORD) LZ_NC_ROUND_X(LZ_NC_CAT(QF, QDECG), WORD, "s_waitcnt vmcnt(0)", "i", "qk", "qkh", "rk0", "rk1")
         // one fast turn (see Lnc_fast)
-#define LZ_NC_FTURN(WORDF, P, N, IC, IN, RN, CQ, C0, C1, NQ, N0, N1, SFX) \
+#define LZ_NC_FTURN(QF, WORDF, P, N, IC, IN, RN, CQ, CQH, C0, C1, NQ, NQP, N0, N1, SFX) \
             "Lnc_fturn" SFX "_%=:\n\t" \
             "s_bitcmp0_b32 %[" P "], 15\n\t" \
             "s_cbranch_scc1 Lnc_fnogo" SFX "_%=\n\t" \
@@ -1029,8 +1121,9 @@ struct DevWave {
             "s_sub_i32 %[gap], %[ap], %[" IC "]\n\t" \
             "s_add_i32 %[" IN "], %[ap], %[t0]\n\t" \
             "s_add_i32 %[" RN "], %[bpos], %[t0]\n\t" \
-            LZ_NC_LOADS_X(IN, RN, NQ, N0, N1) \
-            LZ_NC_ROUND_X(WORDF, "s_waitcnt vmcnt(3)", CQ, C0, C1) \
+            LZ_NC_LOADS_X(QF, IN, RN, NQ, NQP, N0, N1) \
+            LZ_NC_CAT(QF, QPREF)(IC) \
+            LZ_NC_ROUND_X(LZ_NC_CAT(QF, QDECF), WORDF, "s_waitcnt vmcnt(3)", IC, CQ, CQH, C0, C1) \
             LZ_NC_SEEDS \
             "s_cbranch_scc1 Lnc_frec" SFX "_%=\n\t"         /* a seed candidate: the state first, then the seed event */ \
             "s_mov_b32 %[t2], %[qh]\n\t" \
@@ -1097,8 +1190,8 @@ struct DevWave {
             "s_cmp_lg_u32 %[tnt], 0\n\t" \
             "s_cbranch_scc1 Lnc_chk_%=\n\t"
 #define LZ_NC_SPLITIN , [tnt] "s"(tnt_u)
-#define LZ_NC_ASM(WORD, WORDF) LZ_NC_ASM_X(WORD, WORDF, "", "", )
-#define LZ_NC_ASM_X(WORD, WORDF, SPLCHK, SPLGEN, SPLIN) \
+#define LZ_NC_ASM(QF, WORD, WORDF) LZ_NC_ASM_X(QF, WORD, WORDF, "", "", )
+#define LZ_NC_ASM_X(QF, WORD, WORDF, SPLCHK, SPLGEN, SPLIN) \
         asm volatile( \
             LZ_NC_PRIO_ON \
             "s_mov_b32 %[code], 0\n\t" \
@@ -1135,7 +1228,7 @@ struct DevWave {
             "s_cmp_gt_i32 %[rend], %[rlim]\n\t" \
             "s_cbranch_scc1 Lnc_end_%=\n\t" \
             SPLCHK \
-            LZ_NC_LOADS_F \
+            LZ_NC_LOADS_F(QF) \
             /* While the loads fly: the next queued candidate and, should the round find no seed candidate, whether it is */ \
             /* a null event (t2 = 1): plain, distant, the open region short (dropped), both extensions empty by the record */ \
             "v_readlane_b32 %[blen], %[alen], %[qh]\n\t" \
@@ -1199,7 +1292,7 @@ struct DevWave {
             "Lnc_ok_%=:\n\t" \
             "s_mov_b32 %[t2], 1\n" \
             "Lnc_chk_%=:\n\t" \
-            LZ_NC_ROUND_F(WORD) \
+            LZ_NC_ROUND_F(QF, WORD) \
             "s_mov_b32 %[code], 1\n\t" \
             LZ_NC_SEEDS \
             "s_cbranch_scc1 Lnc_sseed_%=\n"                 /* a seed candidate: the round is done; the event itself, if it is simple */ \
@@ -1243,14 +1336,14 @@ struct DevWave {
             "s_sub_i32 %[t2], %[qh], 1\n\t"                /* the last committed entry (t2 stays untouched to the end of the turn) */ \
             "v_readlane_b32 %[cls], %[alen], %[t2]\n"      /* its word */ \
             "Lnc_fstart_%=:\n\t" \
-            LZ_NC_LOADS_F \
+            LZ_NC_LOADS_F(QF) \
             /* Two turns a pass, in two sets of registers that take turns: a turn requests the k-mers of the NEXT turn's round */ \
             /* -- where that round stands follows from the successor's queue entry alone, not from this round's outcome -- */ \
             /* before it waits for its own, so the loads of one turn fly during the LDS phase of the turn before.  A turn that */ \
             /* ends the run (no GO, a seed candidate) leaves the request behind; what leaves the second turn puts the */ \
             /* registers back: cls the committed entry's word, blen the successor's, i / rend the round's, qk / rk0 / rk1 its k-mers. */ \
-            LZ_NC_FTURN(WORDF, "cls", "blen", "i", "t1", "kb", "qk", "rk0", "rk1", "qkb", "rk0b", "rk1b", "") \
-            LZ_NC_FTURN(WORDF, "blen", "cls", "t1", "i", "rend", "qkb", "rk0b", "rk1b", "qk", "rk0", "rk1", "2") \
+            LZ_NC_FTURN(QF, WORDF, "cls", "blen", "i", "t1", "kb", "qk", "qkh", "rk0", "rk1", "qkb", LZ_NC_QKBP, "rk0b", "rk1b", "") \
+            LZ_NC_FTURN(QF, WORDF, "blen", "cls", "t1", "i", "rend", "qkb", "qkbh", "rk0b", "rk1b", "qk", LZ_NC_QKP, "rk0", "rk1", "2") \
             "s_branch Lnc_fturn_%=\n" \
             "Lnc_fnogo2_%=:\n\t" \
             "s_mov_b32 %[i], %[t1]\n\t" \
@@ -1626,27 +1719,29 @@ struct DevWave {
               [code] "=&s"(code), [ap] "=&s"(ap), [bpos] "=&s"(bpos), [blen] "=&s"(blen), [lastb] "=&s"(last_cl), [lastlit] "=&s"(last_clit), [rec] "=&s"(rec), \
               [t0] "=&s"(t0), [t1] "=&s"(t1), [t2] "=&s"(t2), [kb] "=&s"(kb), [kc] "=&s"(kc), [m] "=&s"(m), [seed] "=&s"(seed), \
               [gap] "=&s"(gap), [cls] "=&s"(cls), [fok] "=&s"(fok), [atm] "=&s"(add_tm), [atl] "=&s"(add_tl), [atc] "=&s"(add_tc), [m2] "=&s"(m2), \
-              [rk0] "=&v"(rk0), [rk1] "=&v"(rk1), [qk] "=&v"(qk), [a0] "=&v"(a0), [a1] "=&v"(a1), [aq] "=&v"(aq), [t] "=&v"(t), [bq] "=&v"(bq), [w1] "=&v"(w1), [dumv] "=&v"(dumv), [qkb] "=&v"(qkb), [rk0b] "=&v"(rk0b), [rk1b] "=&v"(rk1b) \
-            : [qc] "s"(qc_u), [ilim] "s"(ilim_u), [rlim] "s"(rlim_u), [qks] "s"(qks), [rks] "s"(rks), [ocl] "s"(ocl_u), [oclit] "s"(oclit_u), \
+              [rk0] "=&v"(rk0), [rk1] "=&v"(rk1), LZ_NC_CAT(QF, QOUT), [a0] "=&v"(a0), [a1] "=&v"(a1), [aq] "=&v"(aq), [t] "=&v"(t), [bq] "=&v"(bq), [w1] "=&v"(w1), [dumv] "=&v"(dumv), LZ_NC_CAT(QF, QOUTB), [rk0b] "=&v"(rk0b), [rk1b] "=&v"(rk1b) \
+            : [qc] "s"(qc_u), [ilim] "s"(ilim_u), [rlim] "s"(rlim_u), LZ_NC_CAT(QF, QIN) [rks] "s"(rks), [ocl] "s"(ocl_u), [oclit] "s"(oclit_u), \
               [rt2] "s"(rt2), [qt2] "s"(qt2), [qend] "s"(qend), [wdum] "s"((int)SEED_BM_WORDS) SPLIN, \
               [apos] "v"(a_pos), [alen] "v"(a_len), [aref] "v"(a_ref), [aext] "v"(a_ext), [lane] "v"(lane), \
               [ldsb] "v"(ldsb), [zero] "v"(zero), [one] "v"(one), \
               [MQD] "n"(MQD), [MRD] "n"(MRD), [REG] "n"(REG), [AW] "n"(AW), [NT] "n"(NT), [WIN] "s"((int)WIN), [NR1] "n"(WIN - 64), [MSL] "n"(MSL), [MSL64] "n"(MSL + 64), [C41M] "n"(3 * MRD + 1 - WIN - MSL), [C40M] "n"(MRD - MSL), [CQ64] "n"(MRD + 64), [C2MRD] "n"(2 * MRD), \
-              [AW1] "n"(AW - 1), [AW1C] "n"(33 - AW), [AWM] "n"((1 << AW) - 1), [ARM] "n"(((1 << AR) - 1) << (AW - AR)), [AM] "n"(AM), [KS5] "n"(2 * MSL + 5), [KS] "n"(2 * MSL) \
+              [AW1] "n"(AW - 1), [AW1C] "n"(33 - AW), [AWM] "n"((1 << AW) - 1), [ARM] "n"(((1 << AR) - 1) << (AW - AR)), [AM] "n"(AM), [KS5] "n"(2 * MSL + 5), [KS] "n"(2 * MSL), [KMASK] "n"((1 << (2 * (MSL <= 7 ? MSL : 7))) - 1) \
             : "vcc", "scc", "memory");
 #ifdef LZANI_PHASE_TIME
         const unsigned long long pt_t0 = pt_now();
 #endif
         if constexpr (SPLITW) {
-            if constexpr (MSL == 9) { LZ_NC_ASM_X(LZ_NC_WORD9, LZ_NC_WORD9, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
-            else if constexpr (MSL == 8) { LZ_NC_ASM_X(LZ_NC_WORD8, LZ_NC_WORD8, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
-            else if constexpr (CP::NF) { LZ_NC_ASM_X(LZ_NC_WORD7, LZ_NC_WORD7N, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
-            else { LZ_NC_ASM_X(LZ_NC_WORD7, LZ_NC_WORD7, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
+            if constexpr (MSL == 9) { LZ_NC_ASM_X(K, LZ_NC_WORD9, LZ_NC_WORD9, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
+            else if constexpr (MSL == 8) { LZ_NC_ASM_X(K, LZ_NC_WORD8, LZ_NC_WORD8, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
+            else if constexpr (QTEXT) { LZ_NC_ASM_X(T, LZ_NC_WORD7, LZ_NC_WORD7N, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) qk = qkT; }
+            else if constexpr (CP::NF) { LZ_NC_ASM_X(K, LZ_NC_WORD7, LZ_NC_WORD7N, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
+            else { LZ_NC_ASM_X(K, LZ_NC_WORD7, LZ_NC_WORD7, LZ_NC_SPLITCHK, LZ_NC_SPLITGEN, LZ_NC_SPLITIN) }
         } else
-        if constexpr (MSL == 9) { LZ_NC_ASM(LZ_NC_WORD9, LZ_NC_WORD9) }
-        else if constexpr (MSL == 8) { LZ_NC_ASM(LZ_NC_WORD8, LZ_NC_WORD8) }
-        else if constexpr (CP::NF) { LZ_NC_ASM(LZ_NC_WORD7, LZ_NC_WORD7N) }          // (N-free by instantiation: see chain_classes)
-        else { LZ_NC_ASM(LZ_NC_WORD7, LZ_NC_WORD7) }
+        if constexpr (MSL == 9) { LZ_NC_ASM(K, LZ_NC_WORD9, LZ_NC_WORD9) }
+        else if constexpr (MSL == 8) { LZ_NC_ASM(K, LZ_NC_WORD8, LZ_NC_WORD8) }
+        else if constexpr (QTEXT) { LZ_NC_ASM(T, LZ_NC_WORD7, LZ_NC_WORD7N) qk = qkT; }          // (N-free by instantiation: see chain_classes)
+        else if constexpr (CP::NF) { LZ_NC_ASM(K, LZ_NC_WORD7, LZ_NC_WORD7N) }
+        else { LZ_NC_ASM(K, LZ_NC_WORD7, LZ_NC_WORD7) }
 #ifdef LZANI_PHASE_TIME
         pt_chain += pt_now() - pt_t0;
 #endif
@@ -1709,7 +1804,7 @@ struct DevWave {
         const int ilim = SPLITW ? imin(iend - NT, stop_i - (int)SPLIT_MARGIN) : iend - NT, rlim = R.len - MSL + 1 - WIN;
         const u32 ldsb = (u32)(size_t)bitmap;
         const u32 zero = 0, one = 1;
-        const u32* const qks = uniform_ptr(qkS);
+        [[maybe_unused]] const u32* const qks = uniform_ptr(qkS);          // (form T of the query words does not read it)
         const u32* const rks = uniform_ptr(rkS);
         const u32* const qkl = uniform_ptr(qkL);
         const u32* const rt2 = uniform_ptr(reinterpret_cast<const u32*>(R.t2));
@@ -1722,6 +1817,9 @@ struct DevWave {
         int ncm, t0, t1, t2, kb, kc, gap, rec, cls, fok, blen, anc, aent;
         u64 m, seed, m2, pmk;
         u32 rk0, rk1, qk, hq, a0, a1, aq, t, bq, w1, dumv;
+        constexpr bool QTEXT = LZ_QTEXT_OF(CP);               // (see null_chain: form T of the query words)
+        [[maybe_unused]] register u32 qkT asm("v60"), qkTh asm("v61");
+        static_assert(!QTEXT || MRD >= 1, "form T states kms_valid_nfree_head for mrd >= 1 only (chain_params_ok)");
         [[maybe_unused]] u64 cwa, cwb;                     // bitmap form: two words of the pair's candidate bitmap
         [[maybe_unused]] u32 e0, e1, e2, e3, tagl;         //              the seed step's bucket, its tag
         [[maybe_unused]] const unsigned long long* const cbp = JOIN ? reinterpret_cast<const unsigned long long*>(uniform_ptr(reinterpret_cast<const u32*>(cand_bits))) : nullptr;
@@ -1867,7 +1965,14 @@ struct DevWave {
 #define LZ_SC_J_XOUT , [cwa] "=&s"(cwa), [cwb] "=&s"(cwb), [e0] "=&s"(e0), [e1] "=&s"(e1), [e2] "=&s"(e2), [e3] "=&s"(e3), [tagl] "=&s"(tagl)
 #define LZ_SC_J_XIN , [cbp] "s"(cbp)
 #define LZ_SC_CAT(F, X) LZ_SC_##F##_##X
-#define LZ_SC_ASM(WORD, F) \
+        /* the steps' mixed mal-mer hashes: at the byte offset of the query's kmS words, which form T does not compute */
+#define LZ_SC_HQLOAD_K "global_load_dword %[hq], %[a0], %[qkl]\n\t"
+#define LZ_SC_HQLOAD_T \
+            "v_add_lshl_u32 %[t], %[lane], %[i], 2\n\t" \
+            "global_load_dword %[hq], %[t], %[qkl]\n\t"
+#define LZ_SC_QOUT_K [qk] "=&v"(qk)
+#define LZ_SC_QOUT_T [qk] "=&v"(qkT), [qkh] "=&v"(qkTh)
+#define LZ_SC_ASM(QF, WORD, F) \
         asm volatile( \
             "s_mov_b32 %[ncm], 0\n\t" "s_mov_b32 %[kind], 0\n\t" LZ_SC_WHY(10) \
             "v_add_u32_e32 %[w1], 64, %[lane]\n\t" \
@@ -1880,10 +1985,10 @@ struct DevWave {
             "s_cbranch_scc1 Lsc_end_%=\n\t" \
             LZ_SC_WHY(1) "s_cmp_gt_i32 %[rend], %[rlim]\n\t" \
             "s_cbranch_scc1 Lsc_end_%=\n\t" \
-            LZ_NC_LOADS_F \
-            "global_load_dword %[hq], %[a0], %[qkl]\n\t"    /* the steps' mixed mal-mer hashes */ \
+            LZ_NC_LOADS_F(QF) \
+            LZ_SC_HQLOAD_##QF \
             "s_mov_b32 %[gap], %[NT]\n\t"                   /* (every tracking step counts: LZ_NC_SEEDS) */ \
-            LZ_NC_ROUND_F(WORD) \
+            LZ_NC_ROUND_F(QF, WORD) \
             LZ_NC_SEEDS \
             LZ_SC_WHY(2) "s_cbranch_scc0 Lsc_noseed_%=\n\t"              /* no seed candidate at all: the anchors of all the steps (find_event, told so) */ \
             LZ_NC_FIX \
@@ -2174,23 +2279,25 @@ struct DevWave {
             : LZ_SC_WHY_OPERAND [i] "+s"(i), [rend] "+s"(r_end), [cl] "+s"(cl), [clit] "+s"(clit), [ncm] "=&s"(ncm), \
               [t0] "=&s"(t0), [t1] "=&s"(t1), [t2] "=&s"(t2), [kb] "=&s"(kb), [kc] "=&s"(kc), [gap] "=&s"(gap), [rec] "=&s"(rec), [cls] "=&s"(cls), \
               [fok] "=&s"(fok), [blen] "=&s"(blen), [anc] "=&s"(anc), [aent] "=&s"(aent), [kind] "=&s"(kind), [m] "=&s"(m), [seed] "=&s"(seed), [m2] "=&s"(m2), [pmk] "=&s"(pmk), \
-              [rk0] "=&v"(rk0), [rk1] "=&v"(rk1), [qk] "=&v"(qk), [hq] "=&v"(hq), [a0] "=&v"(a0), [a1] "=&v"(a1), [aq] "=&v"(aq), [t] "=&v"(t), [bq] "=&v"(bq), \
+              [rk0] "=&v"(rk0), [rk1] "=&v"(rk1), LZ_SC_QOUT_##QF, [hq] "=&v"(hq), [a0] "=&v"(a0), [a1] "=&v"(a1), [aq] "=&v"(aq), [t] "=&v"(t), [bq] "=&v"(bq), \
               [w1] "=&v"(w1), [dumv] "=&v"(dumv) LZ_SC_CAT(F, XOUT) \
-            : [ilim] "s"(ilim_u), [rlim] "s"(rlim_u), [qks] "s"(qks), [rks] "s"(rks), [qkl] "s"(qkl), [rt2] "s"(rt2), [qt2] "s"(qt2), [bkp] "s"(bkp), \
+            : [ilim] "s"(ilim_u), [rlim] "s"(rlim_u), LZ_NC_CAT(QF, QIN) [rks] "s"(rks), [qkl] "s"(qkl), [rt2] "s"(rt2), [qt2] "s"(qt2), [bkp] "s"(bkp), \
               [qend] "s"(qend), [wdum] "s"((int)SEED_BM_WORDS), [TB] "s"(tbits), [PB] "s"(pbits), [TAGM] "s"(tagm) LZ_SC_CAT(F, XIN), \
               [lane] "v"(lane), [ldsb] "v"(ldsb), [zero] "v"(zero), [one] "v"(one), \
               [MRD] "n"(MRD), [NT] "n"(NT), [WIN] "s"((int)WIN), [NR1] "n"(WIN - 64), [MSL] "n"(MSL), [MSL64] "n"(MSL + 64), \
               [C41M] "n"(3 * MRD + 1 - WIN - MSL), [C40M] "n"(MRD - MSL), [CQ64] "n"(MRD + 64), [C2MRD] "n"(2 * MRD), \
-              [AW1] "n"(AW - 1), [AW1C] "n"(33 - AW), [AWM] "n"((1 << AW) - 1), [ARM] "n"(((1 << AR) - 1) << (AW - AR)), [AM] "n"(AM), [KS5] "n"(2 * MSL + 5), [KS] "n"(2 * MSL) \
+              [AW1] "n"(AW - 1), [AW1C] "n"(33 - AW), [AWM] "n"((1 << AW) - 1), [ARM] "n"(((1 << AR) - 1) << (AW - AR)), [AM] "n"(AM), [KS5] "n"(2 * MSL + 5), [KS] "n"(2 * MSL), [KMASK] "n"((1 << (2 * (MSL <= 7 ? MSL : 7))) - 1) \
             : "vcc", "scc", "memory");
         if constexpr (JOIN) {
-            if constexpr (MSL == 9) { LZ_SC_ASM(LZ_NC_WORD9, J) }
-            else if constexpr (MSL == 8) { LZ_SC_ASM(LZ_NC_WORD8, J) }
-            else { LZ_SC_ASM(LZ_NC_WORD7, J) }
+            if constexpr (MSL == 9) { LZ_SC_ASM(K, LZ_NC_WORD9, J) }
+            else if constexpr (MSL == 8) { LZ_SC_ASM(K, LZ_NC_WORD8, J) }
+            else if constexpr (QTEXT) { LZ_SC_ASM(T, LZ_NC_WORD7, J) }
+            else { LZ_SC_ASM(K, LZ_NC_WORD7, J) }
         } else {
-            if constexpr (MSL == 9) { LZ_SC_ASM(LZ_NC_WORD9, P) }
-            else if constexpr (MSL == 8) { LZ_SC_ASM(LZ_NC_WORD8, P) }
-            else { LZ_SC_ASM(LZ_NC_WORD7, P) }
+            if constexpr (MSL == 9) { LZ_SC_ASM(K, LZ_NC_WORD9, P) }
+            else if constexpr (MSL == 8) { LZ_SC_ASM(K, LZ_NC_WORD8, P) }
+            else if constexpr (QTEXT) { LZ_SC_ASM(T, LZ_NC_WORD7, P) }
+            else { LZ_SC_ASM(K, LZ_NC_WORD7, P) }
         }
 #undef LZ_SC_ASM
         last_src = -1;
@@ -2206,6 +2313,29 @@ struct DevWave {
     }
 #undef LZ_NC_LOADS_F
 #undef LZ_NC_LOADS_X
+#undef LZ_NC_CAT
+#undef LZ_NC_QKP
+#undef LZ_NC_QKBP
+#undef LZ_NC_QADDR_K
+#undef LZ_NC_QADDR_T
+#undef LZ_NC_QLOAD_K
+#undef LZ_NC_QLOAD_T
+#undef LZ_NC_QPREF_K
+#undef LZ_NC_QPREF_T
+#undef LZ_NC_QDECF_K
+#undef LZ_NC_QDECG_K
+#undef LZ_NC_QDECF_T
+#undef LZ_NC_QDECG_T
+#undef LZ_NC_QOUT_K
+#undef LZ_NC_QOUT_T
+#undef LZ_NC_QOUTB_K
+#undef LZ_NC_QOUTB_T
+#undef LZ_NC_QIN_K
+#undef LZ_NC_QIN_T
+#undef LZ_SC_HQLOAD_K
+#undef LZ_SC_HQLOAD_T
+#undef LZ_SC_QOUT_K
+#undef LZ_SC_QOUT_T
 #undef LZ_NC_ROUND_X
 #undef LZ_NC_ROUND_F
 #undef LZ_NC_ASM
@@ -2641,6 +2771,7 @@ __device__ __forceinline__ u32 row_of_ticket(const u64* __restrict__ qcum, u32 r
 #ifndef LZANI_WAVES_PER_SIMD
 #define LZANI_WAVES_PER_SIMD 8                 // (occupancy experiments: the register budget of the pair kernel)
 #endif
+static_assert(LZANI_WAVES_PER_SIMD <= 8, "the null chain names v60 .. v63 (form T of the query words): below 64 VGPRs a wave its register pairs must move");
 template <bool FAST, bool NFREE, int DEFP, bool ALN, bool BK, int CAND>
 __device__ __forceinline__ void pairs_loop(const PairArgs& a)
 {
