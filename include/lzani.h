@@ -775,6 +775,84 @@ int lzani_get_cluster_link_info(const lzani_ctx *ctx, lzani_cluster_link_info *i
 /* LZANI_ERR_STATE unless the last run was one of LZANI_CLUSTER_LEIDEN. */
 int lzani_get_cluster_leiden_info(const lzani_ctx *ctx, lzani_cluster_leiden_info *info);
 
+/* ---- Cluster levels: cuts at cluster time, several clusterings of one run ------------------------------------------
+ * Above, the edge threshold of the graph is the output filter of the kept call.  A record store keeps the kept records of
+ * one or more kept calls on the device (36 B each), and a LEVEL makes the edges of a clustering from the store under a CUT
+ * of its own: the alignment runs once under a loose filter, and any number of levels (measure, cut, algorithm) follow.
+ *
+ * Cut.  Five minima as lzani_out_filter's, a minimum of len_ratio and a maximum of num_alns; all zero passes everything
+ * that an output filter whose minima are not negative kept (a negative value, which only made-up integers give, is below
+ * the minimum 0 there as here).
+ * Rule, for one kept record (a < b, X, Y, lines) with the reported lengths la, lb (lzani_cluster_plan.h: cluster_cut_lines,
+ * over out_pair_tani, out_line_ratios and out_filter_line of lzani_out_filter.h):
+ *   - the five values of line 0 ("b against a") and of line 1 ("a against b") are the output filter's; a line passes the
+ *     five minima as there: a value passes unless it is < its minimum, and NaN and inf are below nothing;
+ *   - len_ratio of the pair is the emitter's: (double)min(la, lb) / (double)max(la, lb), one IEEE division, where both
+ *     lengths are nonzero, else 0; both lines pass unless len_ratio < min_len_ratio;
+ *   - num_alns of line 0 is X.no_components, of line 1 Y.no_components; a line passes iff max_num_alns == 0 or
+ *     (int64)no_components <= (int64)max_num_alns;
+ *   - cut_lines = lines & (pass0 | pass1 << 1): a cut only takes away lines that the output filter kept;
+ *   - the record is an edge of the level iff cut_lines != 0, and its weight is lzani_cluster_weight(measure, X, Y,
+ *     cut_lines, la, lb): the weight above over the lines that remain.
+ * A NaN minimum or reserved_ != 0: LZANI_ERR_ARG.
+ * What the definition gives:
+ *   - an all-zero cut makes, record for record and bit for bit, the edges that lzani_cluster_add_kept makes (of records
+ *     kept under minima that are not negative: every line they name passes 0 again);
+ *   - if every minimum of F' is >= that of F, a kept call under F followed by a level whose five minima are F' gives the
+ *     edges of a kept call under F' followed by lzani_cluster_add_kept (passing F' implies passing F, NaN included);
+ *   - levels are independent clusterings: nothing nests a strict level's clusters inside a loose one's, except where the
+ *     algorithm gives it (single linkage).
+ * Record store.  A lifetime group of the context like the kept result and the cluster state, from
+ * lzani_cluster_store_begin to the next one or lzani_set_genomes: n, the n reported lengths on the device, and a buffer of
+ * 9-word records grown geometrically by allocate-and-copy, as the edge buffer grows.  A failed growth leaves the records
+ * that were there.  The store is independent of the cluster state: a level reads it, and no cluster call changes it.
+ * The device stage (k_cl_level): blocks of 256 threads over 4,096 records each, 16 a thread; a count pass (the rule; edges per block of 4,096 records, the
+ * lines in and out summed), a scan, the edge buffer reserved at the exact total, a write pass that stores one 16-byte edge
+ * per passing record, in record order.  Per record 36 B and two lengths read, per edge 16 B written. */
+typedef struct lzani_cluster_cut {
+    double   min_tani, min_gani, min_ani, min_qcov, min_rcov;  /* as lzani_out_filter's            */
+    double   min_len_ratio;                                    /* 0: none                          */
+    uint32_t max_num_alns;                                     /* 0: none                          */
+    uint32_t reserved_;                                        /* must be 0                        */
+} lzani_cluster_cut;                                           /* 56 bytes; all zero: see "Cut" above  */
+typedef struct lzani_cluster_store_info {
+    uint32_t n;                       /* genomes                                                                 */
+    uint64_t records;                /* records added so far                                                    */
+    uint64_t record_bytes;            /* device bytes of the record buffer                                       */
+    double   add_ms;                  /* HIP events on the context's stream: the appends summed                  */
+} lzani_cluster_store_info;
+typedef struct lzani_cluster_level_info {
+    uint64_t records_in, edges_out;   /* the store's records; those of which a line stays: the level's edges     */
+    uint64_t lines_in, lines_out;     /* set bits of `lines` and of cut_lines, summed over the records           */
+    double   level_ms;                /* HIP events on the context's stream: count pass to write pass, the total's read-back and the edge allocation between them included */
+} lzani_cluster_level_info;
+/* The rule as a pure host function (no GPU): cut_lines.  NULL pointers, a NaN minimum or reserved_ != 0: 0xFFFFFFFF. */
+uint32_t lzani_cluster_cut_lines(const lzani_cluster_cut *cut, const lzani_result *x, const lzani_result *y, uint32_t lines,
+                                 uint32_t len_a, uint32_t len_b);
+/* An empty record store for n genomes; report_len, rules and errors as in lzani_cluster_begin.  The drop of the old store
+ * comes first: LZANI_ERR_NOMEM leaves no store.  The cluster state is not touched. */
+int lzani_cluster_store_begin(lzani_ctx *ctx, uint32_t n, const uint32_t *report_len);
+/* Appends the records of the context's current kept result by a device copy.  No store or no kept result: LZANI_ERR_STATE;
+ * a kept result of another n: LZANI_ERR_ARG; LZANI_ERR_NOMEM leaves the records that were there. */
+int lzani_cluster_store_add_kept(lzani_ctx *ctx, uint64_t *records_total);
+/* lzani_cluster_begin(n, the store's lengths, measure) followed by the level's edges: afterwards the context is in an
+ * ordinary begun cluster state, and lzani_cluster_run, fetch, add_kept, debug_add_edges and every info call behave as after
+ * a begin plus adds.  The store is only read: the call may be repeated with another cut or measure any number of times.  As
+ * in lzani_cluster_begin the old cluster state is dropped first: LZANI_ERR_NOMEM leaves no cluster state, the store intact,
+ * and the call may be made again.  No store: LZANI_ERR_STATE; a NaN minimum, reserved_ != 0 or an unknown measure:
+ * LZANI_ERR_ARG, before anything is dropped; more records than one launch covers: LZANI_ERR_ARG. */
+int lzani_cluster_level(lzani_ctx *ctx, int measure, const lzani_cluster_cut *cut, uint64_t *edges);
+/* LZANI_ERR_STATE without a store. */
+int lzani_get_cluster_store_info(const lzani_ctx *ctx, lzani_cluster_store_info *info);
+/* LZANI_ERR_STATE unless the current cluster state came from lzani_cluster_level. */
+int lzani_get_cluster_level_info(const lzani_ctx *ctx, lzani_cluster_level_info *info);
+/* Test hook: appends made-up records from host memory, checked first (a < b < n, lines in 1..3): LZANI_ERR_ARG before
+ * anything runs.  LZANI_ERR_NOMEM leaves the records that were there. */
+int lzani_debug_cluster_store_add(lzani_ctx *ctx, const lzani_kept_pair *rec, uint64_t count);
+/* Test hook: edges first .. first + count - 1 of the current cluster state, in the buffer's order.  No cluster state:
+ * LZANI_ERR_STATE; a range past the end: LZANI_ERR_ARG. */
+int lzani_debug_cluster_edges(lzani_ctx *ctx, uint64_t first, uint64_t count, lzani_cluster_edge *out);
+
 /* ---- Sharding over GPUs ---------------------------------------------------------------
  * The unit that shards is the reference's own work unit, one reference ROW (lz_matcher.cpp:196-255: a worker
  * takes a reference, builds its index once and parses every query of the row).  Rows are independent; the
@@ -844,6 +922,12 @@ int lzani_group_get_cluster_cover_info(const lzani_group *grp, lzani_cluster_cov
 int lzani_group_get_cluster_link_info(const lzani_group *grp, lzani_cluster_link_info *info);
 int lzani_group_set_cluster_leiden(lzani_group *grp, double resolution, int iterations);
 int lzani_group_get_cluster_leiden_info(const lzani_group *grp, lzani_cluster_leiden_info *info);
+/* Cluster levels for the group: the record store and the levels on the first device's context. */
+int lzani_group_cluster_store_begin(lzani_group *grp, uint32_t n, const uint32_t *report_len);
+int lzani_group_cluster_store_add_kept(lzani_group *grp, uint64_t *records_total);
+int lzani_group_cluster_level(lzani_group *grp, int measure, const lzani_cluster_cut *cut, uint64_t *edges);
+int lzani_group_get_cluster_store_info(const lzani_group *grp, lzani_cluster_store_info *info);
+int lzani_group_get_cluster_level_info(const lzani_group *grp, lzani_cluster_level_info *info);
 
 /* The shard bookkeeping of lzani_group_run_rows as a pure host function (no GPU): rows keep their order inside
  * their shard, the shards follow each other in the gathered buffer (shard d from result shard_base[d] on,

@@ -10,12 +10,17 @@
 // (lzani_cluster_begin, lzani_cluster_add_kept, lzani_debug_cluster_add_edges, lzani_cluster_run -- the one choice of a unit
 // by `algo` --, lzani_cluster_fetch, lzani_get_cluster_info, lzani_get_cluster_cover_info, lzani_get_cluster_link_info,
 // lzani_set_cluster_leiden, lzani_get_cluster_leiden_info and the pure lzani_cluster_weight, lzani_cluster_host and
-// lzani_cluster_leiden_host).  A further algorithm is one more unit and one more case in lzani_cluster_run.
+// lzani_cluster_leiden_host); and the cluster levels -- the record store of the context (cluster_store_reserve,
+// cluster_store_append: a device copy behind a growth step), the level's edges (cluster_level_run: count pass, scan, write
+// pass of k_cl_level into a fresh cluster state) and their entry points (lzani_cluster_store_begin,
+// lzani_cluster_store_add_kept, lzani_debug_cluster_store_add, lzani_cluster_level, lzani_debug_cluster_edges,
+// lzani_get_cluster_store_info, lzani_get_cluster_level_info and the pure lzani_cluster_cut_lines).  A further algorithm is one more unit and one more case in lzani_cluster_run.
 // Included by lzani_hip.hip only, behind lzani_kept.h; of that file it uses lzani_ctx (which holds the Cluster and the Kept),
 // fail, HIPCHK and sort_keys, of lzani_prefilter.h pf_blocks and pf_chunks, of lzani_devmem.h DevMem and StreamSpan.  The
 // kernels are lzani_kernels_cluster.h; the group's form is in lzani_multi.h.
 //
-// What the stage reads and writes.  add_kept, per record: 36 B and two lengths read, 16 B written.  SINGLE: per edge 16 B
+// What the stage reads and writes.  add_kept, per record: 36 B and two lengths read, 16 B written.  A level, per record of
+// the store: 36 B and two lengths read by either pass, and per edge 16 B written; the store's append: 36 B copied.  SINGLE: per edge 16 B
 // and the two paths to the roots, one CAS per hook that is won; per node one path.  A greedy round: per edge 16 B and one or
 // two state words read, at most one word stored; per node two words.  The assignment: per edge 16 B and two state words,
 // one atomic per edge of a node that is no representative (BEST: two passes).  The numbering: per node three words, one
@@ -51,12 +56,15 @@ int cluster_state(lzani_ctx* c, const std::string& fn)
     return LZANI_OK;
 }
 
+// whether one launch of a thread per item covers `items` edges or records: the one statement of that limit
+bool cluster_launch_covers(u64 items) { return (items + PF_THREADS - 1) / PF_THREADS <= 0x7FFFFFFFull; }
+
 // Room for `need` edges: kept if there is, else a buffer of at least twice the size, the edges copied on the device.  A
 // failure leaves the buffer and its edges as they were.
 int cluster_reserve(lzani_ctx* c, u64 need)
 {
     Cluster& k = c->cl;
-    if ((need + PF_THREADS - 1) / PF_THREADS > 0x7FFFFFFFull) return fail(c, LZANI_ERR_ARG, "cluster stage: more edges than one launch covers");
+    if (!cluster_launch_covers(need)) return fail(c, LZANI_ERR_ARG, "cluster stage: more edges than one launch covers");
     if (need <= k.edges.capacity()) return LZANI_OK;
     DevMem<lzani_cluster_edge> bigger;
     const u64 twice = std::max<u64>(need, 2 * (u64)k.edges.capacity());
@@ -136,6 +144,98 @@ const u64* cluster_compact(lzani_ctx* c, u64 items, u32* ucnt, u64* uoff, Pass p
     hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, ucnt, (u64)chunks, uoff);
     pass(std::true_type{}, chunks);
     return uoff + chunks;
+}
+
+// ---- the record store of the cluster levels, and a level's edges ----
+int cluster_store_state(lzani_ctx* c, const std::string& fn)
+{
+    if (!c->cls.begun) return fail(c, LZANI_ERR_STATE, fn + ": no record store (call lzani_cluster_store_begin first)");
+    return LZANI_OK;
+}
+// Room for `need` records: kept if there is, else a buffer of at least twice the size, the records copied on the device.  A
+// failure leaves the buffer and its records as they were.
+int cluster_store_reserve(lzani_ctx* c, u64 need)
+{
+    ClusterStore& s = c->cls;
+    if (9 * need <= s.rec.capacity()) return LZANI_OK;
+    DevMem<u32> bigger;
+    const u64 twice = std::max<u64>(9 * need, 2 * (u64)s.rec.capacity());
+    if (!got(bigger.alloc((size_t)twice))) HIPCHK(c, bigger.alloc((size_t)(9 * need)));
+    if (s.info.records) {
+        HIPCHK(c, hipMemcpyAsync(bigger.get(), s.rec.get(), (size_t)s.info.records * 36, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    s.rec = std::move(bigger);
+    s.info.record_bytes = s.rec.bytes();
+    return LZANI_OK;
+}
+// `count` records from `src` (device or host memory, by `kind`) behind the store's: the growth step, then the copy
+int cluster_store_append(lzani_ctx* c, const u32* src, u64 count, hipMemcpyKind kind)
+{
+    ClusterStore& s = c->cls;
+    if (int rc = cluster_store_reserve(c, s.info.records + count)) return rc;
+    if (!count) return LZANI_OK;
+    StreamSpan span;
+    HIPCHK(c, span.begin(c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.rec.get() + 9 * s.info.records, src, (size_t)count * 36, kind, c->stream));
+    HIPCHK(c, span.end(c->stream));
+    float ms = 0;
+    HIPCHK(c, span.elapsed(ms));
+    s.info.add_ms += ms;
+    s.info.records += count;
+    return LZANI_OK;
+}
+
+// The level's edges of the store's records into the fresh cluster state `k`: count pass, k_pf_scan, the exact total read
+// back, the edge buffer at that size, write pass -- cluster_compact's three launches with the read-back and the allocation
+// between the second and the third, hence launched here one by one.  level_ms runs from the count pass to the write pass,
+// that read-back and allocation included.  Everything it allocates is its own or k's.
+int cluster_level_run(lzani_ctx* c, Cluster& k, int measure, const lzani_cluster_cut& cut)
+{
+    const ClusterStore& s = c->cls;
+    const u32 n = s.info.n;
+    const u64 R = s.info.records, chunks = pf_chunks(R);
+    HIPCHK(c, k.len.alloc(n));
+    HIPCHK(c, hipMemcpyAsync(k.len.get(), s.len.get(), (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+    k.info.n = n; k.info.measure = measure; k.info.algo = -1;
+    k.from_level = true;
+    k.level.records_in = R;
+    DevMem<u32> ucnt;
+    DevMem<u64> uoff;
+    DevMem<unsigned long long> counters;
+    HIPCHK(c, ucnt.alloc((size_t)chunks));
+    HIPCHK(c, uoff.alloc((size_t)chunks + 1));
+    HIPCHK(c, counters.alloc(CL_LV_COUNTERS));
+    u64 total = 0;
+    unsigned long long h_counters[CL_LV_COUNTERS] = {0, 0};
+    StreamSpan span;
+    HIPCHK(c, span.begin(c->stream));
+    if (R) {
+        HIPCHK(c, hipMemsetAsync(counters, 0, CL_LV_COUNTERS * sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_cl_level<false>, dim3((u32)chunks), dim3(PF_THREADS), 0, c->stream, s.rec.get(), R, k.len.get(), cut, measure, ucnt.get(),
+                           (const u64*)uoff.get(), (lzani_cluster_edge*)nullptr, counters.get());
+        hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(1024), 0, c->stream, (const u32*)ucnt.get(), chunks, uoff.get());
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&total, uoff.get() + chunks, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h_counters, counters, sizeof h_counters, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (total > R) return fail(c, LZANI_ERR_DEVICE, "lzani_cluster_level: more edges than records");
+    }
+    HIPCHK(c, k.edges.alloc((size_t)total));                   // the exact size, known before the buffer is made
+    k.info.edge_bytes = k.edges.bytes();
+    if (total) {
+        hipLaunchKernelGGL(k_cl_level<true>, dim3((u32)chunks), dim3(PF_THREADS), 0, c->stream, s.rec.get(), R, k.len.get(), cut, measure, ucnt.get(),
+                           (const u64*)uoff.get(), k.edges.get(), counters.get());
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, span.end(c->stream));
+    float ms = 0;
+    HIPCHK(c, span.elapsed(ms));
+    k.info.edges = total;
+    k.level.edges_out = total; k.level.lines_in = h_counters[CL_LV_LINES_IN]; k.level.lines_out = h_counters[CL_LV_LINES_OUT]; k.level.level_ms = ms;
+    TRACE("cluster level: measure=%d records=%llu edges=%llu lines %llu -> %llu", measure, (unsigned long long)R, (unsigned long long)total,
+          h_counters[CL_LV_LINES_IN], h_counters[CL_LV_LINES_OUT]);
+    return LZANI_OK;
 }
 
 // the slots of a table of `insertions`: the smallest power of two >= 2 * insertions (1 for none)
@@ -764,6 +864,114 @@ int lzani_get_cluster_info(const lzani_ctx* c, lzani_cluster_info* info)
     if (!c || !info) return LZANI_ERR_ARG;
     if (!c->cl.begun) return LZANI_ERR_STATE;
     *info = c->cl.info;
+    return LZANI_OK;
+}
+
+uint32_t lzani_cluster_cut_lines(const lzani_cluster_cut* cut, const lzani_result* x, const lzani_result* y, uint32_t lines, uint32_t len_a, uint32_t len_b)
+{
+    if (!cut || !x || !y || !cluster_cut_ok(*cut)) return 0xFFFFFFFFu;
+    return cluster_cut_lines(*cut, *x, *y, lines, len_a, len_b);
+}
+
+int lzani_cluster_store_begin(lzani_ctx* c, uint32_t n, const uint32_t* report_len)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_cluster_store_begin";
+    if (!c->gs.n) return fail(c, LZANI_ERR_STATE, fn + ": no genomes set");
+    if (!n) return fail(c, LZANI_ERR_ARG, fn + ": no genomes");
+    if (!report_len && n != c->gs.n) return fail(c, LZANI_ERR_ARG, fn + ": the genome set's own lengths are those of its n genomes");
+    std::vector<u32> own;
+    if (!report_len) { own = kept_own_lengths(c); report_len = own.data(); }
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->cls = ClusterStore{};                                   // the last store goes first
+    ClusterStore s;
+    HIPCHK(c, s.len.alloc(n));
+    HIPCHK(c, hipMemcpyAsync(s.len.get(), report_len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s.info.n = n;
+    s.begun = true;
+    c->cls = std::move(s);
+    return LZANI_OK;
+}
+
+int lzani_cluster_store_add_kept(lzani_ctx* c, uint64_t* records_total)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_cluster_store_add_kept";
+    if (int rc = cluster_store_state(c, fn)) return rc;
+    if (!c->kept.done) return fail(c, LZANI_ERR_STATE, fn + ": no kept result (call lzani_run_rows_kept first)");
+    if (c->kept.n != c->cls.info.n)
+        return fail(c, LZANI_ERR_ARG, fn + ": the kept result is one of " + std::to_string(c->kept.n) + " genomes, the record store of " + std::to_string(c->cls.info.n));
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (int rc = cluster_store_append(c, c->kept.rec.get(), c->kept.info.kept_pairs, hipMemcpyDeviceToDevice)) return rc;
+    if (records_total) *records_total = c->cls.info.records;
+    return LZANI_OK;
+}
+
+int lzani_debug_cluster_store_add(lzani_ctx* c, const lzani_kept_pair* rec, uint64_t count)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_debug_cluster_store_add";
+    if (int rc = cluster_store_state(c, fn)) return rc;
+    if (count && !rec) return fail(c, LZANI_ERR_ARG, fn + ": null records");
+    static_assert(sizeof(lzani_kept_pair) == 36, "lzani_kept_pair is nine 32-bit fields");
+    for (uint64_t i = 0; i < count; ++i)
+        if (!(rec[i].a < rec[i].b && rec[i].b < c->cls.info.n && rec[i].lines >= 1 && rec[i].lines <= 3))
+            return fail(c, LZANI_ERR_ARG, fn + ": a record without a < b < n, or with lines outside 1..3");
+    if (!count) return LZANI_OK;
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (int rc = cluster_store_append(c, (const u32*)rec, count, hipMemcpyHostToDevice)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LZANI_OK;
+}
+
+int lzani_cluster_level(lzani_ctx* c, int measure, const lzani_cluster_cut* cut, uint64_t* edges)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_cluster_level";
+    if (int rc = cluster_store_state(c, fn)) return rc;
+    if (!cut) return fail(c, LZANI_ERR_ARG, fn + ": null cut");
+    if (!cluster_cut_ok(*cut)) return fail(c, LZANI_ERR_ARG, fn + ": a minimum of the cut is not a number, or its reserved word is not 0");
+    if (!cluster_measure_known(measure)) return fail(c, LZANI_ERR_ARG, fn + ": unknown measure");
+    if (!cluster_launch_covers(c->cls.info.records)) return fail(c, LZANI_ERR_ARG, fn + ": more records than one launch covers");
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->cl = Cluster{};                                         // the last state goes first
+    Cluster k;
+    const int rc = cluster_level_run(c, k, measure, *cut);
+    if (rc != LZANI_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    k.begun = true;
+    c->cl = std::move(k);
+    if (edges) *edges = c->cl.info.edges;
+    return LZANI_OK;
+}
+
+int lzani_debug_cluster_edges(lzani_ctx* c, uint64_t first, uint64_t count, lzani_cluster_edge* out)
+{
+    if (!c) return LZANI_ERR_ARG;
+    const std::string fn = "lzani_debug_cluster_edges";
+    if (int rc = cluster_state(c, fn)) return rc;
+    const u64 E = c->cl.info.edges;
+    if (first > E || count > E - first) return fail(c, LZANI_ERR_ARG, fn + ": the range lies past the end of the edges");
+    if (!count) return LZANI_OK;
+    if (!out) return fail(c, LZANI_ERR_ARG, fn + ": null output");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipMemcpy(out, c->cl.edges.get() + first, (size_t)count * sizeof(lzani_cluster_edge), hipMemcpyDeviceToHost));
+    return LZANI_OK;
+}
+
+int lzani_get_cluster_store_info(const lzani_ctx* c, lzani_cluster_store_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->cls.begun) return LZANI_ERR_STATE;
+    *info = c->cls.info;
+    return LZANI_OK;
+}
+
+int lzani_get_cluster_level_info(const lzani_ctx* c, lzani_cluster_level_info* info)
+{
+    if (!c || !info) return LZANI_ERR_ARG;
+    if (!c->cl.begun || !c->cl.from_level) return LZANI_ERR_STATE;
+    *info = c->cl.level;
     return LZANI_OK;
 }
 

@@ -1,5 +1,5 @@
 // lzani_cluster_plan.h -- the rule and the sequential statement of the cluster stage (include/lzani.h, "clustering the kept
-// pairs"): the weight of an edge, and the six algorithms on a host edge array -- union-find with the smaller root as
+// pairs"): the weight of an edge, the cut of a cluster level (cluster_cut_lines, over lzani_out_filter.h), and the six algorithms on a host edge array -- union-find with the smaller root as
 // parent, the greedy sweep over adjacency lists, greedy set cover by a lazy max-heap, complete linkage by a map from
 // link to (count, smallest weight) with a lazy max-heap of the links, and Leiden (CPM) by the rounds of its statement over
 // adjacency lists per level.  The device stage (lzani_kernels_cluster.h, lzani_cluster.h) calls the
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/lzani.h"
+#include "lzani_out_filter.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define LZANI_CL_HD __host__ __device__
@@ -60,6 +61,40 @@ LZANI_CL_HD inline double cluster_weight(int measure, const lzani_result& X, con
     v0 = (lines & 1u) ? cluster_value(v0) : 0.0;
     v1 = (lines & 2u) ? cluster_value(v1) : 0.0;
     return v0 > v1 ? v0 : v1;
+}
+
+// ---- the cut of a cluster level (include/lzani.h, "cluster levels") ---------------------------------------------------
+// a cut that every entry point takes: no minimum that is not a number, the reserved word 0
+LZANI_CL_HD inline bool cluster_cut_ok(const lzani_cluster_cut& c)
+{
+    const lzani_out_filter f{c.min_tani, c.min_gani, c.min_ani, c.min_qcov, c.min_rcov};
+    return !out_filter_has_nan(f) && c.min_len_ratio == c.min_len_ratio && c.reserved_ == 0;
+}
+
+// len_ratio of a pair as the emitter prints it (host/emit.h): the shorter length over the longer, 0 where either is 0
+LZANI_CL_HD inline double cluster_len_ratio(uint32_t la, uint32_t lb)
+{
+    if (!la || !lb) return 0.0;
+    return la < lb ? (double)la / (double)lb : (double)lb / (double)la;
+}
+
+// a line's num_alns against the cut's maximum (0: none)
+LZANI_CL_HD inline bool cluster_cut_alns(const lzani_cluster_cut& c, const lzani_result& own)
+{
+    return c.max_num_alns == 0 || (int64_t)own.no_components <= (int64_t)c.max_num_alns;
+}
+
+// The lines of the kept record (a < b, X, Y, lines) that stay under the cut: the five minima as the output filter applies
+// them to each line, len_ratio for both, num_alns for each; never a line that `lines` does not name.  The record is an edge
+// of the level iff the result is not 0, with the weight cluster_weight(measure, X, Y, result, la, lb).
+LZANI_CL_HD inline uint32_t cluster_cut_lines(const lzani_cluster_cut& c, const lzani_result& X, const lzani_result& Y, uint32_t lines, uint32_t la, uint32_t lb)
+{
+    const lzani_out_filter f{c.min_tani, c.min_gani, c.min_ani, c.min_qcov, c.min_rcov};
+    const double tani = out_pair_tani(X, Y, la, lb);
+    const bool both = !(cluster_len_ratio(la, lb) < c.min_len_ratio);
+    const bool pass0 = both && cluster_cut_alns(c, X) && out_filter_line(f, out_line_ratios(tani, X, Y, lb, la));
+    const bool pass1 = both && cluster_cut_alns(c, Y) && out_filter_line(f, out_line_ratios(tani, Y, X, la, lb));
+    return lines & ((pass0 ? 1u : 0u) | (pass1 ? 2u : 0u));
 }
 
 // w >= 0 (or +inf): weights order like these

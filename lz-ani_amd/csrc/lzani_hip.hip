@@ -270,6 +270,16 @@ struct Cluster {
     DevMem<u32> len;                     // the reported lengths (n)
     DevMem<lzani_cluster_edge> edges;     // info.edges of them, a < b; grown geometrically
     DevMem<u32> rep_of, cluster_of;       // of the last run (n each)
+    bool from_level = false;              // made by lzani_cluster_level: `level` holds
+    lzani_cluster_level_info level{};
+};
+
+// The record store of the cluster levels (lzani_cluster.h): lzani_cluster_store_begin -> the next one, or lzani_set_genomes.
+struct ClusterStore {
+    bool begun = false;
+    lzani_cluster_store_info info{};
+    DevMem<u32> len;                      // the reported lengths (n)
+    DevMem<u32> rec;                      // 9 words a record (lzani_kept_pair), info.records of them; grown geometrically
 };
 
 // Residency counters of the last run (lzani_get_residency).
@@ -306,6 +316,7 @@ struct lzani_ctx {
     Prefilter pf;
     Kept kept;
     Cluster cl;
+    ClusterStore cls;
     // the last run
     RunRecord run;
     Residency res;
@@ -928,6 +939,7 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     c->pf = Prefilter{};
     c->kept = Kept{};
     c->cl = Cluster{};
+    c->cls = ClusterStore{};
     c->res = Residency{};
     c->gs.L.resize(n);
     c->gs.nmoff.resize(n);

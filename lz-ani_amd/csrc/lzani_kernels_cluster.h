@@ -3,6 +3,9 @@
 // lzani_kernels_prefilter.h it uses PF_THREADS (256-thread blocks), the scan k_pf_scan and the compaction pf_compact, of
 // lzani_prefilter_defs.h pf_splitmix64, of lzani_block.h block_sum.
 //   k_cl_add_kept    one thread per kept record: the weight, one 16-byte edge by one 16-byte vector store
+//   k_cl_level       <false>, k_pf_scan, <true>: the edges of a cluster level -- the records of the store of which a line stays
+//                    under the cut (cluster_cut_lines), in record order, by pf_compact; the count pass sums the lines in
+//                    and out as well
 //   k_cl_init        per node: parent = v, state = UNDECIDED, blocked = 0, best = 0, size = 0
 //   k_cl_hook        SINGLE, one thread per edge: the two roots by following parent, the larger hooked under the smaller
 //                    with atomicCAS(&parent[hi], hi, lo); on a lost CAS, look again.  parent[v] <= v at every moment: no
@@ -50,6 +53,56 @@ __global__ void __launch_bounds__(PF_THREADS) k_cl_add_kept(const u32* __restric
     const double w = cluster_weight(measure, X, Y, r[8], len[a], len[b]);
     const u64 bits = (u64)__double_as_longlong(w);
     reinterpret_cast<uint4*>(edges)[base + i] = make_uint4(a, b, (u32)bits, (u32)(bits >> 32));
+}
+
+// A cluster level's edges, by pf_compact: a block of 256 threads takes 4,096 records, 16 a thread.  Per record 36 B and two lengths read (by either pass), per edge 16 B written by one vector store.
+// The count pass counts the block's edges (blkcnt) and adds the set bits of `lines` and of cut_lines to counters[CL_LV_LINES_IN]
+// and [CL_LV_LINES_OUT]: a block sum each and one atomic add per block.  No block waits for another.
+enum { CL_LV_LINES_IN = 0, CL_LV_LINES_OUT = 1, CL_LV_COUNTERS = 2 };
+template <bool WRITE>
+struct ClLevelItem {
+    const u32* __restrict__ rec;
+    const u32* __restrict__ len;
+    lzani_cluster_cut cut;
+    int measure;
+    lzani_cluster_edge* __restrict__ edges;
+    u32* lines_in;                                               // this thread's sums (the count pass)
+    u32* lines_out;
+    uint4* edge;                                                 // this thread's edge between kept and put (the write pass)
+    __device__ __forceinline__ bool kept(u64 i, u64&) const
+    {
+        const u32* __restrict__ r = rec + 9 * i;
+        const u32 a = r[0], b = r[1], lines = r[8];
+        const lzani_result X{(int)r[2], (int)r[3], (int)r[4]}, Y{(int)r[5], (int)r[6], (int)r[7]};
+        const u32 la = len[a], lb = len[b];
+        const u32 stay = cluster_cut_lines(cut, X, Y, lines, la, lb);
+        if (!WRITE) { *lines_in += (u32)__popc(lines); *lines_out += (u32)__popc(stay); }
+        else if (stay) {
+            const u64 bits = (u64)__double_as_longlong(cluster_weight(measure, X, Y, stay, la, lb));
+            *edge = make_uint4(a, b, (u32)bits, (u32)(bits >> 32));
+        }
+        return stay != 0;
+    }
+    __device__ __forceinline__ void put(u64 at, u64) const { reinterpret_cast<uint4*>(edges)[at] = *edge; }
+};
+template <bool WRITE>
+__global__ void __launch_bounds__(PF_THREADS) k_cl_level(const u32* __restrict__ rec, u64 count, const u32* __restrict__ len, lzani_cluster_cut cut, int measure,
+                                                         u32* __restrict__ blkcnt, const u64* __restrict__ blkoff, lzani_cluster_edge* __restrict__ edges,
+                                                         unsigned long long* __restrict__ counters)
+{
+    __shared__ u32 s_in, s_out;
+    if (!WRITE && threadIdx.x == 0) { s_in = 0; s_out = 0; }     // (the count pass of pf_compact begins with a barrier)
+    u32 lines_in = 0, lines_out = 0;
+    uint4 edge = make_uint4(0, 0, 0, 0);
+    pf_compact<WRITE>(count, blkcnt, blkoff, ClLevelItem<WRITE>{rec, len, cut, measure, edges, &lines_in, &lines_out, &edge});
+    if (!WRITE) {
+        block_sum(lines_in, &s_in);
+        block_sum(lines_out, &s_out);
+        if (threadIdx.x == 0) {
+            if (s_in) atomicAdd(&counters[CL_LV_LINES_IN], (unsigned long long)s_in);
+            if (s_out) atomicAdd(&counters[CL_LV_LINES_OUT], (unsigned long long)s_out);
+        }
+    }
 }
 
 __global__ void __launch_bounds__(PF_THREADS) k_cl_init(u32 n, u32* __restrict__ parent, u32* __restrict__ state, u32* __restrict__ blocked,

@@ -19,7 +19,8 @@
 //                                            lzani_group_run_rows_kept: the same stages up to the scatter kernel, then the output
 //                                            filter's stage (lzani_kept.h) on the CSR-ordered buffer, on the first device's context
 //                                            and stream; the copy out of the full results is left out
-//                                            lzani_group_cluster_*: the cluster stage (lzani_cluster.h) on that context
+//                                            lzani_group_cluster_*: the cluster stage (lzani_cluster.h) on that context, its
+//                                            record store and levels included
 #pragma once
 #include <rccl/rccl.h>
 
@@ -567,6 +568,40 @@ int lzani_group_get_cluster_leiden_info(const lzani_group* g, lzani_cluster_leid
 {
     if (!g) return LZANI_ERR_ARG;
     return lzani_get_cluster_leiden_info(g->ctx[0], info);
+}
+
+// The cluster levels for the group: the record store and the levels on the first device's context.
+int lzani_group_cluster_store_begin(lzani_group* g, uint32_t n, const uint32_t* report_len)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_cluster_store_begin(g->ctx[0], n, report_len);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_cluster_store_add_kept(lzani_group* g, uint64_t* records_total)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_cluster_store_add_kept(g->ctx[0], records_total);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_cluster_level(lzani_group* g, int measure, const lzani_cluster_cut* cut, uint64_t* edges)
+{
+    if (!g) return LZANI_ERR_ARG;
+    const int rc = lzani_cluster_level(g->ctx[0], measure, cut, edges);
+    return rc == LZANI_OK ? rc : gfail(g, rc, lzani_last_error(g->ctx[0]));
+}
+
+int lzani_group_get_cluster_store_info(const lzani_group* g, lzani_cluster_store_info* info)
+{
+    if (!g) return LZANI_ERR_ARG;
+    return lzani_get_cluster_store_info(g->ctx[0], info);
+}
+
+int lzani_group_get_cluster_level_info(const lzani_group* g, lzani_cluster_level_info* info)
+{
+    if (!g) return LZANI_ERR_ARG;
+    return lzani_get_cluster_level_info(g->ctx[0], info);
 }
 
 int lzani_group_set_genome_memory(lzani_group* g, uint64_t bytes)

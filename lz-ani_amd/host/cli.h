@@ -47,6 +47,14 @@ struct Params {
     string leiden_resolution_arg, leiden_iterations_arg;    // --cluster-leiden-resolution, --cluster-leiden-iterations as given
     double leiden_resolution = 0.7;                         // ... and read: Clusty's defaults
     int leiden_iterations = 2;
+    // cluster levels: --cluster-cut <par> <value> as given, and --cluster-level <algorithm> <file_name> <cuts> as given
+    vector<pair<string, string>> cluster_cut_args;
+    struct LevelArg { string algo, out, cuts; };
+    vector<LevelArg> cluster_level_args;
+    // ... and read: the level of --cluster (its cut on top of --out-filter) first, then those of --cluster-level, in their order
+    struct Level { int algo; string out; lzani_cluster_cut cut; };
+    vector<Level> levels;
+    bool levels_on() const { return !cluster_cut_args.empty() || !cluster_level_args.empty(); }   // either flag was given
 };
 
 static Params P;
@@ -88,6 +96,27 @@ static bool parse_size(const string& v, uint64_t& out)
     if (shift && x > (UINT64_MAX >> shift)) return false;
     out = x << shift;
     return true;
+}
+
+// One limit of a cut: par is one of tani, gani, ani, qcov, rcov, len_ratio (a minimum, on the scale of --out-filter's values
+// as out_filter_minima() hands them on) or num_alns (a maximum, an integer >= 1).  Empty on success, else what is wrong.
+static string parse_cut_limit(const string& par, const string& val, lzani_cluster_cut& cut)
+{
+    const map<string, double*> minima = {{"tani", &cut.min_tani}, {"gani", &cut.min_gani}, {"ani", &cut.min_ani}, {"qcov", &cut.min_qcov},
+                                         {"rcov", &cut.min_rcov}, {"len_ratio", &cut.min_len_ratio}};
+    char* end = nullptr;
+    if (par == "num_alns") {
+        const unsigned long long v = strtoull(val.c_str(), &end, 10);
+        if (val.empty() || !isdigit((unsigned char)val[0]) || *end || v < 1 || v > UINT32_MAX) return "num_alns takes an integer >= 1, not '" + val + "'";
+        cut.max_num_alns = (uint32_t)v;
+        return "";
+    }
+    const auto m = minima.find(par);
+    if (m == minima.end()) return "unknown parameter '" + par + "' (tani, gani, ani, qcov, rcov, len_ratio or num_alns)";
+    const double v = strtod(val.c_str(), &end);
+    if (val.empty() || end == val.c_str() || *end || v != v) return par + " takes a number, not '" + val + "'";
+    *m->second = v;
+    return "";
 }
 
 static void usage()
@@ -137,6 +166,12 @@ static void usage()
          << "      --cluster-representatives  - write the representative's id instead of the cluster number\n"
          << "      --cluster-leiden-resolution <float> - leiden-cpm: the resolution, 0 .. 1 (default: 0.7); larger values give smaller clusters\n"
          << "      --cluster-leiden-iterations <int>   - leiden-cpm: the iterations, 1 .. 16 (default: 2)\n"
+         << "      --cluster-cut <par> <float> - with --cluster: cluster only the pairs with <par> (can be: tani, gani, ani, qcov, rcov, len_ratio) at least\n"
+         << "                                   <float>, or with num_alns at most <int>, among those that --out-filter keeps; the output\n"
+         << "                                   files keep every pair of --out-filter; can be used multiple times\n"
+         << "      --cluster-level <algorithm> <file_name> <cuts> - with --cluster: one more clustering of the same run, into <file_name>;\n"
+         << "                                   <cuts> is none or a comma-separated list par=value as for --cluster-cut, e.g. ani=0.95,qcov=0.85;\n"
+         << "                                   up to 16 times; the levels share --cluster-measure, --cluster-representatives and the leiden options\n"
          << "Options - LZ-parsing-related:\n"
          << "  -a, --mal <int>                - min. anchor length (default: 11)\n"
          << "  -s, --msl <int>                - min. seed length (default: 7)\n"
@@ -245,6 +280,8 @@ static bool parse_params(int argc, char** argv)
         else if (par == "--cluster-out" && has(1)) { P.cluster_out = argv[i + 1]; i += 2; }
         else if (par == "--cluster-measure" && has(1)) { P.cluster_measure_arg = argv[i + 1]; i += 2; }
         else if (par == "--cluster-representatives") { P.cluster_reps = true; i += 1; }
+        else if (par == "--cluster-cut" && has(2)) { P.cluster_cut_args.emplace_back(argv[i + 1], argv[i + 2]); i += 3; }
+        else if (par == "--cluster-level" && has(3)) { P.cluster_level_args.push_back(Params::LevelArg{argv[i + 1], argv[i + 2], argv[i + 3]}); i += 4; }
         else if (par == "--cluster-leiden-resolution" && has(1)) { P.leiden_resolution_arg = argv[i + 1]; i += 2; }
         else if (par == "--cluster-leiden-iterations" && has(1)) { P.leiden_iterations_arg = argv[i + 1]; i += 2; }
         else { cerr << "Unknown parameter: " << argv[i] << endl; usage(); exit(1); }
@@ -287,7 +324,10 @@ static bool parse_params(int argc, char** argv)
         cerr << "--cluster-out, --cluster-measure and --cluster-representatives belong to --cluster" << endl;
         exit(1);
     }
-    if ((!P.leiden_resolution_arg.empty() || !P.leiden_iterations_arg.empty()) && P.cluster_arg != "leiden-cpm") {
+    if (!P.cluster && P.levels_on()) { cerr << "--cluster-cut and --cluster-level belong to --cluster" << endl; exit(1); }
+    bool leiden_level = P.cluster_arg == "leiden-cpm";       // a level that takes the Leiden parameters
+    for (const auto& l : P.cluster_level_args) leiden_level = leiden_level || l.algo == "leiden-cpm";
+    if ((!P.leiden_resolution_arg.empty() || !P.leiden_iterations_arg.empty()) && !leiden_level) {
         cerr << "--cluster-leiden-resolution and --cluster-leiden-iterations belong to --cluster leiden-cpm" << endl;
         exit(1);
     }
@@ -322,6 +362,28 @@ static bool parse_params(int argc, char** argv)
         if (P.query2ref) { cerr << "--cluster belongs to the mode all2all (query2ref compares two sets)" << endl; exit(1); }
         if (P.single_txt) { cerr << "--cluster cannot be used with --out-type single-txt (it takes no output filter)" << endl; exit(1); }
         if (!P.flt_mask) { cerr << "--cluster needs an --out-filter: the pairs it keeps are the edges of the graph" << endl; exit(1); }
+        // the levels: that of --cluster with the cut of --cluster-cut, then those of --cluster-level
+        P.levels.assign(1, Params::Level{P.cluster_algo, P.cluster_out, lzani_cluster_cut{}});
+        for (const auto& c : P.cluster_cut_args) {
+            const string why = parse_cut_limit(c.first, c.second, P.levels[0].cut);
+            if (!why.empty()) { cerr << "Invalid value for --cluster-cut: " << why << endl; exit(1); }
+        }
+        if (P.cluster_level_args.size() > 16) { cerr << "--cluster-level can be used at most 16 times" << endl; exit(1); }
+        for (const auto& l : P.cluster_level_args) {
+            const auto la = algos.find(l.algo);
+            if (la == algos.end()) { cerr << "Unknown value for --cluster-level: " << l.algo << " (single, greedy-first, greedy-best, set-cover, complete-linkage or leiden-cpm)" << endl; exit(1); }
+            Params::Level lv{la->second, l.out, lzani_cluster_cut{}};
+            if (l.cuts != "none")
+                for (const auto& item : split(l.cuts, ',')) {
+                    const size_t eq = item.find('=');
+                    const string why = eq == string::npos ? "'" + item + "' is not of the form par=value" : parse_cut_limit(item.substr(0, eq), item.substr(eq + 1), lv.cut);
+                    if (!why.empty()) { cerr << "Invalid value for --cluster-level: " << why << " (none, or a list par=value)" << endl; exit(1); }
+                }
+            if (l.cuts.empty()) { cerr << "Invalid value for --cluster-level: empty cuts (none, or a list par=value)" << endl; exit(1); }
+            for (const auto& other : P.levels)
+                if (other.out == lv.out) { cerr << "--cluster-level: two levels write the same file: " << lv.out << endl; exit(1); }
+            P.levels.push_back(lv);
+        }
     }
     if (P.inputs.empty()) { cerr << "Input file names not provided\n"; return false; }
     // The engine's parameter envelope (lz-ani_amd/csrc/lzani_layout.h: params_supported).  The reference accepts any

@@ -17,7 +17,8 @@
 // keeps the filter, or the clustering, on the host.  Cover and link (what -V 2 says of a set-cover or a
 // complete-linkage run): read where they are there.  Leiden (its parameters and what -V 2 says of a run): a library without
 // them leaves --cluster leiden-cpm to the host.  Limit (--flt-kmers-max-seqs): asked for only where the flag is given, and
-// a library without them is then refused with the name of the symbol it lacks.
+// a library without them is then refused with the name of the symbol it lacks.  Levels (--cluster-cut, --cluster-level:
+// the record store and the levels of the cluster stage): the same, asked for only where either flag is given.
 #define LZANI_ENGINE_REQUIRED(X) \
     X(create) X(destroy) X(last_error) X(set_genomes) X(get_timing) X(run_rows_regions) X(row_costs) X(partition_rows) \
     X(group_create) X(group_destroy) X(group_last_error) X(group_set_genomes) X(group_run_rows) X(group_get_timing) \
@@ -29,11 +30,13 @@
 #define LZANI_ENGINE_COVER(X) X(group_get_cluster_cover_info) X(group_get_cluster_link_info)
 #define LZANI_ENGINE_LEIDEN(X) X(group_set_cluster_leiden) X(group_get_cluster_leiden_info)
 #define LZANI_ENGINE_LIMIT(X) X(prefilter_limit) X(get_prefilter_limit_info)
+#define LZANI_ENGINE_LEVELS(X) \
+    X(group_cluster_store_begin) X(group_cluster_store_add_kept) X(group_cluster_level) X(group_get_cluster_store_info) X(group_get_cluster_level_info)
 
 struct Engine {
     void* so = nullptr;
 #define X(f) decltype(&lzani_##f) f = nullptr;             // a signature that drifts from the header does not compile
-    LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X)
+    LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X) LZANI_ENGINE_LEVELS(X)
 #undef X
 #define X(f) && f
     bool has_kept() const { return true LZANI_ENGINE_KEPT(X); }
@@ -48,6 +51,14 @@ struct Engine {
 #undef X
         return nullptr;
     }
+    // ... and of the levels group
+    const char* missing_levels() const
+    {
+#define X(f) if (!f) return "lzani_" #f;
+        LZANI_ENGINE_LEVELS(X)
+#undef X
+        return nullptr;
+    }
     bool load()
     {
         std::vector<std::string> cand;
@@ -59,7 +70,7 @@ struct Engine {
         for (auto& c : cand) if ((so = dlopen(c.c_str(), RTLD_NOW | RTLD_LOCAL))) break;
         if (!so) { std::cerr << "Cannot load liblzani_hip.so (the HIP engine; there is no CPU fallback): " << dlerror() << std::endl; return false; }
 #define X(f) f = reinterpret_cast<decltype(f)>(dlsym(so, "lzani_" #f));
-        LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X)
+        LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X) LZANI_ENGINE_LEVELS(X)
 #undef X
 #define X(f) if (!f) { std::cerr << "Missing symbol lzani_" #f << std::endl; return false; }
         LZANI_ENGINE_REQUIRED(X)

@@ -16,6 +16,10 @@
 // --cluster <single|greedy-first|greedy-best|set-cover|complete-linkage|leiden-cpm> clusters the pairs the output filter keeps (include/lzani.h,
 // "clustering the kept pairs") and writes one line per genome to --cluster-out: on the device where the filter is applied there
 // (lzani_group_cluster_*), else by the sequential statement of lzani_cluster_plan.h over the emitter's own lines.
+// --cluster-cut <par> <value> cuts the pairs of the --cluster level further at cluster time, and --cluster-level <algorithm>
+// <file_name> <cuts> adds a clustering of the same run with a cut and a file of its own (include/lzani.h, "cluster levels"):
+// on the device the kept records go into a record store and every level is made from it; the TSV and the ids file never
+// depend on either flag.
 // This file keeps the raw seams, the stage sequence and main; cli.h holds the command line, engine.h the binding of the
 // engine, match.h the stages that call it, emit.h the result files and ingest.h the inputs.
 #include "match.h"
@@ -138,7 +142,11 @@ static bool run_all2all()
     else {
         if (!engine_loaded && !E.load()) return false;
         // --out-filter on the device where it applies to the TSV, the library has the stage and the filter's lists are sets
-        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt) && (!P.cluster || (P.cluster_algo == LZANI_CLUSTER_LEIDEN ? E.has_leiden() : E.has_cluster()));
+        bool leiden = false;                                // a level is one of leiden-cpm
+        for (const auto& lv : P.levels) leiden = leiden || lv.algo == LZANI_CLUSTER_LEIDEN;
+        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt) && (!P.cluster || (leiden ? E.has_leiden() : E.has_cluster()));
+        if (kept && P.cluster && P.levels_on())
+            if (const char* sym = E.missing_levels()) { cerr << "Missing symbol " << sym << " (--cluster-cut and --cluster-level need it)" << endl; return false; }
         clustered = kept && P.cluster;
         if (tiled) {
             if (P.verbosity >= 1) cerr << "Storing results (row blocks, while the matching goes on)" << endl;
@@ -153,7 +161,10 @@ static bool run_all2all()
     stamp(stored ? "LZ matching + storing results" : "LZ matching");
     if (!P.results_out.empty() && !write_raw(P.results_out, results)) return false;
 
-    if (P.cluster && !clustered && !cluster_on_host(g, results, ep)) return false;
+    if (P.cluster && !clustered) {
+        if (!P.levels_on()) { if (!cluster_on_host(g, results, ep)) return false; }
+        else for (const auto& lv : P.levels) if (!cluster_on_host(g, results, ep, &lv)) return false;
+    }
 
     if (!stored) {
         if (P.verbosity >= 1) cerr << "Storing results" << endl;

@@ -228,10 +228,11 @@ static bool store_alignment(const vector<Genome>& g, vector<AlnRegion>& regs)
 }
 
 // --cluster-out: one line per genome in the order of the ids file, its id and its cluster number or its representative's id.
-static bool write_clusters(const vector<Genome>& g, const vector<uint32_t>& rep_of, const vector<uint32_t>& cluster_of)
+// A level of --cluster-level writes the same lines into its own file.
+static bool write_clusters(const vector<Genome>& g, const vector<uint32_t>& rep_of, const vector<uint32_t>& cluster_of, const string& fn = P.cluster_out)
 {
-    ofstream o(P.cluster_out, ios::binary);
-    if (!o.is_open()) { cerr << "Cannot open output file: " << P.cluster_out << endl; return false; }
+    ofstream o(fn, ios::binary);
+    if (!o.is_open()) { cerr << "Cannot open output file: " << fn << endl; return false; }
     o << "object\t" << (P.cluster_reps ? "representative" : "cluster") << "\n";
     for (size_t i = 0; i < g.size(); ++i) {
         o << g[i].name << '\t';
@@ -243,7 +244,9 @@ static bool write_clusters(const vector<Genome>& g, const vector<uint32_t>& rep_
 }
 
 // The device path of --cluster: an empty edge set before the kept calls, the edges of each kept call added behind it
-// (run_block), and at the end the run, the fetch and the file.
+// (run_block), and at the end the run, the fetch and the file.  With --cluster-cut or --cluster-level (P.levels_on()): an
+// empty record store before the kept calls, the records of each kept call added behind it, and at the end, for every level in
+// order, the level's edges from the store under its cut, then the run, the fetch and the level's file.
 static bool clustering_failed(const Group& G)
 {
     cerr << "Clustering failed: " << G.E.group_last_error(G) << endl;
@@ -251,13 +254,15 @@ static bool clustering_failed(const Group& G)
 }
 static bool cluster_begin(const Group& G, const vector<uint32_t>& rlen)
 {
+    if (P.levels_on()) return G.E.group_cluster_store_begin(G, (uint32_t)rlen.size(), rlen.data()) == LZANI_OK || clustering_failed(G);
     return G.E.group_cluster_begin(G, (uint32_t)rlen.size(), rlen.data(), P.cluster_measure) == LZANI_OK || clustering_failed(G);
 }
-static bool cluster_finish(const Group& G, const vector<Genome>& g)
+// the run of `algo` on the edges there are, the fetch, what -V 2 says of the run, and the file
+static bool cluster_run_to_file(const Group& G, const vector<Genome>& g, int algo, const string& fn)
 {
     vector<uint32_t> rep_of(g.size()), cluster_of(g.size());
-    if (P.cluster_algo == LZANI_CLUSTER_LEIDEN && G.E.group_set_cluster_leiden(G, P.leiden_resolution, P.leiden_iterations) != LZANI_OK) return clustering_failed(G);
-    if (G.E.group_cluster_run(G, P.cluster_algo, nullptr) != LZANI_OK || G.E.group_cluster_fetch(G, rep_of.data(), cluster_of.data()) != LZANI_OK)
+    if (algo == LZANI_CLUSTER_LEIDEN && G.E.group_set_cluster_leiden(G, P.leiden_resolution, P.leiden_iterations) != LZANI_OK) return clustering_failed(G);
+    if (G.E.group_cluster_run(G, algo, nullptr) != LZANI_OK || G.E.group_cluster_fetch(G, rep_of.data(), cluster_of.data()) != LZANI_OK)
         return clustering_failed(G);
     lzani_cluster_info ci;
     if (P.verbosity >= 2 && G.E.group_get_cluster_info(G, &ci) == LZANI_OK)
@@ -276,24 +281,45 @@ static bool cluster_finish(const Group& G, const vector<Genome>& g)
         cerr << "Leiden: " << ld.distinct_edges << " distinct pairs (" << ld.duplicate_edges << " given again), " << ld.iterations << " iterations, " << ld.levels
              << " levels, " << ld.move_rounds << " moving and " << ld.refine_rounds << " refinement rounds, " << ld.moves << " moves, " << ld.merges
              << " merges, quality " << ld.quality << " / 2^20 (distinct " << ld.dedup_ms << " ms, rounds " << ld.rounds_ms << " ms)\n";
-    return write_clusters(g, rep_of, cluster_of);
+    return write_clusters(g, rep_of, cluster_of, fn);
+}
+static bool cluster_finish(const Group& G, const vector<Genome>& g)
+{
+    if (!P.levels_on()) return cluster_run_to_file(G, g, P.cluster_algo, P.cluster_out);
+    lzani_cluster_store_info si;
+    if (P.verbosity >= 2 && G.E.group_get_cluster_store_info(G, &si) == LZANI_OK)
+        cerr << "cluster record store on the device: " << si.records << " records of " << si.n << " sequences, " << si.record_bytes << " bytes, add " << si.add_ms << " ms\n";
+    for (size_t k = 0; k < P.levels.size(); ++k) {
+        const Params::Level& lv = P.levels[k];
+        if (G.E.group_cluster_level(G, P.cluster_measure, &lv.cut, nullptr) != LZANI_OK) return clustering_failed(G);
+        lzani_cluster_level_info li;
+        if (P.verbosity >= 2 && G.E.group_get_cluster_level_info(G, &li) == LZANI_OK)
+            cerr << "cluster level " << k << " on the device (" << lv.out << "): " << li.records_in << " records in, " << li.edges_out << " edges out, lines "
+                 << li.lines_in << " -> " << li.lines_out << ", level " << li.level_ms << " ms\n";
+        if (!cluster_run_to_file(G, g, lv.algo, lv.out)) return false;
+    }
+    return true;
 }
 
 // The host path of --cluster: the records of the table's pairs of which the filter keeps a line, by the sequential statement.
-static bool cluster_on_host(const vector<Genome>& g, const PairTable& T, const EmitParams& ep)
+// level (--cluster-cut, --cluster-level): of those records the lines that stay under the level's cut (cluster_cut_lines), into
+// the level's file; null: the clustering of --cluster alone.
+static bool cluster_on_host(const vector<Genome>& g, const PairTable& T, const EmitParams& ep, const Params::Level* level = nullptr)
 {
     const vector<uint32_t> len = report_lengths(g, ep.mrd);
+    const int algo = level ? level->algo : P.cluster_algo;
     vector<lzani_cluster_edge> edges;
     for (uint32_t a = 0; a < T.n; ++a)
         for_pairs_led_by(T, a, [&](uint32_t b, const lzani_result& X, const lzani_result& Y) {
             const lzani_kept_pair k = make_record(len, ep, a, b, X, Y);
-            if (k.lines) edges.push_back(lzani_cluster_edge{a, b, lzani::cluster_weight(P.cluster_measure, k.x, k.y, k.lines, len[a], len[b])});
+            const uint32_t lines = level ? lzani::cluster_cut_lines(level->cut, k.x, k.y, k.lines, len[a], len[b]) : k.lines;
+            if (lines) edges.push_back(lzani_cluster_edge{a, b, lzani::cluster_weight(P.cluster_measure, k.x, k.y, lines, len[a], len[b])});
         });
     vector<uint32_t> rep_of(g.size()), cluster_of(g.size());
     uint32_t k = 0;
     auto run = [&]() {
-        if (P.cluster_algo != LZANI_CLUSTER_LEIDEN)
-            return lzani::cluster_host((uint32_t)g.size(), edges.data(), edges.size(), P.cluster_algo, rep_of.data(), cluster_of.data(), &k);
+        if (algo != LZANI_CLUSTER_LEIDEN)
+            return lzani::cluster_host((uint32_t)g.size(), edges.data(), edges.size(), algo, rep_of.data(), cluster_of.data(), &k);
         // Leiden with the resolution and the iterations asked for (cluster_host runs the defaults)
         if (int rc = lzani::cluster_leiden_host((uint32_t)g.size(), edges.data(), edges.size(), P.leiden_resolution, P.leiden_iterations, rep_of.data(), nullptr)) return rc;
         k = lzani::cluster_number((uint32_t)g.size(), rep_of.data(), cluster_of.data());
@@ -304,7 +330,7 @@ static bool cluster_on_host(const vector<Genome>& g, const PairTable& T, const E
         return false;
     }
     if (P.verbosity >= 2) cerr << "clusters on the host: " << k << " of " << g.size() << " sequences from " << edges.size() << " pairs\n";
-    return write_clusters(g, rep_of, cluster_of);
+    return write_clusters(g, rep_of, cluster_of, level ? level->out : P.cluster_out);
 }
 
 // A block of rows as the engine takes it: CSR over ids, q null for dense rows (every id but the row's own).
@@ -312,7 +338,7 @@ struct RowBlock { uint32_t n_rows; const uint32_t* rows; const uint64_t* off; co
 
 // One group call for a block of rows: into `out` (lzani_group_run_rows), or, where out is null, the kept form with the
 // output filter and the printed lengths rlen (lzani_group_run_rows_kept), n_kept records of which stay in the group, and
-// behind it the block's cluster edges (--cluster).  whole: the call is the run's only one, and -V 2 says what it took.
+// behind it the block's cluster edges (--cluster), or with levels its records into the store.  whole: the call is the run's only one, and -V 2 says what it took.
 static bool run_block(const Group& G, const RowBlock& b, lzani_result* out, const vector<uint32_t>& rlen, uint64_t& n_kept, bool whole)
 {
     const lzani_out_filter f = out_filter_minima();
@@ -322,7 +348,8 @@ static bool run_block(const Group& G, const RowBlock& b, lzani_result* out, cons
                        : G.E.group_run_rows_kept(G, b.n_rows, b.rows, b.off, b.q, &f, rlen.data(), &n_kept);
     if (whole && P.verbosity >= 2) print_engine_line(G, chrono::duration<double>(chrono::steady_clock::now() - t_c).count());
     if (rc != LZANI_OK) return matching_failed(G.E.group_last_error(G));
-    if (!out && P.cluster && G.E.group_cluster_add_kept(G, nullptr) != LZANI_OK) return clustering_failed(G);   // before the next kept call replaces the records
+    // before the next kept call replaces the records: their edges, or (levels) the records themselves into the store
+    if (!out && P.cluster && (P.levels_on() ? G.E.group_cluster_store_add_kept(G, nullptr) : G.E.group_cluster_add_kept(G, nullptr)) != LZANI_OK) return clustering_failed(G);
     return true;
 }
 

@@ -49,7 +49,11 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_group_get_cluster_info", "lzani_get_cluster_cover_info", "lzani_group_get_cluster_cover_info",
            "lzani_get_cluster_link_info", "lzani_group_get_cluster_link_info", "lzani_cluster_leiden_host",
            "lzani_debug_cluster_leiden_host_cap", "lzani_set_cluster_leiden", "lzani_group_set_cluster_leiden",
-           "lzani_get_cluster_leiden_info", "lzani_group_get_cluster_leiden_info", "lzani_debug_alloc_fault")
+           "lzani_get_cluster_leiden_info", "lzani_group_get_cluster_leiden_info", "lzani_debug_alloc_fault",
+           "lzani_cluster_cut_lines", "lzani_cluster_store_begin", "lzani_cluster_store_add_kept", "lzani_cluster_level",
+           "lzani_get_cluster_store_info", "lzani_get_cluster_level_info", "lzani_debug_cluster_store_add", "lzani_debug_cluster_edges",
+           "lzani_group_cluster_store_begin", "lzani_group_cluster_store_add_kept", "lzani_group_cluster_level",
+           "lzani_group_get_cluster_store_info", "lzani_group_get_cluster_level_info")
 
 
 class LzaniError(RuntimeError):
@@ -198,6 +202,42 @@ class ClusterLeidenInfo(C.Structure):
                 ("moves", C.c_uint64), ("merges", C.c_uint64), ("quality", C.c_int64), ("resolution_q", C.c_uint64),
                 ("distinct_edges", C.c_uint64), ("duplicate_edges", C.c_uint64), ("table_slots", C.c_uint64), ("workspace_bytes", C.c_uint64),
                 ("dedup_ms", C.c_double), ("rounds_ms", C.c_double)]
+
+
+class ClusterCut(C.Structure):
+    _fields_ = [("min_tani", C.c_double), ("min_gani", C.c_double), ("min_ani", C.c_double), ("min_qcov", C.c_double),
+                ("min_rcov", C.c_double), ("min_len_ratio", C.c_double), ("max_num_alns", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class ClusterStoreInfo(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("records", C.c_uint64), ("record_bytes", C.c_uint64), ("add_ms", C.c_double)]
+
+
+class ClusterLevelInfo(C.Structure):
+    _fields_ = [("records_in", C.c_uint64), ("edges_out", C.c_uint64), ("lines_in", C.c_uint64), ("lines_out", C.c_uint64),
+                ("level_ms", C.c_double)]
+
+
+assert C.sizeof(ClusterCut) == 56
+CUT_FIELDS = FILTER_FIELDS + ("len_ratio", "num_alns")
+
+
+def cluster_cut(cut=None, reserved=0, **limits):
+    """A ClusterCut from a dict / keywords by column name: minima of tani, gani, ani, qcov, rcov and len_ratio, and num_alns,
+    the maximum of a line's num_alns (0: none); what is not named is 0.  reserved: the reserved word (tests)."""
+    m = dict(cut or {}, **limits)
+    assert set(m) <= set(CUT_FIELDS), m
+    return ClusterCut(*[float(m.get(k, 0.0)) for k in FILTER_FIELDS], float(m.get("len_ratio", 0.0)), int(m.get("num_alns", 0)), int(reserved))
+
+
+def cluster_cut_lines(cut, x, y, lines, len_a, len_b):
+    """lzani_cluster_cut_lines (no GPU needed): the lines of the kept record (x, y, lines) of the pair a < b that stay under
+    the cut; 0xFFFFFFFF where a minimum is NaN or the reserved word is not 0."""
+    lib = load_library()
+    f = cut if isinstance(cut, ClusterCut) else cluster_cut(cut)
+    rx, ry = Result(*[int(v) for v in x]), Result(*[int(v) for v in y])
+    return int(lib.lzani_cluster_cut_lines(C.byref(f), C.byref(rx), C.byref(ry), C.c_uint32(int(lines)), C.c_uint32(int(len_a)),
+                                           C.c_uint32(int(len_b))))
 
 
 # lzani_cluster_edge as a numpy record: a < b (either order is taken), w >= 0
@@ -410,6 +450,16 @@ def load_library():
                                                             C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lzani_debug_cluster_add_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         lib.lzani_debug_alloc_fault.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.lzani_cluster_cut_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.lzani_cluster_cut_lines.restype = C.c_uint32
+        for pre in ("lzani_", "lzani_group_"):
+            getattr(lib, pre + "cluster_store_begin").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+            getattr(lib, pre + "cluster_store_add_kept").argtypes = [C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "cluster_level").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "get_cluster_store_info").argtypes = [C.c_void_p, C.c_void_p]
+            getattr(lib, pre + "get_cluster_level_info").argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_debug_cluster_store_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.lzani_debug_cluster_edges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -688,6 +738,41 @@ class _ClusterCalls:
         self._check(getattr(self.lib, self._pre + "get_cluster_leiden_info")(self.h, C.byref(o)), self._pre + "get_cluster_leiden_info")
         return {k: getattr(o, k) for k, _ in ClusterLeidenInfo._fields_}
 
+    def cluster_store_begin(self, n=None, report_len=None):
+        """An empty record store for n genomes (default: the genome set's) with their reported lengths (default: its own)."""
+        n = int(self.n if n is None else n)
+        rl = None if report_len is None else np.ascontiguousarray(report_len, dtype=np.uint32)
+        assert rl is None or len(rl) == n
+        self._check(getattr(self.lib, self._pre + "cluster_store_begin")(self.h, n, _ptr(rl)), self._pre + "cluster_store_begin")
+        self._store_n = n
+
+    def cluster_store_add_kept(self):
+        """Appends the records of the current kept result to the store; returns the number of records there are now."""
+        tot = C.c_uint64(0)
+        self._check(getattr(self.lib, self._pre + "cluster_store_add_kept")(self.h, C.byref(tot)), self._pre + "cluster_store_add_kept")
+        return int(tot.value)
+
+    def cluster_level(self, measure="tani", cut=None):
+        """A begun cluster state whose edges are the store's records under `cut` (a ClusterCut, or a dict by column name);
+        returns the number of edges."""
+        f = cut if isinstance(cut, ClusterCut) else cluster_cut(cut)
+        e = C.c_uint64(0)
+        self._check(getattr(self.lib, self._pre + "cluster_level")(self.h, _measure(measure), C.byref(f), C.byref(e)), self._pre + "cluster_level")
+        self._cluster_n = getattr(self, "_store_n", 0)
+        return int(e.value)
+
+    def cluster_store_info(self):
+        """n, records, record_bytes, add_ms."""
+        o = ClusterStoreInfo()
+        self._check(getattr(self.lib, self._pre + "get_cluster_store_info")(self.h, C.byref(o)), self._pre + "get_cluster_store_info")
+        return {k: getattr(o, k) for k, _ in ClusterStoreInfo._fields_}
+
+    def cluster_level_info(self):
+        """records_in, edges_out, lines_in, lines_out, level_ms of the level that made the current cluster state."""
+        o = ClusterLevelInfo()
+        self._check(getattr(self.lib, self._pre + "get_cluster_level_info")(self.h, C.byref(o)), self._pre + "get_cluster_level_info")
+        return {k: getattr(o, k) for k, _ in ClusterLevelInfo._fields_}
+
 
 class Group(_ClusterCalls):
     """lzani_group_*: one process, several GPUs (what `lz-ani --gpus n` uses)."""
@@ -778,6 +863,20 @@ class Engine(_ClusterCalls):
         """Test hook: appends made-up EDGE_DTYPE edges from host memory."""
         e = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
         self._check(self.lib.lzani_debug_cluster_add_edges(self.h, _ptr(e) if len(e) else None, C.c_uint64(len(e))), "lzani_debug_cluster_add_edges")
+
+    def debug_cluster_store_add(self, records):
+        """Test hook: appends made-up KEPT_DTYPE records from host memory to the record store."""
+        r = np.ascontiguousarray(records, dtype=KEPT_DTYPE)
+        self._check(self.lib.lzani_debug_cluster_store_add(self.h, _ptr(r) if len(r) else None, C.c_uint64(len(r))), "lzani_debug_cluster_store_add")
+
+    def debug_cluster_edges(self, first=0, count=None):
+        """Test hook: edges first .. first + count - 1 (default: to the end) of the current cluster state, EDGE_DTYPE."""
+        if count is None:
+            count = self.cluster_info()["edges"] - int(first)
+        out = np.zeros(int(count), dtype=EDGE_DTYPE)
+        self._check(self.lib.lzani_debug_cluster_edges(self.h, C.c_uint64(int(first)), C.c_uint64(int(count)), _ptr(out) if count else None),
+                    "lzani_debug_cluster_edges")
+        return out
 
     def __init__(self, params=None, device=0):
         self.lib = load_library()
