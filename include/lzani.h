@@ -94,8 +94,8 @@ const char *lzani_last_error(const lzani_ctx *ctx);
  * codes (A0 C1 G2 T3, anything >= 4 is N; seq_reservoir.h:241-248).  The engine packs them to
  * 2 bit + N mask on the device and keeps them resident; caller buffers may be freed on return.
  * Ids used below are indices into this table (the reference's reordered sequence ids).
- * The call drops the genome set there was and everything made from it -- index slabs, candidate scratch, prefilter, kept
- * and cluster results -- before it allocates.  LZANI_ERR_NOMEM, in-core or out-of-core, therefore leaves the context
+ * The call drops the genome set there was and everything made from it -- index slabs, candidate scratch, prefilter, kept,
+ * regions and cluster results -- before it allocates.  LZANI_ERR_NOMEM, in-core or out-of-core, therefore leaves the context
  * without a genome set: every call that needs one returns LZANI_ERR_STATE until a lzani_set_genomes succeeds, and one
  * with the same arguments may be tried again on the same context. */
 int lzani_set_genomes(lzani_ctx *ctx, uint32_t n, const uint8_t *const *codes, const uint32_t *len);
@@ -525,6 +525,72 @@ int lzani_debug_filter_results(lzani_ctx *ctx, uint32_t n, const uint32_t *repor
                                const lzani_out_filter *f, uint64_t *n_kept);
 /* LZANI_ERR_STATE without a kept result. */
 int lzani_get_kept_info(const lzani_ctx *ctx, lzani_kept_info *info);
+
+/* ---- Alignment regions on the device: filtered, ordered, fetched in pieces --------------------------------------------
+ * The reference's --out-alignment prints the regions of every directed pair (lz_matcher.cpp:102-169), pair by pair, and with
+ * an --out-filter drops the pairs of which gani, ani or qcov over the region sums is below its minimum (115-138).  The pair
+ * kernels leave the regions in a device buffer in no order; this stage sums each pair's regions, applies that rule, puts the
+ * regions that stay into the file's order with the engine's radix sort and hands them back in pieces.  It is a post-stage
+ * over a finished buffer, like the output filter: the pair kernels and their dispatch know nothing of it.
+ *   rows       a call's rows are those of the kept forms: distinct ref_ids, strictly ascending lists, checked on the host
+ *              before anything runs (LZANI_ERR_ARG).  Entry e of the CSR is the directed pair (ref a = its row's reference,
+ *              query b); a region belongs to the entry its `pair` names
+ *   sums       mat(e) = the sum of num_matches over the entry's regions, lit(e) = the sum of num_mismatches: 32-bit integer
+ *              sums, as the reference makes them
+ *   the rule   len = aln_len[b] (aln_len == NULL: the genome set's own lengths); every division an IEEE double division:
+ *                gani = (double)mat / len;  ani = mat + lit != 0 ? (double)mat / (mat + lit) : 0;  qcov = (double)(mat + lit) / len
+ *              with a filter f the entry is dropped iff gani < f.min_gani || ani < f.min_ani || qcov < f.min_qcov: a NaN or inf
+ *              value is below nothing, a value equal to its minimum stays.  min_tani and min_rcov are not read (the reference
+ *              reads only the three).  f == NULL: no entry is dropped (the reference with no --out-filter).  A NaN in one of
+ *              the three minima: LZANI_ERR_ARG.  Entries without a region are neither kept nor dropped
+ *   result     the regions of the entries that stay, with pair = e: entries in ascending e; inside an entry the longer
+ *              seq_end - seq_start first, then the smaller seq_start; records equal in all three keep their input order
+ *              (only made-up regions can be: a pair's regions are disjoint in the query).  Rows passed in ascending id order
+ *              give the order of the reference's file
+ *   limits     more than 2^32 - 17 regions (what one sort takes), or 2^32 or more entries in a call: LZANI_ERR_ARG
+ *   capacity   the run writes its regions into a buffer whose size the library chooses: what lzani_set_region_capacity
+ *              forced, else the smallest of (a) sum over the entries of floor((L_b + max_dist_in_ref) / max(min_region_len, 1))
+ *              -- a region is at least min_region_len long in the query and a pair's regions are disjoint there --, (b) what
+ *              one eighth of the free device memory holds at the call, (c) the sort's limit; and at least 1,024.  A run that
+ *              finds more regions than the capacity is repeated once with the exact count: info.runs is 1 or 2
+ * The result -- 32 B a region -- stays in the context until the next regions call or lzani_set_genomes.  LZANI_ERR_NOMEM from
+ * lzani_run_rows_aligned or lzani_debug_order_regions leaves the context with neither a kept result nor a regions result and
+ * otherwise unchanged (genome set, prefilter result and cluster state stay); the same call may be made again. */
+typedef struct lzani_regions_info {
+    uint64_t entries, found, kept;                  /* directed entries of the call; regions the run found; regions that stay */
+    uint64_t entries_with_regions, entries_dropped; /* entries that own a region; those of them the rule drops               */
+    uint64_t capacity, runs;                        /* regions the raw buffer held; runs made (1 or 2; 0: no run, made-up regions) */
+    uint64_t sort_passes;                           /* radix passes of the three sorts, summed                                */
+    uint64_t workspace_bytes;                       /* the stage's device memory beside the raw buffer and the result         */
+    uint64_t bytes_to_host;                         /* copied out by the fetches so far                                       */
+    double   sums_ms, sort_ms, write_ms;            /* HIP events on the context's stream: sums and rule; keys and sorts; gather */
+} lzani_regions_info;
+/* The first capacity of the later lzani_run_rows_aligned calls, in regions; 0 (the default): automatic. */
+int lzani_set_region_capacity(lzani_ctx *ctx, uint64_t regions);
+/* One run with the region sink in device memory, then the stages.  out (host, may be NULL): the results of lzani_run_rows.
+ * kept_filter (may be NULL): the output filter's stage over the same result buffer; its records and info are exactly those
+ * of lzani_run_rows_kept with report_len (NULL: the genome set's own lengths), read with lzani_kept_fetch; NULL: the call
+ * leaves no kept result.  aln_filter (may be NULL), aln_len: the region stage as above.  *n_kept, *n_regions (may be NULL):
+ * the kept pairs and the regions that stay.  Out-of-core sets too. */
+int lzani_run_rows_aligned(lzani_ctx *ctx, uint32_t n_rows, const uint32_t *ref_ids, const uint64_t *row_off, const uint32_t *query_ids,
+                           lzani_result *out, const lzani_out_filter *kept_filter, const uint32_t *report_len,
+                           const lzani_out_filter *aln_filter, const uint32_t *aln_len, uint64_t *n_kept, uint64_t *n_regions);
+/* Records first .. first + count - 1 of the regions result.  A range past the end: LZANI_ERR_ARG; no result: LZANI_ERR_STATE. */
+int lzani_regions_fetch(lzani_ctx *ctx, uint64_t first, uint64_t count, lzani_region *out);
+/* LZANI_ERR_STATE without a regions result. */
+int lzani_get_regions_info(const lzani_ctx *ctx, lzani_regions_info *info);
+/* Test hook: the stage alone on `count` made-up regions of n genomes in host memory (uploaded here).  Needs no genome set;
+ * aln_len must not be NULL.  A region with pair at or beyond the entries, with seq_end <= seq_start or with a negative
+ * field: LZANI_ERR_ARG, on the host.  A kept result there is stays, except where the call ends in LZANI_ERR_NOMEM. */
+int lzani_debug_order_regions(lzani_ctx *ctx, uint32_t n, const uint32_t *aln_len, uint32_t n_rows, const uint32_t *ref_ids,
+                              const uint64_t *row_off, const uint32_t *query_ids, const lzani_region *regions, uint64_t count,
+                              const lzani_out_filter *f, uint64_t *n_regions);
+/* The same statement as a pure host function (no GPU; a stable sort): the regions that stay to out (may be NULL: counted
+ * only), their number to *n_out; info (may be NULL): entries, found, kept, entries_with_regions and entries_dropped, the
+ * other fields 0.  The checks of lzani_debug_order_regions: LZANI_ERR_ARG. */
+int lzani_regions_host(uint32_t n, const uint32_t *aln_len, uint32_t n_rows, const uint32_t *ref_ids, const uint64_t *row_off,
+                       const uint32_t *query_ids, const lzani_region *regions, uint64_t count, const lzani_out_filter *f,
+                       lzani_region *out, uint64_t *n_out, lzani_regions_info *info);
 
 /* ---- Clustering the kept pairs on the device: single linkage, greedy, set cover and complete linkage ---------------
  * The kept records of the output filter are the edge list of the similarity graph; this stage clusters it where it lies.

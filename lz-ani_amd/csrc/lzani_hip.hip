@@ -8,6 +8,7 @@
 //   lzani_kernels_prefilter.h   k_pf_*   the k-mer prefilter: shared k-mer counts of all genome pairs
 //   lzani_kernels_outfilter.h   k_of_kept   the output filter: the pairs of a finished result buffer of which a TSV line passes
 //   lzani_kernels_cluster.h     k_cl_*   the cluster stage: single linkage, greedy clustering, greedy set cover and complete linkage of the kept pairs
+//   lzani_kernels_regions.h     k_rg_*   the alignment-region stage: the regions of the entries that pass the alignment's rule, in file order
 //   lzani_block.h           block_sum, block_rank, block_scan_step   what a block's threads work out together (index, prefilter)
 // The algorithm itself (PairMachine and its building blocks, shared with the host model of the tests) is
 // lzani_core.h; sizes and the parameter envelope are lzani_layout.h.  The pure decisions are free of HIP: those of a run
@@ -15,13 +16,14 @@
 // table of the instantiations, choose_pair_kernel) in lzani_pair_dispatch.h, those of a genome set (the set-level
 // switches, the form of the index, footprints, the block plan, residency, the slot count of the slabs) in lzani_set_plan.h,
 // those of an out-of-core run (the order of its tiles, their local tables, the tables of an upload) in lzani_tile_plan.h.
-// Device memory and events have one owner each, lzani_devmem.h.  Six layers of the host side are files of their own,
+// Device memory and events have one owner each, lzani_devmem.h.  Seven layers of the host side are files of their own,
 // included at fixed places below:
 //   lzani_index.h       the index stage: genome upload, slabs, k-mer words, join lists, the index build, its test hooks
 //   lzani_dense.h       the dense-row stage of a run: candidate bitmaps from the presence matrix, the split of few, long pairs
 //   lzani_ooc.h         genome sets larger than the device: block plan, block uploads, the tiled run
 //   lzani_prefilter.h   the k-mer prefilter's host stage: slice and pass plans, the pass / tile driver, its entry points
 //   lzani_kept.h        the output filter's host stage: a run whose results stay on the device, only the kept pairs come back
+//   lzani_regions.h     the alignment-region stage's host side: a run with the region sink on the device, the stage, the fetch in pieces
 //   lzani_cluster.h     the cluster stage's host side: the edges of the kept results, the run, its entry points
 //   lzani_multi.h       the multi-GPU layer
 #include <hip/hip_runtime.h>
@@ -70,6 +72,7 @@ int lzani_sort_keys(const unsigned long long* in, unsigned long long* out, size_
 #include "lzani_kernels_prefilter.h"
 #include "lzani_kernels_outfilter.h"
 #include "lzani_kernels_cluster.h"
+#include "lzani_kernels_regions.h"
 #include "lzani_rtc.h"
 #include "lzani_devmem.h"
 #include "lzani_run_plan.h"
@@ -261,6 +264,14 @@ struct Kept {
     DevMem<u32> rec;                      // 9 words a kept pair (lzani_kept_pair)
 };
 
+// The ordered regions of the alignment output (lzani_regions.h): a regions call -> the next one, or lzani_set_genomes.  (The
+// name Regions is the pair machine's, lzani_core.h.)
+struct AlignedRegions {
+    bool done = false;
+    lzani_regions_info info{};
+    DevMem<lzani_region> rec;             // info.kept records, in file order
+};
+
 // The cluster stage's state (lzani_cluster.h): lzani_cluster_begin -> the next one, or lzani_set_genomes.
 struct Cluster {
     bool begun = false, ran = false;      // ran: rep_of and cluster_of are those of the edges as they are
@@ -309,12 +320,14 @@ struct lzani_ctx {
     double leiden_resolution = CL_LEIDEN_RESOLUTION;      // lzani_set_cluster_leiden: the parameters of the later Leiden runs
     int leiden_iterations = CL_LEIDEN_ITERATIONS;
     int pf_counting = LZANI_PF_COUNTING_AUTO;     // lzani_set_prefilter_counting: the accumulator of the later prefilter calls
+    u64 region_cap = 0;           // lzani_set_region_capacity: the first capacity of the later lzani_run_rows_aligned calls; 0 = automatic
 
     GenomeSet gs;
     IndexSlabs sl;
     CandScratch cs;
     Prefilter pf;
     Kept kept;
+    AlignedRegions rg;
     Cluster cl;
     ClusterStore cls;
     // the last run
@@ -876,6 +889,7 @@ int run_rows_any(lzani_ctx* c, u32 n_rows, const u32* ref_ids, const u64* row_of
 #include "lzani_prefilter.h"
 #include "lzani_prefilter_limit.h"
 #include "lzani_kept.h"
+#include "lzani_regions.h"
 #include "lzani_cluster.h"
 
 extern "C" {
@@ -938,6 +952,7 @@ int lzani_set_genomes(lzani_ctx* c, uint32_t n, const uint8_t* const* codes, con
     c->cs = CandScratch{};
     c->pf = Prefilter{};
     c->kept = Kept{};
+    c->rg = AlignedRegions{};
     c->cl = Cluster{};
     c->cls = ClusterStore{};
     c->res = Residency{};

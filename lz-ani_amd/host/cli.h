@@ -435,12 +435,20 @@ static lzani_out_filter out_filter_minima()
 {
     return lzani_out_filter{P.flt_vals[(int)Comp::tani], P.flt_vals[(int)Comp::gani], P.flt_vals[(int)Comp::ani], P.flt_vals[(int)Comp::qcov], P.flt_vals[(int)Comp::rcov]};
 }
-// Whether the device applies it: a two-TSV output, no --out-alignment (its own cut stays on the host), no --results-in /
-// --results-out (they carry every pair), numbers for minima (a NaN drops nothing on the host and is refused by the
-// engine), and LZANI_OUT_FILTER=host not set.
+// Whether the device applies it: a two-TSV output, no --results-in / --results-out (they carry every pair), numbers for
+// minima (a NaN drops nothing on the host and is refused by the engine), and LZANI_OUT_FILTER=host not set.  With
+// --out-alignment the caller asks out_aln_on_device() as well: the kept call is then the aligned call.
 static bool out_filter_on_device()
 {
     const char* e = getenv("LZANI_OUT_FILTER");
-    return P.flt_mask != 0 && !P.single_txt && P.out_aln.empty() && P.results_in.empty() && P.results_out.empty()
+    return P.flt_mask != 0 && !P.single_txt && P.results_in.empty() && P.results_out.empty()
            && !lzani::out_filter_has_nan(out_filter_minima()) && !(e && e == "host"s);
+}
+// Whether --out-alignment goes through the device's region stage (lzani_run_rows_aligned), as far as the command line says:
+// no --results-in / --results-out, numbers for minima, and LZANI_OUT_ALN=host not set.  The caller adds what it alone knows:
+// one device, a library with the symbols, filter lists that ascend.
+static bool out_aln_on_device()
+{
+    const char* e = getenv("LZANI_OUT_ALN");
+    return !P.out_aln.empty() && P.results_in.empty() && P.results_out.empty() && !lzani::out_filter_has_nan(out_filter_minima()) && !(e && e == "host"s);
 }

@@ -14,7 +14,8 @@
 
 // Every symbol the binary calls, named once (without its lzani_ prefix).  Required: a library without one is refused.
 // Kept (the output filter on the device) and cluster (the cluster stage): bound where the library has them; an older one
-// keeps the filter, or the clustering, on the host.  Cover and link (what -V 2 says of a set-cover or a
+// keeps the filter, or the clustering, on the host.  Aligned (the alignment-region stage: --out-alignment on the device): the
+// same; an older library keeps the regions' order on the host.  Cover and link (what -V 2 says of a set-cover or a
 // complete-linkage run): read where they are there.  Leiden (its parameters and what -V 2 says of a run): a library without
 // them leaves --cluster leiden-cpm to the host.  Limit (--flt-kmers-max-seqs): asked for only where the flag is given, and
 // a library without them is then refused with the name of the symbol it lacks.  Levels (--cluster-cut, --cluster-level:
@@ -26,6 +27,7 @@
     X(prefilter) X(prefilter_fetch) X(get_prefilter_info) X(prefilter_codes) X(get_prefilter_stream_info) X(get_prefilter_pass_info) \
     X(prefilter_cross) X(prefilter_codes_cross) X(set_prefilter_counting) X(get_prefilter_sparse_info)
 #define LZANI_ENGINE_KEPT(X) X(group_run_rows_kept) X(group_kept_fetch) X(group_get_kept_info)
+#define LZANI_ENGINE_ALIGNED(X) X(run_rows_aligned) X(regions_fetch) X(get_regions_info) X(regions_host) X(kept_fetch) X(get_kept_info)
 #define LZANI_ENGINE_CLUSTER(X) X(group_cluster_begin) X(group_cluster_add_kept) X(group_cluster_run) X(group_cluster_fetch) X(group_get_cluster_info)
 #define LZANI_ENGINE_COVER(X) X(group_get_cluster_cover_info) X(group_get_cluster_link_info)
 #define LZANI_ENGINE_LEIDEN(X) X(group_set_cluster_leiden) X(group_get_cluster_leiden_info)
@@ -36,10 +38,11 @@
 struct Engine {
     void* so = nullptr;
 #define X(f) decltype(&lzani_##f) f = nullptr;             // a signature that drifts from the header does not compile
-    LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X) LZANI_ENGINE_LEVELS(X)
+    LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_ALIGNED(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X) LZANI_ENGINE_LEVELS(X)
 #undef X
 #define X(f) && f
     bool has_kept() const { return true LZANI_ENGINE_KEPT(X); }
+    bool has_aligned() const { return true LZANI_ENGINE_ALIGNED(X); }
     bool has_cluster() const { return true LZANI_ENGINE_CLUSTER(X); }
     bool has_leiden() const { return true LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_LEIDEN(X); }
 #undef X
@@ -70,7 +73,7 @@ struct Engine {
         for (auto& c : cand) if ((so = dlopen(c.c_str(), RTLD_NOW | RTLD_LOCAL))) break;
         if (!so) { std::cerr << "Cannot load liblzani_hip.so (the HIP engine; there is no CPU fallback): " << dlerror() << std::endl; return false; }
 #define X(f) f = reinterpret_cast<decltype(f)>(dlsym(so, "lzani_" #f));
-        LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X) LZANI_ENGINE_LEVELS(X)
+        LZANI_ENGINE_REQUIRED(X) LZANI_ENGINE_KEPT(X) LZANI_ENGINE_ALIGNED(X) LZANI_ENGINE_CLUSTER(X) LZANI_ENGINE_COVER(X) LZANI_ENGINE_LEIDEN(X) LZANI_ENGINE_LIMIT(X) LZANI_ENGINE_LEVELS(X)
 #undef X
 #define X(f) if (!f) { std::cerr << "Missing symbol lzani_" #f << std::endl; return false; }
         LZANI_ENGINE_REQUIRED(X)

@@ -13,6 +13,9 @@
 // and the test seams --results-out / --results-in (raw int triples of the matching stage).
 // --out-filter on a two-TSV output is applied on the device (lzani_group_run_rows_kept): only the pairs of which a line
 // passes come back, and the table of all pairs is never made; LZANI_OUT_FILTER=host keeps the filter on the host.
+// --out-alignment on one device goes through the region stage (lzani_run_rows_aligned): the regions of the pairs that pass the
+// alignment's rule come back in the file's order and are written as they are fetched; with an --out-filter and no --cluster
+// the same call is the kept call.  LZANI_OUT_ALN=host, --gpus above 1 and an older library keep the regions' order on the host.
 // --cluster <single|greedy-first|greedy-best|set-cover|complete-linkage|leiden-cpm> clusters the pairs the output filter keeps (include/lzani.h,
 // "clustering the kept pairs") and writes one line per genome to --cluster-out: on the device where the filter is applied there
 // (lzani_group_cluster_*), else by the sequential statement of lzani_cluster_plan.h over the emitter's own lines.
@@ -144,7 +147,12 @@ static bool run_all2all()
         // --out-filter on the device where it applies to the TSV, the library has the stage and the filter's lists are sets
         bool leiden = false;                                // a level is one of leiden-cpm
         for (const auto& lv : P.levels) leiden = leiden || lv.algo == LZANI_CLUSTER_LEIDEN;
-        const bool kept = out_filter_on_device() && E.has_kept() && lists_ascend(flt) && (!P.cluster || (leiden ? E.has_leiden() : E.has_cluster()));
+        const bool ascend = lists_ascend(flt);
+        // --out-alignment through the device's region stage: one device, a library with the stage, lists that are sets
+        const bool aln_dev = out_aln_on_device() && E.has_aligned() && ascend && device_list(g).size() == 1;
+        // (with --out-alignment the kept call is the aligned call; with --cluster as well, the filter and the clusters stay on the host)
+        const bool kept = out_filter_on_device() && E.has_kept() && ascend && (!P.cluster || (leiden ? E.has_leiden() : E.has_cluster()))
+                          && (P.out_aln.empty() || (aln_dev && !P.cluster));
         if (kept && P.cluster && P.levels_on())
             if (const char* sym = E.missing_levels()) { cerr << "Missing symbol " << sym << " (--cluster-cut and --cluster-level need it)" << endl; return false; }
         clustered = kept && P.cluster;
@@ -153,8 +161,8 @@ static bool run_all2all()
             if (!do_matching_tiled(E, g, results, ep, tile, kept)) return false;
         } else {
             vector<AlnRegion> aln;
-            if (!do_matching(E, g, flt, results, ep, kept, P.out_aln.empty() ? nullptr : &aln)) return false;
-            if (!P.out_aln.empty() && !store_alignment(g, aln)) return false;
+            if (!do_matching(E, g, flt, results, ep, kept, P.out_aln.empty() ? nullptr : &aln, aln_dev)) return false;
+            if (!P.out_aln.empty() && !aln_dev && !store_alignment(E, g, aln)) return false;
             stored = kept;                                  // the kept form writes its records as it fetches them
         }
     }

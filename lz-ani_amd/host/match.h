@@ -11,6 +11,7 @@
 #include <future>
 #include <thread>
 
+#include "../csrc/lzani_aln_rule.h"
 #include "../csrc/lzani_cluster_plan.h"
 #include "cli.h"
 #include "engine.h"
@@ -180,51 +181,81 @@ static bool kmer_filter(const Engine& E, const vector<Genome>& g, Filter& flt, u
     return true;
 }
 
-// store_alignment (lz_matcher.cpp:102-169): one BLAST-tab-like row per region; rows of one pair in
-// calc_regions order (length desc, seq_start asc), pairs in (reference, query) order.
-static bool store_alignment(const vector<Genome>& g, vector<AlnRegion>& regs)
-{
-    ofstream o(P.out_aln, ios::binary);
-    if (!o.is_open()) { cerr << "Cannot open output file: " << P.out_aln << endl; return false; }
-    o << "query\treference\tpident\talnlen\tqstart\tqend\trstart\trend\tnt_match\tnt_mismatch\n";
-    sort(regs.begin(), regs.end(), [](const AlnRegion& a, const AlnRegion& b) {
-        if (a.ref != b.ref) return a.ref < b.ref;
-        if (a.qry != b.qry) return a.qry < b.qry;
-        int la = a.r.seq_end - a.r.seq_start, lb = b.r.seq_end - b.r.seq_start;
-        if (la != lb) return la > lb;
-        return a.r.seq_start < b.r.seq_start;
-    });
-    const lzani_out_filter f = out_filter_minima();
+// The alignment file (store_alignment, lz_matcher.cpp:102-169): one BLAST-tab-like row per region.  Both paths write
+// through it, region by region in the file's order: pairs in (reference, query) order, the rows of one pair in
+// calc_regions order (length desc, seq_start asc).
+struct AlnWriter {
+    ofstream o;
     string line;
     char num[64];
-    for (size_t k = 0; k < regs.size();) {
-        size_t k1 = k;
-        long mat = 0, lit = 0;
-        while (k1 < regs.size() && regs[k1].ref == regs[k].ref && regs[k1].qry == regs[k].qry) { mat += regs[k1].r.num_matches; lit += regs[k1].r.num_mismatches; ++k1; }
-        const uint32_t r = regs[k].ref, q = regs[k].qry;
-        const int len1 = (int)g[r].codes.size(), len2 = (int)g[q].codes.size();
-        bool keep = true;
-        if (P.flt_mask != 0) {                                  // the part of --out-filter that applies here (124-137): a rule of its own, over the region sums
-            double gani = (double)mat / len2, ani = mat + lit != 0 ? (double)mat / (mat + lit) : 0, qcov = (double)(mat + lit) / len2;
-            keep = !(gani < f.min_gani) && !(ani < f.min_ani) && !(qcov < f.min_qcov);
-        }
-        const int rc_corr = 2 * len1 + 2 * P.lz.max_dist_in_ref + 1;
-        for (; k < k1; ++k) {
-            if (!keep) continue;
-            const lzani_region& x = regs[k].r;
-            const int length = x.seq_end - x.seq_start;
-            line.clear();
-            line += g[q].name; line += '\t'; line += g[r].name; line += '\t';
-            line.append(num, real_to_chars(100.0 * x.num_matches / length, num, 6)); line += '\t';
-            auto put = [&](long v, char sep) { line += to_string(v); line += sep; };
-            put(length, '\t'); put(1 + x.seq_start, '\t'); put(x.seq_end, '\t');
-            if (x.ref_start < len1) { put(1 + x.ref_start, '\t'); put(x.ref_end, '\t'); }
-            else { put(rc_corr - (1 + x.ref_start), '\t'); put(rc_corr - x.ref_end, '\t'); }
-            put(x.num_matches, '\t'); put(x.num_mismatches, '\n');
-            o.write(line.data(), (streamsize)line.size());
-        }
+    bool open()
+    {
+        o.open(P.out_aln, ios::binary);
+        if (!o.is_open()) { cerr << "Cannot open output file: " << P.out_aln << endl; return false; }
+        o << "query\treference\tpident\talnlen\tqstart\tqend\trstart\trend\tnt_match\tnt_mismatch\n";
+        return true;
     }
-    return true;
+    void put(const vector<Genome>& g, uint32_t r, uint32_t q, const lzani_region& x)
+    {
+        const int len1 = (int)g[r].codes.size(), rc_corr = 2 * len1 + 2 * P.lz.max_dist_in_ref + 1;
+        const int length = x.seq_end - x.seq_start;
+        line.clear();
+        line += g[q].name; line += '\t'; line += g[r].name; line += '\t';
+        line.append(num, real_to_chars(100.0 * x.num_matches / length, num, 6)); line += '\t';
+        auto field = [&](long v, char sep) { line += to_string(v); line += sep; };
+        field(length, '\t'); field(1 + x.seq_start, '\t'); field(x.seq_end, '\t');
+        if (x.ref_start < len1) { field(1 + x.ref_start, '\t'); field(x.ref_end, '\t'); }
+        else { field(rc_corr - (1 + x.ref_start), '\t'); field(rc_corr - x.ref_end, '\t'); }
+        field(x.num_matches, '\t'); field(x.num_mismatches, '\n');
+        o.write(line.data(), (streamsize)line.size());
+    }
+    bool close() { o.close(); return !o.fail(); }
+};
+
+// The host path of --out-alignment: the regions of every shard, as match_regions left them, through the library's host
+// statement of the region stage (lzani_regions_host: the rule over the region sums -- the part of --out-filter that applies
+// here -- and the file's order).  The call it is given lists the pairs that own a region, in (reference, query) order.  A
+// library without the symbol: lzani::aln_host_order (lzani_aln_rule.h), the header function that lzani_regions_host itself calls.
+static bool store_alignment(const Engine& E, const vector<Genome>& g, vector<AlnRegion>& regs)
+{
+    AlnWriter W;
+    if (!W.open()) return false;
+    const uint32_t n = (uint32_t)g.size();
+    vector<uint64_t> keys(regs.size());
+    for (size_t k = 0; k < regs.size(); ++k) keys[k] = (uint64_t)regs[k].ref << 32 | regs[k].qry;
+    sort(keys.begin(), keys.end());
+    keys.erase(unique(keys.begin(), keys.end()), keys.end());
+    vector<uint32_t> ref_ids, query_ids(keys.size()), len(n);
+    vector<uint64_t> row_off(1, 0);
+    for (size_t e = 0; e < keys.size(); ++e) {
+        if (e == 0 || keys[e] >> 32 != keys[e - 1] >> 32) { if (e) row_off.push_back(e); ref_ids.push_back((uint32_t)(keys[e] >> 32)); }
+        query_ids[e] = (uint32_t)keys[e];
+    }
+    if (!keys.empty()) row_off.push_back(keys.size());
+    for (uint32_t i = 0; i < n; ++i) len[i] = (uint32_t)g[i].codes.size();
+    vector<lzani_region> raw(regs.size()), out(regs.size());
+    for (size_t k = 0; k < regs.size(); ++k) {
+        raw[k] = regs[k].r;
+        raw[k].pair = (uint64_t)(lower_bound(keys.begin(), keys.end(), (uint64_t)regs[k].ref << 32 | regs[k].qry) - keys.begin());
+    }
+    // the part of --out-filter that applies here; a NaN minimum drops nothing and the other minima apply (lzani_regions_host
+    // refuses a NaN: -inf says the same)
+    lzani_out_filter f = out_filter_minima();
+    for (double* m : {&f.min_gani, &f.min_ani, &f.min_qcov}) if (*m != *m) *m = -numeric_limits<double>::infinity();
+    const lzani_out_filter* rule = P.flt_mask != 0 ? &f : nullptr;
+    uint64_t n_out = 0;
+    if (E.regions_host && n) {
+        if (E.regions_host(n, len.data(), (uint32_t)ref_ids.size(), ref_ids.data(), row_off.data(), query_ids.data(), raw.data(), raw.size(), rule, out.data(), &n_out,
+                           nullptr) != LZANI_OK) { cerr << "Ordering the alignment regions failed" << endl; return false; }
+    } else {                                                    // an older library: the statement itself, the header function that call is made of
+        vector<uint64_t> order;
+        lzani::aln_host_counts cnt;
+        lzani::aln_host_order((uint32_t)ref_ids.size(), ref_ids.data(), row_off.data(), query_ids.data(), len.data(), raw.data(), raw.size(), rule, order, cnt);
+        for (uint64_t i : order) out[n_out++] = raw[i];
+    }
+    if (P.verbosity >= 2) cerr << "alignment regions on the host: " << n_out << " of " << raw.size() << " regions stay\n";
+    for (uint64_t k = 0; k < n_out; ++k) W.put(g, (uint32_t)(keys[out[k].pair] >> 32), (uint32_t)keys[out[k].pair], out[k]);
+    return W.close();
 }
 
 // --cluster-out: one line per genome in the order of the ids file, its id and its cluster number or its representative's id.
@@ -420,6 +451,75 @@ static bool match_regions(const Engine& E, const vector<Genome>& g, const vector
     return true;
 }
 
+// -V 2: the one line of the device's region stage
+static void print_regions(const lzani_regions_info& r)
+{
+    cerr << "alignment regions on the device: " << r.kept << " of " << r.found << " regions stay, " << r.entries_dropped << " of " << r.entries_with_regions
+         << " pairs dropped, capacity " << r.capacity << ", " << r.runs << " run(s), " << r.sort_passes << " sort passes, sums " << r.sums_ms << " ms, sorts "
+         << r.sort_ms << " ms, gather " << r.write_ms << " ms, workspace " << r.workspace_bytes << " bytes\n";
+}
+
+// --out-alignment on one device (lzani_run_rows_aligned): one run leaves the results -- in T, or with `kept` as the kept
+// records of the output filter, written here as do_matching writes them -- and the regions of the pairs that pass the
+// alignment's rule, in the file's order; the alignment file is written while they are fetched, in pieces of a million (32 MB).
+static bool match_aligned(const Engine& E, const vector<Genome>& g, const vector<uint32_t>& ref_ids, PairTable& T, const EmitParams& ep, bool kept)
+{
+    const uint32_t n = (uint32_t)g.size();
+    vector<const uint8_t*> ptr; vector<uint32_t> len;
+    genome_views(g, ptr, len);
+    const int dev = device_list(g)[0];
+    Context ctx(E);
+    const auto t_a = chrono::steady_clock::now();
+    int rc = E.create(&P.lz, dev, &ctx.p);
+    if (rc != LZANI_OK) return matching_failed("lzani_create failed with code " + to_string(rc) + (rc == LZANI_ERR_PARAMS ? " (LZ parameters outside the supported envelope)" : ""));
+    const auto t_b = chrono::steady_clock::now();
+    E.set_genome_memory(ctx, P.gpu_mem);
+    if (E.set_genomes(ctx, n, ptr.data(), len.data()) != LZANI_OK) return matching_failed(E.last_error(ctx));
+    const auto t_c = chrono::steady_clock::now();
+    static const uint32_t no_ids[1] = {0};
+    const uint32_t* q = T.dense ? nullptr : T.query_ids.empty() ? no_ids : T.query_ids.data();
+    const vector<uint32_t> rlen = report_lengths(g, ep.mrd);
+    const lzani_out_filter f = out_filter_minima();
+    uint64_t n_kept = 0, n_regs = 0;
+    rc = E.run_rows_aligned(ctx, n, ref_ids.data(), T.row_off.data(), q, kept ? nullptr : T.res.data(), kept ? &f : nullptr, rlen.data(),
+                            P.flt_mask != 0 ? &f : nullptr, nullptr, &n_kept, &n_regs);
+    if (rc != LZANI_OK) return matching_failed(E.last_error(ctx));
+    if (P.verbosity >= 2) {
+        cerr << "engine: create " << chrono::duration<double>(t_b - t_a).count() << " s, genomes to the device " << chrono::duration<double>(t_c - t_b).count()
+             << " s, matching " << chrono::duration<double>(chrono::steady_clock::now() - t_c).count() << " s\n";
+        lzani_timing t; lzani_residency_info ri; lzani_kept_info ki; lzani_regions_info gi;
+        if (E.get_timing(ctx, &t) == LZANI_OK) print_gpu_timing(dev, t, false, nullptr);
+        if (E.get_residency(ctx, &ri) == LZANI_OK) print_residency(dev, ri, ri.tiles, ri.block_uploads, ri.upload_ms);
+        if (kept && E.get_kept_info(ctx, &ki) == LZANI_OK) print_kept(ki);
+        if (E.get_regions_info(ctx, &gi) == LZANI_OK) print_regions(gi);
+    }
+    if (kept) {
+        if (P.verbosity >= 1) cerr << "Storing results" << endl;
+        ResultWriter W;
+        if (!W.open(g, ep)) return false;
+        vector<lzani_kept_pair> rec;
+        for (uint64_t first = 0; first < n_kept; first += rec.size()) {
+            rec.resize((size_t)min<uint64_t>(n_kept - first, 1u << 20));
+            if (E.kept_fetch(ctx, first, rec.size(), rec.data()) != LZANI_OK) return matching_failed(E.last_error(ctx));
+            W.emit_kept(g, rec.data(), rec.size());
+        }
+        if (!W.close()) return false;
+    }
+    AlnWriter A;
+    if (!A.open()) return false;
+    vector<lzani_region> regs;
+    uint32_t row = 0;                                           // the regions come by ascending entry: the row only moves on
+    for (uint64_t first = 0; first < n_regs; first += regs.size()) {
+        regs.resize((size_t)min<uint64_t>(n_regs - first, 1u << 20));
+        if (E.regions_fetch(ctx, first, regs.size(), regs.data()) != LZANI_OK) return matching_failed(E.last_error(ctx));
+        for (const lzani_region& x : regs) {
+            while (x.pair >= T.row_off[row + 1]) ++row;
+            A.put(g, ref_ids[row], T.id_at(row, x.pair - T.row_off[row]), x);
+        }
+    }
+    return A.close();
+}
+
 // do_matching (lz_matcher.cpp:172-277).  The reference's workers pull reference rows off an atomic counter and
 // run one CParser each; here the whole row table goes to the engine in one call: lzani_group_run_rows deals
 // the rows over the GPUs of the group (cyclic for dense rows, LPT for filtered ones), runs them, gathers the
@@ -427,8 +527,9 @@ static bool match_regions(const Engine& E, const vector<Genome>& g, const vector
 // kept: the output filter on the device -- the same rows (the filter's lists sorted by the caller, lists_ascend) through
 // lzani_group_run_rows_kept with the printed lengths; T keeps its layout and no results, and the kept records -- in the
 // order of the output file -- are written here, in pieces of a million (36 MB) as they are fetched.
-// aln (--out-alignment): the regions of every pair as well, by match_regions.
-static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, PairTable& T, const EmitParams& ep, bool kept, vector<AlnRegion>* aln)
+// aln (--out-alignment): the regions of every pair as well, by match_regions (the host path: they come back unordered, for
+// store_alignment); aln_dev: by match_aligned instead, which writes the alignment file, and with `kept` the result files, itself.
+static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, PairTable& T, const EmitParams& ep, bool kept, vector<AlnRegion>* aln, bool aln_dev)
 {
     const uint32_t n = (uint32_t)g.size();
     if (P.verbosity >= 1) cerr << "All2all sparse" << endl;
@@ -436,6 +537,7 @@ static bool do_matching(const Engine& E, const vector<Genome>& g, Filter& flt, P
     else { T.init_sparse(flt.rows, !kept); vector<vector<uint32_t>>().swap(flt.rows); }   // the reference clears filter rows as it goes (266-267)
     vector<uint32_t> ref_ids(n);
     for (uint32_t i = 0; i < n; ++i) ref_ids[i] = i;
+    if (aln_dev) return match_aligned(E, g, ref_ids, T, ep, kept);
     if (aln) return match_regions(E, g, ref_ids, T, *aln);
 
     // (kept: lists that are all empty are still lists, never null; the table form has always passed them as they are, and the

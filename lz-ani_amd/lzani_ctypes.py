@@ -53,7 +53,9 @@ EXPORTS = ("lzani_default_params", "lzani_create", "lzani_destroy", "lzani_last_
            "lzani_cluster_cut_lines", "lzani_cluster_store_begin", "lzani_cluster_store_add_kept", "lzani_cluster_level",
            "lzani_get_cluster_store_info", "lzani_get_cluster_level_info", "lzani_debug_cluster_store_add", "lzani_debug_cluster_edges",
            "lzani_group_cluster_store_begin", "lzani_group_cluster_store_add_kept", "lzani_group_cluster_level",
-           "lzani_group_get_cluster_store_info", "lzani_group_get_cluster_level_info")
+           "lzani_group_get_cluster_store_info", "lzani_group_get_cluster_level_info",
+           "lzani_set_region_capacity", "lzani_run_rows_aligned", "lzani_regions_fetch", "lzani_get_regions_info",
+           "lzani_debug_order_regions", "lzani_regions_host")
 
 
 class LzaniError(RuntimeError):
@@ -179,6 +181,49 @@ def out_filter_lines(flt, x, y, len_a, len_b):
 
 def _kept_info(o):
     return {k: getattr(o, k) for k, _ in KeptInfo._fields_}
+
+
+class RegionsInfo(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("found", C.c_uint64), ("kept", C.c_uint64), ("entries_with_regions", C.c_uint64),
+                ("entries_dropped", C.c_uint64), ("capacity", C.c_uint64), ("runs", C.c_uint64), ("sort_passes", C.c_uint64),
+                ("workspace_bytes", C.c_uint64), ("bytes_to_host", C.c_uint64), ("sums_ms", C.c_double), ("sort_ms", C.c_double),
+                ("write_ms", C.c_double)]
+
+
+# lzani_region as a numpy record
+REGION_DTYPE = np.dtype([("pair", np.uint64), ("ref_start", np.int32), ("ref_end", np.int32), ("seq_start", np.int32),
+                         ("seq_end", np.int32), ("num_matches", np.int32), ("num_mismatches", np.int32)])
+assert REGION_DTYPE.itemsize == 32
+
+
+def _regions_info(o):
+    return {k: getattr(o, k) for k, _ in RegionsInfo._fields_}
+
+
+def _filter_or_null(flt):
+    """None: a NULL filter; an OutFilter or a dict by column name: that filter."""
+    if flt is None:
+        return None
+    return flt if isinstance(flt, OutFilter) else out_filter(flt)
+
+
+def regions_host(n, aln_len, ref_ids, row_off, query_ids, regions, flt=None):
+    """lzani_regions_host (no GPU needed): (the regions of the entries that stay, in file order, REGION_DTYPE; info dict) of
+    made-up REGION_DTYPE regions of n genomes under the alignment filter `flt` (None: no entry is dropped)."""
+    lib = load_library()
+    ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+    row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+    q = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint32)
+    al = np.ascontiguousarray(aln_len, dtype=np.uint32)
+    r = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+    f = _filter_or_null(flt)
+    out = np.zeros(len(r), dtype=REGION_DTYPE)
+    cnt, info = C.c_uint64(0), RegionsInfo()
+    rc = lib.lzani_regions_host(int(n), _ptr(al), len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q), _ptr(r) if len(r) else None, C.c_uint64(len(r)),
+                                C.byref(f) if f is not None else None, _ptr(out) if len(r) else None, C.byref(cnt), C.byref(info))
+    if rc != 0:
+        raise LzaniError(f"lzani_regions_host: {ERRORS.get(rc, rc)}")
+    return out[:cnt.value].copy(), _regions_info(info)
 
 
 class ClusterInfo(C.Structure):
@@ -429,6 +474,12 @@ def load_library():
         lib.lzani_filter_results_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         lib.lzani_debug_filter_results.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         lib.lzani_get_kept_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_set_region_capacity.argtypes = [C.c_void_p, C.c_uint64]
+        lib.lzani_run_rows_aligned.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 10
+        lib.lzani_regions_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.lzani_get_regions_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lzani_debug_order_regions.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.lzani_regions_host.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 4
         lib.lzani_group_run_rows_kept.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         lib.lzani_group_kept_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         lib.lzani_group_get_kept_info.argtypes = [C.c_void_p, C.c_void_p]
@@ -1094,6 +1145,57 @@ class Engine(_ClusterCalls):
         o = KeptInfo()
         self._check(self.lib.lzani_get_kept_info(self.h, C.byref(o)), "lzani_get_kept_info")
         return _kept_info(o)
+
+    def set_region_capacity(self, regions):
+        """lzani_set_region_capacity: the first capacity of the later run_rows_aligned calls, in regions; 0 = automatic."""
+        self._check(self.lib.lzani_set_region_capacity(self.h, C.c_uint64(int(regions))), "lzani_set_region_capacity")
+
+    def run_rows_aligned(self, ref_ids, row_off, query_ids=None, kept_flt=None, report_len=None, aln_flt=None, aln_len=None, results=True):
+        """lzani_run_rows_aligned: one run with the region sink on the device, then the output filter's stage (kept_flt: an
+        OutFilter or a dict, None: none) and the region stage (aln_flt likewise, None: no entry is dropped).  Returns
+        (results int32[entries, 3] or None, the number of kept pairs, the number of regions that stay); kept_fetch() and
+        regions_fetch() read the two results."""
+        ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        q = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint32)
+        rl = None if report_len is None else np.ascontiguousarray(report_len, dtype=np.uint32)
+        al = None if aln_len is None else np.ascontiguousarray(aln_len, dtype=np.uint32)
+        kf, af = _filter_or_null(kept_flt), _filter_or_null(aln_flt)
+        out = np.zeros((int(row_off[-1]) if len(row_off) else 0, 3), dtype=np.int32) if results else None
+        nk, nr = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.lzani_run_rows_aligned(self.h, len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q), _ptr(out) if results and len(out) else None,
+                                                    C.byref(kf) if kf is not None else None, _ptr(rl), C.byref(af) if af is not None else None, _ptr(al),
+                                                    C.byref(nk), C.byref(nr)), "lzani_run_rows_aligned")
+        return out, int(nk.value), int(nr.value)
+
+    def order_regions(self, n, aln_len, ref_ids, row_off, query_ids, regions, flt=None, fetch=True):
+        """lzani_debug_order_regions: the region stage alone on made-up REGION_DTYPE regions of n genomes (uploaded here).
+        Returns the regions that stay, all fetched at once, or with fetch=False their number."""
+        ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        q = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint32)
+        al = np.ascontiguousarray(aln_len, dtype=np.uint32)
+        r = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+        f = _filter_or_null(flt)
+        cnt = C.c_uint64(0)
+        self._check(self.lib.lzani_debug_order_regions(self.h, int(n), _ptr(al), len(ref_ids), _ptr(ref_ids), _ptr(row_off), _ptr(q),
+                                                       _ptr(r) if len(r) else None, C.c_uint64(len(r)), C.byref(f) if f is not None else None,
+                                                       C.byref(cnt)), "lzani_debug_order_regions")
+        return self.regions_fetch(0, int(cnt.value)) if fetch else int(cnt.value)
+
+    def regions_fetch(self, first, count):
+        """lzani_regions_fetch: records first .. first + count - 1 of the regions result (REGION_DTYPE)."""
+        out = np.zeros(int(count), dtype=REGION_DTYPE)
+        self._check(self.lib.lzani_regions_fetch(self.h, C.c_uint64(int(first)), C.c_uint64(int(count)), _ptr(out) if count else None),
+                    "lzani_regions_fetch")
+        return out
+
+    def regions_info(self):
+        """lzani_get_regions_info: entries, found, kept, entries_with_regions, entries_dropped, capacity, runs, sort_passes,
+        workspace_bytes, bytes_to_host, sums_ms, sort_ms, write_ms."""
+        o = RegionsInfo()
+        self._check(self.lib.lzani_get_regions_info(self.h, C.byref(o)), "lzani_get_regions_info")
+        return _regions_info(o)
 
     def run_rows_device(self, ref_ids, row_off, query_ids, d_out_ptr):
         """Results stay on the GPU at raw device pointer d_out_ptr (3 int32 per pair)."""
